@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): frames/s of the kernel-update + mask/depth forward
 (`KernelUpdateIterHead.simple_test_mask_preds`) at 1024x2048, N=153, S=3.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs one process per GPU over RCCL: either under an outer launcher (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or, when no
@@ -1213,6 +1213,32 @@ def cfg4_main(args, dev, world, rank, backend, json_fd):
 HOST_THREADS = 16
 
 
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this much in all, .npy headers included
+DUMP_NAMES = ("obj", "cls", "mask", "mask_up", "depth_up")
+
+
+def dump_outputs(outs, out_dir, seed=0):
+    """--dump-outputs: what the timed step computed, as a caller receives it -- simple_test_mask_preds returns (obj, cls, mask,
+    mask_up), simple_test reads depth_up too -- written as DIR/<name>.npy in float32.  An array with more elements than its share of
+    DUMP_BYTES is written as a fixed sample: the elements at `share` flat indices drawn without replacement by numpy's
+    default_rng(seed), ascending, so a given shape yields the same indices in every run (1-D file).  Returns the dump's description."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BYTES - (1 << 16)) // 4 // len(DUMP_NAMES)
+    info = {"sample_seed": seed, "arrays": {}}
+    for name in DUMP_NAMES:
+        t = outs[name]
+        n = t.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng(seed).choice(n, share, replace=False))
+            a = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        else:
+            a = t
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+        info["arrays"][name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "elements_written": int(a.numel())}
+    return info
+
+
 def host_thread_policy():
     """Host thread policy of THIS process (the bench, not the library): torch's intra-op pool defaults to one thread per
     hardware thread -- 128 here on a 256-thread host -- whose workers keep spinning after every parallel region.  Inside a
@@ -1259,7 +1285,12 @@ def main():
     ap.add_argument("--no-kernel-head", action="store_true")
     ap.add_argument("--no-neck", action="store_true")
     ap.add_argument("--mask-bias", type=float, default=0.0, help="added to the initial mask logits (-2: sparse masks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (obj, cls, mask, mask_up, depth_up) as DIR/<name>.npy "
+                         "in float32, at most 64 MB in all (a fixed, seeded sample of the larger arrays); rank 0's frames")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "cfg4":
+        raise SystemExit("--dump-outputs: the simple_test_mask_preds workloads only (cfg2 / cfg3 / cfg5 / tiny), not cfg4")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
@@ -1359,6 +1390,8 @@ def main():
     from polyphonicformer_amd.dist import barrier_and_max
     dt = barrier_and_max(dt, dev if (world == 1 or backend == "nccl") else torch.device("cpu"))   # MAX over ranks
     fps = world * B * args.steps / dt
+    # before any other leg launches into the same buffers: the outputs of the last timed step
+    dumped = dump_outputs(runner.outputs(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # the one exchange of the path (video track records), outside the timed region, every rank takes part
     try:
@@ -1451,6 +1484,8 @@ def main():
             "in_graph": in_graph,
             "track_allgather": tag,
         }
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         full = args.all_legs
         if world == 1 and full and in_dt in ("bf16", "fp16") and not args.no_kernel_head:
             # the same step when the features arrive as fp32 NCHW (the reference's dtype) and go through the ingest kernel

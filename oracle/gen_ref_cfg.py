@@ -8,7 +8,8 @@ Runs (runpy, in this container) the reference's shipped configs
 
 resolving `_base_` the way mmcv.Config.fromfile does (bases loaded first, the child's dictionaries merged INTO the base's key by
 key, `_delete_=True` replaces), and writes the resulting `model` dict of each -- kwargs only, no source text -- to
-`tests/golden/ref_model_cfg.json`.  `tests/test_ref_configs.py` builds every head of this package from that JSON exactly as
+`tests/golden/ref_model_cfg.json` (and the unresolved `model` dicts of every file in the chain to
+`tests/golden/ref_cfg_tree.json`).  `tests/test_ref_configs.py` builds every head of this package from that JSON exactly as
 `TwoStageDetector.__init__` does (mmdet/models/detectors/two_stage.py:36-49: rpn_head.update(train_cfg=train_cfg.rpn,
 test_cfg=test_cfg.rpn), roi_head.update(train_cfg=train_cfg.rcnn, test_cfg=test_cfg.rcnn)) and `PolyphonicVideo.__init__`
 (polyphonic/polyphonic_former_video.py:49-60), so the kwargs contract of the boundary is pinned by the reference's files and not
@@ -22,6 +23,9 @@ import sys
 
 REF = os.environ.get("POLY_REFERENCE_ROOT", "/root/reference")
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ref_model_cfg.json")
+# the `_base_` list and the `model` dict of every file in the two configs' base chains, before resolution (data, no source text):
+# lets tests/test_ref_configs.py re-run the resolution of load_cfg without the reference on the box
+TREE = os.path.join(os.path.dirname(OUT), "ref_cfg_tree.json")
 
 
 def _merge(child, base):
@@ -59,6 +63,22 @@ def jsonable(v):
     return v
 
 
+def cfg_tree(rel, root=REF, out=None):
+    """{path relative to root: {"_base_": [...], "model": {...}}} of `rel` and, recursively, of its bases"""
+    out = {} if out is None else out
+    path = os.path.normpath(os.path.join(root, rel))
+    ns = runpy.run_path(path)
+    bases = ns.get("_base_", [])
+    bases = [bases] if isinstance(bases, str) else list(bases)
+    entry = {"_base_": bases}
+    if isinstance(ns.get("model"), dict):
+        entry["model"] = jsonable(ns["model"])
+    out[os.path.relpath(path, root)] = entry
+    for b in bases:
+        cfg_tree(os.path.join(os.path.dirname(os.path.relpath(path, root)), b), root, out)
+    return out
+
+
 def main():
     files = {"image": "configs/polyphonic_image/poly_r50_cityscapes_2x.py", "video": "configs/polyphonic_video/poly_r50_cityscapes_1x.py"}
     out = {"_source": {k: v for k, v in files.items()},
@@ -70,6 +90,14 @@ def main():
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
     print(OUT, {k: sorted(v) for k, v in out.items() if not k.startswith("_")})
+    tree = {}
+    for rel in files.values():
+        cfg_tree(rel, REF, tree)
+    with open(TREE, "w") as f:
+        json.dump({"_note": "`_base_` and `model` of every file in the base chains of the configs in ref_model_cfg.json, before "
+                            "resolution (oracle/gen_ref_cfg.py); data only", "files": tree}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(TREE, sorted(tree))
 
 
 if __name__ == "__main__":

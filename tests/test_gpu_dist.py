@@ -178,7 +178,7 @@ def test_bench_cfg4_json_line(gpu):
     assert res["roofline"]["kernel"] == "pool" and 0 < res["roofline"]["frac"] < 1
 
 
-# ---- the 8-rank shape, turnkey: on a box with fewer than 8 GPUs the ranks share GPU 0 and rendezvous over gloo ----
+# ---- the 8-rank shape, turnkey: one rank per GPU, so it needs a box with 8 GPUs ----
 def _bench_line(args, env_extra=None, timeout=1500):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
@@ -190,10 +190,19 @@ def _bench_line(args, env_extra=None, timeout=1500):
     return json.loads(lines[0])
 
 
+def _need_8_gpus():
+    """eight ranks plus this process would hold a GPU open at once: with fewer than 8 GPUs the ranks would share GPU 0 nine
+    processes deep, more than a shared box admits"""
+    n = torch.cuda.device_count()
+    if n < 8:
+        pytest.skip(f"needs 8 GPUs, found {n}")
+
+
 def test_bench_gpus8_self_launch_json_line(gpu):
     """`python bench.py --gpus 8` exactly as the driver's 8-GPU run starts it (minus the outer launcher): rank 0 starts ranks 1..7,
     every rank times its own frames, the line carries n_gpus 8, the max-over-ranks step time, the 8-rank all-gather (payload of all
     8 ranks bit-exact) and value = frames of all ranks / that time"""
+    _need_8_gpus()
     extra = {} if torch.cuda.device_count() >= 8 else {"PH_DIST_BACKEND": "gloo"}
     res = _bench_line(["--gpus", "8", "--workload", "tiny", "--frames", "8", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline",
                        "--no-kernel-head"], extra)
@@ -209,6 +218,7 @@ def test_cfg4_world8_ids_equal_world1(gpu):
     """BASELINE configs[3] at its 8-rank shape: 16 frames as 8 two-frame clips, one per rank, ONE all-gather, the replay on every rank:
     the track ids of all 16 frames equal the single-process loop's on all 8 ranks.  (The timed steps follow the warm-up and calibration
     steps: world 8 with one step times frames 16 .. 31, world 1 reaches them with 2 warm-up + 6 calibration steps of 2 frames.)"""
+    _need_8_gpus()
     ndev = torch.cuda.device_count()
     backend = "nccl" if ndev >= 8 else "gloo"
     one = _cfg4(1, "nccl", 8, warmup=2)[0]

@@ -1,6 +1,6 @@
 """The boundary pinned to the reference's OWN config files: `tests/golden/ref_model_cfg.json` holds the `model`
 dicts of configs/polyphonic_image/poly_r50_cityscapes_2x.py and configs/polyphonic_video/poly_r50_cityscapes_1x.py after `_base_`
-resolution (dumped by oracle/gen_ref_cfg.py from /root/reference -- data, no source text).  Every head of this package is built
+resolution (dumped by oracle/gen_ref_cfg.py from the reference checkout -- data, no source text).  Every head of this package is built
 from those kwargs the way TwoStageDetector.__init__ (mmdet/models/detectors/two_stage.py:36-49) and PolyphonicVideo.__init__
 (polyphonic/polyphonic_former_video.py:49-60) build the reference's; the CPU tests check the parameter names / shapes against the
 reference's state dict and the attributes the detectors read, the GPU test runs `simple_test` on the device."""
@@ -19,18 +19,24 @@ def ref_cfg(which):
         return {"model": copy.deepcopy(json.load(f)[which])}
 
 
-def test_golden_is_the_reference_configs_model_dict():
-    """when /root/reference is present (this container), the committed JSON is what the generator writes today"""
+def test_golden_is_the_reference_configs_model_dict(tmp_path):
+    """the committed JSON is what the generator's `_base_` resolution makes of the reference's config files: their unresolved
+    `_base_` lists and `model` dicts (tests/golden/ref_cfg_tree.json, written by the same generator run) are laid out as a config
+    tree again and resolved by oracle/gen_ref_cfg.load_cfg"""
     import sys
-    ref = os.environ.get("POLY_REFERENCE_ROOT", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "configs")):
-        pytest.skip("the reference is not on this box")
     sys.path.insert(0, os.path.join(Hh.REPO, "oracle"))
     import gen_ref_cfg as G
     with open(os.path.join(Hh.GOLDEN, "ref_model_cfg.json")) as f:
         committed = json.load(f)
+    with open(os.path.join(Hh.GOLDEN, "ref_cfg_tree.json")) as f:
+        tree = json.load(f)["files"]
+    for rel, entry in tree.items():
+        path = tmp_path / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text("".join(f"{k} = {entry[k]!r}\n" for k in ("_base_", "model") if k in entry))
+    assert set(committed["_source"].values()) <= set(tree)
     for which, rel in committed["_source"].items():
-        model = G.load_cfg(os.path.join(ref, rel))["model"]
+        model = G.load_cfg(str(tmp_path / rel))["model"]
         assert G.jsonable({k: v for k, v in model.items() if k not in ("backbone", "neck")}) == committed[which], which
 
 
