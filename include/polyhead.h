@@ -631,6 +631,121 @@ int ph_tracker_match(ph_tracker* t, const float* boxes, const int64_t* labels, c
 int ph_tracker_match_frames(ph_tracker* t, const float* boxes, const int64_t* labels, const float* const* embeds_dev, const int32_t* counts,
                             int nframes, int64_t first_frame_id, int32_t* kept_out, int64_t* ids_out, int32_t* kept_counts, void* stream);
 
+/* ---- N2: the S-stage decode as a native object (csrc/ph_decode.hip): what engine.DecodePlan does from Python --
+ * kernel_update.py:356-401 (simple_test_mask_preds) for a C / C++ caller.  The plan owns no memory: the caller packs every
+ * stage's weights into device memory it owns (ph_decode_pack_bytes / ph_decode_pack_stage, once per weight load), hands a
+ * workspace of ph_decode_workspace_bytes and supplies inputs and outputs per call.  ph_decode_run launches exactly the kernel
+ * sequence engine.DecodePlan.stages launches for the same geometry on the one given stream, with no host synchronisation,
+ * allocation or read of device data: it can be captured into a hipGraph (the captured pointers must then stay valid).
+ * No ph_decode_* function reads the environment: the knobs engine.DecodePlan reads from it are fields of ph_decode_cfg, and
+ * the plan's launches go through internal forms of ph_dynconv / ph_dynconv_up2_wgs / ph_query_stage_counts that take their
+ * launch knobs as arguments (the public entry points keep reading PH_CONV_* / PH_UP2_* / PH_QUERY_*), so setting
+ * those variables changes nothing in a plan.  Errors: every argument and geometry error (sizes, modes, limits of the query,
+ * pooling and fused kernels, a fused form forced where it cannot run, a short workspace, bad pointers or formats) is returned
+ * by ph_decode_create / ph_decode_run before the first launch; only a launch the runtime itself refuses (PH_ELAUNCH) can
+ * come back after earlier kernels of the sequence were queued.
+ * A zero-initialised ph_decode_cfg plus the sizes and the mode is the module API's configuration: every knob on "auto"
+ * (= engine.DecodePlan's rule with no environment variable set). */
+enum { PH_MODE_FP32 = 0, PH_MODE_MIXED = 1, PH_MODE_MIXED16 = 2, PH_MODE_FP16 = 3, PH_MODE_BF16 = 4 };   /* engine.MODES */
+/* poolx / fused_up: AUTO = engine.DecodePlan's rule; ON = the fused form, an error (PH_EUNSUPPORTED) where it cannot run this
+ * geometry; OFF = never; WHERE_SUPPORTED = wherever it can run (what PH_CONV_POOLX=1 / PH_CONV_UP2=1 do for the Python plan) */
+enum { PH_KNOB_AUTO = 0, PH_KNOB_ON = 1, PH_KNOB_OFF = 2, PH_KNOB_WHERE_SUPPORTED = 3 };
+typedef struct {
+    int32_t B, N, H, W;         /* frames, queries (things + stuff), feature map (stride 8) */
+    int32_t S;                  /* update stages, 1 .. 16 */
+    int32_t L;                  /* classes (fc_cls rows), 1 .. 1024 */
+    int32_t F;                  /* feedforward_channels, multiple of 256 */
+    int32_t mode;               /* PH_MODE_* */
+    int32_t out_dtype;          /* PH_OUT_* of mask / mask_up / depth / depth_up (obj, dobj, cls are fp32) */
+    int32_t frame_invariant;    /* 1: a frame's outputs do not depend on B (the module API's default; engine.DecodePlan) */
+    int32_t query_full_split;   /* mixed16 / fp16: 1 = query side hi + lo bf16 (PH_PREC_SPLIT) instead of PH_PREC_QHYBRID */
+    int32_t shares_gpu;         /* 1: one part of a multi-stream step (PH_QUERY_WIDE, the final stage's shared workgroup count) */
+    int32_t poolx;              /* PH_KNOB_*: ph_dynconv_poolx between the stages              (env PH_CONV_POOLX of the Python plan) */
+    int32_t fused_up;           /* PH_KNOB_*: ph_dynconv_up2 for the final stage                (PH_CONV_UP2) */
+    int32_t nsplit;             /* 0 = auto, else pixel ranges of ph_pool_counts                (PH_POOL_NSPLIT) */
+    int32_t nsplit_px;          /* 0 = auto, else pixel ranges of ph_dynconv_poolx; frame_invariant plans use nsplit (PH_POOLX_NSPLIT) */
+    int32_t up2_wgs;            /* 0 = auto (1.5 per CU), else the final stage's workgroups of shares_gpu plans (PH_UP2_SHARED_WGS) */
+} ph_decode_cfg;
+
+/* the geometry a plan chose (ph_decode_info) */
+typedef struct {
+    int32_t nsplit, nsplit_px, poolx, fused_up;
+    int32_t up2_workgroups;     /* workgroups of the fused final stage's launches: 0 = one per CU */
+    int32_t feat_prec, query_prec, conv_prec, kern_format;   /* PH_PREC_* / PH_KERN_* of ingest + pool, query, dynamic conv */
+    int32_t feat_planes;        /* P of the feature planes [P][B][256][HWp] */
+} ph_decode_geometry;
+
+/* ph_decode_run's inputs and outputs.  feat_format:
+ *   PH_FEAT_F32     x / depth_feats fp32 NCHW [B][256][H][W]       (ingested to planes inside the call)
+ *   PH_FEAT_16      16-bit NCHW of the mode's plane format: bf16 for bf16 / mixed / mixed16, fp16 for fp16 (copied into the planes)
+ *   PH_FEAT_PLANES  feature planes [P][B][256][HWp] another kernel produced (ph_khead_*), read only, and `bits` [B][Npad][HWp/32]
+ *                   instead of m0 (copied: the stages rewrite them) */
+enum { PH_FEAT_F32 = 0, PH_FEAT_16 = 1, PH_FEAT_PLANES = 2 };
+typedef struct {
+    int32_t feat_format;        /* PH_FEAT_* */
+    int32_t m0_dtype;           /* PH_OUT_* of m0 */
+    const void* x;
+    const void* depth_feats;
+    const float* k0;            /* proposal_feats [B][N][256] */
+    const float* q0;            /* depth_proposal [B][N][256] */
+    const void* m0;             /* mask logits [B][N][H][W] (unused with PH_FEAT_PLANES) */
+    const uint32_t* bits;       /* PH_FEAT_PLANES only */
+    float* obj;                 /* [B][N][256]  last stage's object_feats */
+    float* dobj;                /* [B][N][256]  last stage's depth_proposal */
+    float* cls;                 /* [B][N][L]    sigmoid class scores */
+    void* mask;                 /* [B][N][H][W]     out_dtype */
+    void* mask_up;              /* [B][N][2H][2W]   out_dtype */
+    void* depth_up;             /* [B][N][2H][2W]   out_dtype */
+    void* depth;                /* nullable: [B][N][H][W] low-resolution depth logits */
+} ph_decode_io;
+
+/* ---- stage packing: the one stage's parameters below, fp32 device tensors in this order (the reference's state_dict names,
+ * SURVEY.md 8b; KernelUpdateHead with num_cls_fcs = num_mask_fcs = 1, num_ffn_fcs = 2), packed into the layout pack.py
+ * describes: the Linear weights as MFMA B-fragments in one or two 16-bit planes, feat_transform / feat_depth_transform folded
+ * into dynamic_layer and fc_mask / fc_depth in float64 (k ascending: deterministic), then rounded to fp32 and split.
+ *    0 attention.attn.in_proj_weight [768][256]    1 attention.attn.in_proj_bias [768]
+ *    2 attention.attn.out_proj.weight [256][256]   3 attention.attn.out_proj.bias
+ *    4 .. 7   attention_depth.attn.* in the same order
+ *    8 attention_norm.weight         9 attention_norm.bias      10 attention_norm_depth.weight   11 attention_norm_depth.bias
+ *   12 kernel_update_conv.dynamic_layer.weight [512][256]      13 .dynamic_layer.bias [512]
+ *   14 kernel_update_conv.input_layer.weight [512][256]        15 .input_layer.bias [512]
+ *   16 .input_gate.weight [256][256]   17 .input_gate.bias     18 .update_gate.weight          19 .update_gate.bias
+ *   20 .norm_in.weight        21 .norm_in.bias                 22 .norm_out.weight             23 .norm_out.bias
+ *   24 .input_norm_in.weight  25 .input_norm_in.bias           26 .input_norm_out.weight       27 .input_norm_out.bias
+ *   28 .fc_layer.weight       29 .fc_layer.bias                30 .fc_norm.weight              31 .fc_norm.bias
+ *   32 .. 51 kernel_update_conv_depth.* in the same order
+ *   52 feat_transform.conv.weight [256][256][1][1]        53 feat_transform.conv.bias
+ *   54 feat_depth_transform.conv.weight                   55 feat_depth_transform.conv.bias
+ *   56 ffn.layers.0.0.weight [F][256]   57 .bias [F]      58 ffn.layers.1.weight [256][F]   59 .bias
+ *   60 ffn_norm.weight                  61 ffn_norm.bias
+ *   62 .. 67 ffn_depth.layers.0.0.{weight, bias}, ffn_depth.layers.1.{weight, bias}, ffn_norm_depth.{weight, bias}
+ *   68 cls_fcs.0.weight    69 cls_fcs.1.weight    70 cls_fcs.1.bias    71 fc_cls.weight [L][256]    72 fc_cls.bias [L]
+ *   73 mask_fcs.0.weight   74 mask_fcs.1.weight   75 mask_fcs.1.bias
+ *   76 depth_regs.0.weight 77 depth_regs.1.weight 78 depth_regs.1.bias
+ *   79 fc_mask.weight      80 fc_mask.bias        81 fc_depth.weight   82 fc_depth.bias
+ * (ph_decode_param_name / ph_decode_param_numel state the same table.)  Vectors are [256] unless noted.
+ * One pack = uint16 planes [P][wb_plane_elems] followed, at the next 256-byte boundary, by the fp32 vectors.  Packs made
+ * by pack.py (engine.StagePack: wb, wf) in the same layout serve a plan as well. */
+#define PH_DECODE_NPARAMS 83
+const char* ph_decode_param_name(int index);                        /* NULL out of range */
+int64_t ph_decode_param_numel(const ph_decode_cfg* cfg, int index); /* elements; < 0 out of range */
+size_t ph_decode_pack_bytes(const ph_decode_cfg* cfg);              /* 0 on a bad cfg (see ph_last_error_string) */
+/* the layout of a pack (pack.py's StageLayout; offsets in elements; wb at byte 0, wf at wf_byte_offset) */
+int ph_decode_pack_layout(const ph_decode_cfg* cfg, ph_stage_layout* layout, size_t* wf_byte_offset);
+/* one launch; `params`: host array of PH_DECODE_NPARAMS device pointers */
+int ph_decode_pack_stage(const ph_decode_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- plan lifetime.  workspace: feature planes, mask bits, pooled partial sums and pixel counts, the query workspace,
+ * every stage's outputs but the last stage's obj / dobj / cls, the low-resolution depth logits of the two-kernel final
+ * stage; 256-byte aligned pieces.  The caller keeps the packs and the workspace alive as long as the plan. */
+typedef struct ph_decode ph_decode;
+size_t ph_decode_workspace_bytes(const ph_decode_cfg* cfg);         /* 0 on a bad cfg */
+int ph_decode_create(const ph_decode_cfg* cfg, const void* const* packs /* S device pointers */, void* workspace,
+                     size_t workspace_bytes, ph_decode** out);
+int ph_decode_info(const ph_decode* plan, ph_decode_geometry* out);
+void ph_decode_destroy(ph_decode* plan);
+int ph_decode_run(ph_decode* plan, const ph_decode_io* io, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -32,6 +32,29 @@ class StageLayout(C.Structure):
                 ("wb_plane_elems", C.c_int64), ("ffn_dim", C.c_int32), ("num_classes", C.c_int32)]
 
 
+# the native decode plan (polyhead.h ph_decode_*)
+PH_MODE = {"fp32": 0, "split": 0, "mixed": 1, "mixed16": 2, "fp16": 3, "bf16": 4}
+PH_KNOB_AUTO, PH_KNOB_ON, PH_KNOB_OFF, PH_KNOB_WHERE_SUPPORTED = 0, 1, 2, 3
+PH_FEAT_F32, PH_FEAT_16, PH_FEAT_PLANES = 0, 1, 2
+PH_DECODE_NPARAMS = 83
+
+
+class DecodeCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "H", "W", "S", "L", "F", "mode", "out_dtype", "frame_invariant", "query_full_split",
+                                          "shares_gpu", "poolx", "fused_up", "nsplit", "nsplit_px", "up2_wgs")]
+
+
+class DecodeGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nsplit", "nsplit_px", "poolx", "fused_up", "up2_workgroups", "feat_prec", "query_prec",
+                                          "conv_prec", "kern_format", "feat_planes")]
+
+
+class DecodeIO(C.Structure):
+    _fields_ = [("feat_format", C.c_int32), ("m0_dtype", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("x", "depth_feats", "k0", "q0", "m0", "bits", "obj", "dobj", "cls", "mask", "mask_up", "depth_up",
+                                   "depth")]
+
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
@@ -148,6 +171,16 @@ SIGNATURES = {
     "ph_tracker_debug_times": (None, [_P, _P]),
     "ph_tracker_match": (C.c_int, [_P, _P, _P, _P, _I, _L, _P, _P, _P]),
     "ph_tracker_match_frames": (C.c_int, [_P, _P, _P, _P, _P, _I, _L, _P, _P, _P, _P]),
+    "ph_decode_param_name": (C.c_char_p, [_I]),
+    "ph_decode_param_numel": (C.c_int64, [C.POINTER(DecodeCfg), _I]),
+    "ph_decode_pack_bytes": (C.c_size_t, [C.POINTER(DecodeCfg)]),
+    "ph_decode_pack_layout": (C.c_int, [C.POINTER(DecodeCfg), C.POINTER(StageLayout), C.POINTER(C.c_size_t)]),
+    "ph_decode_pack_stage": (C.c_int, [C.POINTER(DecodeCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_decode_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeCfg)]),
+    "ph_decode_create": (C.c_int, [C.POINTER(DecodeCfg), C.POINTER(C.c_void_p), _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_decode_info": (C.c_int, [_P, C.POINTER(DecodeGeometry)]),
+    "ph_decode_destroy": (None, [_P]),
+    "ph_decode_run": (C.c_int, [_P, C.POINTER(DecodeIO), _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

@@ -39,6 +39,35 @@ void ph_set_error(const char* fmt, ...);
 // 3.6e-8 of N(0, 1) logits, i.e. about one pixel in four full-size frames -- enough to move a pooled feature by 1e-3.
 #define PH_BIN_THR 0x1.8p-24f
 
+// ---- launch knobs of the decode kernels.  The public entry points (ph_dynconv, ph_dynconv_up2[_wgs], ph_query_stage[_counts])
+// fill them from environment variables -- A/B measurement aids and test switches -- and call the *_k forms below;
+// the native decode plan (ph_decode.hip) passes the defaults explicitly and so reads no environment at all.
+struct PhConvKnobs {
+    int wgs = 0;                 // PH_CONV_WGS: workgroups (0 = one per CU)
+    bool two_halves = false;     // PH_CONV_TWO_HALVES=1
+    bool coop = true;            // PH_CONV_COOP=0 -> false
+};
+struct PhUp2Knobs {
+    int wgs = 0;                 // PH_UP2_WGS: overrides the caller's workgroup count (0 = keep it)
+    bool mfma = true;            // PH_UP2_MFMA=0 -> false (the window-pass kernel)
+    int dbg = 0;                 // PH_UP2_DBG (timing experiments)
+};
+struct PhQueryKnobs {
+    bool v1 = false;                         // PH_QUERY_V1=1: first-generation kernels
+    int nrt = 0;                             // PH_QUERY_NRT: row blocks per workgroup (0 = the launch's own choice)
+    unsigned long long* timeline = nullptr;  // PH_QUERY_TIMELINE=1: phase times of one workgroup (debug; synchronises)
+};
+int ph_dynconv_k(const PhConvKnobs& kn, const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
+                 int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out, void* logits_out,
+                 int out_dtype, int64_t out_batch_stride, int B, int N, int64_t HW, int prec, void* stream);
+int ph_dynconv_up2_k(const PhUp2Knobs& kn, const uint16_t* planes, const uint16_t* kern, int64_t kern_batch_stride, const float* kbias,
+                     int64_t kbias_batch_stride, void* logits_out, void* up_out, int out_dtype, int B, int N, int H, int W, int prec,
+                     int workgroups, void* stream);
+int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int nsplit, const uint32_t* bits, const int32_t* pcount,
+                            const float* k_in, const float* q_in, const uint16_t* wb, const float* wf, const ph_stage_layout* layout,
+                            float* obj, float* dobj, float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
+                            size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream);
+
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects
 // it for fp32 -> __bf16 conversions.

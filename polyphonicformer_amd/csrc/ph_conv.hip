@@ -325,22 +325,21 @@ static int conv_num_cus() {
 template <int PF, int PK, int E, int NRT>
 static int launch_conv(const uint16_t* planes, const uint16_t* kern, int64_t kps, int64_t kbs, const float* kbias,
                        int64_t bbs, uint32_t* bits_out, void* logits_out, int out_dtype, int64_t obs, int B, int N,
-                       int64_t HW, hipStream_t s) {
+                       int64_t HW, const PhConvKnobs& kn, hipStream_t s) {
     const int64_t HWp = ph_hw_padded(HW);
     const int64_t total = (int64_t)B * (HWp / CONV_T);
     // one persistent workgroup per CU (it owns the CU's LDS), tiles split evenly: no tail generation
     int wgs = conv_num_cus();
-    static const int wgs_env = [] { const char* e = getenv("PH_CONV_WGS"); return e ? atoi(e) : 0; }();   // tuning knob, read once
-    if (wgs_env) wgs = wgs_env;
+    if (kn.wgs) wgs = kn.wgs;
     if (wgs > total) wgs = (int)total;
     if (wgs < 1) wgs = 1;
     const dim3 grid(wgs);
-    // tuning knob: PH_CONV_TWO_HALVES=1 forces the two-halves-per-wave form of the two-kernel-plane kernels (A/B measurements)
-    static const bool two_halves = [] { const char* e = getenv("PH_CONV_TWO_HALVES"); return e && atoi(e) != 0; }();
-    // the mixed16 conv converts its bf16 tile to fp16 once per tile in LDS (see k_dynconv); PH_CONV_COOP=0 restores the
+    // kn.two_halves forces the two-halves-per-wave form of the two-kernel-plane kernels (A/B measurements)
+    const bool two_halves = kn.two_halves;
+    // the mixed16 conv converts its bf16 tile to fp16 once per tile in LDS (see k_dynconv); kn.coop = false restores the
     // per-wave conversion in registers for A/B measurements (same box, 24 frames: bits 155 -> 130-136 us, logits 157-162 ->
     // 148-151 us, the 96-frame step 13.16 k -> 13.53 k frames/s; results identical, the conversion is exact either way)
-    static const bool coop = [] { const char* e = getenv("PH_CONV_COOP"); return !(e && atoi(e) == 0); }();
+    const bool coop = kn.coop;
     (void)coop;
 #define PH_CONV_LAUNCH__(BITS, T, F2, CO)                                                                            \
     do {                                                                                                             \
@@ -379,10 +378,9 @@ static int launch_conv(const uint16_t* planes, const uint16_t* kern, int64_t kps
     return 0;
 }
 
-extern "C" int ph_dynconv(const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
-                          int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out,
-                          void* logits_out, int out_dtype, int64_t out_batch_stride, int B, int N, int64_t HW, int prec,
-                          void* stream) {
+int ph_dynconv_k(const PhConvKnobs& kn, const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
+                 int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out, void* logits_out,
+                 int out_dtype, int64_t out_batch_stride, int B, int N, int64_t HW, int prec, void* stream) {
     PH_CHECK_ARG(planes && kern && kbias && B > 0 && N > 0 && HW > 0, "bad pointer or size");
     PH_CHECK_ARG((bits_out != nullptr) != (logits_out != nullptr), "exactly one of bits_out / logits_out");
     PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_BF16_KSPLIT || prec == PH_PREC_F16 ||
@@ -392,7 +390,7 @@ extern "C" int ph_dynconv(const uint16_t* planes, const uint16_t* kern, int64_t 
     const int nrt = ph_n_padded(N) / 32;
     hipStream_t s = (hipStream_t)stream;
 #define PH_CONV_ARGS planes, kern, kern_plane_stride, kern_batch_stride, kbias, kbias_batch_stride, bits_out, logits_out, \
-                     out_dtype, out_batch_stride, B, N, HW, s
+                     out_dtype, out_batch_stride, B, N, HW, kn, s
 #define PH_CONV_CASE(R)                                                                                         \
     case R:                                                                                                     \
         if (prec == PH_PREC_BF16) launch_conv<1, 1, PH_E_BF16, R>(PH_CONV_ARGS);                                \
@@ -410,4 +408,24 @@ extern "C" int ph_dynconv(const uint16_t* planes, const uint16_t* kern, int64_t 
 #undef PH_CONV_ARGS
     PH_CHECK_LAUNCH();
     return PH_OK;
+}
+
+// tuning knobs, read once per process: PH_CONV_WGS, PH_CONV_TWO_HALVES=1, PH_CONV_COOP=0 (A/B measurements)
+static const PhConvKnobs& conv_env_knobs() {
+    static const PhConvKnobs k = [] {
+        PhConvKnobs r;
+        if (const char* e = getenv("PH_CONV_WGS")) r.wgs = atoi(e);
+        if (const char* e = getenv("PH_CONV_TWO_HALVES")) r.two_halves = atoi(e) != 0;
+        if (const char* e = getenv("PH_CONV_COOP")) r.coop = atoi(e) != 0;
+        return r;
+    }();
+    return k;
+}
+
+extern "C" int ph_dynconv(const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
+                          int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out,
+                          void* logits_out, int out_dtype, int64_t out_batch_stride, int B, int N, int64_t HW, int prec,
+                          void* stream) {
+    return ph_dynconv_k(conv_env_knobs(), planes, kern, kern_plane_stride, kern_batch_stride, kbias, kbias_batch_stride, bits_out,
+                        logits_out, out_dtype, out_batch_stride, B, N, HW, prec, stream);
 }

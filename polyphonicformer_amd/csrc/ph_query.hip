@@ -1722,8 +1722,8 @@ static void launch_query2(const QArgs2& a, int phases, hipStream_t s) {
 }
 
 // (error messages of both entry points name this function)
-static int query_run(const float* partial, int nsplit, const uint32_t* bits, const int32_t* pcount, const float* k_in, const float* q_in,
-                     const uint16_t* wb, const float* wf, const ph_stage_layout* layout, float* obj, float* dobj,
+static int query_run(const PhQueryKnobs& kn, const float* partial, int nsplit, const uint32_t* bits, const int32_t* pcount, const float* k_in,
+                     const float* q_in, const uint16_t* wb, const float* wf, const ph_stage_layout* layout, float* obj, float* dobj,
                      float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                      size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases,
                      void* stream) {
@@ -1752,19 +1752,13 @@ static int query_run(const float* partial, int nsplit, const uint32_t* bits, con
     a.Qp = (uint16_t*)workspace; a.Kp = a.Qp + pl; a.Vt = a.Kp + pl; a.o1 = (float*)(a.Vt + pl);
     a.lay = *layout; a.cls_sigmoid = cls_sigmoid; a.kern_f16 = kern_format == PH_KERN_F16; a.nsplit = nsplit; a.B = B; a.N = N; a.Npad = Npad; a.HWp = ph_hw_padded(HW);
     hipStream_t s = (hipStream_t)stream;
-    static const bool v1 = [] { const char* e = getenv("PH_QUERY_V1"); return e && atoi(e) != 0; }();
-    if (v1 && !hybrid) {                  // first-generation kernels (32 / 16 rows per workgroup), kept for A/B measurements
+    if (kn.v1 && !hybrid) {                  // first-generation kernels (32 / 16 rows per workgroup), kept for A/B measurements
         if (PA == 1) launch_query<1, 2>(a, phases, s);
         else launch_query<2, 1>(a, phases, s);
     } else {
         QArgs2 a2;
         a2.q = a;
-        static unsigned long long* tl = [] {            // debug only: PH_QUERY_TIMELINE=1 prints phase times of one workgroup
-            unsigned long long* p = nullptr;
-            const char* e = getenv("PH_QUERY_TIMELINE");
-            if (e && atoi(e) != 0 && hipMalloc((void**)&p, 16 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(p, 0, 128);
-            return p;
-        }();
+        unsigned long long* tl = kn.timeline;          // debug only: phase times of one workgroup
         a2.tl = tl;
         a2.pi = a.o1 + (size_t)B * 2 * Npad * 256;
         // rows per workgroup (16 * nrt, nrt | Npad / 16).  Two regimes, measured at cfg2 (tools/query_time.py, split
@@ -1786,8 +1780,7 @@ static int query_run(const float* partial, int nsplit, const uint32_t* bits, con
             }
             if (nrt == 1) nrt = smallest;
         }
-        static const int cap = [] { const char* e = getenv("PH_QUERY_NRT"); return e ? atoi(e) : 0; }();   // tuning knob
-        if (cap > 0) { nrt = cap; while (t % nrt) --nrt; }
+        if (kn.nrt > 0) { nrt = kn.nrt; while (t % nrt) --nrt; }   // tuning knob
 #define PH_Q2(P, R) launch_query2<P, R>(a2, phases, s)
 #define PH_QH(R) launch_query2<2, R, true>(a2, phases, s)
         if (hybrid) { switch (nrt) { case 5: PH_QH(5); break; case 4: PH_QH(4); break; case 3: PH_QH(3); break; case 2: PH_QH(2); break; default: PH_QH(1); } }
@@ -1808,12 +1801,26 @@ static int query_run(const float* partial, int nsplit, const uint32_t* bits, con
     return PH_OK;
 }
 
+// knobs read once per process: PH_QUERY_V1=1, PH_QUERY_NRT, PH_QUERY_TIMELINE=1 (A/B measurements, debugging)
+static const PhQueryKnobs& query_env_knobs() {
+    static const PhQueryKnobs k = [] {
+        PhQueryKnobs r;
+        if (const char* e = getenv("PH_QUERY_V1")) r.v1 = atoi(e) != 0;
+        if (const char* e = getenv("PH_QUERY_NRT")) r.nrt = atoi(e);
+        const char* e = getenv("PH_QUERY_TIMELINE");
+        if (e && atoi(e) != 0 && hipMalloc((void**)&r.timeline, 16 * sizeof(unsigned long long)) == hipSuccess)
+            (void)hipMemset(r.timeline, 0, 128);
+        return r;
+    }();
+    return k;
+}
+
 extern "C" int ph_query_stage(const float* partial, int nsplit, const uint32_t* bits, const float* k_in, const float* q_in,
                               const uint16_t* wb, const float* wf, const ph_stage_layout* layout, float* obj, float* dobj,
                               float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                               size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases,
                               void* stream) {
-    return query_run(partial, nsplit, bits, nullptr, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
+    return query_run(query_env_knobs(), partial, nsplit, bits, nullptr, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
                      workspace_bytes, B, N, HW, prec, kern_format, phases, stream);
 }
 
@@ -1825,6 +1832,15 @@ extern "C" int ph_query_stage_counts(const float* partial, int nsplit, const uin
                                      void* workspace, size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format,
                                      int phases, void* stream) {
     if (!pcount) { ph_set_error("ph_query_stage_counts: null pcount"); return PH_EINVAL; }
-    return query_run(partial, nsplit, bits, pcount, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
+    return query_run(query_env_knobs(), partial, nsplit, bits, pcount, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias,
+                     workspace, workspace_bytes, B, N, HW, prec, kern_format, phases, stream);
+}
+
+int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int nsplit, const uint32_t* bits, const int32_t* pcount,
+                            const float* k_in, const float* q_in, const uint16_t* wb, const float* wf, const ph_stage_layout* layout,
+                            float* obj, float* dobj, float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
+                            size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream) {
+    if (!pcount) { ph_set_error("ph_query_stage_counts: null pcount"); return PH_EINVAL; }
+    return query_run(kn, partial, nsplit, bits, pcount, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
                      workspace_bytes, B, N, HW, prec, kern_format, phases, stream);
 }

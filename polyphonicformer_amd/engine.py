@@ -458,6 +458,217 @@ class DecodePlan:
                     mask_up=self.mask_up, depth_up=self.depth_up)
 
 
+# ---- the S-stage plan as a native object (include/polyhead.h ph_decode_*) -----------------------------------
+def native_cfg(B, N, H, W, S, L, F, prec, out_dtype=torch.float32, frame_invariant=False, shares_gpu=False, nsplit=None):
+    """the ph_decode_cfg of the DecodePlan that the same arguments (and the same environment) would build: the switches
+    DecodePlan reads from the environment become the cfg's explicit fields -- the native plan itself never reads it"""
+    mode = mode_of(prec)
+    env = _os.environ.get
+    knob = lambda v: {"0": _lib.PH_KNOB_OFF, "1": _lib.PH_KNOB_WHERE_SUPPORTED}.get(v, _lib.PH_KNOB_AUTO)
+    return _lib.DecodeCfg(B=B, N=N, H=H, W=W, S=S, L=L, F=F, mode=_lib.PH_MODE[mode.name], out_dtype=OUT_CODE[out_dtype],
+                          frame_invariant=int(bool(frame_invariant)),
+                          query_full_split=int(mode.name in ("mixed16", "fp16") and mode.query == _lib.PH_PREC_SPLIT),
+                          shares_gpu=int(bool(shares_gpu)), poolx=knob(env("PH_CONV_POOLX")), fused_up=knob(env("PH_CONV_UP2")),
+                          nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0),
+                          nsplit_px=0 if frame_invariant else int(env("PH_POOLX_NSPLIT") or 0),
+                          up2_wgs=int(env("PH_UP2_SHARED_WGS") or 0))
+
+
+def _cfg_error(what):
+    msg = _lib.load().ph_last_error_string()
+    return _lib.PolyheadError(f"{what}: {msg.decode() if msg else ''}")
+
+
+def native_pack_stage(module, cfg, device):
+    """one KernelUpdateHead stage's parameters packed on the device by ph_decode_pack_stage -> uint8 tensor (one pack)"""
+    lib = _lib.load()
+    nbytes = lib.ph_decode_pack_bytes(C.byref(cfg))
+    if nbytes == 0:
+        raise _cfg_error("ph_decode_pack_bytes")
+    sd = module.state_dict() if hasattr(module, "state_dict") else module
+    params = []
+    for i in range(_lib.PH_DECODE_NPARAMS):
+        name = lib.ph_decode_param_name(i).decode()
+        t = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
+        if t.numel() != lib.ph_decode_param_numel(C.byref(cfg), i):
+            raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {lib.ph_decode_param_numel(C.byref(cfg), i)}")
+        params.append(t)
+    ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    pack = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    _lib.check(lib.ph_decode_pack_stage(C.byref(cfg), ptrs, _lib.ptr(pack), _lib.stream_ptr()), "ph_decode_pack_stage")
+    return pack
+
+
+def native_pack_from(pack, cfg):
+    """a StagePack (pack.py's planes + vectors) laid out as one native pack; its layout must be the native one"""
+    lib = _lib.load()
+    lay, off = _lib.StageLayout(), C.c_size_t()
+    _lib.check(lib.ph_decode_pack_layout(C.byref(cfg), C.byref(lay), C.byref(off)), "ph_decode_pack_layout")
+    if bytes(lay) != bytes(pack.lay):
+        raise _lib.PolyheadError("the StagePack's layout differs from the native pack layout of this cfg")
+    blob = torch.zeros((lib.ph_decode_pack_bytes(C.byref(cfg)),), dtype=torch.uint8, device=pack.wb.device)
+    wb = pack.wb.contiguous().view(torch.uint8).reshape(-1)
+    wf = pack.wf.contiguous().view(torch.uint8).reshape(-1)
+    blob[:wb.numel()].copy_(wb)
+    blob[off.value:off.value + wf.numel()].copy_(wf)
+    return blob
+
+
+class NativeDecodePlan:
+    """DecodePlan's surface (set_inputs, run, run_from_planes, renew_outputs, outputs, capture / replay) over ONE native call per
+    decode (ph_decode_run): the same launch sequence and geometry as the DecodePlan of the same arguments, so the same bits.
+    `packs`: StagePacks (re-laid out as native packs once) or native packs (`native_pack_stage`)."""
+
+    def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False,
+                 shares_gpu=False, num_classes=None, ffn_dim=None):
+        self.S, self.B, self.N, self.H, self.W, self.HW = len(packs), B, N, H, W, H * W
+        self.mode = mode_of(prec)
+        self.prec, self.out_dtype, self.frame_invariant, self.shares_gpu = self.mode.feat, out_dtype, frame_invariant, shares_gpu
+        dev = torch.device(device)
+        self.device = dev
+        if all(isinstance(p, StagePack) for p in packs):
+            if any(p.prec != self.mode.query for p in packs):
+                raise _lib.PolyheadError(f"stage packs are not packed for mode '{self.mode.name}'")
+            L, F = packs[0].num_classes, packs[0].lay.ffn_dim
+        else:
+            L, F = num_classes, ffn_dim
+        self.cfg = native_cfg(B, N, H, W, self.S, L, F, self.mode, out_dtype, frame_invariant, shares_gpu, nsplit)
+        lib = _lib.load()
+        nbytes = lib.ph_decode_workspace_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise _cfg_error("ph_decode_workspace_bytes")
+        self.packs = [native_pack_from(p, self.cfg) if isinstance(p, StagePack) else p for p in packs]
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        handle = C.c_void_p()
+        with torch.cuda.device(dev):
+            _lib.check(lib.ph_decode_create(C.byref(self.cfg), (C.c_void_p * self.S)(*[p.data_ptr() for p in self.packs]),
+                                            _lib.ptr(self.workspace), nbytes, C.byref(handle)), "ph_decode_create")
+        self._h = handle
+        geo = _lib.DecodeGeometry()
+        _lib.check(lib.ph_decode_info(self._h, C.byref(geo)), "ph_decode_info")
+        self.geometry = geo
+        self.nsplit, self.nsplit_px, self.poolx, self.fused_up = geo.nsplit, geo.nsplit_px, bool(geo.poolx), bool(geo.fused_up)
+        Npad, HWp = n_padded(N), hw_padded(self.HW)
+        # shapes of the plan's planes and bits (they live in the workspace): what the module API compares a KernelHead hand-off with
+        self.xp = torch.empty((self.mode.FP, B, 256, HWp), dtype=torch.int16, device="meta")
+        self.bits = torch.empty((B, Npad, HWp // 32), dtype=torch.int32, device="meta")
+        self.want_depth_lowres = False
+        self.graph = None
+        self.handoff_runs = 0
+        self._in = None
+        self.io = _lib.DecodeIO()
+        self._alloc_outputs()
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            _lib._lib.ph_decode_destroy(h)
+            self._h = None
+
+    @property
+    def out_code(self):
+        return OUT_CODE[self.out_dtype]
+
+    def _alloc_outputs(self):
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        B, N, H, W = self.B, self.N, self.H, self.W
+        self.obj, self.dobj = e((B, N, 256), torch.float32), e((B, N, 256), torch.float32)
+        self.cls = e((B, N, self.cfg.L), torch.float32)
+        self.mask, self.mask_up, self.depth_up = e((B, N, H, W), self.out_dtype), e((B, N, 2 * H, 2 * W), self.out_dtype), \
+            e((B, N, 2 * H, 2 * W), self.out_dtype)
+        self.depth = e((B, N, H, W), self.out_dtype) if (not self.fused_up or self.want_depth_lowres) else None
+        io = self.io
+        io.obj, io.dobj, io.cls = self.obj.data_ptr(), self.dobj.data_ptr(), self.cls.data_ptr()
+        io.mask, io.mask_up, io.depth_up = self.mask.data_ptr(), self.mask_up.data_ptr(), self.depth_up.data_ptr()
+
+    def renew_outputs(self):
+        """fresh output tensors for the next `run` (DecodePlan.renew_outputs)"""
+        if self.graph is not None:
+            raise _lib.PolyheadError("renew_outputs on a captured plan")
+        self._alloc_outputs()
+
+    def set_inputs(self, x, dfe, k0, q0, m0):
+        """as DecodePlan.set_inputs: fp32 NCHW features, or 16-bit NCHW in the mode's plane format.  Eager plans read the given
+        tensors in place (no copy); a captured plan copies them into the tensors its graph reads."""
+        B, N = self.B, self.N
+        f16 = x.dtype in (torch.bfloat16, torch.float16) and dfe.dtype == x.dtype
+        if f16 and self.mode.feat_dtype != x.dtype:
+            raise _lib.PolyheadError(f"{x.dtype} feature inputs need a mode with that plane format (bf16: 'bf16' / "
+                                     f"'mixed' / 'mixed16', fp16: 'fp16'; this plan: '{self.mode.name}')")
+        for t, nm, numel in ((x, "x", B * 256 * self.HW), (dfe, "depth_feats", B * 256 * self.HW), (k0, "proposal_feats", B * N * 256),
+                             (q0, "depth_proposal", None), (m0, "mask_preds", B * N * self.HW)):
+            _require_gpu(t, nm)
+            if numel is not None and t.numel() != numel:
+                raise _lib.PolyheadError(f"{nm}: {tuple(t.shape)} does not fit the plan (B={B}, N={N}, H={self.H}, W={self.W})")
+        cast = (lambda t: t.contiguous()) if f16 else (lambda t: t.float().contiguous())
+        new = dict(x=cast(x), dfe=cast(dfe), k0=k0.reshape(B, N, 256).float().contiguous(),
+                   q0=q0.reshape(B, N, 256).float().contiguous(),      # materialises the stride-0 expand view
+                   m0=m0.contiguous() if m0.dtype in OUT_CODE else m0.float().contiguous())
+        if self.graph is not None and self._in is not None and self._in.get("feat") == 1 and all(
+                self._in[k].dtype == v.dtype for k, v in new.items()):
+            for k, v in new.items():
+                self._in[k].copy_(v)
+            return
+        self.graph = None           # a captured graph read other tensors: the owner captures again
+        self._in = dict(new, feat=1)
+        self._point_inputs(_lib.PH_FEAT_16 if f16 else _lib.PH_FEAT_F32)
+
+    def _point_inputs(self, feat_format, bits=None):
+        i, io = self._in, self.io
+        io.feat_format = feat_format
+        io.x, io.depth_feats, io.k0, io.q0 = i["x"].data_ptr(), i["dfe"].data_ptr(), i["k0"].data_ptr(), i["q0"].data_ptr()
+        io.m0 = None if bits is not None else i["m0"].data_ptr()
+        io.m0_dtype = OUT_CODE.get(i["m0"].dtype, _lib.PH_OUT_F32) if bits is None else _lib.PH_OUT_F32
+        io.bits = None if bits is None else bits.data_ptr()
+
+    def run(self):
+        """one pass: ingest + S stages + final stage, ONE native call on the current stream"""
+        io = self.io
+        if (not self.fused_up or self.want_depth_lowres) and self.depth is None:
+            self.depth = torch.empty((self.B, self.N, self.H, self.W), dtype=self.out_dtype, device=self.device)
+        io.depth = self.depth.data_ptr() if (not self.fused_up or self.want_depth_lowres) else None
+        _lib.check(_lib.load().ph_decode_run(self._h, C.byref(io), _lib.stream_ptr()), "ph_decode_run")
+
+    def run_from_planes(self, xp, dp, bits, k0, q0):
+        """DecodePlan.run_from_planes: planes and mask bits another kernel produced (read only; the bits are copied)"""
+        if tuple(xp.shape) != tuple(self.xp.shape) or tuple(dp.shape) != tuple(self.xp.shape) or tuple(bits.shape) != tuple(self.bits.shape):
+            raise _lib.PolyheadError("run_from_planes: planes / bits of another geometry")
+        self.handoff_runs += 1
+        B, N = self.B, self.N
+        self.graph = None
+        self._in = dict(x=xp.contiguous(), dfe=dp.contiguous(), k0=k0.reshape(B, N, 256).float().contiguous(),
+                        q0=q0.reshape(B, N, 256).float().contiguous(), m0=None, bits=bits.contiguous())
+        self._point_inputs(_lib.PH_FEAT_PLANES, bits=self._in["bits"])
+        self.run()
+
+    def capture(self):
+        """record `run` into a HIP graph (replay with `replay`); the inputs of the last `set_inputs` become plan-owned copies"""
+        if self._in is None or self._in.get("feat") != 1:
+            raise _lib.PolyheadError("capture needs set_inputs first")
+        ff = self.io.feat_format
+        self._in = dict({k: v.clone() for k, v in self._in.items() if k != "feat"}, feat=1)
+        self._point_inputs(ff)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self.run()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self.run()
+        self.graph = g
+        return g
+
+    def replay(self):
+        self.graph.replay()
+
+    def outputs(self):
+        depth = self.depth if (not self.fused_up or self.want_depth_lowres) else None
+        return dict(obj=self.obj, dobj=self.dobj, cls=self.cls, mask=self.mask, depth=depth, mask_up=self.mask_up,
+                    depth_up=self.depth_up)
+
+
 # ---- KernelHead (a1) ---------------------------------------------------------------------------------
 def _planes_of(w64, P, fp16=False):
     """float64 [..] -> int16 [P, ...] bf16 hi(/lo) planes, or ONE fp16 plane"""

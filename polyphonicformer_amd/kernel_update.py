@@ -76,13 +76,26 @@ class KernelUpdateIterHead(nn.Module):
     # API's default.  False = launch geometry tuned to the batch (bench.py's throughput legs).
     frame_invariant = True
 
+    # opt-in: the decode as ONE native call (engine.NativeDecodePlan, include/polyhead.h ph_decode_*) instead of a launch sequence
+    # issued from Python; same kernels, same geometry, same bits
+    native_plan = False
+
+    def use_native_plan(self, on=True):
+        self.native_plan = bool(on)
+        self._plans.clear()
+        return self
+
     def _plan(self, B, N, H, W, device):
         packs = [h.stage_pack(device, self.precision) for h in self.mask_head]
+        native = bool(self.native_plan)
         key = (B, N, H, W, self.precision, self.output_dtype, str(device), tuple(id(p) for p in packs), bool(self.frame_invariant), E.plan_env_key())
+        if native:
+            key += ("native",)
         plan = self._plans.get(key)
         if plan is None:
             self._plans.clear()
-            plan = E.DecodePlan(packs, B, N, H, W, E.MODES[self.precision], self.output_dtype, device, frame_invariant=bool(self.frame_invariant))
+            cls = E.NativeDecodePlan if native else E.DecodePlan
+            plan = cls(packs, B, N, H, W, E.MODES[self.precision], self.output_dtype, device, frame_invariant=bool(self.frame_invariant))
             self._plans[key] = plan
         return plan
 

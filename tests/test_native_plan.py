@@ -1,0 +1,295 @@
+"""Host-side checks of the native decode plan (include/polyhead.h ph_decode_*): the exported symbols, the struct layouts the
+ctypes side assumes, the workspace / geometry rules against engine.DecodePlan's, the pack layout against pack.py's, argument
+validation, and the Python-free example program's dependencies.  No GPU: nothing here launches a kernel."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+import torch
+
+import bench
+from polyphonicformer_amd import _lib, engine as E
+from polyphonicformer_amd import build as BLD
+from polyphonicformer_amd.pack import pack_stage
+
+NEW_SYMBOLS = ["ph_decode_param_name", "ph_decode_param_numel", "ph_decode_pack_bytes", "ph_decode_pack_layout", "ph_decode_pack_stage",
+               "ph_decode_workspace_bytes", "ph_decode_create", "ph_decode_info", "ph_decode_destroy", "ph_decode_run"]
+
+# (B, N, H, W, S, L): cfg1 (256x512 -> 32x64, N = 100, 1 stage), cfg2 / cfg3 (128x256, N = 153 / 111), cfg5 (48x156, N = 253)
+SHAPES = {"cfg1": (100, 32, 64, 1, 19), "cfg2": (153, 128, 256, 3, 133), "cfg3": (111, 128, 256, 3, 19), "cfg5": (253, 48, 156, 3, 133)}
+MODES = ["fp32", "mixed", "mixed16", "fp16", "bf16"]
+FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and never dereferences
+
+
+def _lib_loaded():
+    return _lib.load()
+
+
+def test_new_symbols_are_exported():
+    lib = _lib_loaded()
+    for name in NEW_SYMBOLS:
+        assert hasattr(lib, name), name
+        assert name in _lib.SIGNATURES, name
+
+
+def _c_layout():
+    """sizeof / offsetof of the new structs as a C compiler sees include/polyhead.h"""
+    cc = shutil.which("cc") or shutil.which("gcc") or BLD._hipcc()
+    src = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "polyhead.h"
+#define O(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
+int main(void) {
+    printf("ph_decode_cfg %zu\nph_decode_io %zu\nph_decode_geometry %zu\n", sizeof(ph_decode_cfg), sizeof(ph_decode_io), sizeof(ph_decode_geometry));
+    O(ph_decode_cfg, B); O(ph_decode_cfg, F); O(ph_decode_cfg, mode); O(ph_decode_cfg, out_dtype); O(ph_decode_cfg, frame_invariant);
+    O(ph_decode_cfg, query_full_split); O(ph_decode_cfg, shares_gpu); O(ph_decode_cfg, poolx); O(ph_decode_cfg, fused_up);
+    O(ph_decode_cfg, nsplit); O(ph_decode_cfg, nsplit_px); O(ph_decode_cfg, up2_wgs);
+    O(ph_decode_io, feat_format); O(ph_decode_io, m0_dtype); O(ph_decode_io, x); O(ph_decode_io, depth_feats); O(ph_decode_io, k0);
+    O(ph_decode_io, q0); O(ph_decode_io, m0); O(ph_decode_io, bits); O(ph_decode_io, obj); O(ph_decode_io, dobj); O(ph_decode_io, cls);
+    O(ph_decode_io, mask); O(ph_decode_io, mask_up); O(ph_decode_io, depth_up); O(ph_decode_io, depth);
+    O(ph_decode_geometry, nsplit); O(ph_decode_geometry, up2_workgroups); O(ph_decode_geometry, feat_planes);
+    return 0;
+}
+'''
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "t.c"), "w") as f:
+            f.write(src)
+        exe = os.path.join(d, "t")
+        lang = [] if os.path.basename(cc) in ("cc", "gcc") else ["-x", "c++"]
+        subprocess.run([cc] + lang + ["-I", os.path.join(BLD.HERE, "..", "include"), os.path.join(d, "t.c"), "-o", exe], check=True,
+                       capture_output=True, timeout=300)
+        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
+    return {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
+
+
+def test_struct_sizes_and_offsets_match_ctypes():
+    c = _c_layout()
+    assert c["ph_decode_cfg"] == C.sizeof(_lib.DecodeCfg)
+    assert c["ph_decode_io"] == C.sizeof(_lib.DecodeIO)
+    assert c["ph_decode_geometry"] == C.sizeof(_lib.DecodeGeometry)
+    for key, off in c.items():
+        if "." not in key:
+            continue
+        struct, field = key.split(".")
+        cls = {"ph_decode_cfg": _lib.DecodeCfg, "ph_decode_io": _lib.DecodeIO, "ph_decode_geometry": _lib.DecodeGeometry}[struct]
+        assert getattr(cls, field).offset == off, key
+
+
+def test_param_table_is_the_stage_state_dict():
+    lib = _lib_loaded()
+    wl = dict(bench.WORKLOADS["tiny"], S=1)
+    head = bench.build_head(wl, "fp32", torch.float32, "cpu")
+    sd = head.mask_head[0].state_dict()
+    names = [lib.ph_decode_param_name(i).decode() for i in range(_lib.PH_DECODE_NPARAMS)]
+    assert lib.ph_decode_param_name(_lib.PH_DECODE_NPARAMS) is None
+    assert names == list(sd.keys())
+    cfg = _lib.DecodeCfg(B=1, N=100, H=16, W=32, S=1, L=wl["n_thing"] + wl["n_stuff"], F=wl["F"], mode=0)
+    assert [lib.ph_decode_param_numel(C.byref(cfg), i) for i in range(len(names))] == [v.numel() for v in sd.values()]
+
+
+class _FakePack:
+    def __init__(self, prec, L, F=2048):
+        self.prec, self.num_classes = prec, L
+        self.lay = _lib.StageLayout(ffn_dim=F, num_classes=L)
+
+
+def _al(n):
+    return (n + 255) // 256 * 256
+
+
+def _decode_plan_bytes(p):
+    """the bytes of every buffer engine.DecodePlan allocates that the native plan keeps in its workspace: everything but the
+    inputs (x, depth_feats, k0, q0, m0) and the caller's outputs (mask, mask_up, depth_up, the last stage's obj / dobj / cls);
+    the low-resolution depth logits only where the final stage writes them (two-kernel form).  256-byte pieces."""
+    nb = lambda t: _al(t.numel() * t.element_size())
+    total = nb(p.xp) + nb(p.dp) + nb(p.bits) + nb(p.partial) + nb(p.pcount) + nb(p.ws)
+    for s, o in enumerate(p.stage_out):
+        total += nb(o["kern"]) + nb(o["kbias"])
+        if s < p.S - 1:
+            total += nb(o["obj"]) + nb(o["dobj"]) + nb(o["cls"])
+    if not p.fused_up:
+        total += nb(p.depth)
+    if p.poolx:
+        total += nb(p.partial_px) + nb(p.pcount_px)
+    return total
+
+
+def _create(cfg, S):
+    lib = _lib_loaded()
+    h = C.c_void_p()
+    rc = lib.ph_decode_create(C.byref(cfg), (C.c_void_p * S)(*([FAKE_PTR] * S)), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h))
+    return rc, h
+
+
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+@pytest.mark.parametrize("B", [1, 8, 32])
+def test_workspace_and_geometry_match_decode_plan(shape, B, monkeypatch):
+    for k in ("PH_POOL_NSPLIT", "PH_CONV_UP2", "PH_CONV_POOLX", "PH_POOLX_NSPLIT", "PH_UP2_SHARED_WGS", "PH_QUERY_FULL_SPLIT"):
+        monkeypatch.delenv(k, raising=False)
+    lib = _lib_loaded()
+    N, H, W, S, L = SHAPES[shape]
+    for mode in MODES:
+        m = E.MODES[mode]
+        for out_dtype in ((torch.float32, m.feat_dtype) if m.feat_dtype is not None else (torch.float32,)):
+            for fi in (False, True):
+                p = E.DecodePlan([_FakePack(m.query, L) for _ in range(S)], B, N, H, W, m, out_dtype, device="meta", frame_invariant=fi)
+                for shares in (False, True):
+                    cfg = E.native_cfg(B, N, H, W, S, L, 2048, m, out_dtype, fi, shares)
+                    cfg.up2_wgs = 384           # the Python plan's 1.5 per CU of a 256-CU device (no device here)
+                    what = (shape, B, mode, out_dtype, fi, shares)
+                    assert lib.ph_decode_workspace_bytes(C.byref(cfg)) == _decode_plan_bytes(p), what
+                    rc, h = _create(cfg, S)
+                    assert rc == 0, (what, lib.ph_last_error_string())
+                    g = _lib.DecodeGeometry()
+                    assert lib.ph_decode_info(h, C.byref(g)) == 0
+                    lib.ph_decode_destroy(h)
+                    assert (g.nsplit, g.nsplit_px, bool(g.poolx), bool(g.fused_up)) == (p.nsplit, p.nsplit_px, p.poolx, p.fused_up), what
+                    wg = 384 if (p.fused_up and shares and B * H >= 4 * 384) else 0
+                    assert g.up2_workgroups == wg, what
+                    assert (g.feat_prec, g.query_prec, g.conv_prec, g.kern_format, g.feat_planes) == \
+                        (m.feat, m.query, m.conv, m.kern_fmt, m.FP), what
+
+
+def test_environment_knobs_map_onto_the_cfg(monkeypatch):
+    """the switches DecodePlan reads from the environment reach the native plan as cfg fields (the native side reads none)"""
+    lib = _lib_loaded()
+    monkeypatch.setenv("PH_CONV_UP2", "1")
+    monkeypatch.setenv("PH_CONV_POOLX", "1")
+    monkeypatch.setenv("PH_POOL_NSPLIT", "3")
+    for mode in MODES:
+        m = E.MODES[mode]
+        out = {"bf16": torch.bfloat16, "mixed16": torch.float16, "fp16": torch.float16}.get(mode, torch.float32)
+        p = E.DecodePlan([_FakePack(m.query, 19) for _ in range(2)], 1, 111, 16, 256, m, out, device="meta", frame_invariant=True)
+        cfg = E.native_cfg(1, 111, 16, 256, 2, 19, 2048, m, out, True)
+        cfg.up2_wgs = 384
+        rc, h = _create(cfg, 2)
+        assert rc == 0
+        g = _lib.DecodeGeometry()
+        lib.ph_decode_info(h, C.byref(g))
+        lib.ph_decode_destroy(h)
+        assert (g.nsplit, g.nsplit_px, bool(g.poolx), bool(g.fused_up)) == (p.nsplit, p.nsplit_px, p.poolx, p.fused_up) == \
+            (3, 3, m.conv in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16), m.KP == 1), mode
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_pack_layout_is_pack_py_layout(mode):
+    lib = _lib_loaded()
+    wl = dict(bench.WORKLOADS["tiny"], S=1)
+    head = bench.build_head(wl, mode, torch.float32, "cpu")
+    sd = {k: v.detach() for k, v in head.mask_head[0].state_dict().items()}
+    L = wl["n_thing"] + wl["n_stuff"]
+    m = E.MODES[mode]
+    wb, wf, lay = pack_stage(sd, "", L, m.query)
+    cfg = E.native_cfg(1, 100, 16, 32, 1, L, wl["F"], m)
+    nlay, off = _lib.StageLayout(), C.c_size_t()
+    assert lib.ph_decode_pack_layout(C.byref(cfg), C.byref(nlay), C.byref(off)) == 0
+    assert bytes(nlay) == bytes(lay)
+    assert off.value == _al(wb.numel() * 2)
+    assert lib.ph_decode_pack_bytes(C.byref(cfg)) == off.value + _al(wf.numel() * 4)
+
+
+def _msg():
+    return _lib_loaded().ph_last_error_string().decode()
+
+
+def test_errors_are_returned_before_anything_is_launched():
+    lib = _lib_loaded()
+    base = dict(B=1, N=111, H=128, W=256, S=3, L=19, F=2048, mode=_lib.PH_MODE["fp16"], out_dtype=_lib.PH_OUT_F16, up2_wgs=384)
+    # geometry the query / pooling kernels refuse
+    cfg = _lib.DecodeCfg(**dict(base, N=300))
+    assert lib.ph_decode_workspace_bytes(C.byref(cfg)) == 0 and "at most 256 queries" in _msg()
+    assert _create(cfg, 3)[0] == -2
+    cfg = _lib.DecodeCfg(**dict(base, F=1000))
+    assert _create(cfg, 3)[0] == -1 and "multiple of 256" in _msg()
+    # a fused form asked for where its kernel cannot run: PH_EUNSUPPORTED (the Python plan would fall back; the native one says so)
+    cfg = _lib.DecodeCfg(**dict(base, W=200, fused_up=_lib.PH_KNOB_ON))
+    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_up2" in _msg()
+    assert lib.ph_dynconv_up2_supported(111, 128, 200, _lib.PH_PREC_F16, _lib.PH_OUT_F16) == 0
+    cfg = _lib.DecodeCfg(**dict(base, N=200, poolx=_lib.PH_KNOB_ON))
+    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_poolx" in _msg()
+    assert lib.ph_dynconv_poolx_supported(200, _lib.PH_PREC_F16) == 0
+    cfg = _lib.DecodeCfg(**dict(base, S=1, poolx=_lib.PH_KNOB_ON))
+    assert _create(cfg, 1)[0] == -2
+    # the same requests "where supported" are no error
+    cfg = _lib.DecodeCfg(**dict(base, W=200, fused_up=_lib.PH_KNOB_WHERE_SUPPORTED))
+    assert _create(cfg, 3)[0] == 0
+    # too small a workspace
+    cfg = _lib.DecodeCfg(**base)
+    need = lib.ph_decode_workspace_bytes(C.byref(cfg))
+    h = C.c_void_p()
+    rc = lib.ph_decode_create(C.byref(cfg), (C.c_void_p * 3)(*([FAKE_PTR] * 3)), C.c_void_p(FAKE_PTR), need - 256, C.byref(h))
+    assert rc == -4 and "workspace too small" in _msg() and not h.value
+    # run-time arguments: in a child process that sees no GPU (_RUN_CHECKS), so that a validation that ever stopped returning
+    # before the first launch fails on the host instead of launching a kernel on the fake addresses
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _RUN_CHECKS], cwd=os.path.dirname(BLD.HERE), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "run checks ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+
+
+_RUN_CHECKS = r"""
+import ctypes as C, sys
+sys.path.insert(0, ".")
+import torch
+from polyphonicformer_amd import _lib
+assert torch.cuda.device_count() == 0, "the run-time argument checks need a process without a visible GPU"
+lib = _lib.load()
+FAKE = 1 << 40
+def create(**kw):
+    cfg = _lib.DecodeCfg(**dict(dict(B=1, N=111, H=128, W=256, S=3, L=19, F=2048, mode=_lib.PH_MODE["fp16"], out_dtype=_lib.PH_OUT_F16,
+                                     up2_wgs=384), **kw))
+    h = C.c_void_p()
+    assert lib.ph_decode_create(C.byref(cfg), (C.c_void_p * 3)(*([FAKE] * 3)), C.c_void_p(FAKE), 1 << 62, C.byref(h)) == 0
+    return h
+msg = lambda: lib.ph_last_error_string().decode()
+h = create()
+io = _lib.DecodeIO(feat_format=_lib.PH_FEAT_F32, x=FAKE, depth_feats=FAKE, k0=FAKE, q0=FAKE, m0=FAKE, obj=FAKE, dobj=FAKE, cls=FAKE,
+                   mask=FAKE, mask_up=FAKE, depth_up=None)
+assert lib.ph_decode_run(h, C.byref(io), None) == -1 and "null input or output" in msg()
+io.depth_up, io.feat_format = FAKE, 7
+assert lib.ph_decode_run(h, C.byref(io), None) == -1 and "feat_format" in msg()
+io.feat_format, io.bits = _lib.PH_FEAT_PLANES, None
+assert lib.ph_decode_run(h, C.byref(io), None) == -1 and "bits" in msg()
+io.feat_format, io.m0_dtype = _lib.PH_FEAT_F32, 9
+assert lib.ph_decode_run(h, C.byref(io), None) == -1 and "m0_dtype" in msg()
+lib.ph_decode_destroy(h)
+h = create(mode=_lib.PH_MODE["fp32"], out_dtype=_lib.PH_OUT_F32)
+io.feat_format, io.m0_dtype = _lib.PH_FEAT_16, _lib.PH_OUT_F32
+assert lib.ph_decode_run(h, C.byref(io), None) == -1 and "16-bit feature inputs" in msg()
+lib.ph_decode_destroy(h)
+print("run checks ok")
+"""
+
+
+def _elf_needed(path):
+    """DT_NEEDED entries of an ELF64 little-endian file (the dynamic section and its string table)"""
+    import struct
+    with open(path, "rb") as f:
+        d = f.read()
+    assert d[:4] == b"\x7fELF" and d[4] == 2 and d[5] == 1
+    shoff, = struct.unpack_from("<Q", d, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
+    sec = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
+    out = []
+    for name, typ, flags, addr, off, size, link, info, align, entsize in sec:
+        if typ != 6:                                     # SHT_DYNAMIC
+            continue
+        stroff = sec[link][4]
+        for o in range(off, off + size, 16):
+            tag, val = struct.unpack_from("<qQ", d, o)
+            if tag == 1:                                 # DT_NEEDED
+                out.append(d[stroff + val:d.index(b"\0", stroff + val)].decode())
+    return out
+
+
+def test_example_program_links_no_python():
+    """the C++ caller is built next to the library and depends on libpolyhead.so and the HIP runtime only"""
+    assert os.path.exists(BLD.EXAMPLE), "built by python -m polyphonicformer_amd.build"
+    needed = _elf_needed(BLD.EXAMPLE)
+    assert "libpolyhead.so" in needed and any(n.startswith("libamdhip64") for n in needed)
+    assert not any("python" in n or "torch" in n or "c10" in n for n in needed), needed
