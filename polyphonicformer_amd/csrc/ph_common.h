@@ -44,16 +44,12 @@ void ph_set_error(const char* fmt, ...);
 // the native decode plan (ph_decode.hip) passes the defaults explicitly and so reads no environment at all.
 struct PhConvKnobs {
     int wgs = 0;                 // PH_CONV_WGS: workgroups (0 = one per CU)
-    bool two_halves = false;     // PH_CONV_TWO_HALVES=1
-    bool coop = true;            // PH_CONV_COOP=0 -> false
 };
 struct PhUp2Knobs {
     int wgs = 0;                 // PH_UP2_WGS: overrides the caller's workgroup count (0 = keep it)
-    bool mfma = true;            // PH_UP2_MFMA=0 -> false (the window-pass kernel)
     int dbg = 0;                 // PH_UP2_DBG (timing experiments)
 };
 struct PhQueryKnobs {
-    bool v1 = false;                         // PH_QUERY_V1=1: first-generation kernels
     int nrt = 0;                             // PH_QUERY_NRT: row blocks per workgroup (0 = the launch's own choice)
     unsigned long long* timeline = nullptr;  // PH_QUERY_TIMELINE=1: phase times of one workgroup (debug; synchronises)
 };
@@ -89,7 +85,7 @@ __device__ __forceinline__ uint32_t pack2(uint32_t a, uint32_t b) { return a | (
 // ---- 16-bit element formats of feature planes / dynamic kernels / outputs: bf16 (8-bit mantissa, fp32 range) or IEEE
 // fp16 (11-bit mantissa, |x| < 65504).  A bf16 value is exactly representable in fp16 when it is inside fp16's normal
 // range, so an fp16 plane carries bf16-rounded inputs unchanged and fp32 inputs with 8x finer rounding.
-enum { PH_E_BF16 = 0, PH_E_F16 = 1, PH_E_F16_FROM_BF16 = 2 /* conv only: bf16 feature fragments converted to fp16 in registers */ };
+enum { PH_E_BF16 = 0, PH_E_F16 = 1, PH_E_F16_FROM_BF16 = 2 /* conv only: bf16 feature tile converted to fp16 in LDS */ };
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t f2h(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }

@@ -23,14 +23,14 @@ constexpr int conv_dma_waves(int nw, int pieces) {
 // 32-pixel half of the tile) and owns the whole LDS of its CU: a ring of NBUF tile buffers, NBUF-1 tiles of DMA
 // in flight while one is consumed (96 KiB at cfg2), plus -- logits output, single-plane precision -- a per-wave
 // transposition patch.
-template <int PF, int PK, int NRT, bool BITS, typename OutT, bool F2 = false> struct ConvCfg {
+template <int PF, int PK, int NRT, bool BITS, typename OutT> struct ConvCfg {
     // 32-pixel halves per wave: one (two waves per row block) while that keeps <= 3 waves per SIMD (168 VGPRs for
     // the 64-VGPR A operand + fragments); two for wide N.  Two kernel planes over one feature plane (A operand = 128
     // VGPRs, the `mixed` mode): a wave that walks both halves is a serial chain of 2 x 16 k-steps with nothing else on its
     // SIMD (113 us per 24 frames whether it has 2, 3 or 4 row blocks); one half per wave fits 2 waves per SIMD up to 4
     // row blocks (86 / 95 / 103 us) and, for the bits output, 3 waves per SIMD at 5-6 row blocks (131 -> 120 us at cfg2;
     // the logits variants would spill 40+ VGPRs there and stay on two halves per wave)
-    static constexpr int HPW = (PK == 1 && NRT <= 6) || (!F2 && PF == 1 && PK == 2 && (NRT <= 4 || (BITS && NRT <= 6))) ? 1 : 2;
+    static constexpr int HPW = (PK == 1 && NRT <= 6) || (PF == 1 && PK == 2 && (NRT <= 4 || (BITS && NRT <= 6))) ? 1 : 2;
     static constexpr int NW = 2 * NRT / HPW;
     static constexpr int TILE = 256 * CONV_T;                                  // elements per plane per buffer
     static constexpr int TILEB = PF * TILE * 2;                                // bytes per ring stage
@@ -49,17 +49,18 @@ template <int PF, int PK, int NRT, bool BITS, typename OutT, bool F2 = false> st
     static constexpr int LDSB = NBUF * TILEB + PATCHB + KBB;
 };
 
-// COOP (E = PH_E_F16_FROM_BF16 only): the landed bf16 tile is converted to fp16 ONCE, in place in LDS, every wave taking a
-// share of its 16-byte pieces, instead of by each of the NRT row-block waves on its own fragments (NRT x the VALU work);
-// costs one more barrier and one LDS round trip of the tile per tile.
-template <int PF, int PK, int E, int NRT, bool BITS, typename OutT, bool F2 = false, bool COOP = false>
-__global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT, F2>::NW * 64)) void k_dynconv(const uint16_t* __restrict__ planes,
+// E = PH_E_F16_FROM_BF16 (one bf16 feature plane): the landed tile is converted to fp16 ONCE, in place in LDS, every wave
+// taking a share of its 16-byte pieces, instead of by each of the NRT row-block waves on its own fragments (NRT x the VALU
+// work); costs one more barrier and one LDS round trip of the tile per tile.  Against the per-wave form (removed; `git show
+// 5b19cf6` has it), same box, 24 frames: bits 155 -> 130-136 us, logits 157-162 -> 148-151 us; results identical.
+template <int PF, int PK, int E, int NRT, bool BITS, typename OutT>
+__global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT>::NW * 64)) void k_dynconv(const uint16_t* __restrict__ planes,
                                                           const uint16_t* __restrict__ kern, int64_t kern_plane_stride,
                                                           int64_t kern_batch_stride, const float* __restrict__ kbias,
                                                           int64_t kbias_batch_stride, uint32_t* __restrict__ bits_out,
                                                           OutT* __restrict__ logits_out, int64_t out_batch_stride, int B,
                                                           int N, int64_t HW, int64_t HWp) {
-    using C = ConvCfg<PF, PK, NRT, BITS, OutT, F2>;
+    using C = ConvCfg<PF, PK, NRT, BITS, OutT>;
     constexpr int Npad = NRT * 32, TILE = C::TILE, NBUF = C::NBUF;
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];   // [NBUF][PF][256][64] | patch[NW][32][PATCH_LD]
 
@@ -214,8 +215,8 @@ __global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT, F2>::NW * 64)) vo
             issue_next(nb);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (COOP) {
-            static_assert(PF == 1 && E == PH_E_F16_FROM_BF16, "cooperative conversion: one bf16 feature plane");
+        if constexpr (E == PH_E_F16_FROM_BF16) {
+            static_assert(PF == 1, "cooperative conversion: one bf16 feature plane");
             constexpr int PIECES = 256 * CONV_T * 2 / 16, LANES = C::NW * 64, ROUNDS = (PIECES + LANES - 1) / LANES;
             const uint32_t tb = lds0 + cur * C::TILEB + 16u * (uint32_t)tid;
             u32x4_t cv[ROUNDS];
@@ -246,7 +247,7 @@ __global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT, F2>::NW * 64)) vo
         constexpr int KB = 2;                        // 4 * PF reads per batch (KB = 4 measured 7 % slower)
         u32x2_t bq[2][PF][KB][2];
         conv_read_batch<PF, KB, 0>(fa, bq[0]);
-        conv_batches<PF, PK, E, KB, 0, COOP>(fa, af, bq, acc, bias);
+        conv_batches<PF, PK, E, KB, 0>(fa, af, bq, acc, bias);
         // ---- epilogue of tile (b, t), 32-pixel half `half`
         const int px_base = t * CONV_T + half * 32;
         const int64_t px = (int64_t)px_base + (lane & 31);
@@ -334,47 +335,24 @@ static int launch_conv(const uint16_t* planes, const uint16_t* kern, int64_t kps
     if (wgs > total) wgs = (int)total;
     if (wgs < 1) wgs = 1;
     const dim3 grid(wgs);
-    // kn.two_halves forces the two-halves-per-wave form of the two-kernel-plane kernels (A/B measurements)
-    const bool two_halves = kn.two_halves;
-    // the mixed16 conv converts its bf16 tile to fp16 once per tile in LDS (see k_dynconv); kn.coop = false restores the
-    // per-wave conversion in registers for A/B measurements (same box, 24 frames: bits 155 -> 130-136 us, logits 157-162 ->
-    // 148-151 us, the 96-frame step 13.16 k -> 13.53 k frames/s; results identical, the conversion is exact either way)
-    const bool coop = kn.coop;
-    (void)coop;
-#define PH_CONV_LAUNCH__(BITS, T, F2, CO)                                                                            \
+#define PH_CONV_LAUNCH(BITS, T)                                                                                      \
     do {                                                                                                             \
-        constexpr int lds = ConvCfg<PF, PK, NRT, BITS, T, F2>::LDSB;                                                 \
-        const dim3 block(ConvCfg<PF, PK, NRT, BITS, T, F2>::NW * 64);                                                \
+        constexpr int lds = ConvCfg<PF, PK, NRT, BITS, T>::LDSB;                                                     \
+        const dim3 block(ConvCfg<PF, PK, NRT, BITS, T>::NW * 64);                                                    \
         static const bool once = [&] {                                                                               \
-            (void)hipFuncSetAttribute((const void*)k_dynconv<PF, PK, E, NRT, BITS, T, F2, CO>,                       \
+            (void)hipFuncSetAttribute((const void*)k_dynconv<PF, PK, E, NRT, BITS, T>,                               \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);                              \
             return true;                                                                                             \
         }();                                                                                                         \
         (void)once;                                                                                                  \
-        hipLaunchKernelGGL((k_dynconv<PF, PK, E, NRT, BITS, T, F2, CO>), grid, block, lds, s, planes, kern, kps, kbs, kbias, bbs, \
+        hipLaunchKernelGGL((k_dynconv<PF, PK, E, NRT, BITS, T>), grid, block, lds, s, planes, kern, kps, kbs, kbias, bbs, \
                            bits_out, (T*)logits_out, obs, B, N, HW, HWp);                                            \
-    } while (0)
-#define PH_CONV_LAUNCH_(BITS, T, F2)                                                                                 \
-    do {                                                                                                             \
-        if constexpr (E == PH_E_F16_FROM_BF16 && PF == 1) {                                                          \
-            if (coop) PH_CONV_LAUNCH__(BITS, T, F2, true);                                                           \
-            else PH_CONV_LAUNCH__(BITS, T, F2, false);                                                               \
-        } else PH_CONV_LAUNCH__(BITS, T, F2, false);                                                                 \
-    } while (0)
-#define PH_CONV_LAUNCH(BITS, T)                                                                                      \
-    do {                                                                                                             \
-        if constexpr (PF == 1 && PK == 2) {                                                                          \
-            if (two_halves) PH_CONV_LAUNCH_(BITS, T, true);                                                          \
-            else PH_CONV_LAUNCH_(BITS, T, false);                                                                    \
-        } else PH_CONV_LAUNCH_(BITS, T, false);                                                                      \
     } while (0)
     if (bits_out) PH_CONV_LAUNCH(true, float);
     else if (out_dtype == PH_OUT_F32) PH_CONV_LAUNCH(false, float);
     else if (out_dtype == PH_OUT_F16) PH_CONV_LAUNCH(false, ph_h16);
     else PH_CONV_LAUNCH(false, uint16_t);
 #undef PH_CONV_LAUNCH
-#undef PH_CONV_LAUNCH_
-#undef PH_CONV_LAUNCH__
     return 0;
 }
 
@@ -410,13 +388,11 @@ int ph_dynconv_k(const PhConvKnobs& kn, const uint16_t* planes, const uint16_t* 
     return PH_OK;
 }
 
-// tuning knobs, read once per process: PH_CONV_WGS, PH_CONV_TWO_HALVES=1, PH_CONV_COOP=0 (A/B measurements)
+// tuning knob, read once per process: PH_CONV_WGS (A/B measurements)
 static const PhConvKnobs& conv_env_knobs() {
     static const PhConvKnobs k = [] {
         PhConvKnobs r;
         if (const char* e = getenv("PH_CONV_WGS")) r.wgs = atoi(e);
-        if (const char* e = getenv("PH_CONV_TWO_HALVES")) r.two_halves = atoi(e) != 0;
-        if (const char* e = getenv("PH_CONV_COOP")) r.coop = atoi(e) != 0;
         return r;
     }();
     return k;

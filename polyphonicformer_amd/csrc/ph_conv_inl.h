@@ -1,4 +1,4 @@
-// Device helpers shared by the dynamic-convolution kernels (ph_conv.hip: k_dynconv; ph_convup.hip: k_dynconv_up2): the LDS
+// Device helpers shared by the dynamic-convolution kernels (ph_conv.hip: k_dynconv; ph_convup.hip: k_dynconv_up2m): the LDS
 // accesses of the tile loop as inline asm, the swizzle of the LDS-DMA tile image, the MFMA phase of one 32-pixel half.
 #pragma once
 #include "ph_common.h"
@@ -65,8 +65,9 @@ __device__ __forceinline__ void conv_read_batch(uint32_t fa, u32x2_t (&dst)[PF][
 }
 
 // PF feature planes x PK kernel planes: (1,1) a.b; (1,2) (a_hi + a_lo).b; (2,2) a_hi.b_hi + a_hi.b_lo + a_lo.b_hi
+// E = PH_E_F16_FROM_BF16: the tile has been converted to fp16 in LDS already (fp16 MFMAs on the fragments as read)
 // SWAP (one plane each): the operands exchanged -- D'[pixel][query], the transposed product (ph_convup.hip: k_dynconv_up2m)
-template <int PF, int PK, int E, int KB, int BI, bool COOP = false, bool SWAP = false>
+template <int PF, int PK, int E, int KB, int BI, bool SWAP = false>
 __device__ __forceinline__ void conv_batches(uint32_t fa, const uint4 (&af)[PK][16], u32x2_t (&bq)[2][PF][KB][2], f32x16_t& acc,
                                              const float (&bias)[16]) {
     constexpr int NBATCH = 16 / KB;
@@ -87,10 +88,7 @@ __device__ __forceinline__ void conv_batches(uint32_t fa, const uint4 (&af)[PK][
             uint4 bf[PF];
 #pragma unroll
             for (int p = 0; p < PF; ++p)
-            {
                 bf[p] = make_uint4(bq[BI & 1][p][k][0].x, bq[BI & 1][p][k][0].y, bq[BI & 1][p][k][1].x, bq[BI & 1][p][k][1].y);
-                if constexpr (E == PH_E_F16_FROM_BF16 && !COOP) bf[p] = bf2h_x8(bf[p]);      // 12 VALU ops under the previous MFMA
-            }
             if constexpr (SWAP) {
                 static_assert(!SWAP || (PF == 1 && PK == 1), "transposed product: one plane each");
                 acc = mfma32e<E>(bf[0], af[0][BI * KB + k], acc);
@@ -100,7 +98,7 @@ __device__ __forceinline__ void conv_batches(uint32_t fa, const uint4 (&af)[PK][
             if (PK == 2) acc = mfma32e<E>(af[PK - 1][BI * KB + k], bf[0], acc);
         }
         __builtin_amdgcn_sched_barrier(0);
-        conv_batches<PF, PK, E, KB, BI + 1, COOP, SWAP>(fa, af, bq, acc, bias);
+        conv_batches<PF, PK, E, KB, BI + 1, SWAP>(fa, af, bq, acc, bias);
     }
 }
 
