@@ -91,18 +91,29 @@ def test_cfg2_identical_16bit_inputs(gpu, precision):
     _teacher_forced(head, sd, CFG2, inp, gpu, TOL_IDENT[precision], feats_dtype=PLANE_DT[precision])   # 16-bit NCHW = planes
 
 
-@pytest.mark.parametrize("precision,out_dtype", [("mixed", torch.float16), ("mixed16", torch.float16), ("fp16", torch.float16), ("mixed", torch.float32)])
-def test_cfg2_headline_function_identical_inputs(gpu, monkeypatch, precision, out_dtype):
+@pytest.mark.parametrize("precision,out_dtype,poolx", [
+    pytest.param("mixed", torch.float16, "auto", id="mixed-out_dtype0"),
+    pytest.param("mixed16", torch.float16, "auto", id="mixed16-out_dtype1"),
+    pytest.param("fp16", torch.float16, "auto", id="fp16-out_dtype2"),
+    pytest.param("mixed", torch.float32, "auto", id="mixed-out_dtype3"),
+    # the bench's parts run the fused conv + pooling of x between the stages (k_dynconv_poolx); one frame only reaches it forced
+    pytest.param("mixed16", torch.float16, "1", id="mixed16-out_dtype1-poolx"),
+    pytest.param("fp16", torch.float16, "1", id="fp16-out_dtype2-poolx")])
+def test_cfg2_headline_function_identical_inputs(gpu, monkeypatch, precision, out_dtype, poolx):
     """`simple_test_mask_preds` itself (what bench.py times), S = 3 free running, in the modes that claim 1e-3: 16-bit
     feature tensors in (as the bench hands them), 16-bit logits out; the oracle gets the same rounded features.  Free
     running through three hard thresholds, a logit within rounding of the threshold flips a pixel and moves a whole
     feature vector (the parity contract is per stage, teacher forced -- the tests above); here the flip rate
     is the bounded quantity (measured: fp32 mode 1.5e-4 at cfg5, 'mixed' 1.2e-4, 'fp16' 9e-4 at cfg2), 1e-3 is
-    asserted whenever no pixel flipped."""
+    asserted whenever no pixel flipped.  `poolx` "1": the stage boundaries through ph_dynconv_poolx, as in the bench's parts."""
     wl = CFG2
     # the bench's launches: at 24 frames per part the final stage is the fused conv + x2 upsample kernel (chosen from B * H >= 512);
     # forced here so that ONE frame takes the same kernels
     monkeypatch.setenv("PH_CONV_UP2", "1")
+    if poolx == "auto":
+        monkeypatch.delenv("PH_CONV_POOLX", raising=False)
+    else:
+        monkeypatch.setenv("PH_CONV_POOLX", poolx)
     head, sd = _head_and_sd(wl, precision, gpu, out_dtype=out_dtype)
     inp = bench.synth_inputs(wl, 1, seed=15)
     rd = PLANE_DT[precision]
@@ -120,6 +131,7 @@ def test_cfg2_headline_function_identical_inputs(gpu, monkeypatch, precision, ou
     assert mask.dtype == out_dtype and mask_up.dtype == out_dtype and mask_up.shape == (1, N, 256, 512)
     plan = next(iter(head._plans.values()))
     assert plan.fused_up == (precision in ("mixed16", "fp16") and out_dtype == torch.float16)      # `mixed` has two kernel planes
+    assert plan.poolx == (poolx == "1")          # auto: one frame has too few pixel ranges for the fused pooling (B * nsplit_px < 192)
     flips = ((mask.float().cpu() > 0) != (ref["mask"] > 0)).float().mean().item()
     e = {n: Hh.rel_err(t.float().cpu(), r) for n, t, r in (("obj", obj.reshape(1, N, 256), ref["obj"]), ("cls", cls, ref["cls"]),
                                                             ("mask", mask, ref["mask"]), ("mask_up", mask_up, ref["mask_up"]),

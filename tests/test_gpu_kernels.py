@@ -418,24 +418,49 @@ def test_dynconv_up2_inside_the_decode_plan(gpu, monkeypatch):
 def test_dynconv_poolx_inside_the_decode_plan(gpu, monkeypatch, precision):
     """the S-stage plan at cfg2's map size with and without the fused conv + pooling (PH_CONV_POOLX=0), 8 frames, 3 stages: the pooled
     x sums of stages 1, 2 differ by fp32 summation order (another pixel split) -- the first stage's outputs, which do not depend on
-    them, are bit-identical; everything after agrees at the grade's own rounding level (a mask bit next to the threshold may flip)"""
+    them, are bit-identical; everything after agrees at the grade's own rounding level (a mask bit next to the threshold may flip).
+    Each form on its own is also held to the grade's contract: frames 0 and 7 against the oracle on the same 16-bit-rounded features,
+    following the hard masks that form pooled with (1e-3 and the element-wise criterion of tests/test_gpu_configs.py)"""
     import bench
+    from oracle import poly_oracle as O
+    from test_gpu_configs import ATOL_FRAC_FREE
     wl = dict(H=128, W=256, Nq=100, n_thing=8, n_stuff=11, S=3, F=2048)
     N = wl["Nq"] + wl["n_stuff"]
     B = 8
     inp = bench.synth_inputs(wl, B, seed=8)
-    outs, stage0, stage1 = {}, {}, {}
+    outs, stage0, stage1, oracle_errs = {}, {}, {}, {}
     for fused in ("1", "0"):
         monkeypatch.setenv("PH_CONV_POOLX", fused)
         head = bench.build_head(wl, precision, torch.float16, gpu, seed=4)
         plan = head._plan(B, N, wl["H"], wl["W"], gpu)
         assert plan.poolx == (fused == "1")
         plan.set_inputs(*[inp[k].to(gpu) for k in ("x", "dfe", "k0", "q0", "m0")])
+        plan.debug_bits = []
         plan.run()
         torch.cuda.synchronize()
+        dev_bits, plan.debug_bits = plan.debug_bits, None
         outs[fused] = {k: (None if v is None else v.clone()) for k, v in plan.outputs().items()}
         stage0[fused] = {k: v.clone() for k, v in plan.stage_out[0].items()}
         stage1[fused] = {k: v.clone() for k, v in plan.stage_out[1].items()}
+        sd = {k: v.detach().cpu() for k, v in head.state_dict().items()}
+        rd = plan.mode.feat_dtype                      # the fp32 features went through the ingest kernel into these planes
+        for f in (0, B - 1):
+            hard = Hh.unpack_hard_masks([b[f:f + 1] for b in dev_bits], N, wl["H"], wl["W"])
+            ref = O.iter_head_mask_preds(sd, wl["S"], inp["x"][f:f + 1].to(rd).float(), inp["k0"][f:f + 1], inp["m0"][f:f + 1],
+                                         inp["q0"][f:f + 1], inp["dfe"][f:f + 1].to(rd).float(), hard_masks=hard)
+            o = outs[fused]
+            for k in ("obj", "cls", "mask", "mask_up", "depth_up"):
+                got, want = o[k][f:f + 1].float().cpu(), ref[k]
+                oracle_errs[(fused, f, k)] = (Hh.rel_err(got, want), Hh.needed_atol(got, want, 1e-3))
+    print("vs the oracle on each form's hard masks (rel err, needed atol):",
+          {f"poolx={a}/f{f}/{k}": f"{e:.1e},{t:.1e}" for (a, f, k), (e, t) in oracle_errs.items()})
+    # the upsampled fp16 logits are rounded twice: the low-resolution logits they blend are fp16 already (the reference upsamples
+    # its own output tensor), so their max-normalised bound carries one more rounding of the output format (2^-11 of the maximum);
+    # both forms measure 0.75e-3 .. 1.2e-3 there, against <= 0.71e-3 on the low-resolution logits.  The element-wise criterion
+    # holds every output, the upsampled ones included, to 0.95e-3.
+    for (a, f, k), (e, t) in oracle_errs.items():
+        assert e < (1e-3 + 2.0 ** -11 if k.endswith("_up") else 1e-3), (a, f, k, e)
+        assert t < ATOL_FRAC_FREE * 1e-3, (a, f, k, t)
     for k in stage0["1"]:
         assert torch.equal(stage0["1"][k], stage0["0"][k]), k
     # stage 1 has seen ONE fused boundary: its pooled x sums differ in the last fp32 bits, which may move a 16-bit rounding of a dynamic
@@ -448,3 +473,160 @@ def test_dynconv_poolx_inside_the_decode_plan(gpu, monkeypatch, precision):
     assert all(e < 5e-3 for k, e in errs.items() if not k.startswith("final_")), errs
     assert all(e < 3e-2 for e in errs.values()), errs
     assert flips["mask_up"] < 5e-3, flips
+
+
+# ---- the query kernels' row tilings (ph_query.hip launch_query2<PA, NRT[, hybrid]>) -------------------------------------------------
+# One pack per query precision, from a stage of a head in the mode that uses it: bf16 (`bf16`), split (`fp32`), hybrid (`mixed16`).
+# N reaches every wide form: Npad / 16 = 10 -> 5 row tiles (153), 8 and 16 -> 4 (111, 253), 6 -> 3 (90), 4 -> 4 (40).
+QUERY_MODES = ["bf16", "fp32", "mixed16"]
+QUERY_NS = [153, 111, 253, 90, 40]
+_query_heads = {}
+
+
+def _query_head(mode, gpu):
+    """a one-stage head with cfg2's classes in `mode` (the query kernels and the plans take N at run time)"""
+    import bench
+    if mode not in _query_heads:
+        wl = dict(H=16, W=32, Nq=100, n_thing=80, n_stuff=53, S=1, F=2048)
+        _query_heads[mode] = bench.build_head(wl, mode, torch.float32, gpu, seed=17)
+    return _query_heads[mode]
+
+
+def _query_inputs(mode, B, N, gpu, seed, H=16, W=32, nsplit=3):
+    """pooled sums, pixel counts and mask bits as the plan's ph_pool_counts leaves them, and the stage's k / q inputs"""
+    m = E.MODES[mode]
+    g = torch.Generator(device=gpu)
+    g.manual_seed(seed)
+    HW = H * W
+    xp = E.ingest(torch.randn((B, 256, H, W), generator=g, device=gpu), m.feat)
+    dp = E.ingest(torch.randn((B, 256, H, W), generator=g, device=gpu), m.feat)
+    bits = E.binarize(torch.randn((B, N, H, W), generator=g, device=gpu))
+    Npad = E.n_padded(N)
+    partial = torch.zeros((B, nsplit, Npad, 512), dtype=torch.float32, device=gpu)
+    counts = torch.zeros((B, nsplit, Npad), dtype=torch.int32, device=gpu)
+    E.pool(xp, dp, bits, N, HW, m.feat, nsplit, out=partial, counts=counts)
+    k = torch.randn((B, N, 256), generator=g, device=gpu)
+    q = torch.randn((B, N, 256), generator=g, device=gpu)
+    return dict(partial=partial, counts=counts, bits=bits, k=k, q=q, HW=HW)
+
+
+def _query_run(pack, mode, inp, N, wide, frames=None):
+    """ph_query_stage_counts with the default row tiling or PH_QUERY_WIDE; `frames`: a subset of the batch as its own launch"""
+    sel = (lambda t: t) if frames is None else (lambda t: t[frames].contiguous())
+    phases = 3 | (_lib.PH_QUERY_WIDE if wide else 0)             # PH_QUERY_PRE | PH_QUERY_POST [| PH_QUERY_WIDE]
+    o = E.query_stage(sel(inp["partial"]), sel(inp["bits"]), sel(inp["k"]), sel(inp["q"]), pack, N, inp["HW"], cls_sigmoid=True,
+                      phases=phases, kern_fmt=E.MODES[mode].kern_fmt, counts=sel(inp["counts"]))
+    # the rows the next launches read: kern / kbias padding rows (>= N) are never consumed
+    return dict(obj=o["obj"], dobj=o["dobj"], cls=o["cls"], kern=o["kern"][:, :, :, :N], kbias=o["kbias"][:, :, :N])
+
+
+@pytest.mark.parametrize("mode", QUERY_MODES)
+@pytest.mark.parametrize("N", QUERY_NS)
+@pytest.mark.parametrize("B", [1, 3])
+def test_query_wide_row_tilings_bit_identical(gpu, mode, N, B):
+    """the PH_QUERY_WIDE launch (5, 4 or 3 row tiles of 16 per workgroup: what every part of the bench's multi-stream step runs)
+    against the default one (2 row tiles at these batches) on the same pooled sums, bits, counts and pack: a row's arithmetic does
+    not depend on how many rows share its workgroup, so obj, dobj, cls and the dynamic kernels agree bit for bit"""
+    pack = _query_head(mode, gpu).mask_head[0].stage_pack(gpu)
+    assert pack.prec == E.MODES[mode].query
+    inp = _query_inputs(mode, B, N, gpu, seed=100 + N + B)
+    a = _query_run(pack, mode, inp, N, wide=False)
+    b = _query_run(pack, mode, inp, N, wide=True)
+    torch.cuda.synchronize()
+    for k in ("obj", "dobj", "cls", "kbias"):
+        assert bool(torch.isfinite(a[k]).all()), k
+    for k in a:
+        assert torch.equal(a[k], b[k]), (mode, N, B, k)
+
+
+@pytest.mark.parametrize("mode", QUERY_MODES)
+def test_query_default_rule_wide_batch(gpu, mode):
+    """a batch large enough for the default rule itself to pick 5 row tiles (N = 153, B = 50: 50 x 2 x 2 >= 200 workgroups)
+    against a 3-frame launch of three of its frames (2 row tiles by default, 5 wide): the same bits"""
+    N, B = 153, 50
+    pack = _query_head(mode, gpu).mask_head[0].stage_pack(gpu)
+    inp = _query_inputs(mode, B, N, gpu, seed=7)
+    big = _query_run(pack, mode, inp, N, wide=False)
+    frames = torch.tensor([0, 1, B - 1], device=gpu)
+    small = _query_run(pack, mode, inp, N, wide=False, frames=frames)
+    small_wide = _query_run(pack, mode, inp, N, wide=True, frames=frames)
+    torch.cuda.synchronize()
+    for k in big:
+        fd = {"kern": 2, "kbias": 1}.get(k, 0)                   # kern [P, 2, B, N, 256], kbias [2, B, N]
+        assert torch.equal(big[k].index_select(fd, frames), small[k]), (mode, k)
+        assert torch.equal(small_wide[k], small[k]), (mode, k)
+
+
+@pytest.mark.parametrize("mode", QUERY_MODES)
+@pytest.mark.parametrize("N", QUERY_NS)
+def test_query_wide_forms_vs_oracle(gpu, mode, N):
+    """each wide form directly against the oracle: a one-stage DecodePlan marked `shares_gpu` (PH_QUERY_WIDE, as in the bench's
+    parts) on a 16 x 32 map, two frames, on the same 16-bit-rounded features, at the mode's identical-input tolerance and the
+    element-wise criterion of tests/test_gpu_configs.py"""
+    from oracle import poly_oracle as O
+    from test_gpu_configs import ATOL_FRAC, TOL_IDENT
+    import bench
+    head = _query_head(mode, gpu)
+    B, H, W = 2, 16, 32
+    plan = head._plan(B, N, H, W, gpu)
+    plan.shares_gpu = True
+    inp = bench.synth_inputs(dict(H=H, W=W, Nq=N, n_stuff=0), B, seed=40 + N)
+    rd = E.MODES[mode].feat_dtype
+    if rd is not None:
+        inp["x"], inp["dfe"] = inp["x"].to(rd).float(), inp["dfe"].to(rd).float()
+    feats = [inp[k].to(gpu) if rd is None else inp[k].to(gpu).to(rd) for k in ("x", "dfe")]    # 16-bit NCHW: the planes
+    plan.set_inputs(*feats, *[inp[k].to(gpu) for k in ("k0", "q0", "m0")])
+    plan.run()
+    torch.cuda.synchronize()
+    out = plan.outputs()
+    sd = {k: v.detach().cpu() for k, v in head.state_dict().items()}
+    ref = O.iter_head_mask_preds(sd, 1, inp["x"], inp["k0"], inp["m0"], inp["q0"], inp["dfe"])
+    tol = TOL_IDENT[mode]
+    errs = {}
+    for k in ("obj", "dobj", "cls", "mask", "depth", "mask_up", "depth_up"):
+        got = out[k].float().cpu()
+        errs[k] = (Hh.rel_err(got, ref[k]), Hh.needed_atol(got, ref[k], tol))
+    print(f"wide query {mode} N={N}:", {k: f"{e:.1e},{a:.1e}" for k, (e, a) in errs.items()})
+    assert all(e < tol for e, _ in errs.values()), errs
+    assert all(a < ATOL_FRAC * tol for _, a in errs.values()), errs
+
+
+# ---- the fused final stage at the launch the bench's parts time -----------------------------------------------------------------
+@pytest.mark.parametrize("prec", [_lib.PH_PREC_BF16_KF16, _lib.PH_PREC_F16])
+def test_dynconv_up2_timed_final_stage_launch(gpu, prec):
+    """ph_dynconv_up2_wgs at one part of the headline step: N = 153, 128 x 256, 32 frames, 384 workgroups (1.5 per CU).  Each
+    workgroup takes 4096 / 384 = 10.67 image rows: uneven ranges that cross frame boundaries.  Low-resolution logits bit-identical to
+    ph_dynconv; upsampled logits within one fp16 ulp of ph_upsample2x of those logits (which test_upsample2x_fp16 pins to
+    F.interpolate) -- compared on the device, the upsampled tensor has 641 M elements"""
+    N, H, W, B, wgs = 153, 128, 256, 32, 384
+    lib = _lib.load()
+    oc = E.OUT_CODE[torch.float16]
+    assert lib.ph_dynconv_up2_supported(N, H, W, prec, oc) == 1
+    g = torch.Generator(device=gpu)
+    g.manual_seed(2024 + prec)
+    HW, Npad = H * W, E.n_padded(N)
+    feat = _lib.PH_PREC_F16 if prec == _lib.PH_PREC_F16 else _lib.PH_PREC_BF16
+    xp = E.ingest(torch.randn((B, 256, H, W), generator=g, device=gpu), feat)
+    kern = _planes16(torch.randn((2, B, Npad, 256), generator=g, device=gpu) * 0.1, torch.float16)[None].contiguous()
+    kbias = torch.randn((2, B, Npad), generator=g, device=gpu) * 0.1
+    for br in (0, 1):
+        low2 = torch.empty((B, N, H, W), device=gpu, dtype=torch.float16)
+        E.dynconv(xp, kern, kbias, br, N, HW, prec, logits_out=low2, out_dtype=oc)
+        low = torch.full((B, N, H, W), float("nan"), device=gpu, dtype=torch.float16)
+        up = torch.full((B, N, 2 * H, 2 * W), float("nan"), device=gpu, dtype=torch.float16)
+        E.dynconv_up2(xp, kern, kbias, br, N, H, W, prec, up, logits_out=low, out_dtype=oc, workgroups=wgs)
+        assert torch.equal(low, low2), br
+        up2 = E.upsample2x(low2)
+        del low, low2
+        assert not torch.isnan(up).any()
+        worst = 0.0
+        for f in range(0, B, 8):                               # fp32 differences in slices of 8 frames (2.5 GB each)
+            a, b = up[f:f + 8].float(), up2[f:f + 8].float()
+            d = (a - b).abs()
+            bound = 2.0 ** -10 * torch.maximum(a.abs(), b.abs()) + 2.0 ** -24
+            assert bool((d <= bound).all()), (br, f, float((d - bound).max()))
+            worst = max(worst, float((d / torch.maximum(a.abs(), b.abs()).clamp_min(2.0 ** -14)).max()))
+            del a, b, d, bound
+        print(f"branch {br}: largest |fused - ph_upsample2x| / |value| {worst:.2e}, "
+              f"{float((up != up2).float().mean()):.1e} of the elements differ")
+        del up, up2
