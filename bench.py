@@ -2,7 +2,11 @@
 """Headline benchmark (BASELINE.json): frames/s of the kernel-update + mask/depth forward
 (`KernelUpdateIterHead.simple_test_mask_preds`) at 1024x2048, N=153, S=3.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set-up, W warm-up steps, K timed steps, the dump, the line.
+`--full` adds everything else the line can carry (per-launch timings and the roofline, the other precision modes, cfg5, sparse
+masks, KernelHead in front, the track-record all-gather, the CPU baseline); `--all-legs` adds the slow secondary legs on top.
 
 N > 1 runs one process per GPU over RCCL: either under an outer launcher (`python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) or, when no
@@ -1175,18 +1179,14 @@ def track_allgather_leg(dev, world, backend, frames_per_rank=2, iters=30):
 
 def cfg4_main(args, dev, world, rank, backend, json_fd):
     """`python bench.py --workload cfg4 --gpus N`: BASELINE configs[3] end to end (see cfg4_run); rank 0 prints the JSON line
-    with frames/s (all ranks' frames / the max-over-ranks time), the collective's time, roofline and cpu_baseline."""
-    import torch.distributed as dist
+    with frames/s (all ranks' frames / the max-over-ranks time) and the collective's time; with --full also roofline,
+    kernels_ms and cpu_baseline."""
     prec = args.precision if args.precision in ("bf16", "fp32") else "fp16"       # the contract grade of neck / heads
     run, pipe = cfg4_run(dev, world, rank, backend, precision=prec, clip_frames=args.clip_frames, steps=args.steps, warmup=args.warmup)
     if rank != 0:
         return
     wl = WORKLOADS["cfg3"]
     N = wl["Nq"] + wl["n_stuff"]
-    plan = next(iter(pipe.roi_head._plans.values()))                 # the decode plan the frames ran on: one frame per launch
-    times, counts = kernel_breakdown(plan)
-    ab = algorithmic_bytes(plan, "pool")
-    achieved = ab / (times["pool"] * 1e-3) / 1e9
     res = {"metric": f"frames/sec video head (heads + merge + association), {wl['H'] * 8}x{wl['W'] * 8} N={N} S={wl['S']}, clips sharded 1/GPU",
            "value": run["frames_per_s"], "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": run["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -1197,14 +1197,22 @@ def cfg4_main(args, dev, world, rank, backend, json_fd):
                       "frames_per_step_per_gpu": args.clip_frames,
                       "parallelism": f"clips sharded over {world} GPU(s); ONE all-gather of the track records per step on "
                                      f"{run['backend']}, tracker replayed in frame order on every rank"},
-           "cfg4": run,
-           "roofline": {"bound": "hbm", "kernel": "pool", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
-                        "frac": round(achieved / 8000.0, 4), "traffic": None, "algorithmic_bytes_per_launch": ab,
-                        "avg_launch_ms": round(times["pool"], 4), "frames_per_launch": plan.B,
-                        "note": "the path's HBM-dominant contraction at THIS workload's launch geometry: one frame per launch, i.e. "
-                                "latency bound (the reference's video loop is one frame at a time); cfg2's batched launches are the "
-                                "default workload"},
-           "kernels_ms": {k: round(v, 4) for k, v in times.items()}}
+           "cfg4": run}
+    if not args.full:
+        res["legs_not_run"] = "roofline, per-launch timings and the CPU baseline need --full"
+        os.write(json_fd, (json.dumps(res) + "\n").encode())
+        return
+    plan = next(iter(pipe.roi_head._plans.values()))                 # the decode plan the frames ran on: one frame per launch
+    times, counts = kernel_breakdown(plan)
+    ab = algorithmic_bytes(plan, "pool")
+    achieved = ab / (times["pool"] * 1e-3) / 1e9
+    res["roofline"] = {"bound": "hbm", "kernel": "pool", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
+                       "frac": round(achieved / 8000.0, 4), "traffic": None, "algorithmic_bytes_per_launch": ab,
+                       "avg_launch_ms": round(times["pool"], 4), "frames_per_launch": plan.B,
+                       "note": "the path's HBM-dominant contraction at THIS workload's launch geometry: one frame per launch, i.e. "
+                               "latency bound (the reference's video loop is one frame at a time); cfg2's batched launches are the "
+                               "default workload"}
+    res["kernels_ms"] = {k: round(v, 4) for k, v in times.items()}
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(wl, pipe.roi_head, all_cores=False, workload_note=f"the decode part, {wl['H'] * 8}x{wl['W'] * 8}, N={N}, S={wl['S']}")
     os.write(json_fd, (json.dumps(res) + "\n").encode())
@@ -1276,10 +1284,14 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--streams", type=int, default=4, choices=[1, 2, 3, 4, 6, 8],
                     help="n > 1: n part-batches on n skewed HIP streams, one HIP graph (engine.DualDecodePlan)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check what it does not need: per-launch timings and the roofline, "
+                         "the fp16 / mixed16 modes, cfg5, sparse masks, KernelHead in front (a1 + a6), the track-record all-gather, "
+                         "the CPU baseline (about two minutes); a plain run times the headline alone")
     ap.add_argument("--all-legs", action="store_true",
-                    help="also run the secondary legs (all five precision modes, cfg5, the parity / fast pairs of a1 + a6, the neck, "
+                    help="--full plus the secondary legs (all five precision modes, the parity / fast pairs of a1 + a6, the neck, "
                          "the whole head from the FPN levels, video cfg3, the assigner, the training step, the 256-thread CPU "
-                         "point): ~10 minutes; the default run takes about two")
+                         "point): ~10 minutes")
     ap.add_argument("--clip-frames", type=int, default=2, help="cfg4: frames of a rank's clip per step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-head", action="store_true")
@@ -1289,6 +1301,7 @@ def main():
                     help="after the timed steps, write what the last one computed (obj, cls, mask, mask_up, depth_up) as DIR/<name>.npy "
                          "in float32, at most 64 MB in all (a fixed, seeded sample of the larger arrays); rank 0's frames")
     args = ap.parse_args()
+    args.full = args.full or args.all_legs
     if args.dump_outputs and args.workload == "cfg4":
         raise SystemExit("--dump-outputs: the simple_test_mask_preds workloads only (cfg2 / cfg3 / cfg5 / tiny), not cfg4")
 
@@ -1323,15 +1336,18 @@ def main():
     else:
         dist.init_process_group(backend, rank=rank, world_size=world)
 
-    if args.workload == "cfg4":
-        cfg4_main(args, dev, world, rank, backend, json_fd)
+    def finish():
         dist.barrier()
         dist.destroy_process_group()
         rc = 0
-        for w in workers:
+        for w in workers:                  # ranks this process started itself (plain `python bench.py --gpus N`)
             rc |= w.wait()
         if rc:
             raise SystemExit(f"a self-launched rank exited with status {rc}")
+
+    if args.workload == "cfg4":
+        cfg4_main(args, dev, world, rank, backend, json_fd)
+        finish()
         return
     wl = WORKLOADS[args.workload]
     B = args.frames
@@ -1392,8 +1408,41 @@ def main():
     fps = world * B * args.steps / dt
     # before any other leg launches into the same buffers: the outputs of the last timed step
     dumped = dump_outputs(runner.outputs(), args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    res = {
+        "metric": "frames/sec kernel-update+mask fwd, 1024x2048 N=153 S=3" if args.workload == "cfg2" else
+                  f"frames/sec kernel-update+mask fwd, {wl['H'] * 8}x{wl['W'] * 8} N={N} S={wl['S']}", "value": round(fps, 2),
+        "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"bf16": "bf16", "mixed": "bf16 (feature planes as given; hi/lo bf16 query GEMMs and dynamic kernels, fp16 logits)",
+                  "mixed16": "bf16 (feature planes as given; query side: updator half hi/lo bf16, attention / FFN / towers one fp16 plane; one fp16 plane of dynamic kernels, fp16 logits)",
+                  "fp16": "fp16 (planes, dynamic kernels, logits; query side: updator half hi/lo bf16, the rest one fp16 plane)",
+                  "fp32": "bf16x3 (fp32-grade split)"}[args.precision],
+        "data": "synthetic", "host_threads": host_threads,
+        "config": {"workload": f"{args.workload}: KernelUpdateIterHead.simple_test_mask_preds, "
+                               f"{wl['H'] * 8}x{wl['W'] * 8}, stride-8 {wl['H']}x{wl['W']}, N={N}, S={wl['S']}, "
+                               f"L={wl['n_thing'] + wl['n_stuff']}, random-init weights",
+                   "frames_per_step_per_gpu": B, "hip_graph": not args.no_graph, "streams": args.streams,
+                   "feature_input_dtype": in_dt, "mask_logit_input_dtype": str(gin[4].dtype).replace("torch.", ""), "output_dtype": str(out_dtype),
+                   "parity_inputs": {"bf16": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads); 6.6e-3 per stage: outside the 1e-3 contract",
+                                     "mixed": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads): 1.2e-5 per stage",
+                                     "mixed16": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads): 5.3e-4-6.6e-4 per stage; "
+                                                "against UNROUNDED fp32 features this mode is gated at 3e-3 -- the `fp16` mode (precision_modes) meets 1e-3 there",
+                                     "fp16": "unrounded fp32 features into the oracle, fp16-rounded into the device: <= 6.6e-4 per stage",
+                                     "fp32": "fp32 features on both sides: 1.3e-5 per stage"}[args.precision],
+                   "parallelism": f"frames sharded over {world} GPU(s), no data-path collective"},
+    }
+    if dumped is not None:
+        res["dump_outputs"] = dumped
+    if not args.full:
+        if rank == 0:
+            res["legs_not_run"] = "per-launch timings, roofline, algorithmic rates, other precision modes, cfg5, sparse masks, KernelHead " \
+                                  "in front, track-record all-gather and the CPU baseline need --full; the slower secondary legs --all-legs"
+            os.write(json_fd, (json.dumps(res) + "\n").encode())
+        finish()
+        return
 
-    # the one exchange of the path (video track records), outside the timed region, every rank takes part
+    # --full: the one exchange of the path (video track records), outside the timed region, every rank takes part
     try:
         tag = {fpr: track_allgather_leg(dev, world, backend, frames_per_rank=fpr) for fpr in (2, 8)}
     except Exception as e:
@@ -1441,29 +1490,7 @@ def main():
                             "in_step_mean_kernel_us": {k: v["mean_us"] for k, v in tl["in_step"].items()}}
         except Exception:
             in_graph = None
-        res = {
-            "metric": "frames/sec kernel-update+mask fwd, 1024x2048 N=153 S=3" if args.workload == "cfg2" else
-                      f"frames/sec kernel-update+mask fwd, {wl['H'] * 8}x{wl['W'] * 8} N={N} S={wl['S']}", "value": round(fps, 2),
-            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"bf16": "bf16", "mixed": "bf16 (feature planes as given; hi/lo bf16 query GEMMs and dynamic kernels, fp16 logits)",
-                      "mixed16": "bf16 (feature planes as given; query side: updator half hi/lo bf16, attention / FFN / towers one fp16 plane; one fp16 plane of dynamic kernels, fp16 logits)",
-                      "fp16": "fp16 (planes, dynamic kernels, logits; query side: updator half hi/lo bf16, the rest one fp16 plane)",
-                      "fp32": "bf16x3 (fp32-grade split)"}[args.precision],
-            "data": "synthetic", "host_threads": host_threads,
-            "config": {"workload": f"{args.workload}: KernelUpdateIterHead.simple_test_mask_preds, "
-                                   f"{wl['H'] * 8}x{wl['W'] * 8}, stride-8 {wl['H']}x{wl['W']}, N={N}, S={wl['S']}, "
-                                   f"L={wl['n_thing'] + wl['n_stuff']}, random-init weights",
-                       "frames_per_step_per_gpu": B, "hip_graph": not args.no_graph, "streams": args.streams,
-                       "feature_input_dtype": in_dt, "mask_logit_input_dtype": str(gin[4].dtype).replace("torch.", ""), "output_dtype": str(out_dtype),
-                       "parity_inputs": {"bf16": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads); 6.6e-3 per stage: outside the 1e-3 contract",
-                                         "mixed": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads): 1.2e-5 per stage",
-                                         "mixed16": "bf16-rounded features on both sides (oracle fed the bf16 tensors the device reads): 5.3e-4-6.6e-4 per stage; "
-                                                    "against UNROUNDED fp32 features this mode is gated at 3e-3 -- the `fp16` mode (precision_modes) meets 1e-3 there",
-                                         "fp16": "unrounded fp32 features into the oracle, fp16-rounded into the device: <= 6.6e-4 per stage",
-                                         "fp32": "fp32 features on both sides: 1.3e-5 per stage"}[args.precision],
-                       "parallelism": f"frames sharded over {world} GPU(s), no data-path collective"},
+        res.update({
             "roofline": dict(roof, traffic=traffic, traffic_source=traffic_src,
                              achievable_GBps_from_profiles={"pure_read": 5800.0, "pure_fill": 6900.0, "copy": 5600.0},
                              achievable_source="profiles/r01/dmabw_ring_microbenchmark.txt (compute-free LDS-DMA ring read), "
@@ -1483,11 +1510,9 @@ def main():
                                f"overlap -- `in_graph` holds what the graph replays",
             "in_graph": in_graph,
             "track_allgather": tag,
-        }
-        if dumped is not None:
-            res["dump_outputs"] = dumped
-        full = args.all_legs
-        if world == 1 and full and in_dt in ("bf16", "fp16") and not args.no_kernel_head:
+        })
+        all_legs = args.all_legs
+        if world == 1 and all_legs and in_dt in ("bf16", "fp16") and not args.no_kernel_head:
             # the same step when the features arrive as fp32 NCHW (the reference's dtype) and go through the ingest kernel
             try:
                 gin32 = [inp[k].to(dev) for k in ("x", "dfe", "k0", "q0", "m0")]
@@ -1508,7 +1533,7 @@ def main():
                         "fp16": "<= 6.6e-4 per stage against unrounded fp32 inputs (1e-3 contract met)",
                         "fp32": "1.3e-5 per stage against fp32 inputs (parity grade)"}
             res["precision_modes"] = {args.precision: {"value": round(fps, 2), "unit": "frames/s", "per_stage_rel_err": err_note[args.precision]}}
-            for mode in (("bf16", "mixed", "mixed16", "fp16", "fp32") if full else ("fp16", "mixed16")):
+            for mode in (("bf16", "mixed", "mixed16", "fp16", "fp32") if all_legs else ("fp16", "mixed16")):
                 if mode == args.precision:
                     continue
                 try:
@@ -1521,7 +1546,7 @@ def main():
                 res["cfg5_fp16"] = mode_leg(WORKLOADS["cfg5"], "fp16", dev, CFG5_FRAMES, 4, breakdown=True)
                 res["cfg5_fp16"]["note"] = "BASELINE configs[4] on ONE GPU (frames shard over 8 like cfg2's): fp16 feature planes and fp16 initial " \
                                            "mask logits resident, fp16 logits out; its own roofline (dominant launch class at this shape)"
-                if full:
+                if all_legs:
                     r32 = mode_leg(WORKLOADS["cfg5"], "fp16", dev, CFG5_FRAMES, 4, fp32_inputs=True)
                     res["cfg5_fp16"]["fp32_feature_inputs"] = {k: r32[k] for k in ("value", "ms_per_step")}
             except Exception as e:
@@ -1545,7 +1570,7 @@ def main():
                 del h16
             except Exception as e:          # secondary leg: never lose the headline line
                 res["with_kernel_head"] = {"error": repr(e)}
-            for name, prec, odt in ((("fast_bf16", "bf16", torch.bfloat16), ("parity_fp32", "fp32", torch.float32)) if full else ()):
+            for name, prec, odt in ((("fast_bf16", "bf16", torch.bfloat16), ("parity_fp32", "fp32", torch.float32)) if all_legs else ()):
                 try:
                     hk = head if args.precision == prec else build_head(wl, prec, odt, dev)
                     r = kernel_head_leg(wl, hk, prec, odt, dev)
@@ -1555,12 +1580,12 @@ def main():
                 except Exception as e:
                     res["with_kernel_head"][name] = {"error": repr(e)}
             torch.cuda.empty_cache()
-        if world == 1 and full and not args.no_kernel_head:
+        if world == 1 and all_legs and not args.no_kernel_head:
             try:
                 res["panoptic_merge"] = panoptic_leg(wl, head, kplan, dev)
             except Exception as e:
                 res["panoptic_merge"] = {"error": repr(e)}
-        if world == 1 and full and not args.no_neck:
+        if world == 1 and all_legs and not args.no_neck:
             # the neck and the whole head from the FPN levels: the fp16 grade (one fp16 plane of weights / activations in the
             # neck and in KernelHead, the decode's `fp16` mode: every stage inside the 1e-3 contract) first, the all-bf16 fast
             # grade (outside the contract) next to it
@@ -1583,36 +1608,30 @@ def main():
             except Exception as e:
                 res.setdefault("full_head_from_fpn", {})["error"] = repr(e)
             torch.cuda.empty_cache()
-        if world == 1 and full and not args.no_neck:
+        if world == 1 and all_legs and not args.no_neck:
             try:
                 res["video_cfg3"] = video_leg(dev, precision="fp16")      # fp16 grade in neck / heads, split-grade track head
                 fast = video_leg(dev, precision="bf16")
                 res["video_cfg3"]["fast_bf16"] = {"ms_per_frame": fast["ms_per_frame"], "eager_launches": fast["eager_launches"]}
             except Exception as e:
                 res.setdefault("video_cfg3", {})["error"] = repr(e)
-        if world == 1 and full and not args.no_neck:
+        if world == 1 and all_legs and not args.no_neck:
             try:
                 res["hungarian_assign"] = assign_leg(dev)
             except Exception as e:
                 res["hungarian_assign"] = {"error": repr(e)}
-        if world == 1 and full and not args.no_neck:
+        if world == 1 and all_legs and not args.no_neck:
             try:
                 res["train_step"] = train_leg(wl, dev, world)
             except Exception as e:
                 res["train_step"] = {"error": repr(e)}
-        if not full:
+        if not all_legs:
             res["legs_not_run"] = "secondary legs (all precision modes, panoptic merge, neck, whole head from the FPN levels, video cfg3, " \
                                   "assigner, training step) need --all-legs; profiles/r06/bench_all_legs.json holds this round's full line"
         if not args.no_cpu_baseline:                       # rank 0, at every N: the line of an N-GPU run carries it too
-            res["cpu_baseline"] = cpu_baseline(wl, head, all_cores=full)
+            res["cpu_baseline"] = cpu_baseline(wl, head, all_cores=all_legs)
         os.write(json_fd, (json.dumps(res) + "\n").encode())
-    dist.barrier()
-    dist.destroy_process_group()
-    rc = 0
-    for w in workers:                  # ranks this process started itself (plain `python bench.py --gpus N`)
-        rc |= w.wait()
-    if rc:
-        raise SystemExit(f"a self-launched rank exited with status {rc}")
+    finish()
 
 
 if __name__ == "__main__":

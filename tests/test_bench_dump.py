@@ -1,8 +1,12 @@
 """bench.py --dump-outputs (CPU): float32 .npy files of the five caller-visible outputs, at most 64 MB in all, the larger arrays as
-a fixed sample that is the same for the same shape in every run."""
+a fixed sample that is the same for the same shape in every run; and (GPU) what a plain run's line carries."""
+import json
 import os
+import subprocess
+import sys
 
 import numpy as np
+import pytest
 import torch
 
 import bench
@@ -38,3 +42,25 @@ def test_dump_outputs_files_budget_and_fixed_sample(tmp_path):
     np.testing.assert_array_equal(np.load(tmp_path / "b" / "mask_up.npy"), (outs["mask_up"] + 1).float().numpy().ravel()[
         np.sort(np.random.default_rng(0).choice(outs["mask_up"].numel(), up.size, replace=False))])
     np.testing.assert_array_equal(np.load(tmp_path / "b" / "depth_up.npy"), np.load(tmp_path / "a" / "depth_up.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_run_line_is_the_headline_and_the_dump(gpu, tmp_path):
+    """a plain run (no --full) times the headline and writes the dump; the legs that need runs of their own stay out of its line"""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--workload", "tiny", "--frames", "8", "--steps", "3", "--warmup", "1",
+                        "--streams", "2", "--dump-outputs", str(tmp_path / "d")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["unit"] == "frames/s" and res["higher_is_better"] is True and res["steps"] == 3 and res["warmup"] == 1
+    assert abs(res["value"] - 8 * 1e3 / res["ms_per_step"]) / res["value"] < 1e-3
+    assert res["dtype"].startswith("bf16") and res["metric"].startswith("frames/sec")
+    for leg in ("roofline", "kernels_ms", "algorithmic", "precision_modes", "cfg5_fp16", "sparse_masks", "with_kernel_head",
+                "track_allgather", "cpu_baseline"):
+        assert leg not in res, leg
+    assert "--full" in res["legs_not_run"]
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(n + ".npy" for n in bench.DUMP_NAMES)
+    assert sorted(res["dump_outputs"]["arrays"]) == sorted(bench.DUMP_NAMES)

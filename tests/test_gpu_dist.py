@@ -72,15 +72,15 @@ def test_allgather_track_records_on_rccl(gpu):
 
 
 def test_bench_launches_its_own_ranks(gpu):
-    """plain `python bench.py --gpus 2` (no outer launcher): rank 0 starts rank 1 itself, ONE JSON line comes back with
-    n_gpus 2, the aggregate of both ranks and the timed track-record all-gather.  With fewer than two GPUs the two
-    ranks share GPU 0 and rendezvous over gloo (PH_DIST_BACKEND), which exercises the same launch path."""
+    """`python bench.py --gpus 2 --full` (no outer launcher): rank 0 starts rank 1 itself, ONE JSON line comes back with
+    n_gpus 2, the aggregate of both ranks and the timed track-record all-gather (a --full leg).  With fewer than two GPUs the
+    two ranks share GPU 0 and rendezvous over gloo (PH_DIST_BACKEND), which exercises the same launch path."""
     env = dict(os.environ)
     if torch.cuda.device_count() < 2:
         env["PH_DIST_BACKEND"] = "gloo"
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--workload", "tiny", "--frames", "8",
-                        "--steps", "3", "--warmup", "1", "--streams", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "3", "--warmup", "1", "--streams", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -163,12 +163,12 @@ def test_cfg4_sharded_clips_track_ids_equal_the_single_process_video_loop(gpu):
 
 
 def test_bench_cfg4_json_line(gpu):
-    """`python bench.py --workload cfg4 --gpus N`: one JSON line with the metric, the collective's time, roofline and
-    cpu_baseline; the process group spans exactly --gpus ranks"""
+    """`python bench.py --workload cfg4 --gpus N --full`: one JSON line with the metric, the collective's time and (--full)
+    roofline; the process group spans exactly --gpus ranks"""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", "cfg4", "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -199,13 +199,13 @@ def _need_8_gpus():
 
 
 def test_bench_gpus8_self_launch_json_line(gpu):
-    """`python bench.py --gpus 8` exactly as the driver's 8-GPU run starts it (minus the outer launcher): rank 0 starts ranks 1..7,
-    every rank times its own frames, the line carries n_gpus 8, the max-over-ranks step time, the 8-rank all-gather (payload of all
-    8 ranks bit-exact) and value = frames of all ranks / that time"""
+    """`python bench.py --gpus 8 --full` as an 8-GPU run starts it without an outer launcher: rank 0 starts ranks 1..7,
+    every rank times its own frames, the line carries n_gpus 8, the max-over-ranks step time, the 8-rank all-gather (a --full leg;
+    payload of all 8 ranks bit-exact) and value = frames of all ranks / that time"""
     _need_8_gpus()
     extra = {} if torch.cuda.device_count() >= 8 else {"PH_DIST_BACKEND": "gloo"}
     res = _bench_line(["--gpus", "8", "--workload", "tiny", "--frames", "8", "--steps", "3", "--warmup", "1", "--streams", "2", "--no-cpu-baseline",
-                       "--no-kernel-head"], extra)
+                       "--no-kernel-head", "--full"], extra)
     assert res["n_gpus"] == 8 and res["scaling"] == "weak" and res["steps"] == 3 and res["value"] > 0
     assert abs(res["value"] - 8 * 8 * 1e3 / res["ms_per_step"]) / res["value"] < 1e-3          # whole-job aggregate over the 8 ranks
     for fpr in ("2", "8"):

@@ -1,4 +1,4 @@
-"""prints a compact summary of a bench.py JSON line read from stdin (tuning helper)"""
+"""prints a compact summary of a `bench.py --full` JSON line read from stdin (tuning helper)"""
 import json
 import sys
 

@@ -4,14 +4,14 @@
 set -u
 TAG=${1:-run}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 if [ "${ALL_LEGS:-1}" = 1 ]; then python bench.py --all-legs > $OUT/bench_all_legs.json 2> $OUT/bench_all_legs.err; fi
-python bench.py --workload cfg4 --steps 40 --warmup 4 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
-python bench.py --workload cfg4 --steps 40 --warmup 4 --clip-frames 8 > $OUT/bench_cfg4_clip8.json 2> $OUT/bench_cfg4_clip8.err
+python bench.py --full --workload cfg4 --steps 40 --warmup 4 > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
+python bench.py --full --workload cfg4 --steps 40 --warmup 4 --clip-frames 8 > $OUT/bench_cfg4_clip8.json 2> $OUT/bench_cfg4_clip8.err
 python tools/video_trace.py 96 > $OUT/v_video_runner_time.txt 2> $OUT/v_video.err; python tools/video_trace.py 96 seq >> $OUT/v_video_runner_time.txt 2>> $OUT/v_video.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/v -o v -- python tools/video_trace.py 48 seq > $OUT/v_video_one_slot_traced.txt 2>> $OUT/v_video.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/d -o d -- python bench.py --no-cpu-baseline --no-kernel-head --no-neck > $OUT/d_bench.json 2> $OUT/d.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/e -o e -- python bench.py --streams 1 --frames 24 --no-cpu-baseline --no-kernel-head --no-neck > $OUT/e_bench.json 2> $OUT/e.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/d -o d -- python bench.py --full --no-cpu-baseline --no-kernel-head --no-neck > $OUT/d_bench.json 2> $OUT/d.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/e -o e -- python bench.py --full --streams 1 --frames 24 --no-cpu-baseline --no-kernel-head --no-neck > $OUT/e_bench.json 2> $OUT/e.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/q -o q -- python tools/query_time.py 64 > $OUT/q_query64.txt 2> $OUT/q.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/k -o k -- python tools/a1_profile.py 16 fp16 > $OUT/k_a1.txt 2> $OUT/k.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmc_fetch -o p -- python tools/pool_only.py mixed16 > /dev/null 2> $OUT/pmc_fetch.err
