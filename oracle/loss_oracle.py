@@ -1,5 +1,9 @@
 """TEST INFRASTRUCTURE ONLY -- CPU restatement (the *oracle*) of the training-side targets and losses of one
-KernelUpdateHead stage and of KernelHead (the rpn side).  Plain fp32 torch on the CPU, functional; every function cites the reference lines it follows.
+KernelUpdateHead stage and of KernelHead (the rpn side).  Plain torch on the CPU, functional; every function cites the reference lines it follows.
+The arithmetic follows the dtype of the PREDICTIONS: fp32 inputs give the reference's fp32 results bit for bit (the goldens), float64
+predictions with autograd give the value and the gradient of the same operation at higher precision (tests/test_gpu_loss_edges.py).
+The loss parameters (weights, focal gamma / alpha, depth term weights and mode, dice eps, pos_weight) are keywords whose defaults are
+the shipped configuration.
 Pinned by tests/golden/loss.npz, which `oracle/gen_golden_loss.py` produced with the reference's own
 `KernelUpdateHead.get_targets` / `.loss`, the vendored mmdet FocalLoss / CrossEntropyLoss / DiceLoss / accuracy and the
 project's DepthLoss and by tests/golden/train_rpn.npz (the reference's KernelHead.forward_train) (tests/test_loss_oracle.py).  Only tests may
@@ -25,13 +29,13 @@ def focal_loss(pred, labels, weight, avg_factor, gamma=2.0, alpha=0.25, loss_wei
 
 def bce_mean(pred, target, loss_weight=1.0):
     """CrossEntropyLoss(use_sigmoid=True) on equal-rank inputs (cross_entropy_loss.py:74-113): mean BCE with logits"""
-    return loss_weight * F.binary_cross_entropy_with_logits(pred, target.float(), reduction="none").mean()
+    return loss_weight * F.binary_cross_entropy_with_logits(pred, target.to(pred.dtype), reduction="none").mean()
 
 
 def dice_one(pred_logits, target, eps=1e-3, loss_weight=4.0):
     """DiceLoss.forward on ONE sample of selected pixels (dice_loss.py:9-46,118-136): sigmoid, 1 - 2a / (b + c)"""
     x = pred_logits.sigmoid().flatten()
-    t = target.flatten().float()
+    t = target.flatten().to(x.dtype)
     a = (x * t).sum()
     b = (x * x).sum() + eps
     c = (t * t).sum() + eps
@@ -50,9 +54,11 @@ def depth_loss(pred_logits, target, mask_weight, mode="sigmoid", loss_weight=5.0
     pixels with 0 < target < 80 and non-zero weight, (terms * weight).mean() * loss_weight.  NB the scale-invariant term
     subtracts sum(log_minus) / n^2 as the reference writes it (:25), not the squared sum."""
     pred = depth_act(pred_logits, mode)
+    target, mask_weight = target.to(pred.dtype), mask_weight.to(pred.dtype)      # log(t), m / t in the predictions' precision
+    w3 = torch.tensor(weights, dtype=pred.dtype)
     mask = (target > min_depth) & (target < max_depth) & (mask_weight != 0)
     if not torch.any(mask):
-        return loss_weight * (torch.zeros(3) * torch.tensor(weights)).mean()
+        return loss_weight * (torch.zeros(3, dtype=pred.dtype) * w3).mean()
     p, t, w = pred[mask], target[mask], mask_weight[mask]
     n = p.shape[0]
     lm = (torch.log(p) - torch.log(t)) * w
@@ -60,7 +66,7 @@ def depth_loss(pred_logits, target, mask_weight, mode="sigmoid", loss_weight=5.0
     si = (lm ** 2).sum() / n - lm.sum() / (n ** 2)
     sq = torch.sqrt(((m / t) ** 2).sum() / n)
     ab = (m / t).abs().sum() / n
-    return loss_weight * (torch.stack((si, sq, ab)) * torch.tensor(weights)).mean()
+    return loss_weight * (torch.stack((si, sq, ab)) * w3).mean()
 
 
 def accuracy_top1(pred, target):
@@ -120,7 +126,7 @@ def target_single(num_classes, n_thing, n_stuff, pos_inds, neg_inds, num_samples
     return labels, label_weights, mask_targets, mask_weights, depth_targets, depth_weights
 
 
-def get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids):
+def get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids, pos_weight=1.0):
     """gts: per image dict(masks, labels, sem_seg, sem_cls, depth, gt_inds, assigned_labels) -- the sampling result of
     MaskPseudoSampler is pos = gt_inds > 0, neg = gt_inds == 0 (funcs/sampler.py:81-113).  Concatenated over images."""
     outs = []
@@ -129,33 +135,37 @@ def get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids):
         neg = (g["gt_inds"] == 0).nonzero().flatten()
         pos_gt = g["masks"][g["gt_inds"][pos] - 1] if len(g["masks"]) else g["masks"][:0]
         outs.append(target_single(num_classes, n_thing, n_stuff, pos, neg, Nq, H, W, pos_gt, g["assigned_labels"][pos], g["sem_seg"],
-                                  g["sem_cls"], g["depth"], v))
+                                  g["sem_cls"], g["depth"], v, pos_weight=pos_weight))
     return tuple(torch.cat([o[k] for o in outs], 0) for k in range(6))
 
 
 # ---- KernelUpdateHead.loss (kernel_update_head.py:355-441) ---------------------------------------------------------------
 def stage_loss(num_classes, cls_score, mask_pred, depth_pred, labels, label_weights, mask_targets, mask_weights, depth_targets,
-               depth_weights, ignore_label=255):
+               depth_weights, ignore_label=255, lw_depth=5.0, depth_terms=(1.0, 1.0, 1.0), depth_mode="sigmoid", lw_cls=2.0,
+               cls_gamma=2.0, cls_alpha=0.25, lw_mask=1.0, lw_dice=4.0, dice_eps=1e-3, lw_rank=0.1):
+    """the keywords are the stage's loss configuration (polyphonic_former.py:111-165); the defaults are the shipped one"""
     losses = {}
     pos = (labels >= 0) & (labels < num_classes)                                             # :375
     avg = pos.sum().float().clamp(min=1.0)                                                   # :376-377
     B, N, H, W = mask_pred.shape
     R = B * N
-    losses["loss_depth"] = depth_loss(depth_pred.reshape(R, H, W), depth_targets, depth_weights)        # :383-391
+    losses["loss_depth"] = depth_loss(depth_pred.reshape(R, H, W), depth_targets, depth_weights, mode=depth_mode,
+                                      loss_weight=lw_depth, weights=depth_terms)            # :383-391
     cs = cls_score.reshape(R, -1)
-    losses["loss_cls"] = focal_loss(cs, labels, label_weights, avg)                          # :395-400
+    losses["loss_cls"] = focal_loss(cs, labels, label_weights, avg, gamma=cls_gamma, alpha=cls_alpha, loss_weight=lw_cls)   # :395-400
     losses["pos_acc"] = accuracy_top1(cs[pos], labels[pos])                                  # :401-402
     if pos.any():                                                                            # :408-437
         pm = mask_pred.reshape(R, H, W)[pos]
         pt = mask_targets[pos]
         pw = mask_weights[pos].bool()
-        losses["loss_rpn_mask"] = bce_mean(pm[pw], pt[pw])
-        losses["loss_rpn_dice"] = torch.stack([dice_one(pm[i][pw[i]], pt[i][pw[i]]) for i in range(pm.shape[0])]).mean()
+        losses["loss_rpn_mask"] = bce_mean(pm[pw], pt[pw], loss_weight=lw_mask)
+        losses["loss_rpn_dice"] = torch.stack([dice_one(pm[i][pw[i]], pt[i][pw[i]], eps=dice_eps, loss_weight=lw_dice)
+                                               for i in range(pm.shape[0])]).mean()
         rank_target = torch.full((B, H, W), ignore_label, dtype=torch.long)
         mt = mask_targets.view(B, -1, H, W).bool()
         for b, j in pos.view(B, -1).nonzero(as_tuple=False).tolist():
             rank_target[b][mt[b][j]] = j
-        losses["loss_rank"] = rank_loss(mask_pred, rank_target, ignore_label)
+        losses["loss_rank"] = rank_loss(mask_pred, rank_target, ignore_label, loss_weight=lw_rank)
     else:
         losses["loss_mask"] = mask_pred.sum() * 0
         losses["loss_dice"] = mask_pred.sum() * 0
@@ -198,7 +208,7 @@ def rpn_target_single(num_classes, n_thing, n_stuff, pos_inds, neg_inds, num_sam
     return labels, label_weights, mask_targets, mask_weights, seg_targets, depth_targets, depth_weights
 
 
-def rpn_get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids):
+def rpn_get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids, pos_weight=1.0):
     """as `get_targets` above; seg_targets are stacked (kernel_head.py:688)"""
     outs = []
     for g, v in zip(gts, valids):
@@ -206,30 +216,34 @@ def rpn_get_targets(num_classes, n_thing, n_stuff, Nq, H, W, gts, valids):
         neg = (g["gt_inds"] == 0).nonzero().flatten()
         pos_gt = g["masks"][g["gt_inds"][pos] - 1] if len(g["masks"]) else g["masks"][:0]
         outs.append(rpn_target_single(num_classes, n_thing, n_stuff, pos, neg, Nq, H, W, pos_gt, g["assigned_labels"][pos], g["sem_seg"],
-                                      g["sem_cls"], g["depth"], v))
+                                      g["sem_cls"], g["depth"], v, pos_weight=pos_weight))
     return tuple(torch.stack([o[k] for o in outs], 0) if k == 4 else torch.cat([o[k] for o in outs], 0) for k in range(7))
 
 
 def rpn_loss(num_classes, mask_pred, seg_preds, depth_pred, labels, label_weights, mask_targets, mask_weights, seg_targets,
-             depth_targets, depth_weights, ignore_label=255):
-    """KernelHead.loss with the shipped losses (polyphonic_former.py:66-97): cls_scores and semantic_aspp are None"""
+             depth_targets, depth_weights, ignore_label=255, lw_depth=5.0, depth_terms=(1.0, 1.0, 1.0), depth_mode="sigmoid", lw_mask=1.0,
+             lw_dice=4.0, dice_eps=1e-3, lw_rank=0.1, lw_seg=1.0, seg_gamma=2.0, seg_alpha=0.25):
+    """KernelHead.loss with the shipped losses (polyphonic_former.py:66-97): cls_scores and semantic_aspp are None; the keywords
+    are the loss configuration, the defaults the shipped one"""
     losses = {}
     pos = (labels >= 0) & (labels < num_classes)                                             # :475
     B, N, H, W = mask_pred.shape
     R = B * N
     Rd = depth_targets.shape[0]                      # B * (proposals + stuff rows): forward_train expands the one map (:386)
-    losses["loss_depth"] = depth_loss(depth_pred.expand(B, Rd // B, H, W).reshape(Rd, H, W), depth_targets, depth_weights)   # :478-486
+    losses["loss_depth"] = depth_loss(depth_pred.expand(B, Rd // B, H, W).reshape(Rd, H, W), depth_targets, depth_weights, mode=depth_mode,
+                                      loss_weight=lw_depth, weights=depth_terms)            # :478-486
     if pos.any():                                                                            # :503-531
         pm = mask_pred.reshape(R, H, W)[pos]
         pt = mask_targets[pos]
         pw = mask_weights[pos].bool()
-        losses["loss_rpn_mask"] = bce_mean(pm[pw], pt[pw])
-        losses["loss_rpn_dice"] = torch.stack([dice_one(pm[i][pw[i]], pt[i][pw[i]]) for i in range(pm.shape[0])]).mean()
+        losses["loss_rpn_mask"] = bce_mean(pm[pw], pt[pw], loss_weight=lw_mask)
+        losses["loss_rpn_dice"] = torch.stack([dice_one(pm[i][pw[i]], pt[i][pw[i]], eps=dice_eps, loss_weight=lw_dice)
+                                               for i in range(pm.shape[0])]).mean()
         rank_target = torch.full((B, H, W), ignore_label, dtype=torch.long)
         mt = mask_targets.view(B, -1, H, W).bool()
         for b, j in pos.view(B, -1).nonzero(as_tuple=False).tolist():
             rank_target[b][mt[b][j]] = j
-        losses["loss_rpn_rank"] = rank_loss(mask_pred, rank_target, ignore_label)
+        losses["loss_rpn_rank"] = rank_loss(mask_pred, rank_target, ignore_label, loss_weight=lw_rank)
     else:                                                                                    # :533-537
         losses["loss_rpn_mask"] = mask_pred.sum() * 0
         losses["loss_rpn_dice"] = mask_pred.sum() * 0
@@ -239,10 +253,10 @@ def rpn_loss(num_classes, mask_pred, seg_preds, depth_pred, labels, label_weight
     flat = seg_preds.permute(1, 0, 2, 3)[..., sel].permute(1, 0)
     ft = seg_targets[sel]
     nd = ((ft >= 0) & (ft < num_classes)).sum().float().clamp(min=1.0)
-    losses["loss_rpn_seg"] = focal_loss(flat, ft, torch.ones(()), nd, loss_weight=1.0)
+    losses["loss_rpn_seg"] = focal_loss(flat, ft, torch.ones(()), nd, gamma=seg_gamma, alpha=seg_alpha, loss_weight=lw_seg)
     return losses
 
 
-def dense_depth(depth_pred, gt_depth):
+def dense_depth(depth_pred, gt_depth, **kw):
     """losses['depth_dense'] (kernel_head.py:438-442)"""
-    return depth_loss(depth_pred, gt_depth, (gt_depth > 0).float())
+    return depth_loss(depth_pred, gt_depth, (gt_depth > 0).float(), **kw)

@@ -518,15 +518,16 @@ __global__ __launch_bounds__(LOSS_T) void k_mask_grad_p(const float* __restrict_
 }
 
 // pixel -> index (within its image) of the LAST positive row whose target covers it (kernel_update_head.py:420-432)
+constexpr int RANK_ROWS_MAX = 512;
 __global__ __launch_bounds__(LOSS_T) void k_rank_target_p(const int64_t* __restrict__ tptr, const uint8_t* __restrict__ pos, int N, int64_t HW,
                                                           int ignore, int* __restrict__ out) {
-    __shared__ int64_t lp[512];
-    __shared__ int lj[512];
+    __shared__ int64_t lp[RANK_ROWS_MAX];
+    __shared__ int lj[RANK_ROWS_MAX];
     __shared__ int cnt;
     const int b = blockIdx.y;
     if (threadIdx.x == 0) {
         int c = 0;
-        for (int j = 0; j < N && c < 512; ++j)
+        for (int j = 0; j < N && c < RANK_ROWS_MAX; ++j)      // ph_train_losses refuses a cfg that could exceed it
             if (pos[b * N + j] && tptr[b * N + j]) { lp[c] = tptr[b * N + j]; lj[c] = j; ++c; }
         cnt = c;
     }
@@ -794,6 +795,9 @@ extern "C" int ph_train_losses(const ph_loss_cfg* cfg, const float* mask_pred, c
     PH_CHECK_ARG(cfg && mask_pred && depth_pred && pos_u8 && tptr && wptr && dstart && losses && scratch, "null pointer");
     const ph_loss_cfg& c = *cfg;
     PH_CHECK_ARG(c.B > 0 && c.N > 0 && c.HW > 0 && c.P >= 0 && c.depth_rows > 0 && (c.P == 0 || pos_rows), "bad size");
+    // k_rank_target_p lists the positive rows of ONE image in LDS, RANK_ROWS_MAX of them; an image has at most min(N, P): beyond
+    // that the rank target would silently lose rows
+    PH_CHECK_ARG(!(c.has_rank && c.P > RANK_ROWS_MAX && c.N > RANK_ROWS_MAX), "rank loss: at most 512 positive rows per image (N or P <= 512)");
     PH_CHECK_ARG(scratch_bytes >= ph_train_losses_scratch_bytes(cfg), "scratch too small");
     PH_CHECK_ARG((cls_score == nullptr) == (labels == nullptr) && (cls_score == nullptr) == (label_w == nullptr), "cls_score, labels, label_w go together");
     PH_CHECK_ARG((seg_pred == nullptr) == (sstart == nullptr), "seg_pred and its paint lists go together");

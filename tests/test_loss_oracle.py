@@ -45,6 +45,45 @@ def _check_losses(z, m, tag, tg, L):
         assert Hh.rel_err(t.grad, z[f"{tag}_g_{name}"]) < 1e-5, name
 
 
+@pytest.mark.parametrize("tag", ["a", "b", "c"])
+def test_float64_oracle_is_the_same_function(tag):
+    """the oracle run in float64 with autograd -- the reference of tests/test_gpu_loss_edges.py -- on the reference's own
+    fixtures: the stored (fp32 reference) loss values within 2e-5 max(1, |want|) and the stored gradients within rel_err 1e-4,
+    the bounds the device kernels are held to.  fp32 inputs still give fp32 results (the golden tests above)."""
+    z, m, gts, valids = load_case(tag)
+    L = m["n_thing"] + m["n_stuff"]
+    tg = LO.get_targets(L, m["n_thing"], m["n_stuff"], m["Nq"], m["H"], m["W"], gts, valids)
+    with torch.enable_grad():
+        mp, cs, dp = (torch.from_numpy(z[f"{tag}_{k}"]).double().requires_grad_(True) for k in ("mask_pred", "cls_score", "depth_pred"))
+        losses = LO.stage_loss(L, cs, mp, dp, *tg)
+        assert all(v.dtype == torch.float64 for k, v in losses.items() if k.startswith("loss")), {k: v.dtype for k, v in losses.items()}
+        sum(v for k, v in losses.items() if k.startswith("loss")).backward()
+    for k, v in losses.items():
+        want = float(np.asarray(z[f"{tag}_l_{k}"]).reshape(-1)[0])
+        assert abs(float(v.detach()) - want) <= 2e-5 * max(1.0, abs(want)), (k, float(v.detach()), want)
+    for name, t in (("mask_pred", mp), ("cls_score", cs), ("depth_pred", dp)):
+        assert t.grad.dtype == torch.float64
+        assert Hh.rel_err(t.grad, z[f"{tag}_g_{name}"]) < 1e-4, name
+
+
+def test_oracle_keywords_reach_the_losses():
+    """every loss parameter is a keyword of stage_loss / rpn_loss / the target functions; the defaults are the shipped ones"""
+    z, m, gts, valids = load_case("c")
+    L = m["n_thing"] + m["n_stuff"]
+    args = (L, m["n_thing"], m["n_stuff"], m["Nq"], m["H"], m["W"], gts, valids)
+    tg, tg2 = LO.get_targets(*args), LO.get_targets(*args, pos_weight=2.0)
+    assert tg2[1].max() == 2.0 and tg[1].max() == 1.0 and (tg2[5] != tg[5]).any() and tg2[5].max() <= 2.0
+    mp, cs, dp = (torch.from_numpy(z[f"c_{k}"]) for k in ("mask_pred", "cls_score", "depth_pred"))
+    base = LO.stage_loss(L, cs, mp, dp, *tg)
+    for kw, key in ((dict(lw_depth=1.0), "loss_depth"), (dict(depth_terms=(0.0, 1.0, 1.0)), "loss_depth"), (dict(depth_mode="monodepth"), "loss_depth"),
+                    (dict(lw_cls=1.0), "loss_cls"), (dict(cls_gamma=1.5), "loss_cls"), (dict(cls_alpha=0.6), "loss_cls"),
+                    (dict(lw_mask=2.0), "loss_rpn_mask"), (dict(lw_dice=1.0), "loss_rpn_dice"), (dict(dice_eps=10.0), "loss_rpn_dice"),
+                    (dict(lw_rank=1.0), "loss_rank")):
+        got = LO.stage_loss(L, cs, mp, dp, *tg, **kw)
+        assert got[key] != base[key], kw
+        assert all(torch.equal(got[k], base[k]) for k in base if k != key), kw
+
+
 def test_rpn_forward_train_matches_reference():
     """KernelHead.forward_train (kernel_head.py:349-454) end to end in the oracle -- post-neck decode, x2 upsample, Hungarian
     assignment, rpn targets, rpn losses, depth_dense -- against the REFERENCE's own forward_train with its assigner, sampler

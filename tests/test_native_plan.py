@@ -266,6 +266,38 @@ print("run checks ok")
 """
 
 
+_LOSS_ARG_CHECKS = r"""
+import ctypes as C, sys
+sys.path.insert(0, ".")
+import torch
+from polyphonicformer_amd import _lib
+from polyphonicformer_amd.losses import LossCfg
+assert torch.cuda.device_count() == 0, "the argument checks need a process without a visible GPU"
+lib = _lib.load()
+FAKE = C.c_void_p(1 << 40)
+msg = lambda: lib.ph_last_error_string().decode()
+def call(**kw):
+    c = LossCfg(**dict(dict(B=2, N=600, L=19, P=1100, depth_rows=1200, HW=493, has_rank=1, ignore=255, cls_avg=1.0), **kw))
+    # scratch_bytes = 0: a cfg that passes every earlier check stops at "scratch too small", before anything is launched
+    return lib.ph_train_losses(C.byref(c), FAKE, None, FAKE, None, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, None, None, None, None,
+                               None, FAKE, None, None, None, None, FAKE, 0, None)
+assert call() == -1 and "at most 512 positive rows per image" in msg(), msg()        # N and P both beyond what the rank target keeps
+assert call(N=513, P=513) == -1 and "at most 512 positive rows per image" in msg(), msg()
+for kw in (dict(N=512), dict(P=512, N=4000), dict(has_rank=0), dict(P=0)):           # an image cannot have more than min(N, P)
+    assert call(**kw) == -1 and "scratch too small" in msg(), (kw, msg())
+print("loss checks ok")
+"""
+
+
+def test_train_losses_refuses_more_rank_rows_than_it_keeps():
+    """`k_rank_target_p` lists at most 512 positive rows per image: `ph_train_losses` returns PH_EINVAL for a cfg that could
+    exceed that instead of dropping rows.  In a child process that sees no GPU, on fake addresses: nothing is launched."""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _LOSS_ARG_CHECKS], cwd=os.path.dirname(BLD.HERE), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "loss checks ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+
+
 def _elf_needed(path):
     """DT_NEEDED entries of an ELF64 little-endian file (the dynamic section and its string table)"""
     import struct
