@@ -501,7 +501,8 @@ int ph_qtrain_backward(const float* const* params, const float* pooled, const fl
  *           counts[1][k] = #{rescale(act_mask[k]) >= 0.5} (counts zeroed by the call).
  * paste   : pan = newid[ids]; depth_final = newid[ids] > 0 ? rescale(act_depth[ids]) : rescale(act_depth0).
  * from_probs != 0: act_* are already full-resolution [K][Ho][Wo] maps (no resampling) -- the integer
- * semantics in isolation. The accept loop between argmax and paste (:500-533) is host logic. */
+ * semantics in isolation. The accept loop between argmax and paste (:500-533) is host logic here; ph_panoptic_accept below
+ * is the same step on the device. */
 /* select  : the segment candidates of kernel_update.py:428-434 / :448-459 on the device, for B frames: the top max_per_img
  *           (query, thing class) pairs of cls_scores [B][N][L] (post-sigmoid) in descending order, then the stuff queries'
  *           own-class scores (the diagonal of the [N - num_proposals] x [L - num_thing_classes] block) in descending order;
@@ -517,6 +518,48 @@ int ph_panoptic_argmax(const float* act_mask, const float* scores, int K, const 
 int ph_panoptic_paste(const int32_t* ids, const int32_t* newid, const float* act_depth, const float* act_depth0,
                       const int32_t* geom, int from_probs, int32_t* pan, float* depth_basic, float* depth_final,
                       void* stream);
+
+/* ---- the merge as launches only, for B frames of ONE geometry -------------------------------
+ * accept  : the accept step (kernel_update.py:497-533) on the device, one workgroup per frame.  Per frame it reads labels[K],
+ *           scores[K] and counts[2][K] as select and argmax leave them (the three pointers advance by in_batch_stride elements
+ *           per frame) and writes newid[K] (0 = rejected), nseg, and the record table seg[K][4] = {new id, candidate index k,
+ *           label, area} with rows in id order and the unused rows zero (nseg and seg advance by rec_batch_stride int32 per
+ *           frame).  A thing is rejected when score < (float)instance_score_thr, evaluated in fp32; every candidate needs
+ *           area > 0 && orig > 0 and !((double)area / (double)orig < overlap_thr), one IEEE fp64 division.  Kept candidates are
+ *           numbered 1.. in the order of a stable descending sort of the scores: ties by ascending index, NaN last
+ *           (torch.argsort(-scores, stable=True)).  K <= 4096.
+ * *_batch : ph_panoptic_activate / _argmax / _paste for B frames in one launch each -- the same kernels with the frame in the
+ *           grid; the single-frame calls are their B = 1 case.  Logits [B][N][h2][w2]; act_mask / act_depth [B][K][..],
+ *           act_depth0 [B][..], ids / pan / depths [B][Ho][Wo] dense; q_idx, scores, counts and newid advance by the given
+ *           stride (in elements) per frame.  generic_only != 0: never the x4 form of the argmax (tests); no environment is read.
+ * merge   : select -> activate -> clear + argmax -> accept -> paste from the decode's outputs (ph_decode_io cls, mask_up, depth_up
+ *           and ph_upsample2x of KernelHead's direct depth) to the id and depth maps.  Enqueue only: no allocation, no
+ *           synchronisation, no environment variable; capturable in a HIP graph.  K = max_per_img + min(N - num_proposals,
+ *           L - num_thing_classes).  The workspace (256-byte aligned, ph_panoptic_merge_workspace_bytes) holds the candidate pack
+ *           [B][5K], act_mask, act_depth, act_depth0, ids and newid.  seg_records [B][1 + 5K] int32 per frame:
+ *           nseg | seg[K][4] | scores[K] as fp32 bits -- all a host needs for the reference's segments_info.
+ *           PH_EINVAL / PH_EUNSUPPORTED / PH_EWORKSPACE are returned before the first launch (message: ph_last_error_string);
+ *           the size query returns 0 for a bad size, with a message.  Candidate order among exactly equal scores is
+ *           ph_panoptic_select's: ascending index. */
+int ph_panoptic_accept(const int32_t* labels, const float* scores, const int32_t* counts /*[2][K]*/, int64_t in_batch_stride, int B,
+                       int K, int num_thing_classes, double instance_score_thr, double overlap_thr, int32_t* newid,
+                       int64_t newid_batch_stride, int32_t* nseg, int32_t* seg /*[K][4]*/, int64_t rec_batch_stride, void* stream);
+int ph_panoptic_activate_batch(const void* mask_up, const void* depth_up, int dtype, const float* depth_init_up,
+                               const int32_t* q_idx, int64_t q_batch_stride, int B, int N, int K, int h2, int w2, int depth_mode,
+                               float* act_mask, float* act_depth, float* act_depth0, void* stream);
+int ph_panoptic_argmax_batch(const float* act_mask, const float* scores, int64_t scores_batch_stride, int B, int K,
+                             const int32_t* geom, int from_probs, int generic_only, int32_t* ids, int32_t* counts,
+                             int64_t counts_batch_stride, void* stream);
+int ph_panoptic_paste_batch(const int32_t* ids, const int32_t* newid, int64_t newid_batch_stride, const float* act_depth,
+                            const float* act_depth0, int B, int K, const int32_t* geom, int from_probs, int32_t* pan,
+                            float* depth_basic, float* depth_final, void* stream);
+size_t ph_panoptic_merge_workspace_bytes(int B, int K, int h2, int w2, const int32_t* geom);
+int ph_panoptic_merge(const float* cls /*[B][N][L]*/, const void* mask_up, const void* depth_up, int dtype,
+                      const float* depth_init_up /*[B][h2][w2]*/, int B, int N, int L, int num_proposals, int num_thing_classes,
+                      int max_per_img, int h2, int w2, const int32_t* geom /*one for the batch*/, int depth_mode,
+                      double instance_score_thr, double overlap_thr, void* workspace, size_t workspace_bytes,
+                      int32_t* pan /*[B][Ho][Wo]*/, float* depth_basic, float* depth_final,
+                      int32_t* seg_records /*[B][1 + 5K]: nseg | seg[K][4] | scores[K] as fp32 bits*/, void* stream);
 
 /* ---- device side of the video association step (polyphonic_former_video.py:359-396) ----------
  * ph_segment_boxes : int32 panoptic id map [H][W], segment ids 1..nseg -> rois [nseg][5] = (0, x1, y1, x2, y2)

@@ -139,6 +139,13 @@ SIGNATURES = {
     "ph_panoptic_activate": (C.c_int, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "ph_panoptic_argmax": (C.c_int, [_P, _P, _I, C.POINTER(C.c_int32), _I, _P, _P, _P]),
     "ph_panoptic_paste": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int32), _I, _P, _P, _P, _P]),
+    "ph_panoptic_accept": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, C.c_double, C.c_double, _P, _L, _P, _P, _L, _P]),
+    "ph_panoptic_activate_batch": (C.c_int, [_P, _P, _I, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "ph_panoptic_argmax_batch": (C.c_int, [_P, _P, _L, _I, _I, C.POINTER(C.c_int32), _I, _I, _P, _P, _L, _P]),
+    "ph_panoptic_paste_batch": (C.c_int, [_P, _P, _L, _P, _P, _I, _I, C.POINTER(C.c_int32), _I, _P, _P, _P, _P]),
+    "ph_panoptic_merge_workspace_bytes": (C.c_size_t, [_I, _I, _I, _I, C.POINTER(C.c_int32)]),
+    "ph_panoptic_merge": (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, C.c_double,
+                                    C.c_double, _P, _Z, _P, _P, _P, _P, _P]),
     "ph_segment_boxes_workspace_bytes": (C.c_size_t, [_I]),
     "ph_segment_boxes": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "ph_roi_align_fpn": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_float), _I, _P, _I, C.c_float,

@@ -85,6 +85,14 @@ class KernelUpdateIterHead(nn.Module):
         self._plans.clear()
         return self
 
+    # opt-in: the panoptic merge of simple_test as ONE launch-only call for the whole batch (panoptic.get_panoptic_batch,
+    # ph_panoptic_merge: accept step on the device) instead of a per-image loop with a host accept loop; same values
+    device_merge = False
+
+    def use_device_merge(self, flag=True):
+        self.device_merge = bool(flag)
+        return self
+
     def _plan(self, B, N, H, W, device):
         packs = [h.stage_pack(device, self.precision) for h in self.mask_head]
         native = bool(self.native_plan)
@@ -158,7 +166,10 @@ class KernelUpdateIterHead(nn.Module):
             raise NotImplementedError        # as the reference (:353)
         o = self._decode(x, proposal_feats, mask_preds, depth_feats, depth_proposal)
         depth_init = E.upsample2x(depth_preds.float().contiguous())            # :302-307
-        from .panoptic import get_panoptic
+        from . import panoptic
+        if self.device_merge:
+            return panoptic.get_panoptic_batch(self, o["cls"], o["mask_up"], o["depth_up"], depth_init, img_metas)
+        get_panoptic = panoptic.get_panoptic
         results = []
         for b in range(len(img_metas)):
             results.append(get_panoptic(self, o["cls"][b], o["mask_up"][b], o["depth_up"][b], depth_init[b],

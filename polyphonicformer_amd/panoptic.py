@@ -232,3 +232,142 @@ class DeviceMerge:
                                          0, _lib.ptr(pan), _lib.ptr(d_basic), _lib.ptr(d_final), _lib.stream_ptr()), "ph_panoptic_paste")
         return pan, info, d_basic, d_final
 
+
+
+def segments_from_records(records_row, K, num_thing_classes):
+    """One frame's record row of `ph_panoptic_merge` -- int32 [1 + 5K]: nseg | seg[K][4] = {new id, candidate index k, label,
+    area} in id order | scores[K] as fp32 bits -- as the reference's `segments_info`: the list `accept_loop` returns, with the
+    same keys, Python types and values.  Pure host code."""
+    row = np.ascontiguousarray(np.asarray(records_row, dtype=np.int32).reshape(-1))
+    if row.shape[0] != 1 + 5 * K:
+        raise ValueError(f"a record row of K = {K} candidates has {1 + 5 * K} entries, got {row.shape[0]}")
+    nseg = int(row[0])
+    seg = row[1:1 + 4 * K].reshape(K, 4)
+    scores = row[1 + 4 * K:].view(np.float32)
+    info = []
+    for seg_id, k, cls, area in seg[:nseg].tolist():
+        if cls < num_thing_classes:
+            info.append({'id': seg_id, 'isthing': True, 'score': float(scores[k]), 'category_id': cls, 'instance_id': k})
+        else:
+            info.append({'id': seg_id, 'isthing': False, 'category_id': cls, 'area': area})
+    return info
+
+
+_DTYPE_CODES = {torch.float32: _lib.PH_OUT_F32, torch.bfloat16: _lib.PH_OUT_BF16, torch.float16: _lib.PH_OUT_F16}
+
+
+class BatchMerge:
+    """The whole merge for B frames of one head and ONE geometry as a single launch-only call (`ph_panoptic_merge`): select ->
+    activate -> clear + argmax -> accept (on the device, `ph_panoptic_accept`) -> paste, one launch per kernel for the batch.
+    `run` neither allocates nor synchronises and reads static buffers only, so it can be captured with `torch.cuda.graph`;
+    `download` queues the D2H copies of the three maps and the per-frame records; after the caller's sync `results` /
+    `results_device` build the reference's return values (segments_info from the records: `segments_from_records`).
+    Same kernels and values as `DeviceMerge` + `accept_loop`; the candidate ORDER among exactly equal scores is
+    `ph_panoptic_select`'s, ascending index (the reference's topk / sort leave it unspecified)."""
+
+    def __init__(self, head, B, N, L, h2, w2, logits_dtype, img_meta, device):
+        if not head.merge_joint:
+            raise NotImplementedError               # as the reference (:467-468)
+        if logits_dtype not in _DTYPE_CODES:
+            raise _lib.PolyheadError("mask/depth logits must both be fp32, both bf16 or both fp16")
+        lib = _lib.load()
+        self.head, self.device, self.logits_dtype = head, torch.device(device), logits_dtype
+        self.B, self.N, self.L, self.h2, self.w2 = B, N, L, h2, w2
+        self.K = K = head.test_cfg.max_per_img + min(N - head.num_proposals, L - head.num_thing_classes)
+        self.dt = _DTYPE_CODES[logits_dtype]
+        self.mode = DEPTH_MODES[head.mask_head[-1].depth_act_mode]
+        self.geom, self.out_hw = _geom((h2, w2), img_meta)
+        Ho, Wo = self.out_hw
+        self.ws_bytes = int(lib.ph_panoptic_merge_workspace_bytes(B, K, h2, w2, self.geom))
+        if self.ws_bytes == 0:
+            raise _lib.PolyheadError(f"ph_panoptic_merge_workspace_bytes: {lib.ph_last_error_string().decode()}")
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+        self.workspace = e((self.ws_bytes,), torch.uint8)
+        self.pan, self.d_basic, self.d_final = e((B, Ho, Wo), torch.int32), e((B, Ho, Wo), torch.float32), e((B, Ho, Wo), torch.float32)
+        self.records = e((B, 1 + 5 * K), torch.int32)
+        self.host = None
+        self._keep = None
+
+    def run(self, cls, mask_up, depth_up, depth_init):
+        """cls [B,N,L] (post-sigmoid, fp32), mask_up / depth_up [B,N,2H,2W] logits, depth_init [B,1,2H,2W] (or [B,2H,2W]) fp32
+        logits, all contiguous on the device: ONE native call, launches only"""
+        B, N, L, h2, w2 = self.B, self.N, self.L, self.h2, self.w2
+        if tuple(cls.shape) != (B, N, L) or tuple(mask_up.shape) != (B, N, h2, w2) or tuple(depth_up.shape) != (B, N, h2, w2) \
+                or depth_init.numel() != B * h2 * w2:
+            raise _lib.PolyheadError("BatchMerge.run: input shapes differ from the ones it was built for")
+        if mask_up.dtype != self.logits_dtype or depth_up.dtype != self.logits_dtype:
+            raise _lib.PolyheadError("BatchMerge.run: logits dtype differs from the one it was built for")
+        cls, d0 = cls.detach().float().contiguous(), depth_init.float().contiguous()
+        m, d = mask_up.contiguous(), depth_up.contiguous()
+        self._keep = (cls, m, d, d0)                        # alive until the launches have run (static under graph capture)
+        head, mc = self.head, self.head.test_cfg.merge_stuff_thing
+        _lib.check(_lib.load().ph_panoptic_merge(
+            _lib.ptr(cls), _lib.ptr(m), _lib.ptr(d), self.dt, _lib.ptr(d0), B, N, L, head.num_proposals, head.num_thing_classes,
+            head.test_cfg.max_per_img, h2, w2, self.geom, self.mode, float(mc.instance_score_thr), float(mc.overlap_thr),
+            _lib.ptr(self.workspace), self.ws_bytes, _lib.ptr(self.pan), _lib.ptr(self.d_basic), _lib.ptr(self.d_final),
+            _lib.ptr(self.records), _lib.stream_ptr()), "ph_panoptic_merge")
+
+    def download(self):
+        """the three maps and the records to pinned host memory, asynchronously on the current stream (not part of a captured
+        graph).  Fresh pinned buffers per call (torch's caching host allocator): earlier results stay valid."""
+        self.host = []
+        for t in (self.pan, self.d_basic, self.d_final, self.records):
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            self.host.append(h)
+
+    def _infos(self):
+        rec = self.host[3].numpy()
+        return [segments_from_records(rec[b], self.K, self.head.num_thing_classes) for b in range(self.B)]
+
+    def results(self):
+        """after the caller has synchronised with `download`: per frame the reference tuple
+        (None, None, (panoptic_seg int32 ndarray, segments_info), depth_basic, depth_final)"""
+        pan, d_basic, d_final = (h.numpy() for h in self.host[:3])
+        return [(None, None, (pan[b], info), d_basic[b], d_final[b]) for b, info in enumerate(self._infos())]
+
+    def results_device(self):
+        """after the caller has synchronised with `download`: per frame what `merge_on_device` returns -- the three maps as
+        DEVICE tensors (views of this object's static outputs: the next `run` overwrites them) and the host segments_info"""
+        return [(self.pan[b], info, self.d_basic[b], self.d_final[b]) for b, info in enumerate(self._infos())]
+
+
+def _geom_key(meta):
+    return (tuple(meta['img_shape'][:2]), tuple(meta['batch_input_shape']), tuple(meta['ori_shape'][:2]))
+
+
+def get_panoptic_batch(head, cls_scores, mask_preds, depth_preds, depth_init, img_metas):
+    """`get_panoptic` for a whole batch: cls_scores [B,N,L] (post-sigmoid), mask_preds / depth_preds [B,N,2H,2W] logits,
+    depth_init [B,1,2H,2W] fp32 logits, one img_meta per frame.  Frames are grouped by geometry (img_shape, batch_input_shape,
+    ori_shape); each group is one `BatchMerge` -- one launch-only native call -- and there is ONE synchronisation in total.
+    Returns, in frame order, what `get_panoptic` returns per frame.  Candidate order among exactly equal scores is
+    `ph_panoptic_select`'s (ascending index), where `get_panoptic` has torch.topk's / torch.sort's."""
+    B = len(img_metas)
+    _, N, L = cls_scores.shape
+    h2, w2 = mask_preds.shape[-2:]
+    if mask_preds.dtype != depth_preds.dtype:
+        raise _lib.PolyheadError("mask/depth logits must both be fp32, both bf16 or both fp16")
+    dev = mask_preds.device
+    groups = {}
+    for b, meta in enumerate(img_metas):
+        groups.setdefault(_geom_key(meta), []).append(b)
+    d0 = depth_init.reshape(-1, h2, w2)
+    merges = []
+    for frames in groups.values():
+        if frames == list(range(cls_scores.shape[0])):
+            ins = (cls_scores, mask_preds, depth_preds, d0)
+        elif frames == list(range(frames[0], frames[0] + len(frames))):     # a contiguous run of frames: views, no copy
+            ins = tuple(t[frames[0]:frames[0] + len(frames)] for t in (cls_scores, mask_preds, depth_preds, d0))
+        else:
+            idx = torch.tensor(frames, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            ins = tuple(t.index_select(0, idx) for t in (cls_scores, mask_preds, depth_preds, d0))
+        bm = BatchMerge(head, len(frames), N, L, h2, w2, mask_preds.dtype, img_metas[frames[0]], dev)
+        bm.run(*ins)
+        bm.download()
+        merges.append((frames, bm))
+    torch.cuda.current_stream().synchronize()
+    out = [None] * B
+    for frames, bm in merges:
+        for b, r in zip(frames, bm.results()):
+            out[b] = r
+    return out
