@@ -789,6 +789,134 @@ int ph_decode_info(const ph_decode* plan, ph_decode_geometry* out);
 void ph_decode_destroy(ph_decode* plan);
 int ph_decode_run(ph_decode* plan, const ph_decode_io* io, void* stream);
 
+/* ---- A1 as a native object (csrc/ph_kheadplan.hip): what engine.KernelHeadPack + engine.KernelHeadPlan do from Python --
+ * kernel_head.py:245-347 (_decode_init_proposals after localization_fpn) for a C / C++ caller: from the neck's three maps to
+ * the feature planes, the mask bits, the mask / seg / depth logits and proposal_feats, i.e. to every input of ph_decode_run
+ * (PH_FEAT_PLANES: x = xp, depth_feats = dp, bits = bits, k0 = proposal, q0 = depth_proposal).  Conventions are ph_decode_*'s:
+ * status codes + ph_last_error_string, caller-owned memory, no allocation of device memory, no synchronisation and no host read
+ * of device data in pack / create / run, every argument or geometry error returned before the first launch.  No ph_khead_plan_*
+ * / ph_khead_pack* function reads the environment: the plan's launches go through internal forms of ph_khead_onepass /
+ * ph_khead_fused_if that take their launch knobs as arguments (the public entry points keep reading PH_KHEAD1_PAIR /
+ * PH_NECK_STATS3 / PH_NECK_APPLY3), and what engine.KernelHeadPlan reads from PH_KHEAD_TWOPASS / PH_POOL_NSPLIT are the cfg's
+ * `onepass` / `nsplit` fields.  The only process-wide setting a plan honours is ph_khead_onepass_set_timeout_us.
+ * A zero-initialised ph_khead_cfg plus the sizes and the mode is the module API's configuration.
+ *   mode         PH_MODE_*, mapped to a1's grade as engine.KHEAD_PREC maps the precision names: PH_MODE_FP16 -> PH_PREC_F16 (one
+ *                fp16 plane; pairs with a PH_MODE_FP16 decode plan), PH_MODE_BF16 -> PH_PREC_BF16 (one bf16 plane; pairs with
+ *                PH_MODE_BF16 / _MIXED / _MIXED16 decode plans), every other mode -> PH_PREC_SPLIT (hi + lo bf16 planes; pairs
+ *                with PH_MODE_FP32)
+ *   logit_dtype  PH_OUT_F32 or PH_OUT_F16 (one-pass form only) of mask_preds / seg_preds / depth_pred
+ *   emit_f32     1: the fp32 NCHW x_feats / depth_feats of the reference API are written too (ph_khead_io x_f32 / dfe_f32)
+ *   onepass      PH_KNOB_AUTO: ph_khead_onepass wherever ph_khead_onepass_supported(B, H*W, groups, grade, PH_IN_F32_NCHW) says so
+ *                (engine.KernelHeadPlan's rule with no environment variable set); PH_KNOB_ON: the same, PH_EUNSUPPORTED where
+ *                it says no; PH_KNOB_OFF: always the two-pass ph_khead_fused (PH_KHEAD_TWOPASS of the Python plan)
+ *   nsplit       0 = engine.default_nsplit(B, H*W, frame_invariant), else the pixel ranges of the object pooling (PH_POOL_NSPLIT) */
+typedef struct {
+    int32_t B, H, W;            /* frames, feature map (stride 8) */
+    int32_t num_proposals;      /* rows of init_kernels (thing queries), 1 .. 256 */
+    int32_t num_classes;        /* rows of conv_seg, 1 .. 256 */
+    int32_t num_thing_classes;  /* <= num_classes; the stuff rows of conv_seg are [num_thing_classes, num_classes) */
+    int32_t cat_stuff;          /* 1: the stuff rows are appended to mask_preds / proposal (cat_stuff_mask, inference) */
+    int32_t groups;             /* GroupNorm groups (divides 256) */
+    int32_t mode;               /* PH_MODE_* */
+    int32_t logit_dtype;        /* PH_OUT_F32 / PH_OUT_F16 */
+    int32_t emit_f32;
+    int32_t frame_invariant;    /* 1: the pooling split of a one-frame launch at any B (the module API's default) */
+    int32_t onepass;            /* PH_KNOB_AUTO / _ON / _OFF */
+    int32_t nsplit;
+} ph_khead_cfg;
+
+/* ---- the parameter table: the 14 fp32 tensors of KernelHead's own state_dict (reference names) that the pack is made of
+ *    0 loc_convs.0.conv.weight [256][256][1][1]   1 loc_convs.0.gn.weight [256]   2 loc_convs.0.gn.bias [256]
+ *    3 .. 5 seg_convs.0.*  and  6 .. 8 depth_convs.0.*  in the same order
+ *    9 init_kernels.weight [num_proposals][256][1][1]
+ *   10 conv_seg.weight [num_classes][256][1][1]   11 conv_seg.bias [num_classes]
+ *   12 conv_direct_depth.weight [1][256][1][1]    13 conv_direct_depth.bias [1] */
+#define PH_KHEAD_NPARAMS 14
+const char* ph_khead_param_name(int index);                        /* NULL out of range */
+int64_t ph_khead_param_numel(const ph_khead_cfg* cfg, int index);  /* elements; < 0 out of range */
+
+/* ---- packing (k_khead_pack: one launch, once per weight load).  The pieces are engine.KernelHeadPack's tensors, byte for byte
+ * (nothing is folded: fp32 -> bf16 / fp16 round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned
+ * offset of one device buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT),
+ * rows32(n) = n rounded up to 32 (pad rows zero):
+ *   WPLANES      uint16 [P][3][256][256]            {loc,seg,depth}_convs.0.conv.weight
+ *   GN           float  [3][2][256]                 (gamma, beta) of the three GroupNorms
+ *   INIT_PLANES  uint16 [P][rows32(num_proposals)][256]     SEG_PLANES [P][rows32(num_classes)][256]     DD_PLANES [P][32][256]
+ *   SEG_BIAS     float  [rows32(num_classes)]               DD_BIAS float [32]
+ *   INIT_FRAG / SEG_FRAG / DD_FRAG   the three planes as MFMA 32x32x16 A fragments (ph_khead_fused's w2_*)
+ *   CONV_FRAG    uint16 [3][8][16][64][8], one-plane grades only (0 bytes for PH_PREC_SPLIT): ph_khead_onepass's conv_frags
+ *   W_INIT_F32 [num_proposals][256], W_SEG_F32 [num_classes][256], W_DD_F32 [256]   fp32 copies (ph_khead_proposals) */
+enum { PH_KPACK_WPLANES = 0, PH_KPACK_GN, PH_KPACK_INIT_PLANES, PH_KPACK_SEG_PLANES, PH_KPACK_DD_PLANES, PH_KPACK_SEG_BIAS,
+       PH_KPACK_DD_BIAS, PH_KPACK_INIT_FRAG, PH_KPACK_SEG_FRAG, PH_KPACK_DD_FRAG, PH_KPACK_CONV_FRAG, PH_KPACK_W_INIT_F32,
+       PH_KPACK_W_SEG_F32, PH_KPACK_W_DD_F32, PH_KPACK_COUNT };
+typedef struct {
+    uint64_t offset[PH_KPACK_COUNT];   /* bytes from the start of the pack, multiples of 256 */
+    uint64_t bytes[PH_KPACK_COUNT];    /* size of the piece; the next piece starts at offset + bytes rounded up to 256 */
+} ph_khead_layout;
+size_t ph_khead_pack_bytes(const ph_khead_cfg* cfg);               /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_khead_pack_layout(const ph_khead_cfg* cfg, ph_khead_layout* layout);
+/* `params`: host array of PH_KHEAD_NPARAMS device pointers; `pack`: 256-byte aligned device buffer of ph_khead_pack_bytes */
+int ph_khead_pack(const ph_khead_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- plan lifetime.  The workspace holds the one-pass launch's hand-off state (one-pass plans), the two-pass kernels'
+ * workspace (the path itself, or the in-call fallback of a one-pass launch that gave up) and the pooled partial sums.
+ * ZEROING CONTRACT: the caller zeroes the whole workspace ONCE (hipMemset) before ph_khead_plan_create and never again --
+ * ph_khead_onepass clears its hand-off state on every call except the sticky time-out words, which count from that one
+ * zeroing on.  ph_khead_plan_create itself touches no device memory.  The caller keeps pack and workspace alive as long as
+ * the plan; both 256-byte aligned. */
+typedef struct ph_khead_plan ph_khead_plan;
+typedef struct {
+    int32_t onepass;            /* 1: ph_khead_onepass + the predicated fallback; 0: ph_khead_fused + ph_binarize */
+    int32_t nsplit;             /* pixel ranges of the object pooling */
+    int32_t N;                  /* num_proposals + stuff rows: rows of mask_preds / proposal */
+    int32_t Npad;               /* N rounded up to 32: rows of bits */
+    int32_t HWp;                /* H * W rounded up to 128 */
+    int32_t P;                  /* planes of xp / dp */
+    int32_t prec;               /* the grade, PH_PREC_* */
+    int32_t n_stuff;
+} ph_khead_geometry;
+size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg);     /* 0 on a bad cfg */
+int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_khead_plan** out);
+int ph_khead_plan_info(const ph_khead_plan* plan, ph_khead_geometry* out);
+void ph_khead_plan_destroy(ph_khead_plan* plan);
+
+/* ---- one a1 call.  Inputs f0 / f1 / f2: the neck's three maps, fp32 NCHW [B][256][H][W] (PH_IN_F32_NCHW) or 16-bit planes
+ * [P][B][256][HWp] of the grade's format, zero in [H*W, HWp) (PH_IN_PLANES).  Outputs are the caller's, per call:
+ *   xp, dp          uint16 [P][B][256][HWp]      x and depth_feats planes      -> ph_decode_io.x / .depth_feats (PH_FEAT_PLANES)
+ *   bits            uint32 [B][Npad][HWp/32]     hard masks of mask_preds      -> ph_decode_io.bits
+ *   x_f32, dfe_f32  float [B][256][H][W]         non-NULL exactly when cfg.emit_f32
+ *   mask_preds [B][N][H][W], seg_preds [B][num_classes][H][W], depth_pred [B][1][H][W]   logit_dtype
+ *                   (ph_upsample2x of depth_pred is ph_panoptic_merge's depth_init_up)
+ *   proposal        float [B][N][256]            proposal_feats                -> ph_decode_io.k0
+ *   depth_proposal  float [B][N][256], nullable  conv_direct_depth.weight in every row (the reference hands it on as a
+ *                   stride-0 view, kernel_head.py:286-289; ph_decode_io.q0 wants it dense)   -> ph_decode_io.q0
+ * The launch sequence is engine.KernelHeadPlan.run's: one-pass plans ph_khead_onepass, ph_khead_fused_if and ph_binarize_if
+ * predicated on its status word, two-pass plans ph_khead_fused and ph_binarize; then ph_pool_rows and ph_khead_proposals (and
+ * the depth_proposal broadcast).  Capturable into a hipGraph.
+ * ph_khead_plan_status: 1 if the last run of a one-pass plan gave up and was redone by the two-pass kernels inside the same
+ * call; ph_khead_plan_timeouts: workgroup time-outs since the workspace was zeroed; both 0 for two-pass plans, negative on a
+ * runtime error, and both SYNCHRONISE the stream (they read device words). */
+typedef struct {
+    int32_t input_format;       /* PH_IN_F32_NCHW / PH_IN_PLANES */
+    int32_t reserved;           /* 0 */
+    const void* f0;
+    const void* f1;
+    const void* f2;
+    uint16_t* xp;
+    uint16_t* dp;
+    uint32_t* bits;
+    float* x_f32;
+    float* dfe_f32;
+    void* mask_preds;
+    void* seg_preds;
+    void* depth_pred;
+    float* proposal;
+    float* depth_proposal;
+} ph_khead_io;
+int ph_khead_plan_run(ph_khead_plan* plan, const ph_khead_io* io, void* stream);
+int ph_khead_plan_status(const ph_khead_plan* plan, void* stream);
+int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

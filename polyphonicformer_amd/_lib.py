@@ -55,6 +55,32 @@ class DecodeIO(C.Structure):
                                    "depth")]
 
 
+# the native KernelHead plan (polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts)
+PH_KHEAD_NPARAMS = 14
+KPACK_PIECES = ("wplanes", "gn", "init_planes", "seg_planes", "dd_planes", "seg_bias", "dd_bias", "init_frag", "seg_frag", "dd_frag",
+                "conv_frag", "w_init_f32", "w_seg_f32", "w_dd_f32")        # PH_KPACK_*; engine.KernelHeadPack's attribute names
+PH_KPACK_COUNT = len(KPACK_PIECES)
+
+
+class KheadCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "num_proposals", "num_classes", "num_thing_classes", "cat_stuff", "groups",
+                                          "mode", "logit_dtype", "emit_f32", "frame_invariant", "onepass", "nsplit")]
+
+
+class KheadLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * PH_KPACK_COUNT), ("bytes", C.c_uint64 * PH_KPACK_COUNT)]
+
+
+class KheadGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("onepass", "nsplit", "N", "Npad", "HWp", "P", "prec", "n_stuff")]
+
+
+class KheadIO(C.Structure):
+    _fields_ = [("input_format", C.c_int32), ("reserved", C.c_int32)] + \
+        [(n, C.c_void_p) for n in ("f0", "f1", "f2", "xp", "dp", "bits", "x_f32", "dfe_f32", "mask_preds", "seg_preds", "depth_pred",
+                                   "proposal", "depth_proposal")]
+
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
@@ -188,6 +214,18 @@ SIGNATURES = {
     "ph_decode_info": (C.c_int, [_P, C.POINTER(DecodeGeometry)]),
     "ph_decode_destroy": (None, [_P]),
     "ph_decode_run": (C.c_int, [_P, C.POINTER(DecodeIO), _P]),
+    "ph_khead_param_name": (C.c_char_p, [_I]),
+    "ph_khead_param_numel": (C.c_int64, [C.POINTER(KheadCfg), _I]),
+    "ph_khead_pack_bytes": (C.c_size_t, [C.POINTER(KheadCfg)]),
+    "ph_khead_pack_layout": (C.c_int, [C.POINTER(KheadCfg), C.POINTER(KheadLayout)]),
+    "ph_khead_pack": (C.c_int, [C.POINTER(KheadCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_khead_plan_workspace_bytes": (C.c_size_t, [C.POINTER(KheadCfg)]),
+    "ph_khead_plan_create": (C.c_int, [C.POINTER(KheadCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_khead_plan_info": (C.c_int, [_P, C.POINTER(KheadGeometry)]),
+    "ph_khead_plan_destroy": (None, [_P]),
+    "ph_khead_plan_run": (C.c_int, [_P, C.POINTER(KheadIO), _P]),
+    "ph_khead_plan_status": (C.c_int, [_P, _P]),
+    "ph_khead_plan_timeouts": (C.c_int, [_P, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

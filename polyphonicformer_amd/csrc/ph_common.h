@@ -64,6 +64,27 @@ int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int ns
                             float* obj, float* dobj, float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                             size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream);
 
+// launch knobs of KernelHead's post-neck kernels, in the same way: the public ph_khead_onepass / ph_khead_fused[_if] / ph_khead_conv_gn /
+// ph_neck_out_convs fill them from PH_KHEAD1_PAIR / PH_NECK_STATS3 / PH_NECK_APPLY3; the native KernelHead plan (ph_kheadplan.hip)
+// passes the defaults
+struct PhKheadKnobs {
+    bool pair = false;           // PH_KHEAD1_PAIR: two 64-pixel workgroups per CU (builds with -DK1_WITH_PAIR only)
+    bool stats3 = true;          // PH_NECK_STATS3=0: the 3-D statistics grid when the three maps share one input
+    bool apply3 = true;          // PH_NECK_APPLY3=0: plain mode's apply pass as one launch per map
+};
+int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
+                       const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init, const uint16_t* w2_seg,
+                       const float* bias_seg, int n_seg, const uint16_t* w2_dd, const float* bias_dd, int stuff_lo, int n_stuff,
+                       uint16_t* x_planes, uint16_t* dfe_planes, float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds,
+                       void* depth_pred, int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
+                       int64_t HW, int prec, int input_format, void* stream);
+int ph_khead_fused_if_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,
+                        const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init, const uint16_t* w2_seg,
+                        const float* bias_seg, int n_seg, const uint16_t* w2_dd, const float* bias_dd, int stuff_lo, int n_stuff,
+                        uint16_t* x_planes, uint16_t* dfe_planes, float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds,
+                        void* depth_pred, int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
+                        int64_t HW, int prec, int input_format, void* stream);
+
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects
 // it for fp32 -> __bf16 conversions.

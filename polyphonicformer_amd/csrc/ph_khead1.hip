@@ -760,20 +760,27 @@ extern "C" size_t ph_khead_onepass_workspace_bytes(int B, int64_t HW) { return k
 static int g_k1_timeout_us = 20000;
 extern "C" void ph_khead_onepass_set_timeout_us(int us) { g_k1_timeout_us = us > 0 ? us : 20000; }
 
-extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
-                                const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
-                                const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
-                                const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
-                                float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
-                                int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
-                                int64_t HW, int prec, int input_format, void* stream) {
-    PH_CHECK_ARG(f0 && f1 && f2 && conv_frags && gn_affine && x_planes && dfe_planes && workspace, "null pointer");
-    PH_CHECK_ARG(w2_init && w2_seg && w2_dd && mask_preds && seg_preds && depth_pred, "null pointer");
-    PH_CHECK_ARG(input_format == PH_IN_F32_NCHW || input_format == PH_IN_PLANES, "bad input_format");
-    PH_CHECK_ARG(out_dtype == PH_OUT_F32 || out_dtype == PH_OUT_F16, "logits: PH_OUT_F32 or PH_OUT_F16");
-    PH_CHECK_ARG(n_init > 0 && n_init <= 256 && n_seg > 0 && n_seg <= 256 && n_stuff >= 0 && stuff_lo >= 0 &&
-                     stuff_lo + n_stuff <= n_seg, "bad row counts (at most 256 rows per static conv)");
-    PH_CHECK_ARG(!bits || (bits_rows >= n_init + n_stuff && bits_rows <= 256), "bits_rows out of range");
+int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
+                       const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
+                       const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
+                       const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
+                       float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
+                       int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
+                       int64_t HW, int prec, int input_format, void* stream) {
+#define K1_ARG(cond, msg)                                          \
+    do {                                                           \
+        if (!(cond)) {                                             \
+            ph_set_error("ph_khead_onepass: %s", msg);             \
+            return PH_EINVAL;                                      \
+        }                                                          \
+    } while (0)
+    K1_ARG(f0 && f1 && f2 && conv_frags && gn_affine && x_planes && dfe_planes && workspace, "null pointer");
+    K1_ARG(w2_init && w2_seg && w2_dd && mask_preds && seg_preds && depth_pred, "null pointer");
+    K1_ARG(input_format == PH_IN_F32_NCHW || input_format == PH_IN_PLANES, "bad input_format");
+    K1_ARG(out_dtype == PH_OUT_F32 || out_dtype == PH_OUT_F16, "logits: PH_OUT_F32 or PH_OUT_F16");
+    K1_ARG(n_init > 0 && n_init <= 256 && n_seg > 0 && n_seg <= 256 && n_stuff >= 0 && stuff_lo >= 0 &&
+               stuff_lo + n_stuff <= n_seg, "bad row counts (at most 256 rows per static conv)");
+    K1_ARG(!bits || (bits_rows >= n_init + n_stuff && bits_rows <= 256), "bits_rows out of range");
     if (!ph_khead_onepass_supported(B, HW, groups, prec, input_format)) {
         ph_set_error("ph_khead_onepass: unsupported geometry or precision (use ph_khead_fused)");
         return PH_EUNSUPPORTED;
@@ -823,8 +830,9 @@ extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, 
     // over the whole chip, so the two workgroups of a CU sit in the same phase of the same frame and wait for the same
     // statistics together, and the exchange itself grows from 10-11k to 16-20k cycles per phase with twice the workgroups.
     const int cus = k1_cus();
+    (void)kn;
 #ifdef K1_WITH_PAIR
-    static const bool want_pair = getenv("PH_KHEAD1_PAIR") != nullptr;
+    const bool want_pair = kn.pair;
 #define K1_GO(I_, E_, O_, F_)                                                                                      \
     do {                                                                                                           \
         static const int pair_ok_ = [] {                                                                           \
@@ -876,8 +884,34 @@ extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, 
     else K1_GO_F(2, PH_E_F16, uint16_t);
 #undef K1_GO_F
 #undef K1_GO
-    PH_CHECK_LAUNCH();
+    {
+        hipError_t e_ = hipGetLastError();
+        if (e_ != hipSuccess) {
+            ph_set_error("ph_khead_onepass: launch failed: %s", hipGetErrorString(e_));
+            return PH_ELAUNCH;
+        }
+    }
     return PH_OK;
+}
+#undef K1_ARG
+
+// the public entry point: the geometry switch is an environment variable (builds with -DK1_WITH_PAIR only), read once per process;
+// the native KernelHead plan (ph_kheadplan.hip) calls the _k form with the defaults and reads none
+extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
+                                const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
+                                const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
+                                const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
+                                float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
+                                int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
+                                int64_t HW, int prec, int input_format, void* stream) {
+    PhKheadKnobs kn;
+#ifdef K1_WITH_PAIR
+    static const bool want_pair = getenv("PH_KHEAD1_PAIR") != nullptr;
+    kn.pair = want_pair;
+#endif
+    return ph_khead_onepass_k(kn, f0, f1, f2, conv_frags, gn_affine, groups, eps, w2_init, n_init, w2_seg, bias_seg, n_seg, w2_dd, bias_dd,
+                              stuff_lo, n_stuff, x_planes, dfe_planes, x_f32, dfe_f32, mask_preds, seg_preds, depth_pred, out_dtype, bits,
+                              bits_rows, workspace, workspace_bytes, B, HW, prec, input_format, stream);
 }
 
 // 1 if the last ph_khead_onepass call on this workspace gave up (a hand-off wait timed out; its caller's predicated fallback

@@ -1,0 +1,399 @@
+// A1 as a native object (include/polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts): the parameter packing of
+// engine.KernelHeadPack as one HIP kernel, and the geometry rules, the buffer plan and the launch sequence of
+// engine.KernelHeadPlan.  Host code only calls the other entry points of this library, on the caller's stream; pack / create /
+// run allocate no device memory, do not synchronise and read no environment variable.
+#include <string.h>
+
+#include <new>
+
+#include "ph_common.h"
+
+#pragma clang fp contract(off)
+
+// ---------------------------------------------------------------------------------------------
+// parameter table (polyhead.h: the reference's state_dict names of KernelHead's own layers)
+static const char* const kParamNames[PH_KHEAD_NPARAMS] = {
+    "loc_convs.0.conv.weight", "loc_convs.0.gn.weight", "loc_convs.0.gn.bias",
+    "seg_convs.0.conv.weight", "seg_convs.0.gn.weight", "seg_convs.0.gn.bias",
+    "depth_convs.0.conv.weight", "depth_convs.0.gn.weight", "depth_convs.0.gn.bias",
+    "init_kernels.weight", "conv_seg.weight", "conv_seg.bias", "conv_direct_depth.weight", "conv_direct_depth.bias"};
+enum { P_CONV = 0, P_INIT = 9, P_SEG = 10, P_SEG_B = 11, P_DD = 12, P_DD_B = 13 };
+
+static int64_t param_numel(const ph_khead_cfg* c, int i) {
+    if (i < 0 || i >= PH_KHEAD_NPARAMS) return -1;
+    if (i < P_INIT) return i % 3 == 0 ? 256 * 256 : 256;
+    if (i == P_INIT) return (int64_t)c->num_proposals * 256;
+    if (i == P_SEG) return (int64_t)c->num_classes * 256;
+    if (i == P_SEG_B) return c->num_classes;
+    return i == P_DD ? 256 : 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// geometry: engine.KernelHeadPlan.__init__'s choices, with the environment replaced by the cfg's fields
+struct KGeo {
+    int B, H, W, Nq, n_seg, n_thing, n_stuff, N, Npad, NqPad, groups, prec, P, logit_dtype, logit_bytes, emit_f32, onepass, nsplit;
+    int64_t HW, HWp;
+    size_t ws1_bytes, ws2_bytes, o_ws1, o_ws2, o_partial, total;     // workspace pieces
+    ph_khead_layout lay;                                             // pack pieces
+    size_t pack_total;
+};
+
+static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
+static int default_nsplit(int B, int64_t HWp, bool fi) {   // engine.default_nsplit without PH_POOL_NSPLIT
+    const int64_t nchunks = HWp / 128;
+    int ns = 512 / (4 * (fi ? 1 : B));
+    if (ns < 1) ns = 1;
+    const int64_t r = ns < 32 ? ns : 32;
+    const int64_t c = nchunks > 1 ? nchunks : 1;
+    return (int)(r < c ? r : c);
+}
+
+// `need_device`: the one-pass rule asks the current device for its CU count; the pack entry points do not need it
+static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn, bool need_device) {
+    if (!c) { ph_set_error("%s: null cfg", fn); return PH_EINVAL; }
+    g = KGeo{};
+    g.B = c->B; g.H = c->H; g.W = c->W; g.Nq = c->num_proposals; g.n_seg = c->num_classes; g.n_thing = c->num_thing_classes;
+    g.groups = c->groups;
+    if (!(g.B > 0 && g.H > 0 && g.W > 0)) { ph_set_error("%s: bad size (B, H, W > 0)", fn); return PH_EINVAL; }
+    if ((int64_t)g.H * g.W > (1ll << 30)) { ph_set_error("%s: H * W must be <= 2^30", fn); return PH_EUNSUPPORTED; }
+    if (g.B > 4096) { ph_set_error("%s: at most 4096 frames per call", fn); return PH_EUNSUPPORTED; }
+    if (!(g.Nq > 0 && g.Nq <= 256)) { ph_set_error("%s: num_proposals must be 1 .. 256", fn); return PH_EINVAL; }
+    if (!(g.n_seg > 0 && g.n_seg <= 256)) { ph_set_error("%s: num_classes must be 1 .. 256", fn); return PH_EINVAL; }
+    if (!(g.n_thing >= 0 && g.n_thing <= g.n_seg)) { ph_set_error("%s: num_thing_classes must be 0 .. num_classes", fn); return PH_EINVAL; }
+    if (!(g.groups > 0 && 256 % g.groups == 0)) { ph_set_error("%s: groups must divide 256", fn); return PH_EINVAL; }
+    switch (c->mode) {   // engine.KHEAD_PREC
+        case PH_MODE_FP16: g.prec = PH_PREC_F16; break;
+        case PH_MODE_BF16: g.prec = PH_PREC_BF16; break;
+        case PH_MODE_FP32: case PH_MODE_MIXED: case PH_MODE_MIXED16: g.prec = PH_PREC_SPLIT; break;
+        default: ph_set_error("%s: bad mode", fn); return PH_EINVAL;
+    }
+    g.P = g.prec == PH_PREC_SPLIT ? 2 : 1;
+    if (!(c->logit_dtype == PH_OUT_F32 || c->logit_dtype == PH_OUT_F16)) { ph_set_error("%s: logit_dtype must be PH_OUT_F32 or PH_OUT_F16", fn); return PH_EINVAL; }
+    if (!(c->onepass == PH_KNOB_AUTO || c->onepass == PH_KNOB_ON || c->onepass == PH_KNOB_OFF) || c->nsplit < 0) {
+        ph_set_error("%s: bad knob value (onepass: PH_KNOB_AUTO / _ON / _OFF, nsplit >= 0)", fn);
+        return PH_EINVAL;
+    }
+    g.logit_dtype = c->logit_dtype;
+    g.logit_bytes = c->logit_dtype == PH_OUT_F32 ? 4 : 2;
+    g.emit_f32 = c->emit_f32 ? 1 : 0;
+    g.n_stuff = c->cat_stuff ? g.n_seg - g.n_thing : 0;
+    g.N = g.Nq + g.n_stuff;
+    if (g.N > 256) { ph_set_error("%s: num_proposals + stuff rows must be <= 256", fn); return PH_EUNSUPPORTED; }
+    g.Npad = ph_n_padded(g.N);
+    g.NqPad = ph_n_padded(g.Nq);
+    g.HW = (int64_t)g.H * g.W;
+    g.HWp = ph_hw_padded(g.HW);
+    if ((int64_t)g.B * g.Npad > 65535) { ph_set_error("%s: B * Npad must be <= 65535", fn); return PH_EUNSUPPORTED; }
+    g.nsplit = c->nsplit ? c->nsplit : default_nsplit(g.B, g.HWp, c->frame_invariant != 0);
+    if (g.nsplit > g.HWp / 64) { ph_set_error("%s: nsplit out of range (at most H*W / 64 rounded up to 128)", fn); return PH_EINVAL; }
+
+    // pack pieces (engine.KernelHeadPack)
+    const size_t P = g.P, r_init = g.NqPad, r_seg = ph_n_padded(g.n_seg);
+    uint64_t* by = g.lay.bytes;
+    by[PH_KPACK_WPLANES] = P * 3 * 256 * 256 * 2;
+    by[PH_KPACK_GN] = 3 * 2 * 256 * 4;
+    by[PH_KPACK_INIT_PLANES] = by[PH_KPACK_INIT_FRAG] = P * r_init * 256 * 2;
+    by[PH_KPACK_SEG_PLANES] = by[PH_KPACK_SEG_FRAG] = P * r_seg * 256 * 2;
+    by[PH_KPACK_DD_PLANES] = by[PH_KPACK_DD_FRAG] = P * 32 * 256 * 2;
+    by[PH_KPACK_SEG_BIAS] = r_seg * 4;
+    by[PH_KPACK_DD_BIAS] = 32 * 4;
+    by[PH_KPACK_CONV_FRAG] = g.P == 1 ? (size_t)3 * 256 * 256 * 2 : 0;
+    by[PH_KPACK_W_INIT_F32] = (size_t)g.Nq * 256 * 4;
+    by[PH_KPACK_W_SEG_F32] = (size_t)g.n_seg * 256 * 4;
+    by[PH_KPACK_W_DD_F32] = 256 * 4;
+    size_t o = 0;
+    for (int i = 0; i < PH_KPACK_COUNT; ++i) { g.lay.offset[i] = o; o += al256(by[i]); }
+    g.pack_total = o;
+    if (!need_device) return PH_OK;
+
+    // one pass or two (engine.KernelHeadPlan: the fp32 input form has the stricter condition, HW % 4 == 0)
+    const bool sup = ph_khead_onepass_supported(g.B, g.HW, g.groups, g.prec, PH_IN_F32_NCHW) != 0;
+    if (c->onepass == PH_KNOB_ON && !sup) {
+        ph_set_error("%s: ph_khead_onepass cannot run this geometry / grade on the current device (H*W / 128 rounded up <= CUs, "
+                     "32 groups, a one-plane grade, H*W %% 4 == 0)", fn);
+        return PH_EUNSUPPORTED;
+    }
+    g.onepass = c->onepass != PH_KNOB_OFF && sup;
+    if (g.logit_dtype != PH_OUT_F32 && !g.onepass) {
+        ph_set_error("%s: 16-bit KernelHead logits need the one-pass form", fn);
+        return PH_EUNSUPPORTED;
+    }
+    // workspace: [one-pass hand-off state] [two-pass workspace] [pooled partial sums]
+    g.ws1_bytes = g.onepass ? ph_khead_onepass_workspace_bytes(g.B, g.HW) : 0;
+    g.ws2_bytes = ph_khead_workspace_bytes(g.B, g.HW, g.groups);
+    o = 0;
+    g.o_ws1 = o; o += al256(g.ws1_bytes);
+    g.o_ws2 = o; o += al256(g.ws2_bytes);
+    g.o_partial = o; o += al256((size_t)g.B * g.nsplit * g.NqPad * 512 * 4);
+    g.total = o;
+    return PH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_khead_pack: every 16-byte unit of the pack is written by one thread (one 16-byte store; the alignment padding as zeros,
+// so two packings of the same weights are byte-equal).  A unit is 8 consecutive 16-bit values or 4 floats, and in every piece
+// those come from consecutive source elements of ONE parameter row.
+enum { KP_PLANES = 0, KP_FRAG = 1, KP_F32 = 2, KP_GN = 3, KP_BIAS = 4 };
+struct KPiece {
+    uint32_t u0;             // first unit of the piece (ascending over the pieces)
+    uint32_t nvalid;         // units that carry data; the rest up to the next piece is padding
+    uint32_t mat_elems;      // PLANES / FRAG: rows32 * 256
+    uint16_t rows_valid;     // PLANES / FRAG: rows below this come from the parameter, the others are zero; BIAS: valid entries
+    uint8_t kind, first, pstep, nmat;   // first parameter, distance between the matrices' parameters, matrices per plane
+};
+struct KPackTable {
+    const float* p[PH_KHEAD_NPARAMS];
+    KPiece pc[PH_KPACK_COUNT];
+    uint32_t total_u;
+    int32_t f16;
+};
+
+__device__ __forceinline__ uint32_t khp_cvt(float w, bool f16, bool lo) {
+    if (f16) return f2h(w);
+    uint32_t h, l;
+    f2bf_split(w, h, l);
+    return lo ? l : h;
+}
+
+__global__ __launch_bounds__(256) void k_khead_pack(const KPackTable t, uint4* __restrict__ pack) {
+    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < t.total_u; u += gridDim.x * 256u) {
+        int k = 0;
+        for (int i = 1; i < PH_KPACK_COUNT; ++i)
+            if (u >= t.pc[i].u0) k = i;          // an empty piece shares its start with its successor, which wins
+        const KPiece pc = t.pc[k];
+        const uint32_t lu = u - pc.u0;
+        uint4 out = make_uint4(0u, 0u, 0u, 0u);
+        if (lu < pc.nvalid) {
+            if (pc.kind == KP_PLANES || pc.kind == KP_FRAG) {
+                const uint32_t e0 = lu * 8u, per = pc.mat_elems * pc.nmat;
+                const uint32_t pl = e0 / per, r0 = e0 % per, m = r0 / pc.mat_elems, i = r0 % pc.mat_elems;
+                uint32_t row, col;
+                if (pc.kind == KP_PLANES) { row = i >> 8; col = i & 255u; }
+                else {    // pack.pack_b32: [ct][ks][g][n][e] holds W[32 ct + n][16 ks + 8 g + e]
+                    const uint32_t n = (i >> 3) & 31u, gq = (i >> 8) & 1u, ks = (i >> 9) & 15u, ct = i >> 13;
+                    row = 32u * ct + n; col = 16u * ks + 8u * gq;
+                }
+                if (row < pc.rows_valid) {
+                    const float* src = t.p[pc.first + m * pc.pstep] + (size_t)row * 256u + col;
+                    uint32_t v[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = khp_cvt(src[e], t.f16 != 0, pl != 0);
+                    out = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+                }
+            } else if (pc.kind == KP_F32) {
+                const float* src = t.p[pc.first] + (size_t)lu * 4u;
+                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
+            } else if (pc.kind == KP_GN) {   // [3][2][256]: (gamma, beta) of map m = parameters 3 m + 1, 3 m + 2
+                const uint32_t i = lu * 4u, m = i >> 9, wb = (i >> 8) & 1u, c = i & 255u;
+                const float* src = t.p[3u * m + 1u + wb] + c;
+                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
+            } else {                          // a bias vector, zero beyond its valid entries
+                uint32_t v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const uint32_t i = lu * 4u + e;
+                    v[e] = i < pc.rows_valid ? __float_as_uint(t.p[pc.first][i]) : 0u;
+                }
+                out = make_uint4(v[0], v[1], v[2], v[3]);
+            }
+        }
+        pack[u] = out;
+    }
+}
+
+static void build_table(const KGeo& g, KPackTable& t) {
+    memset(&t, 0, sizeof(t));
+    auto set = [&](int piece, int kind, int first, int pstep, int nmat, int rows32, int rows_valid) {
+        KPiece& p = t.pc[piece];
+        p.u0 = (uint32_t)(g.lay.offset[piece] / 16);
+        p.nvalid = (uint32_t)(g.lay.bytes[piece] / 16);
+        p.mat_elems = (uint32_t)rows32 * 256u;
+        p.rows_valid = (uint16_t)rows_valid;
+        p.kind = (uint8_t)kind; p.first = (uint8_t)first; p.pstep = (uint8_t)pstep; p.nmat = (uint8_t)nmat;
+    };
+    const int r_seg = ph_n_padded(g.n_seg);
+    set(PH_KPACK_WPLANES, KP_PLANES, P_CONV, 3, 3, 256, 256);
+    set(PH_KPACK_GN, KP_GN, 0, 0, 1, 0, 0);
+    set(PH_KPACK_INIT_PLANES, KP_PLANES, P_INIT, 0, 1, g.NqPad, g.Nq);
+    set(PH_KPACK_SEG_PLANES, KP_PLANES, P_SEG, 0, 1, r_seg, g.n_seg);
+    set(PH_KPACK_DD_PLANES, KP_PLANES, P_DD, 0, 1, 32, 1);
+    set(PH_KPACK_SEG_BIAS, KP_BIAS, P_SEG_B, 0, 1, 0, g.n_seg);
+    set(PH_KPACK_DD_BIAS, KP_BIAS, P_DD_B, 0, 1, 0, 1);
+    set(PH_KPACK_INIT_FRAG, KP_FRAG, P_INIT, 0, 1, g.NqPad, g.Nq);
+    set(PH_KPACK_SEG_FRAG, KP_FRAG, P_SEG, 0, 1, r_seg, g.n_seg);
+    set(PH_KPACK_DD_FRAG, KP_FRAG, P_DD, 0, 1, 32, 1);
+    set(PH_KPACK_CONV_FRAG, KP_FRAG, P_CONV, 3, 3, 256, 256);
+    set(PH_KPACK_W_INIT_F32, KP_F32, P_INIT, 0, 1, 0, 0);
+    set(PH_KPACK_W_SEG_F32, KP_F32, P_SEG, 0, 1, 0, 0);
+    set(PH_KPACK_W_DD_F32, KP_F32, P_DD, 0, 1, 0, 0);
+    t.total_u = (uint32_t)(g.pack_total / 16);
+    t.f16 = g.prec == PH_PREC_F16;
+}
+
+// conv_direct_depth.weight into every row of depth_proposal [rows][256] (kernel_head.py:286-289, the dense form of the view)
+__global__ __launch_bounds__(256) void k_khead_depth_proposal(const float4* __restrict__ w_dd, float4* __restrict__ out, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) out[i] = w_dd[i & 63];
+}
+
+// ---------------------------------------------------------------------------------------------
+extern "C" const char* ph_khead_param_name(int index) {
+    return index >= 0 && index < PH_KHEAD_NPARAMS ? kParamNames[index] : nullptr;
+}
+
+extern "C" int64_t ph_khead_param_numel(const ph_khead_cfg* cfg, int index) {
+    if (!cfg) return -1;
+    return param_numel(cfg, index);
+}
+
+extern "C" size_t ph_khead_pack_bytes(const ph_khead_cfg* cfg) {
+    KGeo g;
+    if (resolve(cfg, g, "ph_khead_pack_bytes", false)) return 0;
+    return g.pack_total;
+}
+
+extern "C" int ph_khead_pack_layout(const ph_khead_cfg* cfg, ph_khead_layout* layout) {
+    KGeo g;
+    const int rc = resolve(cfg, g, "ph_khead_pack_layout", false);
+    if (rc) return rc;
+    PH_CHECK_ARG(layout != nullptr, "null layout");
+    *layout = g.lay;
+    return PH_OK;
+}
+
+extern "C" int ph_khead_pack(const ph_khead_cfg* cfg, const float* const* params, void* pack, void* stream) {
+    KGeo g;
+    const int rc = resolve(cfg, g, "ph_khead_pack", false);
+    if (rc) return rc;
+    PH_CHECK_ARG(params && pack, "null params or pack");
+    for (int i = 0; i < PH_KHEAD_NPARAMS; ++i)
+        if (!params[i]) { ph_set_error("ph_khead_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
+    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
+    KPackTable t;
+    build_table(g, t);
+    for (int i = 0; i < PH_KHEAD_NPARAMS; ++i) t.p[i] = params[i];
+    const unsigned blocks = (t.total_u + 255u) / 256u;
+    hipLaunchKernelGGL(k_khead_pack, dim3(blocks < 1024u ? blocks : 1024u), dim3(256), 0, (hipStream_t)stream, t, (uint4*)pack);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+extern "C" size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg) {
+    KGeo g;
+    if (resolve(cfg, g, "ph_khead_plan_workspace_bytes", true)) return 0;
+    return g.total;
+}
+
+struct ph_khead_plan {
+    KGeo g;
+    const char* pack;
+    char* ws;
+};
+
+extern "C" int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes,
+                                    ph_khead_plan** out) {
+    KGeo g;
+    const int rc = resolve(cfg, g, "ph_khead_plan_create", true);
+    if (rc) return rc;
+    PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
+    *out = nullptr;
+    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
+    if (workspace_bytes < g.total) {
+        ph_set_error("ph_khead_plan_create: workspace too small (%zu < %zu)", workspace_bytes, g.total);
+        return PH_EWORKSPACE;
+    }
+    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    ph_khead_plan* p = new (std::nothrow) ph_khead_plan;
+    if (!p) { ph_set_error("ph_khead_plan_create: out of host memory"); return PH_EINVAL; }
+    p->g = g;
+    p->pack = (const char*)pack;
+    p->ws = (char*)workspace;
+    *out = p;
+    return PH_OK;
+}
+
+extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out) {
+    PH_CHECK_ARG(p && out, "null plan or out");
+    const KGeo& g = p->g;
+    out->onepass = g.onepass; out->nsplit = g.nsplit; out->N = g.N; out->Npad = g.Npad; out->HWp = (int32_t)g.HWp; out->P = g.P;
+    out->prec = g.prec; out->n_stuff = g.n_stuff;
+    return PH_OK;
+}
+
+extern "C" void ph_khead_plan_destroy(ph_khead_plan* p) { delete p; }
+
+// the plan's launches take their knobs from here, never from the environment: the defaults the public entry points use when no
+// PH_KHEAD1_PAIR / PH_NECK_STATS3 / PH_NECK_APPLY3 is set
+static const PhKheadKnobs kKhead{};
+
+#define PH_KRUN(call)                  \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != PH_OK) return rc_;  \
+    } while (0)
+
+extern "C" int ph_khead_plan_run(ph_khead_plan* p, const ph_khead_io* io, void* stream) {
+    PH_CHECK_ARG(p && io, "null plan or io");
+    const KGeo& g = p->g;
+    PH_CHECK_ARG(io->input_format == PH_IN_F32_NCHW || io->input_format == PH_IN_PLANES, "bad input_format");
+    PH_CHECK_ARG(io->f0 && io->f1 && io->f2, "null input map");
+    PH_CHECK_ARG(io->xp && io->dp && io->bits && io->mask_preds && io->seg_preds && io->depth_pred && io->proposal, "null output pointer");
+    if (g.emit_f32) PH_CHECK_ARG(io->x_f32 && io->dfe_f32, "the cfg's emit_f32 needs x_f32 and dfe_f32");
+    else PH_CHECK_ARG(!io->x_f32 && !io->dfe_f32, "x_f32 / dfe_f32 must be NULL without the cfg's emit_f32");
+    PH_CHECK_ARG(((uintptr_t)io->depth_proposal & 15) == 0, "depth_proposal must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = g.B, fmt = io->input_format;
+    const int64_t HW = g.HW;
+    const ph_khead_layout& L = g.lay;
+    auto u16 = [&](int piece) { return (const uint16_t*)(p->pack + L.offset[piece]); };
+    auto f32 = [&](int piece) { return (const float*)(p->pack + L.offset[piece]); };
+    void* ws1 = p->ws + g.o_ws1;
+    void* ws2 = p->ws + g.o_ws2;
+    float* partial = (float*)(p->ws + g.o_partial);
+    if (g.onepass) {
+        PH_KRUN(ph_khead_onepass_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_CONV_FRAG), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                   u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                   u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                   io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, io->bits, g.Npad, ws1,
+                                   g.ws1_bytes, B, HW, g.prec, fmt, s));
+        // the in-call fallback, predicated on the one-pass launch's status word (the first word of its hand-off state)
+        PH_KRUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                    u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                    u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                    io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, (const uint32_t*)ws1,
+                                    ws2, g.ws2_bytes, B, HW, g.prec, fmt, s));
+        PH_KRUN(ph_binarize_if(io->mask_preds, g.logit_dtype, 0, io->bits, B, g.N, HW, (const uint32_t*)ws1, s));
+    } else {
+        PH_KRUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                    u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                    u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                    io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, PH_OUT_F32, nullptr, ws2, g.ws2_bytes,
+                                    B, HW, g.prec, fmt, s));
+        PH_KRUN(ph_binarize((const float*)io->mask_preds, 0, io->bits, B, g.N, HW, s));
+    }
+    // object features: pool x over the THING rows of the bit tensor (kernel_head.py:314-320), add them to the kernels (:324-326)
+    PH_KRUN(ph_pool_rows(io->xp, nullptr, io->bits, g.Npad, partial, B, g.Nq, HW, g.nsplit, g.prec, s));
+    PH_KRUN(ph_khead_proposals(partial, g.nsplit, f32(PH_KPACK_W_INIT_F32),
+                               g.n_stuff ? f32(PH_KPACK_W_SEG_F32) + (size_t)g.n_thing * 256 : nullptr, io->proposal, B, g.Nq,
+                               g.n_stuff, s));
+    if (io->depth_proposal) {
+        const int64_t n4 = (int64_t)B * g.N * 64;
+        const int64_t blocks = (n4 + 255) / 256;
+        hipLaunchKernelGGL(k_khead_depth_proposal, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, s,
+                           (const float4*)f32(PH_KPACK_W_DD_F32), (float4*)io->depth_proposal, n4);
+        PH_CHECK_LAUNCH();
+    }
+    return PH_OK;
+}
+
+extern "C" int ph_khead_plan_status(const ph_khead_plan* p, void* stream) {
+    if (!p) { ph_set_error("ph_khead_plan_status: null plan"); return PH_EINVAL; }
+    if (!p->g.onepass) return 0;
+    return ph_khead_onepass_status(p->ws + p->g.o_ws1, p->g.B, stream);
+}
+
+extern "C" int ph_khead_plan_timeouts(const ph_khead_plan* p, void* stream) {
+    if (!p) { ph_set_error("ph_khead_plan_timeouts: null plan"); return PH_EINVAL; }
+    if (!p->g.onepass) return 0;
+    return ph_khead_onepass_timeouts(p->ws + p->g.o_ws1, p->g.B, p->g.HW, stream);
+}

@@ -878,6 +878,183 @@ class KernelHeadPlan:
         return self.timeouts()
 
 
+# ---- KernelHead's post-neck part as a native object (include/polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts) ------------
+_KHEAD_MODE_OF_PREC = {_lib.PH_PREC_F16: "fp16", _lib.PH_PREC_BF16: "bf16", _lib.PH_PREC_SPLIT: "fp32"}
+
+
+def native_khead_cfg(B, H, W, num_proposals, num_classes, num_thing_classes, cat_stuff, groups, prec, logit_dtype=torch.float32,
+                     want_f32=True, frame_invariant=False, onepass=None, nsplit=None):
+    """the ph_khead_cfg of the KernelHeadPlan that the same arguments (and the same environment) would build: the switches
+    KernelHeadPlan reads from the environment (PH_KHEAD_TWOPASS, PH_POOL_NSPLIT) become cfg fields -- the native plan reads none.
+    `prec`: a precision name (engine.KHEAD_PREC's keys) or a1's grade code; `num_classes`: the rows of conv_seg"""
+    name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
+    env = _os.environ.get
+    if onepass and env("PH_KHEAD_TWOPASS"):
+        raise _lib.PolyheadError("ph_khead_onepass asked for while PH_KHEAD_TWOPASS is set")
+    knob = _lib.PH_KNOB_OFF if (onepass is False or env("PH_KHEAD_TWOPASS")) else (_lib.PH_KNOB_ON if onepass else _lib.PH_KNOB_AUTO)
+    if logit_dtype not in (torch.float32, torch.float16):
+        raise _lib.PolyheadError("KernelHead logits are fp32 or fp16")
+    return _lib.KheadCfg(B=B, H=H, W=W, num_proposals=num_proposals, num_classes=num_classes, num_thing_classes=num_thing_classes,
+                         cat_stuff=int(bool(cat_stuff)), groups=groups, mode=_lib.PH_MODE[name], logit_dtype=OUT_CODE[logit_dtype],
+                         emit_f32=int(bool(want_f32)), frame_invariant=int(bool(frame_invariant)), onepass=knob,
+                         nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0))
+
+
+class NativeKernelHeadPack:
+    """one device buffer packed by ph_khead_pack, and its pieces as views under KernelHeadPack's attribute names (so either plan
+    -- KernelHeadPlan or NativeKernelHeadPlan -- runs from it)"""
+
+    def __init__(self, blob, cfg):
+        lib = _lib.load()
+        lay = _lib.KheadLayout()
+        _lib.check(lib.ph_khead_pack_layout(C.byref(cfg), C.byref(lay)), "ph_khead_pack_layout")
+        self.blob, self.layout = blob, lay
+        # a1's grade of the cfg's mode, as KHEAD_PREC maps the names
+        self.prec = {_lib.PH_MODE["fp16"]: _lib.PH_PREC_F16, _lib.PH_MODE["bf16"]: _lib.PH_PREC_BF16}.get(cfg.mode, _lib.PH_PREC_SPLIT)
+        self.mode = cfg.mode
+        self.groups, self.n_init, self.n_seg = cfg.groups, cfg.num_proposals, cfg.num_classes
+        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
+        dt = dict(wplanes=(torch.int16, (P, 3, 256, 256)), gn=(torch.float32, (3, 2, 256)),
+                  init_planes=(torch.int16, (P, n_padded(self.n_init), 256)), seg_planes=(torch.int16, (P, n_padded(self.n_seg), 256)),
+                  dd_planes=(torch.int16, (P, 32, 256)), seg_bias=(torch.float32, (n_padded(self.n_seg),)), dd_bias=(torch.float32, (32,)),
+                  init_frag=(torch.int16, (P, n_padded(self.n_init) * 256)), seg_frag=(torch.int16, (P, n_padded(self.n_seg) * 256)),
+                  dd_frag=(torch.int16, (P, 32 * 256)), conv_frag=(torch.int16, (3, 256 * 256)),
+                  w_init_f32=(torch.float32, (self.n_init, 256)), w_seg_f32=(torch.float32, (self.n_seg, 256)),
+                  w_dd_f32=(torch.float32, (1, 256, 1, 1)))
+        for i, name in enumerate(_lib.KPACK_PIECES):
+            off, nb = lay.offset[i], lay.bytes[i]
+            d, shape = dt[name]
+            setattr(self, name, blob[off:off + nb].view(d).reshape(shape) if nb else None)
+
+
+def native_khead_pack(module, cfg, device):
+    """KernelHead's own parameters (a module, or a state_dict without the neck's entries) packed on the device by ph_khead_pack"""
+    lib = _lib.load()
+    nbytes = lib.ph_khead_pack_bytes(C.byref(cfg))
+    if nbytes == 0:
+        raise _cfg_error("ph_khead_pack_bytes")
+    sd = module.state_dict() if hasattr(module, "state_dict") else module
+    params = []
+    for i in range(_lib.PH_KHEAD_NPARAMS):
+        name = lib.ph_khead_param_name(i).decode()
+        t = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
+        if t.numel() != lib.ph_khead_param_numel(C.byref(cfg), i):
+            raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {lib.ph_khead_param_numel(C.byref(cfg), i)}")
+        params.append(t)
+    ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.ph_khead_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_khead_pack")
+    return NativeKernelHeadPack(blob, cfg)
+
+
+class NativeKernelHeadPlan:
+    """KernelHeadPlan's surface (set_inputs, run, renew_outputs, timeouts, last_run_fell_back and the output attributes) over ONE
+    native call per a1 (ph_khead_plan_run): the same launch sequence and geometry as the KernelHeadPlan of the same arguments, so
+    the same bits.  `pack`: a NativeKernelHeadPack.  `dense_depth_proposal`: also write depth_proposal [B, N, 256] (what a C caller
+    hands to ph_decode_io.q0; the module API keeps the reference's stride-0 view of the weight and needs no launch for it)."""
+
+    def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
+                 logit_dtype=torch.float32, onepass=None, frame_invariant=False, dense_depth_proposal=False, cfg=None):
+        """`cfg`: a ph_khead_cfg to use as it is (the environment is then not consulted at all) instead of `native_khead_cfg`'s"""
+        if num_classes != pack.n_seg:
+            raise _lib.PolyheadError("the native KernelHead plan needs num_classes == rows of conv_seg (a sigmoid loss_seg)")
+        self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
+        dev = torch.device(device)
+        self.device, self.logit_dtype, self.want_f32 = dev, logit_dtype, want_f32
+        mode = {v: k for k, v in _lib.PH_MODE.items() if k != "split"}[pack.mode]
+        self.cfg = cfg if cfg is not None else native_khead_cfg(B, H, W, pack.n_init, pack.n_seg, num_thing_classes, cat_stuff,
+                                                                pack.groups, mode, logit_dtype, want_f32, frame_invariant, onepass, nsplit)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            nbytes = lib.ph_khead_plan_workspace_bytes(C.byref(self.cfg))
+            if nbytes == 0:
+                raise _cfg_error("ph_khead_plan_workspace_bytes")
+            # zeroed ONCE: the one-pass launch's hand-off state ends in the sticky time-out words, which no call clears
+            self.workspace = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
+            handle = C.c_void_p()
+            _lib.check(lib.ph_khead_plan_create(C.byref(self.cfg), _lib.ptr(pack.blob), _lib.ptr(self.workspace), nbytes,
+                                                C.byref(handle)), "ph_khead_plan_create")
+        self._h = handle
+        geo = _lib.KheadGeometry()
+        _lib.check(lib.ph_khead_plan_info(self._h, C.byref(geo)), "ph_khead_plan_info")
+        self.geometry = geo
+        self.onepass, self.nsplit, self.N, self.n_stuff = bool(geo.onepass), geo.nsplit, geo.N, geo.n_stuff
+        self.Nq = pack.n_init
+        self.dense_depth_proposal = dense_depth_proposal
+        self.f = [None, None, None]
+        self._borrowed = set()
+        self.in_planes = False
+        self.io = _lib.KheadIO()
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        P, HWp = geo.P, geo.HWp
+        self.xp, self.dp = e((P, B, 256, HWp), torch.int16), e((P, B, 256, HWp), torch.int16)
+        self.x_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
+        self.dfe_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
+        self.mask_preds = e((B, self.N, H, W), logit_dtype)
+        self.seg_preds = e((B, pack.n_seg, H, W), logit_dtype)
+        self.depth_pred = e((B, 1, H, W), logit_dtype)
+        self.bits = e((B, geo.Npad, HWp // 32), torch.int32)
+        self.proposal = e((B, self.N, 256), torch.float32)
+        self.depth_proposal = e((B, self.N, 256), torch.float32) if dense_depth_proposal else None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            _lib._lib.ph_khead_plan_destroy(h)
+            self._h = None
+
+    def renew_outputs(self):
+        """fresh tensors for everything handed to the caller (KernelHeadPlan.renew_outputs)"""
+        e = lambda t: None if t is None else torch.empty_like(t)
+        self.xp, self.dp, self.bits = e(self.xp), e(self.dp), e(self.bits)
+        self.x_f32, self.dfe_f32 = e(self.x_f32), e(self.dfe_f32)
+        self.mask_preds, self.seg_preds, self.depth_pred = e(self.mask_preds), e(self.seg_preds), e(self.depth_pred)
+        self.proposal, self.depth_proposal = e(self.proposal), e(self.depth_proposal)
+
+    def set_inputs(self, feats):
+        """as KernelHeadPlan.set_inputs: contiguous fp32 device maps of the plan's shape and plane inputs are read where they
+        are, anything else is copied into the plan's own buffers"""
+        self.in_planes = feats[0].dtype == torch.int16
+        if self.in_planes:
+            for i, src in enumerate(feats):
+                if tuple(src.shape) != (self.geometry.P, self.B, 256, self.geometry.HWp) or not src.is_contiguous():
+                    raise _lib.PolyheadError("plane inputs must be contiguous int16 [P][B][256][HWp]")
+                self.f[i] = src
+            self._borrowed = {t.data_ptr() for t in self.f}
+            return
+        for i, src in enumerate(feats):
+            if (src.dtype == torch.float32 and src.is_contiguous() and src.device == self.xp.device
+                    and tuple(src.shape) == (self.B, 256, self.H, self.W)):
+                self.f[i] = src.detach()
+            else:
+                if self.f[i] is None or self.f[i].data_ptr() in self._borrowed:
+                    self.f[i] = torch.empty((self.B, 256, self.H, self.W), dtype=torch.float32, device=self.xp.device)
+                self.f[i].copy_(src)
+        self._borrowed = {t.data_ptr() for t, src in zip(self.f, feats) if t.data_ptr() == src.data_ptr()}
+
+    def run(self):
+        """one a1 call on the current stream: ONE native call"""
+        io, dp = self.io, lambda t: None if t is None else t.data_ptr()
+        io.input_format = _lib.PH_IN_PLANES if self.in_planes else _lib.PH_IN_F32_NCHW
+        io.f0, io.f1, io.f2 = self.f[0].data_ptr(), self.f[1].data_ptr(), self.f[2].data_ptr()
+        io.xp, io.dp, io.bits, io.x_f32, io.dfe_f32 = dp(self.xp), dp(self.dp), dp(self.bits), dp(self.x_f32), dp(self.dfe_f32)
+        io.mask_preds, io.seg_preds, io.depth_pred = dp(self.mask_preds), dp(self.seg_preds), dp(self.depth_pred)
+        io.proposal, io.depth_proposal = dp(self.proposal), dp(self.depth_proposal)
+        _lib.check(_lib.load().ph_khead_plan_run(self._h, C.byref(io), _lib.stream_ptr()), "ph_khead_plan_run")
+
+    def timeouts(self):
+        """workgroup time-outs of the one-pass launches since the plan was built (KernelHeadPlan.timeouts; synchronises)"""
+        return int(_lib.load().ph_khead_plan_timeouts(self._h, _lib.stream_ptr()))
+
+    def last_run_fell_back(self):
+        """True if the most recent run gave up its one-pass launch and was redone by the two-pass kernels (synchronises)"""
+        return bool(_lib.load().ph_khead_plan_status(self._h, _lib.stream_ptr()) != 0)
+
+    def check_status(self):
+        return self.timeouts()
+
+
 # ---- SemanticFPNWrapper (N3) -------------------------------------------------------------------------------
 def nhwc_ingest(x, add, prec, out):
     B, Cc, H, W = x.shape

@@ -72,6 +72,7 @@ class KernelHead(nn.Module):
         self.emit_fp32_features = True     # the reference API returns x_feats / depth_feats as fp32 NCHW tensors
         self.logit_dtype = torch.float32   # mask_preds / seg_preds / depth_pred; torch.float16 halves their bytes (one-pass form)
         self._pack, self._plans = None, {}
+        self.native_plan = False           # use_native_plan: a1 as ONE native call (engine.NativeKernelHeadPlan)
         self.assigner = self.sampler = None
         if self.train_cfg:                 # kernel_head.py:134-140
             from . import assigner as A
@@ -107,13 +108,28 @@ class KernelHead(nn.Module):
             self.localization_fpn.set_precision("fp32" if precision == "split" else precision)
         return self
 
+    def use_native_plan(self, on=True):
+        """a1 through the native plan object of the C ABI (include/polyhead.h ph_khead_plan_*): the parameters are packed on the
+        device by ph_khead_pack and every `_decode_init_proposals` is ONE native call.  Same launches, same bits.  Default off."""
+        if bool(on) != self.native_plan:
+            self.native_plan = bool(on)
+            self._pack, self._plans = None, {}
+        return self
+
     def _get_pack(self, device):
         prec = E.KHEAD_PREC[self.precision]
         own = {k: v for k, v in self.state_dict().items() if not k.startswith("localization_fpn.")}
         ver = _lib.param_versions(self)
-        if self._pack is None or self._pack[0] != (prec, str(device), ver):
-            self._pack = ((prec, str(device), ver),
-                          E.KernelHeadPack(own, prec, device, self.norm_cfg.get('num_groups', 32)))
+        if self._pack is None or self._pack[0] != (prec, str(device), ver, self.native_plan):
+            groups = self.norm_cfg.get('num_groups', 32)
+            if self.native_plan:
+                # the pack does not depend on the frame geometry: any valid one serves ph_khead_pack
+                cfg = E.native_khead_cfg(1, 1, 1, self.init_kernels.weight.shape[0], self.conv_seg.weight.shape[0],
+                                         self.num_thing_classes, False, groups, prec, nsplit=1)
+                pack = E.native_khead_pack(own, cfg, device)
+            else:
+                pack = E.KernelHeadPack(own, prec, device, groups)
+            self._pack = ((prec, str(device), ver, self.native_plan), pack)
             self._plans = {}
         return self._pack[1]
 
@@ -145,9 +161,10 @@ class KernelHead(nn.Module):
         key = (B, H, W, cat_stuff, self.emit_fp32_features, self.logit_dtype, bool(self.frame_invariant))
         plan = self._plans.get(key)
         if plan is None:
-            self._plans = {key: E.KernelHeadPlan(pack, B, H, W, self.num_thing_classes, self.num_classes, cat_stuff, dev,
-                                                 want_f32=self.emit_fp32_features, logit_dtype=self.logit_dtype,
-                                                 frame_invariant=bool(self.frame_invariant))}
+            Plan = E.NativeKernelHeadPlan if self.native_plan else E.KernelHeadPlan
+            self._plans = {key: Plan(pack, B, H, W, self.num_thing_classes, self.num_classes, cat_stuff, dev,
+                                    want_f32=self.emit_fp32_features, logit_dtype=self.logit_dtype,
+                                    frame_invariant=bool(self.frame_invariant))}
             plan = self._plans[key]
         plan.renew_outputs()         # the 9-tuple (and the hand-off planes) belong to the caller from here on
         plan.set_inputs(list(feats) if handoff else [f.float() for f in feats])

@@ -1,0 +1,244 @@
+"""Host-side checks of the native KernelHead plan (include/polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts): the exported
+symbols, the struct layouts the ctypes side assumes, the parameter table against KernelHead's own state_dict, the pack layout,
+the environment -> cfg mapping, argument validation, and the Python-free example program's dependencies.  No GPU: nothing here
+launches a kernel (the one-pass rule needs the device's CU count: tests/test_gpu_native_khead.py)."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+import pytest
+import torch
+
+from polyphonicformer_amd import _lib, engine as E
+from polyphonicformer_amd import build as BLD
+from polyphonicformer_amd.registry import HEADS
+import polyphonicformer_amd.kernel_head  # noqa: F401
+from test_native_plan import _elf_needed
+
+NEW_SYMBOLS = ["ph_khead_param_name", "ph_khead_param_numel", "ph_khead_pack_bytes", "ph_khead_pack_layout", "ph_khead_pack",
+               "ph_khead_plan_workspace_bytes", "ph_khead_plan_create", "ph_khead_plan_info", "ph_khead_plan_destroy",
+               "ph_khead_plan_run", "ph_khead_plan_status", "ph_khead_plan_timeouts"]
+FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and never dereferences
+STRUCTS = {"ph_khead_cfg": _lib.KheadCfg, "ph_khead_io": _lib.KheadIO, "ph_khead_geometry": _lib.KheadGeometry,
+           "ph_khead_layout": _lib.KheadLayout}
+
+
+def _msg():
+    return _lib.load().ph_last_error_string().decode()
+
+
+def _cfg(**kw):
+    base = dict(B=2, H=48, W=156, num_proposals=100, num_classes=19, num_thing_classes=8, cat_stuff=1, groups=32,
+                mode=_lib.PH_MODE["fp16"], logit_dtype=_lib.PH_OUT_F32, emit_f32=1)
+    return _lib.KheadCfg(**dict(base, **kw))
+
+
+def test_new_symbols_are_exported():
+    lib = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert hasattr(lib, name), name
+        assert name in _lib.SIGNATURES, name
+
+
+def test_struct_sizes_and_offsets_match_ctypes():
+    """sizeof / offsetof of the new structs as a C compiler sees include/polyhead.h"""
+    cc = shutil.which("cc") or shutil.which("gcc") or BLD._hipcc()
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "polyhead.h"', 'int main(void) {']
+    for cname, cls in STRUCTS.items():
+        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
+        for field, _ in cls._fields_:
+            lines.append(f'printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));')
+    lines.append(f'printf("PH_KPACK_COUNT %d\\nPH_KHEAD_NPARAMS %d\\n", (int)PH_KPACK_COUNT, (int)PH_KHEAD_NPARAMS);')
+    lines += ['return 0;', '}']
+    with tempfile.TemporaryDirectory() as d:
+        with open(os.path.join(d, "t.c"), "w") as f:
+            f.write("\n".join(lines))
+        exe = os.path.join(d, "t")
+        lang = [] if os.path.basename(cc) in ("cc", "gcc") else ["-x", "c++"]
+        subprocess.run([cc] + lang + ["-I", os.path.join(BLD.HERE, "..", "include"), os.path.join(d, "t.c"), "-o", exe], check=True,
+                       capture_output=True, timeout=300)
+        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
+    c = {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
+    assert c.pop("PH_KPACK_COUNT") == _lib.PH_KPACK_COUNT == len(_lib.KPACK_PIECES)
+    assert c.pop("PH_KHEAD_NPARAMS") == _lib.PH_KHEAD_NPARAMS
+    for key, val in c.items():
+        if "." in key:
+            struct, field = key.split(".")
+            assert getattr(STRUCTS[struct], field).offset == val, key
+        else:
+            assert C.sizeof(STRUCTS[key]) == val, key
+
+
+def _kernel_head(Nq=100, n_thing=8, n_stuff=11):
+    return HEADS.build(dict(type="KernelHead", num_proposals=Nq, num_classes=n_thing + n_stuff, num_thing_classes=n_thing,
+                            num_stuff_classes=n_stuff, in_channels=256, out_channels=256, cat_stuff_mask=True,
+                            feat_downsample_stride=2, feat_refine_stride=1, feat_refine=False, use_binary=True,
+                            conv_normal_init=True, proposal_feats_with_obj=True, xavier_init_kernel=False, kernel_init_std=1,
+                            loss_seg=dict(type="FocalLoss", use_sigmoid=True), localization_fpn=None))
+
+
+class _Recorder(dict):
+    """a state_dict that records the keys read from it"""
+
+    def __init__(self, d):
+        super().__init__(d)
+        self.read = []
+
+    def __getitem__(self, k):
+        self.read.append(k)
+        return super().__getitem__(k)
+
+
+def test_param_table_is_what_kernel_head_pack_reads():
+    lib = _lib.load()
+    h = _kernel_head(Nq=37, n_thing=5, n_stuff=9)
+    sd = _Recorder(h.state_dict())
+    E.KernelHeadPack(sd, _lib.PH_PREC_BF16, "cpu", 32)
+    names = [lib.ph_khead_param_name(i).decode() for i in range(_lib.PH_KHEAD_NPARAMS)]
+    assert lib.ph_khead_param_name(_lib.PH_KHEAD_NPARAMS) is None and lib.ph_khead_param_name(-1) is None
+    assert set(names) == set(sd.read) and len(set(names)) == _lib.PH_KHEAD_NPARAMS
+    cfg = _cfg(num_proposals=37, num_classes=14, num_thing_classes=5)
+    assert [lib.ph_khead_param_numel(C.byref(cfg), i) for i in range(len(names))] == [sd[n].numel() for n in names]
+    assert lib.ph_khead_param_numel(C.byref(cfg), len(names)) < 0
+
+
+@pytest.mark.parametrize("mode", ["fp16", "bf16", "fp32", "mixed", "mixed16"])
+def test_pack_layout(mode):
+    """offsets 256-byte aligned, in order, non-overlapping, summing to ph_khead_pack_bytes; sizes those of KernelHeadPack's tensors"""
+    lib = _lib.load()
+    h = _kernel_head()
+    prec = E.KHEAD_PREC[mode]
+    ref = E.KernelHeadPack(h.state_dict(), prec, "cpu", 32)
+    cfg = _cfg(mode=_lib.PH_MODE[mode])
+    lay = _lib.KheadLayout()
+    assert lib.ph_khead_pack_layout(C.byref(cfg), C.byref(lay)) == 0
+    end = 0
+    for i, name in enumerate(_lib.KPACK_PIECES):
+        assert lay.offset[i] % 256 == 0 and lay.offset[i] == end, name
+        t = getattr(ref, name)
+        assert lay.bytes[i] == (0 if t is None else t.numel() * t.element_size()), name
+        end = lay.offset[i] + (lay.bytes[i] + 255) // 256 * 256
+    assert end == lib.ph_khead_pack_bytes(C.byref(cfg))
+    assert (getattr(ref, "conv_frag") is None) == (prec == _lib.PH_PREC_SPLIT)
+
+
+def test_native_khead_cfg_maps_the_environment(monkeypatch):
+    """the switches KernelHeadPlan reads from the environment reach the native plan as cfg fields"""
+    for k in ("PH_KHEAD_TWOPASS", "PH_POOL_NSPLIT"):
+        monkeypatch.delenv(k, raising=False)
+    args = (3, 48, 156, 100, 19, 8, True, 32)
+    c = E.native_khead_cfg(*args, "fp16")
+    assert (c.onepass, c.nsplit, c.mode, c.emit_f32, c.logit_dtype) == (_lib.PH_KNOB_AUTO, 0, _lib.PH_MODE["fp16"], 1, _lib.PH_OUT_F32)
+    assert E.native_khead_cfg(*args, "fp16", onepass=False).onepass == _lib.PH_KNOB_OFF
+    assert E.native_khead_cfg(*args, "fp16", onepass=True).onepass == _lib.PH_KNOB_ON
+    assert E.native_khead_cfg(*args, _lib.PH_PREC_SPLIT).mode == _lib.PH_MODE["fp32"]
+    assert E.native_khead_cfg(*args, "bf16", logit_dtype=torch.float16, want_f32=False, frame_invariant=True, nsplit=5).nsplit == 5
+    monkeypatch.setenv("PH_KHEAD_TWOPASS", "1")
+    monkeypatch.setenv("PH_POOL_NSPLIT", "3")
+    c = E.native_khead_cfg(*args, "fp16")
+    assert (c.onepass, c.nsplit) == (_lib.PH_KNOB_OFF, 3)
+    assert E.native_khead_cfg(*args, "fp16", nsplit=7).nsplit == 7
+    with pytest.raises(_lib.PolyheadError):
+        E.native_khead_cfg(*args, "fp16", onepass=True)
+
+
+def _create(cfg, nbytes=1 << 62):
+    h = C.c_void_p()
+    rc = _lib.load().ph_khead_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), nbytes, C.byref(h))
+    return rc, h
+
+
+def test_errors_are_returned_before_anything_is_launched():
+    lib = _lib.load()
+    ws = lambda cfg: lib.ph_khead_plan_workspace_bytes(C.byref(cfg))
+    cfg = _cfg(groups=24)
+    assert ws(cfg) == 0 and "groups" in _msg()
+    assert lib.ph_khead_pack_bytes(C.byref(cfg)) == 0 and "groups" in _msg()
+    assert _create(cfg)[0] == -1 and "groups" in _msg()
+    cfg = _cfg(mode=9)
+    assert ws(cfg) == 0 and "bad mode" in _msg()
+    assert _create(cfg)[0] == -1
+    cfg = _cfg(logit_dtype=_lib.PH_OUT_F16, onepass=_lib.PH_KNOB_OFF)
+    assert ws(cfg) == 0 and "one-pass form" in _msg()
+    assert _create(cfg)[0] == -2 and "one-pass form" in _msg()
+    for bad in (dict(num_proposals=0), dict(num_proposals=300), dict(num_classes=300), dict(num_thing_classes=20), dict(B=0),
+                dict(onepass=7), dict(nsplit=-1), dict(logit_dtype=_lib.PH_OUT_BF16), dict(num_proposals=250, num_classes=30),
+                dict(nsplit=1000)):
+        assert ws(_cfg(**bad)) == 0 and _msg(), bad
+        rc, h = _create(_cfg(**bad))
+        assert rc < 0 and not h.value, bad
+    # two-pass plans need no device: the size, a short workspace, a good one
+    cfg = _cfg(onepass=_lib.PH_KNOB_OFF)
+    need = ws(cfg)
+    assert need > 0 and need % 256 == 0
+    rc, h = _create(cfg, need - 256)
+    assert rc == -4 and "workspace too small" in _msg() and not h.value
+    rc, h = _create(cfg, need)
+    assert rc == 0 and h.value
+    g = _lib.KheadGeometry()
+    assert lib.ph_khead_plan_info(h, C.byref(g)) == 0
+    assert (g.onepass, g.N, g.Npad, g.HWp, g.P, g.prec, g.n_stuff) == (0, 111, 128, 7552, 1, _lib.PH_PREC_F16, 11)
+    assert g.nsplit == E.default_nsplit(2, 48 * 156)
+    lib.ph_khead_plan_destroy(h)
+    rc, h = _create(_cfg(onepass=_lib.PH_KNOB_OFF, mode=_lib.PH_MODE["mixed"], cat_stuff=0, frame_invariant=1))
+    assert rc == 0
+    lib.ph_khead_plan_info(h, C.byref(g))
+    assert (g.N, g.P, g.prec, g.n_stuff, g.nsplit) == (100, 2, _lib.PH_PREC_SPLIT, 0, E.default_nsplit(2, 48 * 156, True))
+    lib.ph_khead_plan_destroy(h)
+    # pack / run arguments, in a child process that sees no GPU: a check that ever stopped returning before the first launch would
+    # fail on the host instead of launching on the fake addresses
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", _RUN_CHECKS], cwd=os.path.dirname(BLD.HERE), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0 and "run checks ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+
+
+_RUN_CHECKS = r"""
+import ctypes as C, sys
+sys.path.insert(0, ".")
+import torch
+from polyphonicformer_amd import _lib
+assert torch.cuda.device_count() == 0, "the run-time argument checks need a process without a visible GPU"
+lib = _lib.load()
+FAKE = 1 << 40
+msg = lambda: lib.ph_last_error_string().decode()
+cfg = _lib.KheadCfg(B=2, H=48, W=156, num_proposals=100, num_classes=19, num_thing_classes=8, cat_stuff=1, groups=32,
+                    mode=_lib.PH_MODE["fp16"], logit_dtype=_lib.PH_OUT_F32, emit_f32=1)
+# without a device the one-pass form cannot be chosen: AUTO gives a two-pass plan, ON is an error
+assert lib.ph_khead_onepass_supported(2, 48 * 156, 32, _lib.PH_PREC_F16, _lib.PH_IN_F32_NCHW) == 0
+cfg.onepass = _lib.PH_KNOB_ON
+assert lib.ph_khead_plan_workspace_bytes(C.byref(cfg)) == 0 and "ph_khead_onepass cannot run" in msg()
+cfg.onepass = _lib.PH_KNOB_AUTO
+params = (C.c_void_p * _lib.PH_KHEAD_NPARAMS)(*([FAKE] * _lib.PH_KHEAD_NPARAMS))
+assert lib.ph_khead_pack(C.byref(cfg), params, C.c_void_p(FAKE + 16), None) == -1 and "aligned" in msg()
+params[11] = None
+assert lib.ph_khead_pack(C.byref(cfg), params, C.c_void_p(FAKE), None) == -1 and "conv_seg.bias" in msg()
+h = C.c_void_p()
+assert lib.ph_khead_plan_create(C.byref(cfg), C.c_void_p(FAKE), C.c_void_p(FAKE), 1 << 62, C.byref(h)) == 0
+ptrs = dict(f0=FAKE, f1=FAKE, f2=FAKE, xp=FAKE, dp=FAKE, bits=FAKE, x_f32=FAKE, dfe_f32=FAKE, mask_preds=FAKE, seg_preds=FAKE,
+            depth_pred=FAKE, proposal=FAKE)
+run = lambda **kw: lib.ph_khead_plan_run(h, C.byref(_lib.KheadIO(**dict(dict(ptrs, input_format=_lib.PH_IN_F32_NCHW), **kw))), None)
+assert run(input_format=5) == -1 and "input_format" in msg()
+assert run(f1=None) == -1 and "input map" in msg()
+assert run(bits=None) == -1 and "output pointer" in msg()
+assert run(x_f32=None) == -1 and "emit_f32" in msg()
+assert run(depth_proposal=FAKE + 4) == -1 and "depth_proposal" in msg()
+assert lib.ph_khead_plan_status(h, None) == 0 and lib.ph_khead_plan_timeouts(h, None) == 0      # two-pass plans: no device read
+lib.ph_khead_plan_destroy(h)
+cfg.emit_f32 = 0
+assert lib.ph_khead_plan_create(C.byref(cfg), C.c_void_p(FAKE), C.c_void_p(FAKE), 1 << 62, C.byref(h)) == 0
+assert run() == -1 and "emit_f32" in msg()
+lib.ph_khead_plan_destroy(h)
+print("run checks ok")
+"""
+
+
+def test_head_program_links_no_python():
+    """the C++ caller of the whole head is built next to the library and depends on libpolyhead.so and the HIP runtime only"""
+    assert os.path.exists(BLD.HEAD_EXAMPLE), "built by python -m polyphonicformer_amd.build"
+    needed = _elf_needed(BLD.HEAD_EXAMPLE)
+    assert "libpolyhead.so" in needed and any(n.startswith("libamdhip64") for n in needed)
+    assert not any("python" in n or "torch" in n or "c10" in n for n in needed), needed
