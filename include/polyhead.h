@@ -96,6 +96,10 @@ int ph_pool_rows(const uint16_t* xplanes, const uint16_t* dplanes, const uint32_
  * `count(M)` of the folded feat_transform bias (kernel_update_head.py:225,241), handed to ph_query_stage_counts */
 int ph_pool_counts(const uint16_t* xplanes, const uint16_t* dplanes, const uint32_t* bits, float* partial, int32_t* pcount,
                    int B, int N, int64_t HW, int nsplit, int prec, void* stream);
+/* the `nsplit` every plan of this library pools with when its caller names none (the cfgs' nsplit = 0, engine.default_nsplit):
+ * 4 * B * nsplit workgroups fill the chip once, at most 32 ranges and one per 128-pixel chunk; frame_invariant != 0: the split
+ * of a one-frame launch at any B (a frame's partial sums are then added in the same order whatever shares its launch) */
+int ph_pool_default_nsplit(int B, int64_t HW, int frame_invariant);
 
 /* ---- packed per-stage weights -------------------------------------------------------------
  * One KernelUpdateHead stage (kernel_update_head.py:21-191 parameters) packed by the host into
@@ -688,10 +692,10 @@ int ph_tracker_match_frames(ph_tracker* t, const float* boxes, const int64_t* la
  * by ph_decode_create / ph_decode_run before the first launch; only a launch the runtime itself refuses (PH_ELAUNCH) can
  * come back after earlier kernels of the sequence were queued.
  * A zero-initialised ph_decode_cfg plus the sizes and the mode is the module API's configuration: every knob on "auto"
- * (= engine.DecodePlan's rule with no environment variable set). */
+ * (= the rule of resolve() in csrc/ph_decode.hip, which engine.DecodePlan follows too, with no environment variable set). */
 enum { PH_MODE_FP32 = 0, PH_MODE_MIXED = 1, PH_MODE_MIXED16 = 2, PH_MODE_FP16 = 3, PH_MODE_BF16 = 4 };   /* engine.MODES */
-/* poolx / fused_up: AUTO = engine.DecodePlan's rule; ON = the fused form, an error (PH_EUNSUPPORTED) where it cannot run this
- * geometry; OFF = never; WHERE_SUPPORTED = wherever it can run (what PH_CONV_POOLX=1 / PH_CONV_UP2=1 do for the Python plan) */
+/* poolx / fused_up: AUTO = the library's rule (ask ph_decode_geometry_of what it picks); ON = the fused form, an error
+ * (PH_EUNSUPPORTED) where it cannot run this geometry; OFF = never; WHERE_SUPPORTED = wherever it can run (what PH_CONV_POOLX=1 / PH_CONV_UP2=1 do for the Python plan) */
 enum { PH_KNOB_AUTO = 0, PH_KNOB_ON = 1, PH_KNOB_OFF = 2, PH_KNOB_WHERE_SUPPORTED = 3 };
 typedef struct {
     int32_t B, N, H, W;         /* frames, queries (things + stuff), feature map (stride 8) */
@@ -710,10 +714,11 @@ typedef struct {
     int32_t up2_wgs;            /* 0 = auto (1.5 per CU), else the final stage's workgroups of shares_gpu plans (PH_UP2_SHARED_WGS) */
 } ph_decode_cfg;
 
-/* the geometry a plan chose (ph_decode_info) */
+/* the geometry a plan chose (ph_decode_info), or would choose (ph_decode_geometry_of) */
 typedef struct {
     int32_t nsplit, nsplit_px, poolx, fused_up;
-    int32_t up2_workgroups;     /* workgroups of the fused final stage's launches: 0 = one per CU */
+    int32_t up2_workgroups;     /* workgroups of the fused final stage's launches: 0 = one per CU; follows cfg.up2_wgs, which
+                                   only ph_decode_create fills from the device: ph_decode_geometry_of reports 0 when it is 0 */
     int32_t feat_prec, query_prec, conv_prec, kern_format;   /* PH_PREC_* / PH_KERN_* of ingest + pool, query, dynamic conv */
     int32_t feat_planes;        /* P of the feature planes [P][B][256][HWp] */
 } ph_decode_geometry;
@@ -786,6 +791,10 @@ size_t ph_decode_workspace_bytes(const ph_decode_cfg* cfg);         /* 0 on a ba
 int ph_decode_create(const ph_decode_cfg* cfg, const void* const* packs /* S device pointers */, void* workspace,
                      size_t workspace_bytes, ph_decode** out);
 int ph_decode_info(const ph_decode* plan, ph_decode_geometry* out);
+/* the same answer without a plan: the launch geometry rule applied to a cfg (it is the only copy of that rule: engine.DecodePlan
+ * takes nsplit, nsplit_px, poolx and fused_up from here).  Needs no device, no packs and no workspace; every cfg error of
+ * ph_decode_create comes back from here too.  up2_workgroups: see ph_decode_geometry */
+int ph_decode_geometry_of(const ph_decode_cfg* cfg, ph_decode_geometry* out);
 void ph_decode_destroy(ph_decode* plan);
 int ph_decode_run(ph_decode* plan, const ph_decode_io* io, void* stream);
 
@@ -809,7 +818,7 @@ int ph_decode_run(ph_decode* plan, const ph_decode_io* io, void* stream);
  *   onepass      PH_KNOB_AUTO: ph_khead_onepass wherever ph_khead_onepass_supported(B, H*W, groups, grade, PH_IN_F32_NCHW) says so
  *                (engine.KernelHeadPlan's rule with no environment variable set); PH_KNOB_ON: the same, PH_EUNSUPPORTED where
  *                it says no; PH_KNOB_OFF: always the two-pass ph_khead_fused (PH_KHEAD_TWOPASS of the Python plan)
- *   nsplit       0 = engine.default_nsplit(B, H*W, frame_invariant), else the pixel ranges of the object pooling (PH_POOL_NSPLIT) */
+ *   nsplit       0 = ph_pool_default_nsplit(B, H*W, frame_invariant), else the pixel ranges of the object pooling (PH_POOL_NSPLIT) */
 typedef struct {
     int32_t B, H, W;            /* frames, feature map (stride 8) */
     int32_t num_proposals;      /* rows of init_kernels (thing queries), 1 .. 256 */

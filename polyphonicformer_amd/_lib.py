@@ -91,6 +91,7 @@ SIGNATURES = {
     "ph_pool": (C.c_int, [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
     "ph_pool_rows": (C.c_int, [_P, _P, _P, _I, _P, _I, _I, _L, _I, _I, _P]),
     "ph_pool_counts": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
+    "ph_pool_default_nsplit": (C.c_int, [_I, _L, _I]),
     "ph_query_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "ph_query_stage": (C.c_int, [_P, _I, _P, _P, _P, _P, _P, C.POINTER(StageLayout), _P, _P, _P, _I, _P, _P,
                                  _P, _Z, _I, _I, _L, _I, _I, _I, _P]),
@@ -212,6 +213,7 @@ SIGNATURES = {
     "ph_decode_workspace_bytes": (C.c_size_t, [C.POINTER(DecodeCfg)]),
     "ph_decode_create": (C.c_int, [C.POINTER(DecodeCfg), C.POINTER(C.c_void_p), _P, _Z, C.POINTER(C.c_void_p)]),
     "ph_decode_info": (C.c_int, [_P, C.POINTER(DecodeGeometry)]),
+    "ph_decode_geometry_of": (C.c_int, [C.POINTER(DecodeCfg), C.POINTER(DecodeGeometry)]),
     "ph_decode_destroy": (None, [_P]),
     "ph_decode_run": (C.c_int, [_P, C.POINTER(DecodeIO), _P]),
     "ph_khead_param_name": (C.c_char_p, [_I]),

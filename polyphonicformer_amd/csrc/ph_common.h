@@ -32,6 +32,16 @@ void ph_set_error(const char* fmt, ...);
         }                                                                          \
     } while (0)
 
+// run-or-return for host code that chains other entry points of this library (the native plans' launch sequences)
+#define PH_RUN(call)                   \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != PH_OK) return rc_;  \
+    } while (0)
+
+// the pieces of a caller-owned workspace or pack start at 256-byte boundaries
+static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+
 // ---- the hard mask threshold (kernel_update_head.py:236-238, kernel_head.py:314-317): `sigmoid(z) > 0.5` in fp32.
 // Evaluated as the reference does -- 1 / (1 + exp(-z)), every operation rounded to fp32 -- the comparison is true exactly
 // for z > 1.5 * 2^-24: below that 1 - z rounds to 1 - 2^-24 or 1, 2 - 2^-24 rounds to 2, and 1 / 2 = 0.5.  (Probe on

@@ -1,5 +1,6 @@
-// N2: the S-stage decode as a native object (include/polyhead.h ph_decode_*): the launch sequence, the geometry rules and the
-// buffer plan of engine.DecodePlan, and the stage packing of pack.py as one HIP kernel.  Host code only calls the other
+// N2: the S-stage decode as a native object (include/polyhead.h ph_decode_*): the launch geometry rule of every decode plan
+// (resolve(): engine.DecodePlan asks it through ph_decode_geometry_of), the launch sequence and the buffer plan of
+// engine.DecodePlan, and the stage packing of pack.py as one HIP kernel.  Host code only calls the other
 // entry points of this library, on the caller's stream; nothing here allocates device memory or synchronises.
 #include <math.h>
 #include <string.h>
@@ -63,7 +64,8 @@ static int64_t param_numel(int F, int L, int i) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// geometry: engine.DecodePlan.__init__'s choices, with the environment replaced by the cfg's fields
+// geometry: resolve() is the ONE launch-geometry rule of the decode -- the native plan's and, through ph_decode_geometry_of,
+// engine.DecodePlan's; the environment switches of the Python side arrive as the cfg's fields (engine.native_cfg)
 struct Geo {
     int B, N, H, W, S, L, F;
     int64_t HW, HWp;
@@ -78,17 +80,6 @@ struct Geo {
     size_t ws_bytes;                                    // ph_query_workspace_bytes (what the query kernel is told)
     size_t s_obj, s_dobj, s_cls, s_kern, s_kbias;       // offsets inside one stage's piece
 };
-
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-static int default_nsplit(int B, int64_t HWp, bool fi) {   // engine.default_nsplit without PH_POOL_NSPLIT
-    const int64_t nchunks = HWp / 128;
-    int ns = 512 / (4 * (fi ? 1 : B));
-    if (ns < 1) ns = 1;
-    int64_t r = ns < 32 ? ns : 32;
-    const int64_t c = nchunks > 1 ? nchunks : 1;
-    return (int)(r < c ? r : c);
-}
 
 static int knob_ok(int k) { return k >= PH_KNOB_AUTO && k <= PH_KNOB_WHERE_SUPPORTED; }
 
@@ -125,10 +116,16 @@ static int resolve(const ph_decode_cfg* c, Geo& g, const char* fn) {
     if ((int64_t)g.B * g.Npad > 65535) { ph_set_error("%s: B * Npad must be <= 65535", fn); return PH_EUNSUPPORTED; }
     if ((int64_t)g.B * g.N * g.HW / 8 >= (1ll << 31)) { ph_set_error("%s: B * N * H * W / 8 must be < 2^31", fn); return PH_EUNSUPPORTED; }
     const bool fi = g.frame_invariant != 0;
-    g.nsplit = c->nsplit ? c->nsplit : default_nsplit(g.B, g.HWp, fi);
+    g.nsplit = c->nsplit ? c->nsplit : ph_pool_default_nsplit(g.B, g.HW, fi);
     if (g.nsplit > g.HWp / 64) { ph_set_error("%s: nsplit out of range (at most H*W / 64 rounded up to 128)", fn); return PH_EINVAL; }
 
-    // final stage: conv + x2 upsample fused where it exists (DecodePlan: one-plane kernels, B * H >= 512 or forced)
+    // Final stage: conv + x2 upsample in ONE kernel where it exists (W = 256, one-plane conv grades, 16-bit outputs): the
+    // low-resolution logits are not written and re-read, the depth branch's are not written at all unless the caller asks (no
+    // caller of simple_test / simple_test_mask_preds ever receives them: kernel_update.py:338-345,401).
+    // Chosen when the batch has at least two image rows per CU (B * H >= 512): below that a workgroup's range is one or two rows
+    // and the silent halo row above it doubles its work -- one frame per launch: 34 us against 26 us for the two kernels, equal
+    // at 2-4 frames, ahead from 8 (same box).  `frame_invariant` plans decide as a one-frame launch would.  The knob forces the
+    // fused form at any size (WHERE_SUPPORTED / ON: tests, PH_CONV_UP2=1) or the two-kernel form (OFF).
     const bool up2_sup = g.KP == 1 && ph_dynconv_up2_supported(g.N, g.H, g.W, g.conv, g.out_dtype);
     if (c->fused_up == PH_KNOB_ON && !up2_sup) {
         ph_set_error("%s: the fused final stage (ph_dynconv_up2) cannot run this geometry / arithmetic (W == 256, 65 <= N <= 224, "
@@ -139,7 +136,14 @@ static int resolve(const ph_decode_cfg* c, Geo& g, const char* fn) {
                : (c->fused_up == PH_KNOB_AUTO ? (up2_sup && (int64_t)(fi ? 1 : g.B) * g.H >= 512) : up2_sup);
     g.up2_wgs = c->up2_wgs;   // 0: 1.5 per CU of the plan's device, filled in by ph_decode_create
 
-    // between the stages: the mask conv also pools the x map for the next stage (ph_dynconv_poolx)
+    // Between the stages: a non-final stage's mask conv also pools the x map for the NEXT stage from the same read of the plane
+    // (ph_dynconv_poolx), the next stage then pools depth_feats alone: 33.5 MB instead of 50 MB per frame and stage boundary at
+    // cfg2.  One workgroup per (frame, pixel range) and CU: for launches that fill the chip (B * nsplit_px >= 192), at least 16
+    // tiles of 64 pixels per workgroup (its prologue loads the frame's kernels, its epilogue writes Npad x 256 sums).  Throughput
+    // plans split by B (256 / B ranges).  `frame_invariant` plans: the kernel's pixel ranges are k_pool's, and in the bf16 / fp16
+    // grades its sums are k_pool's bit for bit at the same split (tests/test_gpu_kernels.py) -- with the plan's one-frame split
+    // the choice between the two forms is invisible in a frame's outputs and may follow B, given 8 tiles per range; `mixed16`
+    // pools the fp16-converted tile (1e-6 apart): its invariant plans keep the separate kernels.
     bool px_ok;
     if (fi) {
         if (c->nsplit_px && c->nsplit_px != g.nsplit) { ph_set_error("%s: frame_invariant plans pool with nsplit (nsplit_px must be 0 or equal)", fn); return PH_EINVAL; }
@@ -501,13 +505,31 @@ extern "C" int ph_decode_create(const ph_decode_cfg* cfg, const void* const* pac
     return PH_OK;
 }
 
-extern "C" int ph_decode_info(const ph_decode* p, ph_decode_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    const Geo& g = p->g;
+// workgroups of the fused final stage's launches: a part of a multi-stream step (`shares_gpu`) takes 1.5 per CU (g.up2_wgs) -- the
+// other parts' query kernels hold CUs when the launch starts, and what cannot start at once leaves a shorter tail; 0 = one per CU
+static int up2_workgroups(const Geo& g) {
+    return (g.fused_up && g.shares_gpu && (int64_t)g.B * g.H >= 4 * (int64_t)g.up2_wgs) ? g.up2_wgs : 0;
+}
+
+static void fill_geometry(const Geo& g, ph_decode_geometry* out) {
     out->nsplit = g.nsplit; out->nsplit_px = g.nsplit_px; out->poolx = g.poolx; out->fused_up = g.fused_up;
-    out->up2_workgroups = (g.fused_up && g.shares_gpu && (int64_t)g.B * g.H >= 4 * (int64_t)g.up2_wgs) ? g.up2_wgs : 0;
+    out->up2_workgroups = up2_workgroups(g);
     out->feat_prec = g.feat; out->query_prec = g.query; out->conv_prec = g.conv; out->kern_format = g.kern_fmt;
     out->feat_planes = g.FP;
+}
+
+extern "C" int ph_decode_geometry_of(const ph_decode_cfg* cfg, ph_decode_geometry* out) {
+    Geo g;
+    const int rc = resolve(cfg, g, "ph_decode_geometry_of");
+    if (rc) return rc;
+    PH_CHECK_ARG(out != nullptr, "null out");
+    fill_geometry(g, out);
+    return PH_OK;
+}
+
+extern "C" int ph_decode_info(const ph_decode* p, ph_decode_geometry* out) {
+    PH_CHECK_ARG(p && out, "null plan or out");
+    fill_geometry(p->g, out);
     return PH_OK;
 }
 
@@ -518,12 +540,6 @@ extern "C" void ph_decode_destroy(ph_decode* p) { delete p; }
 static const PhConvKnobs kConv{};
 static const PhUp2Knobs kUp2{};
 static const PhQueryKnobs kQuery{};
-
-#define PH_DRUN(call)                  \
-    do {                               \
-        const int rc_ = (call);        \
-        if (rc_ != PH_OK) return rc_;  \
-    } while (0)
 
 extern "C" int ph_decode_run(ph_decode* p, const ph_decode_io* io, void* stream) {
     PH_CHECK_ARG(p && io, "null plan or io");
@@ -559,8 +575,8 @@ extern "C" int ph_decode_run(ph_decode* p, const ph_decode_io* io, void* stream)
     // ingest (engine.DecodePlan.ingest / set_inputs / run_from_planes)
     const uint16_t *xr = xp, *dr = dp;
     if (io->feat_format == PH_FEAT_F32) {
-        PH_DRUN(ph_ingest_features((const float*)io->x, xp, B, HW, g.feat, s));
-        PH_DRUN(ph_ingest_features((const float*)io->depth_feats, dp, B, HW, g.feat, s));
+        PH_RUN(ph_ingest_features((const float*)io->x, xp, B, HW, g.feat, s));
+        PH_RUN(ph_ingest_features((const float*)io->depth_feats, dp, B, HW, g.feat, s));
     } else if (io->feat_format == PH_FEAT_16) {
         const dim3 grid((unsigned)((HWp + 255) / 256 < 8 ? (HWp + 255) / 256 : 8), (unsigned)(B * 256));
         hipLaunchKernelGGL(k_decode_rows16, grid, dim3(256), 0, s, (const uint16_t*)io->x, xp, HW, HWp);
@@ -576,7 +592,7 @@ extern "C" int ph_decode_run(ph_decode* p, const ph_decode_io* io, void* stream)
             return PH_ELAUNCH;
         }
     } else {
-        PH_DRUN(ph_binarize_if(io->m0, io->m0_dtype, 0, bits, B, N, HW, nullptr, s));
+        PH_RUN(ph_binarize_if(io->m0, io->m0_dtype, 0, bits, B, N, HW, nullptr, s));
     }
 
     // the S stages (engine.DecodePlan.stages)
@@ -595,35 +611,35 @@ extern "C" int ph_decode_run(ph_decode* p, const ph_decode_io* io, void* stream)
         const int32_t* cnt;
         int ns;
         if (st > 0 && g.poolx) {
-            PH_DRUN(ph_pool_counts(dr, nullptr, bits, partial_px + 256, pcount_px, B, N, HW, g.nsplit_px, g.feat, s));
+            PH_RUN(ph_pool_counts(dr, nullptr, bits, partial_px + 256, pcount_px, B, N, HW, g.nsplit_px, g.feat, s));
             part = partial_px; cnt = pcount_px; ns = g.nsplit_px;
         } else {
-            PH_DRUN(ph_pool_counts(xr, dr, bits, partial, pcount, B, N, HW, g.nsplit, g.feat, s));
+            PH_RUN(ph_pool_counts(xr, dr, bits, partial, pcount, B, N, HW, g.nsplit, g.feat, s));
             part = partial; cnt = pcount; ns = g.nsplit;
         }
         const uint16_t* wb = (const uint16_t*)p->packs[st];
         const float* wf = (const float*)((const char*)p->packs[st] + p->wf_byte_off);
-        PH_DRUN(ph_query_stage_counts_k(kQuery, part, ns, bits, cnt, k, q, wb, wf, &p->lay, obj, dobj, cls, last ? 1 : 0, kern, kbias, ws,
+        PH_RUN(ph_query_stage_counts_k(kQuery, part, ns, bits, cnt, k, q, wb, wf, &p->lay, obj, dobj, cls, last ? 1 : 0, kern, kbias, ws,
                                       g.ws_bytes, B, N, HW, g.query, g.kern_fmt, phases, s));
         if (!last) {
             if (g.poolx)
-                PH_DRUN(ph_dynconv_poolx(xr, kern, Npad * 256, kbias, Npad, bits, partial_px, g.nsplit_px, B, N, HW, g.conv, s));
+                PH_RUN(ph_dynconv_poolx(xr, kern, Npad * 256, kbias, Npad, bits, partial_px, g.nsplit_px, B, N, HW, g.conv, s));
             else
-                PH_DRUN(ph_dynconv_k(kConv, xr, kern, 2 * kb, Npad * 256, kbias, Npad, bits, nullptr, PH_OUT_F32, (int64_t)N * HW, B, N, HW,
+                PH_RUN(ph_dynconv_k(kConv, xr, kern, 2 * kb, Npad * 256, kbias, Npad, bits, nullptr, PH_OUT_F32, (int64_t)N * HW, B, N, HW,
                                    g.conv, s));
         } else if (g.fused_up) {
-            const int wg = (g.shares_gpu && (int64_t)B * H >= 4 * (int64_t)g.up2_wgs) ? g.up2_wgs : 0;
-            PH_DRUN(ph_dynconv_up2_k(kUp2, xr, kern, Npad * 256, kbias, Npad, io->mask, io->mask_up, g.out_dtype, B, N, H, W, g.conv, wg, s));
-            PH_DRUN(ph_dynconv_up2_k(kUp2, dr, kern + kb, Npad * 256, kbias + (int64_t)B * Npad, Npad, io->depth, io->depth_up, g.out_dtype,
+            const int wg = up2_workgroups(g);
+            PH_RUN(ph_dynconv_up2_k(kUp2, xr, kern, Npad * 256, kbias, Npad, io->mask, io->mask_up, g.out_dtype, B, N, H, W, g.conv, wg, s));
+            PH_RUN(ph_dynconv_up2_k(kUp2, dr, kern + kb, Npad * 256, kbias + (int64_t)B * Npad, Npad, io->depth, io->depth_up, g.out_dtype,
                                        B, N, H, W, g.conv, wg, s));
         } else {
             void* depth = io->depth ? io->depth : (void*)(p->ws + g.o_depth);
-            PH_DRUN(ph_dynconv_k(kConv, xr, kern, 2 * kb, Npad * 256, kbias, Npad, nullptr, io->mask, g.out_dtype, (int64_t)N * HW, B, N, HW,
+            PH_RUN(ph_dynconv_k(kConv, xr, kern, 2 * kb, Npad * 256, kbias, Npad, nullptr, io->mask, g.out_dtype, (int64_t)N * HW, B, N, HW,
                                g.conv, s));
-            PH_DRUN(ph_upsample2x(io->mask, io->mask_up, g.out_dtype, (int64_t)B * N, H, W, s));
-            PH_DRUN(ph_dynconv_k(kConv, dr, kern + kb, 2 * kb, Npad * 256, kbias + (int64_t)B * Npad, Npad, nullptr, depth, g.out_dtype,
+            PH_RUN(ph_upsample2x(io->mask, io->mask_up, g.out_dtype, (int64_t)B * N, H, W, s));
+            PH_RUN(ph_dynconv_k(kConv, dr, kern + kb, 2 * kb, Npad * 256, kbias + (int64_t)B * Npad, Npad, nullptr, depth, g.out_dtype,
                                (int64_t)N * HW, B, N, HW, g.conv, s));
-            PH_DRUN(ph_upsample2x(depth, io->depth_up, g.out_dtype, (int64_t)B * N, H, W, s));
+            PH_RUN(ph_upsample2x(depth, io->depth_up, g.out_dtype, (int64_t)B * N, H, W, s));
         }
         k = obj;
         q = dobj;

@@ -38,17 +38,6 @@ struct KGeo {
     size_t pack_total;
 };
 
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
-static int default_nsplit(int B, int64_t HWp, bool fi) {   // engine.default_nsplit without PH_POOL_NSPLIT
-    const int64_t nchunks = HWp / 128;
-    int ns = 512 / (4 * (fi ? 1 : B));
-    if (ns < 1) ns = 1;
-    const int64_t r = ns < 32 ? ns : 32;
-    const int64_t c = nchunks > 1 ? nchunks : 1;
-    return (int)(r < c ? r : c);
-}
-
 // `need_device`: the one-pass rule asks the current device for its CU count; the pack entry points do not need it
 static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn, bool need_device) {
     if (!c) { ph_set_error("%s: null cfg", fn); return PH_EINVAL; }
@@ -85,7 +74,7 @@ static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn, bool need_dev
     g.HW = (int64_t)g.H * g.W;
     g.HWp = ph_hw_padded(g.HW);
     if ((int64_t)g.B * g.Npad > 65535) { ph_set_error("%s: B * Npad must be <= 65535", fn); return PH_EUNSUPPORTED; }
-    g.nsplit = c->nsplit ? c->nsplit : default_nsplit(g.B, g.HWp, c->frame_invariant != 0);
+    g.nsplit = c->nsplit ? c->nsplit : ph_pool_default_nsplit(g.B, g.HW, c->frame_invariant != 0);
     if (g.nsplit > g.HWp / 64) { ph_set_error("%s: nsplit out of range (at most H*W / 64 rounded up to 128)", fn); return PH_EINVAL; }
 
     // pack pieces (engine.KernelHeadPack)
@@ -326,12 +315,6 @@ extern "C" void ph_khead_plan_destroy(ph_khead_plan* p) { delete p; }
 // PH_KHEAD1_PAIR / PH_NECK_STATS3 / PH_NECK_APPLY3 is set
 static const PhKheadKnobs kKhead{};
 
-#define PH_KRUN(call)                  \
-    do {                               \
-        const int rc_ = (call);        \
-        if (rc_ != PH_OK) return rc_;  \
-    } while (0)
-
 extern "C" int ph_khead_plan_run(ph_khead_plan* p, const ph_khead_io* io, void* stream) {
     PH_CHECK_ARG(p && io, "null plan or io");
     const KGeo& g = p->g;
@@ -351,29 +334,29 @@ extern "C" int ph_khead_plan_run(ph_khead_plan* p, const ph_khead_io* io, void* 
     void* ws2 = p->ws + g.o_ws2;
     float* partial = (float*)(p->ws + g.o_partial);
     if (g.onepass) {
-        PH_KRUN(ph_khead_onepass_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_CONV_FRAG), f32(PH_KPACK_GN), g.groups, 1e-5f,
+        PH_RUN(ph_khead_onepass_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_CONV_FRAG), f32(PH_KPACK_GN), g.groups, 1e-5f,
                                    u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
                                    u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
                                    io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, io->bits, g.Npad, ws1,
                                    g.ws1_bytes, B, HW, g.prec, fmt, s));
         // the in-call fallback, predicated on the one-pass launch's status word (the first word of its hand-off state)
-        PH_KRUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+        PH_RUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
                                     u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
                                     u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
                                     io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, (const uint32_t*)ws1,
                                     ws2, g.ws2_bytes, B, HW, g.prec, fmt, s));
-        PH_KRUN(ph_binarize_if(io->mask_preds, g.logit_dtype, 0, io->bits, B, g.N, HW, (const uint32_t*)ws1, s));
+        PH_RUN(ph_binarize_if(io->mask_preds, g.logit_dtype, 0, io->bits, B, g.N, HW, (const uint32_t*)ws1, s));
     } else {
-        PH_KRUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+        PH_RUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
                                     u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
                                     u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
                                     io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, PH_OUT_F32, nullptr, ws2, g.ws2_bytes,
                                     B, HW, g.prec, fmt, s));
-        PH_KRUN(ph_binarize((const float*)io->mask_preds, 0, io->bits, B, g.N, HW, s));
+        PH_RUN(ph_binarize((const float*)io->mask_preds, 0, io->bits, B, g.N, HW, s));
     }
     // object features: pool x over the THING rows of the bit tensor (kernel_head.py:314-320), add them to the kernels (:324-326)
-    PH_KRUN(ph_pool_rows(io->xp, nullptr, io->bits, g.Npad, partial, B, g.Nq, HW, g.nsplit, g.prec, s));
-    PH_KRUN(ph_khead_proposals(partial, g.nsplit, f32(PH_KPACK_W_INIT_F32),
+    PH_RUN(ph_pool_rows(io->xp, nullptr, io->bits, g.Npad, partial, B, g.Nq, HW, g.nsplit, g.prec, s));
+    PH_RUN(ph_khead_proposals(partial, g.nsplit, f32(PH_KPACK_W_INIT_F32),
                                g.n_stuff ? f32(PH_KPACK_W_SEG_F32) + (size_t)g.n_thing * 256 : nullptr, io->proposal, B, g.Nq,
                                g.n_stuff, s));
     if (io->depth_proposal) {

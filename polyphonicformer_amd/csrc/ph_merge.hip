@@ -577,7 +577,6 @@ extern "C" int ph_panoptic_paste_batch(const int32_t* ids, const int32_t* newid,
 // No host step, no allocation, no synchronisation, no environment: capturable in a HIP graph right behind ph_decode_run.
 // Workspace pieces (256-byte aligned each): pack [B][5K] int32 (q | labels | scores | counts [2][K], as panoptic.DeviceMerge keeps
 // them), act_mask / act_depth [B][K][h2][w2] fp32, act_depth0 [B][h2][w2] fp32, ids [B][Ho][Wo] int32, newid [B][K] int32.
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 struct MergeLayout { size_t pack, act_mask, act_depth, act_depth0, ids, newid, total; };
 

@@ -352,3 +352,17 @@ extern "C" int ph_pool_counts(const uint16_t* xplanes, const uint16_t* dplanes, 
     if (!pcount) { ph_set_error("ph_pool_counts: null pcount"); return PH_EINVAL; }
     return pool_run(xplanes, dplanes, bits, 0, partial, pcount, B, N, HW, nsplit, prec, stream, __func__);
 }
+
+// Pixel ranges per frame of the split-K pooling when the caller names none: 4 * B * nsplit workgroups should fill the chip's
+// resident slots (2 workgroups per CU x 256 CUs) without a partial second generation, at most 32 ranges and at most one per
+// 128-pixel chunk.  `frame_invariant`: the split of a ONE-frame launch whatever B is -- the split fixes the order in which a
+// frame's partial sums are added, so this is what keeps a frame's bits independent of the frames that share its launch (the
+// module API; throughput callers -- bench.py -- split by B).  The one copy of this rule: both native plans and
+// engine.default_nsplit call it.
+extern "C" int ph_pool_default_nsplit(int B, int64_t HW, int frame_invariant) {
+    const int64_t nchunks = ph_hw_padded(HW) / 128;
+    int64_t ns = 512 / (4 * (int64_t)(frame_invariant || B < 1 ? 1 : B));
+    if (ns > 32) ns = 32;
+    if (ns > nchunks) ns = nchunks;
+    return ns < 1 ? 1 : (int)ns;
+}

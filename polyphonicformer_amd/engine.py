@@ -90,16 +90,11 @@ def plan_env_key():
 
 
 def default_nsplit(B, HW, frame_invariant=False):
-    """pixel ranges per frame for the split-K pooling: 4*B*nsplit workgroups should fill the chip's resident
-    slots (2 workgroups per CU x 256 CUs) without a partial second generation.  `frame_invariant`: the split of a ONE-frame
-    launch whatever B is -- the split fixes the order in which a frame's partial sums are added, so this is what keeps a frame's
-    bits independent of the frames that share its launch (the module API; throughput callers -- bench.py -- split by B)"""
-    import os
-    if os.environ.get("PH_POOL_NSPLIT"):
-        return int(os.environ["PH_POOL_NSPLIT"])
-    nchunks = hw_padded(HW) // 128
-    ns = max(1, 512 // (4 * (1 if frame_invariant else B)))
-    return int(min(ns, 32, max(1, nchunks)))
+    """pixel ranges per frame for the split-K pooling: PH_POOL_NSPLIT when set, else the library's rule (ph_pool_default_nsplit,
+    csrc/ph_pool.hip, which also says what `frame_invariant` -- the split of a ONE-frame launch whatever B is -- buys)"""
+    if _os.environ.get("PH_POOL_NSPLIT"):
+        return int(_os.environ["PH_POOL_NSPLIT"])
+    return int(_lib.load().ph_pool_default_nsplit(B, HW, int(bool(frame_invariant))))
 
 
 # ---- thin op wrappers (each = one C-ABI call) ---------------------------------------------------
@@ -244,25 +239,60 @@ def upsample2x(src, out=None):
 
 
 # ---- the S-stage plan ------------------------------------------------------------------------------
+def native_cfg(B, N, H, W, S, L, F, prec, out_dtype=torch.float32, frame_invariant=False, shares_gpu=False, nsplit=None):
+    """the ph_decode_cfg of a decode plan, Python or native: the ONE place that reads the plans' environment switches
+    (PH_CONV_POOLX, PH_CONV_UP2, PH_POOL_NSPLIT, PH_POOLX_NSPLIT, PH_UP2_SHARED_WGS), which become the cfg's explicit fields --
+    the library itself never reads them.  DecodePlan asks the library for its launch geometry with it (ph_decode_geometry_of),
+    NativeDecodePlan creates its plan from it, so the two agree by construction"""
+    mode = mode_of(prec)
+    env = _os.environ.get
+    knob = lambda v: {"0": _lib.PH_KNOB_OFF, "1": _lib.PH_KNOB_WHERE_SUPPORTED}.get(v, _lib.PH_KNOB_AUTO)
+    return _lib.DecodeCfg(B=B, N=N, H=H, W=W, S=S, L=L, F=F, mode=_lib.PH_MODE[mode.name], out_dtype=OUT_CODE[out_dtype],
+                          frame_invariant=int(bool(frame_invariant)),
+                          query_full_split=int(mode.name in ("mixed16", "fp16") and mode.query == _lib.PH_PREC_SPLIT),
+                          shares_gpu=int(bool(shares_gpu)), poolx=knob(env("PH_CONV_POOLX")), fused_up=knob(env("PH_CONV_UP2")),
+                          nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0),
+                          nsplit_px=0 if frame_invariant else int(env("PH_POOLX_NSPLIT") or 0),
+                          up2_wgs=int(env("PH_UP2_SHARED_WGS") or 0))
+
+
+def _cfg_error(what):
+    msg = _lib.load().ph_last_error_string()
+    return _lib.PolyheadError(f"{what}: {msg.decode() if msg else ''}")
+
+
 class DecodePlan:
     """All buffers for `simple_test_mask_preds` at one (B, N, H, W, precision, output dtype)."""
 
-    def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False):
+    def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False,
+                 shares_gpu=False):
         """`frame_invariant` (round 6): every choice that touches a frame's arithmetic -- the pooling's pixel split, the fused / two-
         kernel final stage -- is the ONE-frame launch's at any B, so a frame's outputs do not depend on its batch (the module API's
-        default; a clip's frames through one launch equal the per-frame loop bit for bit)"""
+        default; a clip's frames through one launch equal the per-frame loop bit for bit).
+        `shares_gpu`: the plan is one part of a multi-stream step (DualDecodePlan): query launches with the most rows per workgroup
+        (PH_QUERY_WIDE), the fused final stage with `up2_shared_wgs` workgroups -- the other parts' kernels run beside them"""
         self.packs, self.S = packs, len(packs)
-        self.frame_invariant = frame_invariant
+        self.frame_invariant, self.shares_gpu = frame_invariant, shares_gpu
+        self.feat_is_bf16 = False      # set_inputs: the features came as 16-bit planes, no ingest pass
+        self.debug_bits = None         # tests: a list that receives the hard masks every stage pools with (eager runs only)
+        self.on_first_pool = None      # multi-part callers skew their parts by one phase: called behind the first stage's pooling
         self.B, self.N, self.H, self.W, self.HW = B, N, H, W, H * W
         self.mode = mode_of(prec)
         self.prec, self.out_dtype = self.mode.feat, out_dtype           # `prec`: the feature planes' code (ingest / pool)
         if any(p.prec != self.mode.query for p in packs):
             raise _lib.PolyheadError(f"stage packs are not packed for mode '{self.mode.name}'")
-        self.nsplit = nsplit or default_nsplit(B, self.HW, frame_invariant)
+        # the launch geometry -- the pooling's pixel split, whether the stage-boundary conv also pools (ph_dynconv_poolx) and
+        # whether the final stage is conv + x2 upsample in one kernel (ph_dynconv_up2) -- is the library's choice: the rule and the
+        # measurements behind its thresholds live in resolve() of csrc/ph_decode.hip, the same call a native plan is built from
+        L = packs[0].num_classes
+        cfg = native_cfg(B, N, H, W, self.S, L, packs[0].lay.ffn_dim, self.mode, out_dtype, frame_invariant, shares_gpu, nsplit)
+        geo = _lib.DecodeGeometry()
+        if _lib.load().ph_decode_geometry_of(C.byref(cfg), C.byref(geo)) != 0:
+            raise _cfg_error("ph_decode_geometry_of")
+        self.nsplit, self.nsplit_px, self.poolx, self.fused_up = geo.nsplit, geo.nsplit_px, bool(geo.poolx), bool(geo.fused_up)
         dev = torch.device(device)
         P, KP = self.mode.FP, self.mode.KP
         Npad, HWp = n_padded(N), hw_padded(self.HW)
-        L = packs[0].num_classes
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         # static inputs (graph-capturable)
         self.x = e((B, 256, H, W), torch.float32)
@@ -290,37 +320,10 @@ class DecodePlan:
         self.depth_up = e((B, N, 2 * H, 2 * W), out_dtype)
         self.graph = None
         self.handoff_runs = 0          # runs that started from another kernel's planes (tests observe the path taken)
-        # Final stage: conv + x2 upsample in ONE kernel where it exists (W = 256, one-plane conv grades, 16-bit outputs): the
-        # low-resolution logits are not written and re-read, the depth branch's are not written at all (no caller of
-        # simple_test / simple_test_mask_preds ever receives them: kernel_update.py:338-345,401).  `want_depth_lowres` makes the
-        # fused depth launch write them too.
-        # Chosen when the batch has at least two image rows per CU (B * H >= 512): below that a workgroup's range is one or two rows
-        # and the silent halo row above it doubles its work -- one frame per launch: 34 us against 26 us for the two kernels, equal
-        # at 2-4 frames, ahead from 8 (same box).  PH_CONV_UP2=1 forces the fused form at any size (tests), =0 the two-kernel form.
-        _up2 = _os.environ.get("PH_CONV_UP2", "auto")
-        self.fused_up = (KP == 1 and _up2 != "0" and (_up2 == "1" or (1 if frame_invariant else B) * H >= 512)
-                         and bool(_lib.load().ph_dynconv_up2_supported(N, H, W, self.mode.conv, OUT_CODE[out_dtype])))
-        self.want_depth_lowres = False
+        self.want_depth_lowres = False     # the fused final stage writes the depth branch's low-resolution logits only on request
         # workgroups of the fused final stage when the plan is one part of a multi-stream step: 1.5 per CU (PH_UP2_SHARED_WGS=n; stages())
         self.up2_shared_wgs = int(_os.environ.get("PH_UP2_SHARED_WGS") or
-                                  (3 * torch.cuda.get_device_properties(device).multi_processor_count // 2 if torch.device(device).type == "cuda" else 0))
-        # Round 6: a non-final stage's mask conv also pools the x map for the NEXT stage from the same read of the plane
-        # (ph_dynconv_poolx), the next stage then pools depth_feats alone: 33.5 MB instead of 50 MB per frame and stage boundary at
-        # cfg2.  One workgroup per (frame, pixel range) and CU: for launches that fill the chip, at least 16 tiles of 64 pixels per
-        # workgroup (its prologue loads the frame's kernels, its epilogue writes Npad x 256 sums).  Throughput plans split by B
-        # (256 / B ranges).  `frame_invariant` plans: the kernel's pixel ranges are k_pool's, and in the bf16 / fp16 grades its sums are
-        # k_pool's bit for bit at the same split (tests/test_gpu_kernels.py) -- with the plan's one-frame split the choice between the two
-        # forms is invisible in a frame's outputs and may follow B; `mixed16` pools the fp16-converted tile (1e-6 apart): its invariant
-        # plans keep the separate kernels.  PH_CONV_POOLX=0 / 1: never / wherever supported
-        px_env = _os.environ.get("PH_CONV_POOLX", "auto")
-        if frame_invariant:
-            self.nsplit_px = self.nsplit
-            px_ok = self.mode.conv in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) and HWp // (64 * max(self.nsplit_px, 1)) >= 8
-        else:
-            self.nsplit_px = int(_os.environ.get("PH_POOLX_NSPLIT") or max(1, min(256 // max(B, 1), HWp // (64 * 16))))
-            px_ok = True
-        self.poolx = (KP == 1 and self.S > 1 and px_env != "0" and px_ok and (px_env == "1" or B * self.nsplit_px >= 192)
-                      and bool(_lib.load().ph_dynconv_poolx_supported(N, self.mode.conv)))
+                                  (3 * torch.cuda.get_device_properties(device).multi_processor_count // 2 if dev.type == "cuda" else 0))
         if self.poolx:
             self.partial_px = e((B, self.nsplit_px, Npad, 512), torch.float32)
             self.pcount_px = e((B, self.nsplit_px, Npad), torch.int32)
@@ -368,7 +371,7 @@ class DecodePlan:
         self.m0.copy_(m0)
 
     def ingest(self):
-        if not getattr(self, "feat_is_bf16", False):
+        if not self.feat_is_bf16:
             ingest(self.x, self.prec, out=self.xp)
             ingest(self.dfe, self.prec, out=self.dp)
         binarize(self.m0, out=self.bits)
@@ -381,7 +384,7 @@ class DecodePlan:
         k, q = self.k0, self.q0
         for s in range(self.S):
             last = s == self.S - 1
-            if getattr(self, "debug_bits", None) is not None:      # tests: the hard masks stage s pools with (eager runs only)
+            if self.debug_bits is not None:      # tests: the hard masks stage s pools with (eager runs only)
                 self.debug_bits.append(self.bits.clone())
             if s > 0 and self.poolx:
                 # the x map's sums came with the previous stage's conv (same read of the plane): depth_feats alone here
@@ -390,11 +393,11 @@ class DecodePlan:
             else:
                 pool(xp, dp, self.bits, self.N, self.HW, self.prec, self.nsplit, out=self.partial, counts=self.pcount)
                 part, cnt = self.partial, self.pcount
-            if s == 0 and getattr(self, "on_first_pool", None) is not None:
+            if s == 0 and self.on_first_pool is not None:
                 self.on_first_pool()       # multi-part callers skew their parts by one phase (an event recorded here)
             o = query_stage(part, self.bits, k, q, self.packs[s], self.N, self.HW, cls_sigmoid=last,
                             outs=self.stage_out[s], workspace=self.ws, kern_fmt=self.mode.kern_fmt, counts=cnt,
-                            phases=3 | (_lib.PH_QUERY_WIDE if getattr(self, "shares_gpu", False) else 0))
+                            phases=3 | (_lib.PH_QUERY_WIDE if self.shares_gpu else 0))
             cv = self.mode.conv
             if not last:
                 if self.poolx:
@@ -408,7 +411,7 @@ class DecodePlan:
                 if self.fused_up:
                     # a part of a multi-stream step (`shares_gpu`): 1.5 workgroups per CU -- the other parts' query kernels hold CUs when
                     # this launch starts, and what cannot start at once leaves a shorter tail (+0.9 % on the step, profiles/r06/knob_sweep.txt)
-                    wg = self.up2_shared_wgs if (getattr(self, "shares_gpu", False) and self.B * self.H >= 4 * self.up2_shared_wgs) else 0
+                    wg = self.up2_shared_wgs if (self.shares_gpu and self.B * self.H >= 4 * self.up2_shared_wgs) else 0
                     dynconv_up2(xp, o["kern"], o["kbias"], 0, self.N, self.H, self.W, cv, self.mask_up, logits_out=self.mask,
                                 out_dtype=self.out_code, workgroups=wg)
                     dynconv_up2(dp, o["kern"], o["kbias"], 1, self.N, self.H, self.W, cv, self.depth_up,
@@ -459,24 +462,18 @@ class DecodePlan:
 
 
 # ---- the S-stage plan as a native object (include/polyhead.h ph_decode_*) -----------------------------------
-def native_cfg(B, N, H, W, S, L, F, prec, out_dtype=torch.float32, frame_invariant=False, shares_gpu=False, nsplit=None):
-    """the ph_decode_cfg of the DecodePlan that the same arguments (and the same environment) would build: the switches
-    DecodePlan reads from the environment become the cfg's explicit fields -- the native plan itself never reads it"""
-    mode = mode_of(prec)
-    env = _os.environ.get
-    knob = lambda v: {"0": _lib.PH_KNOB_OFF, "1": _lib.PH_KNOB_WHERE_SUPPORTED}.get(v, _lib.PH_KNOB_AUTO)
-    return _lib.DecodeCfg(B=B, N=N, H=H, W=W, S=S, L=L, F=F, mode=_lib.PH_MODE[mode.name], out_dtype=OUT_CODE[out_dtype],
-                          frame_invariant=int(bool(frame_invariant)),
-                          query_full_split=int(mode.name in ("mixed16", "fp16") and mode.query == _lib.PH_PREC_SPLIT),
-                          shares_gpu=int(bool(shares_gpu)), poolx=knob(env("PH_CONV_POOLX")), fused_up=knob(env("PH_CONV_UP2")),
-                          nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0),
-                          nsplit_px=0 if frame_invariant else int(env("PH_POOLX_NSPLIT") or 0),
-                          up2_wgs=int(env("PH_UP2_SHARED_WGS") or 0))
-
-
-def _cfg_error(what):
-    msg = _lib.load().ph_last_error_string()
-    return _lib.PolyheadError(f"{what}: {msg.decode() if msg else ''}")
+def _gather_params(module, device, count, name_of, numel_of):
+    """the `count` parameters a device packer reads, by the names of its table (`name_of(i)`), as fp32 device tensors of
+    `numel_of(i)` elements -> (the tensors, kept alive by the caller until the launch is queued; the host array of their pointers)"""
+    sd = module.state_dict() if hasattr(module, "state_dict") else module
+    params = []
+    for i in range(count):
+        name = name_of(i).decode()
+        t = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
+        if t.numel() != numel_of(i):
+            raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {numel_of(i)}")
+        params.append(t)
+    return params, (C.c_void_p * count)(*[t.data_ptr() for t in params])
 
 
 def native_pack_stage(module, cfg, device):
@@ -485,15 +482,8 @@ def native_pack_stage(module, cfg, device):
     nbytes = lib.ph_decode_pack_bytes(C.byref(cfg))
     if nbytes == 0:
         raise _cfg_error("ph_decode_pack_bytes")
-    sd = module.state_dict() if hasattr(module, "state_dict") else module
-    params = []
-    for i in range(_lib.PH_DECODE_NPARAMS):
-        name = lib.ph_decode_param_name(i).decode()
-        t = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-        if t.numel() != lib.ph_decode_param_numel(C.byref(cfg), i):
-            raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {lib.ph_decode_param_numel(C.byref(cfg), i)}")
-        params.append(t)
-    ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    params, ptrs = _gather_params(module, device, _lib.PH_DECODE_NPARAMS, lib.ph_decode_param_name,
+                                  lambda i: lib.ph_decode_param_numel(C.byref(cfg), i))
     pack = torch.empty((nbytes,), dtype=torch.uint8, device=device)
     _lib.check(lib.ph_decode_pack_stage(C.byref(cfg), ptrs, _lib.ptr(pack), _lib.stream_ptr()), "ph_decode_pack_stage")
     return pack
@@ -722,56 +712,25 @@ class KernelHeadPack:
         self.prec, self.groups = prec, groups
 
 
-class KernelHeadPlan:
-    """buffers + launch sequence of KernelHead's post-neck part for one (B, H, W)."""
+class _KernelHeadPlanBase:
+    """what the two KernelHead plans share: everything `KernelHead.simple_test_rpn` hands to its caller (the 9-tuple and the plane /
+    bit hand-off to KernelUpdateIterHead), and the three input maps.  A subclass sets B, H, W, HW and N, then calls `_alloc_io`."""
 
-    def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
-                 logit_dtype=torch.float32, onepass=None, frame_invariant=False):
-        """`onepass`: None = ph_khead_onepass whenever the geometry / grade allows it (and PH_KHEAD_TWOPASS is unset),
-        False = always the two-pass ph_khead_fused.  `logit_dtype`: fp32 (the reference API) or fp16 (one-pass form only)
-        for mask_preds / seg_preds / depth_pred."""
-        self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
-        self.n_thing_cls, self.n_cls, self.cat_stuff = num_thing_classes, num_classes, cat_stuff
-        self.Nq = pack.n_init
-        self.n_stuff = (num_classes - num_thing_classes) if cat_stuff else 0
-        self.N = self.Nq + self.n_stuff
-        prec = pack.prec
-        P = 2 if prec == _lib.PH_PREC_SPLIT else 1
-        HWp = hw_padded(self.HW)
-        dev = torch.device(device)
-        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    def _alloc_io(self, P, n_seg, want_f32, logit_dtype, device, dense_depth_proposal=False):
+        B, H, W, N, HWp = self.B, self.H, self.W, self.N, hw_padded(self.HW)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)
         self.f = [None, None, None]        # set_inputs: borrowed from the caller or allocated on first copy
         self._borrowed = set()
         self.in_planes = False
         self.xp, self.dp = e((P, B, 256, HWp), torch.int16), e((P, B, 256, HWp), torch.int16)
         self.x_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
         self.dfe_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
-        import os
-        lib = _lib.load()
-        self.ws1 = None
-        self.onepass = False
-        if onepass is not False and not os.environ.get("PH_KHEAD_TWOPASS") and pack.conv_frag is not None:
-            # the input format is only known at set_inputs: the fp32 form has the stricter condition (HW % 4 == 0)
-            self.onepass = bool(lib.ph_khead_onepass_supported(B, self.HW, pack.groups, prec, _lib.PH_IN_F32_NCHW))
-        if onepass and not self.onepass:
-            raise _lib.PolyheadError("ph_khead_onepass does not support this geometry / grade")
-        if logit_dtype != torch.float32 and not self.onepass:
-            raise _lib.PolyheadError("16-bit KernelHead logits need the one-pass form")
-        self.logit_dtype = logit_dtype
-        if self.onepass:
-            # hand-off state of the persistent launch; zeroed ONCE (its last 256 bytes are the sticky time-out words, which the
-            # calls never clear)
-            self.ws1 = torch.zeros((lib.ph_khead_onepass_workspace_bytes(B, self.HW),), dtype=torch.uint8, device=dev)
-        self.mask_preds = e((B, self.N, H, W), logit_dtype)
-        self.seg_preds = e((B, pack.n_seg, H, W), logit_dtype)
+        self.mask_preds = e((B, N, H, W), logit_dtype)
+        self.seg_preds = e((B, n_seg, H, W), logit_dtype)
         self.depth_pred = e((B, 1, H, W), logit_dtype)
-        self.bits = e((B, n_padded(self.N), HWp // 32), torch.int32)
-        self.nsplit = nsplit or default_nsplit(B, self.HW, frame_invariant)     # (see DecodePlan: the one-frame split at any B)
-        self.partial = e((B, self.nsplit, n_padded(self.Nq), 512), torch.float32)
-        self.proposal = e((B, self.N, 256), torch.float32)
-        # the two-pass kernels' workspace: the path itself, or the in-call fallback of a one-pass launch that gave up
-        self.ws = e((lib.ph_khead_workspace_bytes(B, self.HW, pack.groups),), torch.uint8)
-        self.w_stuff = pack.w_seg_f32[num_thing_classes:num_classes].contiguous() if self.n_stuff else None
+        self.bits = e((B, n_padded(N), HWp // 32), torch.int32)
+        self.proposal = e((B, N, 256), torch.float32)
+        self.depth_proposal = e((B, N, 256), torch.float32) if dense_depth_proposal else None
 
     def renew_outputs(self):
         """fresh tensors for everything `KernelHead.simple_test_rpn` hands to its caller (the 9-tuple and the plane / bit
@@ -780,7 +739,7 @@ class KernelHeadPlan:
         self.xp, self.dp, self.bits = e(self.xp), e(self.dp), e(self.bits)
         self.x_f32, self.dfe_f32 = e(self.x_f32), e(self.dfe_f32)
         self.mask_preds, self.seg_preds, self.depth_pred = e(self.mask_preds), e(self.seg_preds), e(self.depth_pred)
-        self.proposal = e(self.proposal)
+        self.proposal, self.depth_proposal = e(self.proposal), e(self.depth_proposal)
 
     def set_inputs(self, feats):
         """the three post-neck maps: contiguous fp32 device tensors of the plan's shape are used where they are (the
@@ -788,9 +747,8 @@ class KernelHeadPlan:
         else is copied into the plan's own buffers"""
         self.in_planes = feats[0].dtype == torch.int16
         if self.in_planes:          # bf16 planes [P][B][256][HWp] from the neck (SemanticFPNWrapper.forward_planes)
-            P = 2 if self.pack.prec == _lib.PH_PREC_SPLIT else 1
             for i, src in enumerate(feats):
-                if tuple(src.shape) != (P, self.B, 256, hw_padded(self.HW)) or not src.is_contiguous():
+                if tuple(src.shape) != tuple(self.xp.shape) or not src.is_contiguous():
                     raise _lib.PolyheadError("plane inputs must be contiguous int16 [P][B][256][HWp]")
                 self.f[i] = src
             self._borrowed = {t.data_ptr() for t in self.f}
@@ -804,6 +762,49 @@ class KernelHeadPlan:
                     self.f[i] = torch.empty((self.B, 256, self.H, self.W), dtype=torch.float32, device=self.xp.device)
                 self.f[i].copy_(src)
         self._borrowed = {t.data_ptr() for t, src in zip(self.f, feats) if t.data_ptr() == src.data_ptr()}
+
+    def check_status(self):
+        """kept for callers of round 3's API: returns `timeouts()`; nothing to raise any more, results are valid either way"""
+        return self.timeouts()
+
+
+class KernelHeadPlan(_KernelHeadPlanBase):
+    """buffers + launch sequence of KernelHead's post-neck part for one (B, H, W)."""
+
+    def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
+                 logit_dtype=torch.float32, onepass=None, frame_invariant=False):
+        """`onepass`: None = ph_khead_onepass whenever the geometry / grade allows it (and PH_KHEAD_TWOPASS is unset),
+        False = always the two-pass ph_khead_fused.  `logit_dtype`: fp32 (the reference API) or fp16 (one-pass form only)
+        for mask_preds / seg_preds / depth_pred."""
+        self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
+        self.n_thing_cls, self.n_cls, self.cat_stuff = num_thing_classes, num_classes, cat_stuff
+        self.Nq = pack.n_init
+        self.n_stuff = (num_classes - num_thing_classes) if cat_stuff else 0
+        self.N = self.Nq + self.n_stuff
+        prec = pack.prec
+        dev = torch.device(device)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        lib = _lib.load()
+        self.ws1 = None
+        self.onepass = False
+        if onepass is not False and not _os.environ.get("PH_KHEAD_TWOPASS") and pack.conv_frag is not None:
+            # the input format is only known at set_inputs: the fp32 form has the stricter condition (HW % 4 == 0)
+            self.onepass = bool(lib.ph_khead_onepass_supported(B, self.HW, pack.groups, prec, _lib.PH_IN_F32_NCHW))
+        if onepass and not self.onepass:
+            raise _lib.PolyheadError("ph_khead_onepass does not support this geometry / grade")
+        if logit_dtype != torch.float32 and not self.onepass:
+            raise _lib.PolyheadError("16-bit KernelHead logits need the one-pass form")
+        self.logit_dtype = logit_dtype
+        if self.onepass:
+            # hand-off state of the persistent launch; zeroed ONCE (its last 256 bytes are the sticky time-out words, which the
+            # calls never clear)
+            self.ws1 = torch.zeros((lib.ph_khead_onepass_workspace_bytes(B, self.HW),), dtype=torch.uint8, device=dev)
+        self._alloc_io(2 if prec == _lib.PH_PREC_SPLIT else 1, pack.n_seg, want_f32, logit_dtype, dev)
+        self.nsplit = nsplit or default_nsplit(B, self.HW, frame_invariant)     # (see DecodePlan: the one-frame split at any B)
+        self.partial = e((B, self.nsplit, n_padded(self.Nq), 512), torch.float32)
+        # the two-pass kernels' workspace: the path itself, or the in-call fallback of a one-pass launch that gave up
+        self.ws = e((lib.ph_khead_workspace_bytes(B, self.HW, pack.groups),), torch.uint8)
+        self.w_stuff = pack.w_seg_f32[num_thing_classes:num_classes].contiguous() if self.n_stuff else None
 
     def run(self):
         lib, pk, s = _lib.load(), self.pack, _lib.stream_ptr
@@ -873,10 +874,6 @@ class KernelHeadPlan:
         """one-pass form: True if the most recent run gave up and was redone by the two-pass kernels (synchronises)"""
         return bool(self.onepass and _lib.load().ph_khead_onepass_status(_lib.ptr(self.ws1), self.B, _lib.stream_ptr()) != 0)
 
-    def check_status(self):
-        """kept for callers of round 3's API: returns `timeouts()`; nothing to raise any more, results are valid either way"""
-        return self.timeouts()
-
 
 # ---- KernelHead's post-neck part as a native object (include/polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts) ------------
 _KHEAD_MODE_OF_PREC = {_lib.PH_PREC_F16: "fp16", _lib.PH_PREC_BF16: "bf16", _lib.PH_PREC_SPLIT: "fp32"}
@@ -933,23 +930,16 @@ def native_khead_pack(module, cfg, device):
     nbytes = lib.ph_khead_pack_bytes(C.byref(cfg))
     if nbytes == 0:
         raise _cfg_error("ph_khead_pack_bytes")
-    sd = module.state_dict() if hasattr(module, "state_dict") else module
-    params = []
-    for i in range(_lib.PH_KHEAD_NPARAMS):
-        name = lib.ph_khead_param_name(i).decode()
-        t = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-        if t.numel() != lib.ph_khead_param_numel(C.byref(cfg), i):
-            raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {lib.ph_khead_param_numel(C.byref(cfg), i)}")
-        params.append(t)
-    ptrs = (C.c_void_p * len(params))(*[t.data_ptr() for t in params])
+    params, ptrs = _gather_params(module, device, _lib.PH_KHEAD_NPARAMS, lib.ph_khead_param_name,
+                                  lambda i: lib.ph_khead_param_numel(C.byref(cfg), i))
     blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
         _lib.check(lib.ph_khead_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_khead_pack")
     return NativeKernelHeadPack(blob, cfg)
 
 
-class NativeKernelHeadPlan:
-    """KernelHeadPlan's surface (set_inputs, run, renew_outputs, timeouts, last_run_fell_back and the output attributes) over ONE
+class NativeKernelHeadPlan(_KernelHeadPlanBase):
+    """KernelHeadPlan's surface (_KernelHeadPlanBase, run, timeouts, last_run_fell_back and the output attributes) over ONE
     native call per a1 (ph_khead_plan_run): the same launch sequence and geometry as the KernelHeadPlan of the same arguments, so
     the same bits.  `pack`: a NativeKernelHeadPack.  `dense_depth_proposal`: also write depth_proposal [B, N, 256] (what a C caller
     hands to ph_decode_io.q0; the module API keeps the reference's stride-0 view of the weight and needs no launch for it)."""
@@ -982,56 +972,14 @@ class NativeKernelHeadPlan:
         self.onepass, self.nsplit, self.N, self.n_stuff = bool(geo.onepass), geo.nsplit, geo.N, geo.n_stuff
         self.Nq = pack.n_init
         self.dense_depth_proposal = dense_depth_proposal
-        self.f = [None, None, None]
-        self._borrowed = set()
-        self.in_planes = False
         self.io = _lib.KheadIO()
-        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        P, HWp = geo.P, geo.HWp
-        self.xp, self.dp = e((P, B, 256, HWp), torch.int16), e((P, B, 256, HWp), torch.int16)
-        self.x_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
-        self.dfe_f32 = e((B, 256, H, W), torch.float32) if want_f32 else None
-        self.mask_preds = e((B, self.N, H, W), logit_dtype)
-        self.seg_preds = e((B, pack.n_seg, H, W), logit_dtype)
-        self.depth_pred = e((B, 1, H, W), logit_dtype)
-        self.bits = e((B, geo.Npad, HWp // 32), torch.int32)
-        self.proposal = e((B, self.N, 256), torch.float32)
-        self.depth_proposal = e((B, self.N, 256), torch.float32) if dense_depth_proposal else None
+        self._alloc_io(geo.P, pack.n_seg, want_f32, logit_dtype, dev, dense_depth_proposal)
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and _lib._lib is not None:
             _lib._lib.ph_khead_plan_destroy(h)
             self._h = None
-
-    def renew_outputs(self):
-        """fresh tensors for everything handed to the caller (KernelHeadPlan.renew_outputs)"""
-        e = lambda t: None if t is None else torch.empty_like(t)
-        self.xp, self.dp, self.bits = e(self.xp), e(self.dp), e(self.bits)
-        self.x_f32, self.dfe_f32 = e(self.x_f32), e(self.dfe_f32)
-        self.mask_preds, self.seg_preds, self.depth_pred = e(self.mask_preds), e(self.seg_preds), e(self.depth_pred)
-        self.proposal, self.depth_proposal = e(self.proposal), e(self.depth_proposal)
-
-    def set_inputs(self, feats):
-        """as KernelHeadPlan.set_inputs: contiguous fp32 device maps of the plan's shape and plane inputs are read where they
-        are, anything else is copied into the plan's own buffers"""
-        self.in_planes = feats[0].dtype == torch.int16
-        if self.in_planes:
-            for i, src in enumerate(feats):
-                if tuple(src.shape) != (self.geometry.P, self.B, 256, self.geometry.HWp) or not src.is_contiguous():
-                    raise _lib.PolyheadError("plane inputs must be contiguous int16 [P][B][256][HWp]")
-                self.f[i] = src
-            self._borrowed = {t.data_ptr() for t in self.f}
-            return
-        for i, src in enumerate(feats):
-            if (src.dtype == torch.float32 and src.is_contiguous() and src.device == self.xp.device
-                    and tuple(src.shape) == (self.B, 256, self.H, self.W)):
-                self.f[i] = src.detach()
-            else:
-                if self.f[i] is None or self.f[i].data_ptr() in self._borrowed:
-                    self.f[i] = torch.empty((self.B, 256, self.H, self.W), dtype=torch.float32, device=self.xp.device)
-                self.f[i].copy_(src)
-        self._borrowed = {t.data_ptr() for t, src in zip(self.f, feats) if t.data_ptr() == src.data_ptr()}
 
     def run(self):
         """one a1 call on the current stream: ONE native call"""
@@ -1050,9 +998,6 @@ class NativeKernelHeadPlan:
     def last_run_fell_back(self):
         """True if the most recent run gave up its one-pass launch and was redone by the two-pass kernels (synchronises)"""
         return bool(_lib.load().ph_khead_plan_status(self._h, _lib.stream_ptr()) != 0)
-
-    def check_status(self):
-        return self.timeouts()
 
 
 # ---- SemanticFPNWrapper (N3) -------------------------------------------------------------------------------
@@ -1286,9 +1231,7 @@ class DualDecodePlan:
         self.B, self.parts = B, parts
         base, rem = divmod(B, parts)
         self.sizes = [base + (1 if i < rem else 0) for i in range(parts)]
-        self.halves = [DecodePlan(packs, n, N, H, W, prec, out_dtype, device) for n in self.sizes]
-        for p in self.halves:
-            p.shares_gpu = True          # query launches with the most rows per workgroup: the other parts' kernels run beside them
+        self.halves = [DecodePlan(packs, n, N, H, W, prec, out_dtype, device, shares_gpu=True) for n in self.sizes]
         self.graph = None
 
     def set_inputs(self, x, dfe, k0, q0, m0):

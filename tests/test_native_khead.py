@@ -20,7 +20,7 @@ from test_native_plan import _elf_needed
 
 NEW_SYMBOLS = ["ph_khead_param_name", "ph_khead_param_numel", "ph_khead_pack_bytes", "ph_khead_pack_layout", "ph_khead_pack",
                "ph_khead_plan_workspace_bytes", "ph_khead_plan_create", "ph_khead_plan_info", "ph_khead_plan_destroy",
-               "ph_khead_plan_run", "ph_khead_plan_status", "ph_khead_plan_timeouts"]
+               "ph_khead_plan_run", "ph_khead_plan_status", "ph_khead_plan_timeouts", "ph_pool_default_nsplit"]
 FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and never dereferences
 STRUCTS = {"ph_khead_cfg": _lib.KheadCfg, "ph_khead_io": _lib.KheadIO, "ph_khead_geometry": _lib.KheadGeometry,
            "ph_khead_layout": _lib.KheadLayout}

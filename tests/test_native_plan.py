@@ -1,7 +1,11 @@
 """Host-side checks of the native decode plan (include/polyhead.h ph_decode_*): the exported symbols, the struct layouts the
-ctypes side assumes, the workspace / geometry rules against engine.DecodePlan's, the pack layout against pack.py's, argument
-validation, and the Python-free example program's dependencies.  No GPU: nothing here launches a kernel."""
+ctypes side assumes, the workspace rule against engine.DecodePlan's buffers, the launch geometry rule (one copy, in the library:
+ph_decode_geometry_of, which engine.DecodePlan asks too) against the choices recorded in tests/golden/plan_geometry.json, the
+pack layout against pack.py's, argument validation, and the Python-free example program's dependencies.  No GPU: nothing here
+launches a kernel."""
 import ctypes as C
+import functools
+import json
 import os
 import shutil
 import subprocess
@@ -16,7 +20,8 @@ from polyphonicformer_amd import build as BLD
 from polyphonicformer_amd.pack import pack_stage
 
 NEW_SYMBOLS = ["ph_decode_param_name", "ph_decode_param_numel", "ph_decode_pack_bytes", "ph_decode_pack_layout", "ph_decode_pack_stage",
-               "ph_decode_workspace_bytes", "ph_decode_create", "ph_decode_info", "ph_decode_destroy", "ph_decode_run"]
+               "ph_decode_workspace_bytes", "ph_decode_create", "ph_decode_info", "ph_decode_geometry_of", "ph_decode_destroy",
+               "ph_decode_run", "ph_pool_default_nsplit"]
 
 # (B, N, H, W, S, L): cfg1 (256x512 -> 32x64, N = 100, 1 stage), cfg2 / cfg3 (128x256, N = 153 / 111), cfg5 (48x156, N = 253)
 SHAPES = {"cfg1": (100, 32, 64, 1, 19), "cfg2": (153, 128, 256, 3, 133), "cfg3": (111, 128, 256, 3, 19), "cfg5": (253, 48, 156, 3, 133)}
@@ -126,6 +131,103 @@ def _create(cfg, S):
     return rc, h
 
 
+# ---- the recorded choices of the launch geometry rule.  tests/golden/plan_geometry.json holds what engine.DecodePlan's own
+# arithmetic chose at the commit named in the file, before that arithmetic was deleted in favour of the library's: the matrix of
+# test_workspace_and_geometry_match_decode_plan, the environment cases, an explicit nsplit, and both sides of every threshold
+ENV_KEYS = ("PH_POOL_NSPLIT", "PH_CONV_UP2", "PH_CONV_POOLX", "PH_POOLX_NSPLIT", "PH_UP2_SHARED_WGS", "PH_QUERY_FULL_SPLIT")
+GEO_FIELDS = [n for n, _ in _lib.DecodeGeometry._fields_]
+
+
+@functools.lru_cache(maxsize=None)
+def _table():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_geometry.json")) as f:
+        return json.load(f)
+
+
+def _row_env(row, monkeypatch):
+    for k in ENV_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in row["env"].items():
+        monkeypatch.setenv(k, v)
+
+
+def _row_args(row):
+    return (row["B"], row["N"], row["H"], row["W"], row["S"], row["L"], E.MODES[row["mode"]], getattr(torch, row["out_dtype"]),
+            row["frame_invariant"], row["nsplit_arg"])
+
+
+def _geometry_of(cfg):
+    g = _lib.DecodeGeometry()
+    rc = _lib_loaded().ph_decode_geometry_of(C.byref(cfg), C.byref(g))
+    assert rc == 0, _lib_loaded().ph_last_error_string()
+    return g
+
+
+def test_recorded_table_pins_both_branches():
+    rows = _table()["decode_geometry"]
+    assert len(rows) >= 216 and len(_table()["producing_commit"]) == 40
+    for i in (2, 3):            # poolx, fused_up
+        assert {r["expect"][i] for r in rows} == {False, True}
+    assert {r["case"].split(":")[0] for r in rows} >= {"matrix", "env", "nsplit_arg", "thr"}
+
+
+def test_geometry_of_equals_the_recorded_table(monkeypatch):
+    """the library's rule (resolve() of ph_decode.hip through ph_decode_geometry_of: no plan, no device, no packs) chooses what the
+    Python rule chose, row by row; and ph_decode_info on a plan created from the same cfg is the same fill, field by field"""
+    lib = _lib_loaded()
+    for row in _table()["decode_geometry"]:
+        _row_env(row, monkeypatch)
+        B, N, H, W, S, L, m, out_dtype, fi, nsplit = _row_args(row)
+        for shares in (False, True):
+            cfg = E.native_cfg(B, N, H, W, S, L, 2048, m, out_dtype, fi, shares, nsplit)
+            g = _geometry_of(cfg)
+            assert [g.nsplit, g.nsplit_px, bool(g.poolx), bool(g.fused_up)] == row["expect"], (row, shares)
+            assert g.up2_workgroups == 0, row           # cfg.up2_wgs == 0: only ph_decode_create asks the device
+            cfg.up2_wgs = 384                           # 1.5 per CU of a 256-CU device
+            g = _geometry_of(cfg)
+            assert g.up2_workgroups == (384 if (row["expect"][3] and shares and B * H >= 4 * 384) else 0), (row, shares)
+            rc, h = _create(cfg, S)
+            assert rc == 0, (row, lib.ph_last_error_string())
+            gi = _lib.DecodeGeometry()
+            assert lib.ph_decode_info(h, C.byref(gi)) == 0
+            lib.ph_decode_destroy(h)
+            assert [getattr(gi, f) for f in GEO_FIELDS] == [getattr(g, f) for f in GEO_FIELDS], (row, shares)
+
+
+def test_decode_plan_attributes_equal_the_recorded_table(monkeypatch):
+    """engine.DecodePlan (which now asks the library) still chooses what its own arithmetic chose"""
+    for row in _table()["decode_geometry"]:
+        _row_env(row, monkeypatch)
+        B, N, H, W, S, L, m, out_dtype, fi, nsplit = _row_args(row)
+        p = E.DecodePlan([_FakePack(m.query, L) for _ in range(S)], B, N, H, W, m, out_dtype, device="meta", nsplit=nsplit,
+                         frame_invariant=fi)
+        assert [p.nsplit, p.nsplit_px, p.poolx, p.fused_up] == row["expect"], row
+        assert p.poolx == hasattr(p, "partial_px"), row
+
+
+def test_default_nsplit_equals_the_recorded_table(monkeypatch):
+    monkeypatch.delenv("PH_POOL_NSPLIT", raising=False)
+    lib = _lib_loaded()
+    rows = _table()["default_nsplit"]
+    assert len(rows) == 8 * 4 * 2
+    for r in rows:
+        assert lib.ph_pool_default_nsplit(r["B"], r["HW"], int(r["frame_invariant"])) == r["expect"], r
+        assert E.default_nsplit(r["B"], r["HW"], r["frame_invariant"]) == r["expect"], r
+    monkeypatch.setenv("PH_POOL_NSPLIT", "7")           # the override stays the Python side's
+    assert E.default_nsplit(1, 32768) == 7 and lib.ph_pool_default_nsplit(1, 32768, 0) == 32
+
+
+def test_decode_plan_refuses_what_the_library_refuses():
+    """a geometry the kernels cannot run is an error at construction (it used to surface at the first launch)"""
+    m = E.MODES["fp16"]
+    with pytest.raises(_lib.PolyheadError, match="at most 256 queries"):
+        E.DecodePlan([_FakePack(m.query, 19)], 1, 300, 16, 32, m, torch.float16, device="meta")
+    g = _lib.DecodeGeometry()
+    assert _lib_loaded().ph_decode_geometry_of(None, C.byref(g)) == -1
+    cfg = E.native_cfg(1, 111, 16, 32, 1, 19, 2048, m, torch.float16)
+    assert _lib_loaded().ph_decode_geometry_of(C.byref(cfg), None) == -1 and "null out" in _lib_loaded().ph_last_error_string().decode()
+
+
 @pytest.mark.parametrize("shape", sorted(SHAPES))
 @pytest.mark.parametrize("B", [1, 8, 32])
 def test_workspace_and_geometry_match_decode_plan(shape, B, monkeypatch):
@@ -133,6 +235,8 @@ def test_workspace_and_geometry_match_decode_plan(shape, B, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     lib = _lib_loaded()
     N, H, W, S, L = SHAPES[shape]
+    recorded = {(r["B"], r["mode"], r["out_dtype"], r["frame_invariant"]): tuple(r["expect"])
+                for r in _table()["decode_geometry"] if r["case"] == "matrix:" + shape}
     for mode in MODES:
         m = E.MODES[mode]
         for out_dtype in ((torch.float32, m.feat_dtype) if m.feat_dtype is not None else (torch.float32,)):
@@ -148,8 +252,11 @@ def test_workspace_and_geometry_match_decode_plan(shape, B, monkeypatch):
                     g = _lib.DecodeGeometry()
                     assert lib.ph_decode_info(h, C.byref(g)) == 0
                     lib.ph_decode_destroy(h)
-                    assert (g.nsplit, g.nsplit_px, bool(g.poolx), bool(g.fused_up)) == (p.nsplit, p.nsplit_px, p.poolx, p.fused_up), what
-                    wg = 384 if (p.fused_up and shares and B * H >= 4 * 384) else 0
+                    # the geometry against the recorded choices (the Python plan takes its own from the same library call now)
+                    want = recorded[(B, mode, str(out_dtype).split(".")[1], fi)]
+                    assert (g.nsplit, g.nsplit_px, bool(g.poolx), bool(g.fused_up)) == want == \
+                        (p.nsplit, p.nsplit_px, p.poolx, p.fused_up), what
+                    wg = 384 if (want[3] and shares and B * H >= 4 * 384) else 0
                     assert g.up2_workgroups == wg, what
                     assert (g.feat_prec, g.query_prec, g.conv_prec, g.kern_format, g.feat_planes) == \
                         (m.feat, m.query, m.conv, m.kern_fmt, m.FP), what
