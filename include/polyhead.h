@@ -926,6 +926,131 @@ int ph_khead_plan_run(ph_khead_plan* plan, const ph_khead_io* io, void* stream);
 int ph_khead_plan_status(const ph_khead_plan* plan, void* stream);
 int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
 
+/* ---- N3 as a native object (csrc/ph_neckplan.hip): what SemanticFPNWrapper._pack + sine_positional_encoding + engine.NeckPlan
+ * do from Python -- semantic_fpn.py:198-235 for a C / C++ caller: from the four FPN levels to the neck's maps, as fp32 NCHW and / or
+ * as the 16-bit planes that ph_khead_io takes (PH_IN_PLANES: f0 / f1 / f2 = out_planes[0 .. 2]).  Conventions are ph_decode_*'s and
+ * ph_khead_*'s: status codes + ph_last_error_string, caller-owned 256-byte aligned memory, no allocation of device memory, no
+ * synchronisation and no host read of device data in pack / posenc / create / run, every argument or geometry error returned
+ * before the first launch.  No ph_neck_plan_* / ph_neck_pack* / ph_neck_posenc function reads the environment: the plan's
+ * launches go through internal forms of ph_conv_nhwc / ph_gn_sum_planes / ph_gn_apply / ph_neck_out_convs that take their launch
+ * knobs as arguments (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW /
+ * PH_CPLANES_TPW / PH_NECK_STATS3 / PH_NECK_APPLY3), and what engine.NeckPlan reads from PH_NECK_OUT2 / PH_NECK_C16 /
+ * PH_NECK_STREAMS are the cfg's `fused_out` / `c16` / `tower_buffers` fields (PH_NECK_OUT2=0 -> fused_out PH_KNOB_OFF,
+ * PH_NECK_C16=0 -> c16 PH_KNOB_OFF, PH_NECK_STREAMS=0 -> tower_buffers 0; the measurement forms PH_NECK_OUT2=2 / 3 have no field).
+ * A zero-initialised ph_neck_cfg plus the sizes, the mode, num_outs, pos_level and an emit flag is the module API's configuration.
+ *   h, w         the four FPN level sizes, level 0 (stride 4) first: each level (n + 1) / 2 of the one before, and levels 2 and 3
+ *                exactly 1/2 and 1/4 of level 1 (they reach it by x2 upsampling); otherwise PH_EUNSUPPORTED
+ *   groups       GroupNorm groups, divides 256
+ *   mode         PH_MODE_*, mapped to the grade as ph_khead_cfg.mode / engine.KHEAD_PREC: PH_MODE_FP16 -> PH_PREC_F16, PH_MODE_BF16 ->
+ *                PH_PREC_BF16, every other mode -> PH_PREC_SPLIT (hi + lo bf16 planes)
+ *   num_outs     1 .. 3: conv_pred + 0 .. 2 aux convs
+ *   pos_level    the level the positional encoding is added to (the module's cat_coors_level), 0 .. 3; -1: none
+ *   emit_planes  1: ph_neck_io.out_planes are written;  emit_f32  1: ph_neck_io.out_f32 are written; at least one
+ *   fused_out    PH_KNOB_AUTO: conv_pred + the aux convs as ONE ph_neck_out_convs when num_outs == 3, groups == 32 and the grade has
+ *                one plane (engine.NeckPlan's rule with no environment variable set); PH_KNOB_ON: the same, PH_EUNSUPPORTED where
+ *                that says no; PH_KNOB_OFF: conv -> finalize -> apply per map (PH_NECK_OUT2=0 of the Python plan)
+ *   c16          PH_KNOB_AUTO: chunk-major planes (PH_PLANES_C16) into level 0's stride-2 conv in one-plane grades;
+ *                PH_KNOB_OFF: channels-last (PH_NECK_C16=0)
+ *   tower_buffers  1: every level owns its ping / pong planes, conv output, statistics and partial sums (engine.NeckPlan's `multi`
+ *                layout), so the four ph_neck_plan_run_level calls may run concurrently; 0: one shared set, a smaller workspace
+ *   eps          GroupNorm epsilon; 0 = 1e-5 */
+typedef struct {
+    int32_t B;
+    int32_t h[4], w[4];
+    int32_t groups;
+    int32_t mode;               /* PH_MODE_* */
+    int32_t num_outs;
+    int32_t pos_level;
+    int32_t emit_planes, emit_f32;
+    int32_t fused_out;          /* PH_KNOB_AUTO / _ON / _OFF */
+    int32_t c16;                /* PH_KNOB_AUTO / _OFF */
+    int32_t tower_buffers;
+    float eps;
+} ph_neck_cfg;
+
+/* ---- the parameter table: (conv.weight [256][256][k][k], gn.weight [256], gn.bias [256]) of the ten convs, fp32 device tensors
+ * under the reference's state_dict names, in this order:
+ *    0 .. 2   convs_all_levels.0.conv0 (3x3, stride 2)      3 .. 5   convs_all_levels.1.conv0
+ *    6 .. 11  convs_all_levels.2.conv0, .conv1              12 .. 20 convs_all_levels.3.conv0, .conv1, .conv2      (3x3)
+ *   21 .. 23  conv_pred     24 .. 26  aux_convs.0     27 .. 29  aux_convs.1                                        (1x1)
+ * the entries of aux convs beyond num_outs - 1 are ignored and may be NULL */
+#define PH_NECK_NPARAMS 30
+const char* ph_neck_param_name(int index);                         /* NULL out of range */
+int64_t ph_neck_param_numel(const ph_neck_cfg* cfg, int index);    /* elements; < 0 out of range */
+
+/* ---- packing (k_neck_pack: one launch, once per weight load).  The pieces are SemanticFPNWrapper._pack's tensors, byte for byte
+ * (fp32 -> bf16 / fp16 round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned offset of one device
+ * buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT), conv c = parameter 3 c:
+ *   WP(c)        uint16 [P][256 * K]   pack.pack_b32 fragments of W[n][tap * 256 + c'] -- the (kh, kw, in) K order, K = 2304 (3x3)
+ *                or 256 (1x1): ph_conv_nhwc's Wp
+ *   GAMMA(c), BETA(c)   float [256]
+ *   OUTS_W       uint16 [P][3][256][256] (out, in) of conv_pred + the two aux convs, OUTS_GN float [3][2][256] (gamma, beta):
+ *                ph_neck_out_convs' operands; only with num_outs == 3 (0 bytes otherwise, as are the pieces of an absent aux conv) */
+#define PH_NPACK_WP(c) (3 * (c))
+#define PH_NPACK_GAMMA(c) (3 * (c) + 1)
+#define PH_NPACK_BETA(c) (3 * (c) + 2)
+enum { PH_NPACK_OUTS_W = 30, PH_NPACK_OUTS_GN = 31, PH_NPACK_COUNT = 32 };
+typedef struct {
+    uint64_t offset[PH_NPACK_COUNT];   /* bytes from the start of the pack, multiples of 256 */
+    uint64_t bytes[PH_NPACK_COUNT];    /* size of the piece; the next piece starts at offset + bytes rounded up to 256 */
+} ph_neck_layout;
+size_t ph_neck_pack_bytes(const ph_neck_cfg* cfg);                 /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_neck_pack_layout(const ph_neck_cfg* cfg, ph_neck_layout* layout);
+/* `params`: host array of PH_NECK_NPARAMS device pointers; `pack`: 256-byte aligned device buffer of ph_neck_pack_bytes */
+int ph_neck_pack(const ph_neck_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- the positional encoding (k_neck_posenc: one launch, once per map size): mmdet's SinePositionalEncoding(normalize=True) for an
+ * empty ignore mask (semantic_fpn.py:202-208), out float [2 * num_feats][H][W] -- the y block first, then x; sin on even and cos on
+ * odd indices of  embed / temperature^(2 (i / 2) / num_feats),  embed = (row or column + 1) / (H or W + eps) * scale.  Evaluated
+ * in fp64 and rounded once to fp32 (the reference evaluates in fp32: the two differ in the last bits; a caller that wants the
+ * Python path's bits hands ph_neck_io.posenc the host-computed table instead).  The shipped model: num_feats 128,
+ * temperature 10000, scale 2 pi, eps 1e-6. */
+int ph_neck_posenc(int H, int W, int num_feats, double temperature, double scale, double eps, float* out, void* stream);
+
+/* ---- plan lifetime.  The workspace holds the towers' ping / pong planes, conv outputs, GroupNorm statistics and partial sums, the
+ * level sum and the output stage's buffers.  ZEROING CONTRACT: none -- every word a launch reads was written by an earlier launch
+ * of the same run.  ph_neck_plan_create touches no device memory.  The caller keeps pack and workspace alive as long as the plan;
+ * both 256-byte aligned. */
+typedef struct ph_neck_plan ph_neck_plan;
+typedef struct {
+    int32_t Ho, Wo;             /* the output (stride-8) size = level 1's */
+    int32_t HWp;                /* Ho * Wo rounded up to 128 */
+    int32_t P;                  /* planes of out_planes */
+    int32_t prec;               /* the grade, PH_PREC_* */
+    int32_t fused_out;          /* 1: ph_neck_out_convs; 0: conv -> finalize -> apply per map */
+    int32_t c16;                /* 1: chunk-major planes into level 0's stride-2 conv */
+    int32_t tower_buffers;
+    int32_t nconvs;             /* 7 + num_outs */
+    int32_t tile_rows[10];      /* per conv (parameter-table order): output rows per tile its ph_conv_nhwc launch takes at this B (2 or
+                                   4; for the output convs of a fused_out plan: what the per-map form would take); 0 beyond nconvs */
+} ph_neck_geometry;
+size_t ph_neck_plan_workspace_bytes(const ph_neck_cfg* cfg);       /* 0 on a bad cfg */
+int ph_neck_plan_create(const ph_neck_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_neck_plan** out);
+int ph_neck_plan_info(const ph_neck_plan* plan, ph_neck_geometry* out);
+void ph_neck_plan_destroy(ph_neck_plan* plan);
+
+/* ---- one neck call.
+ *   feats[l]       float [B][256][h_l][w_l], fp32 NCHW, the four FPN levels
+ *   posenc         float [256][h][w] of level pos_level (ph_neck_posenc, or the caller's own table); NULL exactly when pos_level < 0
+ *   out_planes[i]  uint16 [P][B][256][HWp] of the grade's format: ph_khead_io's PH_IN_PLANES input, zero in [Ho*Wo, HWp) whatever
+ *                  the buffer held before (cfg.emit_planes)
+ *   out_f32[i]     float [B][256][Ho][Wo] (cfg.emit_f32);   entries >= num_outs are ignored; outputs 16-byte aligned
+ * ph_neck_plan_run: the whole neck on one stream, in engine.NeckPlan.run's launch sequence -- per level ph_nhwc_ingest, then
+ * (ph_conv_nhwc, ph_gn_finalize, ph_gn_apply x2 upsample)* and the last conv + finalize; then ph_gn_sum_planes and ph_neck_out_convs
+ * (fused_out) or ph_conv_nhwc, ph_gn_finalize, ph_gn_apply per map.  It is ph_neck_plan_run_level for levels 0 .. 3 and
+ * ph_neck_plan_run_outputs in one call.  With tower_buffers == 1 the four level calls may run on four streams concurrently; the
+ * caller orders them before ph_neck_plan_run_outputs with events.  With tower_buffers == 0 they share buffers and are valid back to
+ * back on one stream only.  All three are capturable into a hipGraph. */
+typedef struct {
+    const float* feats[4];
+    const float* posenc;
+    uint16_t* out_planes[3];
+    float* out_f32[3];
+} ph_neck_io;
+int ph_neck_plan_run(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
+int ph_neck_plan_run_level(ph_neck_plan* plan, int level, const ph_neck_io* io, void* stream);
+int ph_neck_plan_run_outputs(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -81,6 +81,31 @@ class KheadIO(C.Structure):
                                    "proposal", "depth_proposal")]
 
 
+# the native neck plan (polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs)
+PH_NECK_NPARAMS = 30
+PH_NECK_NCONVS = 10
+PH_NPACK_OUTS_W, PH_NPACK_OUTS_GN, PH_NPACK_COUNT = 30, 31, 32      # pieces 3 c, 3 c + 1, 3 c + 2: wp, gamma, beta of conv c
+
+
+class NeckCfg(C.Structure):
+    _fields_ = [("B", C.c_int32), ("h", C.c_int32 * 4), ("w", C.c_int32 * 4)] + \
+        [(n, C.c_int32) for n in ("groups", "mode", "num_outs", "pos_level", "emit_planes", "emit_f32", "fused_out", "c16",
+                                  "tower_buffers")] + [("eps", C.c_float)]
+
+
+class NeckLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * PH_NPACK_COUNT), ("bytes", C.c_uint64 * PH_NPACK_COUNT)]
+
+
+class NeckGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("Ho", "Wo", "HWp", "P", "prec", "fused_out", "c16", "tower_buffers", "nconvs")] + \
+        [("tile_rows", C.c_int32 * PH_NECK_NCONVS)]
+
+
+class NeckIO(C.Structure):
+    _fields_ = [("feats", C.c_void_p * 4), ("posenc", C.c_void_p), ("out_planes", C.c_void_p * 3), ("out_f32", C.c_void_p * 3)]
+
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
@@ -228,6 +253,19 @@ SIGNATURES = {
     "ph_khead_plan_run": (C.c_int, [_P, C.POINTER(KheadIO), _P]),
     "ph_khead_plan_status": (C.c_int, [_P, _P]),
     "ph_khead_plan_timeouts": (C.c_int, [_P, _P]),
+    "ph_neck_param_name": (C.c_char_p, [_I]),
+    "ph_neck_param_numel": (C.c_int64, [C.POINTER(NeckCfg), _I]),
+    "ph_neck_pack_bytes": (C.c_size_t, [C.POINTER(NeckCfg)]),
+    "ph_neck_pack_layout": (C.c_int, [C.POINTER(NeckCfg), C.POINTER(NeckLayout)]),
+    "ph_neck_pack": (C.c_int, [C.POINTER(NeckCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_neck_posenc": (C.c_int, [_I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "ph_neck_plan_workspace_bytes": (C.c_size_t, [C.POINTER(NeckCfg)]),
+    "ph_neck_plan_create": (C.c_int, [C.POINTER(NeckCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_neck_plan_info": (C.c_int, [_P, C.POINTER(NeckGeometry)]),
+    "ph_neck_plan_destroy": (None, [_P]),
+    "ph_neck_plan_run": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
+    "ph_neck_plan_run_level": (C.c_int, [_P, _I, C.POINTER(NeckIO), _P]),
+    "ph_neck_plan_run_outputs": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

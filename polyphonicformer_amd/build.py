@@ -17,6 +17,9 @@ EXAMPLE = os.path.join(HERE, "decode_main")
 # the whole head from C (examples/head_c): neck maps -> KernelHead plan -> decode plan -> panoptic merge
 HEAD_EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "head_c", "head_main.cpp")
 HEAD_EXAMPLE = os.path.join(HERE, "head_main")
+# the neck in front of it (examples/neck_c): FPN levels -> neck plan -> KernelHead plan -> decode plan -> panoptic merge
+NECK_EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "neck_c", "neck_main.cpp")
+NECK_EXAMPLE = os.path.join(HERE, "neck_main")
 OBJ = os.path.join(CSRC, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
@@ -43,10 +46,10 @@ def sources():
 def build_library(force=False, verbose=False):
     srcs = sources()
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-        [os.path.join(os.path.dirname(HERE), "include", "polyhead.h"), EXAMPLE_SRC, HEAD_EXAMPLE_SRC]
+        [os.path.join(os.path.dirname(HERE), "include", "polyhead.h"), EXAMPLE_SRC, HEAD_EXAMPLE_SRC, NECK_EXAMPLE_SRC]
     stamp = os.path.join(OBJ, "stamp")
     dig = _digest(deps)
-    if not force and os.path.exists(LIB) and os.path.exists(EXAMPLE) and os.path.exists(HEAD_EXAMPLE) and os.path.exists(stamp) and open(stamp).read() == dig:
+    if not force and os.path.exists(LIB) and os.path.exists(EXAMPLE) and os.path.exists(HEAD_EXAMPLE) and os.path.exists(NECK_EXAMPLE) and os.path.exists(stamp) and open(stamp).read() == dig:
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
@@ -76,6 +79,10 @@ def build_library(force=False, verbose=False):
                        capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"building {HEAD_EXAMPLE_SRC} failed:\n{r.stderr[-4000:]}")
+    r = subprocess.run([hipcc, "-O2", "-std=c++17", NECK_EXAMPLE_SRC, "-o", NECK_EXAMPLE, "-L" + HERE, "-lpolyhead", "-Wl,-rpath,$ORIGIN"],
+                       capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"building {NECK_EXAMPLE_SRC} failed:\n{r.stderr[-4000:]}")
     with open(stamp, "w") as f:
         f.write(dig)
     return LIB

@@ -23,6 +23,15 @@ void ph_set_error(const char* fmt, ...);
         }                                                              \
     } while (0)
 
+// the same under the public entry point's name, for its internal *_k form
+#define PH_CHECK_ARG_AS(fn, cond, msg)                                 \
+    do {                                                               \
+        if (!(cond)) {                                                 \
+            ph_set_error("%s: %s", fn, msg);                           \
+            return PH_EINVAL;                                          \
+        }                                                              \
+    } while (0)
+
 #define PH_CHECK_LAUNCH()                                                          \
     do {                                                                           \
         hipError_t e_ = hipGetLastError();                                         \
@@ -94,6 +103,30 @@ int ph_khead_fused_if_k(const PhKheadKnobs& kn, const void* f0, const void* f1, 
                         uint16_t* x_planes, uint16_t* dfe_planes, float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds,
                         void* depth_pred, int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
                         int64_t HW, int prec, int input_format, void* stream);
+
+// launch knobs of the neck's kernels (ph_neck.hip), in the same way: the public ph_conv_nhwc / ph_gn_sum_planes / ph_gn_sum_cplanes /
+// ph_gn_apply fill them from PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW / PH_CPLANES_TPW; the native neck plan
+// (ph_neckplan.hip) passes the defaults.  0 = the built-in rule
+struct PhNeckKnobs {
+    int conv_th = 0;             // PH_CONV_TH / PH_CONV_TH_NOW: forced output rows per conv tile (2 or 4; one-plane grades)
+    int gnsum_wgs = 0;           // PH_GNSUM_WGS: workgroups per frame of ph_gn_sum_planes
+    int gnsum_tpw = 0;           // PH_GNSUM_TPW: 64-pixel tiles per workgroup of ph_gn_sum_cplanes
+    int cplanes_tpw = 0;         // PH_CPLANES_TPW: the same of ph_gn_apply's PH_GN_TO_CPLANES mode
+};
+// rows per tile of a ph_conv_nhwc launch of this output size, grade and batch (2 or 4)
+int ph_conv_nhwc_tile_rows_k(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B);
+int ph_conv_nhwc_k(const PhNeckKnobs& kn, const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, float* Y, float* partial,
+                   int ksize, int stride, int B, int H, int W, int prec, void* stream);
+int ph_gn_sum_planes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
+                       const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
+int ph_gn_sum_cplanes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
+                        const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
+int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
+                  int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream);
+int ph_neck_out_convs_k(const PhKheadKnobs& kn, const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes,
+                        const float* gn_affine, int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1,
+                        uint16_t* out_planes2, float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace,
+                        size_t workspace_bytes, int B, int64_t HW, int prec, void* stream);
 
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects

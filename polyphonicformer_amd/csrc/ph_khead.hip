@@ -844,17 +844,26 @@ extern "C" int ph_khead_conv_gn(const float* f0, const float* f1, const float* f
 // 1x1 conv + GroupNorm + ReLU of the SAME level sum) with the two passes above: statistics from a recompute pass, then
 // normalise + ReLU + store.  Against k_conv_nhwc + k_gn_finalize + k_gn_apply per map (fp32 NHWC conv output written, read
 // back, converted) each map moves 16.8 MB of input per pass and its output instead of 16.8 + 33.5 + 33.5 + output MB per frame.
-extern "C" int ph_neck_out_convs(const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes, const float* gn_affine,
-                                 int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1, uint16_t* out_planes2,
-                                 float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace, size_t workspace_bytes,
-                                 int B, int64_t HW, int prec, void* stream) {
-    PH_CHECK_ARG(in_planes && wplanes && gn_affine && workspace, "null pointer");
-    PH_CHECK_ARG((out_planes0 || out_f32_0) && (out_planes1 || out_f32_1) && (out_planes2 || out_f32_2), "every map needs an output");
+int ph_neck_out_convs_k(const PhKheadKnobs& kn, const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes,
+                        const float* gn_affine, int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1,
+                        uint16_t* out_planes2, float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace,
+                        size_t workspace_bytes, int B, int64_t HW, int prec, void* stream) {
+    PH_CHECK_ARG_AS("ph_neck_out_convs", in_planes && wplanes && gn_affine && workspace, "null pointer");
+    PH_CHECK_ARG_AS("ph_neck_out_convs", (out_planes0 || out_f32_0) && (out_planes1 || out_f32_1) && (out_planes2 || out_f32_2),
+                    "every map needs an output");
     const void* fm[3] = {in_planes, in_planes, in_planes};
     uint16_t* outp[3] = {out_planes0, out_planes1, out_planes2};
     float* f32o[3] = {out_f32_0, out_f32_1, out_f32_2};
     return kh_run(fm, in_channels_last ? 2 : 1, wplanes, gn_affine, groups, eps, outp, nullptr, nullptr, nullptr, nullptr, nullptr,
-                  workspace, workspace_bytes, B, HW, prec, stream, __func__, kh_env_knobs(), f32o);
+                  workspace, workspace_bytes, B, HW, prec, stream, "ph_neck_out_convs", kn, f32o);
+}
+
+extern "C" int ph_neck_out_convs(const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes, const float* gn_affine,
+                                 int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1, uint16_t* out_planes2,
+                                 float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace, size_t workspace_bytes,
+                                 int B, int64_t HW, int prec, void* stream) {
+    return ph_neck_out_convs_k(kh_env_knobs(), in_planes, in_channels_last, wplanes, gn_affine, groups, eps, out_planes0, out_planes1,
+                               out_planes2, out_f32_0, out_f32_1, out_f32_2, workspace, workspace_bytes, B, HW, prec, stream);
 }
 
 // ph_khead_fused with (a) a device predicate -- every launch returns at once when *run_if == 0 (null: always run) -- and (b)

@@ -464,13 +464,29 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
 // one-plane formats: 4-row tiles, unless those are fewer than one per CU over the whole launch (then 2-row tiles).  The choice may
 // follow the launch size: the kernels' GroupNorm partial sums are per PAIR of output rows in either form (round 6), so a frame's bits do
 // not depend on it (tests/test_gpu_neck.py::test_conv_tile_forms_give_identical_bits, tests/test_gpu_video.py::test_heads_are_batch_invariant)
-static int conv_th(int Ho, int Wo, int prec, int B) {
+static int conv_th(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B) {
     if (prec == PH_PREC_SPLIT) return 2;
-    static const int force = [] { const char* e = getenv("PH_CONV_TH"); return e ? atoi(e) : 0; }();     // 2 / 4: A/B timing, tests
-    if (const char* e = getenv("PH_CONV_TH_NOW")) { const int f = atoi(e); if (f == 2 || f == 4) return f; }   // tests: read per call
-    if (force == 2 || force == 4) return force;
+    if (kn.conv_th == 2 || kn.conv_th == 4) return kn.conv_th;
     const int64_t t4 = (int64_t)((Wo + CV_TW - 1) / CV_TW) * ((Ho + 3) / 4);
     return B * t4 < 256 ? 2 : 4;
+}
+int ph_conv_nhwc_tile_rows_k(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B) { return conv_th(kn, Ho, Wo, prec & ~PH_PLANES_C16, B); }
+
+// the public entry points' knobs: PH_CONV_TH, PH_GNSUM_*, PH_CPLANES_TPW once per process, PH_CONV_TH_NOW on every call (tests).  The
+// native neck plan (ph_neckplan.hip) calls the *_k forms with the defaults and reads none
+static PhNeckKnobs neck_env_knobs() {
+    static const PhNeckKnobs once = [] {
+        PhNeckKnobs k;
+        auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
+        k.conv_th = num("PH_CONV_TH");             // 2 / 4: A/B timing, tests
+        k.gnsum_wgs = num("PH_GNSUM_WGS");         // tuning knobs
+        k.gnsum_tpw = num("PH_GNSUM_TPW");
+        k.cplanes_tpw = num("PH_CPLANES_TPW");
+        return k;
+    }();
+    PhNeckKnobs k = once;
+    if (const char* e = getenv("PH_CONV_TH_NOW")) { const int f = atoi(e); if (f == 2 || f == 4) k.conv_th = f; }   // tests: read per call
+    return k;
 }
 
 // entries per frame of ph_conv_nhwc's `partial` output = pairs of output rows x 64-pixel column tiles (whatever the tile form;
@@ -487,17 +503,17 @@ extern "C" size_t ph_conv_nhwc_partial_floats(int B, int Ho, int Wo) {
     return (size_t)B * ((Wo + CV_TW - 1) / CV_TW) * ((Ho + 1) / 2) * 256 * 2;
 }
 
-extern "C" int ph_conv_nhwc(const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, float* Y, float* partial, int ksize,
-                            int stride, int B, int H, int W, int prec, void* stream) {
-    PH_CHECK_ARG(X && Wp && Y && partial && B > 0 && H > 0 && W > 0, "bad pointer or size");
-    PH_CHECK_ARG((ksize == 3 && (stride == 1 || stride == 2)) || (ksize == 1 && stride == 1), "supported: 3x3 stride 1/2, 1x1 stride 1");
+int ph_conv_nhwc_k(const PhNeckKnobs& kn, const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, float* Y, float* partial,
+                   int ksize, int stride, int B, int H, int W, int prec, void* stream) {
+    PH_CHECK_ARG_AS("ph_conv_nhwc", X && Wp && Y && partial && B > 0 && H > 0 && W > 0, "bad pointer or size");
+    PH_CHECK_ARG_AS("ph_conv_nhwc", (ksize == 3 && (stride == 1 || stride == 2)) || (ksize == 1 && stride == 1), "supported: 3x3 stride 1/2, 1x1 stride 1");
     const int c16 = (prec & PH_PLANES_C16) ? 1 : 0;
     prec &= ~PH_PLANES_C16;
-    PH_CHECK_ARG(!c16 || (ksize == 3 && stride == 2 && prec != PH_PREC_SPLIT), "PH_PLANES_C16 input: the one-plane 3x3 stride-2 kernel only");
-    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
+    PH_CHECK_ARG_AS("ph_conv_nhwc", !c16 || (ksize == 3 && stride == 2 && prec != PH_PREC_SPLIT), "PH_PLANES_C16 input: the one-plane 3x3 stride-2 kernel only");
+    PH_CHECK_ARG_AS("ph_conv_nhwc", prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
     const int pad = ksize / 2;
     const int Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
-    const int th = conv_th(Ho, Wo, prec, B);
+    const int th = conv_th(kn, Ho, Wo, prec, B);
     const dim3 grid((Wo + CV_TW - 1) / CV_TW, (Ho + th - 1) / th, B);
     const int64_t x_plane = (int64_t)B * H * W * 256;
     hipStream_t s = (hipStream_t)stream;
@@ -529,6 +545,11 @@ extern "C" int ph_conv_nhwc(const uint16_t* X, const uint16_t* Wp, int64_t w_pla
 #undef PH_CV_T
     PH_CHECK_LAUNCH();
     return PH_OK;
+}
+
+extern "C" int ph_conv_nhwc(const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, float* Y, float* partial, int ksize,
+                            int stride, int B, int H, int W, int prec, void* stream) {
+    return ph_conv_nhwc_k(neck_env_knobs(), X, Wp, w_plane_elems, Y, partial, ksize, stride, B, H, W, prec, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -850,12 +871,11 @@ __global__ __launch_bounds__(256) void k_gn_sum_cplanes(const GnSumArgs a, int n
     }
 }
 
-extern "C" int ph_gn_sum_cplanes(const float* const* ys, const float* const* stats, const float* const* gammas,
-                                 const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec,
-                                 void* stream) {
-    PH_CHECK_ARG(ys && stats && gammas && betas && planes && nlev >= 1 && nlev <= 4 && B > 0 && B <= 65535 && HW > 0, "bad pointer or size");
-    PH_CHECK_ARG(groups > 0 && 256 % groups == 0, "bad group count");
-    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
+int ph_gn_sum_cplanes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
+                        const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream) {
+    PH_CHECK_ARG_AS("ph_gn_sum_cplanes", ys && stats && gammas && betas && planes && nlev >= 1 && nlev <= 4 && B > 0 && B <= 65535 && HW > 0, "bad pointer or size");
+    PH_CHECK_ARG_AS("ph_gn_sum_cplanes", groups > 0 && 256 % groups == 0, "bad group count");
+    PH_CHECK_ARG_AS("ph_gn_sum_cplanes", prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
     GnSumArgs a;
     for (int l = 0; l < 4; ++l) {
         const int k = l < nlev ? l : 0;
@@ -864,8 +884,7 @@ extern "C" int ph_gn_sum_cplanes(const float* const* ys, const float* const* sta
     const int64_t HWp = ph_hw_padded(HW), ntiles = HWp / 64;
     int tpw = (int)((ntiles * B + 2047) / 2048);            // ~2048 workgroups: the 4-level affine set-up is amortised over the tiles
     if (tpw < 1) tpw = 1;
-    static const int tpw_env = [] { const char* e = getenv("PH_GNSUM_TPW"); return e ? atoi(e) : 0; }();     // tuning knobs, read once
-    if (tpw_env > 0) tpw = tpw_env;
+    if (kn.gnsum_tpw > 0) tpw = kn.gnsum_tpw;
     const dim3 grid((unsigned)((ntiles + tpw - 1) / tpw), B);
     const size_t lds = 256 * 65 * sizeof(float);
     static const bool once = [&] {
@@ -883,20 +902,24 @@ extern "C" int ph_gn_sum_cplanes(const float* const* ys, const float* const* sta
     return PH_OK;
 }
 
-extern "C" int ph_gn_sum_planes(const float* const* ys, const float* const* stats, const float* const* gammas,
-                                const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec,
-                                void* stream) {
-    PH_CHECK_ARG(ys && stats && gammas && betas && planes && nlev >= 1 && nlev <= 4 && B > 0 && HW > 0, "bad pointer or size");
-    PH_CHECK_ARG(groups > 0 && 256 % groups == 0, "bad group count");
-    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
+extern "C" int ph_gn_sum_cplanes(const float* const* ys, const float* const* stats, const float* const* gammas,
+                                 const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec,
+                                 void* stream) {
+    return ph_gn_sum_cplanes_k(neck_env_knobs(), ys, stats, gammas, betas, nlev, groups, planes, B, HW, prec, stream);
+}
+
+int ph_gn_sum_planes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
+                       const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream) {
+    PH_CHECK_ARG_AS("ph_gn_sum_planes", ys && stats && gammas && betas && planes && nlev >= 1 && nlev <= 4 && B > 0 && HW > 0, "bad pointer or size");
+    PH_CHECK_ARG_AS("ph_gn_sum_planes", groups > 0 && 256 % groups == 0, "bad group count");
+    PH_CHECK_ARG_AS("ph_gn_sum_planes", prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
     GnSumArgs a;
     for (int l = 0; l < 4; ++l) {
         const int k = l < nlev ? l : 0;
         a.y[l] = ys[k]; a.stats[l] = stats[k]; a.gamma[l] = gammas[k]; a.beta[l] = betas[k];
     }
     int gx = 1024;                     // several pixels per workgroup: its per-channel affine set-up (4 levels) is amortised
-    static const int gx_env = [] { const char* e = getenv("PH_GNSUM_WGS"); return e ? atoi(e) : 0; }();
-    if (gx_env) gx = gx_env;
+    if (kn.gnsum_wgs) gx = kn.gnsum_wgs;
     if ((HW + 3) / 4 < gx) gx = (int)((HW + 3) / 4);
     if (prec == PH_PREC_F16) hipLaunchKernelGGL((k_gn_sum_planes<1, PH_E_F16>), dim3(gx, 1, B), dim3(256), 0, (hipStream_t)stream, a, nlev, groups, planes, B, HW);
     else if (prec == PH_PREC_BF16) hipLaunchKernelGGL(k_gn_sum_planes<1>, dim3(gx, 1, B), dim3(256), 0, (hipStream_t)stream, a, nlev, groups, planes, B, HW);
@@ -905,23 +928,28 @@ extern "C" int ph_gn_sum_planes(const float* const* ys, const float* const* stat
     return PH_OK;
 }
 
-extern "C" int ph_gn_apply(const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
-                           int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream) {
-    PH_CHECK_ARG(y && B > 0 && H > 0 && W > 0, "bad pointer or size");
-    PH_CHECK_ARG(!stats || (gamma && beta && groups > 0 && 256 % groups == 0), "stats need gamma, beta and a valid group count");
-    PH_CHECK_ARG(mode >= PH_GN_TO_PLANES && mode <= PH_GN_TO_CPLANES, "bad mode");
-    PH_CHECK_ARG(((mode == PH_GN_TO_PLANES || mode == PH_GN_UP2_PLANES || mode == PH_GN_TO_CPLANES) && planes) ||
+extern "C" int ph_gn_sum_planes(const float* const* ys, const float* const* stats, const float* const* gammas,
+                                const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec,
+                                void* stream) {
+    return ph_gn_sum_planes_k(neck_env_knobs(), ys, stats, gammas, betas, nlev, groups, planes, B, HW, prec, stream);
+}
+
+int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
+                  int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream) {
+    PH_CHECK_ARG_AS("ph_gn_apply", y && B > 0 && H > 0 && W > 0, "bad pointer or size");
+    PH_CHECK_ARG_AS("ph_gn_apply", !stats || (gamma && beta && groups > 0 && 256 % groups == 0), "stats need gamma, beta and a valid group count");
+    PH_CHECK_ARG_AS("ph_gn_apply", mode >= PH_GN_TO_PLANES && mode <= PH_GN_TO_CPLANES, "bad mode");
+    PH_CHECK_ARG_AS("ph_gn_apply", ((mode == PH_GN_TO_PLANES || mode == PH_GN_UP2_PLANES || mode == PH_GN_TO_CPLANES) && planes) ||
                      ((mode == PH_GN_ACCUM || mode == PH_GN_TO_NCHW) && outf),
                  "output pointer missing for this mode");
-    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
+    PH_CHECK_ARG_AS("ph_gn_apply", prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
     if (mode == PH_GN_TO_CPLANES) {
-        PH_CHECK_ARG(stats && B <= 65535, "PH_GN_TO_CPLANES needs statistics (and B <= 65535)");
+        PH_CHECK_ARG_AS("ph_gn_apply", stats && B <= 65535, "PH_GN_TO_CPLANES needs statistics (and B <= 65535)");
         const int64_t HW = (int64_t)H * W, HWp = ph_hw_padded(HW);
         const int64_t ntiles = HWp / 64;
         int tpw = (int)((ntiles * B + 1023) / 1024);          // ~1024 workgroups: the affine set-up is amortised over the tiles
         if (tpw < 1) tpw = 1;
-        static const int ctpw_env = [] { const char* e = getenv("PH_CPLANES_TPW"); return e ? atoi(e) : 0; }();
-        if (ctpw_env) tpw = ctpw_env;
+        if (kn.cplanes_tpw) tpw = kn.cplanes_tpw;
         const dim3 grid((unsigned)((ntiles + tpw - 1) / tpw), B);
         const size_t lds = 256 * 65 * sizeof(float);
         static const bool once = [&] {
@@ -953,4 +981,9 @@ extern "C" int ph_gn_apply(const float* y, const float* stats, const float* gamm
     else hipLaunchKernelGGL(k_gn_apply<2>, grid, dim3(256), 0, (hipStream_t)stream, y, stats, gamma, beta, groups, mode, accumulate, planes, outf, B, H, W);
     PH_CHECK_LAUNCH();
     return PH_OK;
+}
+
+extern "C" int ph_gn_apply(const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
+                           int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream) {
+    return ph_gn_apply_k(neck_env_knobs(), y, stats, gamma, beta, groups, mode, accumulate, planes, outf, B, H, W, prec, stream);
 }

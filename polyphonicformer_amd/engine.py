@@ -10,6 +10,7 @@ Per frame-batch the launch sequence is
 No step synchronises or allocates once a `DecodePlan` exists, so the whole sequence can be captured
 into a HIP graph (`DecodePlan.capture`)."""
 import ctypes as C
+import math
 
 import torch
 
@@ -1068,6 +1069,10 @@ class NeckPlan:
         if ((h0 + 1) // 2, (w0 + 1) // 2) != (h1, w1) or any(shapes[i + 1] != ((shapes[i][0] + 1) // 2, (shapes[i][1] + 1) // 2)
                                                              for i in range(1, 3)):
             raise _lib.PolyheadError(f"FPN level sizes {shapes} are not a stride-2 pyramid")
+        # levels 2 and 3 reach the output size by x2 upsampling; checked here as well as in `_tower`, whose check comes after an upsample
+        # launch that would write (2h, 2w) pixels into an (Ho, Wo) buffer
+        if (2 * shapes[2][0], 2 * shapes[2][1]) != (h1, w1) or (4 * shapes[3][0], 4 * shapes[3][1]) != (h1, w1):
+            raise _lib.PolyheadError("level does not end at the stride-8 size")
         big = max(h * w for h, w in shapes)
         self.xa = e((P, B, big, 256), torch.int16)                 # conv input planes (ping)
         self.xb = e((P, B, self.Ho * self.Wo, 256), torch.int16)   # conv input planes (pong, <= output size)
@@ -1216,6 +1221,197 @@ class NeckPlan:
             else:
                 gn_apply(self.y, self.stats, c, groups, _lib.PH_GN_TO_NCHW, B, self.Ho, self.Wo, prec, outf=self.outs[i])
         return (self.pouts if to_planes else self.outs)[:len(pk["outs"])]
+
+
+# ---- the neck as a native object (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs) ------------------------------
+def native_neck_cfg(B, shapes, groups, prec, num_outs=3, pos_level=3, to_planes=False, tower_streams=True, fused_out=None, c16=None,
+                    device_type="cuda"):
+    """the ph_neck_cfg of the NeckPlan that the same arguments (and the same environment) would build: the switches NeckPlan reads
+    from the environment (PH_NECK_OUT2=0, PH_NECK_C16=0, PH_NECK_STREAMS) become cfg fields -- the native plan reads none.
+    `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `shapes`: the four level sizes; `pos_level`: None / -1 for
+    no positional encoding; `fused_out` / `c16`: None = the environment's choice, else True (fused_out only) / False"""
+    name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
+    env = _os.environ.get
+    out2 = env("PH_NECK_OUT2", "1")
+    if out2 in ("2", "3"):
+        raise _lib.PolyheadError("PH_NECK_OUT2=2 / 3 are measurement forms of the Python NeckPlan; the native neck plan has none")
+    if fused_out and out2 == "0":
+        raise _lib.PolyheadError("ph_neck_out_convs asked for while PH_NECK_OUT2=0 is set")
+    fo = _lib.PH_KNOB_OFF if (fused_out is False or out2 == "0") else (_lib.PH_KNOB_ON if fused_out else _lib.PH_KNOB_AUTO)
+    cc = _lib.PH_KNOB_OFF if (c16 is False or env("PH_NECK_C16", "1") == "0") else _lib.PH_KNOB_AUTO
+    ns = env("PH_NECK_STREAMS", "1")           # NeckPlan's `multi`
+    multi = bool(tower_streams) and (B >= 4 or ns == "2" or tower_streams == "always") and ns != "0" and device_type == "cuda"
+    if len(shapes) != 4:
+        raise _lib.PolyheadError("the neck takes four FPN levels")
+    return _lib.NeckCfg(B=B, h=(C.c_int32 * 4)(*[int(x[0]) for x in shapes]), w=(C.c_int32 * 4)(*[int(x[1]) for x in shapes]),
+                        groups=groups, mode=_lib.PH_MODE[name], num_outs=num_outs, pos_level=-1 if pos_level is None else pos_level,
+                        emit_planes=int(bool(to_planes)), emit_f32=int(not to_planes), fused_out=fo, c16=cc, tower_buffers=int(multi))
+
+
+class NativeNeckPack:
+    """one device buffer packed by ph_neck_pack, and its pieces as views in the form of SemanticFPNWrapper._pack's dict (`pk`: so
+    either plan -- NeckPlan or NativeNeckPlan -- runs from it)"""
+
+    def __init__(self, blob, cfg):
+        lib = _lib.load()
+        lay = _lib.NeckLayout()
+        _lib.check(lib.ph_neck_pack_layout(C.byref(cfg), C.byref(lay)), "ph_neck_pack_layout")
+        self.blob, self.layout, self.mode, self.groups, self.num_outs = blob, lay, cfg.mode, cfg.groups, cfg.num_outs
+        self.prec = {_lib.PH_MODE["fp16"]: _lib.PH_PREC_F16, _lib.PH_MODE["bf16"]: _lib.PH_PREC_BF16}.get(cfg.mode, _lib.PH_PREC_SPLIT)
+        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
+
+        def piece(i, dt, shape):
+            off, nb = lay.offset[i], lay.bytes[i]
+            return blob[off:off + nb].view(dt).reshape(shape) if nb else None
+
+        def one(c):
+            k = 3 if c < 7 else 1
+            return dict(wp=piece(3 * c, torch.int16, (P, 256 * k * k * 256)), gamma=piece(3 * c + 1, torch.float32, (256,)),
+                        beta=piece(3 * c + 2, torch.float32, (256,)), k=k, s=2 if c == 0 else 1)
+        self.pk = dict(levels=[[one(0)], [one(1)], [one(2), one(3)], [one(4), one(5), one(6)]],
+                       outs=[one(7 + i) for i in range(cfg.num_outs)])
+        if cfg.num_outs == 3:
+            self.pk["outs_w"] = piece(_lib.PH_NPACK_OUTS_W, torch.int16, (P, 3, 256, 256))
+            self.pk["outs_gn"] = piece(_lib.PH_NPACK_OUTS_GN, torch.float32, (3, 2, 256))
+
+
+def native_neck_pack(module, cfg, device):
+    """the neck's parameters (a SemanticFPNWrapper, or its state_dict) packed on the device by ph_neck_pack"""
+    lib = _lib.load()
+    nbytes = lib.ph_neck_pack_bytes(C.byref(cfg))
+    if nbytes == 0:
+        raise _cfg_error("ph_neck_pack_bytes")
+    params, ptrs = _gather_params(module, device, 3 * (7 + cfg.num_outs), lib.ph_neck_param_name,
+                                  lambda i: lib.ph_neck_param_numel(C.byref(cfg), i))
+    full = (C.c_void_p * _lib.PH_NECK_NPARAMS)(*[t.data_ptr() for t in params])      # absent aux convs: NULL
+    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.ph_neck_pack(C.byref(cfg), full, _lib.ptr(blob), _lib.stream_ptr()), "ph_neck_pack")
+    return NativeNeckPack(blob, cfg)
+
+
+def native_neck_posenc(H, W, num_feats, temperature=10000, scale=2 * math.pi, eps=1e-6, device="cuda:0"):
+    """ph_neck_posenc: the sine positional encoding evaluated in fp64 on the device -> fp32 [2 * num_feats, H, W]"""
+    out = torch.empty((2 * num_feats, H, W), dtype=torch.float32, device=device)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().ph_neck_posenc(H, W, num_feats, float(temperature), float(scale), float(eps), _lib.ptr(out),
+                                              _lib.stream_ptr()), "ph_neck_posenc")
+    return out
+
+
+class NativeNeckPlan:
+    """NeckPlan's `run` surface over the native plan: ONE native call per forward (ph_neck_plan_run), or -- where NeckPlan would put
+    the four level towers on their own streams -- ph_neck_plan_run_level on the same four streams and ph_neck_plan_run_outputs
+    behind them; the same launch sequence and geometry as the NeckPlan of the same arguments, so the same bits.  `pack`: a
+    NativeNeckPack.  `cfg`: a ph_neck_cfg to use as it is (the environment is then not consulted at all; its emit flags follow
+    each run's `to_planes`) instead of `native_neck_cfg`'s."""
+
+    def __init__(self, pack, B, shapes, device, pos_level=3, tower_streams=True, cfg=None):
+        dev = torch.device(device)
+        self.pack, self.B, self.shapes, self.device = pack, B, tuple(tuple(x) for x in shapes), dev
+        mode = {v: k for k, v in _lib.PH_MODE.items() if k != "split"}[pack.mode]
+        base = cfg if cfg is not None else native_neck_cfg(B, self.shapes, pack.groups, mode, pack.num_outs, pos_level, False,
+                                                           tower_streams, device_type=dev.type)
+        self.cfg = _lib.NeckCfg.from_buffer_copy(bytes(base))
+        self.pos_level, self.groups = self.cfg.pos_level, self.cfg.groups
+        lib = _lib.load()
+        nbytes = lib.ph_neck_plan_workspace_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise _cfg_error("ph_neck_plan_workspace_bytes")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
+        self._handles, self._outs = {}, {}
+        self.geometry = self._info(self._handle(bool(self.cfg.emit_planes) and not self.cfg.emit_f32))
+        self.Ho, self.Wo, self.multi = self.geometry.Ho, self.geometry.Wo, bool(self.geometry.tower_buffers)
+        self._streams = None
+        self.io = _lib.NeckIO()
+
+    def _handle(self, to_planes):
+        """the native plan that writes planes / fp32 maps (the two share the workspace: a run uses one of them)"""
+        h = self._handles.get(to_planes)
+        if h is None:
+            cfg = _lib.NeckCfg.from_buffer_copy(bytes(self.cfg))
+            cfg.emit_planes, cfg.emit_f32 = int(to_planes), int(not to_planes)
+            h = C.c_void_p()
+            _lib.check(_lib.load().ph_neck_plan_create(C.byref(cfg), _lib.ptr(self.pack.blob), _lib.ptr(self.workspace),
+                                                       self.workspace.numel(), C.byref(h)), "ph_neck_plan_create")
+            self._handles[to_planes] = h
+        return h
+
+    @staticmethod
+    def _info(h):
+        geo = _lib.NeckGeometry()
+        _lib.check(_lib.load().ph_neck_plan_info(h, C.byref(geo)), "ph_neck_plan_info")
+        return geo
+
+    def _destroy(self):
+        for h in getattr(self, "_handles", {}).values():
+            if h.value and _lib._lib is not None:
+                _lib._lib.ph_neck_plan_destroy(h)
+        self._handles = {}
+
+    def __del__(self):
+        self._destroy()
+
+    def outputs(self, to_planes):
+        """the output tensors of the planes / fp32 form (allocated on first use)"""
+        if to_planes not in self._outs:
+            g, n = self.geometry, self.cfg.num_outs
+            shape, dt = ((g.P, self.B, 256, g.HWp), torch.int16) if to_planes else ((self.B, 256, g.Ho, g.Wo), torch.float32)
+            self._outs[to_planes] = [torch.empty(shape, dtype=dt, device=self.device) for _ in range(n)]
+        return self._outs[to_planes]
+
+    def _fill_io(self, feats, posenc, outs, to_planes):
+        io = self.io
+        for l in range(4):
+            f = feats[l]
+            if f.dtype != torch.float32 or not f.is_contiguous() or tuple(f.shape) != (self.B, 256) + self.shapes[l] or f.device != self.device:
+                raise _lib.PolyheadError(f"NativeNeckPlan.run: level {l} must be fp32 contiguous {(self.B, 256) + self.shapes[l]} on {self.device}")
+            io.feats[l] = f.data_ptr()
+        if self.pos_level >= 0:
+            if posenc is None or posenc.dtype != torch.float32 or not posenc.is_contiguous() or \
+                    tuple(posenc.shape) != (256,) + self.shapes[self.pos_level] or posenc.device != self.device:
+                raise _lib.PolyheadError("NativeNeckPlan.run: posenc must be fp32 contiguous [256, h, w] of the cfg's pos_level")
+            io.posenc = posenc.data_ptr()
+        else:
+            io.posenc = None
+        for i in range(3):
+            t = outs[i] if i < len(outs) else None
+            io.out_planes[i] = t.data_ptr() if (to_planes and t is not None) else None
+            io.out_f32[i] = t.data_ptr() if (not to_planes and t is not None) else None
+        return io
+
+    def run(self, feats, pk=None, groups=None, posenc=None, pos_level=None, to_planes=False):
+        """NeckPlan.run's arguments; `pk`: the NativeNeckPack to run from (a new one -- re-packed weights -- replaces the plan's),
+        `groups` / `pos_level`: must be the cfg's when given"""
+        if pk is not None and pk is not self.pack:
+            if (pk.mode, pk.groups, pk.num_outs) != (self.pack.mode, self.pack.groups, self.pack.num_outs):
+                raise _lib.PolyheadError("NativeNeckPlan.run: the pack's mode, groups or outputs differ from the plan's")
+            self._destroy()
+            self.pack = pk
+        if groups is not None and groups != self.groups:
+            raise _lib.PolyheadError("NativeNeckPlan.run: groups differ from the plan's cfg")
+        if posenc is None and self.pos_level >= 0 and pos_level is not None:
+            raise _lib.PolyheadError("NativeNeckPlan.run: the plan's cfg has a positional encoding, the call has none")
+        if posenc is not None and pos_level is not None and pos_level != self.pos_level:
+            raise _lib.PolyheadError("NativeNeckPlan.run: pos_level differs from the plan's cfg")
+        lib, h = _lib.load(), self._handle(to_planes)
+        outs = self.outputs(to_planes)
+        io = self._fill_io(feats, posenc if self.pos_level >= 0 else None, outs, to_planes)
+        if self.multi:
+            if self._streams is None:
+                self._streams = [torch.cuda.Stream(device=self.device) for _ in range(4)]
+            cur = torch.cuda.current_stream()
+            for lvl in (0, 3, 2, 1):                # the longest chains first (NeckPlan.run)
+                st = self._streams[lvl]
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    _lib.check(lib.ph_neck_plan_run_level(h, lvl, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_level")
+            for st in self._streams:
+                cur.wait_stream(st)
+            _lib.check(lib.ph_neck_plan_run_outputs(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_outputs")
+        else:
+            _lib.check(lib.ph_neck_plan_run(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run")
+        return outs
 
 
 class DualDecodePlan:

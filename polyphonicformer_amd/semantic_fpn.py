@@ -87,6 +87,15 @@ class SemanticFPNWrapper(nn.Module):
         self.aux_convs = nn.ModuleList([mk(1) for _ in range(num_aux_convs)])
         self.precision = "fp32"
         self._packs, self._plans, self._pos = {}, {}, {}
+        self.native_plan = False
+        self._npacks, self._nplans = {}, {}
+
+    def use_native_plan(self, on=True):
+        """inference `forward` / `forward_planes` through the native neck plan (include/polyhead.h ph_neck_pack + ph_neck_plan_*:
+        the parameters packed on the device by one launch, one native call per forward) instead of `_pack` + engine.NeckPlan: the
+        same launches, the same bits.  The training branch is untouched; `ingest_frames` (borrowed clips) needs the Python plan."""
+        self.native_plan = bool(on)
+        return self
 
     def init_weights(self):
         for m in self.modules():                       # semantic_fpn.py:181-186
@@ -97,6 +106,7 @@ class SemanticFPNWrapper(nn.Module):
         assert precision in E.PREC
         self.precision = precision
         self._packs.clear(); self._plans.clear()
+        self._npacks.clear(); self._nplans.clear()
 
     # ---- packed parameters ---------------------------------------------------------------------------------
     def _pack(self, dev):
@@ -132,6 +142,29 @@ class SemanticFPNWrapper(nn.Module):
                                                       self.pos_cfg.get("scale", 2 * math.pi), self.pos_cfg.get("eps", 1e-6)).to(dev)
         return self._pos[key]
 
+    def _forward_native(self, inputs, dev, B, shapes, planes):
+        """`forward`'s inference branch on the native plan: the pack keyed on the parameter versions exactly as `_pack` is, one
+        NativeNeckPlan per (B, level sizes), the host-computed positional encoding (the Python path's bits)"""
+        pos_level = self.cat_coors_level if self.pos_cfg is not None else -1
+        ts = getattr(self, "tower_streams", True)
+        if ts and B < 4 and getattr(self, "_clip_towers", False):
+            ts = "always"
+        pkey = (str(dev), self.precision, _lib.param_versions(self))
+        pk = self._npacks.get(pkey)
+        if pk is None:
+            self._npacks.clear()
+            cfg = E.native_neck_cfg(B, shapes, self.groups, self.precision, 1 + self.num_aux_convs, pos_level, planes, ts,
+                                    device_type=dev.type)
+            pk = self._npacks[pkey] = E.native_neck_pack(self, cfg, dev)
+        key = (B, shapes, str(dev), self.precision)
+        plan = self._nplans.get(key)
+        if plan is None:
+            with torch.cuda.device(dev):
+                plan = self._nplans[key] = E.NativeNeckPlan(pk, B, shapes, dev, pos_level, ts)
+        add = self._posenc(*shapes[self.cat_coors_level], dev) if self.pos_cfg is not None else None
+        with torch.cuda.device(dev):
+            return plan.run([t.float().contiguous() for t in inputs[:4]], pk, self.groups, add, pos_level, to_planes=planes)
+
     # ---- forward (semantic_fpn.py:198-235) ---------------------------------------------------------------------
     def forward_planes(self, inputs):
         """the same maps as `forward`, as the decode path's feature format: bf16 planes [P][B][256][HWp] (int16 tensors,
@@ -149,6 +182,9 @@ class SemanticFPNWrapper(nn.Module):
         """round 6: fills the plan's conv input planes from B one-frame level tuples, frame by frame and without a batched copy of the
         levels (video.VideoStreamRunner's borrowed clips; engine.NeckPlan.ingest_frames).  `plan`: the plan a captured graph replays
         (the caller holds it); default: this module's plan for that clip size, which must exist (one `forward` of B frames)."""
+        if self.native_plan:
+            raise _lib.PolyheadError("SemanticFPNWrapper.ingest_frames: not available with the native neck plan "
+                                     "(use_native_plan(False) for borrowed clips)")
         t0 = frames[0][0]
         shapes = tuple(tuple(t.shape[-2:]) for t in frames[0][:4])
         if plan is None:
@@ -169,8 +205,13 @@ class SemanticFPNWrapper(nn.Module):
                 return outs
             return [outs[0]] if self.return_list else outs[0]
         dev, B = x0.device, x0.shape[0]
-        pk, prec, G = self._pack(dev), E.KHEAD_PREC[self.precision], self.groups
         shapes = tuple(tuple(t.shape[-2:]) for t in inputs[:4])
+        if self.native_plan:
+            outs = self._forward_native(inputs, dev, B, shapes, _planes)
+            if _planes or self.num_aux_convs > 0:
+                return outs
+            return [outs[0]] if self.return_list else outs[0]
+        pk, prec, G = self._pack(dev), E.KHEAD_PREC[self.precision], self.groups
         plan = self._plans.get((B, shapes, str(dev), self.precision))
         if plan is None:
             # `_clip_towers` (set by video.VideoStreamRunner around the capture of a 2-3 frame clip launch): the four level towers on

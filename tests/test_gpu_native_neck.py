@@ -1,0 +1,618 @@
+"""GPU: the native neck plan (include/polyhead.h ph_neck_pack, ph_neck_posenc, ph_neck_plan_*; engine.NativeNeckPlan;
+SemanticFPNWrapper.use_native_plan; examples/neck_c).  The packing is compared byte for byte with SemanticFPNWrapper._pack, the
+plan's outputs bit for bit with engine.NeckPlan, and the native path against the reference's goldens and the oracle at the
+tolerances of tests/test_gpu_neck.py.  Every module here has non-trivial parameters (conv ~ N(0, 0.05), GroupNorm gamma ~ U(0.5, 1.5),
+beta ~ N(0, 0.2)): default GroupNorm parameters would hide a swapped gamma / beta or a wrong conv index.
+
+The level sizes.  The neck sums the four levels at level 1's size, which levels 2 and 3 reach by x2 upsampling: level 1 must be
+exactly twice level 2 and four times level 3.  Two pyramids of the issue this file answers -- (9,13),(5,7),(3,4),(2,2) and
+(16,140),(8,70),(4,35),(2,18) -- are not (3x4 -> 6x8, not 5x7; 2x18 -> 8x72, not 8x70).  The reference cannot sum such levels, and
+engine.NeckPlan raises "level does not end at the stride-8 size" only in the MIDDLE of its run, after an upsample launch that writes
+more pixels than its buffer holds; so NeckPlan is never run on them here.  What is checked for those two is that the native plan
+refuses them before anything is launched (here and in tests/test_native_neck.py); the bit-identity cases use their nearest valid
+neighbours with the same properties: S1 = (7,15),(4,8),(2,4),(1,2) (odd level 0, every map below one tile) and
+S2 = (16,143),(8,72),(4,36),(2,18) (Wo = 72 crosses the 64-pixel column tile, odd level-0 width)."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import bench
+import helpers as Hh
+from oracle import neck_oracle as NO
+from polyphonicformer_amd import _lib, engine as E
+from polyphonicformer_amd import build as BLD
+from polyphonicformer_amd.registry import HEADS, NECKS, ConfigDict
+from polyphonicformer_amd.semantic_fpn import sine_positional_encoding
+import polyphonicformer_amd.kernel_head  # noqa: F401
+
+pytestmark = pytest.mark.gpu
+torch.set_grad_enabled(False)
+
+KNOBS = ("PH_CONV_TH", "PH_CONV_TH_NOW", "PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS", "PH_GNSUM_TPW", "PH_GNSUM_WGS", "PH_CPLANES_TPW",
+         "PH_NECK_STATS3", "PH_NECK_APPLY3", "PH_KHEAD_TWOPASS", "PH_POOL_NSPLIT")
+S1_ISSUE = ((9, 13), (5, 7), (3, 4), (2, 2))
+S2_ISSUE = ((16, 140), (8, 70), (4, 35), (2, 18))
+S1 = ((7, 15), (4, 8), (2, 4), (1, 2))
+S2 = ((16, 143), (8, 72), (4, 36), (2, 18))
+S3 = ((32, 64), (16, 32), (8, 16), (4, 8))
+S4 = ((128, 512), (64, 256), (32, 128), (16, 64))
+NECK_CFG = dict(type="SemanticFPNWrapper", in_channels=256, feat_channels=256, out_channels=256, start_level=0, end_level=3,
+                upsample_times=2, positional_encoding=dict(type="SinePositionalEncoding", num_feats=128, normalize=True),
+                cat_coors=False, cat_coors_level=3, fuse_by_cat=False, return_list=False, num_aux_convs=2,
+                norm_cfg=dict(type="GN", num_groups=32, requires_grad=True))
+GOLDEN_TOL = {"bf16": 3e-2, "fp32": 1e-3, "fp16": 1e-3}      # tests/test_gpu_neck.py::test_neck_vs_reference_golden
+ORACLE_TOL = 1e-3                                            # tests/test_gpu_neck.py::test_neck_vs_oracle_ragged_sizes
+
+
+@pytest.fixture(autouse=True)
+def _no_knobs(monkeypatch):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+
+
+def _fill(m, seed):
+    g = torch.Generator().manual_seed(seed)
+    for name, p in m.named_parameters():
+        if name.endswith("conv.weight"):
+            p.copy_(0.05 * torch.randn(p.shape, generator=g))
+        elif name.endswith("gn.weight"):
+            p.copy_(0.5 + torch.rand(p.shape, generator=g))
+        else:
+            p.copy_(0.2 * torch.randn(p.shape, generator=g))
+
+
+_NECKS = {}
+
+
+def _neck(precision, num_aux=2, positional=True, groups=32):
+    """a neck with non-trivial parameters on the GPU (shared: built once per configuration)"""
+    key = (precision, num_aux, positional, groups)
+    if key not in _NECKS:
+        cfg = dict(NECK_CFG, num_aux_convs=num_aux, norm_cfg=dict(type="GN", num_groups=groups, requires_grad=True))
+        if not positional:
+            cfg["positional_encoding"] = None
+        m = NECKS.build(cfg)
+        _fill(m, 7 + num_aux)
+        m.eval().to("cuda:0")
+        m.set_precision(precision)
+        _NECKS[key] = m
+    return _NECKS[key]
+
+
+def _feats(shapes, B, gpu, seed=3):
+    g = torch.Generator(device=gpu).manual_seed(seed)
+    return [torch.randn((B, 256) + tuple(s), generator=g, device=gpu) for s in shapes]
+
+
+def _cfg(B, shapes, precision, num_outs=3, pos_level=3, tb=0, fused_out=_lib.PH_KNOB_AUTO, c16=_lib.PH_KNOB_AUTO, groups=32):
+    """an explicit ph_neck_cfg: nothing of it comes from the environment"""
+    return _lib.NeckCfg(B=B, h=(C.c_int32 * 4)(*[s[0] for s in shapes]), w=(C.c_int32 * 4)(*[s[1] for s in shapes]), groups=groups,
+                        mode=_lib.PH_MODE[precision], num_outs=num_outs, pos_level=pos_level, emit_f32=1, fused_out=fused_out, c16=c16,
+                        tower_buffers=tb)
+
+
+def _bytes(t):
+    return t.contiguous().reshape(-1).view(torch.uint8)
+
+
+def _poison(outs):
+    for t in outs:
+        if t.dtype == torch.int16:
+            t.fill_(0x7fff)
+        else:
+            t.fill_(float("nan"))
+
+
+def _tail_is_zero(planes, HW):
+    return all(int(t[..., HW:].ne(0).sum()) == 0 for t in planes)
+
+
+def _native_run(m, cfg, feats, posenc, to_planes, gpu, pack=None):
+    pack = pack if pack is not None else E.native_neck_pack(m, cfg, gpu)
+    plan = E.NativeNeckPlan(pack, cfg.B, list(zip(cfg.h, cfg.w)), gpu, cfg=cfg)
+    _poison(plan.outputs(to_planes))
+    outs = plan.run(feats, posenc=posenc, to_planes=to_planes)
+    torch.cuda.synchronize()
+    return [o.clone() for o in outs], plan
+
+
+# ---- 1. packing -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("num_outs", [1, 3])
+def test_packing_is_the_module_pack_byte_for_byte(gpu, precision, num_outs):
+    """every piece of ph_neck_pack's buffer against the matching tensor of SemanticFPNWrapper._pack (float64 host code); the
+    alignment padding is zero after packing into a poisoned buffer"""
+    lib = _lib.load()
+    m = _neck(precision, num_outs - 1)
+    ref = m._pack(gpu)
+    cfg = _cfg(1, S3, precision, num_outs)
+    nbytes = lib.ph_neck_pack_bytes(C.byref(cfg))
+    params, ptrs = E._gather_params(m, gpu, 3 * (7 + num_outs), lib.ph_neck_param_name, lambda i: lib.ph_neck_param_numel(C.byref(cfg), i))
+    full = (C.c_void_p * _lib.PH_NECK_NPARAMS)(*[t.data_ptr() for t in params])
+    blob = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=gpu)
+    _lib.check(lib.ph_neck_pack(C.byref(cfg), full, _lib.ptr(blob), _lib.stream_ptr()), "ph_neck_pack")
+    torch.cuda.synchronize()
+    pack = E.NativeNeckPack(blob, cfg)
+    flat = [c for lv in ref["levels"] for c in lv] + ref["outs"]
+    nflat = [c for lv in pack.pk["levels"] for c in lv] + pack.pk["outs"]
+    assert len(flat) == len(nflat) == 7 + num_outs and [len(lv) for lv in pack.pk["levels"]] == [1, 1, 2, 3]
+    for i, (a, b) in enumerate(zip(flat, nflat)):
+        assert (a["k"], a["s"]) == (b["k"], b["s"]), i
+        for name in ("wp", "gamma", "beta"):
+            assert a[name].dtype == b[name].dtype and tuple(a[name].shape) == tuple(b[name].shape), (i, name)
+            assert torch.equal(_bytes(a[name]), _bytes(b[name])), (i, name)
+    assert ("outs_w" in ref) == ("outs_w" in pack.pk) == (num_outs == 3)
+    if num_outs == 3:
+        for name in ("outs_w", "outs_gn"):
+            assert tuple(ref[name].shape) == tuple(pack.pk[name].shape) and torch.equal(_bytes(ref[name]), _bytes(pack.pk[name])), name
+    covered = torch.zeros(nbytes, dtype=torch.bool, device=gpu)
+    for i in range(_lib.PH_NPACK_COUNT):
+        covered[pack.layout.offset[i]:pack.layout.offset[i] + pack.layout.bytes[i]] = True
+    assert int(blob[~covered].ne(0).sum()) == 0
+
+
+# ---- 2. bit identity with NeckPlan ------------------------------------------------------------------------------------------
+def _neckplan_run(m, B, shapes, precision, feats, posenc, to_planes, gpu, tower_streams):
+    plan = E.NeckPlan(B, shapes, E.KHEAD_PREC[precision], gpu, tower_streams=tower_streams)
+    outs = plan.run(feats, m._pack(gpu), m.groups, posenc, 3, to_planes=to_planes)
+    torch.cuda.synchronize()
+    return [o.clone() for o in outs], plan
+
+
+IDENT = [("S1", S1, 2, p) for p in ("fp32", "bf16", "fp16")] + [("S2", S2, 1, p) for p in ("fp32", "bf16", "fp16")] + \
+    [("S3", S3, 5, p) for p in ("fp32", "bf16", "fp16")] + [("S4", S4, 5, "fp16")]
+
+
+@pytest.mark.parametrize("name,shapes,B,precision", IDENT, ids=[f"{c[0]}-{c[3]}" for c in IDENT])
+def test_bit_identity_with_neck_plan(gpu, name, shapes, B, precision):
+    """NeckPlan on one stream and on its four tower streams, the native plan with shared and with per-level buffers: the same bits,
+    as planes and as fp32 maps, with the positional encoding (three outputs) and without (one output); the plane outputs' padding
+    is zero whatever the buffer held"""
+    feats = _feats(shapes, B, gpu)
+    HW = shapes[1][0] * shapes[1][1]
+    combos = [(True, 3), (False, 1)] if name != "S4" else [(True, 3)]
+    for positional, num_outs in combos:
+        m = _neck(precision, num_outs - 1)
+        posenc = sine_positional_encoding(*shapes[3], 128).to(gpu) if positional else None
+        for to_planes in (True, False):
+            ref, p0 = _neckplan_run(m, B, shapes, precision, feats, posenc, to_planes, gpu, False)
+            ref2, p1 = _neckplan_run(m, B, shapes, precision, feats, posenc, to_planes, gpu, "always")
+            assert not p0.multi and p1.multi
+            pack = None
+            for tb in (0, 1):
+                cfg = _cfg(B, shapes, precision, num_outs, 3 if positional else -1, tb)
+                got, plan = _native_run(m, cfg, feats, posenc, to_planes, gpu, pack)
+                pack = plan.pack
+                geo = plan.geometry
+                assert (geo.fused_out, geo.c16, geo.tower_buffers) == (int(p0.out2 and num_outs == 3), int(precision != "fp32"), tb)
+                assert (4 in list(geo.tile_rows)) == (name == "S4")
+                assert len(got) == len(ref) == len(ref2) == num_outs
+                for i in range(num_outs):
+                    assert got[i].dtype == ref[i].dtype and tuple(got[i].shape) == tuple(ref[i].shape)
+                    assert torch.equal(got[i], ref[i]) and torch.equal(got[i], ref2[i]), (positional, num_outs, to_planes, tb, i)
+                if to_planes:
+                    assert tuple(got[0].shape) == (geo.P, B, 256, geo.HWp) and _tail_is_zero(got, HW)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+def test_knobs_off_equal_the_python_plan_under_its_environment(gpu, monkeypatch, precision):
+    """fused_out = OFF against PH_NECK_OUT2=0 and c16 = OFF against PH_NECK_C16=0: the variables are set for the Python plan only"""
+    B, shapes = 5, S3
+    m = _neck(precision)
+    feats = _feats(shapes, B, gpu, seed=5)
+    posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
+    for var, kw in (("PH_NECK_OUT2", dict(fused_out=_lib.PH_KNOB_OFF)), ("PH_NECK_C16", dict(c16=_lib.PH_KNOB_OFF))):
+        for to_planes in (True, False):
+            monkeypatch.setenv(var, "0")
+            ref, p = _neckplan_run(m, B, shapes, precision, feats, posenc, to_planes, gpu, "always")
+            assert p.out2 == (var != "PH_NECK_OUT2")
+            monkeypatch.delenv(var)
+            got, plan = _native_run(m, _cfg(B, shapes, precision, tb=1, **kw), feats, posenc, to_planes, gpu)
+            assert (plan.geometry.fused_out, plan.geometry.c16) == (int(var != "PH_NECK_OUT2"), int(var != "PH_NECK_C16"))
+            for a, b in zip(got, ref):
+                assert torch.equal(a, b), (var, to_planes)
+            if to_planes:
+                assert _tail_is_zero(got, 16 * 32)
+
+
+def test_unreachable_level_sizes_are_refused_before_any_launch(gpu):
+    """the issue's S1 / S2 (see the module docstring): no workspace size, no plan, PH_EUNSUPPORTED and NeckPlan's words"""
+    lib = _lib.load()
+    for shapes in (S1_ISSUE, S2_ISSUE):
+        cfg = _cfg(2, shapes, "fp16")
+        assert lib.ph_neck_plan_workspace_bytes(C.byref(cfg)) == 0
+        assert "level does not end at the stride-8 size" in lib.ph_last_error_string().decode()
+        buf = torch.zeros(4096, dtype=torch.uint8, device=gpu)
+        h = C.c_void_p()
+        assert lib.ph_neck_plan_create(C.byref(cfg), _lib.ptr(buf), _lib.ptr(buf), 1 << 40, C.byref(h)) == -2 and not h.value
+        with pytest.raises(_lib.PolyheadError, match="stride-8 size"):
+            E.NativeNeckPlan(E.native_neck_pack(_neck("fp16"), _cfg(2, S1, "fp16"), gpu), 2, shapes, gpu)
+
+
+# ---- 3. against the reference ------------------------------------------------------------------------------------------------
+def _golden_neck(precision, gpu):
+    from test_gpu_neck import _neck as golden_neck, _state
+    sd = _state()
+    return golden_neck(precision, gpu, sd).use_native_plan(True), sd
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16", "fp16"])
+def test_native_neck_vs_reference_golden(gpu, precision):
+    """the native path with the golden's weights against full_neck.npz (mini_neck.npz is the 32-channel model: not this library's),
+    at test_neck_vs_reference_golden's tolerances"""
+    m, _ = _golden_neck(precision, gpu)
+    feats = Hh.fpn_inputs(seed=32, B=1, C=256, H0=16, W0=32)
+    outs = m([f.to(gpu) for f in feats])
+    assert m._nplans and not m._plans
+    g = Hh.load_golden("full_neck.npz")
+    for name, o in zip(("out", "aux0", "aux1"), outs):
+        e = Hh.rel_err(o.cpu(), torch.from_numpy(g[name]))
+        print("native neck", precision, name, e)
+        assert e < GOLDEN_TOL[precision], (name, e)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "fp16"])
+def test_native_neck_vs_oracle_ragged_sizes(gpu, precision):
+    m, sd = _golden_neck(precision, gpu)
+    feats = Hh.fpn_inputs(seed=33, B=2, C=256, H0=24, W0=40)
+    outs = m([f.to(gpu) for f in feats])
+    ref = NO.semantic_fpn(sd, feats, groups=32, num_feats=128)
+    for o, r in zip(outs, ref):
+        assert tuple(o.shape) == tuple(r.shape) == (2, 256, 12, 20)
+        e = Hh.rel_err(o.cpu(), r)
+        print("native neck ragged", precision, e)
+        assert e < ORACLE_TOL
+
+
+# ---- 4. the positional encoding ----------------------------------------------------------------------------------------------
+def _posenc64(H, W, num_feats, temperature=10000, scale=2 * math.pi, eps=1e-6):
+    """sine_positional_encoding's formula in float64"""
+    y = torch.arange(1, H + 1, dtype=torch.float64).view(H, 1).expand(H, W)
+    x = torch.arange(1, W + 1, dtype=torch.float64).view(1, W).expand(H, W)
+    y = y / (y[-1:, :] + eps) * scale
+    x = x / (x[:, -1:] + eps) * scale
+    dim_t = torch.arange(num_feats, dtype=torch.float64)
+    dim_t = temperature ** (2 * (dim_t // 2) / num_feats)
+    px, py = x[..., None] / dim_t, y[..., None] / dim_t
+    px = torch.stack((px[..., 0::2].sin(), px[..., 1::2].cos()), dim=3).view(H, W, -1)
+    py = torch.stack((py[..., 0::2].sin(), py[..., 1::2].cos()), dim=3).view(H, W, -1)
+    return torch.cat((py, px), dim=2).permute(2, 0, 1).contiguous()
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (2, 3), (16, 32)])
+def test_posenc_kernel(gpu, H, W):
+    """fp64 on the device, rounded once: within 2^-23 of the float64 formula (values in [-1, 1]: a correctly rounded fp32 is within
+    2^-24, one more ulp for the device's fp64 sin / cos / pow); within 2e-6 of the host fp32 function (block and index order)"""
+    out = torch.full((256, H, W), float("nan"), device=gpu)
+    _lib.check(_lib.load().ph_neck_posenc(H, W, 128, 10000.0, 2 * math.pi, 1e-6, _lib.ptr(out), _lib.stream_ptr()), "ph_neck_posenc")
+    got = out.cpu()
+    d64 = float((got.double() - _posenc64(H, W, 128)).abs().max())
+    d32 = float((got - sine_positional_encoding(H, W, 128)).abs().max())
+    print("posenc", (H, W), d64, d32)
+    assert d64 <= 2.0 ** -23
+    assert d32 <= 2e-6
+    assert torch.equal(E.native_neck_posenc(H, W, 128, device=gpu).cpu(), got)
+
+
+def test_device_posenc_table_meets_the_golden(gpu):
+    """the whole neck with ph_neck_posenc's table in place of the host one: the same golden, the same tolerance"""
+    m, _ = _golden_neck("fp16", gpu)
+    feats = [f.to(gpu) for f in Hh.fpn_inputs(seed=32, B=1, C=256, H0=16, W0=32)]
+    shapes = [tuple(f.shape[-2:]) for f in feats]
+    cfg = _cfg(1, shapes, "fp16")
+    table = E.native_neck_posenc(*shapes[3], 128, device=gpu)
+    outs, _ = _native_run(m, cfg, feats, table, False, gpu)
+    g = Hh.load_golden("full_neck.npz")
+    for name, o in zip(("out", "aux0", "aux1"), outs):
+        assert Hh.rel_err(o.cpu(), torch.from_numpy(g[name])) < GOLDEN_TOL["fp16"], name
+
+
+# ---- 5. concurrent levels ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+def test_concurrent_levels_equal_the_single_stream_run(gpu, precision):
+    lib = _lib.load()
+    B, shapes = 5, S3
+    m = _neck(precision)
+    feats = _feats(shapes, B, gpu, seed=9)
+    posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
+    for to_planes in (True, False):
+        cfg = _cfg(B, shapes, precision, tb=1)
+        plan = E.NativeNeckPlan(E.native_neck_pack(m, cfg, gpu), B, shapes, gpu, cfg=cfg)
+        h, outs = plan._handle(to_planes), plan.outputs(to_planes)
+        io = plan._fill_io(feats, posenc, outs, to_planes)
+        _poison(outs)
+        _lib.check(lib.ph_neck_plan_run(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run")
+        torch.cuda.synchronize()
+        one = [o.clone() for o in outs]
+        _poison(outs)
+        plan.workspace.fill_(0xEE)
+        cur = torch.cuda.current_stream()
+        streams = [torch.cuda.Stream(device=gpu) for _ in range(4)]
+        done = []
+        for lvl, st in enumerate(streams):
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                _lib.check(lib.ph_neck_plan_run_level(h, lvl, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_level")
+                ev = torch.cuda.Event()
+                ev.record(st)
+                done.append(ev)
+        for ev in done:
+            cur.wait_event(ev)
+        _lib.check(lib.ph_neck_plan_run_outputs(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_outputs")
+        torch.cuda.synchronize()
+        for a, b in zip(outs, one):
+            assert torch.equal(a, b), to_planes
+
+
+# ---- 6. graph capture ----------------------------------------------------------------------------------------------------------
+def test_graph_capture_replays_the_eager_run(gpu):
+    B, shapes = 2, S1
+    m = _neck("fp16")
+    posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
+    cfg = _cfg(B, shapes, "fp16", tb=0)
+    plan = E.NativeNeckPlan(E.native_neck_pack(m, cfg, gpu), B, shapes, gpu, cfg=cfg)
+    static = _feats(shapes, B, gpu, seed=20)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        plan.run(static, posenc=posenc, to_planes=True)      # warm-up outside capture (lazy module load)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        outs = plan.run(static, posenc=posenc, to_planes=True)
+    for seed in (21, 22):
+        new = _feats(shapes, B, gpu, seed=seed)
+        for dst, src in zip(static, new):
+            dst.copy_(src)
+        _poison(outs)
+        graph.replay()
+        torch.cuda.synchronize()
+        replayed = [o.clone() for o in outs]
+        eager, _ = _native_run(m, cfg, new, posenc, True, gpu, plan.pack)
+        for a, b in zip(replayed, eager):
+            assert torch.equal(a, b), seed
+
+
+# ---- 7. the environment ----------------------------------------------------------------------------------------------------------
+def test_environment_does_not_reach_the_native_plan(gpu, monkeypatch):
+    B, shapes = 5, S3                       # every conv launch takes 2-row tiles here: PH_CONV_TH_NOW=4 would change the public path's
+    m = _neck("fp16")
+    feats = _feats(shapes, B, gpu, seed=11)
+    posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
+    cfg = _cfg(B, shapes, "fp16", tb=1)
+    base, plan = _native_run(m, cfg, feats, posenc, True, gpu)
+    geo0 = bytes(plan.geometry)
+    p = E.NeckPlan(B, shapes, _lib.PH_PREC_F16, gpu)
+    assert p.out2 and p.multi
+    for k, v in (("PH_CONV_TH_NOW", "4"), ("PH_NECK_OUT2", "0"), ("PH_NECK_C16", "0"), ("PH_NECK_STREAMS", "0")):
+        monkeypatch.setenv(k, v)
+    got, plan2 = _native_run(m, cfg, feats, posenc, True, gpu)
+    assert bytes(plan2.geometry) == geo0 and 4 not in list(plan2.geometry.tile_rows)
+    for a, b in zip(got, base):
+        assert torch.equal(a, b)
+    p = E.NeckPlan(B, shapes, _lib.PH_PREC_F16, gpu)          # the public path still listens
+    assert not p.out2 and not p.multi
+    c = E.native_neck_cfg(B, shapes, 32, "fp16")              # and the cfg helper maps it
+    assert (c.fused_out, c.c16, c.tower_buffers) == (_lib.PH_KNOB_OFF, _lib.PH_KNOB_OFF, 0)
+
+
+# ---- 8. guarded buffers ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision,tb,fused", [("fp16", 1, _lib.PH_KNOB_AUTO), ("fp32", 0, _lib.PH_KNOB_AUTO), ("bf16", 0, _lib.PH_KNOB_OFF)])
+def test_workspace_and_pack_stay_inside_their_bounds(gpu, precision, tb, fused):
+    """pack and workspace between 4 KiB canaries: intact after pack + run; a workspace 256 bytes short is refused, nothing launched"""
+    lib = _lib.load()
+    B, shapes, G = 3, S2, 4096
+    m = _neck(precision)
+    cfg = _cfg(B, shapes, precision, tb=tb, fused_out=fused)
+    cfg.emit_planes = 1
+    nws, npk = lib.ph_neck_plan_workspace_bytes(C.byref(cfg)), lib.ph_neck_pack_bytes(C.byref(cfg))
+    ws = torch.full((nws + 2 * G,), 0x5A, dtype=torch.uint8, device=gpu)
+    pk = torch.full((npk + 2 * G,), 0x5A, dtype=torch.uint8, device=gpu)
+    params, _ = E._gather_params(m, gpu, _lib.PH_NECK_NPARAMS, lib.ph_neck_param_name, lambda i: lib.ph_neck_param_numel(C.byref(cfg), i))
+    ptrs = (C.c_void_p * _lib.PH_NECK_NPARAMS)(*[t.data_ptr() for t in params])
+    pk_ptr, ws_ptr = C.c_void_p(pk.data_ptr() + G), C.c_void_p(ws.data_ptr() + G)
+    h = C.c_void_p()
+    assert lib.ph_neck_plan_create(C.byref(cfg), pk_ptr, ws_ptr, nws - 256, C.byref(h)) == -4 and not h.value
+    torch.cuda.synchronize()
+    assert int(ws.ne(0x5A).sum()) == 0 and int(pk.ne(0x5A).sum()) == 0
+    _lib.check(lib.ph_neck_pack(C.byref(cfg), ptrs, pk_ptr, _lib.stream_ptr()), "ph_neck_pack")
+    _lib.check(lib.ph_neck_plan_create(C.byref(cfg), pk_ptr, ws_ptr, nws, C.byref(h)), "ph_neck_plan_create")
+    geo = _lib.NeckGeometry()
+    lib.ph_neck_plan_info(h, C.byref(geo))
+    feats = _feats(shapes, B, gpu, seed=13)
+    posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
+    planes = [torch.empty((geo.P, B, 256, geo.HWp), dtype=torch.int16, device=gpu) for _ in range(3)]
+    maps = [torch.empty((B, 256, geo.Ho, geo.Wo), device=gpu) for _ in range(3)]
+    io = _lib.NeckIO(posenc=posenc.data_ptr())
+    for l in range(4):
+        io.feats[l] = feats[l].data_ptr()
+    for i in range(3):
+        io.out_planes[i], io.out_f32[i] = planes[i].data_ptr(), maps[i].data_ptr()
+    _lib.check(lib.ph_neck_plan_run(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run")
+    torch.cuda.synchronize()
+    lib.ph_neck_plan_destroy(h)
+    for buf, n in ((ws, nws), (pk, npk)):
+        assert int(buf[:G].ne(0x5A).sum()) == 0 and int(buf[G + n:].ne(0x5A).sum()) == 0
+    # both output forms of one run agree with the one-form runs of the Python-side plan
+    for to_planes, got in ((True, planes), (False, maps)):
+        ref, _ = _native_run(m, _cfg(B, shapes, precision, tb=tb, fused_out=fused), feats, posenc, to_planes, gpu)
+        for a, b in zip(got, ref):
+            assert torch.equal(a, b), to_planes
+
+
+# ---- 9. the module switch ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+def test_module_api_switch(gpu, precision):
+    B, shapes = 2, S3
+    feats = _feats(shapes, B, gpu, seed=15)
+    for num_aux, return_list in ((0, False), (0, True), (2, False)):
+        cfg = dict(NECK_CFG, num_aux_convs=num_aux, return_list=return_list)
+        m = NECKS.build(cfg)
+        _fill(m, 30 + num_aux)
+        m.eval().to(gpu)
+        m.set_precision(precision)
+        unlist = lambda o: list(o) if isinstance(o, (list, tuple)) else [o]
+        off = [o.clone() for o in unlist(m(feats))]
+        off_type = type(m(feats))
+        m.use_native_plan(True)
+        on = m(feats)
+        assert type(on) is off_type and m._nplans
+        for a, b in zip(unlist(on), off):
+            assert torch.equal(a, b), (num_aux, return_list)
+        if num_aux == 2:
+            pl_on = [o.clone() for o in m.forward_planes(feats)]
+            m.use_native_plan(False)
+            for a, b in zip(pl_on, m.forward_planes(feats)):
+                assert torch.equal(a, b)
+            # an in-place change of one conv weight and one GroupNorm bias re-packs
+            m.convs_all_levels[2].conv1.conv.weight.mul_(1.5)
+            m.aux_convs[0].gn.bias.add_(0.25)
+            new_off = [o.clone() for o in m(feats)]
+            assert not torch.equal(new_off[1], off[1])
+            m.use_native_plan(True)
+            for a, b in zip(m(feats), new_off):
+                assert torch.equal(a, b)
+            with pytest.raises(_lib.PolyheadError, match="native neck plan"):
+                m.ingest_frames([tuple(f[:1] for f in feats)] * B)
+        else:
+            with pytest.raises(NotImplementedError):
+                m.forward_planes(feats)
+
+
+def test_kernel_head_with_its_native_neck(gpu):
+    """test_kernel_head_with_its_neck's construction: equal outputs with the neck's native plan on and off"""
+    kh = HEADS.build(dict(type="KernelHead", num_proposals=100, num_classes=19, num_thing_classes=8, num_stuff_classes=11,
+                          in_channels=256, out_channels=256, cat_stuff_mask=True, feat_downsample_stride=2, feat_refine=False,
+                          use_binary=True, conv_normal_init=True, proposal_feats_with_obj=True, kernel_init_std=1,
+                          loss_seg=dict(type="FocalLoss", use_sigmoid=True), localization_fpn=dict(NECK_CFG)))
+    sd = Hh.seeded_fill({k: tuple(v.shape) for k, v in kh.state_dict().items()}, 41)
+    kh.load_state_dict(sd)
+    kh.eval().to(gpu)
+    for precision in ("fp32", "fp16"):
+        kh.set_precision(precision)
+        feats = tuple(f.to(gpu) for f in Hh.fpn_inputs(seed=42, B=1, C=256, H0=16, W0=24))
+        metas = [Hh.img_meta(64, 96)]
+        kh.localization_fpn.use_native_plan(False)
+        off = [t.clone() if torch.is_tensor(t) else t for t in kh.simple_test_rpn(feats, metas)]
+        kh.localization_fpn.use_native_plan(True)
+        on = kh.simple_test_rpn(feats, metas)
+        assert kh.localization_fpn._nplans
+        for i, (a, b) in enumerate(zip(on, off)):
+            if torch.is_tensor(a):
+                assert torch.equal(a, b), (precision, i)
+
+
+# ---- 10. the C++ program ----------------------------------------------------------------------------------------------------------
+NQ, N_THING, N_STUFF = 20, 3, 5
+L = N_THING + N_STUFF
+
+
+def _small_head(precision):
+    torch.manual_seed(5)
+    h = HEADS.build(dict(type="KernelHead", num_proposals=NQ, num_classes=L, num_thing_classes=N_THING, num_stuff_classes=N_STUFF,
+                         in_channels=256, out_channels=256, cat_stuff_mask=True, feat_downsample_stride=2, feat_refine_stride=1,
+                         feat_refine=False, use_binary=True, conv_normal_init=True, proposal_feats_with_obj=True,
+                         xavier_init_kernel=False, kernel_init_std=1, loss_seg=dict(type="FocalLoss", use_sigmoid=True),
+                         localization_fpn=None))
+    h.init_weights()
+    for n in ("loc", "seg", "depth"):
+        mod = getattr(h, f"{n}_convs")[0]
+        mod.gn.weight.add_(0.2 * torch.randn_like(mod.gn.weight))
+        mod.gn.bias.add_(0.2 * torch.randn_like(mod.gn.bias))
+        mod.conv.weight.mul_(8.0)
+    h.conv_seg.weight.mul_(30.0)
+    h.conv_seg.bias.copy_(0.5 * torch.randn_like(h.conv_seg.bias))
+    h.conv_direct_depth.weight.mul_(30.0)
+    h.conv_direct_depth.bias.fill_(0.37)
+    return {k: v.detach().clone() for k, v in h.state_dict().items()}
+
+
+def _raw(t):
+    return t.detach().contiguous().cpu().numpy().reshape(-1).view("u1")
+
+
+@pytest.mark.parametrize("case", ["S1_B2_bf16", "S3_B1_fp16"])
+def test_neck_program(gpu, case, tmp_path):
+    """examples/neck_c: a fresh process with no Python in it goes from the four FPN levels to the panoptic maps; every file it writes
+    is byte-equal to the Python chain on the same native packs and the device-computed positional encoding: NativeNeckPlan (planes)
+    -> KernelHeadPlan -> DecodePlan.run_from_planes -> upsample2x -> BatchMerge"""
+    from polyphonicformer_amd.panoptic import BatchMerge, DEPTH_MODES
+    from test_gpu_native_plan import _native_as_stagepack
+    assert os.path.exists(BLD.NECK_EXAMPLE), "built by python -m polyphonicformer_amd.build"
+    shapes, B, kmode, dmode = dict(S1_B2_bf16=(S1, 2, "bf16", "mixed16"), S3_B1_fp16=(S3, 1, "fp16", "fp16"))[case]
+    H, W = shapes[1]
+    wl = dict(H=H, W=W, Nq=NQ, n_thing=N_THING, n_stuff=N_STUFF, S=2, F=2048)
+    S, F, N = wl["S"], wl["F"], NQ + N_STUFF
+    out_dtype = torch.float16
+    mode = E.MODES[dmode]
+    neck = _neck(kmode)
+    ksd = _small_head(kmode)
+    ih = bench.build_head(wl, "fp32", torch.float32, gpu, seed=8)
+    ih.test_cfg = ConfigDict(max_per_img=NQ, mask_thr=0.5, merge_stuff_thing=dict(overlap_thr=0.0, instance_score_thr=0.3))
+    ih.mask_head[-1].fc_cls.bias.fill_(1.0)      # un-trained heads: let segments pass the score threshold
+    depth_mode = DEPTH_MODES[ih.mask_head[-1].depth_act_mode]
+    meta = dict(img_shape=(8 * H, 8 * W, 3), ori_shape=(8 * H, 8 * W, 3), batch_input_shape=(8 * H, 8 * W))
+    feats = _feats(shapes, B, gpu, seed=17)
+    d_in, d_out = tmp_path / "in", tmp_path / "out"
+    d_in.mkdir()
+    d_out.mkdir()
+    geom = [2 * H, 2 * W, 8 * H, 8 * W, 8 * H, 8 * W, 8 * H, 8 * W]
+    vals = [B] + [v for s in shapes for v in s] + [32, _lib.PH_MODE[kmode], 3, 128, NQ, L, N_THING, S, F, _lib.PH_MODE[dmode],
+                                                  E.OUT_CODE[out_dtype], 1, NQ, depth_mode] + geom + [0.3, 0.0]
+    (d_in / "cfg.txt").write_text(" ".join(str(v) for v in vals) + "\n")
+    lib = _lib.load()
+    tofile = lambda ts, name: np.concatenate([t.detach().float().cpu().numpy().reshape(-1) for t in ts]).astype("<f4").tofile(d_in / name)
+    nsd = neck.state_dict()
+    tofile([nsd[lib.ph_neck_param_name(i).decode()] for i in range(_lib.PH_NECK_NPARAMS)], "neck.bin")
+    tofile([ksd[lib.ph_khead_param_name(i).decode()] for i in range(_lib.PH_KHEAD_NPARAMS)], "khead.bin")
+    for s, st in enumerate(ih.mask_head):
+        sd = st.state_dict()
+        tofile([sd[lib.ph_decode_param_name(i).decode()] for i in range(_lib.PH_DECODE_NPARAMS)], f"stage{s}.bin")
+    for i, f in enumerate(feats):
+        tofile([f], f"p{i}.bin")
+    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME") and k not in KNOBS}
+    r = subprocess.run(["timeout", "-k", "10", "240", BLD.NECK_EXAMPLE, str(d_in), str(d_out)], capture_output=True, text=True, env=env,
+                       timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    print(r.stdout.strip())
+
+    # the Python chain on the same native packs
+    table = E.native_neck_posenc(*shapes[3], 128, device=gpu)
+    ncfg = _cfg(B, shapes, kmode)
+    planes, nplan = _native_run(neck, ncfg, feats, table, True, gpu)
+    kcfg = E.native_khead_cfg(B, H, W, NQ, L, N_THING, True, 32, kmode, want_f32=False, frame_invariant=True)
+    kpack = E.native_khead_pack(ksd, kcfg, gpu)
+    kp = E.KernelHeadPlan(kpack, B, H, W, N_THING, L, True, gpu, want_f32=False, frame_invariant=True)
+    kp.set_inputs(planes)
+    kp.run()
+    dcfg = E.native_cfg(B, N, H, W, S, L, F, mode, out_dtype, True)
+    blobs = [E.native_pack_stage(st, dcfg, gpu) for st in ih.mask_head]
+    dp = E.DecodePlan([_native_as_stagepack(b, dcfg, mode, L) for b in blobs], B, N, H, W, mode, out_dtype, gpu, frame_invariant=True)
+    q0 = kpack.w_dd_f32.reshape(1, 1, 256).expand(B, N, 256).contiguous()
+    dp.run_from_planes(kp.xp, kp.dp, kp.bits, kp.proposal, q0)
+    d0 = E.upsample2x(kp.depth_pred)
+    o = dp.outputs()
+    bm = BatchMerge(ih, B, N, L, 2 * H, 2 * W, out_dtype, meta, gpu)
+    bm.run(o["cls"], o["mask_up"], o["depth_up"], d0)
+    torch.cuda.synchronize()
+    assert kp.timeouts() == 0
+    want = dict(posenc=table, n0=planes[0], n1=planes[1], n2=planes[2], xp=kp.xp, dp=kp.dp, bits=kp.bits, mask_preds=kp.mask_preds,
+                seg_preds=kp.seg_preds, depth_pred=kp.depth_pred, proposal=kp.proposal, depth_proposal=q0, obj=o["obj"], dobj=o["dobj"],
+                cls=o["cls"], mask=o["mask"], mask_up=o["mask_up"], depth_up=o["depth_up"], depth_init_up=d0, pan=bm.pan,
+                depth_basic=bm.d_basic, depth_final=bm.d_final, seg_records=bm.records)
+    written = sorted(p.name for p in d_out.iterdir())
+    assert written == sorted([f"{k}.bin" for k in want] + ["geometry.txt"])
+    for k in ("pan", "depth_basic", "depth_final") + tuple(k for k in want if k not in ("pan", "depth_basic", "depth_final")):
+        got = np.fromfile(d_out / f"{k}.bin", dtype="u1")
+        w = _raw(want[k])
+        assert got.shape == w.shape and np.array_equal(got, w), k
+    geo = dict(line.split() for line in (d_out / "geometry.txt").read_text().splitlines())
+    assert (int(geo["neck_fused_out"]), int(geo["neck_c16"]), int(geo["neck_P"])) == (1, 1, 1)
+    assert (int(geo["khead_onepass"]), int(geo["fell_back"]), int(geo["timeouts"])) == (int(kp.onepass), 0, 0)
+    assert int(geo["K"]) == bm.K and int(bm.records[:, 0].min()) > 0          # the merge accepted segments in every frame
