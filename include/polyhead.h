@@ -1051,6 +1051,136 @@ int ph_neck_plan_run(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
 int ph_neck_plan_run_level(ph_neck_plan* plan, int level, const ph_neck_io* io, void* stream);
 int ph_neck_plan_run_outputs(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
 
+/* ---- N1 as a native object (csrc/ph_assocplan.hip): the association step of PolyphonicVideo.simple_test
+ * (polyphonic_former_video.py:359-405) behind ph_panoptic_merge, for a C / C++ caller -- what video.VideoAssociator and
+ * track_head.QuasiDenseMaskEmbedHeadGTMask string together from Python: things for tracking -> segment boxes -> FPN RoIAlign ->
+ * track embedding head -> tracker -> `sem` and `track` maps.  Conventions are ph_khead_plan_* / ph_neck_plan_*'s: status codes +
+ * ph_last_error_string, caller-owned 256-byte aligned memory, size queries that return 0 with a message on a bad cfg,
+ * PH_EINVAL / PH_EUNSUPPORTED / PH_EWORKSPACE before the first launch, no environment variable read, no memset node (buffers are
+ * zeroed by kernels).  Everything except ph_assoc_plan_match is enqueue-only and capturable into a hipGraph.
+ *
+ * The track head (track_heads.py:12-102): num_convs x (conv3x3 256 -> 256 without bias, GroupNorm, ReLU) on the 7 x 7 x 256 RoI
+ * features, fcs.0 (256 * 49 -> fc_out_channels, ReLU), fc_embed (fc_out_channels -> embed_channels).
+ *   num_convs        1 .. PH_TRACK_MAX_CONVS
+ *   fc_out_channels  a multiple of 16 (PH_EINVAL otherwise) and of 32 (fc_embed's k-steps; PH_EUNSUPPORTED otherwise)
+ *   embed_channels   a multiple of 16; the association plan and the tracker need 256
+ *   groups           GroupNorm groups, divides 256;   eps: 0 = 1e-5
+ *   prec             PH_PREC_BF16 (one bf16 plane) or PH_PREC_SPLIT (hi + lo planes) */
+#define PH_TRACK_MAX_CONVS 8
+typedef struct {
+    int32_t num_convs, fc_out_channels, embed_channels, groups, prec;
+    float eps;
+} ph_track_cfg;
+
+/* ---- the parameter table, fp32 device tensors under the reference's state_dict names, 3 num_convs + 4 entries:
+ *    3 i .. 3 i + 2      convs.{i}.conv.weight [256][256][3][3], convs.{i}.gn.weight [256], convs.{i}.gn.bias [256]
+ *    3 num_convs + 0..3  fcs.0.weight [F][256 * 49], fcs.0.bias [F], fc_embed.weight [E][F], fc_embed.bias [E] */
+const char* ph_track_param_name(const ph_track_cfg* cfg, int index);      /* NULL out of range or on a bad cfg */
+int64_t ph_track_param_numel(const ph_track_cfg* cfg, int index);         /* elements; < 0 out of range */
+
+/* ---- packing (k_track_pack: one launch, once per weight load).  The pieces are QuasiDenseMaskEmbedHeadGTMask._get_pack's tensors,
+ * byte for byte (hi = bf16(w) round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned offset of one
+ * device buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT):
+ *   CONV(i)          uint16 [P][256 * 2304]  pack.pack_b_fragments of W[n][tap * 256 + c] -- the (kh, kw, in) K order
+ *   GAMMA(i), BETA(i)  float [256]
+ *   FC               uint16 [P][F * 12544]   fragments of fcs.0.weight with its K axis permuted from ci * 49 + pos to pos * 256 + ci
+ *   FC_B             float [F]
+ *   EMB              uint16 [P][E * F]       fragments of fc_embed.weight;   EMB_B  float [E]
+ * pieces of convs beyond num_convs are empty (0 bytes) */
+#define PH_TPACK_CONV(i) (i)
+#define PH_TPACK_GAMMA(i) (PH_TRACK_MAX_CONVS + (i))
+#define PH_TPACK_BETA(i) (2 * PH_TRACK_MAX_CONVS + (i))
+enum { PH_TPACK_FC = 24, PH_TPACK_FC_B = 25, PH_TPACK_EMB = 26, PH_TPACK_EMB_B = 27, PH_TPACK_COUNT = 28 };
+typedef struct {
+    uint64_t offset[PH_TPACK_COUNT];   /* bytes from the start of the pack, multiples of 256 */
+    uint64_t bytes[PH_TPACK_COUNT];    /* size of the piece; the next piece starts at offset + bytes rounded up to 256 */
+} ph_track_layout;
+size_t ph_track_pack_bytes(const ph_track_cfg* cfg);                      /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_track_pack_layout(const ph_track_cfg* cfg, ph_track_layout* layout);
+/* `params`: host array of 3 num_convs + 4 device pointers; `pack`: 256-byte aligned device buffer of ph_track_pack_bytes */
+int ph_track_pack(const ph_track_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- the plan's cfg.
+ *   B                 frames per call
+ *   Ho, Wo            size of the panoptic id map (ph_panoptic_merge's `pan`)
+ *   K                 record capacity of ph_panoptic_merge (seg_records rows are 1 + 5 K words), 1 .. 1024
+ *   max_things        `cap`: rows of a frame's things table = RoIs per frame the launches are sized for, 1 <= cap <= K
+ *   num_thing_classes, num_stuff_classes   labels < num_thing_classes are things; void = num_thing_classes + num_stuff_classes (< 256)
+ *   nlev              FPN levels RoIAlign reads, 1 .. 4, level 0 (the finest) first: h[l], w[l] and inv_stride[l] = 1 / stride
+ *   finest_scale      SingleRoIExtractor's finest_scale (the shipped model: 56)
+ *   track             the track head; embed_channels must be 256 */
+typedef struct {
+    int32_t B, Ho, Wo, K, max_things, num_thing_classes, num_stuff_classes, nlev;
+    int32_t h[4], w[4];
+    float inv_stride[4];
+    float finest_scale;
+    ph_track_cfg track;
+} ph_assoc_cfg;
+
+/* ---- plan lifetime.  ph_assoc_plan_create touches no device memory; the caller keeps pack (ph_track_pack's) and workspace alive as
+ * long as the plan, both 256-byte aligned.  ZEROING CONTRACT: none -- every word a launch reads was written by an earlier launch of
+ * the same run.
+ * The split-K rule of the track head's GEMMs is fixed at create time: ph_gemm_rows_splitk's split of (49 cap, 256, 2304) for the
+ * convs, of (cap, F, 12544) for fcs.0 and of (cap, 256, F) for fc_embed -- it depends neither on the device counts nor on B.  So (1)
+ * with cap == n a frame's embeddings are bit-identical to the Python head's forward_planes on its n RoIs, and (2) for a fixed cap an
+ * embedding does not depend on how many other things or frames share the launch. */
+typedef struct ph_assoc_plan ph_assoc_plan;
+typedef struct {
+    int32_t things_words;       /* int32 words of one frame's things table: 2 + 7 cap */
+    int32_t P;                  /* planes of the grade */
+    int32_t conv_splits, conv_steps, fc_splits, fc_steps, emb_splits, emb_steps;   /* the three GEMMs' split-K geometry */
+    int32_t vec8;               /* 1: the box kernels read 8 pixels per thread (Wo % 8 == 0; needs a 16-byte aligned pan) */
+    int32_t reserved;
+    uint64_t staging_bytes;     /* host staging ph_assoc_plan_match needs: B things tables + B track tables of K + 1 doubles */
+    uint64_t rois_offset;       /* for inspection, bytes into the workspace: the RoIs float [B][K][5] = (0, x1, y1, x2, y2) of every id */
+    uint64_t roi_planes_offset; /* ... and RoIAlign's output, uint16 bf16 planes [P][B][cap][49][256] (channels last) */
+} ph_assoc_geometry;
+size_t ph_assoc_plan_workspace_bytes(const ph_assoc_cfg* cfg);      /* 0 on a bad cfg */
+int ph_assoc_plan_create(const ph_assoc_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_assoc_plan** out);
+int ph_assoc_plan_info(const ph_assoc_plan* plan, ph_assoc_geometry* out);
+void ph_assoc_plan_destroy(ph_assoc_plan* plan);
+
+/* ---- one call for B frames, launches only.
+ *   pan            int32 [B][Ho][Wo]         ph_panoptic_merge's id maps (ids 0 .. K)
+ *   seg_records    int32 [B][1 + 5 K]        ph_panoptic_merge's records: nseg | seg[K][4] | scores[K]
+ *   levels[l]      float [B][256][h_l][w_l]  the FPN levels, frame b at levels[l] + b * level_stride[l] (elements)
+ *   sem_out        uint8 [B][Ho][Wo]         get_semantic_seg: the label of every pixel's segment, void outside
+ *   things_out     int32 [B][2 + 7 cap]      per frame: nthing | seg_id[cap] | label[cap] | box[cap][5] (fp32 bits: the extent box
+ *                                            x1, y1, x2, y2 and the score) | overflow -- the thing segments in the records' order
+ *                                            (panoptic.segments_from_records, then video.things_for_tracking); unused rows are zero;
+ *                                            a frame with more than cap things keeps the first cap and sets overflow = 1
+ *   embeds_out     float [B][cap][256]       the track embeddings of rows < nthing; the other rows are not written
+ * Sequence: k_assoc_things (the tables and the semantic look-up tables), k_assoc_paint (sem_out: it needs nothing from the tracker,
+ * so a caller can start its download at once), the four box kernels of ph_segment_boxes with the frame in blockIdx.y and nseg = K, a
+ * gather of the things' extent boxes, then RoIAlign, the split-K GEMMs and the GroupNorm kernel in their device-count forms: grids
+ * sized for cap RoIs per frame, every workgroup reading its frame's nthing and returning when it lies beyond it. */
+typedef struct {
+    const int32_t* pan;
+    const int32_t* seg_records;
+    const float* levels[4];
+    int64_t level_stride[4];
+    uint8_t* sem_out;
+    int32_t* things_out;
+    float* embeds_out;
+    const uint16_t* roi_planes; /* NULL, or the caller's own RoI features as bf16 planes [P][B][cap][49][256]: RoIAlign is skipped and
+                                   the track head reads these (rows < nthing of every frame) */
+} ph_assoc_io;
+int ph_assoc_plan_run(ph_assoc_plan* plan, const ph_assoc_io* io, void* stream);
+
+/* ---- the ONE stateful, synchronising call of the plan: the tracker and the track-id maps behind ph_assoc_plan_run on the same stream.
+ * It copies the B things tables to `host_staging` (pinned host memory of ph_assoc_geometry.staging_bytes), SYNCHRONISES the stream
+ * once, refuses a frame whose overflow word is set (PH_EUNSUPPORTED), calls ph_tracker_match_frames with the device embedding rows
+ * (which synchronises per non-empty frame itself; frames without things are skipped and do not advance the frame counter), forms
+ * each frame's track look-up table as VideoAssociator.step_device does -- ids + 1, negatives to 0, painted in segment order onto the
+ * ids in the order the tracker returns them (the reference's quirk, polyphonic_former_video.py:403) -- uploads the tables and
+ * launches k_assoc_paint's float64 form.  It does not wait for that launch.
+ *   track_out      double [B][Ho][Wo] on the device
+ *   ids_host_out   int64 [B][cap] on the host, nullable: the value painted onto thing j of frame b (0 beyond nthing)
+ * Returns the number of frames matched (the caller advances its frame counter by it), or a negative error. */
+int ph_assoc_plan_match(ph_assoc_plan* plan, ph_tracker* tracker, const int32_t* pan, const int32_t* things_dev, const float* embeds_dev,
+                        void* host_staging, size_t staging_bytes, int64_t first_frame_id, double* track_out, int64_t* ids_host_out,
+                        void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -106,6 +106,34 @@ class NeckIO(C.Structure):
     _fields_ = [("feats", C.c_void_p * 4), ("posenc", C.c_void_p), ("out_planes", C.c_void_p * 3), ("out_f32", C.c_void_p * 3)]
 
 
+# the native association plan (polyhead.h ph_track_cfg .. ph_assoc_plan_match)
+PH_TRACK_MAX_CONVS = 8
+PH_TPACK_FC, PH_TPACK_FC_B, PH_TPACK_EMB, PH_TPACK_EMB_B, PH_TPACK_COUNT = 24, 25, 26, 27, 28     # conv i, gamma 8 + i, beta 16 + i
+
+
+class TrackCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_convs", "fc_out_channels", "embed_channels", "groups", "prec")] + [("eps", C.c_float)]
+
+
+class TrackLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * PH_TPACK_COUNT), ("bytes", C.c_uint64 * PH_TPACK_COUNT)]
+
+
+class AssocCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "Ho", "Wo", "K", "max_things", "num_thing_classes", "num_stuff_classes", "nlev")] + \
+        [("h", C.c_int32 * 4), ("w", C.c_int32 * 4), ("inv_stride", C.c_float * 4), ("finest_scale", C.c_float), ("track", TrackCfg)]
+
+
+class AssocGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("things_words", "P", "conv_splits", "conv_steps", "fc_splits", "fc_steps", "emb_splits",
+                                          "emb_steps", "vec8", "reserved")] + [(n, C.c_uint64) for n in ("staging_bytes", "rois_offset", "roi_planes_offset")]
+
+
+class AssocIO(C.Structure):
+    _fields_ = [("pan", C.c_void_p), ("seg_records", C.c_void_p), ("levels", C.c_void_p * 4), ("level_stride", C.c_int64 * 4),
+                ("sem_out", C.c_void_p), ("things_out", C.c_void_p), ("embeds_out", C.c_void_p), ("roi_planes", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
@@ -266,6 +294,17 @@ SIGNATURES = {
     "ph_neck_plan_run": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
     "ph_neck_plan_run_level": (C.c_int, [_P, _I, C.POINTER(NeckIO), _P]),
     "ph_neck_plan_run_outputs": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
+    "ph_track_param_name": (C.c_char_p, [C.POINTER(TrackCfg), _I]),
+    "ph_track_param_numel": (C.c_int64, [C.POINTER(TrackCfg), _I]),
+    "ph_track_pack_bytes": (C.c_size_t, [C.POINTER(TrackCfg)]),
+    "ph_track_pack_layout": (C.c_int, [C.POINTER(TrackCfg), C.POINTER(TrackLayout)]),
+    "ph_track_pack": (C.c_int, [C.POINTER(TrackCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_assoc_plan_workspace_bytes": (C.c_size_t, [C.POINTER(AssocCfg)]),
+    "ph_assoc_plan_create": (C.c_int, [C.POINTER(AssocCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_assoc_plan_info": (C.c_int, [_P, C.POINTER(AssocGeometry)]),
+    "ph_assoc_plan_destroy": (None, [_P]),
+    "ph_assoc_plan_run": (C.c_int, [_P, C.POINTER(AssocIO), _P]),
+    "ph_assoc_plan_match": (C.c_int, [_P, _P, _P, _P, _P, _P, _Z, _L, _P, _P, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

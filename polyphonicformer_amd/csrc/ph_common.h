@@ -128,6 +128,21 @@ int ph_neck_out_convs_k(const PhKheadKnobs& kn, const uint16_t* in_planes, int i
                         uint16_t* out_planes2, float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace,
                         size_t workspace_bytes, int B, int64_t HW, int prec, void* stream);
 
+// device-count forms of the association step's kernels (ph_track.hip) for the native association plan (ph_assocplan.hip): B frames per
+// launch, the grids sized for `cap` RoIs per frame, every workgroup reading its frame's count from the things tables on the device
+// (int32 [B][words], word 0 = the count, words 1 .. cap = the segment ids) and returning when it lies beyond it.  The public entry
+// points are the same kernels without the count.
+struct PhThings { const int32_t* tab = nullptr; int words = 0; int cap = 0; };
+void ph_gemm_split(int M, int N, int K, int& S, int& steps);      // ph_gemm_rows_splitk's split of (M, N, K)
+int ph_segment_boxes_b(const char* fn, const int32_t* pan, int B, int H, int W, int nseg, float* rois, float* ext_boxes, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int ph_roi_align_fpn_cnt(const float* const* feats, const int32_t* hw, const float* scales, const int64_t* frame_strides, int nlev,
+                         const float* rois, int nseg, PhThings th, int B, float finest_scale, uint16_t* out_cl, int prec, void* stream);
+int ph_gemm_rows_splitk_cnt(const uint16_t* X, int im2col7, const uint16_t* Wp, int64_t w_plane_elems, const float* bias, int relu, float* Yf,
+                            uint16_t* Yp, int M, int N, int K, int prec, PhThings th, int rows_per, int B, void* workspace, void* stream);
+int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int groups, float eps, uint16_t* out, PhThings th, int B,
+                      int prec, void* stream);
+
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects
 // it for fp32 -> __bf16 conversions.

@@ -17,6 +17,8 @@ constexpr int SEG_LDS_MAX = 1024;          // segments per id map this path hand
 // VEC consecutive pixels of one image row per thread (VEC = 8 when W % 8 == 0: two 16-byte loads); a run that lies inside one
 // segment -- nearly all of them -- is added as ONE record (count VEC, VEC * row, the arithmetic series of its columns, its end
 // points), so the atomics per pixel drop by VEC; runs that straddle a boundary fall back to per-pixel updates.
+// Batched form (the association plan, ph_segment_boxes_b): blockIdx.y is the frame; every array is [B][nseg][.] and the maps [B][H][W],
+// so a frame's arithmetic is the single-frame launch's (gridDim.y == 1).
 struct SegAcc {
     unsigned int* lst; int* lmin; int* lmax; int nl;
     unsigned long long* st; int* emin; int* emax;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(256) void k_seg_stats(const int* __restrict__ pan, 
                                                    unsigned long long* __restrict__ st, int* __restrict__ emin, int* __restrict__ emax) {
     extern __shared__ unsigned int lst[];          // [nl][3] count, sum_row, sum_col | [nl][2] min | [nl][2] max
     const int nl = nseg < SEG_LDS_MAX ? nseg : SEG_LDS_MAX;
+    pan += (int64_t)blockIdx.y * H * W; st += (int64_t)blockIdx.y * 3 * nseg; emin += (int64_t)blockIdx.y * 2 * nseg; emax += (int64_t)blockIdx.y * 2 * nseg;
     int* lmin = (int*)(lst + 3 * nl);
     int* lmax = lmin + 2 * nl;
     for (int k = threadIdx.x; k < 3 * nl; k += blockDim.x) lst[k] = 0u;
@@ -91,6 +94,7 @@ __global__ __launch_bounds__(256) void k_seg_absdev(const int* __restrict__ pan,
                                                     const unsigned long long* __restrict__ st, double* __restrict__ dev) {
     extern __shared__ double ldev[];               // [nl][2]
     const int nl = nseg < SEG_LDS_MAX ? nseg : SEG_LDS_MAX;
+    pan += (int64_t)blockIdx.y * H * W; st += (int64_t)blockIdx.y * 3 * nseg; dev += (int64_t)blockIdx.y * 2 * nseg;
     for (int k = threadIdx.x; k < 2 * nl; k += blockDim.x) ldev[k] = 0.0;
     __syncthreads();
     const int64_t nrun = (int64_t)H * W / VEC;
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(256) void k_seg_absdev(const int* __restrict__ pan,
 __global__ void k_seg_init(unsigned long long* __restrict__ st, double* __restrict__ dev, int* __restrict__ emin, int* __restrict__ emax, int nseg) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
+    st += (int64_t)blockIdx.y * 3 * nseg; dev += (int64_t)blockIdx.y * 2 * nseg; emin += (int64_t)blockIdx.y * 2 * nseg; emax += (int64_t)blockIdx.y * 2 * nseg;
     st[s * 3] = st[s * 3 + 1] = st[s * 3 + 2] = 0ull;
     dev[s * 2] = dev[s * 2 + 1] = 0.0;
     emin[s * 2] = emin[s * 2 + 1] = 0x7f7f7f7f;      // > any coordinate
@@ -150,6 +155,8 @@ __global__ void k_seg_boxes(const unsigned long long* __restrict__ st, const int
                             int nseg, float* __restrict__ rois, float* __restrict__ ext_boxes) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= nseg) return;
+    st += (int64_t)blockIdx.y * 3 * nseg; dev += (int64_t)blockIdx.y * 2 * nseg; emin += (int64_t)blockIdx.y * 2 * nseg; emax += (int64_t)blockIdx.y * 2 * nseg;
+    rois += (int64_t)blockIdx.y * 5 * nseg; ext_boxes += (int64_t)blockIdx.y * 4 * nseg;
     const double n = (double)st[s * 3];
     if (n == 0) {          // empty mask: [0,0,0,0] (video/utils.py:75) and (-1,-1,10,10) (funcs/utils.py:19)
         for (int k = 0; k < 5; ++k) rois[s * 5 + k] = 0.f;
@@ -173,40 +180,51 @@ extern "C" size_t ph_segment_boxes_workspace_bytes(int nseg) {
     return (size_t)nseg * (3 * sizeof(unsigned long long) + 4 * sizeof(int) + 2 * sizeof(double));
 }
 
-extern "C" int ph_segment_boxes(const int32_t* pan, int H, int W, int nseg, float* rois, float* ext_boxes, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-    PH_CHECK_ARG(pan && rois && ext_boxes && workspace && H > 0 && W > 0 && nseg > 0, "bad pointer or size");
-    PH_CHECK_ARG(workspace_bytes >= ph_segment_boxes_workspace_bytes(nseg), "workspace too small");
+// B frames in one launch per kernel: pan [B][H][W], rois [B][nseg][5], ext_boxes [B][nseg][4], workspace B times the single frame's,
+// laid out st [B][nseg][3] | dev [B][nseg][2] | emin [B][nseg][2] | emax [B][nseg][2].  grid.x and the vector width follow the
+// single-frame rule, so with B == 1 this IS the single-frame call.
+int ph_segment_boxes_b(const char* fn, const int32_t* pan, int B, int H, int W, int nseg, float* rois, float* ext_boxes, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+    PH_CHECK_ARG_AS(fn, pan && rois && ext_boxes && workspace && B > 0 && H > 0 && W > 0 && nseg > 0, "bad pointer or size");
+    PH_CHECK_ARG_AS(fn, B <= 65535, "at most 65535 frames per call");
+    PH_CHECK_ARG_AS(fn, workspace_bytes >= (size_t)B * ph_segment_boxes_workspace_bytes(nseg), "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* st = (unsigned long long*)workspace;
-    double* dev = (double*)(st + 3 * nseg);
-    int* emin = (int*)(dev + 2 * nseg);
-    int* emax = emin + 2 * nseg;
-    // one kernel instead of three memset nodes (a captured hipMemsetAsync node misbehaves on replay, see ph_khead1.hip)
-    hipLaunchKernelGGL(k_seg_init, dim3((nseg + 63) / 64), dim3(64), 0, s, st, dev, emin, emax, nseg);
+    double* dev = (double*)(st + (size_t)B * 3 * nseg);
+    int* emin = (int*)(dev + (size_t)B * 2 * nseg);
+    int* emax = emin + (size_t)B * 2 * nseg;
     const int64_t npx = (int64_t)H * W;
     const int vec = (W % 8 == 0 && ((uintptr_t)pan & 15) == 0) ? 8 : 1;
     const int64_t nrun = npx / vec;
     int grid = (int)((nrun + 255) / 256 < 2048 ? (nrun + 255) / 256 : 2048);
     // a block's coordinate sums are 32-bit in LDS: pixels per block x largest coordinate must stay below 2^32
-    PH_CHECK_ARG(((nrun + grid - 1) / grid + 256) * vec * (int64_t)(H > W ? H : W) < (1ll << 32), "id map too large");
+    PH_CHECK_ARG_AS(fn, ((nrun + grid - 1) / grid + 256) * vec * (int64_t)(H > W ? H : W) < (1ll << 32), "id map too large");
+    // one kernel instead of three memset nodes (a captured hipMemsetAsync node misbehaves on replay, see ph_khead1.hip)
+    hipLaunchKernelGGL(k_seg_init, dim3((nseg + 63) / 64, B), dim3(64), 0, s, st, dev, emin, emax, nseg);
     const int nl = nseg < SEG_LDS_MAX ? nseg : SEG_LDS_MAX;
     if (vec == 8) {
-        hipLaunchKernelGGL(k_seg_stats<8>, dim3(grid), dim3(256), (size_t)nl * 7 * sizeof(int), s, pan, H, W, nseg, st, emin, emax);
-        hipLaunchKernelGGL(k_seg_absdev<8>, dim3(grid), dim3(256), (size_t)nl * 2 * sizeof(double), s, pan, H, W, nseg, st, dev);
+        hipLaunchKernelGGL(k_seg_stats<8>, dim3(grid, B), dim3(256), (size_t)nl * 7 * sizeof(int), s, pan, H, W, nseg, st, emin, emax);
+        hipLaunchKernelGGL(k_seg_absdev<8>, dim3(grid, B), dim3(256), (size_t)nl * 2 * sizeof(double), s, pan, H, W, nseg, st, dev);
     } else {
-        hipLaunchKernelGGL(k_seg_stats<1>, dim3(grid), dim3(256), (size_t)nl * 7 * sizeof(int), s, pan, H, W, nseg, st, emin, emax);
-        hipLaunchKernelGGL(k_seg_absdev<1>, dim3(grid), dim3(256), (size_t)nl * 2 * sizeof(double), s, pan, H, W, nseg, st, dev);
+        hipLaunchKernelGGL(k_seg_stats<1>, dim3(grid, B), dim3(256), (size_t)nl * 7 * sizeof(int), s, pan, H, W, nseg, st, emin, emax);
+        hipLaunchKernelGGL(k_seg_absdev<1>, dim3(grid, B), dim3(256), (size_t)nl * 2 * sizeof(double), s, pan, H, W, nseg, st, dev);
     }
-    hipLaunchKernelGGL(k_seg_boxes, dim3((nseg + 63) / 64), dim3(64), 0, s, st, emin, emax, dev, nseg, rois, ext_boxes);
-    PH_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_seg_boxes, dim3((nseg + 63) / 64, B), dim3(64), 0, s, st, emin, emax, dev, nseg, rois, ext_boxes);
+    hipError_t e_ = hipGetLastError();
+    if (e_ != hipSuccess) { ph_set_error("%s: launch failed: %s", fn, hipGetErrorString(e_)); return PH_ELAUNCH; }
     return PH_OK;
+}
+
+extern "C" int ph_segment_boxes(const int32_t* pan, int H, int W, int nseg, float* rois, float* ext_boxes, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    return ph_segment_boxes_b("ph_segment_boxes", pan, 1, H, W, nseg, rois, ext_boxes, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // RoIAlign over an FPN.  out_cl: bf16 planes [P][n][49][256] (channels last, what the track head consumes);
 // out_f32 (optional): [n][256][7][7] like the reference's roi_feats.
 struct FpnArgs { const float* feat[4]; int H[4], W[4]; float scale[4]; int nlev; };
+struct PhFrameStrides { int64_t s[4]; };
 
 __device__ __forceinline__ float roi_bilinear(const float* __restrict__ f, int H, int W, float y, float x) {
     if (y < -1.f || y > (float)H || x < -1.f || x > (float)W) return 0.f;
@@ -218,19 +236,31 @@ __device__ __forceinline__ float roi_bilinear(const float* __restrict__ f, int H
     return hy * hx * f[yl * W + xl] + hy * lx * f[yl * W + xh] + ly * hx * f[yh * W + xl] + ly * lx * f[yh * W + xh];
 }
 
-template <int PA>
+// CNT (the association plan): the grid is (cap, 49, B); frame b = blockIdx.z has things.tab[b * words] RoIs, RoI i is row seg_id[i] - 1
+// of the frame's rois [nseg][5] (seg_id = the things table's second field), the levels are [B][256][H][W] with per-level frame
+// strides, the output planes [P][B][cap][49][256]; a workgroup beyond the frame's count returns before any other load
+template <int PA, bool CNT>
 __global__ __launch_bounds__(256) void k_roi_align_fpn(FpnArgs a, const float* __restrict__ rois, int n, float finest,
-                                                        uint16_t* __restrict__ out_cl, float* __restrict__ out_f32) {
+                                                        uint16_t* __restrict__ out_cl, float* __restrict__ out_f32, PhThings th,
+                                                        PhFrameStrides fs, int nseg) {
     // one block per (RoI, output bin), one thread per channel: 49 n blocks of 16 scattered loads per thread (the planes are NCHW, a
     // wave's 64 channels are 64 cache lines per tap) instead of n blocks walking 784 of them -- same arithmetic per bin
-    const int roi = blockIdx.x, c = threadIdx.x, ph = blockIdx.y / 7, pw = blockIdx.y - 7 * (blockIdx.y / 7);
+    int roi = blockIdx.x;
+    const int c = threadIdx.x, ph = blockIdx.y / 7, pw = blockIdx.y - 7 * (blockIdx.y / 7);
     const float* r = rois + roi * 5;
+    if constexpr (CNT) {
+        const int32_t* tab = th.tab + (int64_t)blockIdx.z * th.words;
+        if (roi >= tab[0]) return;
+        r = rois + ((int64_t)blockIdx.z * nseg + (tab[1 + roi] - 1)) * 5;
+        roi += blockIdx.z * th.cap;                 // row of the [B * cap] output
+    }
     const float sc = sqrtf((r[3] - r[1]) * (r[4] - r[2]));
     int lv = (int)floorf(log2f(sc / finest + 1e-6f));
     lv = lv < 0 ? 0 : (lv > a.nlev - 1 ? a.nlev - 1 : lv);
     const float s = a.scale[lv];
     const int H = a.H[lv], W = a.W[lv];
     const float* f = a.feat[lv] + (int64_t)c * H * W;
+    if constexpr (CNT) f += (int64_t)blockIdx.z * fs.s[lv];
     const float x1 = r[1] * s - 0.5f, y1 = r[2] * s - 0.5f, x2 = r[3] * s - 0.5f, y2 = r[4] * s - 0.5f;
     const float bw = (x2 - x1) / 7.f, bh = (y2 - y1) / 7.f;
     const int64_t plane = (int64_t)n * 49 * 256;
@@ -258,8 +288,23 @@ extern "C" int ph_roi_align_fpn(const float* const* feats, const int32_t* hw /*[
     FpnArgs a;
     a.nlev = nlev;
     for (int l = 0; l < nlev; ++l) { a.feat[l] = feats[l]; a.H[l] = hw[2 * l]; a.W[l] = hw[2 * l + 1]; a.scale[l] = scales[l]; }
-    if (prec == PH_PREC_BF16) hipLaunchKernelGGL(k_roi_align_fpn<1>, dim3(n, 49), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, out_f32);
-    else hipLaunchKernelGGL(k_roi_align_fpn<2>, dim3(n, 49), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, out_f32);
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_roi_align_fpn<1, false>), dim3(n, 49), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, out_f32, PhThings{}, PhFrameStrides{}, 0);
+    else hipLaunchKernelGGL((k_roi_align_fpn<2, false>), dim3(n, 49), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, out_f32, PhThings{}, PhFrameStrides{}, 0);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+// device-count form: arguments checked by the caller (ph_assocplan.hip).  out_cl [P][B][cap][49][256]
+int ph_roi_align_fpn_cnt(const float* const* feats, const int32_t* hw, const float* scales, const int64_t* frame_strides, int nlev,
+                         const float* rois /*[B][nseg][5]*/, int nseg, PhThings th, int B, float finest_scale, uint16_t* out_cl, int prec,
+                         void* stream) {
+    FpnArgs a;
+    PhFrameStrides fs;
+    a.nlev = nlev;
+    for (int l = 0; l < nlev; ++l) { a.feat[l] = feats[l]; a.H[l] = hw[2 * l]; a.W[l] = hw[2 * l + 1]; a.scale[l] = scales[l]; fs.s[l] = frame_strides[l]; }
+    const int n = B * th.cap;                           // rows of a plane
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_roi_align_fpn<1, true>), dim3(th.cap, 49, B), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, (float*)nullptr, th, fs, nseg);
+    else hipLaunchKernelGGL((k_roi_align_fpn<2, true>), dim3(th.cap, 49, B), dim3(256), 0, (hipStream_t)stream, a, rois, n, finest_scale, out_cl, (float*)nullptr, th, fs, nseg);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
@@ -334,11 +379,26 @@ extern "C" int ph_gemm_rows(const uint16_t* X, const uint16_t* Wp, int64_t w_pla
 // channels-last [P][n][49][256] maps, k = tap * 256 + channel) instead of through a materialised [M][2304] matrix.  Every split
 // accumulates its k-steps in order into part[z][M][N]; k_gemm_finish adds the splits in order: deterministic, and per element the same
 // products as k_gemm_rows in a different association.  The split depends on (M, N, K) only.
-template <int PA, bool IM2COL>
+// CNT (the association plan): B frames of M rows CAPACITY each in one launch -- blockIdx.x = frame * row tiles + row tile; frame b
+// has Mv = rows_per * things.tab[b * words] valid rows (rows_per: 49 for the convs, 1 for the fc layers); X is [P][B][M][.], part
+// [B][S][M][N].  A row tile at or beyond Mv returns before any other load.  Split, k order and row tiling are those of the
+// single call with this M, so an element's value is the single call's whatever B and the other frames' counts are.
+template <int PA, bool IM2COL, bool CNT>
 __global__ __launch_bounds__(256) void k_gemm_rows_sk(const uint16_t* __restrict__ X, int64_t x_plane, const uint16_t* __restrict__ Wp,
-                                                      int64_t w_plane, float* __restrict__ part, int M, int N, int K, int steps) {
+                                                      int64_t w_plane, float* __restrict__ part, int M, int N, int K, int steps,
+                                                      PhThings th, int rows_per) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
-    const int row0 = blockIdx.x * 32, ct = blockIdx.y * 4 + wave;
+    int row0 = blockIdx.x * 32;
+    const int ct = blockIdx.y * 4 + wave;
+    const int Mcap = M;
+    if constexpr (CNT) {
+        const int tiles = (Mcap + 31) / 32, b = blockIdx.x / tiles;
+        row0 = (blockIdx.x - b * tiles) * 32;
+        M = th.tab[(int64_t)b * th.words] * rows_per;
+        if (row0 >= M) return;
+        X += (int64_t)b * Mcap * (IM2COL ? 256 : K);
+        part += (int64_t)b * gridDim.z * Mcap * N;
+    }
     if (ct * 16 >= N) return;
     const int KS = K / 32, ks0 = blockIdx.z * steps, ks1 = ks0 + steps < KS ? ks0 + steps : KS;
     f32x4_t acc[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};
@@ -392,7 +452,7 @@ __global__ __launch_bounds__(256) void k_gemm_rows_sk(const uint16_t* __restrict
             }
         }
     }
-    float* out = part + (int64_t)blockIdx.z * M * N;
+    float* out = part + (int64_t)blockIdx.z * Mcap * N;
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
@@ -402,13 +462,22 @@ __global__ __launch_bounds__(256) void k_gemm_rows_sk(const uint16_t* __restrict
         }
 }
 
-template <int PA>
+// CNT: frame = blockIdx.y; part [B][S][M][N], Yf [B][M][N], Yp [P][B][M][N] with M the capacity; the frame's valid rows only
+template <int PA, bool CNT>
 __global__ __launch_bounds__(256) void k_gemm_finish(const float* __restrict__ part, int S, const float* __restrict__ bias, int relu,
-                                                     float* __restrict__ Yf, uint16_t* __restrict__ Yp, int64_t y_plane, int M, int N) {
-    const int64_t total = (int64_t)M * N;
+                                                     float* __restrict__ Yf, uint16_t* __restrict__ Yp, int64_t y_plane, int M, int N,
+                                                     PhThings th, int rows_per) {
+    const int64_t pstride = (int64_t)M * N;
+    int64_t total = pstride;
+    if constexpr (CNT) {
+        total = (int64_t)th.tab[(int64_t)blockIdx.y * th.words] * rows_per * N;
+        part += (int64_t)blockIdx.y * S * pstride;
+        if (Yf) Yf += (int64_t)blockIdx.y * pstride;
+        if (Yp) Yp += (int64_t)blockIdx.y * pstride;
+    }
     for (int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         float v = part[idx];
-        for (int z = 1; z < S; ++z) v += part[(int64_t)z * total + idx];
+        for (int z = 1; z < S; ++z) v += part[(int64_t)z * pstride + idx];
         if (bias) v += bias[idx % N];
         if (relu) v = fmaxf(v, 0.f);
         if (Yf) Yf[idx] = v;
@@ -421,7 +490,7 @@ __global__ __launch_bounds__(256) void k_gemm_finish(const float* __restrict__ p
     }
 }
 
-static void gemm_split(int M, int N, int K, int& S, int& steps) {
+void ph_gemm_split(int M, int N, int K, int& S, int& steps) {
     const int64_t tiles = (int64_t)((M + 31) / 32) * ((N / 16 + 3) / 4);
     const int KS = K / 32;
     steps = 8;
@@ -432,7 +501,7 @@ static void gemm_split(int M, int N, int K, int& S, int& steps) {
 extern "C" size_t ph_gemm_rows_workspace_bytes(int M, int N, int K) {
     if (M <= 0 || N <= 0 || K < 32) return 0;
     int S, steps;
-    gemm_split(M, N, K, S, steps);
+    ph_gemm_split(M, N, K, S, steps);
     return (size_t)S * M * N * sizeof(float);
 }
 
@@ -445,22 +514,50 @@ extern "C" int ph_gemm_rows_splitk(const uint16_t* X, int im2col7, const uint16_
     PH_CHECK_ARG(!im2col7 || (K == 2304 && M % 49 == 0), "im2col7: X is [P][M / 49][49][256] and K = 9 * 256");
     if (workspace_bytes < ph_gemm_rows_workspace_bytes(M, N, K)) { ph_set_error("ph_gemm_rows_splitk: workspace too small"); return PH_EWORKSPACE; }
     int S, steps;
-    gemm_split(M, N, K, S, steps);
+    ph_gemm_split(M, N, K, S, steps);
     const dim3 grid((M + 31) / 32, (N / 16 + 3) / 4, S);
     hipStream_t s = (hipStream_t)stream;
     float* part = (float*)workspace;
     const int64_t x_plane = im2col7 ? (int64_t)M * 256 : (int64_t)M * K;
+    const PhThings th{};
     if (prec == PH_PREC_BF16) {
-        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<1, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps);
-        else hipLaunchKernelGGL((k_gemm_rows_sk<1, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps);
+        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<1, true, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, 0);
+        else hipLaunchKernelGGL((k_gemm_rows_sk<1, false, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, 0);
     } else {
-        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<2, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps);
-        else hipLaunchKernelGGL((k_gemm_rows_sk<2, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps);
+        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<2, true, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, 0);
+        else hipLaunchKernelGGL((k_gemm_rows_sk<2, false, false>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, 0);
     }
     const int64_t total = (int64_t)M * N;
     const int fgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    if (prec == PH_PREC_BF16) hipLaunchKernelGGL(k_gemm_finish<1>, dim3(fgrid), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, total, M, N);
-    else hipLaunchKernelGGL(k_gemm_finish<2>, dim3(fgrid), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, total, M, N);
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_gemm_finish<1, false>), dim3(fgrid), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, total, M, N, th, 0);
+    else hipLaunchKernelGGL((k_gemm_finish<2, false>), dim3(fgrid), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, total, M, N, th, 0);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+// device-count form of ph_gemm_rows_splitk for B frames of M rows capacity each (arguments checked by the caller, ph_assocplan.hip):
+// X [P][B][M][.], Yf [B][M][N], Yp [P][B][M][N], workspace B * ph_gemm_rows_workspace_bytes(M, N, K).  The split is the single
+// call's for (M, N, K): it depends neither on B nor on the device counts.
+int ph_gemm_rows_splitk_cnt(const uint16_t* X, int im2col7, const uint16_t* Wp, int64_t w_plane_elems, const float* bias, int relu, float* Yf,
+                            uint16_t* Yp, int M, int N, int K, int prec, PhThings th, int rows_per, int B, void* workspace, void* stream) {
+    int S, steps;
+    ph_gemm_split(M, N, K, S, steps);
+    const int tiles = (M + 31) / 32;
+    const dim3 grid(tiles * B, (N / 16 + 3) / 4, S);
+    hipStream_t s = (hipStream_t)stream;
+    float* part = (float*)workspace;
+    const int64_t x_plane = (int64_t)B * (im2col7 ? (int64_t)M * 256 : (int64_t)M * K);
+    if (prec == PH_PREC_BF16) {
+        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<1, true, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, rows_per);
+        else hipLaunchKernelGGL((k_gemm_rows_sk<1, false, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, rows_per);
+    } else {
+        if (im2col7) hipLaunchKernelGGL((k_gemm_rows_sk<2, true, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, rows_per);
+        else hipLaunchKernelGGL((k_gemm_rows_sk<2, false, true>), grid, dim3(256), 0, s, X, x_plane, Wp, w_plane_elems, part, M, N, K, steps, th, rows_per);
+    }
+    const int64_t total = (int64_t)M * N, y_plane = (int64_t)B * total;
+    const int fgrid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_gemm_finish<1, true>), dim3(fgrid, B), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, y_plane, M, N, th, rows_per);
+    else hipLaunchKernelGGL((k_gemm_finish<2, true>), dim3(fgrid, B), dim3(256), 0, s, part, S, bias, relu, Yf, Yp, y_plane, M, N, th, rows_per);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
@@ -485,11 +582,18 @@ __global__ __launch_bounds__(256) void k_im2col7(const uint16_t* __restrict__ in
 }
 
 // per-sample GroupNorm (groups of 256/groups channels over the 49 positions) + ReLU on fp32 [n*49][256] -> bf16 planes
-template <int PA>
+// CNT (the association plan): grid (cap, B); y [B][cap * 49][256], out [P][B][cap][49][256] (n = B * cap rows per plane); a sample
+// at or beyond the frame's count returns before any other load
+template <int PA, bool CNT>
 __global__ __launch_bounds__(256) void k_gn_relu_cl(const float* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    int groups, float eps, uint16_t* __restrict__ out, int n) {
+                                                    int groups, float eps, uint16_t* __restrict__ out, int n, PhThings th) {
     __shared__ float red[2][256];
-    const int s = blockIdx.x, c = threadIdx.x, cpg = 256 / groups;
+    int s = blockIdx.x;
+    const int c = threadIdx.x, cpg = 256 / groups;
+    if constexpr (CNT) {
+        if (s >= th.tab[(int64_t)blockIdx.y * th.words]) return;
+        s += blockIdx.y * th.cap;
+    }
     float v[49];
     float sum = 0.f;
 #pragma unroll
@@ -533,8 +637,18 @@ extern "C" int ph_im2col7(const uint16_t* in, uint16_t* out, int n, int prec, vo
 extern "C" int ph_gn_relu_cl(const float* y, const float* gamma, const float* beta, int groups, float eps, uint16_t* out, int n,
                              int prec, void* stream) {
     PH_CHECK_ARG(y && gamma && beta && out && n > 0 && groups > 0 && 256 % groups == 0, "bad pointer or size");
-    if (prec == PH_PREC_BF16) hipLaunchKernelGGL(k_gn_relu_cl<1>, dim3(n), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n);
-    else hipLaunchKernelGGL(k_gn_relu_cl<2>, dim3(n), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n);
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_gn_relu_cl<1, false>), dim3(n), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n, PhThings{});
+    else hipLaunchKernelGGL((k_gn_relu_cl<2, false>), dim3(n), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n, PhThings{});
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+// device-count form (arguments checked by the caller, ph_assocplan.hip)
+int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int groups, float eps, uint16_t* out, PhThings th, int B,
+                      int prec, void* stream) {
+    const int n = B * th.cap;
+    if (prec == PH_PREC_BF16) hipLaunchKernelGGL((k_gn_relu_cl<1, true>), dim3(th.cap, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n, th);
+    else hipLaunchKernelGGL((k_gn_relu_cl<2, true>), dim3(th.cap, B), dim3(256), 0, (hipStream_t)stream, y, gamma, beta, groups, eps, out, n, th);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }

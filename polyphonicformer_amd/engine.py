@@ -1473,3 +1473,149 @@ class DualDecodePlan:
     def outputs(self):
         o = [h.outputs() for h in self.halves]
         return {k: (None if o[0][k] is None else torch.cat([oi[k] for oi in o], 0)) for k in o[0]}
+
+
+# ---- the native association plan (include/polyhead.h ph_track_cfg .. ph_assoc_plan_match; csrc/ph_assocplan.hip) -------------------
+def native_track_cfg(head, prec=None):
+    """a ph_track_cfg of a QuasiDenseMaskEmbedHeadGTMask (or of a dict with its sizes); `prec`: a precision name or PH_PREC_* code,
+    default the head's own"""
+    get = (lambda k, d=None: head.get(k, d)) if isinstance(head, dict) else (lambda k, d=None: getattr(head, k, d))
+    if prec is None:
+        prec = get("precision", "fp32")
+    return _lib.TrackCfg(num_convs=int(get("num_convs", 4)), fc_out_channels=int(get("fc_out_channels", 1024)),
+                         embed_channels=int(get("embed_channels", 256)), groups=int(get("groups", 32)),
+                         prec=PREC[prec] if isinstance(prec, str) else int(prec), eps=0.0)
+
+
+def native_assoc_cfg(B, out_hw, K, max_things, num_thing_classes, num_stuff_classes, level_shapes, track, strides=(4, 8, 16, 32),
+                     finest_scale=56.0):
+    """a ph_assoc_cfg: B frames of an (Ho, Wo) id map with K record rows and `max_things` RoIs per frame; `level_shapes`: (h, w) of
+    the FPN levels RoIAlign reads, finest first; `track`: a ph_track_cfg (`native_track_cfg`).  Reads no environment variable."""
+    L = len(level_shapes)
+    if not 1 <= L <= 4:
+        raise _lib.PolyheadError("native_assoc_cfg: 1 .. 4 FPN levels")
+    c = _lib.AssocCfg(B=B, Ho=out_hw[0], Wo=out_hw[1], K=K, max_things=max_things, num_thing_classes=num_thing_classes,
+                      num_stuff_classes=num_stuff_classes, nlev=L, finest_scale=finest_scale)
+    for l, (h, w) in enumerate(level_shapes):
+        c.h[l], c.w[l], c.inv_stride[l] = int(h), int(w), 1.0 / strides[l]
+    c.track = _lib.TrackCfg.from_buffer_copy(bytes(track))
+    return c
+
+
+class NativeTrackPack:
+    """one device buffer packed by ph_track_pack + views of its pieces under `_get_pack`'s names (the views share the buffer)"""
+
+    def __init__(self, blob, cfg):
+        lay = _lib.TrackLayout()
+        _lib.check(_lib.load().ph_track_pack_layout(C.byref(cfg), C.byref(lay)), "ph_track_pack_layout")
+        self.blob, self.cfg, self.layout = blob, _lib.TrackCfg.from_buffer_copy(bytes(cfg)), lay
+        self.prec, self.P = cfg.prec, 2 if cfg.prec == _lib.PH_PREC_SPLIT else 1
+
+        def piece(i, dtype, shape):
+            n = int(lay.bytes[i])
+            return blob[int(lay.offset[i]):int(lay.offset[i]) + n].view(dtype).reshape(shape)
+        P, F, E, n = self.P, cfg.fc_out_channels, cfg.embed_channels, cfg.num_convs
+        self.pk = dict(convs=[piece(i, torch.int16, (P, 256 * 2304)) for i in range(n)],
+                       gn=[(piece(_lib.PH_TRACK_MAX_CONVS + i, torch.float32, (256,)),
+                            piece(2 * _lib.PH_TRACK_MAX_CONVS + i, torch.float32, (256,))) for i in range(n)],
+                       fc=piece(_lib.PH_TPACK_FC, torch.int16, (P, F * 49 * 256)), fc_b=piece(_lib.PH_TPACK_FC_B, torch.float32, (F,)),
+                       emb=piece(_lib.PH_TPACK_EMB, torch.int16, (P, E * F)), emb_b=piece(_lib.PH_TPACK_EMB_B, torch.float32, (E,)),
+                       prec=self.prec, P=P)
+
+
+def native_track_pack(module, cfg, device):
+    """the track head's parameters (a QuasiDenseMaskEmbedHeadGTMask, or its state_dict) packed on the device by ph_track_pack"""
+    lib = _lib.load()
+    nbytes = lib.ph_track_pack_bytes(C.byref(cfg))
+    if nbytes == 0:
+        raise _cfg_error("ph_track_pack_bytes")
+    count = 3 * cfg.num_convs + 4
+    params, ptrs = _gather_params(module, device, count, lambda i: lib.ph_track_param_name(C.byref(cfg), i),
+                                  lambda i: lib.ph_track_param_numel(C.byref(cfg), i))
+    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.ph_track_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_track_pack")
+    return NativeTrackPack(blob, cfg)
+
+
+class NativeAssocPlan:
+    """The association step of B frames over ph_panoptic_merge's device outputs: `run` is ONE launch-only native call
+    (ph_assoc_plan_run: things tables, `sem`, boxes, RoIAlign, track embeddings -- capturable with torch.cuda.graph), `match` the one
+    synchronising call behind it (ph_assoc_plan_match: the tracker and the `track` maps).  `pack`: a NativeTrackPack; `cfg`: a
+    ph_assoc_cfg (`native_assoc_cfg`).  The outputs are this object's static tensors: the next call overwrites them."""
+
+    def __init__(self, pack, cfg, device):
+        lib, dev = _lib.load(), torch.device(device)
+        self.pack, self.device = pack, dev
+        self.cfg = _lib.AssocCfg.from_buffer_copy(bytes(cfg))
+        if bytes(self.cfg.track) != bytes(pack.cfg):
+            raise _lib.PolyheadError("NativeAssocPlan: the pack was made for another track head cfg")
+        nbytes = lib.ph_assoc_plan_workspace_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise _cfg_error("ph_assoc_plan_workspace_bytes")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
+        self._h = C.c_void_p()
+        _lib.check(lib.ph_assoc_plan_create(C.byref(self.cfg), _lib.ptr(pack.blob), _lib.ptr(self.workspace), nbytes, C.byref(self._h)),
+                   "ph_assoc_plan_create")
+        self.geometry = _lib.AssocGeometry()
+        _lib.check(lib.ph_assoc_plan_info(self._h, C.byref(self.geometry)), "ph_assoc_plan_info")
+        c = self.cfg
+        self.B, self.K, self.cap, self.words = c.B, c.K, c.max_things, self.geometry.things_words
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        self.sem, self.track = e((c.B, c.Ho, c.Wo), torch.uint8), e((c.B, c.Ho, c.Wo), torch.float64)
+        self.things, self.embeds = e((c.B, self.words), torch.int32), e((c.B, self.cap, 256), torch.float32)
+        self.staging = torch.empty((int(self.geometry.staging_bytes),), dtype=torch.uint8, pin_memory=dev.type == "cuda")
+        self.ids = torch.zeros((c.B, self.cap), dtype=torch.int64)
+        self.io = _lib.AssocIO()
+        self._keep = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and _lib._lib is not None:
+            _lib._lib.ph_assoc_plan_destroy(h)
+            self._h = C.c_void_p()
+
+    def rois(self):
+        """the RoIs of the last run, fp32 [B, K, 5] (a view of the workspace; inspection)"""
+        o = int(self.geometry.rois_offset)
+        return self.workspace[o:o + self.B * self.K * 20].view(torch.float32).reshape(self.B, self.K, 5)
+
+    def roi_planes(self):
+        """RoIAlign's output of the last run, bf16 planes as int16 [P, B, cap, 49, 256] (a view of the workspace; inspection)"""
+        o, P = int(self.geometry.roi_planes_offset), self.geometry.P
+        return self.workspace[o:o + P * self.B * self.cap * 49 * 256 * 2].view(torch.int16).reshape(P, self.B, self.cap, 49, 256)
+
+    def run(self, pan, seg_records, levels, roi_planes=None):
+        """pan int32 [B, Ho, Wo], seg_records int32 [B, 1 + 5 K], levels: fp32 [B, 256, h_l, w_l] per level, all contiguous on the
+        device -> (sem uint8 [B, Ho, Wo], things tables int32 [B, 2 + 7 cap], embeddings fp32 [B, cap, 256]); launches only.
+        `roi_planes`: the caller's RoI features, int16 [P, B, cap, 49, 256], instead of RoIAlign's"""
+        if roi_planes is not None and (roi_planes.dtype != torch.int16 or not roi_planes.is_contiguous() or
+                                       tuple(roi_planes.shape) != (self.geometry.P, self.B, self.cap, 49, 256)):
+            raise _lib.PolyheadError("NativeAssocPlan.run: roi_planes must be int16 contiguous [P, B, cap, 49, 256]")
+        self.io.roi_planes = None if roi_planes is None else roi_planes.data_ptr()
+        c, io = self.cfg, self.io
+        if pan.dtype != torch.int32 or tuple(pan.shape) != (c.B, c.Ho, c.Wo) or not pan.is_contiguous() or pan.device != self.device:
+            raise _lib.PolyheadError(f"NativeAssocPlan.run: pan must be int32 contiguous {(c.B, c.Ho, c.Wo)} on {self.device}")
+        if seg_records.dtype != torch.int32 or tuple(seg_records.shape) != (c.B, 1 + 5 * c.K) or not seg_records.is_contiguous():
+            raise _lib.PolyheadError(f"NativeAssocPlan.run: seg_records must be int32 contiguous {(c.B, 1 + 5 * c.K)}")
+        if len(levels) != c.nlev:
+            raise _lib.PolyheadError(f"NativeAssocPlan.run: {c.nlev} FPN levels expected")
+        for l, f in enumerate(levels):
+            if f.dtype != torch.float32 or not f.is_contiguous() or tuple(f.shape) != (c.B, 256, c.h[l], c.w[l]) or f.device != self.device:
+                raise _lib.PolyheadError(f"NativeAssocPlan.run: level {l} must be fp32 contiguous {(c.B, 256, c.h[l], c.w[l])} on {self.device}")
+            io.levels[l], io.level_stride[l] = f.data_ptr(), 256 * c.h[l] * c.w[l]
+        io.pan, io.seg_records = pan.data_ptr(), seg_records.data_ptr()
+        io.sem_out, io.things_out, io.embeds_out = self.sem.data_ptr(), self.things.data_ptr(), self.embeds.data_ptr()
+        self._keep = (pan, seg_records, tuple(levels), roi_planes)      # alive until the launches have run (static under graph capture)
+        _lib.check(_lib.load().ph_assoc_plan_run(self._h, C.byref(io), _lib.stream_ptr()), "ph_assoc_plan_run")
+        return self.sem, self.things, self.embeds
+
+    def match(self, tracker_handle, pan, first_frame_id):
+        """the tracker (a ph_tracker handle) and the track-id maps behind `run` on the current stream: synchronises.  Returns
+        (track float64 [B, Ho, Wo] on the device, painted ids int64 [B, cap] on the host, frames matched)"""
+        m = _lib.load().ph_assoc_plan_match(self._h, tracker_handle, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
+                                            C.c_void_p(self.staging.data_ptr()), self.staging.numel(), int(first_frame_id),
+                                            _lib.ptr(self.track), C.c_void_p(self.ids.data_ptr()), _lib.stream_ptr())
+        if m < 0:
+            _lib.check(m, "ph_assoc_plan_match")
+        return self.track, self.ids, int(m)

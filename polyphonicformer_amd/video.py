@@ -475,6 +475,55 @@ class VideoAssociator:
         self.num_thing_classes, self.num_stuff_classes, self.strides = num_thing_classes, num_stuff_classes, strides
         self.init_tracker()
 
+    native_plan, max_things = False, 100          # `use_native_plan`
+
+    def use_native_plan(self, on=True, max_things=None):
+        """`step_records` for clips whose merge left its records on the device (`panoptic.BatchMerge`): the whole step as the native
+        association plan (csrc/ph_assocplan.hip) -- one launch-only call and one synchronising tracker call for B frames, no
+        `segments_info` on the host.  Off (the default) nothing changes: `step` / `step_device` are the Python chain.
+        `max_things`: RoIs per frame the plan's launches are sized for (a frame with more is an error), at most the merge's K."""
+        self.native_plan = bool(on)
+        if max_things is not None:
+            self.max_things = int(max_things)
+        self._nplans = {}
+        return self
+
+    def _native_plan_for(self, levels, pan_dev, K):
+        from . import engine as E
+        dev = pan_dev.device
+        prec = E.PREC[self.track_head.precision]
+        ver = _lib_versions(self.track_head)
+        pk = self.__dict__.get("_npack")
+        if pk is None or pk[0] != (prec, str(dev), ver):
+            tc = E.native_track_cfg(self.track_head)
+            pk = self._npack = ((prec, str(dev), ver), E.native_track_pack(self.track_head, tc, dev))
+            self._nplans = {}
+        B, Ho, Wo = pan_dev.shape
+        key = (B, Ho, Wo, K, tuple(tuple(f.shape[-2:]) for f in levels))
+        plan = self._nplans.get(key)
+        if plan is None:
+            cfg = E.native_assoc_cfg(B, (Ho, Wo), K, min(self.max_things, K), self.num_thing_classes, self.num_stuff_classes, key[4],
+                                     pk[1].cfg, self.strides)
+            self._nplans.clear()                     # one geometry at a time
+            plan = self._nplans[key] = E.NativeAssocPlan(pk[1], cfg, dev)
+        return plan
+
+    def step_records(self, levels, pan_dev, seg_records_dev):
+        """`step_device` for B frames from the merge's DEVICE outputs: levels fp32 [B, 256, H_l, W_l], pan_dev int32 [B, Ho, Wo],
+        seg_records_dev int32 [B, 1 + 5 K] (`ph_panoptic_merge`'s records).  Returns the (sem uint8, track float64) maps [B, Ho, Wo] on
+        the device (the plan's static outputs: the next call overwrites them).  Reads no `segments_info`; one synchronisation for the
+        tracker's boxes and labels, then the tracker's own."""
+        if not self.native_plan:
+            from . import _lib
+            raise _lib.PolyheadError("VideoAssociator.step_records needs use_native_plan(True)")
+        K = (seg_records_dev.shape[1] - 1) // 5
+        plan = self._native_plan_for(levels, pan_dev, K)
+        plan.run(pan_dev, seg_records_dev, levels)
+        handle = self.tracker._native_handle(pan_dev.device)
+        trk, _, matched = plan.match(handle, pan_dev, self.cnt)
+        self.cnt += matched
+        return plan.sem, trk
+
     def init_tracker(self):
         """polyphonic_former_video.py:59-61"""
         cfg = dict(self.tracker_cfg)
@@ -638,6 +687,11 @@ def build_video_pipeline_from_config(cfg):
         raise NotImplementedError(f"bbox_roi_extractor {ext!r}: libpolyhead implements SingleRoIExtractor(RoIAlign 7x7, sampling_ratio=2, 256 ch)")
     th = build_head(deep_cfg(model["track_head"]))
     return VideoFramePipeline(rpn_head, roi_head, th, deep_cfg(model["tracker"]), strides=tuple(ext["featmap_strides"]))
+
+
+def _lib_versions(module):
+    from . import _lib
+    return _lib.param_versions(module)
 
 
 def _h2d(values, dtype, dev):
