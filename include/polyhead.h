@@ -1181,6 +1181,59 @@ int ph_assoc_plan_match(ph_assoc_plan* plan, ph_tracker* tracker, const int32_t*
                         void* host_staging, size_t staging_bytes, int64_t first_frame_id, double* track_out, int64_t* ids_host_out,
                         void* stream);
 
+/* ================================================================================================================================
+ * DVPQ tallies on the device (ph_dvpq.hip): what dvps_eval.video_evaluate needs from a frame, computed from the maps where they lie.
+ *
+ * The metric compares (gt id, pred id) intersection counts; a clip is its frames side by side, so a clip's counts are the sums of
+ * its frames' counts, and a depth threshold only relabels the pred id of the pixels that violate it.  One pass over a frame
+ * therefore yields a small integer table -- rows (gt id, pred id, mask of violated thresholds, pixel count) -- from which every
+ * window and every threshold follows on the host (dvps_eval.clip_tallies), and the ingredients of dvps_eval.compute_errors.
+ *
+ * Conventions of the ph_*_plan_* family: status codes plus ph_last_error_string, a caller-owned 256-byte aligned workspace, a size
+ * query that returns 0 with a message on a bad cfg, PH_EINVAL / PH_EWORKSPACE before the first launch, no environment variable
+ * read, no memset node, enqueue-only and capturable into a hipGraph.  ZEROING CONTRACT: none -- the first launch clears what the
+ * others read, and every word of table_out / depth_out up to the sizes below is written.
+ *
+ *   B, H, W      frames per call and the map size, H * W < 2^31, B <= 65535
+ *   capacity     rows of a frame's table, a power of two in 64 .. 65536
+ *   nthr, thr    0 .. PH_DVPQ_MAX_THR depth thresholds (not NaN).  Bit j of a pixel's mask is set iff gt_depth > 0 and
+ *                |pred_depth - gt_depth| / gt_depth > thr[j], evaluated in fp32 with one correctly rounded division -- what numpy
+ *                computes in dvps_eval.evaluate_clip for fp32 maps and the threshold rounded to fp32
+ *
+ * Per pixel g = gt_panseg, p = pred_panseg, or, with pred_panseg == NULL, (uint32)(pred_sem * 10000 + (int64)pred_track): the
+ * association plan's own outputs, packed as dvps_eval.wire_record packs them.  Any uint32 is a legal id, (0, 0, 0) is a legal key.
+ *
+ *   table_out    uint32 [B][4 + 4 capacity]: n | overflow | 0 | 0 | n rows (g, p, mask, count) ascending in (g, p, mask) | zeros.
+ *                Canonical: the same inputs give the same bytes.  A frame with more than `capacity` distinct keys sets overflow = 1
+ *                and keeps n <= capacity rows of its true table (ascending, counts exact); which ones is not specified.
+ *   depth_out    double [B][8] over the pixels with gt_depth > 0: their count | sum |g - p| / g | sum (g - p)^2 / g | sum (g - p)^2 |
+ *                sum (ln g - ln p)^2, the terms in fp64 from the fp32 maps | the counts of max(g / p, p / g) < 1.25, 1.5625,
+ *                1.953125, compared in fp32.  *_sums convention: one fixed-order partial record per workgroup, added in index order.
+ *
+ * Launches: k_dvpq_clear, k_dvpq_frames (grid (workgroups per frame, B): equal keys are combined inside a wave, then in a
+ * per-workgroup LDS table, then in the frame's table in the workspace with 64-bit compare-and-swap and add), k_dvpq_finish (one
+ * workgroup per frame: compaction, ranking, the depth partials).  Pointers: maps naturally aligned (a 16-byte aligned frame is read
+ * with 16-byte loads), table_out 16-byte, depth_out 8-byte, workspace 256-byte aligned. */
+#define PH_DVPQ_MAX_THR 8
+typedef struct {
+    int32_t B, H, W;
+    int32_t capacity;                     /* power of two, 64 .. 65536 */
+    int32_t nthr;                         /* 0 .. PH_DVPQ_MAX_THR */
+    float thr[PH_DVPQ_MAX_THR];
+} ph_dvpq_cfg;
+typedef struct {
+    const uint32_t* pred_panseg;          /* [B][H][W], or NULL: then pred_sem + pred_track */
+    const uint8_t* pred_sem;              /* ph_assoc_plan_run's sem_out */
+    const double* pred_track;             /* ph_assoc_plan_match's track_out (integral, >= 0) */
+    const float* pred_depth;              /* [B][H][W] */
+    const uint32_t* gt_panseg;
+    const float* gt_depth;
+    uint32_t* table_out;                  /* [B][4 + 4 capacity] */
+    double* depth_out;                    /* [B][8] */
+} ph_dvpq_io;
+size_t ph_dvpq_workspace_bytes(const ph_dvpq_cfg* cfg);            /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_dvpq_frames(const ph_dvpq_cfg* cfg, const ph_dvpq_io* io, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -134,6 +134,19 @@ class AssocIO(C.Structure):
                 ("sem_out", C.c_void_p), ("things_out", C.c_void_p), ("embeds_out", C.c_void_p), ("roi_planes", C.c_void_p)]
 
 
+# DVPQ tallies on the device (polyhead.h ph_dvpq_cfg .. ph_dvpq_frames)
+PH_DVPQ_MAX_THR = 8
+
+
+class DvpqCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "capacity", "nthr")] + [("thr", C.c_float * PH_DVPQ_MAX_THR)]
+
+
+class DvpqIO(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pred_panseg", "pred_sem", "pred_track", "pred_depth", "gt_panseg", "gt_depth", "table_out",
+                                          "depth_out")]
+
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
@@ -305,6 +318,8 @@ SIGNATURES = {
     "ph_assoc_plan_destroy": (None, [_P]),
     "ph_assoc_plan_run": (C.c_int, [_P, C.POINTER(AssocIO), _P]),
     "ph_assoc_plan_match": (C.c_int, [_P, _P, _P, _P, _P, _P, _Z, _L, _P, _P, _P]),
+    "ph_dvpq_workspace_bytes": (C.c_size_t, [C.POINTER(DvpqCfg)]),
+    "ph_dvpq_frames": (C.c_int, [C.POINTER(DvpqCfg), C.POINTER(DvpqIO), _P, _Z, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),
