@@ -844,7 +844,7 @@ typedef struct {
 const char* ph_khead_param_name(int index);                        /* NULL out of range */
 int64_t ph_khead_param_numel(const ph_khead_cfg* cfg, int index);  /* elements; < 0 out of range */
 
-/* ---- packing (k_khead_pack: one launch, once per weight load).  The pieces are engine.KernelHeadPack's tensors, byte for byte
+/* ---- packing (k_pack_pieces: one launch, once per weight load).  The pieces are engine.KernelHeadPack's tensors, byte for byte
  * (nothing is folded: fp32 -> bf16 / fp16 round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned
  * offset of one device buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT),
  * rows32(n) = n rounded up to 32 (pad rows zero):
@@ -978,7 +978,7 @@ typedef struct {
 const char* ph_neck_param_name(int index);                         /* NULL out of range */
 int64_t ph_neck_param_numel(const ph_neck_cfg* cfg, int index);    /* elements; < 0 out of range */
 
-/* ---- packing (k_neck_pack: one launch, once per weight load).  The pieces are SemanticFPNWrapper._pack's tensors, byte for byte
+/* ---- packing (k_pack_pieces: one launch, once per weight load).  The pieces are SemanticFPNWrapper._pack's tensors, byte for byte
  * (fp32 -> bf16 / fp16 round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned offset of one device
  * buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT), conv c = parameter 3 c:
  *   WP(c)        uint16 [P][256 * K]   pack.pack_b32 fragments of W[n][tap * 256 + c'] -- the (kh, kw, in) K order, K = 2304 (3x3)
@@ -1078,7 +1078,7 @@ typedef struct {
 const char* ph_track_param_name(const ph_track_cfg* cfg, int index);      /* NULL out of range or on a bad cfg */
 int64_t ph_track_param_numel(const ph_track_cfg* cfg, int index);         /* elements; < 0 out of range */
 
-/* ---- packing (k_track_pack: one launch, once per weight load).  The pieces are QuasiDenseMaskEmbedHeadGTMask._get_pack's tensors,
+/* ---- packing (k_pack_pieces: one launch, once per weight load).  The pieces are QuasiDenseMaskEmbedHeadGTMask._get_pack's tensors,
  * byte for byte (hi = bf16(w) round to nearest even, lo = bf16(w - float(hi)) in fp32), each at a 256-byte aligned offset of one
  * device buffer; the alignment padding is written as zeros.  P = planes of the grade (2 for PH_PREC_SPLIT):
  *   CONV(i)          uint16 [P][256 * 2304]  pack.pack_b_fragments of W[n][tap * 256 + c] -- the (kh, kw, in) K order

@@ -11,15 +11,12 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpolyhead.so")
-# the Python-free caller of the C ABI (examples/decode_c), built next to the library it links
-EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "decode_c", "decode_main.cpp")
-EXAMPLE = os.path.join(HERE, "decode_main")
-# the whole head from C (examples/head_c): neck maps -> KernelHead plan -> decode plan -> panoptic merge
-HEAD_EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "head_c", "head_main.cpp")
-HEAD_EXAMPLE = os.path.join(HERE, "head_main")
-# the neck in front of it (examples/neck_c): FPN levels -> neck plan -> KernelHead plan -> decode plan -> panoptic merge
-NECK_EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "neck_c", "neck_main.cpp")
-NECK_EXAMPLE = os.path.join(HERE, "neck_main")
+# the Python-free callers of the C ABI, built next to the library they link: (source, program)
+#   decode_c: the decode plan;  head_c: neck maps -> KernelHead plan -> decode plan -> panoptic merge;  neck_c: FPN levels -> neck plan
+#   in front of that
+EXAMPLES = [(os.path.join(os.path.dirname(HERE), "examples", d, prog + ".cpp"), os.path.join(HERE, prog))
+            for d, prog in (("decode_c", "decode_main"), ("head_c", "head_main"), ("neck_c", "neck_main"))]
+EXAMPLE, HEAD_EXAMPLE, NECK_EXAMPLE = (prog for _, prog in EXAMPLES)
 OBJ = os.path.join(CSRC, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 
@@ -46,10 +43,10 @@ def sources():
 def build_library(force=False, verbose=False):
     srcs = sources()
     deps = srcs + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-        [os.path.join(os.path.dirname(HERE), "include", "polyhead.h"), EXAMPLE_SRC, HEAD_EXAMPLE_SRC, NECK_EXAMPLE_SRC]
+        [os.path.join(os.path.dirname(HERE), "include", "polyhead.h")] + [src for src, _ in EXAMPLES]
     stamp = os.path.join(OBJ, "stamp")
     dig = _digest(deps)
-    if not force and os.path.exists(LIB) and os.path.exists(EXAMPLE) and os.path.exists(HEAD_EXAMPLE) and os.path.exists(NECK_EXAMPLE) and os.path.exists(stamp) and open(stamp).read() == dig:
+    if not force and all(os.path.exists(f) for f in [LIB, stamp] + [prog for _, prog in EXAMPLES]) and open(stamp).read() == dig:
         return LIB
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
@@ -71,18 +68,11 @@ def build_library(force=False, verbose=False):
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stderr[-4000:]}")
     # host code only: the HIP runtime API and libpolyhead.so (found next to the program through its run path)
-    r = subprocess.run([hipcc, "-O2", "-std=c++17", EXAMPLE_SRC, "-o", EXAMPLE, "-L" + HERE, "-lpolyhead", "-Wl,-rpath,$ORIGIN"],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"building {EXAMPLE_SRC} failed:\n{r.stderr[-4000:]}")
-    r = subprocess.run([hipcc, "-O2", "-std=c++17", HEAD_EXAMPLE_SRC, "-o", HEAD_EXAMPLE, "-L" + HERE, "-lpolyhead", "-Wl,-rpath,$ORIGIN"],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"building {HEAD_EXAMPLE_SRC} failed:\n{r.stderr[-4000:]}")
-    r = subprocess.run([hipcc, "-O2", "-std=c++17", NECK_EXAMPLE_SRC, "-o", NECK_EXAMPLE, "-L" + HERE, "-lpolyhead", "-Wl,-rpath,$ORIGIN"],
-                       capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"building {NECK_EXAMPLE_SRC} failed:\n{r.stderr[-4000:]}")
+    for src, prog in EXAMPLES:
+        r = subprocess.run([hipcc, "-O2", "-std=c++17", src, "-o", prog, "-L" + HERE, "-lpolyhead", "-Wl,-rpath,$ORIGIN"],
+                           capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"building {src} failed:\n{r.stderr[-4000:]}")
     with open(stamp, "w") as f:
         f.write(dig)
     return LIB

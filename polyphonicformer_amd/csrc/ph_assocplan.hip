@@ -74,87 +74,26 @@ static int64_t track_numel(const TGeo& g, int index) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_track_pack: every 16-byte unit of the pack is written by one thread (the alignment padding as zeros, so two packings of the same
-// weights are byte-equal).  A unit is 8 consecutive 16-bit values or 4 floats.  In a fragment piece (pack.pack_b_fragments of
-// W2[n][k]: [ct][ks][g][j][e] holds W2[16 ct + j][32 ks + 8 g + e]) the 8 values are 8 consecutive k of one output row:
-//   TP_FRAG_TAP  k = tap * 256 + c of a parameter stored [row][c][tap]: the 3x3 convs (taps = 9, tap = kh * 3 + kw) and fcs.0
-//                (taps = 49: its K axis permuted from ci * 49 + pos to pos * 256 + ci) -- 8 loads `taps` floats apart
-//   TP_FRAG      k as stored: fc_embed
-// The gather is not coalesced, which a once-per-weight-load kernel can afford.
-enum { TP_FRAG_TAP = 0, TP_FRAG = 1, TP_F32 = 2 };
-struct TPiece {
-    uint32_t u0;             // first unit of the piece (ascending over the pieces)
-    uint32_t nvalid;         // units that carry data; the rest up to the next piece is padding
-    uint32_t rows, K;        // fragment pieces: W2 is [rows][K]
-    uint8_t kind, param, taps, pad_;
-};
-struct TPackTable {
-    const float* p[TRACK_NPARAMS_MAX];
-    TPiece pc[PH_TPACK_COUNT];
-    uint32_t total_u;
-};
-
-__global__ __launch_bounds__(256) void k_track_pack(const TPackTable t, uint4* __restrict__ pack) {
-    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < t.total_u; u += gridDim.x * 256u) {
-        int k = 0;
-        for (int i = 1; i < PH_TPACK_COUNT; ++i)
-            if (u >= t.pc[i].u0) k = i;          // an empty piece shares its start with its successor, which wins
-        const TPiece pc = t.pc[k];
-        const uint32_t lu = u - pc.u0;
-        uint4 out = make_uint4(0u, 0u, 0u, 0u);
-        if (lu < pc.nvalid) {
-            if (pc.kind == TP_F32) {
-                const float* src = t.p[pc.param] + (size_t)lu * 4u;
-                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
-            } else {
-                const uint32_t per = pc.rows * pc.K, KS = pc.K / 32u;
-                const uint32_t e0 = lu * 8u, pl = e0 / per, i = e0 % per;
-                const uint32_t j = (i >> 3) & 15u, gq = (i >> 7) & 3u, r = i >> 9, ks = r % KS, ct = r / KS;
-                const uint32_t row = 16u * ct + j, kk = 32u * ks + 8u * gq;
-                const float* src;
-                size_t step;
-                if (pc.kind == TP_FRAG_TAP) {
-                    const uint32_t tap = kk >> 8, c = kk & 255u;
-                    src = t.p[pc.param] + ((size_t)row * 256u + c) * pc.taps + tap;
-                    step = pc.taps;
-                } else {
-                    src = t.p[pc.param] + (size_t)row * pc.K + kk;
-                    step = 1;
-                }
-                uint32_t v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    uint32_t h, l;
-                    f2bf_split(src[(size_t)e * step], h, l);
-                    v[e] = pl ? l : h;
-                }
-                out = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-            }
-        }
-        pack[u] = out;
-    }
-}
-
-static void build_table(const TGeo& g, TPackTable& t) {
-    memset(&t, 0, sizeof(t));
-    auto set = [&](int piece, int kind, int param, int taps, int rows, int K) {
-        TPiece& p = t.pc[piece];
-        p.u0 = (uint32_t)(g.lay.offset[piece] / 16);
-        p.nvalid = (uint32_t)(g.lay.bytes[piece] / 16);
-        p.kind = (uint8_t)kind; p.param = (uint8_t)param; p.taps = (uint8_t)taps; p.rows = (uint32_t)rows; p.K = (uint32_t)K;
+// the pack's pieces for ph_pack_pieces (QuasiDenseMaskEmbedHeadGTMask._get_pack's tensors): the 3x3 convs and fcs.0 are tap-permuted
+// 16-row fragments (fcs.0 has taps = 49: its K axis goes from ci * 49 + pos to pos * 256 + ci), fc_embed's K is as stored
+static void build_table(const TGeo& g, PhPackTable& t) {
+    auto set = [&](int piece, int kind, int first, int taps = 0, int rows = 0, int K = 0) {
+        ph_pack_piece(t, g.lay.offset, g.lay.bytes, piece, kind, first, taps, rows, K, rows);
     };
     for (int i = 0; i < PH_TRACK_MAX_CONVS; ++i) {       // the pieces of an absent conv are empty
         const int pr = i < g.num_convs ? 3 * i : 0;
-        set(PH_TPACK_CONV(i), TP_FRAG_TAP, pr, 9, 256, 2304);
-        set(PH_TPACK_GAMMA(i), TP_F32, pr + 1, 0, 0, 0);
-        set(PH_TPACK_BETA(i), TP_F32, pr + 2, 0, 0, 0);
+        set(PH_TPACK_CONV(i), PH_PIECE_FRAG16, pr, 9, 256, 2304);
+        set(PH_TPACK_GAMMA(i), PH_PIECE_F32, pr + 1);
+        set(PH_TPACK_BETA(i), PH_PIECE_F32, pr + 2);
     }
     const int tail = 3 * g.num_convs;
-    set(PH_TPACK_FC, TP_FRAG_TAP, tail, 49, g.F, FC_K);
-    set(PH_TPACK_FC_B, TP_F32, tail + 1, 0, 0, 0);
-    set(PH_TPACK_EMB, TP_FRAG, tail + 2, 0, g.E, g.F);
-    set(PH_TPACK_EMB_B, TP_F32, tail + 3, 0, 0, 0);
+    set(PH_TPACK_FC, PH_PIECE_FRAG16, tail, 49, g.F, FC_K);
+    set(PH_TPACK_FC_B, PH_PIECE_F32, tail + 1);
+    set(PH_TPACK_EMB, PH_PIECE_FRAG16, tail + 2, 0, g.E, g.F);
+    set(PH_TPACK_EMB_B, PH_PIECE_F32, tail + 3);
+    t.npieces = PH_TPACK_COUNT;
     t.total_u = (uint32_t)(g.pack_total / 16);
+    t.f16 = 0;                                           // the track head's grades are bf16 and the bf16 split
 }
 
 extern "C" const char* ph_track_param_name(const ph_track_cfg* cfg, int index) {
@@ -192,13 +131,10 @@ extern "C" int ph_track_pack(const ph_track_cfg* cfg, const float* const* params
         if (!params[i]) { ph_set_error("ph_track_pack: parameter %d (%s) is NULL", i, ph_track_param_name(cfg, i)); return PH_EINVAL; }
     PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
     PH_CHECK_ARG(g.pack_total / 16 < (1ull << 32), "pack too large");
-    TPackTable t;
+    PhPackTable t{};
     build_table(g, t);
     for (int i = 0; i < g.nparams; ++i) t.p[i] = params[i];
-    const unsigned blocks = (t.total_u + 255u) / 256u;
-    hipLaunchKernelGGL(k_track_pack, dim3(blocks < 4096u ? blocks : 4096u), dim3(256), 0, (hipStream_t)stream, t, (uint4*)pack);
-    PH_CHECK_LAUNCH();
-    return PH_OK;
+    return ph_pack_pieces("ph_track_pack", t, pack, 4096, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -361,12 +297,7 @@ extern "C" int ph_assoc_plan_create(const ph_assoc_cfg* cfg, const void* pack, v
     if (rc) return rc;
     PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
     *out = nullptr;
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    if (workspace_bytes < g.total) {
-        ph_set_error("ph_assoc_plan_create: workspace too small (%zu < %zu)", workspace_bytes, g.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_assoc_plan_create", pack, workspace, workspace_bytes, g.total));
     ph_assoc_plan* p = new (std::nothrow) ph_assoc_plan;
     if (!p) { ph_set_error("ph_assoc_plan_create: out of host memory"); return PH_EINVAL; }
     p->g = g;

@@ -51,6 +51,49 @@ void ph_set_error(const char* fmt, ...);
 // the pieces of a caller-owned workspace or pack start at 256-byte boundaries
 static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
+// every buffer check of a native plan's create / run call, in this order: pack alignment (pack_or_null: none to check), workspace
+// NULL, workspace size (PH_EWORKSPACE), workspace alignment; the messages carry the public function's name (ph_api.hip)
+int ph_check_buffers(const char* fn, const void* pack_or_null, const void* workspace, size_t workspace_bytes, size_t need);
+
+// ---- the weight packs of the native KernelHead / neck / association plans: one kernel (ph_wpack.hip) writes a pack from a table of
+// its pieces.  A piece is a run of 16-byte units of one kind; what lies between its data and the next piece is padding (zeros).
+enum {
+    PH_PIECE_PLANES = 0,     // 16-bit [P][nmat][rows][K] as stored; rows at or above rows_valid are zero
+    PH_PIECE_FRAG32 = 1,     // 16-bit [P][nmat] x pack.pack_b32 fragments of W2 [rows][K]; rows_valid likewise
+    PH_PIECE_FRAG16 = 2,     // 16-bit [P] x pack.pack_b_fragments fragments of W2 [rows][K]
+    PH_PIECE_F32 = 3,        // fp32 copy of parameter `first`
+    PH_PIECE_GN = 4,         // fp32 [3][2][256]: (gamma, beta) of three convs, parameters first + 3 m + 1, + 2
+    PH_PIECE_BIAS = 5        // fp32 parameter `first`, zero at or beyond entry rows_valid
+};
+struct PhPackPiece {
+    uint32_t u0;             // first unit of the piece (ascending over the pieces)
+    uint32_t nvalid;         // units that carry data; the rest up to the next piece is padding
+    uint32_t rows, K;        // 16-bit kinds: W2 is [rows][K] (rows as padded in the pack)
+    uint32_t rows_valid;
+    uint8_t kind, first, pstep, nmat;   // first parameter; 16-bit kinds: distance between the matrices' parameters, matrices per plane
+    uint8_t taps;            // 16-bit kinds: > 0: K = taps * 256 of a parameter stored [row][256][taps]; 0: the parameter is [row][K]
+};
+enum { PH_PACK_MAX_PARAMS = 30, PH_PACK_MAX_PIECES = 32 };
+struct PhPackTable {
+    const float* p[PH_PACK_MAX_PARAMS];
+    PhPackPiece pc[PH_PACK_MAX_PIECES];
+    uint32_t total_u;        // units of the whole pack
+    int32_t npieces;
+    int32_t f16;             // 16-bit values are fp16 (one plane); else bf16 hi (+ lo) planes
+};
+static_assert(sizeof(PhPackTable) <= 2048, "the pack table travels as a kernel argument");
+static_assert(PH_KHEAD_NPARAMS <= PH_PACK_MAX_PARAMS && PH_NECK_NPARAMS <= PH_PACK_MAX_PARAMS && 3 * PH_TRACK_MAX_CONVS + 4 <= PH_PACK_MAX_PARAMS &&
+              PH_KPACK_COUNT <= PH_PACK_MAX_PIECES && PH_NPACK_COUNT <= PH_PACK_MAX_PIECES && PH_TPACK_COUNT <= PH_PACK_MAX_PIECES,
+              "include/polyhead.h: a pack's parameters and pieces fit the table");
+// piece `i` of a pack layout (include/polyhead.h: offset[] / bytes[] of the pieces) into the table
+static inline void ph_pack_piece(PhPackTable& t, const uint64_t* offset, const uint64_t* bytes, int i, int kind, int first, int taps = 0,
+                                 uint32_t rows = 0, uint32_t K = 0, uint32_t rows_valid = 0, int nmat = 1, int pstep = 0) {
+    t.pc[i] = PhPackPiece{(uint32_t)(offset[i] / 16), (uint32_t)(bytes[i] / 16), rows, K, rows_valid,
+                          (uint8_t)kind, (uint8_t)first, (uint8_t)pstep, (uint8_t)nmat, (uint8_t)taps};
+}
+// launches the packer on `stream` with at most `max_blocks` workgroups; `fn`: the public entry point, for the message
+int ph_pack_pieces(const char* fn, const PhPackTable& t, void* pack, unsigned max_blocks, void* stream);
+
 // ---- the hard mask threshold (kernel_update_head.py:236-238, kernel_head.py:314-317): `sigmoid(z) > 0.5` in fp32.
 // Evaluated as the reference does -- 1 / (1 + exp(-z)), every operation rounded to fp32 -- the comparison is true exactly
 // for z > 1.5 * 2^-24: below that 1 - z rounds to 1 - 2^-24 or 1, 2 - 2^-24 rounds to 2, and 1 / 2 = 0.5.  (Probe on

@@ -478,11 +478,7 @@ extern "C" int ph_decode_create(const ph_decode_cfg* cfg, const void* const* pac
     *out = nullptr;
     for (int s = 0; s < g.S; ++s)
         if (!packs[s] || ((uintptr_t)packs[s] & 255)) { ph_set_error("ph_decode_create: pack %d is NULL or not 256-byte aligned", s); return PH_EINVAL; }
-    if (workspace_bytes < g.total) {
-        ph_set_error("ph_decode_create: workspace too small (%zu < %zu)", workspace_bytes, g.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_decode_create", nullptr, workspace, workspace_bytes, g.total));
     ph_decode* p = new (std::nothrow) ph_decode;
     if (!p) { ph_set_error("ph_decode_create: out of host memory"); return PH_EINVAL; }
     if (!g.up2_wgs) {      // engine.DecodePlan: 3 * multi_processor_count / 2 of the plan's device

@@ -333,12 +333,7 @@ extern "C" int ph_dvpq_frames(const ph_dvpq_cfg* cfg, const ph_dvpq_io* io, void
     PH_CHECK_ARG(io->pred_panseg || (io->pred_sem && io->pred_track), "null prediction: pred_panseg, or pred_sem and pred_track");
     PH_CHECK_ARG(io->pred_depth && io->gt_panseg && io->gt_depth, "null pred_depth, gt_panseg or gt_depth");
     PH_CHECK_ARG(io->table_out && io->depth_out, "null table_out or depth_out");
-    PH_CHECK_ARG(workspace != nullptr, "null workspace");
-    if (workspace_bytes < g.total) {
-        ph_set_error("ph_dvpq_frames: workspace too small (%zu < %zu)", workspace_bytes, g.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_dvpq_frames", nullptr, workspace, workspace_bytes, g.total));
     PH_CHECK_ARG((((uintptr_t)io->pred_panseg | (uintptr_t)io->pred_depth | (uintptr_t)io->gt_panseg | (uintptr_t)io->gt_depth) & 3) == 0,
                  "the uint32 / float maps must be 4-byte aligned");
     PH_CHECK_ARG(io->pred_panseg || ((uintptr_t)io->pred_track & 7) == 0, "pred_track must be 8-byte aligned");

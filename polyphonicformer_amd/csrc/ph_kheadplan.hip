@@ -2,8 +2,6 @@
 // engine.KernelHeadPack as one HIP kernel, and the geometry rules, the buffer plan and the launch sequence of
 // engine.KernelHeadPlan.  Host code only calls the other entry points of this library, on the caller's stream; pack / create /
 // run allocate no device memory, do not synchronise and read no environment variable.
-#include <string.h>
-
 #include <new>
 
 #include "ph_common.h"
@@ -120,102 +118,27 @@ static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn, bool need_dev
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_khead_pack: every 16-byte unit of the pack is written by one thread (one 16-byte store; the alignment padding as zeros,
-// so two packings of the same weights are byte-equal).  A unit is 8 consecutive 16-bit values or 4 floats, and in every piece
-// those come from consecutive source elements of ONE parameter row.
-enum { KP_PLANES = 0, KP_FRAG = 1, KP_F32 = 2, KP_GN = 3, KP_BIAS = 4 };
-struct KPiece {
-    uint32_t u0;             // first unit of the piece (ascending over the pieces)
-    uint32_t nvalid;         // units that carry data; the rest up to the next piece is padding
-    uint32_t mat_elems;      // PLANES / FRAG: rows32 * 256
-    uint16_t rows_valid;     // PLANES / FRAG: rows below this come from the parameter, the others are zero; BIAS: valid entries
-    uint8_t kind, first, pstep, nmat;   // first parameter, distance between the matrices' parameters, matrices per plane
-};
-struct KPackTable {
-    const float* p[PH_KHEAD_NPARAMS];
-    KPiece pc[PH_KPACK_COUNT];
-    uint32_t total_u;
-    int32_t f16;
-};
-
-__device__ __forceinline__ uint32_t khp_cvt(float w, bool f16, bool lo) {
-    if (f16) return f2h(w);
-    uint32_t h, l;
-    f2bf_split(w, h, l);
-    return lo ? l : h;
-}
-
-__global__ __launch_bounds__(256) void k_khead_pack(const KPackTable t, uint4* __restrict__ pack) {
-    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < t.total_u; u += gridDim.x * 256u) {
-        int k = 0;
-        for (int i = 1; i < PH_KPACK_COUNT; ++i)
-            if (u >= t.pc[i].u0) k = i;          // an empty piece shares its start with its successor, which wins
-        const KPiece pc = t.pc[k];
-        const uint32_t lu = u - pc.u0;
-        uint4 out = make_uint4(0u, 0u, 0u, 0u);
-        if (lu < pc.nvalid) {
-            if (pc.kind == KP_PLANES || pc.kind == KP_FRAG) {
-                const uint32_t e0 = lu * 8u, per = pc.mat_elems * pc.nmat;
-                const uint32_t pl = e0 / per, r0 = e0 % per, m = r0 / pc.mat_elems, i = r0 % pc.mat_elems;
-                uint32_t row, col;
-                if (pc.kind == KP_PLANES) { row = i >> 8; col = i & 255u; }
-                else {    // pack.pack_b32: [ct][ks][g][n][e] holds W[32 ct + n][16 ks + 8 g + e]
-                    const uint32_t n = (i >> 3) & 31u, gq = (i >> 8) & 1u, ks = (i >> 9) & 15u, ct = i >> 13;
-                    row = 32u * ct + n; col = 16u * ks + 8u * gq;
-                }
-                if (row < pc.rows_valid) {
-                    const float* src = t.p[pc.first + m * pc.pstep] + (size_t)row * 256u + col;
-                    uint32_t v[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = khp_cvt(src[e], t.f16 != 0, pl != 0);
-                    out = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-                }
-            } else if (pc.kind == KP_F32) {
-                const float* src = t.p[pc.first] + (size_t)lu * 4u;
-                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
-            } else if (pc.kind == KP_GN) {   // [3][2][256]: (gamma, beta) of map m = parameters 3 m + 1, 3 m + 2
-                const uint32_t i = lu * 4u, m = i >> 9, wb = (i >> 8) & 1u, c = i & 255u;
-                const float* src = t.p[3u * m + 1u + wb] + c;
-                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
-            } else {                          // a bias vector, zero beyond its valid entries
-                uint32_t v[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const uint32_t i = lu * 4u + e;
-                    v[e] = i < pc.rows_valid ? __float_as_uint(t.p[pc.first][i]) : 0u;
-                }
-                out = make_uint4(v[0], v[1], v[2], v[3]);
-            }
-        }
-        pack[u] = out;
-    }
-}
-
-static void build_table(const KGeo& g, KPackTable& t) {
-    memset(&t, 0, sizeof(t));
+// the pack's pieces for ph_pack_pieces (engine.KernelHeadPack's tensors)
+static void build_table(const KGeo& g, PhPackTable& t) {
     auto set = [&](int piece, int kind, int first, int pstep, int nmat, int rows32, int rows_valid) {
-        KPiece& p = t.pc[piece];
-        p.u0 = (uint32_t)(g.lay.offset[piece] / 16);
-        p.nvalid = (uint32_t)(g.lay.bytes[piece] / 16);
-        p.mat_elems = (uint32_t)rows32 * 256u;
-        p.rows_valid = (uint16_t)rows_valid;
-        p.kind = (uint8_t)kind; p.first = (uint8_t)first; p.pstep = (uint8_t)pstep; p.nmat = (uint8_t)nmat;
+        ph_pack_piece(t, g.lay.offset, g.lay.bytes, piece, kind, first, kind == PH_PIECE_FRAG32 ? 1 : 0, rows32, 256, rows_valid, nmat, pstep);
     };
     const int r_seg = ph_n_padded(g.n_seg);
-    set(PH_KPACK_WPLANES, KP_PLANES, P_CONV, 3, 3, 256, 256);
-    set(PH_KPACK_GN, KP_GN, 0, 0, 1, 0, 0);
-    set(PH_KPACK_INIT_PLANES, KP_PLANES, P_INIT, 0, 1, g.NqPad, g.Nq);
-    set(PH_KPACK_SEG_PLANES, KP_PLANES, P_SEG, 0, 1, r_seg, g.n_seg);
-    set(PH_KPACK_DD_PLANES, KP_PLANES, P_DD, 0, 1, 32, 1);
-    set(PH_KPACK_SEG_BIAS, KP_BIAS, P_SEG_B, 0, 1, 0, g.n_seg);
-    set(PH_KPACK_DD_BIAS, KP_BIAS, P_DD_B, 0, 1, 0, 1);
-    set(PH_KPACK_INIT_FRAG, KP_FRAG, P_INIT, 0, 1, g.NqPad, g.Nq);
-    set(PH_KPACK_SEG_FRAG, KP_FRAG, P_SEG, 0, 1, r_seg, g.n_seg);
-    set(PH_KPACK_DD_FRAG, KP_FRAG, P_DD, 0, 1, 32, 1);
-    set(PH_KPACK_CONV_FRAG, KP_FRAG, P_CONV, 3, 3, 256, 256);
-    set(PH_KPACK_W_INIT_F32, KP_F32, P_INIT, 0, 1, 0, 0);
-    set(PH_KPACK_W_SEG_F32, KP_F32, P_SEG, 0, 1, 0, 0);
-    set(PH_KPACK_W_DD_F32, KP_F32, P_DD, 0, 1, 0, 0);
+    set(PH_KPACK_WPLANES, PH_PIECE_PLANES, P_CONV, 3, 3, 256, 256);
+    set(PH_KPACK_GN, PH_PIECE_GN, 0, 0, 1, 0, 0);
+    set(PH_KPACK_INIT_PLANES, PH_PIECE_PLANES, P_INIT, 0, 1, g.NqPad, g.Nq);
+    set(PH_KPACK_SEG_PLANES, PH_PIECE_PLANES, P_SEG, 0, 1, r_seg, g.n_seg);
+    set(PH_KPACK_DD_PLANES, PH_PIECE_PLANES, P_DD, 0, 1, 32, 1);
+    set(PH_KPACK_SEG_BIAS, PH_PIECE_BIAS, P_SEG_B, 0, 1, 0, g.n_seg);
+    set(PH_KPACK_DD_BIAS, PH_PIECE_BIAS, P_DD_B, 0, 1, 0, 1);
+    set(PH_KPACK_INIT_FRAG, PH_PIECE_FRAG32, P_INIT, 0, 1, g.NqPad, g.Nq);
+    set(PH_KPACK_SEG_FRAG, PH_PIECE_FRAG32, P_SEG, 0, 1, r_seg, g.n_seg);
+    set(PH_KPACK_DD_FRAG, PH_PIECE_FRAG32, P_DD, 0, 1, 32, 1);
+    set(PH_KPACK_CONV_FRAG, PH_PIECE_FRAG32, P_CONV, 3, 3, 256, 256);
+    set(PH_KPACK_W_INIT_F32, PH_PIECE_F32, P_INIT, 0, 1, 0, 0);
+    set(PH_KPACK_W_SEG_F32, PH_PIECE_F32, P_SEG, 0, 1, 0, 0);
+    set(PH_KPACK_W_DD_F32, PH_PIECE_F32, P_DD, 0, 1, 0, 0);
+    t.npieces = PH_KPACK_COUNT;
     t.total_u = (uint32_t)(g.pack_total / 16);
     t.f16 = g.prec == PH_PREC_F16;
 }
@@ -258,13 +181,10 @@ extern "C" int ph_khead_pack(const ph_khead_cfg* cfg, const float* const* params
     for (int i = 0; i < PH_KHEAD_NPARAMS; ++i)
         if (!params[i]) { ph_set_error("ph_khead_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
     PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    KPackTable t;
+    PhPackTable t{};
     build_table(g, t);
     for (int i = 0; i < PH_KHEAD_NPARAMS; ++i) t.p[i] = params[i];
-    const unsigned blocks = (t.total_u + 255u) / 256u;
-    hipLaunchKernelGGL(k_khead_pack, dim3(blocks < 1024u ? blocks : 1024u), dim3(256), 0, (hipStream_t)stream, t, (uint4*)pack);
-    PH_CHECK_LAUNCH();
-    return PH_OK;
+    return ph_pack_pieces("ph_khead_pack", t, pack, 1024, stream);
 }
 
 extern "C" size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg) {
@@ -286,12 +206,7 @@ extern "C" int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, v
     if (rc) return rc;
     PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
     *out = nullptr;
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    if (workspace_bytes < g.total) {
-        ph_set_error("ph_khead_plan_create: workspace too small (%zu < %zu)", workspace_bytes, g.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_khead_plan_create", pack, workspace, workspace_bytes, g.total));
     ph_khead_plan* p = new (std::nothrow) ph_khead_plan;
     if (!p) { ph_set_error("ph_khead_plan_create: out of host memory"); return PH_EINVAL; }
     p->g = g;

@@ -624,11 +624,7 @@ extern "C" int ph_panoptic_merge(const float* cls, const void* mask_up, const vo
     MergeLayout M;
     rc = merge_layout(__func__, B, K, h2, w2, geom, G, M);
     if (rc != PH_OK) return rc;
-    if (workspace_bytes < M.total) {
-        ph_set_error("ph_panoptic_merge: workspace too small (%zu < %zu)", workspace_bytes, M.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_panoptic_merge", nullptr, workspace, workspace_bytes, M.total));
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int32_t* pack = (int32_t*)(ws + M.pack);

@@ -3,7 +3,6 @@
 // plan and the launch sequence of engine.NeckPlan.  Host code only calls the other entry points of this library, on the caller's
 // stream(s); pack / posenc / create / run allocate no device memory, do not synchronise and read no environment variable.
 #include <math.h>
-#include <string.h>
 
 #include <new>
 
@@ -167,85 +166,19 @@ static int resolve(const ph_neck_cfg* c, NGeo& g, const char* fn) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// k_neck_pack: every 16-byte unit of the pack is written by one thread (one 16-byte store; the alignment padding as zeros, so two
-// packings of the same weights are byte-equal).  A unit is 8 consecutive 16-bit values or 4 floats.  In a fragment piece the 8
-// values are 8 consecutive input channels of one (output row, tap): 8 loads `taps` floats apart (the parameter is [out][in][kh][kw]).
-// The stores are whole 128-byte lines per 8 lanes; the gather is not coalesced, which a once-per-weight-load kernel can afford.
-enum { NP_FRAG = 0, NP_F32 = 1, NP_OUTS_W = 2, NP_OUTS_GN = 3 };
-struct NPiece {
-    uint32_t u0;             // first unit of the piece (ascending over the pieces)
-    uint32_t nvalid;         // units that carry data; the rest up to the next piece is padding
-    uint8_t kind, param, taps, pad_;
-};
-struct NPackTable {
-    const float* p[PH_NECK_NPARAMS];
-    NPiece pc[PH_NPACK_COUNT];
-    uint32_t total_u;
-    int32_t f16;
-};
-
-__device__ __forceinline__ uint32_t np_cvt(float w, bool f16, bool lo) {
-    if (f16) return f2h(w);
-    uint32_t h, l;
-    f2bf_split(w, h, l);
-    return lo ? l : h;
-}
-
-__global__ __launch_bounds__(256) void k_neck_pack(const NPackTable t, uint4* __restrict__ pack) {
-    for (uint32_t u = blockIdx.x * 256u + threadIdx.x; u < t.total_u; u += gridDim.x * 256u) {
-        int k = 0;
-        for (int i = 1; i < PH_NPACK_COUNT; ++i)
-            if (u >= t.pc[i].u0) k = i;          // an empty piece shares its start with its successor, which wins
-        const NPiece pc = t.pc[k];
-        const uint32_t lu = u - pc.u0;
-        uint4 out = make_uint4(0u, 0u, 0u, 0u);
-        if (lu < pc.nvalid) {
-            if (pc.kind == NP_FRAG) {
-                // pack.pack_b32 of W2[n][tap * 256 + c]: [ct][ks][g][n][e] holds W2[32 ct + n][16 ks + 8 g + e], ks < K / 16
-                const uint32_t taps = pc.taps, ksteps = taps * 16u, per = 256u * 256u * taps;
-                const uint32_t e0 = lu * 8u, pl = e0 / per, i = e0 % per;
-                const uint32_t n = (i >> 3) & 31u, gq = (i >> 8) & 1u, r = i >> 9, ks = r % ksteps, ct = r / ksteps;
-                const uint32_t row = 32u * ct + n, kk = 16u * ks + 8u * gq, tap = kk >> 8, c = kk & 255u;
-                const float* src = t.p[pc.param] + ((size_t)row * 256u + c) * taps + tap;
-                uint32_t v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = np_cvt(src[(size_t)e * taps], t.f16 != 0, pl != 0);
-                out = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-            } else if (pc.kind == NP_F32) {
-                const float* src = t.p[pc.param] + (size_t)lu * 4u;
-                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
-            } else if (pc.kind == NP_OUTS_W) {   // [P][3][256][256] (out, in) planes of the three 1x1 weights
-                const uint32_t e0 = lu * 8u, pl = e0 / (3u * 65536u), r = e0 % (3u * 65536u), m = r >> 16, i = r & 65535u;
-                const float* src = t.p[3u * (C_PRED + m)] + i;
-                uint32_t v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = np_cvt(src[e], t.f16 != 0, pl != 0);
-                out = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-            } else {                              // [3][2][256]: (gamma, beta) of output conv m
-                const uint32_t i = lu * 4u, m = i >> 9, wb = (i >> 8) & 1u, c = i & 255u;
-                const float* src = t.p[3u * (C_PRED + m) + 1u + wb] + c;
-                out = make_uint4(__float_as_uint(src[0]), __float_as_uint(src[1]), __float_as_uint(src[2]), __float_as_uint(src[3]));
-            }
-        }
-        pack[u] = out;
-    }
-}
-
-static void build_table(const NGeo& g, NPackTable& t) {
-    memset(&t, 0, sizeof(t));
-    auto set = [&](int piece, int kind, int param, int taps) {
-        NPiece& p = t.pc[piece];
-        p.u0 = (uint32_t)(g.lay.offset[piece] / 16);
-        p.nvalid = (uint32_t)(g.lay.bytes[piece] / 16);
-        p.kind = (uint8_t)kind; p.param = (uint8_t)param; p.taps = (uint8_t)taps;
+// the pack's pieces for ph_pack_pieces (SemanticFPNWrapper._pack's tensors)
+static void build_table(const NGeo& g, PhPackTable& t) {
+    auto set = [&](int piece, int kind, int first, int taps = 0, int nmat = 1) {
+        ph_pack_piece(t, g.lay.offset, g.lay.bytes, piece, kind, first, taps, 256, 256 * (taps ? taps : 1), 256, nmat, 3);
     };
     for (int i = 0; i < NCONV_MAX; ++i) {       // the pieces of an absent aux conv are empty
-        set(PH_NPACK_WP(i), NP_FRAG, 3 * i, conv_taps(i));
-        set(PH_NPACK_GAMMA(i), NP_F32, 3 * i + 1, 0);
-        set(PH_NPACK_BETA(i), NP_F32, 3 * i + 2, 0);
+        set(PH_NPACK_WP(i), PH_PIECE_FRAG32, 3 * i, conv_taps(i));
+        set(PH_NPACK_GAMMA(i), PH_PIECE_F32, 3 * i + 1);
+        set(PH_NPACK_BETA(i), PH_PIECE_F32, 3 * i + 2);
     }
-    set(PH_NPACK_OUTS_W, NP_OUTS_W, 0, 0);
-    set(PH_NPACK_OUTS_GN, NP_OUTS_GN, 0, 0);
+    set(PH_NPACK_OUTS_W, PH_PIECE_PLANES, 3 * C_PRED, 0, 3);       // [P][3][256][256] (out, in) planes of the three 1x1 weights
+    set(PH_NPACK_OUTS_GN, PH_PIECE_GN, 3 * C_PRED);
+    t.npieces = PH_NPACK_COUNT;
     t.total_u = (uint32_t)(g.pack_total / 16);
     t.f16 = g.prec == PH_PREC_F16;
 }
@@ -302,13 +235,10 @@ extern "C" int ph_neck_pack(const ph_neck_cfg* cfg, const float* const* params, 
     for (int i = 0; i < 3 * g.nconvs; ++i)
         if (!params[i]) { ph_set_error("ph_neck_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
     PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    NPackTable t;
+    PhPackTable t{};
     build_table(g, t);
     for (int i = 0; i < 3 * g.nconvs; ++i) t.p[i] = params[i];
-    const unsigned blocks = (t.total_u + 255u) / 256u;
-    hipLaunchKernelGGL(k_neck_pack, dim3(blocks < 2048u ? blocks : 2048u), dim3(256), 0, (hipStream_t)stream, t, (uint4*)pack);
-    PH_CHECK_LAUNCH();
-    return PH_OK;
+    return ph_pack_pieces("ph_neck_pack", t, pack, 2048, stream);
 }
 
 extern "C" int ph_neck_posenc(int H, int W, int num_feats, double temperature, double scale, double eps, float* out, void* stream) {
@@ -341,12 +271,7 @@ extern "C" int ph_neck_plan_create(const ph_neck_cfg* cfg, const void* pack, voi
     if (rc) return rc;
     PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
     *out = nullptr;
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    if (workspace_bytes < g.total) {
-        ph_set_error("ph_neck_plan_create: workspace too small (%zu < %zu)", workspace_bytes, g.total);
-        return PH_EWORKSPACE;
-    }
-    PH_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    PH_RUN(ph_check_buffers("ph_neck_plan_create", pack, workspace, workspace_bytes, g.total));
     ph_neck_plan* p = new (std::nothrow) ph_neck_plan;
     if (!p) { ph_set_error("ph_neck_plan_create: out of host memory"); return PH_EINVAL; }
     p->g = g;

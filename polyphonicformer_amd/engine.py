@@ -477,17 +477,50 @@ def _gather_params(module, device, count, name_of, numel_of):
     return params, (C.c_void_p * count)(*[t.data_ptr() for t in params])
 
 
+def _pack_on_device(params_from, cfg, device, bytes_fn, nparams, name_of, numel_of, pack_fn, what):
+    """the body of every native_*_pack* function: the `nparams` parameters of `params_from` (a module or a state_dict; names and
+    sizes from the library's table, `name_of(i)` / `numel_of(cfg, i)`) packed by `pack_fn` (`what`: its name) on the current stream
+    of `device` -> a new uint8 tensor of `bytes_fn(cfg)` bytes"""
+    nbytes = bytes_fn(C.byref(cfg))
+    if nbytes == 0:
+        raise _cfg_error(bytes_fn.__name__)
+    params, ptrs = _gather_params(params_from, device, nparams, name_of, lambda i: numel_of(C.byref(cfg), i))
+    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(pack_fn(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), what)
+    return blob
+
+
+def _pack_piece(blob, layout, i, dtype, shape):
+    """piece `i` of a pack layout as a view of the pack; None for an empty piece"""
+    off, nb = int(layout.offset[i]), int(layout.bytes[i])
+    return blob[off:off + nb].view(dtype).reshape(shape) if nb else None
+
+
+# a1's / the neck's grade of a cfg's mode code (as KHEAD_PREC maps the names), and the mode's name
+_GRADE_OF_MODE = {code: KHEAD_PREC[name] for name, code in _lib.PH_MODE.items()}
+_MODE_NAME = {code: name for name, code in _lib.PH_MODE.items() if name != "split"}
+
+
+class _OwnsHandles:
+    """the Python owner of native plans: its handle `_h`, or the values of `_handles`, are destroyed by the library's
+    `_destroy_symbol` when the object goes -- if the library is still loaded"""
+    _destroy_symbol = None
+
+    def _destroy(self):
+        for h in list(getattr(self, "_handles", {}).values()) + [getattr(self, "_h", None)]:
+            if h is not None and h.value and _lib._lib is not None:
+                getattr(_lib._lib, self._destroy_symbol)(h)
+        self._handles, self._h = {}, None
+
+    __del__ = _destroy
+
+
 def native_pack_stage(module, cfg, device):
     """one KernelUpdateHead stage's parameters packed on the device by ph_decode_pack_stage -> uint8 tensor (one pack)"""
     lib = _lib.load()
-    nbytes = lib.ph_decode_pack_bytes(C.byref(cfg))
-    if nbytes == 0:
-        raise _cfg_error("ph_decode_pack_bytes")
-    params, ptrs = _gather_params(module, device, _lib.PH_DECODE_NPARAMS, lib.ph_decode_param_name,
-                                  lambda i: lib.ph_decode_param_numel(C.byref(cfg), i))
-    pack = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    _lib.check(lib.ph_decode_pack_stage(C.byref(cfg), ptrs, _lib.ptr(pack), _lib.stream_ptr()), "ph_decode_pack_stage")
-    return pack
+    return _pack_on_device(module, cfg, device, lib.ph_decode_pack_bytes, _lib.PH_DECODE_NPARAMS, lib.ph_decode_param_name,
+                           lib.ph_decode_param_numel, lib.ph_decode_pack_stage, "ph_decode_pack_stage")
 
 
 def native_pack_from(pack, cfg):
@@ -505,10 +538,11 @@ def native_pack_from(pack, cfg):
     return blob
 
 
-class NativeDecodePlan:
+class NativeDecodePlan(_OwnsHandles):
     """DecodePlan's surface (set_inputs, run, run_from_planes, renew_outputs, outputs, capture / replay) over ONE native call per
     decode (ph_decode_run): the same launch sequence and geometry as the DecodePlan of the same arguments, so the same bits.
     `packs`: StagePacks (re-laid out as native packs once) or native packs (`native_pack_stage`)."""
+    _destroy_symbol = "ph_decode_destroy"
 
     def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False,
                  shares_gpu=False, num_classes=None, ffn_dim=None):
@@ -549,12 +583,6 @@ class NativeDecodePlan:
         self._in = None
         self.io = _lib.DecodeIO()
         self._alloc_outputs()
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.ph_decode_destroy(h)
-            self._h = None
 
     @property
     def out_code(self):
@@ -907,9 +935,7 @@ class NativeKernelHeadPack:
         lay = _lib.KheadLayout()
         _lib.check(lib.ph_khead_pack_layout(C.byref(cfg), C.byref(lay)), "ph_khead_pack_layout")
         self.blob, self.layout = blob, lay
-        # a1's grade of the cfg's mode, as KHEAD_PREC maps the names
-        self.prec = {_lib.PH_MODE["fp16"]: _lib.PH_PREC_F16, _lib.PH_MODE["bf16"]: _lib.PH_PREC_BF16}.get(cfg.mode, _lib.PH_PREC_SPLIT)
-        self.mode = cfg.mode
+        self.prec, self.mode = _GRADE_OF_MODE[cfg.mode], cfg.mode
         self.groups, self.n_init, self.n_seg = cfg.groups, cfg.num_proposals, cfg.num_classes
         P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
         dt = dict(wplanes=(torch.int16, (P, 3, 256, 256)), gn=(torch.float32, (3, 2, 256)),
@@ -920,30 +946,22 @@ class NativeKernelHeadPack:
                   w_init_f32=(torch.float32, (self.n_init, 256)), w_seg_f32=(torch.float32, (self.n_seg, 256)),
                   w_dd_f32=(torch.float32, (1, 256, 1, 1)))
         for i, name in enumerate(_lib.KPACK_PIECES):
-            off, nb = lay.offset[i], lay.bytes[i]
-            d, shape = dt[name]
-            setattr(self, name, blob[off:off + nb].view(d).reshape(shape) if nb else None)
+            setattr(self, name, _pack_piece(blob, lay, i, *dt[name]))
 
 
 def native_khead_pack(module, cfg, device):
     """KernelHead's own parameters (a module, or a state_dict without the neck's entries) packed on the device by ph_khead_pack"""
     lib = _lib.load()
-    nbytes = lib.ph_khead_pack_bytes(C.byref(cfg))
-    if nbytes == 0:
-        raise _cfg_error("ph_khead_pack_bytes")
-    params, ptrs = _gather_params(module, device, _lib.PH_KHEAD_NPARAMS, lib.ph_khead_param_name,
-                                  lambda i: lib.ph_khead_param_numel(C.byref(cfg), i))
-    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.ph_khead_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_khead_pack")
-    return NativeKernelHeadPack(blob, cfg)
+    return NativeKernelHeadPack(_pack_on_device(module, cfg, device, lib.ph_khead_pack_bytes, _lib.PH_KHEAD_NPARAMS, lib.ph_khead_param_name,
+                                                lib.ph_khead_param_numel, lib.ph_khead_pack, "ph_khead_pack"), cfg)
 
 
-class NativeKernelHeadPlan(_KernelHeadPlanBase):
+class NativeKernelHeadPlan(_KernelHeadPlanBase, _OwnsHandles):
     """KernelHeadPlan's surface (_KernelHeadPlanBase, run, timeouts, last_run_fell_back and the output attributes) over ONE
     native call per a1 (ph_khead_plan_run): the same launch sequence and geometry as the KernelHeadPlan of the same arguments, so
     the same bits.  `pack`: a NativeKernelHeadPack.  `dense_depth_proposal`: also write depth_proposal [B, N, 256] (what a C caller
     hands to ph_decode_io.q0; the module API keeps the reference's stride-0 view of the weight and needs no launch for it)."""
+    _destroy_symbol = "ph_khead_plan_destroy"
 
     def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
                  logit_dtype=torch.float32, onepass=None, frame_invariant=False, dense_depth_proposal=False, cfg=None):
@@ -953,9 +971,8 @@ class NativeKernelHeadPlan(_KernelHeadPlanBase):
         self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
         dev = torch.device(device)
         self.device, self.logit_dtype, self.want_f32 = dev, logit_dtype, want_f32
-        mode = {v: k for k, v in _lib.PH_MODE.items() if k != "split"}[pack.mode]
         self.cfg = cfg if cfg is not None else native_khead_cfg(B, H, W, pack.n_init, pack.n_seg, num_thing_classes, cat_stuff,
-                                                                pack.groups, mode, logit_dtype, want_f32, frame_invariant, onepass, nsplit)
+                                                                pack.groups, _MODE_NAME[pack.mode], logit_dtype, want_f32, frame_invariant, onepass, nsplit)
         lib = _lib.load()
         with torch.cuda.device(dev):
             nbytes = lib.ph_khead_plan_workspace_bytes(C.byref(self.cfg))
@@ -975,12 +992,6 @@ class NativeKernelHeadPlan(_KernelHeadPlanBase):
         self.dense_depth_proposal = dense_depth_proposal
         self.io = _lib.KheadIO()
         self._alloc_io(geo.P, pack.n_seg, want_f32, logit_dtype, dev, dense_depth_proposal)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.ph_khead_plan_destroy(h)
-            self._h = None
 
     def run(self):
         """one a1 call on the current stream: ONE native call"""
@@ -1257,12 +1268,9 @@ class NativeNeckPack:
         lay = _lib.NeckLayout()
         _lib.check(lib.ph_neck_pack_layout(C.byref(cfg), C.byref(lay)), "ph_neck_pack_layout")
         self.blob, self.layout, self.mode, self.groups, self.num_outs = blob, lay, cfg.mode, cfg.groups, cfg.num_outs
-        self.prec = {_lib.PH_MODE["fp16"]: _lib.PH_PREC_F16, _lib.PH_MODE["bf16"]: _lib.PH_PREC_BF16}.get(cfg.mode, _lib.PH_PREC_SPLIT)
+        self.prec = _GRADE_OF_MODE[cfg.mode]
         P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
-
-        def piece(i, dt, shape):
-            off, nb = lay.offset[i], lay.bytes[i]
-            return blob[off:off + nb].view(dt).reshape(shape) if nb else None
+        piece = lambda i, dt, shape: _pack_piece(blob, lay, i, dt, shape)
 
         def one(c):
             k = 3 if c < 7 else 1
@@ -1278,16 +1286,9 @@ class NativeNeckPack:
 def native_neck_pack(module, cfg, device):
     """the neck's parameters (a SemanticFPNWrapper, or its state_dict) packed on the device by ph_neck_pack"""
     lib = _lib.load()
-    nbytes = lib.ph_neck_pack_bytes(C.byref(cfg))
-    if nbytes == 0:
-        raise _cfg_error("ph_neck_pack_bytes")
-    params, ptrs = _gather_params(module, device, 3 * (7 + cfg.num_outs), lib.ph_neck_param_name,
-                                  lambda i: lib.ph_neck_param_numel(C.byref(cfg), i))
-    full = (C.c_void_p * _lib.PH_NECK_NPARAMS)(*[t.data_ptr() for t in params])      # absent aux convs: NULL
-    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.ph_neck_pack(C.byref(cfg), full, _lib.ptr(blob), _lib.stream_ptr()), "ph_neck_pack")
-    return NativeNeckPack(blob, cfg)
+    pack = lambda c, ptrs, blob, s: lib.ph_neck_pack(c, (C.c_void_p * _lib.PH_NECK_NPARAMS)(*ptrs), blob, s)      # absent aux convs: NULL
+    return NativeNeckPack(_pack_on_device(module, cfg, device, lib.ph_neck_pack_bytes, 3 * (7 + cfg.num_outs), lib.ph_neck_param_name,
+                                          lib.ph_neck_param_numel, pack, "ph_neck_pack"), cfg)
 
 
 def native_neck_posenc(H, W, num_feats, temperature=10000, scale=2 * math.pi, eps=1e-6, device="cuda:0"):
@@ -1299,18 +1300,18 @@ def native_neck_posenc(H, W, num_feats, temperature=10000, scale=2 * math.pi, ep
     return out
 
 
-class NativeNeckPlan:
+class NativeNeckPlan(_OwnsHandles):
     """NeckPlan's `run` surface over the native plan: ONE native call per forward (ph_neck_plan_run), or -- where NeckPlan would put
     the four level towers on their own streams -- ph_neck_plan_run_level on the same four streams and ph_neck_plan_run_outputs
     behind them; the same launch sequence and geometry as the NeckPlan of the same arguments, so the same bits.  `pack`: a
     NativeNeckPack.  `cfg`: a ph_neck_cfg to use as it is (the environment is then not consulted at all; its emit flags follow
     each run's `to_planes`) instead of `native_neck_cfg`'s."""
+    _destroy_symbol = "ph_neck_plan_destroy"
 
     def __init__(self, pack, B, shapes, device, pos_level=3, tower_streams=True, cfg=None):
         dev = torch.device(device)
         self.pack, self.B, self.shapes, self.device = pack, B, tuple(tuple(x) for x in shapes), dev
-        mode = {v: k for k, v in _lib.PH_MODE.items() if k != "split"}[pack.mode]
-        base = cfg if cfg is not None else native_neck_cfg(B, self.shapes, pack.groups, mode, pack.num_outs, pos_level, False,
+        base = cfg if cfg is not None else native_neck_cfg(B, self.shapes, pack.groups, _MODE_NAME[pack.mode], pack.num_outs, pos_level, False,
                                                            tower_streams, device_type=dev.type)
         self.cfg = _lib.NeckCfg.from_buffer_copy(bytes(base))
         self.pos_level, self.groups = self.cfg.pos_level, self.cfg.groups
@@ -1342,15 +1343,6 @@ class NativeNeckPlan:
         geo = _lib.NeckGeometry()
         _lib.check(_lib.load().ph_neck_plan_info(h, C.byref(geo)), "ph_neck_plan_info")
         return geo
-
-    def _destroy(self):
-        for h in getattr(self, "_handles", {}).values():
-            if h.value and _lib._lib is not None:
-                _lib._lib.ph_neck_plan_destroy(h)
-        self._handles = {}
-
-    def __del__(self):
-        self._destroy()
 
     def outputs(self, to_planes):
         """the output tensors of the planes / fp32 form (allocated on first use)"""
@@ -1510,10 +1502,7 @@ class NativeTrackPack:
         _lib.check(_lib.load().ph_track_pack_layout(C.byref(cfg), C.byref(lay)), "ph_track_pack_layout")
         self.blob, self.cfg, self.layout = blob, _lib.TrackCfg.from_buffer_copy(bytes(cfg)), lay
         self.prec, self.P = cfg.prec, 2 if cfg.prec == _lib.PH_PREC_SPLIT else 1
-
-        def piece(i, dtype, shape):
-            n = int(lay.bytes[i])
-            return blob[int(lay.offset[i]):int(lay.offset[i]) + n].view(dtype).reshape(shape)
+        piece = lambda i, dtype, shape: _pack_piece(blob, lay, i, dtype, shape)
         P, F, E, n = self.P, cfg.fc_out_channels, cfg.embed_channels, cfg.num_convs
         self.pk = dict(convs=[piece(i, torch.int16, (P, 256 * 2304)) for i in range(n)],
                        gn=[(piece(_lib.PH_TRACK_MAX_CONVS + i, torch.float32, (256,)),
@@ -1526,23 +1515,17 @@ class NativeTrackPack:
 def native_track_pack(module, cfg, device):
     """the track head's parameters (a QuasiDenseMaskEmbedHeadGTMask, or its state_dict) packed on the device by ph_track_pack"""
     lib = _lib.load()
-    nbytes = lib.ph_track_pack_bytes(C.byref(cfg))
-    if nbytes == 0:
-        raise _cfg_error("ph_track_pack_bytes")
-    count = 3 * cfg.num_convs + 4
-    params, ptrs = _gather_params(module, device, count, lambda i: lib.ph_track_param_name(C.byref(cfg), i),
-                                  lambda i: lib.ph_track_param_numel(C.byref(cfg), i))
-    blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _lib.check(lib.ph_track_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_track_pack")
-    return NativeTrackPack(blob, cfg)
+    return NativeTrackPack(_pack_on_device(module, cfg, device, lib.ph_track_pack_bytes, 3 * cfg.num_convs + 4,
+                                           lambda i: lib.ph_track_param_name(C.byref(cfg), i), lib.ph_track_param_numel, lib.ph_track_pack,
+                                           "ph_track_pack"), cfg)
 
 
-class NativeAssocPlan:
+class NativeAssocPlan(_OwnsHandles):
     """The association step of B frames over ph_panoptic_merge's device outputs: `run` is ONE launch-only native call
     (ph_assoc_plan_run: things tables, `sem`, boxes, RoIAlign, track embeddings -- capturable with torch.cuda.graph), `match` the one
     synchronising call behind it (ph_assoc_plan_match: the tracker and the `track` maps).  `pack`: a NativeTrackPack; `cfg`: a
     ph_assoc_cfg (`native_assoc_cfg`).  The outputs are this object's static tensors: the next call overwrites them."""
+    _destroy_symbol = "ph_assoc_plan_destroy"
 
     def __init__(self, pack, cfg, device):
         lib, dev = _lib.load(), torch.device(device)
@@ -1568,12 +1551,6 @@ class NativeAssocPlan:
         self.ids = torch.zeros((c.B, self.cap), dtype=torch.int64)
         self.io = _lib.AssocIO()
         self._keep = None
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value and _lib._lib is not None:
-            _lib._lib.ph_assoc_plan_destroy(h)
-            self._h = C.c_void_p()
 
     def rois(self):
         """the RoIs of the last run, fp32 [B, K, 5] (a view of the workspace; inspection)"""

@@ -30,10 +30,13 @@ SENTINEL = -123.25
 
 
 @functools.lru_cache(maxsize=None)
-def _head(precision):
-    sd = Hh.seeded_fill(Hh.TRACK_HEAD_SHAPES, 4321)
-    head = HEADS.build(dict(type="QuasiDenseMaskEmbedHeadGTMask", num_convs=4, num_fcs=1, embed_channels=256,
-                            norm_cfg=dict(type="GN", num_groups=32)))
+def _head(precision, num_convs=4, fc_out=1024, embed=256):
+    shapes = {k: v for k, v in Hh.TRACK_HEAD_SHAPES.items() if not k.startswith("track_head.convs.") or int(k.split(".")[2]) < num_convs}
+    shapes.update({"track_head.fcs.0.weight": (fc_out, 12544), "track_head.fcs.0.bias": (fc_out,),
+                   "track_head.fc_embed.weight": (embed, fc_out), "track_head.fc_embed.bias": (embed,)})
+    sd = Hh.seeded_fill(shapes, 4321)
+    head = HEADS.build(dict(type="QuasiDenseMaskEmbedHeadGTMask", num_convs=num_convs, num_fcs=1, fc_out_channels=fc_out,
+                            embed_channels=embed, norm_cfg=dict(type="GN", num_groups=32)))
     head.load_state_dict({k[len("track_head."):]: v for k, v in sd.items()})
     head.to("cuda:0").eval()
     head.precision = precision
@@ -102,19 +105,50 @@ def _table(things, b, cap):
 
 
 # ---- 1. packing
-@pytest.mark.parametrize("precision", ["fp32", "bf16"])
-def test_track_pack_is_get_packs_bytes(gpu, precision):
-    head = _head(precision)
-    ref, pk = head._get_pack(gpu), _pack(precision).pk
-    assert pk["P"] == ref["P"] and pk["prec"] == ref["prec"]
-    for i in range(4):
-        assert torch.equal(pk["convs"][i], ref["convs"][i]), i
+def _pack_into_poison(head, gpu):
+    """ph_track_pack into a buffer filled with 0xA5 (stale bytes cannot pass for padding) -> NativeTrackPack"""
+    lib, cfg = _lib.load(), E.native_track_cfg(head)
+    params, ptrs = E._gather_params(head, gpu, 3 * cfg.num_convs + 4, lambda i: lib.ph_track_param_name(C.byref(cfg), i),
+                                    lambda i: lib.ph_track_param_numel(C.byref(cfg), i))
+    blob = torch.full((lib.ph_track_pack_bytes(C.byref(cfg)),), 0xA5, dtype=torch.uint8, device=gpu)
+    _lib.check(lib.ph_track_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_track_pack")
+    torch.cuda.synchronize()
+    return E.NativeTrackPack(blob, cfg)
+
+
+def _assert_pack_is_get_pack(head, pack, gpu):
+    """piece by piece against `_get_pack`; the pieces of the absent convs are empty and every byte outside the pieces is zero"""
+    ref, pk, n = head._get_pack(gpu), pack.pk, head.num_convs
+    assert pk["P"] == ref["P"] and pk["prec"] == ref["prec"] and len(pk["convs"]) == len(pk["gn"]) == n
+    for i in range(n):
+        assert pk["convs"][i].shape == ref["convs"][i].shape and torch.equal(pk["convs"][i], ref["convs"][i]), i
         assert torch.equal(pk["gn"][i][0], ref["gn"][i][0]) and torch.equal(pk["gn"][i][1], ref["gn"][i][1]), i
     for k in ("fc", "emb", "fc_b", "emb_b"):
         assert pk[k].shape == ref[k].shape and torch.equal(pk[k], ref[k]), k
-    # padding is zero, so two packings are byte-equal
-    again = E.native_track_pack(head, E.native_track_cfg(head), gpu)
-    assert torch.equal(again.blob, _pack(precision).blob)
+    lay = pack.layout
+    for i in range(n, _lib.PH_TRACK_MAX_CONVS):
+        assert lay.bytes[i] == lay.bytes[_lib.PH_TRACK_MAX_CONVS + i] == lay.bytes[2 * _lib.PH_TRACK_MAX_CONVS + i] == 0, i
+    covered = torch.zeros_like(pack.blob, dtype=torch.bool)
+    for i in range(_lib.PH_TPACK_COUNT):
+        covered[lay.offset[i]:lay.offset[i] + lay.bytes[i]] = True
+    assert int(pack.blob[~covered].ne(0).sum()) == 0
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_track_pack_is_get_packs_bytes(gpu, precision):
+    head = _head(precision)
+    pack = _pack_into_poison(head, gpu)
+    _assert_pack_is_get_pack(head, pack, gpu)
+    # padding is zero, so a packing into other stale bytes is byte-equal
+    assert torch.equal(pack.blob, _pack(precision).blob)
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_track_pack_of_a_small_head_is_get_packs_bytes(gpu, precision):
+    """2 convs, fc_out_channels 64, embed_channels 32: fc_embed's plain-K fragments with K = 64 (two k-steps) and the 49-tap
+    permutation of fcs.0 with sizes other than the default's -- a wrong K / 32 or tap stride cancels nowhere at this size"""
+    head = _head(precision, 2, 64, 32)
+    _assert_pack_is_get_pack(head, _pack_into_poison(head, gpu), gpu)
 
 
 # ---- 2. things table

@@ -77,11 +77,15 @@ def _bytes(t):
 @pytest.mark.parametrize("precision", ["fp16", "bf16", "fp32"])
 def test_packing_is_kernel_head_pack_byte_for_byte(gpu, precision):
     """every piece ph_khead_pack writes against the tensor KernelHeadPack builds on the host from the same state_dict, pad rows
-    included; the alignment padding is zero and two packings are byte-equal"""
+    included; the alignment padding is zero after packing into a poisoned buffer, so two packings are byte-equal"""
+    lib = _lib.load()
     h, sd = _head(precision)
     ref = E.KernelHeadPack(sd, E.KHEAD_PREC[precision], gpu, 32)
-    nat, cfg = _native_pack(precision, gpu)
-    again, _ = _native_pack(precision, gpu)
+    again, cfg = _native_pack(precision, gpu)
+    params, ptrs = E._gather_params(sd, gpu, _lib.PH_KHEAD_NPARAMS, lib.ph_khead_param_name, lambda i: lib.ph_khead_param_numel(C.byref(cfg), i))
+    blob = torch.full((lib.ph_khead_pack_bytes(C.byref(cfg)),), 0xA5, dtype=torch.uint8, device=gpu)
+    _lib.check(lib.ph_khead_pack(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), "ph_khead_pack")
+    nat = E.NativeKernelHeadPack(blob, cfg)
     torch.cuda.synchronize()
     assert torch.equal(nat.blob, again.blob)
     assert (nat.prec, nat.n_init, nat.n_seg, nat.groups) == (ref.prec, ref.n_init, ref.n_seg, ref.groups)
