@@ -804,9 +804,8 @@ int ph_decode_run(ph_decode* plan, const ph_decode_io* io, void* stream);
  * (PH_FEAT_PLANES: x = xp, depth_feats = dp, bits = bits, k0 = proposal, q0 = depth_proposal).  Conventions are ph_decode_*'s:
  * status codes + ph_last_error_string, caller-owned memory, no allocation of device memory, no synchronisation and no host read
  * of device data in pack / create / run, every argument or geometry error returned before the first launch.  No ph_khead_plan_*
- * / ph_khead_pack* function reads the environment: the plan's launches go through internal forms of ph_khead_onepass /
- * ph_khead_fused_if that take their launch knobs as arguments (the public entry points keep reading PH_KHEAD1_PAIR /
- * PH_NECK_STATS3 / PH_NECK_APPLY3), and what engine.KernelHeadPlan reads from PH_KHEAD_TWOPASS / PH_POOL_NSPLIT are the cfg's
+ * / ph_khead_pack* function reads the environment: the plan's launches are the public ph_khead_onepass / ph_khead_fused_if,
+ * which read none either, and what engine.KernelHeadPlan reads from PH_KHEAD_TWOPASS / PH_POOL_NSPLIT are the cfg's
  * `onepass` / `nsplit` fields.  The only process-wide setting a plan honours is ph_khead_onepass_set_timeout_us.
  * A zero-initialised ph_khead_cfg plus the sizes and the mode is the module API's configuration.
  *   mode         PH_MODE_*, mapped to a1's grade as engine.KHEAD_PREC maps the precision names: PH_MODE_FP16 -> PH_PREC_F16 (one
@@ -932,9 +931,9 @@ int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
  * ph_khead_*'s: status codes + ph_last_error_string, caller-owned 256-byte aligned memory, no allocation of device memory, no
  * synchronisation and no host read of device data in pack / posenc / create / run, every argument or geometry error returned
  * before the first launch.  No ph_neck_plan_* / ph_neck_pack* / ph_neck_posenc function reads the environment: the plan's
- * launches go through internal forms of ph_conv_nhwc / ph_gn_sum_planes / ph_gn_apply / ph_neck_out_convs that take their launch
- * knobs as arguments (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW /
- * PH_CPLANES_TPW / PH_NECK_STATS3 / PH_NECK_APPLY3), and what engine.NeckPlan reads from PH_NECK_OUT2 / PH_NECK_C16 /
+ * launches go through internal forms of ph_conv_nhwc / ph_gn_sum_planes / ph_gn_apply that take their launch knobs as arguments
+ * (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW / PH_CPLANES_TPW; ph_neck_out_convs
+ * has no knobs), and what engine.NeckPlan reads from PH_NECK_OUT2 / PH_NECK_C16 /
  * PH_NECK_STREAMS are the cfg's `fused_out` / `c16` / `tower_buffers` fields (PH_NECK_OUT2=0 -> fused_out PH_KNOB_OFF,
  * PH_NECK_C16=0 -> c16 PH_KNOB_OFF, PH_NECK_STREAMS=0 -> tower_buffers 0; the measurement forms PH_NECK_OUT2=2 / 3 have no field).
  * A zero-initialised ph_neck_cfg plus the sizes, the mode, num_outs, pos_level and an emit flag is the module API's configuration.

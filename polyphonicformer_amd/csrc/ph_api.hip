@@ -23,5 +23,14 @@ int ph_check_buffers(const char* fn, const void* pack_or_null, const void* works
     return PH_OK;
 }
 
+int ph_num_cus() {
+    static const int n = [] {
+        int dev = 0, cu = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+        return cu > 0 ? cu : 0;
+    }();
+    return n;
+}
+
 extern "C" int ph_version(void) { return PH_VERSION; }
 extern "C" const char* ph_last_error_string(void) { return g_err; }

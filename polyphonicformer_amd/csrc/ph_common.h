@@ -55,6 +55,9 @@ static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 // NULL, workspace size (PH_EWORKSPACE), workspace alignment; the messages carry the public function's name (ph_api.hip)
 int ph_check_buffers(const char* fn, const void* pack_or_null, const void* workspace, size_t workspace_bytes, size_t need);
 
+// compute units of the current device, asked once per process (the first device's answer stays); 0 when the query fails
+int ph_num_cus();
+
 // ---- the weight packs of the native KernelHead / neck / association plans: one kernel (ph_wpack.hip) writes a pack from a table of
 // its pieces.  A piece is a run of 16-byte units of one kind; what lies between its data and the next piece is padding (zeros).
 enum {
@@ -102,14 +105,14 @@ int ph_pack_pieces(const char* fn, const PhPackTable& t, void* pack, unsigned ma
 #define PH_BIN_THR 0x1.8p-24f
 
 // ---- launch knobs of the decode kernels.  The public entry points (ph_dynconv, ph_dynconv_up2[_wgs], ph_query_stage[_counts])
-// fill them from environment variables -- A/B measurement aids and test switches -- and call the *_k forms below;
-// the native decode plan (ph_decode.hip) passes the defaults explicitly and so reads no environment at all.
+// fill them from environment variables -- geometry knobs and test switches -- and call the *_k forms below;
+// the native decode plan (ph_decode.hip) passes the defaults explicitly and so reads no environment at all.  KernelHead's post-neck
+// kernels (ph_khead.hip, ph_khead1.hip) have no knobs: their public entry points are what the native plans call.
 struct PhConvKnobs {
     int wgs = 0;                 // PH_CONV_WGS: workgroups (0 = one per CU)
 };
 struct PhUp2Knobs {
     int wgs = 0;                 // PH_UP2_WGS: overrides the caller's workgroup count (0 = keep it)
-    int dbg = 0;                 // PH_UP2_DBG (timing experiments)
 };
 struct PhQueryKnobs {
     int nrt = 0;                             // PH_QUERY_NRT: row blocks per workgroup (0 = the launch's own choice)
@@ -125,27 +128,6 @@ int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int ns
                             const float* k_in, const float* q_in, const uint16_t* wb, const float* wf, const ph_stage_layout* layout,
                             float* obj, float* dobj, float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                             size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream);
-
-// launch knobs of KernelHead's post-neck kernels, in the same way: the public ph_khead_onepass / ph_khead_fused[_if] / ph_khead_conv_gn /
-// ph_neck_out_convs fill them from PH_KHEAD1_PAIR / PH_NECK_STATS3 / PH_NECK_APPLY3; the native KernelHead plan (ph_kheadplan.hip)
-// passes the defaults
-struct PhKheadKnobs {
-    bool pair = false;           // PH_KHEAD1_PAIR: two 64-pixel workgroups per CU (builds with -DK1_WITH_PAIR only)
-    bool stats3 = true;          // PH_NECK_STATS3=0: the 3-D statistics grid when the three maps share one input
-    bool apply3 = true;          // PH_NECK_APPLY3=0: plain mode's apply pass as one launch per map
-};
-int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
-                       const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init, const uint16_t* w2_seg,
-                       const float* bias_seg, int n_seg, const uint16_t* w2_dd, const float* bias_dd, int stuff_lo, int n_stuff,
-                       uint16_t* x_planes, uint16_t* dfe_planes, float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds,
-                       void* depth_pred, int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
-                       int64_t HW, int prec, int input_format, void* stream);
-int ph_khead_fused_if_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,
-                        const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init, const uint16_t* w2_seg,
-                        const float* bias_seg, int n_seg, const uint16_t* w2_dd, const float* bias_dd, int stuff_lo, int n_stuff,
-                        uint16_t* x_planes, uint16_t* dfe_planes, float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds,
-                        void* depth_pred, int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
-                        int64_t HW, int prec, int input_format, void* stream);
 
 // launch knobs of the neck's kernels (ph_neck.hip), in the same way: the public ph_conv_nhwc / ph_gn_sum_planes / ph_gn_sum_cplanes /
 // ph_gn_apply fill them from PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW / PH_CPLANES_TPW; the native neck plan
@@ -166,10 +148,6 @@ int ph_gn_sum_cplanes_k(const PhNeckKnobs& kn, const float* const* ys, const flo
                         const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
 int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
                   int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream);
-int ph_neck_out_convs_k(const PhKheadKnobs& kn, const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes,
-                        const float* gn_affine, int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1,
-                        uint16_t* out_planes2, float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace,
-                        size_t workspace_bytes, int B, int64_t HW, int prec, void* stream);
 
 // device-count forms of the association step's kernels (ph_track.hip) for the native association plan (ph_assocplan.hip): B frames per
 // launch, the grids sized for `cap` RoIs per frame, every workgroup reading its frame's count from the things tables on the device

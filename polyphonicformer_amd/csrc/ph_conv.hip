@@ -41,11 +41,7 @@ template <int PF, int PK, int NRT, bool BITS, typename OutT> struct ConvCfg {
     static constexpr int NDW = conv_dma_waves(NW, 32 * PF);                    // waves that issue DMA
     static constexpr int DPW = 32 * PF / NDW;                                  // ... instructions each per tile
     static constexpr int KBB = NW * 32 * 4;                                    // per-wave copy of its 32 biases
-#ifndef CONV_NBUF_MAX        // A/B timing: -DCONV_NBUF_MAX=2 (+ PH_CONV_WGS=512): two half-CU workgroups per CU instead of one that owns the CU
-#define CONV_NBUF_MAX 4
-#endif
-    static constexpr int NBUF_FIT = 4 * TILEB + PATCHB + KBB <= LDS_MAX ? 4 : (3 * TILEB + PATCHB + KBB <= LDS_MAX ? 3 : 2);
-    static constexpr int NBUF = NBUF_FIT < CONV_NBUF_MAX ? NBUF_FIT : CONV_NBUF_MAX;
+    static constexpr int NBUF = 4 * TILEB + PATCHB + KBB <= LDS_MAX ? 4 : (3 * TILEB + PATCHB + KBB <= LDS_MAX ? 3 : 2);   // ring depth: at most 4
     static constexpr int LDSB = NBUF * TILEB + PATCHB + KBB;
 };
 
@@ -232,9 +228,7 @@ __global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT>::NW * 64)) void k
                     lds_write128_asm(tb + r * LANES * 16, __builtin_bit_cast(u32x4_t, h16));
                 }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef CONV_ABL_NO_COOP_BARRIER          // timing only (wrong results): what the conversion's barrier costs per tile
             __builtin_amdgcn_s_barrier();
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
 
@@ -313,16 +307,6 @@ __global__ __launch_bounds__((ConvCfg<PF, PK, NRT, BITS, OutT>::NW * 64)) void k
     flush();
 }
 
-static int conv_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
 template <int PF, int PK, int E, int NRT>
 static int launch_conv(const uint16_t* planes, const uint16_t* kern, int64_t kps, int64_t kbs, const float* kbias,
                        int64_t bbs, uint32_t* bits_out, void* logits_out, int out_dtype, int64_t obs, int B, int N,
@@ -330,7 +314,8 @@ static int launch_conv(const uint16_t* planes, const uint16_t* kern, int64_t kps
     const int64_t HWp = ph_hw_padded(HW);
     const int64_t total = (int64_t)B * (HWp / CONV_T);
     // one persistent workgroup per CU (it owns the CU's LDS), tiles split evenly: no tail generation
-    int wgs = conv_num_cus();
+    int wgs = ph_num_cus();
+    if (wgs <= 0) wgs = 256;             // the query failed: the MI355X's count
     if (kn.wgs) wgs = kn.wgs;
     if (wgs > total) wgs = (int)total;
     if (wgs < 1) wgs = 1;

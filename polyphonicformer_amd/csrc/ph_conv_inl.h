@@ -1,4 +1,4 @@
-// Device helpers shared by the dynamic-convolution kernels (ph_conv.hip: k_dynconv; ph_convup.hip: k_dynconv_up2m): the LDS
+// Device helpers shared by the dynamic-convolution kernels (ph_conv.hip: k_dynconv; ph_convup.hip: k_dynconv_up2m; ph_convpool.hip: k_dynconv_poolx): the LDS
 // accesses of the tile loop as inline asm, the swizzle of the LDS-DMA tile image, the MFMA phase of one 32-pixel half.
 #pragma once
 #include "ph_common.h"
@@ -20,6 +20,11 @@ template <int OFF> __device__ __forceinline__ u32x2_t lds_tr16_asm(uint32_t byte
 __device__ __forceinline__ u32x4_t lds_read128_asm(uint32_t byte_addr) {
     u32x4_t v;
     asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(byte_addr));
+    return v;
+}
+template <int OFF> __device__ __forceinline__ u32x4_t lds_read128o_asm(uint32_t byte_addr) {      // ... at an immediate offset
+    u32x4_t v;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
     return v;
 }
 template <int OFF> __device__ __forceinline__ void lds_write_asm(uint32_t byte_addr, float v, float*) {

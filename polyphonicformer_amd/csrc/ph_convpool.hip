@@ -33,8 +33,6 @@
 // as it lies in LDS: bf16 / fp16 planes as they are; in the `mixed16` grade the tile has been converted to fp16 for the convolution, which
 // is exact for every bf16 value inside fp16's normal range (values below 6.1e-5 in magnitude lose bits there: features after GroupNorm +
 // ReLU are O(1), the pooled sums are not affected at the 1e-3 contract's scale; tests compare with `k_pool` at 1e-6).
-//
-// -DCP_ABL_NO_CONV / NO_POOL / NO_BALLOT: timing experiments (wrong results) -- what each phase costs inside the ring.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -52,11 +50,6 @@ __device__ __forceinline__ uint32_t cp_lds_read32(uint32_t byte_addr) {
 }
 __device__ __forceinline__ void cp_lds_write32(uint32_t byte_addr, uint32_t v) {
     asm volatile("ds_write_b32 %0, %1" ::"v"(byte_addr), "v"(v) : "memory");
-}
-template <int OFF> __device__ __forceinline__ u32x4_t cp_lds_read128(uint32_t byte_addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
-    return v;
 }
 
 template <int E> __device__ __forceinline__ uint4 cp_expand8(uint32_t byte) {
@@ -114,10 +107,9 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
     const uint32_t lds0 = lds_addr(lds);
 
     // bf16 -> fp16 of a whole tile in place (`mixed16`), every wave of the workgroup: 2048 16-byte pieces, one round at a time
-#ifndef CP_CONV_PIECES
-#define CP_CONV_PIECES 1024          // of the tile's 2048 16-byte pieces, how many the CONVOLUTION waves convert (the pooling waves: the rest).
-                                     // Measured on one box, 32 frames: 1024 (equal) 246-252 us, 640: 249-251, 320: 254, 0: 343 -- equal shares stay
-#endif
+    // of the tile's 2048 16-byte pieces, how many the CONVOLUTION waves convert (the pooling waves: the rest).
+    // Measured on one box, 32 frames: 1024 (equal) 246-252 us, 640: 249-251, 320: 254, 0: 343 -- equal shares stay
+    constexpr int CP_CONV_PIECES = 1024;
     auto convert = [&](int buf, auto role_tag) {
         constexpr bool CONVW = decltype(role_tag)::value;
         constexpr int PIECES = 256 * CONV_T * 2 / 16, P0 = CONVW ? 0 : CP_CONV_PIECES, NP = CONVW ? CP_CONV_PIECES : PIECES - CP_CONV_PIECES;
@@ -178,7 +170,6 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
             f32x16_t acc0, acc1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc0[r] = bias[r]; acc1[r] = bias[r]; }
-#ifndef CP_ABL_NO_CONV
             u32x2_t q[2][4];                                            // [k-step parity][half 0 rows, rows + 4, half 1 rows, rows + 4]
             auto rd = [&](auto ks_tag, u32x2_t (&d)[4]) {
                 constexpr int KS = decltype(ks_tag)::value;
@@ -208,7 +199,6 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
             step(std::integral_constant<int, 9>{}); step(std::integral_constant<int, 10>{}); step(std::integral_constant<int, 11>{});
             step(std::integral_constant<int, 12>{}); step(std::integral_constant<int, 13>{}); step(std::integral_constant<int, 14>{});
             step(std::integral_constant<int, 15>{});
-#endif
             // mask words (k_dynconv's ballot; pixels past HW and rows past N cleared): lane l < 32 = row l's word of pixels 0 .. 31, lane
             // 32 + l = its word of pixels 32 .. 63
             int word = 0;
@@ -227,12 +217,8 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
                     asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(wd) : "s"((uint32_t)(m[r] >> 32) & pxmask), "n"(rr + 4));
                 }
             };
-#ifndef CP_ABL_NO_BALLOT
             ballots(acc0, word, std::integral_constant<int, 0>{});
             ballots(acc1, word, std::integral_constant<int, 1>{});
-#else
-            word = (int)(__float_as_uint(acc0[0] + acc1[3]));
-#endif
             if (!live_row) word = 0;
             cp_lds_write32(bw_w + (uint32_t)par * (Npad * 2 * 4), (uint32_t)word);
             *(uint32_t*)optr = (uint32_t)word;
@@ -314,20 +300,20 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
                 constexpr int S = decltype(s_tag)::value;
                 const u32x4_t a = lds_read128_asm(lut_addr + (((w >> (8 * S)) & 0xFFu) << 4));
                 const uint32_t ad = tb + 16u * (uint32_t)((4 * g + S) ^ pf);
-                u32x4_t d0 = cp_lds_read128<0 * 4096>(ad), d1 = cp_lds_read128<1 * 4096>(ad);
-                u32x4_t d2 = cp_lds_read128<2 * 4096>(ad), d3 = cp_lds_read128<3 * 4096>(ad);
+                u32x4_t d0 = lds_read128o_asm<0 * 4096>(ad), d1 = lds_read128o_asm<1 * 4096>(ad);
+                u32x4_t d2 = lds_read128o_asm<2 * 4096>(ad), d3 = lds_read128o_asm<3 * 4096>(ad);
                 asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 pacc[0] = mfma32e<E>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, d0), pacc[0]);
                 pacc[1] = mfma32e<E>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, d1), pacc[1]);
                 __builtin_amdgcn_sched_barrier(0);
-                d0 = cp_lds_read128<4 * 4096>(ad); d1 = cp_lds_read128<5 * 4096>(ad);
+                d0 = lds_read128o_asm<4 * 4096>(ad); d1 = lds_read128o_asm<5 * 4096>(ad);
                 asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 pacc[2] = mfma32e<E>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, d2), pacc[2]);
                 pacc[3] = mfma32e<E>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, d3), pacc[3]);
                 __builtin_amdgcn_sched_barrier(0);
-                d2 = cp_lds_read128<6 * 4096>(ad); d3 = cp_lds_read128<7 * 4096>(ad);
+                d2 = lds_read128o_asm<6 * 4096>(ad); d3 = lds_read128o_asm<7 * 4096>(ad);
                 asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
                 pacc[4] = mfma32e<E>(__builtin_bit_cast(uint4, a), __builtin_bit_cast(uint4, d0), pacc[4]);
@@ -340,10 +326,8 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
             };
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // the word
             __builtin_amdgcn_sched_barrier(0);
-#ifndef CP_ABL_NO_POOL
             pstep(std::integral_constant<int, 0>{}); pstep(std::integral_constant<int, 1>{});
             pstep(std::integral_constant<int, 2>{}); pstep(std::integral_constant<int, 3>{});
-#endif
         }
         cur = cur + 1 == NBUF ? 0 : cur + 1;
         par ^= 1;

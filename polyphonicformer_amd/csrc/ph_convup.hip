@@ -25,35 +25,16 @@
 
 #include "ph_conv_inl.h"
 
-template <int OFF> __device__ __forceinline__ u32x4_t lds_read128o_asm(uint32_t byte_addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(byte_addr), "n"(OFF));
-    return v;
-}
 __device__ __forceinline__ void lds_wait_all() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
 
 // The upsampled rows and the low-resolution rows leave as whole, aligned 128-byte lines (8 lanes x 16 bytes per query row), so
-// they can bypass the caches like the stand-alone upsample kernel's output (-DUP2_CACHED_STORES: default policy, for A/B runs).
+// they bypass the caches like the stand-alone upsample kernel's output (st_nt16).
 // The first version of this kernel emitted windows shifted by 16 bytes (no data of the NEXT half needed, but every line
 // completed by two stores): 609 us per 24 frames with cached stores, 1 ms with non-temporal ones, 268 us with the stores
 // compiled out -- the memory system, not the arithmetic, and the reason for the one-half-late emission below.
-__device__ __forceinline__ void up_store(void* p, uint4 v) {
-#ifdef UP2_CACHED_STORES
-    *(uint4*)p = v;
-#else
-    st_nt16(p, v);
-#endif
-}
-
-// timing experiments only (-DUP2_TIMING + PH_UP2_DBG=bits at run time): 1 = no stores, 2 = no window passes, 4 = every row silent
-#ifdef UP2_TIMING
-#define UP2_DBG(bit) (dbg & (bit))
-#else
-#define UP2_DBG(bit) false
-#endif
 
 template <typename OutT> struct UpElem;
 template <> struct UpElem<ph_h16> { static constexpr int E = PH_E_F16; };
@@ -130,7 +111,7 @@ template <int E, int NRT, int NTR, bool LOWRES, typename OutT>
 __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_t* __restrict__ planes, const uint16_t* __restrict__ kern,
                                                                   int64_t kern_batch_stride, const float* __restrict__ kbias,
                                                                   int64_t kbias_batch_stride, OutT* __restrict__ logits_out,
-                                                                  OutT* __restrict__ up_out, int B, int N, int H, int dbg) {
+                                                                  OutT* __restrict__ up_out, int B, int N, int H) {
     using C = UpmCfg<NRT>;
     constexpr int NBUF = C::NBUF, W = NTR * 64, ROWT = C::ROWT, EO = UpElem<OutT>::E, NH = 2 * NTR;
     constexpr bool COOP = E == PH_E_F16_FROM_BF16;
@@ -234,7 +215,6 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
         if constexpr (MP >= 0) kp = lds_read128o_asm<MP * 1024>(cf);
         lds_wait_all();
         const uint4 KC = __builtin_bit_cast(uint4, kc), KE = __builtin_bit_cast(uint4, ke), KP = __builtin_bit_cast(uint4, kp);
-#ifndef UPM_SERIAL_TILES
         // the two tiles' chains interleaved (each MFMA waits for its own predecessor only: one other product in between)
         f32x16_t a0 = zero16, a1 = zero16;
         if constexpr (MP >= 0) { a0 = mf(KP, P0, a0); a1 = mf(KP, P1, a1); }
@@ -251,25 +231,6 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
             lds_write64_asm<64>(tw_addr, w[0], w[1]); lds_write64_asm<80>(tw_addr, w[2], w[3]);
             lds_write64_asm<96>(tw_addr, w[4], w[5]); lds_write64_asm<112>(tw_addr, w[6], w[7]);
         }
-#else
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            f32x16_t a = zero16;
-            if constexpr (MP >= 0) a = mf(KP, t == 0 ? P0 : P1, a);
-            a = mf(KC, t == 0 ? C0 : C1, a);
-            a = mf(KE, t == 0 ? e0 : e1, a);
-            uint32_t w[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) w[j] = f2e_pk<EO>(a[2 * j], a[2 * j + 1]);
-            if (t == 0) {
-                lds_write64_asm<0>(tw_addr, w[0], w[1]);  lds_write64_asm<16>(tw_addr, w[2], w[3]);
-                lds_write64_asm<32>(tw_addr, w[4], w[5]); lds_write64_asm<48>(tw_addr, w[6], w[7]);
-            } else {
-                lds_write64_asm<64>(tw_addr, w[0], w[1]); lds_write64_asm<80>(tw_addr, w[2], w[3]);
-                lds_write64_asm<96>(tw_addr, w[4], w[5]); lds_write64_asm<112>(tw_addr, w[6], w[7]);
-            }
-        }
-#endif
         lds_wait_all();
         uint32_t tr = tr_addr;
         asm volatile("" : "+v"(tr));
@@ -279,12 +240,12 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
         lds_wait_all();
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
-            if (rt * 32 + sq + 8 * kk < N && !UP2_DBG(1)) up_store(dst_row + kk * up_kk_bytes + up_lane_off, __builtin_bit_cast(uint4, x[kk]));
+            if (rt * 32 + sq + 8 * kk < N) st_nt16(dst_row + kk * up_kk_bytes + up_lane_off, __builtin_bit_cast(uint4, x[kk]));
     };
     int cur = 0, cur_b = -1;
     for (int gr = R0 - halo; gr < R1; ++gr) {
         const int b = gr / H, r = gr - b * H;
-        const bool silent = gr < R0 || UP2_DBG(4), first = r == 0, last = r == H - 1;
+        const bool silent = gr < R0, first = r == 0, last = r == H - 1;
         if (!producer && b != cur_b) {
             const uint16_t* kr = kern + (int64_t)b * kern_batch_stride + (rt * 32 + (lane & 31)) * PH_C + g * 8;
 #pragma unroll
@@ -402,13 +363,12 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
                             // the half before this one (HH - 1): `prev` of ITS position still holds its P row
                             constexpr int TCp = (HH > 0) ? (HH - 1) / 2 : 0, hp = (HH > 0) ? (HH - 1) % 2 : 0;
                             if constexpr (HH > 0) {
-                                if (!UP2_DBG(2))
-                                    emit(std::integral_constant<int, HH - 1>{}, prev[TCp][hp][0], prev[TCp][hp][1], Cp0, Cp1, Pe, Ce, prev[TC][h][0].x, cu0.x);
+                                emit(std::integral_constant<int, HH - 1>{}, prev[TCp][hp][0], prev[TCp][hp][1], Cp0, Cp1, Pe, Ce, prev[TC][h][0].x, cu0.x);
                                 Pe = prev[TCp][hp][1].w; Ce = Cp1.w;             // its pixel 31: the left neighbour of half HH
                                 prev[TCp][hp][0] = Cp0; prev[TCp][hp][1] = Cp1;  // ... and now it becomes the next image row's P row
                             }
                             if constexpr (HH == NH - 1) {
-                                if (!UP2_DBG(2)) emit(std::integral_constant<int, HH>{}, prev[TC][h][0], prev[TC][h][1], cu0, cu1, Pe, Ce, 0u, 0u);
+                                emit(std::integral_constant<int, HH>{}, prev[TC][h][0], prev[TC][h][1], cu0, cu1, Pe, Ce, 0u, 0u);
                                 prev[TC][h][0] = cu0; prev[TC][h][1] = cu1;
                             } else {
                                 Cp0 = cu0; Cp1 = cu1;                            // waits for its right neighbour
@@ -431,16 +391,6 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
 }
 
 // ====================================================================================================================
-static int up_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-    }
-    return n;
-}
-
 // 1 when the fused final conv + x2 upsample exists for this geometry / arithmetic (otherwise: ph_dynconv + ph_upsample2x)
 extern "C" int ph_dynconv_up2_supported(int N, int H, int W, int prec, int out_dtype) {
     // instantiated for NTR = 4 (W = 256 = 2048 / 8) and 3..7 row blocks: 65 <= N <= 224 (8 row blocks would be 9 waves, three on
@@ -457,11 +407,11 @@ static void launch_up(const uint16_t* planes, const uint16_t* kern, int64_t kbs,
                       void* up_out, int B, int N, int H, int want_wgs, const PhUp2Knobs& kn, hipStream_t s) {
     constexpr int NTR = 4;
     const int64_t rows = (int64_t)B * H;
-    int wgs = want_wgs > 0 ? want_wgs : up_num_cus();
+    int wgs = want_wgs > 0 ? want_wgs : ph_num_cus();
+    if (wgs <= 0) wgs = 256;             // the query failed: the MI355X's count
     if (kn.wgs > 0) wgs = kn.wgs;
     if (wgs > rows) wgs = (int)rows;
     const dim3 grid(wgs), block((NRT + 1) * 64);
-    const int dbg = kn.dbg;
     constexpr int lds = UpmCfg<NRT>::LDSB;
 #define UP_GO(LR)                                                                                                             \
     do {                                                                                                                      \
@@ -471,7 +421,7 @@ static void launch_up(const uint16_t* planes, const uint16_t* kern, int64_t kbs,
         }();                                                                                                                  \
         (void)once;                                                                                                           \
         hipLaunchKernelGGL((k_dynconv_up2m<E, NRT, NTR, LR, OutT>), grid, block, lds, s, planes, kern, kbs, kbias, bbs, (OutT*)logits_out, \
-                           (OutT*)up_out, B, N, H, dbg);                                                                           \
+                           (OutT*)up_out, B, N, H);                                                                                \
     } while (0)
     if (logits_out) UP_GO(true);
     else UP_GO(false);
@@ -514,10 +464,8 @@ extern "C" int ph_dynconv_up2_wgs(const uint16_t* planes, const uint16_t* kern, 
                                   int prec, int workgroups, void* stream) {
     PhUp2Knobs kn;
     // test knob, read per launch on purpose (tests/test_gpu_kernels.py switches it inside one process; an eager launch pays the
-    // environment look-up, a graph replay none); PH_UP2_DBG: timing experiments only, read once
+    // environment look-up, a graph replay none)
     if (const char* e = getenv("PH_UP2_WGS")) kn.wgs = atoi(e) > 0 ? atoi(e) : 0;
-    static const int dbg = [] { const char* e = getenv("PH_UP2_DBG"); return e ? atoi(e) : 0; }();
-    kn.dbg = dbg;
     return ph_dynconv_up2_k(kn, planes, kern, kern_batch_stride, kbias, kbias_batch_stride, logits_out, up_out, out_dtype, B, N, H, W, prec,
                             workgroups, stream);
 }

@@ -134,7 +134,7 @@ static int resolve(const ph_decode_cfg* c, Geo& g, const char* fn) {
     }
     g.fused_up = c->fused_up == PH_KNOB_OFF ? 0
                : (c->fused_up == PH_KNOB_AUTO ? (up2_sup && (int64_t)(fi ? 1 : g.B) * g.H >= 512) : up2_sup);
-    g.up2_wgs = c->up2_wgs;   // 0: 1.5 per CU of the plan's device, filled in by ph_decode_create
+    g.up2_wgs = c->up2_wgs;   // 0: 1.5 per CU (ph_num_cus: the count the process asked for first), filled in by ph_decode_create
 
     // Between the stages: a non-final stage's mask conv also pools the x map for the NEXT stage from the same read of the plane
     // (ph_dynconv_poolx), the next stage then pools depth_feats alone: 33.5 MB instead of 50 MB per frame and stage boundary at
@@ -481,11 +481,11 @@ extern "C" int ph_decode_create(const ph_decode_cfg* cfg, const void* const* pac
     PH_RUN(ph_check_buffers("ph_decode_create", nullptr, workspace, workspace_bytes, g.total));
     ph_decode* p = new (std::nothrow) ph_decode;
     if (!p) { ph_set_error("ph_decode_create: out of host memory"); return PH_EINVAL; }
-    if (!g.up2_wgs) {      // engine.DecodePlan: 3 * multi_processor_count / 2 of the plan's device
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+    if (!g.up2_wgs) {      // engine.DecodePlan's 3 * multi_processor_count / 2, with the CU count the process asked for first (ph_num_cus)
+        const int cus = ph_num_cus();
+        if (cus <= 0) {
             delete p;
-            ph_set_error("ph_decode_create: no current HIP device (%s)", hipGetErrorString(hipGetLastError()));
+            ph_set_error("ph_decode_create: the CU count of the HIP device could not be read");
             return PH_EINVAL;
         }
         g.up2_wgs = 3 * cus / 2;

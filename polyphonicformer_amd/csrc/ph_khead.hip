@@ -660,25 +660,11 @@ struct KhFused {                  // the static 1x1 convs of the fused entry poi
     const unsigned* run_if;       // optional device predicate of every launch
 };
 
-// the public entry points' launch knobs: A/B switches read from the environment once per process (the native KernelHead plan,
-// ph_kheadplan.hip, passes the defaults through ph_khead_fused_if_k and reads none)
-static const PhKheadKnobs& kh_env_knobs() {
-    static const PhKheadKnobs kn = [] {
-        PhKheadKnobs k;
-        const char* e = getenv("PH_NECK_STATS3");      // 0: the 3-D grid (A/B)
-        k.stats3 = !(e && e[0] == '0');
-        e = getenv("PH_NECK_APPLY3");                  // 0: one launch per map (A/B)
-        k.apply3 = !(e && e[0] == '0');
-        return k;
-    }();
-    return kn;
-}
-
 // f32o (nullable): plain mode -- three independent maps (no x = sem + loc), fp32 NCHW output f32o[m] of every map that has one
 static int kh_run(const void* const fm[3], int in_planes, const uint16_t* wplanes, const float* gn_affine, int groups, float eps,
                   uint16_t* const outp[3], const uint16_t* add1, uint16_t* sum1, float* x_f32, float* dfe_f32,
                   const KhFused* fu, void* workspace, size_t workspace_bytes, int B, int64_t HW, int prec, void* stream,
-                  const char* fn, const PhKheadKnobs& kn, float* const* f32o = nullptr) {
+                  const char* fn, float* const* f32o = nullptr) {
     if (!(B > 0 && HW > 0 && groups > 0 && 256 % groups == 0)) { ph_set_error("%s: bad size", fn); return PH_EINVAL; }
     if (!(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16)) {
         ph_set_error("%s: prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16", fn);
@@ -751,17 +737,16 @@ static int kh_run(const void* const fm[3], int in_planes, const uint16_t* wplane
         else hipLaunchKernelGGL((K<2, ##__VA_ARGS__, 3>), G, block, L, s, a);                             \
     } while (0)
     // pass 1: the three maps in one launch, then one finalize over the 3 * B (map, frame) pairs
-    const bool same_input = fm[0] == fm[1] && fm[1] == fm[2] && kn.stats3;
+    const bool same_input = fm[0] == fm[1] && fm[1] == fm[2];
     if (same_input) {
         a.plain3 = 1; a.nwg = nwg;
         const dim3 g3((unsigned)(((nwg * B + 7) / 8) * 8 * 3));
         if (fmt == 3) KH_LAUNCH3(k_khead_stats, g3, lds);
         else KH_LAUNCH(k_khead_stats, g3, lds);
         a.plain3 = 0;
-    } else if (fmt == 3) KH_LAUNCH3(k_khead_stats, dim3(nwg, B, 3), lds);
-    else KH_LAUNCH(k_khead_stats, dim3(nwg, B, 3), lds);
+    } else KH_LAUNCH(k_khead_stats, dim3(nwg, B, 3), lds);     // (channels-last input comes from ph_neck_out_convs alone: one pointer)
     hipLaunchKernelGGL(k_gn_finalize, dim3(3 * B), dim3(1024), 0, s, partial, stats, nwg, groups, HW, eps, a.run_if);
-    if (f32o && kn.apply3) {
+    if (f32o) {
         // plain mode: the three maps in ONE apply launch (see KHArgs::plain3)
         a.plain3 = 1; a.nwg = nwg; a.gn3 = gn_affine; a.stats3 = stats;
         for (int m = 0; m < 3; ++m) {
@@ -790,7 +775,6 @@ static int kh_run(const void* const fm[3], int in_planes, const uint16_t* wplane
         a.f32_sum = m == 1 ? x_f32 : nullptr;
         a.w2 = nullptr; a.out2b = nullptr; a.blocks_out = nullptr; a.blocks_in = nullptr;
         int add = m == 1 ? 1 : 0;
-        if (f32o) { a.add_planes = nullptr; a.sum_planes = nullptr; a.f32_sum = nullptr; a.f32 = f32o[m]; add = 0; }
         if (fu) {
             a.w2 = fu->w2[m];
             a.m2_tiles = (fu->n2[m] + 31) / 32;
@@ -816,8 +800,7 @@ static int kh_run(const void* const fm[3], int in_planes, const uint16_t* wplane
         }
         a.w2_lds = (PA == 1 && a.w2 && lds_apply + (size_t)a.m2_tiles * 16 * 1024 <= 160 * 1024) ? 1 : 0;
         const size_t lds_m = lds_apply + (a.w2_lds ? (size_t)a.m2_tiles * 16 * 1024 : 0);
-        if (fmt == 3) KH_LAUNCH3(k_khead_apply, grid, lds_m, 0);
-        else if (add == 2) KH_LAUNCH(k_khead_apply, grid, lds_m, 2);
+        if (add == 2) KH_LAUNCH(k_khead_apply, grid, lds_m, 2);
         else if (add == 1) KH_LAUNCH(k_khead_apply, grid, lds_m, 1);
         else KH_LAUNCH(k_khead_apply, grid, lds_m, 0);
     }
@@ -837,46 +820,37 @@ extern "C" int ph_khead_conv_gn(const float* f0, const float* f1, const float* f
     const void* fm[3] = {f0, f1, f2};
     uint16_t* outp[3] = {loc_planes, sem_planes, dfe_planes};
     return kh_run(fm, 0, wplanes, gn_affine, groups, eps, outp, loc_planes, x_planes, x_f32, dfe_f32, nullptr, workspace,
-                  workspace_bytes, B, HW, prec, stream, __func__, kh_env_knobs());
+                  workspace_bytes, B, HW, prec, stream, __func__);
 }
 
 // The three output convs of the neck (SemanticFPNWrapper conv_pred + 2 aux convs, semantic_fpn.py:156-178,223-231: each a
 // 1x1 conv + GroupNorm + ReLU of the SAME level sum) with the two passes above: statistics from a recompute pass, then
 // normalise + ReLU + store.  Against k_conv_nhwc + k_gn_finalize + k_gn_apply per map (fp32 NHWC conv output written, read
 // back, converted) each map moves 16.8 MB of input per pass and its output instead of 16.8 + 33.5 + 33.5 + output MB per frame.
-int ph_neck_out_convs_k(const PhKheadKnobs& kn, const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes,
-                        const float* gn_affine, int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1,
-                        uint16_t* out_planes2, float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace,
-                        size_t workspace_bytes, int B, int64_t HW, int prec, void* stream) {
-    PH_CHECK_ARG_AS("ph_neck_out_convs", in_planes && wplanes && gn_affine && workspace, "null pointer");
-    PH_CHECK_ARG_AS("ph_neck_out_convs", (out_planes0 || out_f32_0) && (out_planes1 || out_f32_1) && (out_planes2 || out_f32_2),
-                    "every map needs an output");
-    const void* fm[3] = {in_planes, in_planes, in_planes};
-    uint16_t* outp[3] = {out_planes0, out_planes1, out_planes2};
-    float* f32o[3] = {out_f32_0, out_f32_1, out_f32_2};
-    return kh_run(fm, in_channels_last ? 2 : 1, wplanes, gn_affine, groups, eps, outp, nullptr, nullptr, nullptr, nullptr, nullptr,
-                  workspace, workspace_bytes, B, HW, prec, stream, "ph_neck_out_convs", kn, f32o);
-}
-
 extern "C" int ph_neck_out_convs(const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes, const float* gn_affine,
                                  int groups, float eps, uint16_t* out_planes0, uint16_t* out_planes1, uint16_t* out_planes2,
                                  float* out_f32_0, float* out_f32_1, float* out_f32_2, void* workspace, size_t workspace_bytes,
                                  int B, int64_t HW, int prec, void* stream) {
-    return ph_neck_out_convs_k(kh_env_knobs(), in_planes, in_channels_last, wplanes, gn_affine, groups, eps, out_planes0, out_planes1,
-                               out_planes2, out_f32_0, out_f32_1, out_f32_2, workspace, workspace_bytes, B, HW, prec, stream);
+    PH_CHECK_ARG(in_planes && wplanes && gn_affine && workspace, "null pointer");
+    PH_CHECK_ARG((out_planes0 || out_f32_0) && (out_planes1 || out_f32_1) && (out_planes2 || out_f32_2), "every map needs an output");
+    const void* fm[3] = {in_planes, in_planes, in_planes};
+    uint16_t* outp[3] = {out_planes0, out_planes1, out_planes2};
+    float* f32o[3] = {out_f32_0, out_f32_1, out_f32_2};
+    return kh_run(fm, in_channels_last ? 2 : 1, wplanes, gn_affine, groups, eps, outp, nullptr, nullptr, nullptr, nullptr, nullptr,
+                  workspace, workspace_bytes, B, HW, prec, stream, __func__, f32o);
 }
 
 // ph_khead_fused with (a) a device predicate -- every launch returns at once when *run_if == 0 (null: always run) -- and (b)
 // the logit dtype (PH_OUT_F32 / PH_OUT_F16).  ph_khead_onepass's callers issue it behind every one-pass launch with run_if =
 // that launch's status word: when the persistent launch gave up (its workgroups could not all become resident in time) the
 // two-pass kernels produce the call's results instead, without a host round trip and inside a HIP graph.
-int ph_khead_fused_if_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,
-                        const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
-                        const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
-                        const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
-                        float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
-                        int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
-                        int64_t HW, int prec, int input_format, void* stream) {
+extern "C" int ph_khead_fused_if(const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,
+                                 const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
+                                 const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
+                                 const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
+                                 float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
+                                 int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
+                                 int64_t HW, int prec, int input_format, void* stream) {
 #define KH_ARG(cond, msg)                                          \
     do {                                                           \
         if (!(cond)) {                                             \
@@ -906,19 +880,7 @@ int ph_khead_fused_if_k(const PhKheadKnobs& kn, const void* f0, const void* f1, 
     fu.out2_f16 = logits_dtype == PH_OUT_F16 ? 1 : 0;
     fu.run_if = (const unsigned*)run_if;
     return kh_run(fm, input_format == PH_IN_PLANES ? 1 : 0, wplanes, gn_affine, groups, eps, outp, nullptr, x_planes, x_f32, dfe_f32, &fu, workspace,
-                  workspace_bytes, B, HW, prec, stream, "ph_khead_fused_if", kn);
-}
-
-extern "C" int ph_khead_fused_if(const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,
-                                 const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
-                                 const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
-                                 const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
-                                 float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
-                                 int logits_dtype, const uint32_t* run_if, void* workspace, size_t workspace_bytes, int B,
-                                 int64_t HW, int prec, int input_format, void* stream) {
-    return ph_khead_fused_if_k(kh_env_knobs(), f0, f1, f2, wplanes, gn_affine, groups, eps, w2_init, n_init, w2_seg, bias_seg, n_seg,
-                               w2_dd, bias_dd, stuff_lo, n_stuff, x_planes, dfe_planes, x_f32, dfe_f32, mask_preds, seg_preds,
-                               depth_pred, logits_dtype, run_if, workspace, workspace_bytes, B, HW, prec, input_format, stream);
+                  workspace_bytes, B, HW, prec, stream, __func__);
 }
 
 extern "C" int ph_khead_fused(const void* f0, const void* f1, const void* f2, const uint16_t* wplanes,

@@ -29,33 +29,20 @@
 // zeroed by a memset node in front of every launch.
 #include "ph_common.h"
 
-// Two geometries of the same kernel.  A wave always owns FOUR 32 x 32 accumulator tiles of the conv output (64 registers):
-//   K1Geo<1, 4> ("wide"):  8 waves, wave w = channels 32w..32w+31 of a 128-pixel slice; 159 KB of LDS -> ONE workgroup per CU;
-//   K1Geo<2, 2> ("pair"):  4 waves, wave w = channels 64w..64w+63 of a  64-pixel slice;  78 KB of LDS -> TWO workgroups per CU
-//                          (same registers per wave, same waves per CU).  Built on the SQ counters of the wide form (60 % of
-//                          the wave cycles waiting, MFMA busy 15 %, profiles/r03) in the hope that one workgroup computes
-//                          while the other waits; measured slower (see the launcher), compiled only with -DK1_WITH_PAIR.
-template <int RT_, int CT_> struct K1Geo {
-    static constexpr int RT = RT_, CT = CT_;                  // row tiles (32 channels) x column tiles (32 px) per wave
-    static constexpr int WAVES = 8 / RT, THREADS = 64 * WAVES, PX = 32 * CT;
-    // LDS row stride of the slice.  CT = 4: 160 elements = 80 dwords: rows r .. r+3 of a transposing read start at banks
-    // 0 / 16 / 32 / 48 -> conflict free.  CT = 2: 72 elements = 36 dwords (a conflict-free 96 would not leave room for two
-    // workgroups per CU): the second 16-pixel half of a 32-lane pass collides 2-way with one row of the first.
-    static constexpr int LD = CT == 4 ? 160 : 72;
-    static constexpr int WGS_PER_CU = CT == 4 ? 1 : 2;
-    static constexpr int SSB = CT == 4 ? 4096 : 2048;         // bytes of the ss / bitsl union: [256] float2, [256 rows][CT] words
-    static constexpr size_t LDS_BYTES = (size_t)256 * LD * 2 + (size_t)WAVES * 8192 + SSB + 3 * 512 * 4 + 288 * 4 + 64 * 4 + 64 * 4 + 16;
-};
-typedef K1Geo<1, 4> K1Wide;
-typedef K1Geo<2, 2> K1Pair;
+// Geometry: 8 waves, wave w = channels 32w..32w+31 of a 128-pixel slice, i.e. FOUR 32 x 32 accumulator tiles of the conv output
+// (64 registers) per wave; 159 KB of LDS -> ONE workgroup per CU.  (A pair geometry -- 4 waves, wave w = channels 64w..64w+63 of a
+// 64-pixel slice, 78 KB of LDS -> TWO workgroups per CU, built on the SQ counters of this form (60 % of the wave cycles waiting,
+// MFMA busy 15 %, profiles/r03) in the hope that one workgroup computes while the other waits -- measured slower, see the launcher.)
+constexpr int K1_RT = 1, K1_CT = 4;                            // row tiles (32 channels) x column tiles (32 px) per wave
+constexpr int K1_WAVES = 8, K1_THREADS = 64 * K1_WAVES, K1_PX = 32 * K1_CT;
+// LDS row stride of the slice: 160 elements = 80 dwords: rows r .. r+3 of a transposing read start at banks 0 / 16 / 32 / 48 ->
+// conflict free
+constexpr int K1_LD = 160;
+constexpr int K1_SSB = 4096;                                   // bytes of the ss / bitsl union: [256] float2, [256 rows][K1_CT] words
+constexpr size_t K1_LDS_BYTES = (size_t)256 * K1_LD * 2 + (size_t)K1_WAVES * 8192 + K1_SSB + 3 * 512 * 4 + 288 * 4 + 64 * 4 + 64 * 4 + 16;
 constexpr unsigned long long K1_TICKS_PER_US = 100;            // s_memrealtime counts at 100 MHz
 
 #define K1_RLX __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-#ifdef K1_SKIP_OUT        // timing experiments only
-#define K1_OUT_ON 0
-#else
-#define K1_OUT_ON 1
-#endif
 typedef __attribute__((address_space(1))) unsigned gu32;
 typedef __attribute__((address_space(1))) unsigned long long gu64;
 
@@ -94,10 +81,10 @@ __device__ __forceinline__ void k1_wave_sync() {
 }
 
 // ---- staging registers of one [256 ch][128 px] input slice ----------------------------------------------------------
-template <int INFMT, int E, typename G> struct K1Stage;
-// fp32 NCHW, HW % 4 == 0: PX / 4 threads x 16 B per channel row, 16 rows per pass, 16 passes
-template <int E, typename G> struct K1Stage<1, E, G> {
-    static constexpr int TPR = G::PX / 4;                     // threads per channel row; THREADS / TPR = 16 rows per pass
+template <int INFMT, int E> struct K1Stage;
+// fp32 NCHW, HW % 4 == 0: K1_PX / 4 threads x 16 B per channel row, 16 rows per pass, 16 passes
+template <int E> struct K1Stage<1, E> {
+    static constexpr int TPR = K1_PX / 4;                     // threads per channel row; K1_THREADS / TPR = 16 rows per pass
     uint4 v[16];
     // part < 0: the whole slice; otherwise request `part` alone (the requests of the next slice are paced through the first
     // GEMM: a wave blocks in the issue of a vector-memory instruction while the CU's memory pipe is full, and 8 waves issuing
@@ -126,12 +113,12 @@ template <int E, typename G> struct K1Stage<1, E, G> {
     }
     __device__ __forceinline__ void store(uint16_t* T, int tid) const {
 #pragma unroll
-        for (int q = 0; q < 16; ++q) *(uint2*)(T + (q * 16 + tid / TPR) * G::LD + (tid % TPR) * 4) = pk[q];
+        for (int q = 0; q < 16; ++q) *(uint2*)(T + (q * 16 + tid / TPR) * K1_LD + (tid % TPR) * 4) = pk[q];
     }
 };
-// 16-bit planes (zero padded to HWp by their producer): PX / 8 threads x 16 B per channel row, 32 rows per pass, 8 passes
-template <int E, typename G> struct K1Stage<2, E, G> {
-    static constexpr int TPR = G::PX / 8;
+// 16-bit planes (zero padded to HWp by their producer): K1_PX / 8 threads x 16 B per channel row, 32 rows per pass, 8 passes
+template <int E> struct K1Stage<2, E> {
+    static constexpr int TPR = K1_PX / 8;
     uint4 v[8];
     static constexpr int NREQ = 8;
     template <int part = -1> __device__ __forceinline__ void load(const K1Args& a, int m, int b, int64_t px0, int tid) {
@@ -144,7 +131,7 @@ template <int E, typename G> struct K1Stage<2, E, G> {
     __device__ __forceinline__ void pack(int, int64_t, int64_t) {}
     __device__ __forceinline__ void store(uint16_t* T, int tid) const {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) *(uint4*)(T + (q * 32 + tid / TPR) * G::LD + (tid % TPR) * 8) = v[q];
+        for (int q = 0; q < 8; ++q) *(uint4*)(T + (q * 32 + tid / TPR) * K1_LD + (tid % TPR) * 8) = v[q];
     }
 };
 
@@ -162,7 +149,7 @@ __device__ __forceinline__ void k1_load_a(uint4 (&af)[16], const uint16_t* __res
 // acc0 / acc1 [32 rows of A][32 px of column tiles ct, ct + 1] over K = 256 channel rows of the LDS tile.  Two independent
 // accumulator chains: consecutive MFMAs on ONE accumulator wait for each other's result (64 cycles), two chains issue at
 // the matrix pipe's rate.  `every2(j)` runs after k-steps 2j, 2j + 1 (the paced requests of the next slice).
-template <int E, int K1_LD, typename F>
+template <int E, typename F>
 __device__ __forceinline__ void k1_gemm2(const uint4 (&af)[16], const uint16_t* T, int ct, int lane, f32x16_t& acc0,
                                          f32x16_t& acc1, F&& every2) {
     const int g = lane >> 5, i16 = lane & 15, gi = (lane >> 4) & 1;
@@ -185,7 +172,7 @@ __device__ __forceinline__ void k1_gemm2(const uint4 (&af)[16], const uint16_t* 
     }
 }
 // the second GEMM's forms: D[px][kernel row] (operands swapped), accumulators start at the lane's bias
-template <int E, int K1_LD>
+template <int E>
 __device__ __forceinline__ f32x16_t k1_gemm_t(const uint4 (&w)[16], const uint16_t* T, int ct, int lane, float bz) {
     const int g = lane >> 5, i16 = lane & 15, gi = (lane >> 4) & 1;
     f32x16_t acc;
@@ -201,7 +188,7 @@ __device__ __forceinline__ f32x16_t k1_gemm_t(const uint4 (&w)[16], const uint16
     }
     return acc;
 }
-template <int E, int K1_LD>
+template <int E>
 __device__ __forceinline__ void k1_gemm2_t(const uint4 (&w)[16], const uint16_t* T, int ct, int lane, float bz, f32x16_t& acc0,
                                            f32x16_t& acc1) {
     const int g = lane >> 5, i16 = lane & 15, gi = (lane >> 4) & 1;
@@ -248,14 +235,16 @@ template <> __device__ __forceinline__ void k1_store_logit<uint16_t>(uint16_t* p
 // Rule of the loop body: between the request of the next slice and the top of the next phase a wave must not WAIT for any
 // vector-memory load (global or scratch) -- constants live in LDS, the second GEMM's weights are requested before the
 // slice, the next phase's conv weights after it.
-template <bool W0, int INFMT, int E, typename OutT, bool F32O, typename G>
+template <bool W0, int INFMT, int E, typename OutT, bool F32O>
 __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, int lane, int wave) {
-    constexpr int RT = G::RT, CT = G::CT, LD = G::LD;
+    // (the loops over a wave's RT row tiles stay loops although RT is 1: written out, hipcc allocates this kernel's registers
+    // differently -- the kernel lives at the edge of its register budget, see the abort path below)
+    constexpr int RT = K1_RT, CT = K1_CT, LD = K1_LD;
     uint16_t* T = lds;                                              // [256][LD]: input slice, later the normalised slice
     uint16_t* keepw = lds + 256 * LD + wave * 4096;                 // 8 KB per wave: loc in accumulator layout, later x rows
-    float2* ss = (float2*)(lds + 256 * LD + G::WAVES * 4096);       // [256] per-channel scale / shift of the normalisation ...
+    float2* ss = (float2*)(lds + 256 * LD + K1_WAVES * 4096);       // [256] per-channel scale / shift of the normalisation ...
     uint32_t* bitsl = (uint32_t*)ss;                                // ... and, later in the phase, [256 rows][CT words] mask bits
-    float* gnl = (float*)((char*)ss + G::SSB);                      // [3][2][256] gamma, beta of the three GroupNorms
+    float* gnl = (float*)((char*)ss + K1_SSB);                      // [3][2][256] gamma, beta of the three GroupNorms
     float* b2l = gnl + 3 * 512;                                     // [256 + 32] bias of conv_seg, conv_direct_depth
     float* red = b2l + 288;                                         // [64] this slice's sums
     float* statl = red + 64;                                        // [64] (mean, rstd) x 32 groups
@@ -264,7 +253,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
     const int ch0 = wave * RT * 32;                                 // this wave's first channel
     uint16_t* rows = T + ch0 * LD;                                  // this wave's channel rows
     const int slot = blockIdx.x / a.P, pair = blockIdx.x - slot * a.P;
-    const int64_t px0 = (int64_t)pair * G::PX;
+    const int64_t px0 = (int64_t)pair * K1_PX;
     const int64_t wpr = a.HWp / 32;                                 // mask words per row
     const int nfr = slot < a.B ? (a.B - slot + a.F - 1) / a.F : 0;  // frames of this workgroup: slot, slot + F, ...
     int nph = 3 * nfr;
@@ -274,7 +263,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
     gu32* gstatus = (gu32*)a.status;
     (void)g;
 
-    K1Stage<INFMT, E, G> stg;
+    K1Stage<INFMT, E> stg;
     uint4 af[16];
     stg.load(a, 0, slot, px0, tid);
     k1_load_a(af, a.wfrag[0], wave * RT, lane);
@@ -288,11 +277,10 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
         const int nm = ph1 % 3, nb = slot + (ph1 / 3) * a.F;
         K1_STAMP(0);
         // second GEMM: wpr2 waves share a row tile of the static kernels (each takes CT / wpr2 column tiles of the slice);
-        // WAVES / wpr2 row tiles per pass, as many passes as the map's kernels need (one in the wide geometry)
+        // K1_WAVES / wpr2 row tiles in ONE pass (at most 8 row tiles: 256 rows per static conv)
         const int m2 = a.m2_tiles[m];
         int wpr2 = CT;
-        while (wpr2 > 1 && G::WAVES / wpr2 < m2) wpr2 >>= 1;
-        const int rpass = G::WAVES / wpr2;
+        while (wpr2 > 1 && K1_WAVES / wpr2 < m2) wpr2 >>= 1;
         const int rt2 = wave / wpr2, nct2 = CT / wpr2, ct20 = (wave % wpr2) * nct2;
         const bool act2 = rt2 < m2;
         stg.store(T, k1_fresh(tid));
@@ -300,35 +288,23 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
         K1_STAMP(1);
         __builtin_amdgcn_sched_barrier(0);
         // first GEMM, tile q = t * CT + ct (row tile t of this wave, column tile ct).  The next slice's 16 (8) requests are
-        // issued between the MFMAs of the LAST row tile (behind the reload of the conv weights of that tile: vector memory
-        // returns in order), evenly paced -- except in wave 0, whose polls must not return behind them: it requests its share
-        // after the polls
+        // issued between the MFMAs, evenly paced -- except in wave 0, whose polls must not return behind them: it requests
+        // its share after the polls
         f32x16_t y[4];
         {
             const int l = k1_fresh(lane), t = k1_fresh(tid);
-            constexpr int NR = K1Stage<INFMT, E, G>::NREQ;
-            constexpr int QPS = 4 / CT;                     // request slots (of 16) per `every2` call of the last row tile
+            constexpr int NR = K1Stage<INFMT, E>::NREQ;
 #define K1_REQ(Q)                                                                       \
     if constexpr ((Q) < 16 && (Q) % (16 / NR) == 0) { if (!W0) stg.template load<(Q) / (16 / NR)>(a, nm, nb, px0, t); }
-#define K1_REQJ(BASE, J) { K1_REQ((BASE) + (J) * QPS); if constexpr (QPS == 2) { K1_REQ((BASE) + (J) * QPS + 1); } }
-#define K1_REQS(BASE)                                                                   \
+#define K1_REQS(BASE)       /* one request slot (of 16) per `every2` call */            \
     [&](int j) {                                                                        \
-        if (j == 0) K1_REQJ(BASE, 0) else if (j == 1) K1_REQJ(BASE, 1) else if (j == 2) K1_REQJ(BASE, 2)      \
-        else if (j == 3) K1_REQJ(BASE, 3) else if (j == 4) K1_REQJ(BASE, 4) else if (j == 5) K1_REQJ(BASE, 5) \
-        else if (j == 6) K1_REQJ(BASE, 6) else K1_REQJ(BASE, 7)                                               \
+        if (j == 0) { K1_REQ((BASE) + 0); } else if (j == 1) { K1_REQ((BASE) + 1); } else if (j == 2) { K1_REQ((BASE) + 2); }      \
+        else if (j == 3) { K1_REQ((BASE) + 3); } else if (j == 4) { K1_REQ((BASE) + 4); } else if (j == 5) { K1_REQ((BASE) + 5); } \
+        else if (j == 6) { K1_REQ((BASE) + 6); } else { K1_REQ((BASE) + 7); }                                                      \
     }
-            if constexpr (RT == 1) {
-                k1_gemm2<E, LD>(af, T, 0, l, y[0], y[1], K1_REQS(0));
-                k1_gemm2<E, LD>(af, T, 2, l, y[2], y[3], K1_REQS(8));
-            } else {
-                k1_gemm2<E, LD>(af, T, 0, l, y[0], y[1], [](int) {});
-                __builtin_amdgcn_sched_barrier(0);
-                k1_load_a(af, a.wfrag[m], wave * RT + 1, l);
-                __builtin_amdgcn_sched_barrier(0);
-                k1_gemm2<E, LD>(af, T, 0, l, y[2], y[3], K1_REQS(0));
-            }
+            k1_gemm2<E>(af, T, 0, l, y[0], y[1], K1_REQS(0));
+            k1_gemm2<E>(af, T, 2, l, y[2], y[3], K1_REQS(8));
 #undef K1_REQS
-#undef K1_REQJ
 #undef K1_REQ
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -390,9 +366,6 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
                             x[i] = j < a.P ? __hip_atomic_load(col + j, K1_RLX) : tag;
                             ok = ok && (unsigned)(x[i] >> 32) == (unsigned)(item + 1);
                         }
-#ifdef K1_NO_POLL
-                        break;
-#endif
                         if (__all(ok)) break;
                         if (expired(spins)) { dead = true; break; }
                         __builtin_amdgcn_s_sleep(2);
@@ -445,7 +418,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
         K1_STAMP(7);
         __builtin_amdgcn_sched_barrier(0);
         // ---- normalise in registers ------------------------------------------------------------------------------------
-        for (int t = k1_fresh(tid); t < 256; t += G::THREADS) {
+        for (int t = k1_fresh(tid); t < 256; t += K1_THREADS) {
             const float mean = statl[(t >> 3) * 2], rstd = statl[(t >> 3) * 2 + 1];
             const float ga = gnl[m * 512 + t], be = gnl[m * 512 + 256 + t];
             ss[t] = make_float2(rstd * ga, be - mean * rstd * ga);
@@ -535,7 +508,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
             // stores.  dfe: straight from this wave's rows of T.  x: its accumulator-layout copy in `keep` is first rewritten
             // in place as [32 rows][32 px] rows per tile (the wave's rows of T hold sem for the second GEMM)
             k1_wave_sync();
-            constexpr int TPRO = G::PX / 8, RPI = 64 / TPRO;              // lanes per row segment, rows per wave store
+            constexpr int TPRO = K1_PX / 8, RPI = 64 / TPRO;              // lanes per row segment, rows per wave store
             char* dstp = (char*)((m == 1 ? a.x_planes : a.dfe_planes) + ((int64_t)b * 256 + ch0) * a.HWp + px0);   // uniform
             const int lp = k1_fresh(lane), piece = lp % TPRO, rowl = lp / TPRO;
             const uint32_t voff = (uint32_t)(((int64_t)rowl * a.HWp + piece * 8) * 2);
@@ -564,7 +537,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
                 const int tt = (it * RPI) / 32, rin = (it * RPI) % 32 + rowl;
                 const uint16_t* src = m == 1 ? keepw + (tt * CT + (piece >> 2)) * 1024 + rin * 32 + (piece & 3) * 8
                                              : rows + (it * RPI + rowl) * LD + piece * 8;
-                if (K1_OUT_ON) st_nt16(dstp + (int64_t)it * RPI * a.HWp * 2 + voff, *(const uint4*)src);
+                st_nt16(dstp + (int64_t)it * RPI * a.HWp * 2 + voff, *(const uint4*)src);
             }
         }
         K1_STAMP(10);
@@ -591,35 +564,32 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
                 const bool rok = row < a.n2[m];
                 const bool dual = out2b && row >= a.stuff_lo && row < a.stuff_lo + a.n_stuff;
                 OutT* tb2 = out2b ? out2b + ((int64_t)b * a.out2_rows[0] + a.n_init - a.stuff_lo + rt * 32) * a.HW + pxb : nullptr;
-                if (K1_OUT_ON) {
-                    if (a.HW % 4 == 0) {
-                        const uint32_t go = (uint32_t)(((int64_t)(l2 & 31) * a.HW + 4 * g2h) * sizeof(OutT));   // lane's byte offset in the tile
+                if (a.HW % 4 == 0) {
+                    const uint32_t go = (uint32_t)(((int64_t)(l2 & 31) * a.HW + 4 * g2h) * sizeof(OutT));   // lane's byte offset in the tile
 #pragma unroll
-                        for (int jq = 0; jq < 4; ++jq) {
-                            const bool pin = pxb + 8 * jq + 4 * g2h < a.HW;        // 4 pixels are inside or outside as a whole
-                            if (sizeof(OutT) == 4) {
-                                const uint4 q4 = make_uint4(__float_as_uint(v[4 * jq]), __float_as_uint(v[4 * jq + 1]),
-                                                            __float_as_uint(v[4 * jq + 2]), __float_as_uint(v[4 * jq + 3]));
-                                if (rok && pin) *(uint4*)((char*)tb + go + jq * 8 * sizeof(OutT)) = q4;
-                                if (dual && pin) *(uint4*)((char*)tb2 + go + jq * 8 * sizeof(OutT)) = q4;
-                            } else {
-                                const uint2 q2 = make_uint2(f2h_pk(v[4 * jq], v[4 * jq + 1]), f2h_pk(v[4 * jq + 2], v[4 * jq + 3]));
-                                if (rok && pin) *(uint2*)((char*)tb + go + jq * 8 * sizeof(OutT)) = q2;
-                                if (dual && pin) *(uint2*)((char*)tb2 + go + jq * 8 * sizeof(OutT)) = q2;
-                            }
+                    for (int jq = 0; jq < 4; ++jq) {
+                        const bool pin = pxb + 8 * jq + 4 * g2h < a.HW;        // 4 pixels are inside or outside as a whole
+                        if (sizeof(OutT) == 4) {
+                            const uint4 q4 = make_uint4(__float_as_uint(v[4 * jq]), __float_as_uint(v[4 * jq + 1]),
+                                                        __float_as_uint(v[4 * jq + 2]), __float_as_uint(v[4 * jq + 3]));
+                            if (rok && pin) *(uint4*)((char*)tb + go + jq * 8 * sizeof(OutT)) = q4;
+                            if (dual && pin) *(uint4*)((char*)tb2 + go + jq * 8 * sizeof(OutT)) = q4;
+                        } else {
+                            const uint2 q2 = make_uint2(f2h_pk(v[4 * jq], v[4 * jq + 1]), f2h_pk(v[4 * jq + 2], v[4 * jq + 3]));
+                            if (rok && pin) *(uint2*)((char*)tb + go + jq * 8 * sizeof(OutT)) = q2;
+                            if (dual && pin) *(uint2*)((char*)tb2 + go + jq * 8 * sizeof(OutT)) = q2;
                         }
-                    } else {
+                    }
+                } else {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) {
-                            const int px = (r & 3) + 8 * (r >> 2) + 4 * g2h;
-                            if (pxb + px < a.HW) {
-                                if (rok) k1_store_logit<OutT>(tb + (int64_t)(l2 & 31) * a.HW + px, v[r]);
-                                if (dual) k1_store_logit<OutT>(tb2 + (int64_t)(l2 & 31) * a.HW + px, v[r]);
-                            }
+                    for (int r = 0; r < 16; ++r) {
+                        const int px = (r & 3) + 8 * (r >> 2) + 4 * g2h;
+                        if (pxb + px < a.HW) {
+                            if (rok) k1_store_logit<OutT>(tb + (int64_t)(l2 & 31) * a.HW + px, v[r]);
+                            if (dual) k1_store_logit<OutT>(tb2 + (int64_t)(l2 & 31) * a.HW + px, v[r]);
                         }
                     }
                 }
-#ifndef K1_NO_BITS
                 if (a.bits && m < 2) {
                     // hard mask of these logits (kernel_head.py:314-317): bit (r & 3) + 8 (r >> 2) of this lane's half word,
                     // the upper half-wave's bits sit 4 places higher; lanes l and l + 32 together hold the row's word
@@ -634,18 +604,17 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
                     mk |= (uint32_t)__shfl_xor((int)mk, 32);
                     if (l2 < 32) bitsl[(rt * 32 + l2) * CT + ct] = mk;
                 }
-#endif
             };
             auto row_tile = [&](int rt) {
                 // the bias of a lane's kernel row initialises its accumulators
                 const float bz = m == 0 ? 0.f : bias[rt * 32 + (k1_fresh(lane) & 31)];
                 if (nct2 == 1) {
-                    const f32x16_t acc = k1_gemm_t<E, LD>(a2, T, ct20, k1_fresh(lane), bz);
+                    const f32x16_t acc = k1_gemm_t<E>(a2, T, ct20, k1_fresh(lane), bz);
                     epilogue(acc, rt, ct20);
                 } else {
                     for (int cc = 0; cc < nct2; cc += 2) {
                         f32x16_t acc0, acc1;
-                        k1_gemm2_t<E, LD>(a2, T, ct20 + cc, k1_fresh(lane), bz, acc0, acc1);
+                        k1_gemm2_t<E>(a2, T, ct20 + cc, k1_fresh(lane), bz, acc0, acc1);
                         epilogue(acc0, rt, ct20 + cc);
                         __builtin_amdgcn_sched_barrier(0);
                         epilogue(acc1, rt, ct20 + cc + 1);
@@ -660,18 +629,7 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
 #endif
             if (act2) row_tile(rt2);
             K1_STAMP(16);
-            if constexpr (RT > 1) {
-                // further passes (more row tiles of static kernels than WAVES / wpr2): their weights are requested whole
-                for (int rt = rt2 + rpass; rt < m2; rt += rpass) {
-                    const uint16_t* ap = a.w2[m] + ((int64_t)rt * 16 * 64 + k1_fresh(lane)) * 8;
-#pragma unroll
-                    for (int ks = 0; ks < 16; ++ks) a2[ks] = *(const uint4*)(ap + ks * 512);
-                    __builtin_amdgcn_sched_barrier(0);
-                    row_tile(rt);
-                }
-            }
             K1_STAMP(17);
-            (void)rpass;
         }
         // the conv weights of the next phase: requested behind the slice, needed only when it has landed
         k1_load_a(af, a.wfrag[nm], wave * RT, k1_fresh(lane));
@@ -682,13 +640,12 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
             const int N = a.n_init + a.n_stuff, t = k1_fresh(tid);
             auto put_row = [&](int dst_row, const uint32_t* w /* null: zeros */) {
                 uint32_t* d = a.bits + ((int64_t)b * a.bits_rows + dst_row) * wpr + pair * CT;
-                if constexpr (CT == 4) *(uint4*)d = w ? *(const uint4*)w : make_uint4(0, 0, 0, 0);
-                else *(uint2*)d = w ? *(const uint2*)w : make_uint2(0, 0);
+                *(uint4*)d = w ? *(const uint4*)w : make_uint4(0, 0, 0, 0);
             };
             if (m == 0) {
-                for (int r = t; r < a.n_init; r += G::THREADS) put_row(r, bitsl + r * CT);
+                for (int r = t; r < a.n_init; r += K1_THREADS) put_row(r, bitsl + r * CT);
             } else {
-                for (int r = a.n_init + t; r < a.bits_rows; r += G::THREADS)
+                for (int r = a.n_init + t; r < a.bits_rows; r += K1_THREADS)
                     put_row(r, r < N ? bitsl + (a.stuff_lo + r - a.n_init) * CT : nullptr);
             }
             // bitsl is rewritten only after the next phase's barriers
@@ -697,23 +654,23 @@ __device__ __forceinline__ void k1_run(const K1Args& a, uint16_t* lds, int tid, 
     }
 }
 
-template <int INFMT, int E, typename OutT, bool F32O, typename G>
-__global__ __launch_bounds__(G::THREADS, 2) void k_khead_onepass(const K1Args a) {
+template <int INFMT, int E, typename OutT, bool F32O>
+__global__ __launch_bounds__(K1_THREADS, 2) void k_khead_onepass(const K1Args a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // constants of all three phases go to LDS once (see k1_run's rule)
-    float* gnl = (float*)((char*)(lds + 256 * G::LD + G::WAVES * 4096) + G::SSB);
+    float* gnl = (float*)((char*)(lds + 256 * K1_LD + K1_WAVES * 4096) + K1_SSB);
     float* b2l = gnl + 3 * 512;
-    for (int i = tid; i < 3 * 512; i += G::THREADS) gnl[i] = a.gn[i];
-    for (int i = tid; i < 288; i += G::THREADS)
+    for (int i = tid; i < 3 * 512; i += K1_THREADS) gnl[i] = a.gn[i];
+    for (int i = tid; i < 288; i += K1_THREADS)
         b2l[i] = i < 256 ? ((a.bias2[1] && i < a.m2_tiles[1] * 32) ? a.bias2[1][i] : 0.f) : (a.bias2[2] ? a.bias2[2][i - 256] : 0.f);
     // a workgroup that starts after the launch has given up (status raised by a workgroup whose wait timed out) leaves at once
     volatile int* abortl = (volatile int*)(b2l + 288 + 64 + 64);
     if (tid == 0) *abortl = __hip_atomic_load((gu32*)a.status, K1_RLX) != 0 ? 1 : 0;
     __syncthreads();
     if (*abortl) return;
-    if (wave == 0) k1_run<true, INFMT, E, OutT, F32O, G>(a, lds, tid, lane, wave);
-    else k1_run<false, INFMT, E, OutT, F32O, G>(a, lds, tid, lane, wave);
+    if (wave == 0) k1_run<true, INFMT, E, OutT, F32O>(a, lds, tid, lane, wave);
+    else k1_run<false, INFMT, E, OutT, F32O>(a, lds, tid, lane, wave);
 }
 
 __global__ __launch_bounds__(256) void k_k1_clear(uint4* __restrict__ p, size_t n16) {
@@ -726,21 +683,11 @@ static unsigned long long* g_k1_timeline = nullptr;
 // debugging aid (tools): device buffer of [grid][2][3 * rounds][16] uint64 that the next launches fill with s_memtime stamps
 extern "C" void ph_khead_onepass_set_timeline(void* buf) { g_k1_timeline = (unsigned long long*)buf; }
 
-static int k1_cus() {
-    static const int n = [] {
-        int dev = 0, cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-        return cu;
-    }();
-    return n;
-}
-
 extern "C" int ph_khead_onepass_supported(int B, int64_t HW, int groups, int prec, int input_format) {
     if (B <= 0 || B > 4096 || HW <= 0) return 0;
-    const int cu = k1_cus();
+    const int cu = ph_num_cus();
     const int64_t HWp = ph_hw_padded(HW);
-    if (cu <= 0 || HWp / K1Wide::PX > cu) return 0;
+    if (cu <= 0 || HWp / K1_PX > cu) return 0;
     if (groups != 32) return 0;
     if (!(prec == PH_PREC_BF16 || prec == PH_PREC_F16)) return 0;
     if (input_format == PH_IN_F32_NCHW && (HW % 4) != 0) return 0;
@@ -750,7 +697,7 @@ extern "C" int ph_khead_onepass_supported(int B, int64_t HW, int groups, int pre
 // hand-off state: [status (256 B)] [gran2: 3B x 128 x 8 B] [gran1: 3B x 64 x P x 8 B], cleared by every call, followed by 256
 // bytes the calls never clear (the sticky time-out words; the caller zeroes the workspace once after allocating it)
 static size_t k1_zeroed_bytes(int B, int64_t HW) {
-    const int64_t P = ph_hw_padded(HW) / K1Pair::PX;                 // the geometry with more slices
+    const int64_t P = ph_hw_padded(HW) / 64;                         // twice the 128-pixel slices: the size callers have always been given
     return 256 + (size_t)3 * B * 128 * 8 + (size_t)3 * B * 64 * P * 8;
 }
 extern "C" size_t ph_khead_onepass_workspace_bytes(int B, int64_t HW) { return k1_zeroed_bytes(B, HW) + 256; }
@@ -760,13 +707,13 @@ extern "C" size_t ph_khead_onepass_workspace_bytes(int B, int64_t HW) { return k
 static int g_k1_timeout_us = 20000;
 extern "C" void ph_khead_onepass_set_timeout_us(int us) { g_k1_timeout_us = us > 0 ? us : 20000; }
 
-int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
-                       const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
-                       const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
-                       const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
-                       float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
-                       int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
-                       int64_t HW, int prec, int input_format, void* stream) {
+extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
+                                const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
+                                const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
+                                const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
+                                float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
+                                int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
+                                int64_t HW, int prec, int input_format, void* stream) {
 #define K1_ARG(cond, msg)                                          \
     do {                                                           \
         if (!(cond)) {                                             \
@@ -824,51 +771,22 @@ int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, c
         const int blocks = (int)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
         hipLaunchKernelGGL(k_k1_clear, dim3(blocks), dim3(256), 0, s, (uint4*)workspace, n16);
     }
-    // geometry: one 128-pixel workgroup per CU.  The pair geometry (two 64-pixel workgroups per CU) is compiled only with
-    // -DK1_WITH_PAIR (PH_EXTRA_HIPCC_FLAGS) and chosen with PH_KHEAD1_PAIR=1: it passes the same tests and is SLOWER -- cfg2,
-    // 16 frames: 1.02 against 0.96 ms; cfg5, 32 frames: 0.61 against 0.53 ms on one box.  A frame's pair-slices are spread
-    // over the whole chip, so the two workgroups of a CU sit in the same phase of the same frame and wait for the same
+    // geometry: one 128-pixel workgroup per CU.  A pair geometry (two 64-pixel workgroups per CU) passed the same tests and was
+    // SLOWER -- cfg2, 16 frames: 1.02 against 0.96 ms; cfg5, 32 frames: 0.61 against 0.53 ms on one box.  A frame's pair-slices
+    // are spread over the whole chip, so the two workgroups of a CU sit in the same phase of the same frame and wait for the same
     // statistics together, and the exchange itself grows from 10-11k to 16-20k cycles per phase with twice the workgroups.
-    const int cus = k1_cus();
-    (void)kn;
-#ifdef K1_WITH_PAIR
-    const bool want_pair = kn.pair;
-#define K1_GO(I_, E_, O_, F_)                                                                                      \
-    do {                                                                                                           \
-        static const int pair_ok_ = [] {                                                                           \
-            (void)hipFuncSetAttribute((const void*)k_khead_onepass<I_, E_, O_, F_, K1Wide>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            (void)hipFuncSetAttribute((const void*)k_khead_onepass<I_, E_, O_, F_, K1Pair>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-            int nb = 0;                                                                                            \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_khead_onepass<I_, E_, O_, F_, K1Pair>, K1Pair::THREADS, \
-                                                             K1Pair::LDS_BYTES) != hipSuccess) nb = 0;              \
-            return nb >= 2 ? 1 : 0;                                                                                \
-        }();                                                                                                       \
-        if (pair_ok_ && want_pair) {                                                                               \
-            a.P = (int)(HWp / K1Pair::PX);                                                                         \
-            a.F = 2 * cus / a.P;                                                                                   \
-            if (a.F > B) a.F = B;                                                                                  \
-            hipLaunchKernelGGL((k_khead_onepass<I_, E_, O_, F_, K1Pair>), dim3(a.F * a.P), dim3(K1Pair::THREADS), K1Pair::LDS_BYTES, s, a); \
-        } else {                                                                                                   \
-            a.P = (int)(HWp / K1Wide::PX);                                                                         \
-            a.F = cus / a.P;                                                                                       \
-            if (a.F > B) a.F = B;                                                                                  \
-            hipLaunchKernelGGL((k_khead_onepass<I_, E_, O_, F_, K1Wide>), dim3(a.F * a.P), dim3(K1Wide::THREADS), K1Wide::LDS_BYTES, s, a); \
-        }                                                                                                          \
-    } while (0)
-#else
-    a.P = (int)(HWp / K1Wide::PX);
-    a.F = cus / a.P;
+    a.P = (int)(HWp / K1_PX);
+    a.F = ph_num_cus() / a.P;
     if (a.F > B) a.F = B;
 #define K1_GO(I_, E_, O_, F_)                                                                                      \
     do {                                                                                                           \
         static const bool once_ = [] {                                                                             \
-            (void)hipFuncSetAttribute((const void*)k_khead_onepass<I_, E_, O_, F_, K1Wide>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+            (void)hipFuncSetAttribute((const void*)k_khead_onepass<I_, E_, O_, F_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             return true;                                                                                           \
         }();                                                                                                       \
         (void)once_;                                                                                               \
-        hipLaunchKernelGGL((k_khead_onepass<I_, E_, O_, F_, K1Wide>), dim3(a.F * a.P), dim3(K1Wide::THREADS), K1Wide::LDS_BYTES, s, a); \
+        hipLaunchKernelGGL((k_khead_onepass<I_, E_, O_, F_>), dim3(a.F * a.P), dim3(K1_THREADS), K1_LDS_BYTES, s, a); \
     } while (0)
-#endif
 #define K1_GO_F(I, E, O)              \
     do {                              \
         if (f32o) K1_GO(I, E, O, true); \
@@ -894,25 +812,6 @@ int ph_khead_onepass_k(const PhKheadKnobs& kn, const void* f0, const void* f1, c
     return PH_OK;
 }
 #undef K1_ARG
-
-// the public entry point: the geometry switch is an environment variable (builds with -DK1_WITH_PAIR only), read once per process;
-// the native KernelHead plan (ph_kheadplan.hip) calls the _k form with the defaults and reads none
-extern "C" int ph_khead_onepass(const void* f0, const void* f1, const void* f2, const uint16_t* conv_frags,
-                                const float* gn_affine, int groups, float eps, const uint16_t* w2_init, int n_init,
-                                const uint16_t* w2_seg, const float* bias_seg, int n_seg, const uint16_t* w2_dd,
-                                const float* bias_dd, int stuff_lo, int n_stuff, uint16_t* x_planes, uint16_t* dfe_planes,
-                                float* x_f32, float* dfe_f32, void* mask_preds, void* seg_preds, void* depth_pred,
-                                int out_dtype, uint32_t* bits, int bits_rows, void* workspace, size_t workspace_bytes, int B,
-                                int64_t HW, int prec, int input_format, void* stream) {
-    PhKheadKnobs kn;
-#ifdef K1_WITH_PAIR
-    static const bool want_pair = getenv("PH_KHEAD1_PAIR") != nullptr;
-    kn.pair = want_pair;
-#endif
-    return ph_khead_onepass_k(kn, f0, f1, f2, conv_frags, gn_affine, groups, eps, w2_init, n_init, w2_seg, bias_seg, n_seg, w2_dd, bias_dd,
-                              stuff_lo, n_stuff, x_planes, dfe_planes, x_f32, dfe_f32, mask_preds, seg_preds, depth_pred, out_dtype, bits,
-                              bits_rows, workspace, workspace_bytes, B, HW, prec, input_format, stream);
-}
 
 // 1 if the last ph_khead_onepass call on this workspace gave up (a hand-off wait timed out; its caller's predicated fallback
 // then produced the results); synchronises the stream

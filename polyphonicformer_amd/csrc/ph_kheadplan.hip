@@ -226,10 +226,6 @@ extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out
 
 extern "C" void ph_khead_plan_destroy(ph_khead_plan* p) { delete p; }
 
-// the plan's launches take their knobs from here, never from the environment: the defaults the public entry points use when no
-// PH_KHEAD1_PAIR / PH_NECK_STATS3 / PH_NECK_APPLY3 is set
-static const PhKheadKnobs kKhead{};
-
 extern "C" int ph_khead_plan_run(ph_khead_plan* p, const ph_khead_io* io, void* stream) {
     PH_CHECK_ARG(p && io, "null plan or io");
     const KGeo& g = p->g;
@@ -249,24 +245,24 @@ extern "C" int ph_khead_plan_run(ph_khead_plan* p, const ph_khead_io* io, void* 
     void* ws2 = p->ws + g.o_ws2;
     float* partial = (float*)(p->ws + g.o_partial);
     if (g.onepass) {
-        PH_RUN(ph_khead_onepass_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_CONV_FRAG), f32(PH_KPACK_GN), g.groups, 1e-5f,
-                                   u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
-                                   u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
-                                   io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, io->bits, g.Npad, ws1,
-                                   g.ws1_bytes, B, HW, g.prec, fmt, s));
+        PH_RUN(ph_khead_onepass(io->f0, io->f1, io->f2, u16(PH_KPACK_CONV_FRAG), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, io->bits, g.Npad, ws1,
+                                g.ws1_bytes, B, HW, g.prec, fmt, s));
         // the in-call fallback, predicated on the one-pass launch's status word (the first word of its hand-off state)
-        PH_RUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
-                                    u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
-                                    u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
-                                    io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, (const uint32_t*)ws1,
-                                    ws2, g.ws2_bytes, B, HW, g.prec, fmt, s));
+        PH_RUN(ph_khead_fused_if(io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                 u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                 u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                 io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, g.logit_dtype, (const uint32_t*)ws1,
+                                 ws2, g.ws2_bytes, B, HW, g.prec, fmt, s));
         PH_RUN(ph_binarize_if(io->mask_preds, g.logit_dtype, 0, io->bits, B, g.N, HW, (const uint32_t*)ws1, s));
     } else {
-        PH_RUN(ph_khead_fused_if_k(kKhead, io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
-                                    u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
-                                    u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
-                                    io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, PH_OUT_F32, nullptr, ws2, g.ws2_bytes,
-                                    B, HW, g.prec, fmt, s));
+        PH_RUN(ph_khead_fused_if(io->f0, io->f1, io->f2, u16(PH_KPACK_WPLANES), f32(PH_KPACK_GN), g.groups, 1e-5f,
+                                 u16(PH_KPACK_INIT_FRAG), g.Nq, u16(PH_KPACK_SEG_FRAG), f32(PH_KPACK_SEG_BIAS), g.n_seg,
+                                 u16(PH_KPACK_DD_FRAG), f32(PH_KPACK_DD_BIAS), g.n_thing, g.n_stuff, io->xp, io->dp, io->x_f32,
+                                 io->dfe_f32, io->mask_preds, io->seg_preds, io->depth_pred, PH_OUT_F32, nullptr, ws2, g.ws2_bytes,
+                                 B, HW, g.prec, fmt, s));
         PH_RUN(ph_binarize((const float*)io->mask_preds, 0, io->bits, B, g.N, HW, s));
     }
     // object features: pool x over the THING rows of the bit tensor (kernel_head.py:314-320), add them to the kernels (:324-326)

@@ -129,8 +129,8 @@ extern "C" int ph_nhwc_ingest(const float* src, const float* add, uint16_t* dst,
 // Implicit-GEMM convolution, M = output pixels, N = 256 output channels, K = KS*KS*256 ordered (tap, channel).
 // Workgroup (8 waves) = TH output rows x 64 output pixels x all 256 channels (TH = 4 or 2, ConvGeo); wave w owns
 // channels 32 w .. 32 w + 31 of all TH * 64 pixels: 2 TH 32-pixel M tiles of 32x32x16 MFMA.  Per k-step a wave reads 2 TH A
-// fragments from LDS and ONE B fragment from L2.  (-DCV_WAVES_2X4: wave = 64 channels x half of the rows, half the A reads
-// and twice the B stream -- measured equal, 611 against 604 us at 128 x 256 x 16 frames: timing ablations put the A reads at
+// fragments from LDS and ONE B fragment from L2.  (A 2 x 4 wave arrangement -- wave = 64 channels x half of the rows, half the A
+// reads and twice the B stream -- measured equal, 611 against 604 us at 128 x 256 x 16 frames: timing ablations put the A reads at
 // 46 us and the weight stream at 24 of the 604, the patch prefetch at 40 and the output stores at 60.)
 // Round 5, from those ablations: (i) the next chunk's patch is requested ONE 16-byte piece per few k-steps instead of as
 // a burst behind the first weight fragments -- vector loads of a wave retire in order, so every weight fragment requested
@@ -171,39 +171,24 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
     using G = ConvGeo<KS, S, PA, TH_>;
     constexpr int CH = G::CH, LDP = G::LDP, IR = G::IR, IC = G::IC, PAD = KS / 2;
     constexpr int KSTEPS_TOTAL = KS * KS * 256 / 16;
-#ifndef CV_DEPTH
-#define CV_DEPTH 4
-#endif
-#ifndef CV_ABL
-#define CV_ABL 0          // timing-only ablations (wrong results): 1 no patch prefetch, 2 no weight stream, 4 no stores, 8 no A reads, 16 patch pieces from one 16 KB window, 32 no patch LDS writes, 64 every chunk's k-steps twice
-#endif
-    constexpr int DEPTH = CV_DEPTH;                                         // B fragments requested this many k-steps ahead
+    constexpr int DEPTH = 4;                                                // B fragments requested this many k-steps ahead
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];        // [PA][IR][IC][LDP]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifndef CV_WAVES_2X4
-    constexpr int NT = 1, MT = G::MT;                                       // wave = 32 channels x all rows
-    const int wc = wv, row_base = 0;
-#else
-    constexpr int NT = 2, MT = G::TH;                                       // wave = 64 channels x half of the rows
-    const int wc = wv & 3, row_base = (wv >> 2) * (G::TH / 2);
-#endif
+    constexpr int MT = G::MT;                                               // wave = 32 channels x all rows
     const int b = blockIdx.z, oy0 = blockIdx.y * G::TH, ox0 = blockIdx.x * CV_TW;
     const int iy0 = oy0 * S - PAD, ix0 = ox0 * S - PAD;
     const int m = lane & 31, kg = lane >> 5;
 
-    f32x16_t acc[MT][NT];     // [output row (of this wave) * 2 + 32-pixel half][column tile]
+    f32x16_t acc[MT];         // [output row * 2 + 32-pixel half]
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
+        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
 
     const uint16_t* xb = X + (int64_t)b * H * W * 256;
-    const uint16_t* wbase = Wp + ((int64_t)wc * NT * KSTEPS_TOTAL) * 512 + lane * 8;   // this lane's B-fragment stream(s)
-    constexpr int64_t W_NT = (int64_t)KSTEPS_TOTAL * 512;                             // next column tile
+    const uint16_t* wbase = Wp + ((int64_t)wv * KSTEPS_TOTAL) * 512 + lane * 8;        // this lane's B-fragment stream
 
     // Stride-1 single-plane instantiations double-buffer the patch: chunk c + 1 travels HBM -> registers while the
     // MFMAs of chunk c run and is written to the other LDS buffer after them (one barrier per chunk).  Vector-memory
@@ -228,7 +213,6 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
             const int slot = r * G::ICS + (S == 2 ? (x & 1) * G::HALF + (x >> 1) : x);
             // PH_PLANES_C16 input (16-channel stages only): [chunk][pixel][16] -- a stage's rows are contiguous in memory
             goff[k] = (min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1)) * (c16 ? 16 : 256) + piece * 8;
-            if (CV_ABL & 16) goff[k] &= 0x1ff8;           // timing only: every piece from one 16 KB window (cache hits)
             loff[k] = idx < IR * IC * PIECES ? ((slot * LDP + piece * 8) | (in ? 0 : 0x40000000)) : -1;
         }
     }
@@ -240,10 +224,7 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
         if (loff[k] >= 0) {
             const bool zero = (loff[k] & 0x40000000) != 0;
 #pragma unroll
-            for (int p = 0; p < PA; ++p) {
-                if ((CV_ABL & 32) && v[p].x != 0x12345678u) continue;     // timing only: loads awaited, no LDS write
-                *(uint4*)(buf + p * G::PLANE + (loff[k] & 0xffffff)) = zero ? make_uint4(0, 0, 0, 0) : v[p];
-            }
+            for (int p = 0; p < PA; ++p) *(uint4*)(buf + p * G::PLANE + (loff[k] & 0xffffff)) = zero ? make_uint4(0, 0, 0, 0) : v[p];
         }
     };
     auto patch_load_cond = [&](int c0, int k, uint4 (&v)[PA]) {      // the kernels without a prefetch: only what is inside
@@ -297,70 +278,51 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
             const int tap = j / (CH / 16), kk = j - tap * (CH / 16);
             return tap * 16 + (c0 >> 4) + kk;             // (tap * 256 + c0 + kk * 16) / 16
         };
-        uint4 bq[DEPTH][NT][PA];
+        uint4 bq[DEPTH][PA];
 #pragma unroll
         for (int d = 0; d < DEPTH; ++d)
             if (d < NK) {
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int p = 0; p < PA; ++p) bq[d][nt][p] = *(const uint4*)(wbase + nt * W_NT + p * w_plane + (int64_t)kstep_of(d) * 512);
+                for (int p = 0; p < PA; ++p) bq[d][p] = *(const uint4*)(wbase + p * w_plane + (int64_t)kstep_of(d) * 512);
             }
         uint4 pre[DB ? NPRE : 1][PA];
         const bool more = DB && c0 + CH < 256;
         const int cn = min(c0 + CH, 256 - CH);            // the last chunk re-requests itself (L2 hits) rather than branch
         constexpr int NKS = (NK - DEPTH > 1) ? NK - DEPTH : 1;   // the pieces are spread over the first NKS k-steps
-#if CV_ABL & 8
-        uint4 a[PA][MT];
-#endif
-#if CV_ABL & 64            // timing only: the chunk's k-steps run twice (is the loop or what surrounds it the overhead?)
-#pragma unroll 1
-        for (int rep = 0; rep < 2; ++rep)
-#endif
 #pragma unroll
         for (int j = 0; j < NK; ++j) {
-#if !(CV_ABL & 8)
             uint4 a[PA][MT];
-#endif
-            uint4 bcur[NT][PA];
+            uint4 bcur[PA];
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
+            for (int p = 0; p < PA; ++p) bcur[p] = bq[j % DEPTH][p];
+            if (j + DEPTH < NK) {
 #pragma unroll
-                for (int p = 0; p < PA; ++p) bcur[nt][p] = bq[j % DEPTH][nt][p];
-            if (j + DEPTH < NK && !(CV_ABL & 2)) {
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                    for (int p = 0; p < PA; ++p)
-                        bq[j % DEPTH][nt][p] = *(const uint4*)(wbase + nt * W_NT + p * w_plane + (int64_t)kstep_of(j + DEPTH) * 512);
+                for (int p = 0; p < PA; ++p) bq[j % DEPTH][p] = *(const uint4*)(wbase + p * w_plane + (int64_t)kstep_of(j + DEPTH) * 512);
             }
-            if (DB && !(CV_ABL & 1)) {
+            if (DB) {
 #pragma unroll
                 for (int k = 0; k < NPRE; ++k)
                     if (k >= (j * NPRE + NKS - 1) / NKS && (k < ((j + 1) * NPRE + NKS - 1) / NKS || j == NK - 1)) patch_load(cn, k, pre[k]);
             }
             const int tap = j / (CH / 16), kk = j - tap * (CH / 16);
             const int dy = tap / KS, dx = tap - dy * KS;
-            if (!(CV_ABL & 8) || j == 0)
 #pragma unroll
             for (int p = 0; p < PA; ++p)
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) {
-                    const int row = (row_base + (mt >> 1)) * S + dy;
+                    const int row = (mt >> 1) * S + dy;
                     const int px = (S == 2) ? (dx & 1) * G::HALF + (mt & 1) * 32 + m + (dx >> 1) : (mt & 1) * 32 + m + dx;
                     a[p][mt] = *(const uint4*)(cur + p * G::PLANE + (row * G::ICS + px) * LDP + kk * 16 + kg * 8);
                 }
 #pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc[mt][nt] = mfma32e<E>(a[0][mt], bcur[nt][0], acc[mt][nt]);
-                    if (PA == 2) {
-                        acc[mt][nt] = mfma32e<E>(a[0][mt], bcur[nt][PA - 1], acc[mt][nt]);
-                        acc[mt][nt] = mfma32e<E>(a[PA - 1][mt], bcur[nt][0], acc[mt][nt]);
-                    }
+            for (int mt = 0; mt < MT; ++mt) {
+                acc[mt] = mfma32e<E>(a[0][mt], bcur[0], acc[mt]);
+                if (PA == 2) {
+                    acc[mt] = mfma32e<E>(a[0][mt], bcur[PA - 1], acc[mt]);
+                    acc[mt] = mfma32e<E>(a[PA - 1][mt], bcur[0], acc[mt]);
                 }
-            if (MT * NT > 4) __builtin_amdgcn_sched_barrier(0);   // 128 accumulator VGPRs: keep the A fragments of later k-steps out
+            }
+            if (MT > 4) __builtin_amdgcn_sched_barrier(0);   // 128 accumulator VGPRs: keep the A fragments of later k-steps out
         }
         if (DB) {
             if (more) {
@@ -380,85 +342,47 @@ __global__ __launch_bounds__(512) void k_conv_nhwc(const uint16_t* __restrict__ 
     // GroupNorm partial sums: ONE entry per PAIR of output rows (rows 2p, 2p + 1 of the image x this tile's 64 pixels), in the 2-row
     // kernel's order -- the lane's two rows x two halves x 16 registers, then the two lane halves -- whatever TH is (round 6): a 4-row
     // tile emits two entries, so the sums `ph_gn_finalize` adds, and with them every bit of the normalised output, do not depend on
-    // the tile form the launch size picked (batch-invariant kernels; the 2 x 4 wave arrangement of -DCV_WAVES_2X4
-    // keeps the older per-tile entries).
-    float s1[NT], s2[NT];
+    // the tile form the launch size picked (batch-invariant kernels).
+    float s1 = 0.f, s2 = 0.f;
     float* tbuf = (float*)lds + wv * 2048;
     const int64_t npair_x = gridDim.x, npairs = (int64_t)gridDim.x * ((Ho + 1) / 2);
     // (the single-plane kernels: the last chunk's closing barrier has passed, the LDS is free)
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        s1[nt] = 0.f;
-        s2[nt] = 0.f;
+    for (int row = 0; row < MT / 2; ++row) {
+        const int oy = oy0 + row;
+        if ((row & 1) == 0) { s1 = 0.f; s2 = 0.f; }
 #pragma unroll
-        for (int row = 0; row < MT / 2; ++row) {
-            const int oy = oy0 + row_base + row;
-#ifndef CV_WAVES_2X4
-            if ((row & 1) == 0) { s1[nt] = 0.f; s2[nt] = 0.f; }
-#endif
+        for (int half = 0; half < 2; ++half)
 #pragma unroll
-            for (int half = 0; half < 2; ++half)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int px = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;  // C layout: row = pixel, col = channel
-                    const float v = acc[row * 2 + half][nt][r];
-                    if (DB) tbuf[(px ^ kg) * 32 + m] = v;
-                    if (oy < Ho && ox0 + px < Wo) {
-                        if (!DB) Y[(((int64_t)b * Ho + oy) * Wo + ox0 + px) * 256 + (wc * NT + nt) * 32 + m] = v;
-                        s1[nt] += v;
-                        s2[nt] += v * v;
-                    }
-                }
-            if (DB && oy < Ho) {                          // (the two-plane kernels keep the direct stores above)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int P = (lane >> 3) + 8 * i;
-                    const float4 v = *(const float4*)(tbuf + (P ^ ((P >> 2) & 1)) * 32 + (lane & 7) * 4);
-                    if ((CV_ABL & 4) && v.x != 12345.f) continue;
-                    if (ox0 + P < Wo) *(float4*)(Y + (((int64_t)b * Ho + oy) * Wo + ox0 + P) * 256 + (wc * NT + nt) * 32 + (lane & 7) * 4) = v;
+            for (int r = 0; r < 16; ++r) {
+                const int px = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;  // C layout: row = pixel, col = channel
+                const float v = acc[row * 2 + half][r];
+                if (DB) tbuf[(px ^ kg) * 32 + m] = v;
+                if (oy < Ho && ox0 + px < Wo) {
+                    if (!DB) Y[(((int64_t)b * Ho + oy) * Wo + ox0 + px) * 256 + wv * 32 + m] = v;
+                    s1 += v;
+                    s2 += v * v;
                 }
             }
-#ifndef CV_WAVES_2X4
-            if ((row & 1) == 1 || row == MT / 2 - 1) {
-                // the pair (oy - 1, oy) is complete: its entry (pairs past the image's last row have none)
-                const float t1 = s1[nt] + __shfl_xor(s1[nt], 32), t2 = s2[nt] + __shfl_xor(s2[nt], 32);
-                const int pair_y = (oy0 + row_base + (row & ~1)) >> 1;
-                if (kg == 0 && oy0 + row_base + (row & ~1) < Ho) {
-                    float* o = partial + (((int64_t)b * npairs + (int64_t)pair_y * npair_x + blockIdx.x) * 256 + (wc * NT + nt) * 32 + m) * 2;
-                    o[0] = t1;
-                    o[1] = t2;
-                }
+        if (DB && oy < Ho) {                          // (the two-plane kernels keep the direct stores above)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int P = (lane >> 3) + 8 * i;
+                const float4 v = *(const float4*)(tbuf + (P ^ ((P >> 2) & 1)) * 32 + (lane & 7) * 4);
+                if (ox0 + P < Wo) *(float4*)(Y + (((int64_t)b * Ho + oy) * Wo + ox0 + P) * 256 + wv * 32 + (lane & 7) * 4) = v;
             }
-#endif
         }
-#ifdef CV_WAVES_2X4
-        s1[nt] += __shfl_xor(s1[nt], 32);
-        s2[nt] += __shfl_xor(s2[nt], 32);
-#endif
-    }
-#ifdef CV_WAVES_2X4
-    const int64_t wg = (int64_t)blockIdx.y * gridDim.x + blockIdx.x, nwg = (int64_t)gridDim.x * gridDim.y;
-    // the two row halves of a channel meet in LDS (fixed order: upper rows + lower rows)
-    float* red = (float*)lds;                             // [256 channels][2]
-    __syncthreads();                                      // the transposition buffers are done
-    if (row_base != 0 && kg == 0) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            red[((wc * NT + nt) * 32 + m) * 2 + 0] = s1[nt];
-            red[((wc * NT + nt) * 32 + m) * 2 + 1] = s2[nt];
+        if ((row & 1) == 1 || row == MT / 2 - 1) {
+            // the pair (oy - 1, oy) is complete: its entry (pairs past the image's last row have none)
+            const float t1 = s1 + __shfl_xor(s1, 32), t2 = s2 + __shfl_xor(s2, 32);
+            const int pair_y = (oy0 + (row & ~1)) >> 1;
+            if (kg == 0 && oy0 + (row & ~1) < Ho) {
+                float* o = partial + (((int64_t)b * npairs + (int64_t)pair_y * npair_x + blockIdx.x) * 256 + wv * 32 + m) * 2;
+                o[0] = t1;
+                o[1] = t2;
+            }
         }
     }
-    __syncthreads();
-    if (row_base == 0 && kg == 0) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int c = (wc * NT + nt) * 32 + m;
-            float* o = partial + (((int64_t)b * nwg + wg) * 256 + c) * 2;
-            o[0] = s1[nt] + red[c * 2 + 0];
-            o[1] = s2[nt] + red[c * 2 + 1];
-        }
-    }
-#endif
 }
 
 // one-plane formats: 4-row tiles, unless those are fewer than one per CU over the whole launch (then 2-row tiles).  The choice may

@@ -293,9 +293,8 @@ extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) {
 extern "C" void ph_neck_plan_destroy(ph_neck_plan* p) { delete p; }
 
 // the plan's launches take their knobs from here, never from the environment: the defaults the public entry points use when no
-// PH_CONV_TH[_NOW] / PH_GNSUM_* / PH_CPLANES_TPW / PH_NECK_STATS3 / PH_NECK_APPLY3 is set
+// PH_CONV_TH[_NOW] / PH_GNSUM_* / PH_CPLANES_TPW is set
 static const PhNeckKnobs kNeck{};
-static const PhKheadKnobs kKhead{};
 
 // every pointer check of the three run calls, before any of them launches
 static int check_io(const NGeo& g, const ph_neck_io* io, const char* fn, bool feats, int level, bool outs) {
@@ -380,9 +379,9 @@ static int run_outputs(const ph_neck_plan* p, const ph_neck_io* io, hipStream_t 
         if (g.emit_f32) of[i] = io->out_f32[i];
     }
     if (g.fused_out)
-        return ph_neck_out_convs_k(kKhead, xb, 1, (const uint16_t*)(p->pack + g.lay.offset[PH_NPACK_OUTS_W]),
-                                   (const float*)(p->pack + g.lay.offset[PH_NPACK_OUTS_GN]), g.groups, g.eps, op[0], op[1], op[2], of[0],
-                                   of[1], of[2], p->ws + g.o_ws2, g.ws2_bytes, g.B, g.HWo, g.prec, s);
+        return ph_neck_out_convs(xb, 1, (const uint16_t*)(p->pack + g.lay.offset[PH_NPACK_OUTS_W]),
+                                 (const float*)(p->pack + g.lay.offset[PH_NPACK_OUTS_GN]), g.groups, g.eps, op[0], op[1], op[2], of[0],
+                                 of[1], of[2], p->ws + g.o_ws2, g.ws2_bytes, g.B, g.HWo, g.prec, s);
     float* y = (float*)(p->ws + g.o_y);
     float* stats = (float*)(p->ws + g.o_stats);
     for (int i = 0; i < g.num_outs; ++i) {

@@ -855,8 +855,6 @@ class KernelHeadPlan(_KernelHeadPlanBase):
             # (first word of ws1).  The persistent grid needs a workgroup resident on every CU; when another kernel holds CUs
             # beyond the hand-off bound the launch gives up, raises that word, and these launches -- which otherwise return at
             # once -- rewrite every output of the call.  No host round trip, valid under graph capture and replay.
-            if _os.environ.get("PH_KHEAD_NO_FALLBACK"):       # timing experiments only: what the predicated launches cost
-                return self._finish_run(lib, pk, s, B, HW, prec)
             _lib.check(lib.ph_khead_fused_if(_lib.ptr(self.f[0]), _lib.ptr(self.f[1]), _lib.ptr(self.f[2]), _lib.ptr(pk.wplanes),
                                              _lib.ptr(pk.gn), pk.groups, 1e-5, _lib.ptr(pk.init_frag), self.Nq,
                                              _lib.ptr(pk.seg_frag), _lib.ptr(pk.seg_bias), pk.n_seg, _lib.ptr(pk.dd_frag),

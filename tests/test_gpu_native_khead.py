@@ -432,8 +432,8 @@ print(json.dumps(res))
 
 
 def test_environment_does_not_reach_the_native_plan(gpu):
-    """PH_KHEAD1_PAIR (read by the public ph_khead_onepass), PH_KHEAD_TWOPASS and PH_POOL_NSPLIT (read by the Python plan) leave
-    the launches of a native plan built from an explicit cfg as they are -- the kernel nodes of a captured run (grid, block, LDS)
+    """PH_KHEAD_TWOPASS and PH_POOL_NSPLIT (read by the Python plan) and PH_KHEAD1_PAIR (a switch of the one-pass kernel that no
+    longer exists: nothing reads it) leave the launches of a native plan built from an explicit cfg as they are -- the kernel nodes of a captured run (grid, block, LDS)
     are the same with and without them -- while the Python plan's change.  Without the variables both plans capture the same
     launches."""
     knobs = dict(PH_KHEAD1_PAIR="1", PH_KHEAD_TWOPASS="1", PH_POOL_NSPLIT="3")

@@ -1,5 +1,5 @@
-"""GPU: a1 (KernelHead post-neck, one-pass form) alone at cfg2, HIP-graph replay, ms per call of `frames` frames; with
-PH_KHEAD_NO_FALLBACK=1 in the environment the predicated two-pass launches behind the one-pass kernel are left out (timing only).
+"""GPU: a1 (KernelHead post-neck, one-pass form) alone at cfg2, HIP-graph replay, ms per call of `frames` frames (the predicated
+two-pass launches behind the one-pass kernel included).
 usage: python tools/a1_time.py [frames=16] [grade=fp16] [logits=fp32|fp16] [inputs=f32|planes]"""
 import json, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,4 +39,4 @@ for _ in range(30):
 e.record()
 torch.cuda.synchronize()
 print(json.dumps({"a1_ms_per_call": round(s.elapsed_time(e) / 30, 4), "frames": B, "grade": grade, "logits": str(ldt), "inputs": "planes" if planes else "fp32 NCHW", "onepass": kplan.onepass,
-                  "fallback_launches": not os.environ.get("PH_KHEAD_NO_FALLBACK"), "timeouts": kplan.timeouts()}))
+                  "fallback_launches": True, "timeouts": kplan.timeouts()}))
