@@ -1180,6 +1180,97 @@ int ph_assoc_plan_match(ph_assoc_plan* plan, ph_tracker* tracker, const int32_t*
                         void* host_staging, size_t staging_bytes, int64_t first_frame_id, double* track_out, int64_t* ids_host_out,
                         void* stream);
 
+/* ---- N1: the tracker with its state ON THE DEVICE (csrc/ph_dtracker.hip).  The semantics are ph_tracker_match /
+ * ph_tracker_match_frames' (quasi_dense_embed_tracker.py:47-207), decision for decision and id for id; what differs is where the
+ * state lives and who walks it.  Everything -- the embedding pool, the tracklet table, the backdrop generations, the free-slot stack,
+ * num_tracklets, the frame counter and a status record -- lies in ONE caller-owned 256-byte aligned device buffer; the host object
+ * holds the cfg, the pointers and the sizes: no host mirror, no pinned buffer, no event.  ph_dtracker_run is launches only and
+ * capturable into a hipGraph; the state carries across replays.  Conventions are the ph_*_plan_* family's: status codes +
+ * ph_last_error_string, a size query that returns 0 with a message on a bad cfg, argument errors before the first launch, no
+ * environment variable read, no memset node.  ZEROING CONTRACT: none, but ph_dtracker_reset must run before the first ph_dtracker_run.
+ *
+ * Per frame of a call, in order (a frame depends on the one before): k_dtrk_prepare (one workgroup: stable descending-score order by
+ * counting, de-duplication, the memory columns), the gather of the kept rows and the pool rows, ph_track_affinity's three kernels, and
+ * k_trk_update's EMA, all in device-count forms (grids sized for max_dets / capacity, the counts read from the frame record on the
+ * device), with k_dtrk_assign (one workgroup: the greedy walk, new ids, the slot reservation, update_memo, expiry, status) in between.
+ *
+ * ERRORS are status words, not return codes: a frame is REFUSED when it needs more pool slots than are free (PH_DTRK_EPOOL), when
+ * its `refuse` word is non-zero (PH_DTRK_EREFUSED) or when its count is negative or above max_dets (PH_DTRK_ECOUNT).  The reservation
+ * is checked before the first mutation, so a refused frame leaves the state as the previous frame left it; its kept_counts entry is 0.
+ * The error is sticky: every later frame is skipped the same way (kept_counts 0) until ph_dtracker_reset.
+ *
+ * The status record: PH_DTRK_ST_WORDS int64 words at ph_dtracker_layout.status. */
+enum { PH_DTRK_OK = 0, PH_DTRK_EPOOL = 1, PH_DTRK_EREFUSED = 2, PH_DTRK_ECOUNT = 3 };
+enum {
+    PH_DTRK_ST_MATCHED = 0,        /* frames matched since the reset */
+    PH_DTRK_ST_NUM_TRACKLETS = 1,  /* ids handed out (the next new id) */
+    PH_DTRK_ST_ROWS = 2,           /* live tracklet rows */
+    PH_DTRK_ST_ERROR = 3,          /* PH_DTRK_OK or the code of the first refusal */
+    PH_DTRK_ST_REFUSED_FRAME = 4,  /* index of the first refused frame, counting every frame handed to ph_dtracker_run since the reset
+                                      (empty ones included) from 0; -1: none */
+    PH_DTRK_ST_FRAME_ID = 5,       /* the frame id the next matched frame gets: first_frame_id + frames matched */
+    PH_DTRK_ST_FREE = 6,           /* free pool slots */
+    PH_DTRK_ST_FRAMES_SEEN = 7,    /* frames handed to ph_dtracker_run since the reset */
+    PH_DTRK_ST_WORDS = 8
+};
+typedef struct ph_dtracker ph_dtracker;
+/* byte offsets into the device buffer, multiples of 256.  Tracklet rows 0 .. rows - 1 are live, in creation order; generation g of
+ * the backdrops (0 = the newest frame's) has bd_count[g] rows at [g][0 .. max_dets) of its tables. */
+typedef struct {
+    uint64_t pool;        /* float [capacity][256] */
+    uint64_t trk_id;      /* int64 [capacity] */
+    uint64_t trk_seen;    /* int64 [capacity]: the frame id a row was last matched in */
+    uint64_t trk_label;   /* int32 [capacity] */
+    uint64_t trk_slot;    /* int32 [capacity]: the row's pool slot */
+    uint64_t trk_box;     /* float [capacity][5] */
+    uint64_t bd_count;    /* int32 [generations] */
+    uint64_t bd_label;    /* int32 [generations][max_dets] */
+    uint64_t bd_slot;     /* int32 [generations][max_dets] */
+    uint64_t bd_box;      /* float [generations][max_dets][5] */
+    uint64_t free_stack;  /* int32 [capacity]: entries 0 .. free - 1, the top is taken first */
+    uint64_t status;      /* int64 [PH_DTRK_ST_WORDS] */
+    uint64_t workspace;   /* per-frame scratch (frame record, tables, gathered rows, scores); overwritten by every frame */
+    uint64_t total_bytes; /* ph_dtracker_device_bytes */
+    int32_t capacity, max_dets, generations /* memo_backdrop_frames */, reserved;
+} ph_dtracker_layout;
+/* capacity 16 .. 4096 rows, max_dets 1 .. 128, as ph_tracker_create; cfg->metric 0 .. 2, memo_tracklet_frames >= 0,
+   memo_backdrop_frames 0 .. 16.  0 with a message otherwise. */
+size_t ph_dtracker_device_bytes(const ph_tracker_cfg* cfg, int capacity, int max_dets);
+/* touches no device memory; the caller keeps device_mem (256-byte aligned, ph_dtracker_device_bytes) alive as long as the tracker */
+int ph_dtracker_create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, ph_dtracker** out);
+void ph_dtracker_destroy(ph_dtracker* t);
+/* one launch: empty tables, full free stack, frame counter = first_frame_id, status 0 (refused frame -1) */
+int ph_dtracker_reset(ph_dtracker* t, int64_t first_frame_id, void* stream);
+/* for inspection and checkpointing (a C typedef and a function cannot share a name, hence get_) */
+int ph_dtracker_get_layout(const ph_dtracker* t, ph_dtracker_layout* out);
+/* all DEVICE pointers; frame b at base + b * stride (elements) */
+typedef struct {
+    const float* boxes;    int64_t box_stride;      /* [n][5]: x1, y1, x2, y2, score */
+    const int32_t* labels; int64_t label_stride;
+    const int32_t* counts; int64_t count_stride;    /* n of the frame; 0: the frame is skipped and does not advance the frame counter */
+    const int32_t* refuse; int64_t refuse_stride;   /* nullable: a non-zero word (the things table's overflow word) refuses the frame */
+    const float* embeds;   int64_t embed_stride;    /* [n][256] */
+    int32_t* kept_out;     /* [B][max_dets] indices into the frame's input, descending score; entries < kept_counts[b] are written */
+    int64_t* ids_out;      /* [B][max_dets]: >= 0 track id, -1 unmatched, -2 suppressed */
+    int32_t* kept_counts;  /* [B] */
+} ph_dtracker_io;
+/* B frames in order, launches only, capturable.  The caller learns what happened from the status record whenever it next
+   synchronises. */
+int ph_dtracker_run(ph_dtracker* t, const ph_dtracker_io* io, int B, void* stream);
+
+/* ---- the launch-only counterpart of ph_assoc_plan_match: the device tracker and the track-id maps behind ph_assoc_plan_run on the
+ * same stream, with no host staging and no synchronisation; capturable.  It points a ph_dtracker_io at the things tables (counts at
+ * word 0, labels, boxes and the overflow word at their offsets, embeddings [B][cap][256]) one frame at a time -- the tracker's
+ * per-frame outputs live in the tracker's own buffer, so the plan's workspace is what it was --, forms each frame's track look-up
+ * table on the device exactly as ph_assoc_plan_match documents (ids + 1, negatives to 0, painted in segment order onto the ids in
+ * the order the tracker returns them; all zero for a skipped or refused frame) and launches k_assoc_paint's float64 form.
+ * Needs max_things <= the tracker's max_dets (PH_EINVAL).  A frame with more than max_things things is a refused frame
+ * (PH_DTRK_EREFUSED in the status record).  The frames matched are PH_DTRK_ST_MATCHED of the status record.
+ *   track_out      double [B][Ho][Wo] on the device
+ *   ids_dev_out    int64 [B][cap] on the DEVICE, nullable: the value painted onto thing j of frame b (0 beyond nthing) */
+int ph_assoc_plan_track(ph_assoc_plan* plan, ph_dtracker* tracker, const int32_t* pan, const int32_t* things_dev, const float* embeds_dev,
+                        double* track_out, int64_t* ids_dev_out, void* stream);
+
 /* ================================================================================================================================
  * DVPQ tallies on the device (ph_dvpq.hip): what dvps_eval.video_evaluate needs from a frame, computed from the maps where they lie.
  *

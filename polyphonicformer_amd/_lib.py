@@ -134,6 +134,31 @@ class AssocIO(C.Structure):
                 ("sem_out", C.c_void_p), ("things_out", C.c_void_p), ("embeds_out", C.c_void_p), ("roi_planes", C.c_void_p)]
 
 
+# the device tracker (polyhead.h ph_dtracker_* .. ph_assoc_plan_track); ph_tracker_cfg is the host tracker's too
+PH_DTRK_OK, PH_DTRK_EPOOL, PH_DTRK_EREFUSED, PH_DTRK_ECOUNT = 0, 1, 2, 3
+DTRK_STATUS = ("matched", "num_tracklets", "rows", "error", "refused_frame", "frame_id", "free", "frames_seen")     # PH_DTRK_ST_*
+PH_DTRK_ST_WORDS = len(DTRK_STATUS)
+
+
+class TrackerCfg(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("init_score_thr", "obj_score_thr", "match_score_thr", "memo_momentum", "one_minus_momentum",
+                                         "nms_conf_thr", "nms_backdrop_iou_thr", "nms_class_iou_thr")] + \
+        [(n, C.c_int32) for n in ("memo_tracklet_frames", "memo_backdrop_frames", "with_cats", "metric")]
+
+
+class DtrackerLayout(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("pool", "trk_id", "trk_seen", "trk_label", "trk_slot", "trk_box", "bd_count", "bd_label", "bd_slot",
+                                          "bd_box", "free_stack", "status", "workspace", "total_bytes")] + \
+        [(n, C.c_int32) for n in ("capacity", "max_dets", "generations", "reserved")]
+
+
+class DtrackerIO(C.Structure):
+    _fields_ = [("boxes", C.c_void_p), ("box_stride", C.c_int64), ("labels", C.c_void_p), ("label_stride", C.c_int64),
+                ("counts", C.c_void_p), ("count_stride", C.c_int64), ("refuse", C.c_void_p), ("refuse_stride", C.c_int64),
+                ("embeds", C.c_void_p), ("embed_stride", C.c_int64), ("kept_out", C.c_void_p), ("ids_out", C.c_void_p),
+                ("kept_counts", C.c_void_p)]
+
+
 # DVPQ tallies on the device (polyhead.h ph_dvpq_cfg .. ph_dvpq_frames)
 PH_DVPQ_MAX_THR = 8
 
@@ -318,6 +343,13 @@ SIGNATURES = {
     "ph_assoc_plan_destroy": (None, [_P]),
     "ph_assoc_plan_run": (C.c_int, [_P, C.POINTER(AssocIO), _P]),
     "ph_assoc_plan_match": (C.c_int, [_P, _P, _P, _P, _P, _P, _Z, _L, _P, _P, _P]),
+    "ph_dtracker_device_bytes": (C.c_size_t, [C.POINTER(TrackerCfg), _I, _I]),
+    "ph_dtracker_create": (C.c_int, [C.POINTER(TrackerCfg), _P, _Z, _I, _I, C.POINTER(C.c_void_p)]),
+    "ph_dtracker_destroy": (None, [_P]),
+    "ph_dtracker_reset": (C.c_int, [_P, _L, _P]),
+    "ph_dtracker_get_layout": (C.c_int, [_P, C.POINTER(DtrackerLayout)]),
+    "ph_dtracker_run": (C.c_int, [_P, C.POINTER(DtrackerIO), _I, _P]),
+    "ph_assoc_plan_track": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ph_dvpq_workspace_bytes": (C.c_size_t, [C.POINTER(DvpqCfg)]),
     "ph_dvpq_frames": (C.c_int, [C.POINTER(DvpqCfg), C.POINTER(DvpqIO), _P, _Z, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),

@@ -3,7 +3,8 @@
 // Python -- things for tracking, segment boxes, FPN RoIAlign, the track embedding head, the tracker, the sem / track maps -- as a plan
 // over ph_panoptic_merge's device records.  Three small kernels live here (k_assoc_things, k_assoc_gather, k_assoc_paint); the
 // arithmetic is ph_track.hip's kernels in their batched / device-count forms.  pack / create / run allocate no device memory, do not
-// synchronise and read no environment variable; ph_assoc_plan_match is the one stateful, synchronising call.
+// synchronise and read no environment variable; ph_assoc_plan_match is the one stateful, synchronising call, and ph_assoc_plan_track
+// (the device tracker, ph_dtracker.hip, and k_assoc_trklut) its launch-only counterpart.
 #include <string.h>
 
 #include <new>
@@ -250,6 +251,29 @@ __global__ void k_assoc_gather(const float* __restrict__ ext /*[B][K][4]*/, int 
     box[0] = e[0]; box[1] = e[1]; box[2] = e[2]; box[3] = e[3];
 }
 
+// one frame's track look-up table from the device tracker's outputs, as ph_assoc_plan_match forms it on the host: ids + 1, negatives
+// to 0, painted in segment order onto the ids in the order the tracker returns them; kept_count == 0 (a skipped or refused frame):
+// all zero.  One workgroup; ids_out (nullable): the frame's [cap] painted values
+__global__ __launch_bounds__(256) void k_assoc_trklut(const int32_t* __restrict__ tab, int K, int cap, const int64_t* __restrict__ ids,
+                                                      const int32_t* __restrict__ kept_count, double* __restrict__ lut,
+                                                      int64_t* __restrict__ ids_out) {
+    for (int i = threadIdx.x; i <= K; i += blockDim.x) lut[i] = 0.0;
+    __syncthreads();
+    int n = tab[0];
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    const int k = kept_count[0];
+    for (int j = threadIdx.x; j < cap; j += blockDim.x) {
+        int64_t v = 0;
+        if (j < n && j < k) {
+            v = ids[j] + 1;
+            if (v < 0) v = 0;
+            const int id = tab[1 + j];
+            if (id >= 0 && id <= K) lut[id] = (double)v;
+        }
+        if (ids_out) ids_out[j] = v;
+    }
+}
+
 // out[b][p] = lut[b][pan[b][p]] (ids outside 0 .. K read entry 0); the frame's table is staged in LDS.  T = uint8_t (sem) or double (track)
 template <typename T>
 __global__ __launch_bounds__(256) void k_assoc_paint(const int32_t* __restrict__ pan, const T* __restrict__ lut, T* __restrict__ out, int64_t HW,
@@ -442,4 +466,34 @@ extern "C" int ph_assoc_plan_match(ph_assoc_plan* p, ph_tracker* tracker, const 
     launch_paint<double>(g, pan, trk_dev, track_out, s);
     PH_CHECK_LAUNCH();
     return matched;
+}
+
+extern "C" int ph_assoc_plan_track(ph_assoc_plan* p, ph_dtracker* tracker, const int32_t* pan, const int32_t* things_dev, const float* embeds_dev,
+                                   double* track_out, int64_t* ids_dev_out, void* stream) {
+    PH_CHECK_ARG(p && tracker && pan && things_dev && embeds_dev && track_out, "null pointer");
+    const AGeo& g = p->g;
+    const PhDtrkScratch sc = ph_dtracker_scratch(tracker);
+    if (g.cap > sc.max_dets) {
+        ph_set_error("ph_assoc_plan_track: max_things = %d is more than the tracker's max_dets = %d", g.cap, sc.max_dets);
+        return PH_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* trk_dev = (double*)(p->ws + g.o_trk);
+    // one frame at a time: the tracker's per-frame outputs are its own buffer's, so the plan's workspace is what it was
+    for (int b = 0; b < g.B; ++b) {
+        const int32_t* tab = things_dev + (size_t)b * g.words;
+        ph_dtracker_io io{};
+        io.counts = tab;
+        io.labels = tab + 1 + g.cap;
+        io.boxes = (const float*)(tab + 1 + 2 * g.cap);
+        io.refuse = tab + g.words - 1;
+        io.embeds = embeds_dev + (size_t)b * g.cap * 256;
+        io.kept_out = sc.kept; io.ids_out = sc.ids; io.kept_counts = sc.kept_count;
+        PH_RUN(ph_dtracker_run(tracker, &io, 1, stream));
+        hipLaunchKernelGGL(k_assoc_trklut, dim3(1), dim3(256), 0, s, tab, g.K, g.cap, sc.ids, sc.kept_count, trk_dev + (size_t)b * (g.K + 1),
+                           ids_dev_out ? ids_dev_out + (size_t)b * g.cap : nullptr);
+    }
+    launch_paint<double>(g, pan, trk_dev, track_out, s);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
 }

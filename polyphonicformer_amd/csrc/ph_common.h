@@ -164,6 +164,16 @@ int ph_gemm_rows_splitk_cnt(const uint16_t* X, int im2col7, const uint16_t* Wp, 
 int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int groups, float eps, uint16_t* out, PhThings th, int B,
                       int prec, void* stream);
 
+// device-count form of ph_track_affinity (ph_track.hip) for the device tracker (ph_dtracker.hip): grids sized for (max_n, max_m), every
+// workgroup reading cnt = (n, m, need) on the device -- need == 0: nothing runs.  workspace: ph_track_affinity_workspace_bytes(max_n,
+// max_m).  Launches only; the caller checks the launch.
+void ph_track_affinity_cnt(const float* emb, const int32_t* labels, const float* memo_emb, const int32_t* memo_labels, int max_n, int max_m,
+                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, void* stream);
+// the device tracker's per-frame outputs inside its own buffer, for ph_assoc_plan_track (one frame at a time): kept [max_dets],
+// ids [max_dets], kept_count [1]
+struct PhDtrkScratch { int32_t* kept = nullptr; int64_t* ids = nullptr; int32_t* kept_count = nullptr; int max_dets = 0; };
+PhDtrkScratch ph_dtracker_scratch(const ph_dtracker* t);
+
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects
 // it for fp32 -> __bf16 conversions.

@@ -660,9 +660,17 @@ int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int
 //   bisoftmax: (softmax over the columns + softmax over the detections) / 2 of the dot products; softmax: the first term;
 //   cosine: dot products of the normalised vectors; `with_cats`: zero where the labels differ.
 // n <= 128, m <= 4096: three tiny launches (dot products: one thread per entry; column maxima / sums; row pass), all fp32.
-// The greedy assignment that consumes the matrix stays on the host (sequential, data dependent) -- one D2H of n * m floats.
+// The greedy assignment that consumes the matrix is the caller's: ph_tracker_match walks it on the host (one D2H of n * m floats),
+// the device tracker (ph_dtracker.hip) in one workgroup.
+// CNT: the device-count forms for the device tracker -- grids sized for (max_dets, capacity), (n, m, need) read from the frame record
+// `cnt` on the device, everything else (loop bounds, strides, reduction trees) the same code, so a score has the same bits.
+template <bool CNT>
 __global__ __launch_bounds__(256) void k_aff_dot(const float* __restrict__ emb, const float* __restrict__ memo, int n, int m,
-                                                 int cosine, float* __restrict__ dot) {
+                                                 const int32_t* __restrict__ cnt, int cosine, float* __restrict__ dot) {
+    if constexpr (CNT) {
+        if (!cnt[2]) return;
+        n = cnt[0]; m = cnt[1];
+    }
     const int j = blockIdx.x * 64 + (threadIdx.x & 63), i = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (i >= n || j >= m) return;
     const float4* a = (const float4*)(emb + (int64_t)i * 256);
@@ -681,8 +689,13 @@ __global__ __launch_bounds__(256) void k_aff_dot(const float* __restrict__ emb, 
     dot[(int64_t)i * m + j] = s;
 }
 // per column j: max_i dot[i][j] and sum_i exp(dot[i][j] - max)
-__global__ __launch_bounds__(256) void k_aff_colstat(const float* __restrict__ dot, int n, int m, float* __restrict__ cmax,
-                                                     float* __restrict__ csum) {
+template <bool CNT>
+__global__ __launch_bounds__(256) void k_aff_colstat(const float* __restrict__ dot, int n, int m, const int32_t* __restrict__ cnt,
+                                                     float* __restrict__ cmax, float* __restrict__ csum) {
+    if constexpr (CNT) {
+        if (!cnt[2]) return;
+        n = cnt[0]; m = cnt[1];
+    }
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     float mx = -INFINITY;
@@ -693,10 +706,15 @@ __global__ __launch_bounds__(256) void k_aff_colstat(const float* __restrict__ d
     csum[j] = s;
 }
 // one workgroup per detection row: row softmax, combined with the column softmax, category mask
+template <bool CNT>
 __global__ __launch_bounds__(256) void k_aff_rows(const float* __restrict__ dot, const int* __restrict__ lab, const int* __restrict__ memo_lab,
                                                   const float* __restrict__ cmax, const float* __restrict__ csum, int n, int m,
-                                                  int metric, int with_cats, float* __restrict__ score) {
+                                                  const int32_t* __restrict__ cnt, int metric, int with_cats, float* __restrict__ score) {
     __shared__ float red[256];
+    if constexpr (CNT) {
+        if (!cnt[2] || (int)blockIdx.x >= cnt[0]) return;       // uniform over the workgroup
+        n = cnt[0]; m = cnt[1];
+    }
     const int i = blockIdx.x, t = threadIdx.x;
     const float* d = dot + (int64_t)i * m;
     float mx = -INFINITY;
@@ -737,9 +755,22 @@ extern "C" int ph_track_affinity(const float* emb, const int32_t* labels, const 
     float* cmax = dot + (size_t)n * m;
     float* csum = cmax + m;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_aff_dot, dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, emb, memo_emb, n, m, metric == 2 ? 1 : 0, dot);
-    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat, dim3((m + 255) / 256), dim3(256), 0, s, dot, n, m, cmax, csum);
-    hipLaunchKernelGGL(k_aff_rows, dim3(n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, n, m, metric, with_cats, score);
+    hipLaunchKernelGGL(k_aff_dot<false>, dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, emb, memo_emb, n, m, nullptr, metric == 2 ? 1 : 0, dot);
+    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<false>, dim3((m + 255) / 256), dim3(256), 0, s, dot, n, m, nullptr, cmax, csum);
+    hipLaunchKernelGGL(k_aff_rows<false>, dim3(n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, n, m, nullptr, metric, with_cats, score);
     PH_CHECK_LAUNCH();
     return PH_OK;
+}
+
+// the device-count form (ph_common.h): the caller checked the sizes; the workspace is laid out for (max_n, max_m) as above with the
+// frame's own m as the row stride of dot / score
+void ph_track_affinity_cnt(const float* emb, const int32_t* labels, const float* memo_emb, const int32_t* memo_labels, int max_n, int max_m,
+                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, void* stream) {
+    float* dot = (float*)workspace;
+    float* cmax = dot + (size_t)max_n * max_m;
+    float* csum = cmax + max_m;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_aff_dot<true>, dim3((max_m + 63) / 64, (max_n + 3) / 4), dim3(256), 0, s, emb, memo_emb, 0, 0, cnt, metric == 2 ? 1 : 0, dot);
+    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<true>, dim3((max_m + 255) / 256), dim3(256), 0, s, dot, 0, 0, cnt, cmax, csum);
+    hipLaunchKernelGGL(k_aff_rows<true>, dim3(max_n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, 0, 0, cnt, metric, with_cats, score);
 }

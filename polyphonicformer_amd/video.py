@@ -475,14 +475,19 @@ class VideoAssociator:
         self.num_thing_classes, self.num_stuff_classes, self.strides = num_thing_classes, num_stuff_classes, strides
         self.init_tracker()
 
-    native_plan, max_things = False, 100          # `use_native_plan`
+    native_plan, max_things, device_tracker = False, 100, False          # `use_native_plan`
+    DEVICE_CAPACITY, DEVICE_MAX_DETS = QuasiDenseEmbedTracker.NATIVE_CAPACITY, QuasiDenseEmbedTracker.NATIVE_MAX_DETS
 
-    def use_native_plan(self, on=True, max_things=None):
+    def use_native_plan(self, on=True, max_things=None, device_tracker=False):
         """`step_records` for clips whose merge left its records on the device (`panoptic.BatchMerge`): the whole step as the native
         association plan (csrc/ph_assocplan.hip) -- one launch-only call and one synchronising tracker call for B frames, no
         `segments_info` on the host.  Off (the default) nothing changes: `step` / `step_device` are the Python chain.
-        `max_things`: RoIs per frame the plan's launches are sized for (a frame with more is an error), at most the merge's K."""
-        self.native_plan = bool(on)
+        `max_things`: RoIs per frame the plan's launches are sized for (a frame with more is an error), at most the merge's K.
+        `device_tracker=True`: the tracker's state lives on the device too (csrc/ph_dtracker.hip) and `step_records` is launches only
+        -- no synchronisation, `self.cnt` is not touched, `frames_matched()` reads the status record; a frame with more than
+        `max_things` things is then a refused frame in that record (`device_status()`), not an exception."""
+        self.native_plan, self.device_tracker = bool(on), bool(on and device_tracker)
+        self._dtracker = None
         if max_things is not None:
             self.max_things = int(max_things)
         self._nplans = {}
@@ -519,10 +524,31 @@ class VideoAssociator:
         K = (seg_records_dev.shape[1] - 1) // 5
         plan = self._native_plan_for(levels, pan_dev, K)
         plan.run(pan_dev, seg_records_dev, levels)
+        if self.device_tracker:
+            return plan.sem, plan.track(self._device_tracker_for(pan_dev.device), pan_dev)[0]
         handle = self.tracker._native_handle(pan_dev.device)
         trk, _, matched = plan.match(handle, pan_dev, self.cnt)
         self.cnt += matched
         return plan.sem, trk
+
+    def _device_tracker_for(self, dev):
+        from . import engine as E
+        if self.__dict__.get("_dtracker") is None:
+            kw = {k: v for k, v in self.tracker_cfg.items() if k != "type"}
+            self._dtracker = E.NativeDeviceTracker(E.native_tracker_cfg(**kw), dev, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
+        return self._dtracker
+
+    def device_status(self):
+        """the device tracker's status record (engine.NativeDeviceTracker.status; synchronises); None before its first frame"""
+        d = self.__dict__.get("_dtracker")
+        return None if d is None else d.status()
+
+    def frames_matched(self):
+        """frames the tracker has matched since `init_tracker`; with the device tracker a synchronising read of its status record"""
+        if self.device_tracker:
+            st = self.device_status()
+            return 0 if st is None else st["matched"]
+        return self.cnt - 1
 
     def init_tracker(self):
         """polyphonic_former_video.py:59-61"""
@@ -530,6 +556,8 @@ class VideoAssociator:
         cfg.setdefault("type", "QuasiDenseEmbedTracker")         # the config's own dict (with `type`) or bare kwargs
         self.tracker = TRACKERS.build(cfg)                       # build_tracker(self.tracker_cfg), polyphonic_former_video.py:60
         self.cnt = 1
+        if self.__dict__.get("_dtracker") is not None:
+            self._dtracker.reset(1)
 
     def record(self, fpn_feats, panoptic_seg, segments_info, pan_dev=None):
         from . import track_head as T, engine as E
