@@ -172,6 +172,14 @@ class DvpqIO(C.Structure):
                                           "depth_out")]
 
 
+# C typedef name -> its mirror above: every Structure of this module (tests/test_abi.py compares each layout with the header's)
+STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
+           "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
+           "ph_neck_cfg": NeckCfg, "ph_neck_layout": NeckLayout, "ph_neck_geometry": NeckGeometry, "ph_neck_io": NeckIO,
+           "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
+           "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
+           "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO}
+
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {

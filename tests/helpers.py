@@ -99,6 +99,79 @@ def load_golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+def last_error():
+    """the library's message for the last call that failed on this thread (ph_last_error_string)"""
+    from polyphonicformer_amd import _lib
+    return _lib.load().ph_last_error_string().decode()
+
+
+def elf_needed(path):
+    """DT_NEEDED entries of an ELF64 little-endian file (the dynamic section and its string table)"""
+    import struct
+    with open(path, "rb") as f:
+        d = f.read()
+    assert d[:4] == b"\x7fELF" and d[4] == 2 and d[5] == 1
+    shoff, = struct.unpack_from("<Q", d, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
+    sec = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
+    out = []
+    for name, typ, flags, addr, off, size, link, info, align, entsize in sec:
+        if typ != 6:                                     # SHT_DYNAMIC
+            continue
+        stroff = sec[link][4]
+        for o in range(off, off + size, 16):
+            tag, val = struct.unpack_from("<qQ", d, o)
+            if tag == 1:                                 # DT_NEEDED
+                out.append(d[stroff + val:d.index(b"\0", stroff + val)].decode())
+    return out
+
+
+# every variable a Python plan of tests/test_gpu_native_{plan,khead,neck}.py reads from the environment
+PLAN_KNOBS = ("PH_POOL_NSPLIT", "PH_CONV_UP2", "PH_CONV_POOLX", "PH_POOLX_NSPLIT", "PH_UP2_SHARED_WGS",
+              "PH_KHEAD_TWOPASS", "PH_KHEAD1_PAIR", "PH_KHEAD_NO_FALLBACK",
+              "PH_CONV_TH", "PH_CONV_TH_NOW", "PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS", "PH_GNSUM_TPW", "PH_GNSUM_WGS",
+              "PH_CPLANES_TPW", "PH_NECK_STATS3", "PH_NECK_APPLY3")
+
+
+def clear_plan_knobs(monkeypatch):
+    """the body of those files' autouse fixture: a test starts with none of PLAN_KNOBS set (what it sets itself comes after)"""
+    for k in PLAN_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+
+
+def graph_kernel_nodes(run):
+    """sorted [grid x, y, z, block x, LDS bytes] of every kernel node of `run()` captured into a HIP graph (after one eager call)"""
+    import ctypes as C
+
+    class Dim3(C.Structure):
+        _fields_ = [("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint)]
+
+    class KernelNodeParams(C.Structure):           # hipKernelNodeParams
+        _fields_ = [("blockDim", Dim3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", Dim3), ("kernelParams", C.c_void_p),
+                    ("sharedMemBytes", C.c_uint)]
+    hip = C.CDLL(next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64.so" in l))
+    run()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph(keep_graph=True)
+    with torch.cuda.graph(g):
+        run()
+    graph = C.c_void_p(g.raw_cuda_graph())
+    n = C.c_size_t(0)
+    assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0
+    arr = (C.c_void_p * n.value)()
+    assert hip.hipGraphGetNodes(graph, arr, C.byref(n)) == 0
+    out = []
+    for node in arr:
+        t = C.c_int(-1)
+        assert hip.hipGraphNodeGetType(C.c_void_p(node), C.byref(t)) == 0
+        if t.value != 0:                         # kernel nodes only
+            continue
+        p = KernelNodeParams()
+        assert hip.hipGraphKernelNodeGetParams(C.c_void_p(node), C.byref(p)) == 0
+        out.append([p.gridDim.x, p.gridDim.y, p.gridDim.z, p.blockDim.x, p.sharedMemBytes])
+    return sorted(out)
+
+
 def tracker_records(seed, nframes=12, nobj=14):
     """a synthetic clip: objects drift, appear and disappear; embeddings = identity vector + noise"""
     g = torch.Generator().manual_seed(seed)

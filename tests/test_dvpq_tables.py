@@ -1,18 +1,14 @@
 """DVPQ from per-frame tallies (dvps_eval.clip_tallies / depth_errors_from_tallies) against the metric on whole maps and the goldens
-of the unmodified reference evaluator, and the host side of ph_dvpq_frames (include/polyhead.h): symbols, struct layouts, refusals.
+of the unmodified reference evaluator, and the host side of ph_dvpq_frames (include/polyhead.h): its refusals.
 No GPU: nothing here launches a kernel (tests/test_gpu_dvpq.py does)."""
 import ctypes as C
 import json
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 import helpers as Hh
 from polyphonicformer_amd import _lib
-from polyphonicformer_amd import build as BLD
 from polyphonicformer_amd import dvps_eval as D
 
 THRS = (0.5, 0.25, 0.1)
@@ -82,44 +78,6 @@ def test_relabelling_and_the_zero_key():
     a = D.clip_tallies([t], 0, 19)
     b = D.vpq_eval(np.array([0] * 5 + [190000] + [7] * 2), np.zeros(8, dtype=np.int64), num_classes=19)
     assert all(np.array_equal(x, y) for x, y in zip(a, b))
-
-
-def test_symbols_are_exported_and_declared():
-    lib = _lib.load()
-    hdr = open(os.path.join(Hh.REPO, "include", "polyhead.h")).read()
-    for name in ("ph_dvpq_workspace_bytes", "ph_dvpq_frames"):
-        assert hasattr(lib, name), name
-        assert name in _lib.SIGNATURES, name
-        assert name + "(" in hdr, name
-    assert os.path.exists(os.path.join(BLD.CSRC, "ph_dvpq.hip"))
-
-
-def test_struct_sizes_and_offsets_match_ctypes():
-    structs = {"ph_dvpq_cfg": _lib.DvpqCfg, "ph_dvpq_io": _lib.DvpqIO}
-    cc = shutil.which("cc") or shutil.which("gcc") or BLD._hipcc()
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "polyhead.h"', 'int main(void) {']
-    for cname, cls in structs.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for field, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));')
-    lines += ['printf("MAXTHR %d\\n", (int)PH_DVPQ_MAX_THR);', 'return 0;', '}']
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "t.c"), "w") as f:
-            f.write("\n".join(lines))
-        exe = os.path.join(d, "t")
-        lang = [] if os.path.basename(cc) in ("cc", "gcc") else ["-x", "c++"]
-        subprocess.run([cc] + lang + ["-I", os.path.join(BLD.HERE, "..", "include"), os.path.join(d, "t.c"), "-o", exe], check=True,
-                       capture_output=True, timeout=300)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
-    c = {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
-    assert c.pop("MAXTHR") == _lib.PH_DVPQ_MAX_THR == 8
-    assert len(c) == 2 + 6 + 8
-    for key, val in c.items():
-        if "." in key:
-            struct, field = key.split(".")
-            assert getattr(structs[struct], field).offset == val, key
-        else:
-            assert C.sizeof(structs[key]) == val, key
 
 
 def _cfg(**kw):

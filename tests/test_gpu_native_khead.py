@@ -21,7 +21,6 @@ import polyphonicformer_amd.kernel_head  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("PH_KHEAD_TWOPASS", "PH_POOL_NSPLIT", "PH_KHEAD1_PAIR", "PH_KHEAD_NO_FALLBACK")
 OUTS = ("xp", "dp", "bits", "x_f32", "dfe_f32", "mask_preds", "seg_preds", "depth_pred", "proposal")
 NQ, N_THING, N_STUFF = 100, 8, 11          # num_proposals not a multiple of 32, 19 classes with 8 things
 L = N_THING + N_STUFF
@@ -29,8 +28,7 @@ L = N_THING + N_STUFF
 
 @pytest.fixture(autouse=True)
 def _no_knobs(monkeypatch):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    Hh.clear_plan_knobs(monkeypatch)
 
 
 _HEADS = {}
@@ -376,41 +374,12 @@ def test_module_api_switch(gpu):
 # Child process of test_environment_does_not_reach_the_native_plan: captures one a1 call of a native plan (an explicit, zero-
 # initialised cfg: the module API's) and of the Python plan into graphs and prints the (grid, block, LDS) of every kernel node.
 _GRAPH_NODES = r"""
-import ctypes as C, json, sys
+import json, sys
 sys.path[:0] = [".", "tests"]
 import torch
 import helpers as Hh
 from polyphonicformer_amd import _lib, engine as E
 import test_gpu_native_khead as T
-
-class Dim3(C.Structure):
-    _fields_ = [("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint)]
-class KernelNodeParams(C.Structure):           # hipKernelNodeParams
-    _fields_ = [("blockDim", Dim3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", Dim3), ("kernelParams", C.c_void_p),
-                ("sharedMemBytes", C.c_uint)]
-hip = C.CDLL(next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64.so" in l))
-
-def nodes(run):
-    run()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g):
-        run()
-    graph = C.c_void_p(g.raw_cuda_graph())
-    n = C.c_size_t(0)
-    assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0
-    arr = (C.c_void_p * n.value)()
-    assert hip.hipGraphGetNodes(graph, arr, C.byref(n)) == 0
-    out = []
-    for node in arr:
-        t = C.c_int(-1)
-        assert hip.hipGraphNodeGetType(C.c_void_p(node), C.byref(t)) == 0
-        if t.value != 0:                         # kernel nodes only
-            continue
-        p = KernelNodeParams()
-        assert hip.hipGraphKernelNodeGetParams(C.c_void_p(node), C.byref(p)) == 0
-        out.append([p.gridDim.x, p.gridDim.y, p.gridDim.z, p.blockDim.x, p.sharedMemBytes])
-    return sorted(out)
 
 dev = torch.device("cuda:0")
 B, H, W = 2, 48, 156
@@ -425,7 +394,7 @@ nat = E.NativeKernelHeadPlan(pack, B, H, W, T.N_THING, T.L, True, dev, cfg=cfg)
 py = E.KernelHeadPlan(pack, B, H, W, T.N_THING, T.L, True, dev)
 for name, plan in (("native", nat), ("python", py)):
     plan.set_inputs(feats)
-    res[name] = nodes(plan.run)
+    res[name] = Hh.graph_kernel_nodes(plan.run)
 res["onepass"] = [bool(nat.onepass), bool(py.onepass)]
 print(json.dumps(res))
 """
@@ -437,7 +406,7 @@ def test_environment_does_not_reach_the_native_plan(gpu):
     are the same with and without them -- while the Python plan's change.  Without the variables both plans capture the same
     launches."""
     knobs = dict(PH_KHEAD1_PAIR="1", PH_KHEAD_TWOPASS="1", PH_POOL_NSPLIT="3")
-    base = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    base = {k: v for k, v in os.environ.items() if k not in Hh.PLAN_KNOBS}
     out = {}
     for name, env in (("clean", base), ("knobs", dict(base, **knobs))):
         r = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", _GRAPH_NODES], cwd=Hh.REPO, env=env, capture_output=True,
@@ -493,7 +462,7 @@ def test_head_program(gpu, case, tmp_path):
         tofile([sd[lib.ph_decode_param_name(i).decode()] for i in range(_lib.PH_DECODE_NPARAMS)], f"stage{s}.bin")
     for i, f in enumerate(feats):
         tofile([f], f"f{i}.bin")
-    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME") and k not in KNOBS}
+    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME") and k not in Hh.PLAN_KNOBS}
     r = subprocess.run(["timeout", "-k", "10", "240", BLD.HEAD_EXAMPLE, str(d_in), str(d_out)], capture_output=True, text=True, env=env,
                        timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -33,8 +33,6 @@ import polyphonicformer_amd.kernel_head  # noqa: F401
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
-KNOBS = ("PH_CONV_TH", "PH_CONV_TH_NOW", "PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS", "PH_GNSUM_TPW", "PH_GNSUM_WGS", "PH_CPLANES_TPW",
-         "PH_NECK_STATS3", "PH_NECK_APPLY3", "PH_KHEAD_TWOPASS", "PH_POOL_NSPLIT")
 S1_ISSUE = ((9, 13), (5, 7), (3, 4), (2, 2))
 S2_ISSUE = ((16, 140), (8, 70), (4, 35), (2, 18))
 S1 = ((7, 15), (4, 8), (2, 4), (1, 2))
@@ -51,8 +49,7 @@ ORACLE_TOL = 1e-3                                            # tests/test_gpu_ne
 
 @pytest.fixture(autouse=True)
 def _no_knobs(monkeypatch):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    Hh.clear_plan_knobs(monkeypatch)
 
 
 def _fill(m, seed):
@@ -576,7 +573,7 @@ def test_neck_program(gpu, case, tmp_path):
         tofile([sd[lib.ph_decode_param_name(i).decode()] for i in range(_lib.PH_DECODE_NPARAMS)], f"stage{s}.bin")
     for i, f in enumerate(feats):
         tofile([f], f"p{i}.bin")
-    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME") and k not in KNOBS}
+    env = {k: v for k, v in os.environ.items() if k not in ("PYTHONPATH", "PYTHONHOME") and k not in Hh.PLAN_KNOBS}
     r = subprocess.run(["timeout", "-k", "10", "240", BLD.NECK_EXAMPLE, str(d_in), str(d_out)], capture_output=True, text=True, env=env,
                        timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -23,7 +23,6 @@ pytestmark = pytest.mark.gpu
 MODES = ["fp32", "mixed", "mixed16", "fp16", "bf16"]
 OUT16 = {"fp32": torch.float32, "mixed": torch.float32, "mixed16": torch.float16, "fp16": torch.float16, "bf16": torch.bfloat16}
 TOL_IDENT = {"fp32": 1e-3, "mixed": 1e-3, "mixed16": 1e-3, "fp16": 1e-3, "bf16": 3e-2}      # tests/test_gpu_configs.py
-KNOBS = ("PH_POOL_NSPLIT", "PH_CONV_UP2", "PH_CONV_POOLX", "PH_POOLX_NSPLIT", "PH_UP2_SHARED_WGS")
 
 # name -> (workload, B, shares_gpu): cfg1's exact shape (one frame 32 x 64, N = 100, one stage), cfg3 (N = 111, S = 3) at one and
 # eight frames, cfg5 (48 x 156, N = 253), one 32-frame part of the headline step (cfg2 geometry, a part of a multi-stream step)
@@ -38,8 +37,7 @@ CASES = {
 
 @pytest.fixture(autouse=True)
 def _no_knobs(monkeypatch):
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
+    Hh.clear_plan_knobs(monkeypatch)
 
 
 def _equal_outputs(a, b, what):
@@ -368,40 +366,12 @@ def test_example_program(gpu, mode, tmp_path):
 # Child process of test_environment_does_not_reach_the_native_plan: captures one decode of a native plan and of the Python plan
 # (same packs, the fused final stage) into graphs and prints the (grid, block, LDS) of every kernel node, as JSON.
 _GRAPH_NODES = r"""
-import ctypes as C, json, sys
+import json, sys
 sys.path[:0] = [".", "tests"]
 import torch
 import bench
+import helpers as Hh
 from polyphonicformer_amd import engine as E
-
-class Dim3(C.Structure):
-    _fields_ = [("x", C.c_uint), ("y", C.c_uint), ("z", C.c_uint)]
-class KernelNodeParams(C.Structure):           # hipKernelNodeParams
-    _fields_ = [("blockDim", Dim3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", Dim3), ("kernelParams", C.c_void_p),
-                ("sharedMemBytes", C.c_uint)]
-hip = C.CDLL(next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64.so" in l))
-
-def nodes(run):
-    run()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g):
-        run()
-    graph = C.c_void_p(g.raw_cuda_graph())
-    n = C.c_size_t(0)
-    assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0
-    arr = (C.c_void_p * n.value)()
-    assert hip.hipGraphGetNodes(graph, arr, C.byref(n)) == 0
-    out = []
-    for node in arr:
-        t = C.c_int(-1)
-        assert hip.hipGraphNodeGetType(C.c_void_p(node), C.byref(t)) == 0
-        if t.value != 0:                         # kernel nodes only
-            continue
-        p = KernelNodeParams()
-        assert hip.hipGraphKernelNodeGetParams(C.c_void_p(node), C.byref(p)) == 0
-        out.append([p.gridDim.x, p.gridDim.y, p.gridDim.z, p.blockDim.x, p.sharedMemBytes])
-    return sorted(out)
 
 dev = torch.device("cuda:0")
 wl = bench.WORKLOADS["cfg3"]
@@ -414,7 +384,7 @@ for name, cls in (("native", E.NativeDecodePlan), ("python", E.DecodePlan)):
     plan = cls(packs, B, N, wl["H"], wl["W"], "fp16", torch.float16, dev, frame_invariant=False)
     assert plan.fused_up
     plan.set_inputs(g["x"], g["dfe"], g["k0"], g["q0"], g["m0"])
-    res[name] = nodes(plan.run)
+    res[name] = Hh.graph_kernel_nodes(plan.run)
 print(json.dumps(res))
 """
 
@@ -425,7 +395,7 @@ def test_environment_does_not_reach_the_native_plan(gpu):
     (grid, block, LDS) are the same with and without them, while the Python plan's -- through the public entry points -- change.
     Without the variables both plans capture the same launches."""
     knobs = dict(PH_UP2_WGS="7", PH_CONV_WGS="5", PH_QUERY_NRT="1")
-    base = {k: v for k, v in os.environ.items() if k not in knobs and k not in KNOBS}
+    base = {k: v for k, v in os.environ.items() if k not in knobs and k not in Hh.PLAN_KNOBS}
     out = {}
     for name, env in (("clean", base), ("knobs", dict(base, **knobs))):
         r = subprocess.run(["timeout", "-k", "10", "400", sys.executable, "-c", _GRAPH_NODES], cwd=Hh.REPO, env=env, capture_output=True,

@@ -1,38 +1,24 @@
-"""Host-side checks of the native neck plan (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs): the exported symbols,
-the struct layouts the ctypes side assumes, the parameter table against the reference's state_dict keys, the pack layout, the
+"""Host-side checks of the native neck plan (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs): the parameter table against the reference's state_dict keys, the pack layout, the
 workspace size, argument validation and the geometry rules (`fused_out`, `c16`, `tile_rows`).  No GPU: nothing here launches a
 kernel (tests/test_gpu_native_neck.py does)."""
 import ctypes as C
 import json
 import os
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
 import helpers as Hh
 from polyphonicformer_amd import _lib, engine as E
-from polyphonicformer_amd import build as BLD
 from polyphonicformer_amd.registry import NECKS
 import polyphonicformer_amd.semantic_fpn  # noqa: F401
-from test_native_plan import _elf_needed
 
-NEW_SYMBOLS = ["ph_neck_param_name", "ph_neck_param_numel", "ph_neck_pack_bytes", "ph_neck_pack_layout", "ph_neck_pack", "ph_neck_posenc",
-               "ph_neck_plan_workspace_bytes", "ph_neck_plan_create", "ph_neck_plan_info", "ph_neck_plan_destroy", "ph_neck_plan_run",
-               "ph_neck_plan_run_level", "ph_neck_plan_run_outputs"]
 FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and never dereferences
-STRUCTS = {"ph_neck_cfg": _lib.NeckCfg, "ph_neck_io": _lib.NeckIO, "ph_neck_geometry": _lib.NeckGeometry, "ph_neck_layout": _lib.NeckLayout}
 S3 = ((32, 64), (16, 32), (8, 16), (4, 8))
 # the issue's S1 and S2: stride-2 pyramids by the (n + 1) / 2 rule whose levels 2 / 3 do not reach level 1's size by x2 upsampling
 # (3 x 4 -> 6 x 8, not 5 x 7; 2 x 18 -> 8 x 72, not 8 x 70).  The reference's level sum is undefined there and engine.NeckPlan raises in
 # the middle of its run; the native plan must refuse them BEFORE any launch
 S1_ISSUE = ((9, 13), (5, 7), (3, 4), (2, 2))
 S2_ISSUE = ((16, 140), (8, 70), (4, 35), (2, 18))
-
-
-def _msg():
-    return _lib.load().ph_last_error_string().decode()
 
 
 def _cfg(shapes=S3, **kw):
@@ -46,45 +32,6 @@ def _neck(num_aux_convs=2, groups=32):
                             upsample_times=2, positional_encoding=dict(type="SinePositionalEncoding", num_feats=128, normalize=True),
                             cat_coors=False, cat_coors_level=3, fuse_by_cat=False, return_list=False, num_aux_convs=num_aux_convs,
                             norm_cfg=dict(type="GN", num_groups=groups, requires_grad=True)))
-
-
-def test_new_symbols_are_exported():
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name), name
-        assert name in _lib.SIGNATURES, name
-
-
-def test_struct_sizes_and_offsets_match_ctypes():
-    """sizeof / offsetof of the new structs as a C compiler sees include/polyhead.h"""
-    cc = shutil.which("cc") or shutil.which("gcc") or BLD._hipcc()
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "polyhead.h"', 'int main(void) {']
-    for cname, cls in STRUCTS.items():
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for field, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{field} %zu\\n", offsetof({cname}, {field}));')
-    lines.append('printf("PH_NPACK_COUNT %d\\nPH_NECK_NPARAMS %d\\nPH_NPACK_OUTS_W %d\\nPH_NPACK_OUTS_GN %d\\nWP9 %d\\nBETA9 %d\\n", '
-                 '(int)PH_NPACK_COUNT, (int)PH_NECK_NPARAMS, (int)PH_NPACK_OUTS_W, (int)PH_NPACK_OUTS_GN, PH_NPACK_WP(9), PH_NPACK_BETA(9));')
-    lines += ['return 0;', '}']
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "t.c"), "w") as f:
-            f.write("\n".join(lines))
-        exe = os.path.join(d, "t")
-        lang = [] if os.path.basename(cc) in ("cc", "gcc") else ["-x", "c++"]
-        subprocess.run([cc] + lang + ["-I", os.path.join(BLD.HERE, "..", "include"), os.path.join(d, "t.c"), "-o", exe], check=True,
-                       capture_output=True, timeout=300)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
-    c = {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
-    assert c.pop("PH_NPACK_COUNT") == _lib.PH_NPACK_COUNT == 3 * _lib.PH_NECK_NCONVS + 2
-    assert c.pop("PH_NECK_NPARAMS") == _lib.PH_NECK_NPARAMS == 3 * _lib.PH_NECK_NCONVS
-    assert (c.pop("PH_NPACK_OUTS_W"), c.pop("PH_NPACK_OUTS_GN")) == (_lib.PH_NPACK_OUTS_W, _lib.PH_NPACK_OUTS_GN)
-    assert (c.pop("WP9"), c.pop("BETA9")) == (27, 29)
-    for key, val in c.items():
-        if "." in key:
-            struct, field = key.split(".")
-            assert getattr(STRUCTS[struct], field).offset == val, key
-        else:
-            assert C.sizeof(STRUCTS[key]) == val, key
 
 
 def test_param_table_is_the_reference_state_dict():
@@ -161,11 +108,11 @@ def test_bad_cfgs_are_refused_with_a_message():
            (dict(eps=-1.0), "eps")]
     for kw, word in bad:
         cfg = _cfg(**kw)
-        assert lib.ph_neck_plan_workspace_bytes(C.byref(cfg)) == 0 and word in _msg(), (kw, _msg())
-        assert lib.ph_neck_pack_bytes(C.byref(cfg)) == 0 and word in _msg(), kw
+        assert lib.ph_neck_plan_workspace_bytes(C.byref(cfg)) == 0 and word in Hh.last_error(), (kw, Hh.last_error())
+        assert lib.ph_neck_pack_bytes(C.byref(cfg)) == 0 and word in Hh.last_error(), kw
         h = C.c_void_p()
         rc = lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h))
-        assert rc < 0 and not h.value and word in _msg(), kw
+        assert rc < 0 and not h.value and word in Hh.last_error(), kw
     # the two shape errors are "unsupported", like the over-asked fused form; the rest are invalid arguments
     h = C.c_void_p()
     for kw in (dict(shapes=S1_ISSUE), dict(shapes=((9, 13), (5, 8), (3, 4), (2, 2))), dict(fused_out=_lib.PH_KNOB_ON, num_outs=1)):
@@ -174,32 +121,32 @@ def test_bad_cfgs_are_refused_with_a_message():
     cfg = _cfg()
     need = lib.ph_neck_plan_workspace_bytes(C.byref(cfg))
     assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), need - 256, C.byref(h)) == -4
-    assert "workspace too small" in _msg() and not h.value
-    assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR + 16), need, C.byref(h)) == -1 and "aligned" in _msg()
+    assert "workspace too small" in Hh.last_error() and not h.value
+    assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR + 16), need, C.byref(h)) == -1 and "aligned" in Hh.last_error()
     assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), need, C.byref(h)) == 0 and h.value
     # run-time pointer checks come back before any launch (no GPU in this process' tests: a launch on the fake addresses would fault)
     run = lambda **kw: lib.ph_neck_plan_run(h, C.byref(_io(**kw)), None)
-    assert run(feat2=None) == -1 and "level 2" in _msg()
-    assert run(posenc=None) == -1 and "posenc" in _msg()
-    assert run(plane1=None) == -1 and "out_planes[1]" in _msg()
-    assert run(plane0=FAKE_PTR + 4) == -1 and "16-byte" in _msg()
-    assert lib.ph_neck_plan_run_level(h, 4, C.byref(_io()), None) == -1 and "level" in _msg()
-    assert lib.ph_neck_plan_run_level(h, 1, C.byref(_io(feat1=None)), None) == -1 and "level 1" in _msg()
-    assert lib.ph_neck_plan_run_outputs(h, C.byref(_io(plane2=None)), None) == -1 and "out_planes[2]" in _msg()
+    assert run(feat2=None) == -1 and "level 2" in Hh.last_error()
+    assert run(posenc=None) == -1 and "posenc" in Hh.last_error()
+    assert run(plane1=None) == -1 and "out_planes[1]" in Hh.last_error()
+    assert run(plane0=FAKE_PTR + 4) == -1 and "16-byte" in Hh.last_error()
+    assert lib.ph_neck_plan_run_level(h, 4, C.byref(_io()), None) == -1 and "level" in Hh.last_error()
+    assert lib.ph_neck_plan_run_level(h, 1, C.byref(_io(feat1=None)), None) == -1 and "level 1" in Hh.last_error()
+    assert lib.ph_neck_plan_run_outputs(h, C.byref(_io(plane2=None)), None) == -1 and "out_planes[2]" in Hh.last_error()
     lib.ph_neck_plan_destroy(h)
     cfg = _cfg(pos_level=-1, emit_planes=0, emit_f32=1)
     assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h)) == 0
-    assert run() == -1 and "posenc" in _msg()                                   # a table without a pos_level
-    assert run(posenc=None) == -1 and "out_f32[0]" in _msg()
+    assert run() == -1 and "posenc" in Hh.last_error()                                   # a table without a pos_level
+    assert run(posenc=None) == -1 and "out_f32[0]" in Hh.last_error()
     lib.ph_neck_plan_destroy(h)
     # pack arguments
     params = (C.c_void_p * _lib.PH_NECK_NPARAMS)(*([FAKE_PTR] * _lib.PH_NECK_NPARAMS))
     cfg = _cfg(num_outs=2)
-    assert lib.ph_neck_pack(C.byref(cfg), params, C.c_void_p(FAKE_PTR + 16), None) == -1 and "aligned" in _msg()
+    assert lib.ph_neck_pack(C.byref(cfg), params, C.c_void_p(FAKE_PTR + 16), None) == -1 and "aligned" in Hh.last_error()
     params[25] = None
-    assert lib.ph_neck_pack(C.byref(cfg), params, C.c_void_p(FAKE_PTR), None) == -1 and "aux_convs.0.gn.weight" in _msg()
-    assert lib.ph_neck_posenc(0, 4, 128, 10000.0, 6.28, 1e-6, C.c_void_p(FAKE_PTR), None) == -1 and "bad size" in _msg()
-    assert lib.ph_neck_posenc(2, 4, 128, 10000.0, 6.28, 1e-6, None, None) == -1 and "null out" in _msg()
+    assert lib.ph_neck_pack(C.byref(cfg), params, C.c_void_p(FAKE_PTR), None) == -1 and "aux_convs.0.gn.weight" in Hh.last_error()
+    assert lib.ph_neck_posenc(0, 4, 128, 10000.0, 6.28, 1e-6, C.c_void_p(FAKE_PTR), None) == -1 and "bad size" in Hh.last_error()
+    assert lib.ph_neck_posenc(2, 4, 128, 10000.0, 6.28, 1e-6, None, None) == -1 and "null out" in Hh.last_error()
 
 
 def _io(**kw):
@@ -216,7 +163,7 @@ def _io(**kw):
 def _geo(cfg):
     lib = _lib.load()
     h, g = C.c_void_p(), _lib.NeckGeometry()
-    assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h)) == 0, _msg()
+    assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h)) == 0, Hh.last_error()
     assert lib.ph_neck_plan_info(h, C.byref(g)) == 0
     lib.ph_neck_plan_destroy(h)
     return g
@@ -294,11 +241,3 @@ def test_module_switch_refuses_borrowed_clips():
     with pytest.raises(_lib.PolyheadError, match="native neck plan"):
         m.ingest_frames([])
     assert m.use_native_plan(False).native_plan is False
-
-
-def test_neck_program_links_no_python():
-    """the C++ caller of the neck + head is built next to the library and depends on libpolyhead.so and the HIP runtime only"""
-    assert os.path.exists(BLD.NECK_EXAMPLE), "built by python -m polyphonicformer_amd.build"
-    needed = _elf_needed(BLD.NECK_EXAMPLE)
-    assert "libpolyhead.so" in needed and any(n.startswith("libamdhip64") for n in needed)
-    assert not any("python" in n or "torch" in n or "c10" in n for n in needed), needed

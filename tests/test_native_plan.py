@@ -1,13 +1,11 @@
-"""Host-side checks of the native decode plan (include/polyhead.h ph_decode_*): the exported symbols, the struct layouts the
-ctypes side assumes, the workspace rule against engine.DecodePlan's buffers, the launch geometry rule (one copy, in the library:
-ph_decode_geometry_of, which engine.DecodePlan asks too) against the choices recorded in tests/golden/plan_geometry.json, the
-pack layout against pack.py's, argument validation, and the Python-free example program's dependencies.  No GPU: nothing here
-launches a kernel."""
+"""Host-side checks of the native decode plan (include/polyhead.h ph_decode_*): the workspace rule against engine.DecodePlan's
+buffers, the launch geometry rule (one copy, in the library: ph_decode_geometry_of, which engine.DecodePlan asks too) against the
+choices recorded in tests/golden/plan_geometry.json, the pack layout against pack.py's, and argument validation (symbols, struct
+layouts and the example programs' dependencies: tests/test_abi.py).  No GPU: nothing here launches a kernel."""
 import ctypes as C
 import functools
 import json
 import os
-import shutil
 import subprocess
 import sys
 
@@ -15,13 +13,10 @@ import pytest
 import torch
 
 import bench
+import helpers as Hh
 from polyphonicformer_amd import _lib, engine as E
 from polyphonicformer_amd import build as BLD
 from polyphonicformer_amd.pack import pack_stage
-
-NEW_SYMBOLS = ["ph_decode_param_name", "ph_decode_param_numel", "ph_decode_pack_bytes", "ph_decode_pack_layout", "ph_decode_pack_stage",
-               "ph_decode_workspace_bytes", "ph_decode_create", "ph_decode_info", "ph_decode_geometry_of", "ph_decode_destroy",
-               "ph_decode_run", "ph_pool_default_nsplit"]
 
 # (B, N, H, W, S, L): cfg1 (256x512 -> 32x64, N = 100, 1 stage), cfg2 / cfg3 (128x256, N = 153 / 111), cfg5 (48x156, N = 253)
 SHAPES = {"cfg1": (100, 32, 64, 1, 19), "cfg2": (153, 128, 256, 3, 133), "cfg3": (111, 128, 256, 3, 19), "cfg5": (253, 48, 156, 3, 133)}
@@ -31,58 +26,6 @@ FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and nev
 
 def _lib_loaded():
     return _lib.load()
-
-
-def test_new_symbols_are_exported():
-    lib = _lib_loaded()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name), name
-        assert name in _lib.SIGNATURES, name
-
-
-def _c_layout():
-    """sizeof / offsetof of the new structs as a C compiler sees include/polyhead.h"""
-    cc = shutil.which("cc") or shutil.which("gcc") or BLD._hipcc()
-    src = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "polyhead.h"
-#define O(T, f) printf(#T "." #f " %zu\n", offsetof(T, f))
-int main(void) {
-    printf("ph_decode_cfg %zu\nph_decode_io %zu\nph_decode_geometry %zu\n", sizeof(ph_decode_cfg), sizeof(ph_decode_io), sizeof(ph_decode_geometry));
-    O(ph_decode_cfg, B); O(ph_decode_cfg, F); O(ph_decode_cfg, mode); O(ph_decode_cfg, out_dtype); O(ph_decode_cfg, frame_invariant);
-    O(ph_decode_cfg, query_full_split); O(ph_decode_cfg, shares_gpu); O(ph_decode_cfg, poolx); O(ph_decode_cfg, fused_up);
-    O(ph_decode_cfg, nsplit); O(ph_decode_cfg, nsplit_px); O(ph_decode_cfg, up2_wgs);
-    O(ph_decode_io, feat_format); O(ph_decode_io, m0_dtype); O(ph_decode_io, x); O(ph_decode_io, depth_feats); O(ph_decode_io, k0);
-    O(ph_decode_io, q0); O(ph_decode_io, m0); O(ph_decode_io, bits); O(ph_decode_io, obj); O(ph_decode_io, dobj); O(ph_decode_io, cls);
-    O(ph_decode_io, mask); O(ph_decode_io, mask_up); O(ph_decode_io, depth_up); O(ph_decode_io, depth);
-    O(ph_decode_geometry, nsplit); O(ph_decode_geometry, up2_workgroups); O(ph_decode_geometry, feat_planes);
-    return 0;
-}
-'''
-    import tempfile
-    with tempfile.TemporaryDirectory() as d:
-        with open(os.path.join(d, "t.c"), "w") as f:
-            f.write(src)
-        exe = os.path.join(d, "t")
-        lang = [] if os.path.basename(cc) in ("cc", "gcc") else ["-x", "c++"]
-        subprocess.run([cc] + lang + ["-I", os.path.join(BLD.HERE, "..", "include"), os.path.join(d, "t.c"), "-o", exe], check=True,
-                       capture_output=True, timeout=300)
-        out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=60).stdout
-    return {k: int(v) for k, v in (line.split() for line in out.strip().splitlines())}
-
-
-def test_struct_sizes_and_offsets_match_ctypes():
-    c = _c_layout()
-    assert c["ph_decode_cfg"] == C.sizeof(_lib.DecodeCfg)
-    assert c["ph_decode_io"] == C.sizeof(_lib.DecodeIO)
-    assert c["ph_decode_geometry"] == C.sizeof(_lib.DecodeGeometry)
-    for key, off in c.items():
-        if "." not in key:
-            continue
-        struct, field = key.split(".")
-        cls = {"ph_decode_cfg": _lib.DecodeCfg, "ph_decode_io": _lib.DecodeIO, "ph_decode_geometry": _lib.DecodeGeometry}[struct]
-        assert getattr(cls, field).offset == off, key
 
 
 def test_param_table_is_the_stage_state_dict():
@@ -300,25 +243,21 @@ def test_pack_layout_is_pack_py_layout(mode):
     assert lib.ph_decode_pack_bytes(C.byref(cfg)) == off.value + _al(wf.numel() * 4)
 
 
-def _msg():
-    return _lib_loaded().ph_last_error_string().decode()
-
-
 def test_errors_are_returned_before_anything_is_launched():
     lib = _lib_loaded()
     base = dict(B=1, N=111, H=128, W=256, S=3, L=19, F=2048, mode=_lib.PH_MODE["fp16"], out_dtype=_lib.PH_OUT_F16, up2_wgs=384)
     # geometry the query / pooling kernels refuse
     cfg = _lib.DecodeCfg(**dict(base, N=300))
-    assert lib.ph_decode_workspace_bytes(C.byref(cfg)) == 0 and "at most 256 queries" in _msg()
+    assert lib.ph_decode_workspace_bytes(C.byref(cfg)) == 0 and "at most 256 queries" in Hh.last_error()
     assert _create(cfg, 3)[0] == -2
     cfg = _lib.DecodeCfg(**dict(base, F=1000))
-    assert _create(cfg, 3)[0] == -1 and "multiple of 256" in _msg()
+    assert _create(cfg, 3)[0] == -1 and "multiple of 256" in Hh.last_error()
     # a fused form asked for where its kernel cannot run: PH_EUNSUPPORTED (the Python plan would fall back; the native one says so)
     cfg = _lib.DecodeCfg(**dict(base, W=200, fused_up=_lib.PH_KNOB_ON))
-    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_up2" in _msg()
+    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_up2" in Hh.last_error()
     assert lib.ph_dynconv_up2_supported(111, 128, 200, _lib.PH_PREC_F16, _lib.PH_OUT_F16) == 0
     cfg = _lib.DecodeCfg(**dict(base, N=200, poolx=_lib.PH_KNOB_ON))
-    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_poolx" in _msg()
+    assert _create(cfg, 3)[0] == -2 and "ph_dynconv_poolx" in Hh.last_error()
     assert lib.ph_dynconv_poolx_supported(200, _lib.PH_PREC_F16) == 0
     cfg = _lib.DecodeCfg(**dict(base, S=1, poolx=_lib.PH_KNOB_ON))
     assert _create(cfg, 1)[0] == -2
@@ -330,7 +269,7 @@ def test_errors_are_returned_before_anything_is_launched():
     need = lib.ph_decode_workspace_bytes(C.byref(cfg))
     h = C.c_void_p()
     rc = lib.ph_decode_create(C.byref(cfg), (C.c_void_p * 3)(*([FAKE_PTR] * 3)), C.c_void_p(FAKE_PTR), need - 256, C.byref(h))
-    assert rc == -4 and "workspace too small" in _msg() and not h.value
+    assert rc == -4 and "workspace too small" in Hh.last_error() and not h.value
     # run-time arguments: in a child process that sees no GPU (_RUN_CHECKS), so that a validation that ever stopped returning
     # before the first launch fails on the host instead of launching a kernel on the fake addresses
     env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
@@ -403,32 +342,3 @@ def test_train_losses_refuses_more_rank_rows_than_it_keeps():
     r = subprocess.run([sys.executable, "-c", _LOSS_ARG_CHECKS], cwd=os.path.dirname(BLD.HERE), env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0 and "loss checks ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
-
-
-def _elf_needed(path):
-    """DT_NEEDED entries of an ELF64 little-endian file (the dynamic section and its string table)"""
-    import struct
-    with open(path, "rb") as f:
-        d = f.read()
-    assert d[:4] == b"\x7fELF" and d[4] == 2 and d[5] == 1
-    shoff, = struct.unpack_from("<Q", d, 0x28)
-    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
-    sec = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
-    out = []
-    for name, typ, flags, addr, off, size, link, info, align, entsize in sec:
-        if typ != 6:                                     # SHT_DYNAMIC
-            continue
-        stroff = sec[link][4]
-        for o in range(off, off + size, 16):
-            tag, val = struct.unpack_from("<qQ", d, o)
-            if tag == 1:                                 # DT_NEEDED
-                out.append(d[stroff + val:d.index(b"\0", stroff + val)].decode())
-    return out
-
-
-def test_example_program_links_no_python():
-    """the C++ caller is built next to the library and depends on libpolyhead.so and the HIP runtime only"""
-    assert os.path.exists(BLD.EXAMPLE), "built by python -m polyphonicformer_amd.build"
-    needed = _elf_needed(BLD.EXAMPLE)
-    assert "libpolyhead.so" in needed and any(n.startswith("libamdhip64") for n in needed)
-    assert not any("python" in n or "torch" in n or "c10" in n for n in needed), needed

@@ -1,7 +1,7 @@
 """CPU: the host side of the launch-only panoptic merge (include/polyhead.h ph_panoptic_accept / ph_panoptic_merge).
   * `panoptic.segments_from_records` rebuilds `accept_loop`'s segments_info from a record row, `==` on the list of dicts;
   * where `torch.argsort(-scores, stable=True)` puts NaN and signed zeros is pinned (the device ranks the same way);
-  * the new symbols are exported, the size query refuses a bad size and `ph_panoptic_merge` a small workspace, before
+  * the size query refuses a bad size and `ph_panoptic_merge` a small workspace, before
     anything is launched (in a child process that sees no GPU, on fake addresses).
 `accept_cases` are also the inputs of the device accept step's test (tests/test_gpu_batch_merge.py)."""
 import ctypes as C
@@ -13,13 +13,12 @@ import sys
 import numpy as np
 import torch
 
+import helpers as Hh
 from polyphonicformer_amd import _lib, panoptic as Pn
 from polyphonicformer_amd import build as BLD
 
 NT = 8                       # thing classes of the shipped config
 SCORE_THR, OVERLAP_THR = 0.3, 0.6
-NEW_SYMBOLS = ["ph_panoptic_accept", "ph_panoptic_activate_batch", "ph_panoptic_argmax_batch", "ph_panoptic_paste_batch",
-               "ph_panoptic_merge_workspace_bytes", "ph_panoptic_merge"]
 
 
 def _rows(*rows):
@@ -131,17 +130,6 @@ def test_nan_and_signed_zero_order_of_the_stable_descending_sort():
     assert got == info
 
 
-def test_new_symbols_are_exported():
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert hasattr(lib, name), name
-        assert name in _lib.SIGNATURES, name
-
-
-def _msg():
-    return _lib.load().ph_last_error_string().decode()
-
-
 def test_workspace_query():
     lib = _lib.load()
     geom = (C.c_int32 * 8)(256, 512, 1024, 2048, 1024, 2048, 1024, 2048)
@@ -149,13 +137,13 @@ def test_workspace_query():
     B, K, hw, npx = 4, 111, 256 * 512, 1024 * 2048
     want = al(B * 5 * K * 4) + 2 * al(B * K * hw * 4) + al(B * hw * 4) + al(B * npx * 4) + al(B * K * 4)
     assert lib.ph_panoptic_merge_workspace_bytes(B, K, 256, 512, geom) == want
-    assert lib.ph_panoptic_merge_workspace_bytes(0, K, 256, 512, geom) == 0 and "bad size" in _msg()
-    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 0, 512, geom) == 0 and "bad size" in _msg()
-    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 128, 512, geom) == 0 and "bad geometry" in _msg()      # geom[0] != h2
-    assert lib.ph_panoptic_merge_workspace_bytes(B, 5000, 256, 512, geom) == 0 and "4096 candidates" in _msg()
-    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 256, 512, None) == 0 and "geom" in _msg()
+    assert lib.ph_panoptic_merge_workspace_bytes(0, K, 256, 512, geom) == 0 and "bad size" in Hh.last_error()
+    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 0, 512, geom) == 0 and "bad size" in Hh.last_error()
+    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 128, 512, geom) == 0 and "bad geometry" in Hh.last_error()      # geom[0] != h2
+    assert lib.ph_panoptic_merge_workspace_bytes(B, 5000, 256, 512, geom) == 0 and "4096 candidates" in Hh.last_error()
+    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 256, 512, None) == 0 and "geom" in Hh.last_error()
     bad = (C.c_int32 * 8)(256, 512, 1024, 2048, 1025, 2048, 1024, 2048)                                         # img_shape > batch shape
-    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 256, 512, bad) == 0 and "bad geometry" in _msg()
+    assert lib.ph_panoptic_merge_workspace_bytes(B, K, 256, 512, bad) == 0 and "bad geometry" in Hh.last_error()
 
 
 _MERGE_ARG_CHECKS = r"""
