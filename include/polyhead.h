@@ -1324,6 +1324,56 @@ typedef struct {
 size_t ph_dvpq_workspace_bytes(const ph_dvpq_cfg* cfg);            /* 0 on a bad cfg (see ph_last_error_string) */
 int ph_dvpq_frames(const ph_dvpq_cfg* cfg, const ph_dvpq_io* io, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ================================================================================================================================
+ * The training step's Hungarian assignment and target descriptors on the device (ph_assign.hip): what losses.assign_batch (cost
+ * download + scipy.optimize.linear_sum_assignment per image) and losses.build_desc (numpy pointer tables + one upload) do on the
+ * host, as launches that no host code waits for.  With one-to-one matching every SIZE of the descriptor follows from the
+ * ground-truth counts (ph_assign_desc_layout, a pure host function); only the contents depend on the solve.
+ *
+ * ph_assign_solve: cost fp32 [B][Np][ldg] on the device; counts[b * count_stride] = G_b columns of image b (clamped to 0 .. ldg),
+ * read on the device.  One workgroup of one wave per image restates scipy's shortest-augmenting-path solver in fp64 -- operation
+ * order, scan order of `remaining`, swap-remove and tie rule -- so the matching is the installed scipy's, ties included (transposed
+ * iff G_b < Np, as scipy does).  match int32 [B][ldg]: the prediction row of ground-truth column g < G_b, -1 when G_b > Np leaves it
+ * unmatched; entries at or beyond G_b are not written.  status int64 [B]: PH_ASSIGN_OK; PH_ASSIGN_ENONFINITE: a cost entry is NaN
+ * or infinite (scipy raises) -- the image gets the trivial matching, column g <- row g; PH_ASSIGN_ESOLVE: a loop bound was hit
+ * (cannot happen on finite costs), trivial matching likewise.  max(Np, ldg) <= PH_ASSIGN_MAX, PH_EUNSUPPORTED beyond, before any
+ * launch.  Every loop of the kernel is bounded by the matrix size.
+ *
+ * ph_assign_desc: the one call of a head or stage.  Solves (cost != NULL and ldg > 0; with cost == NULL `match` is taken as it is: a
+ * stage that re-uses the previous assignment) and writes into `blob` every section losses.build_desc produces, byte for byte, the
+ * 16-byte section alignment and the one-element placeholders of empty sections included; every byte up to total_bytes is written.
+ *   cfg        B <= PH_ASSIGN_MAX_B images, Np proposals, N rows per image (Np, + n_stuff for the roi form with stuff), L classes,
+ *              roi: KernelUpdateHead's form (label_w, one depth row per row), else KernelHead's (sstart / sit_m / sit_l, one depth
+ *              row per image); pos_weight as build_desc resolves it (<= 0 there: 1)
+ *   G, S       HOST int32 [B]: instances and stuff masks per image (S nullable without has_sem); last_pos HOST int32 [B], nullable:
+ *              1 where the image's last row is a positive (roi form: its depth item gives way to the direct-depth item)
+ *   gt_table   DEVICE int64 [gt_words]: B records of PH_ASSIGN_GT_WORDS words -- G_b | S_b | address of the masks fp32 [G][HW] |
+ *              of the stuff masks [S][HW] | of the valid map [HW] | of the depth map [HW] | word index of the G_b labels | of the
+ *              S_b stuff classes (distinct within an image, n_thing .. n_thing + n_stuff - 1) -- then the labels and classes
+ *   match, status   DEVICE int32 [B][max(ldg, 1)], int64 [B]
+ * PH_EUNSUPPORTED (before any launch) beyond the limits and for the roi form with depth but without stuff rows. */
+#define PH_ASSIGN_MAX 256
+#define PH_ASSIGN_MAX_B 64
+#define PH_ASSIGN_GT_WORDS 8
+enum { PH_ASSIGN_OK = 0, PH_ASSIGN_ENONFINITE = 1, PH_ASSIGN_ESOLVE = 2 };
+typedef struct {
+    int32_t B, Np, N, L, n_thing, n_stuff;
+    int32_t roi, has_sem, has_depth;
+    float pos_weight;
+    int64_t HW;
+} ph_assign_cfg;
+typedef struct {
+    uint64_t tptr, wptr, labels, pos_u8, pos_rows, dstart, dit_t, dit_w, dit_s, label_w, sstart, sit_m, sit_l;   /* byte offsets */
+    uint64_t total_bytes;
+    int64_t P;             /* positives: LossCfg.P and the focal normaliser */
+    int64_t depth_items, seg_items, depth_rows;
+} ph_assign_layout;
+int ph_assign_desc_layout(const ph_assign_cfg* cfg, const int32_t* G, const int32_t* S, const int32_t* last_pos, ph_assign_layout* out);
+int ph_assign_solve(const float* cost, int B, int Np, int ldg, const int32_t* counts, int64_t count_stride, int32_t* match, int64_t* status,
+                    void* stream);
+int ph_assign_desc(const ph_assign_cfg* cfg, const int32_t* G, const int32_t* S, const int32_t* last_pos, const float* cost, int ldg,
+                   const int64_t* gt_table, int64_t gt_words, int32_t* match, int64_t* status, void* blob, size_t blob_bytes, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -172,13 +172,30 @@ class DvpqIO(C.Structure):
                                           "depth_out")]
 
 
+# the training step's assignment + descriptors on the device (polyhead.h ph_assign_cfg .. ph_assign_desc)
+PH_ASSIGN_MAX, PH_ASSIGN_MAX_B, PH_ASSIGN_GT_WORDS = 256, 64, 8
+PH_ASSIGN_OK, PH_ASSIGN_ENONFINITE, PH_ASSIGN_ESOLVE = 0, 1, 2
+PH_EUNSUPPORTED = -2
+ASSIGN_SECTIONS = ("tptr", "wptr", "labels", "pos_u8", "pos_rows", "dstart", "dit_t", "dit_w", "dit_s", "label_w", "sstart", "sit_m", "sit_l")
+
+
+class AssignCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "Np", "N", "L", "n_thing", "n_stuff", "roi", "has_sem", "has_depth")] + \
+        [("pos_weight", C.c_float), ("HW", C.c_int64)]
+
+
+class AssignLayout(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ASSIGN_SECTIONS + ("total_bytes",)] + \
+        [(n, C.c_int64) for n in ("P", "depth_items", "seg_items", "depth_rows")]
+
+
 # C typedef name -> its mirror above: every Structure of this module (tests/test_abi.py compares each layout with the header's)
 STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
            "ph_neck_cfg": NeckCfg, "ph_neck_layout": NeckLayout, "ph_neck_geometry": NeckGeometry, "ph_neck_io": NeckIO,
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
-           "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO}
+           "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout}
 
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -360,6 +377,9 @@ SIGNATURES = {
     "ph_assoc_plan_track": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "ph_dvpq_workspace_bytes": (C.c_size_t, [C.POINTER(DvpqCfg)]),
     "ph_dvpq_frames": (C.c_int, [C.POINTER(DvpqCfg), C.POINTER(DvpqIO), _P, _Z, _P]),
+    "ph_assign_desc_layout": (C.c_int, [C.POINTER(AssignCfg), _P, _P, _P, C.POINTER(AssignLayout)]),
+    "ph_assign_solve": (C.c_int, [_P, _I, _I, _I, _P, _L, _P, _P, _P]),
+    "ph_assign_desc": (C.c_int, [C.POINTER(AssignCfg), _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _Z, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

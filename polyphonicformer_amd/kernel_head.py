@@ -213,7 +213,7 @@ class KernelHead(nn.Module):
         feats = [f if f.dtype == torch.float32 and f.is_contiguous() else f.float().contiguous() for f in feats]
         with torch.enable_grad():
             losses, r = T.rpn_forward_train(self, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                            want_grads=with_grads)
+                                            want_grads=with_grads, device_assign=getattr(self, "device_assign", False))
             k, mask_preds, q = T.rpn_outputs(self, r)
             B, N = k.shape[:2]
             out = (losses, k.reshape(B, N, 256, 1, 1), r["x"], mask_preds, None, r["dfe"], q.reshape(B, N, 256, 1, 1), r["depth_pred"], None)

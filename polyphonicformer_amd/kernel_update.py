@@ -205,7 +205,7 @@ class KernelUpdateIterHead(nn.Module):
             q = depth_proposal.reshape(depth_proposal.shape[0], depth_proposal.shape[1], -1).expand(B, N, -1)
             losses, last = T.roi_forward_train(self, x.float(), depth_feats.float(), k.float(), mask_preds.float(), q.float(),
                                                depth_preds.float(), img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                               want_grads=with_grads)
+                                               want_grads=with_grads, device_assign=getattr(self, "device_assign", False))
             obj, cls, m, smask = last
             obj = obj.reshape(B, N, -1, 1, 1)
         if not self.tracking:

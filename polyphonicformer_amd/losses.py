@@ -204,6 +204,17 @@ def _depth_from_sums(s, loss_weight, w3):
     return loss, coef
 
 
+def _depth_value_from_sums(s, loss_weight, w3):
+    """the value `_depth_from_sums` returns, without the host reading n: the same fp64 operations in the same order, all on the
+    device (0 where no pixel is labelled)"""
+    n = s[0]
+    si = s[1] / n - s[2] / (n * n)
+    sq = torch.sqrt(s[3] / n)
+    ab = s[4] / n
+    loss = (loss_weight / 3.0) * (w3[0] * si + w3[1] * sq + w3[2] * ab)
+    return torch.where(n == 0, torch.zeros_like(loss), loss)
+
+
 class DepthLoss(_Loss):
     """polyphonic/losses/depth_loss.py:36-65: forward(pred logits, target, mask_weight) -> loss_weight * mean(weight * (si, sq_rel, abs_rel))"""
 
@@ -462,9 +473,10 @@ def dense_depth_loss(head, depth_pred, gt_depth, with_grad=False):
     if dp.numel() != gd.numel():
         raise ValueError(f"depth_dense: prediction {tuple(depth_pred.shape)} and gt_depth {tuple(gt_depth.shape)} differ in size")
     w = (gd > 0).float()
-    loss, coef = _depth_from_sums(depth_loss_sums(dp, gd, w, mode), ld.loss_weight, [float(v) for v in ld.weight])
-    if not with_grad:
-        return loss.float()
+    sums = depth_loss_sums(dp, gd, w, mode)
+    if not with_grad:                      # the logged value of a training step: nothing here waits for the device
+        return _depth_value_from_sums(sums, ld.loss_weight, [float(v) for v in ld.weight]).float()
+    loss, coef = _depth_from_sums(sums, ld.loss_weight, [float(v) for v in ld.weight])
     g = torch.empty_like(dp)
     _lib.check(_lib.load().ph_depth_loss_grad(_lib.ptr(dp), _lib.ptr(gd), _lib.ptr(w), dp.numel(), mode, *coef, _lib.ptr(g),
                                               _lib.stream_ptr()), "ph_depth_loss_grad")
@@ -600,18 +612,32 @@ class StepGT:
         self.valid_base = self.valid.data_ptr() + 4 * HW * np.arange(B, dtype=np.int64)
         self.depth_base = None if self.depth is None else self.depth.data_ptr() + 4 * HW * np.arange(B, dtype=np.int64)
         self.B = B
+        self._table = None                  # `device_table`
+        self.status_words = []              # one int64 [B] device tensor per device solve of the step (`assign_desc_device`)
+
+    def device_table(self):
+        """the ground-truth table `ph_assign_desc` reads (include/polyhead.h): per image the counts, the base addresses and where
+        its labels and stuff classes lie, then those.  int64 on the device, built and uploaded on first use, once per step."""
+        if self._table is None:
+            B, W = self.B, _lib.PH_ASSIGN_GT_WORDS
+            tab = np.zeros(B * W + sum(self.G) + sum(len(c) for c in self.sem_cls_h), np.int64)
+            o = B * W
+            for b in range(B):
+                S = len(self.sem_cls_h[b])
+                tab[b * W:(b + 1) * W] = [self.G[b], S, self.mask_base[b], self.sem_base[b], self.valid_base[b],
+                                          0 if self.depth_base is None else self.depth_base[b], o, o + self.G[b]]
+                tab[o:o + self.G[b]] = self.labels_h[b]
+                tab[o + self.G[b]:o + self.G[b] + S] = self.sem_cls_h[b]
+                o += self.G[b] + S
+            self._table = torch.from_numpy(tab).to(self.valid.device, non_blocking=True)
+        return self._table
 
 
-def assign_batch(assigner, pred, cls_pred, gt):
-    """the Hungarian assignment of B images from ONE `ph_match_sums` pass and ONE device -> host copy (funcs/assigner.py:363-542
-    per image).  pred [B, Np, H, W] detached mask logits, cls_pred [B, Np, n_thing] or None.  -> per image (pred indices
-    ascending, matched gt indices) as numpy arrays.  Configurations the batched algebra does not cover (DepthCost with a weight,
-    topk > 1) are refused by the caller."""
-    from .assigner import MatchSums, _hungarian
+def _assign_cost(assigner, pred, cls_pred, gt):
+    """the [B, Np, Gmax] matching cost of B images from ONE `ph_match_sums` pass (funcs/assigner.py:363-542 per image): class,
+    mask and dice terms in this order, torch ops on the device.  Both assignment paths solve exactly this tensor."""
+    from .assigner import MatchSums
     B, Np = pred.shape[:2]
-    out = [(np.zeros(0, np.int64), np.zeros(0, np.int64))] * B
-    if gt.Gmax == 0:
-        return out
     s = MatchSums(pred, gt.pad, gt.valid)
     cost = 0
     a = assigner
@@ -632,6 +658,20 @@ def assign_batch(assigner, pred, cls_pred, gt):
     if a.dice_cost.weight != 0:
         e = a.dice_cost.eps
         cost = cost + (-(2 * s.A) / ((s.Q + e)[:, :, None] + (s.C + e)[:, None, :]) * a.dice_cost.weight)
+    return cost
+
+
+def assign_batch(assigner, pred, cls_pred, gt):
+    """the Hungarian assignment of B images from ONE `ph_match_sums` pass and ONE device -> host copy (funcs/assigner.py:363-542
+    per image).  pred [B, Np, H, W] detached mask logits, cls_pred [B, Np, n_thing] or None.  -> per image (pred indices
+    ascending, matched gt indices) as numpy arrays.  Configurations the batched algebra does not cover (DepthCost with a weight,
+    topk > 1) are refused by the caller."""
+    from .assigner import _hungarian
+    B, Np = pred.shape[:2]
+    out = [(np.zeros(0, np.int64), np.zeros(0, np.int64))] * B
+    if gt.Gmax == 0:
+        return out
+    cost = _assign_cost(assigner, pred, cls_pred, gt)
     cost = cost.detach().cpu().numpy()
     for i in range(B):
         if gt.G[i]:
@@ -739,6 +779,93 @@ def build_desc(head, gt, assigns, num_proposals, cfg, roi):
         sec.update(sstart=np.asarray(s_cnt, np.int32), sit_m=np.asarray(s_m if s_m else [0], np.int64), sit_l=np.asarray(s_l if s_l else [0], np.int32))
     d = LossDesc(gt.valid.device, sec)
     d.B, d.N, d.R, d.P, d.depth_rows, d.roi, d.has_depth = B, N, R, int(len(pos_rows)), depth_rows, roi, gt.depth_base is not None
+    d.gt = gt              # keeps the ground-truth tensors the pointers address alive
+    return d
+
+
+class DeviceDesc:
+    """what `fused_losses` reads of a `LossDesc` -- `ptr`, `n`, B / N / R / P / depth_rows / roi / has_depth -- with the tables
+    written by `ph_assign_desc`: the counts are the host's (they follow from the ground-truth counts), the contents never leave
+    the device.  `match` int32 [B, ldg] (prediction row per ground-truth column, -1 unmatched), `status` int64 [B]."""
+
+    def launch(self, cost):
+        """`ph_assign_desc` into this descriptor's blob: solve `cost` [B, Np, ldg] (None: keep `match`), write the tables.
+        Launches only.  -> the call's return code"""
+        ip = lambda a: a.ctypes.data_as(C.c_void_p)
+        G, S, last = self.counts
+        return _lib.load().ph_assign_desc(C.byref(self.cfg), ip(G), ip(S), ip(last), _lib.ptr(cost), self.ldg, _lib.ptr(self.table),
+                                          self.table.numel(), _lib.ptr(self.match), _lib.ptr(self.status), _lib.ptr(self.blob),
+                                          self.blob.numel(), _lib.stream_ptr())
+
+
+def _assign_counts(gt, head, roi):
+    """host arrays of `ph_assign_desc` (G, S, last_pos) or None where the ground truth is outside the kernel's contract: stuff
+    classes of an image must be distinct, and for the roi form lie in n_thing .. n_thing + n_stuff - 1"""
+    key = ("_counts", bool(roi), head.num_thing_classes, head.num_stuff_classes)
+    c = gt.__dict__.get(key, False)
+    if c is False:
+        nt, ns = head.num_thing_classes, head.num_stuff_classes
+        ok = True
+        last = np.zeros(gt.B, np.int32)
+        for b, sc in enumerate(gt.sem_cls_h):
+            if len(np.unique(sc)) != len(sc) or (roi and len(sc) and (sc.min() < nt or sc.max() >= nt + ns)):
+                ok = False
+            last[b] = int(roi and gt.has_sem and ns > 0 and (nt + ns - 1) in sc)
+        c = (np.asarray(gt.G, np.int32), np.asarray([len(sc) for sc in gt.sem_cls_h], np.int32), last) if ok else None
+        gt.__dict__[key] = c
+    return c
+
+
+def assign_desc_device(head, gt, assigner, pred, cls_pred, num_proposals, cfg, roi, prev=None):
+    """`assign_batch` + `build_desc` without the host: the cost tensor stays where `_assign_cost` forms it, `ph_assign_desc` solves
+    it per image as scipy would and writes the descriptor blob (csrc/ph_assign.hip).  Launches only.  `prev`: a DeviceDesc whose
+    assignment is used again (a stage beyond `assign_stages`).  Returns a DeviceDesc, or None where the kernels' limits do not
+    hold (more than 256 proposals or instances, more than 64 images, ...): the caller takes the host path."""
+    lib = _lib.load()
+    B, HW = gt.B, gt.HW
+    L, ns, nt = head.num_classes, head.num_stuff_classes, head.num_thing_classes
+    Np = num_proposals
+    N = Np + ns if (roi and gt.has_sem) else Np
+    has_depth = gt.depth_base is not None
+    counts = _assign_counts(gt, head, roi)
+    if (counts is None or B > _lib.PH_ASSIGN_MAX_B or max(Np, gt.Gmax, ns) > _lib.PH_ASSIGN_MAX or (roi and has_depth and N == Np)
+            or pred.shape[1] != Np):
+        return None
+    G, S, last = counts
+    dev = gt.valid.device
+    c = _lib.AssignCfg(B=B, Np=Np, N=N, L=L, n_thing=nt, n_stuff=ns, roi=int(roi), has_sem=int(gt.has_sem), has_depth=int(has_depth),
+                       pos_weight=1.0 if cfg.pos_weight <= 0 else float(cfg.pos_weight), HW=HW)
+    lay = _lib.AssignLayout()
+    ip = lambda a: a.ctypes.data_as(C.c_void_p)
+    _lib.check(lib.ph_assign_desc_layout(C.byref(c), ip(G), ip(S), ip(last), C.byref(lay)), "ph_assign_desc_layout")
+    cost = None
+    if prev is not None:
+        match, status, ldg = prev.match, prev.status, prev.ldg
+    else:
+        ldg = gt.Gmax
+        if ldg:
+            cost = _assign_cost(assigner, pred, cls_pred, gt)
+            if not torch.is_tensor(cost):               # every cost weight is zero: nothing to solve on either path
+                return None
+            cost = cost.detach().float().contiguous()
+            assert cost.shape == (B, Np, ldg)
+        match = torch.empty((B, max(ldg, 1)), dtype=torch.int32, device=dev)
+        status = torch.empty((B,), dtype=torch.int64, device=dev)
+    d = DeviceDesc()
+    d.cfg, d.counts, d.table = c, counts, gt.device_table()
+    d.blob, d.match, d.status, d.ldg = torch.empty((lay.total_bytes,), dtype=torch.uint8, device=dev), match, status, ldg
+    rc = d.launch(cost)
+    if rc == _lib.PH_EUNSUPPORTED:
+        return None
+    _lib.check(rc, "ph_assign_desc")
+    if prev is None:
+        gt.status_words.append(status)
+    base = d.blob.data_ptr()
+    R, P, nd, nsit, depth_rows = B * N, int(lay.P), int(lay.depth_items), int(lay.seg_items), int(lay.depth_rows)
+    d.n = dict(tptr=R, wptr=R, labels=R, pos_u8=R, pos_rows=max(P, 1), dstart=depth_rows + 1, dit_t=max(nd, 1), dit_w=max(nd, 1), dit_s=max(nd, 1))
+    d.n.update(dict(label_w=R * L) if roi else dict(sstart=B + 1, sit_m=max(nsit, 1), sit_l=max(nsit, 1)))
+    d.ptr = {k: C.c_void_p(base + getattr(lay, k)) for k in d.n}
+    d.B, d.N, d.R, d.P, d.depth_rows, d.roi, d.has_depth = B, N, R, P, depth_rows, roi, has_depth
     d.gt = gt              # keeps the ground-truth tensors the pointers address alive
     return d
 

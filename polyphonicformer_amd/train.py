@@ -16,7 +16,7 @@ libpolyhead kernel, forward and backward; torch is the autograd bookkeeping betw
     as in the inference path (pooling and the dynamic convolution are linear in it), gradients included;
   * `_Upsample2x`; `_Objective`: a head's or stage's losses with d(losses)/d(predictions) from the loss kernels
     (csrc/ph_loss.hip);
-  * the discrete parts (Hungarian assignment on the host, targets) in between.
+  * the discrete parts (Hungarian assignment -- scipy on the host, or `device_assign`: csrc/ph_assign.hip --, targets) in between.
 
 The result is checked against the reference's own forward + autograd backward (tests/golden/train_step.npz:
 every loss, the objective and the gradient of every parameter and of the three input maps)."""
@@ -625,12 +625,14 @@ def _step_gt(cache, hard, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
     return cache[hard]
 
 
-def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, want_grads=False, gt_cache=None):
+def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, want_grads=False, gt_cache=None,
+                      device_assign=False):
     """KernelHead.forward_train, kernel_head.py:349-454, on the three post-neck maps (gradients flow into `feats` when they
     require them).  Returns (losses, r): `losses` = the reference's dict with the 'loss' entries attached to the graph
     (`_attach`), `depth_dense` logged only (base.py:198 leaves it out of the objective); r = the differentiable training-
     mode decode (no stuff rows).  want_grads: losses['_grads'] = d(sum of the 'loss' entries) / d(scaled mask, seg and
-    direct depth predictions)."""
+    direct depth predictions).  device_assign: the assignment and the target tables on the device (`losses.assign_desc_device`), no
+    host round trip; the host path where the kernels' limits do not hold."""
     check_rpn_topology(h)
     if h.assigner is None:
         raise ValueError("forward_train needs train_cfg (assigner / sampler)")
@@ -644,8 +646,10 @@ def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_s
     if _fast_assign_ok(h.assigner, h.sampler):
         # round 5: batched assignment (one pixel pass + one D2H for all images), targets as pointer tables, ONE loss call
         gt = _step_gt(gt_cache, bool(h.hard_target), gt_raw, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
-        assigns = Lo.assign_batch(h.assigner, smask.detach(), None, gt)
-        desc = Lo.build_desc(h, gt, assigns, h.num_proposals, h.train_cfg, roi=False)
+        desc = Lo.assign_desc_device(h, gt, h.assigner, smask.detach(), None, h.num_proposals, h.train_cfg, roi=False) if device_assign else None
+        if desc is None:
+            assigns = Lo.assign_batch(h.assigner, smask.detach(), None, gt)
+            desc = Lo.build_desc(h, gt, assigns, h.num_proposals, h.train_cfg, roi=False)
         kept = {}
 
         def fn(mp, sp, dp):
@@ -703,7 +707,7 @@ def rpn_outputs(h, r):
 
 
 def roi_forward_train(ih, x, dfe, k, mask_preds, q, depth_pred, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                      want_grads=False, gt_cache=None):
+                      want_grads=False, gt_cache=None, device_assign=False):
     """KernelUpdateIterHead.forward_train, kernel_update.py:159-280.  x, dfe [B, C, H, W]; k / q [B, N, C] kernels and depth
     kernels; mask_preds [B, N, H, W]; depth_pred [B, 1, H, W].  Every stage: forward in training form, the Hungarian
     assignment on the previous stage's detached predictions, pseudo sampling, targets, the stage's losses as one autograd
@@ -721,7 +725,7 @@ def roi_forward_train(ih, x, dfe, k, mask_preds, q, depth_pred, img_metas, gt_ma
     prev_mask = scale(mask_preds.detach()).detach()                                           # :179-191
     if all(_fast_assign_ok(a, sm) for a, sm in zip(ih.mask_assigner, ih.mask_sampler)):
         return _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                       want_grads, gt_cache)
+                                       want_grads, gt_cache, device_assign)
     prev_depth = scale(depth_pred.detach().expand(-1, N, -1, -1).contiguous()).detach()
     prev_cls = [None] * B                                                                      # :193-196
     if ih.hard_target:
@@ -772,16 +776,17 @@ def roi_forward_train(ih, x, dfe, k, mask_preds, q, depth_pred, img_metas, gt_ma
 
 
 def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, want_grads,
-                            gt_cache):
+                            gt_cache, device_assign=False):
     """the stage loop of `roi_forward_train` on the batched / descriptor path (round 5): per stage ONE `_Stage` node, two
     upsamples, one batched assignment (`ph_match_sums` over all images + one D2H + the host Hungarian solves), one pointer-table
     upload and ONE loss call (`ph_train_losses`).  No sampler gathers, no materialised targets: every target row is a row of the
     step's ground truth (`losses.StepGT`).  The previous stage's depth predictions only feed the DepthCost, whose weight is 0
-    on this path, so they are not formed."""
+    on this path, so they are not formed.  device_assign: assignment and tables by `ph_assign_desc` on the device instead (no D2H,
+    no host solve, no upload); a stage the kernels do not cover takes the host path."""
     B = k.shape[0]
     Np, nt = ih.num_proposals, ih.num_thing_classes
     gt = _step_gt(gt_cache, bool(ih.hard_target), gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
-    total, m, values, grads, assigns, prev_cls = 0.0, mask_preds, {}, [], None, None
+    total, m, values, grads, assigns, prev_cls, ddesc = 0.0, mask_preds, {}, [], None, None, None
     cls = smask = None
     for s in range(ih.num_stages):
         head = ih.mask_head[s]
@@ -790,8 +795,12 @@ def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_m
         smask, sdepth = scale(m), scale(depth)                                                 # training: every stage (:131)
         if s < ih.assign_stages:
             c = None if prev_cls is None else prev_cls[:, :Np, :nt]
-            assigns = Lo.assign_batch(ih.mask_assigner[s], prev_mask[:, :Np], c, gt)           # :231-251
-        desc = Lo.build_desc(head, gt, assigns, Np, ih.train_cfg[s], roi=True)
+            ddesc = Lo.assign_desc_device(head, gt, ih.mask_assigner[s], prev_mask[:, :Np], c, Np, ih.train_cfg[s], roi=True) if device_assign else None
+            if ddesc is None:
+                assigns = Lo.assign_batch(ih.mask_assigner[s], prev_mask[:, :Np], c, gt)       # :231-251
+        elif ddesc is not None:                                                                # the last assignment again, other weights
+            ddesc = Lo.assign_desc_device(head, gt, None, prev_mask[:, :Np], None, Np, ih.train_cfg[s], roi=True, prev=ddesc)
+        desc = ddesc if ddesc is not None else Lo.build_desc(head, gt, assigns, Np, ih.train_cfg[s], roi=True)
         kept = {}
 
         def fn(cs, mp, dp, head=head, desc=desc, kept=kept):
@@ -823,8 +832,12 @@ class TrainStep:
     class adds the bucketed gradient all-reduce.  Use as a context manager (or call `close()`) to take the gradient hooks
     off the parameters again."""
 
-    def __init__(self, rpn_head, roi_head, bucket_bytes=32 << 20, group=None):
+    def __init__(self, rpn_head, roi_head, bucket_bytes=32 << 20, group=None, device_assign=False):
         self.rpn, self.roi = rpn_head, roi_head
+        # the Hungarian assignments and target tables on the device (csrc/ph_assign.hip): the step's forward waits for the host nowhere
+        # after its ground truth is built; off by default
+        self.device_assign = bool(device_assign)
+        self._status = []
         if rpn_head.assigner is None or not roi_head.mask_assigner:
             raise ValueError("TrainStep needs heads built with train_cfg (assigner / sampler)")
         check_rpn_topology(rpn_head)
@@ -849,6 +862,14 @@ class TrainStep:
     def parameters(self):
         return [p for n, p in _lib.named_params(self.rpn).items() if not n.startswith("localization_fpn.")] + list(_lib.named_params(self.roi).values())
 
+    def assign_status(self):
+        """the status words of the last step's device solves, downloaded now (a synchronising copy, when the caller chooses to):
+        int64 [solves, B], 0 = solved; _lib.PH_ASSIGN_ENONFINITE: the image's costs were not finite and it got the trivial matching.
+        Empty without `device_assign` or where every solve took the host path."""
+        if not self._status:
+            return torch.zeros((0, 0), dtype=torch.int64)
+        return torch.stack(self._status).cpu()
+
     def forward_backward(self, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, backward=True):
         feats = [f.detach().float().contiguous().requires_grad_(True) for f in feats]
         for f in feats:
@@ -857,10 +878,11 @@ class TrainStep:
         with torch.enable_grad(), Lo.reduce_group(self.group):
             gt_cache = {}                                   # the step's ground truth (losses.StepGT), shared by the two heads
             rpn_losses, r = rpn_forward_train(self.rpn, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                              gt_cache=gt_cache)
+                                              gt_cache=gt_cache, device_assign=self.device_assign)
             k, mask_preds, q = rpn_outputs(self.rpn, r)
             losses, _ = roi_forward_train(self.roi, r["x"], r["dfe"], k, mask_preds, q, r["depth_pred"], img_metas, gt_masks, gt_labels,
-                                          gt_sem_seg, gt_sem_cls, gt_depth, gt_cache=gt_cache)
+                                          gt_sem_seg, gt_sem_cls, gt_depth, gt_cache=gt_cache, device_assign=self.device_assign)
+            self._status = [w for g in gt_cache.values() for w in g.status_words]
             losses.update(rpn_losses)                       # polyphonic_former.py:126
             total = parse_losses(losses)
             if backward:
