@@ -9,6 +9,7 @@ reference's, and the integer ids are pinned to the reference class's own output 
 With frames sharded over GPUs (`dist.shard_frames`) every rank all-gathers the per-frame records
 (`dist.allgather_track_records`) and replays `match` in frame order; integer track ids are then identical to the
 single-process run (`replay_tracking`, tests/test_tracker.py and tests/test_dist_gloo.py)."""
+import dataclasses
 import os
 
 import numpy as np
@@ -686,10 +687,7 @@ class VideoFramePipeline:
             if r is None:
                 runners.clear()                      # one geometry at a time: a runner owns GBs of plan buffers
                 r = runners[key] = VideoStreamRunner(self, dict(m), graph=True, pipelined=False)
-            r._check_weights()
-            r._start_heads(0, [x])
-            r._finish(0)
-            return r._collect(r._downloads.pop(0))
+            return r.run_one(x)
         _, _, (panoptic_seg, segments_info), _, depth_final = self.heads(x, img_metas, rescale)[0]
         return self.assoc.step(x, panoptic_seg, segments_info, depth_final, records_only=records_only)
 
@@ -728,34 +726,65 @@ def _h2d(values, dtype, dev):
     return torch.tensor(values, dtype=dtype).pin_memory().to(dev, non_blocking=True)
 
 
+@dataclasses.dataclass
+class _Capture:
+    """one heads launch form of a slot, keyed (frames per launch, borrowed) in `_Slot.captures`"""
+    x: tuple                             # static inputs: the FPN levels of the launch's frames, [B, C, h, w] per level
+    graph: object = None                 # the HIP graph neck -> KernelHead -> decode -> upsample (-> merge selection); None: eager
+    outs: tuple = None                   # (cls, mask_up, depth_up, depth_init) the graph writes
+    dm: object = None                    # panoptic.DeviceMerge (device_select)
+    nplan: object = None                 # borrowed: the neck plan the graph replays behind the ingest
+    plans: tuple = ()                    # the plans whose device buffers the graph replays, kept alive
+    frames: list = None                  # borrowed: the caller's tensors of the current launch (RoIAlign reads them)
+
+
+@dataclasses.dataclass
+class _Slot:
+    """a pair of head modules with its own plans, buffers and stream: one heads launch at a time"""
+    rpn: object
+    roi: object
+    stream: object
+    done: object = None                  # event behind the current launch
+    captures: dict = dataclasses.field(default_factory=dict)
+    cur: _Capture = None                 # the capture of the current launch
+    no_borrow: bool = False              # this slot's neck plan cannot take frames one by one: it copies for good
+
+
 class VideoStreamRunner:
     """Throughput form of the reference's per-frame video loop (polyphonic/apis/video_inference.py:8-31 ->
     PolyphonicVideo.simple_test, polyphonic_former_video.py:327-405) for ONE stream of equally sized frames: the same kernels,
     the same tracker calls and therefore the same results as `VideoFramePipeline.simple_test`, issued so that the GPU box's
-    host is not the bottleneck (round 4; the module-API loop spends ~80 % of a 5 ms frame on the host):
+    host is not the bottleneck (the module-API loop spends ~80 % of a 5 ms frame on the host):
 
-      * neck -> KernelHead -> 3-stage decode -> x2 upsample of depth_pred are ONE HIP graph per slot, captured on first use from
-        the unmodified module calls (`rpn_head.simple_test_rpn`, `roi_head._decode`) on static copies of the FPN levels and
-        replayed for every later frame (~70 kernel launches -> one graph launch);
-      * TWO slots (the second one a deep copy of the two head modules with its own plans and buffers): the heads of frame t run
-        on their slot's stream while the host walks frame t - 1 through merge -> boxes -> RoIAlign -> track head -> tracker,
-        whose four small D2H reads (class scores, area histograms, boxes, affinity matrix) synchronise the MAIN stream only.
-        The tracker sees the frames in order; heads are frame-independent (SURVEY 8e);
+      * neck -> KernelHead -> 3-stage decode -> x2 upsample of depth_pred are ONE HIP graph per slot and launch size, captured
+        on first use from the unmodified module calls (`rpn_head.simple_test_rpn`, `roi_head._decode`) and replayed for every
+        later launch (~70 kernel launches -> one graph launch);
       * the panoptic id map never visits the host: the merge's result stays on the device (`panoptic.get_panoptic_device`)
         where the association step consumes it;
       * what the reference returns as numpy -- the uint8 semantic map, the float64 track-id map, the fp32 depth map (26 MB per
         1024x2048 frame) -- is copied to pinned host memory on a side stream under the following frames.
 
-    `push(x)` therefore returns the result of frame t - 2 (None for the first two frames); `flush()` returns the list of the
-    results still in flight, oldest first.  `pipelined=False`: one slot, results one frame late (round 4's first form).
-    Weights are packed at capture time; every push compares the parameters' version counters with the capture-time ones and
-    captures again (all slots) when they changed (`_check_weights`, round 5)."""
+    ONE launch queue drives the TWO slots (the second one a deep copy of the head modules; one slot with `pipelined=False`) for
+    every front end.  A chunk of frames is SUBMITTED: its heads start at once on a free slot's stream when nothing waits in front of
+    it, else it waits -- launch order is frame order.  The oldest launch is CONSUMED frame by frame on the caller's stream (merge ->
+    association; its small D2H reads synchronise the caller's stream only), which frees its slot for the next waiting chunk.  Every
+    front end submits the next launch BEFORE it consumes the previous one, so the heads run under the host's walk through the frames
+    in front of them:
+
+      * `push(x)` / `flush()`: result maps, one frame per launch, returned two calls late (one with `pipelined=False`); with
+        `frames_per_launch=k` the pushed frames are buffered and go k per launch, results up to 2 k frames late;
+      * `records_begin(frames)` / `records_end()` / `records(frames)`: the sharded mode's track records of a clip in `clip_batch`
+        frames per launch; clips queue, `records_end` returns the oldest;
+      * `push_record(x)` / `flush_record()`: the same records for a stream of one-frame clips, one call late;
+      * `run_one(x)`: the frame's own result maps, at once.
+
+    A runner delivers maps OR records until it is drained; starting the other kind in between raises `PolyheadError`.  Weights are
+    packed at capture time: every submit compares the parameters' version counters with the capture-time ones, and a chunk
+    submitted after a change starts only when every earlier launch has been consumed (with the weights it started with) -- then
+    the slots are dropped and it captures again from the current modules."""
 
     def __init__(self, pipe, img_meta, graph=True, pipelined=True, device_select=None, frames_per_launch=1):
-        """`frames_per_launch` (round 6, `push` / `flush`): k > 1 buffers k pushed frames and sends them through the heads in ONE launch
-        (the batch-invariant heads give every frame the bits of its own one-frame launch; fp16 / bf16 grades, see `clip_batch`), two
-        launches in flight on the two slots; results come back in frame order, up to 2 k frames late"""
-        import os
+        """`frames_per_launch`: k > 1 makes `push` buffer k frames per heads launch where the heads are batch invariant (`_launch_size`)"""
         self.pipe, self.metas, self.use_graph, self.pipelined = pipe, [img_meta], graph, pipelined
         self.frames_per_launch = max(1, int(frames_per_launch))
         # the merge's candidate selection + activation + argmax queued behind the decode on the heads' stream (panoptic.DeviceMerge),
@@ -764,18 +793,17 @@ class VideoStreamRunner:
         self.reset()
 
     def reset(self):
-        self._slots = []                 # per slot: dict(rpn, roi, g = {frames per launch: dict(x, graph, outs)}, cur, stream, done)
+        self._slots = []
+        self._versions = None            # the parameters' version counters the slots' captures were made at
+        self._free = list(range(2 if self.pipelined else 1))     # slot indices without a launch
+        self._launches = []              # in flight, oldest first: (slot index, frames)
+        self._waiting = []               # chunks without a slot yet, oldest first: (frames, borrowed, weight versions at submit)
+        self._mode = None                # "maps" / "records": what the launches in flight are consumed into
+        self._clips = []                 # records: launches per queued clip, oldest first
+        self._buf = []                   # batched push: frames waiting for their launch
+        self._downloads = []             # maps: [(event, host tensors, device sources)] oldest first
         self._copy_stream = None
-        self._inflight = None            # frame whose heads are running: (slot index)
-        self._downloads = []             # [(event, host tensors, device sources)] oldest first
-        self._n = 0
-        self._versions = None
-        self._buf = []                   # frames_per_launch > 1: pushed frames waiting for their launch
-        self._inflight_b = None          # ... and the launch whose frames are still to be finished: (slot, frames)
-        self._nb = 0
         self._last_done = None
-        self._rq = []                    # clips queued by records_begin: dict(chunks, next chunk to start, slots of the started ones)
-        self._free = []
 
     def khead_timeouts(self):
         """workgroup time-outs of the one-pass KernelHead kernel over every plan this runner's slots and graphs hold (sticky counters;
@@ -783,9 +811,9 @@ class VideoStreamRunner:
         GPU -- and then those calls' results came from the predicated two-pass kernels: equal to ~1e-6, not bit for bit."""
         seen, n = set(), 0
         for sl in self._slots:
-            plans = list(getattr(sl["rpn"], "_plans", {}).values())
-            for st in sl["g"].values():
-                for d in st.get("plans") or []:
+            plans = list(getattr(sl.rpn, "_plans", {}).values())
+            for cap in sl.captures.values():
+                for d in cap.plans:
                     plans += list(d.values())
             for p in plans:
                 if id(p) not in seen and hasattr(p, "timeouts"):
@@ -797,26 +825,6 @@ class VideoStreamRunner:
         from . import _lib
         return _lib.param_versions(self.pipe.rpn_head) + _lib.param_versions(self.pipe.roi_head)
 
-    def _check_weights(self):
-        """the graphs replay weight PACKS made at capture time and the second slot is a deep copy of the head
-        modules -- after load_state_dict / an optimizer step / a replaced sub-module they would silently keep the old weights.
-        The parameters' version counters are compared with the capture-time ones; on a change the frame in flight is finished
-        (with the weights it started with), the slots are dropped and the next frame captures again from the current modules."""
-        v = self._weight_versions()
-        if self._versions is None:
-            self._versions = v
-        elif v != self._versions:
-            if self._inflight is not None:
-                self._finish(self._inflight)
-                self._inflight = None
-            if getattr(self, "_inflight_b", None) is not None:
-                i, n = self._inflight_b
-                for b in range(n):
-                    self._finish(i, b)
-                self._inflight_b = None
-            self._slots = []
-            self._versions = v
-
     # -- slots ---------------------------------------------------------------------------------------------------
     def _slot(self, i):
         while len(self._slots) <= i:
@@ -826,7 +834,7 @@ class VideoStreamRunner:
                 rpn, roi = self._clone_heads()
             # the slots' streams carry the heads' graphs (milliseconds of HBM-bound launches); the merges / records of the frames in
             # front of them are a dozen small kernels on the caller's stream with the host waiting for each: PH_VIDEO_SLOT_PRIO=low
-            # puts the heads one priority level below them (A/B: see DESIGN 7b "Round 6")
+            # puts the heads one priority level below them
             prio = 0
             if os.environ.get("PH_VIDEO_SLOT_PRIO") == "low":
                 try:
@@ -834,7 +842,7 @@ class VideoStreamRunner:
                     prio = max(lo, hi)
                 except Exception:
                     prio = 0
-            self._slots.append(dict(rpn=rpn, roi=roi, g={}, cur=None, stream=torch.cuda.Stream(priority=prio), done=None))
+            self._slots.append(_Slot(rpn, roi, torch.cuda.Stream(priority=prio)))
         return self._slots[i]
 
     def _clone_heads(self):
@@ -855,149 +863,194 @@ class VideoStreamRunner:
     def _heads_device(self, sl, x):
         from . import engine as E
         (proposal_feats, x_feats, mask_preds, cls_scores, seg_preds, depth_feats, depth_proposal, depth_pred,
-         semantic_aspp_out) = sl["rpn"].simple_test_rpn(x, self.metas * x[0].shape[0])
-        o = sl["roi"]._decode(x_feats, proposal_feats, mask_preds, depth_feats, depth_proposal)
+         semantic_aspp_out) = sl.rpn.simple_test_rpn(x, self.metas * x[0].shape[0])
+        o = sl.roi._decode(x_feats, proposal_feats, mask_preds, depth_feats, depth_proposal)
         depth_init = E.upsample2x(depth_pred.float().contiguous())                         # kernel_update.py:302-307
         return o["cls"], o["mask_up"], o["depth_up"], depth_init
 
-    def _start_heads(self, i, frames, borrowed=False):
-        """copy the frames (a list of one-frame FPN level tuples: ONE for the per-frame calls, a clip's chunk for `records`) into
-        slot i's static inputs for that many frames per launch and start its heads on the slot's stream.
+    # -- one heads launch ------------------------------------------------------------------------------------------
+    def _launch(self, i, frames, borrowed):
+        """start the heads of `frames` (a list of one-frame FPN level tuples) on slot i.
 
-        `borrowed` (round 6, clips): the caller keeps the frames' tensors unchanged until their records have been returned, so nothing
-        is copied -- the neck's ingest (fp32 NCHW -> 16-bit conv input planes, its first kernel) runs per frame straight from the caller's
-        tensors, on the caller's stream and OUTSIDE the graph, which then starts at the towers' first convs; RoIAlign reads the caller's
-        levels.  The staging copy of a 1024 x 2048 frame's four levels is 178 MB read + 178 MB written: 0.9 ms of an 8-frame clip's
-        8.4 ms.  Needs the tower-stream neck plan (clip launches of 2+ frames) and fp32 contiguous levels; otherwise the copy form runs."""
+        `borrowed`: the caller keeps the frames' tensors unchanged until they have been consumed, so nothing is copied -- the neck's
+        ingest (fp32 NCHW -> 16-bit conv input planes, its first kernel) runs per frame straight from the caller's tensors, on the
+        caller's stream and OUTSIDE the graph, which then starts at the towers' first convs; RoIAlign reads the caller's levels.  The
+        staging copy of a 1024 x 2048 frame's four levels is 178 MB read + 178 MB written: 0.9 ms of an 8-frame clip's 8.4 ms.  Needs
+        the tower-stream neck plan (launches of 2+ frames) and fp32 contiguous levels; otherwise the copy form runs."""
         sl = self._slot(i)
-        main = torch.cuda.current_stream()
-        B = len(frames)
-        neck0 = getattr(sl["rpn"], "localization_fpn", None)
-        pre = bool(borrowed and self.use_graph and B >= 2 and neck0 is not None and hasattr(neck0, "ingest_frames")
-                   and os.environ.get("PH_VIDEO_BORROW", "1") != "0"
-                   and all(t.dtype == torch.float32 and t.is_contiguous() for f in frames for t in f[:4]))
-        if sl.get("no_borrow"):
-            pre = False                                      # (this neck plan cannot take frames one by one: found at a first capture)
-        key = ("borrowed", B) if pre else B
-        sl["cur"] = key
-        from . import panoptic as Pn
         if not self.use_graph:
-            # slot-owned copies in this path too (torch.cat copies; one frame is cloned): RoIAlign reads the levels one push
-            # later, and the contract is that the caller may reuse its tensors once push() returns (ADVICE r04)
-            x = tuple(t.clone() for t in frames[0]) if B == 1 else tuple(torch.cat([f[l] for f in frames], 0) for l in range(len(frames[0])))
-            outs = self._heads_device(sl, x)
-            dm = (sl["g"].get(key) or {}).get("dm")
+            return self._launch_eager(sl, frames)
+        neck = getattr(sl.rpn, "localization_fpn", None)
+        borrow = bool(borrowed and not sl.no_borrow and len(frames) >= 2 and neck is not None and hasattr(neck, "ingest_frames")
+                      and os.environ.get("PH_VIDEO_BORROW", "1") != "0"
+                      and all(t.dtype == torch.float32 and t.is_contiguous() for f in frames for t in f[:4]))
+        cap = self._capture(sl, frames, True) if borrow else None
+        if cap is None:                                      # not borrowed, or this slot's neck plan cannot borrow
+            cap = self._capture(sl, frames, False)
+        self._replay(sl, cap, frames)
+
+    def _launch_eager(self, sl, frames):
+        """`graph=False`: the module calls themselves on the caller's stream.  Slot-owned copies in this form too (torch.cat copies;
+        one frame is cloned): RoIAlign reads the levels one push later, and the caller may reuse its tensors once push() returns"""
+        from . import panoptic as Pn
+        B = len(frames)
+        x = tuple(t.clone() for t in frames[0]) if B == 1 else tuple(torch.cat([f[l] for f in frames], 0) for l in range(len(frames[0])))
+        outs = self._heads_device(sl, x)
+        prev = sl.captures.get((B, False))
+        dm = prev.dm if prev is not None else None
+        if self.device_select:
+            dm = dm or Pn.DeviceMerge(sl.roi, *outs, self.metas[0])
+            dm.begin(*outs)
+            dm.download()
+        sl.cur = sl.captures[(B, False)] = _Capture(x=x, outs=outs, dm=dm)
+        sl.done = torch.cuda.Event()
+        sl.done.record(torch.cuda.current_stream())
+
+    def _capture(self, sl, frames, borrow):
+        """the slot's graph for this many frames per launch, captured on first use.  None: `borrow` was asked for and this slot's neck
+        plan cannot be filled frame by frame (shared level buffers, two-plane grade) -- the slot copies from now on."""
+        from . import panoptic as Pn
+        B = len(frames)
+        cap = sl.captures.get((B, borrow))
+        if cap is not None:
+            return cap
+        cap = _Capture(x=tuple(t.new_empty((B,) + tuple(t.shape[1:])) for t in frames[0]))
+        for b, f in enumerate(frames):
+            for d, t in zip(cap.x, f):
+                d[b:b + 1].copy_(t)
+        # 2+ frames per launch: the neck's four level towers run on their own streams inside the graph (the small levels' convs are
+        # 16-64 workgroups; eagerly the forks cost more host time than the overlap returns, in a graph nothing: cfg4 +2-6 %, same
+        # bits).  Not at one frame per launch: the per-frame loops got SLOWER with it (1.68 -> 1.92 ms per frame pipelined: the
+        # previous frame's small association kernels wait behind four streams of neck kernels).  PH_VIDEO_CLIP_TOWERS: 0 never,
+        # 1 (default) as above, 2 + the sequential one-frame loop (heads 1.75 -> 1.64 ms, but merge and association + 0.04 each
+        # behind it: inside the scatter; left off)
+        neck = getattr(sl.rpn, "localization_fpn", None)
+        _ct = os.environ.get("PH_VIDEO_CLIP_TOWERS", "1")
+        towers = neck is not None and _ct != "0" and (B >= 2 or (_ct == "2" and not self.pipelined))
+        if towers:
+            neck._clip_towers = True
+        try:
+            outs = self._heads_device(sl, cap.x)             # warm-up outside the capture: plans, packs, kernel attributes
             if self.device_select:
-                dm = dm or Pn.DeviceMerge(sl["roi"], *outs, self.metas[0])
-                dm.begin(*outs)
-                dm.download()
-            sl["g"][key] = dict(x=x, graph=None, outs=outs, dm=dm, B=B, pre=False)
-            sl["done"] = torch.cuda.Event()
-            sl["done"].record(main)
-            return
-        st = sl["g"].get(key)
-        if st is None:
-            st = sl["g"][key] = dict(x=tuple(t.new_empty((B,) + tuple(t.shape[1:])) for t in frames[0]), graph=None, outs=None, dm=None, B=B,
-                                     pre=pre)
-            for b, f in enumerate(frames):
-                for d, t in zip(st["x"], f):
-                    d[b:b + 1].copy_(t)
-            # a clip's 2-3 frames per launch (`records`): the neck's four level towers run on their own streams inside the graph (the
-            # small levels' convs are 16-64 workgroups; eagerly the forks cost more host time than the overlap returns, in a graph
-            # nothing: cfg4 +2-6 %, same bits).  Not at one frame per launch: the per-frame loops got SLOWER with it (1.68 -> 1.92 ms
-            # per frame pipelined: the previous frame's small association kernels wait behind four streams of neck kernels)
-            neck = getattr(sl["rpn"], "localization_fpn", None)
-            # 0: never, 1 (default): clip launches only, 2: + the sequential one-frame loop (module API: heads 1.75 -> 1.64 ms, but merge
-            # and association + 0.04 each behind it: - 0.05 ms of 2.87 per frame, inside the scatter; left off)
-            _ct = os.environ.get("PH_VIDEO_CLIP_TOWERS", "1")
-            towers = neck is not None and _ct != "0" and (B >= 2 or (_ct == "2" and not self.pipelined))
-            if towers:
-                neck._clip_towers = True
+                cap.dm = Pn.DeviceMerge(sl.roi, *outs, self.metas[0])
+                cap.dm.begin(*outs)
+            torch.cuda.synchronize()
+            if borrow:                                       # the graph starts BEHIND the neck's ingest (engine.NeckPlan.skip_ingest)
+                cap.nplan = neck.clip_plan(B, tuple(tuple(t.shape[-2:]) for t in cap.x[:4]), cap.x[0].device)
+                if cap.nplan is None or not cap.nplan.can_ingest_frames():
+                    sl.no_borrow = True
+                    return None
+            cap.graph = torch.cuda.CUDAGraph()
             try:
-                outs = self._heads_device(sl, st["x"])      # warm-up outside the capture: plans, packs, kernel attributes
-                if self.device_select:
-                    st["dm"] = Pn.DeviceMerge(sl["roi"], *outs, self.metas[0])
-                    st["dm"].begin(*outs)
-                torch.cuda.synchronize()
-                nplan = None
-                if pre:
-                    # borrowed clips: the graph starts BEHIND the neck's ingest (engine.NeckPlan.skip_ingest); when this plan cannot be
-                    # filled frame by frame (shared level buffers, two-plane grade) the slot falls back to the copy form for good
-                    nplan = neck.clip_plan(B, tuple(tuple(t.shape[-2:]) for t in st["x"][:4]), st["x"][0].device)
-                    if nplan is None or not nplan.can_ingest_frames():
-                        sl["no_borrow"] = True               # this slot copies from now on; the launch starts over in the copy form
-                        del sl["g"][key]
-                        return self._start_heads(i, frames, borrowed=False)
-                g = torch.cuda.CUDAGraph()
-                try:
-                    if nplan is not None:
-                        nplan.skip_ingest = True
-                    with torch.cuda.graph(g):
-                        st["outs"] = self._heads_device(sl, st["x"])
-                        if st["dm"] is not None:
-                            st["dm"].begin(*st["outs"])
-                finally:
-                    if nplan is not None:
-                        nplan.skip_ingest = False
+                if cap.nplan is not None:
+                    cap.nplan.skip_ingest = True
+                with torch.cuda.graph(cap.graph):
+                    cap.outs = self._heads_device(sl, cap.x)
+                    if cap.dm is not None:
+                        cap.dm.begin(*cap.outs)
             finally:
-                if towers:
-                    neck._clip_towers = False
-            st["graph"] = g
-            st["nplan"] = nplan
-            # the graph replays the plans' device buffers: KernelHead / KernelUpdateIterHead keep ONE plan and drop it when the
-            # batch size changes (a clip's last chunk), so the graph holds its own references -- without them a later replay wrote
-            # into freed blocks (harmless while the allocator kept them mapped; a memory fault once it had not: clips of 3 + 3 + 2)
-            neck = getattr(sl["rpn"], "localization_fpn", None)
-            st["plans"] = [dict(m._plans) for m in (sl["rpn"], sl["roi"], neck) if m is not None and hasattr(m, "_plans")]
+                if cap.nplan is not None:
+                    cap.nplan.skip_ingest = False
+        finally:
+            if towers:
+                neck._clip_towers = False
+        # the graph replays the plans' device buffers: KernelHead / KernelUpdateIterHead keep ONE plan and drop it when the
+        # batch size changes (a clip's last chunk), so the capture holds its own references -- without them a later replay wrote
+        # into freed blocks (harmless while the allocator kept them mapped; a memory fault once it had not: clips of 3 + 3 + 2)
+        cap.plans = tuple(dict(m._plans) for m in (sl.rpn, sl.roi, neck) if m is not None and hasattr(m, "_plans"))
+        sl.captures[(B, borrow)] = cap
+        return cap
+
+    def _replay(self, sl, cap, frames):
+        """stage the frames on the caller's stream and replay the capture on the slot's stream"""
         for f in frames:
-            if len(f) != len(st["x"]) or any(tuple(d.shape[1:]) != tuple(t.shape[1:]) or d.dtype != t.dtype for d, t in zip(st["x"], f)):
+            if len(f) != len(cap.x) or any(tuple(d.shape[1:]) != tuple(t.shape[1:]) or d.dtype != t.dtype for d, t in zip(cap.x, f)):
                 raise ValueError("VideoStreamRunner: the FPN levels changed shape / dtype; one runner serves one stream of equally "
                                  "sized frames (call reset() to re-capture)")
-        if st.get("pre"):
-            st["frames"] = list(frames)                      # RoIAlign reads these; the references keep the storage alive
-            neck0.ingest_frames(frames, plan=st["nplan"])    # on the caller's stream, in front of `ready`; the plan the graph replays
+        sl.cur = cap
+        if cap.nplan is not None:
+            cap.frames = list(frames)                        # RoIAlign reads these; the references keep the storage alive
+            sl.rpn.localization_fpn.ingest_frames(frames, plan=cap.nplan)    # in front of `ready`; the plan the graph replays
         else:
-            st["frames"] = None
             for b, f in enumerate(frames):
-                for d, t in zip(st["x"], f):
-                    d[b:b + 1].copy_(t, non_blocking=True)   # on the caller's stream: the frame may be reused once push returns
+                for d, t in zip(cap.x, f):
+                    d[b:b + 1].copy_(t, non_blocking=True)   # the frame may be reused once the call returns
         ready = torch.cuda.Event()
-        ready.record(main)
-        with torch.cuda.stream(sl["stream"]):
-            sl["stream"].wait_event(ready)
-            # heads of different launches run ONE AFTER THE OTHER (round 6): what a launch should overlap with is the host's walk
-            # through the frames in front of it and their small kernels, not another heads graph -- two persistent one-pass KernelHead
+        ready.record(torch.cuda.current_stream())
+        with torch.cuda.stream(sl.stream):
+            sl.stream.wait_event(ready)
+            # heads of different launches run ONE AFTER THE OTHER: what a launch should overlap with is the host's walk through
+            # the frames in front of it and their small kernels, not another heads graph -- two persistent one-pass KernelHead
             # launches at once starve each other until one gives up (8-frame clips queued back to back: 18.5 ms per step instead of 8)
-            last = getattr(self, "_last_done", None)
-            if last is not None:
-                sl["stream"].wait_event(last)
-            st["graph"].replay()
-            if st["dm"] is not None:
-                st["dm"].download()
-            sl["done"] = torch.cuda.Event()
-            sl["done"].record(sl["stream"])
-            self._last_done = sl["done"]
+            if self._last_done is not None:
+                sl.stream.wait_event(self._last_done)
+            cap.graph.replay()
+            if cap.dm is not None:
+                cap.dm.download()
+            sl.done = torch.cuda.Event()
+            sl.done.record(sl.stream)
+            self._last_done = sl.done
 
-    def _frame_levels(self, i, b=0):
-        """the FPN levels of frame b of slot i's current launch (views of its static inputs)"""
-        sl = self._slots[i]
-        st = sl["g"][sl["cur"]]
-        if st.get("frames"):                                 # a borrowed clip: the caller's tensors
-            return tuple(st["frames"][b])
-        x = st["x"]
-        return x if sl["cur"] == 1 else tuple(t[b:b + 1] for t in x)
+    # -- the queue -------------------------------------------------------------------------------------------------
+    def _enter(self, mode):
+        from . import _lib
+        if mode != self._mode and (self._launches or self._waiting or self._buf or self._clips):
+            raise _lib.PolyheadError(f"VideoStreamRunner: {self._mode} are in flight; drain them (flush() / flush_record() / "
+                                     f"records_end()) before asking for {mode}")
+        self._mode = mode
+
+    def _submit(self, frames, borrowed=False):
+        self._waiting.append((frames, borrowed, self._weight_versions()))
+        self._start_waiting()
+
+    def _start_waiting(self):
+        while self._waiting and self._free:
+            frames, borrowed, versions = self._waiting[0]
+            if versions != self._versions:
+                if self._launches:
+                    return                                   # new weights: every launch of the old captures is consumed first
+                self._slots, self._versions = [], versions   # the chunk captures again from the current modules
+            self._launch(self._free[0], frames, borrowed)
+            self._waiting.pop(0)
+            self._launches.append((self._free.pop(0), len(frames)))
+
+    def _consume(self, per_frame):
+        """the oldest launch's frames through `per_frame(slot index, frame)`; its slot goes to the next waiting chunk"""
+        i, n = self._launches[0]
+        out = [per_frame(i, b) for b in range(n)]
+        self._launches.pop(0)
+        self._free.append(i)
+        if not self._launches:
+            self._free.sort()                                # drained: the next stream starts on slot 0 again
+        self._start_waiting()
+        return out
+
+    def _consume_down_to(self, keep, per_frame):
+        while len(self._launches) + len(self._waiting) > keep:
+            self._consume(per_frame)
 
     # -- the part of a frame that follows the heads -----------------------------------------------------------------
+    def _frame_levels(self, i, b=0):
+        """the FPN levels of frame b of slot i's current launch (views of its static inputs, or the caller's borrowed tensors)"""
+        cap = self._slots[i].cur
+        if cap.frames:
+            return tuple(cap.frames[b])
+        return cap.x if cap.x[0].shape[0] == 1 else tuple(t[b:b + 1] for t in cap.x)
+
     def _merge(self, i, b=0):
         from . import panoptic as Pn
         sl = self._slots[i]
-        torch.cuda.current_stream().wait_event(sl["done"])
-        st = sl["g"][sl["cur"]]
-        if st["dm"] is not None:
-            sl["done"].synchronize()                         # candidates + histograms are in pinned memory
-            return st["dm"].finish(b)
-        cls, mask_up, depth_up, depth_init = st["outs"]
-        return Pn.get_panoptic_device(sl["roi"], cls[b], mask_up[b], depth_up[b], depth_init[b], self.metas[0])
+        torch.cuda.current_stream().wait_event(sl.done)
+        cap = sl.cur
+        if cap.dm is not None:
+            sl.done.synchronize()                            # candidates + histograms are in pinned memory
+            return cap.dm.finish(b)
+        cls, mask_up, depth_up, depth_init = cap.outs
+        return Pn.get_panoptic_device(sl.roi, cls[b], mask_up[b], depth_up[b], depth_init[b], self.metas[0])
+
+    def _record(self, i, b=0):
+        pan_dev, info, _, _ = self._merge(i, b)
+        return self.pipe.assoc.record(self._frame_levels(i, b), None, info, pan_dev)
 
     def _finish(self, i, b=0):
         """merge -> association -> start the download of the result maps of frame b of slot i's launch"""
@@ -1038,91 +1091,73 @@ class VideoStreamRunner:
         if x[0].shape[0] != 1:
             raise NotImplementedError("video inference is one frame at a time (samples_per_gpu = 1, as in the reference)")
 
+    # -- result maps -----------------------------------------------------------------------------------------------
     def push(self, x):
-        """x: the four FPN levels of ONE frame (device tensors).  Returns the result list [{"sem", "track", "depth"}] (numpy,
-        owned by the caller) of the frame pushed two calls ago (one call ago with pipelined=False), or None."""
+        """x: the four FPN levels of ONE frame (device tensors; the caller may reuse them once push returns).  Returns the result
+        list [{"sem", "track", "depth"}] (numpy, owned by the caller) of the frame pushed two calls ago (one call ago with
+        pipelined=False; up to two launches ago with `frames_per_launch` > 1), or None."""
         self._check(x)
+        self._enter("maps")
+        late = 1
         if self.frames_per_launch > 1 and self._launch_size() > 1:
-            return self._push_batched(x)
-        self._check_weights()
-        if not self.pipelined:
-            self._start_heads(0, [x])
-            self._finish(0)
-            self._n += 1
-            return self._collect(self._downloads.pop(0)) if len(self._downloads) > 1 else None
-        i = self._n & 1
-        self._start_heads(i, [x])                            # frame t: heads on slot i's stream ...
-        if self._inflight is not None:
-            self._finish(self._inflight)                     # ... while the host takes frame t - 1 through merge / association
-        self._inflight = i
-        self._n += 1
-        return self._collect(self._downloads.pop(0)) if len(self._downloads) > 1 else None
-
-    def _launch_size(self):
-        """frames per launch of the batched `push`: `frames_per_launch` where the heads are batch invariant (`clip_batch`'s conditions), else 1"""
-        from . import _lib, engine as E
-        grade = E.KHEAD_PREC.get(getattr(self.pipe.rpn_head, "precision", None))
-        ok = (grade in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) and not os.environ.get("PH_KHEAD_TWOPASS")
-              and getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False))
-        return self.frames_per_launch if ok else 1
+            late = self.frames_per_launch
+            self._buf.append(tuple(t.clone() for t in x))
+            if len(self._buf) >= late:
+                self._launch_buffered()
+        else:
+            self._submit([x])                                # frame t: heads on a slot's stream ...
+            self._consume_down_to(int(self.pipelined), self._finish)     # ... while the host takes frame t - 1 through merge / association
+        return self._collect(self._downloads.pop(0)) if len(self._downloads) > late else None
 
     def _launch_buffered(self):
-        """the buffered frames' heads on the next slot; then the previous launch's frames walk merge -> association underneath them"""
-        if not self._inflight_b and not self._buf:
-            return
-        if self._buf:
-            self._check_weights()                        # (new weights: finishes the launch in flight with the old ones, drops the slots)
-        prev = self._inflight_b
-        self._inflight_b = None
-        if self._buf:
-            i = (self._nb & 1) if self.pipelined else 0
-            if not self.pipelined and prev is not None:
-                for b in range(prev[1]):
-                    self._finish(prev[0], b)
-                prev = None
-            # the buffered frames are this runner's own clones (`_push_batched`): they ARE the slot-owned copy -- borrowed, so the
-            # launch does not copy them a second time into the graph's static inputs (round 6)
-            self._start_heads(i, self._buf, borrowed=True)
-            self._inflight_b = (i, len(self._buf))
-            self._buf = []
-            self._nb += 1
-        if prev is not None:
-            for b in range(prev[1]):
-                self._finish(prev[0], b)
-
-    def _push_batched(self, x):
-        assert self._inflight is None and not self._rq, "push() in batches and push_record() / records() must not be interleaved"
-        self._buf.append(tuple(t.clone() for t in x))    # the caller may reuse its tensors once push returns
-        if len(self._buf) >= self.frames_per_launch:
-            self._launch_buffered()
-        self._n += 1
-        return self._collect(self._downloads.pop(0)) if len(self._downloads) > self.frames_per_launch else None
+        # the buffered frames are this runner's own clones: they ARE the slot-owned copy -- borrowed, so the launch does not copy them
+        # a second time into the graph's static inputs
+        frames, self._buf = self._buf, []
+        self._submit(frames, borrowed=True)
+        self._consume_down_to(1, self._finish)               # (one slot: the previous launch is consumed first, this one stays in flight)
 
     def flush(self):
         """the results still in flight, oldest first (a list of result lists)"""
-        if self._buf or self._inflight_b:
-            self._launch_buffered()                      # the partial last batch (its own launch size), then whatever is still in flight
-            self._launch_buffered()
-        if self._inflight is not None:
-            self._finish(self._inflight)
-            self._inflight = None
+        self._enter("maps")
+        if self._buf:
+            self._launch_buffered()                          # the partial last batch (its own launch size)
+        self._consume_down_to(0, self._finish)
         out = [self._collect(p) for p in self._downloads]
         self._downloads = []
         return out
 
+    def run_one(self, x):
+        """`push` without the delay: the frame's heads, merge and association, and its own result list at once"""
+        self._check(x)
+        self._enter("maps")
+        self._submit([x])
+        self._consume_down_to(0, self._finish)
+        return self._collect(self._downloads.pop())
+
+    def _batch_invariant(self):
+        """whether every frame of a B-frame heads launch gets the bits of its own one-frame launch: the grades whose KernelHead runs
+        the one-pass kernel (fp16 / bf16; the two-pass kernel's tile runs are sized by the batch, which regroups its fp32 partial
+        sums -- 1e-6 differences) and heads left `frame_invariant`"""
+        from . import _lib, engine as E
+        grade = E.KHEAD_PREC.get(getattr(self.pipe.rpn_head, "precision", None))
+        return bool(grade in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) and not os.environ.get("PH_KHEAD_TWOPASS")
+                    and getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False))
+
+    def _launch_size(self):
+        """frames per launch of the batched `push`: `frames_per_launch` where the heads are batch invariant, else 1"""
+        return self.frames_per_launch if self._batch_invariant() else 1
+
+    # -- track records ---------------------------------------------------------------------------------------------
     def clip_batch(self, frames):
         """frames per launch for `records`: the heads are frame independent, so a clip's frames go through neck ->
         KernelHead -> decode TOGETHER -- at one frame per launch those kernels are latency bound and eight frames cost barely more
-        than two.  Every frame's tensors must stay those of the per-frame loop bit for bit.  Round 6: that holds by construction for
-        any batch -- every choice that touches a frame's arithmetic follows the FRAME's geometry, never B (the neck's conv tile rows
+        than two.  Every frame's tensors must stay those of the per-frame loop bit for bit.  That holds by construction for any
+        batch -- every choice that touches a frame's arithmetic follows the FRAME's geometry, never B (the neck's conv tile rows
         and output-stage tile runs, csrc/ph_neck.hip conv_th / ph_khead.hip kh_tiles_per_wg_plain; the pooling's pixel split and the
         final-stage form of `frame_invariant` plans, engine.DecodePlan / KernelHeadPlan; the one-pass KernelHead groups a frame's
-        GroupNorm sums by its own pixel slices) -- so the frames per launch are a pure launch-size choice (`PH_VIDEO_CLIP_BATCH=n`; 1 restores
-        one frame per launch; default below), asserted for 1 .. 16 frames by tests/test_gpu_video.py::test_heads_are_batch_invariant.  Exceptions:
-        the grades whose KernelHead runs the two-pass kernel (fp32 / mixed: its workgroups' tile runs are sized by the batch, which
-        regroups the fp32 partial sums -- 1e-6 differences, not bit identity) and heads switched to `frame_invariant = False`."""
-        import os
-        from . import _lib, engine as E
+        GroupNorm sums by its own pixel slices) -- so the frames per launch are a pure launch-size choice (`PH_VIDEO_CLIP_BATCH=n`; 1
+        restores one frame per launch; default below), asserted for 1 .. 16 frames by
+        tests/test_gpu_video.py::test_heads_are_batch_invariant.  Exceptions: `_batch_invariant`."""
         # default: a clip of 4 or more frames goes as TWO launches (half the clip each, at most 8 frames): the second half's heads run
         # while the host walks the first half through merge -> boxes -> RoIAlign -> track head, and with clips queued (`records_begin`
         # ahead of the previous `records_end`) the next clip's first half follows on the slot that frees up.  Measured on one box
@@ -1130,92 +1165,52 @@ class VideoStreamRunner:
         # 768 / 786 / 889 / 979.  Shorter clips: one launch.
         n = len(frames)
         cap = int(os.environ.get("PH_VIDEO_CLIP_BATCH", "0")) or (n if n <= 3 else min(8, (n + 1) // 2))
-        grade = E.KHEAD_PREC.get(getattr(self.pipe.rpn_head, "precision", None))
-        if grade not in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) or os.environ.get("PH_KHEAD_TWOPASS"):
-            return 1
-        if not (getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False)):
-            return 1
-        return max(1, min(cap, len(frames)))
+        return max(1, min(cap, n)) if self._batch_invariant() else 1
 
     def records(self, frames, borrowed=True):
         """the sharded mode's per-step work for a rank's clip: `simple_test(..., records_only=True)` of every frame in order.
-        The clip goes through the heads in chunks of `clip_batch` frames per launch; the heads of up to two chunks are in flight
-        at a time: chunk k + 1's are started BEFORE chunk k's merges / records, and the clip's first two chunks start back to back.
         Returns [(segment ids, (bboxes, labels, embeds) or None)] per frame.  = `records_begin` + `records_end`.  The call returns when
-        every frame has been consumed, so the frames are `borrowed` (no staging copy, `_start_heads`) unless the caller says otherwise."""
+        every frame has been consumed, so the frames are `borrowed` (no staging copy, `_launch`) unless the caller says otherwise."""
         self.records_begin(frames, borrowed=borrowed)
         return self.records_end()
 
-    def _pump(self):
-        """start the heads of waiting chunks, oldest clip first, while a slot is free (graph replays on the slots' streams)"""
-        for clip in self._rq:
-            while clip["next"] < len(clip["chunks"]) and self._free:
-                i = self._free.pop(0)
-                self._start_heads(i, clip["chunks"][clip["next"]], borrowed=clip.get("borrowed", False))
-                clip["slots"].append(i)
-                clip["next"] += 1
-            if clip["next"] < len(clip["chunks"]):
-                break                                    # launch order = frame order: a later clip never overtakes an earlier one
-
     def records_begin(self, frames, borrowed=False):
-        """first half of `records`: queues the clip and STARTS the heads of as many of its chunks as slots are free -- returns without
-        waiting for the device.  Round 6: clips QUEUE -- `records_begin` of the next clip may be called before `records_end` of the
-        previous one, and then its heads run (on the other slot) underneath the previous clip's merges / records, which are host work
-        and a few small kernels: the sharded video loop (bench.cfg4_run) does exactly that, so a step costs max(heads, merges + records +
-        all-gather + replay) instead of their sum.  `records_end` always returns the OLDEST queued clip's records.
-        `borrowed=True`: the caller leaves the frames' tensors unchanged until `records_end` has returned this clip (`_start_heads`)."""
+        """first half of `records`: submits the clip in chunks of `clip_batch` frames -- the heads of as many chunks as slots are free
+        start, and the call returns without waiting for the device.  Clips QUEUE: `records_begin` of the next clip may be called
+        before `records_end` of the previous one, and then its heads run (on the other slot) underneath the previous clip's merges /
+        records, which are host work and a few small kernels: the sharded video loop (bench.cfg4_run) does exactly that, so a step
+        costs max(heads, merges + records + all-gather + replay) instead of their sum.
+        `borrowed=True`: the caller leaves the frames' tensors unchanged until `records_end` has returned this clip (`_launch`)."""
         frames = list(frames)
-        assert self._inflight is None, "records() and push() / push_record() must not be interleaved"
         for f in frames:
             self._check(f)
-        if not getattr(self, "_rq", None):
-            self._rq = []
-            self._check_weights()                        # (drops the slots when the weights changed: only between clips)
-            self._free = list(range(2 if self.pipelined else 1))
+        self._enter("records")
         Bc = self.clip_batch(frames) if frames else 1
-        self._rq.append(dict(chunks=[frames[k:k + Bc] for k in range(0, len(frames), Bc)], next=0, slots=[], borrowed=bool(borrowed)))
-        self._pump()
+        chunks = [frames[k:k + Bc] for k in range(0, len(frames), Bc)]
+        self._clips.append(len(chunks))
+        for chunk in chunks:
+            self._submit(chunk, borrowed=bool(borrowed))
 
     def records_end(self):
-        """second half of `records`, for the oldest queued clip: merges / records chunk by chunk (the synchronising part); every slot it
-        frees goes to the next waiting chunk at once -- of this clip or of the clip queued behind it"""
-        clip = self._rq[0]
+        """second half of `records`, for the OLDEST queued clip: merges / records launch by launch (the synchronising part); every slot
+        it frees goes to the next waiting chunk at once -- of this clip or of the clip queued behind it"""
+        from . import _lib
+        if not self._clips:
+            raise _lib.PolyheadError("VideoStreamRunner.records_end(): no clip is queued (records_begin first)")
         out = []
-        for c, chunk in enumerate(clip["chunks"]):
-            if c >= len(clip["slots"]):
-                self._pump()                             # (a slot is free: every earlier chunk of this clip has been consumed)
-            i = clip["slots"][c]
-            for b in range(len(chunk)):
-                out.append(self._record(i, b))
-            self._free.append(i)
-            self._pump()
-        self._rq.pop(0)
+        for _ in range(self._clips[0]):
+            out += self._consume(self._record)
+        self._clips.pop(0)
         return out
 
     def push_record(self, x):
         """the sharded mode's per-frame work (`simple_test(..., records_only=True)`) for the frame pushed ONE call ago (None for
-        the first call): its heads ran while the caller dealt with the frame before; `flush_record()` returns the last frame's.
-        Returns (segment ids, (bboxes, labels, embeds) or None); nothing map-sized is downloaded."""
-        self._check(x)
-        i = self._n & 1 if self.pipelined else 0
-        prev = None
-        if not self.pipelined:
-            self._start_heads(0, [x])
-            self._n += 1
-            return self._record(0)
-        self._start_heads(i, [x])
-        if self._inflight is not None:
-            prev = self._record(self._inflight)
-        self._inflight = i
-        self._n += 1
-        return prev
+        the first call; this call's own frame with pipelined=False): its heads ran while the caller dealt with the frame before;
+        `flush_record()` returns the last frame's.  Returns (segment ids, (bboxes, labels, embeds) or None); nothing map-sized is
+        downloaded.  The stream is a queue of one-frame clips."""
+        self.records_begin([x])
+        return self.records_end()[0] if len(self._clips) > int(self.pipelined) else None
 
     def flush_record(self):
-        if self._inflight is None:
-            return None
-        i, self._inflight = self._inflight, None
-        return self._record(i)
-
-    def _record(self, i, b=0):
-        pan_dev, info, _, _ = self._merge(i, b)
-        return self.pipe.assoc.record(self._frame_levels(i, b), None, info, pan_dev)
+        self._enter("records")
+        return self.records_end()[0] if self._clips else None

@@ -563,7 +563,7 @@ def test_stream_runner_batches_a_clips_frames_per_launch(gpu, graph, monkeypatch
     runner = V.VideoStreamRunner(pipe, meta[0], graph=graph)
     assert runner.clip_batch(frames) == 3 and runner.clip_batch(frames[:2]) == 2 and runner.clip_batch(frames[:1]) == 1
     got = runner.records(frames)
-    sizes = lambda sl: sorted(k[1] if isinstance(k, tuple) else k for k in sl["g"])       # (graph: the clip's frames are borrowed, round 6)
+    sizes = lambda sl: sorted(B for B, borrowed in sl.captures)       # (graph: the clip's frames are borrowed, round 6)
     assert sizes(runner._slots[0]) == [3] and sizes(runner._slots[1]) == [2]
     nrec = 0
     for x, (ids_a, rec_a) in zip(frames, got):
@@ -599,7 +599,7 @@ def test_heads_are_batch_invariant(gpu, B):
     torch.cuda.synchronize()
     # round 6: launches that fill the chip take the fused conv + pooling of x (ph_dynconv_poolx) -- its sums are k_pool's bit for bit in
     # this grade, so the frames below (one-frame launches: the separate kernels) must still be identical
-    plan_b = next(iter(sl["roi"]._plans.values()))
+    plan_b = next(iter(sl.roi._plans.values()))
     assert plan_b.B == B and plan_b.frame_invariant and plan_b.poolx == (B >= 6)
     for b in sorted({0, B // 2, B - 1}):               # first, middle and last frame of the launch against their own one-frame launches
         o1 = runner._heads_device(sl, frames[b])
@@ -655,7 +655,7 @@ def test_stream_runner_clip_of_3_3_2_replays_graphs_whose_plans_were_replaced(gp
     for clip in range(2):
         frames = [tuple(torch.roll(t, (8 * clip + f, 2 * f), dims=(2, 3)) for t in base) for f in range(8)]
         got = runner.records(frames)
-        sizes = lambda sl: sorted(k[1] if isinstance(k, tuple) else k for k in sl["g"])
+        sizes = lambda sl: sorted(B for B, borrowed in sl.captures)
         assert sizes(runner._slots[0]) == [2, 3] and sizes(runner._slots[1]) == [3]
         torch.cuda.empty_cache()                      # freed blocks really go back to the driver
         for x, (ids_a, rec_a) in zip(frames, got):
@@ -681,8 +681,8 @@ def test_borrowed_clip_frames_give_the_same_records(gpu, monkeypatch):
     for mode in ("copy", "borrowed"):
         runner = V.VideoStreamRunner(pipe, meta[0])
         outs[mode] = [runner.records(clip, borrowed=(mode == "borrowed")) for clip in (frames[:5], frames[2:7], frames[:5])]
-        keys = [k for sl in runner._slots for k in sl["g"]]
-        assert all(isinstance(k, tuple) and k[0] == "borrowed" for k in keys) == (mode == "borrowed"), keys
+        keys = [k for sl in runner._slots for k in sl.captures]
+        assert keys and all(borrowed == (mode == "borrowed") for B, borrowed in keys), keys
     nrec = 0
     for ca, cb in zip(outs["copy"], outs["borrowed"]):
         assert len(ca) == len(cb) == 5
@@ -691,3 +691,101 @@ def test_borrowed_clip_frames_give_the_same_records(gpu, monkeypatch):
             assert ra is None or all(torch.equal(u, v) for u, v in zip(ra, rb))
             nrec += ra is not None
     assert nrec > 0
+
+
+def _small_stream(gpu, n, seed):
+    """the fp16 cfg3 pipeline on n frames of 256 x 512 (levels 64x128 .. 8x16: the smallest all four strides still produce; the
+    runner's launch queue does not depend on the frame size)"""
+    pipe, sd, cfg, wl = _cfg3_pipeline(gpu, precision="fp16")
+    H8, W8 = 256, 512
+    g = torch.Generator().manual_seed(seed)
+    base = [torch.randn(1, 256, H8 // s, W8 // s, generator=g).to(gpu) for s in (4, 8, 16, 32)]
+    frames = [tuple(torch.roll(t, (f, 2 * f), dims=(2, 3)) for t in base) for f in range(n)]
+    return pipe, frames, [Hh.img_meta(H8, W8)]
+
+
+def _records_equal(a, b):
+    return len(a) == len(b) and all(ia == ib and (ra is None) == (rb is None) and (ra is None or all(torch.equal(u, v) for u, v in zip(ra, rb)))
+                                    for (ia, ra), (ib, rb) in zip(a, b))
+
+
+def test_queued_clips_and_record_streams_follow_weight_changes(gpu):
+    """new weights between `records_begin` of clip A and of clip B, A still in flight: A's records are the old weights', B's the new
+    ones' -- B waits until A has been consumed, then the slots capture again (the parent commit checked the weights only with an
+    empty clip queue and replayed the old packs for B); the same for a `push_record` stream whose weights change before frame 2"""
+    from polyphonicformer_amd import video as V
+    pipe, frames, meta = _small_stream(gpu, 4, 41)
+    A, B = frames[:2], frames[2:]
+    sd0 = {k: v.detach().clone() for k, v in pipe.roi_head.state_dict().items()}
+    sd1 = {k: (v * 1.05 if v.dtype.is_floating_point and "fc_mask" in k else v.clone()) for k, v in sd0.items()}
+    api = lambda clip: [pipe.simple_test(x, meta, records_only=True) for x in clip]
+    a0, b0 = api(A), api(B)
+    pipe.roi_head.load_state_dict(sd1)
+    b1 = api(B)
+    assert any(rec is not None for _, rec in a0 + b1)
+    assert not _records_equal(b0, b1)                  # the new weights do change B's records
+    pipe.roi_head.load_state_dict(sd0)
+    runner = V.VideoStreamRunner(pipe, meta[0])
+    runner.records_begin(A)
+    runner.records_begin(B)                            # both slots hold captures made with the old weights
+    assert _records_equal(runner.records_end(), a0) and _records_equal(runner.records_end(), b0)
+    runner.records_begin(A)
+    pipe.roi_head.load_state_dict(sd1)
+    runner.records_begin(B)
+    assert _records_equal(runner.records_end(), a0), "clip A: the weights it was begun with"
+    assert _records_equal(runner.records_end(), b1), "clip B: the weights loaded before it was begun"
+    pipe.roi_head.load_state_dict(sd0)
+    got = []
+    for f, x in enumerate(frames):
+        if f == 2:
+            pipe.roi_head.load_state_dict(sd1)
+        got.append(runner.push_record(x))
+    got.append(runner.flush_record())
+    assert got[0] is None and runner.flush_record() is None
+    assert _records_equal(got[1:], a0 + b1), "push_record stream"
+
+
+def test_mixing_maps_and_records_raises(gpu):
+    """a runner delivers result maps or records until it is drained: the other kind in between is a `PolyheadError` (not an
+    `assert`, which python -O drops), and works again once the runner has been drained"""
+    from polyphonicformer_amd import video as V
+    pipe, frames, meta = _small_stream(gpu, 4, 42)
+    pipe.init_tracker()
+    runner = V.VideoStreamRunner(pipe, meta[0], frames_per_launch=2)
+    assert runner._launch_size() == 2
+    for n, x in enumerate(frames[:3]):                 # one frame buffered; then a launch in flight; then both
+        assert runner.push(tuple(t.clone() for t in x)) is None
+        with pytest.raises(_lib.PolyheadError):
+            runner.records_begin(frames[:2])
+        with pytest.raises(_lib.PolyheadError):
+            runner.push_record(frames[0])
+    maps = runner.flush()
+    assert len(maps) == 3 and any((m[0]["track"] > 0).any() for m in maps)
+    assert runner.push_record(frames[0]) is None
+    with pytest.raises(_lib.PolyheadError):
+        runner.push(frames[1])
+    with pytest.raises(_lib.PolyheadError):
+        runner.flush()
+    assert runner.flush_record() is not None
+    runner.records_begin(frames[:2])
+    with pytest.raises(_lib.PolyheadError):
+        runner.push(frames[2])
+    assert len(runner.records_end()) == 2
+    assert runner.push(frames[2]) is None and len(runner.flush()) == 1
+
+
+def test_one_queue_four_front_ends_one_answer(gpu):
+    """a 6-frame stream's records through `records`, through `push_record` x 6 + `flush_record`, through three 2-frame clips begun back
+    to back and then ended, and through the per-frame module API: segment ids, boxes, labels and embeddings bit for bit"""
+    from polyphonicformer_amd import video as V
+    pipe, frames, meta = _small_stream(gpu, 6, 43)
+    want = [pipe.simple_test(x, meta, records_only=True) for x in frames]
+    assert any(rec is not None for _, rec in want)
+    runner = V.VideoStreamRunner(pipe, meta[0])
+    assert _records_equal(runner.records(frames), want), "records"
+    got = [runner.push_record(x) for x in frames] + [runner.flush_record()]
+    assert got[0] is None and _records_equal(got[1:], want), "push_record"
+    for k in range(0, 6, 2):
+        runner.records_begin(frames[k:k + 2], borrowed=True)
+    got = runner.records_end() + runner.records_end() + runner.records_end()
+    assert _records_equal(got, want), "queued clips"

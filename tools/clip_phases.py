@@ -30,7 +30,7 @@ th, tm, tr = [], [], []
 for _ in range(5):
     Bc = runner.clip_batch(frames)
     sync(); t0 = time.perf_counter()
-    runner._start_heads(0, frames[:Bc]); sync()
+    runner._launch(0, frames[:Bc], False); sync()
     t1 = time.perf_counter()
     merged = []
     for b in range(Bc):

@@ -29,8 +29,7 @@ acc = dict(heads=0.0, merge=0.0, assoc=0.0, download=0.0)
 for f in range(n):
     x = xs[f % 6]
     sync(); t = time.perf_counter()
-    r._check_weights()
-    r._start_heads(0, [x])
+    r._launch(0, [x], False)
     sync(); t1 = time.perf_counter()
     pan_dev, info, _, d_final = r._merge(0)
     sync(); t2 = time.perf_counter()
