@@ -189,13 +189,22 @@ class AssignLayout(C.Structure):
         [(n, C.c_int64) for n in ("P", "depth_items", "seg_items", "depth_rows")]
 
 
+# the training path's losses from descriptors (polyhead.h ph_loss_cfg, ph_train_losses)
+class LossCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "L", "P", "depth_rows", "seg_L", "has_rank", "ignore", "depth_mode")] + \
+        [("HW", C.c_int64)] + \
+        [(n, C.c_float) for n in ("lw_mask", "lw_dice", "dice_eps", "lw_rank", "lw_depth", "dw_si", "dw_sq", "dw_abs", "lw_cls",
+                                  "cls_gamma", "cls_alpha", "cls_avg", "lw_seg", "seg_gamma", "seg_alpha")]
+
+
 # C typedef name -> its mirror above: every Structure of this module (tests/test_abi.py compares each layout with the header's)
 STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
            "ph_neck_cfg": NeckCfg, "ph_neck_layout": NeckLayout, "ph_neck_geometry": NeckGeometry, "ph_neck_io": NeckIO,
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
-           "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout}
+           "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout,
+           "ph_loss_cfg": LossCfg}
 
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t

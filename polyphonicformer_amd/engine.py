@@ -1522,7 +1522,7 @@ class NativeAssocPlan(_OwnsHandles):
     """The association step of B frames over ph_panoptic_merge's device outputs: `run` is ONE launch-only native call
     (ph_assoc_plan_run: things tables, `sem`, boxes, RoIAlign, track embeddings -- capturable with torch.cuda.graph), `match` the one
     synchronising call behind it (ph_assoc_plan_match: the tracker and the `track` maps), `track` that call's launch-only counterpart
-    over a NativeDeviceTracker (ph_assoc_plan_track).  `pack`: a NativeTrackPack; `cfg`: a
+    over a tracker.NativeDeviceTracker (ph_assoc_plan_track).  `pack`: a NativeTrackPack; `cfg`: a
     ph_assoc_cfg (`native_assoc_cfg`).  The outputs are this object's static tensors: the next call overwrites them."""
     _destroy_symbol = "ph_assoc_plan_destroy"
 
@@ -1587,10 +1587,10 @@ class NativeAssocPlan(_OwnsHandles):
         _lib.check(_lib.load().ph_assoc_plan_run(self._h, C.byref(io), _lib.stream_ptr()), "ph_assoc_plan_run")
         return self.sem, self.things, self.embeds
 
-    def match(self, tracker_handle, pan, first_frame_id):
-        """the tracker (a ph_tracker handle) and the track-id maps behind `run` on the current stream: synchronises.  Returns
-        (track float64 [B, Ho, Wo] on the device, painted ids int64 [B, cap] on the host, frames matched)"""
-        m = _lib.load().ph_assoc_plan_match(self._h, tracker_handle, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
+    def match(self, tracker, pan, first_frame_id):
+        """the host tracker (a tracker.NativeHostTracker) and the track-id maps behind `run` on the current stream: synchronises.
+        Returns (track float64 [B, Ho, Wo] on the device, painted ids int64 [B, cap] on the host, frames matched)"""
+        m = _lib.load().ph_assoc_plan_match(self._h, tracker.handle, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
                                             C.c_void_p(self.staging.data_ptr()), self.staging.numel(), int(first_frame_id),
                                             _lib.ptr(self.track_map), C.c_void_p(self.ids.data_ptr()), _lib.stream_ptr())
         if m < 0:
@@ -1598,92 +1598,9 @@ class NativeAssocPlan(_OwnsHandles):
         return self.track_map, self.ids, int(m)
 
     def track(self, dtracker, pan):
-        """the device tracker (a NativeDeviceTracker) and the track-id maps behind `run` on the current stream: launches only, no
+        """the device tracker (a tracker.NativeDeviceTracker) and the track-id maps behind `run` on the current stream: launches only, no
         synchronisation, capturable.  Returns (track float64 [B, Ho, Wo], painted ids int64 [B, cap]), both on the device; the frames
         matched are `dtracker.status()["matched"]`"""
         _lib.check(_lib.load().ph_assoc_plan_track(self._h, dtracker._h, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
                                                    _lib.ptr(self.track_map), _lib.ptr(self.ids_dev), _lib.stream_ptr()), "ph_assoc_plan_track")
         return self.track_map, self.ids_dev
-
-
-# ---- the device tracker (include/polyhead.h ph_dtracker_*; csrc/ph_dtracker.hip) ---------------------------------------------------
-def native_tracker_cfg(init_score_thr=0.8, obj_score_thr=0.5, match_score_thr=0.5, memo_tracklet_frames=10, memo_backdrop_frames=1,
-                       memo_momentum=0.8, nms_conf_thr=0.5, nms_backdrop_iou_thr=0.3, nms_class_iou_thr=0.7, with_cats=True,
-                       match_metric="bisoftmax", **_):
-    """a ph_tracker_cfg from QuasiDenseEmbedTracker's kwargs (1 - momentum evaluated in double, as `(1 - momentum) * tensor` does)"""
-    return _lib.TrackerCfg(init_score_thr, obj_score_thr, match_score_thr, memo_momentum, 1 - memo_momentum, nms_conf_thr,
-                           nms_backdrop_iou_thr, nms_class_iou_thr, memo_tracklet_frames, memo_backdrop_frames, 1 if with_cats else 0,
-                           {"bisoftmax": 0, "softmax": 1, "cosine": 2}[match_metric])
-
-
-class NativeDeviceTracker(_OwnsHandles):
-    """The tracker whose state lives in ONE device buffer this object owns (ph_dtracker_*): `reset` and `run` are launches only on
-    the current stream (capturable), `status()` and `tables()` synchronising reads.  `cfg`: a ph_tracker_cfg (`native_tracker_cfg`)."""
-    _destroy_symbol = "ph_dtracker_destroy"
-
-    def __init__(self, cfg, device, capacity=4096, max_dets=128, first_frame_id=1):
-        lib, dev = _lib.load(), torch.device(device)
-        self.cfg, self.device, self.capacity, self.max_dets = _lib.TrackerCfg.from_buffer_copy(bytes(cfg)), dev, capacity, max_dets
-        nbytes = lib.ph_dtracker_device_bytes(C.byref(self.cfg), capacity, max_dets)
-        if nbytes == 0:
-            raise _cfg_error("ph_dtracker_device_bytes")
-        self.mem = torch.empty((nbytes,), dtype=torch.uint8, device=dev)             # zeroing contract: none (`reset` below)
-        self._h = C.c_void_p()
-        _lib.check(lib.ph_dtracker_create(C.byref(self.cfg), _lib.ptr(self.mem), nbytes, capacity, max_dets, C.byref(self._h)),
-                   "ph_dtracker_create")
-        self.layout = _lib.DtrackerLayout()
-        _lib.check(lib.ph_dtracker_get_layout(self._h, C.byref(self.layout)), "ph_dtracker_get_layout")
-        self.io = _lib.DtrackerIO()
-        self._keep = None
-        self.reset(first_frame_id)
-
-    def reset(self, first_frame_id=1):
-        """one launch: empty tables, full free stack, the frame counter at `first_frame_id`, status 0"""
-        _lib.check(_lib.load().ph_dtracker_reset(self._h, int(first_frame_id), _lib.stream_ptr()), "ph_dtracker_reset")
-
-    def run(self, boxes, labels, counts, embeds, refuse=None, out=None):
-        """B frames in order: boxes fp32 [B, n, 5], labels int32 [B, n], counts int32 [B], embeds fp32 [B, n, 256], refuse int32 [B] or
-        None, contiguous on the device -> (kept int32 [B, max_dets], ids int64 [B, max_dets], kept_counts int32 [B]) on the device
-        (`out`: the same three, to write into); launches only"""
-        B, dev = counts.shape[0], self.device
-        for t, dt, nm in ((boxes, torch.float32, "boxes"), (labels, torch.int32, "labels"), (counts, torch.int32, "counts"),
-                          (embeds, torch.float32, "embeds")) + (((refuse, torch.int32, "refuse"),) if refuse is not None else ()):
-            if t.dtype != dt or not t.is_contiguous() or t.device != dev or t.shape[0] != B:
-                raise _lib.PolyheadError(f"NativeDeviceTracker.run: {nm} must be {dt} contiguous [{B}, ...] on {dev}")
-        if out is None:
-            out = (torch.empty((B, self.max_dets), dtype=torch.int32, device=dev), torch.empty((B, self.max_dets), dtype=torch.int64, device=dev),
-                   torch.empty((B,), dtype=torch.int32, device=dev))
-        io = self.io
-        io.boxes, io.box_stride = boxes.data_ptr(), boxes[0].numel()
-        io.labels, io.label_stride = labels.data_ptr(), labels[0].numel()
-        io.counts, io.count_stride = counts.data_ptr(), 1
-        io.refuse, io.refuse_stride = (None, 0) if refuse is None else (refuse.data_ptr(), 1)
-        io.embeds, io.embed_stride = embeds.data_ptr(), embeds[0].numel()
-        io.kept_out, io.ids_out, io.kept_counts = (o.data_ptr() for o in out)
-        self._keep = (boxes, labels, counts, embeds, refuse, out)      # alive until the launches have run (static under graph capture)
-        _lib.check(_lib.load().ph_dtracker_run(self._h, C.byref(io), B, _lib.stream_ptr()), "ph_dtracker_run")
-        return out
-
-    def _piece(self, offset, dtype, shape):
-        n = int(torch.tensor([], dtype=dtype).element_size()) * int(math.prod(shape))
-        return self.mem[int(offset):int(offset) + n].view(dtype).reshape(shape)
-
-    def status(self):
-        """the status record as a dict of ints (_lib.DTRK_STATUS); synchronises"""
-        return dict(zip(_lib.DTRK_STATUS, self._piece(self.layout.status, torch.int64, (_lib.PH_DTRK_ST_WORDS,)).cpu().tolist()))
-
-    def tables(self):
-        """the live tracklet rows in creation order (ids, labels, seen, boxes, slots, and `pool`: their embedding rows) plus the
-        backdrop generations, newest first, as host tensors; synchronises.  For tests and checkpointing"""
-        l, Cn, N, G = self.layout, self.capacity, self.max_dets, self.layout.generations
-        rows = self.status()["rows"]
-        tr = dict(ids=self._piece(l.trk_id, torch.int64, (Cn,))[:rows].cpu(), labels=self._piece(l.trk_label, torch.int32, (Cn,))[:rows].cpu(),
-                  seen=self._piece(l.trk_seen, torch.int64, (Cn,))[:rows].cpu(), boxes=self._piece(l.trk_box, torch.float32, (Cn, 5))[:rows].cpu(),
-                  slots=self._piece(l.trk_slot, torch.int32, (Cn,))[:rows].cpu())
-        pool = self._piece(l.pool, torch.float32, (Cn, 256))
-        tr["pool"] = pool[tr["slots"].long().to(self.device)].cpu()
-        counts = self._piece(l.bd_count, torch.int32, (G,)).cpu().tolist()
-        lab, slot, box = (self._piece(l.bd_label, torch.int32, (G, N)).cpu(), self._piece(l.bd_slot, torch.int32, (G, N)).cpu(),
-                          self._piece(l.bd_box, torch.float32, (G, N, 5)).cpu())
-        tr["backdrops"] = [dict(labels=lab[g, :c], slots=slot[g, :c], boxes=box[g, :c]) for g, c in enumerate(counts)]
-        return tr

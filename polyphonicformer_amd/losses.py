@@ -563,11 +563,7 @@ import ctypes as C  # noqa: E402
 import numpy as np  # noqa: E402
 
 
-class LossCfg(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("B", "N", "L", "P", "depth_rows", "seg_L", "has_rank", "ignore", "depth_mode")] + \
-               [("HW", C.c_int64)] + \
-               [(n, C.c_float) for n in ("lw_mask", "lw_dice", "dice_eps", "lw_rank", "lw_depth", "dw_si", "dw_sq", "dw_abs", "lw_cls",
-                                         "cls_gamma", "cls_alpha", "cls_avg", "lw_seg", "seg_gamma", "seg_alpha")]
+LossCfg = _lib.LossCfg                 # ph_loss_cfg
 
 
 class StepGT:

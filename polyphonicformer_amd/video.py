@@ -1,428 +1,16 @@
-"""Video association step (the consumer of the one multi-GPU exchange):
-drop-in for `QuasiDenseEmbedTracker` (polyphonic/video/qdtrack/trackers/quasi_dense_embed_tracker.py:8-207).
-
-The tracker is *host logic*: stateful, strictly sequential in frame order, data-dependent control flow over
-<= max_per_img detections and a memory of a few hundred rows.  This build keeps that memory as a struct of arrays
-(`_TrackTable`) and formulates de-duplication, affinity and greedy assignment as array operations; constructor
-kwargs, the `match(bboxes, labels, track_feats, frame_id)` signature / return value and the registry name are the
-reference's, and the integer ids are pinned to the reference class's own output (tests/golden/tracker.npz).
-With frames sharded over GPUs (`dist.shard_frames`) every rank all-gathers the per-frame records
-(`dist.allgather_track_records`) and replays `match` in frame order; integer track ids are then identical to the
-single-process run (`replay_tracking`, tests/test_tracker.py and tests/test_dist_gloo.py)."""
+"""Video inference after the heads: the per-frame association step of `PolyphonicVideo.simple_test`
+(`VideoAssociator`), the module-API frame pipeline (`VideoFramePipeline`) and the throughput form of the per-frame loop
+(`VideoStreamRunner`).  The trackers they drive live in tracker.py; `TRACKERS`, `QuasiDenseEmbedTracker`, `replay_tracking` and
+`bbox_overlaps` are re-exported here."""
 import dataclasses
 import os
 
 import numpy as np
 import torch
 
-from .registry import Registry
-
-TRACKERS = Registry("trackers")
-
-
-def _idx_to(dev, idx):
-    """a host index tensor to the device the embeddings live on: through pinned memory and asynchronously when that is a GPU
-    (six such transfers per frame in `match`; pageable ones cost 30-100 us each on the GPU box), a no-op on the CPU"""
-    if torch.device(dev).type != "cuda":
-        return idx
-    return idx.pin_memory().to(dev, non_blocking=True)
-
-
-def bbox_overlaps(b1, b2, eps=1e-6):
-    """IoU matrix of xyxy boxes [n,4] x [m,4] (what mmdet.core.bbox_overlaps(mode='iou') returns)"""
-    n, m = b1.shape[0], b2.shape[0]
-    if n == 0 or m == 0:
-        return b1.new_zeros((n, m))
-    x1 = torch.maximum(b1[:, None, 0], b2[None, :, 0])
-    y1 = torch.maximum(b1[:, None, 1], b2[None, :, 1])
-    x2 = torch.minimum(b1[:, None, 2], b2[None, :, 2])
-    y2 = torch.minimum(b1[:, None, 3], b2[None, :, 3])
-    inter = (x2 - x1).clamp(min=0) * (y2 - y1).clamp(min=0)
-    a1 = (b1[:, 2] - b1[:, 0]) * (b1[:, 3] - b1[:, 1])
-    a2 = (b2[:, 2] - b2[:, 0]) * (b2[:, 3] - b2[:, 1])
-    return inter / (a1[:, None] + a2[None, :] - inter).clamp(min=eps)
-
-
-def _iou_np(b1, b2, eps=1e-6):
-    """`bbox_overlaps` on numpy float32 arrays: the same fp32 operations in the same order (bit-identical values), at numpy's
-    per-call cost -- the tracker's bookkeeping is ~60 tiny array operations per frame"""
-    n, m = b1.shape[0], b2.shape[0]
-    if n == 0 or m == 0:
-        return np.zeros((n, m), dtype=np.float32)
-    x1 = np.maximum(b1[:, None, 0], b2[None, :, 0])
-    y1 = np.maximum(b1[:, None, 1], b2[None, :, 1])
-    x2 = np.minimum(b1[:, None, 2], b2[None, :, 2])
-    y2 = np.minimum(b1[:, None, 3], b2[None, :, 3])
-    inter = np.maximum(x2 - x1, np.float32(0)) * np.maximum(y2 - y1, np.float32(0))
-    a1 = (b1[:, 2] - b1[:, 0]) * (b1[:, 3] - b1[:, 1])
-    a2 = (b2[:, 2] - b2[:, 0]) * (b2[:, 3] - b2[:, 1])
-    return inter / np.maximum(a1[:, None] + a2[None, :] - inter, np.float32(eps))
-
-
-def _rows_to(dev, rows):
-    """numpy row indices -> an index tensor where the embeddings live"""
-    return _idx_to(dev, torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)))
-
-
-class _TrackTable:
-    """The tracker's memory as a struct of arrays: one row per live tracklet, in creation order (the order the
-    affinity columns are laid out in, which decides ties), plus the most recent frames' unmatched detections
-    ("backdrops", newest frame first).  Rows are updated / appended / expired with index operations; nothing here is
-    per-object Python state.  ids / boxes / labels / last-seen frames are numpy arrays on the host, the embeddings a torch
-    tensor on the device the track head left them on."""
-
-    def __init__(self, backdrop_frames):
-        self.ids = np.zeros((0,), dtype=np.int64)
-        self.box = np.zeros((0, 5), dtype=np.float32)
-        self.emb = torch.zeros((0, 0))                            # lives where the track head left its embeddings (device)
-        self.lab = np.zeros((0,), dtype=np.int64)
-        self.seen = np.zeros((0,), dtype=np.int64)                # frame a row was last matched in
-        self.backdrop_frames = backdrop_frames
-        self.backdrops = []                                       # [(box, emb, lab)], newest first
-
-    def __len__(self):
-        return int(self.ids.shape[0])
-
-    def columns(self):
-        """(ids, labels, embeds) of everything a detection can be matched to: tracklets, then backdrops (id -1)"""
-        ids, lab, emb = [self.ids], [self.lab], [self.emb]
-        for (bb, be, bl) in self.backdrops:
-            ids.append(np.full((be.shape[0],), -1, dtype=np.int64))
-            lab.append(bl)
-            emb.append(be)
-        emb = [e for e in emb if e.shape[0]]
-        return np.concatenate(ids), np.concatenate(lab), (torch.cat(emb, 0) if len(emb) > 1 else (emb[0] if emb else self.emb))
-
-    def absorb(self, ids, box, emb, lab, frame, momentum):
-        """matched detections refresh their rows (embedding = exponential moving average), unknown ids append rows"""
-        if ids.shape[0] == 0:
-            return
-        pos = {t: r for r, t in enumerate(self.ids.tolist())}
-        row = np.array([pos.get(t, -1) for t in ids.tolist()], dtype=np.int64)
-        old, new = row >= 0, row < 0
-        dev = emb.device
-        if old.any():
-            r = row[old]
-            rd = _rows_to(dev, r)
-            self.emb[rd] = (1 - momentum) * self.emb[rd] + momentum * emb[_rows_to(dev, np.flatnonzero(old))]
-            self.box[r], self.lab[r], self.seen[r] = box[old], lab[old], frame
-        if new.any():
-            k = int(new.sum())
-            self.ids = np.concatenate([self.ids, ids[new]])
-            self.box = np.concatenate([self.box, box[new]], 0)
-            self.emb = torch.cat([self.emb.reshape(-1, emb.shape[1]).to(dev), emb[_rows_to(dev, np.flatnonzero(new))]], 0)
-            self.lab = np.concatenate([self.lab, lab[new]])
-            self.seen = np.concatenate([self.seen, np.full((k,), frame, dtype=np.int64)])
-
-    def expire(self, frame, max_age):
-        live = (frame - self.seen) < max_age
-        if not live.all():
-            self.ids, self.box, self.emb, self.lab, self.seen = (self.ids[live], self.box[live],
-                                                                  self.emb[_rows_to(self.emb.device, np.flatnonzero(live))],
-                                                                  self.lab[live], self.seen[live])
-
-    def push_backdrop(self, box, emb, lab):
-        self.backdrops.insert(0, (box, emb, lab))
-        del self.backdrops[self.backdrop_frames:]
-        if self.backdrop_frames == 0:
-            self.backdrops = []
-
-
-@TRACKERS.register_module()
-class QuasiDenseEmbedTracker(object):
-    """Quasi-dense embedding tracker with the constructor kwargs, `match` signature and integer-id semantics of
-    polyphonic/video/qdtrack/trackers/quasi_dense_embed_tracker.py:8-207 (pinned by tests/golden/tracker.npz, which the
-    reference class produced).  This build's formulation: detections are de-duplicated with one triangular IoU test,
-    the memory is a `_TrackTable`, the affinity matrix is computed once and the greedy one-to-one assignment walks the
-    detections in score order with a `taken` mask over tracklet columns.  The reference also carries a per-tracklet
-    velocity that nothing reads (its `match` ignores `memo_vs`); it is not kept.
-    Where the arithmetic runs: boxes, labels, ids and the control flow on the host, as numpy float32 / int64 arrays (the same
-    IEEE operations as the torch CPU ops they replace -- same values, a third of the per-call cost; the frame's ~60 tiny array
-    operations were 0.6 ms of a 2 ms video frame); the EMBEDDINGS (detections and memory) stay on the device the track head
-    produced them on, and the [detections x memory] affinity matrix is computed there (`ph_track_affinity`, csrc/ph_track.hip)
-    -- one D2H of that matrix per frame feeds the greedy walk.  With CPU inputs (the CPU tests, gloo) the affinity runs as
-    torch CPU ops; no process-global state is touched either way."""
-
-    def __init__(self, init_score_thr=0.8, obj_score_thr=0.5, match_score_thr=0.5, memo_tracklet_frames=10,
-                 memo_backdrop_frames=1, memo_momentum=0.8, nms_conf_thr=0.5, nms_backdrop_iou_thr=0.3,
-                 nms_class_iou_thr=0.7, with_cats=True, match_metric='bisoftmax'):
-        if not (0 <= memo_momentum <= 1.0) or memo_tracklet_frames < 0 or memo_backdrop_frames < 0:
-            raise AssertionError("bad memo configuration")
-        if match_metric not in ('bisoftmax', 'softmax', 'cosine'):
-            raise AssertionError(f"unknown match_metric {match_metric}")
-        self.init_score_thr, self.obj_score_thr, self.match_score_thr = init_score_thr, obj_score_thr, match_score_thr
-        self.memo_tracklet_frames, self.memo_backdrop_frames = memo_tracklet_frames, memo_backdrop_frames
-        self.memo_momentum, self.nms_conf_thr = memo_momentum, nms_conf_thr
-        self.nms_backdrop_iou_thr, self.nms_class_iou_thr, self.with_cats = nms_backdrop_iou_thr, nms_class_iou_thr, with_cats
-        self.match_metric = match_metric
-        self._num_tracklets = 0
-        self.table = _TrackTable(memo_backdrop_frames)
-        self._native = None           # (handle, device memory, device): round 5, embeddings on a GPU -> csrc/ph_tracker.hip
-
-    @property
-    def num_tracklets(self):
-        if self._native is not None:
-            from . import _lib
-            return int(_lib.load().ph_tracker_num_tracklets(self._native[0]))
-        return self._num_tracklets
-
-    @num_tracklets.setter
-    def num_tracklets(self, v):
-        self._num_tracklets = v
-
-    @property
-    def empty(self):
-        if self._native is not None:
-            from . import _lib
-            return _lib.load().ph_tracker_rows(self._native[0]) == 0
-        return len(self.table) == 0
-
-    def __del__(self):
-        nat = getattr(self, "_native", None)
-        if nat is not None:
-            try:
-                from . import _lib
-                _lib.load().ph_tracker_destroy(nat[0])
-            except Exception:
-                pass
-
-    # -- the native form (embeddings on a GPU): one C call per frame ----------------------------------------------
-    NATIVE_CAPACITY, NATIVE_MAX_DETS = 4096, 128
-    native = True                 # False: the array form below also for GPU embeddings (tests compare the two)
-
-    def _native_handle(self, dev):
-        """the C++ tracker object of this stream (csrc/ph_tracker.hip), created on first use on the embeddings' device"""
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        if self._native is None:
-            if len(self.table) or self._num_tracklets:
-                raise _lib.PolyheadError("QuasiDenseEmbedTracker: a tracker that started on CPU embeddings cannot continue on the GPU")
-
-            class Cfg(C.Structure):
-                _fields_ = [(n, C.c_float) for n in ("init_score_thr", "obj_score_thr", "match_score_thr", "memo_momentum", "one_minus_momentum",
-                                                     "nms_conf_thr", "nms_backdrop_iou_thr", "nms_class_iou_thr")] + \
-                           [(n, C.c_int32) for n in ("memo_tracklet_frames", "memo_backdrop_frames", "with_cats", "metric")]
-            c = Cfg(self.init_score_thr, self.obj_score_thr, self.match_score_thr, self.memo_momentum, 1 - self.memo_momentum, self.nms_conf_thr,
-                    self.nms_backdrop_iou_thr, self.nms_class_iou_thr, self.memo_tracklet_frames, self.memo_backdrop_frames,
-                    1 if self.with_cats else 0, {'bisoftmax': 0, 'softmax': 1, 'cosine': 2}[self.match_metric])
-            nb = lib.ph_tracker_device_bytes(self.NATIVE_CAPACITY, self.NATIVE_MAX_DETS)
-            mem = torch.empty((nb,), dtype=torch.uint8, device=dev)
-            h = lib.ph_tracker_create(C.byref(c), _lib.ptr(mem), nb, self.NATIVE_CAPACITY, self.NATIVE_MAX_DETS)
-            if not h:
-                raise _lib.PolyheadError("ph_tracker_create failed: " + (lib.ph_last_error_string() or b"").decode())
-            self._native = (C.c_void_p(h), mem, dev)
-        if dev != self._native[2]:
-            raise _lib.PolyheadError("QuasiDenseEmbedTracker: the embeddings moved to another device mid-stream")
-        return self._native[0]
-
-    def native_ready(self, n, emb):
-        """True if `match` of n detections with these embeddings takes the native path"""
-        return bool(self.native and emb.is_cuda and n <= self.NATIVE_MAX_DETS and emb.shape[1] == 256
-                    and (self._native is not None or (len(self.table) == 0 and self._num_tracklets == 0)))
-
-    def match_frames(self, boxes, labels, embeds, first_frame_id):
-        """a step's frames in ONE native call (`ph_tracker_match_frames`): boxes [sum n, 5] float32 / labels [sum n] int64 numpy arrays
-        on the host, embeds: per frame a [n, 256] device tensor (frames without detections: n = 0, skipped like the reference's loop).
-        Returns per frame the int64 ids of its kept detections in `match`'s order, and the number of frames matched."""
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        nf = len(embeds)
-        counts = np.asarray([int(e.shape[0]) for e in embeds], dtype=np.int32)
-        tot = int(counts.sum())
-        dev = next((e.device for e in embeds if e.shape[0]), None)
-        if dev is None:
-            return [np.empty((0,), dtype=np.int64) for _ in embeds], 0
-        h = self._native_handle(dev)
-        embs = [e.detach().float().contiguous() for e in embeds]
-        ptrs = (C.c_void_p * nf)(*[e.data_ptr() if e.shape[0] else None for e in embs])
-        box = np.ascontiguousarray(boxes, dtype=np.float32)
-        lab = np.ascontiguousarray(labels, dtype=np.int64)
-        kept, ids, kc = np.empty((max(tot, 1),), dtype=np.int32), np.empty((max(tot, 1),), dtype=np.int64), np.empty((nf,), dtype=np.int32)
-        vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        m = lib.ph_tracker_match_frames(h, vp(box), vp(lab), ptrs, vp(counts), nf, int(first_frame_id), vp(kept), vp(ids), vp(kc), _lib.stream_ptr())
-        if m < 0:
-            _lib.check(m, "ph_tracker_match_frames")
-        o = np.concatenate([[0], np.cumsum(counts)])
-        return [ids[o[f]:o[f] + kc[f]].copy() for f in range(nf)], int(m)
-
-    def _match_native(self, bboxes, labels, track_feats, frame_id):
-        """csrc/ph_tracker.hip: bookkeeping in C++, embeddings in a device pool, per frame two small uploads, six launches and
-        ONE synchronising download (the [detections x memory] scores).  Same integer ids as the array form below."""
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        dev = track_feats.device
-        handle = self._native_handle(dev)
-        # boxes / labels: torch tensors (any device) or host numpy arrays (`replay_tracking` downloads a whole step's at once)
-        box = bboxes if isinstance(bboxes, np.ndarray) else bboxes.detach().cpu().float().numpy()
-        lab = labels if isinstance(labels, np.ndarray) else labels.detach().cpu().long().numpy()
-        box, lab = np.ascontiguousarray(box, dtype=np.float32), np.ascontiguousarray(lab, dtype=np.int64)
-        emb = track_feats.detach().float().contiguous()
-        n = box.shape[0]
-        kept, ids = np.empty((max(n, 1),), dtype=np.int32), np.empty((max(n, 1),), dtype=np.int64)
-        k = lib.ph_tracker_match(handle, box.ctypes.data_as(C.c_void_p), lab.ctypes.data_as(C.c_void_p), _lib.ptr(emb), n, int(frame_id),
-                                 kept.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), _lib.stream_ptr())
-        if k < 0:
-            _lib.check(k, "ph_tracker_match")
-        kept = kept[:k].astype(np.int64)
-        return torch.from_numpy(box[kept]), torch.from_numpy(lab[kept]), torch.from_numpy(ids[:k].copy())
-
-    # -- pieces of `match` ---------------------------------------------------------------------------------
-    def _dedup(self, box):
-        """a detection is dropped when ANY higher-scored detection (kept or not) overlaps it by more than the IoU
-        threshold of its own score class (:147-155).  box: numpy float32 [n, 5], descending score"""
-        f32 = np.float32
-        iou = _iou_np(box[:, :4], box[:, :4])
-        thr = np.where(box[:, 4] < f32(self.obj_score_thr), f32(self.nms_backdrop_iou_thr), f32(self.nms_class_iou_thr))
-        return ~(np.tril(iou, -1) > thr[:, None]).any(1), iou
-
-    def _affinity(self, emb, lab, memo_emb, memo_lab):
-        """[detections x memory columns] match scores (:165-182), returned on the host (torch fp32).  Labels: numpy or torch"""
-        lab, memo_lab = torch.as_tensor(lab), torch.as_tensor(memo_lab)
-        # the fused kernel keeps a detection row in one workgroup: n <= 128 detections, m <= 4096 memory columns (max_per_img is
-        # 100 and the memory a few hundred columns in the shipped configs).  Beyond that the same formula runs as torch ops ON
-        # THE DEVICE the embeddings live on (below) -- the reference has no limit, a long video must not abort mid-stream
-        if emb.is_cuda and emb.shape[0] <= 128 and memo_emb.shape[0] <= 4096:
-            from . import _lib
-            lib = _lib.load()
-            n, m = emb.shape[0], memo_emb.shape[0]
-            dev = emb.device
-            score = torch.empty((n, m), dtype=torch.float32, device=dev)
-            ws = torch.empty((lib.ph_track_affinity_workspace_bytes(n, m),), dtype=torch.uint8, device=dev)
-            metric = {'bisoftmax': 0, 'softmax': 1, 'cosine': 2}[self.match_metric]
-            # named, so that the four operands are alive (and distinct blocks of the caching allocator) until the launch is queued
-            e, me = emb.contiguous(), memo_emb.contiguous()
-            both = torch.cat([lab.reshape(-1), memo_lab.reshape(-1)]).to(torch.int32)          # ONE pinned transfer for both label vectors
-            both = both.to(dev) if both.is_cuda else both.pin_memory().to(dev, non_blocking=True)
-            l, ml = both[:n], both[n:]
-            _lib.check(lib.ph_track_affinity(_lib.ptr(e), _lib.ptr(l), _lib.ptr(me), _lib.ptr(ml), n, m, metric, 1 if self.with_cats else 0,
-                                             _lib.ptr(score), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "ph_track_affinity")
-            host = torch.empty((n, m), dtype=torch.float32, pin_memory=True)
-            host.copy_(score, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            return host
-        if self.match_metric == 'cosine':
-            unit = torch.nn.functional.normalize
-            s = unit(emb, p=2, dim=1) @ unit(memo_emb, p=2, dim=1).t()
-        else:
-            dot = emb @ memo_emb.t()
-            s = dot.softmax(dim=1)
-            if self.match_metric == 'bisoftmax':
-                s = (s + dot.softmax(dim=0)) / 2
-        if self.with_cats:
-            s = s * (lab.to(s.device)[:, None] == memo_lab.to(s.device)[None, :]).float()
-        return s.cpu()
-
-    def _assign(self, score, det_conf, memo_ids):
-        """greedy, in detection (score) order: best still-free column; a tracklet column is consumed by a confident
-        detection, a weak detection that resembles a tracklet is marked -2 (neither a new track nor a backdrop),
-        matches to backdrop columns assign nothing (:183-197).  numpy: score fp32 [n, m], det_conf fp32 [n], memo_ids int64 [m]"""
-        f32 = np.float32
-        n = score.shape[0]
-        out = np.full((n,), -1, dtype=np.int64)
-        taken = np.zeros(score.shape[1], dtype=bool)
-        match_thr, obj_thr, conf_thr = f32(self.match_score_thr), f32(self.obj_score_thr), f32(self.nms_conf_thr)
-        for i in range(n):
-            row = np.where(taken, f32(0), score[i])
-            j = int(row.argmax())                                  # first maximal column, like torch.max(0)
-            conf = row[j]
-            if not conf > match_thr or memo_ids[j] < 0:
-                continue
-            if det_conf[i] > obj_thr:
-                out[i] = memo_ids[j]
-                taken[j] = True
-            elif conf > conf_thr:
-                out[i] = -2
-        return out
-
-    def match(self, bboxes, labels, track_feats, frame_id, asso_tau=-1):
-        """bboxes [n,5] (x1,y1,x2,y2,score), labels [n], track_feats [n,256] -> (bboxes, labels, ids) of the kept
-        detections in descending-score order; ids >= 0 track, -1 unmatched, -2 suppressed."""
-        return self._match(bboxes, labels, track_feats, frame_id)
-
-    def _match(self, bboxes, labels, track_feats, frame_id):
-        if self.native and track_feats.is_cuda and bboxes.shape[0] <= self.NATIVE_MAX_DETS and bboxes.shape[1] == 5 and track_feats.shape[1] == 256 \
-                and (self._native is not None or (len(self.table) == 0 and self._num_tracklets == 0)):
-            return self._match_native(bboxes, labels, track_feats, frame_id)
-        if self._native is not None:
-            from . import _lib
-            # the native tracker owns the memory and the id counter from its first frame on: the array form below would start a second,
-            # empty state (ids from 0 again, colliding with live native ids) and the native memory would miss this frame
-            raise _lib.PolyheadError(f"QuasiDenseEmbedTracker: the native tracker has started and this frame does not fit it (device embeddings of "
-                                f"width 256, [n, 5] boxes, n <= {self.NATIVE_MAX_DETS}; got n = {bboxes.shape[0]}, boxes {tuple(bboxes.shape)}, "
-                                f"embeddings {tuple(track_feats.shape)} on {track_feats.device}); build the tracker with native=False for such streams")
-        box_t, lab_t, emb = bboxes.detach().cpu().float(), labels.detach().cpu().long(), track_feats.detach().float()   # emb: stays put
-        dev = emb.device
-        order = box_t[:, 4].sort(descending=True)[1].numpy()      # torch's order among equal scores (what the goldens were pinned with)
-        box, lab = box_t.numpy()[order], lab_t.numpy()[order]
-        keep, iou = self._dedup(box)
-        kept = order[keep]                                        # one gather of the embeddings for both steps
-        box, lab, emb = box[keep], lab[keep], emb[_rows_to(dev, kept)]
-        ids = np.full((box.shape[0],), -1, dtype=np.int64)
-        if box.shape[0] and not self.empty:
-            memo_ids, memo_lab, memo_emb = self.table.columns()
-            ids = self._assign(self._affinity(emb, lab, memo_emb, memo_lab).numpy(), box[:, 4], memo_ids)
-        born = (ids == -1) & (box[:, 4] > np.float32(self.init_score_thr))
-        k = int(born.sum())
-        ids[born] = np.arange(self._num_tracklets, self._num_tracklets + k, dtype=np.int64)
-        self._num_tracklets += k
-        self._remember(ids, box, emb, lab, frame_id, iou[keep][:, keep])
-        return torch.from_numpy(box), torch.from_numpy(lab), torch.from_numpy(ids)
-
-    def _remember(self, ids, box, emb, lab, frame_id, iou):
-        """:47-102: tracked detections go to the table; the still-unmatched ones that no higher-scored detection covers
-        become this frame's backdrops; tracklets unseen for `memo_tracklet_frames` frames are forgotten.  `iou`: the kept
-        detections' pairwise IoU (the de-duplication's matrix restricted to them -- the same values)"""
-        tracked = ids > -1
-        self.table.absorb(ids[tracked], box[tracked], emb[_rows_to(emb.device, np.flatnonzero(tracked))], lab[tracked], frame_id,
-                          self.memo_momentum)
-        loose = ids == -1
-        covered = (np.tril(iou, -1) > np.float32(self.nms_backdrop_iou_thr)).any(1)
-        bd = loose & ~covered
-        self.table.push_backdrop(box[bd], emb[_rows_to(emb.device, np.flatnonzero(bd))], lab[bd])
-        self.table.expire(frame_id, self.memo_tracklet_frames)
-
-
-def replay_tracking(records, tracker_cfg=None, tracker=None, first_count=1):
-    """records: [(frame_id, bboxes[n,5], labels[n], embeds[n,256])] of ALL frames (any order); replays `match` in
-    frame order like polyphonic_former_video.py:391-402 (frame_id = running count from 1, ids + 1, -1 -> 0).
-    A stream that arrives in batches passes its persistent `tracker` and `first_count` = 1 + the number of non-empty frames
-    replayed so far.  Returns {frame_id: ids tensor}."""
-    if tracker is None:
-        tracker = QuasiDenseEmbedTracker(**(tracker_cfg or {}))
-    out, cnt = {}, first_count
-    records = sorted(records, key=lambda r: r[0])
-    if records and all(r[1].is_cuda and r[2].is_cuda for r in records):
-        # device records (after an RCCL all-gather): ONE download of the step's boxes and labels instead of two per frame
-        ns = [int(r[1].shape[0]) for r in records]
-        if sum(ns):
-            bl = torch.cat([torch.cat([r[1].float(), r[2].float()[:, None]], 1) for r in records if r[1].shape[0]], 0).cpu().numpy()
-            o = np.cumsum([0] + ns)
-            records = [(r[0], bl[o[i]:o[i + 1], :5], bl[o[i]:o[i + 1], 5].astype(np.int64), r[3]) for i, r in enumerate(records)]
-    if records and all(isinstance(r[1], np.ndarray) and tracker.native_ready(r[1].shape[0], r[3]) for r in records):
-        # device embeddings, host boxes: the whole step in ONE native call (a Python round trip per frame was half of the 0.13 ms a
-        # frame's replay cost)
-        per_frame, matched = tracker.match_frames(np.concatenate([r[1] for r in records], 0) if records else None,
-                                                  np.concatenate([r[2] for r in records], 0), [r[3] for r in records], cnt)
-        for r, ids in zip(records, per_frame):
-            ids = ids + 1
-            ids[ids == -1] = 0
-            out[r[0]] = torch.from_numpy(ids)
-        return out
-    for fid, bb, lab, emb in records:
-        if bb.shape[0] > 0:
-            if isinstance(bb, np.ndarray) and not (tracker.native and emb.is_cuda and bb.shape[0] <= tracker.NATIVE_MAX_DETS):
-                bb, lab = torch.from_numpy(bb), torch.from_numpy(lab)
-            _, _, ids = tracker.match(bboxes=bb, labels=lab, track_feats=emb, frame_id=cnt)
-            cnt += 1
-            ids = ids + 1
-            ids[ids == -1] = 0
-        else:
-            ids = torch.zeros((0,), dtype=torch.long)
-        out[fid] = ids
-    return out
+from . import _lib, engine as E
+from .tracker import (TRACKERS, NativeDeviceTracker, QuasiDenseEmbedTracker, bbox_overlaps, native_tracker_cfg,  # noqa: F401
+                      painted_ids, replay_tracking)
 
 
 # ---- the per-frame association step of PolyphonicVideo.simple_test (polyphonic_former_video.py:359-405) ----------
@@ -443,7 +31,6 @@ def things_for_tracking(panoptic_seg, segments_info):
 
 def semantic_map(panoptic_seg, segments_info, num_thing_classes, num_stuff_classes):
     """get_semantic_seg (:436-440) as one table lookup; void = num_thing + num_stuff (uint8 like the reference)"""
-    import numpy as np
     lut = np.full(int(panoptic_seg.max()) + 1, num_thing_classes + num_stuff_classes, dtype=np.uint8)
     for s in segments_info:
         lut[s['id']] = s['category_id']
@@ -452,7 +39,6 @@ def semantic_map(panoptic_seg, segments_info, num_thing_classes, num_stuff_class
 
 def track_id_map(panoptic_seg, seg_ids, ids):
     """generate_track_id_maps (:442-451): float64 map, 0 = no track (the masks are `panoptic_seg == segment id`)"""
-    import numpy as np
     lut = np.zeros(int(panoptic_seg.max()) + 1, dtype=np.float64)
     for sid, tid in zip(seg_ids, ids):
         lut[sid] = float(tid)
@@ -474,6 +60,9 @@ class VideoAssociator:
     def __init__(self, track_head, tracker_cfg, num_thing_classes, num_stuff_classes, strides=(4, 8, 16, 32)):
         self.track_head, self.tracker_cfg = track_head, dict(tracker_cfg)
         self.num_thing_classes, self.num_stuff_classes, self.strides = num_thing_classes, num_stuff_classes, strides
+        self._dtracker = None                # `use_native_plan(device_tracker=True)`: the NativeDeviceTracker, from its first frame on
+        self._npack = None                   # (key, NativeTrackPack): the track head's weights as the native plans read them
+        self._nplans = {}                    # geometry -> NativeAssocPlan, one at a time
         self.init_tracker()
 
     native_plan, max_things, device_tracker = False, 100, False          # `use_native_plan`
@@ -495,11 +84,10 @@ class VideoAssociator:
         return self
 
     def _native_plan_for(self, levels, pan_dev, K):
-        from . import engine as E
         dev = pan_dev.device
         prec = E.PREC[self.track_head.precision]
-        ver = _lib_versions(self.track_head)
-        pk = self.__dict__.get("_npack")
+        ver = _lib.param_versions(self.track_head)
+        pk = self._npack
         if pk is None or pk[0] != (prec, str(dev), ver):
             tc = E.native_track_cfg(self.track_head)
             pk = self._npack = ((prec, str(dev), ver), E.native_track_pack(self.track_head, tc, dev))
@@ -520,29 +108,24 @@ class VideoAssociator:
         the device (the plan's static outputs: the next call overwrites them).  Reads no `segments_info`; one synchronisation for the
         tracker's boxes and labels, then the tracker's own."""
         if not self.native_plan:
-            from . import _lib
             raise _lib.PolyheadError("VideoAssociator.step_records needs use_native_plan(True)")
         K = (seg_records_dev.shape[1] - 1) // 5
         plan = self._native_plan_for(levels, pan_dev, K)
         plan.run(pan_dev, seg_records_dev, levels)
         if self.device_tracker:
             return plan.sem, plan.track(self._device_tracker_for(pan_dev.device), pan_dev)[0]
-        handle = self.tracker._native_handle(pan_dev.device)
-        trk, _, matched = plan.match(handle, pan_dev, self.cnt)
+        trk, _, matched = plan.match(self.tracker.native_tracker(pan_dev.device), pan_dev, self.cnt)
         self.cnt += matched
         return plan.sem, trk
 
     def _device_tracker_for(self, dev):
-        from . import engine as E
-        if self.__dict__.get("_dtracker") is None:
-            kw = {k: v for k, v in self.tracker_cfg.items() if k != "type"}
-            self._dtracker = E.NativeDeviceTracker(E.native_tracker_cfg(**kw), dev, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
+        if self._dtracker is None:
+            self._dtracker = NativeDeviceTracker(native_tracker_cfg(**self.tracker_cfg), dev, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
         return self._dtracker
 
     def device_status(self):
-        """the device tracker's status record (engine.NativeDeviceTracker.status; synchronises); None before its first frame"""
-        d = self.__dict__.get("_dtracker")
-        return None if d is None else d.status()
+        """the device tracker's status record (tracker.NativeDeviceTracker.status; synchronises); None before its first frame"""
+        return None if self._dtracker is None else self._dtracker.status()
 
     def frames_matched(self):
         """frames the tracker has matched since `init_tracker`; with the device tracker a synchronising read of its status record"""
@@ -557,11 +140,11 @@ class VideoAssociator:
         cfg.setdefault("type", "QuasiDenseEmbedTracker")         # the config's own dict (with `type`) or bare kwargs
         self.tracker = TRACKERS.build(cfg)                       # build_tracker(self.tracker_cfg), polyphonic_former_video.py:60
         self.cnt = 1
-        if self.__dict__.get("_dtracker") is not None:
+        if self._dtracker is not None:
             self._dtracker.reset(1)
 
     def record(self, fpn_feats, panoptic_seg, segments_info, pan_dev=None):
-        from . import track_head as T, engine as E
+        from . import track_head as T
         seg_ids, idxs, labels, score = things_for_tracking(panoptic_seg, segments_info)
         if not seg_ids:
             return seg_ids, None
@@ -618,30 +201,24 @@ class VideoAssociator:
         if early is not None:
             early(sem)
         seg_ids, rec = self.record(fpn_feats, None, segments_info, pan_dev)
-        ids = []
-        if rec is not None:
-            _, _, ids = self.tracker.match(bboxes=rec[0], labels=rec[1], track_feats=rec[2], frame_id=self.cnt)
-            self.cnt += 1
-            ids = ids + 1
-            ids[ids == -1] = 0
-            ids = ids.tolist()
-        return sem, self._trk_map_device(idx, segments_info, seg_ids, ids)
+        return sem, self._trk_map_device(idx, segments_info, seg_ids, self._match_ids(rec))
+
+    def _match_ids(self, rec):
+        """the tracker on one frame's record -> the painted ids as a list (none for a frame without things).
+        NB the reference sorts detections by score inside `match`; ids come back in that order (:142-145) and are
+        painted onto the masks in segment order (:403) -- mirrored as is"""
+        if rec is None:
+            return []
+        _, _, ids = self.tracker.match(bboxes=rec[0], labels=rec[1], track_feats=rec[2], frame_id=self.cnt)
+        self.cnt += 1
+        return painted_ids(ids).tolist()
 
     def step(self, fpn_feats, panoptic_seg, segments_info, depth_final, records_only=False):
         pan_dev = torch.from_numpy(panoptic_seg).to(fpn_feats[0].device)
         seg_ids, rec = self.record(fpn_feats, panoptic_seg, segments_info, pan_dev)
         if records_only:
             return seg_ids, rec
-        ids = []
-        if rec is not None:
-            # NB the reference sorts detections by score inside `match`; ids come back in that order (:142-145) and are
-            # painted onto the masks in segment order (:403) -- mirrored as is
-            _, _, ids = self.tracker.match(bboxes=rec[0], labels=rec[1], track_feats=rec[2], frame_id=self.cnt)
-            self.cnt += 1
-            ids = ids + 1
-            ids[ids == -1] = 0
-            ids = ids.tolist()
-        sem, trk = self._maps_on_device(pan_dev, segments_info, seg_ids, ids)
+        sem, trk = self._maps_on_device(pan_dev, segments_info, seg_ids, self._match_ids(rec))
         return [{"sem": sem, "track": trk, "depth": depth_final}]
 
 
@@ -659,6 +236,7 @@ class VideoFramePipeline:
     def __init__(self, rpn_head, roi_head, track_head, tracker_cfg, strides=(4, 8, 16, 32)):
         self.rpn_head, self.roi_head = rpn_head, roi_head
         self.assoc = VideoAssociator(track_head, tracker_cfg, roi_head.num_thing_classes, roi_head.num_stuff_classes, strides)
+        self._api_runners = {}               # `simple_test`: frame geometry -> its one-slot VideoStreamRunner, one at a time
 
     def init_tracker(self):
         self.assoc.init_tracker()
@@ -678,15 +256,13 @@ class VideoFramePipeline:
         their versions change.  PH_VIDEO_API_EAGER=1: the eager launches of rounds 1-4."""
         if x[0].shape[0] != 1:
             raise NotImplementedError("video inference is one frame at a time (samples_per_gpu = 1, as in the reference)")
-        import os
         if not records_only and x[0].is_cuda and not os.environ.get("PH_VIDEO_API_EAGER"):
             m = img_metas[0]
             key = (tuple(m["img_shape"]), tuple(m["ori_shape"]), tuple(m["batch_input_shape"]), tuple(tuple(t.shape) for t in x), x[0].dtype)
-            runners = self.__dict__.setdefault("_api_runners", {})
-            r = runners.get(key)
+            r = self._api_runners.get(key)
             if r is None:
-                runners.clear()                      # one geometry at a time: a runner owns GBs of plan buffers
-                r = runners[key] = VideoStreamRunner(self, dict(m), graph=True, pipelined=False)
+                self._api_runners.clear()            # one geometry at a time: a runner owns GBs of plan buffers
+                r = self._api_runners[key] = VideoStreamRunner(self, dict(m), graph=True, pipelined=False)
             return r.run_one(x)
         _, _, (panoptic_seg, segments_info), _, depth_final = self.heads(x, img_metas, rescale)[0]
         return self.assoc.step(x, panoptic_seg, segments_info, depth_final, records_only=records_only)
@@ -713,11 +289,6 @@ def build_video_pipeline_from_config(cfg):
         raise NotImplementedError(f"bbox_roi_extractor {ext!r}: libpolyhead implements SingleRoIExtractor(RoIAlign 7x7, sampling_ratio=2, 256 ch)")
     th = build_head(deep_cfg(model["track_head"]))
     return VideoFramePipeline(rpn_head, roi_head, th, deep_cfg(model["tracker"]), strides=tuple(ext["featmap_strides"]))
-
-
-def _lib_versions(module):
-    from . import _lib
-    return _lib.param_versions(module)
 
 
 def _h2d(values, dtype, dev):
@@ -822,7 +393,6 @@ class VideoStreamRunner:
         return n
 
     def _weight_versions(self):
-        from . import _lib
         return _lib.param_versions(self.pipe.rpn_head) + _lib.param_versions(self.pipe.roi_head)
 
     # -- slots ---------------------------------------------------------------------------------------------------
@@ -861,7 +431,6 @@ class VideoStreamRunner:
         return rpn2, roi2
 
     def _heads_device(self, sl, x):
-        from . import engine as E
         (proposal_feats, x_feats, mask_preds, cls_scores, seg_preds, depth_feats, depth_proposal, depth_pred,
          semantic_aspp_out) = sl.rpn.simple_test_rpn(x, self.metas * x[0].shape[0])
         o = sl.roi._decode(x_feats, proposal_feats, mask_preds, depth_feats, depth_proposal)
@@ -993,7 +562,6 @@ class VideoStreamRunner:
 
     # -- the queue -------------------------------------------------------------------------------------------------
     def _enter(self, mode):
-        from . import _lib
         if mode != self._mode and (self._launches or self._waiting or self._buf or self._clips):
             raise _lib.PolyheadError(f"VideoStreamRunner: {self._mode} are in flight; drain them (flush() / flush_record() / "
                                      f"records_end()) before asking for {mode}")
@@ -1138,7 +706,6 @@ class VideoStreamRunner:
         """whether every frame of a B-frame heads launch gets the bits of its own one-frame launch: the grades whose KernelHead runs
         the one-pass kernel (fp16 / bf16; the two-pass kernel's tile runs are sized by the batch, which regroups its fp32 partial
         sums -- 1e-6 differences) and heads left `frame_invariant`"""
-        from . import _lib, engine as E
         grade = E.KHEAD_PREC.get(getattr(self.pipe.rpn_head, "precision", None))
         return bool(grade in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) and not os.environ.get("PH_KHEAD_TWOPASS")
                     and getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False))
@@ -1194,7 +761,6 @@ class VideoStreamRunner:
     def records_end(self):
         """second half of `records`, for the OLDEST queued clip: merges / records launch by launch (the synchronising part); every slot
         it frees goes to the next waiting chunk at once -- of this clip or of the clip queued behind it"""
-        from . import _lib
         if not self._clips:
             raise _lib.PolyheadError("VideoStreamRunner.records_end(): no clip is queued (records_begin first)")
         out = []

@@ -2,8 +2,10 @@
 struct layout and shared constant as a C compiler sees them (one compiled program), every prototype's return and argument classes
 against its SIGNATURES row, the exported symbols, and what the example programs link.  A struct, constant or entry point added to
 one side only fails here."""
+import ast
 import ctypes as C
 import functools
+import glob
 import os
 import re
 import shutil
@@ -71,6 +73,19 @@ def test_every_structure_has_a_c_name():
     missing = [m.__name__ for m in mirrors if m not in _lib.STRUCTS.values()]
     assert not missing, f"ctypes.Structure classes of _lib without a _lib.STRUCTS entry: {missing}"
     assert len(set(_lib.STRUCTS.values())) == len(_lib.STRUCTS) == len(mirrors)
+
+
+def test_structures_are_defined_in_lib_only():
+    """a ctypes mirror defined anywhere else in the package escapes the two tests around this one"""
+    pkg = os.path.dirname(_lib.__file__)
+    stray = []
+    for path in sorted(glob.glob(os.path.join(pkg, "**", "*.py"), recursive=True)):
+        if os.path.samefile(path, _lib.__file__):
+            continue
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if isinstance(node, ast.ClassDef) and any("Structure" in ast.unparse(b) for b in node.bases):
+                stray.append(f"{os.path.relpath(path, pkg)}:{node.lineno} class {node.name}")
+    assert not stray, f"ctypes.Structure classes outside _lib.py (move them there, with a _lib.STRUCTS entry): {stray}"
 
 
 def test_struct_layouts_match_the_header():

@@ -4,14 +4,14 @@ kernel or touches device memory (tests/test_gpu_device_tracker.py does)."""
 import ctypes as C
 
 import helpers as Hh
-from polyphonicformer_amd import _lib, engine as E
+from polyphonicformer_amd import _lib, engine as E, tracker as TR
 
 FAKE_PTR = 1 << 40          # a 256-byte aligned address create() stores and never dereferences
 LEVELS = ((16, 32), (8, 16), (4, 8), (2, 4))
 
 
 def _cfg(**kw):
-    return E.native_tracker_cfg(**kw)
+    return TR.native_tracker_cfg(**kw)
 
 
 def al256(n):

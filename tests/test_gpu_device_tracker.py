@@ -1,5 +1,5 @@
 """GPU: the device tracker (csrc/ph_dtracker.hip: ph_dtracker_*, ph_assoc_plan_track) against the host-side native tracker
-(csrc/ph_tracker.hip through ph_tracker_match / ph_assoc_plan_match), the CPU form's tables (video._TrackTable) and the reference's
+(csrc/ph_tracker.hip through ph_tracker_match / ph_assoc_plan_match), the CPU form's tables (tracker._TrackTable) and the reference's
 goldens (tests/golden/tracker.npz) -- never against itself.  Everything is integer or bit equality: there is no tolerance here."""
 import ctypes as C
 import functools
@@ -11,7 +11,7 @@ import torch
 
 import helpers as Hh
 import test_gpu_native_assoc as NA
-from polyphonicformer_amd import _lib, engine as E, video as V
+from polyphonicformer_amd import _lib, tracker as TR, video as V
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -35,7 +35,7 @@ def _host_match(tr, bb, lab, emb_dev, frame_id):
     box, lb = np.ascontiguousarray(bb.numpy(), dtype=np.float32), np.ascontiguousarray(lab.numpy(), dtype=np.int64)
     n = box.shape[0]
     kept, ids = np.empty((max(n, 1),), dtype=np.int32), np.empty((max(n, 1),), dtype=np.int64)
-    k = lib.ph_tracker_match(tr._native_handle(emb_dev.device), box.ctypes.data_as(C.c_void_p), lb.ctypes.data_as(C.c_void_p), _lib.ptr(emb_dev), n,
+    k = lib.ph_tracker_match(tr.native_tracker(emb_dev.device).handle, box.ctypes.data_as(C.c_void_p), lb.ctypes.data_as(C.c_void_p), _lib.ptr(emb_dev), n,
                              int(frame_id), kept.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), _lib.stream_ptr())
     return k, kept[:max(k, 0)].tolist(), ids[:max(k, 0)].tolist()
 
@@ -86,7 +86,7 @@ def _device_stream(dt, tabs, per_call=1):
 
 
 def _dtracker(cfg, gpu, capacity=512, max_dets=128):
-    return E.NativeDeviceTracker(E.native_tracker_cfg(**cfg), gpu, capacity, max_dets)
+    return TR.NativeDeviceTracker(TR.native_tracker_cfg(**cfg), gpu, capacity, max_dets)
 
 
 def _painted(ids):
@@ -115,7 +115,7 @@ def test_reference_ids(gpu, metric):
         assert matched > 0 and -1 in flat and -2 in flat, (seed, matched)
         st = dt.status()
         assert (st["matched"], st["num_tracklets"], st["rows"], st["error"], st["refused_frame"], st["frame_id"]) == \
-            (len(recs), tr.num_tracklets, _lib.load().ph_tracker_rows(tr._native[0]), 0, -1, len(recs) + 1)
+            (len(recs), tr.num_tracklets, _lib.load().ph_tracker_rows(tr._native.handle), 0, -1, len(recs) + 1)
         if metric == "bisoftmax":
             for (f, _, _, _), (_, ids) in zip(recs, got):
                 assert np.array_equal(_painted(ids), z[f"s{seed}_f{f}_ids"]), (seed, f)
@@ -128,8 +128,8 @@ def _long_stream():
     recs = [r for s in range(8) for r in Hh.tracker_records(200 + s, nframes=2, nobj=120)]
     host, tr, cpu, max_m, max_n = _host_stream(_gold_cfg(), recs, gpu, capacity=512, cpu_form=True)
     torch.cuda.synchronize()
-    pool = tr._native[1][:512 * 1024].view(torch.float32).reshape(512, 256).cpu()
-    return dict(recs=recs, host=host, num=tr.num_tracklets, rows=_lib.load().ph_tracker_rows(tr._native[0]), table=cpu.table, pool=pool,
+    pool = tr._native.mem[:512 * 1024].view(torch.float32).reshape(512, 256).cpu()
+    return dict(recs=recs, host=host, num=tr.num_tracklets, rows=_lib.load().ph_tracker_rows(tr._native.handle), table=cpu.table, pool=pool,
                 max_m=max_m, max_n=max_n, tabs=_tables(recs, gpu, 128))
 
 
@@ -168,7 +168,7 @@ def _same(cfg, recs, gpu, **kw):
     got = _device_stream(dt, _tables(recs, gpu))
     assert got == host
     st = dt.status()
-    assert (st["num_tracklets"], st["rows"], st["error"]) == (tr.num_tracklets, _lib.load().ph_tracker_rows(tr._native[0]), 0)
+    assert (st["num_tracklets"], st["rows"], st["error"]) == (tr.num_tracklets, _lib.load().ph_tracker_rows(tr._native.handle), 0)
     return host, dt
 
 
@@ -293,18 +293,18 @@ def test_refuse_word_and_count_above_max_dets_are_status_words(gpu):
 
 # ---- 6. the whole step
 def _tcfg():
-    return E.native_tracker_cfg(**NA.TRACKER_CFG)
+    return TR.native_tracker_cfg(**NA.TRACKER_CFG)
 
 
 def test_whole_step_equals_the_host_path(gpu):
     w = NA._whole_step()
     pan, rec, levels = w["batch"]
     host_plan, host_tr = NA._plan("fp32", 3, (64, 128), 12, levels), V.QuasiDenseEmbedTracker(**NA.TRACKER_CFG)
-    plan, dt = NA._plan("fp32", 3, (64, 128), 12, levels), E.NativeDeviceTracker(_tcfg(), gpu, 512, 12)
+    plan, dt = NA._plan("fp32", 3, (64, 128), 12, levels), TR.NativeDeviceTracker(_tcfg(), gpu, 512, 12)
     first = 1
     for call in range(2):                                # the second call continues the stream
         host_plan.run(pan, rec, levels)
-        trk_h, ids_h, matched = host_plan.match(host_tr._native_handle(gpu), pan, first)
+        trk_h, ids_h, matched = host_plan.match(host_tr.native_tracker(gpu), pan, first)
         first += matched
         plan.run(pan, rec, levels)
         trk, ids = plan.track(dt, pan)
@@ -325,12 +325,12 @@ def test_run_and_track_in_one_graph_carry_the_state_across_replays(gpu):
     host_plan, host_tr, first, want = NA._plan("bf16", 2, hw, 8, batches[0][2]), V.QuasiDenseEmbedTracker(**NA.TRACKER_CFG), 1, []
     for pan, rec, levels in batches:
         host_plan.run(pan, rec, levels)
-        trk, ids, matched = host_plan.match(host_tr._native_handle(gpu), pan, first)
+        trk, ids, matched = host_plan.match(host_tr.native_tracker(gpu), pan, first)
         first += matched
         want.append((trk.clone(), ids.clone(), host_plan.sem.clone()))
     assert first == 5 and any(int(i.max()) > 0 for _, i, _ in want)
     pan, rec, levels = (batches[0][0].clone(), batches[0][1].clone(), [l.clone() for l in batches[0][2]])
-    plan, dt = NA._plan("bf16", 2, hw, 8, levels), E.NativeDeviceTracker(_tcfg(), gpu, 256, 8)
+    plan, dt = NA._plan("bf16", 2, hw, 8, levels), TR.NativeDeviceTracker(_tcfg(), gpu, 256, 8)
     plan.run(pan, rec, levels)                           # warm-up outside the capture
     plan.track(dt, pan)
     dt.reset(1)

@@ -320,7 +320,7 @@ def _whole_step():
     plan = _plan("fp32", 3, (64, 128), 12, levels)
     plan.run(pan, rec, levels)
     tr = V.QuasiDenseEmbedTracker(**TRACKER_CFG)
-    trk, ids, matched = plan.match(tr._native_handle(gpu), pan, 1)
+    trk, ids, matched = plan.match(tr.native_tracker(gpu), pan, 1)
     torch.cuda.synchronize()
     return dict(frames=frames, ref=ref, sem=plan.sem.cpu(), trk=trk.cpu(), ids=ids.clone(), matched=matched, things=plan.things.cpu(),
                 embeds=plan.embeds.cpu(), cnt=assoc.cnt, batch=(pan, rec, levels))

@@ -390,12 +390,48 @@ def test_native_tracker_pool_exhaustion_leaves_the_state_as_it_was(gpu):
     with pytest.raises(_lib.PolyheadError, match="pool exhausted"):
         a.match(bboxes=f2[0], labels=f2[1], track_feats=f2[2], frame_id=2)
     lib = _lib.load()
-    assert a.num_tracklets == 10 and lib.ph_tracker_rows(a._native[0]) == 10
+    assert a.num_tracklets == 10 and lib.ph_tracker_rows(a._native.handle) == 10
     f3 = frame(3, 4, 0.9)
     f3 = (f3[0] + torch.tensor([0, 9000, 0, 9000, 0], device=gpu), f3[1], f3[2])
     ra = a.match(bboxes=f3[0], labels=f3[1], track_feats=f3[2], frame_id=2)
     rb = b.match(bboxes=f3[0], labels=f3[1], track_feats=f3[2], frame_id=2)
     assert torch.equal(ra[2], rb[2]) and a.num_tracklets == b.num_tracklets == 14
+
+
+def test_native_host_tracker_owns_its_handle(gpu, monkeypatch):
+    """`tracker.NativeHostTracker` built directly: `match` gives the CPU array form's ids and kept rows, `rows` / `num_tracklets`
+    follow its table, `_destroy()` may run twice, and a QuasiDenseEmbedTracker that owns one goes away without a complaint"""
+    import gc
+    import json
+    import sys
+    import numpy as np
+    from polyphonicformer_amd import tracker as TR
+    cfg = json.loads(bytes(Hh.load_golden("tracker.npz")["cfg_json"]).decode())
+    frames = [(bb[:8], lab[:8], emb[:8]) for _, bb, lab, emb in Hh.tracker_records(1)[:3]]
+    own, cpu = TR.NativeHostTracker(TR.native_tracker_cfg(**cfg), gpu, 16, 8), TR.QuasiDenseEmbedTracker(**cfg)
+    assert own.handle.value and own.device == gpu and own.mem.is_cuda and (own.num_tracklets, own.rows) == (0, 0)
+    for cnt, (bb, lab, emb) in enumerate(frames, 1):
+        kept, ids = own.match(bb.numpy(), lab.numpy(), emb.to(gpu), cnt)
+        cbb, clab, cids = cpu.match(bboxes=bb, labels=lab, track_feats=emb, frame_id=cnt)
+        assert ids.dtype == np.int64 and np.array_equal(ids, cids.numpy()), (cnt, ids.tolist(), cids.tolist())
+        assert np.array_equal(bb.numpy()[kept], cbb.numpy()) and np.array_equal(lab.numpy()[kept], clab.numpy())
+        assert own.num_tracklets == cpu.num_tracklets > 0 and own.rows == len(cpu.table) > 0
+    own._destroy()
+    own._destroy()
+    assert own.handle is None
+
+    class Small(TR.QuasiDenseEmbedTracker):
+        NATIVE_CAPACITY, NATIVE_MAX_DETS = 16, 8
+
+    tr = Small(**cfg)
+    bb, lab, emb = frames[0]
+    tr.match(bboxes=bb.to(gpu), labels=lab.to(gpu), track_feats=emb.to(gpu), frame_id=1)
+    assert isinstance(tr._native, TR.NativeHostTracker) and tr.native_tracker(gpu) is tr._native and tr._native.handle.value
+    unraisable = []
+    monkeypatch.setattr(sys, "unraisablehook", unraisable.append)      # what a failing __del__ reports to
+    del tr
+    gc.collect()
+    assert not unraisable, unraisable
 
 
 def test_replay_of_a_step_in_one_native_call(gpu):

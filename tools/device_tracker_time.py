@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import helpers as Hh  # noqa: E402
 from native_assoc_time import CFG, K, N_STUFF, N_THING, frame  # noqa: E402
-from polyphonicformer_amd import engine as E, video as V  # noqa: E402
+from polyphonicformer_amd import engine as E, tracker as TR, video as V  # noqa: E402
 from polyphonicformer_amd.registry import HEADS  # noqa: E402
 import polyphonicformer_amd.track_head  # noqa: E402,F401
 
@@ -49,13 +49,13 @@ def main():
         cfg = E.native_assoc_cfg(B, (H, W), K, cap, N_THING, N_STUFF, [tuple(f.shape[-2:]) for f in levels], pack.cfg)
         plans = [E.NativeAssocPlan(pack, cfg, dev) for _ in range(3)]                  # host path, device path, captured device path
         host = V.QuasiDenseEmbedTracker(**CFG)
-        handle = host._native_handle(dev)
-        dts = [E.NativeDeviceTracker(E.native_tracker_cfg(**CFG), dev, 4096, 128) for _ in range(2)]
+        native = host.native_tracker(dev)
+        dts = [TR.NativeDeviceTracker(TR.native_tracker_cfg(**CFG), dev, 4096, 128) for _ in range(2)]
         cnt = [1]
 
         def run_match():
             plans[0].run(pans, recs, levels)
-            cnt[0] += plans[0].match(handle, pans, cnt[0])[2]
+            cnt[0] += plans[0].match(native, pans, cnt[0])[2]
 
         def run_track():
             plans[1].run(pans, recs, levels)
