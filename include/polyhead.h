@@ -629,18 +629,16 @@ int ph_conv_nhwc(const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, f
 int ph_gn_finalize(const float* partial, float* stats, int nwg, int groups, int64_t HW, float eps, int B, void* stream);
 int ph_gn_sum_planes(const float* const* ys, const float* const* stats, const float* const* gammas, const float* const* betas,
                      int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
-/* ph_gn_sum_cplanes: ph_gn_sum_planes with the result as CHANNEL planes [P][B][256][HWp] (zero in [HW, HWp)), the input format of
- * ph_neck_out_convs: conv_pred + the two aux convs (semantic_fpn.py:156-178,223-231; each 1x1 conv + GN + ReLU of the level sum)
+/* ph_neck_out_convs: conv_pred + the two aux convs (semantic_fpn.py:156-178,223-231; each 1x1 conv + GN + ReLU of the level sum)
  * in two passes over that sum -- statistics by recomputation, then normalise + ReLU + store -- without an fp32 conv output in
- * memory.  in_channels_last != 0: the sum is ph_gn_sum_planes' [P][B][HW][256] instead (a 64-pixel tile is 32 KiB of consecutive
+ * memory.  in_channels_last == 0: the sum as CHANNEL planes [P][B][256][HWp] (zero in [HW, HWp)); != 0: ph_gn_sum_planes'
+ * [P][B][HW][256] instead (a 64-pixel tile is 32 KiB of consecutive
  * bytes and its B fragments are plain 16-byte LDS reads: no transposition anywhere -- the form NeckPlan uses).
  * wplanes: 16-bit planes [P][3][256][256] (out, in) of the three conv weights; gn_affine fp32 [3][2][256];
  * out_planes_m: 16-bit planes [P][B][256][HWp] and / or out_f32_m: fp32 NCHW [B][256][HW], at least one per map;
  * workspace: ph_neck_out_convs_workspace_bytes(B, HW, groups).  Up to 3 frames per launch a frame's outputs are bit-identical to
  * those of a one-frame launch (tile runs and summation order do not depend on B). */
 size_t ph_neck_out_convs_workspace_bytes(int B, int64_t HW, int groups);
-int ph_gn_sum_cplanes(const float* const* ys, const float* const* stats, const float* const* gammas, const float* const* betas,
-                      int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
 int ph_neck_out_convs(const uint16_t* in_planes, int in_channels_last, const uint16_t* wplanes, const float* gn_affine, int groups,
                       float eps, uint16_t* out_planes0, uint16_t* out_planes1, uint16_t* out_planes2, float* out_f32_0,
                       float* out_f32_1, float* out_f32_2, void* workspace, size_t workspace_bytes, int B, int64_t HW, int prec,
@@ -886,6 +884,10 @@ typedef struct {
 size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg);     /* 0 on a bad cfg */
 int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_khead_plan** out);
 int ph_khead_plan_info(const ph_khead_plan* plan, ph_khead_geometry* out);
+/* the same answer without a plan: the geometry rule applied to a cfg (the only copy of that rule: engine.KernelHeadPlan takes
+ * onepass and nsplit from here).  Needs no pack and no workspace, but -- like ph_khead_plan_create -- the CURRENT DEVICE: the
+ * one-pass rule asks it for its CU count.  Every cfg error of ph_khead_plan_create comes back from here too. */
+int ph_khead_geometry_of(const ph_khead_cfg* cfg, ph_khead_geometry* out);
 void ph_khead_plan_destroy(ph_khead_plan* plan);
 
 /* ---- one a1 call.  Inputs f0 / f1 / f2: the neck's three maps, fp32 NCHW [B][256][H][W] (PH_IN_F32_NCHW) or 16-bit planes
@@ -932,10 +934,11 @@ int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
  * synchronisation and no host read of device data in pack / posenc / create / run, every argument or geometry error returned
  * before the first launch.  No ph_neck_plan_* / ph_neck_pack* / ph_neck_posenc function reads the environment: the plan's
  * launches go through internal forms of ph_conv_nhwc / ph_gn_sum_planes / ph_gn_apply that take their launch knobs as arguments
- * (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW / PH_CPLANES_TPW; ph_neck_out_convs
- * has no knobs), and what engine.NeckPlan reads from PH_NECK_OUT2 / PH_NECK_C16 /
- * PH_NECK_STREAMS are the cfg's `fused_out` / `c16` / `tower_buffers` fields (PH_NECK_OUT2=0 -> fused_out PH_KNOB_OFF,
- * PH_NECK_C16=0 -> c16 PH_KNOB_OFF, PH_NECK_STREAMS=0 -> tower_buffers 0; the measurement forms PH_NECK_OUT2=2 / 3 have no field).
+ * (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_CPLANES_TPW; ph_neck_out_convs
+ * has no knobs), and the Python side's PH_NECK_OUT2 / PH_NECK_C16 / PH_NECK_STREAMS arrive as the cfg's `fused_out` / `c16` /
+ * `tower_buffers` fields: engine.native_neck_cfg is the one place that reads them (PH_NECK_OUT2=0 -> fused_out PH_KNOB_OFF,
+ * PH_NECK_C16=0 -> c16 PH_KNOB_OFF, PH_NECK_STREAMS=0 -> tower_buffers 0), and engine.NeckPlan takes its choices from
+ * ph_neck_geometry_of of that cfg, so the Python plan and the native plan agree by construction.
  * A zero-initialised ph_neck_cfg plus the sizes, the mode, num_outs, pos_level and an emit flag is the module API's configuration.
  *   h, w         the four FPN level sizes, level 0 (stride 4) first: each level (n + 1) / 2 of the one before, and levels 2 and 3
  *                exactly 1/2 and 1/4 of level 1 (they reach it by x2 upsampling); otherwise PH_EUNSUPPORTED
@@ -946,7 +949,7 @@ int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
  *   pos_level    the level the positional encoding is added to (the module's cat_coors_level), 0 .. 3; -1: none
  *   emit_planes  1: ph_neck_io.out_planes are written;  emit_f32  1: ph_neck_io.out_f32 are written; at least one
  *   fused_out    PH_KNOB_AUTO: conv_pred + the aux convs as ONE ph_neck_out_convs when num_outs == 3, groups == 32 and the grade has
- *                one plane (engine.NeckPlan's rule with no environment variable set); PH_KNOB_ON: the same, PH_EUNSUPPORTED where
+ *                one plane; PH_KNOB_ON: the same, PH_EUNSUPPORTED where
  *                that says no; PH_KNOB_OFF: conv -> finalize -> apply per map (PH_NECK_OUT2=0 of the Python plan)
  *   c16          PH_KNOB_AUTO: chunk-major planes (PH_PLANES_C16) into level 0's stride-2 conv in one-plane grades;
  *                PH_KNOB_OFF: channels-last (PH_NECK_C16=0)
@@ -1026,6 +1029,10 @@ typedef struct {
 size_t ph_neck_plan_workspace_bytes(const ph_neck_cfg* cfg);       /* 0 on a bad cfg */
 int ph_neck_plan_create(const ph_neck_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_neck_plan** out);
 int ph_neck_plan_info(const ph_neck_plan* plan, ph_neck_geometry* out);
+/* the same answer without a plan: the geometry rule applied to a cfg (the only copy of that rule: engine.NeckPlan takes
+ * fused_out, c16 and tower_buffers from here).  Needs no device, no pack and no workspace; every cfg error of ph_neck_plan_create
+ * comes back from here too. */
+int ph_neck_geometry_of(const ph_neck_cfg* cfg, ph_neck_geometry* out);
 void ph_neck_plan_destroy(ph_neck_plan* plan);
 
 /* ---- one neck call.

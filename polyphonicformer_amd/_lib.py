@@ -316,8 +316,6 @@ SIGNATURES = {
     "ph_gn_finalize": (C.c_int, [_P, _P, _I, _I, _L, C.c_float, _I, _P]),
     "ph_gn_sum_planes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                    _I, _I, _P, _I, _L, _I, _P]),
-    "ph_gn_sum_cplanes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                    _I, _I, _P, _I, _L, _I, _P]),
     "ph_neck_out_convs_workspace_bytes": (C.c_size_t, [_I, _L, _I]),
     "ph_neck_out_convs": (C.c_int, [_P, _I, _P, _P, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _L, _I, _P]),
     "ph_gn_apply": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
@@ -349,6 +347,7 @@ SIGNATURES = {
     "ph_khead_plan_workspace_bytes": (C.c_size_t, [C.POINTER(KheadCfg)]),
     "ph_khead_plan_create": (C.c_int, [C.POINTER(KheadCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
     "ph_khead_plan_info": (C.c_int, [_P, C.POINTER(KheadGeometry)]),
+    "ph_khead_geometry_of": (C.c_int, [C.POINTER(KheadCfg), C.POINTER(KheadGeometry)]),
     "ph_khead_plan_destroy": (None, [_P]),
     "ph_khead_plan_run": (C.c_int, [_P, C.POINTER(KheadIO), _P]),
     "ph_khead_plan_status": (C.c_int, [_P, _P]),
@@ -362,6 +361,7 @@ SIGNATURES = {
     "ph_neck_plan_workspace_bytes": (C.c_size_t, [C.POINTER(NeckCfg)]),
     "ph_neck_plan_create": (C.c_int, [C.POINTER(NeckCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
     "ph_neck_plan_info": (C.c_int, [_P, C.POINTER(NeckGeometry)]),
+    "ph_neck_geometry_of": (C.c_int, [C.POINTER(NeckCfg), C.POINTER(NeckGeometry)]),
     "ph_neck_plan_destroy": (None, [_P]),
     "ph_neck_plan_run": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
     "ph_neck_plan_run_level": (C.c_int, [_P, _I, C.POINTER(NeckIO), _P]),

@@ -129,14 +129,13 @@ int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int ns
                             float* obj, float* dobj, float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                             size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream);
 
-// launch knobs of the neck's kernels (ph_neck.hip), in the same way: the public ph_conv_nhwc / ph_gn_sum_planes / ph_gn_sum_cplanes /
-// ph_gn_apply fill them from PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_GNSUM_TPW / PH_CPLANES_TPW; the native neck plan
+// launch knobs of the neck's kernels (ph_neck.hip), in the same way: the public ph_conv_nhwc / ph_gn_sum_planes /
+// ph_gn_apply fill them from PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_CPLANES_TPW; the native neck plan
 // (ph_neckplan.hip) passes the defaults.  0 = the built-in rule
 struct PhNeckKnobs {
     int conv_th = 0;             // PH_CONV_TH / PH_CONV_TH_NOW: forced output rows per conv tile (2 or 4; one-plane grades)
     int gnsum_wgs = 0;           // PH_GNSUM_WGS: workgroups per frame of ph_gn_sum_planes
-    int gnsum_tpw = 0;           // PH_GNSUM_TPW: 64-pixel tiles per workgroup of ph_gn_sum_cplanes
-    int cplanes_tpw = 0;         // PH_CPLANES_TPW: the same of ph_gn_apply's PH_GN_TO_CPLANES mode
+    int cplanes_tpw = 0;         // PH_CPLANES_TPW: 64-pixel tiles per workgroup of ph_gn_apply's PH_GN_TO_CPLANES mode
 };
 // rows per tile of a ph_conv_nhwc launch of this output size, grade and batch (2 or 4)
 int ph_conv_nhwc_tile_rows_k(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B);
@@ -144,8 +143,6 @@ int ph_conv_nhwc_k(const PhNeckKnobs& kn, const uint16_t* X, const uint16_t* Wp,
                    int ksize, int stride, int B, int H, int W, int prec, void* stream);
 int ph_gn_sum_planes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
                        const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
-int ph_gn_sum_cplanes_k(const PhNeckKnobs& kn, const float* const* ys, const float* const* stats, const float* const* gammas,
-                        const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec, void* stream);
 int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
                   int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream);
 

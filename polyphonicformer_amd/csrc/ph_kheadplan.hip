@@ -27,7 +27,8 @@ static int64_t param_numel(const ph_khead_cfg* c, int i) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// geometry: engine.KernelHeadPlan.__init__'s choices, with the environment replaced by the cfg's fields
+// geometry: resolve() is the ONE launch-geometry rule of a1 -- the native plan's and, through ph_khead_geometry_of,
+// engine.KernelHeadPlan's; the environment switches of the Python side arrive as the cfg's fields (engine.native_khead_cfg)
 struct KGeo {
     int B, H, W, Nq, n_seg, n_thing, n_stuff, N, Npad, NqPad, groups, prec, P, logit_dtype, logit_bytes, emit_f32, onepass, nsplit;
     int64_t HW, HWp;
@@ -216,11 +217,23 @@ extern "C" int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, v
     return PH_OK;
 }
 
-extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    const KGeo& g = p->g;
+static void fill_geometry(const KGeo& g, ph_khead_geometry* out) {
     out->onepass = g.onepass; out->nsplit = g.nsplit; out->N = g.N; out->Npad = g.Npad; out->HWp = (int32_t)g.HWp; out->P = g.P;
     out->prec = g.prec; out->n_stuff = g.n_stuff;
+}
+
+extern "C" int ph_khead_geometry_of(const ph_khead_cfg* cfg, ph_khead_geometry* out) {
+    KGeo g;
+    const int rc = resolve(cfg, g, "ph_khead_geometry_of", true);
+    if (rc) return rc;
+    PH_CHECK_ARG(out != nullptr, "null out");
+    fill_geometry(g, out);
+    return PH_OK;
+}
+
+extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out) {
+    PH_CHECK_ARG(p && out, "null plan or out");
+    fill_geometry(p->g, out);
     return PH_OK;
 }
 

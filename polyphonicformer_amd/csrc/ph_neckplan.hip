@@ -30,7 +30,8 @@ static const int kLevelFirst[4] = {0, 1, 2, 4}, kLevelConvs[4] = {1, 1, 2, 3};
 static inline int conv_taps(int c) { return c < NCONV_TOWERS ? 9 : 1; }
 
 // ---------------------------------------------------------------------------------------------
-// geometry: engine.NeckPlan.__init__'s choices, with the environment replaced by the cfg's fields
+// geometry: resolve() is the ONE launch-geometry rule of the neck -- the native plan's and, through ph_neck_geometry_of,
+// engine.NeckPlan's; the environment switches of the Python side arrive as the cfg's fields (engine.native_neck_cfg)
 struct NLevelBufs { size_t xa, xb, y, stats, partial; };
 struct NGeo {
     int B, h[4], w[4], Ho, Wo, groups, prec, P, num_outs, nconvs, pos_level, emit_planes, emit_f32, fused_out, c16, tower_buffers;
@@ -89,7 +90,7 @@ static int resolve(const ph_neck_cfg* c, NGeo& g, const char* fn) {
     g.eps = c->eps > 0.f ? c->eps : 1e-5f;
     g.nconvs = NCONV_TOWERS + g.num_outs;
     g.tower_buffers = c->tower_buffers;
-    // the recompute output stage: NeckPlan's rule with no PH_NECK_OUT2 set -- three maps, 32 groups, one plane
+    // the recompute output stage: three maps, 32 groups, one plane
     const bool can_fuse = g.num_outs == 3 && g.groups == 32 && g.P == 1;
     if (c->fused_out == PH_KNOB_ON && !can_fuse) {
         ph_set_error("%s: ph_neck_out_convs needs num_outs == 3, groups == 32 and a one-plane grade", fn);
@@ -281,19 +282,31 @@ extern "C" int ph_neck_plan_create(const ph_neck_cfg* cfg, const void* pack, voi
     return PH_OK;
 }
 
-extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    const NGeo& g = p->g;
+static void fill_geometry(const NGeo& g, ph_neck_geometry* out) {
     out->Ho = g.Ho; out->Wo = g.Wo; out->HWp = (int32_t)g.HWp; out->P = g.P; out->prec = g.prec; out->fused_out = g.fused_out;
     out->c16 = g.c16; out->tower_buffers = g.tower_buffers; out->nconvs = g.nconvs;
     for (int i = 0; i < NCONV_MAX; ++i) out->tile_rows[i] = g.tile_rows[i];
+}
+
+extern "C" int ph_neck_geometry_of(const ph_neck_cfg* cfg, ph_neck_geometry* out) {
+    NGeo g;
+    const int rc = resolve(cfg, g, "ph_neck_geometry_of");
+    if (rc) return rc;
+    PH_CHECK_ARG(out != nullptr, "null out");
+    fill_geometry(g, out);
+    return PH_OK;
+}
+
+extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) {
+    PH_CHECK_ARG(p && out, "null plan or out");
+    fill_geometry(p->g, out);
     return PH_OK;
 }
 
 extern "C" void ph_neck_plan_destroy(ph_neck_plan* p) { delete p; }
 
 // the plan's launches take their knobs from here, never from the environment: the defaults the public entry points use when no
-// PH_CONV_TH[_NOW] / PH_GNSUM_* / PH_CPLANES_TPW is set
+// PH_CONV_TH[_NOW] / PH_GNSUM_WGS / PH_CPLANES_TPW is set
 static const PhNeckKnobs kNeck{};
 
 // every pointer check of the three run calls, before any of them launches

@@ -85,11 +85,6 @@ class StagePack:
         self.prec = prec
 
 
-def plan_env_key():
-    """the environment switches a DecodePlan's kernel choice reads at construction: part of the module API's plan-cache key"""
-    return tuple(_os.environ.get(k) for k in ("PH_POOL_NSPLIT", "PH_CONV_UP2", "PH_CONV_POOLX", "PH_POOLX_NSPLIT", "PH_UP2_SHARED_WGS"))
-
-
 def default_nsplit(B, HW, frame_invariant=False):
     """pixel ranges per frame for the split-K pooling: PH_POOL_NSPLIT when set, else the library's rule (ph_pool_default_nsplit,
     csrc/ph_pool.hip, which also says what `frame_invariant` -- the split of a ONE-frame launch whatever B is -- buys)"""
@@ -286,9 +281,9 @@ class DecodePlan:
         # whether the final stage is conv + x2 upsample in one kernel (ph_dynconv_up2) -- is the library's choice: the rule and the
         # measurements behind its thresholds live in resolve() of csrc/ph_decode.hip, the same call a native plan is built from
         L = packs[0].num_classes
-        cfg = native_cfg(B, N, H, W, self.S, L, packs[0].lay.ffn_dim, self.mode, out_dtype, frame_invariant, shares_gpu, nsplit)
+        self.cfg = native_cfg(B, N, H, W, self.S, L, packs[0].lay.ffn_dim, self.mode, out_dtype, frame_invariant, shares_gpu, nsplit)
         geo = _lib.DecodeGeometry()
-        if _lib.load().ph_decode_geometry_of(C.byref(cfg), C.byref(geo)) != 0:
+        if _lib.load().ph_decode_geometry_of(C.byref(self.cfg), C.byref(geo)) != 0:
             raise _cfg_error("ph_decode_geometry_of")
         self.nsplit, self.nsplit_px, self.poolx, self.fused_up = geo.nsplit, geo.nsplit_px, bool(geo.poolx), bool(geo.fused_up)
         dev = torch.device(device)
@@ -802,9 +797,9 @@ class KernelHeadPlan(_KernelHeadPlanBase):
 
     def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
                  logit_dtype=torch.float32, onepass=None, frame_invariant=False):
-        """`onepass`: None = ph_khead_onepass whenever the geometry / grade allows it (and PH_KHEAD_TWOPASS is unset),
-        False = always the two-pass ph_khead_fused.  `logit_dtype`: fp32 (the reference API) or fp16 (one-pass form only)
-        for mask_preds / seg_preds / depth_pred."""
+        """`onepass`: None = ph_khead_onepass whenever the geometry / grade allows it (and native_khead_cfg's switch is unset),
+        True = the same, an error where it cannot run, False = always the two-pass ph_khead_fused.  `logit_dtype`: fp32 (the
+        reference API) or fp16 (one-pass form only) for mask_preds / seg_preds / depth_pred."""
         self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
         self.n_thing_cls, self.n_cls, self.cat_stuff = num_thing_classes, num_classes, cat_stuff
         self.Nq = pack.n_init
@@ -814,22 +809,24 @@ class KernelHeadPlan(_KernelHeadPlanBase):
         dev = torch.device(device)
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
         lib = _lib.load()
-        self.ws1 = None
-        self.onepass = False
-        if onepass is not False and not _os.environ.get("PH_KHEAD_TWOPASS") and pack.conv_frag is not None:
-            # the input format is only known at set_inputs: the fp32 form has the stricter condition (HW % 4 == 0)
-            self.onepass = bool(lib.ph_khead_onepass_supported(B, self.HW, pack.groups, prec, _lib.PH_IN_F32_NCHW))
-        if onepass and not self.onepass:
-            raise _lib.PolyheadError("ph_khead_onepass does not support this geometry / grade")
-        if logit_dtype != torch.float32 and not self.onepass:
-            raise _lib.PolyheadError("16-bit KernelHead logits need the one-pass form")
+        # one pass or two and the pooling's pixel split are the library's choice: the rule lives in resolve() of
+        # csrc/ph_kheadplan.hip, the same call a native plan is built from (it asks the current device for its CU count)
+        self.cfg = native_khead_cfg(B, H, W, pack.n_init, pack.n_seg, num_thing_classes, cat_stuff, pack.groups, prec, logit_dtype,
+                                    want_f32, frame_invariant, onepass, nsplit)
+        geo = _lib.KheadGeometry()
+        with torch.cuda.device(dev):
+            if lib.ph_khead_geometry_of(C.byref(self.cfg), C.byref(geo)) != 0:
+                raise _cfg_error("ph_khead_geometry_of")
+        self.onepass, self.nsplit = bool(geo.onepass), geo.nsplit
+        if self.onepass and pack.conv_frag is None:
+            raise _lib.PolyheadError("ph_khead_onepass needs the pack's conv fragments (a one-plane grade)")
         self.logit_dtype = logit_dtype
+        self.ws1 = None
         if self.onepass:
             # hand-off state of the persistent launch; zeroed ONCE (its last 256 bytes are the sticky time-out words, which the
             # calls never clear)
             self.ws1 = torch.zeros((lib.ph_khead_onepass_workspace_bytes(B, self.HW),), dtype=torch.uint8, device=dev)
         self._alloc_io(2 if prec == _lib.PH_PREC_SPLIT else 1, pack.n_seg, want_f32, logit_dtype, dev)
-        self.nsplit = nsplit or default_nsplit(B, self.HW, frame_invariant)     # (see DecodePlan: the one-frame split at any B)
         self.partial = e((B, self.nsplit, n_padded(self.Nq), 512), torch.float32)
         # the two-pass kernels' workspace: the path itself, or the in-call fallback of a one-pass launch that gave up
         self.ws = e((lib.ph_khead_workspace_bytes(B, self.HW, pack.groups),), torch.uint8)
@@ -908,8 +905,9 @@ _KHEAD_MODE_OF_PREC = {_lib.PH_PREC_F16: "fp16", _lib.PH_PREC_BF16: "bf16", _lib
 
 def native_khead_cfg(B, H, W, num_proposals, num_classes, num_thing_classes, cat_stuff, groups, prec, logit_dtype=torch.float32,
                      want_f32=True, frame_invariant=False, onepass=None, nsplit=None):
-    """the ph_khead_cfg of the KernelHeadPlan that the same arguments (and the same environment) would build: the switches
-    KernelHeadPlan reads from the environment (PH_KHEAD_TWOPASS, PH_POOL_NSPLIT) become cfg fields -- the native plan reads none.
+    """the ph_khead_cfg of an a1 plan, Python or native: the ONE place that reads the plans' environment switches
+    (PH_KHEAD_TWOPASS, PH_POOL_NSPLIT), which become the cfg's explicit fields.  KernelHeadPlan asks the library for its geometry
+    with it (ph_khead_geometry_of), NativeKernelHeadPlan creates its plan from it, so the two agree by construction.
     `prec`: a precision name (engine.KHEAD_PREC's keys) or a1's grade code; `num_classes`: the rows of conv_seg"""
     name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
     env = _os.environ.get
@@ -1044,15 +1042,6 @@ def gn_sum_planes(ys, stats, pks, groups, planes, B, HW, prec):
                                     _lib.ptr(planes), B, HW, prec, _lib.stream_ptr()), "ph_gn_sum_planes")
 
 
-def gn_sum_cplanes(ys, stats, pks, groups, planes, B, HW, prec):
-    """the level sum as channel planes [P,B,256,HWp] (ph_neck_out_convs' input)"""
-    lib = _lib.load()
-    n = len(ys)
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    _lib.check(lib.ph_gn_sum_cplanes(arr(ys), arr(stats), arr([p["gamma"] for p in pks]), arr([p["beta"] for p in pks]), n, groups,
-                                     _lib.ptr(planes), B, HW, prec, _lib.stream_ptr()), "ph_gn_sum_cplanes")
-
-
 def neck_out_convs(planes, channels_last, wplanes, gn_affine, groups, out_planes, out_f32, ws, B, HW, prec, eps=1e-5):
     """conv_pred + 2 aux convs (1x1 conv + GN + ReLU each) of the level sum `planes` ([P,B,HW,256] when channels_last, else channel
     planes [P,B,256,HWp]); out_planes / out_f32: lists of 3 (None: not wanted)"""
@@ -1068,26 +1057,25 @@ class NeckPlan:
     """buffers + launch sequence of SemanticFPNWrapper.forward for one (B, level shapes): channels-last bf16 planes
     between the convs, fp32 channels-last conv outputs (one per level for the fused level sum), three fp32 NCHW outputs"""
 
-    def __init__(self, B, shapes, prec, device, tower_streams=True):
-        self.B, self.shapes, self.prec = B, shapes, prec
+    def __init__(self, B, shapes, prec, device, tower_streams=True, groups=32, num_outs=3):
+        self.B, self.shapes, self.prec, self.groups, self.num_outs = B, shapes, prec, groups, num_outs
         P = 2 if prec == _lib.PH_PREC_SPLIT else 1
         dev = torch.device(device)
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
-        (h0, w0), (h1, w1) = shapes[0], shapes[1]
-        self.Ho, self.Wo = h1, w1                                  # stride-8 output size
-        if ((h0 + 1) // 2, (w0 + 1) // 2) != (h1, w1) or any(shapes[i + 1] != ((shapes[i][0] + 1) // 2, (shapes[i][1] + 1) // 2)
-                                                             for i in range(1, 3)):
-            raise _lib.PolyheadError(f"FPN level sizes {shapes} are not a stride-2 pyramid")
-        # levels 2 and 3 reach the output size by x2 upsampling; checked here as well as in `_tower`, whose check comes after an upsample
-        # launch that would write (2h, 2w) pixels into an (Ho, Wo) buffer
-        if (2 * shapes[2][0], 2 * shapes[2][1]) != (h1, w1) or (4 * shapes[3][0], 4 * shapes[3][1]) != (h1, w1):
-            raise _lib.PolyheadError("level does not end at the stride-8 size")
+        lib = _lib.load()
+        # the tower-stream form, the fused output stage and level 0's plane layout are the library's choice, and so is the check of
+        # the level sizes (a stride-2 pyramid whose levels 2 and 3 reach the stride-8 size by x2 upsampling): the rule lives in
+        # resolve() of csrc/ph_neckplan.hip, the same call a native plan is built from
+        self.cfg = native_neck_cfg(B, shapes, groups, prec, num_outs, tower_streams=tower_streams, device_type=dev.type)
+        geo = _lib.NeckGeometry()
+        if lib.ph_neck_geometry_of(C.byref(self.cfg), C.byref(geo)) != 0:
+            raise _cfg_error("ph_neck_geometry_of")
+        self.Ho, self.Wo = geo.Ho, geo.Wo                          # stride-8 output size
         big = max(h * w for h, w in shapes)
         self.xa = e((P, B, big, 256), torch.int16)                 # conv input planes (ping)
         self.xb = e((P, B, self.Ho * self.Wo, 256), torch.int16)   # conv input planes (pong, <= output size)
         self.ys = [e((B, self.Ho * self.Wo, 256), torch.float32) for _ in range(4)]   # last conv output of each level
         self.y = e((B, self.Ho * self.Wo, 256), torch.float32)     # other conv outputs (pre-norm)
-        lib = _lib.load()
         self.partial = e((lib.ph_conv_nhwc_partial_floats(B, self.Ho, self.Wo),), torch.float32)
         self.lstats = [e((B, 256, 2), torch.float32) for _ in range(4)]
         self.stats = e((B, 256, 2), torch.float32)
@@ -1095,13 +1083,8 @@ class NeckPlan:
         self.pouts = None                                          # plane outputs, allocated on first use
         # Round 3: the four level towers are independent until the level sum and the small ones leave most of the chip idle
         # (a 3x3 conv at 16 x 32 x 16 frames is 32 workgroups): each tower gets its own buffers and its own HIP stream, the
-        # small launches run beside the stride-4 level's ingest + stride-2 conv.  PH_NECK_STREAMS=0 or the module attribute
-        # `tower_streams = False`: one stream, shared buffers (needed when TWO pipelines are captured into one HIP graph: the
-        # nested fork / join of 2 x 4 streams made hipStreamEndCapture segfault on ROCm 7.2).
-        # (from 4 frames per call: one frame at a time -- the video loop -- is bound by the host's launch rate, where the stream
-        # switches cost more than the overlap returns: cfg4 7.95 -> 9.08 ms per two frames with tower streams)
-        _ns = _os.environ.get("PH_NECK_STREAMS", "1")
-        self.multi = tower_streams and (B >= 4 or _ns == "2" or tower_streams == "always") and _ns != "0" and dev.type == "cuda"
+        # small launches run beside the stride-4 level's ingest + stride-2 conv (native_neck_cfg says when)
+        self.multi = bool(geo.tower_buffers)
         self.lv = None
         if self.multi:
             self.lv = []
@@ -1114,16 +1097,14 @@ class NeckPlan:
         self._streams = None                                       # created on first use; not part of a copy of the plan
         self.skip_ingest = False                                   # set around a capture whose replays follow `ingest_frames`
         # Round 4: the three output convs (conv_pred + 2 aux convs) as stats / apply passes over the level sum in channel planes
-        # (ph_neck_out_convs) instead of conv -> fp32 NHWC -> finalize -> apply per map.  PH_NECK_OUT2=0: the per-map form.
-        # one-plane grades only: with hi / lo planes the recompute pass is three MFMAs per product and costs more than the fp32
-        # round trip it removes (whole head 19.1 -> 20.4 ms per 16 frames at the parity grade, same box)
-        self.out2 = _os.environ.get("PH_NECK_OUT2", "1") != "0" and (P == 1 or _os.environ.get("PH_NECK_OUT2") == "3")
-        self.sc = self.ws2 = None
-        self.out2_cplanes = _os.environ.get("PH_NECK_OUT2", "1") == "2"
-        if self.out2:
-            if self.out2_cplanes:
-                self.sc = e((P, B, 256, hw_padded(self.Ho * self.Wo)), torch.int16)
-            self.ws2 = e((lib.ph_neck_out_convs_workspace_bytes(B, self.Ho * self.Wo, 32) // 4 + 64,), torch.float32)
+        # (ph_neck_out_convs) instead of conv -> fp32 NHWC -> finalize -> apply per map.  Three maps, 32 groups and one-plane grades
+        # only: with hi / lo planes the recompute pass is three MFMAs per product and costs more than the fp32 round trip it removes
+        # (whole head 19.1 -> 20.4 ms per 16 frames at the parity grade, same box)
+        self.out2 = bool(geo.fused_out)
+        self.ws2 = e((lib.ph_neck_out_convs_workspace_bytes(B, self.Ho * self.Wo, 32) // 4 + 64,), torch.float32) if self.out2 else None
+        # a level that starts with the stride-2 conv (level 0) hands it chunk-major planes (PH_PLANES_C16: the kernel's 16-channel
+        # stages then read whole lines; else channels-last); one-plane grades
+        self.c16 = _lib.PH_PLANES_C16 if geo.c16 else 0
 
     def __getstate__(self):
         d = dict(self.__dict__)
@@ -1147,10 +1128,7 @@ class NeckPlan:
         H, W = self.shapes[lvl]
         xa, xb, y, stats, partial = bufs["xa"], bufs["xb"], bufs["y"], bufs["stats"], bufs["partial"]
         convs = pk["levels"][lvl]
-        # a level that starts with the stride-2 conv (level 0) hands it chunk-major planes (PH_PLANES_C16: the kernel's 16-channel
-        # stages then read whole lines; PH_NECK_C16=0: channels-last, A/B timing)
-        c16 = _lib.PH_PLANES_C16 if (convs[0]["s"] == 2 and convs[0]["k"] == 3 and prec != _lib.PH_PREC_SPLIT
-                                     and _os.environ.get("PH_NECK_C16", "1") != "0") else 0
+        c16 = self.c16 if (convs[0]["s"] == 2 and convs[0]["k"] == 3) else 0      # the plan's layout into a stride-2 3x3 first conv
         if not self.skip_ingest:
             nhwc_ingest(feat, posenc, prec | c16, xa)
         src = xa
@@ -1180,7 +1158,7 @@ class NeckPlan:
         lib, st = _lib.load(), _lib.stream_ptr()
         for lvl, (h, w) in enumerate(self.shapes):
             convs = pk["levels"][lvl]
-            c16 = _lib.PH_PLANES_C16 if (convs[0]["s"] == 2 and convs[0]["k"] == 3 and _os.environ.get("PH_NECK_C16", "1") != "0") else 0
+            c16 = self.c16 if (convs[0]["s"] == 2 and convs[0]["k"] == 3) else 0
             xa = self.lv[lvl]["xa"]
             add = _lib.ptr(posenc) if lvl == pos_level and posenc is not None else None
             for b, f in enumerate(frames):
@@ -1192,6 +1170,9 @@ class NeckPlan:
 
     def run(self, feats, pk, groups, posenc, pos_level, to_planes=False):
         B, prec = self.B, self.prec
+        if len(pk["outs"]) != self.num_outs or groups != self.groups:
+            raise _lib.PolyheadError(f"NeckPlan.run: the plan was built for {self.num_outs} output convs and {self.groups} groups, "
+                                     f"not {len(pk['outs'])} and {groups}")
         if self.multi:
             if self._streams is None:
                 self._streams = [torch.cuda.Stream(device=self.xa.device) for _ in range(4)]
@@ -1211,18 +1192,14 @@ class NeckPlan:
             P = 2 if prec == _lib.PH_PREC_SPLIT else 1
             self.pouts = [torch.empty((P, B, 256, hw_padded(self.Ho * self.Wo)), dtype=torch.int16, device=self.xa.device)
                           for _ in range(3)]
-        if self.out2 and len(pk["outs"]) == 3 and groups == 32:
-            # level sum (channels-last planes, as before); statistics pass (three maps in one launch) + finalize + one apply launch
-            # per map.  PH_NECK_OUT2=2: through channel planes (ph_gn_sum_cplanes; the transposing sum is 0.2 ms slower per 16 frames)
-            if self.out2_cplanes:
-                gn_sum_cplanes(self.ys, self.lstats, [pk["levels"][l][-1] for l in range(4)], groups, self.sc, B, self.Ho * self.Wo, prec)
-            else:
-                gn_sum_planes(self.ys, self.lstats, [pk["levels"][l][-1] for l in range(4)], groups, self.xb, B, self.Ho * self.Wo, prec)
-            neck_out_convs(self.sc if self.out2_cplanes else self.xb, not self.out2_cplanes, pk["outs_w"], pk["outs_gn"], groups,
+        # sum over levels of ReLU(GN(.)) straight to conv input planes (channels-last)
+        gn_sum_planes(self.ys, self.lstats, [pk["levels"][l][-1] for l in range(4)], groups, self.xb, B, self.Ho * self.Wo, prec)
+        if self.out2:
+            # statistics pass (three maps in one launch) + finalize + one apply launch per map
+            neck_out_convs(self.xb, True, pk["outs_w"], pk["outs_gn"], groups,
                            self.pouts if to_planes else None, None if to_planes else self.outs, self.ws2, B, self.Ho * self.Wo, prec)
             return self.pouts if to_planes else self.outs
-        # sum over levels of ReLU(GN(.)) straight to conv input planes, then conv_pred / aux convs -> fp32 NCHW
-        gn_sum_planes(self.ys, self.lstats, [pk["levels"][l][-1] for l in range(4)], groups, self.xb, B, self.Ho * self.Wo, prec)
+        # conv_pred / aux convs -> fp32 NCHW
         for i, c in enumerate(pk["outs"]):
             self._conv_gn(self.xb, c, self.Ho, self.Wo, groups, self.y, self.stats)
             if to_planes:       # bf16 channel planes, the decode path's feature format (KernelHead hand-off)
@@ -1235,20 +1212,26 @@ class NeckPlan:
 # ---- the neck as a native object (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs) ------------------------------
 def native_neck_cfg(B, shapes, groups, prec, num_outs=3, pos_level=3, to_planes=False, tower_streams=True, fused_out=None, c16=None,
                     device_type="cuda"):
-    """the ph_neck_cfg of the NeckPlan that the same arguments (and the same environment) would build: the switches NeckPlan reads
-    from the environment (PH_NECK_OUT2=0, PH_NECK_C16=0, PH_NECK_STREAMS) become cfg fields -- the native plan reads none.
+    """the ph_neck_cfg of a neck plan, Python or native: the ONE place that reads the plans' environment switches (PH_NECK_OUT2=0,
+    PH_NECK_C16=0, PH_NECK_STREAMS), which become the cfg's explicit fields.  NeckPlan asks the library for its geometry with it
+    (ph_neck_geometry_of), NativeNeckPlan creates its plan from it, so the two agree by construction.
     `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `shapes`: the four level sizes; `pos_level`: None / -1 for
     no positional encoding; `fused_out` / `c16`: None = the environment's choice, else True (fused_out only) / False"""
     name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
     env = _os.environ.get
     out2 = env("PH_NECK_OUT2", "1")
     if out2 in ("2", "3"):
-        raise _lib.PolyheadError("PH_NECK_OUT2=2 / 3 are measurement forms of the Python NeckPlan; the native neck plan has none")
+        raise _lib.PolyheadError("PH_NECK_OUT2=2 / 3: these measurement forms of the neck's output stage were removed (both were slower)")
     if fused_out and out2 == "0":
         raise _lib.PolyheadError("ph_neck_out_convs asked for while PH_NECK_OUT2=0 is set")
     fo = _lib.PH_KNOB_OFF if (fused_out is False or out2 == "0") else (_lib.PH_KNOB_ON if fused_out else _lib.PH_KNOB_AUTO)
     cc = _lib.PH_KNOB_OFF if (c16 is False or env("PH_NECK_C16", "1") == "0") else _lib.PH_KNOB_AUTO
-    ns = env("PH_NECK_STREAMS", "1")           # NeckPlan's `multi`
+    # the four level towers with their own buffers, each on its own stream (NeckPlan.__init__): from 4 frames per call -- one frame
+    # at a time (the video loop) is bound by the host's launch rate, where the stream switches cost more than the overlap returns
+    # (cfg4 7.95 -> 9.08 ms per two frames with tower streams).  PH_NECK_STREAMS=0 or the module attribute `tower_streams = False`:
+    # one stream, shared buffers (needed when TWO pipelines are captured into one HIP graph: the nested fork / join of 2 x 4 streams
+    # made hipStreamEndCapture segfault on ROCm 7.2); PH_NECK_STREAMS=2 or tower_streams = "always": at any B
+    ns = env("PH_NECK_STREAMS", "1")
     multi = bool(tower_streams) and (B >= 4 or ns == "2" or tower_streams == "always") and ns != "0" and device_type == "cuda"
     if len(shapes) != 4:
         raise _lib.PolyheadError("the neck takes four FPN levels")

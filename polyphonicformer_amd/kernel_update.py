@@ -96,9 +96,10 @@ class KernelUpdateIterHead(nn.Module):
     def _plan(self, B, N, H, W, device):
         packs = [h.stage_pack(device, self.precision) for h in self.mask_head]
         native = bool(self.native_plan)
-        key = (B, N, H, W, self.precision, self.output_dtype, str(device), tuple(id(p) for p in packs), bool(self.frame_invariant), E.plan_env_key())
-        if native:
-            key += ("native",)
+        # keyed by the cfg the plan is built from (engine.native_cfg: the geometry AND the environment switches) plus what it does not hold
+        cfg = E.native_cfg(B, N, H, W, len(packs), packs[0].num_classes, packs[0].lay.ffn_dim, E.MODES[self.precision],
+                           self.output_dtype, bool(self.frame_invariant))
+        key = (bytes(cfg), str(device), tuple(id(p) for p in packs), native)
         plan = self._plans.get(key)
         if plan is None:
             self._plans.clear()

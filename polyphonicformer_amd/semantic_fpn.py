@@ -142,25 +142,32 @@ class SemanticFPNWrapper(nn.Module):
                                                       self.pos_cfg.get("scale", 2 * math.pi), self.pos_cfg.get("eps", 1e-6)).to(dev)
         return self._pos[key]
 
-    def _forward_native(self, inputs, dev, B, shapes, planes):
-        """`forward`'s inference branch on the native plan: the pack keyed on the parameter versions exactly as `_pack` is, one
-        NativeNeckPlan per (B, level sizes), the host-computed positional encoding (the Python path's bits)"""
-        pos_level = self.cat_coors_level if self.pos_cfg is not None else -1
+    def _plan_cfg(self, B, shapes, dev, prec, pos_level=3):
+        """(tower_streams, the ph_neck_cfg) of the plan `forward` uses for B frames of these level sizes: the call the plan itself
+        makes (engine.native_neck_cfg: the geometry AND the environment switches, so a switch changed between two calls rebuilds the
+        plan); with the device string (and the native pack) it is the plan caches' key"""
+        # `_clip_towers` (set by video.VideoStreamRunner around the capture of a 2-3 frame clip launch): the four level towers on
+        # their own streams also below 4 frames -- inside a HIP graph the forks cost the host nothing (engine.NeckPlan)
         ts = getattr(self, "tower_streams", True)
         if ts and B < 4 and getattr(self, "_clip_towers", False):
             ts = "always"
+        return ts, E.native_neck_cfg(B, shapes, self.groups, prec, 1 + self.num_aux_convs, pos_level, False, ts, device_type=dev.type)
+
+    def _forward_native(self, inputs, dev, B, shapes, planes):
+        """`forward`'s inference branch on the native plan: the pack keyed on the parameter versions exactly as `_pack` is, one
+        NativeNeckPlan per cfg, the host-computed positional encoding (the Python path's bits)"""
+        pos_level = self.cat_coors_level if self.pos_cfg is not None else -1
+        ts, cfg = self._plan_cfg(B, shapes, dev, self.precision, pos_level)
         pkey = (str(dev), self.precision, _lib.param_versions(self))
         pk = self._npacks.get(pkey)
         if pk is None:
-            self._npacks.clear()
-            cfg = E.native_neck_cfg(B, shapes, self.groups, self.precision, 1 + self.num_aux_convs, pos_level, planes, ts,
-                                    device_type=dev.type)
+            self._npacks.clear(); self._nplans.clear()
             pk = self._npacks[pkey] = E.native_neck_pack(self, cfg, dev)
-        key = (B, shapes, str(dev), self.precision)
+        key = (bytes(cfg), str(dev), id(pk))
         plan = self._nplans.get(key)
         if plan is None:
             with torch.cuda.device(dev):
-                plan = self._nplans[key] = E.NativeNeckPlan(pk, B, shapes, dev, pos_level, ts)
+                plan = self._nplans[key] = E.NativeNeckPlan(pk, B, shapes, dev, pos_level, ts, cfg=cfg)
         add = self._posenc(*shapes[self.cat_coors_level], dev) if self.pos_cfg is not None else None
         with torch.cuda.device(dev):
             return plan.run([t.float().contiguous() for t in inputs[:4]], pk, self.groups, add, pos_level, to_planes=planes)
@@ -176,7 +183,8 @@ class SemanticFPNWrapper(nn.Module):
 
     def clip_plan(self, B, shapes, dev):
         """the device plan `forward` uses for B frames of these level sizes (None before the first such call)"""
-        return self._plans.get((B, tuple(tuple(s) for s in shapes), str(dev), self.precision))
+        dev = torch.device(dev)
+        return self._plans.get((bytes(self._plan_cfg(B, tuple(tuple(s) for s in shapes), dev, E.KHEAD_PREC[self.precision])[1]), str(dev)))
 
     def ingest_frames(self, frames, plan=None):
         """round 6: fills the plan's conv input planes from B one-frame level tuples, frame by frame and without a batched copy of the
@@ -212,15 +220,11 @@ class SemanticFPNWrapper(nn.Module):
                 return outs
             return [outs[0]] if self.return_list else outs[0]
         pk, prec, G = self._pack(dev), E.KHEAD_PREC[self.precision], self.groups
-        plan = self._plans.get((B, shapes, str(dev), self.precision))
+        ts, cfg = self._plan_cfg(B, shapes, dev, prec)
+        key = (bytes(cfg), str(dev))
+        plan = self._plans.get(key)
         if plan is None:
-            # `_clip_towers` (set by video.VideoStreamRunner around the capture of a 2-3 frame clip launch): the four level towers on
-            # their own streams also below 4 frames -- inside a HIP graph the forks cost the host nothing (engine.NeckPlan)
-            ts = getattr(self, "tower_streams", True)
-            if ts and B < 4 and getattr(self, "_clip_towers", False):
-                ts = "always"
-            plan = E.NeckPlan(B, shapes, prec, dev, tower_streams=ts)
-            self._plans[(B, shapes, str(dev), self.precision)] = plan
+            plan = self._plans[key] = E.NeckPlan(B, shapes, prec, dev, tower_streams=ts, groups=G, num_outs=1 + self.num_aux_convs)
         add = self._posenc(*shapes[self.cat_coors_level], dev) if self.pos_cfg is not None else None
         outs = plan.run([t.float().contiguous() for t in inputs[:4]], pk, G, add, self.cat_coors_level, to_planes=_planes)
         if _planes:

@@ -501,3 +501,61 @@ def test_head_program(gpu, case, tmp_path):
     assert (int(geo["nsplit"]), int(geo["nsplit_px"]), int(geo["poolx"]), int(geo["fused_up"])) == \
         (dp.nsplit, dp.nsplit_px, int(dp.poolx), int(dp.fused_up))
     assert int(geo["K"]) == bm.K and int(bm.records[:, 0].min()) > 0          # the merge accepted segments in every frame
+
+
+# ---- engine.KernelHeadPlan asks the library (ph_khead_geometry_of) ----------------------------------------------------------------
+def _asked(plan):
+    g = _lib.KheadGeometry()
+    with torch.cuda.device(plan.xp.device):
+        assert _lib.load().ph_khead_geometry_of(C.byref(plan.cfg), C.byref(g)) == 0, Hh.last_error()
+    assert (plan.onepass, plan.nsplit) == (bool(g.onepass), g.nsplit)
+    return g
+
+
+def test_kernel_head_plan_takes_its_choices_from_the_library(gpu, monkeypatch):
+    """one pass or two and the pooling split of a KernelHeadPlan are ph_khead_geometry_of's answer for the plan's own cfg, with and
+    without the two environment switches; a cfg the library refuses is a PolyheadError with its message.
+    PH_POOL_NSPLIT=3 is checked at 8 x 32, the smallest map of this height with three 64-pixel chunks: at 8 x 16 (128 pixels, two
+    chunks) a split of 3 is out of the pooling kernel's range, which the library now says when the plan is built"""
+    pack, _ = _native_pack("fp16", gpu)
+    lib = _lib.load()
+    plan = lambda H, W, **kw: E.KernelHeadPlan(pack, 2, H, W, N_THING, L, True, gpu, **kw)
+    sup = bool(lib.ph_khead_onepass_supported(2, 8 * 16, 32, _lib.PH_PREC_F16, _lib.PH_IN_F32_NCHW))
+    p = plan(8, 16)
+    assert sup and p.onepass == bool(_asked(p).onepass) == sup
+    monkeypatch.setenv("PH_KHEAD_TWOPASS", "1")
+    p = plan(8, 16)
+    assert not p.onepass and _asked(p).onepass == 0
+    monkeypatch.delenv("PH_KHEAD_TWOPASS")
+    monkeypatch.setenv("PH_POOL_NSPLIT", "3")
+    p = plan(8, 32)
+    assert p.nsplit == 3 and _asked(p).nsplit == 3 and p.partial.shape[1] == 3
+    with pytest.raises(_lib.PolyheadError, match="nsplit out of range"):
+        plan(8, 16)
+    monkeypatch.delenv("PH_POOL_NSPLIT")
+    p = plan(7, 9)                                   # 63 pixels: the fp32 input form needs H * W % 4 == 0
+    assert not p.onepass and _asked(p).onepass == 0
+    with pytest.raises(_lib.PolyheadError, match="ph_khead_onepass cannot run"):
+        plan(7, 9, onepass=True)
+    pack32, _ = _native_pack("fp32", gpu)
+    with pytest.raises(_lib.PolyheadError, match="one-pass form"):
+        E.KernelHeadPlan(pack32, 2, 8, 16, N_THING, L, True, gpu, logit_dtype=torch.float16)
+
+
+def test_module_plan_cache_follows_the_environment(gpu, monkeypatch):
+    """KernelHead's plan cache is keyed by the plan's cfg: PH_KHEAD_TWOPASS=1 set between two calls builds another plan"""
+    kh, _ = _head("fp16")
+    kh.use_native_plan(False)
+    B, H, W = 2, 8, 16
+    feats = [f.to(gpu) for f in Hh.neck_inputs(17, B, 256, H, W)]
+    meta = [dict(img_shape=(64, 128, 3), ori_shape=(64, 128, 3), batch_input_shape=(64, 128))] * B
+    with torch.no_grad():
+        kh.simple_test_rpn(feats, meta)
+        p1 = next(iter(kh._plans.values()))
+        assert p1.onepass
+        monkeypatch.setenv("PH_KHEAD_TWOPASS", "1")
+        kh.simple_test_rpn(feats, meta)
+        p2 = next(iter(kh._plans.values()))
+    torch.cuda.synchronize()
+    assert p2 is not p1 and not p2.onepass and len(kh._plans) == 1
+    assert p1.timeouts() == 0

@@ -155,7 +155,7 @@ def test_packing_is_the_module_pack_byte_for_byte(gpu, precision, num_outs):
 
 # ---- 2. bit identity with NeckPlan ------------------------------------------------------------------------------------------
 def _neckplan_run(m, B, shapes, precision, feats, posenc, to_planes, gpu, tower_streams):
-    plan = E.NeckPlan(B, shapes, E.KHEAD_PREC[precision], gpu, tower_streams=tower_streams)
+    plan = E.NeckPlan(B, shapes, E.KHEAD_PREC[precision], gpu, tower_streams=tower_streams, groups=m.groups, num_outs=1 + m.num_aux_convs)
     outs = plan.run(feats, m._pack(gpu), m.groups, posenc, 3, to_planes=to_planes)
     torch.cuda.synchronize()
     return [o.clone() for o in outs], plan
@@ -613,3 +613,83 @@ def test_neck_program(gpu, case, tmp_path):
     assert (int(geo["neck_fused_out"]), int(geo["neck_c16"]), int(geo["neck_P"])) == (1, 1, 1)
     assert (int(geo["khead_onepass"]), int(geo["fell_back"]), int(geo["timeouts"])) == (int(kp.onepass), 0, 0)
     assert int(geo["K"]) == bm.K and int(bm.records[:, 0].min()) > 0          # the merge accepted segments in every frame
+
+
+# ---- engine.NeckPlan asks the library (ph_neck_geometry_of) ----------------------------------------------------------------------
+PYR = ((16, 32), (8, 16), (4, 8), (2, 4))
+
+
+def _choices(B, precision, gpu):
+    """(out2, c16, multi) of a NeckPlan, which must be what ph_neck_geometry_of says of the plan's own cfg"""
+    p = E.NeckPlan(B, PYR, E.KHEAD_PREC[precision], gpu)
+    g = _lib.NeckGeometry()
+    assert _lib.load().ph_neck_geometry_of(C.byref(p.cfg), C.byref(g)) == 0, Hh.last_error()
+    assert (p.out2, p.c16 != 0, p.multi) == (bool(g.fused_out), bool(g.c16), bool(g.tower_buffers)), (B, precision)
+    assert p.c16 in (0, _lib.PH_PLANES_C16) and (p.Ho, p.Wo) == (g.Ho, g.Wo) == PYR[1]
+    return int(p.out2), int(p.c16 != 0), int(p.multi)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "fp32"])
+def test_neck_plan_takes_its_choices_from_the_library(gpu, monkeypatch, precision):
+    """the fused output stage and chunk-major planes in the one-plane grade only, tower streams from 4 frames; each of the three
+    environment switches, one at a time, turns its choice off and leaves the other two"""
+    one = int(precision == "fp16")
+    for B in (1, 3, 4, 5):
+        assert _choices(B, precision, gpu) == (one, one, int(B >= 4)), B
+    for i, var in enumerate(("PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS")):
+        monkeypatch.setenv(var, "0")
+        for B in (1, 3, 4, 5):
+            want = [one, one, int(B >= 4)]
+            want[i] = 0
+            assert _choices(B, precision, gpu) == tuple(want), (var, B)
+        monkeypatch.delenv(var)
+
+
+def test_neck_plan_reads_no_environment_after_construction(gpu, monkeypatch):
+    """PH_NECK_C16=0 set AFTER the plan was built changes nothing: a second run gives the first run's bits (the variable used to
+    be read on every tower call, which switched level 0's layout under a plan -- and under a captured graph -- built for the other)"""
+    B = 2
+    m = _neck("fp16")
+    feats = _feats(PYR, B, gpu, seed=9)
+    posenc = sine_positional_encoding(*PYR[3], 128).to(gpu)
+    plan = E.NeckPlan(B, PYR, _lib.PH_PREC_F16, gpu)
+    assert plan.c16 == _lib.PH_PLANES_C16
+    first = [o.clone() for o in plan.run(feats, m._pack(gpu), m.groups, posenc, 3)]
+    monkeypatch.setenv("PH_NECK_C16", "0")
+    _poison(plan.outs)
+    second = plan.run(feats, m._pack(gpu), m.groups, posenc, 3)
+    torch.cuda.synchronize()
+    assert plan.c16 == _lib.PH_PLANES_C16
+    for a, b in zip(first, second):
+        assert torch.equal(a, b)
+    assert E.NeckPlan(B, PYR, _lib.PH_PREC_F16, gpu).c16 == 0          # a plan built now listens
+
+
+def test_neck_plan_refuses_another_pack_geometry(gpu):
+    """a plan built for three output convs and 32 groups refuses a pack with one, or other groups, before any launch"""
+    feats = _feats(PYR, 1, gpu)
+    plan = E.NeckPlan(1, PYR, _lib.PH_PREC_F16, gpu)
+    m1 = _neck("fp16", 0)
+    with pytest.raises(_lib.PolyheadError, match="3 output convs"):
+        plan.run(feats, m1._pack(gpu), m1.groups, None, 3)
+    m = _neck("fp16")
+    with pytest.raises(_lib.PolyheadError, match="32 groups"):
+        plan.run(feats, m._pack(gpu), 16, None, 3)
+    with pytest.raises(_lib.PolyheadError, match="stride-2 pyramid"):
+        E.NeckPlan(1, ((16, 32), (8, 16), (4, 8), (3, 4)), _lib.PH_PREC_F16, gpu)
+
+
+def test_module_plan_cache_follows_the_environment(gpu, monkeypatch):
+    """SemanticFPNWrapper's plan cache is keyed by the plan's cfg: PH_NECK_OUT2=0 set between two calls builds another plan"""
+    m = _neck("fp16").use_native_plan(False)
+    feats = _feats(PYR, 2, gpu)
+    m(feats)
+    p1 = m.clip_plan(2, PYR, gpu)
+    assert p1 is not None and p1.out2
+    monkeypatch.setenv("PH_NECK_OUT2", "0")
+    m(feats)
+    p2 = m.clip_plan(2, PYR, gpu)
+    assert p2 is not None and p2 is not p1 and not p2.out2
+    monkeypatch.delenv("PH_NECK_OUT2")
+    assert m.clip_plan(2, PYR, gpu) is p1
+    torch.cuda.synchronize()

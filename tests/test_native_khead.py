@@ -102,6 +102,16 @@ def _create(cfg, nbytes=1 << 62):
     return rc, h
 
 
+# cfgs every entry point that takes one refuses: (fields, return code, a word of the message) and fields alone
+BAD_WITH_WORD = [(dict(groups=24), -1, "groups"), (dict(mode=9), -1, "bad mode"),
+                 (dict(logit_dtype=_lib.PH_OUT_F16, onepass=_lib.PH_KNOB_OFF), -2, "one-pass form")]
+BAD = (dict(num_proposals=0), dict(num_proposals=300), dict(num_classes=300), dict(num_thing_classes=20), dict(B=0),
+       dict(onepass=7), dict(nsplit=-1), dict(logit_dtype=_lib.PH_OUT_BF16), dict(num_proposals=250, num_classes=30),
+       dict(nsplit=1000))
+# the cfgs this file creates plans from on a machine without a device (two-pass: the one-pass rule is not asked)
+TWO_PASS = (dict(onepass=_lib.PH_KNOB_OFF), dict(onepass=_lib.PH_KNOB_OFF, mode=_lib.PH_MODE["mixed"], cat_stuff=0, frame_invariant=1))
+
+
 def test_errors_are_returned_before_anything_is_launched():
     lib = _lib.load()
     ws = lambda cfg: lib.ph_khead_plan_workspace_bytes(C.byref(cfg))
@@ -115,9 +125,7 @@ def test_errors_are_returned_before_anything_is_launched():
     cfg = _cfg(logit_dtype=_lib.PH_OUT_F16, onepass=_lib.PH_KNOB_OFF)
     assert ws(cfg) == 0 and "one-pass form" in Hh.last_error()
     assert _create(cfg)[0] == -2 and "one-pass form" in Hh.last_error()
-    for bad in (dict(num_proposals=0), dict(num_proposals=300), dict(num_classes=300), dict(num_thing_classes=20), dict(B=0),
-                dict(onepass=7), dict(nsplit=-1), dict(logit_dtype=_lib.PH_OUT_BF16), dict(num_proposals=250, num_classes=30),
-                dict(nsplit=1000)):
+    for bad in BAD:
         assert ws(_cfg(**bad)) == 0 and Hh.last_error(), bad
         rc, h = _create(_cfg(**bad))
         assert rc < 0 and not h.value, bad
@@ -147,6 +155,33 @@ def test_errors_are_returned_before_anything_is_launched():
     assert r.returncode == 0 and "run checks ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 
 
+def test_geometry_of_is_what_a_plan_reports():
+    """ph_khead_geometry_of(cfg) against ph_khead_plan_info of a plan created from the same cfg: the two structs byte for byte"""
+    lib = _lib.load()
+    for kw in TWO_PASS:
+        cfg = _cfg(**kw)
+        asked, told = _lib.KheadGeometry(), _lib.KheadGeometry()
+        assert lib.ph_khead_geometry_of(C.byref(cfg), C.byref(asked)) == 0, Hh.last_error()
+        rc, h = _create(cfg)
+        assert rc == 0 and lib.ph_khead_plan_info(h, C.byref(told)) == 0
+        lib.ph_khead_plan_destroy(h)
+        assert bytes(asked) == bytes(told), kw
+        assert asked.onepass == 0 and asked.nsplit > 0
+
+
+def test_geometry_of_checks_its_arguments():
+    """null cfg, null out and every cfg ph_khead_plan_workspace_bytes refuses: the same codes and messages, `out` untouched"""
+    lib = _lib.load()
+    g = _lib.KheadGeometry()
+    assert lib.ph_khead_geometry_of(None, C.byref(g)) == -1 and "ph_khead_geometry_of: null cfg" in Hh.last_error()
+    assert lib.ph_khead_geometry_of(C.byref(_cfg(onepass=_lib.PH_KNOB_OFF)), None) == -1 and "ph_khead_geometry_of: null out" in Hh.last_error()
+    for kw, rc, word in BAD_WITH_WORD:
+        assert lib.ph_khead_geometry_of(C.byref(_cfg(**kw)), C.byref(g)) == rc and word in Hh.last_error(), kw
+    for kw in BAD:
+        assert lib.ph_khead_geometry_of(C.byref(_cfg(**kw)), C.byref(g)) < 0 and "ph_khead_geometry_of" in Hh.last_error(), kw
+    assert bytes(g) == bytes(_lib.KheadGeometry())
+
+
 _RUN_CHECKS = r"""
 import ctypes as C, sys
 sys.path.insert(0, ".")
@@ -162,7 +197,10 @@ cfg = _lib.KheadCfg(B=2, H=48, W=156, num_proposals=100, num_classes=19, num_thi
 assert lib.ph_khead_onepass_supported(2, 48 * 156, 32, _lib.PH_PREC_F16, _lib.PH_IN_F32_NCHW) == 0
 cfg.onepass = _lib.PH_KNOB_ON
 assert lib.ph_khead_plan_workspace_bytes(C.byref(cfg)) == 0 and "ph_khead_onepass cannot run" in msg()
+geo = _lib.KheadGeometry()
+assert lib.ph_khead_geometry_of(C.byref(cfg), C.byref(geo)) == -2 and "ph_khead_onepass cannot run" in msg()
 cfg.onepass = _lib.PH_KNOB_AUTO
+assert lib.ph_khead_geometry_of(C.byref(cfg), C.byref(geo)) == 0 and geo.onepass == 0
 params = (C.c_void_p * _lib.PH_KHEAD_NPARAMS)(*([FAKE] * _lib.PH_KHEAD_NPARAMS))
 assert lib.ph_khead_pack(C.byref(cfg), params, C.c_void_p(FAKE + 16), None) == -1 and "aligned" in msg()
 params[11] = None

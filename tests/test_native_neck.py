@@ -95,18 +95,21 @@ def test_workspace_bytes():
             assert sizes0 == sorted(sizes0) and sizes1 == sorted(sizes1)         # non-decreasing in B
 
 
+# cfgs every entry point that takes one refuses, with a word of the message
+BAD = [(dict(shapes=((9, 13), (5, 8), (3, 4), (2, 2))), "stride-2 pyramid"),
+       (dict(shapes=S1_ISSUE), "stride-8 size"), (dict(shapes=S2_ISSUE), "stride-8 size"),
+       (dict(groups=48), "groups"), (dict(B=0), "B > 0"), (dict(num_outs=4), "num_outs"), (dict(num_outs=0), "num_outs"),
+       (dict(emit_planes=0, emit_f32=0), "emit_planes"), (dict(pos_level=4), "pos_level"), (dict(pos_level=-2), "pos_level"),
+       (dict(fused_out=_lib.PH_KNOB_ON, num_outs=1), "ph_neck_out_convs"),
+       (dict(fused_out=_lib.PH_KNOB_ON, groups=16), "ph_neck_out_convs"),
+       (dict(fused_out=_lib.PH_KNOB_ON, mode=_lib.PH_MODE["fp32"]), "ph_neck_out_convs"),
+       (dict(mode=9), "bad mode"), (dict(fused_out=7), "knob"), (dict(c16=_lib.PH_KNOB_ON), "knob"), (dict(tower_buffers=2), "knob"),
+       (dict(eps=-1.0), "eps")]
+
+
 def test_bad_cfgs_are_refused_with_a_message():
     lib = _lib.load()
-    bad = [(dict(shapes=((9, 13), (5, 8), (3, 4), (2, 2))), "stride-2 pyramid"),
-           (dict(shapes=S1_ISSUE), "stride-8 size"), (dict(shapes=S2_ISSUE), "stride-8 size"),
-           (dict(groups=48), "groups"), (dict(B=0), "B > 0"), (dict(num_outs=4), "num_outs"), (dict(num_outs=0), "num_outs"),
-           (dict(emit_planes=0, emit_f32=0), "emit_planes"), (dict(pos_level=4), "pos_level"), (dict(pos_level=-2), "pos_level"),
-           (dict(fused_out=_lib.PH_KNOB_ON, num_outs=1), "ph_neck_out_convs"),
-           (dict(fused_out=_lib.PH_KNOB_ON, groups=16), "ph_neck_out_convs"),
-           (dict(fused_out=_lib.PH_KNOB_ON, mode=_lib.PH_MODE["fp32"]), "ph_neck_out_convs"),
-           (dict(mode=9), "bad mode"), (dict(fused_out=7), "knob"), (dict(c16=_lib.PH_KNOB_ON), "knob"), (dict(tower_buffers=2), "knob"),
-           (dict(eps=-1.0), "eps")]
-    for kw, word in bad:
+    for kw, word in BAD:
         cfg = _cfg(**kw)
         assert lib.ph_neck_plan_workspace_bytes(C.byref(cfg)) == 0 and word in Hh.last_error(), (kw, Hh.last_error())
         assert lib.ph_neck_pack_bytes(C.byref(cfg)) == 0 and word in Hh.last_error(), kw
@@ -161,12 +164,84 @@ def _io(**kw):
 
 
 def _geo(cfg):
+    """what a plan created from the cfg reports (ph_neck_plan_info) -- and what the query without a plan (ph_neck_geometry_of) says
+    of the same cfg, which must be the same struct byte for byte"""
     lib = _lib.load()
-    h, g = C.c_void_p(), _lib.NeckGeometry()
+    h, g, asked = C.c_void_p(), _lib.NeckGeometry(), _lib.NeckGeometry()
     assert lib.ph_neck_plan_create(C.byref(cfg), C.c_void_p(FAKE_PTR), C.c_void_p(FAKE_PTR), 1 << 62, C.byref(h)) == 0, Hh.last_error()
     assert lib.ph_neck_plan_info(h, C.byref(g)) == 0
     lib.ph_neck_plan_destroy(h)
+    assert lib.ph_neck_geometry_of(C.byref(cfg), C.byref(asked)) == 0, Hh.last_error()
+    assert bytes(asked) == bytes(g)
     return g
+
+
+def test_geometry_of_is_what_a_plan_reports():
+    """the cfgs test_bad_cfgs_are_refused_with_a_message creates plans from (every other cfg of this file goes through `_geo`)"""
+    for cfg in (_cfg(), _cfg(pos_level=-1, emit_planes=0, emit_f32=1)):
+        g = _geo(cfg)
+        assert (g.Ho, g.Wo, g.fused_out, g.c16, g.tower_buffers) == (16, 32, 1, 1, 0)
+
+
+def test_geometry_of_checks_its_arguments():
+    """null cfg, null out and every cfg ph_neck_plan_workspace_bytes refuses: the same messages, `out` untouched"""
+    lib = _lib.load()
+    g = _lib.NeckGeometry()
+    assert lib.ph_neck_geometry_of(None, C.byref(g)) == -1 and "ph_neck_geometry_of: null cfg" in Hh.last_error()
+    assert lib.ph_neck_geometry_of(C.byref(_cfg()), None) == -1 and "ph_neck_geometry_of: null out" in Hh.last_error()
+    for kw, word in BAD:
+        assert lib.ph_neck_geometry_of(C.byref(_cfg(**kw)), C.byref(g)) < 0 and word in Hh.last_error(), kw
+        assert "ph_neck_geometry_of" in Hh.last_error()
+    assert bytes(g) == bytes(_lib.NeckGeometry())
+
+
+PYR = ((16, 32), (8, 16), (4, 8), (2, 4))
+
+
+def _asked(B=1, prec="fp16", env=None, monkeypatch=None, **kw):
+    """(fused_out, c16, tower_buffers) of ph_neck_geometry_of(native_neck_cfg(..)): what engine.NeckPlan takes as out2, c16, multi"""
+    for k in ("PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    cfg = E.native_neck_cfg(B, PYR, kw.pop("groups", 32), prec, **kw)
+    g = _lib.NeckGeometry()
+    assert _lib.load().ph_neck_geometry_of(C.byref(cfg), C.byref(g)) == 0, Hh.last_error()
+    return g.fused_out, g.c16, g.tower_buffers
+
+
+def test_neck_plan_choices_table(monkeypatch):
+    """the choices engine.NeckPlan takes from the library, against a literal table (each row confirmed once against the attributes
+    of the Python rule this query replaced)"""
+    ask = lambda *a, **kw: _asked(*a, monkeypatch=monkeypatch, **kw)
+    for prec in ("fp16", "bf16"):
+        for B in (1, 3):
+            assert ask(B, prec) == (1, 1, 0), (prec, B)
+        for B in (4, 5):
+            assert ask(B, prec) == (1, 1, 1), (prec, B)
+    for B in (1, 3, 4, 5):
+        assert ask(B, "fp32") == (0, 0, int(B >= 4)), B
+    for B in (1, 5):
+        assert ask(B, num_outs=1)[0] == 0 and ask(B, groups=16)[0] == 0
+        assert ask(B, tower_streams=False)[2] == 0 and ask(B, device_type="cpu")[2] == 0
+    assert ask(2)[2] == 0 and ask(2, tower_streams="always")[2] == 1
+    assert ask(5, env=dict(PH_NECK_OUT2="0")) == (0, 1, 1)
+    assert ask(5, env=dict(PH_NECK_C16="0")) == (1, 0, 1)
+    assert ask(5, env=dict(PH_NECK_STREAMS="0")) == (1, 1, 0)
+    assert ask(2, env=dict(PH_NECK_STREAMS="2")) == (1, 1, 1)
+
+
+def test_a_refused_pyramid_arrives_from_the_library(monkeypatch):
+    """level sizes that are no stride-2 pyramid: native_neck_cfg builds the cfg, the library refuses it -- engine.NeckPlan has no
+    check of its own any more"""
+    for k in ("PH_NECK_OUT2", "PH_NECK_C16", "PH_NECK_STREAMS"):
+        monkeypatch.delenv(k, raising=False)
+    cfg = E.native_neck_cfg(2, ((16, 32), (8, 16), (4, 8), (3, 4)), 32, "fp16")
+    g = _lib.NeckGeometry()
+    assert _lib.load().ph_neck_geometry_of(C.byref(cfg), C.byref(g)) == _lib.PH_EUNSUPPORTED
+    assert "stride-2 pyramid" in Hh.last_error()
+    with pytest.raises(_lib.PolyheadError, match="stride-2 pyramid"):
+        E.NeckPlan(2, ((16, 32), (8, 16), (4, 8), (3, 4)), _lib.PH_PREC_F16, "cpu")
 
 
 @pytest.mark.parametrize("mode", ["fp16", "bf16", "fp32", "mixed16"])

@@ -8,7 +8,7 @@ cd $R
 python - <<PY
 import csv, json, glob
 rows = list(csv.DictReader(open(glob.glob("/tmp/nk/**/nk_kernel_stats.csv", recursive=True)[0])))
-nfwd = [int(r["Calls"]) for r in rows if "k_gn_sum_planes" in r["Name"] or "k_gn_sum_cplanes" in r["Name"]][0]      # one launch per forward
+nfwd = [int(r["Calls"]) for r in rows if "k_gn_sum_planes" in r["Name"]][0]      # one launch per forward
 tot = 0
 for r in rows:
     if "nhwc" in r["Name"] or "gn_" in r["Name"] or "k_khead" in r["Name"]:
