@@ -1381,6 +1381,52 @@ int ph_assign_solve(const float* cost, int B, int Np, int ldg, const int32_t* co
 int ph_assign_desc(const ph_assign_cfg* cfg, const int32_t* G, const int32_t* S, const int32_t* last_pos, const float* cost, int ldg,
                    const int64_t* gt_table, int64_t gt_words, int32_t* match, int64_t* status, void* blob, size_t blob_bytes, void* stream);
 
+/* ---- training the track head: QDTrack targets, both losses and their gradients in ONE call (csrc/ph_trackloss.hip) -------------
+ * Replaces, for `pairs` key / reference image pairs, get_track_targets + match + loss of QuasiDenseMaskEmbedHeadGTMask
+ * (polyphonic/video/track_heads.py:104-162) with cal_similarity, MultiPosCrossEntropyLoss and L2Loss (hard mining) behind them, for
+ * softmax_temp <= 0.  One workgroup per pair; launches only: no allocation, no synchronisation, no atomics, fixed summation orders
+ * (fp32 products, fp64 loss sums), so two calls on the same inputs give the same bits and a pair's numbers do not depend on the
+ * other pairs of the call.
+ *   cfg        pairs <= PH_TRACK_LOSS_MAX_PAIRS, E (embedding width, a multiple of 4), the two loss weights, L2Loss's neg_pos_ub
+ *              (<= 0: no mining), pos_margin / neg_margin (applied when > 0) and hard_mining.  hard_mining == 0 with neg_pos_ub > 0
+ *              is PH_EINVAL: whether a pair exceeds the bound is known on the device only, and the reference's random choice is not
+ *              implemented.
+ *   key_start, ref_start, match_start   HOST int32 [pairs + 1]: row offsets of each pair's RoIs in key_emb / ref_emb (and key_gt /
+ *              ref_gt) and of its ground truths in gt_match.  1 .. PH_TRACK_LOSS_MAX_ROIS RoIs per side and pair, PH_EINVAL
+ *              otherwise (the reference asserts on an empty side); checked before anything is launched.
+ *   key_emb [sum Nk][E], ref_emb [sum Nr][E]   DEVICE fp32, 16-byte aligned
+ *   key_gt [sum Nk], ref_gt [sum Nr]   DEVICE int32: pos_assigned_gt_inds of every RoI; a key index outside the pair's gt_match
+ *              range matches nothing
+ *   gt_match   DEVICE int32: per key-frame ground truth its index among the reference frame's, or -1
+ *   target[i][j] = (gt_match[key_gt[i]] == ref_gt[j]); row weight = any_j target.
+ *   losses [2] DEVICE: loss_track, loss_track_aux, weighted and divided by `pairs`
+ *   g_key, g_ref   DEVICE, nullable together: d(loss_track + loss_track_aux) / d(embedding), overwritten
+ *   scratch    DEVICE, 16-byte aligned, the bytes the size query returns (PH_EWORKSPACE when smaller)
+ * Hard mining: when num_neg > neg_pos_ub * (num_pos + 1), the num_pos * neg_pos_ub negatives of largest squared clamped cost keep
+ * weight 1, found by a bitwise select on the costs' bit patterns in LDS; TIES at the cut go to the lowest row-major index i * Nr + j
+ * (torch.topk leaves its tie order unspecified; ties at cost 0 change neither loss nor gradient).  The clamp's gradient is 1 on the
+ * closed interval.  A pair without any positive gives 0 / 0 as in the reference: NaN in both losses and in every gradient row of
+ * that pair, the other pairs' rows unaffected. */
+#define PH_TRACK_LOSS_MAX_ROIS 128
+#define PH_TRACK_LOSS_MAX_PAIRS 64
+typedef struct {
+    int32_t pairs, E;
+    float lw_track, lw_aux;
+    int32_t neg_pos_ub;
+    float pos_margin, neg_margin;
+    int32_t hard_mining;
+} ph_track_loss_cfg;
+size_t ph_track_loss_scratch_bytes(const ph_track_loss_cfg* cfg, int total_key, int total_ref);
+int ph_track_loss(const ph_track_loss_cfg* cfg, const float* key_emb, const float* ref_emb, const int32_t* key_start,
+                  const int32_t* ref_start, const int32_t* key_gt, const int32_t* ref_gt, const int32_t* match_start,
+                  const int32_t* gt_match, float* losses, float* g_key, float* g_ref, void* scratch, size_t scratch_bytes, void* stream);
+/* Gradient of ph_roi_align_fpn's fp32 output into the FPN levels: g_roi [n][256][7][7] -> g_feats[l] [1][256][H_l][W_l] (HOST array
+ * of DEVICE pointers), every level overwritten in full, zeros included.  The forward's level map and sampling.  A gather: one thread
+ * per pixel and 16 channels walks the RoIs in index order (the weight of bin (ph, pw) on pixel (y, x) is Wy[ph](y) Wx[pw](x) / 4), so
+ * there are no atomics and two calls give the same bits.  n <= 1024. */
+int ph_roi_align_fpn_bwd(const float* g_roi, const int32_t* hw, const float* scales, int nlev, const float* rois, int n,
+                         float finest_scale, float* const* g_feats, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

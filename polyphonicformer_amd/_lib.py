@@ -197,6 +197,15 @@ class LossCfg(C.Structure):
                                   "cls_gamma", "cls_alpha", "cls_avg", "lw_seg", "seg_gamma", "seg_alpha")]
 
 
+# the track head's training losses (polyhead.h ph_track_loss_cfg, ph_track_loss)
+PH_TRACK_LOSS_MAX_ROIS, PH_TRACK_LOSS_MAX_PAIRS = 128, 64
+
+
+class TrackLossCfg(C.Structure):
+    _fields_ = [("pairs", C.c_int32), ("E", C.c_int32), ("lw_track", C.c_float), ("lw_aux", C.c_float), ("neg_pos_ub", C.c_int32),
+                ("pos_margin", C.c_float), ("neg_margin", C.c_float), ("hard_mining", C.c_int32)]
+
+
 # C typedef name -> its mirror above: every Structure of this module (tests/test_abi.py compares each layout with the header's)
 STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
@@ -204,7 +213,7 @@ STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decod
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
            "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout,
-           "ph_loss_cfg": LossCfg}
+           "ph_loss_cfg": LossCfg, "ph_track_loss_cfg": TrackLossCfg}
 
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -389,6 +398,10 @@ SIGNATURES = {
     "ph_assign_desc_layout": (C.c_int, [C.POINTER(AssignCfg), _P, _P, _P, C.POINTER(AssignLayout)]),
     "ph_assign_solve": (C.c_int, [_P, _I, _I, _I, _P, _L, _P, _P, _P]),
     "ph_assign_desc": (C.c_int, [C.POINTER(AssignCfg), _P, _P, _P, _P, _I, _P, _L, _P, _P, _P, _Z, _P]),
+    "ph_track_loss_scratch_bytes": (C.c_size_t, [C.POINTER(TrackLossCfg), _I, _I]),
+    "ph_track_loss": (C.c_int, [C.POINTER(TrackLossCfg), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32),
+                                _P, _P, _P, _P, _P, _Z, _P]),
+    "ph_roi_align_fpn_bwd": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), _I, _P, _I, C.c_float, C.POINTER(C.c_void_p), _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

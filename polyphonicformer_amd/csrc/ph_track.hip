@@ -294,6 +294,114 @@ extern "C" int ph_roi_align_fpn(const float* const* feats, const int32_t* hw /*[
     return PH_OK;
 }
 
+// ---- backward of the fp32 output: g_roi [n][256][7][7] -> g_feat[l] [256][H_l][W_l], a GATHER (no atomics, fixed order).
+// The forward's bin (ph, pw) averages 2 x 2 bilinear samples; a sample is dropped when y or x leaves [-1, H] x [-1, W] -- a product of
+// a condition on y and one on x -- so the weight of the bin on pixel (Y, X) is Wy[ph](Y) * Wx[pw](X) / 4 with
+//   Wy[ph](Y) = sum over the bin's two sample rows of (valid ? (1 - ly) [Y == yl] + ly [Y == yh] : 0)
+// and the same along x.  One thread per pixel of a level and ROI_BWD_CG channels walks the RoIs in index order; RoIs of other levels
+// or whose samples cannot reach the pixel are skipped by their descriptor (level + pixel box), which every workgroup derives into LDS.
+constexpr int ROI_BWD_CG = 16, ROI_BWD_MAX = 1024;
+struct RoiBwdArgs { float* g[4]; int H[4], W[4], blk0[5]; float scale[4]; int nlev; };
+struct RoiDesc { int lv, ylo, yhi, xlo, xhi; float x1, y1, bw, bh; };
+
+// one axis: the weights of the 7 bins on pixel coordinate P of an axis of length L (the forward's roi_bilinear, one dimension)
+__device__ __forceinline__ void roi_axis_weights(float s1, float bsz, int L, int P, float (&w)[7]) {
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+        float acc = 0.f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float v = s1 + b * bsz + (i + 0.5f) * bsz / 2.f;
+            if (v < -1.f || v > (float)L) continue;
+            v = fmaxf(v, 0.f);
+            int lo = (int)v, hi;
+            if (lo >= L - 1) { hi = lo = L - 1; v = (float)lo; } else hi = lo + 1;
+            const float l = v - lo;
+            if (P == lo) acc += 1.f - l;
+            if (P == hi) acc += l;
+        }
+        w[b] = acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_roi_align_fpn_bwd(RoiBwdArgs a, const float* __restrict__ g_roi, const float* __restrict__ rois,
+                                                            int n, float finest) {
+    extern __shared__ RoiDesc desc[];                 // [n]
+    for (int r = threadIdx.x; r < n; r += blockDim.x) {
+        const float* q = rois + r * 5;
+        const float sc = sqrtf((q[3] - q[1]) * (q[4] - q[2]));
+        int lv = (int)floorf(log2f(sc / finest + 1e-6f));
+        lv = lv < 0 ? 0 : (lv > a.nlev - 1 ? a.nlev - 1 : lv);
+        const float s = a.scale[lv];
+        const int H = a.H[lv], W = a.W[lv];
+        RoiDesc d;
+        d.lv = lv;
+        d.x1 = q[1] * s - 0.5f; d.y1 = q[2] * s - 0.5f;
+        const float x2 = q[3] * s - 0.5f, y2 = q[4] * s - 0.5f;
+        d.bw = (x2 - d.x1) / 7.f; d.bh = (y2 - d.y1) / 7.f;
+        // the pixel box the 14 sample coordinates per axis can touch (one pixel of slack on either side; the weights decide)
+        const float ya = d.y1, yb = d.y1 + 7.f * d.bh, xa = d.x1, xb = d.x1 + 7.f * d.bw;
+        const float ymin = fminf(ya, yb), ymax = fmaxf(ya, yb), xmin = fminf(xa, xb), xmax = fmaxf(xa, xb);
+        const bool ok = ymin == ymin && ymax == ymax && xmin == xmin && xmax == xmax;       // a NaN box reaches nothing
+        d.ylo = ok ? (int)fmaxf(floorf(ymin) - 1.f, 0.f) : 1;
+        d.yhi = ok ? (int)fminf(floorf(ymax) + 2.f, (float)(H - 1)) : 0;
+        d.xlo = ok ? (int)fmaxf(floorf(xmin) - 1.f, 0.f) : 1;
+        d.xhi = ok ? (int)fminf(floorf(xmax) + 2.f, (float)(W - 1)) : 0;
+        desc[r] = d;
+    }
+    __syncthreads();
+    int lv = 0;
+    while (lv + 1 < a.nlev && (int)blockIdx.x >= a.blk0[lv + 1]) ++lv;
+    const int H = a.H[lv], W = a.W[lv], HW = H * W;
+    const int pix = ((int)blockIdx.x - a.blk0[lv]) * 256 + threadIdx.x;
+    if (pix >= HW) return;
+    const int Y = pix / W, X = pix - Y * W, c0 = blockIdx.y * ROI_BWD_CG;
+    float acc[ROI_BWD_CG];
+#pragma unroll
+    for (int c = 0; c < ROI_BWD_CG; ++c) acc[c] = 0.f;
+    for (int r = 0; r < n; ++r) {
+        const RoiDesc d = desc[r];
+        if (d.lv != lv || Y < d.ylo || Y > d.yhi || X < d.xlo || X > d.xhi) continue;
+        float wy[7], wx[7];
+        roi_axis_weights(d.y1, d.bh, H, Y, wy);
+        roi_axis_weights(d.x1, d.bw, W, X, wx);
+        const float* g = g_roi + ((int64_t)r * 256 + c0) * 49;
+#pragma unroll
+        for (int ph = 0; ph < 7; ++ph) {
+            if (wy[ph] == 0.f) continue;
+            const float wq = 0.25f * wy[ph];
+#pragma unroll
+            for (int pw = 0; pw < 7; ++pw) {
+                if (wx[pw] == 0.f) continue;
+                const float w = wq * wx[pw];
+#pragma unroll
+                for (int c = 0; c < ROI_BWD_CG; ++c) acc[c] += w * g[c * 49 + ph * 7 + pw];
+            }
+        }
+    }
+    float* out = a.g[lv] + (int64_t)c0 * HW + pix;
+#pragma unroll
+    for (int c = 0; c < ROI_BWD_CG; ++c) out[(int64_t)c * HW] = acc[c];
+}
+
+extern "C" int ph_roi_align_fpn_bwd(const float* g_roi, const int32_t* hw /*[nlev][2]*/, const float* scales, int nlev, const float* rois,
+                                    int n, float finest_scale, float* const* g_feats, void* stream) {
+    PH_CHECK_ARG(g_roi && hw && scales && rois && g_feats && nlev >= 1 && nlev <= 4 && n > 0, "bad pointer or size");
+    PH_CHECK_ARG(n <= ROI_BWD_MAX, "at most 1024 RoIs per call");
+    RoiBwdArgs a;
+    a.nlev = nlev;
+    a.blk0[0] = 0;
+    for (int l = 0; l < nlev; ++l) {
+        PH_CHECK_ARG(g_feats[l] && hw[2 * l] > 0 && hw[2 * l + 1] > 0 && (int64_t)hw[2 * l] * hw[2 * l + 1] < (1ll << 22), "bad level pointer or size");
+        a.g[l] = g_feats[l]; a.H[l] = hw[2 * l]; a.W[l] = hw[2 * l + 1]; a.scale[l] = scales[l];
+        a.blk0[l + 1] = a.blk0[l] + (a.H[l] * a.W[l] + 255) / 256;
+    }
+    hipLaunchKernelGGL(k_roi_align_fpn_bwd, dim3(a.blk0[nlev], 256 / ROI_BWD_CG), dim3(256), (size_t)n * sizeof(RoiDesc), (hipStream_t)stream, a,
+                       g_roi, rois, n, finest_scale);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
 // device-count form: arguments checked by the caller (ph_assocplan.hip).  out_cl [P][B][cap][49][256]
 int ph_roi_align_fpn_cnt(const float* const* feats, const int32_t* hw, const float* scales, const int64_t* frame_strides, int nlev,
                          const float* rois /*[B][nseg][5]*/, int nseg, PhThings th, int B, float finest_scale, uint16_t* out_cl, int prec,

@@ -1,8 +1,12 @@
 """Track embedding head and RoI extraction -- drop-ins for `QuasiDenseMaskEmbedHeadGTMask`
-(polyphonic/video/track_heads.py:12-102, inference side) and the `SingleRoIExtractor` + RoIAlign call of
+(polyphonic/video/track_heads.py:12-162) and the `SingleRoIExtractor` + RoIAlign call of
 `PolyphonicVideo._track_forward` (polyphonic_former_video.py:408-419), on libpolyhead (csrc/ph_track.hip).
 Same registry name, constructor kwargs and state_dict keys (convs.{i}.conv.weight, convs.{i}.gn.*, fcs.0.*,
-fc_embed.*)."""
+fc_embed.*).
+
+Inference (eval mode or no_grad) runs the packed 16-bit kernels (`forward_planes`).  In training mode with grad enabled `forward`
+runs the fp32 training form on the nodes of train.py (`_Conv3x3`, `_GNReLU`) and the linear layers on `ph_gemm32`; `track_loss` is
+the reference's `loss(*match(...), *get_track_targets(...))` as ONE autograd node on `ph_track_loss` (csrc/ph_trackloss.hip)."""
 import ctypes as C
 
 import torch
@@ -16,6 +20,86 @@ from .registry import LOSSES, register_everywhere
 for _n in ("MultiPosCrossEntropyLoss", "L2Loss"):
     if _n not in LOSSES:
         LOSSES.register_module(name=_n, module=type(_n, (_LossStub,), {}))
+
+
+LOSS_TRACK_DEFAULT = dict(type="MultiPosCrossEntropyLoss", loss_weight=0.25)
+LOSS_TRACK_AUX_DEFAULT = dict(type="L2Loss", neg_pos_ub=3, pos_margin=0, neg_margin=0.1, hard_mining=True, loss_weight=1.0)
+
+
+def _gemm32(A, lda, kcA, B, ldb, kcB, M, N, K, ksplit=1, bias=None):
+    """C [M, N] = A(m, k) B(k, n) (+ bias[n]) on the training side's fp32-MFMA GEMM; kc: the operand is stored [row][k], else [k][row].
+    ksplit > 1: the partial products are added in split order"""
+    Cm = torch.empty((ksplit, M, N), dtype=torch.float32, device=A.device)
+    _lib.check(_lib.load().ph_gemm32(_lib.ptr(A), lda, kcA, _lib.ptr(B), ldb, kcB, _lib.ptr(Cm), N, M, N, K, ksplit, _lib.ptr(bias),
+                                     _lib.stream_ptr()), "ph_gemm32")
+    return Cm[0] if ksplit == 1 else Cm.sum(0)
+
+
+def _ksplit(K, want):
+    """a split of K's 32-wide steps that leaves no part empty"""
+    steps = (K + 31) // 32
+    ks = max(1, min(want, steps))
+    per = (steps + ks - 1) // ks
+    return (steps + per - 1) // per
+
+
+class _FcEmbed(torch.autograd.Function):
+    """fc_embed(relu(fcs.0(x))) (track_heads.py:96-101) as one node: x [n, 12544] (the NCHW flatten), fp32 MFMA products.
+    backward: dX, both weight gradients (dW1 [F][12544] tiled over its 12 544 columns) and the bias gradients.  Every operand's
+    vectorised axis (k, or the row index of a transposed operand) is a multiple of 4 here, which is all ph_gemm32 asks."""
+
+    @staticmethod
+    def forward(ctx, x, W1, b1, W2, b2):
+        from .train import _gpu32, _param32
+        x = _gpu32(x, "x")
+        W1, b1, W2, b2 = (_param32(p, "track head linear parameter") for p in (W1, b1, W2, b2))
+        n, K1 = x.shape
+        F_, Ee = W1.shape[0], W2.shape[0]
+        if K1 % 4 or F_ % 4 or Ee % 4:
+            raise _lib.PolyheadError("track head linear layers: widths must be multiples of 4")
+        h = _gemm32(x, K1, 1, W1, K1, 1, n, F_, K1, _ksplit(K1, 16), b1).clamp_(min=0)
+        out = _gemm32(h, F_, 1, W2, F_, 1, n, Ee, F_, _ksplit(F_, 8), b2)
+        ctx.save_for_backward(x, h, W1, W2)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .train import _gpu32
+        x, h, W1, W2 = ctx.saved_tensors
+        g = _gpu32(g, "grad")
+        n, K1 = x.shape
+        F_, Ee = W1.shape[0], W2.shape[0]
+        gW2 = _gemm32(g, Ee, 0, h, F_, 0, Ee, F_, n)                    # dE^T h
+        gh = _gemm32(g, Ee, 1, W2, F_, 0, n, F_, Ee)                     # dE W2
+        gh = gh * (h > 0)
+        gW1 = _gemm32(gh, F_, 0, x, K1, 0, F_, K1, n)                    # dH^T x
+        gx = _gemm32(gh, F_, 1, W1, K1, 0, n, K1, F_) if ctx.needs_input_grad[0] else None
+        return gx, gW1, gh.sum(0), gW2, g.sum(0)
+
+
+class _TrackLoss(torch.autograd.Function):
+    """`ph_track_loss` as one node: -> (loss_track + loss_track_aux, the two values); backward hands the stored gradients on"""
+
+    @staticmethod
+    def forward(ctx, cfg, host, key_gt, ref_gt, gt_match, key, ref):
+        from .train import _gpu32
+        lib = _lib.load()
+        key, ref = _gpu32(key, "key embeddings"), _gpu32(ref, "reference embeddings")
+        losses = torch.empty((2,), dtype=torch.float32, device=key.device)
+        gk, gr = torch.empty_like(key), torch.empty_like(ref)
+        scratch = torch.empty((max(lib.ph_track_loss_scratch_bytes(C.byref(cfg), key.shape[0], ref.shape[0]), 16),), dtype=torch.uint8,
+                              device=key.device)
+        _lib.check(lib.ph_track_loss(C.byref(cfg), _lib.ptr(key), _lib.ptr(ref), host[0], host[1], _lib.ptr(key_gt), _lib.ptr(ref_gt), host[2],
+                                     _lib.ptr(gt_match), _lib.ptr(losses), _lib.ptr(gk), _lib.ptr(gr), _lib.ptr(scratch), scratch.numel(),
+                                     _lib.stream_ptr()), "ph_track_loss")
+        ctx.save_for_backward(gk, gr)
+        ctx.mark_non_differentiable(losses)
+        return (losses[0].double() + losses[1].double()).float(), losses
+
+    @staticmethod
+    def backward(ctx, g, _):
+        gk, gr = ctx.saved_tensors
+        return None, None, None, None, None, g * gk, g * gr
 
 
 def segment_boxes(pan, nseg):
@@ -88,6 +172,9 @@ class QuasiDenseMaskEmbedHeadGTMask(nn.Module):
         self.fc_embed = nn.Linear(fc_out_channels, embed_channels)
         self.precision = "fp32"
         self._pack = None
+        # the loss configs are read for their numbers (track_loss); nothing is built from them
+        self.loss_track_cfg = dict(LOSS_TRACK_DEFAULT if loss_track is None else loss_track)
+        self.loss_track_aux_cfg = None if loss_track_aux is None else dict(loss_track_aux)
 
     def init_weights(self):
         for m in self.fcs:
@@ -151,6 +238,8 @@ class QuasiDenseMaskEmbedHeadGTMask(nn.Module):
     def forward(self, x):
         """track_heads.py:92-102: x fp32 [n,256,7,7] (RoI features) -> [n, embed_channels]"""
         E._require_gpu(x, "roi feats")
+        if self.training and torch.is_grad_enabled():
+            return self.forward_train(x)
         n = x.shape[0]
         P = 2 if E.PREC[self.precision] == _lib.PH_PREC_SPLIT else 1
         xc = x.float().permute(0, 2, 3, 1).reshape(n, 49, 256)            # layout change only (channels last)
@@ -160,8 +249,83 @@ class QuasiDenseMaskEmbedHeadGTMask(nn.Module):
             planes.append((xc - hi.float()).to(torch.bfloat16).view(torch.int16))
         return self.forward_planes(torch.stack(planes, 0).contiguous())
 
+    def forward_train(self, x):
+        """the fp32 training form of `forward`, differentiable: 4 x (`_Conv3x3` -> `_GNReLU`), the NCHW flatten, `_FcEmbed`"""
+        from .train import _Conv3x3, _GNReLU
+        E._require_gpu(x, "roi feats")
+        t = x.float()
+        for m in self.convs:
+            t = _GNReLU.apply(_Conv3x3.apply(t, m.conv.weight, 1), m.gn.weight, m.gn.bias, self.groups, None)
+        return _FcEmbed.apply(t.reshape(t.shape[0], -1), self.fcs[0].weight, self.fcs[0].bias, self.fc_embed.weight, self.fc_embed.bias)
+
+    def get_track_targets(self, gt_match_indices, key_sampling_results, ref_sampling_results):
+        """track_heads.py:104-121 -> (targets: int [Nk, Nr] per pair, weights: float [Nk]); integer torch ops, any device.  For
+        inspection and tests: the training path forms the targets inside `ph_track_loss`."""
+        targets, weights = [], []
+        for gm, kr, rr in zip(gt_match_indices, key_sampling_results, ref_sampling_results):
+            m = gm[kr.pos_assigned_gt_inds.long()]
+            t = (m.view(-1, 1) == rr.pos_assigned_gt_inds.view(1, -1)).int()
+            targets.append(t)
+            weights.append((t.sum(dim=1) > 0).float())
+        return targets, weights
+
+    def _track_loss_cfg(self, pairs, E_):
+        if self.softmax_temp > 0:
+            raise NotImplementedError("track_loss: softmax_temp > 0 (cosine logits) is not implemented; the shipped value is -1")
+        lt, la = self.loss_track_cfg, self.loss_track_aux_cfg
+        if lt.get("type") != "MultiPosCrossEntropyLoss" or lt.get("reduction", "mean") != "mean":
+            raise NotImplementedError(f"track_loss: loss_track must be MultiPosCrossEntropyLoss with mean reduction, got {lt}")
+        if la is None or la.get("type") != "L2Loss" or la.get("reduction", "mean") != "mean":
+            raise NotImplementedError(f"track_loss: loss_track_aux must be L2Loss with mean reduction, got {la}")
+        unknown = set(la) - {"type", "neg_pos_ub", "pos_margin", "neg_margin", "hard_mining", "reduction", "loss_weight"}
+        if unknown:
+            raise NotImplementedError(f"track_loss: L2Loss arguments {sorted(unknown)} are not the reference class's")
+        ub = la.get("neg_pos_ub", -1)
+        if ub != int(ub):
+            raise NotImplementedError("track_loss: neg_pos_ub must be an integer")
+        return _lib.TrackLossCfg(pairs=pairs, E=E_, lw_track=float(lt.get("loss_weight", 1.0)), lw_aux=float(la.get("loss_weight", 1.0)),
+                                 neg_pos_ub=int(ub), pos_margin=float(la.get("pos_margin", -1)), neg_margin=float(la.get("neg_margin", -1)),
+                                 hard_mining=int(bool(la.get("hard_mining", False))))
+
+    def track_loss(self, key_embeds, ref_embeds, gt_match_indices, key_sampling_results, ref_sampling_results):
+        """The reference's `loss(*match(key_embeds, ref_embeds, ...), *get_track_targets(...))` (track_heads.py:104-162) in one call:
+        key_embeds [sum Nk, E], ref_embeds [sum Nr, E] on the GPU, per pair gt_match_indices and the two sampling results (their
+        `pos_assigned_gt_inds`).  -> {'loss_track', 'loss_track_aux'} attached to the graph; their SUM carries the gradient (one
+        node, `train._attach`)."""
+        from .train import _attach
+        E._require_gpu(key_embeds, "key embeddings")
+        dev = key_embeds.device
+        kg = [r.pos_assigned_gt_inds for r in key_sampling_results]
+        rg = [r.pos_assigned_gt_inds for r in ref_sampling_results]
+        pairs = len(kg)
+        if not (pairs == len(rg) == len(gt_match_indices)) or pairs == 0:
+            raise ValueError("track_loss: one gt_match_indices, key and reference sampling result per pair")
+        cfg = self._track_loss_cfg(pairs, key_embeds.shape[1])
+
+        def starts(parts):
+            arr = (C.c_int32 * (pairs + 1))()
+            for i, t in enumerate(parts):
+                arr[i + 1] = arr[i] + int(t.numel())
+            return arr
+
+        def dev32(parts):
+            if not sum(int(t.numel()) for t in parts):                  # no ground truth at all: a readable placeholder
+                return torch.zeros((1,), dtype=torch.int32, device=dev)
+            return torch.cat([torch.as_tensor(t).reshape(-1).to(dev, torch.int32) for t in parts]).contiguous()
+
+        host = (starts(kg), starts(rg), starts(gt_match_indices))
+        if host[0][pairs] != key_embeds.shape[0] or host[1][pairs] != ref_embeds.shape[0]:
+            raise ValueError("track_loss: the sampling results' RoI counts do not add up to the embedding rows")
+        total, values = _TrackLoss.apply(cfg, host, dev32(kg), dev32(rg), dev32(gt_match_indices), key_embeds, ref_embeds)
+        return _attach({"loss_track": values[0], "loss_track_aux": values[1]}, total)
+
+    def match(self, *a, **k):
+        raise NotImplementedError("match() returns similarity matrices the training path never forms: use track_loss(key_embeds, ref_embeds, "
+                                  "gt_match_indices, key_sampling_results, ref_sampling_results)")
+
     def loss(self, *a, **k):
-        raise NotImplementedError("training is outside the implemented path")
+        raise NotImplementedError("loss() takes similarity matrices the training path never forms: use track_loss(key_embeds, ref_embeds, "
+                                  "gt_match_indices, key_sampling_results, ref_sampling_results)")
 
 
 register_everywhere(QuasiDenseMaskEmbedHeadGTMask)

@@ -555,6 +555,60 @@ def neck_forward_train(neck, inputs):
     return list(res)
 
 
+# ---- the video side: RoI features of the key frame and the track head's losses -------------------------------------------------
+class _RoIExtract(torch.autograd.Function):
+    """SingleRoIExtractor + RoIAlign(7, sampling_ratio 2, aligned) of one image (track_head.roi_extract, fp32 output); backward:
+    `ph_roi_align_fpn_bwd`, a gather that writes every level's gradient in full"""
+
+    @staticmethod
+    def forward(ctx, rois, strides, finest_scale, *feats):
+        from .track_head import roi_extract
+        feats = [_gpu32(f, "FPN level") for f in feats]
+        rois = _gpu32(rois, "rois")
+        _, f32 = roi_extract(feats, rois, _lib.PH_PREC_BF16, strides, float(finest_scale), want_f32=True)
+        ctx.shapes, ctx.strides, ctx.finest = [tuple(f.shape) for f in feats], tuple(strides), float(finest_scale)
+        ctx.save_for_backward(rois)
+        return f32
+
+    @staticmethod
+    def backward(ctx, g):
+        rois, = ctx.saved_tensors
+        g = _gpu32(g, "grad")
+        L = len(ctx.shapes)
+        outs = [torch.empty(s, dtype=torch.float32, device=g.device) for s in ctx.shapes]
+        ptrs = (C.c_void_p * L)(*[o.data_ptr() for o in outs])
+        hw = (C.c_int32 * (2 * L))(*[v for s in ctx.shapes for v in s[-2:]])
+        sc = (C.c_float * L)(*[1.0 / s for s in ctx.strides[:L]])
+        _lib.check(_lib.load().ph_roi_align_fpn_bwd(_lib.ptr(g), hw, sc, L, _lib.ptr(rois), rois.shape[0], ctx.finest, ptrs, _lib.stream_ptr()),
+                   "ph_roi_align_fpn_bwd")
+        return (None, None, None) + tuple(o if need else None for o, need in zip(outs, ctx.needs_input_grad[3:]))
+
+
+def track_forward_train(track_head, feats, ref_feats, rois, ref_rois, key_gt_inds, ref_gt_inds, gt_match_indices, strides=(4, 8, 16, 32),
+                        finest_scale=56):
+    """The track branch of PolyphonicVideo.forward_train (polyphonic_former_video.py:245-319) after the boxes: per image i the RoI
+    features of the key frame (feats[i]: its FPN levels [1, 256, H_l, W_l], gradients flow) and of the reference frame (ref_feats[i],
+    from the no-grad pass: no gradient), the track head in its training form on all of them, `track_loss`.  rois[i] / ref_rois[i]:
+    [n, 5] (0, x1, y1, x2, y2) -- the caller computes the boxes from its masks; key_gt_inds[i] / ref_gt_inds[i]: the RoIs'
+    pos_assigned_gt_inds; gt_match_indices[i]: per key ground truth its index among the reference frame's or -1.
+    -> {'loss_track', 'loss_track_aux'} attached to the graph."""
+    import types
+    from .track_head import roi_extract
+    B = len(feats)
+    if not (B == len(ref_feats) == len(rois) == len(ref_rois) == len(key_gt_inds) == len(ref_gt_inds) == len(gt_match_indices)) or B == 0:
+        raise ValueError("track_forward_train: one entry per image in every list")
+    with torch.enable_grad():
+        key_x = [_RoIExtract.apply(rois[i], tuple(strides), finest_scale, *feats[i]) for i in range(B)]
+        with torch.no_grad():
+            ref_x = [roi_extract([f.detach() for f in ref_feats[i]], ref_rois[i], _lib.PH_PREC_BF16, strides, float(finest_scale), want_f32=True)[1]
+                     for i in range(B)]
+        nk = sum(t.shape[0] for t in key_x)
+        emb = track_head.forward_train(torch.cat(key_x + ref_x))          # GroupNorm is per RoI: one pass for both frames
+        ks = [types.SimpleNamespace(pos_assigned_gt_inds=torch.as_tensor(t)) for t in key_gt_inds]
+        rs = [types.SimpleNamespace(pos_assigned_gt_inds=torch.as_tensor(t)) for t in ref_gt_inds]
+        return track_head.track_loss(emb[:nk], emb[nk:], [torch.as_tensor(t) for t in gt_match_indices], ks, rs)
+
+
 # ---- the two heads' training forwards (ONE implementation: the API methods and TrainStep both call these) --------------------
 def parse_losses(losses):
     """mmdet BaseDetector._parse_losses (base.py:188-199): the objective is the sum of the entries with 'loss' in the key"""
