@@ -1427,6 +1427,46 @@ int ph_track_loss(const ph_track_loss_cfg* cfg, const float* key_emb, const floa
 int ph_roi_align_fpn_bwd(const float* g_roi, const int32_t* hw, const float* scales, int nlev, const float* rois, int n,
                          float finest_scale, float* const* g_feats, void* stream);
 
+/* ---- the RoIs of a training step's sampled ground-truth masks, from the masks at the assign resolution (csrc/ph_gtbox.hip) -------
+ * Replaces, for `frames` key / reference frames, what PolyphonicVideo.forward_train does per sampled mask on the host
+ * (polyphonic_former_video.py:283-305, 413-415; video/utils.py:39-83): F.interpolate(size = (H, W), bilinear, align_corners = False)
+ * of the mask [h][w], sigmoid > 0.5, nonzero, centre +- 2 max(mean |deviation|, 1) per axis, (0, 0, 0, 0) for an empty mask,
+ * bboxlist2roi and clamp(min = 0).  No [n][H][W] tensor is formed: a box needs the row and column pixel counts r[Y], c[X] only,
+ *     n = sum r,  mean_y = sum Y r[Y] / n,  MAD_y = sum r[Y] |Y - mean_y| / n  (likewise in x),
+ * counts and coordinate sums are integers, means and deviations fp64, each coordinate rounded once to fp32.
+ *
+ * The selection happens in the same call.  match: DEVICE int32, row b * match_stride of frame b as ph_assign_solve leaves it -- the
+ * prediction row of ground truth g < G[b], or -1.  The frame's RoIs come out in ascending prediction row (MaskPseudoSampler's
+ * pos_inds): RoI r is the ground truth whose row has rank r among the matched ones, and pos_gt[r] is that ground truth (the
+ * reference's pos_assigned_gt_inds, the form ph_track_loss takes as key_gt / ref_gt).  n[b] = min(G[b], Np) is the number of matched
+ * ground truths: the host knows it from the counts, so no size depends on a download.  A match row with more entries >= 0 than n[b]
+ * has the surplus ranks dropped, one with fewer leaves the last rows of the frame unwritten; nothing is written out of bounds.
+ *
+ * The per-pixel predicate is ATen's bilinear form in fp32 without contraction -- source index scale (dst + 0.5) - 0.5 clamped at 0,
+ * scale = float(in) / out, h0 (w0 a + w1 b) + h1 (w0 c + w1 d), the + 1 tap falling on the same pixel at the last row / column --
+ * followed by the fp32 sigmoid test (value > 1.5 * 2^-24).  INPUT CONTRACT: the masks are non-negative (ground-truth masks), and no
+ * upsampled value lies in (0, 2^-20); then a pixel is on exactly when a tap with a non-zero weight is positive, whatever the rounding
+ * of the evaluation.  (A binary mask downsampled bilinearly by 4 and upsampled again has no positive value below 2^-8.)
+ *
+ *   masks      HOST [frames] of DEVICE fp32 [G[b]][h][w] (NULL allowed where G[b] == 0)
+ *   G, n, roi_start   HOST int32 [frames]: ground truths (0 .. PH_ASSIGN_MAX), matched count (<= PH_TRACK_LOSS_MAX_ROIS), first row of
+ *              the frame in rois / pos_gt / count.  A frame with n == 0 writes nothing.
+ *   h, w, H, W one size for the call; H >= h and W >= w, any ratio, at most 65536.  mode: PH_GTBOX_BILINEAR; the nearest mode of the
+ *              semantic_kitti configuration is PH_EUNSUPPORTED, as is a downsample
+ *   rois [sum n][5] fp32 (0, x1, y1, x2, y2) | pos_gt [sum n] int32 | count [sum n] int64: the on pixels of the upsampled mask
+ *   workspace  DEVICE, 16-byte aligned, ph_gtmask_boxes_workspace_bytes = al256(S H 4) + al256(S ceil(H / 64) W 2) bytes with
+ *              S = sum G and al256 rounding up to 256: the row histograms and, per band of 64 rows, the column partials
+ * Launches only (two): no allocation, no synchronisation, no atomics, no memset node, capturable.  ZEROING CONTRACT: none -- every
+ * word the second launch reads is written by the first.  Integer sums: two calls give the same bits and a frame's rows do not depend
+ * on the other frames of the call.  PH_EINVAL (n > 128, n != min(G, Np), ...) / PH_EUNSUPPORTED / PH_EWORKSPACE are returned
+ * before anything is launched. */
+#define PH_GTBOX_MAX_FRAMES 64
+enum { PH_GTBOX_BILINEAR = 0, PH_GTBOX_NEAREST = 1 };
+size_t ph_gtmask_boxes_workspace_bytes(int frames, const int32_t* G, int H, int W);   /* 0 on a bad argument (ph_last_error_string) */
+int ph_gtmask_boxes(const float* const* masks, const int32_t* G, const int32_t* n, const int32_t* roi_start, const int32_t* match,
+                    int64_t match_stride, int Np, int frames, int h, int w, int H, int W, int mode, float* rois, int32_t* pos_gt,
+                    int64_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -201,6 +201,11 @@ class LossCfg(C.Structure):
 PH_TRACK_LOSS_MAX_ROIS, PH_TRACK_LOSS_MAX_PAIRS = 128, 64
 
 
+# the RoIs of the sampled ground-truth masks (polyhead.h ph_gtmask_boxes)
+PH_GTBOX_MAX_FRAMES, PH_GTBOX_BILINEAR, PH_GTBOX_NEAREST = 64, 0, 1
+PH_EINVAL, PH_EWORKSPACE = -1, -4
+
+
 class TrackLossCfg(C.Structure):
     _fields_ = [("pairs", C.c_int32), ("E", C.c_int32), ("lw_track", C.c_float), ("lw_aux", C.c_float), ("neg_pos_ub", C.c_int32),
                 ("pos_margin", C.c_float), ("neg_margin", C.c_float), ("hard_mining", C.c_int32)]
@@ -402,6 +407,9 @@ SIGNATURES = {
     "ph_track_loss": (C.c_int, [C.POINTER(TrackLossCfg), _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, C.POINTER(C.c_int32),
                                 _P, _P, _P, _P, _P, _Z, _P]),
     "ph_roi_align_fpn_bwd": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), _I, _P, _I, C.c_float, C.POINTER(C.c_void_p), _P]),
+    "ph_gtmask_boxes_workspace_bytes": (C.c_size_t, [_I, C.POINTER(C.c_int32), _I, _I]),
+    "ph_gtmask_boxes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _L, _I, _I,
+                                  _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

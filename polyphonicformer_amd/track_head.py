@@ -116,6 +116,60 @@ def segment_boxes(pan, nseg):
     return rois, ext
 
 
+def gt_mask_rois(masks, match, n, out_hw, num_proposals=None, mode="bilinear"):
+    """The RoIs of the sampled ground-truth masks of a training step (polyphonic_former_video.py:283-305 + 413-415) from the masks at the
+    assign resolution, selection included: `ph_gtmask_boxes` (csrc/ph_gtbox.hip), launches only.  Per frame b: masks[b] fp32 [G, h, w]
+    on the GPU (non-negative), match[b] int32 [>= G] on the GPU -- the prediction row of every ground truth or -1, as `ph_assign_solve`
+    leaves it (or one [frames, ld] tensor) --, n[b] = min(G, num_proposals) matched ground truths (host ints).  out_hw: the padded
+    image size.  -> per-frame lists (rois [n, 5] fp32 (0, x1, y1, x2, y2) in ascending prediction row, pos_gt [n] int32, count [n] int64:
+    the on pixels of the upsampled mask), views of ONE allocation."""
+    lib = _lib.load()
+    F_ = len(masks)
+    if F_ == 0 or len(n) != F_ or (not torch.is_tensor(match) and len(match) != F_):
+        raise ValueError("gt_mask_rois: one masks / match / n entry per frame")
+    for m in masks:
+        E._require_gpu(m, "ground-truth masks")
+        if m.dim() != 3 or m.dtype != torch.float32 or not m.is_contiguous() or m.shape[1:] != masks[0].shape[1:]:
+            raise _lib.PolyheadError("gt_mask_rois: masks are fp32 contiguous [G, h, w] of one size per call")
+    dev = masks[0].device
+    h, w = (int(v) for v in masks[0].shape[1:])
+    H, W = int(out_hw[0]), int(out_hw[1])
+    G = [int(m.shape[0]) for m in masks]
+    n = [int(v) for v in n]
+    if num_proposals is None:             # any Np >= max G is consistent with n == G everywhere; a frame with n < G names it
+        cut = [v for v, g in zip(n, G) if v < g]
+        num_proposals = cut[0] if cut else max(G + [0])
+    if torch.is_tensor(match) and match.dim() == 2 and match.dtype == torch.int32 and match.is_contiguous() and match.shape[0] == F_:
+        mt = match
+    else:
+        mt = torch.full((F_, max(G + [1])), -1, dtype=torch.int32, device=dev)
+        for b in range(F_):
+            if G[b]:
+                mt[b, :G[b]] = match[b].reshape(-1)[:G[b]]
+    E._require_gpu(mt, "match")
+    total = sum(max(v, 0) for v in n)
+    buf = torch.empty((max(total, 1) * 32,), dtype=torch.uint8, device=dev)        # count [total] int64 | rois [total][5] | pos_gt [total]
+    count = buf[:8 * total].view(torch.int64)
+    rois = buf[8 * total:28 * total].view(torch.float32).view(total, 5)
+    pos_gt = buf[28 * total:32 * total].view(torch.int32)
+    start = [0]
+    for v in n:
+        start.append(start[-1] + max(v, 0))
+    i32 = lambda a: (C.c_int32 * len(a))(*a)
+    md = {"bilinear": _lib.PH_GTBOX_BILINEAR, "nearest": _lib.PH_GTBOX_NEAREST}[mode]
+    for b0 in range(0, F_, _lib.PH_GTBOX_MAX_FRAMES):
+        b1 = min(F_, b0 + _lib.PH_GTBOX_MAX_FRAMES)
+        Gc = i32(G[b0:b1])
+        need = lib.ph_gtmask_boxes_workspace_bytes(b1 - b0, Gc, H, W)
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        ptrs = (C.c_void_p * (b1 - b0))(*[m.data_ptr() if m.shape[0] else None for m in masks[b0:b1]])
+        _lib.check(lib.ph_gtmask_boxes(ptrs, Gc, i32(n[b0:b1]), i32(start[b0:b1]), _lib.ptr(mt[b0:]), mt.stride(0), int(num_proposals), b1 - b0,
+                                       h, w, H, W, md, _lib.ptr(rois), _lib.ptr(pos_gt), _lib.ptr(count), _lib.ptr(ws), need,
+                                       _lib.stream_ptr()), "ph_gtmask_boxes")
+    cut = lambda t: [t[start[b]:start[b + 1]] for b in range(F_)]
+    return cut(rois), cut(pos_gt), cut(count)
+
+
 def roi_extract(feats, rois, prec, strides=(4, 8, 16, 32), finest_scale=56.0, want_f32=False):
     """feats: list of fp32 [1,256,H_l,W_l] GPU tensors (the FPN levels), rois [n,5] GPU.
     Returns channels-last bf16 planes int16 [P,n,49,256] (and fp32 [n,256,7,7] if asked)."""

@@ -609,6 +609,87 @@ def track_forward_train(track_head, feats, ref_feats, rois, ref_rois, key_gt_ind
         return track_head.track_loss(emb[:nk], emb[nk:], [torch.as_tensor(t) for t in gt_match_indices], ks, rs)
 
 
+def gt_match_indices(gt_ids, ref_ids):
+    """polyphonic_former_video.py:246-251 for one image: per key-frame ground truth the FIRST index of its instance id among the
+    reference frame's ids, or -1 (`ref_ids.index(i) if i in ref_ids else -1`).  Integer torch on the ids' device -- a minimum over a
+    masked index, not an argmax on ties --, nothing is downloaded.  -> int64 [len(gt_ids)]"""
+    g = gt_ids.reshape(-1).long()
+    r = ref_ids.reshape(-1).long().to(g.device)
+    R = r.numel()
+    if R == 0 or g.numel() == 0:
+        return torch.full((g.numel(),), -1, dtype=torch.long, device=g.device)
+    idx = torch.arange(R, device=g.device)[None].expand(g.numel(), R)
+    first = torch.where(g[:, None] == r[None, :], idx, torch.full_like(idx, R)).min(dim=1).values
+    return torch.where(first < R, first, torch.full_like(first, -1))
+
+
+def _track_assign_ok(assigner):
+    from .assigner import _MaskAssignerBase
+    return isinstance(assigner, _MaskAssignerBase) and assigner.topk == 1 and (assigner.depth_cost is None or assigner.depth_cost.weight == 0)
+
+
+def track_sample(assigner, mask_preds, cls_scores, gt, num_proposals, num_thing_classes, device_assign=False):
+    """polyphonic_former_video.py:256-280 for the B images of one frame set: the track assigner (MaskHungarianAssigner: class, mask and
+    dice costs over ALL pixels, no valid map, no depth cost) on the detached final-stage scaled_mask_preds[:, :Np] and
+    cls_scores[:, :Np, :n_thing] against the UN-hardened thing masks at the assign resolution (`gt`: a soft `losses.StepGT`).  Pseudo
+    sampling is the identity on the assignment, so what comes back is the assignment itself: `match` int32 [B, max(Gmax, 1)] on the
+    device, the prediction row of every ground truth or -1 -- the form `track_head.gt_mask_rois` takes.  Host path:
+    `losses.assign_batch` (one download, scipy); device_assign: the cost stays where `losses._assign_cost` forms it and `ph_assign_solve`
+    solves it (its status words are appended to gt.status_words); beyond the kernel's limits the host path runs."""
+    import types
+    import numpy as np
+    if not _track_assign_ok(assigner):
+        raise NotImplementedError("track_sample: one-to-one Hungarian matching on class / mask / dice costs (the shipped track_train_cfg)")
+    Np, nt = int(num_proposals), int(num_thing_classes)
+    pred = _gpu32(mask_preds, "scaled_mask_preds")[:, :Np]
+    cls = None if cls_scores is None else cls_scores.detach()[:, :Np, :nt].float()
+    B, dev = gt.B, pred.device
+    if pred.shape[0] != B or pred.shape[1] != Np:
+        raise ValueError("track_sample: mask_preds must hold num_proposals rows for every image of the ground truth")
+    ld = max(gt.Gmax, 1)
+    all_px = types.SimpleNamespace(pad=gt.pad, valid=None, Gmax=gt.Gmax, G=gt.G, labels_dev=gt.labels_dev, B=B)     # assigner.py:199-360
+    if gt.Gmax == 0:
+        return torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+    if device_assign and max(Np, gt.Gmax) <= _lib.PH_ASSIGN_MAX:
+        cost = Lo._assign_cost(assigner, pred, cls, all_px)
+        if torch.is_tensor(cost):
+            cost = cost.detach().float().contiguous()
+            match = torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+            status = torch.empty((B,), dtype=torch.int64, device=dev)
+            counts = gt.device_table().view(torch.int32)                   # word 0 of every record: G_b (little endian int64)
+            _lib.check(_lib.load().ph_assign_solve(_lib.ptr(cost), B, Np, ld, _lib.ptr(counts), 2 * _lib.PH_ASSIGN_GT_WORDS, _lib.ptr(match),
+                                                   _lib.ptr(status), _lib.stream_ptr()), "ph_assign_solve")
+            gt.status_words.append(status)
+            return match
+    rows = np.full((B, ld), -1, np.int32)
+    for i, (r, c) in enumerate(Lo.assign_batch(assigner, pred, cls, all_px)):
+        rows[i, c] = r
+    return torch.from_numpy(rows).to(dev, non_blocking=True)
+
+
+def video_track_branch(track_head, track_assigner, x, x_ref, key_last, ref_last, gt, ref_gt, gt_ids, ref_ids, pad_hw, num_proposals,
+                       num_thing_classes, device_assign=False, strides=(4, 8, 16, 32), finest_scale=56):
+    """The tracking part of PolyphonicVideo.forward_train (polyphonic_former_video.py:245-319) in one function: `gt_match_indices`, the
+    two `track_sample`s, ONE `gt_mask_rois` call for all key and reference frames, `track_forward_train`.
+    x / x_ref: the FPN levels [B, 256, H_l, W_l] of the key (gradients flow) and reference frames; key_last / ref_last: the final stage's
+    (object_feats, cls_score, mask_preds, scaled_mask_preds) of `roi_forward_train` / `simple_test_mask_preds`; gt / ref_gt: soft
+    `losses.StepGT` of the two frames' thing masks; gt_ids / ref_ids: per image the instance ids; pad_hw: the padded image size.
+    With device_assign nothing here waits for the host.  -> {'loss_track', 'loss_track_aux'} attached to the graph."""
+    from .track_head import gt_mask_rois
+    B, Np = gt.B, int(num_proposals)
+    if ref_gt.B != B or len(gt_ids) != B or len(ref_ids) != B:
+        raise ValueError("video_track_branch: one reference frame, id list and ground truth per key image")
+    gmi = [gt_match_indices(gt_ids[i], ref_ids[i]) for i in range(B)]
+    mk = track_sample(track_assigner, key_last[3], key_last[1], gt, Np, num_thing_classes, device_assign)
+    mr = track_sample(track_assigner, ref_last[3], ref_last[1], ref_gt, Np, num_thing_classes, device_assign)
+    n = [min(g, Np) for g in gt.G + ref_gt.G]
+    rois, pos_gt, _ = gt_mask_rois(list(gt.masks) + list(ref_gt.masks), [mk[i] for i in range(B)] + [mr[i] for i in range(B)], n, pad_hw,
+                                   num_proposals=Np)
+    feats = [[lv[i:i + 1] for lv in x] for i in range(B)]
+    ref_feats = [[lv[i:i + 1] for lv in x_ref] for i in range(B)]
+    return track_forward_train(track_head, feats, ref_feats, rois[:B], rois[B:], pos_gt[:B], pos_gt[B:], gmi, strides, finest_scale)
+
+
 # ---- the two heads' training forwards (ONE implementation: the API methods and TrainStep both call these) --------------------
 def parse_losses(losses):
     """mmdet BaseDetector._parse_losses (base.py:188-199): the objective is the sum of the entries with 'loss' in the key"""
@@ -877,6 +958,19 @@ def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_m
 
 
 # ---- the step ------------------------------------------------------------------------------------------------------------------
+def _heads_forward_train(rpn, roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, device_assign):
+    """the two heads on the three post-neck maps, what both steps run: -> (the 24 losses attached to the graph, the final stage's
+    (object_feats, cls_score, mask_preds, scaled_mask_preds), the step's ground-truth cache)"""
+    gt_cache = {}                                           # the step's ground truth (losses.StepGT), shared by the two heads
+    rpn_losses, r = rpn_forward_train(rpn, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
+                                      gt_cache=gt_cache, device_assign=device_assign)
+    k, mask_preds, q = rpn_outputs(rpn, r)
+    losses, last = roi_forward_train(roi, r["x"], r["dfe"], k, mask_preds, q, r["depth_pred"], img_metas, gt_masks, gt_labels,
+                                     gt_sem_seg, gt_sem_cls, gt_depth, gt_cache=gt_cache, device_assign=device_assign)
+    losses.update(rpn_losses)                               # polyphonic_former.py:126
+    return losses, last, gt_cache
+
+
 class TrainStep:
     """rpn_head: KernelHead, roi_head: KernelUpdateIterHead, both built with train_cfg.  `forward_backward` evaluates one
     step on the three post-neck maps and leaves `.grad` on every parameter of the two heads (accumulating, like autograd; averaged over the ranks
@@ -930,17 +1024,113 @@ class TrainStep:
             if not f.is_cuda:
                 raise _lib.PolyheadError("the post-neck maps must live on the GPU: libpolyhead has no CPU path")
         with torch.enable_grad(), Lo.reduce_group(self.group):
-            gt_cache = {}                                   # the step's ground truth (losses.StepGT), shared by the two heads
-            rpn_losses, r = rpn_forward_train(self.rpn, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                              gt_cache=gt_cache, device_assign=self.device_assign)
-            k, mask_preds, q = rpn_outputs(self.rpn, r)
-            losses, _ = roi_forward_train(self.roi, r["x"], r["dfe"], k, mask_preds, q, r["depth_pred"], img_metas, gt_masks, gt_labels,
-                                          gt_sem_seg, gt_sem_cls, gt_depth, gt_cache=gt_cache, device_assign=self.device_assign)
+            losses, _, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
+                                                       self.device_assign)
             self._status = [w for g in gt_cache.values() for w in g.status_words]
-            losses.update(rpn_losses)                       # polyphonic_former.py:126
             total = parse_losses(losses)
             if backward:
                 self.buckets.start()
                 total.backward()
                 self.buckets.finish()
         return {k_: v.detach() for k_, v in losses.items()}, total.detach(), [f.grad for f in feats]
+
+
+class VideoTrainStep:
+    """PolyphonicVideo.forward_train after extract_feat (polyphonic_former_video.py:185-325) as one step: the neck in training form on
+    the key frame's FPN levels and in eval form on the reference frame's, the two heads on the key frame exactly as `TrainStep` runs
+    them, the reference frame through `simple_test_rpn` + `simple_test_mask_preds` in eval mode under no_grad, the track branch
+    (`video_track_branch`), the objective, ONE backward with bucketed gradient all-reduce over the parameters of neck, both heads and
+    the track head.  track_train_cfg: dict(assigner=...) as the model config has it (MaskHungarianAssigner, FocalLossCost 2, DiceCost 4,
+    MaskCost 1) or a built assigner.  `rpn_head.localization_fpn` is None (the neck is this step's) or the same neck."""
+
+    def __init__(self, neck, rpn_head, roi_head, track_head, track_train_cfg, bucket_bytes=32 << 20, group=None, device_assign=False,
+                 strides=(4, 8, 16, 32), finest_scale=56):
+        from .assigner import build_assigner
+        from .dist import GradBuckets
+        self.neck, self.rpn, self.roi, self.track_head = neck, rpn_head, roi_head, track_head
+        self.device_assign = bool(device_assign)
+        self.strides, self.finest_scale = tuple(strides), finest_scale
+        self._status = []
+        if rpn_head.assigner is None or not roi_head.mask_assigner:
+            raise ValueError("VideoTrainStep needs heads built with train_cfg (assigner / sampler)")
+        if rpn_head.localization_fpn is not None and rpn_head.localization_fpn is not neck:
+            raise ValueError("VideoTrainStep: rpn_head.localization_fpn must be None or the step's neck")
+        check_rpn_topology(rpn_head)
+        for h in roi_head.mask_head:
+            check_stage_topology(h)
+        a = track_train_cfg.get("assigner") if isinstance(track_train_cfg, dict) else getattr(track_train_cfg, "assigner", track_train_cfg)
+        self.track_assigner = build_assigner(dict(a)) if isinstance(a, dict) else a
+        if not _track_assign_ok(self.track_assigner):
+            raise NotImplementedError("VideoTrainStep: track_train_cfg.assigner must be a one-to-one mask Hungarian assigner without depth cost")
+        self.group = group
+        self.buckets = GradBuckets(self.parameters(), bucket_bytes=bucket_bytes, group=group)
+
+    def close(self):
+        self.buckets.remove()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def parameters(self):
+        out, seen = [], set()
+        heads = [p for n, p in _lib.named_params(self.rpn).items() if not n.startswith("localization_fpn.")]
+        for p in list(_lib.named_params(self.neck).values()) + heads + list(_lib.named_params(self.roi).values()) + \
+                list(_lib.named_params(self.track_head).values()):
+            if id(p) not in seen:
+                seen.add(id(p))
+                out.append(p)
+        return out
+
+    def assign_status(self):
+        """as `TrainStep.assign_status`; with device_assign the two track solves add a row each"""
+        if not self._status:
+            return torch.zeros((0, 0), dtype=torch.int64)
+        return torch.stack(self._status).cpu()
+
+    def _reference_frame(self, x_ref, ref_metas):
+        """:186-191, 207-243 for the reference frame: neck, rpn head and roi head in eval mode under no_grad, at the grade the module API
+        runs; every module's `training` flag is put back"""
+        mods = [m for top in (self.neck, self.rpn, self.roi) for m in top.modules()]
+        flags = [m.training for m in mods]
+        try:
+            for top in (self.neck, self.rpn, self.roi):
+                top.eval()
+            with torch.no_grad():
+                src = x_ref if self.rpn.localization_fpn is not None else self.neck(x_ref)
+                (pf, xf, mp, cs, _, df, dp, dpr, _) = self.rpn.simple_test_rpn(src, ref_metas)
+                return self.roi.simple_test_mask_preds(xf, pf, mp, cs, ref_metas, depth_preds=dpr, depth_feats=df, depth_proposal=dp, imgs_whwh=None)
+        finally:
+            for m, f in zip(mods, flags):
+                m.training = f
+
+    def forward_backward(self, x, x_ref, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, gt_instance_ids, ref_gt_masks,
+                         ref_gt_labels, ref_gt_instance_ids, pad_hw, backward=True, ref_img_metas=None):
+        """x / x_ref: the FPN levels of the key and the reference frames; the ground truth as the reference has it at :185 (things and
+        stuff split, at the assign resolution).  -> (losses: the 24 image losses + loss_track + loss_track_aux, objective, gradients of
+        the key frame's FPN levels: neck path + RoIAlign path).  The reference frame's levels get no gradient."""
+        x = [f.detach().float().contiguous().requires_grad_(True) for f in x]
+        x_ref = [f.detach().float().contiguous() for f in x_ref]
+        for f in x + x_ref:
+            if not f.is_cuda:
+                raise _lib.PolyheadError("the FPN levels must live on the GPU: libpolyhead has no CPU path")
+        with torch.enable_grad(), Lo.reduce_group(self.group):
+            feats = neck_forward_train(self.neck, x)                                                   # :185
+            losses, last, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls,
+                                                          gt_depth, self.device_assign)
+            ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas)
+            gt = _step_gt(gt_cache, False, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)       # the soft masks (:259)
+            ref_gt = Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
+            losses.update(video_track_branch(self.track_head, self.track_assigner, x, x_ref, last, ref_last, gt, ref_gt, gt_instance_ids,
+                                             ref_gt_instance_ids, pad_hw, self.roi.num_proposals, self.roi.num_thing_classes,
+                                             self.device_assign, self.strides, self.finest_scale))
+            self._status = [w for g in list(gt_cache.values()) + [ref_gt] for w in g.status_words]
+            total = parse_losses(losses)
+            if backward:
+                self.buckets.start()
+                total.backward()
+                self.buckets.finish()
+        return {k_: v.detach() for k_, v in losses.items()}, total.detach(), [f.grad for f in x]
