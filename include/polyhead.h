@@ -1467,6 +1467,34 @@ int ph_gtmask_boxes(const float* const* masks, const int32_t* G, const int32_t* 
                     int64_t match_stride, int Np, int frames, int h, int w, int H, int W, int mode, float* rois, int32_t* pos_gt,
                     int64_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- a training step's ground truth from one segment-index map per frame (csrc/ph_gtprep.hip).  A loader's masks of a frame are
+ * disjoint (they tile the image), so the [G][Hp][Wp] stack polyphonic_former_video.py:115 uploads as fp32 is one byte per pixel: the
+ * index of the pixel's segment in the loader's list, 255 where there is none.  This call turns `frames` such maps into everything
+ * the step reads at the assign resolution (:114-138 and what losses.StepGT derives from it):
+ *   seg        DEVICE uint8 [frames][Hs][Ws], the loader's un-padded size.  Pixels at y >= Hs or x >= Ws up to the padded size
+ *              Hp x Wp read as "no segment" (the F.pad(..., value=0) of :116-118).
+ *   row_of     DEVICE int32 [frames][256]: segment index -> output row.  0 .. Gmax-1 a row of `things`, Gmax .. Gmax+Smax-1 row
+ *              (value - Gmax) of `stuff`, anything else (-1) dropped.  Entry 255 and the entries from nseg[b] on count as -1 whatever they hold.
+ *   nseg       HOST int32 [frames]: segments in the frame's list, 0 .. PH_GTPREP_MAX_SEGMENTS
+ *   depth      DEVICE fp32 [frames][Hp][Wp] or NULL (then depth_out is NULL too)
+ *   things [frames][Gmax][aH][aW] | stuff [frames][Smax][aH][aW] fp32: the soft masks; rows no segment maps to are zero, so
+ *              `things` is the zero-padded stack the batched assignment reads.  NULL allowed for a stack without rows.
+ *   things_hard, stuff_hard   the same shapes or NULL: value != 0 ? 1 : 0 (kernel_head.py:400-403)
+ *   valid [frames][aH][aW] fp32: 1 where any row of either stack is non-zero | depth_out [frames][aH][aW] fp32
+ * Arithmetic, fp32 without contraction.  PH_GTBOX_BILINEAR: ATen's bilinear form (align_corners = False), scale = float(in) / out
+ * with in the PADDED size, source index max(scale (dst + 0.5) - 0.5, 0), the + 1 tap falling on the same pixel at the last row /
+ * column, value h0 (w0 a + w1 b) + h1 (w0 c + w1 d) with a .. d = 1.0 where the tap's segment maps to the row, else 0.0.
+ * PH_GTBOX_NEAREST: the tap at min(floor(dst scale), in - 1).  The depth map is always nearest (:135-138).
+ * One launch: no allocation, no synchronisation, no atomics, no workspace, capturable.  ZEROING CONTRACT: none -- every word of
+ * every output is written, zeros included.  Two calls give the same bits; a frame's outputs do not depend on the other frames.
+ * PH_EINVAL (more than 254 segments in a frame, Gmax or Smax above PH_ASSIGN_MAX, Hs > Hp, Ws > Wp, a size <= 0, ...) is returned
+ * before anything is launched. */
+#define PH_GTPREP_MAX_FRAMES 64
+#define PH_GTPREP_MAX_SEGMENTS 254
+int ph_gt_prepare(const uint8_t* seg, const int32_t* row_of, const int32_t* nseg, const float* depth, int frames, int Hs, int Ws, int Hp,
+                  int Wp, int aH, int aW, int Gmax, int Smax, int mode, float* things, float* stuff, float* things_hard,
+                  float* stuff_hard, float* valid, float* depth_out, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

@@ -203,6 +203,8 @@ PH_TRACK_LOSS_MAX_ROIS, PH_TRACK_LOSS_MAX_PAIRS = 128, 64
 
 # the RoIs of the sampled ground-truth masks (polyhead.h ph_gtmask_boxes)
 PH_GTBOX_MAX_FRAMES, PH_GTBOX_BILINEAR, PH_GTBOX_NEAREST = 64, 0, 1
+# the step's ground truth from segment-index maps (polyhead.h ph_gt_prepare)
+PH_GTPREP_MAX_FRAMES, PH_GTPREP_MAX_SEGMENTS = 64, 254
 PH_EINVAL, PH_EWORKSPACE = -1, -4
 
 
@@ -410,6 +412,7 @@ SIGNATURES = {
     "ph_gtmask_boxes_workspace_bytes": (C.c_size_t, [_I, C.POINTER(C.c_int32), _I, _I]),
     "ph_gtmask_boxes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _L, _I, _I,
                                   _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+    "ph_gt_prepare": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

@@ -611,6 +611,39 @@ class StepGT:
         self._table = None                  # `device_table`
         self.status_words = []              # one int64 [B] device tensor per device solve of the step (`assign_desc_device`)
 
+    @classmethod
+    def from_prepared(cls, things, G, labels_h, labels_dev, valid, stuff=None, S=None, sem_cls_h=None, depth=None):
+        """the same object over buffers `ph_gt_prepare` wrote (gt.PreparedGT.step_gt): things [B, max(Gmax, 1), H, W] with zero rows
+        beyond G[b] -- the soft or the hardened stack -- is `pad` as it stands and every image's masks are its leading rows; stuff
+        [B, Smax, H, W] or None (no stuff targets, as `StepGT(m, l, None, None, None, h)`); valid [B, H, W]; depth [B, H, W] or None;
+        labels_h / sem_cls_h the host lists, labels_dev their device copies.  No pass over the masks, no device -> host read."""
+        self = cls.__new__(cls)
+        B = self.B = len(G)
+        self.H, self.W = things.shape[-2:]
+        HW = self.HW = self.H * self.W
+        self.G = [int(g) for g in G]
+        self.Gmax = max(self.G + [0])
+        if tuple(things.shape) != (B, max(self.Gmax, 1), self.H, self.W) or tuple(valid.shape) != (B, self.H, self.W):
+            raise ValueError("StepGT.from_prepared: things must be [B, max(Gmax, 1), H, W] and valid [B, H, W]")
+        self.pad = things
+        self.masks = [things[b, :self.G[b]] for b in range(B)]
+        self.has_sem = stuff is not None
+        self.S = [int(s) for s in S] if self.has_sem else [0] * B
+        self.sem = [stuff[b, :self.S[b]] for b in range(B)] if self.has_sem else [self.masks[0][:0]] * B
+        self.valid = valid
+        self.depth = None if depth is None else depth.reshape(B, HW)
+        self.labels_h = [np.asarray(l, np.int64) for l in labels_h]
+        self.sem_cls_h = [np.asarray(c, np.int64) for c in sem_cls_h] if self.has_sem else [np.zeros(0, np.int64)] * B
+        self.labels_dev = list(labels_dev)
+        rows = np.arange(B, dtype=np.int64)
+        self.mask_base = things.data_ptr() + 4 * HW * things.shape[1] * rows
+        self.sem_base = stuff.data_ptr() + 4 * HW * stuff.shape[1] * rows if self.has_sem else np.array([s.data_ptr() for s in self.sem], np.int64)
+        self.valid_base = valid.data_ptr() + 4 * HW * rows
+        self.depth_base = None if depth is None else depth.data_ptr() + 4 * HW * rows
+        self._table = None
+        self.status_words = []
+        return self
+
     def device_table(self):
         """the ground-truth table `ph_assign_desc` reads (include/polyhead.h): per image the counts, the base addresses and where
         its labels and stuff classes lie, then those.  int64 on the device, built and uploaded on first use, once per step."""

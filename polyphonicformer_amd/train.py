@@ -771,16 +771,13 @@ def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_s
     check_rpn_topology(h)
     if h.assigner is None:
         raise ValueError("forward_train needs train_cfg (assigner / sampler)")
-    gt_raw = gt_masks
-    if h.hard_target:                     # local to the rpn side, as in the reference (kernel_head.py:400-403)
-        gt_masks = [m.bool().float() for m in gt_masks]
     r = rpn_forward(h, feats)
     up = (lambda t: upsample2x(t)) if h.feat_downsample_stride == 2 else (lambda t: t)
     smask, sseg, sdep0 = up(r["mask_preds"]), up(r["seg_preds"]), up(r["depth_pred"])         # :364-398
     N = h.num_proposals + h.num_stuff_classes
     if _fast_assign_ok(h.assigner, h.sampler):
         # round 5: batched assignment (one pixel pass + one D2H for all images), targets as pointer tables, ONE loss call
-        gt = _step_gt(gt_cache, bool(h.hard_target), gt_raw, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
+        gt = _step_gt(gt_cache, bool(h.hard_target), gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
         desc = Lo.assign_desc_device(h, gt, h.assigner, smask.detach(), None, h.num_proposals, h.train_cfg, roi=False) if device_assign else None
         if desc is None:
             assigns = Lo.assign_batch(h.assigner, smask.detach(), None, gt)
@@ -800,6 +797,8 @@ def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_s
         if want_grads:
             losses["_grads"] = kept
         return losses, r
+    if h.hard_target:                     # local to the rpn side, as in the reference (kernel_head.py:400-403); StepGT hardens its own
+        gt_masks = [m.bool().float() for m in gt_masks]
     sdep = sdep0.detach().expand(-1, N, -1, -1)
     srs = []
     for i in range(len(img_metas)):                                                           # :411-426
@@ -958,10 +957,11 @@ def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_m
 
 
 # ---- the step ------------------------------------------------------------------------------------------------------------------
-def _heads_forward_train(rpn, roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, device_assign):
+def _heads_forward_train(rpn, roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, device_assign, gt_cache=None):
     """the two heads on the three post-neck maps, what both steps run: -> (the 24 losses attached to the graph, the final stage's
-    (object_feats, cls_score, mask_preds, scaled_mask_preds), the step's ground-truth cache)"""
-    gt_cache = {}                                           # the step's ground truth (losses.StepGT), shared by the two heads
+    (object_feats, cls_score, mask_preds, scaled_mask_preds), the step's ground-truth cache).  gt_cache: the cache pre-filled
+    (`_prepared_cache`), so that no `losses.StepGT` is derived from the lists."""
+    gt_cache = {} if gt_cache is None else gt_cache         # the step's ground truth (losses.StepGT), shared by the two heads
     rpn_losses, r = rpn_forward_train(rpn, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
                                       gt_cache=gt_cache, device_assign=device_assign)
     k, mask_preds, q = rpn_outputs(rpn, r)
@@ -969,6 +969,17 @@ def _heads_forward_train(rpn, roi, feats, img_metas, gt_masks, gt_labels, gt_sem
                                      gt_sem_seg, gt_sem_cls, gt_depth, gt_cache=gt_cache, device_assign=device_assign)
     losses.update(rpn_losses)                               # polyphonic_former.py:126
     return losses, last, gt_cache
+
+
+def _prepared_cache(prepared, hards):
+    """the ground-truth cache of a step whose ground truth `gt.prepare_gt` left on the device: one `losses.StepGT` per `hard_target`
+    value the step asks for, views of the prepared buffers"""
+    return {bool(h): prepared.step_gt(bool(h)) for h in set(bool(h) for h in hards)}
+
+
+def _prepared_lists(prepared):
+    """(gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth) as `forward_backward` takes them, views of the prepared buffers"""
+    return prepared.gt_masks, prepared.gt_labels, prepared.gt_sem_seg, prepared.gt_sem_cls, prepared.gt_depth
 
 
 class TrainStep:
@@ -1019,13 +1030,21 @@ class TrainStep:
         return torch.stack(self._status).cpu()
 
     def forward_backward(self, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, backward=True):
+        return self._forward_backward(feats, img_metas, (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth), None, backward)
+
+    def forward_backward_prepared(self, feats, img_metas, gt, backward=True):
+        """`forward_backward` on ground truth `gt.prepare_gt` left on the device (gt: a `gt.PreparedGT`): the step's `losses.StepGT`s
+        are views of the prepared buffers, nothing is derived from the mask lists and nothing is read back"""
+        cache = _prepared_cache(gt, (self.rpn.hard_target, self.roi.hard_target))
+        return self._forward_backward(feats, img_metas, _prepared_lists(gt), cache, backward)
+
+    def _forward_backward(self, feats, img_metas, lists, gt_cache, backward):
         feats = [f.detach().float().contiguous().requires_grad_(True) for f in feats]
         for f in feats:
             if not f.is_cuda:
                 raise _lib.PolyheadError("the post-neck maps must live on the GPU: libpolyhead has no CPU path")
         with torch.enable_grad(), Lo.reduce_group(self.group):
-            losses, _, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                                       self.device_assign)
+            losses, _, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
             self._status = [w for g in gt_cache.values() for w in g.status_words]
             total = parse_losses(losses)
             if backward:
@@ -1112,6 +1131,26 @@ class VideoTrainStep:
         """x / x_ref: the FPN levels of the key and the reference frames; the ground truth as the reference has it at :185 (things and
         stuff split, at the assign resolution).  -> (losses: the 24 image losses + loss_track + loss_track_aux, objective, gradients of
         the key frame's FPN levels: neck path + RoIAlign path).  The reference frame's levels get no gradient."""
+        return self._forward_backward(x, x_ref, img_metas, (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, gt_instance_ids),
+                                      (ref_gt_masks, ref_gt_labels, ref_gt_instance_ids), pad_hw, backward, ref_img_metas)
+
+    def forward_backward_prepared(self, x, x_ref, img_metas, gt, ref_gt, pad_hw, backward=True, ref_img_metas=None):
+        """`forward_backward` on ground truth `gt.prepare_gt` left on the device: gt / ref_gt are the `gt.PreparedGT` of the key and
+        the reference frames (both prepared with gt_instance_ids).  Every `losses.StepGT` of the step is a view of the prepared
+        buffers; the reference frames' holds their things alone, as `forward_backward` builds it."""
+        if gt.gt_instance_ids is None or ref_gt.gt_instance_ids is None:
+            raise ValueError("VideoTrainStep.forward_backward_prepared: prepare both frames' ground truth with gt_instance_ids")
+        cache = _prepared_cache(gt, (self.rpn.hard_target, self.roi.hard_target, False))
+        return self._forward_backward(x, x_ref, img_metas, _prepared_lists(gt) + (gt.gt_instance_ids,),
+                                      (ref_gt.gt_masks, ref_gt.gt_labels, ref_gt.gt_instance_ids), pad_hw, backward, ref_img_metas,
+                                      gt_cache=cache, ref_gt=ref_gt.step_gt(False, with_stuff=False))
+
+    def _forward_backward(self, x, x_ref, img_metas, key, ref, pad_hw, backward, ref_img_metas, gt_cache=None, ref_gt=None):
+        """key: (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, gt_instance_ids), ref: (ref_gt_masks, ref_gt_labels,
+        ref_gt_instance_ids); gt_cache / ref_gt: the key frames' cache and the reference frames' `losses.StepGT` where they are
+        prepared, else derived from the lists where the step first needs them"""
+        lists, gt_instance_ids = key[:5], key[5]
+        ref_gt_masks, ref_gt_labels, ref_gt_instance_ids = ref
         x = [f.detach().float().contiguous().requires_grad_(True) for f in x]
         x_ref = [f.detach().float().contiguous() for f in x_ref]
         for f in x + x_ref:
@@ -1119,11 +1158,11 @@ class VideoTrainStep:
                 raise _lib.PolyheadError("the FPN levels must live on the GPU: libpolyhead has no CPU path")
         with torch.enable_grad(), Lo.reduce_group(self.group):
             feats = neck_forward_train(self.neck, x)                                                   # :185
-            losses, last, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls,
-                                                          gt_depth, self.device_assign)
+            losses, last, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
             ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas)
-            gt = _step_gt(gt_cache, False, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)       # the soft masks (:259)
-            ref_gt = Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
+            gt = _step_gt(gt_cache, False, *lists)                                                     # the soft masks (:259)
+            if ref_gt is None:
+                ref_gt = Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
             losses.update(video_track_branch(self.track_head, self.track_assigner, x, x_ref, last, ref_last, gt, ref_gt, gt_instance_ids,
                                              ref_gt_instance_ids, pad_hw, self.roi.num_proposals, self.roi.num_thing_classes,
                                              self.device_assign, self.strides, self.finest_scale))
