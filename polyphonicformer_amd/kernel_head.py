@@ -193,8 +193,9 @@ class KernelHead(nn.Module):
 
     def forward_train(self, img, img_metas, gt_masks, gt_labels, gt_sem_seg=None, gt_sem_cls=None, gt_depth=None, with_grads=False):
         """kernel_head.py:349-454: the decode in training mode, the x`feat_downsample_stride` upsample of the mask / seg /
-        depth predictions, the Hungarian assignment on the detached masks (`assigner.py`), pseudo sampling, `get_targets`,
-        `loss` and `depth_dense`; returns the reference's 9-tuple, the stuff rows appended when `cat_stuff_mask`.
+        depth predictions, the Hungarian assignment on the detached masks, the losses on the assigned targets (the shipped
+        configuration: descriptors into the step's ground truth and one `ph_train_losses` call, `losses.fused_losses`; any other
+        assigner or sampler: per-image sampling, `get_targets`, `losses.rpn_losses`) and `depth_dense`; returns the reference's 9-tuple, the stuff rows appended when `cat_stuff_mask`.
         `gt_depth`: [B, 1, H, W] at the scaled size, as the dataset pipeline delivers it.
         It TRAINS: the forward runs as differentiable libpolyhead operations (`train.rpn_forward_train`, hand-written
         backward of every map-sized product), the 'loss' entries of the returned dict are attached to one autograd node, and

@@ -184,8 +184,10 @@ class KernelUpdateIterHead(nn.Module):
                       depth_preds=None, depth_feats=None, depth_proposal=None, gt_bboxes_ignore=None, imgs_whwh=None,
                       gt_bboxes=None, gt_sem_seg=None, gt_sem_cls=None, with_grads=False):
         """kernel_update.py:159-280: every stage's predictions, the Hungarian assignment on the previous stage's detached
-        predictions (`assigner.py`, ph_match_sums), pseudo sampling, `get_targets` and the stage's losses -- the dict of
-        `s{stage}_{loss}` the reference returns (with `tracking=True` also object_feats, cls_score, mask_preds,
+        predictions (ph_match_sums) and the stage's losses on the assigned targets.  On the shipped configuration the targets are
+        descriptors into the step's ground truth and one `ph_train_losses` call per stage evaluates them (`losses.build_desc`,
+        `losses.fused_losses`); any other assigner or sampler goes through per-image sampling, `get_targets` and
+        `losses.stage_losses`.  Returns the dict of `s{stage}_{loss}` the reference returns (with `tracking=True` also object_feats, cls_score, mask_preds,
         scaled_mask_preds).  It TRAINS: `train.roi_forward_train` runs the stages as differentiable libpolyhead operations
         and attaches the 'loss' entries to one autograd node per stage, so that `sum(losses).backward()` -- what mmdet's
         `_parse_losses` + `backward()` do (mmdet/models/detectors/base.py:176-199) -- leaves the gradient of the objective

@@ -558,6 +558,7 @@ def rpn_get_targets(head, sampling_results, gt_mask, rpn_train_cfg, concat=True,
 # result lives on the host, every target row is a ground-truth row that already lies in HBM, so the host writes pointer tables
 # (numpy, ~100 us), uploads them in one copy and ONE C call evaluates the head's or stage's losses and gradients.
 # =================================================================================================================================
+import copy  # noqa: E402
 import ctypes as C  # noqa: E402
 
 import numpy as np  # noqa: E402
@@ -658,8 +659,15 @@ class StepGT:
                 tab[o:o + self.G[b]] = self.labels_h[b]
                 tab[o + self.G[b]:o + self.G[b] + S] = self.sem_cls_h[b]
                 o += self.G[b] + S
-            self._table = torch.from_numpy(tab).to(self.valid.device, non_blocking=True)
+            self._table = torch.from_numpy(tab).to(self.pad.device, non_blocking=True)
         return self._table
+
+    def all_pixels(self):
+        """the same ground truth without its valid map, as an assigner that counts every pixel reads it (MaskHungarianAssigner,
+        assigner.py:199-360): a shallow copy -- the tensors, the lists and `status_words` are this object's own"""
+        v = copy.copy(self)
+        v.valid = None
+        return v
 
 
 def _assign_cost(assigner, pred, cls_pred, gt):
@@ -710,33 +718,61 @@ def assign_batch(assigner, pred, cls_pred, gt):
     return out
 
 
-class LossDesc:
-    """the pointer tables of one head / stage on the device (one upload) + what the host knows about them"""
+def assign_match(assigner, pred, cls_pred, gt, device_assign=False):
+    """the same assignment as a table on the device: `match` int32 [B, max(Gmax, 1)], the prediction row of every ground truth or
+    -1.  Host path: `assign_batch` (one download, scipy) and one upload.  device_assign: the cost stays where `_assign_cost` forms
+    it and `ph_assign_solve` solves it (its status words are appended to gt.status_words); beyond the kernel's limits, or with
+    every cost weight zero, the host path runs."""
+    B, Np = pred.shape[:2]
+    ld, dev = max(gt.Gmax, 1), pred.device
+    if gt.Gmax == 0:
+        return torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+    if device_assign and max(Np, gt.Gmax) <= _lib.PH_ASSIGN_MAX:
+        cost = _assign_cost(assigner, pred, cls_pred, gt)
+        if torch.is_tensor(cost):
+            cost = cost.detach().float().contiguous()
+            match = torch.full((B, ld), -1, dtype=torch.int32, device=dev)
+            status = torch.empty((B,), dtype=torch.int64, device=dev)
+            counts = gt.device_table().view(torch.int32)                   # word 0 of every record: G_b (little endian int64)
+            _lib.check(_lib.load().ph_assign_solve(_lib.ptr(cost), B, Np, ld, _lib.ptr(counts), 2 * _lib.PH_ASSIGN_GT_WORDS, _lib.ptr(match),
+                                                   _lib.ptr(status), _lib.stream_ptr()), "ph_assign_solve")
+            gt.status_words.append(status)
+            return match
+    rows = np.full((B, ld), -1, np.int32)
+    for i, (r, c) in enumerate(assign_batch(assigner, pred, cls_pred, gt)):
+        rows[i, c] = r
+    return torch.from_numpy(rows).to(dev, non_blocking=True)
 
-    def __init__(self, dev, sections):
-        off, total = {}, 0
-        for k, a in sections.items():
-            off[k] = total
-            total += (a.nbytes + 15) // 16 * 16
-        buf = np.zeros(max(total, 16), dtype=np.uint8)
-        for k, a in sections.items():
-            buf[off[k]:off[k] + a.nbytes] = a.view(np.uint8).reshape(-1)
-        self.blob = torch.from_numpy(buf).to(dev, non_blocking=True)
-        base = self.blob.data_ptr()
-        self.ptr = {k: C.c_void_p(base + o) for k, o in off.items()}
-        self.n = {k: a.size for k, a in sections.items()}
+
+class LossDesc:
+    """the pointer tables of one head / stage on the device + what the host knows about them: everything `fused_losses` reads.
+    blob: the tables, uint8 on the device; offsets / n: per table its byte offset in the blob and its entry count; N rows per image,
+    P of all rows positive; `gt` keeps the ground-truth tensors the pointers address alive"""
+
+    def __init__(self, gt, N, P, depth_rows, roi, blob, offsets, n):
+        self.blob, self.n = blob, n
+        base = blob.data_ptr()
+        self.ptr = {k: C.c_void_p(base + o) for k, o in offsets.items()}
+        self.B, self.N, self.R, self.P, self.depth_rows, self.roi = gt.B, N, gt.B * N, P, depth_rows, roi
+        self.has_depth = gt.depth_base is not None
+        self.gt = gt
+
+
+def _desc_rows(head, gt, cfg, num_proposals, roi):
+    """(N, pos_weight) of a head's or stage's descriptor: the stuff rows follow the proposals where the roi head has stuff targets"""
+    N = num_proposals + head.num_stuff_classes if (roi and gt.has_sem) else num_proposals
+    return N, 1.0 if cfg.pos_weight <= 0 else float(cfg.pos_weight)
 
 
 def build_desc(head, gt, assigns, num_proposals, cfg, roi):
     """roi=True : KernelUpdateHead._get_target_single (kernel_update_head.py:443-531) for B images: N = num_proposals + stuff rows
     roi=False: KernelHead._get_target_single (kernel_head.py:571-647): N = num_proposals rows, dense semantic target, the depth
-    items of an image all on its ONE direct depth map"""
+    items of an image all on its ONE direct depth map.  The tables are packed on the host and uploaded once."""
     B, HW = gt.B, gt.HW
     L, ns, nt = head.num_classes, head.num_stuff_classes, head.num_thing_classes
     Np = num_proposals
-    N = Np + ns if (roi and gt.has_sem) else Np
+    N, pw = _desc_rows(head, gt, cfg, Np, roi)
     R = B * N
-    pw = 1.0 if cfg.pos_weight <= 0 else float(cfg.pos_weight)
     HW4 = 4 * HW
     tptr, wptr = np.zeros(R, np.int64), np.zeros(R, np.int64)
     labels = np.full(R, L, np.int64)
@@ -806,16 +842,31 @@ def build_desc(head, gt, assigns, num_proposals, cfg, roi):
         sec["label_w"] = label_w.reshape(-1)
     else:
         sec.update(sstart=np.asarray(s_cnt, np.int32), sit_m=np.asarray(s_m if s_m else [0], np.int64), sit_l=np.asarray(s_l if s_l else [0], np.int32))
-    d = LossDesc(gt.valid.device, sec)
-    d.B, d.N, d.R, d.P, d.depth_rows, d.roi, d.has_depth = B, N, R, int(len(pos_rows)), depth_rows, roi, gt.depth_base is not None
-    d.gt = gt              # keeps the ground-truth tensors the pointers address alive
-    return d
+    off, total = {}, 0
+    for k, a in sec.items():
+        off[k] = total
+        total += (a.nbytes + 15) // 16 * 16
+    buf = np.zeros(max(total, 16), dtype=np.uint8)
+    for k, a in sec.items():
+        buf[off[k]:off[k] + a.nbytes] = a.view(np.uint8).reshape(-1)
+    blob = torch.from_numpy(buf).to(gt.valid.device, non_blocking=True)
+    return LossDesc(gt, N, int(len(pos_rows)), depth_rows, roi, blob, off, {k: a.size for k, a in sec.items()})
 
 
-class DeviceDesc:
-    """what `fused_losses` reads of a `LossDesc` -- `ptr`, `n`, B / N / R / P / depth_rows / roi / has_depth -- with the tables
-    written by `ph_assign_desc`: the counts are the host's (they follow from the ground-truth counts), the contents never leave
-    the device.  `match` int32 [B, ldg] (prediction row per ground-truth column, -1 unmatched), `status` int64 [B]."""
+class DeviceDesc(LossDesc):
+    """a `LossDesc` whose tables `ph_assign_desc` writes: the counts are the host's (they follow from the ground-truth counts), the
+    contents never leave the device.  What a later stage needs to use the assignment again (`prev=`) stays with it: `match` int32
+    [B, ldg] (prediction row per ground-truth column, -1 unmatched), `status` int64 [B], the kernel's cfg, counts and table."""
+
+    def __init__(self, gt, N, roi, cfg, counts, lay, match, status, ldg):
+        B, L = gt.B, cfg.L
+        R, P, nd, nsit, depth_rows = B * N, int(lay.P), int(lay.depth_items), int(lay.seg_items), int(lay.depth_rows)
+        n = dict(tptr=R, wptr=R, labels=R, pos_u8=R, pos_rows=max(P, 1), dstart=depth_rows + 1, dit_t=max(nd, 1), dit_w=max(nd, 1), dit_s=max(nd, 1))
+        n.update(dict(label_w=R * L) if roi else dict(sstart=B + 1, sit_m=max(nsit, 1), sit_l=max(nsit, 1)))
+        blob = torch.empty((lay.total_bytes,), dtype=torch.uint8, device=gt.valid.device)
+        super().__init__(gt, N, P, depth_rows, roi, blob, {k: getattr(lay, k) for k in n}, n)
+        self.cfg, self.counts, self.table = cfg, counts, gt.device_table()
+        self.match, self.status, self.ldg = match, status, ldg
 
     def launch(self, cost):
         """`ph_assign_desc` into this descriptor's blob: solve `cost` [B, Np, ldg] (None: keep `match`), write the tables.
@@ -854,7 +905,7 @@ def assign_desc_device(head, gt, assigner, pred, cls_pred, num_proposals, cfg, r
     B, HW = gt.B, gt.HW
     L, ns, nt = head.num_classes, head.num_stuff_classes, head.num_thing_classes
     Np = num_proposals
-    N = Np + ns if (roi and gt.has_sem) else Np
+    N, pw = _desc_rows(head, gt, cfg, Np, roi)
     has_depth = gt.depth_base is not None
     counts = _assign_counts(gt, head, roi)
     if (counts is None or B > _lib.PH_ASSIGN_MAX_B or max(Np, gt.Gmax, ns) > _lib.PH_ASSIGN_MAX or (roi and has_depth and N == Np)
@@ -863,7 +914,7 @@ def assign_desc_device(head, gt, assigner, pred, cls_pred, num_proposals, cfg, r
     G, S, last = counts
     dev = gt.valid.device
     c = _lib.AssignCfg(B=B, Np=Np, N=N, L=L, n_thing=nt, n_stuff=ns, roi=int(roi), has_sem=int(gt.has_sem), has_depth=int(has_depth),
-                       pos_weight=1.0 if cfg.pos_weight <= 0 else float(cfg.pos_weight), HW=HW)
+                       pos_weight=pw, HW=HW)
     lay = _lib.AssignLayout()
     ip = lambda a: a.ctypes.data_as(C.c_void_p)
     _lib.check(lib.ph_assign_desc_layout(C.byref(c), ip(G), ip(S), ip(last), C.byref(lay)), "ph_assign_desc_layout")
@@ -880,22 +931,13 @@ def assign_desc_device(head, gt, assigner, pred, cls_pred, num_proposals, cfg, r
             assert cost.shape == (B, Np, ldg)
         match = torch.empty((B, max(ldg, 1)), dtype=torch.int32, device=dev)
         status = torch.empty((B,), dtype=torch.int64, device=dev)
-    d = DeviceDesc()
-    d.cfg, d.counts, d.table = c, counts, gt.device_table()
-    d.blob, d.match, d.status, d.ldg = torch.empty((lay.total_bytes,), dtype=torch.uint8, device=dev), match, status, ldg
+    d = DeviceDesc(gt, N, roi, c, counts, lay, match, status, ldg)
     rc = d.launch(cost)
     if rc == _lib.PH_EUNSUPPORTED:
         return None
     _lib.check(rc, "ph_assign_desc")
     if prev is None:
         gt.status_words.append(status)
-    base = d.blob.data_ptr()
-    R, P, nd, nsit, depth_rows = B * N, int(lay.P), int(lay.depth_items), int(lay.seg_items), int(lay.depth_rows)
-    d.n = dict(tptr=R, wptr=R, labels=R, pos_u8=R, pos_rows=max(P, 1), dstart=depth_rows + 1, dit_t=max(nd, 1), dit_w=max(nd, 1), dit_s=max(nd, 1))
-    d.n.update(dict(label_w=R * L) if roi else dict(sstart=B + 1, sit_m=max(nsit, 1), sit_l=max(nsit, 1)))
-    d.ptr = {k: C.c_void_p(base + getattr(lay, k)) for k in d.n}
-    d.B, d.N, d.R, d.P, d.depth_rows, d.roi, d.has_depth = B, N, R, P, depth_rows, roi, has_depth
-    d.gt = gt              # keeps the ground-truth tensors the pointers address alive
     return d
 
 

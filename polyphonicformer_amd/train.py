@@ -21,6 +21,8 @@ libpolyhead kernel, forward and backward; torch is the autograd bookkeeping betw
 The result is checked against the reference's own forward + autograd backward (tests/golden/train_step.npz:
 every loss, the objective and the gradient of every parameter and of the three input maps)."""
 import ctypes as C
+import types
+import weakref
 
 import torch
 
@@ -31,16 +33,14 @@ BIN_THR = 1.5 * 2.0 ** -24          # sigmoid(z) > 0.5 in fp32 (csrc/ph_common.h
 
 
 def _gpu32(t, name):
-    if not t.is_cuda:
-        raise _lib.PolyheadError(f"{name} must live on the GPU: libpolyhead has no CPU path")
+    Lo._gpu(t, name)
     return t.detach().contiguous().float()
 
 
 def _param32(p, name="parameter"):
     """a parameter whose storage a kernel reads through a raw pointer: fp32, contiguous, on the GPU -- anything else would be read as
     fp32 garbage with no error (a head cast to half / bf16, a non-contiguous view), so it is refused"""
-    if not p.is_cuda:
-        raise _lib.PolyheadError(f"{name} must live on the GPU: libpolyhead has no CPU path")
+    Lo._gpu(p, name)
     if p.dtype != torch.float32 or not p.is_contiguous():
         raise _lib.PolyheadError(f"training forward: fp32 contiguous parameters only ({name}: {p.dtype}, contiguous={p.is_contiguous()})")
     return p.detach()
@@ -303,7 +303,6 @@ def _stage_meta(head):
             p = plist[i if i < QT_NPARAM else QT_NPARAM + j]
             offsets.append(off); sizes.append(p.numel()); shapes.append(tuple(p.shape))
             off += (p.numel() + 3) // 4 * 4
-        import weakref
         c = dict(key=key, L=head.num_classes, F=P["ffn.layers.0.0.weight"].shape[0], offsets=offsets, sizes=sizes, shapes=shapes, total=off,
                  module=weakref.ref(head))
         if P["fc_cls.weight"].shape[0] != c["L"] or P["feat_transform.conv.weight"].shape[:2] != (256, 256) or head.attention.attn.num_heads != 8:
@@ -592,7 +591,6 @@ def track_forward_train(track_head, feats, ref_feats, rois, ref_rois, key_gt_ind
     [n, 5] (0, x1, y1, x2, y2) -- the caller computes the boxes from its masks; key_gt_inds[i] / ref_gt_inds[i]: the RoIs'
     pos_assigned_gt_inds; gt_match_indices[i]: per key ground truth its index among the reference frame's or -1.
     -> {'loss_track', 'loss_track_aux'} attached to the graph."""
-    import types
     from .track_head import roi_extract
     B = len(feats)
     if not (B == len(ref_feats) == len(rois) == len(ref_rois) == len(key_gt_inds) == len(ref_gt_inds) == len(gt_match_indices)) or B == 0:
@@ -624,8 +622,17 @@ def gt_match_indices(gt_ids, ref_ids):
 
 
 def _track_assign_ok(assigner):
+    """what the batched assignment covers (`losses._assign_cost`): one-to-one mask Hungarian matching on class / mask / dice costs,
+    no weighted depth cost"""
     from .assigner import _MaskAssignerBase
     return isinstance(assigner, _MaskAssignerBase) and assigner.topk == 1 and (assigner.depth_cost is None or assigner.depth_cost.weight == 0)
+
+
+def _fast_assign_ok(assigner, sampler):
+    """the descriptor path covers the shipped training configuration (polyphonic_former.py:170-192): an assigner the batched
+    assignment covers, and the pseudo sampler"""
+    from .assigner import MaskPseudoSampler
+    return _track_assign_ok(assigner) and isinstance(sampler, MaskPseudoSampler)
 
 
 def track_sample(assigner, mask_preds, cls_scores, gt, num_proposals, num_thing_classes, device_assign=False):
@@ -633,38 +640,17 @@ def track_sample(assigner, mask_preds, cls_scores, gt, num_proposals, num_thing_
     dice costs over ALL pixels, no valid map, no depth cost) on the detached final-stage scaled_mask_preds[:, :Np] and
     cls_scores[:, :Np, :n_thing] against the UN-hardened thing masks at the assign resolution (`gt`: a soft `losses.StepGT`).  Pseudo
     sampling is the identity on the assignment, so what comes back is the assignment itself: `match` int32 [B, max(Gmax, 1)] on the
-    device, the prediction row of every ground truth or -1 -- the form `track_head.gt_mask_rois` takes.  Host path:
-    `losses.assign_batch` (one download, scipy); device_assign: the cost stays where `losses._assign_cost` forms it and `ph_assign_solve`
-    solves it (its status words are appended to gt.status_words); beyond the kernel's limits the host path runs."""
-    import types
-    import numpy as np
+    device, the prediction row of every ground truth or -1 -- the form `track_head.gt_mask_rois` takes
+    (`losses.assign_match`: solved on the host, or with device_assign by `ph_assign_solve`, whose status words are appended to
+    gt.status_words)."""
     if not _track_assign_ok(assigner):
         raise NotImplementedError("track_sample: one-to-one Hungarian matching on class / mask / dice costs (the shipped track_train_cfg)")
     Np, nt = int(num_proposals), int(num_thing_classes)
     pred = _gpu32(mask_preds, "scaled_mask_preds")[:, :Np]
     cls = None if cls_scores is None else cls_scores.detach()[:, :Np, :nt].float()
-    B, dev = gt.B, pred.device
-    if pred.shape[0] != B or pred.shape[1] != Np:
+    if pred.shape[0] != gt.B or pred.shape[1] != Np:
         raise ValueError("track_sample: mask_preds must hold num_proposals rows for every image of the ground truth")
-    ld = max(gt.Gmax, 1)
-    all_px = types.SimpleNamespace(pad=gt.pad, valid=None, Gmax=gt.Gmax, G=gt.G, labels_dev=gt.labels_dev, B=B)     # assigner.py:199-360
-    if gt.Gmax == 0:
-        return torch.full((B, ld), -1, dtype=torch.int32, device=dev)
-    if device_assign and max(Np, gt.Gmax) <= _lib.PH_ASSIGN_MAX:
-        cost = Lo._assign_cost(assigner, pred, cls, all_px)
-        if torch.is_tensor(cost):
-            cost = cost.detach().float().contiguous()
-            match = torch.full((B, ld), -1, dtype=torch.int32, device=dev)
-            status = torch.empty((B,), dtype=torch.int64, device=dev)
-            counts = gt.device_table().view(torch.int32)                   # word 0 of every record: G_b (little endian int64)
-            _lib.check(_lib.load().ph_assign_solve(_lib.ptr(cost), B, Np, ld, _lib.ptr(counts), 2 * _lib.PH_ASSIGN_GT_WORDS, _lib.ptr(match),
-                                                   _lib.ptr(status), _lib.stream_ptr()), "ph_assign_solve")
-            gt.status_words.append(status)
-            return match
-    rows = np.full((B, ld), -1, np.int32)
-    for i, (r, c) in enumerate(Lo.assign_batch(assigner, pred, cls, all_px)):
-        rows[i, c] = r
-    return torch.from_numpy(rows).to(dev, non_blocking=True)
+    return Lo.assign_match(assigner, pred, cls, gt.all_pixels(), device_assign)
 
 
 def video_track_branch(track_head, track_assigner, x, x_ref, key_last, ref_last, gt, ref_gt, gt_ids, ref_ids, pad_hw, num_proposals,
@@ -744,14 +730,6 @@ def _valid_pixels(gt_masks_i, gt_sem_seg_i):
     return v.float()
 
 
-def _fast_assign_ok(assigner, sampler):
-    """the batched descriptor path covers the shipped training configuration: one-to-one Hungarian matching on class / mask / dice
-    costs (DepthCost weight 0, polyphonic_former.py:170-192) and the pseudo sampler"""
-    from .assigner import _MaskAssignerBase, MaskPseudoSampler
-    return (isinstance(assigner, _MaskAssignerBase) and assigner.topk == 1 and isinstance(sampler, MaskPseudoSampler)
-            and (assigner.depth_cost is None or assigner.depth_cost.weight == 0))
-
-
 def _step_gt(cache, hard, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth):
     if cache is None:
         cache = {}
@@ -782,37 +760,25 @@ def rpn_forward_train(h, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_s
         if desc is None:
             assigns = Lo.assign_batch(h.assigner, smask.detach(), None, gt)
             desc = Lo.build_desc(h, gt, assigns, h.num_proposals, h.train_cfg, roi=False)
-        kept = {}
-
-        def fn(mp, sp, dp):
-            ls, g = Lo.fused_losses(h, desc, mp, None, dp, sp, with_grads=True)
-            kept.update(mask_pred=g["mask_pred"], seg_preds=g["seg_preds"], depth_pred=g["depth_pred"])
-            return ls, (g["mask_pred"], g["seg_preds"], g["depth_pred"])
-
-        values = {}
-        total = _Objective.apply(fn, values, smask, sseg, sdep0)
-        losses = _attach(values, total)
-        if gt_depth is not None:
-            losses["depth_dense"] = Lo.dense_depth_loss(h, sdep0.detach(), gt_depth)          # :438-442, logged only
-        if want_grads:
-            losses["_grads"] = kept
-        return losses, r
-    if h.hard_target:                     # local to the rpn side, as in the reference (kernel_head.py:400-403); StepGT hardens its own
-        gt_masks = [m.bool().float() for m in gt_masks]
-    sdep = sdep0.detach().expand(-1, N, -1, -1)
-    srs = []
-    for i in range(len(img_metas)):                                                           # :411-426
-        valid = _valid_pixels(gt_masks[i], gt_sem_seg[i])
-        ar = h.assigner.assign(smask[i].detach(), None, gt_masks[i], gt_labels[i], img_metas[i], depth_pred=sdep[i],
-                               gt_depth=gt_depth[i], gt_valid=valid)
-        sr = h.sampler.sample(ar, smask[i].detach(), gt_masks[i], depth=sdep[i])
-        sr.valid_mask = valid
-        srs.append(sr)
-    targets = h.get_targets(srs, gt_masks, h.train_cfg, True, gt_sem_seg=gt_sem_seg, gt_sem_cls=gt_sem_cls, gt_depth=gt_depth)
+        loss_fn = lambda mp, sp, dp: Lo.fused_losses(h, desc, mp, None, dp, sp, with_grads=True)
+    else:
+        if h.hard_target:                 # local to the rpn side, as in the reference (kernel_head.py:400-403); StepGT hardens its own
+            gt_masks = [m.bool().float() for m in gt_masks]
+        sdep = sdep0.detach().expand(-1, N, -1, -1)
+        srs = []
+        for i in range(len(img_metas)):                                                       # :411-426
+            valid = _valid_pixels(gt_masks[i], gt_sem_seg[i])
+            ar = h.assigner.assign(smask[i].detach(), None, gt_masks[i], gt_labels[i], img_metas[i], depth_pred=sdep[i],
+                                   gt_depth=gt_depth[i], gt_valid=valid)
+            sr = h.sampler.sample(ar, smask[i].detach(), gt_masks[i], depth=sdep[i])
+            sr.valid_mask = valid
+            srs.append(sr)
+        targets = h.get_targets(srs, gt_masks, h.train_cfg, True, gt_sem_seg=gt_sem_seg, gt_sem_cls=gt_sem_cls, gt_depth=gt_depth)
+        loss_fn = lambda mp, sp, dp: Lo.rpn_losses(h, mp, sp, dp.expand(-1, N, -1, -1), *targets, with_grads=True)
     kept = {}
 
     def fn(mp, sp, dp):
-        ls, g = Lo.rpn_losses(h, mp, sp, dp.expand(-1, N, -1, -1), *targets, with_grads=True)
+        ls, g = loss_fn(mp, sp, dp)
         kept.update(mask_pred=g["mask_pred"], seg_preds=g["seg_preds"], depth_pred=g["depth_pred"])
         return ls, (g["mask_pred"], g["seg_preds"], g["depth_pred"])
 
@@ -844,101 +810,37 @@ def roi_forward_train(ih, x, dfe, k, mask_preds, q, depth_pred, img_metas, gt_ma
                       want_grads=False, gt_cache=None, device_assign=False):
     """KernelUpdateIterHead.forward_train, kernel_update.py:159-280.  x, dfe [B, C, H, W]; k / q [B, N, C] kernels and depth
     kernels; mask_preds [B, N, H, W]; depth_pred [B, 1, H, W].  Every stage: forward in training form, the Hungarian
-    assignment on the previous stage's detached predictions, pseudo sampling, targets, the stage's losses as one autograd
-    node.  Returns (losses, last): losses = {s{stage}_{name}} weighted and attached (`_attach`), last = the final stage's
-    (object_feats, cls_score, mask_preds, scaled_mask_preds)."""
+    assignment on the previous stage's detached predictions and the stage's losses on the assigned targets as one autograd node.
+    Where the targets come from is the one thing that differs between configurations: descriptors into the step's ground truth
+    (`_DescTargets`, the shipped configuration) or per-image sampling and materialised targets (`_ListTargets`).  Returns (losses,
+    last): losses = {s{stage}_{name}} weighted and attached (`_attach`), last = the final stage's (object_feats, cls_score,
+    mask_preds, scaled_mask_preds)."""
     if ih.post_assign:
         raise NotImplementedError                       # as the reference (:222-223)
     if not ih.mask_assigner:
         raise ValueError("forward_train needs train_cfg (assigner / sampler per stage)")
-    B, N = k.shape[:2]
     up = ih.mask_head[0].mask_upsample_stride
     if up not in (1, 2):
         raise NotImplementedError("libpolyhead: mask_upsample_stride must be 1 or 2")
     scale = (lambda t: upsample2x(t)) if up == 2 else (lambda t: t)
     prev_mask = scale(mask_preds.detach()).detach()                                           # :179-191
     if all(_fast_assign_ok(a, sm) for a, sm in zip(ih.mask_assigner, ih.mask_sampler)):
-        return _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth,
-                                       want_grads, gt_cache, device_assign)
-    prev_depth = scale(depth_pred.detach().expand(-1, N, -1, -1).contiguous()).detach()
-    prev_cls = [None] * B                                                                      # :193-196
-    if ih.hard_target:
-        gt_masks = [m.bool().float() for m in gt_masks]
-    # the pixels some ground-truth mask covers (:238): the same for every stage -- evaluated once per image instead of once per
-    # image and stage (a 24 MB concatenation + reduction each at the assign stride of cfg2)
-    valids = [_valid_pixels(gt_masks[i], gt_sem_seg[i]) for i in range(B)]
-    total, m, assign, values, grads = 0.0, mask_preds, [], {}, []
+        gt = _step_gt(gt_cache, bool(ih.hard_target), gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
+        targets = _DescTargets(ih, gt, device_assign)
+    else:
+        targets = _ListTargets(ih, scale, depth_pred, k.shape[1], img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
+    total, m, values, grads, prev_cls = 0.0, mask_preds, {}, [], None                         # :193-196
     cls = smask = None
     for s in range(ih.num_stages):
         head = ih.mask_head[s]
         check_stage_topology(head)
         cls, m, k, depth, q = stage_forward(head, x, dfe, k, m, q)
         smask, sdepth = scale(m), scale(depth)                                                 # training: every stage (:131)
-        srs = []
-        if s < ih.assign_stages:
-            assign = []
-        for i in range(B):
-            valid = valids[i]
-            if s < ih.assign_stages:
-                c = None if prev_cls[i] is None else prev_cls[i][:ih.num_proposals, :ih.num_thing_classes]
-                assign.append(ih.mask_assigner[s].assign(prev_mask[i][:ih.num_proposals], c, gt_masks[i], gt_labels[i], img_metas[i],
-                                                         depth_pred=prev_depth[i][:ih.num_proposals], gt_depth=gt_depth[i],
-                                                         gt_valid=valid))
-            sr = ih.mask_sampler[s].sample(assign[i], smask[i].detach(), gt_masks[i], depth=sdepth[i].detach())
-            sr.valid_mask = valid
-            srs.append(sr)
-        targets = head.get_targets(srs, gt_masks, gt_labels, ih.train_cfg[s], True, gt_sem_seg=gt_sem_seg, gt_sem_cls=gt_sem_cls,
-                                   gt_depth=gt_depth)
+        loss_fn = targets.stage(s, head, prev_mask, prev_cls, smask, sdepth)
         kept = {}
 
-        def fn(cs, mp, dp, head=head, targets=targets, kept=kept):
-            ls, g = Lo.stage_losses(head, cs, mp, dp, *targets, with_grads=True)
-            kept.update(g)
-            return ls, (g["cls_score"], g["mask_pred"], g["depth_pred"])
-
-        box = {}
-        w = ih.stage_loss_weights[s]
-        total = total + w * _Objective.apply(fn, box, cls, smask, sdepth)
-        for key, v in box.items():
-            values[f"s{s}_{key}"] = v * w
-        grads.append(kept)
-        prev_mask, prev_cls, prev_depth = smask.detach(), cls.detach(), sdepth.detach()       # :273-276
-    losses = _attach(values, total)
-    if want_grads:
-        losses["_grads"] = grads
-    return losses, (k, cls, m, smask)
-
-
-def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, want_grads,
-                            gt_cache, device_assign=False):
-    """the stage loop of `roi_forward_train` on the batched / descriptor path (round 5): per stage ONE `_Stage` node, two
-    upsamples, one batched assignment (`ph_match_sums` over all images + one D2H + the host Hungarian solves), one pointer-table
-    upload and ONE loss call (`ph_train_losses`).  No sampler gathers, no materialised targets: every target row is a row of the
-    step's ground truth (`losses.StepGT`).  The previous stage's depth predictions only feed the DepthCost, whose weight is 0
-    on this path, so they are not formed.  device_assign: assignment and tables by `ph_assign_desc` on the device instead (no D2H,
-    no host solve, no upload); a stage the kernels do not cover takes the host path."""
-    B = k.shape[0]
-    Np, nt = ih.num_proposals, ih.num_thing_classes
-    gt = _step_gt(gt_cache, bool(ih.hard_target), gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
-    total, m, values, grads, assigns, prev_cls, ddesc = 0.0, mask_preds, {}, [], None, None, None
-    cls = smask = None
-    for s in range(ih.num_stages):
-        head = ih.mask_head[s]
-        check_stage_topology(head)
-        cls, m, k, depth, q = stage_forward(head, x, dfe, k, m, q)
-        smask, sdepth = scale(m), scale(depth)                                                 # training: every stage (:131)
-        if s < ih.assign_stages:
-            c = None if prev_cls is None else prev_cls[:, :Np, :nt]
-            ddesc = Lo.assign_desc_device(head, gt, ih.mask_assigner[s], prev_mask[:, :Np], c, Np, ih.train_cfg[s], roi=True) if device_assign else None
-            if ddesc is None:
-                assigns = Lo.assign_batch(ih.mask_assigner[s], prev_mask[:, :Np], c, gt)       # :231-251
-        elif ddesc is not None:                                                                # the last assignment again, other weights
-            ddesc = Lo.assign_desc_device(head, gt, None, prev_mask[:, :Np], None, Np, ih.train_cfg[s], roi=True, prev=ddesc)
-        desc = ddesc if ddesc is not None else Lo.build_desc(head, gt, assigns, Np, ih.train_cfg[s], roi=True)
-        kept = {}
-
-        def fn(cs, mp, dp, head=head, desc=desc, kept=kept):
-            ls, g = Lo.fused_losses(head, desc, mp, cs, dp, None, with_grads=True)
+        def fn(cs, mp, dp, loss_fn=loss_fn, kept=kept):
+            ls, g = loss_fn(cs, mp, dp)
             kept.update(g)
             return ls, (g["cls_score"], g["mask_pred"], g["depth_pred"])
 
@@ -954,6 +856,68 @@ def _roi_forward_train_fast(ih, x, dfe, k, mask_preds, q, prev_mask, scale, gt_m
     if want_grads:
         losses["_grads"] = grads
     return losses, (k, cls, m, smask)
+
+
+class _DescTargets:
+    """where `roi_forward_train`'s stages take their targets from on the shipped configuration (`_fast_assign_ok`): per stage one
+    batched assignment (`ph_match_sums` over all images + one D2H + the host Hungarian solves), one pointer-table upload and ONE loss
+    call (`ph_train_losses`).  No sampler gathers, no materialised targets: every target row is a row of the step's ground truth
+    (`losses.StepGT`).  The previous stage's depth predictions only feed the DepthCost, whose weight is 0 here, so they are not
+    formed.  device_assign: assignment and tables by `ph_assign_desc` on the device instead (no D2H, no host solve, no upload); a
+    stage the kernels do not cover takes the host path."""
+
+    def __init__(self, ih, gt, device_assign):
+        self.ih, self.gt, self.device_assign = ih, gt, device_assign
+        self.assigns = self.ddesc = None
+
+    def stage(self, s, head, prev_mask, prev_cls, smask, sdepth):
+        """-> the stage's `fn(cls, mask, depth) -> (losses, grads dict)`; prev_*: the previous stage's detached predictions"""
+        ih, gt = self.ih, self.gt
+        Np, nt, cfg = ih.num_proposals, ih.num_thing_classes, ih.train_cfg[s]
+        if s < ih.assign_stages:
+            c = None if prev_cls is None else prev_cls[:, :Np, :nt]
+            self.ddesc = Lo.assign_desc_device(head, gt, ih.mask_assigner[s], prev_mask[:, :Np], c, Np, cfg, roi=True) if self.device_assign else None
+            if self.ddesc is None:
+                self.assigns = Lo.assign_batch(ih.mask_assigner[s], prev_mask[:, :Np], c, gt)  # :231-251
+        elif self.ddesc is not None:                                                           # the last assignment again, other weights
+            self.ddesc = Lo.assign_desc_device(head, gt, None, prev_mask[:, :Np], None, Np, cfg, roi=True, prev=self.ddesc)
+        desc = self.ddesc if self.ddesc is not None else Lo.build_desc(head, gt, self.assigns, Np, cfg, roi=True)
+        return lambda cs, mp, dp: Lo.fused_losses(head, desc, mp, cs, dp, None, with_grads=True)
+
+
+class _ListTargets:
+    """the same for every other configuration (topk > 1, a weighted DepthCost, another sampler): per image `assign` and `sample`, the
+    head's `get_targets`, `losses.stage_losses` on the materialised targets.  prev_depth: the scaled direct depth prediction expanded
+    to the N rows ([B, N, 2H, 2W]), then every stage's own -- only this path's DepthCost reads it."""
+
+    def __init__(self, ih, scale, depth_pred, N, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth):
+        if ih.hard_target:
+            gt_masks = [m.bool().float() for m in gt_masks]
+        self.ih, self.img_metas, self.assign = ih, img_metas, []
+        self.prev_depth = scale(depth_pred.detach().expand(-1, N, -1, -1).contiguous()).detach()
+        self.gt = (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth)
+        # the pixels some ground-truth mask covers (:238): the same for every stage -- evaluated once per image instead of once per
+        # image and stage (a 24 MB concatenation + reduction each at the assign stride of cfg2)
+        self.valids = [_valid_pixels(gt_masks[i], gt_sem_seg[i]) for i in range(len(gt_masks))]
+
+    def stage(self, s, head, prev_mask, prev_cls, smask, sdepth):
+        ih = self.ih
+        gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth = self.gt
+        Np, nt = ih.num_proposals, ih.num_thing_classes
+        srs = []
+        if s < ih.assign_stages:
+            self.assign = []
+        for i, valid in enumerate(self.valids):
+            if s < ih.assign_stages:
+                c = None if prev_cls is None else prev_cls[i][:Np, :nt]
+                self.assign.append(ih.mask_assigner[s].assign(prev_mask[i][:Np], c, gt_masks[i], gt_labels[i], self.img_metas[i],
+                                                              depth_pred=self.prev_depth[i][:Np], gt_depth=gt_depth[i], gt_valid=valid))
+            sr = ih.mask_sampler[s].sample(self.assign[i], smask[i].detach(), gt_masks[i], depth=sdepth[i].detach())
+            sr.valid_mask = valid
+            srs.append(sr)
+        targets = head.get_targets(srs, gt_masks, gt_labels, ih.train_cfg[s], True, gt_sem_seg=gt_sem_seg, gt_sem_cls=gt_sem_cls, gt_depth=gt_depth)
+        self.prev_depth = sdepth.detach()                                                      # :273-276
+        return lambda cs, mp, dp: Lo.stage_losses(head, cs, mp, dp, *targets, with_grads=True)
 
 
 # ---- the step ------------------------------------------------------------------------------------------------------------------
@@ -982,23 +946,19 @@ def _prepared_lists(prepared):
     return prepared.gt_masks, prepared.gt_labels, prepared.gt_sem_seg, prepared.gt_sem_cls, prepared.gt_depth
 
 
-class TrainStep:
-    """rpn_head: KernelHead, roi_head: KernelUpdateIterHead, both built with train_cfg.  `forward_backward` evaluates one
-    step on the three post-neck maps and leaves `.grad` on every parameter of the two heads (accumulating, like autograd; averaged over the ranks
-    when torch.distributed runs with more than one) and returns (losses, objective, gradients of the three maps).  The
-    same two functions back the reference-named API methods (`KernelHead.forward_train`,
-    `KernelUpdateIterHead.forward_train`), whose loss dicts mmdet's `_parse_losses` + `backward()` consume unchanged; this
-    class adds the bucketed gradient all-reduce.  Use as a context manager (or call `close()`) to take the gradient hooks
-    off the parameters again."""
+class _StepBase:
+    """what the two training steps share: the checks of the two heads, the bucketed gradient all-reduce over `parameters()`, the
+    leaves, the objective / backward tail, the device solves' status words.  A subclass sets the modules it trains (`_trained`, in
+    parameter order) before it calls this constructor, and runs its forward through `_step`."""
 
-    def __init__(self, rpn_head, roi_head, bucket_bytes=32 << 20, group=None, device_assign=False):
+    def __init__(self, rpn_head, roi_head, bucket_bytes, group, device_assign):
         self.rpn, self.roi = rpn_head, roi_head
         # the Hungarian assignments and target tables on the device (csrc/ph_assign.hip): the step's forward waits for the host nowhere
         # after its ground truth is built; off by default
         self.device_assign = bool(device_assign)
         self._status = []
         if rpn_head.assigner is None or not roi_head.mask_assigner:
-            raise ValueError("TrainStep needs heads built with train_cfg (assigner / sampler)")
+            raise ValueError(f"{type(self).__name__} needs heads built with train_cfg (assigner / sampler)")
         check_rpn_topology(rpn_head)
         for h in roi_head.mask_head:
             check_stage_topology(h)
@@ -1019,15 +979,55 @@ class TrainStep:
         return False
 
     def parameters(self):
-        return [p for n, p in _lib.named_params(self.rpn).items() if not n.startswith("localization_fpn.")] + list(_lib.named_params(self.roi).values())
+        """every parameter of the trained modules once (by identity), module by module; the rpn head's `localization_fpn.*` are the
+        neck's: left out where the step does not train the neck, listed with the neck where it does"""
+        out, seen = [], set()
+        for m in self._trained:
+            for n, p in _lib.named_params(m).items():
+                if id(p) not in seen and not (m is self.rpn and n.startswith("localization_fpn.")):
+                    seen.add(id(p))
+                    out.append(p)
+        return out
 
     def assign_status(self):
         """the status words of the last step's device solves, downloaded now (a synchronising copy, when the caller chooses to):
         int64 [solves, B], 0 = solved; _lib.PH_ASSIGN_ENONFINITE: the image's costs were not finite and it got the trivial matching.
-        Empty without `device_assign` or where every solve took the host path."""
+        Empty without `device_assign` or where every solve took the host path.  The video step's two track solves add a row each."""
         if not self._status:
             return torch.zeros((0, 0), dtype=torch.int64)
         return torch.stack(self._status).cpu()
+
+    @staticmethod
+    def _leaves(maps, name, requires_grad=True):
+        """the step's own fp32 contiguous copies or views of its input maps, on the GPU; leaves of the graph where they get a gradient"""
+        return [_gpu32(f, name).requires_grad_(requires_grad) for f in maps]
+
+    def _step(self, leaves, forward, backward):
+        """forward() -> (losses attached to the graph, the `losses.StepGT`s the step used); the objective, backward with the bucketed
+        all-reduce -> (losses, objective, gradients of `leaves`), all detached"""
+        with torch.enable_grad(), Lo.reduce_group(self.group):
+            losses, gts = forward()
+            self._status = [w for g in gts for w in g.status_words]
+            total = parse_losses(losses)
+            if backward:
+                self.buckets.start()
+                total.backward()
+                self.buckets.finish()
+        return {k_: v.detach() for k_, v in losses.items()}, total.detach(), [f.grad for f in leaves]
+
+
+class TrainStep(_StepBase):
+    """rpn_head: KernelHead, roi_head: KernelUpdateIterHead, both built with train_cfg.  `forward_backward` evaluates one
+    step on the three post-neck maps and leaves `.grad` on every parameter of the two heads (accumulating, like autograd; averaged over the ranks
+    when torch.distributed runs with more than one) and returns (losses, objective, gradients of the three maps).  The
+    same two functions back the reference-named API methods (`KernelHead.forward_train`,
+    `KernelUpdateIterHead.forward_train`), whose loss dicts mmdet's `_parse_losses` + `backward()` consume unchanged; this
+    class adds the bucketed gradient all-reduce.  Use as a context manager (or call `close()`) to take the gradient hooks
+    off the parameters again."""
+
+    def __init__(self, rpn_head, roi_head, bucket_bytes=32 << 20, group=None, device_assign=False):
+        self._trained = (rpn_head, roi_head)
+        super().__init__(rpn_head, roi_head, bucket_bytes, group, device_assign)
 
     def forward_backward(self, feats, img_metas, gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, backward=True):
         return self._forward_backward(feats, img_metas, (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth), None, backward)
@@ -1039,22 +1039,16 @@ class TrainStep:
         return self._forward_backward(feats, img_metas, _prepared_lists(gt), cache, backward)
 
     def _forward_backward(self, feats, img_metas, lists, gt_cache, backward):
-        feats = [f.detach().float().contiguous().requires_grad_(True) for f in feats]
-        for f in feats:
-            if not f.is_cuda:
-                raise _lib.PolyheadError("the post-neck maps must live on the GPU: libpolyhead has no CPU path")
-        with torch.enable_grad(), Lo.reduce_group(self.group):
-            losses, _, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
-            self._status = [w for g in gt_cache.values() for w in g.status_words]
-            total = parse_losses(losses)
-            if backward:
-                self.buckets.start()
-                total.backward()
-                self.buckets.finish()
-        return {k_: v.detach() for k_, v in losses.items()}, total.detach(), [f.grad for f in feats]
+        feats = self._leaves(feats, "the post-neck maps")
+
+        def forward():
+            losses, _, cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
+            return losses, cache.values()
+
+        return self._step(feats, forward, backward)
 
 
-class VideoTrainStep:
+class VideoTrainStep(_StepBase):
     """PolyphonicVideo.forward_train after extract_feat (polyphonic_former_video.py:185-325) as one step: the neck in training form on
     the key frame's FPN levels and in eval form on the reference frame's, the two heads on the key frame exactly as `TrainStep` runs
     them, the reference frame through `simple_test_rpn` + `simple_test_mask_preds` in eval mode under no_grad, the track branch
@@ -1065,50 +1059,16 @@ class VideoTrainStep:
     def __init__(self, neck, rpn_head, roi_head, track_head, track_train_cfg, bucket_bytes=32 << 20, group=None, device_assign=False,
                  strides=(4, 8, 16, 32), finest_scale=56):
         from .assigner import build_assigner
-        from .dist import GradBuckets
-        self.neck, self.rpn, self.roi, self.track_head = neck, rpn_head, roi_head, track_head
-        self.device_assign = bool(device_assign)
+        self.neck, self.track_head = neck, track_head
+        self._trained = (neck, rpn_head, roi_head, track_head)
         self.strides, self.finest_scale = tuple(strides), finest_scale
-        self._status = []
-        if rpn_head.assigner is None or not roi_head.mask_assigner:
-            raise ValueError("VideoTrainStep needs heads built with train_cfg (assigner / sampler)")
         if rpn_head.localization_fpn is not None and rpn_head.localization_fpn is not neck:
             raise ValueError("VideoTrainStep: rpn_head.localization_fpn must be None or the step's neck")
-        check_rpn_topology(rpn_head)
-        for h in roi_head.mask_head:
-            check_stage_topology(h)
         a = track_train_cfg.get("assigner") if isinstance(track_train_cfg, dict) else getattr(track_train_cfg, "assigner", track_train_cfg)
         self.track_assigner = build_assigner(dict(a)) if isinstance(a, dict) else a
         if not _track_assign_ok(self.track_assigner):
             raise NotImplementedError("VideoTrainStep: track_train_cfg.assigner must be a one-to-one mask Hungarian assigner without depth cost")
-        self.group = group
-        self.buckets = GradBuckets(self.parameters(), bucket_bytes=bucket_bytes, group=group)
-
-    def close(self):
-        self.buckets.remove()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
-
-    def parameters(self):
-        out, seen = [], set()
-        heads = [p for n, p in _lib.named_params(self.rpn).items() if not n.startswith("localization_fpn.")]
-        for p in list(_lib.named_params(self.neck).values()) + heads + list(_lib.named_params(self.roi).values()) + \
-                list(_lib.named_params(self.track_head).values()):
-            if id(p) not in seen:
-                seen.add(id(p))
-                out.append(p)
-        return out
-
-    def assign_status(self):
-        """as `TrainStep.assign_status`; with device_assign the two track solves add a row each"""
-        if not self._status:
-            return torch.zeros((0, 0), dtype=torch.int64)
-        return torch.stack(self._status).cpu()
+        super().__init__(rpn_head, roi_head, bucket_bytes, group, device_assign)
 
     def _reference_frame(self, x_ref, ref_metas):
         """:186-191, 207-243 for the reference frame: neck, rpn head and roi head in eval mode under no_grad, at the grade the module API
@@ -1151,25 +1111,18 @@ class VideoTrainStep:
         prepared, else derived from the lists where the step first needs them"""
         lists, gt_instance_ids = key[:5], key[5]
         ref_gt_masks, ref_gt_labels, ref_gt_instance_ids = ref
-        x = [f.detach().float().contiguous().requires_grad_(True) for f in x]
-        x_ref = [f.detach().float().contiguous() for f in x_ref]
-        for f in x + x_ref:
-            if not f.is_cuda:
-                raise _lib.PolyheadError("the FPN levels must live on the GPU: libpolyhead has no CPU path")
-        with torch.enable_grad(), Lo.reduce_group(self.group):
+        x = self._leaves(x, "the FPN levels")
+        x_ref = self._leaves(x_ref, "the FPN levels", requires_grad=False)
+
+        def forward():
             feats = neck_forward_train(self.neck, x)                                                   # :185
-            losses, last, gt_cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
+            losses, last, cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
             ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas)
-            gt = _step_gt(gt_cache, False, *lists)                                                     # the soft masks (:259)
-            if ref_gt is None:
-                ref_gt = Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
-            losses.update(video_track_branch(self.track_head, self.track_assigner, x, x_ref, last, ref_last, gt, ref_gt, gt_instance_ids,
+            gt = _step_gt(cache, False, *lists)                                                        # the soft masks (:259)
+            rgt = ref_gt if ref_gt is not None else Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
+            losses.update(video_track_branch(self.track_head, self.track_assigner, x, x_ref, last, ref_last, gt, rgt, gt_instance_ids,
                                              ref_gt_instance_ids, pad_hw, self.roi.num_proposals, self.roi.num_thing_classes,
                                              self.device_assign, self.strides, self.finest_scale))
-            self._status = [w for g in list(gt_cache.values()) + [ref_gt] for w in g.status_words]
-            total = parse_losses(losses)
-            if backward:
-                self.buckets.start()
-                total.backward()
-                self.buckets.finish()
-        return {k_: v.detach() for k_, v in losses.items()}, total.detach(), [f.grad for f in x]
+            return losses, list(cache.values()) + [rgt]
+
+        return self._step(x, forward, backward)

@@ -326,6 +326,14 @@ def stage_cfg(C=256, F=2048, heads=8, L=19, n_thing=8, n_stuff=11):
         depth_act_mode="sigmoid")
 
 
+# the assigners of the shipped train_cfg (configs/_base_/models/polyphonic_former.py:170-192): KernelHead's, and the stages' with the
+# DepthCost at weight 0.  A head's constructor consumes its config: hand it `copy.deepcopy(...)`
+RPN_ASSIGNER = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
+                    dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True))
+ROI_ASSIGNER = dict(RPN_ASSIGNER, depth_cost=dict(type='DepthCost', weight=0., loss_fn=dict(type='DepthMatchLoss', loss_weight=1.),
+                                                  depth_act_mode='sigmoid'))
+
+
 def train_gt(seed, B, H, W, n_thing, n_stuff, gts):
     """ground truth of a training step at the assign stride (H x W = the x2-upsampled mask size), shared with the tests"""
     g = torch.Generator().manual_seed(seed)

@@ -87,9 +87,7 @@ def test_oversize_is_refused_before_any_launch(gpu):
 
 # ---- the descriptor blob ---------------------------------------------------------------------------------------------------------
 NT, NS = 8, 11
-ROI_ASSIGNER = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-                    dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True),
-                    depth_cost=dict(type='DepthCost', weight=0., loss_fn=dict(type='DepthMatchLoss', loss_weight=1.), depth_act_mode='sigmoid'))
+ROI_ASSIGNER = Hh.ROI_ASSIGNER
 
 
 def _tie_gt(H, W):
@@ -206,6 +204,34 @@ def test_whole_step_without_the_host_solver(gpu, heads, monkeypatch):
     for k in host[0]:
         assert torch.equal(host[0][k], dev[0][k]), (k, float(host[0][k]), float(dev[0][k]))
     assert _same(host, dev)
+
+
+def test_whole_step_on_materialised_targets(gpu, heads, monkeypatch):
+    """the other path of the training forward -- per-image `assign` / `sample`, `get_targets`, `stage_losses` / `rpn_losses`: what a
+    configuration outside `train._fast_assign_ok` (topk > 1, a weighted DepthCost, another sampler) runs -- forced on the shipped
+    configuration: the descriptor path's 24 keys, the objective and every value within `test_gpu_loss_edges.VALUE_BOUND` of the
+    descriptor path's (the forward does not depend on the targets, so both paths see the same predictions in every stage: what
+    differs is what `test_fused_vs_unfused` compares under that bound), every parameter and map gradient present and finite.
+    Gradients are not compared across the two paths: the abs-rel depth term's gradient jumps at p == t, and two fp32 kernels may
+    sit on different sides of it at single pixels."""
+    from polyphonicformer_amd import train as T
+    from test_gpu_loss_edges import close
+    rpn, roi, args = heads
+    desc = _run_step(T, rpn, roi, args)
+    monkeypatch.setattr(T, "_fast_assign_ok", lambda a, s: False)
+
+    def no_descriptors(*a, **k):
+        raise AssertionError("the descriptor path ran although _fast_assign_ok refuses it")
+
+    monkeypatch.setattr(Lo, "fused_losses", no_descriptors)
+    mat = _run_step(T, rpn, roi, args)
+    assert set(mat[0]) == set(desc[0]) and len(mat[0]) == 24
+    close(mat[1], desc[1], "objective")
+    for k in sorted(desc[0]):
+        close(mat[0][k], desc[0][k], k)
+    for g in mat[2] + mat[3]:
+        assert g is not None and torch.isfinite(g).all()
+    assert len(mat[2]) == 3 and mat[4].numel() == 0
 
 
 def test_device_step_does_not_wait_for_the_host(gpu, heads, monkeypatch):

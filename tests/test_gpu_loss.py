@@ -2,6 +2,7 @@
 loss kernels (csrc/ph_loss.hip) against the REFERENCE's own outputs (tests/golden/loss.npz: the reference classes with the
 vendored mmdet losses and the project's DepthLoss, oracle/gen_golden_loss.py): targets bit for bit, every loss value,
 and d(sum of losses) / d(predictions) against the reference's autograd gradients."""
+import copy
 import json
 
 import numpy as np
@@ -119,8 +120,8 @@ def test_mask_loss_modules_forward(gpu):
 
 def test_forward_train_vs_reference(gpu):
     """KernelUpdateIterHead.forward_train (kernel_update.py:159-280), forward side, S = 3 at the full channel sizes: stage
-    forwards on libpolyhead, Hungarian assignment (ph_match_sums + scipy), pseudo sampling, get_targets, stage losses --
-    all 18 `s{stage}_{loss}` values against the REFERENCE's (tests/golden/train.npz: the reference head with its own
+    forwards on libpolyhead, Hungarian assignment (ph_match_sums + scipy), the targets as descriptors into the step's ground
+    truth (`losses.build_desc`), one `ph_train_losses` call per stage -- all 18 `s{stage}_{loss}` values against the REFERENCE's (tests/golden/train.npz: the reference head with its own
     assigner, sampler and the real loss modules).  Free running over three stages and three discrete assignments."""
     from test_gpu_parity import _full_weights
     from polyphonicformer_amd.registry import HEADS
@@ -128,9 +129,7 @@ def test_forward_train_vs_reference(gpu):
     z = Hh.load_golden("train.npz")
     m = json.loads(bytes(z["meta_json"]).decode())
     B, H, W, S, N = m["B"], m["H"], m["W"], m["S"], m["N"]
-    assigner = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-                    dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True),
-                    depth_cost=dict(type='DepthCost', weight=0., loss_fn=dict(type='DepthMatchLoss', loss_weight=1.), depth_act_mode='sigmoid'))
+    assigner = copy.deepcopy(Hh.ROI_ASSIGNER)
     head = HEADS.build(dict(type="KernelUpdateIterHead", num_stages=S, assign_stages=S, stage_loss_weights=[1] * S, num_proposals=100,
                             num_thing_classes=8, num_stuff_classes=11, do_panoptic=True, merge_joint=True,
                             mask_head=Hh.stage_cfg(256, 2048, 8, 19, 8, 11),
@@ -160,8 +159,7 @@ def _rpn_head(gpu, cat_stuff_mask=True):
     from polyphonicformer_amd.registry import HEADS
     import polyphonicformer_amd.kernel_head  # noqa: F401
     from test_gpu_parity import _full_weights
-    assigner = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-                    dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True))
+    assigner = copy.deepcopy(Hh.RPN_ASSIGNER)
     head = HEADS.build(dict(
         type="KernelHead", num_proposals=100, num_classes=19, num_thing_classes=8, num_stuff_classes=11, cat_stuff_mask=cat_stuff_mask,
         feat_downsample_stride=2, feat_refine=False, use_binary=True, proposal_feats_with_obj=True, localization_fpn=None,
@@ -326,9 +324,7 @@ def test_train_step_vs_reference(gpu, monkeypatch, golden, path):
     m = json.loads(bytes(z["meta_json"]).decode())
     B, H, W, S = m["B"], m["H"], m["W"], m["S"]
     rpn, sd = _rpn_head(gpu)
-    roi_a = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-                 dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True),
-                 depth_cost=dict(type='DepthCost', weight=0., loss_fn=dict(type='DepthMatchLoss', loss_weight=1.), depth_act_mode='sigmoid'))
+    roi_a = copy.deepcopy(Hh.ROI_ASSIGNER)
     roi = HEADS.build(dict(type="KernelUpdateIterHead", num_stages=S, assign_stages=S, stage_loss_weights=[1] * S, num_proposals=100,
                            num_thing_classes=8, num_stuff_classes=11, do_panoptic=True, merge_joint=True,
                            mask_head=Hh.stage_cfg(256, 2048, 8, 19, 8, 11),
@@ -421,8 +417,7 @@ def test_training_steps_reduce_the_objective(gpu):
     from polyphonicformer_amd import train as T
     import polyphonicformer_amd.kernel_update  # noqa: F401
     rpn, sd = _rpn_head(gpu)
-    roi_a = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-                 dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True))
+    roi_a = copy.deepcopy(Hh.RPN_ASSIGNER)           # no DepthCost entry at all: the stages' assigner without it
     roi = HEADS.build(dict(type="KernelUpdateIterHead", num_stages=3, assign_stages=3, stage_loss_weights=[1] * 3, num_proposals=100,
                            num_thing_classes=8, num_stuff_classes=11, mask_head=Hh.stage_cfg(256, 2048, 8, 19, 8, 11),
                            train_cfg=dict(assigner=roi_a, sampler=dict(type='MaskPseudoSampler'), pos_weight=1.)))

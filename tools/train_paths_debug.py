@@ -1,5 +1,6 @@
 """GPU debug: the training step's descriptor path against the generic (materialised targets) path on the train_step fixture:
 per-stage loss values and d(losses)/d(predictions)"""
+import copy
 import json
 import os
 import sys
@@ -21,9 +22,7 @@ z = Hh.load_golden(sys.argv[1] if len(sys.argv) > 1 else "train_step.npz")
 m = json.loads(bytes(z["meta_json"]).decode())
 B, H, W, S = m["B"], m["H"], m["W"], m["S"]
 rpn, sd = TL._rpn_head(gpu)
-roi_a = dict(type='MaskHungarianAssignerWithDepth', cls_cost=dict(type='FocalLossCost', weight=2.0),
-             dice_cost=dict(type='DiceCost', weight=4.0, pred_act=True), mask_cost=dict(type='MaskCost', weight=1.0, pred_act=True),
-             depth_cost=dict(type='DepthCost', weight=0., loss_fn=dict(type='DepthMatchLoss', loss_weight=1.), depth_act_mode='sigmoid'))
+roi_a = copy.deepcopy(Hh.ROI_ASSIGNER)
 roi = HEADS.build(dict(type="KernelUpdateIterHead", num_stages=S, assign_stages=S, stage_loss_weights=[1] * S, num_proposals=100,
                        num_thing_classes=8, num_stuff_classes=11, do_panoptic=True, merge_joint=True, mask_head=Hh.stage_cfg(256, 2048, 8, 19, 8, 11),
                        train_cfg=dict(assigner=roi_a, sampler=dict(type='MaskPseudoSampler'), pos_weight=1.)))
