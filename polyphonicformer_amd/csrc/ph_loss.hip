@@ -1,18 +1,30 @@
-// SURVEY.md 8f row N4 -- the pixel passes of one stage's training losses (polyphonic/kernel_update_head.py:355-441):
-//   ph_mask_loss_sums / _grad : loss_mask (BCE with logits, mmdet cross_entropy_loss.py:74-113) and loss_dice (dice_loss.py:9-46)
-//                               over the valid pixels of the POSITIVE prediction rows
-//   ph_rank_loss_sum  / _grad : loss_rank, a softmax cross entropy over the N mask channels per pixel (:9-47, ignore_index)
-//   ph_depth_loss_sums / _grad: DepthLoss (polyphonic/losses/depth_loss.py:9-65): scale-invariant, squared-relative and
-//                               absolute-relative error over the pixels with 0 < target < 80 and a non-zero weight
-//   ph_focal_loss_sum / _grad : FocalLoss (focal_loss.py:12-60) on the [rows][classes] scores
-// The reference evaluates these as ~40 ATen launches per stage with boolean-mask gathers (pred[weights] copies of every
-// positive mask); here each loss is ONE pass that produces fixed-order partial sums (fp64 accumulators, one record per
-// workgroup, combined in index order by the caller: bit-reproducible) and ONE pass that writes d loss / d logits, the
-// first step of the backward pass.  Pure HBM streaming kernels, 16 bytes per lane where the layout allows.
+// The pixel passes of the training losses (polyphonic/kernel_update_head.py:355-441, kernel_head.py:456-569):
+//   mask : loss_mask (BCE with logits, mmdet cross_entropy_loss.py:74-113) and loss_dice (dice_loss.py:9-46) over the valid
+//          pixels of the POSITIVE prediction rows
+//   rank : loss_rank, a softmax cross entropy over the N mask channels per pixel (:9-47, ignore_index)
+//   depth: DepthLoss (polyphonic/losses/depth_loss.py:9-65): scale-invariant, squared-relative and absolute-relative error
+//          over the pixels with 0 < target < 80 and a non-zero weight
+//   focal: FocalLoss (focal_loss.py:12-60) on [rows][classes] scores and on the class-major conv_seg map
+// Each loss is ONE pass that produces fixed-order partial sums (fp64 accumulators, one record per workgroup, combined in index
+// order: bit-reproducible) and ONE pass that writes d loss / d logits, the first step of the backward pass.  Pure HBM streaming
+// kernels.  The file has three parts:
+//   1. the arithmetic: every formula once, as __device__ helpers
+//   2. the MATERIALISED family behind ph_*_loss_*, ph_seg_focal_* and ph_*_target: targets and weights are [rows][HW] tensors as
+//      the reference's get_targets builds them; the caller combines the sums and forms the gradient coefficients
+//   3. the DESCRIPTOR family behind ph_train_losses: a target or weight row is a pointer to the ground truth where it lies, the
+//      sums are finalised on the device, one call per head and stage.  It launches part 2's rank and focal kernels as they are.
 #include "ph_common.h"
 
 constexpr int LOSS_T = 256;
 
+static int loss_grid(int64_t n, int cap) {
+    int64_t g = (n + LOSS_T - 1) / LOSS_T;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// =================================================================================================================================
+// 1. The arithmetic
+// =================================================================================================================================
 // block-wide sum of K doubles per thread -> thread 0 holds the totals (fixed order: lanes by xor-butterfly, waves ascending)
 template <int K>
 __device__ __forceinline__ void block_sum(double (&v)[K], double* lds /* [4][K] */) {
@@ -34,50 +46,36 @@ __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-
 // binary_cross_entropy_with_logits: max(z, 0) - z t + log1p(exp(-|z|))
 __device__ __forceinline__ float bce_logits(float z, float t) { return fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z))); }
 
-// ---- mask: BCE + dice over the weighted pixels of the positive rows -----------------------------------------------------
-// out [P][nsplit][5] doubles: sum bce, count, a = sum sig*t, b = sum sig^2, c = sum t^2
-__global__ __launch_bounds__(LOSS_T) void k_mask_loss_sums(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                           const float* __restrict__ wgt, const int* __restrict__ rows, int64_t HW,
-                                                           int nsplit, double* __restrict__ out) {
-    __shared__ double lds[4 * 5];
-    const int p = blockIdx.y, sp = blockIdx.x;
-    const int64_t base = (int64_t)rows[p] * HW;
-    const int64_t i0 = HW * sp / nsplit, i1 = HW * (sp + 1) / nsplit;
-    double v[5] = {0, 0, 0, 0, 0};
+// ---- mask: BCE + dice over the weighted pixels of one row (z_ logits, t_ targets or NULL = zeros, w_ weights) ----------------
+// v += (sum bce, count, a = sum sig*t, b = sum sig^2, c = sum t^2) over this thread's pixels of [i0, i1): start i0 + threadIdx.x,
+// step LOSS_T -- the order of the fp64 additions
+__device__ __forceinline__ void mask_sums_row(const float* __restrict__ z_, const float* __restrict__ t_, const float* __restrict__ w_,
+                                              int64_t i0, int64_t i1, double (&v)[5]) {
     for (int64_t i = i0 + threadIdx.x; i < i1; i += LOSS_T) {
-        if (wgt[base + i] == 0.f) continue;                  // mask_weights[pos_inds].bool()   (:413)
-        const float z = pred[base + i], t = tgt[base + i], s = sigmoidf_(z);
+        if (w_[i] == 0.f) continue;                          // mask_weights[pos_inds].bool()   (:413)
+        const float z = z_[i], t = t_ ? t_[i] : 0.f, s = sigmoidf_(z);
         v[0] += (double)bce_logits(z, t);
         v[1] += 1.0;
         v[2] += (double)(s * t);
         v[3] += (double)(s * s);
         v[4] += (double)(t * t);
     }
-    block_sum<5>(v, lds);
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) out[((int64_t)p * nsplit + sp) * 5 + k] = v[k];
 }
 
-// grad[row][i] += w * ( c_bce (sig - t) + dice_row terms ); coef [P][3] floats: bce scale, dice A = -2 lw / (P (b + c)),
-// dice B = 4 lw a / (P (b + c)^2):  d dice / dz = (A t + B sig) sig (1 - sig)
-__global__ __launch_bounds__(LOSS_T) void k_mask_loss_grad(const float* __restrict__ pred, const float* __restrict__ tgt,
-                                                           const float* __restrict__ wgt, const int* __restrict__ rows, int64_t HW,
-                                                           const float* __restrict__ coef, float* __restrict__ grad) {
-    const int p = blockIdx.y;
-    const int64_t base = (int64_t)rows[p] * HW;
-    const float cb = coef[p * 3], cA = coef[p * 3 + 1], cB = coef[p * 3 + 2];
+// g_[i] += cb (sig - t) + (cA t + cB sig) sig (1 - sig) on the weighted pixels of the row: cb the BCE scale, the rest
+// d dice / dz with A = -2 lw / (P (b + c)), B = 4 lw a / (P (b + c)^2)
+__device__ __forceinline__ void mask_grad_row(const float* __restrict__ z_, const float* __restrict__ t_, const float* __restrict__ w_,
+                                              float* __restrict__ g_, int64_t HW, float cb, float cA, float cB) {
     for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < HW; i += (int64_t)gridDim.x * LOSS_T) {
-        if (wgt[base + i] == 0.f) continue;
-        const float z = pred[base + i], t = tgt[base + i], s = sigmoidf_(z);
-        grad[base + i] += cb * (s - t) + (cA * t + cB * s) * s * (1.f - s);
+        if (w_[i] == 0.f) continue;
+        const float z = z_[i], t = t_ ? t_[i] : 0.f, s = sigmoidf_(z);
+        g_[i] += cb * (s - t) + (cA * t + cB * s) * s * (1.f - s);
     }
 }
 
-// ---- rank: softmax cross entropy over the N channels of every pixel -------------------------------------------------------
+// ---- rank: softmax cross entropy over the N channels of every pixel ------------------------------------------------------------
 // One thread owns V consecutive pixels (V = 4: 16-byte loads when HW % 4 == 0) and walks the N rows once with an online
-// softmax (running max m and sum s of exp(z - m)), four rows of loads in flight; the first version walked the rows three
-// times with one dependent 4-byte load per step (0.6 TB/s).
+// softmax (running max m and sum s of exp(z - m)), four rows of loads in flight.
 template <int V> struct PxVec;
 template <> struct PxVec<4> {
     float v[4];
@@ -118,6 +116,84 @@ __device__ __forceinline__ void online_softmax(const float* __restrict__ pb, int
             m[j] = nm;
         }
     }
+}
+
+// ---- depth --------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float depth_act_f(float z, int mode) {
+    const float s = sigmoidf_(z);
+    if (mode == 0) return s * (80.f - 0.01f) + 0.01f;                    // funcs/depth_utils.py 'sigmoid'
+    const float mn = 1.f / 80.f, mxd = 1.f / 0.01f;
+    return 1.f / (mn + (mxd - mn) * s);                                  // 'monodepth'
+}
+// d depth_act / dz
+__device__ __forceinline__ float depth_act_df(float z, int mode) {
+    const float s = sigmoidf_(z), ds = s * (1.f - s);
+    if (mode == 0) return (80.f - 0.01f) * ds;
+    const float mn = 1.f / 80.f, mxd = 1.f / 0.01f, q = mn + (mxd - mn) * s;
+    return -(mxd - mn) * ds / (q * q);
+}
+// One (pixel, target, weight) is counted where 0 < t < 80 and w != 0; its terms from p = depth_act(z): lm = (log p - log t) w,
+// r = (p - t) w / t.  p comes from the caller, so that a pixel with several items activates its logit once.
+__device__ __forceinline__ bool depth_counted(float t, float w) { return t > 0.f && t < 80.f && w != 0.f; }
+struct DepthPx { float p, lm, r; };
+__device__ __forceinline__ DepthPx depth_px(float p, float t, float w) { return {p, (logf(p) - logf(t)) * w, (p - t) * w / t}; }
+// v += (n, sum lm^2, sum lm, sum r^2, sum |r|)
+__device__ __forceinline__ void depth_sums_add(const DepthPx& d, double (&v)[5]) {
+    v[0] += 1.0;
+    v[1] += (double)(d.lm * d.lm);
+    v[2] += (double)d.lm;
+    v[3] += (double)(d.r * d.r);
+    v[4] += (double)fabsf(d.r);
+}
+// d loss / dp of the item: c0 lm (w / p) + c1 (w / p) + c2 r (w / t) + c3 sign(r) (w / t); times depth_act_df = d loss / dz.
+// The callers multiply: with the derivative evaluated in front of this sum the compiler fuses another of its products (last bits).
+__device__ __forceinline__ float depth_grad_term(const DepthPx& d, float t, float w, float c0, float c1, float c2, float c3) {
+    const float sg = d.r > 0.f ? 1.f : (d.r < 0.f ? -1.f : 0.f);
+    return (c0 * d.lm + c1) * (w / d.p) + (c2 * d.r + c3 * sg) * (w / t);
+}
+
+// ---- focal: one logit z against t in {0, 1} -------------------------------------------------------------------------------------
+// GRAD false: at pt^g bce.  GRAD true: k d/dz [ at pt^g bce ] = k at ( g pt^(g-1) dpt bce + pt^g (p - t) ), dpt/dz = (1 - 2 t) p (1 - p),
+// k the caller's factor (scale, or scale * weight).  SQ: gamma == 2 (every shipped config) takes two multiplies instead of two
+// powf -- the class-major kernel's arithmetic; the [rows][classes] kernel calls powf always.  The two differ in the last bits.
+template <bool GRAD, bool SQ>
+__device__ __forceinline__ float focal_term(float z, float t, float gamma, float alpha, float k) {
+    const float p = sigmoidf_(z);
+    const float pt = (1.f - p) * t + p * (1.f - t);
+    const float at = alpha * t + (1.f - alpha) * (1.f - t);
+    const float bce = bce_logits(z, t);
+    const bool sq = SQ && gamma == 2.f;
+    const float ptg = sq ? pt * pt : powf(pt, gamma), ptg1 = sq ? pt : powf(pt, gamma - 1.f);
+    if (!GRAD) return bce * at * ptg;
+    const float dpt = (1.f - 2.f * t) * p * (1.f - p);
+    return k * at * (gamma * ptg1 * dpt * bce + ptg * (p - t));
+}
+
+// =================================================================================================================================
+// 2. The materialised family: targets and weights as [rows][HW] tensors
+// =================================================================================================================================
+// out [P][nsplit][5] doubles: the five mask sums of split sp of positive row p
+__global__ __launch_bounds__(LOSS_T) void k_mask_loss_sums(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                           const float* __restrict__ wgt, const int* __restrict__ rows, int64_t HW,
+                                                           int nsplit, double* __restrict__ out) {
+    __shared__ double lds[4 * 5];
+    const int p = blockIdx.y, sp = blockIdx.x;
+    const int64_t base = (int64_t)rows[p] * HW;
+    double v[5] = {0, 0, 0, 0, 0};
+    mask_sums_row(pred + base, tgt + base, wgt + base, HW * sp / nsplit, HW * (sp + 1) / nsplit, v);
+    block_sum<5>(v, lds);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) out[((int64_t)p * nsplit + sp) * 5 + k] = v[k];
+}
+
+// grad[row] += the mask gradient; coef [P][3] floats: cb, cA, cB of positive row p
+__global__ __launch_bounds__(LOSS_T) void k_mask_loss_grad(const float* __restrict__ pred, const float* __restrict__ tgt,
+                                                           const float* __restrict__ wgt, const int* __restrict__ rows, int64_t HW,
+                                                           const float* __restrict__ coef, float* __restrict__ grad) {
+    const int p = blockIdx.y;
+    const int64_t base = (int64_t)rows[p] * HW;
+    mask_grad_row(pred + base, tgt + base, wgt + base, grad + base, HW, coef[p * 3], coef[p * 3 + 1], coef[p * 3 + 2]);
 }
 
 // out [B * nblk] doubles: sum over the non-ignored pixels of (logsumexp - z_target)
@@ -178,21 +254,7 @@ __global__ __launch_bounds__(LOSS_T) void k_rank_loss_grad(const float* __restri
     }
 }
 
-// ---- depth ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float depth_act_f(float z, int mode) {
-    const float s = sigmoidf_(z);
-    if (mode == 0) return s * (80.f - 0.01f) + 0.01f;                    // funcs/depth_utils.py 'sigmoid'
-    const float mn = 1.f / 80.f, mxd = 1.f / 0.01f;
-    return 1.f / (mn + (mxd - mn) * s);                                  // 'monodepth'
-}
-// d depth_act / dz
-__device__ __forceinline__ float depth_act_df(float z, int mode) {
-    const float s = sigmoidf_(z), ds = s * (1.f - s);
-    if (mode == 0) return (80.f - 0.01f) * ds;
-    const float mn = 1.f / 80.f, mxd = 1.f / 0.01f, q = mn + (mxd - mn) * s;
-    return -(mxd - mn) * ds / (q * q);
-}
-// out [nblk][5] doubles: n, sum lm^2, sum lm, sum (m / t)^2, sum |m / t|   (lm = (log p - log t) w, m = (p - t) w)
+// out [nblk][5] doubles: the five depth sums of a flat grid-stride partition of all pixels
 __global__ __launch_bounds__(LOSS_T) void k_depth_loss_sums(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                             const float* __restrict__ wgt, int64_t total, int mode,
                                                             double* __restrict__ out) {
@@ -200,38 +262,28 @@ __global__ __launch_bounds__(LOSS_T) void k_depth_loss_sums(const float* __restr
     double v[5] = {0, 0, 0, 0, 0};
     for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < total; i += (int64_t)gridDim.x * LOSS_T) {
         const float t = tgt[i], w = wgt[i];
-        if (!(t > 0.f && t < 80.f && w != 0.f)) continue;
-        const float p = depth_act_f(pred[i], mode);
-        const float lm = (logf(p) - logf(t)) * w, r = (p - t) * w / t;
-        v[0] += 1.0;
-        v[1] += (double)(lm * lm);
-        v[2] += (double)lm;
-        v[3] += (double)(r * r);
-        v[4] += (double)fabsf(r);
+        if (depth_counted(t, w)) depth_sums_add(depth_px(depth_act_f(pred[i], mode), t, w), v);
     }
     block_sum<5>(v, lds);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < 5; ++k) out[(int64_t)blockIdx.x * 5 + k] = v[k];
 }
-// grad = [ c0 lm (w / p) + c1 (w / p) + c2 r (w / t) + c3 sign(r) (w / t) ] * d depth_act / dz   (OVERWRITES grad)
+// grad = the depth gradient term on the counted pixels, 0 elsewhere (OVERWRITES grad)
 __global__ __launch_bounds__(LOSS_T) void k_depth_loss_grad(const float* __restrict__ pred, const float* __restrict__ tgt,
                                                             const float* __restrict__ wgt, int64_t total, int mode, float c0, float c1,
                                                             float c2, float c3, float* __restrict__ grad) {
     for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < total; i += (int64_t)gridDim.x * LOSS_T) {
         const float t = tgt[i], w = wgt[i];
         float g = 0.f;
-        if (t > 0.f && t < 80.f && w != 0.f) {
-            const float z = pred[i], p = depth_act_f(z, mode);
-            const float lm = (logf(p) - logf(t)) * w, r = (p - t) * w / t;
-            const float sg = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f);
-            g = ((c0 * lm + c1) * (w / p) + (c2 * r + c3 * sg) * (w / t)) * depth_act_df(z, mode);
+        if (depth_counted(t, w)) {
+            const float z = pred[i];
+            g = depth_grad_term(depth_px(depth_act_f(z, mode), t, w), t, w, c0, c1, c2, c3) * depth_act_df(z, mode);
         }
         grad[i] = g;
     }
 }
 
-// ---- focal ------------------------------------------------------------------------------------------------------------------
 // pred [R][L], labels [R] (class index; >= L = background), weight [R][L]; out [nblk] doubles / grad [R][L]
 template <bool GRAD>
 __global__ __launch_bounds__(LOSS_T) void k_focal(const float* __restrict__ pred, const int64_t* __restrict__ labels,
@@ -243,17 +295,10 @@ __global__ __launch_bounds__(LOSS_T) void k_focal(const float* __restrict__ pred
     for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < total; i += (int64_t)gridDim.x * LOSS_T) {
         const int64_t r = i / L;
         const int c = (int)(i - r * L);
-        const float z = pred[i], t = labels[r] == c ? 1.f : 0.f, p = sigmoidf_(z), w = wgt[i];
-        const float pt = (1.f - p) * t + p * (1.f - t);
-        const float at = alpha * t + (1.f - alpha) * (1.f - t);
-        const float bce = bce_logits(z, t);
-        if (!GRAD) {
-            v[0] += (double)(bce * at * powf(pt, gamma) * w);
-        } else {
-            // d/dz [ at pt^g bce ] = at ( g pt^(g-1) dpt bce + pt^g (p - t) ),  dpt/dz = (1 - 2 t) p (1 - p)
-            const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-            grad[i] = scale * w * at * (gamma * powf(pt, gamma - 1.f) * dpt * bce + powf(pt, gamma) * (p - t));
-        }
+        const float t = labels[r] == c ? 1.f : 0.f, w = wgt[i];
+        const float f = focal_term<GRAD, false>(pred[i], t, gamma, alpha, scale * w);
+        if (!GRAD) v[0] += (double)(f * w);
+        else grad[i] = f;
     }
     if (!GRAD) {
         block_sum<1>(v, lds);
@@ -261,15 +306,17 @@ __global__ __launch_bounds__(LOSS_T) void k_focal(const float* __restrict__ pred
     }
 }
 
-// ---- focal loss over a class-major map: pred [B][L][HW], target [B][HW] (class index; == L: pixel not selected) -------------
-// KernelHead's loss_rpn_seg (kernel_head.py:538-551): the pixels with seg_targets != L, all L classes of each
+// focal loss over a class-major map: pred [B][L][HW], target [B][HW] (class index; == L: pixel not selected).  KernelHead's
+// loss_rpn_seg (kernel_head.py:538-551): the pixels with seg_targets != L, all L classes of each.  The gradient's scale is
+// *scale_dev where that is given (ph_train_losses: lw / number of selected pixels, from k_loss_finalize), else `scale`.
 template <bool GRAD>
 __global__ __launch_bounds__(LOSS_T) void k_seg_focal(const float* __restrict__ pred, const int* __restrict__ target, int L, int64_t HW,
-                                                      float gamma, float alpha, float scale, double* __restrict__ out,
-                                                      float* __restrict__ grad) {
+                                                      float gamma, float alpha, float scale, const float* __restrict__ scale_dev,
+                                                      double* __restrict__ out, float* __restrict__ grad) {
     __shared__ double lds[4];
     const int b = blockIdx.y;
     const float* pb = pred + (int64_t)b * L * HW;
+    const float sc = GRAD && scale_dev ? *scale_dev : scale;
     double v[1] = {0};
     for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < HW; i += (int64_t)gridDim.x * LOSS_T) {
         const int tg = target[(int64_t)b * HW + i];
@@ -280,29 +327,15 @@ __global__ __launch_bounds__(LOSS_T) void k_seg_focal(const float* __restrict__ 
                 if (GRAD) grad[(int64_t)b * L * HW + idx] = 0.f;
                 continue;
             }
-            const float z = pb[idx], t = tg == c ? 1.f : 0.f, p = sigmoidf_(z);
-            const float pt = (1.f - p) * t + p * (1.f - t);
-            const float at = alpha * t + (1.f - alpha) * (1.f - t);
-            const float bce = bce_logits(z, t);
-            // gamma == 2 (every shipped config): two multiplies instead of two powf
-            const float ptg = gamma == 2.f ? pt * pt : powf(pt, gamma), ptg1 = gamma == 2.f ? pt : powf(pt, gamma - 1.f);
-            if (!GRAD) v[0] += (double)(bce * at * ptg);
-            else {
-                const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-                grad[(int64_t)b * L * HW + idx] = scale * at * (gamma * ptg1 * dpt * bce + ptg * (p - t));
-            }
+            const float f = focal_term<GRAD, true>(pb[idx], tg == c ? 1.f : 0.f, gamma, alpha, sc);
+            if (!GRAD) v[0] += (double)f;
+            else grad[(int64_t)b * L * HW + idx] = f;
         }
     }
     if (!GRAD) {
         block_sum<1>(v, lds);
         if (threadIdx.x == 0) out[(int64_t)b * gridDim.x + blockIdx.x] = v[0];
     }
-}
-
-// =================================================================================================================================
-static int loss_grid(int64_t n, int cap) {
-    int64_t g = (n + LOSS_T - 1) / LOSS_T;
-    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 extern "C" int ph_mask_loss_sums(const float* pred, const float* target, const float* weight, const int32_t* pos_rows, int P,
@@ -395,7 +428,7 @@ extern "C" int ph_seg_focal_sum(const float* pred, const int32_t* target, int B,
                                 double* out /* [B * ph_rank_loss_blocks(HW)] */, void* stream) {
     PH_CHECK_ARG(pred && target && out && B > 0 && L > 0 && HW > 0, "bad pointer or size");
     hipLaunchKernelGGL(k_seg_focal<false>, dim3(loss_grid(HW, 256), B), dim3(LOSS_T), 0, (hipStream_t)stream, pred, target, L, HW, gamma,
-                       alpha, 0.f, out, (float*)nullptr);
+                       alpha, 0.f, (const float*)nullptr, out, (float*)nullptr);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
@@ -404,7 +437,7 @@ extern "C" int ph_seg_focal_grad(const float* pred, const int32_t* target, int B
                                  float scale, float* grad, void* stream) {
     PH_CHECK_ARG(pred && target && grad && B > 0 && L > 0 && HW > 0, "bad pointer or size");
     hipLaunchKernelGGL(k_seg_focal<true>, dim3(loss_grid(HW, 256), B), dim3(LOSS_T), 0, (hipStream_t)stream, pred, target, L, HW, gamma,
-                       alpha, scale, (double*)nullptr, grad);
+                       alpha, scale, (const float*)nullptr, (double*)nullptr, grad);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
@@ -459,14 +492,11 @@ extern "C" int ph_seg_target(const float* sem_seg /* [S][HW], may be NULL when S
 }
 
 // =================================================================================================================================
-// Round 5 (VERDICT r04 #1d): ONE call per head and stage for targets + losses + d(losses)/d(predictions), from DESCRIPTORS.
-// The reference materialises per stage and image labels / label_weights / mask_targets / mask_weights / depth_targets /
-// depth_weights as [rows][H][W] tensors (kernel_update_head.py:443-591, kernel_head.py:571-698: index_put, cat, fill -- 30 % of
-// round 4's training-step GPU time went into ATen copies of ground-truth masks) and evaluates the losses over them with
-// boolean-mask gathers.  Every one of those rows is a ground-truth mask, the image's valid map, its depth map, all ones or all
-// zeros -- so a row is described by POINTERS: tptr / wptr (mask target / weight row, 0 = zeros), depth items (target row, weight
-// row or 1 = ones, scale) grouped per prediction row, paint lists for the dense semantic target.  The host builds the tables from
-// the Hungarian result it already holds (no device gather, no D2H), the kernels read the ground truth where it lies.
+// 3. The descriptor family: ONE call per head and stage for targets + losses + d(losses)/d(predictions)
+// Every materialised target row is a ground-truth mask, the image's valid map, its depth map, all ones or all zeros, so a row is
+// described by POINTERS: tptr / wptr (mask target / weight row, 0 = zeros), depth items (target row, weight row or 1 = ones,
+// scale) grouped per prediction row, paint lists for the dense semantic target.  The tables come from the host (losses.build_desc)
+// or from ph_assign_desc; the kernels read the ground truth where it lies.
 // Launch sequence: [seg target, seg focal sum] mask sums, rank target, rank sum, depth sums, focal sum -> finalize (loss values,
 // gradient coefficients: on the device, no host round trip) -> rank / mask / depth / focal / seg gradients.
 // =================================================================================================================================
@@ -474,26 +504,15 @@ namespace {
 
 __device__ __forceinline__ const float* as_row(int64_t p) { return (const float*)(uintptr_t)p; }
 
+// k_mask_loss_sums with the row's target and weight read from the pointer tables; a row without a weight row sums to zeros
 __global__ __launch_bounds__(LOSS_T) void k_mask_sums_p(const float* __restrict__ pred, const int* __restrict__ rows,
                                                         const int64_t* __restrict__ tptr, const int64_t* __restrict__ wptr, int64_t HW,
                                                         int nsplit, double* __restrict__ out) {
     __shared__ double lds[4 * 5];
     const int p = blockIdx.y, sp = blockIdx.x, row = rows[p];
-    const float* z_ = pred + (int64_t)row * HW;
-    const float* t_ = as_row(tptr[row]);
     const float* w_ = as_row(wptr[row]);
-    const int64_t i0 = HW * sp / nsplit, i1 = HW * (sp + 1) / nsplit;
     double v[5] = {0, 0, 0, 0, 0};
-    if (w_)
-        for (int64_t i = i0 + threadIdx.x; i < i1; i += LOSS_T) {
-            if (w_[i] == 0.f) continue;
-            const float z = z_[i], t = t_ ? t_[i] : 0.f, s = sigmoidf_(z);
-            v[0] += (double)bce_logits(z, t);
-            v[1] += 1.0;
-            v[2] += (double)(s * t);
-            v[3] += (double)(s * s);
-            v[4] += (double)(t * t);
-        }
+    if (w_) mask_sums_row(pred + (int64_t)row * HW, as_row(tptr[row]), w_, HW * sp / nsplit, HW * (sp + 1) / nsplit, v);
     block_sum<5>(v, lds);
     if (threadIdx.x == 0)
 #pragma unroll
@@ -504,17 +523,10 @@ __global__ __launch_bounds__(LOSS_T) void k_mask_grad_p(const float* __restrict_
                                                         const int64_t* __restrict__ tptr, const int64_t* __restrict__ wptr, int64_t HW,
                                                         const float* __restrict__ coef, float* __restrict__ grad) {
     const int p = blockIdx.y, row = rows[p];
-    const float* z_ = pred + (int64_t)row * HW;
-    const float* t_ = as_row(tptr[row]);
     const float* w_ = as_row(wptr[row]);
     if (!w_) return;
-    float* g_ = grad + (int64_t)row * HW;
-    const float cb = coef[p * 3], cA = coef[p * 3 + 1], cB = coef[p * 3 + 2];
-    for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < HW; i += (int64_t)gridDim.x * LOSS_T) {
-        if (w_[i] == 0.f) continue;
-        const float z = z_[i], t = t_ ? t_[i] : 0.f, s = sigmoidf_(z);
-        g_[i] += cb * (s - t) + (cA * t + cB * s) * s * (1.f - s);
-    }
+    mask_grad_row(pred + (int64_t)row * HW, as_row(tptr[row]), w_, grad + (int64_t)row * HW, HW, coef[p * 3], coef[p * 3 + 1],
+                  coef[p * 3 + 2]);
 }
 
 // pixel -> index (within its image) of the LAST positive row whose target covers it (kernel_update_head.py:420-432)
@@ -541,7 +553,8 @@ __global__ __launch_bounds__(LOSS_T) void k_rank_target_p(const int64_t* __restr
     }
 }
 
-// depth items of prediction row r: [dstart[r], dstart[r + 1]); item = (target row, weight row (1: ones), scale)
+// depth items of prediction row r: [dstart[r], dstart[r + 1]); item = (target row, weight row (1: ones), scale).
+// out [rows][nsplit][5] doubles: the five depth sums of split sp of row r over its items
 __global__ __launch_bounds__(LOSS_T) void k_depth_sums_csr(const float* __restrict__ pred, const int* __restrict__ dstart,
                                                            const int64_t* __restrict__ it_t, const int64_t* __restrict__ it_w,
                                                            const float* __restrict__ it_s, int64_t HW, int nsplit, int mode,
@@ -558,14 +571,7 @@ __global__ __launch_bounds__(LOSS_T) void k_depth_sums_csr(const float* __restri
         if (sc == 0.f) continue;
         for (int64_t i = i0 + threadIdx.x; i < i1; i += LOSS_T) {
             const float t = t_[i], w = w_ ? w_[i] * sc : sc;
-            if (!(t > 0.f && t < 80.f && w != 0.f)) continue;
-            const float p = depth_act_f(z_[i], mode);
-            const float lm = (logf(p) - logf(t)) * w, q = (p - t) * w / t;
-            v[0] += 1.0;
-            v[1] += (double)(lm * lm);
-            v[2] += (double)lm;
-            v[3] += (double)(q * q);
-            v[4] += (double)fabsf(q);
+            if (depth_counted(t, w)) depth_sums_add(depth_px(depth_act_f(z_[i], mode), t, w), v);
         }
     }
     block_sum<5>(v, lds);
@@ -574,6 +580,7 @@ __global__ __launch_bounds__(LOSS_T) void k_depth_sums_csr(const float* __restri
         for (int k = 0; k < 5; ++k) out[((int64_t)r * nsplit + sp) * 5 + k] = v[k];
 }
 
+// grad[r] = the sum of the row's items' gradient terms (OVERWRITES grad); coef [4] floats: c0..c3
 __global__ __launch_bounds__(LOSS_T) void k_depth_grad_csr(const float* __restrict__ pred, const int* __restrict__ dstart,
                                                            const int64_t* __restrict__ it_t, const int64_t* __restrict__ it_w,
                                                            const float* __restrict__ it_s, int64_t HW, int mode,
@@ -588,16 +595,14 @@ __global__ __launch_bounds__(LOSS_T) void k_depth_grad_csr(const float* __restri
         if (a < e) {
             const float z = z_[i];
             float p = 0.f, df = 0.f;
-            bool have = false;
+            bool have = false;                               // p and df: once per pixel, on its first counted item
             for (int it = a; it < e; ++it) {
                 const float sc = it_s[it];
                 const float t = as_row(it_t[it])[i];
                 const float w = it_w[it] == 1 ? sc : as_row(it_w[it])[i] * sc;
-                if (!(t > 0.f && t < 80.f && w != 0.f)) continue;
+                if (!depth_counted(t, w)) continue;
                 if (!have) { p = depth_act_f(z, mode); df = depth_act_df(z, mode); have = true; }
-                const float lm = (logf(p) - logf(t)) * w, q = (p - t) * w / t;
-                const float sg = q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f);
-                g += ((c0 * lm + c1) * (w / p) + (c2 * q + c3 * sg) * (w / t)) * df;
+                g += depth_grad_term(depth_px(p, t, w), t, w, c0, c1, c2, c3) * df;
             }
         }
         g_[i] = g;
@@ -642,23 +647,28 @@ struct FinArgs {
     float* seg_scale;     // [1]
 };
 
+// the sum of one double per thread, to every thread of the workgroup: an LDS tree, halving from LOSS_T / 2 (fixed order)
+__device__ __forceinline__ double block_total(double x, double* sh /* [LOSS_T] */) {
+    const int t = threadIdx.x;
+    sh[t] = x;
+    __syncthreads();
+    for (int o = LOSS_T / 2; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
 // one workgroup: fixed-order sums of the partial records, the loss values, the coefficients of the gradient passes
 __global__ __launch_bounds__(LOSS_T) void k_loss_finalize(const FinArgs a) {
     __shared__ double sh[LOSS_T];
-    __shared__ double tot[8];
     const int t = threadIdx.x;
     auto total = [&](const double* p, int n, int stride, int off) {      // sum_{i < n} p[i * stride + off], fixed order
         double s = 0;
         for (int i = t; i < n; i += LOSS_T) s += p[(int64_t)i * stride + off];
-        sh[t] = s;
-        __syncthreads();
-        for (int o = LOSS_T / 2; o > 0; o >>= 1) {
-            if (t < o) sh[t] += sh[t + o];
-            __syncthreads();
-        }
-        const double r = sh[0];
-        __syncthreads();
-        return r;
+        return block_total(s, sh);
     };
     const ph_loss_cfg& c = a.c;
     // ---- masks: per positive row the 5 sums over its splits (thread p), then BCE mean / dice mean
@@ -674,15 +684,9 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_finalize(const FinArgs a) {
             a.mask_coef[p * 3 + 1] = (float)(-2.0 * c.lw_dice / (a.P * bc));
             a.mask_coef[p * 3 + 2] = (float)(4.0 * c.lw_dice * s[2] / (a.P * bc * bc));
         }
-        sh[t] = loc_b; __syncthreads();
-        for (int o = LOSS_T / 2; o > 0; o >>= 1) { if (t < o) sh[t] += sh[t + o]; __syncthreads(); }
-        bce = sh[0]; __syncthreads();
-        sh[t] = loc_c; __syncthreads();
-        for (int o = LOSS_T / 2; o > 0; o >>= 1) { if (t < o) sh[t] += sh[t + o]; __syncthreads(); }
-        cnt = sh[0]; __syncthreads();
-        sh[t] = loc_d; __syncthreads();
-        for (int o = LOSS_T / 2; o > 0; o >>= 1) { if (t < o) sh[t] += sh[t + o]; __syncthreads(); }
-        dice = sh[0]; __syncthreads();
+        bce = block_total(loc_b, sh);
+        cnt = block_total(loc_c, sh);
+        dice = block_total(loc_d, sh);
         for (int p = t; p < a.P; p += LOSS_T) a.mask_coef[p * 3] = (float)(c.lw_mask / cnt);
     }
     const double rank = a.rank_n ? total(a.rank_part, a.rank_n, 1, 0) : 0.0;
@@ -701,10 +705,7 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_finalize(const FinArgs a) {
                 if (row[l] > row[best]) best = l;
             hit += best == (int)a.labels[a.pos_rows[p]] ? 1.0 : 0.0;
         }
-        sh[t] = hit; __syncthreads();
-        for (int o = LOSS_T / 2; o > 0; o >>= 1) { if (t < o) sh[t] += sh[t + o]; __syncthreads(); }
-        acc = sh[0] * 100.0 / a.P;
-        __syncthreads();
+        acc = block_total(hit, sh) * 100.0 / a.P;
     }
     if (t == 0) {
         // DepthLoss from the five sums (depth_loss.py:19-32; the reference's sum(log_minus) / n^2 kept)
@@ -730,33 +731,6 @@ __global__ __launch_bounds__(LOSS_T) void k_loss_finalize(const FinArgs a) {
         a.losses[5] = (float)(c.lw_seg * seg / nd);
         a.losses[6] = (float)acc;
         a.losses[7] = (float)nd;
-    }
-}
-
-// the class-major focal gradient with its scale read from the device (lw / number of selected pixels, from k_loss_finalize)
-__global__ __launch_bounds__(LOSS_T) void k_seg_focal_grad_dev(const float* __restrict__ pred, const int* __restrict__ target, int L, int64_t HW,
-                                                               float gamma, float alpha, const float* __restrict__ scale_dev,
-                                                               float* __restrict__ grad) {
-    const int b = blockIdx.y;
-    const float scale = *scale_dev;
-    const float* pb = pred + (int64_t)b * L * HW;
-    for (int64_t i = blockIdx.x * (int64_t)LOSS_T + threadIdx.x; i < HW; i += (int64_t)gridDim.x * LOSS_T) {
-        const int tg = target[(int64_t)b * HW + i];
-        const bool sel = tg != L;
-        for (int c = 0; c < L; ++c) {
-            const int64_t idx = (int64_t)c * HW + i;
-            float g = 0.f;
-            if (sel) {
-                const float z = pb[idx], t = tg == c ? 1.f : 0.f, p = sigmoidf_(z);
-                const float pt = (1.f - p) * t + p * (1.f - t);
-                const float at = alpha * t + (1.f - alpha) * (1.f - t);
-                const float bce = bce_logits(z, t);
-                const float ptg = gamma == 2.f ? pt * pt : powf(pt, gamma), ptg1 = gamma == 2.f ? pt : powf(pt, gamma - 1.f);
-                const float dpt = (1.f - 2.f * t) * p * (1.f - p);
-                g = scale * at * (gamma * ptg1 * dpt * bce + ptg * (p - t));
-            }
-            grad[(int64_t)b * L * HW + idx] = g;
-        }
     }
 }
 
@@ -817,7 +791,7 @@ extern "C" int ph_train_losses(const ph_loss_cfg* cfg, const float* mask_pred, c
         hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, s, nsel);
         hipLaunchKernelGGL(k_seg_target_p, dim3(loss_grid(HW, 256), c.B), dim3(LOSS_T), 0, s, sstart, sit_m, sit_l, c.seg_L, HW, seg_target, nsel);
         hipLaunchKernelGGL(k_seg_focal<false>, dim3(lay.rank_nb, c.B), dim3(LOSS_T), 0, s, seg_pred, seg_target, c.seg_L, HW, c.seg_gamma,
-                           c.seg_alpha, 0.f, D + lay.o_seg, (float*)nullptr);
+                           c.seg_alpha, 0.f, (const float*)nullptr, D + lay.o_seg, (float*)nullptr);
     }
     if (c.P > 0) {
         hipLaunchKernelGGL(k_mask_sums_p, dim3(lay.mask_ns, c.P), dim3(LOSS_T), 0, s, mask_pred, pos_rows, tptr, wptr, HW, lay.mask_ns, D + lay.o_mask);
@@ -861,8 +835,8 @@ extern "C" int ph_train_losses(const ph_loss_cfg* cfg, const float* mask_pred, c
             hipLaunchKernelGGL(k_focal<true>, dim3(lay.focal_nb), dim3(LOSS_T), 0, s, cls_score, labels, label_w, R, c.L, c.cls_gamma, c.cls_alpha,
                                c.lw_cls / c.cls_avg, (double*)nullptr, g_cls);
         if (seg_pred)
-            hipLaunchKernelGGL(k_seg_focal_grad_dev, dim3(loss_grid(HW, 256), c.B), dim3(LOSS_T), 0, s, seg_pred, seg_target, c.seg_L, HW,
-                               c.seg_gamma, c.seg_alpha, seg_scale, g_seg);
+            hipLaunchKernelGGL(k_seg_focal<true>, dim3(loss_grid(HW, 256), c.B), dim3(LOSS_T), 0, s, seg_pred, seg_target, c.seg_L, HW,
+                               c.seg_gamma, c.seg_alpha, 0.f, (const float*)seg_scale, (double*)nullptr, g_seg);
         PH_CHECK_LAUNCH();
     }
     return PH_OK;

@@ -26,54 +26,81 @@ def _f32(t):
     return t.detach().contiguous().float()
 
 
-# ---- the four passes --------------------------------------------------------------------------------------------------------
+# ---- the launches: sums (fixed-order fp64 records, combined here), gradients and targets (into the caller's buffers) ----------
+def _run(name, *args):
+    """queue libpolyhead's `name` on torch's current stream: tensors (None: NULL) go as pointers, everything else as it is"""
+    _lib.check(getattr(_lib.load(), name)(*(_lib.ptr(a) if a is None or torch.is_tensor(a) else a for a in args), _lib.stream_ptr()), name)
+
+
 def mask_loss_sums(pred, target, weight, pos_rows, nsplit=None):
     """pred / target / weight [R, HW] fp32, pos_rows int32 [P] -> float64 [P, 5] (BCE sum, count, a, b, c), fixed order"""
     P, HW = pos_rows.numel(), pred.shape[1]
     nsplit = nsplit or max(1, min(64, 2048 // max(P, 1)))
     out = torch.empty((P, nsplit, 5), dtype=torch.float64, device=pred.device)
-    lib = _lib.load()
-    _lib.check(lib.ph_mask_loss_sums(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(pos_rows), P, HW, nsplit,
-                                     _lib.ptr(out), _lib.stream_ptr()), "ph_mask_loss_sums")
+    _run("ph_mask_loss_sums", pred, target, weight, pos_rows, P, HW, nsplit, out)
     return out.sum(1)
 
 
 def rank_loss_sum(pred, rank_target, ignore):
     B, N, H, W = pred.shape
-    lib = _lib.load()
-    out = torch.empty((B * lib.ph_rank_loss_blocks(H * W),), dtype=torch.float64, device=pred.device)
-    _lib.check(lib.ph_rank_loss_sum(_lib.ptr(pred), _lib.ptr(rank_target), B, N, H * W, ignore, _lib.ptr(out), _lib.stream_ptr()),
-               "ph_rank_loss_sum")
+    out = torch.empty((B * _lib.load().ph_rank_loss_blocks(H * W),), dtype=torch.float64, device=pred.device)
+    _run("ph_rank_loss_sum", pred, rank_target, B, N, H * W, ignore, out)
     return out.sum()
 
 
 def depth_loss_sums(pred, target, weight, mode):
-    lib = _lib.load()
     total = pred.numel()
-    out = torch.empty((lib.ph_depth_loss_blocks(total), 5), dtype=torch.float64, device=pred.device)
-    _lib.check(lib.ph_depth_loss_sums(_lib.ptr(pred), _lib.ptr(target), _lib.ptr(weight), total, mode, _lib.ptr(out),
-                                      _lib.stream_ptr()), "ph_depth_loss_sums")
+    out = torch.empty((_lib.load().ph_depth_loss_blocks(total), 5), dtype=torch.float64, device=pred.device)
+    _run("ph_depth_loss_sums", pred, target, weight, total, mode, out)
     return out.sum(0)
 
 
 def seg_focal_sum(pred, target, gamma, alpha):
     """pred [B, L, HW] fp32 (class-major, as conv_seg writes it), target int32 [B, HW] (== L: pixel not selected)"""
-    lib = _lib.load()
     B, L, HW = pred.shape
-    nb = lib.ph_rank_loss_blocks(HW)
-    out = torch.empty((B * nb,), dtype=torch.float64, device=pred.device)
-    _lib.check(lib.ph_seg_focal_sum(_lib.ptr(pred), _lib.ptr(target), B, L, HW, gamma, alpha, _lib.ptr(out), _lib.stream_ptr()),
-               "ph_seg_focal_sum")
+    out = torch.empty((B * _lib.load().ph_rank_loss_blocks(HW),), dtype=torch.float64, device=pred.device)
+    _run("ph_seg_focal_sum", pred, target, B, L, HW, gamma, alpha, out)
     return out.sum()
 
 
 def focal_loss_sum(pred, labels, weight, gamma, alpha):
-    lib = _lib.load()
     R, L = pred.shape
-    out = torch.empty((lib.ph_focal_loss_blocks(R * L),), dtype=torch.float64, device=pred.device)
-    _lib.check(lib.ph_focal_loss_sum(_lib.ptr(pred), _lib.ptr(labels), _lib.ptr(weight), R, L, gamma, alpha, _lib.ptr(out),
-                                     _lib.stream_ptr()), "ph_focal_loss_sum")
+    out = torch.empty((_lib.load().ph_focal_loss_blocks(R * L),), dtype=torch.float64, device=pred.device)
+    _run("ph_focal_loss_sum", pred, labels, weight, R, L, gamma, alpha, out)
     return out.sum()
+
+
+def mask_loss_grad(pred, target, weight, pos_rows, coef, grad):
+    """grad [R, HW] += d(BCE + dice) / d pred on the positive rows; coef float32 [P, 3] as ph_mask_loss_grad reads it"""
+    _run("ph_mask_loss_grad", pred, target, weight, pos_rows, pos_rows.numel(), pred.shape[1], coef, grad)
+
+
+def rank_loss_grad(pred, rank_target, B, N, HW, ignore, scale, grad):
+    """grad [B * N, HW] = scale * d(rank cross entropy) / d pred; rank_target int32 [B, HW] or None (every pixel ignored)"""
+    _run("ph_rank_loss_grad", pred, rank_target, B, N, HW, ignore, scale, grad)
+
+
+def depth_loss_grad(pred, target, weight, mode, coef, grad):
+    """grad = d DepthLoss / d pred, element for element; coef: the four coefficients of `_depth_from_sums`"""
+    _run("ph_depth_loss_grad", pred, target, weight, pred.numel(), mode, *coef, grad)
+
+
+def focal_loss_grad(pred, labels, weight, gamma, alpha, scale, grad):
+    _run("ph_focal_loss_grad", pred, labels, weight, pred.shape[0], pred.shape[1], gamma, alpha, scale, grad)
+
+
+def seg_focal_grad(pred, target, gamma, alpha, scale, grad):
+    _run("ph_seg_focal_grad", pred, target, *pred.shape, gamma, alpha, scale, grad)
+
+
+def rank_target(mask_targets, pos_u8, B, N, HW, ignore, out):
+    """out int32 [B, HW]: pixel -> index (within its image) of the LAST positive row whose target covers it, else `ignore`"""
+    _run("ph_rank_target", mask_targets, pos_u8, B, N, HW, ignore, out)
+
+
+def seg_target(sem_seg, sem_cls, S, pos_masks, pos_labels, P, L, out):
+    """out int64 [H, W] of one image: background L, the S stuff masks in order, then the P assigned thing masks in order"""
+    _run("ph_seg_target", sem_seg, sem_cls, S, pos_masks, pos_labels, P, L, out.numel(), out)
 
 
 # ---- loss modules (configuration holders with the reference's names) -----------------------------------------------------------
@@ -189,30 +216,38 @@ class DiceLoss(_Loss):
         return (self.loss_weight * dice.mean()).float()
 
 
-def _depth_from_sums(s, loss_weight, w3):
-    """DepthLoss from the five sums (depth_loss.py:19-32): returns (loss fp64 scalar tensor, coefficients of the grad pass)"""
-    n = s[0]
-    if float(n) == 0.0:
-        return s[0] * 0.0, (0.0, 0.0, 0.0, 0.0)
-    si = s[1] / n - s[2] / (n * n)                      # as the reference writes it: sum(log_minus) / n^2, not its square
-    sq = torch.sqrt(s[3] / n)
-    ab = s[4] / n
-    K = loss_weight / 3.0
-    loss = K * (w3[0] * si + w3[1] * sq + w3[2] * ab)
-    nf, sqf = float(n), float(sq)
-    coef = (K * w3[0] * 2.0 / nf, -K * w3[0] / (nf * nf), (K * w3[1] / (nf * sqf)) if sqf > 0 else 0.0, K * w3[2] / nf)
-    return loss, coef
-
-
 def _depth_value_from_sums(s, loss_weight, w3):
-    """the value `_depth_from_sums` returns, without the host reading n: the same fp64 operations in the same order, all on the
-    device (0 where no pixel is labelled)"""
+    """DepthLoss from the five sums (depth_loss.py:19-32), an fp64 scalar tensor, 0 where no pixel is labelled.  All on the
+    device: the host never reads n"""
     n = s[0]
-    si = s[1] / n - s[2] / (n * n)
+    si = s[1] / n - s[2] / (n * n)                      # as the reference writes it: sum(log_minus) / n^2, not its square
     sq = torch.sqrt(s[3] / n)
     ab = s[4] / n
     loss = (loss_weight / 3.0) * (w3[0] * si + w3[1] * sq + w3[2] * ab)
     return torch.where(n == 0, torch.zeros_like(loss), loss)
+
+
+def _depth_from_sums(s, loss_weight, w3):
+    """(that value, the four coefficients of the gradient pass): those the host forms, so it reads n and the sq_rel root"""
+    loss, n = _depth_value_from_sums(s, loss_weight, w3), float(s[0])
+    if n == 0.0:
+        return loss, (0.0, 0.0, 0.0, 0.0)
+    K, sq = loss_weight / 3.0, float(torch.sqrt(s[3] / s[0]))
+    return loss, (K * w3[0] * 2.0 / n, -K * w3[0] / (n * n), (K * w3[1] / (n * sq)) if sq > 0 else 0.0, K * w3[2] / n)
+
+
+def _depth_terms(ld, dp, dt, dw, want_grad, grad_out=None):
+    """DepthLoss `ld` of the contiguous fp32 prediction dp against targets / weights of its size: (float32 loss, d loss / d dp or
+    None).  The gradient goes into `grad_out` where given.  Without `want_grad` nothing here waits for the device."""
+    mode, w3 = DEPTH_MODES[ld.depth_act_mode], [float(v) for v in ld.weight]
+    dt, dw = _f32(dt), _f32(dw)
+    sums = depth_loss_sums(dp, dt, dw, mode)
+    if not want_grad:
+        return _depth_value_from_sums(sums, ld.loss_weight, w3).float(), None
+    loss, coef = _depth_from_sums(sums, ld.loss_weight, w3)
+    g = torch.empty_like(dp) if grad_out is None else grad_out
+    depth_loss_grad(dp, dt, dw, mode, coef, g)
+    return loss.float(), g
 
 
 class DepthLoss(_Loss):
@@ -228,7 +263,7 @@ class DepthLoss(_Loss):
             return (pred * 0).sum()
         _gpu(pred, "pred")
         s = depth_loss_sums(_f32(pred), _f32(target), _f32(mask_weight), DEPTH_MODES[self.depth_act_mode])
-        loss, _ = _depth_from_sums(s, self.loss_weight, [float(v) for v in self.weight])
+        loss = _depth_value_from_sums(s, self.loss_weight, [float(v) for v in self.weight])
         if reduction_override == "sum":
             loss = loss * 3.0
         return loss.float()
@@ -243,7 +278,7 @@ def _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, g
     pixels of the positive rows, the mean of the per-row dice losses, the rank cross-entropy.  mp [R, HW] fp32; `grad` (or
     None) [R, HW] receives d(sum of the three) / d(mask_pred).  `keys` / `empty_keys` name the entries with / without
     positives (the reference's names differ between the two cases)."""
-    lib, dev = _lib.load(), mp.device
+    dev = mp.device
     R, HW = B * N, H * W
     ignore, lr = head.ignore_label, head.loss_rank
     num_pos = int(pos.sum())
@@ -263,26 +298,19 @@ def _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, g
     losses[keys[0]] = (lm.loss_weight * s[:, 0].sum() / ntot).float()                          # BCE mean over the selected pixels
     bc = s[:, 3] + s[:, 4] + 2 * ldice.eps
     losses[keys[1]] = (ldice.loss_weight * (1 - 2 * s[:, 2] / bc).mean()).float()
-    rank_target = None
     if lr is not None:
-        # rank target: pixel -> index (within its image) of the LAST positive row whose target covers it
-        rank_target = torch.empty((B, HW), dtype=torch.int32, device=dev)
-        pos_u8 = pos.to(torch.uint8).contiguous()      # named: alive until the launch is queued
-        _lib.check(lib.ph_rank_target(_lib.ptr(mt), _lib.ptr(pos_u8), B, N, HW, ignore, _lib.ptr(rank_target),
-                                      _lib.stream_ptr()), "ph_rank_target")
-        losses[keys[2]] = (lr.loss_weight * rank_loss_sum(mp.reshape(B, N, H, W), rank_target, ignore) / (B * HW)).float()
+        rt = torch.empty((B, HW), dtype=torch.int32, device=dev)
+        rank_target(mt, pos.to(torch.uint8).contiguous(), B, N, HW, ignore, rt)
+        losses[keys[2]] = (lr.loss_weight * rank_loss_sum(mp.reshape(B, N, H, W), rt, ignore) / (B * HW)).float()
     if grad is not None:
         if lr is not None:
-            _lib.check(lib.ph_rank_loss_grad(_lib.ptr(mp), _lib.ptr(rank_target), B, N, HW, ignore, lr.loss_weight / (B * HW),
-                                             _lib.ptr(grad), _lib.stream_ptr()), "ph_rank_loss_grad")
+            rank_loss_grad(mp, rt, B, N, HW, ignore, lr.loss_weight / (B * HW), grad)
         else:
             grad.zero_()
         P = rows.numel()
         coef = torch.stack([torch.full((P,), lm.loss_weight, dtype=torch.float64, device=dev) / ntot,
                             -2.0 * ldice.loss_weight / (P * bc), 4.0 * ldice.loss_weight * s[:, 2] / (P * bc * bc)], 1)
-        coef = coef.float().contiguous()
-        _lib.check(lib.ph_mask_loss_grad(_lib.ptr(mp), _lib.ptr(mt), _lib.ptr(mw), _lib.ptr(rows), P, HW, _lib.ptr(coef),
-                                         _lib.ptr(grad), _lib.stream_ptr()), "ph_mask_loss_grad")
+        mask_loss_grad(mp, mt, mw, rows, coef.float().contiguous(), grad)
 
 
 # ---- one stage -----------------------------------------------------------------------------------------------------------------
@@ -292,7 +320,7 @@ def stage_losses(head, cls_score, mask_pred, depth_pred, labels, label_weights, 
     assign stride), targets as `get_targets` returns them.  Returns the reference's dict of losses (+ 'pos_acc'); with
     `with_grads` also dict(mask_pred=, cls_score=, depth_pred=) = d(sum of the losses) / d(prediction)."""
     _gpu(mask_pred, "mask_pred")
-    lib, dev = _lib.load(), mask_pred.device
+    dev = mask_pred.device
     B, N, H, W = mask_pred.shape
     R, HW, L = B * N, H * W, head.num_classes
     mp, dp, cs = _f32(mask_pred).reshape(R, HW), _f32(depth_pred).reshape(R, HW), _f32(cls_score).reshape(R, -1)
@@ -301,20 +329,12 @@ def stage_losses(head, cls_score, mask_pred, depth_pred, labels, label_weights, 
     num_pos = int(pos.sum())
     from .dist import reduce_mean
     avg = max(float(reduce_mean(pos.sum().float(), _REDUCE_GROUP[-1])), 1.0)                  # :376-377 (mean over ranks, clamp)
-    losses, grads = {}, None
-    if with_grads:
-        grads = dict(mask_pred=torch.empty((R, HW), dtype=torch.float32, device=dev),
-                     cls_score=torch.empty_like(cs), depth_pred=torch.empty((R, HW), dtype=torch.float32, device=dev))
+    losses = {}
+    grads = dict(mask_pred=torch.empty_like(mp).view(B, N, H, W), cls_score=torch.empty_like(cs).view(B, N, -1),
+                 depth_pred=torch.empty_like(dp).view(B, N, H, W)) if with_grads else None
+    flat = lambda k: grads[k].view(R, -1) if with_grads else None             # the kernels write [R, .] rows
     # ---- depth (:383-391)
-    ld = head.loss_depth
-    mode = DEPTH_MODES[ld.depth_act_mode]
-    dt, dw = _f32(depth_targets).reshape(R, HW), _f32(depth_weights).reshape(R, HW)
-    w3 = [float(v) for v in ld.weight]
-    loss_d, dcoef = _depth_from_sums(depth_loss_sums(dp, dt, dw, mode), ld.loss_weight, w3)
-    losses["loss_depth"] = loss_d.float()
-    if with_grads:
-        _lib.check(lib.ph_depth_loss_grad(_lib.ptr(dp), _lib.ptr(dt), _lib.ptr(dw), R * HW, mode, *dcoef, _lib.ptr(grads["depth_pred"]),
-                                          _lib.stream_ptr()), "ph_depth_loss_grad")
+    losses["loss_depth"], _ = _depth_terms(head.loss_depth, dp, depth_targets, depth_weights, with_grads, flat("depth_pred"))
     # ---- classification (:393-402)
     lc = head.loss_cls
     lw = _f32(label_weights).reshape(R, -1)
@@ -324,16 +344,11 @@ def stage_losses(head, cls_score, mask_pred, depth_pred, labels, label_weights, 
     else:
         losses["pos_acc"] = torch.zeros((), device=dev)
     if with_grads:
-        _lib.check(lib.ph_focal_loss_grad(_lib.ptr(cs), _lib.ptr(labels), _lib.ptr(lw), R, cs.shape[1], lc.gamma, lc.alpha,
-                                          lc.loss_weight / avg, _lib.ptr(grads["cls_score"]), _lib.stream_ptr()), "ph_focal_loss_grad")
+        focal_loss_grad(cs, labels, lw, lc.gamma, lc.alpha, lc.loss_weight / avg, flat("cls_score"))
     # ---- masks (:404-437)
-    _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, grads["mask_pred"] if with_grads else None,
+    _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, flat("mask_pred"),
                 ("loss_rpn_mask", "loss_rpn_dice", "loss_rank"), ("loss_mask", "loss_dice", "loss_rank"))
-    if with_grads:
-        grads = dict(mask_pred=grads["mask_pred"].reshape(B, N, H, W), cls_score=grads["cls_score"].reshape(B, N, -1),
-                     depth_pred=grads["depth_pred"].reshape(B, N, H, W))
-        return losses, grads
-    return losses
+    return (losses, grads) if with_grads else losses
 
 
 # ---- targets (kernel_update_head.py:443-591) ------------------------------------------------------------------------------------
@@ -412,7 +427,6 @@ def get_targets(head, sampling_results, gt_mask, gt_labels, rcnn_train_cfg, conc
     return tuple(cols)
 
 
-
 # ---- KernelHead (the rpn side): kernel_head.py:456-698 --------------------------------------------------------------------------
 def rpn_losses(head, mask_pred, seg_preds, depth_pred, labels, label_weights, mask_targets, mask_weights, seg_targets,
                depth_targets, depth_weights, with_grads=False):
@@ -421,29 +435,21 @@ def rpn_losses(head, mask_pred, seg_preds, depth_pred, labels, label_weights, ma
     loss_rpn_seg = sigmoid focal loss of conv_seg's map over the labelled pixels.  mask_pred [B, N, H, W], seg_preds
     [B, L, H, W], depth_pred [B, 1 or N + stuff rows, H, W].  With `with_grads`: dict(mask_pred=, seg_preds=, depth_pred= [B, 1, H, W])."""
     _gpu(mask_pred, "mask_pred")
-    lib, dev = _lib.load(), mask_pred.device
+    dev = mask_pred.device
     B, N, H, W = mask_pred.shape
     R, HW, L = B * N, H * W, head.num_classes
     mp = _f32(mask_pred).reshape(R, HW)
     labels = labels.to(dev).long().contiguous()
     pos = (labels >= 0) & (labels < L)                                                        # :475
-    losses, grads = {}, None
-    if with_grads:
-        grads = dict(mask_pred=torch.empty((R, HW), dtype=torch.float32, device=dev))
-    if depth_pred is not None:                                                                # :478-486
-        ld = head.loss_depth
-        mode = DEPTH_MODES[ld.depth_act_mode]
+    losses = {}
+    grads = dict(mask_pred=torch.empty_like(mp).view(B, N, H, W)) if with_grads else None
+    if depth_pred is not None:                                                               # :478-486
         Rd = depth_targets.shape[0]               # B * (proposals + stuff rows): one broadcast map per image (:386,482)
         dp = _f32(depth_pred.expand(B, Rd // B, H, W)).reshape(Rd, HW)
-        dt, dw = _f32(depth_targets).reshape(Rd, HW), _f32(depth_weights).reshape(Rd, HW)
-        loss_d, dcoef = _depth_from_sums(depth_loss_sums(dp, dt, dw, mode), ld.loss_weight, [float(v) for v in ld.weight])
-        losses["loss_depth"] = loss_d.float()
+        losses["loss_depth"], g = _depth_terms(head.loss_depth, dp, depth_targets, depth_weights, with_grads)
         if with_grads:
-            g = torch.empty((Rd, HW), dtype=torch.float32, device=dev)
-            _lib.check(lib.ph_depth_loss_grad(_lib.ptr(dp), _lib.ptr(dt), _lib.ptr(dw), Rd * HW, mode, *dcoef, _lib.ptr(g),
-                                              _lib.stream_ptr()), "ph_depth_loss_grad")
             grads["depth_pred"] = g.reshape(B, Rd // B, H, W).sum(1, keepdim=True)           # the rows are one broadcast map
-    _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, grads["mask_pred"] if with_grads else None,
+    _mask_terms(head, mp, mask_targets, mask_weights, pos, B, N, H, W, losses, grads["mask_pred"].view(R, HW) if with_grads else None,
                 ("loss_rpn_mask", "loss_rpn_dice", "loss_rpn_rank"), ("loss_rpn_mask", "loss_rpn_dice", "loss_rank"))
     if seg_preds is not None:                                                                 # :538-551
         ls = head.loss_seg
@@ -456,31 +462,19 @@ def rpn_losses(head, mask_pred, seg_preds, depth_pred, labels, label_weights, ma
         losses["loss_rpn_seg"] = (ls.loss_weight * seg_focal_sum(sp, st, ls.gamma, ls.alpha) / nd).float()
         if with_grads:
             g = torch.empty_like(sp)
-            _lib.check(lib.ph_seg_focal_grad(_lib.ptr(sp), _lib.ptr(st), B, sp.shape[1], HW, ls.gamma, ls.alpha, ls.loss_weight / nd,
-                                             _lib.ptr(g), _lib.stream_ptr()), "ph_seg_focal_grad")
+            seg_focal_grad(sp, st, ls.gamma, ls.alpha, ls.loss_weight / nd, g)
             grads["seg_preds"] = g.reshape(seg_preds.shape)
-    if with_grads:
-        grads["mask_pred"] = grads["mask_pred"].reshape(B, N, H, W)
-        return losses, grads
-    return losses
+    return (losses, grads) if with_grads else losses
 
 
 def dense_depth_loss(head, depth_pred, gt_depth, with_grad=False):
     """losses['depth_dense'] (kernel_head.py:438-442): DepthLoss of the direct depth map against the ground truth, weight = gt > 0"""
-    ld = head.loss_depth
-    mode = DEPTH_MODES[ld.depth_act_mode]
     dp, gd = _f32(depth_pred).reshape(-1), _f32(gt_depth.to(depth_pred.device)).reshape(-1)
     if dp.numel() != gd.numel():
         raise ValueError(f"depth_dense: prediction {tuple(depth_pred.shape)} and gt_depth {tuple(gt_depth.shape)} differ in size")
-    w = (gd > 0).float()
-    sums = depth_loss_sums(dp, gd, w, mode)
-    if not with_grad:                      # the logged value of a training step: nothing here waits for the device
-        return _depth_value_from_sums(sums, ld.loss_weight, [float(v) for v in ld.weight]).float()
-    loss, coef = _depth_from_sums(sums, ld.loss_weight, [float(v) for v in ld.weight])
-    g = torch.empty_like(dp)
-    _lib.check(_lib.load().ph_depth_loss_grad(_lib.ptr(dp), _lib.ptr(gd), _lib.ptr(w), dp.numel(), mode, *coef, _lib.ptr(g),
-                                              _lib.stream_ptr()), "ph_depth_loss_grad")
-    return loss.float(), g.reshape(depth_pred.shape)
+    # without the gradient this is the logged value of a training step: nothing here waits for the device
+    loss, g = _depth_terms(head.loss_depth, dp, gd, (gd > 0).float(), with_grad)
+    return (loss, g.reshape(depth_pred.shape)) if with_grad else loss
 
 
 def rpn_target_single(head, pos_inds, neg_inds, pos_mask, neg_mask, pos_gt_mask, pos_gt_labels, gt_sem_seg, gt_sem_cls, pos_depth,
@@ -512,8 +506,7 @@ def rpn_target_single(head, pos_inds, neg_inds, pos_mask, neg_mask, pos_gt_mask,
     sem_c = gt_sem_cls.to(dev).long().contiguous() if S else None
     pgm = pos_gt_mask.float().contiguous() if num_pos else None
     pgl = pos_gt_labels.to(dev).long().contiguous() if num_pos else None
-    _lib.check(_lib.load().ph_seg_target(_lib.ptr(sem_f), _lib.ptr(sem_c), S, _lib.ptr(pgm), _lib.ptr(pgl), num_pos, L, H * W,
-                                         _lib.ptr(seg_targets), _lib.stream_ptr()), "ph_seg_target")
+    seg_target(sem_f, sem_c, S, pgm, pgl, num_pos, L, seg_targets)
     if num_neg:
         label_weights[neg_inds] = 1.0
     depth_targets = depth_weights = None
@@ -997,9 +990,7 @@ def fused_losses(head, desc, mask_pred, cls_score, depth_pred, seg_pred, with_gr
         g = dict(mask_pred=torch.empty_like(mp), depth_pred=torch.empty_like(dp) if have_depth else None,
                  cls_score=torch.empty_like(cs) if cs is not None else None, seg_preds=torch.empty_like(sp) if sp is not None else None)
     P = desc.ptr
-    gd = g["depth_pred"] if (g and have_depth) else (torch.empty_like(dp) if g else None)
-    if not have_depth:        # no depth items: an empty item table (dstart all zero) -- the kernel reads nothing
-        pass
+    gd = g["depth_pred"] if (g and have_depth) else (torch.empty_like(dp) if g else None)      # no depth items: dstart is all zero
     _lib.check(lib.ph_train_losses(C.byref(c), _lib.ptr(mp), _lib.ptr(cs), _lib.ptr(dp), _lib.ptr(sp), P["pos_rows"], P["pos_u8"], P["tptr"],
                                    P["wptr"], P["dstart"], P["dit_t"], P["dit_w"], P["dit_s"], P["labels"] if cs is not None else None,
                                    P.get("label_w") if cs is not None else None, P.get("sstart") if sp is not None else None,
