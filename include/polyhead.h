@@ -1495,6 +1495,79 @@ int ph_gt_prepare(const uint8_t* seg, const int32_t* row_of, const int32_t* nseg
                   int Wp, int aH, int aW, int Gmax, int Smax, int mode, float* things, float* stuff, float* things_hard,
                   float* stuff_hard, float* valid, float* depth_out, void* stream);
 
+/* ---- the optimizer step: gradient clipping by the global L2 norm + AdamW over every tensor in ONE call (csrc/ph_optim.hip) ------
+ * Replaces torch.nn.utils.clip_grad_norm_(max_norm, norm_type = 2) + torch.optim.AdamW.step (the schedule of every shipped config:
+ * AdamW(lr = 2e-4, weight_decay = 0.05) behind grad_clip = dict(max_norm = 1, norm_type = 2)) without rewriting a gradient.
+ *
+ * THE TABLE.  One ph_optim_tensor per tensor, the same bytes on the host (table_host: read by the argument checks) and on the device
+ * (table_dev: read by the kernels; the caller uploads it and keeps the two equal).  p, g, m, v: DEVICE fp32 [n], any 4-byte
+ * alignment; g == NULL: the tensor takes no part in the call (torch's `.grad is None`).  lr: the tensor's base rate, multiplied by
+ * the call's lr_factor; weight_decay: decoupled, as AdamW's.
+ *
+ * WORK ITEMS.  An item is one chunk of PH_OPTIM_CHUNK elements of ONE tensor, the last chunk of a tensor short; the items are numbered
+ * tensor by tensor and first_item is the number of the tensor's first one (a tensor of n == 0 has none and shares its number with its
+ * successor; n > 0 with g == NULL keeps its items, which do nothing).  The call checks the column.  A workgroup of 256 threads takes
+ * items in a grid-stride loop (at most max_blocks workgroups; 0: the library's choice), finds an item's tensor by a search over the
+ * column in LDS, and moves 16 bytes per lane where p, g, m, v of the tensor are all 16-byte aligned, 4 bytes otherwise and on the
+ * last n % 4 elements.  Everything a launch reduces is stored per item and summed in index order: no float atomics, and the results
+ * do not depend on the grid.
+ *
+ * AT MOST THREE LAUNCHES, nothing else: no allocation, no synchronisation, no memset node, capturable.
+ *   1. k_optim_sumsq     partial[item] = sum g^2, squared and summed in fp64 from the element up (a finite |g| > 1.8e19 does not
+ *                        overflow).  Omitted when neither max_norm > 0 nor PH_OPTIM_SKIP_NONFINITE asks for the norm.
+ *   2. k_optim_finalize  one workgroup: the partials in a fixed tree in fp64, norm = sqrt(sum), coef = max_norm / (norm + 1e-6) clamped
+ *                        at 1 as torch does (a NaN stays a NaN; max_norm <= 0: coef = 1), skip = norm not finite and
+ *                        PH_OPTIM_SKIP_NONFINITE; when not skipping the step counter t advances; 1 - beta1^t and sqrt(1 - beta2^t) in
+ *                        fp64, each rounded once to fp32; the state record.
+ *   3. k_optim_update    torch's _single_tensor_adamw in fp32 without contraction, g' = g coef on the fly, lr = tensor lr * lr_factor:
+ *                            p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = beta2 v + ((1 - beta2) g') g';
+ *                            p += (-(lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps)
+ *                        (1 - lr wd and lr / bc1 formed in fp64 and rounded once, as torch's Python scalars are).  g is NOT modified
+ *                        unless PH_OPTIM_ZERO_GRADS is set: then zeros are stored over every gradient read.  On a skipped call p, m,
+ *                        v and the step counter keep their bits; the gradients are still zeroed if asked.
+ * lr_factor_dev != NULL: the factor is read from that DEVICE fp32 by the kernel (a captured graph follows a schedule); else the
+ * host value lr_factor is used.
+ *
+ * state      DEVICE, 8-byte aligned, zeroed by the caller before the first call (step 0): see ph_optim_state
+ * workspace  DEVICE, 256-byte aligned, ph_optim_workspace_bytes: the fp64 partials.  ZEROING CONTRACT: none.
+ * PH_EINVAL (ntensors <= 0, n < 0, a null p / m / v with n > 0, a first_item that is not the running item count, beta1 / beta2
+ * outside [0, 1), eps <= 0, a misaligned state or workspace), PH_EUNSUPPORTED (more than PH_OPTIM_MAX_TENSORS tensors, 2^31 items)
+ * and PH_EWORKSPACE are returned before anything is launched, with ph_last_error_string naming the argument. */
+#define PH_OPTIM_CHUNK 4096
+#define PH_OPTIM_MAX_TENSORS 4096
+enum { PH_OPTIM_SKIP_NONFINITE = 1, PH_OPTIM_ZERO_GRADS = 2 };      /* ph_optim_cfg.flags */
+enum { PH_OPTIM_OK = 0, PH_OPTIM_ENONFINITE = 1 };                  /* ph_optim_state.status */
+typedef struct {
+    float* p;
+    float* g;
+    float* m;
+    float* v;
+    int64_t n;
+    double lr, weight_decay;
+    int64_t first_item;
+} ph_optim_tensor;
+typedef struct {
+    double beta1, beta2, eps;
+    double max_norm;         /* <= 0: no clipping */
+    int32_t flags;
+    int32_t max_blocks;      /* workgroups per launch at most; 0: the library's choice.  The results do not depend on it */
+} ph_optim_cfg;
+typedef struct {
+    int64_t step;            /* calls applied so far: AdamW's t, ONE count for every tensor */
+    int64_t skipped;         /* calls skipped so far */
+    int32_t status;          /* of the last call: PH_OPTIM_OK, or PH_OPTIM_ENONFINITE: its norm was not finite */
+    int32_t skip;            /* 1: the last call was skipped (p, m, v, step untouched) */
+    float grad_norm;         /* of the last call, before clipping; -1 where the call did not ask for it */
+    float clip_coef;         /* g' = g clip_coef */
+    float bias1, bias2_sqrt; /* 1 - beta1^step, sqrt(1 - beta2^step) */
+} ph_optim_state;
+size_t ph_optim_workspace_bytes(const ph_optim_tensor* table_host, int ntensors);   /* 0 on a bad table (ph_last_error_string) */
+int ph_optim_step(const ph_optim_cfg* cfg, const ph_optim_tensor* table_host, const ph_optim_tensor* table_dev, int ntensors,
+                  float lr_factor, const float* lr_factor_dev, ph_optim_state* state, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* zeros over every gradient of the table, in place: ONE launch, the same items (the table checks of ph_optim_step apply) */
+int ph_optim_zero_grads(const ph_optim_tensor* table_host, const ph_optim_tensor* table_dev, int ntensors, int max_blocks, void* stream);
+
 /* ---- self tests of the gfx950 fragment layouts the kernels rely on (tests/test_gpu_selftest.py) */
 int ph_selftest_mfma16(const uint16_t* a /*[16][32]*/, const uint16_t* bt /*[16][32]*/, float* d /*[16][16]*/, void* stream);
 int ph_selftest_mfma32(const uint16_t* a /*[32][16]*/, const uint16_t* bt /*[32][16]*/, float* d /*[32][32]*/, void* stream);

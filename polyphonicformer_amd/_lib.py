@@ -213,6 +213,26 @@ class TrackLossCfg(C.Structure):
                 ("pos_margin", C.c_float), ("neg_margin", C.c_float), ("hard_mining", C.c_int32)]
 
 
+# the optimizer step (polyhead.h ph_optim_tensor .. ph_optim_zero_grads)
+PH_OPTIM_CHUNK, PH_OPTIM_MAX_TENSORS = 4096, 4096
+PH_OPTIM_SKIP_NONFINITE, PH_OPTIM_ZERO_GRADS = 1, 2
+PH_OPTIM_OK, PH_OPTIM_ENONFINITE = 0, 1
+
+
+class OptimTensor(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("p", "g", "m", "v")] + [("n", C.c_int64), ("lr", C.c_double), ("weight_decay", C.c_double),
+                                                                  ("first_item", C.c_int64)]
+
+
+class OptimCfg(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("beta1", "beta2", "eps", "max_norm")] + [("flags", C.c_int32), ("max_blocks", C.c_int32)]
+
+
+class OptimState(C.Structure):
+    _fields_ = [("step", C.c_int64), ("skipped", C.c_int64), ("status", C.c_int32), ("skip", C.c_int32)] + \
+        [(n, C.c_float) for n in ("grad_norm", "clip_coef", "bias1", "bias2_sqrt")]
+
+
 # C typedef name -> its mirror above: every Structure of this module (tests/test_abi.py compares each layout with the header's)
 STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
@@ -220,7 +240,8 @@ STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decod
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
            "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout,
-           "ph_loss_cfg": LossCfg, "ph_track_loss_cfg": TrackLossCfg}
+           "ph_loss_cfg": LossCfg, "ph_track_loss_cfg": TrackLossCfg, "ph_optim_tensor": OptimTensor, "ph_optim_cfg": OptimCfg,
+           "ph_optim_state": OptimState}
 
 # name -> (restype, argtypes); every symbol include/polyhead.h declares
 _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
@@ -413,6 +434,9 @@ SIGNATURES = {
     "ph_gtmask_boxes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _L, _I, _I,
                                   _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ph_gt_prepare": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ph_optim_workspace_bytes": (C.c_size_t, [_P, _I]),
+    "ph_optim_step": (C.c_int, [C.POINTER(OptimCfg), _P, _P, _I, C.c_float, _P, _P, _P, _Z, _P]),
+    "ph_optim_zero_grads": (C.c_int, [_P, _P, _I, _I, _P]),
     "ph_selftest_mfma16": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_mfma32": (C.c_int, [_P, _P, _P, _P]),
     "ph_selftest_readbw": (C.c_int, [_P, _L, _I, _P, _P]),

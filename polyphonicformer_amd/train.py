@@ -989,6 +989,12 @@ class _StepBase:
                     out.append(p)
         return out
 
+    def optimizer(self, **kw):
+        """an `optim.AdamWStep` over `parameters()`: gradient clipping + AdamW in one launch-only call behind `forward_backward`
+        (kw: lr, betas, eps, weight_decay, max_norm, skip_nonfinite)"""
+        from .optim import AdamWStep
+        return AdamWStep(self.parameters(), **kw)
+
     def assign_status(self):
         """the status words of the last step's device solves, downloaded now (a synchronising copy, when the caller chooses to):
         int64 [solves, B], 0 = solved; _lib.PH_ASSIGN_ENONFINITE: the image's costs were not finite and it got the trivial matching.
