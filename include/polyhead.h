@@ -1265,6 +1265,30 @@ typedef struct {
    synchronises. */
 int ph_dtracker_run(ph_dtracker* t, const ph_dtracker_io* io, int B, void* stream);
 
+/* ---- a BANK of device trackers: `streams` independent states (1 .. 64 cameras) advanced by one frame each in ONE launch sequence.
+ * Stream s's block -- its whole state and per-frame scratch, ph_dtracker_layout's layout -- lies at s * total_bytes of one caller-owned
+ * buffer of ph_dtracker_bank_bytes; ph_dtracker_get_layout keeps answering for stream 0.  The kernels are ph_dtracker_run's with one
+ * more grid dimension of size `streams`: a step of S streams is the seven launches of one frame, and the tracker of ph_dtracker_create
+ * is the bank of one.  Streams share nothing (no atomics, no hand-off between workgroups).  Same conventions as above. */
+/* 0 with a message on a bad cfg, capacity, max_dets or streams outside 1 .. 64 */
+size_t ph_dtracker_bank_bytes(const ph_tracker_cfg* cfg, int capacity, int max_dets, int streams);
+/* ph_dtracker_create for `streams` states; device_mem: ph_dtracker_bank_bytes, 256-byte aligned.  Destroyed by ph_dtracker_destroy */
+int ph_dtracker_bank_create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, int streams,
+                            ph_dtracker** out);
+/* the stream count and the bytes between two streams' blocks (ph_dtracker_layout.total_bytes) */
+int ph_dtracker_get_streams(const ph_dtracker* t, int* streams_out, uint64_t* stride_bytes_out);
+/* one launch: the streams whose bit is set in `mask` (bit s = stream s; the 64 bits of the word, stream 63 being its sign bit) are
+   reset as ph_dtracker_reset does -- a camera starts a new sequence --, the others are untouched.  A bit beyond the tracker's streams:
+   PH_EINVAL.  ph_dtracker_reset resets every stream. */
+int ph_dtracker_reset_streams(ph_dtracker* t, int64_t mask, int64_t first_frame_id, void* stream);
+/* one frame of every stream: io's strides index STREAMS (frame s is stream s's next frame; kept_out / ids_out [streams][max_dets],
+   kept_counts [streams]).  active: nullable DEVICE int32 [streams]; a zero word means the stream has no frame in this step -- its
+   workgroups return before they read or write anything of the stream, so its state, frame counter and status keep their bits, and its
+   kept_counts entry is 0.  Count 0, `refuse`, PH_DTRK_ECOUNT, PH_DTRK_EPOOL and the sticky error mean per stream what they mean for
+   ph_dtracker_run; a refused or sticky stream does not affect any other.  Launches only; capturable.  ph_dtracker_run on a tracker of
+   more than one stream is PH_EINVAL: its frames are in order, a bank's are side by side. */
+int ph_dtracker_step(ph_dtracker* t, const ph_dtracker_io* io, const int32_t* active, void* stream);
+
 /* ---- the launch-only counterpart of ph_assoc_plan_match: the device tracker and the track-id maps behind ph_assoc_plan_run on the
  * same stream, with no host staging and no synchronisation; capturable.  It points a ph_dtracker_io at the things tables (counts at
  * word 0, labels, boxes and the overflow word at their offsets, embeddings [B][cap][256]) one frame at a time -- the tracker's
@@ -1277,6 +1301,11 @@ int ph_dtracker_run(ph_dtracker* t, const ph_dtracker_io* io, int B, void* strea
  *   ids_dev_out    int64 [B][cap] on the DEVICE, nullable: the value painted onto thing j of frame b (0 beyond nthing) */
 int ph_assoc_plan_track(ph_assoc_plan* plan, ph_dtracker* tracker, const int32_t* pan, const int32_t* things_dev, const float* embeds_dev,
                         double* track_out, int64_t* ids_dev_out, void* stream);
+/* ph_assoc_plan_track with frame b of the plan going to STREAM b of a tracker bank: one ph_dtracker_step over the things tables, one
+ * k_assoc_trklut launch over the B frames, the paint.  Needs plan B == the tracker's streams and max_things <= max_dets (PH_EINVAL).
+ * active: as ph_dtracker_step's; an idle stream's track map is all zero. */
+int ph_assoc_plan_track_streams(ph_assoc_plan* plan, ph_dtracker* tracker, const int32_t* pan, const int32_t* things_dev,
+                                const float* embeds_dev, const int32_t* active, double* track_out, int64_t* ids_dev_out, void* stream);
 
 /* ================================================================================================================================
  * DVPQ tallies on the device (ph_dvpq.hip): what dvps_eval.video_evaluate needs from a frame, computed from the maps where they lie.

@@ -421,6 +421,12 @@ SIGNATURES = {
     "ph_dtracker_get_layout": (C.c_int, [_P, C.POINTER(DtrackerLayout)]),
     "ph_dtracker_run": (C.c_int, [_P, C.POINTER(DtrackerIO), _I, _P]),
     "ph_assoc_plan_track": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "ph_dtracker_bank_bytes": (C.c_size_t, [C.POINTER(TrackerCfg), _I, _I, _I]),
+    "ph_dtracker_bank_create": (C.c_int, [C.POINTER(TrackerCfg), _P, _Z, _I, _I, _I, C.POINTER(C.c_void_p)]),
+    "ph_dtracker_get_streams": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "ph_dtracker_reset_streams": (C.c_int, [_P, _L, _L, _P]),
+    "ph_dtracker_step": (C.c_int, [_P, C.POINTER(DtrackerIO), _P, _P]),
+    "ph_assoc_plan_track_streams": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ph_dvpq_workspace_bytes": (C.c_size_t, [C.POINTER(DvpqCfg)]),
     "ph_dvpq_frames": (C.c_int, [C.POINTER(DvpqCfg), C.POINTER(DvpqIO), _P, _Z, _P]),
     "ph_assign_desc_layout": (C.c_int, [C.POINTER(AssignCfg), _P, _P, _P, C.POINTER(AssignLayout)]),

@@ -253,15 +253,22 @@ __global__ void k_assoc_gather(const float* __restrict__ ext /*[B][K][4]*/, int 
 
 // one frame's track look-up table from the device tracker's outputs, as ph_assoc_plan_match forms it on the host: ids + 1, negatives
 // to 0, painted in segment order onto the ids in the order the tracker returns them; kept_count == 0 (a skipped or refused frame):
-// all zero.  One workgroup; ids_out (nullable): the frame's [cap] painted values
-__global__ __launch_bounds__(256) void k_assoc_trklut(const int32_t* __restrict__ tab, int K, int cap, const int64_t* __restrict__ ids,
-                                                      const int32_t* __restrict__ kept_count, double* __restrict__ lut,
+// all zero.  One workgroup per frame, grid (frames): frame b's table at tab + b * words, its tracker outputs at ids + b * ids_stride
+// and kept_count + b * kc_stride (the streams of a bank, one frame each), its look-up table at lut + b * (K + 1); ids_out (nullable):
+// the frame's [cap] painted values.  active (nullable, int32 [frames]): a zero word is an idle stream, whose tracker outputs are not
+// read -- all zero
+__global__ __launch_bounds__(256) void k_assoc_trklut(const int32_t* __restrict__ tab, int words, int K, int cap, const int64_t* __restrict__ ids,
+                                                      int64_t ids_stride, const int32_t* __restrict__ kept_count, int64_t kc_stride,
+                                                      const int32_t* __restrict__ active, double* __restrict__ lut,
                                                       int64_t* __restrict__ ids_out) {
+    const int b = blockIdx.x;
+    tab += (int64_t)b * words; ids += b * ids_stride; kept_count += b * kc_stride; lut += (int64_t)b * (K + 1);
+    if (ids_out) ids_out += (int64_t)b * cap;
     for (int i = threadIdx.x; i <= K; i += blockDim.x) lut[i] = 0.0;
     __syncthreads();
     int n = tab[0];
     n = n < 0 ? 0 : (n > cap ? cap : n);
-    const int k = kept_count[0];
+    const int k = (active && active[b] == 0) ? 0 : kept_count[0];
     for (int j = threadIdx.x; j < cap; j += blockDim.x) {
         int64_t v = 0;
         if (j < n && j < k) {
@@ -490,9 +497,40 @@ extern "C" int ph_assoc_plan_track(ph_assoc_plan* p, ph_dtracker* tracker, const
         io.embeds = embeds_dev + (size_t)b * g.cap * 256;
         io.kept_out = sc.kept; io.ids_out = sc.ids; io.kept_counts = sc.kept_count;
         PH_RUN(ph_dtracker_run(tracker, &io, 1, stream));
-        hipLaunchKernelGGL(k_assoc_trklut, dim3(1), dim3(256), 0, s, tab, g.K, g.cap, sc.ids, sc.kept_count, trk_dev + (size_t)b * (g.K + 1),
-                           ids_dev_out ? ids_dev_out + (size_t)b * g.cap : nullptr);
+        hipLaunchKernelGGL(k_assoc_trklut, dim3(1), dim3(256), 0, s, tab, g.words, g.K, g.cap, sc.ids, (int64_t)0, sc.kept_count, (int64_t)0,
+                           nullptr, trk_dev + (size_t)b * (g.K + 1), ids_dev_out ? ids_dev_out + (size_t)b * g.cap : nullptr);
     }
+    launch_paint<double>(g, pan, trk_dev, track_out, s);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+extern "C" int ph_assoc_plan_track_streams(ph_assoc_plan* p, ph_dtracker* tracker, const int32_t* pan, const int32_t* things_dev,
+                                           const float* embeds_dev, const int32_t* active, double* track_out, int64_t* ids_dev_out,
+                                           void* stream) {
+    PH_CHECK_ARG(p && tracker && pan && things_dev && embeds_dev && track_out, "null pointer");
+    const AGeo& g = p->g;
+    const PhDtrkScratch sc = ph_dtracker_scratch(tracker);
+    if (g.B != sc.streams) {
+        ph_set_error("ph_assoc_plan_track_streams: the plan has B = %d frames, the tracker %d streams", g.B, sc.streams);
+        return PH_EINVAL;
+    }
+    if (g.cap > sc.max_dets) {
+        ph_set_error("ph_assoc_plan_track_streams: max_things = %d is more than the tracker's max_dets = %d", g.cap, sc.max_dets);
+        return PH_EINVAL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* trk_dev = (double*)(p->ws + g.o_trk);
+    // frame b is stream b's next frame: the things tables' own strides index the streams
+    ph_dtracker_io io{};
+    io.counts = things_dev; io.count_stride = g.words;
+    io.labels = things_dev + 1 + g.cap; io.label_stride = g.words;
+    io.boxes = (const float*)(things_dev + 1 + 2 * g.cap); io.box_stride = g.words;
+    io.refuse = things_dev + g.words - 1; io.refuse_stride = g.words;
+    io.embeds = embeds_dev; io.embed_stride = (int64_t)g.cap * 256;
+    PH_RUN(ph_dtracker_step_scratch(tracker, &io, active, stream));
+    hipLaunchKernelGGL(k_assoc_trklut, dim3(g.B), dim3(256), 0, s, things_dev, g.words, g.K, g.cap, sc.ids, sc.ids_stride, sc.kept_count,
+                       sc.kc_stride, active, trk_dev, ids_dev_out);
     launch_paint<double>(g, pan, trk_dev, track_out, s);
     PH_CHECK_LAUNCH();
     return PH_OK;

@@ -163,13 +163,22 @@ int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int
 
 // device-count form of ph_track_affinity (ph_track.hip) for the device tracker (ph_dtracker.hip): grids sized for (max_n, max_m), every
 // workgroup reading cnt = (n, m, need) on the device -- need == 0: nothing runs.  workspace: ph_track_affinity_workspace_bytes(max_n,
-// max_m).  Launches only; the caller checks the launch.
+// max_m).  Launches only; the caller checks the launch.  `streams` trackers side by side: every pointer (cnt and workspace included)
+// is stream 0's and stream s's lies s * stride_bytes behind it; one more grid dimension of size `streams`; `active` (nullable, int32
+// [streams]): a zero word's workgroups return before they read anything of their stream.
 void ph_track_affinity_cnt(const float* emb, const int32_t* labels, const float* memo_emb, const int32_t* memo_labels, int max_n, int max_m,
-                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, void* stream);
-// the device tracker's per-frame outputs inside its own buffer, for ph_assoc_plan_track (one frame at a time): kept [max_dets],
-// ids [max_dets], kept_count [1]
-struct PhDtrkScratch { int32_t* kept = nullptr; int64_t* ids = nullptr; int32_t* kept_count = nullptr; int max_dets = 0; };
+                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, int streams, size_t stride_bytes,
+                           const int32_t* active, void* stream);
+// the device tracker's per-frame outputs inside its own buffer, for ph_assoc_plan_track (one frame at a time) and
+// ph_assoc_plan_track_streams (one frame per stream): kept [max_dets], ids [max_dets], kept_count [1] of stream 0; stream s's lie
+// s * the strides (elements) behind them
+struct PhDtrkScratch {
+    int32_t* kept = nullptr; int64_t* ids = nullptr; int32_t* kept_count = nullptr; int max_dets = 0;
+    int streams = 1; int64_t kept_stride = 0, ids_stride = 0, kc_stride = 0;
+};
 PhDtrkScratch ph_dtracker_scratch(const ph_dtracker* t);
+// ph_dtracker_step with these pieces as its outputs; `in`: the input pointers and strides of a ph_dtracker_io (checked by the caller)
+int ph_dtracker_step_scratch(ph_dtracker* t, const ph_dtracker_io* in, const int32_t* active, void* stream);
 
 // ---- bf16 bit helpers (round to nearest even; inputs are finite in this code base) ----------
 // gfx950 has a hardware round-to-nearest-even conversion (v_cvt_pk_bf16_f32); the compiler selects

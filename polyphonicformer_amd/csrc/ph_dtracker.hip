@@ -5,6 +5,11 @@
 // single-workgroup kernels walk them (k_dtrk_prepare, k_dtrk_assign: n <= 128 detections, m <= 4096 columns, latency-bound by design)
 // and a frame is seven launches that no host code waits for -- ph_dtracker_run can be captured into a graph.
 //
+// A BANK is S such trackers in one buffer: stream s has its whole block (state, scratch, io_* pieces; resolve()'s layout) at
+// s * total_bytes, every kernel has one grid dimension of size S and derives its stream's DState from the base and the stride and its
+// DFrame from the io strides, so a step of S streams is the same seven launches.  Streams share nothing: no atomics, no hand-off
+// between workgroups, and a workgroup of an idle stream returns before it touches that stream.  The single tracker is the bank of one.
+//
 // Arithmetic: thresholds are compared in fp32, iou1 is one rounded operation per statement with a correctly rounded division (what
 // the host's iou1 does under `fp contract(off)`), the EMA is k_trk_update's two rounded products and one rounded sum, and the scores
 // are ph_track_affinity's own kernels in their device-count forms (ph_track.hip), bit for bit.
@@ -43,6 +48,46 @@ struct DFrame {
     const float* boxes; const int32_t* labels; const int32_t* count; const int32_t* refuse; const float* embeds;
     int32_t* kept_out; int64_t* ids_out; int32_t* kept_count;
 };
+
+// the S streams of a launch: stream s's block starts s * stride bytes behind stream 0's; active (nullable): int32 [S], 0 = idle
+struct DBank { DState st; size_t stride; const int32_t* active; };
+// the S frames of a launch: frame s at base + s * stride (elements), outputs included; zero_idle: an idle stream's kept_count is
+// written 0 (the caller's array; never when the outputs are the streams' own io_* pieces)
+struct DIo {
+    ph_dtracker_io io;
+    int64_t kept_stride, ids_stride, kc_stride;
+    int zero_idle;
+};
+
+template <class T>
+__device__ __forceinline__ T* shifted(T* p, size_t bytes) { return (T*)((char*)p + bytes); }
+
+__device__ __forceinline__ DState stream_state(const DBank& bk, int s) {
+    const size_t o = (size_t)s * bk.stride;
+    const DState& b = bk.st;
+    DState d;
+    d.pool = shifted(b.pool, o); d.trk_id = shifted(b.trk_id, o); d.trk_seen = shifted(b.trk_seen, o); d.trk_label = shifted(b.trk_label, o);
+    d.trk_slot = shifted(b.trk_slot, o); d.trk_box = shifted(b.trk_box, o);
+    d.bd_count = shifted(b.bd_count, o); d.bd_label = shifted(b.bd_label, o); d.bd_slot = shifted(b.bd_slot, o); d.bd_box = shifted(b.bd_box, o);
+    d.free_stack = shifted(b.free_stack, o); d.status = shifted(b.status, o);
+    d.rec = shifted(b.rec, o); d.kept = shifted(b.kept, o); d.det_lab = shifted(b.det_lab, o); d.kbox = shifted(b.kbox, o);
+    d.memo_slot = shifted(b.memo_slot, o); d.memo_lab = shifted(b.memo_lab, o); d.act = shifted(b.act, o);
+    d.tmp_id = shifted(b.tmp_id, o); d.tmp_seen = shifted(b.tmp_seen, o); d.tmp_label = shifted(b.tmp_label, o); d.tmp_slot = shifted(b.tmp_slot, o);
+    d.tmp_box = shifted(b.tmp_box, o);
+    d.det = shifted(b.det, o); d.memo = shifted(b.memo, o); d.score = shifted(b.score, o); d.aff_ws = shifted((char*)b.aff_ws, o);
+    d.io_kept = shifted(b.io_kept, o); d.io_ids = shifted(b.io_ids, o); d.io_kc = shifted(b.io_kc, o);
+    d.capacity = b.capacity; d.max_dets = b.max_dets; d.gens = b.gens;
+    return d;
+}
+
+__device__ __forceinline__ DFrame stream_frame(const DIo& d, int s) {
+    const ph_dtracker_io& io = d.io;
+    return DFrame{io.boxes + s * io.box_stride, io.labels + s * io.label_stride, io.counts + s * io.count_stride,
+                  io.refuse ? io.refuse + s * io.refuse_stride : nullptr, io.embeds + s * io.embed_stride,
+                  io.kept_out + s * d.kept_stride, io.ids_out + s * d.ids_stride, io.kept_counts + s * d.kc_stride};
+}
+
+__device__ __forceinline__ bool stream_idle(const DBank& bk, int s) { return bk.active && bk.active[s] == 0; }
 
 struct Geo {
     ph_dtracker_layout lay;
@@ -104,8 +149,12 @@ __device__ float iou1(const float* a, const float* b) {
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// ---- one launch: empty tables, full free stack (slot 0 on top, as ph_tracker_create leaves it), counter, status
-__global__ __launch_bounds__(256) void k_dtrk_reset(DState st, int64_t first_frame_id) {
+// ---- one launch: empty tables, full free stack (slot 0 on top, as ph_tracker_create leaves it), counter, status; grid (x, S), the
+// streams outside `mask` are untouched
+__global__ __launch_bounds__(256) void k_dtrk_reset(DBank bk, unsigned long long mask, int64_t first_frame_id) {
+    const int s = blockIdx.y;
+    if (!((mask >> s) & 1ull)) return;
+    const DState st = stream_state(bk, s);
     const int i0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
     for (int i = i0; i < st.capacity; i += step) {
         st.free_stack[i] = st.capacity - 1 - i;
@@ -128,8 +177,11 @@ __global__ __launch_bounds__(256) void k_dtrk_reset(DState st, int64_t first_fra
 // ---- k_dtrk_prepare, one workgroup: what ph_tracker_match does before its first upload.  Stable descending-score order by counting
 // (rank = scores above + equal scores at a lower index: std::stable_sort's order), de-duplication against EVERY higher-scored
 // detection, kept or not (:147-155) -- so parallel over the positions --, compaction to the kept list, and the memory columns:
-// tracklets in creation order, then the backdrops newest first.  Writes the frame record and the row / label / slot tables.
-__global__ __launch_bounds__(256) void k_dtrk_prepare(DState st, ph_tracker_cfg c, DFrame f) {
+// tracklets in creation order, then the backdrops newest first.  Writes the frame record and the row / label / slot tables.  Grid (S).
+__global__ __launch_bounds__(256) void k_dtrk_prepare(DBank bk, ph_tracker_cfg c, DIo io) {
+    if (stream_idle(bk, blockIdx.x)) return;
+    const DState st = stream_state(bk, blockIdx.x);
+    const DFrame f = stream_frame(io, blockIdx.x);
     __shared__ float sbox[DT_MAXN * 5];
     __shared__ float skey[DT_MAXN];
     __shared__ int order[DT_MAXN];
@@ -190,8 +242,11 @@ __global__ __launch_bounds__(256) void k_dtrk_prepare(DState st, ph_tracker_cfg 
     }
 }
 
-// ---- k_trk_gather (ph_tracker.hip) in device-count form: grid max_dets + capacity, workgroups beyond the counts return
-__global__ __launch_bounds__(256) void k_dtrk_gather(DState st, const float* __restrict__ det_src) {
+// ---- k_trk_gather (ph_tracker.hip) in device-count form: grid (max_dets + capacity, S), workgroups beyond the counts return
+__global__ __launch_bounds__(256) void k_dtrk_gather(DBank bk, DIo io) {
+    if (stream_idle(bk, blockIdx.y)) return;
+    const DState st = stream_state(bk, blockIdx.y);
+    const float* __restrict__ det_src = io.io.embeds + blockIdx.y * io.io.embed_stride;
     const int r = blockIdx.x;
     if (r < st.max_dets) {
         if (r >= st.rec[REC_K]) return;
@@ -204,8 +259,10 @@ __global__ __launch_bounds__(256) void k_dtrk_gather(DState st, const float* __r
     }
 }
 
-// ---- k_trk_update (ph_tracker.hip) in device-count form: grid max_dets
-__global__ __launch_bounds__(256) void k_dtrk_update(DState st, float one_minus, float mom) {
+// ---- k_trk_update (ph_tracker.hip) in device-count form: grid (max_dets, S)
+__global__ __launch_bounds__(256) void k_dtrk_update(DBank bk, float one_minus, float mom) {
+    if (stream_idle(bk, blockIdx.y)) return;
+    const DState st = stream_state(bk, blockIdx.y);
     const int i = blockIdx.x;
     if (i >= st.rec[REC_K]) return;
     const int slot = clampi(st.act[2 * i], 0, st.capacity - 1), mode = st.act[2 * i + 1];
@@ -217,8 +274,8 @@ __global__ __launch_bounds__(256) void k_dtrk_update(DState st, float one_minus,
 
 // ---- k_dtrk_assign, one workgroup: everything ph_tracker_match does between its score download and its update launch.
 // A matched detection's tracklet row IS its column (columns 0 .. rows - 1 are the rows in creation order) and a new id is in no row
-// (ids are unique and below num_tracklets), so the host's searches for an id become `mrow`.
-__global__ __launch_bounds__(256) void k_dtrk_assign(DState st, ph_tracker_cfg c, DFrame f) {
+// (ids are unique and below num_tracklets), so the host's searches for an id become `mrow`.  Grid (S).
+__global__ __launch_bounds__(256) void k_dtrk_assign(DBank bk, ph_tracker_cfg c, DIo io) {
     __shared__ float red_v[256];
     __shared__ int red_j[256];
     __shared__ unsigned char taken[DT_MAXC];
@@ -230,6 +287,12 @@ __global__ __launch_bounds__(256) void k_dtrk_assign(DState st, ph_tracker_cfg c
     __shared__ int part[256];
     __shared__ int s_born, s_refuse, s_free, s_rows;
     const int t = threadIdx.x;
+    if (stream_idle(bk, blockIdx.x)) {                   // uniform: no frame in this step, nothing of the stream is read or written
+        if (io.zero_idle && t == 0) io.io.kept_counts[blockIdx.x * io.kc_stride] = 0;
+        return;
+    }
+    const DState st = stream_state(bk, blockIdx.x);
+    const DFrame f = stream_frame(io, blockIdx.x);
     int64_t* S = st.status;
     const int mode = st.rec[REC_MODE];
     if (mode != MODE_RUN) {                              // an empty frame, a frame behind an error, or a frame refused by its own tables
@@ -402,26 +465,35 @@ __global__ __launch_bounds__(256) void k_dtrk_assign(DState st, ph_tracker_cfg c
 struct ph_dtracker {
     ph_tracker_cfg c;
     Geo g;
-    DState st;
+    DState st;                                           // stream 0's
+    int streams;
+    size_t stride;                                       // bytes between two streams' blocks: g.lay.total_bytes
 };
 
-extern "C" size_t ph_dtracker_device_bytes(const ph_tracker_cfg* cfg, int capacity, int max_dets) {
-    Geo g;
-    if (resolve(cfg, capacity, max_dets, g, "ph_dtracker_device_bytes")) return 0;
-    return g.lay.total_bytes;
+namespace {
+
+constexpr int DT_MAXS = 64;
+
+int check_streams(int streams, const char* fn) {
+    if (streams < 1 || streams > DT_MAXS) { ph_set_error("%s: streams must be 1 .. %d, got %d", fn, DT_MAXS, streams); return PH_EINVAL; }
+    return PH_OK;
 }
 
-extern "C" int ph_dtracker_create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, ph_dtracker** out) {
+int create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, int streams, ph_dtracker** out,
+           const char* fn) {
     Geo g;
-    const int rc = resolve(cfg, capacity, max_dets, g, "ph_dtracker_create");
+    int rc = resolve(cfg, capacity, max_dets, g, fn);
+    if (!rc) rc = check_streams(streams, fn);
     if (rc) return rc;
-    PH_CHECK_ARG(out != nullptr, "null out");
+    if (!out) { ph_set_error("%s: null out", fn); return PH_EINVAL; }
     *out = nullptr;
-    PH_RUN(ph_check_buffers("ph_dtracker_create", nullptr, device_mem, device_bytes, g.lay.total_bytes));
+    PH_RUN(ph_check_buffers(fn, nullptr, device_mem, device_bytes, g.lay.total_bytes * (size_t)streams));
     ph_dtracker* t = new (std::nothrow) ph_dtracker;
-    if (!t) { ph_set_error("ph_dtracker_create: out of host memory"); return PH_EINVAL; }
+    if (!t) { ph_set_error("%s: out of host memory", fn); return PH_EINVAL; }
     t->c = *cfg;
     t->g = g;
+    t->streams = streams;
+    t->stride = g.lay.total_bytes;
     char* b = (char*)device_mem;
     const ph_dtracker_layout& l = g.lay;
     DState& s = t->st;
@@ -444,6 +516,59 @@ extern "C" int ph_dtracker_create(const ph_tracker_cfg* cfg, void* device_mem, s
     return PH_OK;
 }
 
+int check_io(const ph_dtracker_io* io, const char* fn) {
+    if (!(io->boxes && io->labels && io->counts && io->embeds)) { ph_set_error("%s: null boxes, labels, counts or embeds", fn); return PH_EINVAL; }
+    if (!(io->kept_out && io->ids_out && io->kept_counts)) { ph_set_error("%s: null kept_out, ids_out or kept_counts", fn); return PH_EINVAL; }
+    return PH_OK;
+}
+
+// one frame of each of S streams: the seven launches
+int launch_frames(const ph_dtracker* t, const DIo& io, int S, const int32_t* active, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const DState& st = t->st;
+    const ph_tracker_cfg& c = t->c;
+    const DBank bk{st, t->stride, active};
+    hipLaunchKernelGGL(k_dtrk_prepare, dim3(S), dim3(256), 0, s, bk, c, io);
+    hipLaunchKernelGGL(k_dtrk_gather, dim3(st.max_dets + st.capacity, S), dim3(TE), 0, s, bk, io);
+    ph_track_affinity_cnt(st.det, st.det_lab, st.memo, st.memo_lab, st.max_dets, st.capacity, st.rec, c.metric, c.with_cats, st.score, st.aff_ws, S,
+                          t->stride, active, stream);
+    hipLaunchKernelGGL(k_dtrk_assign, dim3(S), dim3(256), 0, s, bk, c, io);
+    hipLaunchKernelGGL(k_dtrk_update, dim3(st.max_dets, S), dim3(TE), 0, s, bk, c.one_minus_momentum, c.memo_momentum);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+int reset_streams(ph_dtracker* t, uint64_t mask, int64_t first_frame_id, void* stream) {
+    const DBank bk{t->st, t->stride, nullptr};
+    hipLaunchKernelGGL(k_dtrk_reset, dim3((t->st.capacity + 255) / 256, t->streams), dim3(256), 0, (hipStream_t)stream, bk,
+                       (unsigned long long)mask, first_frame_id);
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ph_dtracker_device_bytes(const ph_tracker_cfg* cfg, int capacity, int max_dets) {
+    Geo g;
+    if (resolve(cfg, capacity, max_dets, g, "ph_dtracker_device_bytes")) return 0;
+    return g.lay.total_bytes;
+}
+
+extern "C" size_t ph_dtracker_bank_bytes(const ph_tracker_cfg* cfg, int capacity, int max_dets, int streams) {
+    Geo g;
+    if (resolve(cfg, capacity, max_dets, g, "ph_dtracker_bank_bytes") || check_streams(streams, "ph_dtracker_bank_bytes")) return 0;
+    return g.lay.total_bytes * (size_t)streams;
+}
+
+extern "C" int ph_dtracker_create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, ph_dtracker** out) {
+    return create(cfg, device_mem, device_bytes, capacity, max_dets, 1, out, "ph_dtracker_create");
+}
+
+extern "C" int ph_dtracker_bank_create(const ph_tracker_cfg* cfg, void* device_mem, size_t device_bytes, int capacity, int max_dets, int streams,
+                                       ph_dtracker** out) {
+    return create(cfg, device_mem, device_bytes, capacity, max_dets, streams, out, "ph_dtracker_bank_create");
+}
+
 extern "C" void ph_dtracker_destroy(ph_dtracker* t) { delete t; }
 
 extern "C" int ph_dtracker_get_layout(const ph_dtracker* t, ph_dtracker_layout* out) {
@@ -452,34 +577,58 @@ extern "C" int ph_dtracker_get_layout(const ph_dtracker* t, ph_dtracker_layout* 
     return PH_OK;
 }
 
-PhDtrkScratch ph_dtracker_scratch(const ph_dtracker* t) { return PhDtrkScratch{t->st.io_kept, t->st.io_ids, t->st.io_kc, t->st.max_dets}; }
+extern "C" int ph_dtracker_get_streams(const ph_dtracker* t, int* streams_out, uint64_t* stride_bytes_out) {
+    PH_CHECK_ARG(t && streams_out && stride_bytes_out, "null tracker or out");
+    *streams_out = t->streams;
+    *stride_bytes_out = t->stride;
+    return PH_OK;
+}
+
+PhDtrkScratch ph_dtracker_scratch(const ph_dtracker* t) {
+    return PhDtrkScratch{t->st.io_kept, t->st.io_ids, t->st.io_kc, t->st.max_dets, t->streams, (int64_t)(t->stride / 4), (int64_t)(t->stride / 8),
+                         (int64_t)(t->stride / 4)};
+}
 
 extern "C" int ph_dtracker_reset(ph_dtracker* t, int64_t first_frame_id, void* stream) {
     PH_CHECK_ARG(t != nullptr, "null tracker");
-    hipLaunchKernelGGL(k_dtrk_reset, dim3((t->st.capacity + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->st, first_frame_id);
-    PH_CHECK_LAUNCH();
-    return PH_OK;
+    return reset_streams(t, ~0ull, first_frame_id, stream);
+}
+
+extern "C" int ph_dtracker_reset_streams(ph_dtracker* t, int64_t mask_bits, int64_t first_frame_id, void* stream) {
+    PH_CHECK_ARG(t != nullptr, "null tracker");
+    const uint64_t mask = (uint64_t)mask_bits;
+    PH_CHECK_ARG(t->streams == DT_MAXS || (mask >> t->streams) == 0, "the mask names a stream the tracker does not have");
+    return reset_streams(t, mask, first_frame_id, stream);
 }
 
 extern "C" int ph_dtracker_run(ph_dtracker* t, const ph_dtracker_io* io, int B, void* stream) {
     PH_CHECK_ARG(t && io, "null tracker or io");
+    PH_CHECK_ARG(t->streams == 1, "a tracker of several streams takes its frames side by side: ph_dtracker_step");
     PH_CHECK_ARG(B >= 1 && B <= 4096, "B must be 1 .. 4096 frames");
-    PH_CHECK_ARG(io->boxes && io->labels && io->counts && io->embeds, "null boxes, labels, counts or embeds");
-    PH_CHECK_ARG(io->kept_out && io->ids_out && io->kept_counts, "null kept_out, ids_out or kept_counts");
-    hipStream_t s = (hipStream_t)stream;
-    const DState& st = t->st;
-    const ph_tracker_cfg& c = t->c;
-    for (int b = 0; b < B; ++b) {
-        const DFrame f{io->boxes + b * io->box_stride, io->labels + b * io->label_stride, io->counts + b * io->count_stride,
-                       io->refuse ? io->refuse + b * io->refuse_stride : nullptr, io->embeds + b * io->embed_stride,
-                       io->kept_out + (int64_t)b * st.max_dets, io->ids_out + (int64_t)b * st.max_dets, io->kept_counts + b};
-        hipLaunchKernelGGL(k_dtrk_prepare, dim3(1), dim3(256), 0, s, st, c, f);
-        hipLaunchKernelGGL(k_dtrk_gather, dim3(st.max_dets + st.capacity), dim3(TE), 0, s, st, f.embeds);
-        ph_track_affinity_cnt(st.det, st.det_lab, st.memo, st.memo_lab, st.max_dets, st.capacity, st.rec, c.metric, c.with_cats, st.score, st.aff_ws,
-                              stream);
-        hipLaunchKernelGGL(k_dtrk_assign, dim3(1), dim3(256), 0, s, st, c, f);
-        hipLaunchKernelGGL(k_dtrk_update, dim3(st.max_dets), dim3(TE), 0, s, st, c.one_minus_momentum, c.memo_momentum);
-        PH_CHECK_LAUNCH();
+    PH_RUN(check_io(io, "ph_dtracker_run"));
+    const int N = t->st.max_dets;
+    for (int b = 0; b < B; ++b) {                        // in order through the one state: frame b is a step of the bank of one
+        DIo f{*io, 0, 0, 0, 0};
+        f.io.boxes += b * io->box_stride; f.io.labels += b * io->label_stride; f.io.counts += b * io->count_stride;
+        if (io->refuse) f.io.refuse += b * io->refuse_stride;
+        f.io.embeds += b * io->embed_stride;
+        f.io.kept_out += (int64_t)b * N; f.io.ids_out += (int64_t)b * N; f.io.kept_counts += b;
+        PH_RUN(launch_frames(t, f, 1, nullptr, stream));
     }
     return PH_OK;
+}
+
+extern "C" int ph_dtracker_step(ph_dtracker* t, const ph_dtracker_io* io, const int32_t* active, void* stream) {
+    PH_CHECK_ARG(t && io, "null tracker or io");
+    PH_RUN(check_io(io, "ph_dtracker_step"));
+    const int N = t->st.max_dets;
+    return launch_frames(t, DIo{*io, N, N, 1, 1}, t->streams, active, stream);
+}
+
+// ph_dtracker_step with the outputs in the streams' own io_* pieces (ph_dtracker_scratch), for ph_assoc_plan_track / _track_streams
+int ph_dtracker_step_scratch(ph_dtracker* t, const ph_dtracker_io* in, const int32_t* active, void* stream) {
+    const PhDtrkScratch sc = ph_dtracker_scratch(t);
+    DIo f{*in, sc.kept_stride, sc.ids_stride, sc.kc_stride, 0};
+    f.io.kept_out = sc.kept; f.io.ids_out = sc.ids; f.io.kept_counts = sc.kept_count;
+    return launch_frames(t, f, t->streams, active, stream);
 }

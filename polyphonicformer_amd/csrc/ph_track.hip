@@ -772,10 +772,22 @@ int ph_gn_relu_cl_cnt(const float* y, const float* gamma, const float* beta, int
 // the device tracker (ph_dtracker.hip) in one workgroup.
 // CNT: the device-count forms for the device tracker -- grids sized for (max_dets, capacity), (n, m, need) read from the frame record
 // `cnt` on the device, everything else (loop bounds, strides, reduction trees) the same code, so a score has the same bits.
+// The CNT forms carry a stream coordinate for a bank of trackers (ph_common.h ph_track_affinity_cnt): the grid's free dimension
+// (z for k_aff_dot, y for the other two) is the stream, whose pointers lie `sstride` bytes per stream behind stream 0's; a stream
+// whose `active` word is 0 returns before it reads anything of its own.
+template <class T>
+__device__ __forceinline__ T* aff_at(T* p, size_t bytes) { return (T*)((char*)p + bytes); }
+template <class T>
+__device__ __forceinline__ const T* aff_at(const T* p, size_t bytes) { return (const T*)((const char*)p + bytes); }
+
 template <bool CNT>
 __global__ __launch_bounds__(256) void k_aff_dot(const float* __restrict__ emb, const float* __restrict__ memo, int n, int m,
-                                                 const int32_t* __restrict__ cnt, int cosine, float* __restrict__ dot) {
+                                                 const int32_t* __restrict__ cnt, int cosine, float* __restrict__ dot, size_t sstride,
+                                                 const int32_t* __restrict__ active) {
     if constexpr (CNT) {
+        if (active && active[blockIdx.z] == 0) return;
+        const size_t o = blockIdx.z * sstride;
+        emb = aff_at(emb, o); memo = aff_at(memo, o); cnt = aff_at(cnt, o); dot = aff_at(dot, o);
         if (!cnt[2]) return;
         n = cnt[0]; m = cnt[1];
     }
@@ -799,8 +811,12 @@ __global__ __launch_bounds__(256) void k_aff_dot(const float* __restrict__ emb, 
 // per column j: max_i dot[i][j] and sum_i exp(dot[i][j] - max)
 template <bool CNT>
 __global__ __launch_bounds__(256) void k_aff_colstat(const float* __restrict__ dot, int n, int m, const int32_t* __restrict__ cnt,
-                                                     float* __restrict__ cmax, float* __restrict__ csum) {
+                                                     float* __restrict__ cmax, float* __restrict__ csum, size_t sstride,
+                                                     const int32_t* __restrict__ active) {
     if constexpr (CNT) {
+        if (active && active[blockIdx.y] == 0) return;
+        const size_t o = blockIdx.y * sstride;
+        dot = aff_at(dot, o); cnt = aff_at(cnt, o); cmax = aff_at(cmax, o); csum = aff_at(csum, o);
         if (!cnt[2]) return;
         n = cnt[0]; m = cnt[1];
     }
@@ -817,9 +833,14 @@ __global__ __launch_bounds__(256) void k_aff_colstat(const float* __restrict__ d
 template <bool CNT>
 __global__ __launch_bounds__(256) void k_aff_rows(const float* __restrict__ dot, const int* __restrict__ lab, const int* __restrict__ memo_lab,
                                                   const float* __restrict__ cmax, const float* __restrict__ csum, int n, int m,
-                                                  const int32_t* __restrict__ cnt, int metric, int with_cats, float* __restrict__ score) {
+                                                  const int32_t* __restrict__ cnt, int metric, int with_cats, float* __restrict__ score,
+                                                  size_t sstride, const int32_t* __restrict__ active) {
     __shared__ float red[256];
     if constexpr (CNT) {
+        if (active && active[blockIdx.y] == 0) return;          // uniform over the workgroup
+        const size_t o = blockIdx.y * sstride;
+        dot = aff_at(dot, o); lab = aff_at(lab, o); memo_lab = aff_at(memo_lab, o); cmax = aff_at(cmax, o); csum = aff_at(csum, o);
+        cnt = aff_at(cnt, o); score = aff_at(score, o);
         if (!cnt[2] || (int)blockIdx.x >= cnt[0]) return;       // uniform over the workgroup
         n = cnt[0]; m = cnt[1];
     }
@@ -863,22 +884,26 @@ extern "C" int ph_track_affinity(const float* emb, const int32_t* labels, const 
     float* cmax = dot + (size_t)n * m;
     float* csum = cmax + m;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_aff_dot<false>, dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, emb, memo_emb, n, m, nullptr, metric == 2 ? 1 : 0, dot);
-    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<false>, dim3((m + 255) / 256), dim3(256), 0, s, dot, n, m, nullptr, cmax, csum);
-    hipLaunchKernelGGL(k_aff_rows<false>, dim3(n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, n, m, nullptr, metric, with_cats, score);
+    hipLaunchKernelGGL(k_aff_dot<false>, dim3((m + 63) / 64, (n + 3) / 4), dim3(256), 0, s, emb, memo_emb, n, m, nullptr, metric == 2 ? 1 : 0, dot, (size_t)0, nullptr);
+    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<false>, dim3((m + 255) / 256), dim3(256), 0, s, dot, n, m, nullptr, cmax, csum, (size_t)0, nullptr);
+    hipLaunchKernelGGL(k_aff_rows<false>, dim3(n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, n, m, nullptr, metric, with_cats, score, (size_t)0, nullptr);
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
 
 // the device-count form (ph_common.h): the caller checked the sizes; the workspace is laid out for (max_n, max_m) as above with the
-// frame's own m as the row stride of dot / score
+// frame's own m as the row stride of dot / score; `streams` of them stride_bytes apart
 void ph_track_affinity_cnt(const float* emb, const int32_t* labels, const float* memo_emb, const int32_t* memo_labels, int max_n, int max_m,
-                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, void* stream) {
+                           const int32_t* cnt, int metric, int with_cats, float* score, void* workspace, int streams, size_t stride_bytes,
+                           const int32_t* active, void* stream) {
     float* dot = (float*)workspace;
     float* cmax = dot + (size_t)max_n * max_m;
     float* csum = cmax + max_m;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_aff_dot<true>, dim3((max_m + 63) / 64, (max_n + 3) / 4), dim3(256), 0, s, emb, memo_emb, 0, 0, cnt, metric == 2 ? 1 : 0, dot);
-    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<true>, dim3((max_m + 255) / 256), dim3(256), 0, s, dot, 0, 0, cnt, cmax, csum);
-    hipLaunchKernelGGL(k_aff_rows<true>, dim3(max_n), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, 0, 0, cnt, metric, with_cats, score);
+    hipLaunchKernelGGL(k_aff_dot<true>, dim3((max_m + 63) / 64, (max_n + 3) / 4, streams), dim3(256), 0, s, emb, memo_emb, 0, 0, cnt, metric == 2 ? 1 : 0,
+                       dot, stride_bytes, active);
+    if (metric == 0) hipLaunchKernelGGL(k_aff_colstat<true>, dim3((max_m + 255) / 256, streams), dim3(256), 0, s, dot, 0, 0, cnt, cmax, csum, stride_bytes,
+                                        active);
+    hipLaunchKernelGGL(k_aff_rows<true>, dim3(max_n, streams), dim3(256), 0, s, dot, labels, memo_labels, cmax, csum, 0, 0, cnt, metric, with_cats, score,
+                       stride_bytes, active);
 }

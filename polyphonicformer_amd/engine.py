@@ -1587,3 +1587,14 @@ class NativeAssocPlan(_OwnsHandles):
         _lib.check(_lib.load().ph_assoc_plan_track(self._h, dtracker._h, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
                                                    _lib.ptr(self.track_map), _lib.ptr(self.ids_dev), _lib.stream_ptr()), "ph_assoc_plan_track")
         return self.track_map, self.ids_dev
+
+    def track_streams(self, bank, pan, active=None):
+        """`track` with frame b going to stream b of a tracker.NativeDeviceTrackerBank of B streams (ph_assoc_plan_track_streams): one
+        tracker step for the B frames.  `active`: int32 [B] on the device or None; a zero word is an idle stream -- its tracker is
+        untouched and its track map all zero.  Launches only, capturable; same returns as `track`"""
+        active = bank._active(active)
+        self._keep_active = active
+        _lib.check(_lib.load().ph_assoc_plan_track_streams(self._h, bank._h, _lib.ptr(pan), _lib.ptr(self.things), _lib.ptr(self.embeds),
+                                                           None if active is None else _lib.ptr(active), _lib.ptr(self.track_map),
+                                                           _lib.ptr(self.ids_dev), _lib.stream_ptr()), "ph_assoc_plan_track_streams")
+        return self.track_map, self.ids_dev

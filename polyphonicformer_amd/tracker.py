@@ -7,7 +7,8 @@ The tracker is *host logic*: stateful, strictly sequential in frame order, data-
 kwargs, the `match(bboxes, labels, track_feats, frame_id)` signature / return value and the registry name are the
 reference's, and the integer ids are pinned to the reference class's own output (tests/golden/tracker.npz).  With the
 embeddings on a GPU the same class hands each frame to `NativeHostTracker` (csrc/ph_tracker.hip: bookkeeping in C++, the
-memory in a device pool); `NativeDeviceTracker` (csrc/ph_dtracker.hip) keeps the bookkeeping on the device too.
+memory in a device pool); `NativeDeviceTracker` (csrc/ph_dtracker.hip) keeps the bookkeeping on the device too, and
+`NativeDeviceTrackerBank` is S of those in one buffer, one frame of each per launch sequence (live cameras).
 With frames sharded over GPUs (`dist.shard_frames`) every rank all-gathers the per-frame records
 (`dist.allgather_track_records`) and replays `match` in frame order; integer track ids are then identical to the
 single-process run (`replay_tracking`, tests/test_tracker.py and tests/test_dist_gloo.py)."""
@@ -471,11 +472,16 @@ class NativeDeviceTracker(_OwnsHandles):
         """B frames in order: boxes fp32 [B, n, 5], labels int32 [B, n], counts int32 [B], embeds fp32 [B, n, 256], refuse int32 [B] or
         None, contiguous on the device -> (kept int32 [B, max_dets], ids int64 [B, max_dets], kept_counts int32 [B]) on the device
         (`out`: the same three, to write into); launches only"""
+        return self._launch(boxes, labels, counts, embeds, refuse, out, "run")
+
+    def _launch(self, boxes, labels, counts, embeds, refuse, out, how, active=None):
         B, dev = counts.shape[0], self.device
+        if how == "step" and B != self.streams:
+            raise _lib.PolyheadError(f"NativeDeviceTrackerBank.step: {self.streams} streams, tables of {B}")
         for t, dt, nm in ((boxes, torch.float32, "boxes"), (labels, torch.int32, "labels"), (counts, torch.int32, "counts"),
                           (embeds, torch.float32, "embeds")) + (((refuse, torch.int32, "refuse"),) if refuse is not None else ()):
             if t.dtype != dt or not t.is_contiguous() or t.device != dev or t.shape[0] != B:
-                raise _lib.PolyheadError(f"NativeDeviceTracker.run: {nm} must be {dt} contiguous [{B}, ...] on {dev}")
+                raise _lib.PolyheadError(f"{type(self).__name__}.{how}: {nm} must be {dt} contiguous [{B}, ...] on {dev}")
         if out is None:
             out = (torch.empty((B, self.max_dets), dtype=torch.int32, device=dev), torch.empty((B, self.max_dets), dtype=torch.int64, device=dev),
                    torch.empty((B,), dtype=torch.int32, device=dev))
@@ -486,30 +492,100 @@ class NativeDeviceTracker(_OwnsHandles):
         io.refuse, io.refuse_stride = (None, 0) if refuse is None else (refuse.data_ptr(), 1)
         io.embeds, io.embed_stride = embeds.data_ptr(), embeds[0].numel()
         io.kept_out, io.ids_out, io.kept_counts = (o.data_ptr() for o in out)
-        self._keep = (boxes, labels, counts, embeds, refuse, out)      # alive until the launches have run (static under graph capture)
-        _lib.check(_lib.load().ph_dtracker_run(self._h, C.byref(io), B, _lib.stream_ptr()), "ph_dtracker_run")
+        self._keep = (boxes, labels, counts, embeds, refuse, out, active)      # alive until the launches have run (static under graph capture)
+        if how == "step":
+            _lib.check(_lib.load().ph_dtracker_step(self._h, C.byref(io), None if active is None else _lib.ptr(active), _lib.stream_ptr()),
+                       "ph_dtracker_step")
+        else:
+            _lib.check(_lib.load().ph_dtracker_run(self._h, C.byref(io), B, _lib.stream_ptr()), "ph_dtracker_run")
         return out
 
-    def _piece(self, offset, dtype, shape):
+    def _piece(self, offset, dtype, shape, s=0):
+        """a piece of stream s's block (`layout` is stream 0's; a bank's blocks are `layout.total_bytes` apart)"""
         n = int(torch.tensor([], dtype=dtype).element_size()) * int(math.prod(shape))
-        return self.mem[int(offset):int(offset) + n].view(dtype).reshape(shape)
+        at = int(s) * int(self.layout.total_bytes) + int(offset)
+        return self.mem[at:at + n].view(dtype).reshape(shape)
 
-    def status(self):
-        """the status record as a dict of ints (_lib.DTRK_STATUS); synchronises"""
-        return dict(zip(_lib.DTRK_STATUS, self._piece(self.layout.status, torch.int64, (_lib.PH_DTRK_ST_WORDS,)).cpu().tolist()))
+    def status(self, s=0):
+        """the status record (of stream s of a bank) as a dict of ints (_lib.DTRK_STATUS); synchronises"""
+        return dict(zip(_lib.DTRK_STATUS, self._piece(self.layout.status, torch.int64, (_lib.PH_DTRK_ST_WORDS,), s).cpu().tolist()))
 
-    def tables(self):
+    def tables(self, s=0):
         """the live tracklet rows in creation order (ids, labels, seen, boxes, slots, and `pool`: their embedding rows) plus the
-        backdrop generations, newest first, as host tensors; synchronises.  For tests and checkpointing"""
+        backdrop generations, newest first, as host tensors (of stream s of a bank); synchronises.  For tests and checkpointing"""
         l, Cn, N, G = self.layout, self.capacity, self.max_dets, self.layout.generations
-        rows = self.status()["rows"]
-        tr = dict(ids=self._piece(l.trk_id, torch.int64, (Cn,))[:rows].cpu(), labels=self._piece(l.trk_label, torch.int32, (Cn,))[:rows].cpu(),
-                  seen=self._piece(l.trk_seen, torch.int64, (Cn,))[:rows].cpu(), boxes=self._piece(l.trk_box, torch.float32, (Cn, 5))[:rows].cpu(),
-                  slots=self._piece(l.trk_slot, torch.int32, (Cn,))[:rows].cpu())
-        pool = self._piece(l.pool, torch.float32, (Cn, 256))
+        rows = self.status(s)["rows"]
+        P = lambda off, dt, shape: self._piece(off, dt, shape, s)
+        tr = dict(ids=P(l.trk_id, torch.int64, (Cn,))[:rows].cpu(), labels=P(l.trk_label, torch.int32, (Cn,))[:rows].cpu(),
+                  seen=P(l.trk_seen, torch.int64, (Cn,))[:rows].cpu(), boxes=P(l.trk_box, torch.float32, (Cn, 5))[:rows].cpu(),
+                  slots=P(l.trk_slot, torch.int32, (Cn,))[:rows].cpu())
+        pool = P(l.pool, torch.float32, (Cn, 256))
         tr["pool"] = pool[tr["slots"].long().to(self.device)].cpu()
-        counts = self._piece(l.bd_count, torch.int32, (G,)).cpu().tolist()
-        lab, slot, box = (self._piece(l.bd_label, torch.int32, (G, N)).cpu(), self._piece(l.bd_slot, torch.int32, (G, N)).cpu(),
-                          self._piece(l.bd_box, torch.float32, (G, N, 5)).cpu())
+        counts = P(l.bd_count, torch.int32, (G,)).cpu().tolist()
+        lab, slot, box = (P(l.bd_label, torch.int32, (G, N)).cpu(), P(l.bd_slot, torch.int32, (G, N)).cpu(),
+                          P(l.bd_box, torch.float32, (G, N, 5)).cpu())
         tr["backdrops"] = [dict(labels=lab[g, :c], slots=slot[g, :c], boxes=box[g, :c]) for g, c in enumerate(counts)]
         return tr
+
+
+class NativeDeviceTrackerBank(NativeDeviceTracker):
+    """`streams` (1 .. 64) device trackers in ONE buffer, advanced by one frame each in one launch sequence (ph_dtracker_bank_* /
+    ph_dtracker_step, csrc/ph_dtracker.hip): the trackers of S live cameras whose current frames share a launch.  Stream s's block lies
+    at s * `layout.total_bytes` of `mem`; `status(s)` and `tables(s)` are NativeDeviceTracker's, per stream.  `reset` and `step` are
+    launches only on the current stream (capturable)."""
+
+    def __init__(self, cfg, device, streams, capacity=4096, max_dets=128, first_frame_id=1):
+        lib, dev = _lib.load(), torch.device(device)
+        self.cfg, self.device, self.capacity, self.max_dets = _lib.TrackerCfg.from_buffer_copy(bytes(cfg)), dev, capacity, max_dets
+        self.streams = int(streams)
+        nbytes = lib.ph_dtracker_bank_bytes(C.byref(self.cfg), capacity, max_dets, self.streams)
+        if nbytes == 0:
+            raise _cfg_error("ph_dtracker_bank_bytes")
+        self.mem = torch.empty((nbytes,), dtype=torch.uint8, device=dev)             # zeroing contract: none (`reset` below)
+        self._h = C.c_void_p()
+        _lib.check(lib.ph_dtracker_bank_create(C.byref(self.cfg), _lib.ptr(self.mem), nbytes, capacity, max_dets, self.streams, C.byref(self._h)),
+                   "ph_dtracker_bank_create")
+        self.layout = _lib.DtrackerLayout()
+        _lib.check(lib.ph_dtracker_get_layout(self._h, C.byref(self.layout)), "ph_dtracker_get_layout")
+        n, stride = C.c_int(), C.c_uint64()
+        _lib.check(lib.ph_dtracker_get_streams(self._h, C.byref(n), C.byref(stride)), "ph_dtracker_get_streams")
+        assert (n.value, stride.value) == (self.streams, self.layout.total_bytes)
+        self.io = _lib.DtrackerIO()
+        self._keep = None
+        self.reset(None, first_frame_id)
+
+    def block(self, s):
+        """stream s's whole block (state and scratch) as a uint8 view of `mem`"""
+        return self._piece(0, torch.uint8, (int(self.layout.total_bytes),), s)
+
+    def reset(self, streams=None, first_frame_id=1):
+        """one launch: the named streams (an iterable of indices; None: all) start a new sequence, the others are untouched"""
+        mask = 0
+        for s in (range(self.streams) if streams is None else streams):
+            if not 0 <= int(s) < self.streams:
+                raise _lib.PolyheadError(f"NativeDeviceTrackerBank.reset: stream {s} of {self.streams}")
+            mask |= 1 << int(s)
+        mask -= (mask >> 63) << 64                               # the 64 bits as the ABI's int64
+        _lib.check(_lib.load().ph_dtracker_reset_streams(self._h, mask, int(first_frame_id), _lib.stream_ptr()), "ph_dtracker_reset_streams")
+
+    def _active(self, active):
+        """`active` as the int32 [streams] device words ph_dtracker_step reads (None stays None: every stream has a frame)"""
+        if active is None:
+            return None
+        if not torch.is_tensor(active):
+            active = torch.tensor([1 if a else 0 for a in active], dtype=torch.int32)
+            if self.device.type == "cuda":
+                active = active.pin_memory().to(self.device, non_blocking=True)
+        if active.dtype != torch.int32 or tuple(active.shape) != (self.streams,) or not active.is_contiguous() or active.device != self.device:
+            raise _lib.PolyheadError(f"NativeDeviceTrackerBank: active must be int32 contiguous [{self.streams}] on {self.device}")
+        return active
+
+    def step(self, boxes, labels, counts, embeds, refuse=None, active=None, out=None):
+        """one frame of every stream: `NativeDeviceTracker.run`'s tables with the leading dimension indexing STREAMS ([S, n, 5] ..),
+        `active`: int32 [S] on the device (or a host sequence) or None -- a zero word's stream has no frame in this step and keeps every
+        bit of its state; its kept_counts entry is 0.  Returns (kept [S, max_dets], ids [S, max_dets], kept_counts [S]); launches only"""
+        active = self._active(active)
+        return self._launch(boxes, labels, counts, embeds, refuse, out, "step", active)
+
+    def run(self, *a, **kw):
+        raise _lib.PolyheadError("NativeDeviceTrackerBank.run: a bank's frames are side by side, not in order: step()")

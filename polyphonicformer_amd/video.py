@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, engine as E
-from .tracker import (TRACKERS, NativeDeviceTracker, QuasiDenseEmbedTracker, bbox_overlaps, native_tracker_cfg,  # noqa: F401
+from .tracker import (TRACKERS, NativeDeviceTracker, NativeDeviceTrackerBank, QuasiDenseEmbedTracker, bbox_overlaps, native_tracker_cfg,  # noqa: F401
                       painted_ids, replay_tracking)
 
 
@@ -65,18 +65,27 @@ class VideoAssociator:
         self._nplans = {}                    # geometry -> NativeAssocPlan, one at a time
         self.init_tracker()
 
-    native_plan, max_things, device_tracker = False, 100, False          # `use_native_plan`
+    native_plan, max_things, device_tracker, streams = False, 100, False, None          # `use_native_plan`
     DEVICE_CAPACITY, DEVICE_MAX_DETS = QuasiDenseEmbedTracker.NATIVE_CAPACITY, QuasiDenseEmbedTracker.NATIVE_MAX_DETS
 
-    def use_native_plan(self, on=True, max_things=None, device_tracker=False):
+    def use_native_plan(self, on=True, max_things=None, device_tracker=False, streams=None):
         """`step_records` for clips whose merge left its records on the device (`panoptic.BatchMerge`): the whole step as the native
         association plan (csrc/ph_assocplan.hip) -- one launch-only call and one synchronising tracker call for B frames, no
         `segments_info` on the host.  Off (the default) nothing changes: `step` / `step_device` are the Python chain.
         `max_things`: RoIs per frame the plan's launches are sized for (a frame with more is an error), at most the merge's K.
         `device_tracker=True`: the tracker's state lives on the device too (csrc/ph_dtracker.hip) and `step_records` is launches only
         -- no synchronisation, `self.cnt` is not touched, `frames_matched()` reads the status record; a frame with more than
-        `max_things` things is then a refused frame in that record (`device_status()`), not an exception."""
+        `max_things` things is then a refused frame in that record (`device_status()`), not an exception.
+        `streams=S` (with `device_tracker=True`): the B == S frames of a `step_records` call are the CURRENT frames of S independent
+        video streams (live cameras), frame b stream b's, tracked by one tracker.NativeDeviceTrackerBank in one tracker step;
+        `init_tracker`, `frames_matched` and `device_status` then take streams.  Without `streams` nothing changes."""
+        if streams is not None:
+            if not (on and device_tracker):
+                raise _lib.PolyheadError("VideoAssociator.use_native_plan: streams needs the native plan with device_tracker=True")
+            if not 1 <= int(streams) <= 64:
+                raise _lib.PolyheadError(f"VideoAssociator.use_native_plan: streams must be 1 .. 64, got {streams}")
         self.native_plan, self.device_tracker = bool(on), bool(on and device_tracker)
+        self.streams = None if streams is None else int(streams)
         self._dtracker = None
         if max_things is not None:
             self.max_things = int(max_things)
@@ -102,16 +111,24 @@ class VideoAssociator:
             plan = self._nplans[key] = E.NativeAssocPlan(pk[1], cfg, dev)
         return plan
 
-    def step_records(self, levels, pan_dev, seg_records_dev):
+    def step_records(self, levels, pan_dev, seg_records_dev, active=None):
         """`step_device` for B frames from the merge's DEVICE outputs: levels fp32 [B, 256, H_l, W_l], pan_dev int32 [B, Ho, Wo],
         seg_records_dev int32 [B, 1 + 5 K] (`ph_panoptic_merge`'s records).  Returns the (sem uint8, track float64) maps [B, Ho, Wo] on
         the device (the plan's static outputs: the next call overwrites them).  Reads no `segments_info`; one synchronisation for the
-        tracker's boxes and labels, then the tracker's own."""
+        tracker's boxes and labels, then the tracker's own.
+        `use_native_plan(streams=S)`: B == S, frame b is stream b's next frame; `active` (int32 [S] on the device, a host sequence or
+        None): a zero word is a stream without a frame in this step -- its tracker is untouched, its track map all zero."""
         if not self.native_plan:
             raise _lib.PolyheadError("VideoAssociator.step_records needs use_native_plan(True)")
+        if self.streams is None and active is not None:
+            raise _lib.PolyheadError("VideoAssociator.step_records: active needs use_native_plan(streams=...)")
+        if self.streams is not None and pan_dev.shape[0] != self.streams:
+            raise _lib.PolyheadError(f"VideoAssociator.step_records: {self.streams} streams, {pan_dev.shape[0]} frames")
         K = (seg_records_dev.shape[1] - 1) // 5
         plan = self._native_plan_for(levels, pan_dev, K)
         plan.run(pan_dev, seg_records_dev, levels)
+        if self.streams is not None:
+            return plan.sem, plan.track_streams(self._device_tracker_for(pan_dev.device), pan_dev, active)[0]
         if self.device_tracker:
             return plan.sem, plan.track(self._device_tracker_for(pan_dev.device), pan_dev)[0]
         trk, _, matched = plan.match(self.tracker.native_tracker(pan_dev.device), pan_dev, self.cnt)
@@ -120,22 +137,46 @@ class VideoAssociator:
 
     def _device_tracker_for(self, dev):
         if self._dtracker is None:
-            self._dtracker = NativeDeviceTracker(native_tracker_cfg(**self.tracker_cfg), dev, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
+            cfg = native_tracker_cfg(**self.tracker_cfg)
+            if self.streams is not None:
+                self._dtracker = NativeDeviceTrackerBank(cfg, dev, self.streams, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
+            else:
+                self._dtracker = NativeDeviceTracker(cfg, dev, self.DEVICE_CAPACITY, self.DEVICE_MAX_DETS)
         return self._dtracker
 
-    def device_status(self):
-        """the device tracker's status record (tracker.NativeDeviceTracker.status; synchronises); None before its first frame"""
-        return None if self._dtracker is None else self._dtracker.status()
+    def _stream_index(self, stream, what):
+        if self.streams is None:
+            if stream not in (None, 0):
+                raise _lib.PolyheadError(f"VideoAssociator.{what}: stream {stream} without use_native_plan(streams=...)")
+            return 0
+        if stream is None or not 0 <= int(stream) < self.streams:
+            raise _lib.PolyheadError(f"VideoAssociator.{what}: name one of the {self.streams} streams, got {stream}")
+        return int(stream)
 
-    def frames_matched(self):
-        """frames the tracker has matched since `init_tracker`; with the device tracker a synchronising read of its status record"""
+    def device_status(self, stream=None):
+        """the device tracker's status record (tracker.NativeDeviceTracker.status; synchronises); None before its first frame.
+        With `use_native_plan(streams=S)`: of stream `stream`"""
+        s = self._stream_index(stream, "device_status")
+        return None if self._dtracker is None else self._dtracker.status(s)
+
+    def frames_matched(self, stream=None):
+        """frames the tracker has matched since `init_tracker`; with the device tracker a synchronising read of its status record
+        (of stream `stream` with `use_native_plan(streams=S)`)"""
         if self.device_tracker:
-            st = self.device_status()
+            st = self.device_status(stream)
             return 0 if st is None else st["matched"]
         return self.cnt - 1
 
-    def init_tracker(self):
-        """polyphonic_former_video.py:59-61"""
+    def init_tracker(self, streams=None):
+        """polyphonic_former_video.py:59-61.  With `use_native_plan(streams=S)`: `streams` names the streams that start a new video
+        (an iterable of indices; None: all); the others go on"""
+        if self.streams is None and streams is not None:
+            raise _lib.PolyheadError("VideoAssociator.init_tracker: streams without use_native_plan(streams=...)")
+        if self.streams is not None:
+            streams = list(range(self.streams)) if streams is None else [self._stream_index(s, "init_tracker") for s in streams]
+            if self._dtracker is not None:
+                self._dtracker.reset(streams, 1)
+            return
         cfg = dict(self.tracker_cfg)
         cfg.setdefault("type", "QuasiDenseEmbedTracker")         # the config's own dict (with `type`) or bare kwargs
         self.tracker = TRACKERS.build(cfg)                       # build_tracker(self.tracker_cfg), polyphonic_former_video.py:60
@@ -780,3 +821,81 @@ class VideoStreamRunner:
     def flush_record(self):
         self._enter("records")
         return self.records_end()[0] if self._clips else None
+
+
+class MultiStreamRunner:
+    """S live video streams (cameras) of equally sized frames on one GPU: the frames that share a launch are the CURRENT frames of the
+    S streams, frame s stream s's -- the next frame of a live stream does not exist yet, so `VideoStreamRunner`'s several frames per
+    launch of ONE stream are out of reach there.  One `step`:
+
+      * neck -> KernelHead -> decode -> x2 upsample of depth_pred for the S frames through the pipeline's own heads (frame invariant:
+        a frame's bits do not depend on the frames that share its launch, `VideoStreamRunner.clip_batch`);
+      * ONE `panoptic.BatchMerge.run` (accept step on the device);
+      * ONE `VideoAssociator.step_records` in its `streams=S` form: the native association plan and one step of a
+        tracker.NativeDeviceTrackerBank -- S independent tracker states, seven launches for all of them;
+      * the downloads of what `PolyphonicVideo.simple_test` returns per frame, and ONE synchronisation, at the end.
+
+    The results are those of S `VideoStreamRunner(pipe, meta, graph=False).run_one` loops, one per stream (tests/
+    test_gpu_multistream.py).  The runner has its own VideoAssociator; the pipeline's is not touched.  Eager launches: graph replay of
+    the heads and a one-step-deep download pipeline (results one step late, the copies under the next step) are follow-ups."""
+
+    def __init__(self, pipe, img_meta, streams, max_things=None):
+        if not 1 <= int(streams) <= 64:
+            raise _lib.PolyheadError(f"MultiStreamRunner: streams must be 1 .. 64, got {streams}")
+        for h in (pipe.rpn_head, pipe.roi_head):
+            if not getattr(h, "frame_invariant", False):
+                raise _lib.PolyheadError("MultiStreamRunner needs frame-invariant heads: a stream's results must not depend on the others'")
+        self.pipe, self.meta, self.streams = pipe, dict(img_meta), int(streams)
+        a = pipe.assoc
+        self.assoc = VideoAssociator(a.track_head, a.tracker_cfg, a.num_thing_classes, a.num_stuff_classes, a.strides)
+        self.assoc.use_native_plan(True, max_things=a.max_things if max_things is None else max_things, device_tracker=True, streams=self.streams)
+        self._merge = None                   # (key, panoptic.BatchMerge)
+
+    def init_tracker(self, stream=None):
+        """`stream` (an index; None: every stream) starts a new video: its track ids start again, the others go on"""
+        self.assoc.init_tracker(None if stream is None else [stream])
+
+    def device_status(self, stream):
+        """stream `stream`'s tracker status record (synchronises); a frame with more than `max_things` things is that stream's refused
+        frame there, as in the single-stream form"""
+        return self.assoc.device_status(stream)
+
+    def frames_matched(self, stream):
+        return self.assoc.frames_matched(stream)
+
+    def _batch_merge(self, cls, mask_up):
+        from . import panoptic as Pn
+        B, N, L = cls.shape
+        h2, w2 = mask_up.shape[-2:]
+        key = (B, N, L, h2, w2, mask_up.dtype, str(mask_up.device))
+        if self._merge is None or self._merge[0] != key:
+            self._merge = (key, Pn.BatchMerge(self.pipe.roi_head, B, N, L, h2, w2, mask_up.dtype, self.meta, mask_up.device))
+        return self._merge[1]
+
+    def step(self, x, active=None):
+        """x: the FPN levels of the S streams' current frames, [S, 256, H_l, W_l] per level on the device; `active`: a host sequence
+        of S flags (None: every stream has a frame) -- an idle stream's slot of `x` may hold anything, its tracker is untouched.
+        Returns per stream the result list [{"sem" uint8, "track" float64, "depth" fp32}] (numpy, owned by the caller) of
+        `PolyphonicVideo.simple_test`, or None for an idle stream.  One synchronisation, at the end."""
+        S = self.streams
+        if any(t.shape[0] != S for t in x):
+            raise _lib.PolyheadError(f"MultiStreamRunner.step: {S} streams, levels of {[int(t.shape[0]) for t in x]} frames")
+        if active is not None and len(active) != S:
+            raise _lib.PolyheadError(f"MultiStreamRunner.step: {S} streams, {len(active)} active flags")
+        pipe = self.pipe
+        (proposal_feats, x_feats, mask_preds, cls_scores, seg_preds, depth_feats, depth_proposal, depth_pred,
+         semantic_aspp_out) = pipe.rpn_head.simple_test_rpn(x, [self.meta] * S)
+        o = pipe.roi_head._decode(x_feats, proposal_feats, mask_preds, depth_feats, depth_proposal)
+        depth_init = E.upsample2x(depth_pred.float().contiguous())                         # kernel_update.py:302-307
+        bm = self._batch_merge(o["cls"], o["mask_up"])
+        bm.run(o["cls"], o["mask_up"], o["depth_up"], depth_init)
+        levels = [t.float().contiguous() for t in x[:4]]
+        sem, trk = self.assoc.step_records(levels, bm.pan, bm.records, active=None if active is None else [bool(a) for a in active])
+        host = []
+        for t in (sem, trk, bm.d_final):
+            h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            h.copy_(t, non_blocking=True)
+            host.append(h.numpy())
+        torch.cuda.current_stream().synchronize()
+        return [None if active is not None and not active[s] else [{"sem": host[0][s], "track": host[1][s], "depth": host[2][s]}]
+                for s in range(S)]
