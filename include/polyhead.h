@@ -1524,6 +1524,67 @@ int ph_gt_prepare(const uint8_t* seg, const int32_t* row_of, const int32_t* nseg
                   int Wp, int aH, int aW, int Gmax, int Smax, int mode, float* things, float* stuff, float* things_hard,
                   float* stuff_hard, float* valid, float* depth_out, void* stream);
 
+/* ---- the segment-index maps themselves from the dataset's panoptic id maps (csrc/ph_gtseg.hip).  In the file a frame's ground truth
+ * is one raw id per pixel, class * raw_divisor + instance, and it stays one id per pixel through every transform of the shipped
+ * train_pipeline (nearest resize, flip, crop, pad: separable nearest gathers).  The two calls replace the loader's numpy work in front
+ * of ph_gt_prepare: to_coco (datasets/cityscapes_dvps.py:89-109), np.unique and a full-frame compare per segment
+ * (datasets/pipelines/loading.py:201-220), bitmasks2bboxes (:11-21), and the resize / flip / crop / pad of the [G][H][W] stack and of
+ * the depth map (datasets/pipelines/transforms.py).  The loader keeps the id map and the augmentation's parameters.
+ *
+ * Shared arguments:
+ *   raw        DEVICE [frames][Hs][Ws], int32 (PH_GTSEG_I32) or uint16 (PH_GTSEG_U16), the ids as the file holds them; fewer than
+ *              2^31 pixels a frame
+ *   class_map  HOST int32 [n_map], raw class -> training class 0 .. 255; -1: not a class of this dataset; the no-object class maps
+ *              to no_obj_class.  Two raw classes must not map to one training class other than no_obj_class (PH_EINVAL: their segments
+ *              would share ids).  It travels as a kernel argument; n_map <= 256.
+ *   raw_divisor, divisor   1 <= raw_divisor <= divisor <= 2^23.  mapped id = class_map[raw / raw_divisor] * divisor + raw % raw_divisor
+ *              (to_coco; a pixel whose mapped class is no_obj_class belongs to no segment, whatever its instance part)
+ * THE LIMIT: n_map * raw_divisor <= PH_GTSEG_MAX_KEYS (262144 raw ids: a presence bitmap of 32 KB, one workgroup's LDS), beyond it
+ * PH_EUNSUPPORTED before any launch.  Cityscapes-DVPS has 33 * 1000.
+ *
+ * ph_gt_segments: one segment table per frame, what loading.py:201-220 and bitmasks2bboxes leave at file resolution.
+ *   tables     DEVICE int32 [frames][PH_GTSEG_TABLE_WORDS]: word 0 the count n of segments (no-object excluded), then
+ *              PH_GTPREP_MAX_SEGMENTS rows of (mapped id, xmin, ymin, xmax, ymax, area), ascending by mapped id -- np.unique's order --
+ *              boxes inclusive in pixels, rows from n on zero
+ *   status     DEVICE int32 [frames]: 0, or an OR of PH_GTSEG_ETOOMANY (more than 254 segments), PH_GTSEG_EUNMAPPED (an id whose
+ *              class maps to -1), PH_GTSEG_EOUTSIDE (an id below 0 or at or above n_map * raw_divisor).  A stuff id with a non-zero
+ *              instance part is no error (the reference only asserts it).  Always written.  A frame with a non-zero status keeps
+ *              its table as the caller left it; the other frames of the call are not affected.
+ *   workspace  DEVICE, 256-byte aligned, ph_gt_segments_workspace_bytes: per frame the presence bitmap, the keys present and their rows
+ * Four launches, nothing else: no allocation, no synchronisation, no host read, no memset node, capturable.  ZEROING CONTRACT: none --
+ * the first launch clears what the others accumulate into, and every word of the table of a frame with status 0 is written.  Integer
+ * atomics only (or, min, max, add): the order and every number are exact, two calls give the same bits, a frame's outputs do not
+ * depend on the other frames of the call.
+ *
+ * ph_gt_index_maps: the raw maps through the augmentation, a pure gather; it takes no position on any resize rule.
+ *   kept_id    DEVICE int32 [frames][256]: the mapped ids of the segments the crop kept, ascending; a pixel's output is its
+ *              segment's index in this list (the index in the loader's list).  kept_n HOST int32 [frames]: 0 .. 254 entries
+ *   src_y, src_x   DEVICE int32 [frames][Hc] and [frames][Wc]: the file row / column of every output row / column; -1: none (the
+ *              pixel has no segment and depth 0 -- a frame smaller than the call's Hc x Wc).  src_y_host, src_x_host: the same words
+ *              on the HOST, bounds-checked before anything is launched (PH_EINVAL); the caller keeps the two copies equal, and an
+ *              index the kernels find outside the file reads as -1
+ *   raw_depth  DEVICE uint16 [frames][Hs][Ws] or NULL (then depth is NULL too); depth_div (256), depth_max (80); scale_mean HOST fp32
+ *              [frames], the mean of the frame's resize factors
+ *   seg        uint8 [frames][Hc][Wc], any alignment: the index in kept_id, 255 where the mapped id is not in it (dropped, no-object,
+ *              unmapped, outside).  One 16-byte store per 16 pixels where Wc is a multiple of 16 and seg 16-byte aligned, bytes otherwise
+ *   depth      fp32 [frames][Hp][Wp], Hp >= Hc, Wp >= Wc: min(float(u) / depth_div, depth_max) / scale_mean in fp32 with IEEE
+ *              divisions (numpy's bits), zero outside Hc x Wc
+ * Two launches (one without depth): no allocation, no synchronisation, no atomics, no workspace, capturable.  ZEROING CONTRACT:
+ * none -- every word of both outputs is written, the pad included.  Two calls give the same bits; a frame's outputs do not depend on
+ * the other frames.  The output is what ph_gt_prepare takes as seg (Hs, Ws there = Hc, Wc here) and depth. */
+#define PH_GTSEG_MAX_KEYS 262144
+#define PH_GTSEG_ROW_WORDS 6
+#define PH_GTSEG_TABLE_WORDS (1 + PH_GTPREP_MAX_SEGMENTS * PH_GTSEG_ROW_WORDS)
+enum { PH_GTSEG_I32 = 0, PH_GTSEG_U16 = 1 };
+enum { PH_GTSEG_ETOOMANY = 1, PH_GTSEG_EUNMAPPED = 2, PH_GTSEG_EOUTSIDE = 4 };
+size_t ph_gt_segments_workspace_bytes(int frames, int n_map, int raw_divisor);   /* 0 on a bad argument (ph_last_error_string) */
+int ph_gt_segments(const void* raw, int dtype, int frames, int Hs, int Ws, const int32_t* class_map, int n_map, int raw_divisor,
+                   int divisor, int no_obj_class, int32_t* tables, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int ph_gt_index_maps(const void* raw, int dtype, const uint16_t* raw_depth, int frames, int Hs, int Ws, const int32_t* class_map, int n_map,
+                     int raw_divisor, int divisor, int no_obj_class, const int32_t* kept_id, const int32_t* kept_n,
+                     const int32_t* src_y_host, const int32_t* src_x_host, const int32_t* src_y, const int32_t* src_x, int Hc, int Wc, int Hp,
+                     int Wp, float depth_div, float depth_max, const float* scale_mean, uint8_t* seg, float* depth, void* stream);
+
 /* ---- the optimizer step: gradient clipping by the global L2 norm + AdamW over every tensor in ONE call (csrc/ph_optim.hip) ------
  * Replaces torch.nn.utils.clip_grad_norm_(max_norm, norm_type = 2) + torch.optim.AdamW.step (the schedule of every shipped config:
  * AdamW(lr = 2e-4, weight_decay = 0.05) behind grad_clip = dict(max_norm = 1, norm_type = 2)) without rewriting a gradient.

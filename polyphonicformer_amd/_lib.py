@@ -205,6 +205,10 @@ PH_TRACK_LOSS_MAX_ROIS, PH_TRACK_LOSS_MAX_PAIRS = 128, 64
 PH_GTBOX_MAX_FRAMES, PH_GTBOX_BILINEAR, PH_GTBOX_NEAREST = 64, 0, 1
 # the step's ground truth from segment-index maps (polyhead.h ph_gt_prepare)
 PH_GTPREP_MAX_FRAMES, PH_GTPREP_MAX_SEGMENTS = 64, 254
+# the index maps from the dataset's panoptic id maps (polyhead.h ph_gt_segments, ph_gt_index_maps)
+PH_GTSEG_MAX_KEYS, PH_GTSEG_ROW_WORDS, PH_GTSEG_TABLE_WORDS = 262144, 6, 1 + 254 * 6
+PH_GTSEG_I32, PH_GTSEG_U16 = 0, 1
+PH_GTSEG_ETOOMANY, PH_GTSEG_EUNMAPPED, PH_GTSEG_EOUTSIDE = 1, 2, 4
 PH_EINVAL, PH_EWORKSPACE = -1, -4
 
 
@@ -440,6 +444,10 @@ SIGNATURES = {
     "ph_gtmask_boxes": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _L, _I, _I,
                                   _I, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
     "ph_gt_prepare": (C.c_int, [_P, _P, C.POINTER(C.c_int32), _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "ph_gt_segments_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
+    "ph_gt_segments": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "ph_gt_index_maps": (C.c_int, [_P, _I, _P, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P, _P,
+                                   _I, _I, _I, _I, C.c_float, C.c_float, C.POINTER(C.c_float), _P, _P, _P]),
     "ph_optim_workspace_bytes": (C.c_size_t, [_P, _I]),
     "ph_optim_step": (C.c_int, [C.POINTER(OptimCfg), _P, _P, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "ph_optim_zero_grads": (C.c_int, [_P, _P, _I, _I, _P]),
