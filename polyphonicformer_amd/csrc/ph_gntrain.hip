@@ -3,7 +3,9 @@
 // SemanticFPNWrapper (funcs/semantic_fpn.py:75-178) in training mode.  Replaces ATen's group_norm / threshold kernels and their
 // autograd (RowwiseMoments + three elementwise passes forward, five backward).
 //
-// forward : pass 1 sums x and x^2 of every (image, group) in fp64 over fixed pixel slices (partial records, fixed order);
+// forward : pass 1 sums x and x^2 of every (image, group) in fp64 over fixed pixel slices (partial records, fixed order); every
+//           element is widened BEFORE it is squared or added: a square rounded to fp32 is off by up to 2^-25 x^2, which a constant
+//           group keeps in full (x = 2.3: var 1.8e-7 against eps 1e-5, rstd 0.9 % low -- tests/test_gpu_train_tiles.py);
 //           pass 2 turns them into mean / rstd (fp64: E[x^2] - mean^2 is safe there), writes out = relu(gamma xhat + beta),
 //           optionally out_sum = out + add (KernelHead's x_feats = sem + loc, kernel_head.py:303) and the statistics.
 // backward: dy = dyA (+ dyB: a second gradient contribution, no ATen add over the map) masked by out > 0 (recomputed);
@@ -48,14 +50,15 @@ __global__ __launch_bounds__(GT_T) void k_gnt_stats(const float* __restrict__ y,
         i1 = sp + 1 == nsplit ? n : (i1 & ~(int64_t)3);
         for (int64_t i = i0 + threadIdx.x * 4; i < i1; i += GT_T * 4) {
             const float4 v = *(const float4*)(p + i);
-            s += (double)((v.x + v.y) + (v.z + v.w));
-            q += (double)((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w));
+            const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+            s += (x0 + x1) + (x2 + x3);
+            q += (x0 * x0 + x1 * x1) + (x2 * x2 + x3 * x3);
         }
     } else {
         for (int64_t i = i0 + threadIdx.x; i < i1; i += GT_T) {
-            const float v = p[i];
-            s += (double)v;
-            q += (double)(v * v);
+            const double v = p[i];
+            s += v;
+            q += v * v;
         }
     }
     block_sum2(s, q, lds);

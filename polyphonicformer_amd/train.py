@@ -456,13 +456,23 @@ class _Conv3x3(torch.autograd.Function):
         M, Ho, Wo = W.shape[0], gY.shape[2], gY.shape[3]
         gX = gW = None
         if ctx.needs_input_grad[0]:
-            gX = torch.empty_like(X)
+            # the kernel writes whole 16-row tiles of its output channels -- here the conv's INPUT channels: K % 16 != 0 (the forward
+            # only asks for K % 8 == 0) runs on zero-padded taps into a padded gradient (the shipped 256-channel towers never do)
+            Kp = (K + 15) // 16 * 16
+            taps = _Conv3x3._taps(W, True, s == 1)
+            if Kp != K:
+                padded = torch.zeros((9, Kp, M), dtype=torch.float32, device=X.device)
+                padded[:, :K] = taps
+                taps = padded
+            gX = torch.empty((B, Kp, Hi, Wi), dtype=torch.float32, device=X.device)
             if s == 1:
-                _lib.check(lib.ph_conv3x3_train(_lib.ptr(_Conv3x3._taps(W, True, True)), K, M, _lib.ptr(gY), _lib.ptr(gX), B, Ho, Wo, Hi, Wi, 1, 0,
+                _lib.check(lib.ph_conv3x3_train(_lib.ptr(taps), Kp, M, _lib.ptr(gY), _lib.ptr(gX), B, Ho, Wo, Hi, Wi, 1, 0,
                                                 _lib.stream_ptr()), "ph_conv3x3_train(dgrad)")
             else:
-                _lib.check(lib.ph_conv3x3_train(_lib.ptr(_Conv3x3._taps(W, True, False)), K, M, _lib.ptr(gY), _lib.ptr(gX), B, Ho, Wo, Hi, Wi, 2, 1,
+                _lib.check(lib.ph_conv3x3_train(_lib.ptr(taps), Kp, M, _lib.ptr(gY), _lib.ptr(gX), B, Ho, Wo, Hi, Wi, 2, 1,
                                                 _lib.stream_ptr()), "ph_conv3x3_train(dgrad, stride 2)")
+            if Kp != K:
+                gX = gX[:, :K].contiguous()
         if ctx.needs_input_grad[1]:
             ns = lib.ph_map_x_map_t_nsplit(B, M, Ho * Wo)
             part = torch.empty((B, ns, M, K), dtype=torch.float32, device=X.device)
