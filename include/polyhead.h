@@ -647,6 +647,27 @@ int ph_gn_apply(const float* y, const float* stats /* nullable */, const float* 
                 int accumulate, uint16_t* planes /* nullable */, float* outf /* nullable */, int B, int H, int W, int prec,
                 void* stream);
 
+/* ---- FPN: the step before the neck (mmdet/models/necks/fpn.py:151-203 as configs/_base_/models/polyphonic_former.py:22-29 builds
+ * it: four 1x1 lateral convs K -> 256 and four 3x3 output convs 256 -> 256, each with bias, no norm, no activation, nearest top-down
+ * add).  Both calls launch only: no allocation, no synchronisation, no environment variable.
+ * ph_fpn_lateral : one level's lateral conv + top-down add (fpn.py:157-173).  x: the backbone stage, NCHW-contiguous [B][K][H * W] of
+ *                  x_dtype PH_OUT_F32 / PH_OUT_BF16 / PH_OUT_F16, K a multiple of 64 in [64, 4096]; every element is read once and
+ *                  converted through fp32 to the grade's 16-bit format inside the kernel.  Wp: pack.pack_b32 fragments of W[256][K],
+ *                  one blob per plane (w_plane_elems = 256 K); bias fp32 [256].  coarse (nullable): the finished lateral of the next
+ *                  coarser level, planes [P][B][Hc * Wc][256] of the same grade; its value at (min(y Hc / H, Hc - 1),
+ *                  min(x Wc / W, Wc - 1)) -- integer division -- is added in fp32 before the one rounding.  That index is
+ *                  F.interpolate(mode='nearest', size=(H, W))'s whenever H is 2 Hc or 2 Hc - 1 and W is 2 Wc or 2 Wc - 1 (every
+ *                  stride-2 pyramid); any other size pair is PH_EINVAL with a message, never an approximate gather.
+ *                  out: 16-bit NHWC planes [P][B][H * W][256], what ph_conv_nhwc reads.  prec PH_PREC_BF16 / PH_PREC_F16: one plane;
+ *                  PH_PREC_SPLIT: hi + lo planes of both operands, hi.hi + hi.lo + lo.hi.  fp32 accumulation.  A frame's result
+ *                  does not depend on B.  A bad argument leaves `out` untouched.
+ * ph_fpn_output  : the tail of an output conv (fpn.py:177-179): y = ph_conv_nhwc's fp32 NHWC [B][HW][256] result (ksize 3, stride 1,
+ *                  on the lateral planes) + bias[256] -> fp32 NCHW [B][256][HW], the level as the module returns it. */
+int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
+                   const uint16_t* coarse /* nullable */, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
+                   void* stream);
+int ph_fpn_output(const float* y, const float* bias, float* out, int B, int64_t HW, void* stream);
+
 /* ---- N1: the quasi-dense embedding tracker as a native object (csrc/ph_tracker.hip; polyphonic/video/qdtrack/trackers/
  * quasi_dense_embed_tracker.py:47-207).  Host bookkeeping in C++ (boxes, labels, ids, ages), embeddings in a device POOL of
  * `capacity` rows of 256 floats inside `device_mem` (ph_tracker_device_bytes; owned by the caller, alive as long as the tracker).

@@ -1209,6 +1209,63 @@ class NeckPlan:
         return (self.pouts if to_planes else self.outs)[:len(pk["outs"])]
 
 
+# ---- FPN (mmdet/models/necks/fpn.py:151-203): backbone stages -> the four pyramid levels ------------------------------------
+def fpn_lateral(x, wp, bias, coarse, coarse_hw, out, prec):
+    """one level's 1x1 lateral conv + nearest top-down add: x [B, K, H, W] (fp32 / bf16 / fp16, contiguous) -> 16-bit NHWC planes
+    `out` [P, B, H*W, 256]; coarse: the next coarser level's planes [P, B, Hc*Wc, 256] with coarse_hw = (Hc, Wc), or None"""
+    B, K, H, W = x.shape
+    Hc, Wc = coarse_hw if coarse is not None else (0, 0)
+    lib = _lib.load()
+    _lib.check(lib.ph_fpn_lateral(_lib.ptr(x), OUT_CODE[x.dtype], _lib.ptr(wp), wp.shape[1], _lib.ptr(bias), _lib.ptr(coarse), Hc, Wc,
+                                  _lib.ptr(out), B, K, H, W, prec, _lib.stream_ptr()), "ph_fpn_lateral")
+    return out
+
+
+def fpn_output(y, bias, out, B, HW):
+    """fp32 NHWC conv result [B, HW, 256] + bias -> fp32 NCHW `out`"""
+    _lib.check(_lib.load().ph_fpn_output(_lib.ptr(y), _lib.ptr(bias), _lib.ptr(out), B, HW, _lib.stream_ptr()), "ph_fpn_output")
+    return out
+
+
+class FpnPlan:
+    """buffers + launch sequence of fpn.FPN.forward for one (B, level shapes, input channels): the four lateral sums as 16-bit
+    channels-last planes, one fp32 channels-last conv output, the four fp32 NCHW levels.  `run` issues everything on the current
+    stream -- one stream only, so a captured graph of it has no parallel branches -- and neither allocates nor synchronises; the
+    outputs are the plan's buffers and are overwritten by the next call, as NeckPlan's are."""
+
+    def __init__(self, B, shapes, in_channels, prec, device):
+        if len(shapes) != 4 or len(in_channels) != 4:
+            raise _lib.PolyheadError("FpnPlan: four levels")
+        self.B, self.shapes, self.in_channels, self.prec = B, tuple(tuple(s) for s in shapes), tuple(in_channels), prec
+        P = 2 if prec == _lib.PH_PREC_SPLIT else 1
+        dev = torch.device(device)
+        e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        lib = _lib.load()
+        self.lat = [e((P, B, h * w, 256), torch.int16) for h, w in self.shapes]
+        big = max(h * w for h, w in self.shapes)
+        self.y = e((B, big, 256), torch.float32)
+        self.partial = e((max(lib.ph_conv_nhwc_partial_floats(B, h, w) for h, w in self.shapes),), torch.float32)   # the conv's GN sums: unused
+        self.outs = [e((B, 256, h, w), torch.float32) for h, w in self.shapes]
+
+    def run(self, feats, pk):
+        """feats: the four backbone stages [B, K_l, H_l, W_l]; pk: fpn.FPN's pack (lateral / output: lists of dicts)"""
+        B, prec = self.B, self.prec
+        for lvl, t in enumerate(feats):
+            if tuple(t.shape) != (B, self.in_channels[lvl]) + self.shapes[lvl] or t.dtype not in OUT_CODE or not t.is_contiguous() \
+                    or t.device != self.y.device:
+                raise _lib.PolyheadError(f"FpnPlan.run: inputs[{lvl}] must be a contiguous fp32 / bf16 / fp16 device tensor of shape "
+                                         f"{(B, self.in_channels[lvl]) + self.shapes[lvl]}")
+        for lvl in (3, 2, 1, 0):                  # coarse to fine: each lateral adds the finished one above it
+            c = pk["lateral"][lvl]
+            fpn_lateral(feats[lvl], c["wp"], c["bias"], self.lat[lvl + 1] if lvl < 3 else None,
+                        self.shapes[lvl + 1] if lvl < 3 else None, self.lat[lvl], prec)
+        for lvl, (h, w) in enumerate(self.shapes):
+            c = pk["output"][lvl]
+            conv_nhwc(self.lat[lvl], c, self.y, self.partial, B, h, w, prec)
+            fpn_output(self.y, c["bias"], self.outs[lvl], B, h * w)
+        return self.outs
+
+
 # ---- the neck as a native object (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs) ------------------------------
 def native_neck_cfg(B, shapes, groups, prec, num_outs=3, pos_level=3, to_planes=False, tower_streams=True, fused_out=None, c16=None,
                     device_type="cuda"):

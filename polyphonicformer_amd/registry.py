@@ -108,7 +108,8 @@ def wrap_fp16_model(model):
     """mmcv.runner.wrap_fp16_model as the reference applies it (tools/test.py:202-204, tools/test_video.py: `fp16_cfg =
     cfg.get('fp16', None); if fp16_cfg is not None: wrap_fp16_model(model)`): every module of this package under `model`
     that has precision grades is switched to its fp16 grade -- KernelHead (and its neck) to one fp16 plane of maps and
-    weights, KernelUpdateIterHead to the `fp16` mode of engine.MODES with fp16 logits, the track head to the grade engine.PREC maps 'fp16' to.
+    weights, KernelUpdateIterHead to the `fp16` mode of engine.MODES with fp16 logits, the track head to the grade engine.PREC maps 'fp16' to,
+    an FPN of this package (fpn.FPN) to one fp16 plane.
     `model`: a module tree (a detector holding `rpn_head` / `roi_head`, or a head), or an iterable of modules."""
     import torch
     mods = list(model) if isinstance(model, (list, tuple)) else [model]
@@ -123,6 +124,9 @@ def wrap_fp16_model(model):
                 done.append(m)
             elif m.__class__.__name__ == "QuasiDenseMaskEmbedHeadGTMask" and hasattr(m, "precision"):
                 m.precision = "fp16"             # engine.PREC: the split grade of the track head (its embeddings feed a hard match)
+                done.append(m)
+            elif m.__class__.__name__ == "FPN" and m.__class__.__module__ == __package__ + ".fpn":
+                m.set_precision("fp16")          # this package's FPN only (mmdet's own has no grades): one fp16 plane
                 done.append(m)
     return done
 
