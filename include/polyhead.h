@@ -667,6 +667,18 @@ int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, int64_t w_pla
                    const uint16_t* coarse /* nullable */, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
                    void* stream);
 int ph_fpn_output(const float* y, const float* bias, float* out, int B, int64_t HW, void* stream);
+/* ph_fpn_output_planes : the same tail, handing the level to the neck directly: y (as above, read once) + bias -> the 16-bit planes
+ *                  the neck's first convolution of that level reads, and -- out_f32 given -- the fp32 NCHW level as well (ph_fpn_output's
+ *                  bits: y + bias, without `add`; the track head's RoIAlign and the module API take it).  planes: channels-last
+ *                  [P][B][HW][256] for PH_PREC_BF16 / PH_PREC_F16 / PH_PREC_SPLIT (hi + lo), or with PH_PLANES_C16 OR-ed into `prec`
+ *                  (one-plane grades) chunk-major [B][16][HW][16]: ph_nhwc_ingest's two layouts.  add (nullable): fp32 [256][HW], the
+ *                  positional encoding of the neck's pos_level as ph_nhwc_ingest takes it.  Order: v = y + bias rounded to fp32,
+ *                  v + add rounded to fp32, one rounding to 16 bits (lo = bf16 of v - hi), no contraction: the planes are bit for bit
+ *                  what ph_nhwc_ingest writes from ph_fpn_output's level and the same `add`.  Any HW; a frame's bits do not depend
+ *                  on B.  A NULL y / bias / planes, PH_PLANES_C16 with PH_PREC_SPLIT or an unknown grade is PH_EINVAL with a message
+ *                  before any launch: the outputs stay untouched. */
+int ph_fpn_output_planes(const float* y, const float* bias, const float* add /* nullable */, uint16_t* planes,
+                         float* out_f32 /* nullable */, int B, int64_t HW, int prec /* may carry PH_PLANES_C16 */, void* stream);
 
 /* ---- N1: the quasi-dense embedding tracker as a native object (csrc/ph_tracker.hip; polyphonic/video/qdtrack/trackers/
  * quasi_dense_embed_tracker.py:47-207).  Host bookkeeping in C++ (boxes, labels, ids, ages), embeddings in a device POOL of
@@ -1077,6 +1089,108 @@ typedef struct {
 int ph_neck_plan_run(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
 int ph_neck_plan_run_level(ph_neck_plan* plan, int level, const ph_neck_io* io, void* stream);
 int ph_neck_plan_run_outputs(ph_neck_plan* plan, const ph_neck_io* io, void* stream);
+/* ---- a level started from planes: the producer of a level (ph_fpn_output_planes, ph_fpn_plan_run_output) writes the level's
+ * conv-input planes itself and the tower runs without its ph_nhwc_ingest; ph_neck_io.feats is then not read at all.
+ * ph_neck_plan_level_input: the device address of level `level`'s conv-input planes inside the plan's workspace (P planes of
+ *   B * h_l * w_l * 256 elements) and the value a writer passes as `prec`: the grade, with PH_PLANES_C16 OR-ed in where the level's
+ *   first convolution reads chunk-major planes (level 0 of a c16 plan).  The writer adds the positional encoding of pos_level.
+ * ph_neck_plan_run_level_planes: ph_neck_plan_run_level without the ingest, from what the caller wrote there.
+ * ORDERING.  tower_buffers == 0: the four levels share ONE input buffer (ph_neck_plan_level_input returns the same address for
+ *   each), so a level's planes are written and its ph_neck_plan_run_level_planes is enqueued -- same stream -- before the next
+ *   level's planes are written.  tower_buffers == 1: every level owns its buffer; the four may be written in any order and their
+ *   towers run concurrently, each ordered behind its own writer.  ph_neck_plan_run_outputs follows the four towers as before. */
+int ph_neck_plan_level_input(const ph_neck_plan* plan, int level, uint16_t** planes, int32_t* prec_layout);
+int ph_neck_plan_run_level_planes(ph_neck_plan* plan, int level, void* stream);
+
+/* ---- the FPN as a native object (csrc/ph_fpnplan.hip): what fpn.FPN._pack + engine.FpnPlan do from Python -- fpn.py:151-203 for a
+ * C / C++ caller: from the four backbone stages to the four pyramid levels, as fp32 NCHW maps and / or as the conv-input planes of a
+ * neck plan (ph_neck_plan_level_input).  Conventions are ph_neck_plan_*'s: status codes + ph_last_error_string, caller-owned
+ * 256-byte aligned pack and workspace, no allocation of device memory, no synchronisation, no host read of device data and no
+ * environment variable in pack / create / run (the 3x3 convolutions go through the internal form of ph_conv_nhwc that takes its
+ * launch knobs as arguments), every cfg or pointer error returned before the first launch, every run call capturable into a hipGraph.
+ *   B            frames per call, 1 .. 4096
+ *   k            channels of the four backbone stages, each a multiple of 64 in [64, 4096] (PH_EINVAL otherwise)
+ *   h, w         the four stage = level sizes, level 0 (the finest) first; each level 2 n or 2 n - 1 of the next coarser one in both
+ *                directions -- ph_fpn_lateral's rule, at which the integer nearest index is torch's -- otherwise PH_EUNSUPPORTED
+ *   mode         PH_MODE_*, mapped to the grade as ph_neck_cfg.mode
+ *   x_dtype      element type of the stages: PH_OUT_F32 / PH_OUT_BF16 / PH_OUT_F16
+ *   emit_f32     1: ph_fpn_io.out_f32 are written;  emit_planes  1: ph_fpn_io.out_planes are written; at least one */
+typedef struct {
+    int32_t B;
+    int32_t k[4];
+    int32_t h[4], w[4];
+    int32_t mode;               /* PH_MODE_* */
+    int32_t x_dtype;            /* PH_OUT_* */
+    int32_t emit_f32, emit_planes;
+} ph_fpn_cfg;
+
+/* ---- the parameter table: fp32 device tensors under the reference's 16 state_dict keys, in state_dict order:
+ *    2 l, 2 l + 1       lateral_convs.l.conv.weight [256][k_l][1][1], .bias [256]     (l = 0 .. 3)
+ *    8 + 2 l, 9 + 2 l   fpn_convs.l.conv.weight [256][256][3][3], .bias [256] */
+#define PH_FPN_NPARAMS 16
+const char* ph_fpn_param_name(int index);                          /* NULL out of range */
+int64_t ph_fpn_param_numel(const ph_fpn_cfg* cfg, int index);      /* elements; < 0 out of range or on a bad k */
+
+/* ---- packing (k_pack_pieces: one launch, once per weight load).  Piece i is parameter i; the pieces are fpn.FPN._pack's tensors,
+ * byte for byte, each at a 256-byte aligned offset of one device buffer, the alignment padding written as zeros:
+ *   LAT_W(l)   uint16 [P][256 * k_l]    pack.pack_b32 fragments of W[n][c]: ph_fpn_lateral's Wp
+ *   OUT_W(l)   uint16 [P][256 * 2304]   pack.pack_b32 fragments of W[n][tap * 256 + c]: ph_conv_nhwc's Wp
+ *   LAT_B(l), OUT_B(l)   float [256] */
+#define PH_FPACK_LAT_W(l) (2 * (l))
+#define PH_FPACK_LAT_B(l) (2 * (l) + 1)
+#define PH_FPACK_OUT_W(l) (8 + 2 * (l))
+#define PH_FPACK_OUT_B(l) (9 + 2 * (l))
+enum { PH_FPACK_COUNT = 16 };
+typedef struct {
+    uint64_t offset[PH_FPACK_COUNT];   /* bytes from the start of the pack, multiples of 256 */
+    uint64_t bytes[PH_FPACK_COUNT];    /* size of the piece; the next piece starts at offset + bytes rounded up to 256 */
+} ph_fpn_layout;
+size_t ph_fpn_pack_bytes(const ph_fpn_cfg* cfg);                   /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_fpn_pack_layout(const ph_fpn_cfg* cfg, ph_fpn_layout* layout);
+/* `params`: host array of PH_FPN_NPARAMS device pointers; `pack`: 256-byte aligned device buffer of ph_fpn_pack_bytes */
+int ph_fpn_pack(const ph_fpn_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- plan lifetime.  The workspace holds the four lateral sums as 16-bit channels-last planes, ONE fp32 channels-last conv output
+ * (the largest level's) and the conv's per-workgroup GroupNorm sums, which nothing reads.  ZEROING CONTRACT: none.
+ * ph_fpn_plan_create touches no device memory.  The caller keeps pack and workspace alive as long as the plan. */
+typedef struct ph_fpn_plan ph_fpn_plan;
+typedef struct {
+    int32_t P;                  /* planes of the grade */
+    int32_t prec;               /* the grade, PH_PREC_* */
+    int32_t tile_rows[4];       /* per level: output rows per tile its ph_conv_nhwc launch takes at this B (2 or 4) */
+} ph_fpn_geometry;
+size_t ph_fpn_plan_workspace_bytes(const ph_fpn_cfg* cfg);         /* 0 on a bad cfg */
+int ph_fpn_plan_create(const ph_fpn_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_fpn_plan** out);
+int ph_fpn_plan_info(const ph_fpn_plan* plan, ph_fpn_geometry* out);
+/* the same answer without a plan; needs no device, no pack and no workspace; every cfg error of ph_fpn_plan_create comes back
+ * from here too */
+int ph_fpn_geometry_of(const ph_fpn_cfg* cfg, ph_fpn_geometry* out);
+void ph_fpn_plan_destroy(ph_fpn_plan* plan);
+
+/* ---- one FPN call.
+ *   stages[l]         the backbone stage [B][k_l][h_l][w_l] of cfg.x_dtype, NCHW-contiguous
+ *   out_f32[l]        float [B][256][h_l][w_l], the level as the module returns it (cfg.emit_f32)
+ *   out_planes[l]     the level as conv-input planes of the grade (cfg.emit_planes): channels-last [P][B][h_l * w_l][256] when
+ *                     planes_layout[l] == 0, chunk-major [B][16][h_l * w_l][16] when it is PH_PLANES_C16 (one-plane grades) --
+ *                     the address and the layout ph_neck_plan_level_input returns; 16-byte aligned
+ *   add[l]            nullable: float [256][h_l][w_l] added to the planes (never to out_f32): the neck's positional encoding on its
+ *                     pos_level; ignored without cfg.emit_planes
+ * ph_fpn_plan_run_laterals: the four ph_fpn_lateral launches, coarse to fine (reads `stages` only).
+ * ph_fpn_plan_run_output: level `level`'s 3x3 convolution on its lateral sum, then ONE tail launch: ph_fpn_output_planes when planes
+ *   are emitted (with out_f32 when that is emitted too), else ph_fpn_output (reads that level's output entries only).
+ * ph_fpn_plan_run: the laterals, then the outputs of levels 0 .. 3, all on `stream`: a captured graph of it has no parallel branches.
+ * A neck plan with tower_buffers == 0 takes ph_fpn_plan_run_laterals once and then, level by level, ph_fpn_plan_run_output followed
+ * by ph_neck_plan_run_level_planes (ph_neck_plan_level_input's ordering rule); the results equal ph_fpn_plan_run's. */
+typedef struct {
+    const void* stages[4];
+    float* out_f32[4];
+    uint16_t* out_planes[4];
+    int32_t planes_layout[4];   /* 0 or PH_PLANES_C16 */
+    const float* add[4];
+} ph_fpn_io;
+int ph_fpn_plan_run_laterals(ph_fpn_plan* plan, const ph_fpn_io* io, void* stream);
+int ph_fpn_plan_run_output(ph_fpn_plan* plan, int level, const ph_fpn_io* io, void* stream);
+int ph_fpn_plan_run(ph_fpn_plan* plan, const ph_fpn_io* io, void* stream);
 
 /* ---- N1 as a native object (csrc/ph_assocplan.hip): the association step of PolyphonicVideo.simple_test
  * (polyphonic_former_video.py:359-405) behind ph_panoptic_merge, for a C / C++ caller -- what video.VideoAssociator and

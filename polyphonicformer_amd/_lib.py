@@ -106,6 +106,29 @@ class NeckIO(C.Structure):
     _fields_ = [("feats", C.c_void_p * 4), ("posenc", C.c_void_p), ("out_planes", C.c_void_p * 3), ("out_f32", C.c_void_p * 3)]
 
 
+# the native FPN plan (polyhead.h ph_fpn_cfg .. ph_fpn_plan_run); piece i of the pack is parameter i: lateral l weight 2 l, bias 2 l + 1,
+# output conv l weight 8 + 2 l, bias 9 + 2 l
+PH_FPN_NPARAMS = PH_FPACK_COUNT = 16
+
+
+class FpnCfg(C.Structure):
+    _fields_ = [("B", C.c_int32), ("k", C.c_int32 * 4), ("h", C.c_int32 * 4), ("w", C.c_int32 * 4)] + \
+        [(n, C.c_int32) for n in ("mode", "x_dtype", "emit_f32", "emit_planes")]
+
+
+class FpnLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * PH_FPACK_COUNT), ("bytes", C.c_uint64 * PH_FPACK_COUNT)]
+
+
+class FpnGeometry(C.Structure):
+    _fields_ = [("P", C.c_int32), ("prec", C.c_int32), ("tile_rows", C.c_int32 * 4)]
+
+
+class FpnIO(C.Structure):
+    _fields_ = [("stages", C.c_void_p * 4), ("out_f32", C.c_void_p * 4), ("out_planes", C.c_void_p * 4), ("planes_layout", C.c_int32 * 4),
+                ("add", C.c_void_p * 4)]
+
+
 # the native association plan (polyhead.h ph_track_cfg .. ph_assoc_plan_match)
 PH_TRACK_MAX_CONVS = 8
 PH_TPACK_FC, PH_TPACK_FC_B, PH_TPACK_EMB, PH_TPACK_EMB_B, PH_TPACK_COUNT = 24, 25, 26, 27, 28     # conv i, gamma 8 + i, beta 16 + i
@@ -241,6 +264,7 @@ class OptimState(C.Structure):
 STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decode_geometry": DecodeGeometry, "ph_decode_io": DecodeIO,
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
            "ph_neck_cfg": NeckCfg, "ph_neck_layout": NeckLayout, "ph_neck_geometry": NeckGeometry, "ph_neck_io": NeckIO,
+           "ph_fpn_cfg": FpnCfg, "ph_fpn_layout": FpnLayout, "ph_fpn_geometry": FpnGeometry, "ph_fpn_io": FpnIO,
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
            "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout,
@@ -362,6 +386,7 @@ SIGNATURES = {
     "ph_gn_apply": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "ph_fpn_lateral": (C.c_int, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ph_fpn_output": (C.c_int, [_P, _P, _P, _I, _L, _P]),
+    "ph_fpn_output_planes": (C.c_int, [_P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "ph_tracker_device_bytes": (C.c_size_t, [_I, _I]),
     "ph_tracker_create": (C.c_void_p, [_P, _P, _Z, _I, _I]),
     "ph_tracker_destroy": (None, [_P]),
@@ -409,6 +434,21 @@ SIGNATURES = {
     "ph_neck_plan_run": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
     "ph_neck_plan_run_level": (C.c_int, [_P, _I, C.POINTER(NeckIO), _P]),
     "ph_neck_plan_run_outputs": (C.c_int, [_P, C.POINTER(NeckIO), _P]),
+    "ph_neck_plan_level_input": (C.c_int, [_P, _I, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]),
+    "ph_neck_plan_run_level_planes": (C.c_int, [_P, _I, _P]),
+    "ph_fpn_param_name": (C.c_char_p, [_I]),
+    "ph_fpn_param_numel": (C.c_int64, [C.POINTER(FpnCfg), _I]),
+    "ph_fpn_pack_bytes": (C.c_size_t, [C.POINTER(FpnCfg)]),
+    "ph_fpn_pack_layout": (C.c_int, [C.POINTER(FpnCfg), C.POINTER(FpnLayout)]),
+    "ph_fpn_pack": (C.c_int, [C.POINTER(FpnCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_fpn_plan_workspace_bytes": (C.c_size_t, [C.POINTER(FpnCfg)]),
+    "ph_fpn_plan_create": (C.c_int, [C.POINTER(FpnCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_fpn_plan_info": (C.c_int, [_P, C.POINTER(FpnGeometry)]),
+    "ph_fpn_geometry_of": (C.c_int, [C.POINTER(FpnCfg), C.POINTER(FpnGeometry)]),
+    "ph_fpn_plan_destroy": (None, [_P]),
+    "ph_fpn_plan_run_laterals": (C.c_int, [_P, C.POINTER(FpnIO), _P]),
+    "ph_fpn_plan_run_output": (C.c_int, [_P, _I, C.POINTER(FpnIO), _P]),
+    "ph_fpn_plan_run": (C.c_int, [_P, C.POINTER(FpnIO), _P]),
     "ph_track_param_name": (C.c_char_p, [C.POINTER(TrackCfg), _I]),
     "ph_track_param_numel": (C.c_int64, [C.POINTER(TrackCfg), _I]),
     "ph_track_pack_bytes": (C.c_size_t, [C.POINTER(TrackCfg)]),

@@ -86,6 +86,7 @@ struct PhPackTable {
 };
 static_assert(sizeof(PhPackTable) <= 2048, "the pack table travels as a kernel argument");
 static_assert(PH_KHEAD_NPARAMS <= PH_PACK_MAX_PARAMS && PH_NECK_NPARAMS <= PH_PACK_MAX_PARAMS && 3 * PH_TRACK_MAX_CONVS + 4 <= PH_PACK_MAX_PARAMS &&
+              PH_FPN_NPARAMS <= PH_PACK_MAX_PARAMS && PH_FPACK_COUNT <= PH_PACK_MAX_PIECES &&
               PH_KPACK_COUNT <= PH_PACK_MAX_PIECES && PH_NPACK_COUNT <= PH_PACK_MAX_PIECES && PH_TPACK_COUNT <= PH_PACK_MAX_PIECES,
               "include/polyhead.h: a pack's parameters and pieces fit the table");
 // piece `i` of a pack layout (include/polyhead.h: offset[] / bytes[] of the pieces) into the table

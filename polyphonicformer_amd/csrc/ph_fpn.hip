@@ -289,3 +289,92 @@ extern "C" int ph_fpn_output(const float* y, const float* bias, float* out, int 
     PH_CHECK_LAUNCH();
     return PH_OK;
 }
+
+// ---- the direct hand-over to the neck: the tail of an output conv that writes the neck's conv-input planes itself, so the fp32 NCHW
+// level does not cross memory twice on its way there (ph_fpn_output writes it, ph_nhwc_ingest reads it back).  One block = 32 pixels
+// x 256 channels, k_fpn_output's tile: y is read once as whole 1 KiB pixel vectors, v = y + bias goes to LDS as [channel][pixel];
+// a channel-row pass then writes the fp32 NCHW level (128-byte runs of 32 pixels, k_fpn_output's stores and bits) and / or adds the
+// positional encoding ([256][HW], the same runs) in place; the last pass rounds once and writes whole 128-byte lines of planes:
+//   channels-last [P][B][HW][256]: 8 lanes x 16 bytes = 64 channels of a pixel (k_nhwc_ingest_v4's stores), a wave = 8 pixels
+//   PH_PLANES_C16 [B][16][HW][16]: a wave = the 32 pixels of one 16-channel chunk, 1 KiB of consecutive bytes
+// The arithmetic is ph_nhwc_ingest's on ph_fpn_output's value: (y + bias) rounded to fp32, + add, one rounding to 16 bits.
+// `zadd`: ph_nhwc_ingest's 16-byte form (HW % 4 == 0) adds a zero where there is no table, which turns -0 into +0; the same here.
+#pragma clang fp contract(off)
+template <int PA, int E, bool C16>
+__global__ __launch_bounds__(256) void k_fpn_output_planes(const float* __restrict__ y, const float* __restrict__ bias,
+                                                           const float* __restrict__ add, uint16_t* __restrict__ planes,
+                                                           float* __restrict__ outf, int B, int64_t HW, int zadd) {
+    __shared__ float t[256][33];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t p0 = (int64_t)blockIdx.x * 32;
+    {
+        const int c4 = (tid & 63) * 4, pq = tid >> 6;
+        const float4 bv = *(const float4*)(bias + c4);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int pl = k * 4 + pq;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (p0 + pl < HW) {
+                const uint4 q = ld_nt16(y + ((int64_t)b * HW + p0 + pl) * 256 + c4);
+                v = make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w));
+            }
+            t[c4][pl] = v.x + bv.x; t[c4 + 1][pl] = v.y + bv.y; t[c4 + 2][pl] = v.z + bv.z; t[c4 + 3][pl] = v.w + bv.w;
+        }
+    }
+    __syncthreads();
+    if (outf || add) {                                            // uniform: kernel arguments
+        const int pl = tid & 31, cr = tid >> 5;                   // 8 channel rows per pass; a thread rewrites its own elements only
+        if (p0 + pl < HW) {
+#pragma unroll 4
+            for (int c = cr; c < 256; c += 8) {
+                const float v = t[c][pl];
+                if (outf) outf[((int64_t)b * 256 + c) * HW + p0 + pl] = v;
+                if (add) t[c][pl] = v + add[(int64_t)c * HW + p0 + pl];
+            }
+        }
+        __syncthreads();
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    const int64_t plane = (int64_t)B * HW * 256;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // channels-last: 64 channels of wave `wave`, pixels 8 k .. 8 k + 7;  C16: chunk 4 k + wave, all 32 pixels
+        const int px = C16 ? lane >> 1 : k * 8 + (lane >> 3);
+        const int c0 = C16 ? (k * 4 + wave) * 16 + (lane & 1) * 8 : wave * 64 + (lane & 7) * 8;
+        if (p0 + px >= HW) continue;
+        uint32_t hi[8], lo[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float s = t[c0 + e][px];
+            if (zadd) s += 0.f;
+            f2e_split<E>(s, hi[e], lo[e]);
+        }
+        uint16_t* d = C16 ? planes + (((int64_t)b * 16 + (c0 >> 4)) * HW + p0 + px) * 16 + (c0 & 15)
+                          : planes + ((int64_t)b * HW + p0 + px) * 256 + c0;
+        *(uint4*)d = make_uint4(pack2(hi[0], hi[1]), pack2(hi[2], hi[3]), pack2(hi[4], hi[5]), pack2(hi[6], hi[7]));
+        if (PA == 2) *(uint4*)(d + plane) = make_uint4(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]), pack2(lo[4], lo[5]), pack2(lo[6], lo[7]));
+    }
+}
+
+extern "C" int ph_fpn_output_planes(const float* y, const float* bias, const float* add, uint16_t* planes, float* out_f32, int B,
+                                    int64_t HW, int prec, void* stream) {
+    PH_CHECK_ARG(y && bias && planes, "null pointer (y, bias, planes)");
+    const bool c16 = (prec & PH_PLANES_C16) != 0;
+    prec &= ~PH_PLANES_C16;
+    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
+    PH_CHECK_ARG(!c16 || prec != PH_PREC_SPLIT, "PH_PLANES_C16 output: one-plane formats only");
+    PH_CHECK_ARG(B > 0 && B <= 65535 && HW > 0 && HW <= (int64_t)32 * 0x7FFFFFFF, "B, HW out of range");
+    PH_CHECK_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)bias & 15) == 0 && ((uintptr_t)planes & 15) == 0,
+                 "y, bias and planes must be 16-byte aligned");
+    PH_CHECK_ARG(((uintptr_t)add & 3) == 0 && ((uintptr_t)out_f32 & 3) == 0, "add and out_f32 must be 4-byte aligned");
+    const dim3 grid((unsigned)((HW + 31) / 32), (unsigned)B);
+    const int zadd = !add && (HW & 3) == 0;
+    hipStream_t s = (hipStream_t)stream;
+#define PH_FOP(PA_, E_, C_) hipLaunchKernelGGL((k_fpn_output_planes<PA_, E_, C_>), grid, dim3(256), 0, s, y, bias, add, planes, out_f32, B, HW, zadd)
+    if (prec == PH_PREC_SPLIT) PH_FOP(2, PH_E_BF16, false);
+    else if (prec == PH_PREC_F16) { if (c16) PH_FOP(1, PH_E_F16, true); else PH_FOP(1, PH_E_F16, false); }
+    else { if (c16) PH_FOP(1, PH_E_BF16, true); else PH_FOP(1, PH_E_BF16, false); }
+#undef PH_FOP
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}

@@ -342,7 +342,8 @@ static int conv_gn(const NGeo& g, const ph_neck_plan* p, const uint16_t* x, int 
     return PH_OK;
 }
 
-// one level (engine.NeckPlan._tower): ingest -> (conv + GN + ReLU + x2 upsample)* -> last conv (its GroupNorm is applied by the level sum)
+// one level (engine.NeckPlan._tower): ingest -> (conv + GN + ReLU + x2 upsample)* -> last conv (its GroupNorm is applied by the level sum);
+// io == nullptr: no ingest, the caller has written the level's planes (ph_neck_plan_run_level_planes)
 static int run_tower(const ph_neck_plan* p, int lvl, const ph_neck_io* io, hipStream_t s) {
     const NGeo& g = p->g;
     const NLevelBufs& b = g.lv[lvl];
@@ -353,7 +354,7 @@ static int run_tower(const ph_neck_plan* p, int lvl, const ph_neck_io* io, hipSt
     float* partial = (float*)(p->ws + b.partial);
     int H = g.h[lvl], W = g.w[lvl];
     const int c16 = (lvl == 0 && g.c16) ? PH_PLANES_C16 : 0;
-    PH_RUN(ph_nhwc_ingest(io->feats[lvl], lvl == g.pos_level ? io->posenc : nullptr, xa, g.B, (int64_t)H * W, g.prec | c16, s));
+    if (io) PH_RUN(ph_nhwc_ingest(io->feats[lvl], lvl == g.pos_level ? io->posenc : nullptr, xa, g.B, (int64_t)H * W, g.prec | c16, s));
     uint16_t* src = xa;
     for (int j = 0; j < kLevelConvs[lvl]; ++j) {
         const int conv = kLevelFirst[lvl] + j, lay = j == 0 ? c16 : 0;
@@ -413,6 +414,20 @@ extern "C" int ph_neck_plan_run_level(ph_neck_plan* p, int level, const ph_neck_
     PH_CHECK_ARG(level >= 0 && level < 4, "level must be 0 .. 3");
     PH_RUN(check_io(p->g, io, "ph_neck_plan_run_level", true, level, false));
     return run_tower(p, level, io, (hipStream_t)stream);
+}
+
+extern "C" int ph_neck_plan_level_input(const ph_neck_plan* p, int level, uint16_t** planes, int32_t* prec_layout) {
+    PH_CHECK_ARG(p && planes && prec_layout, "null plan, planes or prec_layout");
+    PH_CHECK_ARG(level >= 0 && level < 4, "level must be 0 .. 3");
+    *planes = (uint16_t*)(p->ws + p->g.lv[level].xa);
+    *prec_layout = p->g.prec | ((level == 0 && p->g.c16) ? PH_PLANES_C16 : 0);
+    return PH_OK;
+}
+
+extern "C" int ph_neck_plan_run_level_planes(ph_neck_plan* p, int level, void* stream) {
+    PH_CHECK_ARG(p != nullptr, "null plan");
+    PH_CHECK_ARG(level >= 0 && level < 4, "level must be 0 .. 3");
+    return run_tower(p, level, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int ph_neck_plan_run_outputs(ph_neck_plan* p, const ph_neck_io* io, void* stream) {

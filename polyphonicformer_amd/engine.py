@@ -1168,11 +1168,43 @@ class NeckPlan:
                 _lib.check(lib.ph_nhwc_ingest(_lib.ptr(t), add, C.c_void_p(xa.data_ptr() + b * h * w * 256 * 2), 1, h * w, self.prec | c16, st),
                            "ph_nhwc_ingest(frame)")
 
-    def run(self, feats, pk, groups, posenc, pos_level, to_planes=False):
-        B, prec = self.B, self.prec
+    def _check_pk(self, pk, groups):
         if len(pk["outs"]) != self.num_outs or groups != self.groups:
             raise _lib.PolyheadError(f"NeckPlan.run: the plan was built for {self.num_outs} output convs and {self.groups} groups, "
                                      f"not {len(pk['outs'])} and {groups}")
+
+    # ---- a level started from planes (FpnPlan.run's `neck`): the producer writes `level_input` -- positional encoding included --
+    # and the tower runs without its ingest.  Shared buffers (`multi` False): the four levels share `xa`, so a level's planes are
+    # written and its `run_level_planes` issued before the next level's are written; `multi`: every level owns its `xa` and
+    # `run_towers_planes` runs the four towers on their streams
+    def level_input(self, lvl, pk, to_planes=False):
+        """(the level's conv input planes, the `prec` value -- grade | layout -- their writer uses)"""
+        c0 = pk["levels"][lvl][0]
+        c16 = self.c16 if (c0["s"] == 2 and c0["k"] == 3) else 0
+        return (self.lv[lvl]["xa"] if self.multi else self.xa), self.prec | c16
+
+    def _from_planes(self, fn):
+        saved, self.skip_ingest = self.skip_ingest, True
+        try:
+            fn()
+        finally:
+            self.skip_ingest = saved
+
+    def run_level_planes(self, lvl, pk, groups, to_planes=False):
+        self._check_pk(pk, groups)
+        bufs = self.lv[lvl] if self.multi else dict(xa=self.xa, xb=self.xb, y=self.y, stats=self.stats, partial=self.partial)
+        self._from_planes(lambda: self._tower(lvl, None, pk, groups, None, bufs))
+
+    def run_towers_planes(self, pk, groups, to_planes=False):
+        self._check_pk(pk, groups)
+        self._from_planes(lambda: self._towers([None] * 4, pk, groups, None, -1))
+
+    def run(self, feats, pk, groups, posenc, pos_level, to_planes=False):
+        self._check_pk(pk, groups)
+        self._towers(feats, pk, groups, posenc, pos_level)
+        return self.run_outputs(pk, groups, to_planes)
+
+    def _towers(self, feats, pk, groups, posenc, pos_level):
         if self.multi:
             if self._streams is None:
                 self._streams = [torch.cuda.Stream(device=self.xa.device) for _ in range(4)]
@@ -1188,6 +1220,10 @@ class NeckPlan:
             shared = dict(xa=self.xa, xb=self.xb, y=self.y, stats=self.stats, partial=self.partial)
             for lvl in range(4):
                 self._tower(lvl, feats[lvl], pk, groups, posenc if lvl == pos_level else None, shared)
+
+    def run_outputs(self, pk, groups, to_planes=False, posenc=None):
+        """the level sum and conv_pred / the aux convs, behind the four towers"""
+        B, prec = self.B, self.prec
         if to_planes and self.pouts is None:
             P = 2 if prec == _lib.PH_PREC_SPLIT else 1
             self.pouts = [torch.empty((P, B, 256, hw_padded(self.Ho * self.Wo)), dtype=torch.int16, device=self.xa.device)
@@ -1227,6 +1263,33 @@ def fpn_output(y, bias, out, B, HW):
     return out
 
 
+def fpn_output_planes(y, bias, add, planes, out_f32, B, HW, prec):
+    """fp32 NHWC conv result [B, HW, 256] + bias (+ add [256, HW], or None) -> the neck's conv input `planes` (a tensor or a device
+    address; `prec`: the grade, | PH_PLANES_C16 for chunk-major planes) and, `out_f32` given, the fp32 NCHW level as well"""
+    pp = planes if isinstance(planes, C.c_void_p) else _lib.ptr(planes)
+    _lib.check(_lib.load().ph_fpn_output_planes(_lib.ptr(y), _lib.ptr(bias), _lib.ptr(add), pp, _lib.ptr(out_f32), B, HW, prec,
+                                                _lib.stream_ptr()), "ph_fpn_output_planes")
+
+
+class NeckHandoff:
+    """FpnPlan.run's `neck`: a neck plan (NeckPlan or NativeNeckPlan) with the arguments of its run.  `FpnPlan.run(.., neck=this)`
+    writes the levels into the plan's conv input planes (and, shared buffers, runs each level's tower); `finish()` runs what is left
+    -- the four towers of the tower-buffer form, the level sum and the output convs -- and returns the neck's outputs"""
+
+    def __init__(self, plan, pk, groups, posenc, pos_level, to_planes=False):
+        self.plan, self.pk, self.groups, self.to_planes = plan, pk, groups, to_planes
+        self.posenc = posenc
+        self.pos_level = -1 if (posenc is None or pos_level is None) else pos_level
+        if posenc is not None and (posenc.dtype != torch.float32 or not posenc.is_contiguous() or
+                                   tuple(posenc.shape) != (256,) + tuple(plan.shapes[self.pos_level])):
+            raise _lib.PolyheadError("NeckHandoff: posenc must be fp32 contiguous [256, h, w] of pos_level")
+
+    def finish(self):
+        if self.plan.multi:
+            self.plan.run_towers_planes(self.pk, self.groups, self.to_planes)
+        return self.plan.run_outputs(self.pk, self.groups, self.to_planes, posenc=self.posenc)
+
+
 class FpnPlan:
     """buffers + launch sequence of fpn.FPN.forward for one (B, level shapes, input channels): the four lateral sums as 16-bit
     channels-last planes, one fp32 channels-last conv output, the four fp32 NCHW levels.  `run` issues everything on the current
@@ -1247,9 +1310,16 @@ class FpnPlan:
         self.partial = e((max(lib.ph_conv_nhwc_partial_floats(B, h, w) for h, w in self.shapes),), torch.float32)   # the conv's GN sums: unused
         self.outs = [e((B, 256, h, w), torch.float32) for h, w in self.shapes]
 
-    def run(self, feats, pk):
-        """feats: the four backbone stages [B, K_l, H_l, W_l]; pk: fpn.FPN's pack (lateral / output: lists of dicts)"""
+    def run(self, feats, pk, neck=None, want_levels=True):
+        """feats: the four backbone stages [B, K_l, H_l, W_l]; pk: fpn.FPN's pack (lateral / output: lists of dicts).
+        neck: a NeckHandoff -- the direct hand-over: each output conv's tail (ph_fpn_output_planes) writes the neck plan's conv input
+        planes of that level, positional encoding included, instead of the fp32 level that the neck would ingest; the fp32 levels are
+        written as well when `want_levels`.  Shared neck buffers: the level's tower runs before the next level is written; tower
+        buffers: the four inputs are written and `neck.finish()` runs the towers.  Either way `neck.finish()` returns the neck's
+        outputs, bit for bit those of the neck plan's `run` on this plan's levels."""
         B, prec = self.B, self.prec
+        if neck is not None and (neck.plan.B != B or tuple(tuple(x) for x in neck.plan.shapes) != self.shapes or neck.plan.prec != prec):
+            raise _lib.PolyheadError("FpnPlan.run: the neck plan's frames, level sizes or grade differ from this plan's")
         for lvl, t in enumerate(feats):
             if tuple(t.shape) != (B, self.in_channels[lvl]) + self.shapes[lvl] or t.dtype not in OUT_CODE or not t.is_contiguous() \
                     or t.device != self.y.device:
@@ -1262,7 +1332,14 @@ class FpnPlan:
         for lvl, (h, w) in enumerate(self.shapes):
             c = pk["output"][lvl]
             conv_nhwc(self.lat[lvl], c, self.y, self.partial, B, h, w, prec)
-            fpn_output(self.y, c["bias"], self.outs[lvl], B, h * w)
+            if neck is None:
+                fpn_output(self.y, c["bias"], self.outs[lvl], B, h * w)
+                continue
+            xa, layout = neck.plan.level_input(lvl, neck.pk, neck.to_planes)
+            fpn_output_planes(self.y, c["bias"], neck.posenc if lvl == neck.pos_level else None, xa,
+                              self.outs[lvl] if want_levels else None, B, h * w, layout)
+            if not neck.plan.multi:
+                neck.plan.run_level_planes(lvl, neck.pk, neck.groups, neck.to_planes)
         return self.outs
 
 
@@ -1442,6 +1519,149 @@ class NativeNeckPlan(_OwnsHandles):
         else:
             _lib.check(lib.ph_neck_plan_run(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run")
         return outs
+
+    # ---- a level started from planes (NeckPlan's surface of the same names; `pk` / `groups` are the plan's own)
+    prec = property(lambda self: self.geometry.prec)
+
+    def level_input(self, lvl, pk=None, to_planes=False):
+        p, layout = C.c_void_p(), C.c_int32()
+        _lib.check(_lib.load().ph_neck_plan_level_input(self._handle(to_planes), lvl, C.byref(p), C.byref(layout)), "ph_neck_plan_level_input")
+        return p, layout.value
+
+    def run_level_planes(self, lvl, pk=None, groups=None, to_planes=False):
+        _lib.check(_lib.load().ph_neck_plan_run_level_planes(self._handle(to_planes), lvl, _lib.stream_ptr()), "ph_neck_plan_run_level_planes")
+
+    def run_towers_planes(self, pk=None, groups=None, to_planes=False):
+        if self._streams is None:
+            self._streams = [torch.cuda.Stream(device=self.device) for _ in range(4)]
+        cur = torch.cuda.current_stream()
+        for lvl in (0, 3, 2, 1):                    # the longest chains first (NeckPlan.run)
+            st = self._streams[lvl]
+            st.wait_stream(cur)
+            with torch.cuda.stream(st):
+                self.run_level_planes(lvl, to_planes=to_planes)
+        for st in self._streams:
+            cur.wait_stream(st)
+
+    def run_outputs(self, pk=None, groups=None, to_planes=False, posenc=None):
+        outs = self.outputs(to_planes)
+        io = self.io
+        io.posenc = posenc.data_ptr() if (self.pos_level >= 0 and posenc is not None) else None
+        for i in range(3):
+            t = outs[i] if i < len(outs) else None
+            io.out_planes[i] = t.data_ptr() if (to_planes and t is not None) else None
+            io.out_f32[i] = t.data_ptr() if (not to_planes and t is not None) else None
+        _lib.check(_lib.load().ph_neck_plan_run_outputs(self._handle(to_planes), C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_outputs")
+        return outs
+
+
+# ---- the FPN as a native object (include/polyhead.h ph_fpn_cfg .. ph_fpn_plan_run) -------------------------------------------
+def native_fpn_cfg(B, shapes, in_channels, prec, x_dtype=torch.float32, emit_f32=True, emit_planes=False):
+    """the ph_fpn_cfg of a native FPN plan.  `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `shapes`: the four
+    level sizes; `in_channels`: the four stage widths; `x_dtype`: the stages' torch dtype.  The FPN has no environment switch"""
+    name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
+    if len(shapes) != 4 or len(in_channels) != 4:
+        raise _lib.PolyheadError("the FPN takes four stages")
+    if x_dtype not in OUT_CODE:
+        raise _lib.PolyheadError("the FPN's stages are fp32, bf16 or fp16")
+    i4 = lambda xs: (C.c_int32 * 4)(*[int(x) for x in xs])
+    return _lib.FpnCfg(B=B, k=i4(in_channels), h=i4([x[0] for x in shapes]), w=i4([x[1] for x in shapes]), mode=_lib.PH_MODE[name],
+                       x_dtype=OUT_CODE[x_dtype], emit_f32=int(bool(emit_f32)), emit_planes=int(bool(emit_planes)))
+
+
+class NativeFpnPack:
+    """one device buffer packed by ph_fpn_pack, and its pieces as views in the form of fpn.FPN._pack's dict (`pk`: so either plan --
+    FpnPlan or NativeFpnPlan -- runs from it)"""
+
+    def __init__(self, blob, cfg):
+        lay = _lib.FpnLayout()
+        _lib.check(_lib.load().ph_fpn_pack_layout(C.byref(cfg), C.byref(lay)), "ph_fpn_pack_layout")
+        self.blob, self.layout, self.mode, self.in_channels = blob, lay, cfg.mode, tuple(cfg.k)
+        self.prec = _GRADE_OF_MODE[cfg.mode]
+        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
+        one = lambda i, kk, k: dict(wp=_pack_piece(blob, lay, i, torch.int16, (P, 256 * kk)),
+                                    bias=_pack_piece(blob, lay, i + 1, torch.float32, (256,)), k=k, s=1)
+        self.pk = dict(lateral=[one(2 * l, cfg.k[l], 1) for l in range(4)], output=[one(8 + 2 * l, 9 * 256, 3) for l in range(4)])
+
+
+def native_fpn_pack(module, cfg, device):
+    """the FPN's parameters (a fpn.FPN, or its state_dict) packed on the device by ph_fpn_pack"""
+    lib = _lib.load()
+    return NativeFpnPack(_pack_on_device(module, cfg, device, lib.ph_fpn_pack_bytes, _lib.PH_FPN_NPARAMS, lib.ph_fpn_param_name,
+                                         lib.ph_fpn_param_numel, lib.ph_fpn_pack, "ph_fpn_pack"), cfg)
+
+
+class NativeFpnPlan(_OwnsHandles):
+    """FpnPlan's `run` surface over the native plan: ONE native call per forward (ph_fpn_plan_run), or -- handing over to a neck plan
+    with shared buffers -- ph_fpn_plan_run_laterals and then ph_fpn_plan_run_output level by level with the level's tower behind it;
+    the same launch sequence as the FpnPlan of the same arguments, so the same bits.  `pack`: a NativeFpnPack; `cfg`: a ph_fpn_cfg to
+    use as it is (its emit flags follow each run) instead of `native_fpn_cfg`'s."""
+    _destroy_symbol = "ph_fpn_plan_destroy"
+
+    def __init__(self, pack, B, shapes, device, x_dtype=torch.float32, cfg=None):
+        dev = torch.device(device)
+        self.pack, self.B, self.shapes, self.device = pack, B, tuple(tuple(x) for x in shapes), dev
+        base = cfg if cfg is not None else native_fpn_cfg(B, self.shapes, pack.in_channels, _MODE_NAME[pack.mode], x_dtype)
+        self.cfg = _lib.FpnCfg.from_buffer_copy(bytes(base))
+        self.in_channels, self.x_dtype = tuple(self.cfg.k), {v: k for k, v in OUT_CODE.items()}[self.cfg.x_dtype]
+        lib = _lib.load()
+        nbytes = lib.ph_fpn_plan_workspace_bytes(C.byref(self.cfg))
+        if nbytes == 0:
+            raise _cfg_error("ph_fpn_plan_workspace_bytes")
+        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
+        self._handles = {}
+        self.geometry = _lib.FpnGeometry()
+        _lib.check(lib.ph_fpn_plan_info(self._handle(True, False), C.byref(self.geometry)), "ph_fpn_plan_info")
+        self.prec = self.geometry.prec
+        self.outs = None                                                            # the fp32 levels, allocated on first use
+        self.io = _lib.FpnIO()
+
+    def _handle(self, emit_f32, emit_planes):
+        """the native plan of these emit flags (they share the workspace: a run uses one of them)"""
+        key = (bool(emit_f32), bool(emit_planes))
+        h = self._handles.get(key)
+        if h is None:
+            cfg = _lib.FpnCfg.from_buffer_copy(bytes(self.cfg))
+            cfg.emit_f32, cfg.emit_planes = int(key[0]), int(key[1])
+            h = C.c_void_p()
+            _lib.check(_lib.load().ph_fpn_plan_create(C.byref(cfg), _lib.ptr(self.pack.blob), _lib.ptr(self.workspace),
+                                                      self.workspace.numel(), C.byref(h)), "ph_fpn_plan_create")
+            self._handles[key] = h
+        return h
+
+    def run(self, feats, pk=None, neck=None, want_levels=True):
+        """FpnPlan.run's arguments (`pk`: the plan's own pack, when given)"""
+        if pk is not None and pk is not self.pack and pk is not self.pack.pk:
+            raise _lib.PolyheadError("NativeFpnPlan.run: the plan runs from the pack it was created with")
+        B, io, lib = self.B, self.io, _lib.load()
+        for l, t in enumerate(feats):
+            if tuple(t.shape) != (B, self.in_channels[l]) + self.shapes[l] or t.dtype != self.x_dtype or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise _lib.PolyheadError(f"NativeFpnPlan.run: inputs[{l}] must be a contiguous {self.x_dtype} tensor of shape "
+                                         f"{(B, self.in_channels[l]) + self.shapes[l]} on {self.device}")
+            io.stages[l] = t.data_ptr()
+        if neck is not None and (neck.plan.B != B or tuple(tuple(x) for x in neck.plan.shapes) != self.shapes or neck.plan.prec != self.prec):
+            raise _lib.PolyheadError("NativeFpnPlan.run: the neck plan's frames, level sizes or grade differ from this plan's")
+        want_f32 = neck is None or want_levels
+        if want_f32 and self.outs is None:
+            self.outs = [torch.empty((B, 256, h, w), dtype=torch.float32, device=self.device) for h, w in self.shapes]
+        for l in range(4):
+            io.out_f32[l] = self.outs[l].data_ptr() if want_f32 else None
+            io.out_planes[l], io.planes_layout[l], io.add[l] = None, 0, None
+            if neck is not None:
+                xa, layout = neck.plan.level_input(l, neck.pk, neck.to_planes)
+                io.out_planes[l] = xa.value if isinstance(xa, C.c_void_p) else xa.data_ptr()
+                io.planes_layout[l] = layout & _lib.PH_PLANES_C16
+                io.add[l] = neck.posenc.data_ptr() if l == neck.pos_level else None
+        h, st = self._handle(want_f32, neck is not None), _lib.stream_ptr()
+        if neck is None or neck.plan.multi:
+            _lib.check(lib.ph_fpn_plan_run(h, C.byref(io), st), "ph_fpn_plan_run")
+        else:
+            _lib.check(lib.ph_fpn_plan_run_laterals(h, C.byref(io), st), "ph_fpn_plan_run_laterals")
+            for l in range(4):
+                _lib.check(lib.ph_fpn_plan_run_output(h, l, C.byref(io), st), "ph_fpn_plan_run_output")
+                neck.plan.run_level_planes(l, neck.pk, neck.groups, neck.to_planes)
+        return self.outs if want_f32 else None
 
 
 class DualDecodePlan:

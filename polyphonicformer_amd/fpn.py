@@ -108,6 +108,13 @@ class FPN(nn.Module):
         assert len(inputs) == len(self.in_channels)
         if self.training and torch.is_grad_enabled():
             return self._forward_torch(inputs)
+        plan, pk, feats = self._plan_of(inputs)
+        with torch.cuda.device(feats[0].device):
+            return tuple(plan.run(feats, pk))
+
+    def _plan_of(self, inputs):
+        """(the device plan of these stages, the packed parameters, the stages as the plan takes them): what `forward` runs, and
+        what SemanticFPNWrapper.forward_from_fpn runs with the neck's plan as the receiver of the levels"""
         x0 = inputs[0]
         E._require_gpu(x0, "inputs[0]")
         dev, B = x0.device, x0.shape[0]
@@ -119,9 +126,7 @@ class FPN(nn.Module):
         if plan is None:
             with torch.cuda.device(dev):
                 plan = self._plans[key] = E.FpnPlan(B, shapes, self.in_channels, prec, dev)
-        feats = [t.contiguous() if t.dtype in E.OUT_CODE else t.contiguous().float() for t in inputs]
-        with torch.cuda.device(dev):
-            return tuple(plan.run(feats, pk))
+        return plan, pk, [t.contiguous() if t.dtype in E.OUT_CODE else t.contiguous().float() for t in inputs]
 
 
 MODELS.register_module(module=FPN, force=True)       # this package's registry only: mmdet's own FPN stays mmdet's

@@ -156,6 +156,12 @@ class SemanticFPNWrapper(nn.Module):
     def _forward_native(self, inputs, dev, B, shapes, planes):
         """`forward`'s inference branch on the native plan: the pack keyed on the parameter versions exactly as `_pack` is, one
         NativeNeckPlan per cfg, the host-computed positional encoding (the Python path's bits)"""
+        plan, pk, add, pos_level = self._native_plan(dev, B, shapes)
+        with torch.cuda.device(dev):
+            return plan.run([t.float().contiguous() for t in inputs[:4]], pk, self.groups, add, pos_level, to_planes=planes)
+
+    def _native_plan(self, dev, B, shapes):
+        """(the NativeNeckPlan of B frames of these level sizes, its pack, the positional encoding, its level)"""
         pos_level = self.cat_coors_level if self.pos_cfg is not None else -1
         ts, cfg = self._plan_cfg(B, shapes, dev, self.precision, pos_level)
         pkey = (str(dev), self.precision, _lib.param_versions(self))
@@ -169,8 +175,7 @@ class SemanticFPNWrapper(nn.Module):
             with torch.cuda.device(dev):
                 plan = self._nplans[key] = E.NativeNeckPlan(pk, B, shapes, dev, pos_level, ts, cfg=cfg)
         add = self._posenc(*shapes[self.cat_coors_level], dev) if self.pos_cfg is not None else None
-        with torch.cuda.device(dev):
-            return plan.run([t.float().contiguous() for t in inputs[:4]], pk, self.groups, add, pos_level, to_planes=planes)
+        return plan, pk, add, pos_level
 
     # ---- forward (semantic_fpn.py:198-235) ---------------------------------------------------------------------
     def forward_planes(self, inputs):
@@ -219,6 +224,16 @@ class SemanticFPNWrapper(nn.Module):
             if _planes or self.num_aux_convs > 0:
                 return outs
             return [outs[0]] if self.return_list else outs[0]
+        plan, pk, add, G = self._python_plan(dev, B, shapes)
+        outs = plan.run([t.float().contiguous() for t in inputs[:4]], pk, G, add, self.cat_coors_level, to_planes=_planes)
+        if _planes:
+            return outs
+        if self.num_aux_convs > 0:
+            return outs
+        return [outs[0]] if self.return_list else outs[0]
+
+    def _python_plan(self, dev, B, shapes):
+        """(the NeckPlan of B frames of these level sizes, the packed parameters, the positional encoding, the groups)"""
         pk, prec, G = self._pack(dev), E.KHEAD_PREC[self.precision], self.groups
         ts, cfg = self._plan_cfg(B, shapes, dev, prec)
         key = (bytes(cfg), str(dev))
@@ -226,12 +241,35 @@ class SemanticFPNWrapper(nn.Module):
         if plan is None:
             plan = self._plans[key] = E.NeckPlan(B, shapes, prec, dev, tower_streams=ts, groups=G, num_outs=1 + self.num_aux_convs)
         add = self._posenc(*shapes[self.cat_coors_level], dev) if self.pos_cfg is not None else None
-        outs = plan.run([t.float().contiguous() for t in inputs[:4]], pk, G, add, self.cat_coors_level, to_planes=_planes)
-        if _planes:
-            return outs
-        if self.num_aux_convs > 0:
-            return outs
-        return [outs[0]] if self.return_list else outs[0]
+        return plan, pk, add, G
+
+    def forward_from_fpn(self, fpn, stages, planes=False, want_levels=False):
+        """`forward(fpn(stages))` -- `forward_planes(fpn(stages))` with `planes` -- with the direct hand-over: the FPN's output
+        convolutions write this neck's conv input planes themselves (ph_fpn_output_planes, the positional encoding included), so the
+        fp32 levels are not written and read back on the way; the same bits.  `fpn`: a fpn.FPN of the same precision.  With
+        `want_levels` the fp32 levels are written too and the result is (outputs, levels) -- the track head's RoIAlign takes them.
+        Python or native neck plan (`use_native_plan`).  Inference only: training goes through `forward`."""
+        if (self.training or fpn.training) and torch.is_grad_enabled():
+            raise _lib.PolyheadError("SemanticFPNWrapper.forward_from_fpn is the inference hand-over; in training mode with grad enabled "
+                                     "call forward(fpn(stages))")
+        if planes and self.num_aux_convs != 2:
+            raise NotImplementedError("planes need the three outputs (num_aux_convs = 2)")
+        if fpn.precision != self.precision:
+            raise _lib.PolyheadError(f"forward_from_fpn: the FPN's precision ({fpn.precision}) differs from the neck's ({self.precision})")
+        fplan, fpk, feats = fpn._plan_of(stages)
+        dev, B, shapes = feats[0].device, feats[0].shape[0], fplan.shapes
+        if self.native_plan:
+            plan, pk, add, pos_level = self._native_plan(dev, B, shapes)
+        else:
+            plan, pk, add, _ = self._python_plan(dev, B, shapes)
+            pos_level = self.cat_coors_level
+        neck = E.NeckHandoff(plan, pk, self.groups, add, pos_level, to_planes=planes)
+        with torch.cuda.device(dev):
+            levels = fplan.run(feats, fpk, neck=neck, want_levels=want_levels)
+            outs = neck.finish()
+        if not planes and self.num_aux_convs == 0:
+            outs = [outs[0]] if self.return_list else outs[0]
+        return (outs, tuple(levels)) if want_levels else outs
 
 
 register_everywhere(SemanticFPNWrapper)
