@@ -434,6 +434,28 @@ int ph_gn_train_fwd(const float* y, const float* gamma, const float* beta, int g
 int ph_gn_train_bwd(const float* y, const float* stats, const float* gamma, const float* beta, int groups, const float* dyA,
                     const float* dyB, float* dx, float* dgamma, float* dbeta, double* partial, int B, int C, int64_t HW, void* stream);
 int ph_hard_count(const float* logits, float* out, int64_t rows, int64_t HW, void* stream);
+/* FPN in training (fp32 NCHW, csrc/ph_fpntrain.hip; mmdet/models/necks/fpn.py:151-203): what the lateral 1x1 convolutions, the
+ * top-down pathway and the biased 3x3 output convolutions need beyond the calls above.  Launch-only, no atomics, fixed-order sums.
+ * map_x_map_t_wide : ph_map_x_map_t_ex without binarize_g for any K in 1 .. 4096 (K tiles of 256 columns; for K <= 256 and the
+ *                same nsplit the same bits): O[b][m][k] = sum_p G[b][m][p] X[b][k][p], rowsum [B][M] = sum_p G (both null or both given with rs_partial
+ *                [B][nsplit][M]), sum_batch != 0: out [M][K] and rowsum [M] summed over the images too -- the weight and bias
+ *                gradients of a lateral convolution.  nsplit from ph_map_x_map_t_wide_nsplit (the workgroup budget divided by row
+ *                passes and K tiles, at least 256 pixels per split); partial holds B * nsplit * M * K floats.
+ * nearest_up_add : in place fine[pl][y][x] += coarse[pl][y * Hc / H][x * Wc / W] (F.interpolate nearest to the finer size + add);
+ *                H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1 (ph_fpn_lateral's rule: there the source index is y >> 1).
+ * nearest_up_add_bwd : its transpose as a gather: g_coarse[pl][Y][X] (accumulate != 0: the value already there, else 0) + g_fine[2Y][2X]
+ *                + g_fine[2Y][2X+1] + g_fine[2Y+1][2X] + g_fine[2Y+1][2X+1], in-bounds terms only, added in that order.
+ * nchw_bias_add : in place y[b][c][p] += bias[c].   nchw_channel_sums : out[c] = sum_b sum_p g[b][c][p], accumulated in fp64 in a
+ *                fixed order; partial: C * B * ph_nchw_channel_sums_nsplit(HW) doubles of scratch. */
+int ph_map_x_map_t_wide_nsplit(int B, int M, int K, int64_t HW);
+int ph_map_x_map_t_wide(const float* G, const float* X, float* partial, float* out, int B, int M, int K, int64_t HW, int nsplit,
+                        float* rs_partial, float* rowsum, int sum_batch, void* stream);
+int ph_nearest_up_add(float* fine, const float* coarse, int64_t planes, int H, int W, int Hc, int Wc, void* stream);
+int ph_nearest_up_add_bwd(const float* g_fine, float* g_coarse, int64_t planes, int H, int W, int Hc, int Wc, int accumulate,
+                          void* stream);
+int ph_nchw_bias_add(float* y, const float* bias, int B, int C, int64_t HW, void* stream);
+int ph_nchw_channel_sums_nsplit(int64_t HW);
+int ph_nchw_channel_sums(const float* g, double* partial, float* out, int B, int C, int64_t HW, void* stream);
 
 /* ---- N4: targets + losses + d(losses)/d(predictions) of one head / stage in ONE call, from DESCRIPTORS (csrc/ph_loss.hip) ------
  * Replaces `get_targets` + `loss` of both heads on the training path (kernel_update_head.py:355-591, kernel_head.py:456-698): every

@@ -345,6 +345,13 @@ SIGNATURES = {
     "ph_gn_train_fwd": (C.c_int, [_P, _P, _P, _I, C.c_float, _P, _P, _P, _P, _P, _I, _I, _L, _P]),
     "ph_gn_train_bwd": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _L, _P]),
     "ph_hard_count": (C.c_int, [_P, _P, _L, _L, _P]),
+    "ph_map_x_map_t_wide_nsplit": (C.c_int, [_I, _I, _I, _L]),
+    "ph_map_x_map_t_wide": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P, _P, _I, _P]),
+    "ph_nearest_up_add": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P]),
+    "ph_nearest_up_add_bwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "ph_nchw_bias_add": (C.c_int, [_P, _P, _I, _I, _L, _P]),
+    "ph_nchw_channel_sums_nsplit": (C.c_int, [_L]),
+    "ph_nchw_channel_sums": (C.c_int, [_P, _P, _P, _I, _I, _L, _P]),
     "ph_train_losses_scratch_bytes": (C.c_size_t, [_P]),
     "ph_train_losses": (C.c_int, [_P] * 24 + [_Z, _P]),
     "ph_gemm32": (C.c_int, [_P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P]),

@@ -147,6 +147,12 @@ int ph_gn_sum_planes_k(const PhNeckKnobs& kn, const float* const* ys, const floa
 int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
                   int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream);
 
+// the map x map^T product of the training path (ph_train.hip) under its public names: ph_map_x_map_t_ex (wide = 0: K <= 256) and
+// ph_map_x_map_t_wide (ph_fpntrain.hip; wide != 0: K <= 4096 in tiles of 256 columns); row passes of M rows per image and split
+int ph_map_x_map_t_k(const char* fn, int wide, const float* G, const float* X, float* partial, float* out, int B, int M, int K, int64_t HW,
+                     int nsplit, int binarize_g, float* rs_partial, float* rowsum, int sum_batch, void* stream);
+int ph_map_x_map_t_passes(int M);
+
 // device-count forms of the association step's kernels (ph_track.hip) for the native association plan (ph_assocplan.hip): B frames per
 // launch, the grids sized for `cap` RoIs per frame, every workgroup reading its frame's count from the things tables on the device
 // (int32 [B][words], word 0 = the count, words 1 .. cap = the segment ids) and returning when it lies beyond it.  The public entry

@@ -385,6 +385,10 @@ __global__ __launch_bounds__(512) void k_rows_x_map_lds(const float* __restrict_
 // (80-byte pitch: the 16 rows x 16 bytes of a fragment read hit 16 distinct bank groups) -> fragments by ds_read_b128.
 // (First version: every wave converted its own fragments straight from global memory, G four times over: 1.1 - 1.5 TB/s.)
 // partial [B][nsplit][M][K]; a fixed-order second pass sums the splits.
+// K > 256 (ph_map_x_map_t_wide, csrc/ph_fpntrain.hip): `ktiles` tiles of 256 columns share grid.z with the row passes (tile
+// fastest); a tile stages X rows k0 .. k0 + 255 of the image's K rows and writes its columns in place into the [M][K] record --
+// the last tile is ragged, guarded per row like K < 256 always was.  Tile 0 alone writes the row sums.  ktiles = 1 is the
+// kernel as it was, bit for bit.
 constexpr int MXM_RT = 10;                 // 160 rows of G per pass
 constexpr int MXM_ROWS = 448;               // 160 rows of G + 256 rows of X, rounded up to the 64 rows one staging pass covers
 constexpr int MXM_PITCH = 40;              // uint16 elements per LDS row: 32 pixels + 16 bytes of padding
@@ -398,16 +402,18 @@ struct TapShift {
 };
 template <bool VEC, bool BIN>
 __global__ __launch_bounds__(512) void k_map_x_mapT(const float* __restrict__ G, const float* __restrict__ X, float* __restrict__ partial,
-                                                       int M, int K, int64_t HW, int64_t chunk, float* __restrict__ rs_partial, const TapShift sh) {
+                                                       int M, int K, int64_t HW, int64_t chunk, float* __restrict__ rs_partial, const TapShift sh,
+                                                       int ktiles) {
     __shared__ __attribute__((aligned(16))) uint16_t lds[2][MXM_ROWS][MXM_PITCH];     // [hi | lo][row][pixel]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     const int s = blockIdx.x, nsplit = gridDim.x, b = blockIdx.y;
-    const int m0 = blockIdx.z * (MXM_RT * 16);
+    const int kt = blockIdx.z % ktiles, k0 = kt * 256, Kt = min(256, K - k0);     // this tile's columns: k0 .. k0 + Kt - 1
+    const int m0 = (blockIdx.z / ktiles) * (MXM_RT * 16);
     const int64_t pa = s * chunk, pe = min(HW, pa + chunk);
     const float* Gb = G + ((int64_t)b * M + m0) * HW;
     const int64_t HWx = sh.on ? (int64_t)sh.Hi * sh.Wi : HW;
-    const float* Xb = X + (int64_t)b * K * HWx;
+    const float* Xb = X + ((int64_t)b * K + k0) * HWx;
     const int r0 = tid >> 3, p4 = (tid & 7) * 4;
     // row j of this thread: LDS row r0 + 32 j; rows < 160 are G rows m0 + .., the others X rows
     float4 st[MXM_LOADS];
@@ -418,7 +424,7 @@ __global__ __launch_bounds__(512) void k_map_x_mapT(const float* __restrict__ G,
             const int row = r0 + 64 * j;
             const bool isg = row < MXM_RT * 16;
             const int rr = isg ? row : row - MXM_RT * 16;
-            const bool ok = isg ? (m0 + rr < M) : (rr < K);
+            const bool ok = isg ? (m0 + rr < M) : (rr < Kt);
             const float* src = (isg ? Gb : Xb) + (int64_t)rr * HW + p + p4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ok && sh.on && !isg) {          // a tap of a 3x3 conv: every pixel of the step computes its own source address
@@ -502,10 +508,10 @@ __global__ __launch_bounds__(512) void k_map_x_mapT(const float* __restrict__ G,
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = m0 + (wr * WRT + r) * 16 + g * 4 + i;
-                if (r < nrt && m < M && k < K) out[(int64_t)m * K + k] = acc[r][t][i];
+                if (r < nrt && m < M && k < Kt) out[(int64_t)m * K + k0 + k] = acc[r][t][i];
             }
         }
-    if (rs_partial) {           // the 8 threads of a row are 8 adjacent lanes: xor-1/2/4 butterfly, lane 0 of the group writes
+    if (rs_partial && kt == 0) {           // the 8 threads of a row are 8 adjacent lanes: xor-1/2/4 butterfly, lane 0 of the group writes
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             float v = rsum[j];
@@ -632,19 +638,27 @@ extern "C" int ph_map_x_map_t_nsplit(int B, int M, int64_t HW) {
     return (int)want;
 }
 
-extern "C" int ph_map_x_map_t_ex(const float* G, const float* X, float* partial /* [B][nsplit][M][K] */, float* out /* [B][M][K] */, int B,
-                                int M, int K, int64_t HW, int nsplit, int binarize_g, float* rs_partial /* [B][nsplit][M] or null */,
-                                float* rowsum /* [B][M] or null */, int sum_batch /* out [M][K], rowsum [M]: summed over the images too */,
-                                void* stream) {
-    PH_CHECK_ARG((rs_partial == nullptr) == (rowsum == nullptr), "rs_partial and rowsum go together");
-    PH_CHECK_ARG(G && X && partial && out && B > 0 && M > 0 && K > 0 && K <= 256 && HW > 0 && nsplit >= 1, "bad pointer or size (K <= 256)");
+// the body of ph_map_x_map_t_ex and of ph_map_x_map_t_wide (csrc/ph_fpntrain.hip): `fn` the public name, `wide` != 0: K up to 4096 in
+// tiles of 256 columns, else K <= 256 (one tile: the launch as it always was)
+int ph_map_x_map_t_k(const char* fn, int wide, const float* G, const float* X, float* partial /* [B][nsplit][M][K] */, float* out /* [B][M][K] */,
+                     int B, int M, int K, int64_t HW, int nsplit, int binarize_g, float* rs_partial /* [B][nsplit][M] or null */,
+                     float* rowsum /* [B][M] or null */, int sum_batch /* out [M][K], rowsum [M]: summed over the images too */, void* stream) {
+    PH_CHECK_ARG_AS(fn, (rs_partial == nullptr) == (rowsum == nullptr), "rs_partial and rowsum go together");
+    if (wide)
+        PH_CHECK_ARG_AS(fn, G && X && partial && out && B > 0 && B <= 65535 && M > 0 && K > 0 && K <= 4096 && HW > 0 && nsplit >= 1,
+                        "bad pointer or size (1 <= K <= 4096, B <= 65535)");
+    else
+        PH_CHECK_ARG_AS(fn, G && X && partial && out && B > 0 && M > 0 && K > 0 && K <= 256 && HW > 0 && nsplit >= 1, "bad pointer or size (K <= 256)");
+    const int ktiles = (K + 255) / 256;
+    const int64_t zdim = (int64_t)(((M + 15) / 16 + MXM_RT - 1) / MXM_RT) * ktiles;
+    PH_CHECK_ARG_AS(fn, zdim <= 65535, "M too large: row passes x K tiles exceed the grid");
     int64_t chunk = (HW + nsplit - 1) / nsplit;
     chunk = (chunk + 31) / 32 * 32;
     const bool vec = (HW % 4) == 0 && (((uintptr_t)G | (uintptr_t)X) & 15) == 0;
-    const dim3 grid(nsplit, B, ((M + 15) / 16 + MXM_RT - 1) / MXM_RT);
+    const dim3 grid(nsplit, B, (unsigned)zdim);
     hipStream_t s = (hipStream_t)stream;
     const TapShift sh{};
-#define PH_MXM(V, Bn) hipLaunchKernelGGL((k_map_x_mapT<V, Bn>), grid, dim3(512), 0, s, G, X, partial, M, K, HW, chunk, rs_partial, sh)
+#define PH_MXM(V, Bn) hipLaunchKernelGGL((k_map_x_mapT<V, Bn>), grid, dim3(512), 0, s, G, X, partial, M, K, HW, chunk, rs_partial, sh, ktiles)
     if (vec) { if (binarize_g) PH_MXM(true, true); else PH_MXM(true, false); }
     else { if (binarize_g) PH_MXM(false, true); else PH_MXM(false, false); }
 #undef PH_MXM
@@ -659,6 +673,13 @@ extern "C" int ph_map_x_map_t_ex(const float* G, const float* X, float* partial 
         PH_CHECK_LAUNCH();
     }
     return PH_OK;
+}
+
+int ph_map_x_map_t_passes(int M) { return ((M + 15) / 16 + MXM_RT - 1) / MXM_RT; }
+
+extern "C" int ph_map_x_map_t_ex(const float* G, const float* X, float* partial, float* out, int B, int M, int K, int64_t HW, int nsplit,
+                                int binarize_g, float* rs_partial, float* rowsum, int sum_batch, void* stream) {
+    return ph_map_x_map_t_k("ph_map_x_map_t_ex", 0, G, X, partial, out, B, M, K, HW, nsplit, binarize_g, rs_partial, rowsum, sum_batch, stream);
 }
 
 extern "C" int ph_map_x_map_t(const float* G, const float* X, float* partial, float* out, int B, int M, int K, int64_t HW, int nsplit,
@@ -714,8 +735,8 @@ extern "C" int ph_conv3x3_wgrad(const float* dY /* [B][M][Ho][Wo] */, const floa
     const int64_t MK = (int64_t)M * K;
     for (int tap = 0; tap < 9; ++tap) {
         const TapShift sh{1, Hi, Wi, Wo, stride, tap / 3, tap % 3};
-        if (vec) hipLaunchKernelGGL((k_map_x_mapT<true, false>), grid, dim3(512), 0, s, dY, X, partial, M, K, HW, chunk, (float*)nullptr, sh);
-        else hipLaunchKernelGGL((k_map_x_mapT<false, false>), grid, dim3(512), 0, s, dY, X, partial, M, K, HW, chunk, (float*)nullptr, sh);
+        if (vec) hipLaunchKernelGGL((k_map_x_mapT<true, false>), grid, dim3(512), 0, s, dY, X, partial, M, K, HW, chunk, (float*)nullptr, sh, 1);
+        else hipLaunchKernelGGL((k_map_x_mapT<false, false>), grid, dim3(512), 0, s, dY, X, partial, M, K, HW, chunk, (float*)nullptr, sh, 1);
         hipLaunchKernelGGL(k_sum_splits, dim3((unsigned)((MK + 255) / 256)), dim3(256), 0, s, partial, taps_out + tap * MK, nsplit * B, MK, 1);
     }
     PH_CHECK_LAUNCH();

@@ -6,9 +6,10 @@ Same constructor keywords and the reference's 16 state_dict keys (`lateral_convs
 `fpn_convs.{i}.conv.{weight,bias}`).  Inference runs in libpolyhead (csrc/ph_fpn.hip + the neck's 3x3 kernel): the laterals read the
 backbone's NCHW maps as they are (fp32, bf16 or fp16) and write channels-last 16-bit planes, the 3x3 convolutions run on those.
 
-Training the FPN stays torch's job, like the backbone's: in training mode with grad enabled `forward` runs the reference's
-statements on the module's own parameters with torch ops (`F.conv2d`, `F.interpolate`), on whatever device the inputs live.  A
-training form on the library's kernels is a follow-up."""
+Training: in training mode with grad enabled `forward` runs the reference's statements on the module's own parameters with torch ops
+(`F.conv2d`, `F.interpolate`), on whatever device the inputs live -- the default.  `train_on_device()` switches that branch to the
+library's own autograd nodes (`train.fpn_forward_train`: csrc/ph_fpntrain.hip + the training kernels of the neck), fp32 NCHW on
+the GPU, whose gradients are summed in a fixed order; it is opt-in because it is not the faster of the two."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -66,6 +67,7 @@ class FPN(nn.Module):
         self.lateral_convs = nn.ModuleList([_Conv(c, 256, 1) for c in in_channels])
         self.fpn_convs = nn.ModuleList([_Conv(256, 256, 3) for _ in in_channels])
         self.precision = "fp32"
+        self.device_training = False
         self._packs, self._plans = {}, {}
 
     def init_weights(self):
@@ -79,6 +81,12 @@ class FPN(nn.Module):
         assert precision in E.PREC
         self.precision = precision
         self._packs.clear(); self._plans.clear()
+
+    def train_on_device(self, flag=True):
+        """training-mode `forward` on the library's nodes (`train.fpn_forward_train`) instead of torch ops; off by default.  On that
+        path the stages must live on the GPU and the parameters be fp32 (`PolyheadError` names the argument otherwise)."""
+        self.device_training = bool(flag)
+        return self
 
     # ---- packed parameters: keyed on the parameter versions (load_state_dict / an optimizer step after a first forward re-pack)
     def _pack(self, dev):
@@ -107,6 +115,9 @@ class FPN(nn.Module):
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)
         if self.training and torch.is_grad_enabled():
+            if self.device_training:
+                from .train import fpn_forward_train
+                return fpn_forward_train(self, inputs)
             return self._forward_torch(inputs)
         plan, pk, feats = self._plan_of(inputs)
         with torch.cuda.device(feats[0].device):

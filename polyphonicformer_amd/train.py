@@ -16,6 +16,8 @@ libpolyhead kernel, forward and backward; torch is the autograd bookkeeping betw
     as in the inference path (pooling and the dynamic convolution are linear in it), gradients included;
   * `_Upsample2x`; `_Objective`: a head's or stage's losses with d(losses)/d(predictions) from the loss kernels
     (csrc/ph_loss.hip);
+  * in front of the neck, on request (`fpn_forward_train`, `VideoTrainStep(fpn=...)`): the FPN as `_Lateral`, `_NearestUpAdd` and
+    `_Conv3x3Bias` nodes (csrc/ph_fpntrain.hip), so that the step starts at the backbone stages and ends with their gradients;
   * the discrete parts (Hungarian assignment -- scipy on the host, or `device_assign`: csrc/ph_assign.hip --, targets) in between.
 
 The result is checked against the reference's own forward + autograd backward (tests/golden/train_step.npz:
@@ -564,6 +566,146 @@ def neck_forward_train(neck, inputs):
     return list(res)
 
 
+# ---- FPN in training: backbone stages -> the four pyramid levels as differentiable libpolyhead nodes (csrc/ph_fpntrain.hip) ------
+def map_x_mapT_wide(G, X, out=None, rowsum=None, sum_batch=False):
+    """`map_x_mapT` without binarisation for K up to 4096 (`ph_map_x_map_t_wide`: K tiles of 256 columns); for K <= 256 the same bits"""
+    G, X = _gpu32(G, "G"), _gpu32(X, "X")
+    B, M = G.shape[:2]
+    K = X.shape[1]
+    HW = X[0, 0].numel()
+    assert G[0, 0].numel() == HW and X.shape[0] == B
+    lib = _lib.load()
+    ns = lib.ph_map_x_map_t_wide_nsplit(B, M, K, HW)
+    part = torch.empty((B, ns, M, K), dtype=torch.float32, device=X.device)
+    Bo = 1 if sum_batch else B
+    if out is None:
+        out = torch.empty((M, K) if sum_batch else (B, M, K), dtype=torch.float32, device=X.device)
+    assert out.is_contiguous() and out.numel() == Bo * M * K and out.dtype == torch.float32
+    rsp = None
+    if rowsum is not None:
+        assert rowsum.is_contiguous() and rowsum.numel() == Bo * M and rowsum.dtype == torch.float32
+        rsp = torch.empty((B, ns, M), dtype=torch.float32, device=X.device)
+    _lib.check(lib.ph_map_x_map_t_wide(_lib.ptr(G), _lib.ptr(X), _lib.ptr(part), _lib.ptr(out), B, M, K, HW, ns, _lib.ptr(rsp),
+                                       _lib.ptr(rowsum), int(sum_batch), _lib.stream_ptr()), "ph_map_x_map_t_wide")
+    return out
+
+
+def nearest_up_add(fine, coarse):
+    """in place: fine += F.interpolate(coarse, size=fine.shape[2:], mode='nearest'); both fp32 contiguous [B, C, h, w] on the GPU"""
+    (B, Cn, H, W), (Hc, Wc) = fine.shape, coarse.shape[2:]
+    assert fine.is_contiguous() and coarse.is_contiguous() and fine.dtype == coarse.dtype == torch.float32 and coarse.shape[:2] == (B, Cn)
+    _lib.check(_lib.load().ph_nearest_up_add(_lib.ptr(fine), _lib.ptr(coarse), B * Cn, H, W, Hc, Wc, _lib.stream_ptr()), "ph_nearest_up_add")
+    return fine
+
+
+def nearest_up_add_bwd(g_fine, g_coarse, accumulate=True):
+    """the transpose of `nearest_up_add`: g_coarse (+)= the sum of its up to four fine pixels, gathered in a fixed order"""
+    (B, Cn, H, W), (Hc, Wc) = g_fine.shape, g_coarse.shape[2:]
+    assert g_fine.is_contiguous() and g_coarse.is_contiguous() and g_fine.dtype == g_coarse.dtype == torch.float32
+    assert g_coarse.shape[:2] == (B, Cn)
+    _lib.check(_lib.load().ph_nearest_up_add_bwd(_lib.ptr(g_fine), _lib.ptr(g_coarse), B * Cn, H, W, Hc, Wc, int(accumulate),
+                                                 _lib.stream_ptr()), "ph_nearest_up_add_bwd")
+    return g_coarse
+
+
+def nchw_bias_add(y, bias):
+    """in place: y[b, c] += bias[c]"""
+    B, Cn = y.shape[:2]
+    assert y.is_contiguous() and y.dtype == torch.float32 and bias.is_contiguous() and bias.dtype == torch.float32 and bias.numel() == Cn
+    _lib.check(_lib.load().ph_nchw_bias_add(_lib.ptr(y), _lib.ptr(bias), B, Cn, y[0, 0].numel(), _lib.stream_ptr()), "ph_nchw_bias_add")
+    return y
+
+
+def nchw_channel_sums(g):
+    """[C]: sum over images and pixels of g [B, C, *spatial], accumulated in fp64 in a fixed order"""
+    g = _gpu32(g, "g")
+    B, Cn = g.shape[:2]
+    HW = g[0, 0].numel()
+    lib = _lib.load()
+    part = torch.empty((Cn, B, lib.ph_nchw_channel_sums_nsplit(HW)), dtype=torch.float64, device=g.device)
+    out = torch.empty((Cn,), dtype=torch.float32, device=g.device)
+    _lib.check(lib.ph_nchw_channel_sums(_lib.ptr(g), _lib.ptr(part), _lib.ptr(out), B, Cn, HW, _lib.stream_ptr()), "ph_nchw_channel_sums")
+    return out
+
+
+class _Lateral(torch.autograd.Function):
+    """F.conv2d(X, W [M, K, 1, 1], bias) (fpn.py:158-161): `ph_rows_x_map_ex` with the bias in its epilogue; backward: the input
+    gradient is the same product on W^T (only where the stage asks for one), the weight and bias gradients ONE wide map x map^T
+    pass over (dL/dY, X) summed over the batch"""
+
+    @staticmethod
+    def forward(ctx, X, W, bias):
+        X, Wd, bd = _gpu32(X, "X"), _param32(W, "lateral conv weight"), _param32(bias, "lateral conv bias")
+        B = X.shape[0]
+        Y = rows_x_map(Wd.flatten(1)[None], X, bias=bd[None].expand(B, -1))
+        ctx.save_for_backward(X, Wd)
+        return Y
+
+    @staticmethod
+    def backward(ctx, gY):
+        X, W = ctx.saved_tensors
+        gY = _gpu32(gY, "grad")
+        gX = gW = gb = None
+        if ctx.needs_input_grad[0]:
+            gX = rows_x_map(W.flatten(1).t()[None], gY)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gb = torch.empty((W.shape[0],), dtype=torch.float32, device=X.device)
+            gW = map_x_mapT_wide(gY, X, rowsum=gb, sum_batch=True).view(W.shape)
+        return gX, gW, gb
+
+
+class _NearestUpAdd(torch.autograd.Function):
+    """the top-down pathway (fpn.py:164-175) on the four lateral maps, in place: level i - 1 += nearest(level i), from the coarsest
+    down.  Backward runs the other way, from level 0 up: each coarse level's own gradient takes the gather of the (finished) finer
+    one's, so the four results are the gradients of the four laterals and nothing is added outside the kernel."""
+
+    @staticmethod
+    def forward(ctx, *lat):
+        for i in range(len(lat) - 1, 0, -1):
+            nearest_up_add(lat[i - 1], lat[i])
+        ctx.mark_dirty(*lat[:-1])
+        return lat
+
+    @staticmethod
+    def backward(ctx, *gs):
+        gs = [_gpu32(g, "grad") for g in gs]
+        out = [gs[0]]
+        for i in range(1, len(gs)):
+            out.append(nearest_up_add_bwd(out[i - 1], gs[i].clone(), accumulate=True))
+        return tuple(out)
+
+
+class _Conv3x3Bias(torch.autograd.Function):
+    """an FPN output convolution (fpn.py:177-179): `_Conv3x3` at stride 1 with the bias added in place behind it; the bias gradient
+    is the channel sums of dL/dY"""
+
+    @staticmethod
+    def forward(ctx, X, W, bias):
+        bd = _param32(bias, "output conv bias")
+        return nchw_bias_add(_Conv3x3.forward(ctx, X, _param32(W, "output conv weight"), 1), bd)
+
+    @staticmethod
+    def backward(ctx, gY):
+        gX, gW, _ = _Conv3x3.backward(ctx, gY)
+        return gX, gW, (nchw_channel_sums(gY) if ctx.needs_input_grad[2] else None)
+
+
+def fpn_forward_train(fpn, stages):
+    """fpn.FPN.forward (mmdet/models/necks/fpn.py:151-203) for the shipped structure, every operation a differentiable libpolyhead
+    node: four lateral 1x1 convolutions with bias, the nearest top-down add, four 3x3 output convolutions with bias.  fp32 NCHW,
+    products on hi + lo bf16 MFMA like the neck's.  Gradients flow to the 16 parameters and to the stages that require one.
+    -> the four levels, a tuple"""
+    if len(stages) != len(fpn.lateral_convs):
+        raise _lib.PolyheadError(f"fpn_forward_train: {len(fpn.lateral_convs)} stages, got {len(stages)}")
+    for i, t in enumerate(stages):
+        Lo._gpu(t, f"inputs[{i}]")
+    for n, p in fpn.named_parameters():
+        _param32(p, n)
+    lat = [_Lateral.apply(stages[i].float(), m.conv.weight, m.conv.bias) for i, m in enumerate(fpn.lateral_convs)]
+    lat = _NearestUpAdd.apply(*lat)
+    return tuple(_Conv3x3Bias.apply(lat[i], m.conv.weight, m.conv.bias) for i, m in enumerate(fpn.fpn_convs))
+
+
 # ---- the video side: RoI features of the key frame and the track head's losses -------------------------------------------------
 class _RoIExtract(torch.autograd.Function):
     """SingleRoIExtractor + RoIAlign(7, sampling_ratio 2, aligned) of one image (track_head.roi_extract, fp32 output); backward:
@@ -1070,13 +1212,17 @@ class VideoTrainStep(_StepBase):
     them, the reference frame through `simple_test_rpn` + `simple_test_mask_preds` in eval mode under no_grad, the track branch
     (`video_track_branch`), the objective, ONE backward with bucketed gradient all-reduce over the parameters of neck, both heads and
     the track head.  track_train_cfg: dict(assigner=...) as the model config has it (MaskHungarianAssigner, FocalLossCost 2, DiceCost 4,
-    MaskCost 1) or a built assigner.  `rpn_head.localization_fpn` is None (the neck is this step's) or the same neck."""
+    MaskCost 1) or a built assigner.  `rpn_head.localization_fpn` is None (the neck is this step's) or the same neck.
+    fpn (a `fpn.FPN`, optional): the step starts one module earlier -- x / x_ref are the BACKBONE STAGES of the two frames, the key
+    frame's go through `fpn_forward_train`, the reference frame's through the FPN's eval plan under no_grad, the FPN's 16 parameters
+    are the first of `parameters()`, and the returned gradients are those of the key frame's stages (what the backbone's backward
+    takes).  Without it nothing changes."""
 
     def __init__(self, neck, rpn_head, roi_head, track_head, track_train_cfg, bucket_bytes=32 << 20, group=None, device_assign=False,
-                 strides=(4, 8, 16, 32), finest_scale=56):
+                 strides=(4, 8, 16, 32), finest_scale=56, fpn=None):
         from .assigner import build_assigner
-        self.neck, self.track_head = neck, track_head
-        self._trained = (neck, rpn_head, roi_head, track_head)
+        self.neck, self.track_head, self.fpn = neck, track_head, fpn
+        self._trained = (neck, rpn_head, roi_head, track_head) if fpn is None else (fpn, neck, rpn_head, roi_head, track_head)
         self.strides, self.finest_scale = tuple(strides), finest_scale
         if rpn_head.localization_fpn is not None and rpn_head.localization_fpn is not neck:
             raise ValueError("VideoTrainStep: rpn_head.localization_fpn must be None or the step's neck")
@@ -1086,15 +1232,21 @@ class VideoTrainStep(_StepBase):
             raise NotImplementedError("VideoTrainStep: track_train_cfg.assigner must be a one-to-one mask Hungarian assigner without depth cost")
         super().__init__(rpn_head, roi_head, bucket_bytes, group, device_assign)
 
-    def _reference_frame(self, x_ref, ref_metas):
-        """:186-191, 207-243 for the reference frame: neck, rpn head and roi head in eval mode under no_grad, at the grade the module API
-        runs; every module's `training` flag is put back"""
-        mods = [m for top in (self.neck, self.rpn, self.roi) for m in top.modules()]
+    def _reference_frame(self, x_ref, ref_metas, levels_out=None):
+        """:186-191, 207-243 for the reference frame: (FPN,) neck, rpn head and roi head in eval mode under no_grad, at the grade the
+        module API runs; every module's `training` flag is put back.  With an FPN x_ref are the frame's backbone stages and
+        `levels_out` (a list) receives its FPN levels: the eval plan's buffers, valid until that plan runs again"""
+        tops = [t for t in (self.fpn, self.neck, self.rpn, self.roi) if t is not None]
+        mods = [m for top in tops for m in top.modules()]
         flags = [m.training for m in mods]
         try:
-            for top in (self.neck, self.rpn, self.roi):
+            for top in tops:
                 top.eval()
             with torch.no_grad():
+                if self.fpn is not None:
+                    x_ref = list(self.fpn(x_ref))
+                    if levels_out is not None:
+                        levels_out[:] = x_ref
                 src = x_ref if self.rpn.localization_fpn is not None else self.neck(x_ref)
                 (pf, xf, mp, cs, _, df, dp, dpr, _) = self.rpn.simple_test_rpn(src, ref_metas)
                 return self.roi.simple_test_mask_preds(xf, pf, mp, cs, ref_metas, depth_preds=dpr, depth_feats=df, depth_proposal=dp, imgs_whwh=None)
@@ -1106,7 +1258,8 @@ class VideoTrainStep(_StepBase):
                          ref_gt_labels, ref_gt_instance_ids, pad_hw, backward=True, ref_img_metas=None):
         """x / x_ref: the FPN levels of the key and the reference frames; the ground truth as the reference has it at :185 (things and
         stuff split, at the assign resolution).  -> (losses: the 24 image losses + loss_track + loss_track_aux, objective, gradients of
-        the key frame's FPN levels: neck path + RoIAlign path).  The reference frame's levels get no gradient."""
+        the key frame's FPN levels: neck path + RoIAlign path).  The reference frame's levels get no gradient.  With the step's `fpn`:
+        x / x_ref are the backbone stages and the gradients returned are those of the key frame's stages."""
         return self._forward_backward(x, x_ref, img_metas, (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, gt_instance_ids),
                                       (ref_gt_masks, ref_gt_labels, ref_gt_instance_ids), pad_hw, backward, ref_img_metas)
 
@@ -1127,16 +1280,21 @@ class VideoTrainStep(_StepBase):
         prepared, else derived from the lists where the step first needs them"""
         lists, gt_instance_ids = key[:5], key[5]
         ref_gt_masks, ref_gt_labels, ref_gt_instance_ids = ref
-        x = self._leaves(x, "the FPN levels")
-        x_ref = self._leaves(x_ref, "the FPN levels", requires_grad=False)
+        what = "the FPN levels" if self.fpn is None else "the backbone stages"
+        x = self._leaves(x, what)
+        x_ref = self._leaves(x_ref, what, requires_grad=False)
 
         def forward():
-            feats = neck_forward_train(self.neck, x)                                                   # :185
+            lv, lv_ref = x, x_ref
+            if self.fpn is not None:
+                lv, lv_ref = fpn_forward_train(self.fpn, x), []
+            feats = neck_forward_train(self.neck, lv)                                                  # :185
             losses, last, cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
-            ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas)
+            ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas,
+                                             levels_out=None if self.fpn is None else lv_ref)
             gt = _step_gt(cache, False, *lists)                                                        # the soft masks (:259)
             rgt = ref_gt if ref_gt is not None else Lo.StepGT(ref_gt_masks, ref_gt_labels, None, None, None, False)
-            losses.update(video_track_branch(self.track_head, self.track_assigner, x, x_ref, last, ref_last, gt, rgt, gt_instance_ids,
+            losses.update(video_track_branch(self.track_head, self.track_assigner, lv, lv_ref, last, ref_last, gt, rgt, gt_instance_ids,
                                              ref_gt_instance_ids, pad_hw, self.roi.num_proposals, self.roi.num_thing_classes,
                                              self.device_assign, self.strides, self.finest_scale))
             return losses, list(cache.values()) + [rgt]
