@@ -1742,6 +1742,44 @@ int ph_gt_index_maps(const void* raw, int dtype, const uint16_t* raw_depth, int 
                      const int32_t* src_y_host, const int32_t* src_x_host, const int32_t* src_y, const int32_t* src_x, int Hc, int Wc, int Hp,
                      int Wp, float depth_div, float depth_max, const float* scale_mean, uint8_t* seg, float* depth, void* stream);
 
+/* ---- the image of the same frame from the file's bytes (csrc/ph_imgprep.hip): the reference's train_pipeline on the image
+ * (configs/_base_/datasets/cityscapes_dvps.py:8-21: bilinear resize on uint8, horizontal flip, crop, Normalize, Pad(size_divisor = 32),
+ * the transpose to CHW) and its test_pipeline (:23-41: Normalize, Pad, ImageToTensor) in one launch, ending at the tensor the backbone
+ * takes.  Like ph_gt_index_maps it takes TABLES, not a resize rule: the host composes resize, flip and crop into one two-tap table per
+ * axis and frame (image.bilinear_tables), with the augmentation parameters ph_gt_index_maps' tables are made of, so the image and the
+ * ground truth of a frame cannot disagree on geometry.
+ *   raw        DEVICE uint8 [frames][Hs][Ws][3], the image as decoded from the file, interleaved channels, any alignment.
+ *              Hs, Ws <= 32767, beyond it PH_EUNSUPPORTED
+ *   tab_y, tab_x   DEVICE int32 [frames][Hc][2] and [frames][Wc][2], 8-byte aligned.  Word 0 = i0 | i1 << 16: the two source rows /
+ *              columns of the output row / column; word 0 == -1: none, the pixel is pad (a frame smaller than the call's Hc x Wc).
+ *              Word 1 = w0 | w1 << 16: the two tap weights, each 0 .. 2048 (11 coefficient bits).  Both indices and both weights
+ *              travel: OpenCV's rule does not make i1 = i0 + 1 or w0 = 2048 - w1 in every case.  tab_y_host, tab_x_host: the same
+ *              words on the HOST, checked before anything is launched (PH_EINVAL: an index at or above Hs / Ws, a weight above 2048);
+ *              the caller keeps the two copies equal, and an index the kernel finds outside the file reads as none
+ *   mean, stdinv   HOST fp32 [3], finite; to_rgb 0 or 1.  With to_rgb = 1 output channel c reads input channel 2 - c, and mean /
+ *              stdinv index the OUTPUT channel, as mmcv.imnormalize does after its colour conversion
+ *   out        out_dtype PH_OUT_F32 or PH_OUT_BF16 (round to nearest even), aligned to its element; layout PH_IMG_NCHW
+ *              [frames][3][Hp][Wp] or PH_IMG_NHWC [frames][Hp][Wp][3] (the memory of a channels-last tensor of shape
+ *              [frames, 3, Hp, Wp]); Hp >= Hc, Wp >= Wc
+ * ARITHMETIC, exact by definition (S a source byte, a / b the weights of tab_x / tab_y; OpenCV's generic fixed-point INTER_LINEAR path
+ * for 8-bit images):
+ *     H0 = S[y0][x0][c] a0 + S[y0][x1][c] a1                                        (int32; H1 the same on row y1)
+ *     v  = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2               (0 .. 255 where a0 + a1 = b0 + b1 = 2048)
+ *     out = (float(v) - mean[c]) stdinv[c]                                          (fp32: one subtract, one multiply)
+ * and exactly +0.0 outside Hc x Wc and where a table word is -1: the reference pads AFTER Normalize, so the pad is zero in normalised
+ * units.  Identity tables (w0 = 2048, w1 = 0) return S itself, so the test pipeline, which does not resize, is the same code path.
+ * One launch: no allocation, no synchronisation, no atomics, no workspace, capturable.  ZEROING CONTRACT: none -- every word of the
+ * output is written, the pad included.  Two calls give the same bits; a frame's output does not depend on the other frames.  A wave
+ * writes 512 adjacent columns of one row, a lane 8 of them: 16-byte stores, contiguous from lane to lane in either layout, where Wp is a
+ * multiple of 16 bytes of elements (4 fp32, 8 bf16) and out is 16-byte aligned, element stores otherwise.  The source is read with
+ * unaligned 8-byte loads that stay inside [raw, raw + frames Hs Ws 3).  A bad argument returns its code before anything is launched,
+ * with ph_last_error_string naming it. */
+#define PH_IMGPREP_MAX_FRAMES 64
+enum { PH_IMG_NCHW = 0, PH_IMG_NHWC = 1 };
+int ph_image_prepare(const uint8_t* raw, int frames, int Hs, int Ws, const int32_t* tab_y_host, const int32_t* tab_x_host,
+                     const int32_t* tab_y, const int32_t* tab_x, int Hc, int Wc, int Hp, int Wp, const float* mean, const float* stdinv,
+                     int to_rgb, int out_dtype, int layout, void* out, void* stream);
+
 /* ---- the optimizer step: gradient clipping by the global L2 norm + AdamW over every tensor in ONE call (csrc/ph_optim.hip) ------
  * Replaces torch.nn.utils.clip_grad_norm_(max_norm, norm_type = 2) + torch.optim.AdamW.step (the schedule of every shipped config:
  * AdamW(lr = 2e-4, weight_decay = 0.05) behind grad_clip = dict(max_norm = 1, norm_type = 2)) without rewriting a gradient.

@@ -233,6 +233,9 @@ PH_GTSEG_MAX_KEYS, PH_GTSEG_ROW_WORDS, PH_GTSEG_TABLE_WORDS = 262144, 6, 1 + 254
 PH_GTSEG_I32, PH_GTSEG_U16 = 0, 1
 PH_GTSEG_ETOOMANY, PH_GTSEG_EUNMAPPED, PH_GTSEG_EOUTSIDE = 1, 2, 4
 PH_EINVAL, PH_EWORKSPACE = -1, -4
+# the image of the frame from the file's bytes (polyhead.h ph_image_prepare); its out_dtype is PH_OUT_F32 / PH_OUT_BF16
+PH_IMGPREP_MAX_FRAMES = 64
+PH_IMG_NCHW, PH_IMG_NHWC = 0, 1
 
 
 class TrackLossCfg(C.Structure):
@@ -497,6 +500,8 @@ SIGNATURES = {
     "ph_gt_segments": (C.c_int, [_P, _I, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     "ph_gt_index_maps": (C.c_int, [_P, _I, _P, _I, _I, _I, C.POINTER(C.c_int32), _I, _I, _I, _I, _P, C.POINTER(C.c_int32), _P, _P, _P, _P,
                                    _I, _I, _I, _I, C.c_float, C.c_float, C.POINTER(C.c_float), _P, _P, _P]),
+    "ph_image_prepare": (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float), _I, _I, _I,
+                                   _P, _P]),
     "ph_optim_workspace_bytes": (C.c_size_t, [_P, _I]),
     "ph_optim_step": (C.c_int, [C.POINTER(OptimCfg), _P, _P, _I, C.c_float, _P, _P, _P, _Z, _P]),
     "ph_optim_zero_grads": (C.c_int, [_P, _P, _I, _I, _P]),
