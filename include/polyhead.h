@@ -4,7 +4,7 @@
  * torch types.  Every entry point
  *   - returns 0 on success or a negative PH_E* code (never throws, see ph_last_error_string),
  *   - never allocates and never synchronises: the caller owns every buffer and passes the stream,
- *   - is thread-compatible (no mutable globals besides a thread-local error string).
+ *   - is thread-compatible (no mutable globals besides a thread-local error string and the atomic switch table below).
  *
  * The reference is 100 % Python: there is no FFI in it to mirror.  Each function
  * below therefore cites the reference *Python* lines whose device work it replaces; the Python
@@ -61,6 +61,34 @@ enum { PH_IN_F32_NCHW = 0, PH_IN_PLANES = 1 };   /* ph_khead_fused input_format 
 
 int         ph_version(void);
 const char* ph_last_error_string(void);
+
+/* ---- the library's switches -----------------------------------------------------------------
+ * Measurement and test switches of the public launch entry points: ONE process-wide table of integers, 0 = the
+ * built-in rule.  The table is filled from the environment exactly once, on the first use of any of them (a launch through one of
+ * the entry points named below, ph_get_switch or ph_set_switch), from the variable named with each id; after that the
+ * environment is never read again and a switch changes by ph_set_switch only.  PH_CONV_TH_NOW, the retired per-call spelling of
+ * PH_SWITCH_CONV_TILE_ROWS, is still honoured at that one read and, as before, wins over PH_CONV_TH when both are set.  A variable
+ * whose value ph_set_switch would refuse is ignored.
+ * Every entry is a relaxed atomic: a launch concurrent with a ph_set_switch sees the old or the new value, never a mix; a
+ * captured graph keeps the geometry it was captured with, whatever is set before its replay.  No native plan function
+ * (ph_decode_*, ph_khead_plan_*, ph_neck_plan_*, ph_fpn_plan_*, ph_assoc_plan_*, ...) consults the table: their choices are their
+ * cfg's fields.  ph_set_switch allocates nothing and launches nothing. */
+enum {
+    PH_SWITCH_CONV_WGS = 0,        /* PH_CONV_WGS: workgroups of ph_dynconv; >= 0 */
+    PH_SWITCH_UP2_WGS = 1,         /* PH_UP2_WGS: workgroups of ph_dynconv_up2[_wgs], over the caller's count; >= 0 */
+    PH_SWITCH_QUERY_NRT = 2,       /* PH_QUERY_NRT: 16-row blocks per workgroup of ph_query_stage[_counts]; >= 0 */
+    PH_SWITCH_QUERY_TIMELINE = 3,  /* PH_QUERY_TIMELINE: 1 = ph_query_stage[_counts] prints one workgroup's phase times (debug:
+                                      synchronises; the first such launch allocates the 128-byte stamp buffer); 0 or 1 */
+    PH_SWITCH_CONV_TILE_ROWS = 4,  /* PH_CONV_TH: output rows per tile of ph_conv_nhwc in the one-plane grades; 0, 2 or 4 */
+    PH_SWITCH_GNSUM_WGS = 5,       /* PH_GNSUM_WGS: workgroups per frame of ph_gn_sum_planes; >= 0 */
+    PH_SWITCH_CPLANES_TPW = 6,     /* PH_CPLANES_TPW: 64-pixel tiles per workgroup of ph_gn_apply's PH_GN_TO_CPLANES mode; >= 0 */
+    PH_SWITCH_PAN_GENERIC = 7,     /* PH_PAN_GENERIC (set to anything): 1 = ph_panoptic_argmax takes the generic kernel on the x4
+                                      geometry too; 0 or 1 */
+    PH_SWITCH_COUNT = 8
+};
+/* PH_EINVAL, with a message and nothing changed, on an id outside the enum or a value outside the id's range above */
+int ph_set_switch(int id, int value);
+int ph_get_switch(int id, int* value);
 
 /* ---- geometry helpers ------------------------------------------------------------------- */
 static inline int64_t ph_hw_padded(int64_t hw) { return (hw + 127) / 128 * 128; }
@@ -989,8 +1017,8 @@ int ph_khead_plan_timeouts(const ph_khead_plan* plan, void* stream);
  * synchronisation and no host read of device data in pack / posenc / create / run, every argument or geometry error returned
  * before the first launch.  No ph_neck_plan_* / ph_neck_pack* / ph_neck_posenc function reads the environment: the plan's
  * launches go through internal forms of ph_conv_nhwc / ph_gn_sum_planes / ph_gn_apply that take their launch knobs as arguments
- * (the public entry points keep reading PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_CPLANES_TPW; ph_neck_out_convs
- * has no knobs), and the Python side's PH_NECK_OUT2 / PH_NECK_C16 / PH_NECK_STREAMS arrive as the cfg's `fused_out` / `c16` /
+ * (the public entry points take theirs from the switch table: PH_SWITCH_CONV_TILE_ROWS / PH_SWITCH_GNSUM_WGS /
+ * PH_SWITCH_CPLANES_TPW; ph_neck_out_convs has no knobs), and the Python side's PH_NECK_OUT2 / PH_NECK_C16 / PH_NECK_STREAMS arrive as the cfg's `fused_out` / `c16` /
  * `tower_buffers` fields: engine.native_neck_cfg is the one place that reads them (PH_NECK_OUT2=0 -> fused_out PH_KNOB_OFF,
  * PH_NECK_C16=0 -> c16 PH_KNOB_OFF, PH_NECK_STREAMS=0 -> tower_buffers 0), and engine.NeckPlan takes its choices from
  * ph_neck_geometry_of of that cfg, so the Python plan and the native plan agree by construction.

@@ -1,5 +1,6 @@
 """ctypes binding of libpolyhead.so (include/polyhead.h).  The library is the ONLY compute path:
 if it is missing or fails to load this module raises -- there is no CPU or PyTorch fallback."""
+import contextlib
 import ctypes as C
 import os
 
@@ -17,6 +18,9 @@ PH_OUT_F32, PH_OUT_BF16, PH_OUT_F16 = 0, 1, 2
 PH_KERN_BF16_PLANES, PH_KERN_F16 = 0, 1
 PH_GN_TO_PLANES, PH_GN_UP2_PLANES, PH_GN_ACCUM, PH_GN_TO_NCHW, PH_GN_TO_CPLANES = 0, 1, 2, 3, 4
 PH_IN_F32_NCHW, PH_IN_PLANES = 0, 1
+
+# the library's switches (polyhead.h PH_SWITCH_*): position = id; `switches` below sets them by these names
+SWITCHES = ("conv_wgs", "up2_wgs", "query_nrt", "query_timeline", "conv_tile_rows", "gnsum_wgs", "cplanes_tpw", "pan_generic")
 
 W_NAMES = ["DYN", "INP", "IG", "UG", "FC", "QKV", "OUT", "FFN1", "FFN2", "H0A", "H0B", "CLS", "KERN"]
 V_NAMES = ["DYN_CNT", "DYN_B", "INP_B", "IG_B", "UG_B", "LN_IG_G", "LN_IG_B", "LN_UG_G", "LN_UG_B",
@@ -279,6 +283,8 @@ _P, _I, _L, _Z = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
 SIGNATURES = {
     "ph_version": (C.c_int, []),
     "ph_last_error_string": (C.c_char_p, []),
+    "ph_set_switch": (C.c_int, [_I, _I]),
+    "ph_get_switch": (C.c_int, [_I, C.POINTER(C.c_int)]),
     "ph_ingest_features": (C.c_int, [_P, _P, _I, _L, _I, _P]),
     "ph_binarize": (C.c_int, [_P, _L, _P, _I, _I, _L, _P]),
     "ph_pool": (C.c_int, [_P, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
@@ -538,6 +544,23 @@ def check(rc, what):
     if rc != 0:
         msg = load().ph_last_error_string()
         raise PolyheadError(f"{what} failed with code {rc}: {msg.decode() if msg else ''}")
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """sets library switches by name (SWITCHES) for the block and puts the values it found back afterwards:
+    `with _lib.switches(up2_wgs=7): ...`.  The table lives in the library alone (ph_get_switch reads it)"""
+    lib, old = load(), {}
+    try:
+        for name, v in values.items():
+            i, cur = SWITCHES.index(name), C.c_int()
+            check(lib.ph_get_switch(i, cur), "ph_get_switch")
+            check(lib.ph_set_switch(i, v), f"ph_set_switch({name}, {v})")
+            old[i] = cur.value
+        yield
+    finally:
+        for i, v in old.items():
+            check(lib.ph_set_switch(i, v), "ph_set_switch")
 
 
 def ptr(t):

@@ -106,18 +106,20 @@ int ph_pack_pieces(const char* fn, const PhPackTable& t, void* pack, unsigned ma
 #define PH_BIN_THR 0x1.8p-24f
 
 // ---- launch knobs of the decode kernels.  The public entry points (ph_dynconv, ph_dynconv_up2[_wgs], ph_query_stage[_counts])
-// fill them from environment variables -- geometry knobs and test switches -- and call the *_k forms below;
-// the native decode plan (ph_decode.hip) passes the defaults explicitly and so reads no environment at all.  KernelHead's post-neck
-// kernels (ph_khead.hip, ph_khead1.hip) have no knobs: their public entry points are what the native plans call.
+// fill them, by value and once per call, from the library's switch table (ph_api.hip, include/polyhead.h PH_SWITCH_*: read from
+// the environment once at first use, set by ph_set_switch after that) and call the *_k forms below; the native decode
+// plan (ph_decode.hip) passes the defaults explicitly and so consults neither.  KernelHead's post-neck kernels (ph_khead.hip,
+// ph_khead1.hip) have no knobs: their public entry points are what the native plans call.
+int ph_switch(int id);           // the current value of switch PH_SWITCH_<id>
 struct PhConvKnobs {
-    int wgs = 0;                 // PH_CONV_WGS: workgroups (0 = one per CU)
+    int wgs = 0;                 // PH_SWITCH_CONV_WGS: workgroups (0 = one per CU)
 };
 struct PhUp2Knobs {
-    int wgs = 0;                 // PH_UP2_WGS: overrides the caller's workgroup count (0 = keep it)
+    int wgs = 0;                 // PH_SWITCH_UP2_WGS: overrides the caller's workgroup count (0 = keep it)
 };
 struct PhQueryKnobs {
-    int nrt = 0;                             // PH_QUERY_NRT: row blocks per workgroup (0 = the launch's own choice)
-    unsigned long long* timeline = nullptr;  // PH_QUERY_TIMELINE=1: phase times of one workgroup (debug; synchronises)
+    int nrt = 0;                             // PH_SWITCH_QUERY_NRT: row blocks per workgroup (0 = the launch's own choice)
+    unsigned long long* timeline = nullptr;  // PH_SWITCH_QUERY_TIMELINE: phase times of one workgroup (debug; synchronises)
 };
 int ph_dynconv_k(const PhConvKnobs& kn, const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
                  int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out, void* logits_out,
@@ -131,12 +133,12 @@ int ph_query_stage_counts_k(const PhQueryKnobs& kn, const float* partial, int ns
                             size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases, void* stream);
 
 // launch knobs of the neck's kernels (ph_neck.hip), in the same way: the public ph_conv_nhwc / ph_gn_sum_planes /
-// ph_gn_apply fill them from PH_CONV_TH / PH_CONV_TH_NOW / PH_GNSUM_WGS / PH_CPLANES_TPW; the native neck plan
-// (ph_neckplan.hip) passes the defaults.  0 = the built-in rule
+// ph_gn_apply fill them from the switch table; the native neck and FPN plans (ph_neckplan.hip, ph_fpnplan.hip) pass the
+// defaults.  0 = the built-in rule
 struct PhNeckKnobs {
-    int conv_th = 0;             // PH_CONV_TH / PH_CONV_TH_NOW: forced output rows per conv tile (2 or 4; one-plane grades)
-    int gnsum_wgs = 0;           // PH_GNSUM_WGS: workgroups per frame of ph_gn_sum_planes
-    int cplanes_tpw = 0;         // PH_CPLANES_TPW: 64-pixel tiles per workgroup of ph_gn_apply's PH_GN_TO_CPLANES mode
+    int conv_th = 0;             // PH_SWITCH_CONV_TILE_ROWS: forced output rows per conv tile (2 or 4; one-plane grades)
+    int gnsum_wgs = 0;           // PH_SWITCH_GNSUM_WGS: workgroups per frame of ph_gn_sum_planes
+    int cplanes_tpw = 0;         // PH_SWITCH_CPLANES_TPW: 64-pixel tiles per workgroup of ph_gn_apply's PH_GN_TO_CPLANES mode
 };
 // rows per tile of a ph_conv_nhwc launch of this output size, grade and batch (2 or 4)
 int ph_conv_nhwc_tile_rows_k(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B);

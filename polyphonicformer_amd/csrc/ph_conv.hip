@@ -373,20 +373,10 @@ int ph_dynconv_k(const PhConvKnobs& kn, const uint16_t* planes, const uint16_t* 
     return PH_OK;
 }
 
-// tuning knob, read once per process: PH_CONV_WGS (A/B measurements)
-static const PhConvKnobs& conv_env_knobs() {
-    static const PhConvKnobs k = [] {
-        PhConvKnobs r;
-        if (const char* e = getenv("PH_CONV_WGS")) r.wgs = atoi(e);
-        return r;
-    }();
-    return k;
-}
-
 extern "C" int ph_dynconv(const uint16_t* planes, const uint16_t* kern, int64_t kern_plane_stride,
                           int64_t kern_batch_stride, const float* kbias, int64_t kbias_batch_stride, uint32_t* bits_out,
                           void* logits_out, int out_dtype, int64_t out_batch_stride, int B, int N, int64_t HW, int prec,
                           void* stream) {
-    return ph_dynconv_k(conv_env_knobs(), planes, kern, kern_plane_stride, kern_batch_stride, kbias, kbias_batch_stride, bits_out,
+    return ph_dynconv_k(PhConvKnobs{ph_switch(PH_SWITCH_CONV_WGS)}, planes, kern, kern_plane_stride, kern_batch_stride, kbias, kbias_batch_stride, bits_out,
                         logits_out, out_dtype, out_batch_stride, B, N, HW, prec, stream);
 }

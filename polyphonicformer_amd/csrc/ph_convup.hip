@@ -462,11 +462,7 @@ int ph_dynconv_up2_k(const PhUp2Knobs& kn, const uint16_t* planes, const uint16_
 extern "C" int ph_dynconv_up2_wgs(const uint16_t* planes, const uint16_t* kern, int64_t kern_batch_stride, const float* kbias,
                                   int64_t kbias_batch_stride, void* logits_out, void* up_out, int out_dtype, int B, int N, int H, int W,
                                   int prec, int workgroups, void* stream) {
-    PhUp2Knobs kn;
-    // test knob, read per launch on purpose (tests/test_gpu_kernels.py switches it inside one process; an eager launch pays the
-    // environment look-up, a graph replay none)
-    if (const char* e = getenv("PH_UP2_WGS")) kn.wgs = atoi(e) > 0 ? atoi(e) : 0;
-    return ph_dynconv_up2_k(kn, planes, kern, kern_batch_stride, kbias, kbias_batch_stride, logits_out, up_out, out_dtype, B, N, H, W, prec,
+    return ph_dynconv_up2_k(PhUp2Knobs{ph_switch(PH_SWITCH_UP2_WGS)}, planes, kern, kern_batch_stride, kbias, kbias_batch_stride, logits_out, up_out, out_dtype, B, N, H, W, prec,
                             workgroups, stream);
 }
 

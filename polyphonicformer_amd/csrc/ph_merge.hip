@@ -516,8 +516,7 @@ extern "C" int ph_panoptic_argmax(const float* act_mask, const float* scores, in
     PH_CHECK_ARG(act_mask && scores && geom && ids && counts && K > 0 && K <= 4096, "bad pointer or K");
     PanGeom G;
     PH_CHECK_ARG(fill_geom(G, geom, from_probs) == 0, "bad geometry");
-    // tests: the generic kernel on the x4 geometry (read per launch on purpose: tests/test_gpu_panoptic.py switches it in-process)
-    const bool generic_only = getenv("PH_PAN_GENERIC") != nullptr;
+    const bool generic_only = ph_switch(PH_SWITCH_PAN_GENERIC) != 0;      // tests: the generic kernel on the x4 geometry
     launch_argmax(act_mask, scores, 0, 1, K, G, from_probs, generic_only, ids, counts, 0, (hipStream_t)stream);
     PH_CHECK_LAUNCH();
     return PH_OK;

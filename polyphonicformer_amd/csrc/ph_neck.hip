@@ -396,20 +396,9 @@ static int conv_th(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B) {
 }
 int ph_conv_nhwc_tile_rows_k(const PhNeckKnobs& kn, int Ho, int Wo, int prec, int B) { return conv_th(kn, Ho, Wo, prec & ~PH_PLANES_C16, B); }
 
-// the public entry points' knobs: PH_CONV_TH, PH_GNSUM_WGS, PH_CPLANES_TPW once per process, PH_CONV_TH_NOW on every call (tests).  The
-// native neck plan (ph_neckplan.hip) calls the *_k forms with the defaults and reads none
-static PhNeckKnobs neck_env_knobs() {
-    static const PhNeckKnobs once = [] {
-        PhNeckKnobs k;
-        auto num = [](const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; };
-        k.conv_th = num("PH_CONV_TH");             // 2 / 4: A/B timing, tests
-        k.gnsum_wgs = num("PH_GNSUM_WGS");         // tuning knobs
-        k.cplanes_tpw = num("PH_CPLANES_TPW");
-        return k;
-    }();
-    PhNeckKnobs k = once;
-    if (const char* e = getenv("PH_CONV_TH_NOW")) { const int f = atoi(e); if (f == 2 || f == 4) k.conv_th = f; }   // tests: read per call
-    return k;
+// the public entry points' knobs, from the switch table.  The native neck plan (ph_neckplan.hip) calls the *_k forms with the defaults
+static PhNeckKnobs neck_switches() {
+    return PhNeckKnobs{ph_switch(PH_SWITCH_CONV_TILE_ROWS), ph_switch(PH_SWITCH_GNSUM_WGS), ph_switch(PH_SWITCH_CPLANES_TPW)};
 }
 
 // entries per frame of ph_conv_nhwc's `partial` output = pairs of output rows x 64-pixel column tiles (whatever the tile form;
@@ -472,7 +461,7 @@ int ph_conv_nhwc_k(const PhNeckKnobs& kn, const uint16_t* X, const uint16_t* Wp,
 
 extern "C" int ph_conv_nhwc(const uint16_t* X, const uint16_t* Wp, int64_t w_plane_elems, float* Y, float* partial, int ksize,
                             int stride, int B, int H, int W, int prec, void* stream) {
-    return ph_conv_nhwc_k(neck_env_knobs(), X, Wp, w_plane_elems, Y, partial, ksize, stride, B, H, W, prec, stream);
+    return ph_conv_nhwc_k(neck_switches(), X, Wp, w_plane_elems, Y, partial, ksize, stride, B, H, W, prec, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -750,7 +739,7 @@ int ph_gn_sum_planes_k(const PhNeckKnobs& kn, const float* const* ys, const floa
 extern "C" int ph_gn_sum_planes(const float* const* ys, const float* const* stats, const float* const* gammas,
                                 const float* const* betas, int nlev, int groups, uint16_t* planes, int B, int64_t HW, int prec,
                                 void* stream) {
-    return ph_gn_sum_planes_k(neck_env_knobs(), ys, stats, gammas, betas, nlev, groups, planes, B, HW, prec, stream);
+    return ph_gn_sum_planes_k(neck_switches(), ys, stats, gammas, betas, nlev, groups, planes, B, HW, prec, stream);
 }
 
 int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
@@ -804,5 +793,5 @@ int ph_gn_apply_k(const PhNeckKnobs& kn, const float* y, const float* stats, con
 
 extern "C" int ph_gn_apply(const float* y, const float* stats, const float* gamma, const float* beta, int groups, int mode,
                            int accumulate, uint16_t* planes, float* outf, int B, int H, int W, int prec, void* stream) {
-    return ph_gn_apply_k(neck_env_knobs(), y, stats, gamma, beta, groups, mode, accumulate, planes, outf, B, H, W, prec, stream);
+    return ph_gn_apply_k(neck_switches(), y, stats, gamma, beta, groups, mode, accumulate, planes, outf, B, H, W, prec, stream);
 }

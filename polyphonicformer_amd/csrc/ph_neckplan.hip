@@ -305,8 +305,8 @@ extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) {
 
 extern "C" void ph_neck_plan_destroy(ph_neck_plan* p) { delete p; }
 
-// the plan's launches take their knobs from here, never from the environment: the defaults the public entry points use when no
-// PH_CONV_TH[_NOW] / PH_GNSUM_WGS / PH_CPLANES_TPW is set
+// the plan's launches take their knobs from here, never from the switch table: the defaults the public entry points use when
+// PH_SWITCH_CONV_TILE_ROWS / PH_SWITCH_GNSUM_WGS / PH_SWITCH_CPLANES_TPW are 0
 static const PhNeckKnobs kNeck{};
 
 // every pointer check of the three run calls, before any of them launches

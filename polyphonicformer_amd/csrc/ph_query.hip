@@ -1117,16 +1117,19 @@ static int query_run(const PhQueryKnobs& kn, const float* partial, int nsplit, c
     return PH_OK;
 }
 
-// knobs read once per process: PH_QUERY_NRT, PH_QUERY_TIMELINE=1 (A/B measurements, debugging)
-static const PhQueryKnobs& query_env_knobs() {
-    static const PhQueryKnobs k = [] {
-        PhQueryKnobs r;
-        if (const char* e = getenv("PH_QUERY_NRT")) r.nrt = atoi(e);
-        const char* e = getenv("PH_QUERY_TIMELINE");
-        if (e && atoi(e) != 0 && hipMalloc((void**)&r.timeline, 16 * sizeof(unsigned long long)) == hipSuccess)
-            (void)hipMemset(r.timeline, 0, 128);
-        return r;
-    }();
+// the public entry points' knobs, from the switch table; the timeline's stamp buffer is allocated once, by the first of these
+// launches that sees PH_SWITCH_QUERY_TIMELINE on (A/B measurements, debugging)
+static PhQueryKnobs query_switches() {
+    PhQueryKnobs k;
+    k.nrt = ph_switch(PH_SWITCH_QUERY_NRT);
+    if (ph_switch(PH_SWITCH_QUERY_TIMELINE)) {
+        static unsigned long long* const tl = [] {
+            unsigned long long* p = nullptr;
+            if (hipMalloc((void**)&p, 16 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(p, 0, 128);
+            return p;
+        }();
+        k.timeline = tl;
+    }
     return k;
 }
 
@@ -1135,7 +1138,7 @@ extern "C" int ph_query_stage(const float* partial, int nsplit, const uint32_t* 
                               float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                               size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases,
                               void* stream) {
-    return query_run(query_env_knobs(), partial, nsplit, bits, nullptr, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
+    return query_run(query_switches(), partial, nsplit, bits, nullptr, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias, workspace,
                      workspace_bytes, B, N, HW, prec, kern_format, phases, stream);
 }
 
@@ -1147,7 +1150,7 @@ extern "C" int ph_query_stage_counts(const float* partial, int nsplit, const uin
                                      void* workspace, size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format,
                                      int phases, void* stream) {
     if (!pcount) { ph_set_error("ph_query_stage_counts: null pcount"); return PH_EINVAL; }
-    return query_run(query_env_knobs(), partial, nsplit, bits, pcount, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias,
+    return query_run(query_switches(), partial, nsplit, bits, pcount, k_in, q_in, wb, wf, layout, obj, dobj, cls, cls_sigmoid, kern, kbias,
                      workspace, workspace_bytes, B, N, HW, prec, kern_format, phases, stream);
 }
 

@@ -317,9 +317,9 @@ class DecodePlan:
         self.graph = None
         self.handoff_runs = 0          # runs that started from another kernel's planes (tests observe the path taken)
         self.want_depth_lowres = False     # the fused final stage writes the depth branch's low-resolution logits only on request
-        # workgroups of the fused final stage when the plan is one part of a multi-stream step: 1.5 per CU (PH_UP2_SHARED_WGS=n; stages())
-        self.up2_shared_wgs = int(_os.environ.get("PH_UP2_SHARED_WGS") or
-                                  (3 * torch.cuda.get_device_properties(device).multi_processor_count // 2 if dev.type == "cuda" else 0))
+        # workgroups of the fused final stage when the plan is one part of a multi-stream step: 1.5 per CU (cfg.up2_wgs = n; stages())
+        self.up2_shared_wgs = self.cfg.up2_wgs or \
+            (3 * torch.cuda.get_device_properties(device).multi_processor_count // 2 if dev.type == "cuda" else 0)
         if self.poolx:
             self.partial_px = e((B, self.nsplit_px, Npad, 512), torch.float32)
             self.pcount_px = e((B, self.nsplit_px, Npad), torch.int32)

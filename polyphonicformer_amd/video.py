@@ -748,8 +748,11 @@ class VideoStreamRunner:
         the one-pass kernel (fp16 / bf16; the two-pass kernel's tile runs are sized by the batch, which regroups its fp32 partial
         sums -- 1e-6 differences) and heads left `frame_invariant`"""
         grade = E.KHEAD_PREC.get(getattr(self.pipe.rpn_head, "precision", None))
-        return bool(grade in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16) and not os.environ.get("PH_KHEAD_TWOPASS")
-                    and getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False))
+        if grade not in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16):
+            return False
+        # the one-pass switch as the head's plans will get it (native_khead_cfg is its one reader; the field depends on no size)
+        onepass = E.native_khead_cfg(1, 1, 1, 1, 1, 1, False, 32, grade).onepass != _lib.PH_KNOB_OFF
+        return bool(onepass and getattr(self.pipe.rpn_head, "frame_invariant", False) and getattr(self.pipe.roi_head, "frame_invariant", False))
 
     def _launch_size(self):
         """frames per launch of the batched `push`: `frames_per_launch` where the heads are batch invariant, else 1"""

@@ -139,8 +139,9 @@ def clear_plan_knobs(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-def graph_kernel_nodes(run):
-    """sorted [grid x, y, z, block x, LDS bytes] of every kernel node of `run()` captured into a HIP graph (after one eager call)"""
+def graph_kernel_nodes(run, graph=None):
+    """sorted [grid x, y, z, block x, LDS bytes] of every kernel node of `run()` captured into a HIP graph (after one eager call);
+    `graph`: of this captured torch.cuda.CUDAGraph(keep_graph=True) instead, `run` unused"""
     import ctypes as C
 
     class Dim3(C.Structure):
@@ -150,11 +151,13 @@ def graph_kernel_nodes(run):
         _fields_ = [("blockDim", Dim3), ("extra", C.c_void_p), ("func", C.c_void_p), ("gridDim", Dim3), ("kernelParams", C.c_void_p),
                     ("sharedMemBytes", C.c_uint)]
     hip = C.CDLL(next(l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64.so" in l))
-    run()
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph(keep_graph=True)
-    with torch.cuda.graph(g):
+    g = graph
+    if g is None:
         run()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph(keep_graph=True)
+        with torch.cuda.graph(g):
+            run()
     graph = C.c_void_p(g.raw_cuda_graph())
     n = C.c_size_t(0)
     assert hip.hipGraphGetNodes(graph, None, C.byref(n)) == 0

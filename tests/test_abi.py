@@ -43,7 +43,9 @@ CONSTANTS = [
     ("PH_DTRK_EREFUSED", _lib.PH_DTRK_EREFUSED, 2),
     ("PH_DTRK_ECOUNT", _lib.PH_DTRK_ECOUNT, 3),
     ("PH_DVPQ_MAX_THR", _lib.PH_DVPQ_MAX_THR, 8),
-] + [("PH_DTRK_ST_" + n.upper(), i) for i, n in enumerate(_lib.DTRK_STATUS)]
+    ("PH_SWITCH_COUNT", len(_lib.SWITCHES), 8),
+] + [("PH_DTRK_ST_" + n.upper(), i) for i, n in enumerate(_lib.DTRK_STATUS)] + \
+    [("PH_SWITCH_" + n.upper(), i) for i, n in enumerate(_lib.SWITCHES)]
 
 
 @functools.lru_cache(maxsize=None)

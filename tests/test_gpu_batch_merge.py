@@ -206,7 +206,7 @@ def _geoms(sh, sw, cut_h, cut_w):
 
 @pytest.mark.parametrize("form", ["x4", "generic"])
 @pytest.mark.parametrize("shape", [(24, 40, 0, 0), (17, 23, 3, 2), (8, 16, 1, 3), (1, 1, 0, 0), (64, 128, 0, 0)])
-def test_batched_kernels_equal_the_single_frame_calls(gpu, shape, form, monkeypatch):
+def test_batched_kernels_equal_the_single_frame_calls(gpu, shape, form):
     lib, s = _lib.load(), _lib.stream_ptr
     sh, sw, cut_h, cut_w = shape
     geom, (Ho, Wo) = _geoms(sh, sw, cut_h, cut_w)[form]
@@ -240,12 +240,11 @@ def test_batched_kernels_equal_the_single_frame_calls(gpu, shape, form, monkeypa
     newid = torch.randint(0, 3, (B, Kk), generator=g).int()
     newid = (newid * torch.arange(1, Kk + 1).int()).to(gpu)            # a third of the candidates rejected
     for generic_only in ((0, 1) if form == "x4" else (0,)):
-        if generic_only:
-            monkeypatch.setenv("PH_PAN_GENERIC", "1")                  # the single-frame call's switch; the batched call has a flag
         ref = []
         for b in range(B):
             ids, cnt = e((Ho, Wo), torch.int32, -7), e((2, Kk), torch.int32, -7)
-            _lib.check(lib.ph_panoptic_argmax(_lib.ptr(a[b]), _lib.ptr(scd[b]), Kk, geom, 0, _lib.ptr(ids), _lib.ptr(cnt), s()), "argmax")
+            with _lib.switches(pan_generic=generic_only):              # the single-frame call's switch; the batched call has a flag
+                _lib.check(lib.ph_panoptic_argmax(_lib.ptr(a[b]), _lib.ptr(scd[b]), Kk, geom, 0, _lib.ptr(ids), _lib.ptr(cnt), s()), "argmax")
             pan, db, df = e((Ho, Wo), torch.int32, -7), e((Ho, Wo), torch.float32, -7), e((Ho, Wo), torch.float32, -7)
             _lib.check(lib.ph_panoptic_paste(_lib.ptr(ids), _lib.ptr(newid[b]), _lib.ptr(dep[b]), _lib.ptr(dep0[b]), geom, 0, _lib.ptr(pan),
                                              _lib.ptr(db), _lib.ptr(df), s()), "paste")

@@ -310,14 +310,12 @@ def test_upsample2x_fp16(gpu, H, W):
                                        # five row blocks (round 6: the last block's windows run on helper waves, one tile late): ranges of many
                                        # rows spanning frames, a last block with ONE live query-row group, with all 32 rows live, one-row frames
                                        (153, 16, 2, 5), (130, 7, 3, 3), (160, 5, 2, 2), (137, 1, 5, 2), (145, 2, 3, 0)])
-def test_dynconv_up2_fused_final_stage(gpu, monkeypatch, prec, dt, N, H, B, wgs):
+def test_dynconv_up2_fused_final_stage(gpu, prec, dt, N, H, B, wgs):
     """ph_dynconv_up2 = ph_dynconv (16-bit logits) + ph_upsample2x in one kernel (kernel_update_head.py:317-329 +
-    kernel_update.py:131-143).  W = 256; workgroup ranges of one row (rows < CUs), of many rows spanning frames (PH_UP2_WGS),
+    kernel_update.py:131-143).  W = 256; workgroup ranges of one row (rows < CUs), of many rows spanning frames (the up2_wgs switch),
     and cfg2's full map.  Low-resolution logits: bit-identical to the two-kernel form (same MFMA sequence).  Upsampled
     logits: within one 16-bit ulp of F.interpolate on those low-resolution values (fp32 blend, one final rounding), and almost
     everywhere bit-identical to ph_upsample2x (the blend is vertical-then-horizontal here, horizontal-then-vertical there)."""
-    if wgs:
-        monkeypatch.setenv("PH_UP2_WGS", str(wgs))
     W = 256
     lib = _lib.load()
     oc = E.OUT_CODE[dt]
@@ -331,23 +329,24 @@ def test_dynconv_up2_fused_final_stage(gpu, monkeypatch, prec, dt, N, H, B, wgs)
     kern = _planes16(kern_f, kdt)[None].contiguous().to(gpu)
     xp = E.ingest(x.to(gpu), _lib.PH_PREC_F16 if prec == _lib.PH_PREC_F16 else _lib.PH_PREC_BF16)
     ulp = 2.0 ** -10 if dt == torch.float16 else 2.0 ** -7
-    for br in (0, 1):
-        low2 = torch.empty(B, N, H, W, device=gpu, dtype=dt)
-        E.dynconv(xp, kern, kbias, br, N, HW, prec, logits_out=low2, out_dtype=oc)
-        up2 = E.upsample2x(low2)
-        low = torch.full((B, N, H, W), float("nan"), device=gpu, dtype=dt)
-        up = torch.full((B, N, 2 * H, 2 * W), float("nan"), device=gpu, dtype=dt)
-        E.dynconv_up2(xp, kern, kbias, br, N, H, W, prec, up, logits_out=low, out_dtype=oc)
-        assert torch.equal(low, low2), br
-        ref = F.interpolate(low2.float().cpu(), scale_factor=2, mode="bilinear", align_corners=False)
-        d = (up.float().cpu() - ref).abs()
-        assert not torch.isnan(up.float()).any()
-        assert bool((d <= ulp * ref.abs() + 1e-7).all()), float((d / ref.abs().clamp_min(1e-6)).max())
-        assert float((up != up2).float().mean()) < 2e-3
-        # without the low-resolution output (the depth branch's form): the same upsampled tensor
-        upn = torch.full_like(up, float("nan"))
-        E.dynconv_up2(xp, kern, kbias, br, N, H, W, prec, upn, logits_out=None, out_dtype=oc)
-        assert torch.equal(upn, up)
+    with _lib.switches(up2_wgs=wgs):
+        for br in (0, 1):
+            low2 = torch.empty(B, N, H, W, device=gpu, dtype=dt)
+            E.dynconv(xp, kern, kbias, br, N, HW, prec, logits_out=low2, out_dtype=oc)
+            up2 = E.upsample2x(low2)
+            low = torch.full((B, N, H, W), float("nan"), device=gpu, dtype=dt)
+            up = torch.full((B, N, 2 * H, 2 * W), float("nan"), device=gpu, dtype=dt)
+            E.dynconv_up2(xp, kern, kbias, br, N, H, W, prec, up, logits_out=low, out_dtype=oc)
+            assert torch.equal(low, low2), br
+            ref = F.interpolate(low2.float().cpu(), scale_factor=2, mode="bilinear", align_corners=False)
+            d = (up.float().cpu() - ref).abs()
+            assert not torch.isnan(up.float()).any()
+            assert bool((d <= ulp * ref.abs() + 1e-7).all()), float((d / ref.abs().clamp_min(1e-6)).max())
+            assert float((up != up2).float().mean()) < 2e-3
+            # without the low-resolution output (the depth branch's form): the same upsampled tensor
+            upn = torch.full_like(up, float("nan"))
+            E.dynconv_up2(xp, kern, kbias, br, N, H, W, prec, upn, logits_out=None, out_dtype=oc)
+            assert torch.equal(upn, up)
 
 
 @pytest.mark.parametrize("prec,feat,kdt", [(_lib.PH_PREC_BF16_KF16, _lib.PH_PREC_BF16, torch.float16), (_lib.PH_PREC_F16, _lib.PH_PREC_F16, torch.float16),

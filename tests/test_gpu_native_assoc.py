@@ -407,7 +407,7 @@ def test_run_is_capturable_and_replays_on_new_inputs(gpu):
 
 # ---- 11. environment
 def test_environment_does_not_reach_the_plan(gpu, monkeypatch):
-    """the launch variables the library's public entry points read change nothing in the plan"""
+    """the library's switches (set by call) and the variables the Python plans read change nothing in the plan"""
     frames = [_frame((64, 128), [1, 9, 0, 5, 12], 71), _frame((64, 128), [3, 3], 72)]
     pan, rec, levels = _batch(frames, gpu)
     plan = _plan("bf16", 2, (64, 128), 6, levels)
@@ -416,12 +416,12 @@ def test_environment_does_not_reach_the_plan(gpu, monkeypatch):
     valid = lambda p: [p.roi_planes()[:, b, :n].clone() for b, n in enumerate(p.things[:, 0].tolist())]     # rows < nthing are written
     ref = [t.clone() for t in (plan.sem, plan.things, plan.embeds)] + valid(plan)
     assert plan.things[:, 0].tolist() == [3, 2]
-    for k, v in dict(PH_CONV_WGS="7", PH_UP2_WGS="5", PH_QUERY_NRT="1", PH_CONV_TH="4", PH_CONV_TH_NOW="4", PH_GNSUM_WGS="3", PH_GNSUM_TPW="2",
-                     PH_CPLANES_TPW="2", PH_NECK_STATS3="0", PH_NECK_APPLY3="0", PH_KHEAD1_PAIR="1", PH_POOL_NSPLIT="3").items():
+    for k, v in dict(PH_GNSUM_TPW="2", PH_NECK_STATS3="0", PH_NECK_APPLY3="0", PH_KHEAD1_PAIR="1", PH_POOL_NSPLIT="3").items():
         monkeypatch.setenv(k, v)
-    again = _plan("bf16", 2, (64, 128), 6, levels)
-    again.embeds.fill_(SENTINEL)
-    again.run(pan, rec, levels)
+    with _lib.switches(conv_wgs=7, up2_wgs=5, query_nrt=1, conv_tile_rows=4, gnsum_wgs=3, cplanes_tpw=2):
+        again = _plan("bf16", 2, (64, 128), 6, levels)
+        again.embeds.fill_(SENTINEL)
+        again.run(pan, rec, levels)
     for a, b in zip(ref, [again.sem, again.things, again.embeds] + valid(again)):
         assert torch.equal(a, b)
     g0, g1 = plan.geometry, again.geometry

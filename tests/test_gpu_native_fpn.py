@@ -206,7 +206,7 @@ def test_workspace_and_pack_stay_inside_their_bounds(gpu, grade, layout0):
 
 # ---- 4. the environment -----------------------------------------------------------------------------------------------------------------
 def test_environment_does_not_reach_the_native_plan(gpu, monkeypatch):
-    B, shapes, grade = 2, TH.P_WIDE, "fp16"         # every conv launch takes 2-row tiles here: PH_CONV_TH_NOW=4 would change the public path's
+    B, shapes, grade = 2, TH.P_WIDE, "fp16"         # every conv launch takes 2-row tiles here: conv_tile_rows=4 changes the public path's
     m = TH._fpn(grade)
     stages = TH._stages(shapes, B, gpu, seed=11)
     cfg = E.native_fpn_cfg(B, shapes, CH, grade)
@@ -216,19 +216,19 @@ def test_environment_does_not_reach_the_native_plan(gpu, monkeypatch):
     geo0 = bytes(plan.geometry)
     assert 4 not in list(plan.geometry.tile_rows)
     nodes0 = Hh.graph_kernel_nodes(lambda: plan.run(stages))
-    for k, v in (("PH_CONV_TH_NOW", "4"), ("PH_CONV_TH", "4"), ("PH_NECK_OUT2", "0"), ("PH_NECK_C16", "0"), ("PH_NECK_STREAMS", "0"),
-                 ("PH_GNSUM_WGS", "3"), ("PH_CPLANES_TPW", "2")):
+    for k, v in (("PH_NECK_OUT2", "0"), ("PH_NECK_C16", "0"), ("PH_NECK_STREAMS", "0")):
         assert k in Hh.PLAN_KNOBS
         monkeypatch.setenv(k, v)
-    plan2 = E.NativeFpnPlan(E.native_fpn_pack(m, E.native_fpn_cfg(B, shapes, CH, grade), gpu), B, shapes, gpu)
-    got = plan2.run(stages)
-    torch.cuda.synchronize()
-    assert bytes(plan2.geometry) == geo0
-    for a, b in zip(got, base):
-        assert torch.equal(a, b)
-    assert Hh.graph_kernel_nodes(lambda: plan2.run(stages)) == nodes0           # the same launches, whatever the environment says
-    pyplan = E.FpnPlan(B, shapes, CH, GRADES[grade], gpu)                        # the public conv entry point still listens
-    assert Hh.graph_kernel_nodes(lambda: pyplan.run(stages, m._pack(gpu))) != nodes0
+    with _lib.switches(conv_tile_rows=4, gnsum_wgs=3, cplanes_tpw=2):            # the library's switches, by call
+        plan2 = E.NativeFpnPlan(E.native_fpn_pack(m, E.native_fpn_cfg(B, shapes, CH, grade), gpu), B, shapes, gpu)
+        got = plan2.run(stages)
+        torch.cuda.synchronize()
+        assert bytes(plan2.geometry) == geo0
+        for a, b in zip(got, base):
+            assert torch.equal(a, b)
+        assert Hh.graph_kernel_nodes(lambda: plan2.run(stages)) == nodes0       # the same launches, whatever the switches say
+        pyplan = E.FpnPlan(B, shapes, CH, GRADES[grade], gpu)                    # the public conv entry point listens
+        assert Hh.graph_kernel_nodes(lambda: pyplan.run(stages, m._pack(gpu))) != nodes0
 
 
 # ---- 5. graph capture -------------------------------------------------------------------------------------------------------------------

@@ -378,7 +378,7 @@ def test_graph_capture_replays_the_eager_run(gpu):
 
 # ---- 7. the environment ----------------------------------------------------------------------------------------------------------
 def test_environment_does_not_reach_the_native_plan(gpu, monkeypatch):
-    B, shapes = 5, S3                       # every conv launch takes 2-row tiles here: PH_CONV_TH_NOW=4 would change the public path's
+    B, shapes = 5, S3                       # every conv launch takes 2-row tiles here: conv_tile_rows=4 would change the public path's
     m = _neck("fp16")
     feats = _feats(shapes, B, gpu, seed=11)
     posenc = sine_positional_encoding(*shapes[3], 128).to(gpu)
@@ -387,9 +387,10 @@ def test_environment_does_not_reach_the_native_plan(gpu, monkeypatch):
     geo0 = bytes(plan.geometry)
     p = E.NeckPlan(B, shapes, _lib.PH_PREC_F16, gpu)
     assert p.out2 and p.multi
-    for k, v in (("PH_CONV_TH_NOW", "4"), ("PH_NECK_OUT2", "0"), ("PH_NECK_C16", "0"), ("PH_NECK_STREAMS", "0")):
+    for k, v in (("PH_NECK_OUT2", "0"), ("PH_NECK_C16", "0"), ("PH_NECK_STREAMS", "0")):
         monkeypatch.setenv(k, v)
-    got, plan2 = _native_run(m, cfg, feats, posenc, True, gpu)
+    with _lib.switches(conv_tile_rows=4):
+        got, plan2 = _native_run(m, cfg, feats, posenc, True, gpu)
     assert bytes(plan2.geometry) == geo0 and 4 not in list(plan2.geometry.tile_rows)
     for a, b in zip(got, base):
         assert torch.equal(a, b)

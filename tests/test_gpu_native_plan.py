@@ -390,8 +390,8 @@ print(json.dumps(res))
 
 
 def test_environment_does_not_reach_the_native_plan(gpu):
-    """the launch knobs the public entry points read from the environment (PH_UP2_WGS per launch, PH_CONV_WGS / PH_QUERY_NRT
-    once per process) leave the native plan's launches as they are: the kernel nodes of a captured native decode
+    """the launch switches the public entry points take from the library's table, filled from the environment at first use
+    (PH_UP2_WGS, PH_CONV_WGS, PH_QUERY_NRT), leave the native plan's launches as they are: the kernel nodes of a captured native decode
     (grid, block, LDS) are the same with and without them, while the Python plan's -- through the public entry points -- change.
     Without the variables both plans capture the same launches."""
     knobs = dict(PH_UP2_WGS="7", PH_CONV_WGS="5", PH_QUERY_NRT="1")

@@ -61,7 +61,7 @@ def test_conv_nhwc(gpu, prec, k, s, H, W, B):
 
 @pytest.mark.parametrize("prec", [_lib.PH_PREC_BF16, _lib.PH_PREC_F16])
 @pytest.mark.parametrize("k,s,H,W,B", [(3, 1, 6, 70, 2), (3, 1, 33, 130, 1), (3, 2, 19, 131, 2), (1, 1, 7, 64, 3), (3, 1, 128, 256, 1)])
-def test_conv_tile_forms_give_identical_bits(gpu, monkeypatch, prec, k, s, H, W, B):
+def test_conv_tile_forms_give_identical_bits(gpu, prec, k, s, H, W, B):
     """round 6: the 2-row and the 4-row tile forms of k_conv_nhwc write the same conv output AND the same GroupNorm
     partial sums -- one entry per pair of output rows, in the 2-row kernel's order -- so the form a launch's size picks never shows in
     a frame's bits (odd row counts: the last pair is one row; the last 4-row tile may hold one pair only)"""
@@ -77,15 +77,14 @@ def test_conv_tile_forms_give_identical_bits(gpu, monkeypatch, prec, k, s, H, W,
     nwg = lib.ph_conv_nhwc_workgroups_b(k, s, Ho, Wo, prec, B)
     assert nwg == ((Wo + 63) // 64) * ((Ho + 1) // 2)
     outs = []
-    for th in ("2", "4"):
-        monkeypatch.setenv("PH_CONV_TH_NOW", th)
+    for th in (2, 4):
         y = torch.empty((B, Ho * Wo, 256), dtype=torch.float32, device=gpu)
         partial = torch.full((lib.ph_conv_nhwc_partial_floats(B, Ho, Wo),), float("nan"), dtype=torch.float32, device=gpu)
-        E.conv_nhwc(xp, dict(wp=wp, k=k, s=s), y, partial, B, H, W, prec)
+        with _lib.switches(conv_tile_rows=th):
+            E.conv_nhwc(xp, dict(wp=wp, k=k, s=s), y, partial, B, H, W, prec)
         stats = torch.empty((B, 32, 2), dtype=torch.float32, device=gpu)
         E.gn_finalize(partial, stats, nwg, 32, Ho * Wo, B)
         outs.append((y.cpu(), partial.cpu()[:B * nwg * 512], stats.cpu()))
-    monkeypatch.delenv("PH_CONV_TH_NOW")
     assert not torch.isnan(outs[0][1]).any()                      # every entry the finalize pass reads is written
     for a, b in zip(outs[0], outs[1]):
         assert torch.equal(a, b)

@@ -89,7 +89,7 @@ def test_get_panoptic_fused_vs_reference_golden(gpu, case, dtype):
 
 
 @pytest.mark.parametrize("shape", [(24, 40, 0, 0), (17, 23, 3, 2), (8, 16, 1, 3), (1, 1, 0, 0), (64, 128, 0, 0)])
-def test_argmax_x4_form_equals_the_generic_kernel(gpu, shape, monkeypatch):
+def test_argmax_x4_form_equals_the_generic_kernel(gpu, shape):
     """the shipped geometry (identity second resize, exact x4 first) takes a kernel of its own (4 x 2 pixel blocks, ballot
     histograms): ids and both histograms must be the generic kernel's bit for bit, cropped maps and borders included"""
     from polyphonicformer_amd import _lib
@@ -106,12 +106,11 @@ def test_argmax_x4_form_equals_the_generic_kernel(gpu, shape, monkeypatch):
     lib = _lib.load()
     a, s = act.to(gpu).contiguous(), sc.to(gpu)
     outs = []
-    for generic in (False, True):
-        if generic:
-            monkeypatch.setenv("PH_PAN_GENERIC", "1")
+    for generic in (0, 1):
         ids = torch.full((Ho, Wo), -7, dtype=torch.int32, device=gpu)
         cnt = torch.empty((2, K), dtype=torch.int32, device=gpu)
-        _lib.check(lib.ph_panoptic_argmax(_lib.ptr(a), _lib.ptr(s), K, geom, 0, _lib.ptr(ids), _lib.ptr(cnt), _lib.stream_ptr()), "argmax")
+        with _lib.switches(pan_generic=generic):
+            _lib.check(lib.ph_panoptic_argmax(_lib.ptr(a), _lib.ptr(s), K, geom, 0, _lib.ptr(ids), _lib.ptr(cnt), _lib.stream_ptr()), "argmax")
         outs.append((ids.cpu(), cnt.cpu()))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert int(outs[0][1][0].sum()) == Ho * Wo and int(outs[0][0].min()) >= 0
