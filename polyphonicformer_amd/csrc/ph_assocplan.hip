@@ -4,13 +4,13 @@
 // over ph_panoptic_merge's device records.  Three small kernels live here (k_assoc_things, k_assoc_gather, k_assoc_paint); the
 // arithmetic is ph_track.hip's kernels in their batched / device-count forms.  pack / create / run allocate no device memory, do not
 // synchronise and read no environment variable; ph_assoc_plan_match is the one stateful, synchronising call, and ph_assoc_plan_track
-// (the device tracker, ph_dtracker.hip, and k_assoc_trklut) its launch-only counterpart.
+// (the device tracker, ph_dtracker.hip, and k_assoc_trklut) its launch-only counterpart.  The track pack's and the plan's pack / create /
+// info scaffold is the shared one (ph_plan_inl.h).
 #include <string.h>
 
-#include <new>
 #include <vector>
 
-#include "ph_common.h"
+#include "ph_plan_inl.h"
 
 #pragma clang fp contract(off)
 
@@ -108,34 +108,22 @@ extern "C" int64_t ph_track_param_numel(const ph_track_cfg* cfg, int index) {
     return track_numel(g, index);
 }
 
-extern "C" size_t ph_track_pack_bytes(const ph_track_cfg* cfg) {
-    TGeo g;
-    if (resolve_track(cfg, g, "ph_track_pack_bytes")) return 0;
-    return g.pack_total;
-}
+// the track pack's description for the shared scaffold
+struct TrackFam {
+    typedef ph_track_cfg Cfg; typedef TGeo Geo; typedef ph_track_layout Layout;
+    static constexpr auto resolve = &resolve_track;
+    static constexpr auto build_table = &::build_table;
+    static int nparams(const TGeo& g) { return g.nparams; }
+    static constexpr auto param_name = &ph_track_param_name;
+    static constexpr unsigned kPackBlocks = 4096;
+};
 
-extern "C" int ph_track_pack_layout(const ph_track_cfg* cfg, ph_track_layout* layout) {
-    TGeo g;
-    const int rc = resolve_track(cfg, g, "ph_track_pack_layout");
-    if (rc) return rc;
-    PH_CHECK_ARG(layout != nullptr, "null layout");
-    *layout = g.lay;
-    return PH_OK;
-}
+extern "C" size_t ph_track_pack_bytes(const ph_track_cfg* cfg) { return plan::pack_bytes<TrackFam>(cfg, __func__); }
+
+extern "C" int ph_track_pack_layout(const ph_track_cfg* cfg, ph_track_layout* layout) { return plan::pack_layout<TrackFam>(cfg, layout, __func__); }
 
 extern "C" int ph_track_pack(const ph_track_cfg* cfg, const float* const* params, void* pack, void* stream) {
-    TGeo g;
-    const int rc = resolve_track(cfg, g, "ph_track_pack");
-    if (rc) return rc;
-    PH_CHECK_ARG(params && pack, "null params or pack");
-    for (int i = 0; i < g.nparams; ++i)
-        if (!params[i]) { ph_set_error("ph_track_pack: parameter %d (%s) is NULL", i, ph_track_param_name(cfg, i)); return PH_EINVAL; }
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    PH_CHECK_ARG(g.pack_total / 16 < (1ull << 32), "pack too large");
-    PhPackTable t{};
-    build_table(g, t);
-    for (int i = 0; i < g.nparams; ++i) t.p[i] = params[i];
-    return ph_pack_pieces("ph_track_pack", t, pack, 4096, stream);
+    return plan::pack<TrackFam>(cfg, params, pack, stream, __func__);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -304,10 +292,15 @@ static void launch_paint(const AGeo& g, const int32_t* pan, const T* lut, T* out
 }
 
 // ---------------------------------------------------------------------------------------------
-extern "C" size_t ph_assoc_plan_workspace_bytes(const ph_assoc_cfg* cfg) {
-    AGeo g;
-    if (resolve(cfg, g, "ph_assoc_plan_workspace_bytes")) return 0;
-    return g.total;
+static void fill_geometry(const AGeo& g, ph_assoc_geometry* out) {
+    memset(out, 0, sizeof(*out));
+    out->things_words = g.words; out->P = g.t.P;
+    out->conv_splits = g.S[0]; out->conv_steps = g.steps[0]; out->fc_splits = g.S[1]; out->fc_steps = g.steps[1];
+    out->emb_splits = g.S[2]; out->emb_steps = g.steps[2];
+    out->vec8 = g.vec8;
+    out->staging_bytes = g.staging;
+    out->rois_offset = g.o_rois;
+    out->roi_planes_offset = g.o_roi;
 }
 
 struct ph_assoc_plan {
@@ -321,39 +314,26 @@ struct ph_assoc_plan {
     std::vector<const float*> embs;
 };
 
+// the plan's description for the shared scaffold
+struct AssocFam {
+    typedef ph_assoc_cfg Cfg; typedef AGeo Geo; typedef ph_assoc_geometry Geometry; typedef ph_assoc_plan Plan;
+    static constexpr auto resolve = &::resolve;
+    static constexpr auto fill_geometry = &::fill_geometry;
+};
+
+extern "C" size_t ph_assoc_plan_workspace_bytes(const ph_assoc_cfg* cfg) { return plan::workspace_bytes<AssocFam>(cfg, __func__); }
+
 extern "C" int ph_assoc_plan_create(const ph_assoc_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes,
                                     ph_assoc_plan** out) {
-    AGeo g;
-    const int rc = resolve(cfg, g, "ph_assoc_plan_create");
-    if (rc) return rc;
-    PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
-    *out = nullptr;
-    PH_RUN(ph_check_buffers("ph_assoc_plan_create", pack, workspace, workspace_bytes, g.total));
-    ph_assoc_plan* p = new (std::nothrow) ph_assoc_plan;
-    if (!p) { ph_set_error("ph_assoc_plan_create: out of host memory"); return PH_EINVAL; }
-    p->g = g;
-    p->pack = (const char*)pack;
-    p->ws = (char*)workspace;
-    const size_t tot = (size_t)g.B * g.cap;
+    PH_RUN(plan::create<AssocFam>(cfg, pack, workspace, workspace_bytes, out, __func__));
+    ph_assoc_plan* p = *out;
+    const size_t tot = (size_t)p->g.B * p->g.cap;
     p->boxes.resize(tot * 5); p->labels.resize(tot); p->ids.resize(tot); p->kept.resize(tot);
-    p->counts.resize(g.B); p->kept_counts.resize(g.B); p->embs.resize(g.B);
-    *out = p;
+    p->counts.resize(p->g.B); p->kept_counts.resize(p->g.B); p->embs.resize(p->g.B);
     return PH_OK;
 }
 
-extern "C" int ph_assoc_plan_info(const ph_assoc_plan* p, ph_assoc_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    const AGeo& g = p->g;
-    memset(out, 0, sizeof(*out));
-    out->things_words = g.words; out->P = g.t.P;
-    out->conv_splits = g.S[0]; out->conv_steps = g.steps[0]; out->fc_splits = g.S[1]; out->fc_steps = g.steps[1];
-    out->emb_splits = g.S[2]; out->emb_steps = g.steps[2];
-    out->vec8 = g.vec8;
-    out->staging_bytes = g.staging;
-    out->rois_offset = g.o_rois;
-    out->roi_planes_offset = g.o_roi;
-    return PH_OK;
-}
+extern "C" int ph_assoc_plan_info(const ph_assoc_plan* p, ph_assoc_geometry* out) { return plan::info<AssocFam>(p, out, __func__); }
 
 extern "C" void ph_assoc_plan_destroy(ph_assoc_plan* p) { delete p; }
 

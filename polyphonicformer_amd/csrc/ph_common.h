@@ -51,6 +51,19 @@ void ph_set_error(const char* fmt, ...);
 // the pieces of a caller-owned workspace or pack start at 256-byte boundaries
 static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
+// a cfg's mode (PH_MODE_*) -> the grade of the KernelHead / neck / FPN kernels (engine.KHEAD_PREC); -1: no such mode
+static inline int ph_mode_grade(int mode) {
+    switch (mode) {
+        case PH_MODE_FP16: return PH_PREC_F16;
+        case PH_MODE_BF16: return PH_PREC_BF16;
+        case PH_MODE_FP32: case PH_MODE_MIXED: case PH_MODE_MIXED16: return PH_PREC_SPLIT;
+        default: return -1;
+    }
+}
+
+// the FPN's top-down size rule: a level is 2 n or 2 n - 1 of the coarser one's n (the sizes at which the integer nearest index is torch's)
+static inline bool ph_fpn_size_rule(int fine, int coarse) { return fine == 2 * coarse || fine == 2 * coarse - 1; }
+
 // every buffer check of a native plan's create / run call, in this order: pack alignment (pack_or_null: none to check), workspace
 // NULL, workspace size (PH_EWORKSPACE), workspace alignment; the messages carry the public function's name (ph_api.hip)
 int ph_check_buffers(const char* fn, const void* pack_or_null, const void* workspace, size_t workspace_bytes, size_t need);

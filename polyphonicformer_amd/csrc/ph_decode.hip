@@ -1,13 +1,12 @@
 // N2: the S-stage decode as a native object (include/polyhead.h ph_decode_*): the launch geometry rule of every decode plan
 // (resolve(): engine.DecodePlan asks it through ph_decode_geometry_of), the launch sequence and the buffer plan of
 // engine.DecodePlan, and the stage packing of pack.py as one HIP kernel.  Host code only calls the other
-// entry points of this library, on the caller's stream; nothing here allocates device memory or synchronises.
+// entry points of this library, on the caller's stream; nothing here allocates device memory or synchronises.  Workspace bytes,
+// geometry-of and info are the shared scaffold's (ph_plan_inl.h); the stage layout, the packer and create are its own.
 #include <math.h>
 #include <string.h>
 
-#include <new>
-
-#include "ph_common.h"
+#include "ph_plan_inl.h"
 
 #pragma clang fp contract(off)
 
@@ -455,12 +454,6 @@ extern "C" int ph_decode_pack_stage(const ph_decode_cfg* cfg, const float* const
     return PH_OK;
 }
 
-extern "C" size_t ph_decode_workspace_bytes(const ph_decode_cfg* cfg) {
-    Geo g;
-    if (resolve(cfg, g, "ph_decode_workspace_bytes")) return 0;
-    return g.total;
-}
-
 struct ph_decode {
     Geo g;
     ph_stage_layout lay;
@@ -514,20 +507,18 @@ static void fill_geometry(const Geo& g, ph_decode_geometry* out) {
     out->feat_planes = g.FP;
 }
 
-extern "C" int ph_decode_geometry_of(const ph_decode_cfg* cfg, ph_decode_geometry* out) {
-    Geo g;
-    const int rc = resolve(cfg, g, "ph_decode_geometry_of");
-    if (rc) return rc;
-    PH_CHECK_ARG(out != nullptr, "null out");
-    fill_geometry(g, out);
-    return PH_OK;
-}
+// the family's description for the shared scaffold
+struct DecodeFam {
+    typedef ph_decode_cfg Cfg; typedef ::Geo Geo; typedef ph_decode_geometry Geometry; typedef ph_decode Plan;
+    static constexpr auto resolve = &::resolve;
+    static constexpr auto fill_geometry = &::fill_geometry;
+};
 
-extern "C" int ph_decode_info(const ph_decode* p, ph_decode_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    fill_geometry(p->g, out);
-    return PH_OK;
-}
+extern "C" size_t ph_decode_workspace_bytes(const ph_decode_cfg* cfg) { return plan::workspace_bytes<DecodeFam>(cfg, __func__); }
+
+extern "C" int ph_decode_geometry_of(const ph_decode_cfg* cfg, ph_decode_geometry* out) { return plan::geometry_of<DecodeFam>(cfg, out, __func__); }
+
+extern "C" int ph_decode_info(const ph_decode* p, ph_decode_geometry* out) { return plan::info<DecodeFam>(p, out, __func__); }
 
 extern "C" void ph_decode_destroy(ph_decode* p) { delete p; }
 

@@ -196,8 +196,6 @@ __global__ __launch_bounds__(FL_THREADS) void k_fpn_lateral(const FLArgs a) {
     }
 }
 
-static bool fl_size_rule(int fine, int coarse) { return fine == 2 * coarse || fine == 2 * coarse - 1; }
-
 extern "C" int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
                               const uint16_t* coarse, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
                               void* stream) {
@@ -208,7 +206,7 @@ extern "C" int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, in
     PH_CHECK_ARG(x_dtype == PH_OUT_F32 || x_dtype == PH_OUT_BF16 || x_dtype == PH_OUT_F16, "x_dtype must be PH_OUT_F32, PH_OUT_BF16 or PH_OUT_F16");
     PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_SPLIT || prec == PH_PREC_F16, "prec must be PH_PREC_BF16, PH_PREC_SPLIT or PH_PREC_F16");
     if (coarse) {
-        PH_CHECK_ARG(Hc > 0 && Wc > 0 && fl_size_rule(H, Hc) && fl_size_rule(W, Wc),
+        PH_CHECK_ARG(Hc > 0 && Wc > 0 && ph_fpn_size_rule(H, Hc) && ph_fpn_size_rule(W, Wc),
                      "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1 (the sizes at which the integer nearest index is torch's)");
         PH_CHECK_ARG(((uintptr_t)coarse & 15) == 0, "coarse must be 16-byte aligned");
     }

@@ -1,10 +1,8 @@
 // The FPN as a native object (include/polyhead.h ph_fpn_cfg .. ph_fpn_plan_run): the parameter packing of fpn.FPN._pack through the
 // shared packer (ph_wpack.hip), and the geometry rules, the buffer plan and the launch sequence of engine.FpnPlan.  Host code only:
 // it calls the other entry points of this library on the caller's stream; pack / create / run allocate no device memory, do not
-// synchronise and read no environment variable.
-#include <new>
-
-#include "ph_common.h"
+// synchronise and read no environment variable.  The pack / create / info scaffold is the shared one (ph_plan_inl.h).
+#include "ph_plan_inl.h"
 
 // ---------------------------------------------------------------------------------------------
 // parameter table (polyhead.h: the reference's state_dict names of FPN, in state_dict order); piece i of the pack is parameter i
@@ -15,7 +13,6 @@ static const char* const kParamNames[PH_FPN_NPARAMS] = {
     "fpn_convs.2.conv.weight", "fpn_convs.2.conv.bias", "fpn_convs.3.conv.weight", "fpn_convs.3.conv.bias"};
 
 static bool k_ok(int k) { return k >= 64 && k <= 4096 && k % 64 == 0; }
-static bool size_rule(int fine, int coarse) { return fine == 2 * coarse || fine == 2 * coarse - 1; }      // ph_fpn_lateral's
 
 // ---------------------------------------------------------------------------------------------
 // geometry: resolve() is the one rule of the native plan (cfg checks, pack pieces, workspace pieces)
@@ -39,17 +36,13 @@ static int resolve(const ph_fpn_cfg* c, FGeo& g, const char* fn) {
     }
     if ((int64_t)g.h[0] * g.w[0] > (1ll << 26)) { ph_set_error("%s: h * w of level 0 must be <= 2^26", fn); return PH_EUNSUPPORTED; }
     for (int l = 0; l < 3; ++l)
-        if (!size_rule(g.h[l], g.h[l + 1]) || !size_rule(g.w[l], g.w[l + 1])) {
+        if (!ph_fpn_size_rule(g.h[l], g.h[l + 1]) || !ph_fpn_size_rule(g.w[l], g.w[l + 1])) {      // ph_fpn_lateral's
             ph_set_error("%s: level %d (%d, %d) over level %d (%d, %d): each size must be 2 n or 2 n - 1 of the coarser level's (the sizes "
                          "at which the integer nearest index is torch's)", fn, l, g.h[l], g.w[l], l + 1, g.h[l + 1], g.w[l + 1]);
             return PH_EUNSUPPORTED;
         }
-    switch (c->mode) {   // ph_neck_cfg.mode's mapping (engine.KHEAD_PREC)
-        case PH_MODE_FP16: g.prec = PH_PREC_F16; break;
-        case PH_MODE_BF16: g.prec = PH_PREC_BF16; break;
-        case PH_MODE_FP32: case PH_MODE_MIXED: case PH_MODE_MIXED16: g.prec = PH_PREC_SPLIT; break;
-        default: ph_set_error("%s: bad mode", fn); return PH_EINVAL;
-    }
+    g.prec = ph_mode_grade(c->mode);
+    if (g.prec < 0) { ph_set_error("%s: bad mode", fn); return PH_EINVAL; }
     g.P = g.prec == PH_PREC_SPLIT ? 2 : 1;
     g.x_dtype = c->x_dtype;
     if (!(g.x_dtype == PH_OUT_F32 || g.x_dtype == PH_OUT_BF16 || g.x_dtype == PH_OUT_F16)) {
@@ -113,39 +106,9 @@ extern "C" int64_t ph_fpn_param_numel(const ph_fpn_cfg* cfg, int index) {
     return k_ok(cfg->k[index / 2]) ? (int64_t)256 * cfg->k[index / 2] : -1;
 }
 
-extern "C" size_t ph_fpn_pack_bytes(const ph_fpn_cfg* cfg) {
-    FGeo g;
-    if (resolve(cfg, g, "ph_fpn_pack_bytes")) return 0;
-    return g.pack_total;
-}
-
-extern "C" int ph_fpn_pack_layout(const ph_fpn_cfg* cfg, ph_fpn_layout* layout) {
-    FGeo g;
-    const int rc = resolve(cfg, g, "ph_fpn_pack_layout");
-    if (rc) return rc;
-    PH_CHECK_ARG(layout != nullptr, "null layout");
-    *layout = g.lay;
-    return PH_OK;
-}
-
-extern "C" int ph_fpn_pack(const ph_fpn_cfg* cfg, const float* const* params, void* pack, void* stream) {
-    FGeo g;
-    const int rc = resolve(cfg, g, "ph_fpn_pack");
-    if (rc) return rc;
-    PH_CHECK_ARG(params && pack, "null params or pack");
-    for (int i = 0; i < PH_FPN_NPARAMS; ++i)
-        if (!params[i]) { ph_set_error("ph_fpn_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    PhPackTable t{};
-    build_table(g, t);
-    for (int i = 0; i < PH_FPN_NPARAMS; ++i) t.p[i] = params[i];
-    return ph_pack_pieces("ph_fpn_pack", t, pack, 2048, stream);
-}
-
-extern "C" size_t ph_fpn_plan_workspace_bytes(const ph_fpn_cfg* cfg) {
-    FGeo g;
-    if (resolve(cfg, g, "ph_fpn_plan_workspace_bytes")) return 0;
-    return g.total;
+static void fill_geometry(const FGeo& g, ph_fpn_geometry* out) {
+    out->P = g.P; out->prec = g.prec;
+    for (int l = 0; l < 4; ++l) out->tile_rows[l] = g.tile_rows[l];
 }
 
 struct ph_fpn_plan {
@@ -154,41 +117,34 @@ struct ph_fpn_plan {
     char* ws;
 };
 
+// the family's description for the shared scaffold
+struct FpnFam {
+    typedef ph_fpn_cfg Cfg; typedef FGeo Geo; typedef ph_fpn_layout Layout; typedef ph_fpn_geometry Geometry; typedef ph_fpn_plan Plan;
+    static constexpr auto resolve = &::resolve;
+    static constexpr auto build_table = &::build_table;
+    static constexpr auto fill_geometry = &::fill_geometry;
+    static int nparams(const FGeo&) { return PH_FPN_NPARAMS; }
+    static const char* param_name(const ph_fpn_cfg*, int i) { return kParamNames[i]; }
+    static constexpr unsigned kPackBlocks = 2048;
+};
+
+extern "C" size_t ph_fpn_pack_bytes(const ph_fpn_cfg* cfg) { return plan::pack_bytes<FpnFam>(cfg, __func__); }
+
+extern "C" int ph_fpn_pack_layout(const ph_fpn_cfg* cfg, ph_fpn_layout* layout) { return plan::pack_layout<FpnFam>(cfg, layout, __func__); }
+
+extern "C" int ph_fpn_pack(const ph_fpn_cfg* cfg, const float* const* params, void* pack, void* stream) {
+    return plan::pack<FpnFam>(cfg, params, pack, stream, __func__);
+}
+
+extern "C" size_t ph_fpn_plan_workspace_bytes(const ph_fpn_cfg* cfg) { return plan::workspace_bytes<FpnFam>(cfg, __func__); }
+
 extern "C" int ph_fpn_plan_create(const ph_fpn_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_fpn_plan** out) {
-    FGeo g;
-    const int rc = resolve(cfg, g, "ph_fpn_plan_create");
-    if (rc) return rc;
-    PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
-    *out = nullptr;
-    PH_RUN(ph_check_buffers("ph_fpn_plan_create", pack, workspace, workspace_bytes, g.total));
-    ph_fpn_plan* p = new (std::nothrow) ph_fpn_plan;
-    if (!p) { ph_set_error("ph_fpn_plan_create: out of host memory"); return PH_EINVAL; }
-    p->g = g;
-    p->pack = (const char*)pack;
-    p->ws = (char*)workspace;
-    *out = p;
-    return PH_OK;
+    return plan::create<FpnFam>(cfg, pack, workspace, workspace_bytes, out, __func__);
 }
 
-static void fill_geometry(const FGeo& g, ph_fpn_geometry* out) {
-    out->P = g.P; out->prec = g.prec;
-    for (int l = 0; l < 4; ++l) out->tile_rows[l] = g.tile_rows[l];
-}
+extern "C" int ph_fpn_geometry_of(const ph_fpn_cfg* cfg, ph_fpn_geometry* out) { return plan::geometry_of<FpnFam>(cfg, out, __func__); }
 
-extern "C" int ph_fpn_geometry_of(const ph_fpn_cfg* cfg, ph_fpn_geometry* out) {
-    FGeo g;
-    const int rc = resolve(cfg, g, "ph_fpn_geometry_of");
-    if (rc) return rc;
-    PH_CHECK_ARG(out != nullptr, "null out");
-    fill_geometry(g, out);
-    return PH_OK;
-}
-
-extern "C" int ph_fpn_plan_info(const ph_fpn_plan* p, ph_fpn_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    fill_geometry(p->g, out);
-    return PH_OK;
-}
+extern "C" int ph_fpn_plan_info(const ph_fpn_plan* p, ph_fpn_geometry* out) { return plan::info<FpnFam>(p, out, __func__); }
 
 extern "C" void ph_fpn_plan_destroy(ph_fpn_plan* p) { delete p; }
 

@@ -93,8 +93,6 @@ __global__ __launch_bounds__(256) void k_nchw_channel_final(const double* __rest
     out[c] = (float)acc;
 }
 
-bool size_rule(int fine, int coarse) { return coarse > 0 && (fine == 2 * coarse || fine == 2 * coarse - 1); }
-
 unsigned row_blocks(int64_t rows) {
     const int64_t blocks = (rows + 3) / 4;
     return (unsigned)(blocks > 65536 ? 65536 : blocks);
@@ -123,7 +121,7 @@ extern "C" int ph_map_x_map_t_wide(const float* G, const float* X, float* partia
 extern "C" int ph_nearest_up_add(float* fine /* [planes][H][W], in place */, const float* coarse /* [planes][Hc][Wc] */, int64_t planes, int H,
                                  int W, int Hc, int Wc, void* stream) {
     PH_CHECK_ARG(fine && coarse && planes > 0 && H > 0 && W > 0, "bad pointer or size");
-    PH_CHECK_ARG(size_rule(H, Hc) && size_rule(W, Wc), "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1");
+    PH_CHECK_ARG(Hc > 0 && Wc > 0 && ph_fpn_size_rule(H, Hc) && ph_fpn_size_rule(W, Wc), "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1");
     const int64_t rows = planes * H;
     hipLaunchKernelGGL(k_nearest_up_add, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, fine, coarse, rows, H, W, Hc, Wc);
     PH_CHECK_LAUNCH();
@@ -133,7 +131,7 @@ extern "C" int ph_nearest_up_add(float* fine /* [planes][H][W], in place */, con
 extern "C" int ph_nearest_up_add_bwd(const float* g_fine /* [planes][H][W] */, float* g_coarse /* [planes][Hc][Wc] */, int64_t planes, int H,
                                      int W, int Hc, int Wc, int accumulate, void* stream) {
     PH_CHECK_ARG(g_fine && g_coarse && planes > 0 && H > 0 && W > 0, "bad pointer or size");
-    PH_CHECK_ARG(size_rule(H, Hc) && size_rule(W, Wc), "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1");
+    PH_CHECK_ARG(Hc > 0 && Wc > 0 && ph_fpn_size_rule(H, Hc) && ph_fpn_size_rule(W, Wc), "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1");
     const int64_t rows = planes * Hc;
     if (accumulate)
         hipLaunchKernelGGL(k_nearest_up_add_bwd<true>, dim3(row_blocks(rows)), dim3(256), 0, (hipStream_t)stream, g_fine, g_coarse, rows, H, W, Hc, Wc);

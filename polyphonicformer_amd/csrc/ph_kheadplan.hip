@@ -1,10 +1,9 @@
 // A1 as a native object (include/polyhead.h ph_khead_cfg .. ph_khead_plan_timeouts): the parameter packing of
 // engine.KernelHeadPack as one HIP kernel, and the geometry rules, the buffer plan and the launch sequence of
 // engine.KernelHeadPlan.  Host code only calls the other entry points of this library, on the caller's stream; pack / create /
-// run allocate no device memory, do not synchronise and read no environment variable.
-#include <new>
-
-#include "ph_common.h"
+// run allocate no device memory, do not synchronise and read no environment variable.  The pack / create / info scaffold is the
+// shared one (ph_plan_inl.h).
+#include "ph_plan_inl.h"
 
 #pragma clang fp contract(off)
 
@@ -50,12 +49,8 @@ static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn, bool need_dev
     if (!(g.n_seg > 0 && g.n_seg <= 256)) { ph_set_error("%s: num_classes must be 1 .. 256", fn); return PH_EINVAL; }
     if (!(g.n_thing >= 0 && g.n_thing <= g.n_seg)) { ph_set_error("%s: num_thing_classes must be 0 .. num_classes", fn); return PH_EINVAL; }
     if (!(g.groups > 0 && 256 % g.groups == 0)) { ph_set_error("%s: groups must divide 256", fn); return PH_EINVAL; }
-    switch (c->mode) {   // engine.KHEAD_PREC
-        case PH_MODE_FP16: g.prec = PH_PREC_F16; break;
-        case PH_MODE_BF16: g.prec = PH_PREC_BF16; break;
-        case PH_MODE_FP32: case PH_MODE_MIXED: case PH_MODE_MIXED16: g.prec = PH_PREC_SPLIT; break;
-        default: ph_set_error("%s: bad mode", fn); return PH_EINVAL;
-    }
+    g.prec = ph_mode_grade(c->mode);
+    if (g.prec < 0) { ph_set_error("%s: bad mode", fn); return PH_EINVAL; }
     g.P = g.prec == PH_PREC_SPLIT ? 2 : 1;
     if (!(c->logit_dtype == PH_OUT_F32 || c->logit_dtype == PH_OUT_F16)) { ph_set_error("%s: logit_dtype must be PH_OUT_F32 or PH_OUT_F16", fn); return PH_EINVAL; }
     if (!(c->onepass == PH_KNOB_AUTO || c->onepass == PH_KNOB_ON || c->onepass == PH_KNOB_OFF) || c->nsplit < 0) {
@@ -159,39 +154,9 @@ extern "C" int64_t ph_khead_param_numel(const ph_khead_cfg* cfg, int index) {
     return param_numel(cfg, index);
 }
 
-extern "C" size_t ph_khead_pack_bytes(const ph_khead_cfg* cfg) {
-    KGeo g;
-    if (resolve(cfg, g, "ph_khead_pack_bytes", false)) return 0;
-    return g.pack_total;
-}
-
-extern "C" int ph_khead_pack_layout(const ph_khead_cfg* cfg, ph_khead_layout* layout) {
-    KGeo g;
-    const int rc = resolve(cfg, g, "ph_khead_pack_layout", false);
-    if (rc) return rc;
-    PH_CHECK_ARG(layout != nullptr, "null layout");
-    *layout = g.lay;
-    return PH_OK;
-}
-
-extern "C" int ph_khead_pack(const ph_khead_cfg* cfg, const float* const* params, void* pack, void* stream) {
-    KGeo g;
-    const int rc = resolve(cfg, g, "ph_khead_pack", false);
-    if (rc) return rc;
-    PH_CHECK_ARG(params && pack, "null params or pack");
-    for (int i = 0; i < PH_KHEAD_NPARAMS; ++i)
-        if (!params[i]) { ph_set_error("ph_khead_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    PhPackTable t{};
-    build_table(g, t);
-    for (int i = 0; i < PH_KHEAD_NPARAMS; ++i) t.p[i] = params[i];
-    return ph_pack_pieces("ph_khead_pack", t, pack, 1024, stream);
-}
-
-extern "C" size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg) {
-    KGeo g;
-    if (resolve(cfg, g, "ph_khead_plan_workspace_bytes", true)) return 0;
-    return g.total;
+static void fill_geometry(const KGeo& g, ph_khead_geometry* out) {
+    out->onepass = g.onepass; out->nsplit = g.nsplit; out->N = g.N; out->Npad = g.Npad; out->HWp = (int32_t)g.HWp; out->P = g.P;
+    out->prec = g.prec; out->n_stuff = g.n_stuff;
 }
 
 struct ph_khead_plan {
@@ -200,42 +165,42 @@ struct ph_khead_plan {
     char* ws;
 };
 
-extern "C" int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes,
-                                    ph_khead_plan** out) {
-    KGeo g;
-    const int rc = resolve(cfg, g, "ph_khead_plan_create", true);
-    if (rc) return rc;
-    PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
-    *out = nullptr;
-    PH_RUN(ph_check_buffers("ph_khead_plan_create", pack, workspace, workspace_bytes, g.total));
-    ph_khead_plan* p = new (std::nothrow) ph_khead_plan;
-    if (!p) { ph_set_error("ph_khead_plan_create: out of host memory"); return PH_EINVAL; }
-    p->g = g;
-    p->pack = (const char*)pack;
-    p->ws = (char*)workspace;
-    *out = p;
-    return PH_OK;
+// the family's descriptions for the shared scaffold: the pack calls resolve without the device, the plan calls with it
+struct KheadPackFam {
+    typedef ph_khead_cfg Cfg; typedef KGeo Geo; typedef ph_khead_layout Layout; typedef ph_khead_geometry Geometry; typedef ph_khead_plan Plan;
+    static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn) { return ::resolve(c, g, fn, false); }
+    static constexpr auto build_table = &::build_table;
+    static constexpr auto fill_geometry = &::fill_geometry;
+    static int nparams(const KGeo&) { return PH_KHEAD_NPARAMS; }
+    static const char* param_name(const ph_khead_cfg*, int i) { return kParamNames[i]; }
+    static constexpr unsigned kPackBlocks = 1024;
+};
+struct KheadPlanFam : KheadPackFam {
+    static int resolve(const ph_khead_cfg* c, KGeo& g, const char* fn) { return ::resolve(c, g, fn, true); }
+};
+
+extern "C" size_t ph_khead_pack_bytes(const ph_khead_cfg* cfg) { return plan::pack_bytes<KheadPackFam>(cfg, __func__); }
+
+extern "C" int ph_khead_pack_layout(const ph_khead_cfg* cfg, ph_khead_layout* layout) {
+    return plan::pack_layout<KheadPackFam>(cfg, layout, __func__);
 }
 
-static void fill_geometry(const KGeo& g, ph_khead_geometry* out) {
-    out->onepass = g.onepass; out->nsplit = g.nsplit; out->N = g.N; out->Npad = g.Npad; out->HWp = (int32_t)g.HWp; out->P = g.P;
-    out->prec = g.prec; out->n_stuff = g.n_stuff;
+extern "C" int ph_khead_pack(const ph_khead_cfg* cfg, const float* const* params, void* pack, void* stream) {
+    return plan::pack<KheadPackFam>(cfg, params, pack, stream, __func__);
+}
+
+extern "C" size_t ph_khead_plan_workspace_bytes(const ph_khead_cfg* cfg) { return plan::workspace_bytes<KheadPlanFam>(cfg, __func__); }
+
+extern "C" int ph_khead_plan_create(const ph_khead_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes,
+                                    ph_khead_plan** out) {
+    return plan::create<KheadPlanFam>(cfg, pack, workspace, workspace_bytes, out, __func__);
 }
 
 extern "C" int ph_khead_geometry_of(const ph_khead_cfg* cfg, ph_khead_geometry* out) {
-    KGeo g;
-    const int rc = resolve(cfg, g, "ph_khead_geometry_of", true);
-    if (rc) return rc;
-    PH_CHECK_ARG(out != nullptr, "null out");
-    fill_geometry(g, out);
-    return PH_OK;
+    return plan::geometry_of<KheadPlanFam>(cfg, out, __func__);
 }
 
-extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    fill_geometry(p->g, out);
-    return PH_OK;
-}
+extern "C" int ph_khead_plan_info(const ph_khead_plan* p, ph_khead_geometry* out) { return plan::info<KheadPlanFam>(p, out, __func__); }
 
 extern "C" void ph_khead_plan_destroy(ph_khead_plan* p) { delete p; }
 

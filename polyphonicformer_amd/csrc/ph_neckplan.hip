@@ -1,12 +1,11 @@
 // N3 as a native object (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs): the parameter packing of
 // SemanticFPNWrapper._pack as one HIP kernel, the sine positional encoding as one HIP kernel, and the geometry rules, the buffer
 // plan and the launch sequence of engine.NeckPlan.  Host code only calls the other entry points of this library, on the caller's
-// stream(s); pack / posenc / create / run allocate no device memory, do not synchronise and read no environment variable.
+// stream(s); pack / posenc / create / run allocate no device memory, do not synchronise and read no environment variable.  The pack /
+// create / info scaffold is the shared one (ph_plan_inl.h).
 #include <math.h>
 
-#include <new>
-
-#include "ph_common.h"
+#include "ph_plan_inl.h"
 
 #pragma clang fp contract(off)
 
@@ -69,12 +68,8 @@ static int resolve(const ph_neck_cfg* c, NGeo& g, const char* fn) {
         return PH_EUNSUPPORTED;
     }
     if (!(g.groups > 0 && 256 % g.groups == 0)) { ph_set_error("%s: groups must divide 256", fn); return PH_EINVAL; }
-    switch (c->mode) {   // engine.KHEAD_PREC
-        case PH_MODE_FP16: g.prec = PH_PREC_F16; break;
-        case PH_MODE_BF16: g.prec = PH_PREC_BF16; break;
-        case PH_MODE_FP32: case PH_MODE_MIXED: case PH_MODE_MIXED16: g.prec = PH_PREC_SPLIT; break;
-        default: ph_set_error("%s: bad mode", fn); return PH_EINVAL;
-    }
+    g.prec = ph_mode_grade(c->mode);
+    if (g.prec < 0) { ph_set_error("%s: bad mode", fn); return PH_EINVAL; }
     g.P = g.prec == PH_PREC_SPLIT ? 2 : 1;
     if (!(g.num_outs >= 1 && g.num_outs <= 3)) { ph_set_error("%s: num_outs must be 1 .. 3 (conv_pred + 0 .. 2 aux convs)", fn); return PH_EINVAL; }
     if (!(g.pos_level >= -1 && g.pos_level <= 3)) { ph_set_error("%s: pos_level must be 0 .. 3, or -1 for none", fn); return PH_EINVAL; }
@@ -213,33 +208,35 @@ extern "C" int64_t ph_neck_param_numel(const ph_neck_cfg* cfg, int index) {
     return index % 3 == 0 ? (int64_t)256 * 256 * conv_taps(index / 3) : 256;
 }
 
-extern "C" size_t ph_neck_pack_bytes(const ph_neck_cfg* cfg) {
-    NGeo g;
-    if (resolve(cfg, g, "ph_neck_pack_bytes")) return 0;
-    return g.pack_total;
+static void fill_geometry(const NGeo& g, ph_neck_geometry* out) {
+    out->Ho = g.Ho; out->Wo = g.Wo; out->HWp = (int32_t)g.HWp; out->P = g.P; out->prec = g.prec; out->fused_out = g.fused_out;
+    out->c16 = g.c16; out->tower_buffers = g.tower_buffers; out->nconvs = g.nconvs;
+    for (int i = 0; i < NCONV_MAX; ++i) out->tile_rows[i] = g.tile_rows[i];
 }
 
-extern "C" int ph_neck_pack_layout(const ph_neck_cfg* cfg, ph_neck_layout* layout) {
+struct ph_neck_plan {
     NGeo g;
-    const int rc = resolve(cfg, g, "ph_neck_pack_layout");
-    if (rc) return rc;
-    PH_CHECK_ARG(layout != nullptr, "null layout");
-    *layout = g.lay;
-    return PH_OK;
-}
+    const char* pack;
+    char* ws;
+};
+
+// the family's description for the shared scaffold
+struct NeckFam {
+    typedef ph_neck_cfg Cfg; typedef NGeo Geo; typedef ph_neck_layout Layout; typedef ph_neck_geometry Geometry; typedef ph_neck_plan Plan;
+    static constexpr auto resolve = &::resolve;
+    static constexpr auto build_table = &::build_table;
+    static constexpr auto fill_geometry = &::fill_geometry;
+    static int nparams(const NGeo& g) { return 3 * g.nconvs; }
+    static const char* param_name(const ph_neck_cfg*, int i) { return kParamNames[i]; }
+    static constexpr unsigned kPackBlocks = 2048;
+};
+
+extern "C" size_t ph_neck_pack_bytes(const ph_neck_cfg* cfg) { return plan::pack_bytes<NeckFam>(cfg, __func__); }
+
+extern "C" int ph_neck_pack_layout(const ph_neck_cfg* cfg, ph_neck_layout* layout) { return plan::pack_layout<NeckFam>(cfg, layout, __func__); }
 
 extern "C" int ph_neck_pack(const ph_neck_cfg* cfg, const float* const* params, void* pack, void* stream) {
-    NGeo g;
-    const int rc = resolve(cfg, g, "ph_neck_pack");
-    if (rc) return rc;
-    PH_CHECK_ARG(params && pack, "null params or pack");
-    for (int i = 0; i < 3 * g.nconvs; ++i)
-        if (!params[i]) { ph_set_error("ph_neck_pack: parameter %d (%s) is NULL", i, kParamNames[i]); return PH_EINVAL; }
-    PH_CHECK_ARG(((uintptr_t)pack & 255) == 0, "pack must be 256-byte aligned");
-    PhPackTable t{};
-    build_table(g, t);
-    for (int i = 0; i < 3 * g.nconvs; ++i) t.p[i] = params[i];
-    return ph_pack_pieces("ph_neck_pack", t, pack, 2048, stream);
+    return plan::pack<NeckFam>(cfg, params, pack, stream, __func__);
 }
 
 extern "C" int ph_neck_posenc(int H, int W, int num_feats, double temperature, double scale, double eps, float* out, void* stream) {
@@ -253,55 +250,16 @@ extern "C" int ph_neck_posenc(int H, int W, int num_feats, double temperature, d
     return PH_OK;
 }
 
-extern "C" size_t ph_neck_plan_workspace_bytes(const ph_neck_cfg* cfg) {
-    NGeo g;
-    if (resolve(cfg, g, "ph_neck_plan_workspace_bytes")) return 0;
-    return g.total;
-}
-
-struct ph_neck_plan {
-    NGeo g;
-    const char* pack;
-    char* ws;
-};
+extern "C" size_t ph_neck_plan_workspace_bytes(const ph_neck_cfg* cfg) { return plan::workspace_bytes<NeckFam>(cfg, __func__); }
 
 extern "C" int ph_neck_plan_create(const ph_neck_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes,
                                    ph_neck_plan** out) {
-    NGeo g;
-    const int rc = resolve(cfg, g, "ph_neck_plan_create");
-    if (rc) return rc;
-    PH_CHECK_ARG(out && pack && workspace, "null pack, workspace or out");
-    *out = nullptr;
-    PH_RUN(ph_check_buffers("ph_neck_plan_create", pack, workspace, workspace_bytes, g.total));
-    ph_neck_plan* p = new (std::nothrow) ph_neck_plan;
-    if (!p) { ph_set_error("ph_neck_plan_create: out of host memory"); return PH_EINVAL; }
-    p->g = g;
-    p->pack = (const char*)pack;
-    p->ws = (char*)workspace;
-    *out = p;
-    return PH_OK;
+    return plan::create<NeckFam>(cfg, pack, workspace, workspace_bytes, out, __func__);
 }
 
-static void fill_geometry(const NGeo& g, ph_neck_geometry* out) {
-    out->Ho = g.Ho; out->Wo = g.Wo; out->HWp = (int32_t)g.HWp; out->P = g.P; out->prec = g.prec; out->fused_out = g.fused_out;
-    out->c16 = g.c16; out->tower_buffers = g.tower_buffers; out->nconvs = g.nconvs;
-    for (int i = 0; i < NCONV_MAX; ++i) out->tile_rows[i] = g.tile_rows[i];
-}
+extern "C" int ph_neck_geometry_of(const ph_neck_cfg* cfg, ph_neck_geometry* out) { return plan::geometry_of<NeckFam>(cfg, out, __func__); }
 
-extern "C" int ph_neck_geometry_of(const ph_neck_cfg* cfg, ph_neck_geometry* out) {
-    NGeo g;
-    const int rc = resolve(cfg, g, "ph_neck_geometry_of");
-    if (rc) return rc;
-    PH_CHECK_ARG(out != nullptr, "null out");
-    fill_geometry(g, out);
-    return PH_OK;
-}
-
-extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) {
-    PH_CHECK_ARG(p && out, "null plan or out");
-    fill_geometry(p->g, out);
-    return PH_OK;
-}
+extern "C" int ph_neck_plan_info(const ph_neck_plan* p, ph_neck_geometry* out) { return plan::info<NeckFam>(p, out, __func__); }
 
 extern "C" void ph_neck_plan_destroy(ph_neck_plan* p) { delete p; }
 

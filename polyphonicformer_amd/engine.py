@@ -9,6 +9,7 @@ Per frame-batch the launch sequence is
 
 No step synchronises or allocates once a `DecodePlan` exists, so the whole sequence can be captured
 into a HIP graph (`DecodePlan.capture`)."""
+import contextlib
 import ctypes as C
 import math
 
@@ -458,9 +459,10 @@ class DecodePlan:
 
 
 # ---- the S-stage plan as a native object (include/polyhead.h ph_decode_*) -----------------------------------
-def _gather_params(module, device, count, name_of, numel_of):
+def _gather_params(module, device, count, name_of, numel_of, slots=None):
     """the `count` parameters a device packer reads, by the names of its table (`name_of(i)`), as fp32 device tensors of
-    `numel_of(i)` elements -> (the tensors, kept alive by the caller until the launch is queued; the host array of their pointers)"""
+    `numel_of(i)` elements -> (the tensors, kept alive by the caller until the launch is queued; the host array of their pointers,
+    `slots` long with NULL behind the parameters when the table has more entries than this cfg reads)"""
     sd = module.state_dict() if hasattr(module, "state_dict") else module
     params = []
     for i in range(count):
@@ -469,20 +471,22 @@ def _gather_params(module, device, count, name_of, numel_of):
         if t.numel() != numel_of(i):
             raise _lib.PolyheadError(f"{name}: {t.numel()} elements, the cfg needs {numel_of(i)}")
         params.append(t)
-    return params, (C.c_void_p * count)(*[t.data_ptr() for t in params])
+    return params, (C.c_void_p * (slots or count))(*[t.data_ptr() for t in params])
 
 
-def _pack_on_device(params_from, cfg, device, bytes_fn, nparams, name_of, numel_of, pack_fn, what):
-    """the body of every native_*_pack* function: the `nparams` parameters of `params_from` (a module or a state_dict; names and
-    sizes from the library's table, `name_of(i)` / `numel_of(cfg, i)`) packed by `pack_fn` (`what`: its name) on the current stream
-    of `device` -> a new uint8 tensor of `bytes_fn(cfg)` bytes"""
-    nbytes = bytes_fn(C.byref(cfg))
+def _pack_on_device(params_from, cfg, device, symbols, nparams, slots=None, name_takes_cfg=False):
+    """the body of every native_*_pack* function: the `nparams` parameters of `params_from` (a module or a state_dict) packed on the
+    current stream of `device` -> a new uint8 tensor.  `symbols`: the library's (pack bytes, parameter name, parameter numel, pack)"""
+    lib, ref = _lib.load(), C.byref(cfg)
+    bytes_fn, name_fn, numel_fn, pack_fn = (getattr(lib, s) for s in symbols)
+    nbytes = bytes_fn(ref)
     if nbytes == 0:
-        raise _cfg_error(bytes_fn.__name__)
-    params, ptrs = _gather_params(params_from, device, nparams, name_of, lambda i: numel_of(C.byref(cfg), i))
+        raise _cfg_error(symbols[0])
+    name_of = (lambda i: name_fn(ref, i)) if name_takes_cfg else name_fn
+    params, ptrs = _gather_params(params_from, device, nparams, name_of, lambda i: numel_fn(ref, i), slots)
     blob = torch.empty((nbytes,), dtype=torch.uint8, device=device)
     with torch.cuda.device(device):
-        _lib.check(pack_fn(C.byref(cfg), ptrs, _lib.ptr(blob), _lib.stream_ptr()), what)
+        _lib.check(pack_fn(ref, ptrs, _lib.ptr(blob), _lib.stream_ptr()), symbols[3])
     return blob
 
 
@@ -495,6 +499,31 @@ def _pack_piece(blob, layout, i, dtype, shape):
 # a1's / the neck's grade of a cfg's mode code (as KHEAD_PREC maps the names), and the mode's name
 _GRADE_OF_MODE = {code: KHEAD_PREC[name] for name, code in _lib.PH_MODE.items()}
 _MODE_NAME = {code: name for name, code in _lib.PH_MODE.items() if name != "split"}
+
+
+class _NativePack:
+    """the base of the four native packs: one device buffer packed by the library, its layout asked from the library,
+    a copy of its cfg, `mode` / `prec` / `P`, and the views a family cuts from it in `_pieces(cfg)` with `piece`.  Per family:
+    `_symbols`, the library's (pack bytes, parameter name, parameter numel, pack, pack layout); `_layout_type`; `_nparams(cfg)`;
+    `_slots`, the length of the pointer table when it is longer than that"""
+    _symbols, _layout_type, _slots, _name_takes_cfg = (), None, None, False
+
+    def __init__(self, blob, cfg):
+        lay = self._layout_type()
+        _lib.check(getattr(_lib.load(), self._symbols[4])(C.byref(cfg), C.byref(lay)), self._symbols[4])
+        self.blob, self.layout, self.cfg = blob, lay, type(cfg).from_buffer_copy(bytes(cfg))
+        self.mode = getattr(cfg, "mode", None)                       # the track head's cfg carries its grade itself
+        self.prec = cfg.prec if self.mode is None else _GRADE_OF_MODE[self.mode]
+        self.P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
+        self._pieces(cfg)
+
+    def piece(self, i, dtype, shape):
+        return _pack_piece(self.blob, self.layout, i, dtype, shape)
+
+    @classmethod
+    def pack_on_device(cls, module, cfg, device):
+        """`module`'s parameters (a module or its state_dict) packed on the device by the family's packer -> the pack"""
+        return cls(_pack_on_device(module, cfg, device, cls._symbols[:4], cls._nparams(cfg), cls._slots, cls._name_takes_cfg), cfg)
 
 
 class _OwnsHandles:
@@ -511,11 +540,67 @@ class _OwnsHandles:
     __del__ = _destroy
 
 
+def _on(dev):
+    """the device context of a plan's library calls (the CU count the library asks for is the current device's); none off the GPU"""
+    return torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext()
+
+
+class _NativePlan(_OwnsHandles):
+    """the base of the native plans over `self.cfg`, `self.device` and `self.workspace`.  Per family: `_symbols`, the
+    library's (workspace bytes, create, info); `_geometry_type`; `_destroy_symbol`; `_zeroed`, the workspace's contract"""
+    _symbols, _geometry_type, _zeroed = (), None, False
+
+    def _alloc_workspace(self):
+        """the workspace of `self.cfg`, or the library's words about the cfg"""
+        with _on(self.device):
+            nbytes = getattr(_lib.load(), self._symbols[0])(C.byref(self.cfg))
+            if nbytes == 0:
+                raise _cfg_error(self._symbols[0])
+            self.workspace = (torch.zeros if self._zeroed else torch.empty)((nbytes,), dtype=torch.uint8, device=self.device)
+
+    def _create(self, pack, **fields):
+        """a native plan of `self.cfg`, these fields replaced, over `pack` (a pointer, or an array of them) and the workspace"""
+        cfg = type(self.cfg).from_buffer_copy(bytes(self.cfg))
+        for k, v in fields.items():
+            setattr(cfg, k, int(v))
+        h = C.c_void_p()
+        with _on(self.device):
+            _lib.check(getattr(_lib.load(), self._symbols[1])(C.byref(cfg), pack, _lib.ptr(self.workspace), self.workspace.numel(),
+                                                             C.byref(h)), self._symbols[1])
+        return h
+
+    def _handle_of(self, **fields):
+        """the plan of these cfg fields, created on first use: the plans of one object share its workspace -- a run uses one of them"""
+        key = tuple(fields.values())
+        if key not in self._handles:
+            self._handles[key] = self._create(_lib.ptr(self.pack.blob), **fields)
+        return self._handles[key]
+
+    def _info(self, h):
+        geo = self._geometry_type()
+        _lib.check(getattr(_lib.load(), self._symbols[2])(h, C.byref(geo)), self._symbols[2])
+        return geo
+
+
+def _fan_out_towers(streams, device, tower):
+    """the four level towers side by side: streams[l] (made here on first use) waits for the current stream and runs `tower(l)`,
+    the longest chains first, and the current stream waits for all four.  -> the streams"""
+    if streams is None:
+        streams = [torch.cuda.Stream(device=device) for _ in range(4)]
+    cur = torch.cuda.current_stream()
+    for lvl in (0, 3, 2, 1):
+        streams[lvl].wait_stream(cur)
+        with torch.cuda.stream(streams[lvl]):
+            tower(lvl)
+    for st in streams:
+        cur.wait_stream(st)
+    return streams
+
+
 def native_pack_stage(module, cfg, device):
     """one KernelUpdateHead stage's parameters packed on the device by ph_decode_pack_stage -> uint8 tensor (one pack)"""
-    lib = _lib.load()
-    return _pack_on_device(module, cfg, device, lib.ph_decode_pack_bytes, _lib.PH_DECODE_NPARAMS, lib.ph_decode_param_name,
-                           lib.ph_decode_param_numel, lib.ph_decode_pack_stage, "ph_decode_pack_stage")
+    return _pack_on_device(module, cfg, device, ("ph_decode_pack_bytes", "ph_decode_param_name", "ph_decode_param_numel",
+                                                 "ph_decode_pack_stage"), _lib.PH_DECODE_NPARAMS)
 
 
 def native_pack_from(pack, cfg):
@@ -533,11 +618,12 @@ def native_pack_from(pack, cfg):
     return blob
 
 
-class NativeDecodePlan(_OwnsHandles):
+class NativeDecodePlan(_NativePlan):
     """DecodePlan's surface (set_inputs, run, run_from_planes, renew_outputs, outputs, capture / replay) over ONE native call per
     decode (ph_decode_run): the same launch sequence and geometry as the DecodePlan of the same arguments, so the same bits.
     `packs`: StagePacks (re-laid out as native packs once) or native packs (`native_pack_stage`)."""
-    _destroy_symbol = "ph_decode_destroy"
+    _symbols, _geometry_type, _destroy_symbol = ("ph_decode_workspace_bytes", "ph_decode_create", "ph_decode_info"), _lib.DecodeGeometry, \
+        "ph_decode_destroy"
 
     def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False,
                  shares_gpu=False, num_classes=None, ffn_dim=None):
@@ -553,20 +639,10 @@ class NativeDecodePlan(_OwnsHandles):
         else:
             L, F = num_classes, ffn_dim
         self.cfg = native_cfg(B, N, H, W, self.S, L, F, self.mode, out_dtype, frame_invariant, shares_gpu, nsplit)
-        lib = _lib.load()
-        nbytes = lib.ph_decode_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise _cfg_error("ph_decode_workspace_bytes")
+        self._alloc_workspace()
         self.packs = [native_pack_from(p, self.cfg) if isinstance(p, StagePack) else p for p in packs]
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        handle = C.c_void_p()
-        with torch.cuda.device(dev):
-            _lib.check(lib.ph_decode_create(C.byref(self.cfg), (C.c_void_p * self.S)(*[p.data_ptr() for p in self.packs]),
-                                            _lib.ptr(self.workspace), nbytes, C.byref(handle)), "ph_decode_create")
-        self._h = handle
-        geo = _lib.DecodeGeometry()
-        _lib.check(lib.ph_decode_info(self._h, C.byref(geo)), "ph_decode_info")
-        self.geometry = geo
+        self._h = self._create((C.c_void_p * self.S)(*[p.data_ptr() for p in self.packs]))
+        self.geometry = geo = self._info(self._h)
         self.nsplit, self.nsplit_px, self.poolx, self.fused_up = geo.nsplit, geo.nsplit_px, bool(geo.poolx), bool(geo.fused_up)
         Npad, HWp = n_padded(N), hw_padded(self.HW)
         # shapes of the plan's planes and bits (they live in the workspace): what the module API compares a KernelHead hand-off with
@@ -922,18 +998,15 @@ def native_khead_cfg(B, H, W, num_proposals, num_classes, num_thing_classes, cat
                          nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0))
 
 
-class NativeKernelHeadPack:
+class NativeKernelHeadPack(_NativePack):
     """one device buffer packed by ph_khead_pack, and its pieces as views under KernelHeadPack's attribute names (so either plan
     -- KernelHeadPlan or NativeKernelHeadPlan -- runs from it)"""
+    _symbols = ("ph_khead_pack_bytes", "ph_khead_param_name", "ph_khead_param_numel", "ph_khead_pack", "ph_khead_pack_layout")
+    _layout_type, _nparams = _lib.KheadLayout, staticmethod(lambda cfg: _lib.PH_KHEAD_NPARAMS)
 
-    def __init__(self, blob, cfg):
-        lib = _lib.load()
-        lay = _lib.KheadLayout()
-        _lib.check(lib.ph_khead_pack_layout(C.byref(cfg), C.byref(lay)), "ph_khead_pack_layout")
-        self.blob, self.layout = blob, lay
-        self.prec, self.mode = _GRADE_OF_MODE[cfg.mode], cfg.mode
+    def _pieces(self, cfg):
         self.groups, self.n_init, self.n_seg = cfg.groups, cfg.num_proposals, cfg.num_classes
-        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
+        P = self.P
         dt = dict(wplanes=(torch.int16, (P, 3, 256, 256)), gn=(torch.float32, (3, 2, 256)),
                   init_planes=(torch.int16, (P, n_padded(self.n_init), 256)), seg_planes=(torch.int16, (P, n_padded(self.n_seg), 256)),
                   dd_planes=(torch.int16, (P, 32, 256)), seg_bias=(torch.float32, (n_padded(self.n_seg),)), dd_bias=(torch.float32, (32,)),
@@ -942,22 +1015,22 @@ class NativeKernelHeadPack:
                   w_init_f32=(torch.float32, (self.n_init, 256)), w_seg_f32=(torch.float32, (self.n_seg, 256)),
                   w_dd_f32=(torch.float32, (1, 256, 1, 1)))
         for i, name in enumerate(_lib.KPACK_PIECES):
-            setattr(self, name, _pack_piece(blob, lay, i, *dt[name]))
+            setattr(self, name, self.piece(i, *dt[name]))
 
 
 def native_khead_pack(module, cfg, device):
     """KernelHead's own parameters (a module, or a state_dict without the neck's entries) packed on the device by ph_khead_pack"""
-    lib = _lib.load()
-    return NativeKernelHeadPack(_pack_on_device(module, cfg, device, lib.ph_khead_pack_bytes, _lib.PH_KHEAD_NPARAMS, lib.ph_khead_param_name,
-                                                lib.ph_khead_param_numel, lib.ph_khead_pack, "ph_khead_pack"), cfg)
+    return NativeKernelHeadPack.pack_on_device(module, cfg, device)
 
 
-class NativeKernelHeadPlan(_KernelHeadPlanBase, _OwnsHandles):
+class NativeKernelHeadPlan(_KernelHeadPlanBase, _NativePlan):
     """KernelHeadPlan's surface (_KernelHeadPlanBase, run, timeouts, last_run_fell_back and the output attributes) over ONE
     native call per a1 (ph_khead_plan_run): the same launch sequence and geometry as the KernelHeadPlan of the same arguments, so
     the same bits.  `pack`: a NativeKernelHeadPack.  `dense_depth_proposal`: also write depth_proposal [B, N, 256] (what a C caller
     hands to ph_decode_io.q0; the module API keeps the reference's stride-0 view of the weight and needs no launch for it)."""
-    _destroy_symbol = "ph_khead_plan_destroy"
+    _symbols, _geometry_type, _destroy_symbol = ("ph_khead_plan_workspace_bytes", "ph_khead_plan_create", "ph_khead_plan_info"), \
+        _lib.KheadGeometry, "ph_khead_plan_destroy"
+    _zeroed = True      # ONCE: the one-pass launch's hand-off state ends in the sticky time-out words, which no call clears
 
     def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
                  logit_dtype=torch.float32, onepass=None, frame_invariant=False, dense_depth_proposal=False, cfg=None):
@@ -969,20 +1042,9 @@ class NativeKernelHeadPlan(_KernelHeadPlanBase, _OwnsHandles):
         self.device, self.logit_dtype, self.want_f32 = dev, logit_dtype, want_f32
         self.cfg = cfg if cfg is not None else native_khead_cfg(B, H, W, pack.n_init, pack.n_seg, num_thing_classes, cat_stuff,
                                                                 pack.groups, _MODE_NAME[pack.mode], logit_dtype, want_f32, frame_invariant, onepass, nsplit)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            nbytes = lib.ph_khead_plan_workspace_bytes(C.byref(self.cfg))
-            if nbytes == 0:
-                raise _cfg_error("ph_khead_plan_workspace_bytes")
-            # zeroed ONCE: the one-pass launch's hand-off state ends in the sticky time-out words, which no call clears
-            self.workspace = torch.zeros((nbytes,), dtype=torch.uint8, device=dev)
-            handle = C.c_void_p()
-            _lib.check(lib.ph_khead_plan_create(C.byref(self.cfg), _lib.ptr(pack.blob), _lib.ptr(self.workspace), nbytes,
-                                                C.byref(handle)), "ph_khead_plan_create")
-        self._h = handle
-        geo = _lib.KheadGeometry()
-        _lib.check(lib.ph_khead_plan_info(self._h, C.byref(geo)), "ph_khead_plan_info")
-        self.geometry = geo
+        self._alloc_workspace()
+        self._h = self._create(_lib.ptr(pack.blob))
+        self.geometry = geo = self._info(self._h)
         self.onepass, self.nsplit, self.N, self.n_stuff = bool(geo.onepass), geo.nsplit, geo.N, geo.n_stuff
         self.Nq = pack.n_init
         self.dense_depth_proposal = dense_depth_proposal
@@ -1206,16 +1268,8 @@ class NeckPlan:
 
     def _towers(self, feats, pk, groups, posenc, pos_level):
         if self.multi:
-            if self._streams is None:
-                self._streams = [torch.cuda.Stream(device=self.xa.device) for _ in range(4)]
-            cur = torch.cuda.current_stream()
-            for lvl in (0, 3, 2, 1):                # the longest chains first
-                st = self._streams[lvl]
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    self._tower(lvl, feats[lvl], pk, groups, posenc if lvl == pos_level else None, self.lv[lvl])
-            for st in self._streams:
-                cur.wait_stream(st)
+            self._streams = _fan_out_towers(self._streams, self.xa.device, lambda lvl: self._tower(
+                lvl, feats[lvl], pk, groups, posenc if lvl == pos_level else None, self.lv[lvl]))
         else:
             shared = dict(xa=self.xa, xb=self.xb, y=self.y, stats=self.stats, partial=self.partial)
             for lvl in range(4):
@@ -1374,18 +1428,16 @@ def native_neck_cfg(B, shapes, groups, prec, num_outs=3, pos_level=3, to_planes=
                         emit_planes=int(bool(to_planes)), emit_f32=int(not to_planes), fused_out=fo, c16=cc, tower_buffers=int(multi))
 
 
-class NativeNeckPack:
+class NativeNeckPack(_NativePack):
     """one device buffer packed by ph_neck_pack, and its pieces as views in the form of SemanticFPNWrapper._pack's dict (`pk`: so
     either plan -- NeckPlan or NativeNeckPlan -- runs from it)"""
+    _symbols = ("ph_neck_pack_bytes", "ph_neck_param_name", "ph_neck_param_numel", "ph_neck_pack", "ph_neck_pack_layout")
+    _layout_type, _nparams = _lib.NeckLayout, staticmethod(lambda cfg: 3 * (7 + cfg.num_outs))
+    _slots = _lib.PH_NECK_NPARAMS                                  # absent aux convs: NULL
 
-    def __init__(self, blob, cfg):
-        lib = _lib.load()
-        lay = _lib.NeckLayout()
-        _lib.check(lib.ph_neck_pack_layout(C.byref(cfg), C.byref(lay)), "ph_neck_pack_layout")
-        self.blob, self.layout, self.mode, self.groups, self.num_outs = blob, lay, cfg.mode, cfg.groups, cfg.num_outs
-        self.prec = _GRADE_OF_MODE[cfg.mode]
-        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
-        piece = lambda i, dt, shape: _pack_piece(blob, lay, i, dt, shape)
+    def _pieces(self, cfg):
+        self.groups, self.num_outs = cfg.groups, cfg.num_outs
+        P, piece = self.P, self.piece
 
         def one(c):
             k = 3 if c < 7 else 1
@@ -1400,10 +1452,7 @@ class NativeNeckPack:
 
 def native_neck_pack(module, cfg, device):
     """the neck's parameters (a SemanticFPNWrapper, or its state_dict) packed on the device by ph_neck_pack"""
-    lib = _lib.load()
-    pack = lambda c, ptrs, blob, s: lib.ph_neck_pack(c, (C.c_void_p * _lib.PH_NECK_NPARAMS)(*ptrs), blob, s)      # absent aux convs: NULL
-    return NativeNeckPack(_pack_on_device(module, cfg, device, lib.ph_neck_pack_bytes, 3 * (7 + cfg.num_outs), lib.ph_neck_param_name,
-                                          lib.ph_neck_param_numel, pack, "ph_neck_pack"), cfg)
+    return NativeNeckPack.pack_on_device(module, cfg, device)
 
 
 def native_neck_posenc(H, W, num_feats, temperature=10000, scale=2 * math.pi, eps=1e-6, device="cuda:0"):
@@ -1415,13 +1464,14 @@ def native_neck_posenc(H, W, num_feats, temperature=10000, scale=2 * math.pi, ep
     return out
 
 
-class NativeNeckPlan(_OwnsHandles):
+class NativeNeckPlan(_NativePlan):
     """NeckPlan's `run` surface over the native plan: ONE native call per forward (ph_neck_plan_run), or -- where NeckPlan would put
     the four level towers on their own streams -- ph_neck_plan_run_level on the same four streams and ph_neck_plan_run_outputs
     behind them; the same launch sequence and geometry as the NeckPlan of the same arguments, so the same bits.  `pack`: a
     NativeNeckPack.  `cfg`: a ph_neck_cfg to use as it is (the environment is then not consulted at all; its emit flags follow
     each run's `to_planes`) instead of `native_neck_cfg`'s."""
-    _destroy_symbol = "ph_neck_plan_destroy"
+    _symbols, _geometry_type, _destroy_symbol = ("ph_neck_plan_workspace_bytes", "ph_neck_plan_create", "ph_neck_plan_info"), \
+        _lib.NeckGeometry, "ph_neck_plan_destroy"
 
     def __init__(self, pack, B, shapes, device, pos_level=3, tower_streams=True, cfg=None):
         dev = torch.device(device)
@@ -1430,11 +1480,7 @@ class NativeNeckPlan(_OwnsHandles):
                                                            tower_streams, device_type=dev.type)
         self.cfg = _lib.NeckCfg.from_buffer_copy(bytes(base))
         self.pos_level, self.groups = self.cfg.pos_level, self.cfg.groups
-        lib = _lib.load()
-        nbytes = lib.ph_neck_plan_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise _cfg_error("ph_neck_plan_workspace_bytes")
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
+        self._alloc_workspace()
         self._handles, self._outs = {}, {}
         self.geometry = self._info(self._handle(bool(self.cfg.emit_planes) and not self.cfg.emit_f32))
         self.Ho, self.Wo, self.multi = self.geometry.Ho, self.geometry.Wo, bool(self.geometry.tower_buffers)
@@ -1442,22 +1488,8 @@ class NativeNeckPlan(_OwnsHandles):
         self.io = _lib.NeckIO()
 
     def _handle(self, to_planes):
-        """the native plan that writes planes / fp32 maps (the two share the workspace: a run uses one of them)"""
-        h = self._handles.get(to_planes)
-        if h is None:
-            cfg = _lib.NeckCfg.from_buffer_copy(bytes(self.cfg))
-            cfg.emit_planes, cfg.emit_f32 = int(to_planes), int(not to_planes)
-            h = C.c_void_p()
-            _lib.check(_lib.load().ph_neck_plan_create(C.byref(cfg), _lib.ptr(self.pack.blob), _lib.ptr(self.workspace),
-                                                       self.workspace.numel(), C.byref(h)), "ph_neck_plan_create")
-            self._handles[to_planes] = h
-        return h
-
-    @staticmethod
-    def _info(h):
-        geo = _lib.NeckGeometry()
-        _lib.check(_lib.load().ph_neck_plan_info(h, C.byref(geo)), "ph_neck_plan_info")
-        return geo
+        """the native plan that writes planes / fp32 maps"""
+        return self._handle_of(emit_planes=bool(to_planes), emit_f32=not to_planes)
 
     def outputs(self, to_planes):
         """the output tensors of the planes / fp32 form (allocated on first use)"""
@@ -1481,6 +1513,10 @@ class NativeNeckPlan(_OwnsHandles):
             io.posenc = posenc.data_ptr()
         else:
             io.posenc = None
+        return self._point_outputs(outs, to_planes)
+
+    def _point_outputs(self, outs, to_planes):
+        io = self.io
         for i in range(3):
             t = outs[i] if i < len(outs) else None
             io.out_planes[i] = t.data_ptr() if (to_planes and t is not None) else None
@@ -1505,16 +1541,8 @@ class NativeNeckPlan(_OwnsHandles):
         outs = self.outputs(to_planes)
         io = self._fill_io(feats, posenc if self.pos_level >= 0 else None, outs, to_planes)
         if self.multi:
-            if self._streams is None:
-                self._streams = [torch.cuda.Stream(device=self.device) for _ in range(4)]
-            cur = torch.cuda.current_stream()
-            for lvl in (0, 3, 2, 1):                # the longest chains first (NeckPlan.run)
-                st = self._streams[lvl]
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    _lib.check(lib.ph_neck_plan_run_level(h, lvl, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_level")
-            for st in self._streams:
-                cur.wait_stream(st)
+            self._streams = _fan_out_towers(self._streams, self.device, lambda lvl: _lib.check(
+                lib.ph_neck_plan_run_level(h, lvl, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_level"))
             _lib.check(lib.ph_neck_plan_run_outputs(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_outputs")
         else:
             _lib.check(lib.ph_neck_plan_run(h, C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run")
@@ -1532,25 +1560,12 @@ class NativeNeckPlan(_OwnsHandles):
         _lib.check(_lib.load().ph_neck_plan_run_level_planes(self._handle(to_planes), lvl, _lib.stream_ptr()), "ph_neck_plan_run_level_planes")
 
     def run_towers_planes(self, pk=None, groups=None, to_planes=False):
-        if self._streams is None:
-            self._streams = [torch.cuda.Stream(device=self.device) for _ in range(4)]
-        cur = torch.cuda.current_stream()
-        for lvl in (0, 3, 2, 1):                    # the longest chains first (NeckPlan.run)
-            st = self._streams[lvl]
-            st.wait_stream(cur)
-            with torch.cuda.stream(st):
-                self.run_level_planes(lvl, to_planes=to_planes)
-        for st in self._streams:
-            cur.wait_stream(st)
+        self._streams = _fan_out_towers(self._streams, self.device, lambda lvl: self.run_level_planes(lvl, to_planes=to_planes))
 
     def run_outputs(self, pk=None, groups=None, to_planes=False, posenc=None):
         outs = self.outputs(to_planes)
-        io = self.io
+        io = self._point_outputs(outs, to_planes)
         io.posenc = posenc.data_ptr() if (self.pos_level >= 0 and posenc is not None) else None
-        for i in range(3):
-            t = outs[i] if i < len(outs) else None
-            io.out_planes[i] = t.data_ptr() if (to_planes and t is not None) else None
-            io.out_f32[i] = t.data_ptr() if (not to_planes and t is not None) else None
         _lib.check(_lib.load().ph_neck_plan_run_outputs(self._handle(to_planes), C.byref(io), _lib.stream_ptr()), "ph_neck_plan_run_outputs")
         return outs
 
@@ -1569,34 +1584,30 @@ def native_fpn_cfg(B, shapes, in_channels, prec, x_dtype=torch.float32, emit_f32
                        x_dtype=OUT_CODE[x_dtype], emit_f32=int(bool(emit_f32)), emit_planes=int(bool(emit_planes)))
 
 
-class NativeFpnPack:
+class NativeFpnPack(_NativePack):
     """one device buffer packed by ph_fpn_pack, and its pieces as views in the form of fpn.FPN._pack's dict (`pk`: so either plan --
     FpnPlan or NativeFpnPlan -- runs from it)"""
+    _symbols = ("ph_fpn_pack_bytes", "ph_fpn_param_name", "ph_fpn_param_numel", "ph_fpn_pack", "ph_fpn_pack_layout")
+    _layout_type, _nparams = _lib.FpnLayout, staticmethod(lambda cfg: _lib.PH_FPN_NPARAMS)
 
-    def __init__(self, blob, cfg):
-        lay = _lib.FpnLayout()
-        _lib.check(_lib.load().ph_fpn_pack_layout(C.byref(cfg), C.byref(lay)), "ph_fpn_pack_layout")
-        self.blob, self.layout, self.mode, self.in_channels = blob, lay, cfg.mode, tuple(cfg.k)
-        self.prec = _GRADE_OF_MODE[cfg.mode]
-        P = 2 if self.prec == _lib.PH_PREC_SPLIT else 1
-        one = lambda i, kk, k: dict(wp=_pack_piece(blob, lay, i, torch.int16, (P, 256 * kk)),
-                                    bias=_pack_piece(blob, lay, i + 1, torch.float32, (256,)), k=k, s=1)
+    def _pieces(self, cfg):
+        self.in_channels = tuple(cfg.k)
+        one = lambda i, kk, k: dict(wp=self.piece(i, torch.int16, (self.P, 256 * kk)), bias=self.piece(i + 1, torch.float32, (256,)), k=k, s=1)
         self.pk = dict(lateral=[one(2 * l, cfg.k[l], 1) for l in range(4)], output=[one(8 + 2 * l, 9 * 256, 3) for l in range(4)])
 
 
 def native_fpn_pack(module, cfg, device):
     """the FPN's parameters (a fpn.FPN, or its state_dict) packed on the device by ph_fpn_pack"""
-    lib = _lib.load()
-    return NativeFpnPack(_pack_on_device(module, cfg, device, lib.ph_fpn_pack_bytes, _lib.PH_FPN_NPARAMS, lib.ph_fpn_param_name,
-                                         lib.ph_fpn_param_numel, lib.ph_fpn_pack, "ph_fpn_pack"), cfg)
+    return NativeFpnPack.pack_on_device(module, cfg, device)
 
 
-class NativeFpnPlan(_OwnsHandles):
+class NativeFpnPlan(_NativePlan):
     """FpnPlan's `run` surface over the native plan: ONE native call per forward (ph_fpn_plan_run), or -- handing over to a neck plan
     with shared buffers -- ph_fpn_plan_run_laterals and then ph_fpn_plan_run_output level by level with the level's tower behind it;
     the same launch sequence as the FpnPlan of the same arguments, so the same bits.  `pack`: a NativeFpnPack; `cfg`: a ph_fpn_cfg to
     use as it is (its emit flags follow each run) instead of `native_fpn_cfg`'s."""
-    _destroy_symbol = "ph_fpn_plan_destroy"
+    _symbols, _geometry_type, _destroy_symbol = ("ph_fpn_plan_workspace_bytes", "ph_fpn_plan_create", "ph_fpn_plan_info"), \
+        _lib.FpnGeometry, "ph_fpn_plan_destroy"
 
     def __init__(self, pack, B, shapes, device, x_dtype=torch.float32, cfg=None):
         dev = torch.device(device)
@@ -1604,30 +1615,16 @@ class NativeFpnPlan(_OwnsHandles):
         base = cfg if cfg is not None else native_fpn_cfg(B, self.shapes, pack.in_channels, _MODE_NAME[pack.mode], x_dtype)
         self.cfg = _lib.FpnCfg.from_buffer_copy(bytes(base))
         self.in_channels, self.x_dtype = tuple(self.cfg.k), {v: k for k, v in OUT_CODE.items()}[self.cfg.x_dtype]
-        lib = _lib.load()
-        nbytes = lib.ph_fpn_plan_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise _cfg_error("ph_fpn_plan_workspace_bytes")
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
+        self._alloc_workspace()
         self._handles = {}
-        self.geometry = _lib.FpnGeometry()
-        _lib.check(lib.ph_fpn_plan_info(self._handle(True, False), C.byref(self.geometry)), "ph_fpn_plan_info")
+        self.geometry = self._info(self._handle(True, False))
         self.prec = self.geometry.prec
         self.outs = None                                                            # the fp32 levels, allocated on first use
         self.io = _lib.FpnIO()
 
     def _handle(self, emit_f32, emit_planes):
-        """the native plan of these emit flags (they share the workspace: a run uses one of them)"""
-        key = (bool(emit_f32), bool(emit_planes))
-        h = self._handles.get(key)
-        if h is None:
-            cfg = _lib.FpnCfg.from_buffer_copy(bytes(self.cfg))
-            cfg.emit_f32, cfg.emit_planes = int(key[0]), int(key[1])
-            h = C.c_void_p()
-            _lib.check(_lib.load().ph_fpn_plan_create(C.byref(cfg), _lib.ptr(self.pack.blob), _lib.ptr(self.workspace),
-                                                      self.workspace.numel(), C.byref(h)), "ph_fpn_plan_create")
-            self._handles[key] = h
-        return h
+        """the native plan of these emit flags"""
+        return self._handle_of(emit_f32=bool(emit_f32), emit_planes=bool(emit_planes))
 
     def run(self, feats, pk=None, neck=None, want_levels=True):
         """FpnPlan.run's arguments (`pk`: the plan's own pack, when given)"""
@@ -1752,16 +1749,13 @@ def native_assoc_cfg(B, out_hw, K, max_things, num_thing_classes, num_stuff_clas
     return c
 
 
-class NativeTrackPack:
+class NativeTrackPack(_NativePack):
     """one device buffer packed by ph_track_pack + views of its pieces under `_get_pack`'s names (the views share the buffer)"""
+    _symbols = ("ph_track_pack_bytes", "ph_track_param_name", "ph_track_param_numel", "ph_track_pack", "ph_track_pack_layout")
+    _layout_type, _nparams, _name_takes_cfg = _lib.TrackLayout, staticmethod(lambda cfg: 3 * cfg.num_convs + 4), True
 
-    def __init__(self, blob, cfg):
-        lay = _lib.TrackLayout()
-        _lib.check(_lib.load().ph_track_pack_layout(C.byref(cfg), C.byref(lay)), "ph_track_pack_layout")
-        self.blob, self.cfg, self.layout = blob, _lib.TrackCfg.from_buffer_copy(bytes(cfg)), lay
-        self.prec, self.P = cfg.prec, 2 if cfg.prec == _lib.PH_PREC_SPLIT else 1
-        piece = lambda i, dtype, shape: _pack_piece(blob, lay, i, dtype, shape)
-        P, F, E, n = self.P, cfg.fc_out_channels, cfg.embed_channels, cfg.num_convs
+    def _pieces(self, cfg):
+        piece, P, F, E, n = self.piece, self.P, cfg.fc_out_channels, cfg.embed_channels, cfg.num_convs
         self.pk = dict(convs=[piece(i, torch.int16, (P, 256 * 2304)) for i in range(n)],
                        gn=[(piece(_lib.PH_TRACK_MAX_CONVS + i, torch.float32, (256,)),
                             piece(2 * _lib.PH_TRACK_MAX_CONVS + i, torch.float32, (256,))) for i in range(n)],
@@ -1772,35 +1766,27 @@ class NativeTrackPack:
 
 def native_track_pack(module, cfg, device):
     """the track head's parameters (a QuasiDenseMaskEmbedHeadGTMask, or its state_dict) packed on the device by ph_track_pack"""
-    lib = _lib.load()
-    return NativeTrackPack(_pack_on_device(module, cfg, device, lib.ph_track_pack_bytes, 3 * cfg.num_convs + 4,
-                                           lambda i: lib.ph_track_param_name(C.byref(cfg), i), lib.ph_track_param_numel, lib.ph_track_pack,
-                                           "ph_track_pack"), cfg)
+    return NativeTrackPack.pack_on_device(module, cfg, device)
 
 
-class NativeAssocPlan(_OwnsHandles):
+class NativeAssocPlan(_NativePlan):
     """The association step of B frames over ph_panoptic_merge's device outputs: `run` is ONE launch-only native call
     (ph_assoc_plan_run: things tables, `sem`, boxes, RoIAlign, track embeddings -- capturable with torch.cuda.graph), `match` the one
     synchronising call behind it (ph_assoc_plan_match: the tracker and the `track` maps), `track` that call's launch-only counterpart
     over a tracker.NativeDeviceTracker (ph_assoc_plan_track).  `pack`: a NativeTrackPack; `cfg`: a
     ph_assoc_cfg (`native_assoc_cfg`).  The outputs are this object's static tensors: the next call overwrites them."""
-    _destroy_symbol = "ph_assoc_plan_destroy"
+    _symbols, _geometry_type, _destroy_symbol = ("ph_assoc_plan_workspace_bytes", "ph_assoc_plan_create", "ph_assoc_plan_info"), \
+        _lib.AssocGeometry, "ph_assoc_plan_destroy"
 
     def __init__(self, pack, cfg, device):
-        lib, dev = _lib.load(), torch.device(device)
+        dev = torch.device(device)
         self.pack, self.device = pack, dev
         self.cfg = _lib.AssocCfg.from_buffer_copy(bytes(cfg))
         if bytes(self.cfg.track) != bytes(pack.cfg):
             raise _lib.PolyheadError("NativeAssocPlan: the pack was made for another track head cfg")
-        nbytes = lib.ph_assoc_plan_workspace_bytes(C.byref(self.cfg))
-        if nbytes == 0:
-            raise _cfg_error("ph_assoc_plan_workspace_bytes")
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)      # zeroing contract: none
-        self._h = C.c_void_p()
-        _lib.check(lib.ph_assoc_plan_create(C.byref(self.cfg), _lib.ptr(pack.blob), _lib.ptr(self.workspace), nbytes, C.byref(self._h)),
-                   "ph_assoc_plan_create")
-        self.geometry = _lib.AssocGeometry()
-        _lib.check(lib.ph_assoc_plan_info(self._h, C.byref(self.geometry)), "ph_assoc_plan_info")
+        self._alloc_workspace()
+        self._h = self._create(_lib.ptr(pack.blob))
+        self.geometry = self._info(self._h)
         c = self.cfg
         self.B, self.K, self.cap, self.words = c.B, c.K, c.max_things, self.geometry.things_words
         e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
