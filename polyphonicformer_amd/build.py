@@ -8,6 +8,8 @@ import shutil
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
+from . import knobs
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpolyhead.so")
@@ -53,7 +55,7 @@ def build_library(force=False, verbose=False):
 
     def cc(src):
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-        cmd = [hipcc] + FLAGS + os.environ.get("PH_EXTRA_HIPCC_FLAGS", "").split() + ["-c", src, "-o", obj]
+        cmd = [hipcc] + FLAGS + knobs.get("PH_EXTRA_HIPCC_FLAGS").split() + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{r.stderr[-4000:]}")

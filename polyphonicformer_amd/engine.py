@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, knobs
 from .pack import pack_stage
 
 import collections
@@ -24,10 +24,10 @@ import collections
 #   feat  : element format / planes of the feature maps (ingest, pool)        query : the query-side GEMMs
 #   conv  : the dynamic 1x1 conv (feature planes x kernel planes)             kern_fmt : what the query kernel emits for it
 Mode = collections.namedtuple("Mode", "name feat query conv kern_fmt FP KP feat_dtype")
-import os as _os
 # query side of the modes that emit fp16 dynamic kernels: hybrid grade (updator half hi/lo bf16, attention / FFN / tower half one
-# fp16 plane, include/polyhead.h PH_PREC_QHYBRID) unless PH_QUERY_FULL_SPLIT=1 asks for hi/lo bf16 throughout
-_QH = _lib.PH_PREC_SPLIT if _os.environ.get("PH_QUERY_FULL_SPLIT") else _lib.PH_PREC_QHYBRID
+# fp16 plane, include/polyhead.h PH_PREC_QHYBRID) unless PH_QUERY_FULL_SPLIT=1 asks for hi/lo bf16 throughout (read here, at
+# import: MODES is a module constant)
+_QH = _lib.PH_PREC_SPLIT if knobs.get("PH_QUERY_FULL_SPLIT") else _lib.PH_PREC_QHYBRID
 MODES = {
     # fast: bf16 everywhere, one plane (6e-3 per stage against fp32)
     "bf16": Mode("bf16", _lib.PH_PREC_BF16, _lib.PH_PREC_BF16, _lib.PH_PREC_BF16, _lib.PH_KERN_BF16_PLANES, 1, 1, torch.bfloat16),
@@ -89,8 +89,9 @@ class StagePack:
 def default_nsplit(B, HW, frame_invariant=False):
     """pixel ranges per frame for the split-K pooling: PH_POOL_NSPLIT when set, else the library's rule (ph_pool_default_nsplit,
     csrc/ph_pool.hip, which also says what `frame_invariant` -- the split of a ONE-frame launch whatever B is -- buys)"""
-    if _os.environ.get("PH_POOL_NSPLIT"):
-        return int(_os.environ["PH_POOL_NSPLIT"])
+    n = knobs.get("PH_POOL_NSPLIT")
+    if n is not None:                   # a set 0 included (knobs.py: the known oddity against the cfg builders' "0 = the rule")
+        return n
     return int(_lib.load().ph_pool_default_nsplit(B, HW, int(bool(frame_invariant))))
 
 
@@ -236,21 +237,29 @@ def upsample2x(src, out=None):
 
 
 # ---- the S-stage plan ------------------------------------------------------------------------------
+def _knob_code(off, on, on_code):
+    """a cfg's off / on / auto field (include/polyhead.h PH_KNOB_*): PH_KNOB_OFF if `off`, else `on_code` if `on`, else
+    PH_KNOB_AUTO.  `on_code` says what "on" asks of the library: PH_KNOB_WHERE_SUPPORTED (the decode's fields: the fused form
+    wherever it exists, the plain one elsewhere) or PH_KNOB_ON (KernelHead's and the neck's: an error where AUTO says no)"""
+    return _lib.PH_KNOB_OFF if off else (on_code if on else _lib.PH_KNOB_AUTO)
+
+
 def native_cfg(B, N, H, W, S, L, F, prec, out_dtype=torch.float32, frame_invariant=False, shares_gpu=False, nsplit=None):
-    """the ph_decode_cfg of a decode plan, Python or native: the ONE place that reads the plans' environment switches
-    (PH_CONV_POOLX, PH_CONV_UP2, PH_POOL_NSPLIT, PH_POOLX_NSPLIT, PH_UP2_SHARED_WGS), which become the cfg's explicit fields --
-    the library itself never reads them.  DecodePlan asks the library for its launch geometry with it (ph_decode_geometry_of),
-    NativeDecodePlan creates its plan from it, so the two agree by construction"""
+    """the ph_decode_cfg of a decode plan, Python or native.  The decode's variables (knobs.py: PH_CONV_POOLX, PH_CONV_UP2,
+    PH_POOL_NSPLIT, PH_POOLX_NSPLIT, PH_UP2_SHARED_WGS) are read here, through knobs.get, at every call, and become the cfg's
+    explicit fields -- the library itself never reads them.  DecodePlan asks the library for its launch geometry with it
+    (ph_decode_geometry_of), NativeDecodePlan creates its plan from it, so the two agree by construction"""
     mode = mode_of(prec)
-    env = _os.environ.get
-    knob = lambda v: {"0": _lib.PH_KNOB_OFF, "1": _lib.PH_KNOB_WHERE_SUPPORTED}.get(v, _lib.PH_KNOB_AUTO)
+    poolx, up2 = knobs.get("PH_CONV_POOLX"), knobs.get("PH_CONV_UP2")
     return _lib.DecodeCfg(B=B, N=N, H=H, W=W, S=S, L=L, F=F, mode=_lib.PH_MODE[mode.name], out_dtype=OUT_CODE[out_dtype],
                           frame_invariant=int(bool(frame_invariant)),
                           query_full_split=int(mode.name in ("mixed16", "fp16") and mode.query == _lib.PH_PREC_SPLIT),
-                          shares_gpu=int(bool(shares_gpu)), poolx=knob(env("PH_CONV_POOLX")), fused_up=knob(env("PH_CONV_UP2")),
-                          nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0),
-                          nsplit_px=0 if frame_invariant else int(env("PH_POOLX_NSPLIT") or 0),
-                          up2_wgs=int(env("PH_UP2_SHARED_WGS") or 0))
+                          shares_gpu=int(bool(shares_gpu)),
+                          poolx=_knob_code(poolx == "0", poolx == "1", _lib.PH_KNOB_WHERE_SUPPORTED),
+                          fused_up=_knob_code(up2 == "0", up2 == "1", _lib.PH_KNOB_WHERE_SUPPORTED),
+                          nsplit=int(nsplit or knobs.get("PH_POOL_NSPLIT") or 0),
+                          nsplit_px=0 if frame_invariant else knobs.get("PH_POOLX_NSPLIT") or 0,
+                          up2_wgs=knobs.get("PH_UP2_SHARED_WGS") or 0)
 
 
 def _cfg_error(what):
@@ -981,21 +990,21 @@ _KHEAD_MODE_OF_PREC = {_lib.PH_PREC_F16: "fp16", _lib.PH_PREC_BF16: "bf16", _lib
 
 def native_khead_cfg(B, H, W, num_proposals, num_classes, num_thing_classes, cat_stuff, groups, prec, logit_dtype=torch.float32,
                      want_f32=True, frame_invariant=False, onepass=None, nsplit=None):
-    """the ph_khead_cfg of an a1 plan, Python or native: the ONE place that reads the plans' environment switches
-    (PH_KHEAD_TWOPASS, PH_POOL_NSPLIT), which become the cfg's explicit fields.  KernelHeadPlan asks the library for its geometry
-    with it (ph_khead_geometry_of), NativeKernelHeadPlan creates its plan from it, so the two agree by construction.
+    """the ph_khead_cfg of an a1 plan, Python or native.  KernelHead's variables (knobs.py: PH_KHEAD_TWOPASS, PH_POOL_NSPLIT) are
+    read here, through knobs.get, at every call, and become the cfg's explicit fields.  KernelHeadPlan asks the library for its
+    geometry with it (ph_khead_geometry_of), NativeKernelHeadPlan creates its plan from it, so the two agree by construction.
     `prec`: a precision name (engine.KHEAD_PREC's keys) or a1's grade code; `num_classes`: the rows of conv_seg"""
     name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
-    env = _os.environ.get
-    if onepass and env("PH_KHEAD_TWOPASS"):
+    twopass = knobs.get("PH_KHEAD_TWOPASS")
+    if onepass and twopass:
         raise _lib.PolyheadError("ph_khead_onepass asked for while PH_KHEAD_TWOPASS is set")
-    knob = _lib.PH_KNOB_OFF if (onepass is False or env("PH_KHEAD_TWOPASS")) else (_lib.PH_KNOB_ON if onepass else _lib.PH_KNOB_AUTO)
     if logit_dtype not in (torch.float32, torch.float16):
         raise _lib.PolyheadError("KernelHead logits are fp32 or fp16")
     return _lib.KheadCfg(B=B, H=H, W=W, num_proposals=num_proposals, num_classes=num_classes, num_thing_classes=num_thing_classes,
                          cat_stuff=int(bool(cat_stuff)), groups=groups, mode=_lib.PH_MODE[name], logit_dtype=OUT_CODE[logit_dtype],
-                         emit_f32=int(bool(want_f32)), frame_invariant=int(bool(frame_invariant)), onepass=knob,
-                         nsplit=int(nsplit or env("PH_POOL_NSPLIT") or 0))
+                         emit_f32=int(bool(want_f32)), frame_invariant=int(bool(frame_invariant)),
+                         onepass=_knob_code(onepass is False or twopass, onepass, _lib.PH_KNOB_ON),
+                         nsplit=int(nsplit or knobs.get("PH_POOL_NSPLIT") or 0))
 
 
 class NativeKernelHeadPack(_NativePack):
@@ -1034,7 +1043,7 @@ class NativeKernelHeadPlan(_KernelHeadPlanBase, _NativePlan):
 
     def __init__(self, pack, B, H, W, num_thing_classes, num_classes, cat_stuff, device, want_f32=True, nsplit=None,
                  logit_dtype=torch.float32, onepass=None, frame_invariant=False, dense_depth_proposal=False, cfg=None):
-        """`cfg`: a ph_khead_cfg to use as it is (the environment is then not consulted at all) instead of `native_khead_cfg`'s"""
+        """`cfg`: a ph_khead_cfg to use as it is (no PH_* variable is then consulted) instead of `native_khead_cfg`'s"""
         if num_classes != pack.n_seg:
             raise _lib.PolyheadError("the native KernelHead plan needs num_classes == rows of conv_seg (a sigmoid loss_seg)")
         self.pack, self.B, self.H, self.W, self.HW = pack, B, H, W, H * W
@@ -1400,26 +1409,25 @@ class FpnPlan:
 # ---- the neck as a native object (include/polyhead.h ph_neck_cfg .. ph_neck_plan_run_outputs) ------------------------------
 def native_neck_cfg(B, shapes, groups, prec, num_outs=3, pos_level=3, to_planes=False, tower_streams=True, fused_out=None, c16=None,
                     device_type="cuda"):
-    """the ph_neck_cfg of a neck plan, Python or native: the ONE place that reads the plans' environment switches (PH_NECK_OUT2=0,
-    PH_NECK_C16=0, PH_NECK_STREAMS), which become the cfg's explicit fields.  NeckPlan asks the library for its geometry with it
-    (ph_neck_geometry_of), NativeNeckPlan creates its plan from it, so the two agree by construction.
+    """the ph_neck_cfg of a neck plan, Python or native.  The neck's variables (knobs.py: PH_NECK_OUT2=0, PH_NECK_C16=0,
+    PH_NECK_STREAMS) are read here, through knobs.get, at every call, and become the cfg's explicit fields.  NeckPlan asks the
+    library for its geometry with it (ph_neck_geometry_of), NativeNeckPlan creates its plan from it, so the two agree by construction.
     `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `shapes`: the four level sizes; `pos_level`: None / -1 for
-    no positional encoding; `fused_out` / `c16`: None = the environment's choice, else True (fused_out only) / False"""
+    no positional encoding; `fused_out` / `c16`: None = the variable's choice, else True (fused_out only) / False"""
     name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
-    env = _os.environ.get
-    out2 = env("PH_NECK_OUT2", "1")
+    out2 = knobs.get("PH_NECK_OUT2")
     if out2 in ("2", "3"):
         raise _lib.PolyheadError("PH_NECK_OUT2=2 / 3: these measurement forms of the neck's output stage were removed (both were slower)")
     if fused_out and out2 == "0":
         raise _lib.PolyheadError("ph_neck_out_convs asked for while PH_NECK_OUT2=0 is set")
-    fo = _lib.PH_KNOB_OFF if (fused_out is False or out2 == "0") else (_lib.PH_KNOB_ON if fused_out else _lib.PH_KNOB_AUTO)
-    cc = _lib.PH_KNOB_OFF if (c16 is False or env("PH_NECK_C16", "1") == "0") else _lib.PH_KNOB_AUTO
+    fo = _knob_code(fused_out is False or out2 == "0", fused_out, _lib.PH_KNOB_ON)
+    cc = _lib.PH_KNOB_OFF if (c16 is False or knobs.get("PH_NECK_C16") == "0") else _lib.PH_KNOB_AUTO      # a field without an "on"
     # the four level towers with their own buffers, each on its own stream (NeckPlan.__init__): from 4 frames per call -- one frame
     # at a time (the video loop) is bound by the host's launch rate, where the stream switches cost more than the overlap returns
     # (cfg4 7.95 -> 9.08 ms per two frames with tower streams).  PH_NECK_STREAMS=0 or the module attribute `tower_streams = False`:
     # one stream, shared buffers (needed when TWO pipelines are captured into one HIP graph: the nested fork / join of 2 x 4 streams
     # made hipStreamEndCapture segfault on ROCm 7.2); PH_NECK_STREAMS=2 or tower_streams = "always": at any B
-    ns = env("PH_NECK_STREAMS", "1")
+    ns = knobs.get("PH_NECK_STREAMS")
     multi = bool(tower_streams) and (B >= 4 or ns == "2" or tower_streams == "always") and ns != "0" and device_type == "cuda"
     if len(shapes) != 4:
         raise _lib.PolyheadError("the neck takes four FPN levels")
@@ -1468,7 +1476,7 @@ class NativeNeckPlan(_NativePlan):
     """NeckPlan's `run` surface over the native plan: ONE native call per forward (ph_neck_plan_run), or -- where NeckPlan would put
     the four level towers on their own streams -- ph_neck_plan_run_level on the same four streams and ph_neck_plan_run_outputs
     behind them; the same launch sequence and geometry as the NeckPlan of the same arguments, so the same bits.  `pack`: a
-    NativeNeckPack.  `cfg`: a ph_neck_cfg to use as it is (the environment is then not consulted at all; its emit flags follow
+    NativeNeckPack.  `cfg`: a ph_neck_cfg to use as it is (no PH_* variable is then consulted; its emit flags follow
     each run's `to_planes`) instead of `native_neck_cfg`'s."""
     _symbols, _geometry_type, _destroy_symbol = ("ph_neck_plan_workspace_bytes", "ph_neck_plan_create", "ph_neck_plan_info"), \
         _lib.NeckGeometry, "ph_neck_plan_destroy"
@@ -1573,7 +1581,7 @@ class NativeNeckPlan(_NativePlan):
 # ---- the FPN as a native object (include/polyhead.h ph_fpn_cfg .. ph_fpn_plan_run) -------------------------------------------
 def native_fpn_cfg(B, shapes, in_channels, prec, x_dtype=torch.float32, emit_f32=True, emit_planes=False):
     """the ph_fpn_cfg of a native FPN plan.  `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `shapes`: the four
-    level sizes; `in_channels`: the four stage widths; `x_dtype`: the stages' torch dtype.  The FPN has no environment switch"""
+    level sizes; `in_channels`: the four stage widths; `x_dtype`: the stages' torch dtype.  The FPN has no PH_* variable"""
     name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
     if len(shapes) != 4 or len(in_channels) != 4:
         raise _lib.PolyheadError("the FPN takes four stages")
@@ -1737,7 +1745,7 @@ def native_track_cfg(head, prec=None):
 def native_assoc_cfg(B, out_hw, K, max_things, num_thing_classes, num_stuff_classes, level_shapes, track, strides=(4, 8, 16, 32),
                      finest_scale=56.0):
     """a ph_assoc_cfg: B frames of an (Ho, Wo) id map with K record rows and `max_things` RoIs per frame; `level_shapes`: (h, w) of
-    the FPN levels RoIAlign reads, finest first; `track`: a ph_track_cfg (`native_track_cfg`).  Reads no environment variable."""
+    the FPN levels RoIAlign reads, finest first; `track`: a ph_track_cfg (`native_track_cfg`).  Reads no PH_* variable."""
     L = len(level_shapes)
     if not 1 <= L <= 4:
         raise _lib.PolyheadError("native_assoc_cfg: 1 .. 4 FPN levels")

@@ -158,7 +158,7 @@ class KernelHead(nn.Module):
             dev = feats[0].device
         pack = self._get_pack(dev)
         cat_stuff = self.cat_stuff_mask and not self.training
-        # keyed by the cfg the plan is built from (engine.native_khead_cfg: the geometry AND the environment switches, so a switch
+        # keyed by the cfg the plan is built from (engine.native_khead_cfg: the geometry AND the PH_* variables (knobs.py), so a switch
         # changed between two calls rebuilds the plan) plus what the cfg does not hold
         cfg = E.native_khead_cfg(B, H, W, pack.n_init, pack.n_seg, self.num_thing_classes, cat_stuff, pack.groups, pack.prec,
                                  self.logit_dtype, self.emit_fp32_features, bool(self.frame_invariant))

@@ -96,7 +96,7 @@ class KernelUpdateIterHead(nn.Module):
     def _plan(self, B, N, H, W, device):
         packs = [h.stage_pack(device, self.precision) for h in self.mask_head]
         native = bool(self.native_plan)
-        # keyed by the cfg the plan is built from (engine.native_cfg: the geometry AND the environment switches) plus what it does not hold
+        # keyed by the cfg the plan is built from (engine.native_cfg: the geometry AND the PH_* variables (knobs.py)) plus what it does not hold
         cfg = E.native_cfg(B, N, H, W, len(packs), packs[0].num_classes, packs[0].lay.ffn_dim, E.MODES[self.precision],
                            self.output_dtype, bool(self.frame_invariant))
         key = (bytes(cfg), str(device), tuple(id(p) for p in packs), native)

@@ -144,7 +144,7 @@ class SemanticFPNWrapper(nn.Module):
 
     def _plan_cfg(self, B, shapes, dev, prec, pos_level=3):
         """(tower_streams, the ph_neck_cfg) of the plan `forward` uses for B frames of these level sizes: the call the plan itself
-        makes (engine.native_neck_cfg: the geometry AND the environment switches, so a switch changed between two calls rebuilds the
+        makes (engine.native_neck_cfg: the geometry AND the PH_* variables (knobs.py), so a switch changed between two calls rebuilds the
         plan); with the device string (and the native pack) it is the plan caches' key"""
         # `_clip_towers` (set by video.VideoStreamRunner around the capture of a 2-3 frame clip launch): the four level towers on
         # their own streams also below 4 frames -- inside a HIP graph the forks cost the host nothing (engine.NeckPlan)

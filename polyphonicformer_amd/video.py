@@ -3,12 +3,11 @@
 (`VideoStreamRunner`).  The trackers they drive live in tracker.py; `TRACKERS`, `QuasiDenseEmbedTracker`, `replay_tracking` and
 `bbox_overlaps` are re-exported here."""
 import dataclasses
-import os
 
 import numpy as np
 import torch
 
-from . import _lib, engine as E
+from . import _lib, engine as E, knobs
 from .tracker import (TRACKERS, NativeDeviceTracker, NativeDeviceTrackerBank, QuasiDenseEmbedTracker, bbox_overlaps, native_tracker_cfg,  # noqa: F401
                       painted_ids, replay_tracking)
 
@@ -297,7 +296,7 @@ class VideoFramePipeline:
         their versions change.  PH_VIDEO_API_EAGER=1: the eager launches of rounds 1-4."""
         if x[0].shape[0] != 1:
             raise NotImplementedError("video inference is one frame at a time (samples_per_gpu = 1, as in the reference)")
-        if not records_only and x[0].is_cuda and not os.environ.get("PH_VIDEO_API_EAGER"):
+        if not records_only and x[0].is_cuda and not knobs.get("PH_VIDEO_API_EAGER"):
             m = img_metas[0]
             key = (tuple(m["img_shape"]), tuple(m["ori_shape"]), tuple(m["batch_input_shape"]), tuple(tuple(t.shape) for t in x), x[0].dtype)
             r = self._api_runners.get(key)
@@ -401,7 +400,7 @@ class VideoStreamRunner:
         self.frames_per_launch = max(1, int(frames_per_launch))
         # the merge's candidate selection + activation + argmax queued behind the decode on the heads' stream (panoptic.DeviceMerge),
         # inside the graph; False = the module API's form (class scores to the host, torch.topk there)
-        self.device_select = (not os.environ.get("PH_VIDEO_HOST_SELECT")) if device_select is None else device_select
+        self.device_select = (not knobs.get("PH_VIDEO_HOST_SELECT")) if device_select is None else device_select
         self.reset()
 
     def reset(self):
@@ -447,7 +446,7 @@ class VideoStreamRunner:
             # front of them are a dozen small kernels on the caller's stream with the host waiting for each: PH_VIDEO_SLOT_PRIO=low
             # puts the heads one priority level below them
             prio = 0
-            if os.environ.get("PH_VIDEO_SLOT_PRIO") == "low":
+            if knobs.get("PH_VIDEO_SLOT_PRIO") == "low":
                 try:
                     lo, hi = torch.cuda.Stream.priority_range()
                     prio = max(lo, hi)
@@ -492,7 +491,7 @@ class VideoStreamRunner:
             return self._launch_eager(sl, frames)
         neck = getattr(sl.rpn, "localization_fpn", None)
         borrow = bool(borrowed and not sl.no_borrow and len(frames) >= 2 and neck is not None and hasattr(neck, "ingest_frames")
-                      and os.environ.get("PH_VIDEO_BORROW", "1") != "0"
+                      and knobs.get("PH_VIDEO_BORROW") != "0"
                       and all(t.dtype == torch.float32 and t.is_contiguous() for f in frames for t in f[:4]))
         cap = self._capture(sl, frames, True) if borrow else None
         if cap is None:                                      # not borrowed, or this slot's neck plan cannot borrow
@@ -535,7 +534,7 @@ class VideoStreamRunner:
         # 1 (default) as above, 2 + the sequential one-frame loop (heads 1.75 -> 1.64 ms, but merge and association + 0.04 each
         # behind it: inside the scatter; left off)
         neck = getattr(sl.rpn, "localization_fpn", None)
-        _ct = os.environ.get("PH_VIDEO_CLIP_TOWERS", "1")
+        _ct = knobs.get("PH_VIDEO_CLIP_TOWERS")
         towers = neck is not None and _ct != "0" and (B >= 2 or (_ct == "2" and not self.pipelined))
         if towers:
             neck._clip_towers = True
@@ -775,7 +774,7 @@ class VideoStreamRunner:
         # (profiles/r06/cfg4_sweep.txt, 8-frame clips): 2 / 3 / 4 / 8 frames per launch 785 / 830 / 943 / 734 frames/s; 16-frame clips:
         # 768 / 786 / 889 / 979.  Shorter clips: one launch.
         n = len(frames)
-        cap = int(os.environ.get("PH_VIDEO_CLIP_BATCH", "0")) or (n if n <= 3 else min(8, (n + 1) // 2))
+        cap = knobs.get("PH_VIDEO_CLIP_BATCH") or (n if n <= 3 else min(8, (n + 1) // 2))
         return max(1, min(cap, n)) if self._batch_invariant() else 1
 
     def records(self, frames, borrowed=True):
