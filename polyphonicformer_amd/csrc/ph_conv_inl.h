@@ -56,6 +56,35 @@ __device__ __forceinline__ void st_out(ph_h16* p, float v) { p->v = (uint16_t)f2
 __device__ __forceinline__ int conv_swz(int row) { return ((row >> 1) & 1) << 2; }
 
 
+// ---- `mixed16` (PH_E_F16_FROM_BF16): a bf16 tile on its way to LDS through a PRODUCER wave's registers ----------------------
+// The tile's pieces are the LDS-DMA ring's: instruction j = channel rows 8 j .. 8 j + 7 x 128 B, 16 bytes per lane, same source
+// addresses (swizzle on the source side), same stream cache policy -- but as ordinary loads (the compiler counts their vmcnt), so
+// that bf2h_x8 runs on data that is in registers anyway and ds_write_b128 puts the fp16 piece where the DMA would have put the
+// bf16 one: no LDS read-back, no in-place rewrite, no barrier behind a conversion phase.  Register staging reads a feature stream
+// at the LDS-DMA rate.  The descriptor spans the tile's 256 rows and nothing else (`tile` is wave uniform); !valid: no bytes at
+// all -- the range check then drops the loads (zeros, no memory traffic), which lets a pipeline's tail issue them unconditionally.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t conv_stage_rsrc(const void* tile, int64_t row_stride_elems, bool valid = true) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)tile, 0, valid ? (int)(2 * ((PH_C - 1) * row_stride_elems + CONV_T)) : 0, 0x00020000);
+}
+// pieces j0 .. j0 + NL - 1, j0 even and wave uniform; off_even / off_odd: the lane's byte offset inside a piece with even / odd j
+template <int NL, int J = 0>
+__device__ __forceinline__ void conv_stage_load(__amdgpu_buffer_rsrc_t rs, uint32_t off_even, uint32_t off_odd, uint32_t row8_bytes, int j0,
+                                                u32x4_t (&v)[NL]) {
+    if constexpr (J < NL) {
+        v[J] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((J & 1) ? off_odd : off_even), (int)((uint32_t)(j0 + J) * row8_bytes),
+                                                     PH_CPOL_STREAM);
+        conv_stage_load<NL, J + 1>(rs, off_even, off_odd, row8_bytes, j0, v);
+    }
+}
+// ... converted and written: `piece_lane` = the LDS address of piece j0 in the ring slot + 16 * lane.  Ends with the writes in flight.
+template <int NL, int J = 0> __device__ __forceinline__ void conv_stage_put(uint32_t piece_lane, const u32x4_t (&v)[NL]) {
+    if constexpr (J < NL) {
+        const uint4 h16 = bf2h_x8(__builtin_bit_cast(uint4, v[J]));
+        asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(piece_lane), "v"(__builtin_bit_cast(u32x4_t, h16)), "n"(J * 1024) : "memory");
+        conv_stage_put<NL, J + 1>(piece_lane, v);
+    }
+}
+
 // ---- MFMA phase of one 32-pixel half: 16 k-steps, B fragments by transposing reads, KB k-steps per batch, the
 // reads of batch i+1 in flight while the MFMAs of batch i run.  Compile-time recursion (immediate offsets).
 template <int PF, int KB, int BI, int K = 0, int P = 0>

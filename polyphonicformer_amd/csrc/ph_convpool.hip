@@ -14,8 +14,15 @@
 //   waves NRT .. 2 NRT-1 ("pooling"): 32 queries x 256 channels over tile t - 1, which is still in the ring: A = its mask words expanded
 //       through the 256-entry byte -> 8 x {0, 1} table `k_pool` uses, B = the tile (8 accumulators, 32 MFMAs); the first four of these
 //       waves also issue the ring's DMA (tile t + 2 over tile t - 2).
-// ONE barrier per tile (tile t landed + tile t - 1's words complete), a second one in the `mixed16` grade, whose tile is converted
-// bf16 -> fp16 in place by all waves first.  The first form of this kernel (every wave: convolution, barrier, pooling of the same tile;
+// ONE barrier per tile (tile t landed + tile t - 1's words complete).
+//   `mixed16` (bf16 plane, fp16 kernels), NRT <= 5: waves 2 NRT, 2 NRT + 1 ("producers") replace the DMA ring.  Each owns one half of
+//       the tile's channel rows, loads it with 16 ordinary 16-byte loads per lane (the DMA's addresses and nt | sc1 policy), converts
+//       bf16 -> fp16 in its registers and writes the fp16 image with ds_write_b128 into the same four slots (conv_stage_*,
+//       ph_conv_inl.h), two tiles in flight per producer (2 x 64 VGPRs: the 64 KB per CU the ring has in flight).  The tile is fp16 when
+//       its barrier falls: still ONE barrier per tile, and the other waves neither issue DMA nor wait on vmcnt.  12 waves at NRT = 5 =
+//       three on every SIMD at the 168 registers the kernel compiles to anyway.  (Before: all waves converted the landed tile in place,
+//       LDS -> registers -> LDS, with a second barrier behind it.)  NRT = 6 would be 14 waves at 128 registers: it keeps that form.
+// The first form of this kernel (every wave: convolution, barrier, pooling of the same tile;
 // three barriers) ran 207 us per 24 frames at cfg2 against 130 + 200 - 98 for the kernels it replaces -- no gain; with the roles the
 // matrix pipe has the other role's MFMAs while one waits on LDS: 145 us (`mixed16`), 133 us (fp16), +4.9 % on the step
 // (profiles/r06/poolx_ab.txt).  Counters: MFMA busy 0.53 (0.64 on the two SIMDs that host three waves), LDS bank conflicts 3 % of cycles.
@@ -63,8 +70,11 @@ template <int E> __device__ __forceinline__ uint4 cp_expand8(uint32_t byte) {
     return make_uint4(r[0], r[1], r[2], r[3]);
 }
 
-template <int NRT> struct CpCfg {
-    static constexpr int NW = 2 * NRT;                                  // NRT convolution waves + NRT pooling waves
+// `mixed16` with NRT <= 5: two more waves, the PRODUCERS, stage the bf16 tile through their registers (header).  NRT = 6 would be 14
+// waves at 128 registers, which the pooling waves' 8 accumulators + fragments do not fit in: it keeps the in-place conversion.
+template <int NRT, bool COOP> struct CpCfg {
+    static constexpr bool STAGED = COOP && NRT <= 5;
+    static constexpr int NW = 2 * NRT + (STAGED ? 2 : 0);               // NRT convolution waves + NRT pooling waves (+ 2 producers)
     static constexpr int TILEB = 256 * CONV_T * 2;
     static constexpr int NDW = NRT >= 4 ? 4 : 2;                        // pooling waves that issue the tile's 32 LDS-DMA instructions
     static constexpr int LUTB = 256 * 16, BWB = 2 * NRT * 32 * 2 * 4, KBB = NRT * 32 * 4;
@@ -72,16 +82,18 @@ template <int NRT> struct CpCfg {
 };
 
 template <int E, int NRT, bool COOP>
-__global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t* __restrict__ planes, const uint16_t* __restrict__ kern,
+__global__ __launch_bounds__((CpCfg<NRT, COOP>::NW * 64)) void k_dynconv_poolx(const uint16_t* __restrict__ planes, const uint16_t* __restrict__ kern,
                                                                   int64_t kern_batch_stride, const float* __restrict__ kbias,
                                                                   int64_t kbias_batch_stride, uint32_t* __restrict__ bits_out,
                                                                   float* __restrict__ partial, int B, int N, int64_t HW, int64_t HWp, int nsplit) {
-    using C = CpCfg<NRT>;
+    using C = CpCfg<NRT, COOP>;
     constexpr int Npad = NRT * 32, NBUF = CP_NBUF, NDW = C::NDW, DPW = 32 / NDW;
+    constexpr bool STAGED = C::STAGED;
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];   // [NBUF][256][64] | lut[256] x 16 B | mask words [2][Npad][2] | biases [Npad]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool is_conv = wave < NRT;                                  // waves 0 .. NRT - 1: convolution of tile t; NRT .. 2 NRT - 1: pooling of tile t - 1
+                                                                      // (STAGED: 2 NRT, 2 NRT + 1: the producers)
     const int rt = is_conv ? wave : wave - NRT;                       // the wave's 32-query block
     const int g = lane >> 5;
     const int split = blockIdx.x, b = blockIdx.y;
@@ -106,7 +118,56 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
     }
     const uint32_t lds0 = lds_addr(lds);
 
-    // bf16 -> fp16 of a whole tile in place (`mixed16`), every wave of the workgroup: 2048 16-byte pieces, one round at a time
+    if constexpr (STAGED) {
+        if (wave >= 2 * NRT) {
+            // =========================================== producer waves (`mixed16`): the tile from HBM to LDS through registers, as fp16
+            // Producer p owns channel rows 128 p .. 128 p + 127 = pieces 16 p .. 16 p + 15 of every tile (conv_stage_*, ph_conv_inl.h)
+            // and keeps TWO tiles in flight in 2 x 64 VGPRs -- with both producers the 64 KB per CU the DMA ring has in flight.  Before
+            // barrier (A) of tile t it has written tile t; behind it it converts and writes tile t + 1 over tile t - 3 (pooled one
+            // barrier ago) and issues tile t + 3 into the registers that frees.
+            const int p = wave - 2 * NRT, r8 = lane >> 3;
+            const uint32_t off_even = 2u * (uint32_t)(r8 * HWp + (((lane & 7) ^ cp_swz(r8)) * 8));
+            const uint32_t off_odd = 2u * (uint32_t)(r8 * HWp + (((lane & 7) ^ cp_swz(8 + r8)) * 8));
+            const uint32_t row8 = (uint32_t)(2 * 8 * HWp);
+            const char* tptr = (const char*)planes + 2 * ((int64_t)b * PH_C * HWp + (int64_t)t0 * CONV_T);
+            const uint32_t piece_lane = lds0 + (uint32_t)(16 * p * 1024) + 16u * (uint32_t)lane;
+            u32x4_t va[16], vb[16];
+            // Every load is issued unconditionally -- past the range's end through an EMPTY descriptor, which fetches nothing -- so that
+            // the compiler's vmcnt waits stay counted (a load under a branch makes them vmcnt(0): one tile in flight, not two).
+            auto load = [&](u32x4_t (&v)[16], int t) {
+                conv_stage_load<16>(conv_stage_rsrc(tptr, HWp, t < t1), off_even, off_odd, row8, 16 * p, v);
+                tptr += 2 * CONV_T;
+            };
+            auto put = [&](int slot, const u32x4_t (&v)[16]) {
+                conv_stage_put<16>(piece_lane + slot * C::TILEB, v);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            load(va, t0);
+            load(vb, t0 + 1);
+            put(0, va);
+            load(va, t0 + 2);
+            int nslot = 1;                                              // the slot of tile t + 1
+            // one step: barrier (A) of tile t, then tile t + 1 from `v` to its slot and tile t + 3 into `v`
+            auto step = [&](int t, u32x4_t (&v)[16]) {
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                put(nslot, v);
+                load(v, t + 3);
+                nslot = nslot + 1 == NBUF ? 0 : nslot + 1;
+            };
+            for (int t = t0;; t += 2) {                                 // a range is whole PAIRS of tiles (t0, t1 above; HWp % 128 == 0):
+                step(t, vb);                                            // tiles t0 + 1, t0 + 3, .. travel in `vb`, the others in `va`
+                if (t + 2 >= t1) break;
+                step(t + 1, va);
+            }
+            __builtin_amdgcn_s_barrier();                               // (A) of the range's last tile
+            __builtin_amdgcn_s_barrier();                               // (A) of t = t1: the pooling waves' last tile
+            return;
+        }
+    }
+
+    // bf16 -> fp16 of a whole tile in place (`mixed16` at NRT = 6, which has no producer waves), every wave of the workgroup: 2048 16-byte pieces, one round at a time
     // of the tile's 2048 16-byte pieces, how many the CONVOLUTION waves convert (the pooling waves: the rest).
     // Measured on one box, 32 frames: 1024 (equal) 246-252 us, 640: 249-251, 320: 254, 0: 343 -- equal shares stay
     constexpr int CP_CONV_PIECES = 1024;
@@ -158,7 +219,7 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
             __builtin_amdgcn_s_barrier();                             // (A) tile t has landed; the pooling waves are past tile t - 2
             __builtin_amdgcn_sched_barrier(0);
             if (t == t1) break;
-            if constexpr (COOP) {
+            if constexpr (COOP && !STAGED) {
                 convert(cur, std::true_type{});
                 __builtin_amdgcn_s_barrier();                         // (B) the tile is fp16
                 __builtin_amdgcn_sched_barrier(0);
@@ -254,8 +315,10 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
         ++ti;
         iptr += 2 * CONV_T;
     };
-    issue_next(0);
-    if (ti < t1) issue_next(1);
+    if constexpr (!STAGED) {                                          // (STAGED: the producer waves bring the tiles)
+        issue_next(0);
+        if (ti < t1) issue_next(1);
+    }
 
     // B fragment of channel block blk, k-step s = 16 bytes of row 32 blk + (lane & 31) at piece (4 g + s) ^ f(row); f does not depend on blk
     const int prow = lane & 31;
@@ -272,19 +335,21 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
 
     int cur = 0, par = 0;
     for (int t = t0; t <= t1; ++t) {
-        if (pw < NDW && t < t1) {
+        if (!STAGED && pw < NDW && t < t1) {
             if (t + 1 < t1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPW) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();                                   // (A) tile t has landed; tile t - 1's mask words are complete
         __builtin_amdgcn_sched_barrier(0);
-        if (ti < t1) {
-            int nb = cur + 2;
-            if (nb >= NBUF) nb -= NBUF;
-            issue_next(nb);                                             // tile t + 2 over tile t - 2
+        if constexpr (!STAGED) {
+            if (ti < t1) {
+                int nb = cur + 2;
+                if (nb >= NBUF) nb -= NBUF;
+                issue_next(nb);                                         // tile t + 2 over tile t - 2
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (COOP) {
+        if constexpr (COOP && !STAGED) {
             if (t < t1) {
                 convert(cur, std::false_type{});
                 __builtin_amdgcn_s_barrier();                           // (B) the tile is fp16
@@ -346,13 +411,13 @@ __global__ __launch_bounds__((2 * NRT * 64)) void k_dynconv_poolx(const uint16_t
 template <int E, int NRT, bool COOP>
 static void launch_cp(const uint16_t* planes, const uint16_t* kern, int64_t kbs, const float* kbias, int64_t bbs, uint32_t* bits_out,
                       float* partial, int B, int N, int64_t HW, int nsplit, hipStream_t s) {
-    constexpr int lds = CpCfg<NRT>::LDSB;
+    constexpr int lds = CpCfg<NRT, COOP>::LDSB;
     static const bool once = [] {
         (void)hipFuncSetAttribute((const void*)k_dynconv_poolx<E, NRT, COOP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         return true;
     }();
     (void)once;
-    hipLaunchKernelGGL((k_dynconv_poolx<E, NRT, COOP>), dim3(nsplit, B), dim3(2 * NRT * 64), lds, s, planes, kern, kbs, kbias, bbs, bits_out,
+    hipLaunchKernelGGL((k_dynconv_poolx<E, NRT, COOP>), dim3(nsplit, B), dim3(CpCfg<NRT, COOP>::NW * 64), lds, s, planes, kern, kbs, kbias, bbs, bits_out,
                        partial, B, N, HW, ph_hw_padded(HW), nsplit);
 }
 

@@ -15,6 +15,12 @@
 //     recipe: whole 128-byte lines, XOR swizzle on the source side, counted vmcnt).  The consumers' vector-memory queues then
 //     hold nothing but their own output stores -- ~40 per tile and wave -- which never have to drain inside the loop; in
 //     ph_conv.hip's form (every wave issues DMA and counts it with vmcnt) each tile would wait for the stores in front of it.
+//     `mixed16` (bf16 plane, fp16 kernels: PH_E_F16_FROM_BF16) has no DMA ring: its producer loads the tile with 32 ordinary
+//     16-byte loads per lane (same addresses, same nt | sc1 policy), converts bf16 -> fp16 in its registers and writes the fp16
+//     image the consumers read with ds_write_b128 (conv_stage_*, ph_conv_inl.h).  The tile is fp16 when its one barrier falls:
+//     no conversion pass over LDS by all waves, no second barrier.  ONE tile in flight (128 VGPRs, in a loop of the producer's
+//     own, where the consumers' 230 registers are not live) is enough: the loads are issued a whole tile of consumer work
+//     (~6 us) before they are waited for, several memory latencies.  Same bytes in LDS, same MFMA sequence: same results.
 //   * vertical direction: the previous image row of a wave's own accumulator positions stays in REGISTERS as packed 16-bit
 //     pairs (NTR tiles x 2 halves x 8 VGPRs = 64 at W = 256).  A workgroup whose range starts inside a frame first runs the
 //     row above it silently (halo: + 1 / 12 of the tiles at cfg2's 24 frames).
@@ -105,7 +111,7 @@ template <int EO> __device__ __forceinline__ uint4 upm_edge_frag(int lane, float
     return make_uint4(pack2(f2e<EO>(wP * l), f2e<EO>(wP * r)), pack2(f2e<EO>(wC * l), f2e<EO>(wC * r)), 0u, 0u);
 }
 
-// E: MFMA element format (PH_E_BF16 / PH_E_F16 / PH_E_F16_FROM_BF16 = bf16 plane converted to fp16 once per tile in LDS);
+// E: MFMA element format (PH_E_BF16 / PH_E_F16 / PH_E_F16_FROM_BF16 = bf16 plane converted to fp16 in the producer's registers on its way to LDS);
 // OutT: ph_h16 (fp16) or uint16_t (bf16) outputs; LOWRES: also write the low-resolution logits [B][N][H][W]
 template <int E, int NRT, int NTR, bool LOWRES, typename OutT>
 __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_t* __restrict__ planes, const uint16_t* __restrict__ kern,
@@ -146,7 +152,32 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
         iptr += 2 * CONV_T;
         if (++it == ntiles) { it = 0; iptr += frame_jump; }
     };
-    if (producer) {
+    if constexpr (COOP) {
+        // `mixed16`: the producer stages the tile through its registers (conv_stage_*, ph_conv_inl.h) and leaves the kernel's main loop
+        // to the consumers -- the tile's 128 VGPRs live where the consumers' operands and previous row do not.  One tile in flight:
+        // tile tg's loads are issued before the wave sleeps on tile tg - 1's barrier, a whole tile of consumer work (~6 us, several
+        // memory latencies) before it wakes up to convert them; it writes slot tg % NBUF while the consumers read slot (tg - 1) % NBUF.
+        // Barriers: the prologue's, then one per tile, as the consumers count them.
+        if (producer) {
+            const uint32_t slot_lane = lds_addr(lds) + 16u * (uint32_t)lane;
+            int buf = 0;
+            while (ti < tg1) {
+                u32x4_t v[32];
+                conv_stage_load<32>(conv_stage_rsrc(iptr, HW), dma_lane_off, dma_lane_off, (uint32_t)row8_bytes, 0, v);
+                ++ti;
+                iptr += 2 * CONV_T;
+                if (++it == ntiles) { it = 0; iptr += frame_jump; }
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_barrier();                // the prologue's barrier, then the barrier of the tile before this one
+                __builtin_amdgcn_sched_barrier(0);
+                conv_stage_put<32>(slot_lane + buf * C::TILEB, v);
+                lds_wait_all();
+                buf = buf + 1 == NBUF ? 0 : buf + 1;
+            }
+            __builtin_amdgcn_s_barrier();                    // the last tile's
+            return;
+        }
+    } else if (producer) {
 #pragma unroll
         for (int d = 0; d < NBUF - 1; ++d)
             if (ti < tg1) issue_next(d);
@@ -290,39 +321,24 @@ __global__ __launch_bounds__(((NRT + 1) * 64)) void k_dynconv_up2m(const uint16_
         auto tile = [&](auto tc_tag) {
             constexpr int TC = decltype(tc_tag)::value;
             const int tg = gr * NTR + TC;
-            if (producer) {
-                const int younger = (tg1 - 1 - tg) < (NBUF - 2) ? (tg1 - 1 - tg) : (NBUF - 2);
-                if (NBUF >= 3 && younger >= 1) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if constexpr (!COOP) {
+                if (producer) {
+                    const int younger = (tg1 - 1 - tg) < (NBUF - 2) ? (tg1 - 1 - tg) : (NBUF - 2);
+                    if (NBUF >= 3 && younger >= 1) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                }
             }
-            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();                    // the tile has landed (`mixed16`: as fp16, from the producer's registers)
             __builtin_amdgcn_sched_barrier(0);
-            if (producer && ti < tg1) {
-                int nb = cur + NBUF - 1;
-                if (nb >= NBUF) nb -= NBUF;
-                issue_next(nb);
+            if constexpr (!COOP) {
+                if (producer && ti < tg1) {
+                    int nb = cur + NBUF - 1;
+                    if (nb >= NBUF) nb -= NBUF;
+                    issue_next(nb);
+                }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if constexpr (COOP) {
-                constexpr int PIECES = 256 * CONV_T * 2 / 16, LANES = C::NW * 64, ROUNDS = (PIECES + LANES - 1) / LANES;
-                const uint32_t tb = lds0 + cur * C::TILEB + 16u * (uint32_t)tid;
-                u32x4_t cv[ROUNDS];
-#pragma unroll
-                for (int q = 0; q < ROUNDS; ++q)
-                    if ((q + 1) * LANES <= PIECES || tid < PIECES - q * LANES) cv[q] = lds_read128_asm(tb + q * LANES * 16);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < ROUNDS; ++q)
-                    if ((q + 1) * LANES <= PIECES || tid < PIECES - q * LANES) {
-                        const uint4 h16 = bf2h_x8(__builtin_bit_cast(uint4, cv[q]));
-                        lds_write128_asm(tb + q * LANES * 16, __builtin_bit_cast(u32x4_t, h16));
-                    }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (!producer) {
+            if (COOP || !producer) {
                 // this lane's bias (a lane = one query in the transposed product)
                 float bl;
                 asm volatile("ds_read_b32 %0, %1\n s_waitcnt lgkmcnt(0)" : "=&v"(bl) : "v"(kb_addr) : "memory");
