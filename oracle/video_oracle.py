@@ -8,7 +8,8 @@ functions/classes run in the build container (tests/golden/video.npz, written by
 configs/polyphonic_video/poly_r50_cityscapes_1x.py:65-71 -> mmdet SingleRoIExtractor ->
 polyphonic_former_video.py:416).  mmcv is not installable here, so for that one op parity is UNPINNED by a reference
 run: it is anchored on the published algorithm (Mask R-CNN RoIAlign with the half-pixel `aligned` offset) and on
-analytic properties tested in tests/test_video_oracle.py (constant / affine fields)."""
+analytic properties tested in tests/test_video_oracle.py (constant / affine fields).  `roi_extract_vec` is the same extraction
+vectorised in float64 (differentiable, fast enough for a thousand RoIs); tests/test_track_oracle_host.py holds it to the loop form."""
 import math
 
 import numpy as np
@@ -57,7 +58,7 @@ def _bilinear(feat, y, x):
     """feat [C,H,W]; y, x scalars (python floats).  mmcv roi_align bilinear_interpolate."""
     C, H, W = feat.shape
     if y < -1.0 or y > H or x < -1.0 or x > W:
-        return torch.zeros(C)
+        return feat.new_zeros(C)
     y, x = max(y, 0.0), max(x, 0.0)
     yl, xl = int(y), int(x)
     if yl >= H - 1:
@@ -79,7 +80,7 @@ def roi_align(feat, rois, spatial_scale, out_size=7, sampling_ratio=2, aligned=T
     """feat [1,C,H,W] fp32, rois [k,5] (batch index ignored: one image).  Returns [k,C,out,out]."""
     f = feat[0]
     k = rois.shape[0]
-    out = torch.zeros((k, f.shape[0], out_size, out_size))
+    out = f.new_zeros((k, f.shape[0], out_size, out_size))                 # the features' type: float64 in, float64 out
     off = 0.5 if aligned else 0.0
     for i in range(k):
         x1, y1, x2, y2 = [float(np.float32(v) * np.float32(spatial_scale)) - off for v in rois[i, 1:].tolist()]
@@ -90,7 +91,7 @@ def roi_align(feat, rois, spatial_scale, out_size=7, sampling_ratio=2, aligned=T
         g = sampling_ratio
         for ph in range(out_size):
             for pw in range(out_size):
-                acc = torch.zeros(f.shape[0])
+                acc = f.new_zeros(f.shape[0])
                 for iy in range(g):
                     yy = y1 + ph * bh + (iy + 0.5) * bh / g
                     for ix in range(g):
@@ -103,12 +104,77 @@ def roi_align(feat, rois, spatial_scale, out_size=7, sampling_ratio=2, aligned=T
 def roi_extract(feats, rois, strides=(4, 8, 16, 32), finest_scale=56):
     """SingleRoIExtractor.forward (single_level_roi_extractor.py:58-113), one image."""
     lv = map_roi_levels(rois, len(strides), finest_scale)
-    out = torch.zeros((rois.shape[0], feats[0].shape[1], 7, 7))
+    out = feats[0].new_zeros((rois.shape[0], feats[0].shape[1], 7, 7))
     for l, s in enumerate(strides):
         idx = (lv == l).nonzero().squeeze(1)
         if idx.numel():
             out[idx] = roi_align(feats[l], rois[idx], 1.0 / s)
     return out
+
+
+def roi_sample_coords(rois, lv, hw, strides=(4, 8, 16, 32), out_size=7, sampling_ratio=2):
+    """the sample coordinates of `roi_align` for RoIs mapped to the levels `lv`: (ys, xs) float64 [n, out_size * sampling_ratio],
+    sample s = bin * sampling_ratio + i; and the levels' (H, W) per RoI.  The same rule as the loop form: float32(roi) *
+    float32(scale) - 0.5, the rest in double and in the loop's order of operations."""
+    scale = torch.tensor([float(np.float32(1.0 / s)) for s in strides], dtype=torch.float32)[lv]
+    c = (rois[:, 1:].float() * scale[:, None]).double() - 0.5                      # x1, y1, x2, y2
+    x1, y1 = c[:, 0:1], c[:, 1:2]
+    bw, bh = (c[:, 2:3] - x1) / out_size, (c[:, 3:4] - y1) / out_size
+    g = sampling_ratio
+    b = torch.arange(out_size, dtype=torch.float64).repeat_interleave(g)[None]
+    i = torch.arange(g, dtype=torch.float64).repeat(out_size)[None]
+    ys = y1 + b * bh + (i + 0.5) * bh / g
+    xs = x1 + b * bw + (i + 0.5) * bw / g
+    HW = torch.tensor([list(s) for s in hw], dtype=torch.long)[lv]
+    return ys, xs, HW[:, 0], HW[:, 1]
+
+
+def _axis_taps(v, L):
+    """`_bilinear` along one axis for coordinates v [n, S] on an axis of length L [n]: (valid, low index, high index, high weight)"""
+    Lf = L[:, None].double()
+    valid = ~((v < -1.0) | (v > Lf))
+    v = v.clamp_min(0.0)
+    lo = v.floor().long()
+    edge = lo >= L[:, None] - 1
+    lo = torch.where(edge, (L[:, None] - 1).expand_as(lo), lo)
+    hi = torch.where(edge, lo, lo + 1)
+    v = torch.where(edge, lo.double(), v)
+    return valid, lo, hi, v - lo.double()
+
+
+def roi_extract_vec(feats, rois, strides=(4, 8, 16, 32), finest_scale=56, chunk=128):
+    """`roi_extract` in float64, vectorised (every RoI, bin and sample of a level at once; a gather by computed indices) and
+    differentiable with respect to `feats`.  A RoI with a non-finite coordinate gives zeros and no gradient (the loop form cannot
+    run on one).  -> [n, C, 7, 7] float64"""
+    finite = torch.isfinite(rois[:, 1:]).all(1)
+    safe = torch.where(finite[:, None], rois, torch.zeros_like(rois))
+    lv = map_roi_levels(safe, len(strides), finest_scale)
+    ys, xs, Hn, Wn = roi_sample_coords(safe, lv, [f.shape[-2:] for f in feats], strides)
+    vy, yl, yh, ly = _axis_taps(ys, Hn)
+    vx, xl, xh, lx = _axis_taps(xs, Wn)
+    C = feats[0].shape[1]
+    pieces, order = [], []
+    for l in range(len(strides)):
+        f = feats[l][0].double()
+        H, W = f.shape[-2:]
+        flat = f.reshape(C, H * W)
+        idx = ((lv == l) & finite).nonzero().squeeze(1)
+        for s in range(0, idx.numel(), chunk):
+            q = idx[s:s + chunk]
+            m = q.numel()
+            ok = (vy[q][:, :, None] & vx[q][:, None, :]).double()                                     # [m, 14, 14]
+            acc = 0.0
+            for yi, wy in ((yl[q], 1.0 - ly[q]), (yh[q], ly[q])):
+                for xi, wx in ((xl[q], 1.0 - lx[q]), (xh[q], lx[q])):
+                    lin = (yi[:, :, None] * W + xi[:, None, :]).reshape(-1)
+                    acc = acc + flat.index_select(1, lin).reshape(C, m, 14, 14) * (ok * wy[:, :, None] * wx[:, None, :])
+            pieces.append(acc.reshape(C, m, 7, 2, 7, 2).sum((3, 5)) / 4.0)
+            order.append(q)
+    bad = (~finite).nonzero().squeeze(1)
+    pieces.append(torch.zeros((C, bad.numel(), 7, 7), dtype=torch.float64))
+    order.append(bad)
+    back = torch.argsort(torch.cat(order))
+    return torch.cat(pieces, 1).index_select(1, back).permute(1, 0, 2, 3).contiguous()
 
 
 def track_embed_head(sd, x, groups=32, prefix="track_head."):

@@ -106,11 +106,15 @@ __global__ __launch_bounds__(256) void k_gemm32(const GemmBatch gb) {
     }
     const bool want_cs = J.colsum != nullptr && tn == 0;
     float cs[4] = {0.f, 0.f, 0.f, 0.f};
-    f32x4_t acc[2][2];
+    // Two levels of summation: `acc` runs over the PD steps (128 k) of one trip of the loop below and is then added to `tot`.  One
+    // fp32 chain over all of K measured 3.5e-6 .. 4.6e-6 against float64 at K = 12544 (tests/test_gpu_track_train_edges.py: as far
+    // off as a float32 loop in index order on the CPU, up to 3 x the bound a blocked float32 product sets); chains of 32 MFMAs under a
+    // chain of K / 128 additions keep the rounding near that of a blocked product.  K <= 128 is the one chain it always was.
+    f32x4_t acc[2][2], tot[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        for (int b = 0; b < 2; ++b) acc[a][b] = tot[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     // The loop is bound by the LATENCY of the operand loads (every launch measured ~24 us whatever its size: 8 steps x ~2.5 us with
     // one step of prefetch), so the loads run PD steps ahead of the MFMAs through a register ring.
     constexpr int PD = 4;
@@ -180,6 +184,13 @@ __global__ __launch_bounds__(256) void k_gemm32(const GemmBatch gb) {
 #undef QT_MF
             }
         }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                tot[a][b] += acc[a][b];
+                acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            }
     }
     // ---- epilogue: D lane (li, lg), reg r -> row lg * 4 + r, col li of its 16 x 16 tile.  Two passes: every load of the extras
     // first, then the stores -- interleaved, the compiler must keep each element's loads behind the previous element's store (the
@@ -195,7 +206,7 @@ __global__ __launch_bounds__(256) void k_gemm32(const GemmBatch gb) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int m = m0 + wm * 32 + a * 16 + lg * 4 + r;
-                float v = acc[a][b][r];
+                float v = tot[a][b][r];
                 if (m < J.M && n < J.N) {
                     if (first) {
                         if (J.bias) v += J.bias[n];
