@@ -124,6 +124,14 @@ int ph_pool_rows(const uint16_t* xplanes, const uint16_t* dplanes, const uint32_
  * `count(M)` of the folded feat_transform bias (kernel_update_head.py:225,241), handed to ph_query_stage_counts */
 int ph_pool_counts(const uint16_t* xplanes, const uint16_t* dplanes, const uint32_t* bits, float* partial, int32_t* pcount,
                    int B, int N, int64_t HW, int nsplit, int prec, void* stream);
+/* ONE read of depth_feats pooled under TWO mask sets (the depth halves of two consecutive stages' poolings, behind two
+ * ph_dynconv_poolx launches): columns 256 .. 511 of partialA / partialB ([B][nsplit][Npad][512]; columns 0 .. 255 are not touched)
+ * and pcountA / pcountB ([B][nsplit][Npad]) are, bit for bit, what ph_pool_counts(dplanes, NULL, bitsX, partialX + 256, pcountX, ...)
+ * leaves for X = A and X = B at the same nsplit: the pixel split, the chunk order and the MFMA order of every row are the same.
+ * ph_pool_depth_pair_supported: one feature plane (PH_PREC_BF16 / PH_PREC_F16) and N <= 160; elsewhere PH_EUNSUPPORTED. */
+int ph_pool_depth_pair_supported(int N, int prec);
+int ph_pool_depth_pair(const uint16_t* dplanes, const uint32_t* bitsA, const uint32_t* bitsB, float* partialA, float* partialB,
+                       int32_t* pcountA, int32_t* pcountB, int B, int N, int64_t HW, int nsplit, int prec, void* stream);
 /* the `nsplit` every plan of this library pools with when its caller names none (the cfgs' nsplit = 0, engine.default_nsplit):
  * 4 * B * nsplit workgroups fill the chip once, at most 32 ranges and one per 128-pixel chunk; frame_invariant != 0: the split
  * of a one-frame launch at any B (a frame's partial sums are then added in the same order whatever shares its launch) */
@@ -183,8 +191,12 @@ typedef struct {
  * Workspace (ph_query_workspace_bytes): q/k/v planes + residual.
  * phases: PH_QUERY_PRE | PH_QUERY_POST, optionally | PH_QUERY_WIDE: as many rows per workgroup as divide the padded row
  *         count (fewest CU-seconds; for launches that share the GPU with other streams).  Without it the launch is shaped
- *         to fill the chip by itself (lowest latency of a single launch). */
-enum { PH_QUERY_PRE = 1, PH_QUERY_POST = 2, PH_QUERY_BOTH = 3, PH_QUERY_WIDE = 0x100 };
+ *         to fill the chip by itself (lowest latency of a single launch).
+ *         | PH_QUERY_MASK_ONLY or | PH_QUERY_DEPTH_ONLY: one branch's half of the launch (grid.y = 1).  The branches share no data
+ *         inside a stage, so the two halves, in either order, leave exactly what the full launch leaves: the mask half writes obj,
+ *         cls, kern[0], kbias[0] from columns 0 .. 255 of `partial`, the depth half dobj, kern[1], kbias[1] from columns 256 .. 511.
+ *         The pixel counts are the same integers from the bit rows (ph_query_stage) as from ph_pool_counts. */
+enum { PH_QUERY_PRE = 1, PH_QUERY_POST = 2, PH_QUERY_BOTH = 3, PH_QUERY_WIDE = 0x100, PH_QUERY_MASK_ONLY = 0x200, PH_QUERY_DEPTH_ONLY = 0x400 };
 size_t ph_query_workspace_bytes(int B, int N, int prec);
 /* byte offset, inside the workspace, of the fp32 [B][2][Npad][256] KernelUpdator outputs
  * (funcs/kernel_updator.py:93) that the PRE phase leaves behind for the POST phase. */

@@ -16,6 +16,7 @@ if knobs.get("PH_ALT_LIB"):           # measurement aid: a variant build (tools/
 PH_PREC_BF16, PH_PREC_BF16_KSPLIT, PH_PREC_SPLIT, PH_PREC_F16, PH_PREC_BF16_KF16, PH_PREC_QHYBRID = 1, 2, 3, 5, 6, 7
 PH_PLANES_C16 = 0x100            # flag on `prec` of ph_nhwc_ingest / ph_conv_nhwc: chunk-major planes [B][16][HW][16] (polyhead.h)
 PH_QUERY_WIDE = 0x100            # ph_query_stage phases flag: most rows per workgroup (launches that share the GPU)
+PH_QUERY_MASK_ONLY, PH_QUERY_DEPTH_ONLY = 0x200, 0x400      # ... one branch's half of the launch
 PH_OUT_F32, PH_OUT_BF16, PH_OUT_F16 = 0, 1, 2
 PH_KERN_BF16_PLANES, PH_KERN_F16 = 0, 1
 PH_GN_TO_PLANES, PH_GN_UP2_PLANES, PH_GN_ACCUM, PH_GN_TO_NCHW, PH_GN_TO_CPLANES = 0, 1, 2, 3, 4
@@ -322,6 +323,8 @@ SIGNATURES = {
     "ph_match_sums": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
     "ph_upsample2x": (C.c_int, [_P, _P, _I, _L, _I, _I, _P]),
     "ph_dynconv_poolx_supported": (C.c_int, [_I, _I]),
+    "ph_pool_depth_pair_supported": (C.c_int, [_I, _I]),
+    "ph_pool_depth_pair": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P]),
     "ph_dynconv_poolx": (C.c_int, [_P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _L, _I, _P]),
     "ph_dynconv_up2_supported": (C.c_int, [_I, _I, _I, _I, _I]),
     "ph_dynconv_up2": (C.c_int, [_P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -320,6 +320,7 @@ struct QArgs2 {
     QArgs q;
     unsigned long long* tl;   // debug (PH_QUERY_TIMELINE=1): s_memrealtime stamps of workgroup (0,0,0), else null
     float* pi;      // [B][2][Npad][2][256] fp32: norm_out(param_out), input_norm_out(input_out) parked by the pre kernel
+    int br0, nbr;   // branches of this launch: br0 .. br0 + nbr - 1 (0, 2: both; PH_QUERY_MASK_ONLY 0, 1; PH_QUERY_DEPTH_ONLY 1, 1)
 };
 
 #define PH_TL(k)                                                                                             \
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
-    const int row0 = blockIdx.x * ROWS, br = blockIdx.y, b = blockIdx.z;
+    const int row0 = blockIdx.x * ROWS, br = blockIdx.y + aa.br0, b = blockIdx.z;
     const int N = a.N, Npad = a.Npad;
     const uint16_t* wb = a.wb;
     const int64_t wpl = a.lay.wb_plane_elems;
@@ -660,7 +661,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_post2(const QArgs2 aa) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 15, g = lane >> 4;
-    const int row0 = blockIdx.x * ROWS, br = blockIdx.y, b = blockIdx.z;
+    const int row0 = blockIdx.x * ROWS, br = blockIdx.y + aa.br0, b = blockIdx.z;
     const uint16_t* wb = a.wb;
     const int64_t wpl = a.lay.wb_plane_elems;
     const float* wf = a.wf;
@@ -1022,7 +1023,7 @@ static void launch_query2(const QArgs2& a, int phases, hipStream_t s) {
             return true;
         }();
         (void)once;
-        const dim3 grid(a.q.Npad / ROWS, 2, a.q.B);
+        const dim3 grid(a.q.Npad / ROWS, a.nbr, a.q.B);
         if (phases & 1) hipLaunchKernelGGL((k_query_pre2<2, NRT, true>), grid, dim3(NTHREADS), lds_pre, s, a);
         if (phases & 2) hipLaunchKernelGGL((k_query_post2<1, NRT, PH_E_F16>), grid, dim3(NTHREADS), lds_post, s, a);
         return;
@@ -1037,7 +1038,7 @@ static void launch_query2(const QArgs2& a, int phases, hipStream_t s) {
         return true;
     }();
     (void)once;
-    const dim3 grid(a.q.Npad / ROWS, 2, a.q.B);
+    const dim3 grid(a.q.Npad / ROWS, a.nbr, a.q.B);
     if (phases & 1) hipLaunchKernelGGL((k_query_pre2<PA, NRT>), grid, dim3(NTHREADS), lds_pre, s, a);
     if (phases & 2) hipLaunchKernelGGL((k_query_post2<PA, NRT>), grid, dim3(NTHREADS), lds_post, s, a);
 }
@@ -1048,8 +1049,9 @@ static int query_run(const PhQueryKnobs& kn, const float* partial, int nsplit, c
                      float* cls, int cls_sigmoid, uint16_t* kern, float* kbias, void* workspace,
                      size_t workspace_bytes, int B, int N, int64_t HW, int prec, int kern_format, int phases,
                      void* stream) {
-    PH_CHECK_ARG((phases & ~(PH_QUERY_BOTH | PH_QUERY_WIDE)) == 0 && (phases & PH_QUERY_BOTH) != 0,
-                 "phases must be PH_QUERY_PRE | PH_QUERY_POST [| PH_QUERY_WIDE]");
+    PH_CHECK_ARG((phases & ~(PH_QUERY_BOTH | PH_QUERY_WIDE | PH_QUERY_MASK_ONLY | PH_QUERY_DEPTH_ONLY)) == 0 && (phases & PH_QUERY_BOTH) != 0 &&
+                     (phases & (PH_QUERY_MASK_ONLY | PH_QUERY_DEPTH_ONLY)) != (PH_QUERY_MASK_ONLY | PH_QUERY_DEPTH_ONLY),
+                 "phases must be PH_QUERY_PRE | PH_QUERY_POST [| PH_QUERY_WIDE] [| PH_QUERY_MASK_ONLY or PH_QUERY_DEPTH_ONLY]");
     PH_CHECK_ARG(partial && bits && k_in && q_in && wb && wf && layout && obj && dobj && cls && kern && kbias && workspace,
                  "null pointer");
     PH_CHECK_ARG(B > 0 && N > 0 && N <= 256 && HW > 0 && nsplit >= 1, "bad size");
@@ -1061,6 +1063,8 @@ static int query_run(const PhQueryKnobs& kn, const float* partial, int nsplit, c
     const bool hybrid = prec == PH_PREC_QHYBRID;
     const int PA = (prec == PH_PREC_SPLIT || hybrid) ? 2 : 1, Npad = ph_n_padded(N);
     const bool wide = (phases & PH_QUERY_WIDE) != 0;
+    // one branch alone: the same workgroups as that branch's half of the full launch (the row tiling below does not look at it)
+    const int br0 = (phases & PH_QUERY_DEPTH_ONLY) ? 1 : 0, nbr = (phases & (PH_QUERY_MASK_ONLY | PH_QUERY_DEPTH_ONLY)) ? 1 : 2;
     phases &= PH_QUERY_BOTH;
     if (workspace_bytes < q_ws_bytes(B, Npad, PA)) {
         ph_set_error("ph_query_stage: workspace too small (%zu < %zu)", workspace_bytes, q_ws_bytes(B, Npad, PA));
@@ -1078,6 +1082,7 @@ static int query_run(const PhQueryKnobs& kn, const float* partial, int nsplit, c
     unsigned long long* tl = kn.timeline;          // debug only: phase times of one workgroup
     a2.tl = tl;
     a2.pi = a.o1 + (size_t)B * 2 * Npad * 256;
+    a2.br0 = br0; a2.nbr = nbr;
     // rows per workgroup (16 * nrt, nrt | Npad / 16).  Two regimes, measured at cfg2 (tools/query_time.py, split
     // precision, pre + post): 24 frames alone on the GPU 306 us at 80 rows (96 workgroups) against 166 us at 32 rows (240
     // workgroups) -- a launch that has the chip to itself wants the chip FILLED; inside the multi-stream step the 80-row

@@ -195,6 +195,14 @@ def pool_depth_only(dp, bits, N, HW, prec, partial, counts):
                                   _lib.stream_ptr()), "ph_pool_counts(depth)")
 
 
+def pool_depth_pair(dp, bits_a, bits_b, N, HW, prec, partial_a, partial_b, counts_a, counts_b):
+    """pool_depth_only under two mask sets from ONE read of depth_feats (ph_pool_depth_pair): the same bits as two calls"""
+    B, nsplit = partial_a.shape[0], partial_a.shape[1]
+    _lib.check(_lib.load().ph_pool_depth_pair(_lib.ptr(dp), _lib.ptr(bits_a), _lib.ptr(bits_b), _lib.ptr(partial_a), _lib.ptr(partial_b),
+                                              _lib.ptr(counts_a), _lib.ptr(counts_b), B, N, HW, nsplit, prec, _lib.stream_ptr()),
+               "ph_pool_depth_pair")
+
+
 def dynconv_up2(planes, kern, kbias, branch, N, H, W, prec, up_out, logits_out=None, out_dtype=_lib.PH_OUT_F16, workgroups=0):
     """final-stage dynamic conv + x2 bilinear upsample in one kernel (ph_dynconv_up2): kern [1,2,B,Npad,256] (one 16-bit
     plane), kbias [2,B,Npad]; writes up_out [B,N,2H,2W] and, when given, the low-resolution logits [B,N,H,W].
@@ -237,6 +245,9 @@ def upsample2x(src, out=None):
 
 
 # ---- the S-stage plan ------------------------------------------------------------------------------
+POOL_PAIR = knobs.get("PH_POOL_PAIR") != "0"       # A/B: DecodePlan's paired depth pooling of the last two stages (read once, here)
+
+
 def _knob_code(off, on, on_code):
     """a cfg's off / on / auto field (include/polyhead.h PH_KNOB_*): PH_KNOB_OFF if `off`, else `on_code` if `on`, else
     PH_KNOB_AUTO.  `on_code` says what "on" asks of the library: PH_KNOB_WHERE_SUPPORTED (the decode's fields: the fused form
@@ -271,8 +282,9 @@ class DecodePlan:
     """All buffers for `simple_test_mask_preds` at one (B, N, H, W, precision, output dtype)."""
 
     def __init__(self, packs, B, N, H, W, prec, out_dtype=torch.float32, device="cuda:0", nsplit=None, frame_invariant=False,
-                 shares_gpu=False):
-        """`frame_invariant` (round 6): every choice that touches a frame's arithmetic -- the pooling's pixel split, the fused / two-
+                 shares_gpu=False, pair=None):
+        """`pair`: the last two stages pool depth_feats in one launch (None: POOL_PAIR; only where the plan can, see `self.pair`).
+        `frame_invariant` (round 6): every choice that touches a frame's arithmetic -- the pooling's pixel split, the fused / two-
         kernel final stage -- is the ONE-frame launch's at any B, so a frame's outputs do not depend on its batch (the module API's
         default; a clip's frames through one launch equal the per-frame loop bit for bit).
         `shares_gpu`: the plan is one part of a multi-stream step (DualDecodePlan): query launches with the most rows per workgroup
@@ -333,6 +345,12 @@ class DecodePlan:
         if self.poolx:
             self.partial_px = e((B, self.nsplit_px, Npad, 512), torch.float32)
             self.pcount_px = e((B, self.nsplit_px, Npad), torch.int32)
+        # the depth halves of the last two stages' poolings from ONE read of depth_feats (ph_pool_depth_pair): the last stage's mask
+        # bits, partial sums and counts get buffers of their own (the B set; the names above stay the A set).  Same bits either way
+        self.pair = bool((POOL_PAIR if pair is None else pair) and self.poolx and self.S >= 3 and
+                         _lib.load().ph_pool_depth_pair_supported(N, self.prec))
+        if self.pair:
+            self.bits_b, self.partial_px_b, self.pcount_px_b = (torch.empty_like(t) for t in (self.bits, self.partial_px, self.pcount_px))
 
     @property
     def out_code(self):
@@ -388,23 +406,41 @@ class DecodePlan:
         xp = self.xp if xp is None else xp
         dp = self.dp if dp is None else dp
         k, q = self.k0, self.q0
+        cv = self.mode.conv
+
+        def query(s, part, bits, cnt, branches=0):
+            return query_stage(part, bits, k, q, self.packs[s], self.N, self.HW, cls_sigmoid=s == self.S - 1,
+                               outs=self.stage_out[s], workspace=self.ws, kern_fmt=self.mode.kern_fmt, counts=cnt,
+                               phases=3 | (_lib.PH_QUERY_WIDE if self.shares_gpu else 0) | branches)
+
         for s in range(self.S):
             last = s == self.S - 1
+            bits = self.bits_b if self.pair and last else self.bits
             if self.debug_bits is not None:      # tests: the hard masks stage s pools with (eager runs only)
-                self.debug_bits.append(self.bits.clone())
-            if s > 0 and self.poolx:
+                self.debug_bits.append(bits.clone())
+            if self.pair and s == self.S - 2:
+                # the depth branch never feeds the mask branch (kernel_update_head.py:250-288), so this stage's depth half waits until
+                # its mask half and the conv behind it have written the LAST stage's masks: depth_feats is then read once for both
+                # stages.  The mask half runs before anything has counted its masks' pixels: it counts the bit rows (same integers)
+                o = query(s, self.partial_px, bits, None, _lib.PH_QUERY_MASK_ONLY)
+                dynconv_poolx(xp, o["kern"], o["kbias"], self.N, self.HW, cv, self.bits_b, self.partial_px_b)
+                pool_depth_pair(dp, bits, self.bits_b, self.N, self.HW, self.prec, self.partial_px, self.partial_px_b,
+                                self.pcount_px, self.pcount_px_b)
+                query(s, self.partial_px, bits, self.pcount_px, _lib.PH_QUERY_DEPTH_ONLY)
+                k, q = o["obj"], o["dobj"]
+                continue
+            if self.pair and last:
+                part, cnt = self.partial_px_b, self.pcount_px_b      # both halves are there
+            elif s > 0 and self.poolx:
                 # the x map's sums came with the previous stage's conv (same read of the plane): depth_feats alone here
-                pool_depth_only(dp, self.bits, self.N, self.HW, self.prec, self.partial_px, self.pcount_px)
+                pool_depth_only(dp, bits, self.N, self.HW, self.prec, self.partial_px, self.pcount_px)
                 part, cnt = self.partial_px, self.pcount_px
             else:
-                pool(xp, dp, self.bits, self.N, self.HW, self.prec, self.nsplit, out=self.partial, counts=self.pcount)
+                pool(xp, dp, bits, self.N, self.HW, self.prec, self.nsplit, out=self.partial, counts=self.pcount)
                 part, cnt = self.partial, self.pcount
             if s == 0 and self.on_first_pool is not None:
                 self.on_first_pool()       # multi-part callers skew their parts by one phase (an event recorded here)
-            o = query_stage(part, self.bits, k, q, self.packs[s], self.N, self.HW, cls_sigmoid=last,
-                            outs=self.stage_out[s], workspace=self.ws, kern_fmt=self.mode.kern_fmt, counts=cnt,
-                            phases=3 | (_lib.PH_QUERY_WIDE if self.shares_gpu else 0))
-            cv = self.mode.conv
+            o = query(s, part, bits, cnt)
             if not last:
                 if self.poolx:
                     dynconv_poolx(xp, o["kern"], o["kbias"], self.N, self.HW, cv, self.bits, self.partial_px)

@@ -23,6 +23,9 @@ KNOBS = {k.name: k for k in (
          "`0` never / `1` wherever it exists: the stage-boundary conv also pools (`ph_dynconv_poolx`); anything else: the library's rule"),
     Knob("PH_CONV_UP2", "text", "auto", "plan cfg", "engine.native_cfg",
          "`0` never / `1` wherever it exists: final stage as `ph_dynconv_up2`; anything else: the library's rule (fused from B·H ≥ 512, §4.4b)"),
+    Knob("PH_POOL_PAIR", "text", "1", "import", "engine.POOL_PAIR",
+         "`0`: the last two stages pool depth_feats in a launch each; anything else: in one paired launch where "
+         "`ph_pool_depth_pair_supported` (`DecodePlan` with the fused conv + pooling and S ≥ 3, §4.2; same bits either way)"),
     Knob("PH_POOL_NSPLIT", "int", None, "plan cfg", "engine.native_cfg, native_khead_cfg, default_nsplit",
          "pixel ranges of the pooling kernels (cfg field `nsplit`; an `nsplit` argument wins).  Known oddity: `0` means the "
          "library's rule in the cfg builders, while `engine.default_nsplit` returns the 0"),
