@@ -53,6 +53,15 @@ struct QArgs {
 };
 
 // ------------------------------------------------------------------------------------------------
+// A phase's own copy of the lane id.  Every epilogue indexes rows as rt * 16 + g * 4 + r: left alone, the compiler computes
+// those 20 row indices and their byte offsets ONCE for the whole kernel and keeps them live from the first epilogue to the
+// last (about 60 registers at NRT = 5, most of the 80-row forms' spills).  An index derived from q_lane() is private to its
+// phase and dies with it; recomputing it is a handful of VALU operations.
+__device__ __forceinline__ int q_lane(int lane) {
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
 template <int NRT> __device__ __forceinline__ void tile_zero(f32x4_t (&a)[NRT][CT]) {
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
@@ -76,6 +85,7 @@ __device__ __forceinline__ void tile_add_bias(Tile<NRT>& t, const float* __restr
 // bf16 plane(s) of a tile -> LDS activation buffer [rows][LDA]
 template <int PA, int NRT, int E = PH_E_BF16>
 __device__ __forceinline__ void tile_to_lds(const Tile<NRT>& t, uint16_t* dst, int plane, int wave, int lane) {
+    lane = q_lane(lane);
     const int i = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
@@ -96,10 +106,26 @@ __device__ __forceinline__ void tile_to_lds(const Tile<NRT>& t, uint16_t* dst, i
 
 // LayerNorm over the 256 columns of NT tiles at once (two-pass: mean, then centred variance).
 // red: float [2][NT][NW waves][NRT*16]
+// The 8 waves' partial sums of a row are added up ONCE, by one thread per row (wave 0, 1, 2, ... in that order, as every lane
+// did for itself before: 8 LDS reads per row and lane, 160 per pass at 80 rows, in all 512 threads), and left in wave 0's slot:
+// a lane then reads one word per row.  One more barrier per pass.
+template <int NRT, int NT>
+__device__ __forceinline__ void ln_row_totals(float* red, int pass, int tid) {
+    constexpr int ROWS = NRT * 16;
+    for (int idx = tid; idx < NT * ROWS; idx += NTHREADS) {
+        float* p = red + ((pass * NT + idx / ROWS) * NW) * ROWS + idx % ROWS;
+        float tot = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) tot += p[w * ROWS];
+        p[0] = tot;
+    }
+    __syncthreads();
+}
 template <int NRT, int NT>
 __device__ __forceinline__ void ln_tiles(Tile<NRT> (&t)[NT], const float* const (&gam)[NT], const float* const (&bet)[NT],
                                          float* red, int wave, int lane) {
     constexpr int ROWS = NRT * 16;
+    lane = q_lane(lane);
     const int i = lane & 15, g = lane >> 4;
     float mean[NT][NRT][4];
 #pragma unroll
@@ -115,20 +141,17 @@ __device__ __forceinline__ void ln_tiles(Tile<NRT> (&t)[NT], const float* const 
                 if (i == 0) red[((0 * NT + n) * NW + wave) * ROWS + rt * 16 + g * 4 + r] = s;
             }
     __syncthreads();
+    ln_row_totals<NRT, NT>(red, 0, wave * 64 + lane);
 #pragma unroll
     for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt) {
-            // bound the scheduler's hoisting of the 8-reads-per-row LDS gathers: all NT*NRT groups at once
-            // cost 128 VGPRs next to a prefetched weight set
+            // bound the scheduler's hoisting of the LDS reads of the row totals
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("" ::: "memory");      // also pins the IR-level order of the LDS gathers (sched_barrier is IntrNoMem)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float* p = red + (0 * NT + n) * NW * ROWS + rt * 16 + g * 4 + r;
-                float tot = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) tot += p[w * ROWS];
+                const float tot = red[(0 * NT + n) * NW * ROWS + rt * 16 + g * 4 + r];
                 mean[n][rt][r] = tot * (1.f / 256.f);
                 float s = 0.f;
 #pragma unroll
@@ -146,6 +169,7 @@ __device__ __forceinline__ void ln_tiles(Tile<NRT> (&t)[NT], const float* const 
             for (int ct = 0; ct < CT; ++ct) asm volatile("" : "+v"(t[n].v[rt][ct]));
         }
     __syncthreads();
+    ln_row_totals<NRT, NT>(red, 1, wave * 64 + lane);
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         float gm[CT], bt[CT];
@@ -160,10 +184,7 @@ __device__ __forceinline__ void ln_tiles(Tile<NRT> (&t)[NT], const float* const 
             asm volatile("" ::: "memory");      // also pins the IR-level order of the LDS gathers (sched_barrier is IntrNoMem)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float* p = red + (1 * NT + n) * NW * ROWS + rt * 16 + g * 4 + r;
-                float tot = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) tot += p[w * ROWS];
+                const float tot = red[(1 * NT + n) * NW * ROWS + rt * 16 + g * 4 + r];
                 const float var = tot * (1.f / 256.f);
                 const float rstd = fast_rsqrt(var + LN_EPS);
 #pragma unroll
@@ -180,6 +201,7 @@ __device__ __forceinline__ void ln_tiles(Tile<NRT> (&t)[NT], const float* const 
 template <int PA, int NRT, int PART, bool QF16 = false>
 __device__ __forceinline__ void store_qkv(const Tile<NRT>& T, const QArgs& a, const float* bias, int64_t qk_base,
                                           int64_t qk_plane, int64_t vt_base, int wave, int lane) {
+    lane = q_lane(lane);
     const int i = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
@@ -265,6 +287,7 @@ __device__ __forceinline__ void gemm_stream(f32x4_t (&acc)[NRT][NCT], const uint
                                             const WRef2& r, int64_t w_plane, int lane, Next next) {
     constexpr int KCH = kch<PA>(), NCH = NKS / KCH;
     static_assert(NKS % KCH == 0 && NCH % 2 == 0, "a call is an even number of chunks");
+    constexpr int RG = PA == 2 ? 1 : (NRT < 2 ? NRT : 2);       // row tiles whose A fragments are loaded together
     const int i = lane & 15, g = lane >> 4;
     __builtin_amdgcn_sched_barrier(0);          // phases do not interleave: the register pressure of a call is local
 #pragma unroll
@@ -273,24 +296,31 @@ __device__ __forceinline__ void gemm_stream(f32x4_t (&acc)[NRT][NCT], const uint
         else next();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int k = 0; k < KCH; ++k) {
-            uint4 a[PA][NRT];
+        for (int k = 0; k < KCH; ++k)
+            // row tiles in groups of RG: only a group's A fragments (PA x RG x 4 registers) are live next to the two chunk buffers.
+            // Two planes: one row tile at a time, 8 registers instead of 40 at <2, 5>.  One plane: two at a time (a single tile is
+            // only NCT MFMAs per LDS read: POST <1, 5, 1> alone on the GPU 95.4 us with 1, 93.9 with 2, 92.1 with all 5, which
+            // spills again; profiles/r09).  Every acc[rt][ct] sees the same products in the same order whatever RG is.
 #pragma unroll
-            for (int p = 0; p < PA; ++p)
+            for (int rt0 = 0; rt0 < NRT; rt0 += RG) {
+                uint4 a[PA][RG];
 #pragma unroll
-                for (int rt = 0; rt < NRT; ++rt)
-                    a[p][rt] = *(const uint4*)(A + p * a_plane + (rt * 16 + i) * lda + (kc * KCH + k) * 32 + g * 8);
+                for (int p = 0; p < PA; ++p)
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
+                    for (int rr = 0; rr < RG && rt0 + rr < NRT; ++rr)
+                        a[p][rr] = *(const uint4*)(A + p * a_plane + ((rt0 + rr) * 16 + i) * lda + (kc * KCH + k) * 32 + g * 8);
 #pragma unroll
-                for (int rt = 0; rt < NRT; ++rt) {
-                    acc[rt][ct] = mfma16e<E>(a[0][rt], ws.f[kc & 1][k][ct], acc[rt][ct]);
-                    if (PA == 2) {
-                        acc[rt][ct] = mfma16(a[0][rt], ws.f[kc & 1][(PA - 1) * KCH + k][ct], acc[rt][ct]);
-                        acc[rt][ct] = mfma16(a[PA - 1][rt], ws.f[kc & 1][k][ct], acc[rt][ct]);
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int rr = 0; rr < RG && rt0 + rr < NRT; ++rr) {
+                        f32x4_t& c = acc[rt0 + rr][ct];
+                        c = mfma16e<E>(a[0][rr], ws.f[kc & 1][k][ct], c);
+                        if (PA == 2) {
+                            c = mfma16(a[0][rr], ws.f[kc & 1][(PA - 1) * KCH + k][ct], c);
+                            c = mfma16(a[PA - 1][rr], ws.f[kc & 1][k][ct], c);
+                        }
                     }
-                }
-        }
+            }
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -298,6 +328,7 @@ __device__ __forceinline__ void gemm_stream(f32x4_t (&acc)[NRT][NCT], const uint
 // bf16 plane(s) of an [NRT*16 x 16*NCT]-per-wave tile -> LDS buffer with row stride `ld`, column offset `col0`
 template <int PA, int NRT, int NCT, int E = PH_E_BF16>
 __device__ __forceinline__ void frag_to_lds(const f32x4_t (&t)[NRT][NCT], uint16_t* dst, int ld, int plane, int col0, int lane) {
+    lane = q_lane(lane);
     const int i = lane & 15, g = lane >> 4;
 #pragma unroll
     for (int rt = 0; rt < NRT; ++rt)
@@ -446,6 +477,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
     {
         Tile<NRT> Po[1];
         tile_zero(Po[0].v);
+        const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
         gemm_stream<PA, NRT, CT, 8>(Po[0].v, act, LDA, PLANE, ws, c_dyn_o, wpl, lane, prime(c_dyn_i));
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -470,14 +502,17 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
     Tile<NRT> Pin;                                               // param_in, then the gate input
     tile_zero(Pin.v);
     gemm_stream<PA, NRT, CT, 8>(Pin.v, act, LDA, PLANE, ws, c_dyn_i, wpl, lane, prime(c_inp_i));
+    {
+        const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-        const int col = wave * WCOLS + ct * 16 + i;
-        const float vc0 = vc[col], bd0 = bd[col];
+        for (int ct = 0; ct < CT; ++ct) {
+            const int col = wave * WCOLS + ct * 16 + i;
+            const float vc0 = vc[col], bd0 = bd[col];
 #pragma unroll
-        for (int rt = 0; rt < NRT; ++rt)
+            for (int rt = 0; rt < NRT; ++rt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) Pin.v[rt][ct][r] += cnt[rt * 16 + g * 4 + r] * vc0 + bd0;
+                for (int r = 0; r < 4; ++r) Pin.v[rt][ct][r] += cnt[rt * 16 + g * 4 + r] * vc0 + bd0;
+        }
     }
     __syncthreads();                                             // every wave is done reading u
     PH_TL(2);
@@ -515,6 +550,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
     {
         Tile<NRT> Iin;
         tile_zero(Iin.v);
+        const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
         gemm_stream<PA, NRT, CT, 8>(Iin.v, act, LDA, PLANE, ws, c_inp_i, wpl, lane, prime(c_inp_o));
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -528,6 +564,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
     {
         Tile<NRT> Io[1];
         tile_zero(Io[0].v);
+        const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
         gemm_stream<PA, NRT, CT, 8>(Io[0].v, act, LDA, PLANE, ws, c_inp_o, wpl, lane, prime(c_ug));
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
@@ -564,6 +601,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
             const float* const gm[1] = {wf + VO[g_idx]};
             const float* const bt[1] = {wf + VO[be_idx]};
             ln_tiles<NRT, 1>(G, gm, bt, red, wave, lane);
+            const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
 #pragma unroll
             for (int rt = 0; rt < NRT; ++rt) {
                 float pv[CT][4];
@@ -597,6 +635,7 @@ __global__ __launch_bounds__(NTHREADS) void k_query_pre2(const QArgs2 aa) {
         const float* const gm[1] = {wf + VO[PH_V_LN_FC_G]};
         const float* const bt[1] = {wf + VO[PH_V_LN_FC_B]};
         ln_tiles<NRT, 1>(O, gm, bt, red, wave, lane);           // barriers: readers of the gated feature are done
+        const int lp = q_lane(lane), i = lp & 15, g = lp >> 4;      // this phase's own row indices (q_lane)
         float* o1 = a.o1 + (((int64_t)b * 2 + br) * Npad + row0) * 256;
 #pragma unroll
         for (int rt = 0; rt < NRT; ++rt)
