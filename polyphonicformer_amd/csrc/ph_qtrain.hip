@@ -663,7 +663,8 @@ struct Launcher {
     int R;
     GemmBatch gb;
     int nj = 0, maxtiles = 0;
-    bool failed = false;
+    bool failed = false;       // the call cannot return PH_OK: a launch failed or a launched table held a misfit.  Set by flush(), never cleared
+    bool misfit = false;       // an operand of a job now in the table breaks vec_ok: recomputed by padded_A, handed to `failed` by flush()
 
     // a float4 of the operand is wholly inside or wholly outside: aligned base, ld % 4 == 0, the vectorised axis (k when the operand is
     // k-contiguous, else its row index) a multiple of 4 long
@@ -676,7 +677,7 @@ struct Launcher {
         j = GemmJob{};
         j.A = A; j.lda = lda; j.kcA = kcA; j.B = B; j.ldb = ldb; j.kcB = kcB; j.C = C; j.ldc = ldc; j.M = M; j.N = N; j.K = K;
         j.rowsA = M; j.KA = K; j.KB = K;
-        if (!vec_ok(A, lda, kcA ? K : M) || !vec_ok(B, ldb, kcB ? K : N)) failed = true;       // callers pad (see `padded`)
+        if (!vec_ok(A, lda, kcA ? K : M) || !vec_ok(B, ldb, kcB ? K : N)) misfit = true;       // callers pad (see `padded_A`)
         j.ksplit = 1;
         j.kcA2 = j.kcB2 = 1;
         return j;
@@ -688,14 +689,16 @@ struct Launcher {
     void padded_A(GemmJob& j, int rows_padded, int k_padded) {
         j.rowsA = rows_padded; j.KA = k_padded;
         if (k_padded > j.K) j.K = k_padded;
-        failed = false;
+        misfit = false;
         for (int i = 0; i < nj; ++i) {
             const GemmJob& q = gb.j[i];
-            if (!vec_ok(q.A, q.lda, q.kcA ? q.KA : q.rowsA) || !vec_ok(q.B, q.ldb, q.kcB ? q.KB : q.N)) failed = true;
+            if (!vec_ok(q.A, q.lda, q.kcA ? q.KA : q.rowsA) || !vec_ok(q.B, q.ldb, q.kcB ? q.KB : q.N)) misfit = true;
         }
     }
     void flush() {
         if (!nj) return;
+        if (misfit) failed = true;
+        misfit = false;
         maxtiles = 0;
         for (int i = 0; i < nj; ++i) {
             GemmJob& j = gb.j[i];

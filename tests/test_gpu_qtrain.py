@@ -1,7 +1,8 @@
 """GPU: one KernelUpdateHead stage in TRAINING form as a single autograd node (`train._Stage`: hard-mask pooling, the fused
 query side of csrc/ph_qtrain.hip, the dynamic convolutions) against the CPU oracle's `update_stage` under torch autograd --
 every output, and the gradient of every parameter and input, for random cotangents.  The oracle applies feat_transform as
-written (kernel_update_head.py:224-226); the device path folds it, so its weight / bias gradients check the folding too."""
+written (kernel_update_head.py:224-226); the device path folds it, so its weight / bias gradients check the folding too.
+The query side alone at its size and value edges, every tensor against max(4 e_ref, 1e-6): tests/test_gpu_qtrain_edges.py."""
 import pytest
 import torch
 
