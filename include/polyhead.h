@@ -742,6 +742,34 @@ int ph_fpn_output(const float* y, const float* bias, float* out, int B, int64_t 
 int ph_fpn_output_planes(const float* y, const float* bias, const float* add /* nullable */, uint16_t* planes,
                          float* out_f32 /* nullable */, int B, int64_t HW, int prec /* may carry PH_PLANES_C16 */, void* stream);
 
+/* ---- ResNet backbone at inference: the step before the FPN (mmdet/models/backbones/resnet.py as configs/_base_/models/
+ * polyphonic_former.py:12-21 builds it; csrc/ph_resnet.hip).  norm_eval=True makes every BatchNorm an affine map, folded by the
+ * caller in float64: w' = w g / sqrt(var + eps) rounded once to the grade, b' = beta - mu g / sqrt(var + eps) in fp32.  Activations
+ * are ONE 16-bit channels-last plane [B][H * W][C]; prec is PH_PREC_BF16 or PH_PREC_F16 (the FPN's one-plane grades); accumulation
+ * is fp32 and each layer output is rounded once.  All three calls launch only: no allocation, no synchronisation, no environment
+ * variable; a frame's bits do not depend on B; a bad argument is PH_EINVAL with a message before any launch, the output untouched.
+ * The *_workgroups functions return the workgroups of the launch the same arguments take (negative: the error code).
+ * ph_conv_cl     : Y[b][p][n] = act(sum_{tap, c} X[b][s p + tap][c] W'[n][tap][c] + b'[n] + R[b][p][n]).  ksize 1 or 3 (pad ksize / 2),
+ *                  stride 1 or 2 (a 1x1 stride-2 conv reads the sampled pixels only), Cin and Cout multiples of 64 in [64, 2048];
+ *                  output size floor((H + 2 pad - ksize) / stride) + 1 per axis, any H, W.  X: [B][H * W][Cin]; Wp: pack.pack_b32
+ *                  fragments of W'[Cout][ksize^2 * Cin] with k = tap * Cin + c, tap = 3 kh + kw; bias: b', fp32 [Cout]; R (nullable):
+ *                  the residual, Y's layout and format, added in fp32 before the one rounding; relu != 0: ReLU, else identity.
+ * ph_resnet_stem : conv 7x7 stride 2 pad 3 (3 -> 64) + b' + ReLU + MaxPool2d(3, 2, 1) in one kernel (the half-resolution map stays
+ *                  in LDS).  x: NCHW [B][3][H][W] of x_dtype PH_OUT_F32 or PH_OUT_BF16 (what ph_image_prepare writes), rounded to the
+ *                  grade as it is staged; Wp: pack.pack_b32 fragments of W'[64][176] with k = 24 kh + 3 kw + c (kw < 7; zero
+ *                  elsewhere); Y: [B][Hq * Wq][64], Hc = (H - 1) / 2 + 1, Hq = (Hc - 1) / 2 + 1 and likewise for W.  The maximum
+ *                  is over the window's entries inside the conv map only.
+ * ph_cl_to_nchw  : a plane X [B][HW][C] of grade prec (C a multiple of 64 in [64, 4096]) -> NCHW [B][C][HW] of out_dtype PH_OUT_F32 /
+ *                  PH_OUT_BF16 / PH_OUT_F16, each value through fp32 (exact unless out_dtype is the other 16-bit format). */
+int ph_conv_cl_workgroups(int ksize, int stride, int Cin, int Cout, int H, int W, int B);
+int ph_conv_cl(const uint16_t* X, const uint16_t* Wp, const float* bias, const uint16_t* R /* nullable */, uint16_t* Y, int ksize,
+               int stride, int relu, int B, int H, int W, int Cin, int Cout, int prec, void* stream);
+int ph_resnet_stem_workgroups(int H, int W, int B);
+int ph_resnet_stem(const void* x, int x_dtype, const uint16_t* Wp, const float* bias, uint16_t* Y, int B, int H, int W, int prec,
+                   void* stream);
+int ph_cl_to_nchw_workgroups(int B, int64_t HW, int C);
+int ph_cl_to_nchw(const uint16_t* X, void* out, int out_dtype, int B, int64_t HW, int C, int prec, void* stream);
+
 /* ---- N1: the quasi-dense embedding tracker as a native object (csrc/ph_tracker.hip; polyphonic/video/qdtrack/trackers/
  * quasi_dense_embed_tracker.py:47-207).  Host bookkeeping in C++ (boxes, labels, ids, ages), embeddings in a device POOL of
  * `capacity` rows of 256 floats inside `device_mem` (ph_tracker_device_bytes; owned by the caller, alive as long as the tracker).

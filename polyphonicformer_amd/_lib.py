@@ -408,6 +408,12 @@ SIGNATURES = {
     "ph_fpn_lateral": (C.c_int, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ph_fpn_output": (C.c_int, [_P, _P, _P, _I, _L, _P]),
     "ph_fpn_output_planes": (C.c_int, [_P, _P, _P, _P, _P, _I, _L, _I, _P]),
+    "ph_conv_cl_workgroups": (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),
+    "ph_conv_cl": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ph_resnet_stem_workgroups": (C.c_int, [_I, _I, _I]),
+    "ph_resnet_stem": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ph_cl_to_nchw_workgroups": (C.c_int, [_I, _L, _I]),
+    "ph_cl_to_nchw": (C.c_int, [_P, _P, _I, _I, _L, _I, _I, _P]),
     "ph_tracker_device_bytes": (C.c_size_t, [_I, _I]),
     "ph_tracker_create": (C.c_void_p, [_P, _P, _Z, _I, _I]),
     "ph_tracker_destroy": (None, [_P]),

@@ -1905,3 +1905,119 @@ class NativeAssocPlan(_NativePlan):
                                                            None if active is None else _lib.ptr(active), _lib.ptr(self.track_map),
                                                            _lib.ptr(self.ids_dev), _lib.stream_ptr()), "ph_assoc_plan_track_streams")
         return self.track_map, self.ids_dev
+
+
+# ---- ResNet backbone at inference (mmdet/models/backbones/resnet.py; csrc/ph_resnet.hip): the image tensor -> the FPN's stages ----
+def conv_out_size(n, k, s):
+    return (n + 2 * (k // 2) - k) // s + 1
+
+
+def conv_cl(x, wp, bias, res, y, k, s, relu, B, H, W, cin, cout, prec):
+    """channels-last 16-bit plane x [B, H*W, cin] -> y [B, Ho*Wo, cout]: conv k x k stride s with the folded BN (wp: pack_b32 fragments
+    of W'[cout][k*k*cin], bias: b'), + res (y's form, or None), ReLU if `relu`, one rounding"""
+    _lib.check(_lib.load().ph_conv_cl(_lib.ptr(x), _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(res), _lib.ptr(y), k, s, int(bool(relu)), B, H, W,
+                                      cin, cout, prec, _lib.stream_ptr()), "ph_conv_cl")
+    return y
+
+
+def resnet_stem(x, wp, bias, y, prec):
+    """x [B, 3, H, W] fp32 / bf16 contiguous -> y [B, Hq*Wq, 64]: conv 7x7 s2 + folded BN + ReLU + MaxPool2d(3, 2, 1)"""
+    B, _, H, W = x.shape
+    _lib.check(_lib.load().ph_resnet_stem(_lib.ptr(x), OUT_CODE[x.dtype], _lib.ptr(wp), _lib.ptr(bias), _lib.ptr(y), B, H, W, prec,
+                                          _lib.stream_ptr()), "ph_resnet_stem")
+    return y
+
+
+def stem_out_size(n):
+    return ((n - 1) // 2 + 1 - 1) // 2 + 1
+
+
+def cl_to_nchw(x, out, B, HW, C_, prec):
+    """channels-last 16-bit plane x [B, HW, C] of grade `prec` -> out [B, C, h, w] fp32 / bf16 / fp16"""
+    _lib.check(_lib.load().ph_cl_to_nchw(_lib.ptr(x), _lib.ptr(out), OUT_CODE[out.dtype], B, HW, C_, prec, _lib.stream_ptr()), "ph_cl_to_nchw")
+    return out
+
+
+class ResNetPlan:
+    """buffers + launch sequence of resnet.ResNet.forward for one (B, H, W, block structure, grade, hand-off dtype): the stem's plane, two
+    ping-pong block planes, the two inner planes of a bottleneck, the downsample plane and the NCHW stages, all sized here.  `run`
+    issues everything on the current stream -- one stream, so a captured graph of it has no parallel branches -- and neither
+    allocates nor synchronises; the outputs are the plan's buffers and are overwritten by the next call, as FpnPlan's are.
+    blocks: per stage a list of (cin, planes, stride, has_downsample)."""
+
+    def __init__(self, B, H, W, blocks, out_indices, prec, stage_dtype, device):
+        if prec not in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16):
+            raise _lib.PolyheadError("ResNetPlan: the grade must be bf16 or fp16 (one 16-bit plane)")
+        if stage_dtype not in OUT_CODE:
+            raise _lib.PolyheadError("ResNetPlan: the hand-off dtype must be torch.float32, torch.bfloat16 or torch.float16")
+        self.B, self.H, self.W, self.prec, self.stage_dtype = B, H, W, prec, stage_dtype
+        self.blocks, self.out_indices = [list(s) for s in blocks], tuple(out_indices)
+        lib, dev = _lib.load(), torch.device(device)
+        self.device = dev
+
+        def wg(n, what):
+            if n <= 0:
+                _lib.check(n if n < 0 else _lib.PH_EINVAL, what)
+            return n
+        h, w = stem_out_size(H), stem_out_size(W)
+        self.stem_hw = (h, w)
+        self.workgroups = [("stem", wg(lib.ph_resnet_stem_workgroups(H, W, B), "ph_resnet_stem_workgroups"))]
+        io = inner = down = 0
+        self.stage_shapes = []
+        for si, stage in enumerate(self.blocks):
+            for j, (cin, planes, s, has_down) in enumerate(stage):
+                ho, wo = conv_out_size(h, 3, s), conv_out_size(w, 3, s)
+                for name, k, st, ci, co, hh, ww in (("conv1", 1, 1, cin, planes, h, w), ("conv2", 3, s, planes, planes, h, w),
+                                                    ("conv3", 1, 1, planes, 4 * planes, ho, wo)) + \
+                        ((("downsample", 1, s, cin, 4 * planes, h, w),) if has_down else ()):
+                    self.workgroups.append((f"layer{si + 1}.{j}.{name}", wg(lib.ph_conv_cl_workgroups(k, st, ci, co, hh, ww, B),
+                                                                          "ph_conv_cl_workgroups")))
+                inner = max(inner, h * w * planes, ho * wo * planes)
+                io = max(io, ho * wo * 4 * planes)
+                if has_down:
+                    down = max(down, ho * wo * 4 * planes)
+                elif (cin, s) != (4 * planes, 1):
+                    raise _lib.PolyheadError("ResNetPlan: a block without downsample must keep its shape")
+                h, w = ho, wo
+            self.stage_shapes.append((4 * stage[-1][1], h, w))
+            self.workgroups.append((f"layer{si + 1}.to_nchw", wg(lib.ph_cl_to_nchw_workgroups(B, h * w, 4 * stage[-1][1]),
+                                                               "ph_cl_to_nchw_workgroups")))
+        e = lambda n: torch.empty((B * n,), dtype=torch.int16, device=dev)
+        self.p0 = e(self.stem_hw[0] * self.stem_hw[1] * 64)
+        self.pa, self.pb, self.t1, self.t2, self.pd = e(io), e(io), e(inner), e(inner), e(max(down, 8))
+        self.outs = {i: torch.empty((B,) + self.stage_shapes[i], dtype=stage_dtype, device=dev) for i in self.out_indices}
+
+    def run_stem(self, x, pk):
+        """the stem's launch; x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device"""
+        B = self.B
+        if tuple(x.shape) != (B, 3, self.H, self.W) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() \
+                or x.device != self.device:
+            raise _lib.PolyheadError(f"ResNetPlan.run: x must be a contiguous fp32 / bf16 device tensor of shape {(B, 3, self.H, self.W)}")
+        resnet_stem(x, pk["stem"][0], pk["stem"][1], self.p0, self.prec)
+        self._at = (self.stem_hw, self.p0, self.pa)                 # (size, the plane that holds the activation, the one to write next)
+
+    def run_stage(self, si, pk):
+        """stage si's launches (its bottlenecks and, if it is an output, the NCHW conversion) on what the previous step left"""
+        B, prec, stage = self.B, self.prec, self.blocks[si]
+        (h, w), cur, nxt = self._at
+        for j, (cin, planes, s, has_down) in enumerate(stage):
+            c = pk["blocks"][si][j]
+            ho, wo = conv_out_size(h, 3, s), conv_out_size(w, 3, s)
+            conv_cl(cur, c["conv1"][0], c["conv1"][1], None, self.t1, 1, 1, True, B, h, w, cin, planes, prec)
+            conv_cl(self.t1, c["conv2"][0], c["conv2"][1], None, self.t2, 3, s, True, B, h, w, planes, planes, prec)
+            idn = cur
+            if has_down:
+                idn = conv_cl(cur, c["downsample"][0], c["downsample"][1], None, self.pd, 1, s, False, B, h, w, cin, 4 * planes, prec)
+            conv_cl(self.t2, c["conv3"][0], c["conv3"][1], idn, nxt, 1, 1, True, B, ho, wo, planes, 4 * planes, prec)
+            cur, nxt = nxt, (self.pb if nxt is self.pa else self.pa)
+            h, w = ho, wo
+        if si in self.outs:
+            cl_to_nchw(cur, self.outs[si], B, h * w, 4 * stage[-1][1], prec)
+        self._at = ((h, w), cur, nxt)
+
+    def run(self, x, pk):
+        """x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device; pk: resnet.ResNet's pack.  Returns the NCHW stages of out_indices"""
+        self.run_stem(x, pk)
+        for si in range(max(self.out_indices) + 1):              # a stage behind the last output has no reader
+            self.run_stage(si, pk)
+        return tuple(self.outs[i] for i in self.out_indices)

@@ -75,6 +75,11 @@ def build_neck(cfg):
     return NECKS.build(cfg)
 
 
+def build_backbone(cfg):
+    from . import resnet  # noqa: F401  (registers `ResNet`)
+    return BACKBONES.build(cfg)
+
+
 def build_loss(cfg):
     return LOSSES.build(cfg)
 
@@ -109,7 +114,7 @@ def wrap_fp16_model(model):
     cfg.get('fp16', None); if fp16_cfg is not None: wrap_fp16_model(model)`): every module of this package under `model`
     that has precision grades is switched to its fp16 grade -- KernelHead (and its neck) to one fp16 plane of maps and
     weights, KernelUpdateIterHead to the `fp16` mode of engine.MODES with fp16 logits, the track head to the grade engine.PREC maps 'fp16' to,
-    an FPN of this package (fpn.FPN) to one fp16 plane.
+    an FPN of this package (fpn.FPN) to one fp16 plane, a ResNet of this package (resnet.ResNet) to fp16 planes and folded weights.
     `model`: a module tree (a detector holding `rpn_head` / `roi_head`, or a head), or an iterable of modules."""
     import torch
     mods = list(model) if isinstance(model, (list, tuple)) else [model]
@@ -127,6 +132,9 @@ def wrap_fp16_model(model):
                 done.append(m)
             elif m.__class__.__name__ == "FPN" and m.__class__.__module__ == __package__ + ".fpn":
                 m.set_precision("fp16")          # this package's FPN only (mmdet's own has no grades): one fp16 plane
+                done.append(m)
+            elif m.__class__.__name__ == "ResNet" and m.__class__.__module__ == __package__ + ".resnet":
+                m.set_precision("fp16")          # this package's ResNet only: fp16 activation planes and folded weights
                 done.append(m)
     return done
 
