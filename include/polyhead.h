@@ -1282,6 +1282,98 @@ int ph_fpn_plan_run_laterals(ph_fpn_plan* plan, const ph_fpn_io* io, void* strea
 int ph_fpn_plan_run_output(ph_fpn_plan* plan, int level, const ph_fpn_io* io, void* stream);
 int ph_fpn_plan_run(ph_fpn_plan* plan, const ph_fpn_io* io, void* stream);
 
+/* ---- the backbone as a native object (csrc/ph_resnetplan.hip): what resnet.ResNet._pack + engine.ResNetPlan do from Python --
+ * mmdet/models/backbones/resnet.py:631-646 at inference for a C / C++ caller: from the image tensor to the four stages ph_fpn_io.stages
+ * takes.  Conventions are ph_fpn_plan_*'s: status codes + ph_last_error_string, caller-owned 256-byte aligned pack and workspace, no
+ * allocation of device memory, no synchronisation, no host read of device data and no environment variable in pack / create / run,
+ * every cfg or pointer error returned before the first launch, every run call capturable into a hipGraph (one stream, no parallel
+ * branches).  The launches are ph_resnet_stem, ph_conv_cl and ph_cl_to_nchw with engine.ResNetPlan's arguments, so the bits of every
+ * stage are the Python plan's.
+ *   B            frames per call, 1 .. 4096
+ *   H, W         image size; a size at which ph_resnet_stem, ph_conv_cl or ph_cl_to_nchw would refuse its launch is refused with its words
+ *   depth        50, 101 or 152 (Bottleneck blocks (3, 4, 6, 3) / (3, 4, 23, 3) / (3, 8, 36, 3)); anything else is PH_EUNSUPPORTED
+ *   mode         PH_MODE_*, mapped to the grade as ph_fpn_cfg.mode; the backbone has one-plane grades only (PH_MODE_BF16, PH_MODE_FP16):
+ *                a mode whose grade is hi + lo is PH_EUNSUPPORTED
+ *   x_dtype      element type of the image: PH_OUT_F32 / PH_OUT_BF16 (ph_resnet_stem's)
+ *   out_dtype    element type of the stages: PH_OUT_F32 / PH_OUT_BF16 / PH_OUT_F16 (ph_cl_to_nchw's)
+ *   out_mask     bit i set: stage i is written; non-zero, within the low 4 bits.  Stages behind the highest set bit are not run
+ *   eps          the BatchNorm eps of the fold (finite, >= 0) */
+typedef struct {
+    int32_t B, H, W;
+    int32_t depth;
+    int32_t mode;               /* PH_MODE_* */
+    int32_t x_dtype, out_dtype; /* PH_OUT_* */
+    int32_t out_mask;
+    double eps;
+} ph_resnet_cfg;
+
+/* ---- the parameter table: fp32 device tensors under the reference's state_dict keys, in state_dict order without the
+ * num_batches_tracked entries.  Convolution c owns entries 5 c .. 5 c + 4: its weight [Cout][Cin][k][k], then its norm's weight, bias,
+ * running_mean, running_var [Cout].  Convolution 0 is conv1 / bn1; then per block conv1 / bn1, conv2 / bn2, conv3 / bn3 and, where the
+ * block has one, downsample.0 / downsample.1.  53 / 104 / 155 convolutions, 265 / 520 / 775 parameters at depth 50 / 101 / 152. */
+#define PH_RESNET_MAX_CONVS 155
+int ph_resnet_nparams(const ph_resnet_cfg* cfg);                            /* reads cfg.depth only; < 0 on a bad depth */
+const char* ph_resnet_param_name(const ph_resnet_cfg* cfg, int index);      /* NULL out of range or on a bad depth */
+int64_t ph_resnet_param_numel(const ph_resnet_cfg* cfg, int index);         /* elements; < 0 out of range or on a bad depth */
+
+/* ---- packing (k_resnet_pack: the float64 BatchNorm fold and the fragment order in one kernel, one launch per convolution, once per
+ * weight load).  Convolution c has two pieces, 2 c (W) and 2 c + 1 (b), each at a 256-byte aligned offset of one device buffer, the
+ * alignment padding written as zeros; they are resnet.ResNet._pack's tensors, byte for byte:
+ *   W   uint16 [rows * K]   pack.pack_b32 fragments of the folded W'[n][tap * Cin + c] = fp32(w[n][c][tap] * s[n]) rounded to the grade,
+ *                           s = gamma / sqrt(var + eps) in float64; K = k * k * Cin; rows = Cout rounded up to a multiple of 32, the
+ *                           rows at or above Cout zero.  The stem's matrix is [64][176] in resnet.stem_matrix's K order
+ *                           (24 kh + 3 kw + c, zero where 3 kw + c >= 21 or K >= 168): ph_resnet_stem's Wp
+ *   b   float [Cout]        b' = fp32(beta - mean * s), in float64 */
+#define PH_RPACK_W(c) (2 * (c))
+#define PH_RPACK_B(c) (2 * (c) + 1)
+typedef struct {
+    uint64_t offset[2 * PH_RESNET_MAX_CONVS];   /* bytes from the start of the pack, multiples of 256 */
+    uint64_t bytes[2 * PH_RESNET_MAX_CONVS];    /* size of the piece; the next piece starts at offset + bytes rounded up to 256 */
+    int32_t nconvs;                             /* convolutions in use: pieces 0 .. 2 nconvs - 1 */
+    int32_t reserved;
+} ph_resnet_layout;
+size_t ph_resnet_pack_bytes(const ph_resnet_cfg* cfg);                      /* 0 on a bad cfg (see ph_last_error_string) */
+int ph_resnet_pack_layout(const ph_resnet_cfg* cfg, ph_resnet_layout* layout);
+/* `params`: host array of ph_resnet_nparams device pointers; `pack`: 256-byte aligned device buffer of ph_resnet_pack_bytes */
+int ph_resnet_pack(const ph_resnet_cfg* cfg, const float* const* params, void* pack, void* stream);
+
+/* ---- plan lifetime.  The workspace holds engine.ResNetPlan's planes (16-bit channels-last): the stem's, two ping-pong block planes,
+ * a bottleneck's two inner planes and the downsample plane.  The stages are the caller's.  ZEROING CONTRACT: none.
+ * ph_resnet_plan_create touches no device memory.  The caller keeps pack and workspace alive as long as the plan. */
+typedef struct ph_resnet_plan ph_resnet_plan;
+typedef struct {
+    int32_t prec;               /* the grade, PH_PREC_BF16 or PH_PREC_F16 */
+    int32_t launches;           /* launches of ph_resnet_plan_run: 1 + convolutions of the stages run + stages written */
+    int32_t nconvs;             /* ph_conv_cl launches of a run */
+    int32_t stem_workgroups;    /* ph_resnet_stem_workgroups */
+    int32_t c[4], h[4], w[4];   /* the four stages: [B][c][h][w] */
+    int32_t nchw_workgroups[4]; /* ph_cl_to_nchw_workgroups of a stage that is written, 0 otherwise */
+    int32_t conv_workgroups[PH_RESNET_MAX_CONVS];  /* ph_conv_cl_workgroups per convolution in launch order (per block: conv1, conv2,
+                                                      downsample where the block has one, conv3); 0 behind nconvs */
+} ph_resnet_geometry;
+size_t ph_resnet_plan_workspace_bytes(const ph_resnet_cfg* cfg);            /* 0 on a bad cfg */
+int ph_resnet_plan_create(const ph_resnet_cfg* cfg, const void* pack, void* workspace, size_t workspace_bytes, ph_resnet_plan** out);
+int ph_resnet_plan_info(const ph_resnet_plan* plan, ph_resnet_geometry* out);
+/* the same answer without a plan; needs no device, no pack and no workspace; every cfg error of ph_resnet_plan_create comes back
+ * from here too */
+int ph_resnet_geometry_of(const ph_resnet_cfg* cfg, ph_resnet_geometry* out);
+void ph_resnet_plan_destroy(ph_resnet_plan* plan);
+
+/* ---- one backbone call.
+ *   image          [B][3][H][W] of cfg.x_dtype, NCHW-contiguous
+ *   stages[i]      [B][c_i][h_i][w_i] of cfg.out_dtype, NCHW-contiguous, for every bit i of cfg.out_mask; the others are not read
+ * ph_resnet_plan_run_stem: the stem's launch (reads `image`).
+ * ph_resnet_plan_run_stage: stage `stage`'s bottlenecks on what the previous piece left in the workspace and, if the stage is written,
+ *   its ph_cl_to_nchw launch (reads stages[stage] only).  Stage 0 follows the stem, stage i stage i - 1.
+ * ph_resnet_plan_run: the stem, then stages 0 .. the highest bit of out_mask, all on `stream`. */
+typedef struct {
+    const void* image;
+    void* stages[4];
+} ph_resnet_io;
+int ph_resnet_plan_run_stem(ph_resnet_plan* plan, const ph_resnet_io* io, void* stream);
+int ph_resnet_plan_run_stage(ph_resnet_plan* plan, int stage, const ph_resnet_io* io, void* stream);
+int ph_resnet_plan_run(ph_resnet_plan* plan, const ph_resnet_io* io, void* stream);
+
 /* ---- N1 as a native object (csrc/ph_assocplan.hip): the association step of PolyphonicVideo.simple_test
  * (polyphonic_former_video.py:359-405) behind ph_panoptic_merge, for a C / C++ caller -- what video.VideoAssociator and
  * track_head.QuasiDenseMaskEmbedHeadGTMask string together from Python: things for tracking -> segment boxes -> FPN RoIAlign ->

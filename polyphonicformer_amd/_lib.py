@@ -136,6 +136,29 @@ class FpnIO(C.Structure):
                 ("add", C.c_void_p * 4)]
 
 
+# the native backbone plan (polyhead.h ph_resnet_cfg .. ph_resnet_plan_run); convolution c of the depth's table owns parameters
+# 5 c .. 5 c + 4 and pack pieces 2 c (W) and 2 c + 1 (b)
+PH_RESNET_MAX_CONVS = 155
+
+
+class ResNetCfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "H", "W", "depth", "mode", "x_dtype", "out_dtype", "out_mask")] + [("eps", C.c_double)]
+
+
+class ResNetLayout(C.Structure):
+    _fields_ = [("offset", C.c_uint64 * (2 * PH_RESNET_MAX_CONVS)), ("bytes", C.c_uint64 * (2 * PH_RESNET_MAX_CONVS)),
+                ("nconvs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResNetGeometry(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("prec", "launches", "nconvs", "stem_workgroups")] + \
+        [(n, C.c_int32 * 4) for n in ("c", "h", "w", "nchw_workgroups")] + [("conv_workgroups", C.c_int32 * PH_RESNET_MAX_CONVS)]
+
+
+class ResNetIO(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("stages", C.c_void_p * 4)]
+
+
 # the native association plan (polyhead.h ph_track_cfg .. ph_assoc_plan_match)
 PH_TRACK_MAX_CONVS = 8
 PH_TPACK_FC, PH_TPACK_FC_B, PH_TPACK_EMB, PH_TPACK_EMB_B, PH_TPACK_COUNT = 24, 25, 26, 27, 28     # conv i, gamma 8 + i, beta 16 + i
@@ -275,6 +298,7 @@ STRUCTS = {"ph_stage_layout": StageLayout, "ph_decode_cfg": DecodeCfg, "ph_decod
            "ph_khead_cfg": KheadCfg, "ph_khead_layout": KheadLayout, "ph_khead_geometry": KheadGeometry, "ph_khead_io": KheadIO,
            "ph_neck_cfg": NeckCfg, "ph_neck_layout": NeckLayout, "ph_neck_geometry": NeckGeometry, "ph_neck_io": NeckIO,
            "ph_fpn_cfg": FpnCfg, "ph_fpn_layout": FpnLayout, "ph_fpn_geometry": FpnGeometry, "ph_fpn_io": FpnIO,
+           "ph_resnet_cfg": ResNetCfg, "ph_resnet_layout": ResNetLayout, "ph_resnet_geometry": ResNetGeometry, "ph_resnet_io": ResNetIO,
            "ph_track_cfg": TrackCfg, "ph_track_layout": TrackLayout, "ph_assoc_cfg": AssocCfg, "ph_assoc_geometry": AssocGeometry,
            "ph_assoc_io": AssocIO, "ph_tracker_cfg": TrackerCfg, "ph_dtracker_layout": DtrackerLayout, "ph_dtracker_io": DtrackerIO,
            "ph_dvpq_cfg": DvpqCfg, "ph_dvpq_io": DvpqIO, "ph_assign_cfg": AssignCfg, "ph_assign_layout": AssignLayout,
@@ -476,6 +500,20 @@ SIGNATURES = {
     "ph_fpn_plan_run_laterals": (C.c_int, [_P, C.POINTER(FpnIO), _P]),
     "ph_fpn_plan_run_output": (C.c_int, [_P, _I, C.POINTER(FpnIO), _P]),
     "ph_fpn_plan_run": (C.c_int, [_P, C.POINTER(FpnIO), _P]),
+    "ph_resnet_nparams": (C.c_int, [C.POINTER(ResNetCfg)]),
+    "ph_resnet_param_name": (C.c_char_p, [C.POINTER(ResNetCfg), _I]),
+    "ph_resnet_param_numel": (C.c_int64, [C.POINTER(ResNetCfg), _I]),
+    "ph_resnet_pack_bytes": (C.c_size_t, [C.POINTER(ResNetCfg)]),
+    "ph_resnet_pack_layout": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetLayout)]),
+    "ph_resnet_pack": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_resnet_plan_workspace_bytes": (C.c_size_t, [C.POINTER(ResNetCfg)]),
+    "ph_resnet_plan_create": (C.c_int, [C.POINTER(ResNetCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
+    "ph_resnet_plan_info": (C.c_int, [_P, C.POINTER(ResNetGeometry)]),
+    "ph_resnet_geometry_of": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetGeometry)]),
+    "ph_resnet_plan_destroy": (None, [_P]),
+    "ph_resnet_plan_run_stem": (C.c_int, [_P, C.POINTER(ResNetIO), _P]),
+    "ph_resnet_plan_run_stage": (C.c_int, [_P, _I, C.POINTER(ResNetIO), _P]),
+    "ph_resnet_plan_run": (C.c_int, [_P, C.POINTER(ResNetIO), _P]),
     "ph_track_param_name": (C.c_char_p, [C.POINTER(TrackCfg), _I]),
     "ph_track_param_numel": (C.c_int64, [C.POINTER(TrackCfg), _I]),
     "ph_track_pack_bytes": (C.c_size_t, [C.POINTER(TrackCfg)]),

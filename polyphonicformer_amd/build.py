@@ -15,10 +15,11 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpolyhead.so")
 # the Python-free callers of the C ABI, built next to the library they link: (source, program)
 #   decode_c: the decode plan;  head_c: neck maps -> KernelHead plan -> decode plan -> panoptic merge;  neck_c: FPN levels -> neck plan
-#   in front of that;  fpn_c: backbone stages -> FPN plan in front of that
+#   in front of that;  fpn_c: backbone stages -> FPN plan in front of that;  image_c: the image -> backbone plan in front of that
 EXAMPLES = [(os.path.join(os.path.dirname(HERE), "examples", d, prog + ".cpp"), os.path.join(HERE, prog))
-            for d, prog in (("decode_c", "decode_main"), ("head_c", "head_main"), ("neck_c", "neck_main"), ("fpn_c", "fpn_main"))]
-EXAMPLE, HEAD_EXAMPLE, NECK_EXAMPLE, FPN_EXAMPLE = (prog for _, prog in EXAMPLES)
+            for d, prog in (("decode_c", "decode_main"), ("head_c", "head_main"), ("neck_c", "neck_main"), ("fpn_c", "fpn_main"),
+                            ("image_c", "image_main"))]
+EXAMPLE, HEAD_EXAMPLE, NECK_EXAMPLE, FPN_EXAMPLE, IMAGE_EXAMPLE = (prog for _, prog in EXAMPLES)
 OBJ = os.path.join(CSRC, "build")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

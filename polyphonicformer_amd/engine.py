@@ -2021,3 +2021,108 @@ class ResNetPlan:
         for si in range(max(self.out_indices) + 1):              # a stage behind the last output has no reader
             self.run_stage(si, pk)
         return tuple(self.outs[i] for i in self.out_indices)
+
+
+# ---- the backbone as a native object (include/polyhead.h ph_resnet_cfg .. ph_resnet_plan_run) --------------------------------
+RESNET_ARCH = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}       # Bottleneck blocks per stage
+
+
+def native_resnet_cfg(B, H, W, depth, prec, x_dtype=torch.float32, stage_dtype=torch.float32, out_indices=(0, 1, 2, 3), eps=1e-5):
+    """the ph_resnet_cfg of a native backbone plan.  `prec`: a precision name (engine.KHEAD_PREC's keys) or the grade code; `x_dtype`:
+    the image's torch dtype; `stage_dtype`: the stages'; `out_indices`: the stages written.  The backbone has no PH_* variable"""
+    name = prec if isinstance(prec, str) else _KHEAD_MODE_OF_PREC[prec]
+    if x_dtype not in OUT_CODE or stage_dtype not in OUT_CODE:
+        raise _lib.PolyheadError("the backbone's image is fp32 or bf16, its stages fp32, bf16 or fp16")
+    if not out_indices or min(out_indices) < 0 or max(out_indices) > 3:
+        raise _lib.PolyheadError("out_indices must lie in [0, 4)")
+    mask = 0
+    for i in out_indices:
+        mask |= 1 << int(i)
+    return _lib.ResNetCfg(B=B, H=H, W=W, depth=depth, mode=_lib.PH_MODE[name], x_dtype=OUT_CODE[x_dtype], out_dtype=OUT_CODE[stage_dtype],
+                          out_mask=mask, eps=float(eps))
+
+
+class NativeResNetPack(_NativePack):
+    """one device buffer packed by ph_resnet_pack (the BatchNorm fold in float64 on the device), and its pieces as views in the form
+    of resnet.ResNet._pack's dict (`pk`: so either plan -- ResNetPlan or NativeResNetPlan -- runs from it)"""
+    _symbols = ("ph_resnet_pack_bytes", "ph_resnet_param_name", "ph_resnet_param_numel", "ph_resnet_pack", "ph_resnet_pack_layout")
+    _layout_type, _name_takes_cfg = _lib.ResNetLayout, True
+    _nparams = staticmethod(lambda cfg: _lib.load().ph_resnet_nparams(C.byref(cfg)))
+
+    def _pieces(self, cfg):
+        self.depth, self.eps = cfg.depth, cfg.eps
+        convs = iter(range(self.layout.nconvs))                 # state_dict order: a block's conv1, conv2, conv3, downsample
+
+        def one():
+            c = next(convs)
+            return self.piece(2 * c, torch.int16, (-1,)), self.piece(2 * c + 1, torch.float32, (-1,))
+        stem = one()
+        self.pk = dict(stem=stem, blocks=[[dict(conv1=one(), conv2=one(), conv3=one(), downsample=one() if j == 0 else None)
+                                           for j in range(nb)] for nb in RESNET_ARCH[cfg.depth]])
+
+
+def native_resnet_pack(module, cfg, device):
+    """the backbone's parameters and running statistics (a resnet.ResNet, or its state_dict) folded and packed on the device by
+    ph_resnet_pack"""
+    return NativeResNetPack.pack_on_device(module, cfg, device)
+
+
+class NativeResNetPlan(_NativePlan):
+    """ResNetPlan's `run` / `run_stem` / `run_stage` surface over the native plan: ONE native call per forward (ph_resnet_plan_run)
+    instead of 57 at depth 50; the same launch sequence and arguments as the ResNetPlan of the same shape, so the same bits.  The
+    plan owns the stage tensors as ResNetPlan does.  `pack`: a NativeResNetPack; `cfg`: a ph_resnet_cfg to use as it is (its x_dtype
+    follows each run's image) instead of `native_resnet_cfg`'s."""
+    _symbols, _geometry_type, _destroy_symbol = ("ph_resnet_plan_workspace_bytes", "ph_resnet_plan_create", "ph_resnet_plan_info"), \
+        _lib.ResNetGeometry, "ph_resnet_plan_destroy"
+
+    def __init__(self, pack, B, H, W, device, stage_dtype=torch.float32, out_indices=(0, 1, 2, 3), cfg=None):
+        dev = torch.device(device)
+        self.pack, self.B, self.H, self.W, self.device = pack, B, H, W, dev
+        base = cfg if cfg is not None else native_resnet_cfg(B, H, W, pack.depth, _MODE_NAME[pack.mode], torch.float32, stage_dtype,
+                                                             out_indices, pack.eps)
+        self.cfg = _lib.ResNetCfg.from_buffer_copy(bytes(base))
+        self.out_indices = tuple(i for i in range(4) if self.cfg.out_mask >> i & 1)
+        self.stage_dtype = {v: k for k, v in OUT_CODE.items()}[self.cfg.out_dtype]
+        self._alloc_workspace()
+        self._handles = {}
+        self.geometry = geo = self._info(self._handle(torch.float32))
+        self.prec = geo.prec
+        self.stage_shapes = [(geo.c[i], geo.h[i], geo.w[i]) for i in range(4)]
+        self.outs = {i: torch.empty((B,) + self.stage_shapes[i], dtype=self.stage_dtype, device=dev) for i in self.out_indices}
+        self.io = _lib.ResNetIO()
+        for i, t in self.outs.items():
+            self.io.stages[i] = t.data_ptr()
+
+    def _handle(self, x_dtype):
+        """the native plan of this image dtype"""
+        return self._handle_of(x_dtype=OUT_CODE[x_dtype])
+
+    def _own(self, pk, what):
+        if pk is not None and pk is not self.pack and pk is not self.pack.pk:
+            raise _lib.PolyheadError(f"NativeResNetPlan.{what}: the plan runs from the pack it was created with")
+
+    def _image(self, x):
+        if tuple(x.shape) != (self.B, 3, self.H, self.W) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() \
+                or x.device != self.device:
+            raise _lib.PolyheadError(f"NativeResNetPlan.run: x must be a contiguous fp32 / bf16 device tensor of shape "
+                                     f"{(self.B, 3, self.H, self.W)}")
+        self.io.image = x.data_ptr()
+        self._h_run = self._handle(x.dtype)
+
+    def run_stem(self, x, pk=None):
+        """the stem's launch; x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device"""
+        self._own(pk, "run_stem")
+        self._image(x)
+        _lib.check(_lib.load().ph_resnet_plan_run_stem(self._h_run, C.byref(self.io), _lib.stream_ptr()), "ph_resnet_plan_run_stem")
+
+    def run_stage(self, si, pk=None):
+        """stage si's launches on what the previous step left (ResNetPlan.run_stage)"""
+        self._own(pk, "run_stage")
+        _lib.check(_lib.load().ph_resnet_plan_run_stage(self._h_run, si, C.byref(self.io), _lib.stream_ptr()), "ph_resnet_plan_run_stage")
+
+    def run(self, x, pk=None):
+        """ResNetPlan.run's arguments (`pk`: the plan's own pack, when given).  Returns the NCHW stages of out_indices"""
+        self._own(pk, "run")
+        self._image(x)
+        _lib.check(_lib.load().ph_resnet_plan_run(self._h_run, C.byref(self.io), _lib.stream_ptr()), "ph_resnet_plan_run")
+        return tuple(self.outs[i] for i in self.out_indices)

@@ -8,7 +8,8 @@ Same constructor keywords and the reference's state_dict keys (`conv1.weight`, `
 Inference (`forward` on the device with no gradient asked for) runs in libpolyhead (csrc/ph_resnet.hip): every BatchNorm is folded
 into its convolution in float64 (`fold_bn`), activations are one 16-bit channels-last plane ('bf16', the default, or 'fp16'), and the
 stages come back as NCHW tensors (fp32 by default; `set_stage_dtype` for the 16-bit hand-off `ph_fpn_lateral` also takes).
-`_forward_torch` is the same arithmetic in torch ops: CPU tensors, and whenever grad is enabled and a parameter or the input requires
+`use_native_plan(True)` moves the fold, the packing and the launch sequence into the library as well (ph_resnet_pack,
+engine.NativeResNetPlan: one native call per forward, the same bits).  `_forward_torch` is the same arithmetic in torch ops: CPU tensors, and whenever grad is enabled and a parameter or the input requires
 grad -- training the backbone is torch's job, as with fpn.FPN's default.
 
 Keywords taken for the signature's sake only: `with_cp` (activation checkpointing trades memory for time and changes no value; it is
@@ -23,7 +24,7 @@ from . import _lib, engine as E
 from .pack import pack_b32
 from .registry import register_everywhere
 
-ARCH = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+ARCH = E.RESNET_ARCH
 STEM_K = 176            # 7 kernel rows x 24 (21 values (kw, c) + 3 zeros) = 168, padded to a multiple of 16
 
 
@@ -133,6 +134,7 @@ class ResNet(nn.Module):
         self.feat_dim = 2048
         self.precision, self.stage_dtype = "bf16", torch.float32
         self._packs, self._plans = {}, {}
+        self._native, self._native_packs, self._native_plans = False, {}, {}
         self._freeze_stages()
 
     def init_weights(self):
@@ -153,6 +155,7 @@ class ResNet(nn.Module):
             raise ValueError(f"ResNet.set_precision: 'bf16' or 'fp16', not {precision!r} (a hi + lo grade is not built)")
         self.precision = precision
         self._packs.clear(); self._plans.clear()
+        self._native_packs.clear(); self._native_plans.clear()
         return self
 
     def set_stage_dtype(self, dtype):
@@ -160,7 +163,13 @@ class ResNet(nn.Module):
         if dtype not in E.OUT_CODE:
             raise ValueError("ResNet.set_stage_dtype: torch.float32, torch.bfloat16 or torch.float16")
         self.stage_dtype = dtype
-        self._plans.clear()
+        self._plans.clear(); self._native_plans.clear()
+        return self
+
+    def use_native_plan(self, flag=True):
+        """opt in: `forward` on the device folds and packs with ph_resnet_pack and runs engine.NativeResNetPlan -- one native call per
+        forward, the same launches and the same bits as the default path"""
+        self._native = bool(flag)
         return self
 
     # ---- resnet.py:613-658
@@ -218,6 +227,33 @@ class ResNet(nn.Module):
             self._packs[key] = dict(stem=one(self.conv1, self.bn1, stem_matrix), blocks=blocks)
         return self._packs[key]
 
+    def _native_pack(self, dev, cfg):
+        key = (str(dev), self.precision, self._versions())
+        if key not in self._native_packs:
+            self._native_packs.clear(); self._native_plans.clear()           # a plan is created over its pack
+            self._native_packs[key] = E.native_resnet_pack(self, cfg, dev)
+        return self._native_packs[key]
+
+    def _native_plan_of(self, x):
+        """`_plan_of` for the native path: (the NativeResNetPlan of this input, its pack, the input as the plan takes it)"""
+        E._require_gpu(x, "x")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise _lib.PolyheadError("ResNet: x must be [B, 3, H, W]")
+        eps = {m.eps for m in self.modules() if isinstance(m, nn.BatchNorm2d)}
+        if len(eps) != 1:
+            raise _lib.PolyheadError("ResNet.use_native_plan: ph_resnet_cfg carries one BatchNorm eps; this module's norms have several")
+        dev, (B, _, H, W) = x.device, x.shape
+        cfg = E.native_resnet_cfg(B, H, W, self.depth, self.precision, torch.float32, self.stage_dtype, self.out_indices, eps.pop())
+        with torch.cuda.device(dev):
+            pack = self._native_pack(dev, cfg)
+            key = (B, H, W, str(dev), self.stage_dtype, tuple(self.out_indices))
+            plan = self._native_plans.get(key)
+            if plan is None:
+                if len(self._native_plans) >= self.MAX_PLANS:
+                    self._native_plans.clear()
+                plan = self._native_plans[key] = E.NativeResNetPlan(pack, B, H, W, dev, cfg=cfg)
+        return plan, pack, x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.contiguous().float()
+
     def block_table(self):
         """per stage a list of (cin, planes, stride, has_downsample): what engine.ResNetPlan sizes its buffers from"""
         return [[(m.inplanes, m.planes, m.stride, m.downsample is not None) for m in getattr(self, name)] for name in self.res_layers]
@@ -242,7 +278,7 @@ class ResNet(nn.Module):
     def forward(self, x):
         if not x.is_cuda or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
             return self._forward_torch(x)
-        plan, pk, xin = self._plan_of(x)
+        plan, pk, xin = self._native_plan_of(x) if self._native else self._plan_of(x)
         with torch.cuda.device(x.device):
             return plan.run(xin, pk)
 

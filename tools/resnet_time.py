@@ -9,11 +9,17 @@ the device path and the two torch forms take turns inside every repetition; the 
     group's launches alone (`ResNetPlan.run_stem` / `run_stage`, without `forward`'s host work) and the achieved TFLOP/s from
     2 K Cout per output pixel -- twice the multiply-add count -- (the stem counted with K = 147; the NCHW conversion is inside its
     layer's window),
-  * the whole backbone beside the FPN + neck's time (--fpn-neck-ms, DESIGN.md 7f7: 1.07 ms).
+  * the whole backbone beside the FPN + neck's time (--fpn-neck-ms, DESIGN.md 7f7: 1.07 ms),
+  * with --native-out, INSTEAD of the sections above: the native plan beside the Python plan, same method (HIP events, median of
+    --reps after --warmup, alternating in one process): per B the GPU time and the host wall time per call (the time the call takes to
+    return, the queue empty before it) of `NativeResNetPlan.run` (one native call) and `ResNetPlan.run` (57 ctypes calls) on the same
+    pack; and the weight load from a resident fp32 state_dict, wall time to the finished pack: `ph_resnet_pack` (engine.
+    native_resnet_pack) against `ResNet._pack` (host float64).
 
 The result is written to --out after every section, so a run that is cut short leaves what it measured.
 
     python tools/resnet_time.py --out profiles/resnet/time.json
+    python tools/resnet_time.py --native-out profiles/resnet/native_time.json
 """
 import argparse
 import copy
@@ -21,6 +27,7 @@ import json
 import os
 import statistics
 import sys
+import time
 
 import torch
 
@@ -57,6 +64,63 @@ def alternate(runs, reps, warmup):
     return {k: summary(v) for k, v in samples.items()}
 
 
+def alternate_host(runs, reps, warmup, sync_inside=False):
+    """`alternate` with the host's wall time beside the GPU's: {name: {"gpu": summary, "host": summary}}.  The queue is empty when a
+    call starts; `sync_inside`: the wall time runs to the end of the call's GPU work (a weight load), not to its return (a launch call)"""
+    gpu, host = {k: [] for k in runs}, {k: [] for k in runs}
+    for rep in range(warmup + reps):
+        for k, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a.record()
+            fn()
+            b.record()
+            if sync_inside:
+                torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            if rep >= warmup:
+                gpu[k].append(a.elapsed_time(b))
+                host[k].append((t1 - t0) * 1e3)
+    return {k: {"gpu": summary(gpu[k]), "host": summary(host[k])} for k in runs}
+
+
+def native_section(m, dev, batches, reps, warmup, out):
+    """the native plan beside the Python plan, and the two weight loads; written to `out` after every part"""
+    res = {"command": "python tools/resnet_time.py --native-out OUT", "workload": "ResNet-50 of a 1024 x 2048 fp32 image -> four fp32 NCHW "
+           "stages, grade bf16: NativeResNetPlan.run (one native call) and ResNetPlan.run (57 ctypes calls) on the same pack alternate in "
+           "one process; gpu = HIP events around the call, host = wall time of the call itself with the queue empty before it.  pack: "
+           "wall time from a resident fp32 state_dict to the finished device pack", "reps": reps, "warmup": warmup}
+
+    def flush():
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+    m = copy.deepcopy(m).set_precision("bf16")
+    with torch.no_grad():
+        cfg = E.native_resnet_cfg(1, H, W, 50, "bf16")
+        pack = E.native_resnet_pack(m, cfg, dev)
+        for B in batches:
+            x = resnet_cases.inputs(1, (B, 3, H, W))[0].to(dev)
+            native = E.NativeResNetPlan(pack, B, H, W, dev)
+            python = E.ResNetPlan(B, H, W, m.block_table(), (0, 1, 2, 3), E.KHEAD_PREC["bf16"], torch.float32, dev)
+            res[f"B{B}"] = alternate_host({"native_plan_run": lambda: native.run(x), "python_plan_run": lambda: python.run(x, pack.pk)},
+                                          reps, warmup)
+            del native, python
+            torch.cuda.empty_cache()
+            flush()
+        sd = {k: v.detach().float().to(dev) for k, v in m.state_dict().items()}
+
+        def python_pack():
+            m._packs.clear()
+            m._pack(dev)
+        res["pack"] = alternate_host({"ph_resnet_pack": lambda: E.native_resnet_pack(sd, cfg, dev), "ResNet._pack": python_pack}, reps, warmup,
+                                     sync_inside=True)
+        flush()
+
+
 def group_gflop(m):
     """GFLOP per frame of the stem and of each layer: 2 K Cout per output pixel"""
     h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -79,6 +143,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batches", default="1,4")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch forms")
+    ap.add_argument("--native-out", default=None, help="measure the native plan beside the Python plan, and the two weight loads, instead")
     ap.add_argument("--fpn-neck-ms", type=float, default=1.07, help="the FPN + neck's time per frame to set the backbone beside")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -87,6 +152,8 @@ def main():
     m = ResNet(50, frozen_stages=1, norm_eval=True)
     m.load_state_dict(resnet_cases.fill(m.state_dict()))
     m.eval().to(dev)
+    if args.native_out:
+        return native_section(m, dev, [int(b) for b in args.batches.split(",")], args.reps, args.warmup, args.native_out)
     gf = group_gflop(m)
     res = {"command": "python tools/resnet_time.py", "workload": "ResNet-50 of a 1024 x 2048 image: fp32 NCHW image -> four fp32 NCHW stages; "
            "HIP events around the calls; ResNet.forward in both grades and the two torch forms alternate in one process, the per-group times are a separate section on ResNetPlan's steps", "reps": args.reps, "warmup": args.warmup,
