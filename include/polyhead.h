@@ -770,6 +770,51 @@ int ph_resnet_stem(const void* x, int x_dtype, const uint16_t* Wp, const float* 
 int ph_cl_to_nchw_workgroups(int B, int64_t HW, int C);
 int ph_cl_to_nchw(const uint16_t* X, void* out, int out_dtype, int B, int64_t HW, int C, int prec, void* stream);
 
+/* ---- ResNet backbone in training: data and weight gradients of ph_conv_cl's layers (csrc/ph_resnet_train.hip).  The forward of one
+ * convolution + BatchNorm (norm_eval=True) is z = W' * x + b' with s = gamma / sqrt(var + eps), W' = w s rounded to bf16, b' = beta - mu s.
+ * With dZ the gradient at z (behind the ReLU mask): dW'[n][tap][c] = sum_{b, p} dZ[b][p][n] X[b][stride p + tap - pad][c], db[n] =
+ * sum_{b, p} dZ[b][p][n]; dw = dW' s, dbeta = db, dgamma = (sum_k dW'[n][k] w[n][k] - mu[n] db[n]) / sqrt(var[n] + eps) (the rounding of W'
+ * passed straight through).  Planes are bf16 channels-last [B][H * W][C], accumulation is fp32.  All calls launch only: no allocation,
+ * no synchronisation, no atomics, sums in a fixed order (the same bits from run to run); a bad argument is PH_EINVAL with a message
+ * before any launch, the outputs untouched.  ksize, stride, Cin, Cout, H, W, B are the FORWARD layer's (ph_conv_cl's limits); H, W its
+ * input size, Ho, Wo = floor((H + 2 pad - ksize) / stride) + 1.
+ * ph_conv_cl_bwd_data   : dX[b][q][c] = mask(sum_{tap, n} dZ[b][(q + pad - tap) / stride][n] W'[n][tap][c] + R), over the taps whose
+ *                         quotient is whole on both axes and inside Ho x Wo.  dZ: [B][Ho * Wo][Cout]; Wt: the transposed pack of the
+ *                         same rounded W' (ph_conv_cl_pack_bwd); R (nullable): a bf16 plane added in fp32 before the one rounding --
+ *                         r_stride 1: dX's size; r_stride 2: [B][Hr * Wr][Cin] with Hr = (H - 1) / 2 + 1, read at (qy / 2, qx / 2) where
+ *                         qy and qx are even and zero elsewhere (a stride-2 1x1 layer's gradient spread to the pixels it sampled);
+ *                         M (nullable): dX's size, the output is zero where M <= 0 (-0 included).  A stride-2 layer runs the MFMAs
+ *                         of every tap and zeroes the operands the parity rule excludes.
+ * ph_conv_cl_bwd_weight : dW fp32 [Cout][ksize^2 * Cin] in ph_conv_cl's K order (k = tap * Cin + c) and db fp32 [Cout], from dZ
+ *                         [B][Ho * Wo][Cout] and X [B][H * W][Cin].  The (frame, pixel) axis is cut into 64-pixel chunks per frame and
+ *                         those into nsplit ranges (0: ph_conv_cl_bwd_weight_nsplit, the library's rule); with more than one range the
+ *                         partial sums go to `partial` (ph_conv_cl_bwd_weight_partial_floats floats, 16-byte aligned; nullable for
+ *                         one range) and are added in range order.  nsplit above the number of chunks B ceil(Ho Wo / 64): PH_EINVAL.
+ * ph_resnet_fold_bwd    : (dW', db) and the fp32 w [Cout][Cin][kh][kw], gamma, mean, var -> dw in w's order, dgamma, dbeta (both
+ *                         nullable: a norm whose parameters do not require grad); s and the dgamma sum in float64, outputs fp32.
+ * ph_conv_cl_pack_bwd   : Wt = pack.pack_b32 fragments of WT[Cin][ksize^2 * Cout], WT[c][t * Cout + n] = W'[n][ksize^2 - 1 - t][c]: a
+ *                         permutation of the 16-bit values of ph_conv_cl's Wp.
+ * ph_resnet_pack_bwd    : ph_conv_cl_pack_bwd over a ph_resnet_pack buffer, for the convolutions whose input gradient a backward from
+ *                         layer4 down to layer2.0 needs: layer2 .. layer4 without layer2.0's conv1 and downsample.  The layout is a
+ *                         ph_resnet_layout whose piece PH_RPACK_W(c) is convolution c's Wt (its bytes the forward piece's) and whose
+ *                         other pieces are empty; cfg.mode must be PH_MODE_BF16.
+ * ph_nchw_grad_to_cl    : out[b][p][c] = bf16((add ? add[b][p][c] : 0) + g[b][c][p]), zero where mask[b][p][c] <= 0; g: a stage's fp32
+ *                         NCHW gradient, add / mask (nullable): bf16 planes; C a multiple of 64 in [64, 4096], any HW. */
+int ph_conv_cl_bwd_data_workgroups(int ksize, int stride, int Cin, int Cout, int H, int W, int B);
+int ph_conv_cl_bwd_data(const uint16_t* dZ, const uint16_t* Wt, const uint16_t* R /* nullable */, int r_stride,
+                        const uint16_t* M /* nullable */, uint16_t* dX, int ksize, int stride, int B, int H, int W, int Cin, int Cout,
+                        void* stream);
+int ph_conv_cl_bwd_weight_nsplit(int ksize, int stride, int Cin, int Cout, int H, int W, int B);
+int64_t ph_conv_cl_bwd_weight_partial_floats(int ksize, int stride, int Cin, int Cout, int H, int W, int B, int nsplit);
+int ph_conv_cl_bwd_weight(const uint16_t* dZ, const uint16_t* X, float* dW, float* db, float* partial /* nullable */, int nsplit, int ksize,
+                          int stride, int B, int H, int W, int Cin, int Cout, void* stream);
+int ph_resnet_fold_bwd(const float* dWp, const float* db, const float* w, const float* gamma, const float* mean, const float* var,
+                       double eps, float* dw, float* dgamma /* nullable */, float* dbeta /* nullable */, int ksize, int Cin, int Cout,
+                       void* stream);
+int ph_conv_cl_pack_bwd(const uint16_t* Wp, uint16_t* Wt, int ksize, int Cin, int Cout, void* stream);
+int ph_nchw_grad_to_cl(const float* g, const uint16_t* add /* nullable */, const uint16_t* mask /* nullable */, uint16_t* out, int B,
+                       int64_t HW, int C, void* stream);
+
 /* ---- N1: the quasi-dense embedding tracker as a native object (csrc/ph_tracker.hip; polyphonic/video/qdtrack/trackers/
  * quasi_dense_embed_tracker.py:47-207).  Host bookkeeping in C++ (boxes, labels, ids, ages), embeddings in a device POOL of
  * `capacity` rows of 256 floats inside `device_mem` (ph_tracker_device_bytes; owned by the caller, alive as long as the tracker).
@@ -1336,6 +1381,11 @@ size_t ph_resnet_pack_bytes(const ph_resnet_cfg* cfg);                      /* 0
 int ph_resnet_pack_layout(const ph_resnet_cfg* cfg, ph_resnet_layout* layout);
 /* `params`: host array of ph_resnet_nparams device pointers; `pack`: 256-byte aligned device buffer of ph_resnet_pack_bytes */
 int ph_resnet_pack(const ph_resnet_cfg* cfg, const float* const* params, void* pack, void* stream);
+/* the data gradient's operands from a packed buffer (ph_resnet_pack_bwd in the training block above); `pack_bwd`: 256-byte aligned
+   device buffer of ph_resnet_pack_bwd_bytes (0 on a bad cfg) */
+size_t ph_resnet_pack_bwd_bytes(const ph_resnet_cfg* cfg);
+int ph_resnet_pack_bwd_layout(const ph_resnet_cfg* cfg, ph_resnet_layout* layout);
+int ph_resnet_pack_bwd(const ph_resnet_cfg* cfg, const void* pack, void* pack_bwd, void* stream);
 
 /* ---- plan lifetime.  The workspace holds engine.ResNetPlan's planes (16-bit channels-last): the stem's, two ping-pong block planes,
  * a bottleneck's two inner planes and the downsample plane.  The stages are the caller's.  ZEROING CONTRACT: none.

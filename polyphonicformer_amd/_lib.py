@@ -438,6 +438,14 @@ SIGNATURES = {
     "ph_resnet_stem": (C.c_int, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ph_cl_to_nchw_workgroups": (C.c_int, [_I, _L, _I]),
     "ph_cl_to_nchw": (C.c_int, [_P, _P, _I, _I, _L, _I, _I, _P]),
+    "ph_conv_cl_bwd_data_workgroups": (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),
+    "ph_conv_cl_bwd_data": (C.c_int, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ph_conv_cl_bwd_weight_nsplit": (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),
+    "ph_conv_cl_bwd_weight_partial_floats": (C.c_int64, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "ph_conv_cl_bwd_weight": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ph_resnet_fold_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, _P, _P, _P, _I, _I, _I, _P]),
+    "ph_conv_cl_pack_bwd": (C.c_int, [_P, _P, _I, _I, _I, _P]),
+    "ph_nchw_grad_to_cl": (C.c_int, [_P, _P, _P, _P, _I, _L, _I, _P]),
     "ph_tracker_device_bytes": (C.c_size_t, [_I, _I]),
     "ph_tracker_create": (C.c_void_p, [_P, _P, _Z, _I, _I]),
     "ph_tracker_destroy": (None, [_P]),
@@ -506,6 +514,9 @@ SIGNATURES = {
     "ph_resnet_pack_bytes": (C.c_size_t, [C.POINTER(ResNetCfg)]),
     "ph_resnet_pack_layout": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetLayout)]),
     "ph_resnet_pack": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(C.c_void_p), _P, _P]),
+    "ph_resnet_pack_bwd_bytes": (C.c_size_t, [C.POINTER(ResNetCfg)]),
+    "ph_resnet_pack_bwd_layout": (C.c_int, [C.POINTER(ResNetCfg), C.POINTER(ResNetLayout)]),
+    "ph_resnet_pack_bwd": (C.c_int, [C.POINTER(ResNetCfg), _P, _P, _P]),
     "ph_resnet_plan_workspace_bytes": (C.c_size_t, [C.POINTER(ResNetCfg)]),
     "ph_resnet_plan_create": (C.c_int, [C.POINTER(ResNetCfg), _P, _P, _Z, C.POINTER(C.c_void_p)]),
     "ph_resnet_plan_info": (C.c_int, [_P, C.POINTER(ResNetGeometry)]),

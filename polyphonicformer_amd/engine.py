@@ -2126,3 +2126,234 @@ class NativeResNetPlan(_NativePlan):
         self._image(x)
         _lib.check(_lib.load().ph_resnet_plan_run(self._h_run, C.byref(self.io), _lib.stream_ptr()), "ph_resnet_plan_run")
         return tuple(self.outs[i] for i in self.out_indices)
+
+
+# ---- the backbone in training (csrc/ph_resnet_train.hip): data and weight gradients of the stages behind the frozen ones -----------
+def conv_cl_bwd_data(dz, wt, r, r_stride, m, dx, k, s, B, H, W, cin, cout):
+    """gradient at a convolution's input plane dx [B, H*W, cin] from the gradient dz [B, Ho*Wo, cout] at its output; wt: the transposed
+    pack (ph_conv_cl_pack_bwd); r (bf16 plane or None, r_stride 1: dx's size, 2: the half-resolution plane spread to the even pixels) is
+    added in fp32, the result is zero where the plane m (or None) is <= 0; k, s, H, W, cin, cout: the FORWARD layer's"""
+    _lib.check(_lib.load().ph_conv_cl_bwd_data(_lib.ptr(dz), _lib.ptr(wt), _lib.ptr(r), r_stride, _lib.ptr(m), _lib.ptr(dx), k, s, B, H, W,
+                                               cin, cout, _lib.stream_ptr()), "ph_conv_cl_bwd_data")
+    return dx
+
+
+def conv_cl_bwd_weight(dz, x, dw, db, partial, nsplit, k, s, B, H, W, cin, cout):
+    """dw fp32 [cout, k*k*cin] (k = tap * cin + c) and db fp32 [cout] of a convolution from dz [B, Ho*Wo, cout] and its input plane x
+    [B, H*W, cin]; nsplit 0: the library's rule; partial: fp32 scratch of ph_conv_cl_bwd_weight_partial_floats (None for one range)"""
+    _lib.check(_lib.load().ph_conv_cl_bwd_weight(_lib.ptr(dz), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(partial), nsplit, k, s, B,
+                                                 H, W, cin, cout, _lib.stream_ptr()), "ph_conv_cl_bwd_weight")
+    return dw, db
+
+
+def resnet_fold_bwd(dwp, db, w, gamma, mean, var, eps, dw, dgamma, dbeta, k, cin, cout):
+    """(dW', db) of a folded convolution -> dw (w's shape), dgamma, dbeta (either None: not wanted)"""
+    _lib.check(_lib.load().ph_resnet_fold_bwd(_lib.ptr(dwp), _lib.ptr(db), _lib.ptr(w), _lib.ptr(gamma), _lib.ptr(mean), _lib.ptr(var),
+                                              float(eps), _lib.ptr(dw), _lib.ptr(dgamma), _lib.ptr(dbeta), k, cin, cout, _lib.stream_ptr()),
+               "ph_resnet_fold_bwd")
+
+
+def conv_cl_pack_bwd(wp, wt, k, cin, cout):
+    """a convolution's forward pack wp -> the data gradient's operand wt (int16, the same number of elements)"""
+    _lib.check(_lib.load().ph_conv_cl_pack_bwd(_lib.ptr(wp), _lib.ptr(wt), k, cin, cout, _lib.stream_ptr()), "ph_conv_cl_pack_bwd")
+    return wt
+
+
+def nchw_grad_to_cl(g, add, mask, out, B, HW, C_):
+    """a stage's fp32 NCHW gradient g (+ the bf16 plane add) -> the bf16 channels-last plane out, zero where the plane mask is <= 0"""
+    _lib.check(_lib.load().ph_nchw_grad_to_cl(_lib.ptr(g), _lib.ptr(add), _lib.ptr(mask), _lib.ptr(out), B, HW, C_, _lib.stream_ptr()),
+               "ph_nchw_grad_to_cl")
+    return out
+
+
+def native_resnet_pack_bwd(pack):
+    """the data-gradient operands of a NativeResNetPack (bf16), packed on the device by ph_resnet_pack_bwd -> {convolution index in
+    state_dict order: its int16 view}"""
+    lib, ref = _lib.load(), C.byref(pack.cfg)
+    nbytes = lib.ph_resnet_pack_bwd_bytes(ref)
+    if nbytes == 0:
+        raise _cfg_error("ph_resnet_pack_bwd_bytes")
+    lay = _lib.ResNetLayout()
+    _lib.check(lib.ph_resnet_pack_bwd_layout(ref, C.byref(lay)), "ph_resnet_pack_bwd_layout")
+    blob = torch.empty((nbytes,), dtype=torch.uint8, device=pack.blob.device)
+    with torch.cuda.device(blob.device):
+        _lib.check(lib.ph_resnet_pack_bwd(ref, _lib.ptr(pack.blob), _lib.ptr(blob), _lib.stream_ptr()), "ph_resnet_pack_bwd")
+    return {c: _pack_piece(blob, lay, 2 * c, torch.int16, (-1,)) for c in range(lay.nconvs) if lay.bytes[2 * c]}
+
+
+def resnet_conv_index(blocks):
+    """{(stage, block, name): index of the convolution in state_dict order} (the stem is 0) of a block table"""
+    out, n = {}, 1
+    for si, stage in enumerate(blocks):
+        for j, (_, _, _, has_down) in enumerate(stage):
+            for name in ("conv1", "conv2", "conv3") + (("downsample",) if has_down else ()):
+                out[(si, j, name)] = n
+                n += 1
+    return out
+
+
+def resnet_train_sizes(B, H, W, blocks, first_trained):
+    """the element counts engine.ResNetTrainPlan allocates, from the sizes alone (no device): dict(frozen_io, frozen_inner, frozen_down:
+    the shared planes of the stages in front of `first_trained`; kept: the a1 + a2 + y (+ downsample) planes of every trained block;
+    grad_io / grad_inner / grad_down: the backward's planes; wmax: floats of the largest dW'; layers: per trained convolution
+    (stage, block, name, k, s, cin, cout, h, w) in forward order), all per plan, B included"""
+    h, w = stem_out_size(H), stem_out_size(W)
+    z = dict(stem=B * h * w * 64, frozen_io=0, frozen_inner=0, frozen_down=0, kept=0, grad_io=0, grad_inner=0, grad_down=0, wmax=0, layers=[])
+    for si, stage in enumerate(blocks):
+        for j, (cin, planes, s, has_down) in enumerate(stage):
+            ho, wo = conv_out_size(h, 3, s), conv_out_size(w, 3, s)
+            a1, a2, y = B * h * w * planes, B * ho * wo * planes, B * ho * wo * 4 * planes
+            if si < first_trained:
+                z["frozen_inner"] = max(z["frozen_inner"], a1, a2)
+                z["frozen_io"] = max(z["frozen_io"], y)
+                z["frozen_down"] = max(z["frozen_down"], y if has_down else 0)
+            else:
+                z["kept"] += a1 + a2 + y + (y if has_down else 0)
+                z["grad_inner"] = max(z["grad_inner"], a1, a2)
+                z["grad_io"] = max(z["grad_io"], y, B * h * w * cin if (si, j) != (first_trained, 0) else 0)
+                if has_down and si > first_trained:
+                    z["grad_down"] = max(z["grad_down"], B * ho * wo * cin)
+                for name, k, st, ci, co, hh, ww in (("conv1", 1, 1, cin, planes, h, w), ("conv2", 3, s, planes, planes, h, w),
+                                                    ("conv3", 1, 1, planes, 4 * planes, ho, wo)) + \
+                        ((("downsample", 1, s, cin, 4 * planes, h, w),) if has_down else ()):
+                    z["layers"].append((si, j, name, k, st, ci, co, hh, ww))
+                    z["wmax"] = max(z["wmax"], co * k * k * ci)
+            h, w = ho, wo
+    return z
+
+
+class ResNetTrainPlan:
+    """forward + backward of resnet.ResNet's trained stages for one (B, H, W, block structure), grade bf16: the forward is ResNetPlan's
+    launch sequence with the a1, a2 and y planes (and the downsample plane) of every block of a trained stage kept in planes of their
+    own -- the frozen stages in front share ResNetPlan's ping-pong planes --; the backward runs from the last block down to the first
+    block of stage `first_trained` on gradient planes of its own (two block-gradient planes, two inner ones, one for a downsample's
+    low-resolution input gradient), with one dW' / db buffer and one partial-sum scratch for every weight gradient, and writes the
+    parameter gradients into `self.grads`.  Everything is sized here; `forward` and `backward` issue launches on the current stream and
+    neither allocate nor synchronise.  `nbytes`: the device memory the plan holds."""
+
+    def __init__(self, B, H, W, blocks, out_indices, first_trained, device, stage_dtype=torch.float32):
+        if not 1 <= first_trained <= 3:
+            raise _lib.PolyheadError("ResNetTrainPlan: first_trained must lie in [1, 3] (the stem and layer1 have no backward)")
+        lib, dev = _lib.load(), torch.device(device)
+        self.B, self.H, self.W, self.first_trained, self.device, self.prec = B, H, W, first_trained, dev, _lib.PH_PREC_BF16
+        self.blocks, self.out_indices = [list(s) for s in blocks], tuple(out_indices)
+        self.index = resnet_conv_index(self.blocks)
+        z = self.sizes = resnet_train_sizes(B, H, W, self.blocks, first_trained)
+        self._tensors = []
+
+        def e(n, dtype=torch.int16):
+            t = torch.empty((max(int(n), 8),), dtype=dtype, device=dev)
+            self._tensors.append(t)
+            return t
+        self.p0, self.pa, self.pb = e(z["stem"]), e(z["frozen_io"]), e(z["frozen_io"])
+        self.t1, self.t2, self.pd = e(z["frozen_inner"]), e(z["frozen_inner"]), e(z["frozen_down"])
+        h, w = stem_out_size(H), stem_out_size(W)
+        self.kept, self.stage_shapes, self.geo = {}, [], {}
+        for si, stage in enumerate(self.blocks):
+            for j, (cin, planes, s, has_down) in enumerate(stage):
+                ho, wo = conv_out_size(h, 3, s), conv_out_size(w, 3, s)
+                self.geo[(si, j)] = (h, w, ho, wo)
+                if si >= first_trained:
+                    self.kept[(si, j)] = dict(a1=e(B * h * w * planes), a2=e(B * ho * wo * planes), y=e(B * ho * wo * 4 * planes),
+                                              d=e(B * ho * wo * 4 * planes) if has_down else None)
+                if not has_down and (cin, s) != (4 * planes, 1):
+                    raise _lib.PolyheadError("ResNetTrainPlan: a block without downsample must keep its shape")
+                h, w = ho, wo
+            self.stage_shapes.append((4 * stage[-1][1], h, w))
+        self.outs = {i: e(B * self.stage_shapes[i][0] * self.stage_shapes[i][1] * self.stage_shapes[i][2], stage_dtype)
+                     .view((B,) + self.stage_shapes[i]) for i in self.out_indices}
+        # backward
+        self.ga, self.gb, self.d1, self.d2, self.dt = e(z["grad_io"]), e(z["grad_io"]), e(z["grad_inner"]), e(z["grad_inner"]), e(z["grad_down"])
+        self.dwp, self.dbp = e(z["wmax"], torch.float32), e(2048, torch.float32)
+        self.nsplit, pmax = {}, 0
+        for (si, j, name, k, s, ci, co, hh, ww) in z["layers"]:
+            n = lib.ph_conv_cl_bwd_weight_nsplit(k, s, ci, co, hh, ww, B)
+            if n <= 0:
+                _lib.check(n if n < 0 else _lib.PH_EINVAL, "ph_conv_cl_bwd_weight_nsplit")
+            self.nsplit[(si, j, name)] = n
+            pmax = max(pmax, lib.ph_conv_cl_bwd_weight_partial_floats(k, s, ci, co, hh, ww, B, n))
+        self.partial = e(pmax, torch.float32)
+        self.zero_grads = {si: e(B * c * hh * ww, torch.float32).zero_().view(B, c, hh, ww)
+                           for si, (c, hh, ww) in enumerate(self.stage_shapes) if si >= first_trained}
+        self.grads = {}
+        for (si, j, name, k, s, ci, co, hh, ww) in z["layers"]:
+            self.grads[(si, j, name)] = (e(co * ci * k * k, torch.float32).view(co, ci, k, k), e(co, torch.float32)[:co], e(co, torch.float32)[:co])
+        self.nbytes = sum(t.numel() * t.element_size() for t in self._tensors)
+        self.generation = 0
+
+    def forward(self, x, pk):
+        """x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device; pk: the forward pack (resnet.ResNet._pack's dict).  Returns the
+        NCHW stages of out_indices: the plan's buffers, and the bits of ResNetPlan.run"""
+        B, prec = self.B, self.prec
+        if tuple(x.shape) != (B, 3, self.H, self.W) or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous() \
+                or x.device != self.device:
+            raise _lib.PolyheadError(f"ResNetTrainPlan.forward: x must be a contiguous fp32 / bf16 device tensor of shape {(B, 3, self.H, self.W)}")
+        self.generation += 1
+        resnet_stem(x, pk["stem"][0], pk["stem"][1], self.p0, prec)
+        cur, nxt = self.p0, self.pa
+        self.inputs = {}
+        for si, stage in enumerate(self.blocks):
+            for j, (cin, planes, s, has_down) in enumerate(stage):
+                c, (h, w, ho, wo) = pk["blocks"][si][j], self.geo[(si, j)]
+                kp = self.kept.get((si, j))
+                t1, t2, pd, y = (kp["a1"], kp["a2"], kp["d"], kp["y"]) if kp else (self.t1, self.t2, self.pd, nxt)
+                self.inputs[(si, j)] = cur
+                conv_cl(cur, c["conv1"][0], c["conv1"][1], None, t1, 1, 1, True, B, h, w, cin, planes, prec)
+                conv_cl(t1, c["conv2"][0], c["conv2"][1], None, t2, 3, s, True, B, h, w, planes, planes, prec)
+                idn = cur
+                if has_down:
+                    idn = conv_cl(cur, c["downsample"][0], c["downsample"][1], None, pd, 1, s, False, B, h, w, cin, 4 * planes, prec)
+                conv_cl(t2, c["conv3"][0], c["conv3"][1], idn, y, 1, 1, True, B, ho, wo, planes, 4 * planes, prec)
+                cur, nxt = y, (self.pb if nxt is self.pa else self.pa)
+            if si in self.outs:
+                c_, hh, ww = self.stage_shapes[si]
+                cl_to_nchw(cur, self.outs[si], B, hh * ww, c_, prec)
+        return tuple(self.outs[i] for i in self.out_indices)
+
+    def backward(self, stage_grads, wt, params):
+        """stage_grads: {stage: fp32 contiguous [B, C, h, w] gradient} for the trained stages (a missing one is zeros); wt: the transposed
+        packs by convolution index (native_resnet_pack_bwd); params: {(stage, block, name): (w, gamma, mean, var, eps, want_bn)} fp32
+        device tensors of every trained convolution.  Fills and returns self.grads: {(stage, block, name): (dw, dgamma, dbeta)}"""
+        B, ft = self.B, self.first_trained
+        cur, nxt = self.ga, self.gb
+
+        def ingest(si, add):
+            c_, hh, ww = self.stage_shapes[si]
+            g = stage_grads.get(si)
+            g = self.zero_grads[si] if g is None else g
+            if tuple(g.shape) != (B, c_, hh, ww) or g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device:
+                raise _lib.PolyheadError(f"ResNetTrainPlan.backward: stage {si}'s gradient must be a contiguous fp32 tensor of shape {(B, c_, hh, ww)}")
+            return nchw_grad_to_cl(g, add, self.kept[(si, len(self.blocks[si]) - 1)]["y"], cur, B, hh * ww, c_)
+
+        def wgrad(key, dz, x, k, s, h, w, ci, co):
+            conv_cl_bwd_weight(dz, x, self.dwp, self.dbp, self.partial, self.nsplit[key], k, s, B, h, w, ci, co)
+            wp, gamma, mean, var, eps, want_bn = params[key]
+            dw, dg, dbt = self.grads[key]
+            resnet_fold_bwd(self.dwp, self.dbp, wp, gamma, mean, var, eps, dw, dg if want_bn else None, dbt if want_bn else None, k, ci, co)
+
+        top = len(self.blocks) - 1
+        ingest(top, None)
+        for si in range(top, ft - 1, -1):
+            for j in range(len(self.blocks[si]) - 1, -1, -1):
+                cin, planes, s, has_down = self.blocks[si][j]
+                (h, w, ho, wo), kp, x, ix = self.geo[(si, j)], self.kept[(si, j)], self.inputs[(si, j)], self.index
+                need_dx = (si, j) != (ft, 0)
+                g = cur
+                conv_cl_bwd_data(g, wt[ix[(si, j, "conv3")]], None, 1, kp["a2"], self.d2, 1, 1, B, ho, wo, planes, 4 * planes)
+                wgrad((si, j, "conv3"), g, kp["a2"], 1, 1, ho, wo, planes, 4 * planes)
+                if has_down:
+                    wgrad((si, j, "downsample"), g, x, 1, s, h, w, cin, 4 * planes)
+                    if need_dx:                                   # the 1x1 layer on the pixels it sampled: a stride-1 layer at ho x wo
+                        conv_cl_bwd_data(g, wt[ix[(si, j, "downsample")]], None, 1, None, self.dt, 1, 1, B, ho, wo, cin, 4 * planes)
+                conv_cl_bwd_data(self.d2, wt[ix[(si, j, "conv2")]], None, 1, kp["a1"], self.d1, 3, s, B, h, w, planes, planes)
+                wgrad((si, j, "conv2"), self.d2, kp["a1"], 3, s, h, w, planes, planes)
+                wgrad((si, j, "conv1"), self.d1, x, 1, 1, h, w, cin, planes)
+                if not need_dx:
+                    continue
+                if has_down:                                      # the stage's first block: dL/dx unmasked, then the stage in front
+                    conv_cl_bwd_data(self.d1, wt[ix[(si, j, "conv1")]], self.dt, s, None, nxt, 1, 1, B, h, w, cin, planes)
+                    ingest(si - 1, nxt)
+                else:
+                    conv_cl_bwd_data(self.d1, wt[ix[(si, j, "conv1")]], g, 1, x, nxt, 1, 1, B, h, w, cin, planes)
+                    cur, nxt = nxt, cur
+        return self.grads

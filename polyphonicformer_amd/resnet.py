@@ -9,8 +9,14 @@ Inference (`forward` on the device with no gradient asked for) runs in libpolyhe
 into its convolution in float64 (`fold_bn`), activations are one 16-bit channels-last plane ('bf16', the default, or 'fp16'), and the
 stages come back as NCHW tensors (fp32 by default; `set_stage_dtype` for the 16-bit hand-off `ph_fpn_lateral` also takes).
 `use_native_plan(True)` moves the fold, the packing and the launch sequence into the library as well (ph_resnet_pack,
-engine.NativeResNetPlan: one native call per forward, the same bits).  `_forward_torch` is the same arithmetic in torch ops: CPU tensors, and whenever grad is enabled and a parameter or the input requires
-grad -- training the backbone is torch's job, as with fpn.FPN's default.
+engine.NativeResNetPlan: one native call per forward, the same bits).  `_forward_torch` is the same arithmetic in torch ops: CPU tensors, and by default whenever grad is enabled and a parameter or the
+input requires grad, as with fpn.FPN's default.
+
+Training on the device is opt-in (`train_on_device()`): the training-mode `forward` then runs `train.resnet_forward_train` -- the
+inference launch sequence with every activation kept, and a backward of data and weight gradients (csrc/ph_resnet_train.hip) from
+layer4 down to the first stage behind the frozen ones, through the BatchNorm fold back to `conv.weight`, `bn.weight` and `bn.bias`.
+Its scope is the shipped configuration: `frozen_stages >= 1`, `norm_eval=True`, grade 'bf16', an image that does not require grad;
+anything else raises NotImplementedError naming the argument, never a fall-back to torch.
 
 Keywords taken for the signature's sake only: `with_cp` (activation checkpointing trades memory for time and changes no value; it is
 stored and not applied), `stage_with_dcn` (stored; without `dcn` it selects nothing), `pretrained` and `init_cfg` (loading a checkpoint
@@ -135,6 +141,7 @@ class ResNet(nn.Module):
         self.precision, self.stage_dtype = "bf16", torch.float32
         self._packs, self._plans = {}, {}
         self._native, self._native_packs, self._native_plans = False, {}, {}
+        self.device_training = False
         self._freeze_stages()
 
     def init_weights(self):
@@ -170,6 +177,13 @@ class ResNet(nn.Module):
         """opt in: `forward` on the device folds and packs with ph_resnet_pack and runs engine.NativeResNetPlan -- one native call per
         forward, the same launches and the same bits as the default path"""
         self._native = bool(flag)
+        return self
+
+    def train_on_device(self, flag=True):
+        """opt in: `forward` with grad enabled and a parameter that requires grad runs `train.resnet_forward_train` (the library's
+        forward with every activation kept, and its backward) instead of torch ops; off by default.  Out of its scope --
+        frozen_stages < 1, norm_eval=False, grade 'fp16', an image that requires grad -- it raises NotImplementedError"""
+        self.device_training = bool(flag)
         return self
 
     # ---- resnet.py:613-658
@@ -276,7 +290,12 @@ class ResNet(nn.Module):
         return plan, pk, x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.contiguous().float()
 
     def forward(self, x):
-        if not x.is_cuda or (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if self.device_training:
+                from .train import resnet_forward_train
+                return resnet_forward_train(self, x)
+            return self._forward_torch(x)
+        if not x.is_cuda:
             return self._forward_torch(x)
         plan, pk, xin = self._native_plan_of(x) if self._native else self._plan_of(x)
         with torch.cuda.device(x.device):

@@ -706,6 +706,101 @@ def fpn_forward_train(fpn, stages):
     return tuple(_Conv3x3Bias.apply(lat[i], m.conv.weight, m.conv.bias) for i, m in enumerate(fpn.fpn_convs))
 
 
+# ---- the backbone in training: the image -> the stages, the stage gradients -> the gradients of the trained parameters -------------
+def _resnet_train_state(backbone, img):
+    """the refusals of the device training path, then (plan, forward pack, transposed packs, image as the plan takes it)"""
+    def no(arg, why):
+        raise NotImplementedError(f"resnet_forward_train: {arg}: the device training path covers the shipped backbone ({why})")
+    if backbone.frozen_stages < 1:
+        no("frozen_stages", "frozen_stages >= 1: the stem and layer1 have no backward")
+    if not backbone.norm_eval:
+        no("norm_eval", "norm_eval=True: BatchNorm in training mode is not built")
+    if backbone.precision != "bf16":
+        no("precision", "grade 'bf16': fp16 would need loss scaling, which does not exist here")
+    if img.requires_grad:
+        no("img", "an input image that requires grad: no gradient is returned for the image")
+    if any(m.training for m in backbone.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
+        no("norm_eval", "every BatchNorm in eval mode (ResNet.train() leaves them there)")
+    E._require_gpu(img, "img")
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise _lib.PolyheadError("resnet_forward_train: img must be [B, 3, H, W]")
+    eps = {m.eps for m in backbone.modules() if isinstance(m, torch.nn.BatchNorm2d)}
+    if len(eps) != 1:
+        raise _lib.PolyheadError("resnet_forward_train: ph_resnet_cfg carries one BatchNorm eps; this module's norms have several")
+    dev, (B, _, H, W) = img.device, img.shape
+    st = backbone.__dict__.setdefault("_train_state", dict(packs={}, plans={}))
+    with torch.cuda.device(dev):
+        key = (str(dev), backbone._versions())
+        if key not in st["packs"]:
+            st["packs"].clear()
+            cfg = E.native_resnet_cfg(B, H, W, backbone.depth, "bf16", torch.float32, torch.float32, (0, 1, 2, 3), eps.pop())
+            pack = E.native_resnet_pack(backbone, cfg, dev)
+            st["packs"][key] = (pack, E.native_resnet_pack_bwd(pack))
+        pack, wt = st["packs"][key]
+        pkey = (B, H, W, str(dev), tuple(backbone.out_indices), backbone.frozen_stages, tuple(map(tuple, backbone.block_table())))
+        plan = st["plans"].get(pkey)
+        if plan is None:
+            if len(st["plans"]) >= 2:                    # a training plan keeps every activation of its size
+                st["plans"].clear()
+            plan = st["plans"][pkey] = E.ResNetTrainPlan(B, H, W, backbone.block_table(), backbone.out_indices, backbone.frozen_stages, dev)
+    return plan, pack.pk, wt, img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.contiguous().float()
+
+
+def _resnet_trained(backbone):
+    """[(key, conv, bn)] of the trained convolutions in the plan's order, key = (stage, block, name)"""
+    out = []
+    for si in range(backbone.frozen_stages, 4):
+        for j, m in enumerate(getattr(backbone, backbone.res_layers[si])):
+            out += [((si, j, "conv1"), m.conv1, m.bn1), ((si, j, "conv2"), m.conv2, m.bn2), ((si, j, "conv3"), m.conv3, m.bn3)]
+            if m.downsample is not None:
+                out.append(((si, j, "downsample"), m.downsample[0], m.downsample[1]))
+    return out
+
+
+class _ResNetStages(torch.autograd.Function):
+    """resnet.ResNet's forward on engine.ResNetTrainPlan; backward: the stage gradients through the plan's backward.  The parameters
+    are inputs for the graph's sake only (the forward reads the packs): per trained convolution its weight, its norm's weight and bias"""
+
+    @staticmethod
+    def forward(ctx, backbone, img, *params):
+        plan, pk, wt, xin = _resnet_train_state(backbone, img)
+        with torch.cuda.device(img.device):
+            outs = plan.forward(xin, pk)
+        ctx.backbone, ctx.plan, ctx.wt, ctx.generation = backbone, plan, wt, plan.generation
+        return tuple(o.clone() for o in outs)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        backbone, plan = ctx.backbone, ctx.plan
+        if plan.generation != ctx.generation:
+            raise _lib.PolyheadError("resnet_forward_train: the plan ran another forward before this backward; its activations are gone")
+        grads = {si: g.float().contiguous() for si, g in zip(backbone.out_indices, gs) if g is not None and si >= plan.first_trained}
+        trained = _resnet_trained(backbone)
+        f32 = lambda t: _param32(t.detach(), "backbone parameter")
+        params = {key: (f32(c.weight), f32(bn.weight), f32(bn.running_mean), f32(bn.running_var), bn.eps,
+                        bn.weight.requires_grad or bn.bias.requires_grad) for key, c, bn in trained}
+        with torch.cuda.device(plan.device):
+            out = plan.backward(grads, ctx.wt, params)
+        res = []
+        for i, (key, c, bn) in enumerate(trained):
+            dw, dg, db = out[key]
+            need = ctx.needs_input_grad[2 + 3 * i:5 + 3 * i]
+            res += [dw.clone() if need[0] else None, dg.clone() if need[1] else None, db.clone() if need[2] else None]
+        return (None, None) + tuple(res)
+
+
+def resnet_forward_train(backbone, img):
+    """resnet.ResNet.forward (mmdet/models/backbones/resnet.py:631-646) for training the stages behind the frozen ones on the device:
+    the forward is the inference path's launch sequence with every activation kept (engine.ResNetTrainPlan; the folded weights are
+    re-packed on the device whenever a parameter's or a running statistic's version changed), the backward takes the gradients of the
+    stages -- a missing one is zeros, those of the frozen stages are ignored -- to the gradients of every trained conv.weight,
+    bn.weight and bn.bias (csrc/ph_resnet_train.hip).  Scope: depth 50 / 101 / 152, frozen_stages >= 1, norm_eval=True, grade bf16, an
+    image that does not require grad; anything else raises NotImplementedError naming the argument.  Returns the stages of
+    out_indices as fp32 NCHW."""
+    params = [p for _, c, bn in _resnet_trained(backbone) for p in (c.weight, bn.weight, bn.bias)]
+    return _ResNetStages.apply(backbone, img, *params)
+
+
 # ---- the video side: RoI features of the key frame and the track head's losses -------------------------------------------------
 class _RoIExtract(torch.autograd.Function):
     """SingleRoIExtractor + RoIAlign(7, sampling_ratio 2, aligned) of one image (track_head.roi_extract, fp32 output); backward:
@@ -1136,6 +1231,8 @@ class _StepBase:
         out, seen = [], set()
         for m in self._trained:
             for n, p in _lib.named_params(m).items():
+                if m is getattr(self, "backbone", None) and not p.requires_grad:        # its frozen stages: no gradient, no bucket
+                    continue
                 if id(p) not in seen and not (m is self.rpn and n.startswith("localization_fpn.")):
                     seen.add(id(p))
                     out.append(p)
@@ -1216,13 +1313,19 @@ class VideoTrainStep(_StepBase):
     fpn (a `fpn.FPN`, optional): the step starts one module earlier -- x / x_ref are the BACKBONE STAGES of the two frames, the key
     frame's go through `fpn_forward_train`, the reference frame's through the FPN's eval plan under no_grad, the FPN's 16 parameters
     are the first of `parameters()`, and the returned gradients are those of the key frame's stages (what the backbone's backward
-    takes).  Without it nothing changes."""
+    takes).  Without it nothing changes.
+    backbone (a `resnet.ResNet`, optional, needs `fpn`): the step starts at the images -- x / x_ref are the image tensors [B, 3, H, W] of
+    the two frames, the key frames go through `resnet_forward_train` (its scope: frozen_stages >= 1, norm_eval=True, grade bf16), the
+    reference frames through the backbone's inference plan under no_grad, the backbone's trained parameters are the first of
+    `parameters()`, and no input gradient is returned.  Without it nothing changes."""
 
     def __init__(self, neck, rpn_head, roi_head, track_head, track_train_cfg, bucket_bytes=32 << 20, group=None, device_assign=False,
-                 strides=(4, 8, 16, 32), finest_scale=56, fpn=None):
+                 strides=(4, 8, 16, 32), finest_scale=56, fpn=None, backbone=None):
         from .assigner import build_assigner
-        self.neck, self.track_head, self.fpn = neck, track_head, fpn
-        self._trained = (neck, rpn_head, roi_head, track_head) if fpn is None else (fpn, neck, rpn_head, roi_head, track_head)
+        if backbone is not None and fpn is None:
+            raise ValueError("VideoTrainStep: backbone needs fpn (the backbone's stages feed the FPN)")
+        self.neck, self.track_head, self.fpn, self.backbone = neck, track_head, fpn, backbone
+        self._trained = tuple(m for m in (backbone, fpn) if m is not None) + (neck, rpn_head, roi_head, track_head)
         self.strides, self.finest_scale = tuple(strides), finest_scale
         if rpn_head.localization_fpn is not None and rpn_head.localization_fpn is not neck:
             raise ValueError("VideoTrainStep: rpn_head.localization_fpn must be None or the step's neck")
@@ -1235,14 +1338,17 @@ class VideoTrainStep(_StepBase):
     def _reference_frame(self, x_ref, ref_metas, levels_out=None):
         """:186-191, 207-243 for the reference frame: (FPN,) neck, rpn head and roi head in eval mode under no_grad, at the grade the
         module API runs; every module's `training` flag is put back.  With an FPN x_ref are the frame's backbone stages and
-        `levels_out` (a list) receives its FPN levels: the eval plan's buffers, valid until that plan runs again"""
-        tops = [t for t in (self.fpn, self.neck, self.rpn, self.roi) if t is not None]
+        `levels_out` (a list) receives its FPN levels: the eval plan's buffers, valid until that plan runs again; with a backbone
+        x_ref is the frames' image tensor"""
+        tops = [t for t in (self.backbone, self.fpn, self.neck, self.rpn, self.roi) if t is not None]
         mods = [m for top in tops for m in top.modules()]
         flags = [m.training for m in mods]
         try:
             for top in tops:
                 top.eval()
             with torch.no_grad():
+                if self.backbone is not None:
+                    x_ref = list(self.backbone(x_ref))                              # the inference plan: no gradient is asked for
                 if self.fpn is not None:
                     x_ref = list(self.fpn(x_ref))
                     if levels_out is not None:
@@ -1259,7 +1365,8 @@ class VideoTrainStep(_StepBase):
         """x / x_ref: the FPN levels of the key and the reference frames; the ground truth as the reference has it at :185 (things and
         stuff split, at the assign resolution).  -> (losses: the 24 image losses + loss_track + loss_track_aux, objective, gradients of
         the key frame's FPN levels: neck path + RoIAlign path).  The reference frame's levels get no gradient.  With the step's `fpn`:
-        x / x_ref are the backbone stages and the gradients returned are those of the key frame's stages."""
+        x / x_ref are the backbone stages and the gradients returned are those of the key frame's stages; with its `backbone` they
+        are the image tensors and the list of gradients is empty."""
         return self._forward_backward(x, x_ref, img_metas, (gt_masks, gt_labels, gt_sem_seg, gt_sem_cls, gt_depth, gt_instance_ids),
                                       (ref_gt_masks, ref_gt_labels, ref_gt_instance_ids), pad_hw, backward, ref_img_metas)
 
@@ -1281,13 +1388,16 @@ class VideoTrainStep(_StepBase):
         lists, gt_instance_ids = key[:5], key[5]
         ref_gt_masks, ref_gt_labels, ref_gt_instance_ids = ref
         what = "the FPN levels" if self.fpn is None else "the backbone stages"
-        x = self._leaves(x, what)
-        x_ref = self._leaves(x_ref, what, requires_grad=False)
+        if self.backbone is not None:
+            img, x, x_ref = _gpu32(x, "the key frames' images"), [], _gpu32(x_ref, "the reference frames' images")
+        else:
+            x = self._leaves(x, what)
+            x_ref = self._leaves(x_ref, what, requires_grad=False)
 
         def forward():
             lv, lv_ref = x, x_ref
             if self.fpn is not None:
-                lv, lv_ref = fpn_forward_train(self.fpn, x), []
+                lv, lv_ref = fpn_forward_train(self.fpn, x if self.backbone is None else resnet_forward_train(self.backbone, img)), []
             feats = neck_forward_train(self.neck, lv)                                                  # :185
             losses, last, cache = _heads_forward_train(self.rpn, self.roi, feats, img_metas, *lists, self.device_assign, gt_cache=gt_cache)
             ref_last = self._reference_frame(x_ref, ref_img_metas if ref_img_metas is not None else img_metas,

@@ -16,10 +16,18 @@ the device path and the two torch forms take turns inside every repetition; the 
     pack; and the weight load from a resident fp32 state_dict, wall time to the finished pack: `ph_resnet_pack` (engine.
     native_resnet_pack) against `ResNet._pack` (host float64).
 
+  * with --train-out, INSTEAD of the sections above: forward + backward of the trained stages (frozen_stages=1, norm_eval=True) at
+    B = 2 and B = 4 (--train-batches), gradients of randn on all four stages.  First, device path only, the weight-gradient kernel
+    alone per layer group (every ph_conv_cl_bwd_weight launch of layer2 / layer3 / layer4 on the plan's own planes, the fold backward
+    not included) with its TFLOP/s from 2 K Cout per output pixel, and the data gradient likewise (plus its three stride-2 3x3
+    layers by themselves); then three sides alternating in one process: the device path
+    (`train_on_device()`: module forward, `torch.autograd.backward`), torch fp32 NCHW, torch bf16 autocast on channels-last.
+
 The result is written to --out after every section, so a run that is cut short leaves what it measured.
 
     python tools/resnet_time.py --out profiles/resnet/time.json
     python tools/resnet_time.py --native-out profiles/resnet/native_time.json
+    python tools/resnet_time.py --train-out profiles/resnet/train_time.json
 """
 import argparse
 import copy
@@ -121,6 +129,106 @@ def native_section(m, dev, batches, reps, warmup, out):
         flush()
 
 
+def train_section(dev, batches, reps, warmup, out):
+    """forward + backward of the trained stages: the weight-gradient kernel per layer group, then the three sides; written to `out`
+    after every part"""
+    from polyphonicformer_amd import train as T
+    res = {"command": "python tools/resnet_time.py --train-out OUT", "workload": "ResNet-50 (frozen_stages=1, norm_eval=True) of 1024 x 2048 "
+           "fp32 images, forward + backward from randn gradients on the four fp32 NCHW stages to the 126 trained parameters' gradients; HIP "
+           "events around forward + backward, the three sides alternate in one process; wgrad_groups / dgrad_groups: every "
+           "ph_conv_cl_bwd_weight / ph_conv_cl_bwd_data launch of a layer group alone (2 K Cout per output pixel; the data gradient counts "
+           "what it issues, stride2_conv2 = the three stride-2 3x3 layers, which issue 4 x their useful work)", "reps": reps, "warmup": warmup}
+
+    def flush():
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+
+    def fresh():
+        m = ResNet(50, frozen_stages=1, norm_eval=True)
+        m.load_state_dict(resnet_cases.fill(m.state_dict()))
+        return m.to(dev).train()
+    m_dev, m_f32, m_cl = fresh().train_on_device(), fresh(), fresh().to(memory_format=torch.channels_last)
+
+    def step(m, x, ups, autocast=False):
+        for p in m.parameters():
+            p.grad = None
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            outs = m(x)
+        pairs = [(o, u.to(o.dtype)) for o, u in zip(outs, ups) if o.requires_grad]           # torch: layer1's stage is frozen
+        torch.autograd.backward([o for o, _ in pairs], [u for _, u in pairs])
+
+    for B in batches:
+        x = resnet_cases.inputs(1, (B, 3, H, W))[0].to(dev)
+        xcl = x.contiguous(memory_format=torch.channels_last)
+        with torch.no_grad():
+            shapes = [tuple(o.shape) for o in m_dev.eval()(x)]
+        m_dev.train()
+        g = torch.Generator().manual_seed(11)
+        ups = [torch.randn(s, generator=g).to(dev) for s in shapes]
+        step(m_dev, x, ups)                                        # builds the packs and the plan
+        plan = T._resnet_train_state(m_dev, x)[0]
+        res[f"B{B}"] = {"plan_bytes": plan.nbytes}
+        groups, gflop = {}, {}
+        for si in (1, 2, 3):
+            calls = []
+            for (s_, j, name, k, st, ci, co, hh, ww) in plan.sizes["layers"]:
+                if s_ != si:
+                    continue
+                kp = plan.kept[(s_, j)]
+                dz = {"conv1": kp["a1"], "conv2": kp["a2"], "conv3": kp["y"], "downsample": kp["y"]}[name]     # a plane of dZ's size
+                xin = {"conv1": plan.inputs[(s_, j)], "conv2": kp["a1"], "conv3": kp["a2"], "downsample": plan.inputs[(s_, j)]}[name]
+                calls.append((dz, xin, plan.nsplit[(s_, j, name)], k, st, hh, ww, ci, co))
+                gflop[si] = gflop.get(si, 0.0) + 2.0 * k * k * ci * co * E.conv_out_size(hh, k, st) * E.conv_out_size(ww, k, st) * B / 1e9
+            groups[f"layer{si + 1}"] = (lambda cs=calls: [E.conv_cl_bwd_weight(dz, xin, plan.dwp, plan.dbp, plan.partial, ns, k, st, B, hh, ww,
+                                                                               ci, co) for dz, xin, ns, k, st, hh, ww, ci, co in cs])
+        t = alternate(groups, reps, warmup)
+        for si in (1, 2, 3):
+            t[f"layer{si + 1}"]["tflops"] = round(gflop[si] / t[f"layer{si + 1}"]["ms"], 1)
+            t[f"layer{si + 1}"]["gflop"] = round(gflop[si], 1)
+        res[f"B{B}"]["wgrad_groups"] = t
+        flush()
+        # the data gradient alone: every ph_conv_cl_bwd_data launch of a layer group with the plan's own operands, and the three
+        # stride-2 3x3 layers by themselves (their MFMAs run all nine taps: issued = 4 x useful)
+        wt, ix = T._resnet_train_state(m_dev, x)[2], plan.index
+        dgroups, dgf, s2_calls, s2_gf = {}, {}, [], 0.0
+        for si in (1, 2, 3):
+            calls = []
+            for j, (cin, planes, st, has_down) in enumerate(plan.blocks[si]):
+                (h, w, ho, wo), kp, xin = plan.geo[(si, j)], plan.kept[(si, j)], plan.inputs[(si, j)]
+                calls.append((kp["y"], wt[ix[(si, j, "conv3")]], None, 1, kp["a2"], plan.d2, 1, 1, ho, wo, planes, 4 * planes))
+                c2 = (kp["a2"], wt[ix[(si, j, "conv2")]], None, 1, kp["a1"], plan.d1, 3, st, h, w, planes, planes)
+                calls.append(c2)
+                if st == 2:
+                    s2_calls.append(c2)
+                    s2_gf += 2.0 * 9 * planes * planes * h * w * B / 1e9
+                if (si, j) == (1, 0):
+                    continue                                       # layer2.0: nothing trained in front of it
+                if has_down:
+                    calls.append((kp["y"], wt[ix[(si, j, "downsample")]], None, 1, None, plan.dt, 1, 1, ho, wo, cin, 4 * planes))
+                    calls.append((kp["a1"], wt[ix[(si, j, "conv1")]], plan.dt, st, None, plan.ga, 1, 1, h, w, cin, planes))
+                else:
+                    calls.append((kp["a1"], wt[ix[(si, j, "conv1")]], kp["y"], 1, xin, plan.ga, 1, 1, h, w, cin, planes))
+            dgf[si] = sum(2.0 * k * k * co * ci * hh * ww * B / 1e9 for (_, _, _, _, _, _, k, _, hh, ww, ci, co) in calls)
+            dgroups[f"layer{si + 1}"] = calls
+        dgroups["stride2_conv2"] = s2_calls
+        run_d = lambda cs: [E.conv_cl_bwd_data(dz, w_, r, rs, mk, o, k, st, B, hh, ww, ci, co) for dz, w_, r, rs, mk, o, k, st, hh, ww, ci, co in cs]
+        t = alternate({name: (lambda cs=cs: run_d(cs)) for name, cs in dgroups.items()}, reps, warmup)
+        for si in (1, 2, 3):
+            t[f"layer{si + 1}"]["gflop_issued"] = round(dgf[si], 1)
+            t[f"layer{si + 1}"]["tflops_issued"] = round(dgf[si] / t[f"layer{si + 1}"]["ms"], 1)
+        t["stride2_conv2"]["gflop_issued"], t["stride2_conv2"]["gflop_useful"] = round(s2_gf, 1), round(s2_gf / 4, 1)
+        res[f"B{B}"]["dgrad_groups"] = t
+        flush()
+        runs = {"device_bf16": lambda: step(m_dev, x, ups), "torch_fp32_nchw": lambda: step(m_f32, x, ups),
+                "torch_bf16_autocast_channels_last": lambda: step(m_cl, xcl, ups, autocast=True)}
+        res[f"B{B}"].update(alternate(runs, reps, warmup))
+        flush()
+        m_dev.__dict__.pop("_train_state", None)
+        torch.cuda.empty_cache()
+
+
 def group_gflop(m):
     """GFLOP per frame of the stem and of each layer: 2 K Cout per output pixel"""
     h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -144,11 +252,15 @@ def main():
     ap.add_argument("--batches", default="1,4")
     ap.add_argument("--no-torch", action="store_true", help="skip the torch forms")
     ap.add_argument("--native-out", default=None, help="measure the native plan beside the Python plan, and the two weight loads, instead")
+    ap.add_argument("--train-out", default=None, help="measure forward + backward of the trained stages instead")
+    ap.add_argument("--train-batches", default="2,4")
     ap.add_argument("--fpn-neck-ms", type=float, default=1.07, help="the FPN + neck's time per frame to set the backbone beside")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("resnet_time.py measures on a GPU; none is visible")
     dev = torch.device("cuda:0")
+    if args.train_out:
+        return train_section(dev, [int(b) for b in args.train_batches.split(",")], args.reps, args.warmup, args.train_out)
     m = ResNet(50, frozen_stages=1, norm_eval=True)
     m.load_state_dict(resnet_cases.fill(m.state_dict()))
     m.eval().to(dev)
