@@ -711,7 +711,7 @@ int ph_gn_apply(const float* y, const float* stats /* nullable */, const float* 
 
 /* ---- FPN: the step before the neck (mmdet/models/necks/fpn.py:151-203 as configs/_base_/models/polyphonic_former.py:22-29 builds
  * it: four 1x1 lateral convs K -> 256 and four 3x3 output convs 256 -> 256, each with bias, no norm, no activation, nearest top-down
- * add).  Both calls launch only: no allocation, no synchronisation, no environment variable.
+ * add).  Every call launches only: no allocation, no synchronisation, no environment variable.
  * ph_fpn_lateral : one level's lateral conv + top-down add (fpn.py:157-173).  x: the backbone stage, NCHW-contiguous [B][K][H * W] of
  *                  x_dtype PH_OUT_F32 / PH_OUT_BF16 / PH_OUT_F16, K a multiple of 64 in [64, 4096]; every element is read once and
  *                  converted through fp32 to the grade's 16-bit format inside the kernel.  Wp: pack.pack_b32 fragments of W[256][K],
@@ -723,11 +723,20 @@ int ph_gn_apply(const float* y, const float* stats /* nullable */, const float* 
  *                  out: 16-bit NHWC planes [P][B][H * W][256], what ph_conv_nhwc reads.  prec PH_PREC_BF16 / PH_PREC_F16: one plane;
  *                  PH_PREC_SPLIT: hi + lo planes of both operands, hi.hi + hi.lo + lo.hi.  fp32 accumulation.  A frame's result
  *                  does not depend on B.  A bad argument leaves `out` untouched.
+ * ph_fpn_lateral_cl : ph_fpn_lateral for a stage that is a channels-last 16-bit plane X [B][H * W][K] of grade x_prec (PH_PREC_BF16 /
+ *                  PH_PREC_F16: the backbone's plane as ph_conv_cl writes it), 16-byte aligned; every other argument, the K range and
+ *                  the size rule are ph_fpn_lateral's.  prec PH_PREC_BF16 / PH_PREC_F16; with x_prec != prec each value goes through
+ *                  fp32 to the grade while it is staged.  The same MFMA, B fragments, accumulation order and epilogue: the bits of
+ *                  ph_fpn_lateral on ph_cl_to_nchw's tensor of X, without that tensor crossing memory.  PH_PREC_SPLIT is
+ *                  PH_EUNSUPPORTED before any launch (the hi + lo grade keeps the NCHW path).
  * ph_fpn_output  : the tail of an output conv (fpn.py:177-179): y = ph_conv_nhwc's fp32 NHWC [B][HW][256] result (ksize 3, stride 1,
  *                  on the lateral planes) + bias[256] -> fp32 NCHW [B][256][HW], the level as the module returns it. */
 int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
                    const uint16_t* coarse /* nullable */, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
                    void* stream);
+int ph_fpn_lateral_cl(const uint16_t* X, int x_prec, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
+                      const uint16_t* coarse /* nullable */, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
+                      void* stream);
 int ph_fpn_output(const float* y, const float* bias, float* out, int B, int64_t HW, void* stream);
 /* ph_fpn_output_planes : the same tail, handing the level to the neck directly: y (as above, read once) + bias -> the 16-bit planes
  *                  the neck's first convolution of that level reads, and -- out_f32 given -- the fp32 NCHW level as well (ph_fpn_output's

@@ -430,6 +430,7 @@ SIGNATURES = {
     "ph_neck_out_convs": (C.c_int, [_P, _I, _P, _P, _I, C.c_float, _P, _P, _P, _P, _P, _P, _P, _Z, _I, _L, _I, _P]),
     "ph_gn_apply": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     "ph_fpn_lateral": (C.c_int, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
+    "ph_fpn_lateral_cl": (C.c_int, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P]),
     "ph_fpn_output": (C.c_int, [_P, _P, _P, _I, _L, _P]),
     "ph_fpn_output_planes": (C.c_int, [_P, _P, _P, _P, _P, _I, _L, _I, _P]),
     "ph_conv_cl_workgroups": (C.c_int, [_I, _I, _I, _I, _I, _I, _I]),

@@ -5,6 +5,7 @@
 //   k_fpn_lateral : one level's lateral.  out[b][px][n] = round16(sum_k W[n][k] x[b][k][px] + bias[n] + coarse[b][nearest(px)][n])
 //                   straight from the backbone's NCHW map (fp32 / bf16 / fp16; every element crosses HBM once, converted through
 //                   fp32 to the grade's 16-bit format while it is staged) to the channels-last 16-bit planes the 3x3 kernel reads.
+//   k_fpn_lateral_cl : the same lateral from the backbone's channels-last 16-bit plane, which then never becomes an NCHW tensor.
 //   k_fpn_output  : fp32 NHWC conv result + bias -> fp32 NCHW, the level the module hands out.
 //
 // GEMM core of the lateral (the recipe of ph_khead.hip with the operands swapped): M = 64-pixel tile, N = 256 output channels, K in
@@ -89,6 +90,63 @@ __device__ __forceinline__ void fl_store(const float (&v)[8][4], uint16_t* lds, 
     }
 }
 
+// the epilogue of both lateral kernels, called by all 512 threads behind the last chunk: accumulators + bias as fp32 [64 px][256]
+// through LDS, then whole 16-byte channel runs -- the coarse level's value in, one rounding, the output planes out
+template <int PA, int E>
+__device__ __forceinline__ void fl_epilogue(const FLArgs& a, const f32x16_t (&acc)[2], uint16_t* lds, int b, int64_t HW, int64_t px0,
+                                            int tid, int lane, int wave, int g) {
+    // D layout: row = pixel (r & 3) + 8 (r >> 2) + 4 g of sub-tile ct, column = channel 32 wave + (lane & 31)
+    __syncthreads();                                     // the last chunk's fragment reads are done: the LDS is free
+    float* tf = (float*)lds;
+    {
+        const int ch = wave * 32 + (lane & 31);
+        const float bv = a.bias[ch];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int px = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+                tf[px * FL_EP + ch] = acc[ct][r] + bv;
+            }
+    }
+    __syncthreads();
+    const int64_t oplane = (int64_t)a.B * HW * 256;
+    const int64_t HWc = (int64_t)a.Hc * a.Wc, cplane = (int64_t)a.B * HWc * 256;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int idx = tid + it * FL_THREADS;
+        const int pl = idx >> 5, c8 = (idx & 31) * 8;
+        const int64_t px = px0 + pl;
+        if (px >= HW) continue;
+        const float4 s0 = *(const float4*)(tf + pl * FL_EP + c8), s1 = *(const float4*)(tf + pl * FL_EP + c8 + 4);
+        float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+        if (a.coarse) {
+            // F.interpolate(mode='nearest', size=(H, W)) for H in {2 Hc, 2 Hc - 1}: source index y Hc / H in integers (host-checked)
+            const int y = (int)(px / a.W), x = (int)(px - (int64_t)y * a.W);
+            int cy = y * a.Hc / a.H, cx = x * a.Wc / a.W;
+            if (cy > a.Hc - 1) cy = a.Hc - 1;
+            if (cx > a.Wc - 1) cx = a.Wc - 1;
+            const uint16_t* cp = a.coarse + ((int64_t)b * HWc + (int64_t)cy * a.Wc + cx) * 256 + c8;
+#pragma unroll
+            for (int p = 0; p < PA; ++p) {
+                const uint4 q = *(const uint4*)(cp + p * cplane);
+                const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    s[2 * e] += e2f<E>(wds[e] & 0xFFFFu);
+                    s[2 * e + 1] += e2f<E>(wds[e] >> 16);
+                }
+            }
+        }
+        uint32_t hi[8], lo[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f2e_split<E>(s[e], hi[e], lo[e]);
+        uint16_t* op = a.out + ((int64_t)b * HW + px) * 256 + c8;
+        *(uint4*)op = make_uint4(pack2(hi[0], hi[1]), pack2(hi[2], hi[3]), pack2(hi[4], hi[5]), pack2(hi[6], hi[7]));
+        if (PA == 2) *(uint4*)(op + oplane) = make_uint4(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]), pack2(lo[4], lo[5]), pack2(lo[6], lo[7]));
+    }
+}
+
 template <int PA, int E, int INDT, bool AL4>
 __global__ __launch_bounds__(FL_THREADS) void k_fpn_lateral(const FLArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
@@ -144,56 +202,7 @@ __global__ __launch_bounds__(FL_THREADS) void k_fpn_lateral(const FLArgs a) {
         }
     }
 
-    // ---- epilogue.  D layout: row = pixel (r & 3) + 8 (r >> 2) + 4 g of sub-tile ct, column = channel 32 wave + (lane & 31)
-    __syncthreads();                                     // the last chunk's transposed reads are done: the LDS is free
-    float* tf = (float*)lds;
-    {
-        const int ch = wave * 32 + (lane & 31);
-        const float bv = a.bias[ch];
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int px = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                tf[px * FL_EP + ch] = acc[ct][r] + bv;
-            }
-    }
-    __syncthreads();
-    const int64_t oplane = (int64_t)a.B * HW * 256;
-    const int64_t HWc = (int64_t)a.Hc * a.Wc, cplane = (int64_t)a.B * HWc * 256;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int idx = tid + it * FL_THREADS;
-        const int pl = idx >> 5, c8 = (idx & 31) * 8;
-        const int64_t px = px0 + pl;
-        if (px >= HW) continue;
-        const float4 s0 = *(const float4*)(tf + pl * FL_EP + c8), s1 = *(const float4*)(tf + pl * FL_EP + c8 + 4);
-        float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-        if (a.coarse) {
-            // F.interpolate(mode='nearest', size=(H, W)) for H in {2 Hc, 2 Hc - 1}: source index y Hc / H in integers (host-checked)
-            const int y = (int)(px / a.W), x = (int)(px - (int64_t)y * a.W);
-            int cy = y * a.Hc / a.H, cx = x * a.Wc / a.W;
-            if (cy > a.Hc - 1) cy = a.Hc - 1;
-            if (cx > a.Wc - 1) cx = a.Wc - 1;
-            const uint16_t* cp = a.coarse + ((int64_t)b * HWc + (int64_t)cy * a.Wc + cx) * 256 + c8;
-#pragma unroll
-            for (int p = 0; p < PA; ++p) {
-                const uint4 q = *(const uint4*)(cp + p * cplane);
-                const uint32_t wds[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    s[2 * e] += e2f<E>(wds[e] & 0xFFFFu);
-                    s[2 * e + 1] += e2f<E>(wds[e] >> 16);
-                }
-            }
-        }
-        uint32_t hi[8], lo[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f2e_split<E>(s[e], hi[e], lo[e]);
-        uint16_t* op = a.out + ((int64_t)b * HW + px) * 256 + c8;
-        *(uint4*)op = make_uint4(pack2(hi[0], hi[1]), pack2(hi[2], hi[3]), pack2(hi[4], hi[5]), pack2(hi[6], hi[7]));
-        if (PA == 2) *(uint4*)(op + oplane) = make_uint4(pack2(lo[0], lo[1]), pack2(lo[2], lo[3]), pack2(lo[4], lo[5]), pack2(lo[6], lo[7]));
-    }
+    fl_epilogue<PA, E>(a, acc, lds, b, HW, px0, tid, lane, wave, g);
 }
 
 extern "C" int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
@@ -248,6 +257,118 @@ extern "C" int ph_fpn_lateral(const void* x, int x_dtype, const uint16_t* Wp, in
 #undef PH_FL_D
 #undef PH_FL_A
 #undef PH_FL
+    PH_CHECK_LAUNCH();
+    return PH_OK;
+}
+
+// ---- the lateral of a stage that is a channels-last 16-bit plane [B][HW][K] (the backbone's own, as ph_conv_cl writes it): the same
+// GEMM -- tile, MFMA, B fragments, one accumulator chain per output element over ascending k, fl_epilogue -- so ph_fpn_lateral's
+// bits on the NCHW form of the same values.  Channels-last makes the A fragment of a pixel 8 consecutive channels, so the chunk is
+// staged [64 px][256 c] (k_conv_cl's staging at this tile) and read back with plain 16-byte LDS reads.  Row pitch 264 elements =
+// 132 dwords: the 16 rows of each lane group of a 16-byte read start 4 banks apart, every group covers the 64 banks once.
+constexpr int FC_LDA = FL_KC + 8;
+
+// the four 16-byte units of this thread: rows tid / 32 + 16 q, channels 8 (tid % 32) ..; every load is unconditional and inside the
+// plane: a row past HW is clamped to the last pixel (its output is never written, and no other row's output reads it), a unit past
+// K -- the last chunk of a K that is no multiple of 256 -- to the row's last unit (the k-loop never reads it)
+__device__ __forceinline__ void fc_load(uint4 (&v)[4], const uint16_t* src, int K, int64_t HW, int k0, int64_t px0, int tid) {
+    int c = k0 + (tid & 31) * 8;
+    if (c > K - 8) c = K - 8;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        int64_t px = px0 + (tid >> 5) + 16 * q;
+        if (px > HW - 1) px = HW - 1;
+        v[q] = ld_nt16(src + px * K + c);
+    }
+}
+
+// format XE -> fp32 -> format E (fl_store's conversion of the fp32 stage); the same format passes through
+template <int XE, int E> __device__ __forceinline__ uint32_t fc_cv2(uint32_t w) {
+    if constexpr (XE == E) return w;
+    else return pack2(f2e<E>(e2f<XE>(w & 0xFFFFu)), f2e<E>(e2f<XE>(w >> 16)));
+}
+
+template <int XE, int E>
+__global__ __launch_bounds__(FL_THREADS) void k_fpn_lateral_cl(const FLArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 5, l32 = lane & 31;
+    const int b = blockIdx.y, K = a.K;
+    const int64_t HW = (int64_t)a.H * a.W, px0 = (int64_t)blockIdx.x * FL_T;
+    const uint16_t* src = (const uint16_t*)a.x + (int64_t)b * HW * K;
+    const uint16_t* wrow = a.w + ((int64_t)wave * (K / 16) * 64 + lane) * 8;
+
+    f32x16_t acc[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+
+    uint4 v[4];
+    fc_load(v, src, K, HW, 0, px0, tid);
+    for (int k0 = 0; k0 < K; k0 += FL_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            *(uint4*)(lds + ((tid >> 5) + 16 * q) * FC_LDA + (tid & 31) * 8) =
+                make_uint4(fc_cv2<XE, E>(v[q].x), fc_cv2<XE, E>(v[q].y), fc_cv2<XE, E>(v[q].z), fc_cv2<XE, E>(v[q].w));
+        __syncthreads();
+        if (k0 + FL_KC < K) fc_load(v, src, K, HW, k0 + FL_KC, px0, tid);                // in flight during the MFMAs (uniform branch)
+        const int nks = (K - k0 < FL_KC ? K - k0 : FL_KC) / 16;                          // K % 64 == 0: a multiple of 4
+        const uint16_t* wk = wrow + (int64_t)(k0 / 16) * 512;
+        for (int ks4 = 0; ks4 < nks; ks4 += 4) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int ks = ks4 + kk;
+                const uint4 wf = *(const uint4*)(wk + (int64_t)ks * 512);
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const uint4 xf = *(const uint4*)(lds + (ct * 32 + l32) * FC_LDA + ks * 16 + g * 8);
+                    acc[ct] = mfma32e<E>(xf, wf, acc[ct]);
+                }
+            }
+        }
+    }
+
+    fl_epilogue<1, E>(a, acc, lds, b, HW, px0, tid, lane, wave, g);
+}
+
+extern "C" int ph_fpn_lateral_cl(const uint16_t* X, int x_prec, const uint16_t* Wp, int64_t w_plane_elems, const float* bias,
+                                 const uint16_t* coarse, int Hc, int Wc, uint16_t* out, int B, int K, int H, int W, int prec,
+                                 void* stream) {
+    PH_CHECK_ARG(X && Wp && bias && out, "null pointer (X, Wp, bias, out)");
+    PH_CHECK_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= (int64_t)FL_T * 0x7FFFFFFF, "B, H, W out of range");
+    PH_CHECK_ARG(K >= 64 && K <= 4096 && K % 64 == 0, "K must be a multiple of 64 in [64, 4096]");
+    PH_CHECK_ARG(w_plane_elems == (int64_t)256 * K, "w_plane_elems must be 256 * K (pack_b32 fragments of W[256][K])");
+    PH_CHECK_ARG(x_prec == PH_PREC_BF16 || x_prec == PH_PREC_F16, "x_prec must be PH_PREC_BF16 or PH_PREC_F16");
+    if (prec == PH_PREC_SPLIT) {
+        ph_set_error("%s: %s", __func__, "PH_PREC_SPLIT: the hi + lo grade takes the NCHW stage (ph_cl_to_nchw, then ph_fpn_lateral)");
+        return PH_EUNSUPPORTED;
+    }
+    PH_CHECK_ARG(prec == PH_PREC_BF16 || prec == PH_PREC_F16, "prec must be PH_PREC_BF16 or PH_PREC_F16");
+    if (coarse) {
+        PH_CHECK_ARG(Hc > 0 && Wc > 0 && ph_fpn_size_rule(H, Hc) && ph_fpn_size_rule(W, Wc),
+                     "coarse size: H must be 2 Hc or 2 Hc - 1 and W must be 2 Wc or 2 Wc - 1 (the sizes at which the integer nearest index is torch's)");
+        PH_CHECK_ARG(((uintptr_t)coarse & 15) == 0, "coarse must be 16-byte aligned");
+    }
+    PH_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)Wp & 15) == 0, "X, out and Wp must be 16-byte aligned");
+    FLArgs a{X, Wp, w_plane_elems, bias, coarse, out, B, K, H, W, coarse ? Hc : 1, coarse ? Wc : 1};
+    const dim3 grid((unsigned)(((int64_t)H * W + FL_T - 1) / FL_T), (unsigned)B);
+    constexpr size_t lds = (size_t)FL_T * FL_EP * sizeof(float);             // the epilogue tile; the staged chunk is smaller
+    static_assert((size_t)FL_T * FC_LDA * sizeof(uint16_t) <= lds, "the staged chunk must fit the epilogue tile");
+    hipStream_t s = (hipStream_t)stream;
+#define PH_FC(XE_, E_)                                                                                                            \
+    do {                                                                                                                          \
+        static const bool once = [&] {                                                                                            \
+            (void)hipFuncSetAttribute((const void*)k_fpn_lateral_cl<XE_, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            return true;                                                                                                          \
+        }();                                                                                                                      \
+        (void)once;                                                                                                               \
+        hipLaunchKernelGGL((k_fpn_lateral_cl<XE_, E_>), grid, dim3(FL_THREADS), lds, s, a);                                       \
+    } while (0)
+    if (prec == PH_PREC_BF16) { if (x_prec == PH_PREC_BF16) PH_FC(PH_E_BF16, PH_E_BF16); else PH_FC(PH_E_F16, PH_E_BF16); }
+    else { if (x_prec == PH_PREC_BF16) PH_FC(PH_E_BF16, PH_E_F16); else PH_FC(PH_E_F16, PH_E_F16); }
+#undef PH_FC
     PH_CHECK_LAUNCH();
     return PH_OK;
 }

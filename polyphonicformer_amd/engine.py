@@ -1356,6 +1356,19 @@ def fpn_lateral(x, wp, bias, coarse, coarse_hw, out, prec):
     return out
 
 
+def fpn_lateral_cl(x, x_prec, hw, wp, bias, coarse, coarse_hw, out, prec):
+    """`fpn_lateral` for a stage that is a channels-last 16-bit plane: x int16 [B, H*W, K] of grade `x_prec` with hw = (H, W); the
+    other arguments are fpn_lateral's, `prec` PH_PREC_BF16 / PH_PREC_F16.  The bits of fpn_lateral on cl_to_nchw's tensor of x"""
+    B, HW, K = x.shape
+    H, W = hw
+    if H * W != HW:
+        raise _lib.PolyheadError("fpn_lateral_cl: x must be [B, H*W, K]")
+    Hc, Wc = coarse_hw if coarse is not None else (0, 0)
+    _lib.check(_lib.load().ph_fpn_lateral_cl(_lib.ptr(x), x_prec, _lib.ptr(wp), wp.shape[1], _lib.ptr(bias), _lib.ptr(coarse), Hc, Wc,
+                                             _lib.ptr(out), B, K, H, W, prec, _lib.stream_ptr()), "ph_fpn_lateral_cl")
+    return out
+
+
 def fpn_output(y, bias, out, B, HW):
     """fp32 NHWC conv result [B, HW, 256] + bias -> fp32 NCHW `out`"""
     _lib.check(_lib.load().ph_fpn_output(_lib.ptr(y), _lib.ptr(bias), _lib.ptr(out), B, HW, _lib.stream_ptr()), "ph_fpn_output")
@@ -1408,9 +1421,32 @@ class FpnPlan:
         self.y = e((B, big, 256), torch.float32)
         self.partial = e((max(lib.ph_conv_nhwc_partial_floats(B, h, w) for h, w in self.shapes),), torch.float32)   # the conv's GN sums: unused
         self.outs = [e((B, 256, h, w), torch.float32) for h, w in self.shapes]
+        self.stages_f32 = None                    # the hi + lo grade's NCHW stages of a StagePlanes input, allocated when first needed
+
+    def _laterals_cl(self, sp, pk):
+        """the four laterals from a StagePlanes: ph_fpn_lateral_cl in the one-plane grades; the hi + lo grade converts each plane to a
+        plan-owned fp32 NCHW stage (ph_cl_to_nchw: exact) and runs ph_fpn_lateral on it"""
+        B, prec = self.B, self.prec
+        if len(sp) != 4 or sp.B != B or sp.device != self.y.device or \
+                tuple(sp.shapes) != tuple((k,) + hw for k, hw in zip(self.in_channels, self.shapes)):
+            raise _lib.PolyheadError(f"FpnPlan.run: the StagePlanes must hold {B} frames of the plan's four stages "
+                                     f"{[(k,) + hw for k, hw in zip(self.in_channels, self.shapes)]} on its device")
+        split = prec == _lib.PH_PREC_SPLIT
+        if split and self.stages_f32 is None:
+            self.stages_f32 = [torch.empty((B, k) + hw, dtype=torch.float32, device=self.y.device)
+                               for k, hw in zip(self.in_channels, self.shapes)]
+        for lvl in (3, 2, 1, 0):
+            c, (h, w) = pk["lateral"][lvl], self.shapes[lvl]
+            coarse, chw = (self.lat[lvl + 1], self.shapes[lvl + 1]) if lvl < 3 else (None, None)
+            if split:
+                cl_to_nchw(sp.planes[lvl], self.stages_f32[lvl], B, h * w, self.in_channels[lvl], sp.prec)
+                fpn_lateral(self.stages_f32[lvl], c["wp"], c["bias"], coarse, chw, self.lat[lvl], prec)
+            else:
+                fpn_lateral_cl(sp.planes[lvl], sp.prec, (h, w), c["wp"], c["bias"], coarse, chw, self.lat[lvl], prec)
 
     def run(self, feats, pk, neck=None, want_levels=True):
-        """feats: the four backbone stages [B, K_l, H_l, W_l]; pk: fpn.FPN's pack (lateral / output: lists of dicts).
+        """feats: the four backbone stages [B, K_l, H_l, W_l], or a StagePlanes (the backbone's own channels-last planes: the laterals
+        read them directly, everything behind the laterals is the same); pk: fpn.FPN's pack (lateral / output: lists of dicts).
         neck: a NeckHandoff -- the direct hand-over: each output conv's tail (ph_fpn_output_planes) writes the neck plan's conv input
         planes of that level, positional encoding included, instead of the fp32 level that the neck would ingest; the fp32 levels are
         written as well when `want_levels`.  Shared neck buffers: the level's tower runs before the next level is written; tower
@@ -1419,15 +1455,18 @@ class FpnPlan:
         B, prec = self.B, self.prec
         if neck is not None and (neck.plan.B != B or tuple(tuple(x) for x in neck.plan.shapes) != self.shapes or neck.plan.prec != prec):
             raise _lib.PolyheadError("FpnPlan.run: the neck plan's frames, level sizes or grade differ from this plan's")
-        for lvl, t in enumerate(feats):
-            if tuple(t.shape) != (B, self.in_channels[lvl]) + self.shapes[lvl] or t.dtype not in OUT_CODE or not t.is_contiguous() \
-                    or t.device != self.y.device:
-                raise _lib.PolyheadError(f"FpnPlan.run: inputs[{lvl}] must be a contiguous fp32 / bf16 / fp16 device tensor of shape "
-                                         f"{(B, self.in_channels[lvl]) + self.shapes[lvl]}")
-        for lvl in (3, 2, 1, 0):                  # coarse to fine: each lateral adds the finished one above it
-            c = pk["lateral"][lvl]
-            fpn_lateral(feats[lvl], c["wp"], c["bias"], self.lat[lvl + 1] if lvl < 3 else None,
-                        self.shapes[lvl + 1] if lvl < 3 else None, self.lat[lvl], prec)
+        if isinstance(feats, StagePlanes):
+            self._laterals_cl(feats, pk)
+        else:
+            for lvl, t in enumerate(feats):
+                if tuple(t.shape) != (B, self.in_channels[lvl]) + self.shapes[lvl] or t.dtype not in OUT_CODE or not t.is_contiguous() \
+                        or t.device != self.y.device:
+                    raise _lib.PolyheadError(f"FpnPlan.run: inputs[{lvl}] must be a contiguous fp32 / bf16 / fp16 device tensor of shape "
+                                             f"{(B, self.in_channels[lvl]) + self.shapes[lvl]}")
+            for lvl in (3, 2, 1, 0):                  # coarse to fine: each lateral adds the finished one above it
+                c = pk["lateral"][lvl]
+                fpn_lateral(feats[lvl], c["wp"], c["bias"], self.lat[lvl + 1] if lvl < 3 else None,
+                            self.shapes[lvl + 1] if lvl < 3 else None, self.lat[lvl], prec)
         for lvl, (h, w) in enumerate(self.shapes):
             c = pk["output"][lvl]
             conv_nhwc(self.lat[lvl], c, self.y, self.partial, B, h, w, prec)
@@ -1943,9 +1982,13 @@ class ResNetPlan:
     ping-pong block planes, the two inner planes of a bottleneck, the downsample plane and the NCHW stages, all sized here.  `run`
     issues everything on the current stream -- one stream, so a captured graph of it has no parallel branches -- and neither
     allocates nor synchronises; the outputs are the plan's buffers and are overwritten by the next call, as FpnPlan's are.
-    blocks: per stage a list of (cin, planes, stride, has_downsample)."""
+    blocks: per stage a list of (cin, planes, stride, has_downsample).
+    stage_planes=True: the last bottleneck of every output stage writes a plane the plan owns for that stage (`stage_plane(i)`) instead
+    of a ping-pong plane, which the next stage overwrites -- the same launches and values, so the stage outlives the run as the 16-bit
+    channels-last plane `fpn_lateral_cl` reads; `run(.., nchw=False)` then skips the NCHW conversions, and the NCHW tensors are
+    allocated at the first run that asks for them."""
 
-    def __init__(self, B, H, W, blocks, out_indices, prec, stage_dtype, device):
+    def __init__(self, B, H, W, blocks, out_indices, prec, stage_dtype, device, stage_planes=False):
         if prec not in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16):
             raise _lib.PolyheadError("ResNetPlan: the grade must be bf16 or fp16 (one 16-bit plane)")
         if stage_dtype not in OUT_CODE:
@@ -1985,7 +2028,23 @@ class ResNetPlan:
         e = lambda n: torch.empty((B * n,), dtype=torch.int16, device=dev)
         self.p0 = e(self.stem_hw[0] * self.stem_hw[1] * 64)
         self.pa, self.pb, self.t1, self.t2, self.pd = e(io), e(io), e(inner), e(inner), e(max(down, 8))
-        self.outs = {i: torch.empty((B,) + self.stage_shapes[i], dtype=stage_dtype, device=dev) for i in self.out_indices}
+        self.planes = {i: e(math.prod(self.stage_shapes[i])).view(B, -1, self.stage_shapes[i][0]) for i in self.out_indices} \
+            if stage_planes else None
+        self.outs = None if stage_planes else self._nchw()
+
+    def _nchw(self):
+        return {i: torch.empty((self.B,) + self.stage_shapes[i], dtype=self.stage_dtype, device=self.device) for i in self.out_indices}
+
+    def stage_plane(self, i):
+        """output stage i as the last run left it: int16 [B, h*w, C] holding the grade's 16-bit values (stage_planes=True only)"""
+        if self.planes is None:
+            raise _lib.PolyheadError("ResNetPlan.stage_plane: the plan was built without stage_planes=True")
+        return self.planes[i]
+
+    def bytes(self):
+        """device memory the plan holds at this moment"""
+        ts = [self.p0, self.pa, self.pb, self.t1, self.t2, self.pd] + list((self.planes or {}).values()) + list((self.outs or {}).values())
+        return sum(t.numel() * t.element_size() for t in ts)
 
     def run_stem(self, x, pk):
         """the stem's launch; x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device"""
@@ -1996,11 +2055,13 @@ class ResNetPlan:
         resnet_stem(x, pk["stem"][0], pk["stem"][1], self.p0, self.prec)
         self._at = (self.stem_hw, self.p0, self.pa)                 # (size, the plane that holds the activation, the one to write next)
 
-    def run_stage(self, si, pk):
-        """stage si's launches (its bottlenecks and, if it is an output, the NCHW conversion) on what the previous step left"""
+    def run_stage(self, si, pk, nchw=True):
+        """stage si's launches (its bottlenecks and, if it is an output and `nchw`, the NCHW conversion) on what the previous step left"""
         B, prec, stage = self.B, self.prec, self.blocks[si]
         (h, w), cur, nxt = self._at
         for j, (cin, planes, s, has_down) in enumerate(stage):
+            if self.planes is not None and si in self.planes and j == len(stage) - 1:
+                nxt = self.planes[si]                            # both ping-pong planes are free behind it
             c = pk["blocks"][si][j]
             ho, wo = conv_out_size(h, 3, s), conv_out_size(w, 3, s)
             conv_cl(cur, c["conv1"][0], c["conv1"][1], None, self.t1, 1, 1, True, B, h, w, cin, planes, prec)
@@ -2011,16 +2072,44 @@ class ResNetPlan:
             conv_cl(self.t2, c["conv3"][0], c["conv3"][1], idn, nxt, 1, 1, True, B, ho, wo, planes, 4 * planes, prec)
             cur, nxt = nxt, (self.pb if nxt is self.pa else self.pa)
             h, w = ho, wo
-        if si in self.outs:
+        if nchw and si in self.out_indices:
+            if self.outs is None:
+                self.outs = self._nchw()
             cl_to_nchw(cur, self.outs[si], B, h * w, 4 * stage[-1][1], prec)
         self._at = ((h, w), cur, nxt)
 
-    def run(self, x, pk):
-        """x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device; pk: resnet.ResNet's pack.  Returns the NCHW stages of out_indices"""
+    def run(self, x, pk, nchw=True):
+        """x: [B, 3, H, W] fp32 / bf16 contiguous on the plan's device; pk: resnet.ResNet's pack.  Returns the NCHW stages of
+        out_indices; nchw=False (a stage_planes plan): the launches without the NCHW conversions, returns None -- `stage_plane(i)`"""
+        if not nchw and self.planes is None:
+            raise _lib.PolyheadError("ResNetPlan.run: nchw=False needs a plan built with stage_planes=True")
         self.run_stem(x, pk)
         for si in range(max(self.out_indices) + 1):              # a stage behind the last output has no reader
-            self.run_stage(si, pk)
-        return tuple(self.outs[i] for i in self.out_indices)
+            self.run_stage(si, pk, nchw)
+        return tuple(self.outs[i] for i in self.out_indices) if nchw else None
+
+
+class StagePlanes:
+    """the backbone's output stages as it holds them: `planes[l]` int16 [B, h*w, C] (16-bit channels-last values of grade `prec`,
+    PH_PREC_BF16 / PH_PREC_F16), `shapes[l]` = (C, h, w).  What resnet.ResNet.forward_planes returns and FpnPlan.run, fpn.FPN and
+    SemanticFPNWrapper.forward_from_fpn take in place of the NCHW tensors.  The planes are the backbone plan's buffers: the next
+    forward of the same size overwrites them."""
+
+    def __init__(self, planes, shapes, prec):
+        if prec not in (_lib.PH_PREC_BF16, _lib.PH_PREC_F16):
+            raise _lib.PolyheadError("StagePlanes: the grade must be PH_PREC_BF16 or PH_PREC_F16")
+        self.planes, self.shapes, self.prec = tuple(planes), tuple(tuple(int(v) for v in s) for s in shapes), prec
+        if len(self.planes) != len(self.shapes):
+            raise _lib.PolyheadError("StagePlanes: one (C, h, w) per plane")
+        for t, (c, h, w) in zip(self.planes, self.shapes):
+            if t.dtype != torch.int16 or not t.is_contiguous() or t.dim() != 3 or tuple(t.shape[1:]) != (h * w, c):
+                raise _lib.PolyheadError(f"StagePlanes: a plane must be contiguous int16 [B, {h * w}, {c}]")
+
+    B = property(lambda self: self.planes[0].shape[0])
+    device = property(lambda self: self.planes[0].device)
+
+    def __len__(self):
+        return len(self.planes)
 
 
 # ---- the backbone as a native object (include/polyhead.h ph_resnet_cfg .. ph_resnet_plan_run) --------------------------------

@@ -113,23 +113,28 @@ class FPN(nn.Module):
         return tuple(F.conv2d(lat[i], m.conv.weight, m.conv.bias, padding=1) for i, m in enumerate(self.fpn_convs))
 
     def forward(self, inputs):
+        """inputs: the four backbone stages, or an engine.StagePlanes (resnet.ResNet.forward_planes: the laterals then read the
+        backbone's channels-last planes directly -- the same levels, bit for bit; inference on the device only)"""
         assert len(inputs) == len(self.in_channels)
         if self.training and torch.is_grad_enabled():
+            if isinstance(inputs, E.StagePlanes):
+                raise _lib.PolyheadError("FPN: StagePlanes are the inference hand-over; in training mode with grad enabled pass the stages")
             if self.device_training:
                 from .train import fpn_forward_train
                 return fpn_forward_train(self, inputs)
             return self._forward_torch(inputs)
         plan, pk, feats = self._plan_of(inputs)
-        with torch.cuda.device(feats[0].device):
+        with torch.cuda.device(plan.y.device):
             return tuple(plan.run(feats, pk))
 
     def _plan_of(self, inputs):
         """(the device plan of these stages, the packed parameters, the stages as the plan takes them): what `forward` runs, and
         what SemanticFPNWrapper.forward_from_fpn runs with the neck's plan as the receiver of the levels"""
-        x0 = inputs[0]
+        planes = isinstance(inputs, E.StagePlanes)
+        x0 = inputs.planes[0] if planes else inputs[0]
         E._require_gpu(x0, "inputs[0]")
         dev, B = x0.device, x0.shape[0]
-        shapes = tuple(tuple(t.shape[-2:]) for t in inputs)
+        shapes = tuple(s[1:] for s in inputs.shapes) if planes else tuple(tuple(t.shape[-2:]) for t in inputs)
         prec = E.KHEAD_PREC[self.precision]
         pk = self._pack(dev)
         key = (B, shapes, str(dev), self.precision)
@@ -137,6 +142,8 @@ class FPN(nn.Module):
         if plan is None:
             with torch.cuda.device(dev):
                 plan = self._plans[key] = E.FpnPlan(B, shapes, self.in_channels, prec, dev)
+        if planes:
+            return plan, pk, inputs
         return plan, pk, [t.contiguous() if t.dtype in E.OUT_CODE else t.contiguous().float() for t in inputs]
 
 

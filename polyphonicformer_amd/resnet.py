@@ -8,6 +8,8 @@ Same constructor keywords and the reference's state_dict keys (`conv1.weight`, `
 Inference (`forward` on the device with no gradient asked for) runs in libpolyhead (csrc/ph_resnet.hip): every BatchNorm is folded
 into its convolution in float64 (`fold_bn`), activations are one 16-bit channels-last plane ('bf16', the default, or 'fp16'), and the
 stages come back as NCHW tensors (fp32 by default; `set_stage_dtype` for the 16-bit hand-off `ph_fpn_lateral` also takes).
+`forward_planes` hands the stages out as the plan's own channels-last planes instead (engine.StagePlanes), which fpn.FPN reads
+directly (`ph_fpn_lateral_cl`): the same levels without an NCHW stage in between.
 `use_native_plan(True)` moves the fold, the packing and the launch sequence into the library as well (ph_resnet_pack,
 engine.NativeResNetPlan: one native call per forward, the same bits).  `_forward_torch` is the same arithmetic in torch ops: CPU tensors, and by default whenever grad is enabled and a parameter or the
 input requires grad, as with fpn.FPN's default.
@@ -272,21 +274,23 @@ class ResNet(nn.Module):
         """per stage a list of (cin, planes, stride, has_downsample): what engine.ResNetPlan sizes its buffers from"""
         return [[(m.inplanes, m.planes, m.stride, m.downsample is not None) for m in getattr(self, name)] for name in self.res_layers]
 
-    def _plan_of(self, x):
-        """(the device plan of this input, the packed parameters, the input as the plan takes it)"""
+    def _plan_of(self, x, stage_planes=False):
+        """(the device plan of this input, the packed parameters, the input as the plan takes it); stage_planes: the plan that keeps
+        every output stage as a plane of its own (`forward_planes`)"""
         E._require_gpu(x, "x")
         if x.dim() != 4 or x.shape[1] != 3:
             raise _lib.PolyheadError("ResNet: x must be [B, 3, H, W]")
         dev, (B, _, H, W) = x.device, x.shape
         pk = self._pack(dev)
-        key = (B, H, W, str(dev), self.precision, self.stage_dtype, tuple(self.out_indices), tuple(map(tuple, self.block_table())))
+        key = (B, H, W, str(dev), self.precision, self.stage_dtype, tuple(self.out_indices), tuple(map(tuple, self.block_table())),
+               stage_planes)
         plan = self._plans.get(key)
         if plan is None:
             if len(self._plans) >= self.MAX_PLANS:               # a plan holds every activation plane of its size: keep a few, not all
                 self._plans.clear()
             with torch.cuda.device(dev):
                 plan = self._plans[key] = E.ResNetPlan(B, H, W, self.block_table(), self.out_indices, E.KHEAD_PREC[self.precision],
-                                                       self.stage_dtype, dev)
+                                                       self.stage_dtype, dev, stage_planes=stage_planes)
         return plan, pk, x.contiguous() if x.dtype in (torch.float32, torch.bfloat16) else x.contiguous().float()
 
     def forward(self, x):
@@ -300,6 +304,21 @@ class ResNet(nn.Module):
         plan, pk, xin = self._native_plan_of(x) if self._native else self._plan_of(x)
         with torch.cuda.device(x.device):
             return plan.run(xin, pk)
+
+
+    def forward_planes(self, x):
+        """`forward` without the NCHW hand-off: the output stages as the engine.StagePlanes of the plan's own channels-last 16-bit
+        planes, which fpn.FPN.forward and SemanticFPNWrapper.forward_from_fpn take in place of the tensors (ph_fpn_lateral_cl reads
+        them: the same levels as `fpn(backbone(x))`, bit for bit, without the stages crossing memory as fp32 NCHW).  The planes are
+        overwritten by the next call at this size.  Inference on the device, Python plan only."""
+        if self._native:
+            raise _lib.PolyheadError("ResNet.forward_planes: the native plan hands out NCHW stages only; use_native_plan(False)")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise _lib.PolyheadError("ResNet.forward_planes is the inference hand-over; with grad enabled call forward")
+        plan, pk, xin = self._plan_of(x, stage_planes=True)
+        with torch.cuda.device(x.device):
+            plan.run(xin, pk, nchw=False)
+        return E.StagePlanes([plan.stage_plane(i) for i in self.out_indices], [plan.stage_shapes[i] for i in self.out_indices], plan.prec)
 
 
 register_everywhere(ResNet, kind="backbone")

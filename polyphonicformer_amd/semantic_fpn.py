@@ -246,7 +246,9 @@ class SemanticFPNWrapper(nn.Module):
     def forward_from_fpn(self, fpn, stages, planes=False, want_levels=False):
         """`forward(fpn(stages))` -- `forward_planes(fpn(stages))` with `planes` -- with the direct hand-over: the FPN's output
         convolutions write this neck's conv input planes themselves (ph_fpn_output_planes, the positional encoding included), so the
-        fp32 levels are not written and read back on the way; the same bits.  `fpn`: a fpn.FPN of the same precision.  With
+        fp32 levels are not written and read back on the way; the same bits.  `fpn`: a fpn.FPN of the same precision; `stages`: the
+        backbone's four stages, or its engine.StagePlanes (resnet.ResNet.forward_planes), with which the whole front from image to
+        neck stays channels-last.  With
         `want_levels` the fp32 levels are written too and the result is (outputs, levels) -- the track head's RoIAlign takes them.
         Python or native neck plan (`use_native_plan`).  Inference only: training goes through `forward`."""
         if (self.training or fpn.training) and torch.is_grad_enabled():
@@ -257,7 +259,7 @@ class SemanticFPNWrapper(nn.Module):
         if fpn.precision != self.precision:
             raise _lib.PolyheadError(f"forward_from_fpn: the FPN's precision ({fpn.precision}) differs from the neck's ({self.precision})")
         fplan, fpk, feats = fpn._plan_of(stages)
-        dev, B, shapes = feats[0].device, feats[0].shape[0], fplan.shapes
+        dev, B, shapes = fplan.y.device, fplan.B, fplan.shapes
         if self.native_plan:
             plan, pk, add, pos_level = self._native_plan(dev, B, shapes)
         else:

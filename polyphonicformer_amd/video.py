@@ -270,16 +270,32 @@ class VideoFramePipeline:
         get_things_id_for_tracking -> boxes / RoIAlign on the FPN levels `x` -> track_head -> tracker.match
         -> [{"sem": uint8 map, "track": float64 map, "depth": fp32 map}]
 
-    One instance per video stream (the tracker is stateful; `init_tracker` starts a new video, :59-61).  Backbone and FPN
-    are the caller's (`x` = the four FPN levels of ONE frame, as `extract_feat` returns them)."""
+    One instance per video stream (the tracker is stateful; `init_tracker` starts a new video, :59-61).  `x` = the four FPN levels
+    of ONE frame, as `extract_feat` returns them: the caller's own backbone and FPN, or -- with `backbone` (a resnet.ResNet) and
+    `fpn` (a fpn.FPN) given -- this pipeline's `extract_feat(img)`, which `simple_test_image` and the runners' image calls use."""
 
-    def __init__(self, rpn_head, roi_head, track_head, tracker_cfg, strides=(4, 8, 16, 32)):
+    def __init__(self, rpn_head, roi_head, track_head, tracker_cfg, strides=(4, 8, 16, 32), backbone=None, fpn=None):
         self.rpn_head, self.roi_head = rpn_head, roi_head
+        self.backbone, self.fpn = backbone, fpn
         self.assoc = VideoAssociator(track_head, tracker_cfg, roi_head.num_thing_classes, roi_head.num_stuff_classes, strides)
         self._api_runners = {}               # `simple_test`: frame geometry -> its one-slot VideoStreamRunner, one at a time
 
     def init_tracker(self):
         self.assoc.init_tracker()
+
+    def extract_feat(self, img):
+        """`PolyphonicVideo.extract_feat` (:62-66): img [B, 3, H, W] on the device -> the four fp32 FPN levels, through the direct
+        path: the backbone's channels-last stage planes go straight into the FPN's laterals (ResNet.forward_planes; the bits of
+        `fpn(backbone(img))`).  The levels are the FPN plan's buffers: the next call at this size overwrites them."""
+        if self.backbone is None or self.fpn is None:
+            raise _lib.PolyheadError("VideoFramePipeline.extract_feat: the pipeline was built without backbone and fpn "
+                                     "(build_video_pipeline_from_config(cfg, with_backbone=True))")
+        with torch.no_grad():
+            return self.fpn(self.backbone.forward_planes(img))
+
+    def simple_test_image(self, img, img_metas, rescale=False, records_only=False):
+        """`simple_test` from the image: `simple_test(extract_feat(img), ...)`"""
+        return self.simple_test(self.extract_feat(img), img_metas, rescale=rescale, records_only=records_only)
 
     def heads(self, x, img_metas, rescale=False):
         """the two heads exactly as :343-357 calls them; returns roi_head.simple_test's result list"""
@@ -308,14 +324,15 @@ class VideoFramePipeline:
         return self.assoc.step(x, panoptic_seg, segments_info, depth_final, records_only=records_only)
 
 
-def build_video_pipeline_from_config(cfg):
+def build_video_pipeline_from_config(cfg, with_backbone=False):
     """`PolyphonicVideo.__init__` (polyphonic/polyphonic_former_video.py:23-60) from a loaded reference config (nested dict with a
     `model` key, e.g. configs/polyphonic_video/poly_r50_cityscapes_1x.py after `_base_` resolution): rpn_head / roi_head with
     train_cfg / test_cfg injected as TwoStageDetector does, `track_head` from the registry, the tracker from `model.tracker`, the
     RoI extractor from `model.bbox_roi_extractor` (the shipped one: SingleRoIExtractor over RoIAlign 7x7, sampling_ratio 2 --
-    csrc/ph_track.hip implements exactly that; anything else is refused).  Backbone and FPN stay the caller's.  Returns a
-    `VideoFramePipeline`."""
-    from .registry import build_heads_from_config, build_head, deep_cfg
+    csrc/ph_track.hip implements exactly that; anything else is refused).  Backbone and FPN stay the caller's unless
+    `with_backbone`: then `model.backbone` and `model.neck` are built from the registries as well (resnet.ResNet, fpn.FPN) and the
+    pipeline takes images (`extract_feat`, `simple_test_image`).  Returns a `VideoFramePipeline`."""
+    from .registry import build_heads_from_config, build_head, build_backbone, build_neck, deep_cfg
     from . import track_head  # noqa: F401  (registers QuasiDenseMaskEmbedHeadGTMask and the loss names its config carries)
     model = cfg["model"]
     for k in ("track_head", "tracker", "bbox_roi_extractor"):
@@ -328,7 +345,15 @@ def build_video_pipeline_from_config(cfg):
             or rl.get("sampling_ratio", 0) != 2 or ext.get("out_channels") != 256:
         raise NotImplementedError(f"bbox_roi_extractor {ext!r}: libpolyhead implements SingleRoIExtractor(RoIAlign 7x7, sampling_ratio=2, 256 ch)")
     th = build_head(deep_cfg(model["track_head"]))
-    return VideoFramePipeline(rpn_head, roi_head, th, deep_cfg(model["tracker"]), strides=tuple(ext["featmap_strides"]))
+    backbone = fpn = None
+    if with_backbone:
+        for k in ("backbone", "neck"):
+            if model.get(k) is None:
+                raise ValueError(f"model.{k} is missing: with_backbone=True builds it")
+        from . import resnet, fpn as _fpn  # noqa: F401  (register ResNet and FPN)
+        backbone, fpn = build_backbone(deep_cfg(model["backbone"])), build_neck(deep_cfg(model["neck"]))
+    return VideoFramePipeline(rpn_head, roi_head, th, deep_cfg(model["tracker"]), strides=tuple(ext["featmap_strides"]),
+                              backbone=backbone, fpn=fpn)
 
 
 def _h2d(values, dtype, dev):
@@ -734,6 +759,15 @@ class VideoStreamRunner:
         self._downloads = []
         return out
 
+    def push_image(self, img):
+        """`push` from the frame's image [1, 3, H, W]: the pipeline's backbone and FPN (`extract_feat`) on the caller's stream, then
+        `push` of the levels"""
+        return self.push(self.pipe.extract_feat(img))
+
+    def run_one_image(self, img):
+        """`run_one` from the frame's image [1, 3, H, W]"""
+        return self.run_one(self.pipe.extract_feat(img))
+
     def run_one(self, x):
         """`push` without the delay: the frame's heads, merge and association, and its own result list at once"""
         self._check(x)
@@ -873,6 +907,11 @@ class MultiStreamRunner:
         if self._merge is None or self._merge[0] != key:
             self._merge = (key, Pn.BatchMerge(self.pipe.roi_head, B, N, L, h2, w2, mask_up.dtype, self.meta, mask_up.device))
         return self._merge[1]
+
+    def step_images(self, imgs, active=None):
+        """`step` from the S streams' current images [S, 3, H, W]: the pipeline's backbone and FPN (`extract_feat`) on the caller's
+        stream for the S frames at once (a frame's levels do not depend on the others'), then `step` of the levels"""
+        return self.step(self.pipe.extract_feat(imgs), active=active)
 
     def step(self, x, active=None):
         """x: the FPN levels of the S streams' current frames, [S, 256, H_l, W_l] per level on the device; `active`: a host sequence

@@ -23,11 +23,18 @@ the device path and the two torch forms take turns inside every repetition; the 
     layers by themselves); then three sides alternating in one process: the device path
     (`train_on_device()`: module forward, `torch.autograd.backward`), torch fp32 NCHW, torch bf16 autocast on channels-last.
 
+  * with --handoff-out, INSTEAD of the sections above: the backbone's hand-over to the FPN, the NCHW form (`fpn(backbone(img))`:
+    ph_cl_to_nchw writes fp32 NCHW stages, ph_fpn_lateral reads them) beside the direct one (`fpn(backbone.forward_planes(img))`:
+    ph_fpn_lateral_cl reads the backbone's planes), same method, grades 'bf16' and 'fp16', B = 1 and B = 4: backbone + FPN through
+    the module calls (GPU time and the host's wall time per call); the four laterals alone in both forms and the four NCHW
+    conversions alone, with the bytes each moves per second; the device memory of the backbone plan in both forms.
+
 The result is written to --out after every section, so a run that is cut short leaves what it measured.
 
     python tools/resnet_time.py --out profiles/resnet/time.json
     python tools/resnet_time.py --native-out profiles/resnet/native_time.json
     python tools/resnet_time.py --train-out profiles/resnet/train_time.json
+    python tools/resnet_time.py --handoff-out profiles/resnet/handoff_time.json
 """
 import argparse
 import copy
@@ -229,6 +236,83 @@ def train_section(dev, batches, reps, warmup, out):
         torch.cuda.empty_cache()
 
 
+def handoff_section(m, dev, batches, reps, warmup, out):
+    """backbone + FPN and the laterals alone, NCHW hand-over beside the direct one; written to `out` after every part"""
+    import helpers
+    from polyphonicformer_amd.fpn import FPN
+    res = {"command": "python tools/resnet_time.py --handoff-out OUT", "workload": "ResNet-50 + FPN of a 1024 x 2048 fp32 image -> four fp32 "
+           "NCHW levels.  nchw: fpn(backbone(img)) -- fp32 NCHW stages between them; planes: fpn(backbone.forward_planes(img)) -- "
+           "ph_fpn_lateral_cl on the backbone's 16-bit channels-last planes.  The sides alternate in one process; gpu = HIP events around "
+           "the call, host = wall time of the call itself with the queue empty before it.  laterals: the four lateral launches alone "
+           "(to_nchw: the four ph_cl_to_nchw launches the nchw form needs in front of them); gbytes = stage read + output planes written "
+           "+ coarse planes read once + weights, gb_per_s from it.  plan_bytes: the backbone plan's device memory", "reps": reps, "warmup": warmup}
+
+    def flush():
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(json.dumps(res) + "\n")
+        print(json.dumps(res), flush=True)
+    fpn = FPN([256, 512, 1024, 2048], 256, 4)
+    fpn.load_state_dict(helpers.seeded_fill({k: tuple(v.shape) for k, v in fpn.state_dict().items()}, 17))
+    fpn.eval().to(dev)
+    with torch.no_grad():
+        for grade in ("bf16", "fp16"):
+            mg = copy.deepcopy(m).set_precision(grade)
+            fpn.set_precision(grade)
+            prec = E.KHEAD_PREC[grade]
+            for B in batches:
+                x = resnet_cases.inputs(1, (B, 3, H, W))[0].to(dev)
+                r = res[f"{grade}_B{B}"] = {}
+                r["backbone_fpn"] = alternate_host({"nchw": lambda: fpn(mg(x)), "planes": lambda: fpn(mg.forward_planes(x))}, reps, warmup)
+                g = r["backbone_fpn"]
+                g["planes_over_nchw_gpu"] = round(g["planes"]["gpu"]["ms"] / g["nchw"]["gpu"]["ms"], 4)
+                flush()
+                # the laterals alone, on the stages of one run in both forms and the FPN plan's own lateral planes
+                pk, fpk = mg._pack(dev), fpn._pack(dev)
+                rplan = mg._plan_of(x, stage_planes=True)[0]
+                stages = rplan.run(x, pk)
+                shapes = rplan.stage_shapes
+                fplan = fpn._plan_of(stages)[0]
+                r["plan_bytes"] = {"nchw": mg._plan_of(x)[0].bytes(), "planes_with_nchw_stages": rplan.bytes(),
+                                   "planes": rplan.bytes() - sum(t.numel() * t.element_size() for t in rplan.outs.values())}
+
+                def lateral(lvl, cl):
+                    c = fpk["lateral"][lvl]
+                    coarse, chw = (fplan.lat[lvl + 1], fplan.shapes[lvl + 1]) if lvl < 3 else (None, None)
+                    if cl:
+                        E.fpn_lateral_cl(rplan.stage_plane(lvl), prec, shapes[lvl][1:], c["wp"], c["bias"], coarse, chw, fplan.lat[lvl], prec)
+                    else:
+                        E.fpn_lateral(stages[lvl], c["wp"], c["bias"], coarse, chw, fplan.lat[lvl], prec)
+
+                def to_nchw(lvl):
+                    k, h, w = shapes[lvl]
+                    E.cl_to_nchw(rplan.stage_plane(lvl), stages[lvl], B, h * w, k, prec)
+                runs = {"to_nchw": lambda: [to_nchw(l) for l in (3, 2, 1, 0)],
+                        "lateral_nchw": lambda: [lateral(l, False) for l in (3, 2, 1, 0)],
+                        "lateral_cl": lambda: [lateral(l, True) for l in (3, 2, 1, 0)]}
+                for l in range(4):
+                    runs[f"lateral_nchw_level{l}"] = (lambda l=l: lateral(l, False))
+                    runs[f"lateral_cl_level{l}"] = (lambda l=l: lateral(l, True))
+                t = alternate(runs, reps, warmup)
+
+                def gbytes(lvl, esz):
+                    k, h, w = shapes[lvl]
+                    coarse = B * fplan.shapes[lvl + 1][0] * fplan.shapes[lvl + 1][1] * 256 * 2 if lvl < 3 else 0
+                    return (B * k * h * w * esz + B * h * w * 256 * 2 + coarse + 256 * k * 2) / 1e9
+                for name, esz in (("lateral_nchw", 4), ("lateral_cl", 2)):
+                    per = [gbytes(l, esz) for l in range(4)]
+                    for key, gb in [(name, sum(per))] + [(f"{name}_level{l}", per[l]) for l in range(4)]:
+                        t[key]["gbytes"] = round(gb, 4)
+                        t[key]["gb_per_s"] = round(gb / t[key]["ms"] * 1e3, 1)
+                gb = sum(B * k * h * w * (2 + 4) for k, h, w in shapes) / 1e9
+                t["to_nchw"]["gbytes"], t["to_nchw"]["gb_per_s"] = round(gb, 4), round(gb / t["to_nchw"]["ms"] * 1e3, 1)
+                r["laterals"] = t
+                flush()
+                mg._plans.clear(); fpn._plans.clear()
+                del rplan, fplan, stages
+                torch.cuda.empty_cache()
+
+
 def group_gflop(m):
     """GFLOP per frame of the stem and of each layer: 2 K Cout per output pixel"""
     h, w = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -254,6 +338,7 @@ def main():
     ap.add_argument("--native-out", default=None, help="measure the native plan beside the Python plan, and the two weight loads, instead")
     ap.add_argument("--train-out", default=None, help="measure forward + backward of the trained stages instead")
     ap.add_argument("--train-batches", default="2,4")
+    ap.add_argument("--handoff-out", default=None, help="measure the backbone -> FPN hand-over, NCHW stages beside stage planes, instead")
     ap.add_argument("--fpn-neck-ms", type=float, default=1.07, help="the FPN + neck's time per frame to set the backbone beside")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -264,6 +349,8 @@ def main():
     m = ResNet(50, frozen_stages=1, norm_eval=True)
     m.load_state_dict(resnet_cases.fill(m.state_dict()))
     m.eval().to(dev)
+    if args.handoff_out:
+        return handoff_section(m, dev, [int(b) for b in args.batches.split(",")], args.reps, args.warmup, args.handoff_out)
     if args.native_out:
         return native_section(m, dev, [int(b) for b in args.batches.split(",")], args.reps, args.warmup, args.native_out)
     gf = group_gflop(m)
